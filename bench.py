@@ -5,7 +5,10 @@
 A "step" is one batched RHS sweep: B states of the 10k-species / 50k-reaction synthetic CRN
 (SURVEY.md 8(d), C3/C4), each state with its own rate-constant vector (ensemble of
 temperatures), all inputs resident in HBM before the timed region. `value` = RHS evaluations
-per second over all ranks. The same JSON line carries
+per second over all ranks, `ms_per_step` = wall-clock of one timed step. A plain run sets up, spins the clocks up, warms up,
+times --steps sweeps, writes the last sweep's output with --dump-outputs DIR, and prints the line with `roofline` from the
+timed steps' HIP events. Everything below that takes runs of its own is measured with --full only (a plain run leaves
+`traffic` and `sustained_launch_ms` null). With --full the same JSON line carries
   roofline      - algorithmic bytes of one sweep (M2: 20R + B(8R + 16N)) / HIP-event time of the sweep kernel; `traffic`
                   is MEASURED IN THIS RUN: rank 0 (N = 1) starts two child processes under `rocprofv3 --pmc` (FETCH_SIZE
                   and WRITE_SIZE cannot share a pass on gfx950) that launch the same sweep, before this process touches
@@ -57,6 +60,13 @@ def parse():
     ap.add_argument("--no-crossover", dest="crossover", action="store_false", help="skip the network-size crossover table and the ensemble launch")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 --pmc child runs (traffic = null)")
+    ap.add_argument("--full", action="store_true",
+                    help="run every leg beyond the headline sweep (PMC traffic, sustained sweeps, library-order sweeps, solve_network "
+                         "with its CPU port, replicas, configurations and crossover, CPU baselines, the N > 1 legs); the --no-* "
+                         "options above switch single legs off again. Without it only the headline sweep is set up and timed")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed sweep returned as DIR/*.npy (float64): all of du when it "
+                         "fits in 32 MB, else a fixed, seeded sample of its states")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--replica-worker", type=int, nargs=3, default=None, help=argparse.SUPPRESS)   # threads, chunks, first replica index
     return ap.parse_args()
@@ -284,8 +294,9 @@ def main():
 
     import torch  # device memory, streams, torch.distributed: plumbing only (importing it makes no GPU call)
 
-    traffic, traffic_note = None, "not measured (--no-pmc, the counter-collecting child itself, or N > 1)"
-    if rank == 0 and world == 1 and not args.no_pmc and not args.pmc_child:
+    full = args.full
+    traffic, traffic_note = None, "not measured (a run without --full, --no-pmc, the counter-collecting child itself, or N > 1)"
+    if full and rank == 0 and world == 1 and not args.no_pmc and not args.pmc_child:
         traffic, traffic_note = measure_traffic(args)      # child processes; this process has not touched the GPU yet
 
     # rehearsal knobs (a one-GPU box can run 2 ranks on the same card over gloo): never set by the driver
@@ -372,10 +383,20 @@ def main():
     elapsed = max_over_ranks(elapsed, dist, coll_dev)
     kernel_ms = float(np.mean([a.elapsed_time(b) for a, b in ev]))
 
+    # ---- what the last timed sweep returned (du[B][N], rank 0's): all of it when it fits in 32 MB, else a fixed sample of
+    # states drawn with a fixed seed; the row indices go next to it. Nothing has written d_du since the last timed step.
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        n_rows = min(B, max(1, (32 << 20) // (8 * N)))
+        rows = np.arange(B) if n_rows == B else np.sort(np.random.default_rng(0).choice(B, n_rows, replace=False))
+        du_rows = d_du[torch.as_tensor(rows, device=dev)].cpu().numpy()
+        np.save(os.path.join(args.dump_outputs, "rhs_du.npy"), np.ascontiguousarray(du_rows, dtype=np.float64))
+        np.save(os.path.join(args.dump_outputs, "rhs_du_rows.npy"), rows.astype(np.float64))
+
     # ---- the same sweep back to back for a few seconds (outside the timed region): the rate the chip sustains once its
     # clock management has settled, and enough GPU-resident time for an outside observer to see the device busy
     sustained_ms = None
-    if args.sustain_seconds > 0:
+    if full and args.sustain_seconds > 0:
         n_sus = max(10, int(args.sustain_seconds / (kernel_ms * 1e-3)))
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
@@ -421,7 +442,7 @@ def main():
     # ---- the sweep in the library's own data layout (kin_rhs_tiled_dev): the same C3 states with k written in library
     # order by the rate-table kernel and with NO k at all (rate constants formed inside the sweep from T[b], SURVEY M1'),
     # and the C5 network (50k species / 250k reactions, state too large for LDS: hubs + windows), rank 0 at N = 1
-    if rank == 0 and world == 1 and args.tiled:
+    if full and rank == 0 and world == 1 and args.tiled:
         def tiled_leg(hh, Nn, Rr, Bb, uu, TT):
             lay = hh.lib_layout()
             kl = torch.empty((Bb, lay["k_len"]), dtype=torch.float64, device=dev)
@@ -517,7 +538,7 @@ def main():
 
     # ---- ONE trajectory's RHS with the reactions split over the ranks and an all-reduce of du (N doubles):
     # measured at N > 1 so that the cost of the single-trajectory decomposition is a number, not an argument
-    if world > 1:
+    if full and world > 1:
         from kinetica_jl_amd.distributed import time_rhs_reaction_blocks
         h.set_rates(k1000)
         split = time_rhs_reaction_blocks(h, d_u[0].clone(), dist, reps=200)
@@ -528,7 +549,7 @@ def main():
     # ---- an ensemble of ONE small network sharded by members over the ranks: 64 members per rank (weak scaling), each
     # rank ONE kin_solve_ensemble launch on its GPU, then one row per member (the per-species maxima identify_next_seeds reads) and
     # the return codes all-gathered in member order (RCCL on device tensors). No data-path collective during the solves.
-    if world > 1 and args.solve_chunks > 0:
+    if full and world > 1 and args.solve_chunks > 0:
         def sharded_ensemble_leg():
             from kinetica_jl_amd.distributed import solve_ensemble_sharded
             net_e, Ea_e, A_e = synthetic_crn(300, 1500)
@@ -567,7 +588,7 @@ def main():
             out["ensemble_sharded_by_members"] = leg
 
     # ---- single-state RHS latency (what the integrator sees), rank 0 only
-    if rank == 0:
+    if full and rank == 0:
         u1 = 10.0 ** np.random.default_rng(0).uniform(-12, 0, N)
         h.set_rates(k1000)
         h.rhs(u1)
@@ -599,7 +620,7 @@ def main():
         return capi.KinParams(tspan0=0.0, tspan1=chunk * nch, abstol=1e-10, reltol=1e-8, adaptive_tols=1, update_tols=0,
                               solve_chunks=1, ban_negatives=0, solve_chunkstep=chunk, maxiters=100000, save_interval=-1.0)
 
-    if args.solve_chunks > 0:
+    if full and args.solve_chunks > 0:
         k_rank = h.rates_at(1000.0 + 10.0 * rank)
         # cold wall-clock of ONE solve_network call as an exploration level makes it (explore_network solves every
         # network exactly once, exploration/methods.jl:221): handle creation (network compilation, table upload) +
@@ -713,7 +734,7 @@ def main():
     # ramp (200 rate updates / restarts) against the committed tight-tolerance truth; a 5-chunk solve of the C5 network
     # (50k species). The ramp and the complete-timespan solve need dtmin below the reference's hard-coded eps(.) on this
     # synthetic CRN: kin_params.dtmin = 1e-30, what INTEGRATION.md's shim passes as HIPBDF(dtmin).
-    if rank == 0 and world == 1 and args.configs and args.solve_chunks > 0:
+    if full and rank == 0 and world == 1 and args.configs and args.solve_chunks > 0:
         RAMP_DTMIN = 1e-30
 
         def kpc(t1, chunk, save=-1.0, chunks=1, dtmin=0.0):
@@ -836,7 +857,7 @@ def main():
     # ---- where a GPU pays: 20-chunk static solves over network sizes - GPU warm, GPU cold (handle creation + symbolic analysis
     # + solve, what an exploration level pays), the CPU port on one core; and one LAUNCH that integrates an ensemble of
     # trajectories (kin_solve_ensemble: one workgroup per member, resident on the GPU)
-    if rank == 0 and world == 1 and args.crossover and args.solve_chunks > 0:
+    if full and rank == 0 and world == 1 and args.crossover and args.solve_chunks > 0:
         def crossover():
             rows = []
             for n in (100, 300, 1000, 3000, 10000):
@@ -959,7 +980,7 @@ def main():
         guarded(sn, "ensemble_one_launch", ensemble_launch)
 
     # ---- CPU baseline for the headline metric: oracle RHS, 1 core, bounded sample
-    if rank == 0 and not args.no_cpu and world == 1:
+    if full and rank == 0 and not args.no_cpu and world == 1:
         from oracle import oracle as orc
         on = orc.OracleNetwork.from_flat(net)
         u1 = 10.0 ** np.random.default_rng(0).uniform(-12, 0, N)

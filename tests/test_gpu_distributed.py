@@ -108,7 +108,7 @@ def test_bench_two_ranks_on_one_card_end_to_end():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, BENCH_SINGLE_DEVICE="1", BENCH_BACKEND="gloo")
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--species", "1000", "--reactions", "5000",
-                        "--batch", "256", "--steps", "3", "--warmup", "1", "--solve-chunks", "2", "--no-cpu", "--no-pmc",
+                        "--batch", "256", "--steps", "3", "--warmup", "1", "--full", "--solve-chunks", "2", "--no-cpu", "--no-pmc",
                         "--sustain-seconds", "0", "--replicas", ""], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                        text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
@@ -135,7 +135,7 @@ def test_bench_four_ranks_rehearsal_reports_who_took_part():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, BENCH_SINGLE_DEVICE="1", BENCH_BACKEND="gloo")
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "4", "--species", "1000", "--reactions", "5000",
-                        "--batch", "128", "--steps", "3", "--warmup", "1", "--solve-chunks", "2", "--no-cpu", "--no-pmc",
+                        "--batch", "128", "--steps", "3", "--warmup", "1", "--full", "--solve-chunks", "2", "--no-cpu", "--no-pmc",
                         "--sustain-seconds", "0", "--spinup-seconds", "0", "--replicas", ""], env=env, stdout=subprocess.PIPE,
                        stderr=subprocess.PIPE, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
@@ -159,7 +159,7 @@ def test_bench_five_ranks_rehearsal():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, BENCH_SINGLE_DEVICE="1", BENCH_BACKEND="gloo")
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "5", "--species", "1000", "--reactions", "5000",
-                        "--batch", "64", "--steps", "3", "--warmup", "1", "--solve-chunks", "2", "--no-cpu", "--no-pmc", "--no-tiled",
+                        "--batch", "64", "--steps", "3", "--warmup", "1", "--full", "--solve-chunks", "2", "--no-cpu", "--no-pmc", "--no-tiled",
                         "--sustain-seconds", "0", "--spinup-seconds", "0", "--replicas", ""], env=env, stdout=subprocess.PIPE,
                        stderr=subprocess.PIPE, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]

@@ -7,7 +7,7 @@ TAG=${1:-r01}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/prof_$TAG
 rm -rf "$OUT" && mkdir -p "$OUT"
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -- python3 bench.py --solve-chunks 20 --cpu-solve-chunks 0 --no-pmc --no-tiled --no-configs --no-crossover --replicas "" --sustain-seconds 0.5 > "$OUT/bench_stats.log" 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -- python3 bench.py --full --solve-chunks 20 --cpu-solve-chunks 0 --no-pmc --no-tiled --no-configs --no-crossover --replicas "" --sustain-seconds 0.5 > "$OUT/bench_stats.log" 2>&1
 # the same command without the spin-up and the sustained leg: the profiler's average then covers the warm-up + timed launches only (cold clocks)
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats_timed" -- python3 bench.py --solve-chunks 0 --no-cpu --no-pmc --no-tiled --no-configs --no-crossover --sustain-seconds 0 --spinup-seconds 0 > "$OUT/bench_stats_timed.log" 2>&1
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/fetch" -- python3 bench.py --steps 5 --solve-chunks 0 --no-cpu --no-pmc --no-tiled --no-configs --no-crossover --sustain-seconds 0 --spinup-seconds 0 > "$OUT/bench_fetch.log" 2>&1

@@ -265,6 +265,23 @@ int kin_solve_explicit(kin_network* h, const kin_params* params, const double* u
  * (src/utils.jl:135-139). Chunking / save grid / retry semantics as kin_solve; no restarts at all. */
 int kin_solve_continuous(kin_network* h, const kin_params* params, const double* u0, const double* t_nodes,
                          const double* T_nodes, int64_t n_nodes, int64_t* n_saved, int32_t* retcode, kin_stats* stats);
+/* An ENSEMBLE of K trajectories under continuous rate updates, one temperature profile per member (reference: a
+ * VariableODESolve whose ConditionSet has no ts_update, methods.jl:363-653; the obvious sweep is a set of heating rates or
+ * start temperatures). Member m's rates are re-evaluated at T(t) of every step attempt, T(t) the linear interpolation of its
+ * profile (t_nodes, T_nodes)[node_ptr[m] .. node_ptr[m + 1]) in global time (src/utils.jl:135-139); node counts may differ.
+ *   - a network the resident kernel takes (as in kin_solve_ensemble): ONE launch, one workgroup per member, the profiles
+ *     uploaded once; a member's result is bit-identical to a K = 1 call with its inputs and equals its kin_solve_continuous
+ *     within the step-sequence tolerance;
+ *   - larger networks: kin_solve_continuous calls on host threads (KIN_ENSEMBLE_THREADS; beyond it a thread takes several
+ *     members), bit-identical to kin_solve_continuous on the member's inputs. There is no lockstep form:
+ *     KIN_ENSEMBLE_ROUTE=lockstep returns KIN_ERR_UNSUPPORTED.
+ * Per member as kin_solve_continuous: >= 2 nodes, non-decreasing t (else KIN_ERR_INVALID_ARG), Arrhenius parameters set on
+ * the handle (else KIN_ERR_STATE). u0, the save-grid requirement, the outputs, the size query and the return value are those
+ * of kin_solve_ensemble. */
+int kin_solve_ensemble_continuous(kin_network* h, const kin_params* params, int64_t K, const double* u0,
+                                  const int64_t* node_ptr, const double* t_nodes, const double* T_nodes,
+                                  int64_t* n_rows, double* out_t, double* out_u, int64_t* n_saved,
+                                  int32_t* retcodes, kin_stats* stats);
 /* N1: return_integrator=true (methods.jl:105-106, 175-178, 242-246, 706-709): `init(oprob, solver; kwargs...)`
  * without solve!. The integrator spans the whole tspan (solve_chunks = 0) or the first chunk
  * [0, solve_chunkstep] (solve_chunks = 1, what the reference hands back); tstops / T_stops / k_table as
@@ -323,8 +340,9 @@ const char* kin_version(void);
 /* Layout version of this header's structs and argument lists. A binding compares it (and, if it wants certainty, the
  * struct sizes) with the values it was written against before the first call: kin_params / kin_stats have grown between
  * versions (1: round 1; 2: + dtmin and the LU-cache counters; 3: + the library-order sweep entry points; 4: + kin_solve_ensemble,
- * kin_lu_analyze_host - structs unchanged; 5: + kin_rhs_batched_klib_dev - structs unchanged). */
-#define KIN_ABI_VERSION 5
+ * kin_lu_analyze_host - structs unchanged; 5: + kin_rhs_batched_klib_dev - structs unchanged; 6: + kin_solve_ensemble_continuous -
+ * structs unchanged). */
+#define KIN_ABI_VERSION 6
 int kin_abi_version(void);
 int64_t kin_struct_size(int which); /* 0: sizeof(kin_params), 1: sizeof(kin_stats), else -1 */
 

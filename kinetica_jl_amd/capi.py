@@ -29,9 +29,9 @@ SYMBOLS = [
     "kin_solution_max_dev", "kin_rate_table_dev", "kin_rhs_block_dev",
     "kin_lib_layout", "kin_lib_layout_host", "kin_states_to_lib_dev", "kin_states_from_lib_dev", "kin_rates_to_lib_dev", "kin_rate_table_lib_dev",
     "kin_rhs_tiled_dev", "kin_rhs_batched_T_dev", "kin_rhs_batched_klib_dev", "kin_abi_version", "kin_struct_size",
-    "kin_solve_ensemble", "kin_lu_analyze_host",
+    "kin_solve_ensemble", "kin_lu_analyze_host", "kin_solve_ensemble_continuous",
 ]
-ABI_VERSION = 5   # include/kinetica_hip.h: KIN_ABI_VERSION this binding was written against
+ABI_VERSION = 6   # include/kinetica_hip.h: KIN_ABI_VERSION this binding was written against
 
 
 class KinParams(ctypes.Structure):
@@ -108,6 +108,8 @@ def lib():
                                 POINTER(KinStats)]
         L.kin_solve_continuous.argtypes = [c_void_p, POINTER(KinParams), PD, PD, PD, c_int64, P64, POINTER(c_int32),
                                            POINTER(KinStats)]
+        L.kin_solve_ensemble_continuous.argtypes = [c_void_p, POINTER(KinParams), c_int64, PD, P64, PD, PD, P64, PD, PD, P64,
+                                                    POINTER(c_int32), POINTER(KinStats)]
         L.kin_solve_ensemble.argtypes = [c_void_p, POINTER(KinParams), c_int64, PD, PD, PD, PD, PD, PD, c_int64, P64, PD, PD, P64,
                                          POINTER(c_int32), POINTER(KinStats)]
         L.kin_integrator_init.argtypes = [c_void_p, POINTER(KinParams), PD, PD, PD, PD, c_int64]
@@ -397,6 +399,32 @@ class HipNetwork:
         stats = (KinStats * K)()
         self._chk(fn(self._h, ctypes.byref(params), K, _pd(u0), _pd(k), _pd(T), _pd(tstops), _pd(T_stops), _pd(k_table), n_stops,
                      ctypes.byref(rows), _pd(t), _pd(u), ns.ctypes.data_as(POINTER(c_int64)), rcs.ctypes.data_as(POINTER(c_int32)), stats))
+        return t, u, ns, rcs, [s_.as_dict() for s_ in stats]
+
+    def solve_ensemble_continuous(self, params: KinParams, u0, nodes):
+        """kin_solve_ensemble_continuous: K trajectories under continuous rate updates, member m's rates at T(t) of its own
+        profile. u0[K][N]; nodes: K pairs (t_nodes, T_nodes) in global time (node counts may differ).
+        Returns what solve_ensemble returns: (t[M], u[K][M][N], n_saved[K], retcodes[K], [stats dict] * K)."""
+        u0 = np.ascontiguousarray(np.atleast_2d(_f64(u0)))
+        K = u0.shape[0]
+        assert u0.shape == (K, self.n) and len(nodes) == K
+        tn = [_f64(a).ravel() for a, _ in nodes]
+        Tn = [_f64(b).ravel() for _, b in nodes]
+        assert all(len(a) == len(b) for a, b in zip(tn, Tn))
+        ptr = np.zeros(K + 1, np.int64)
+        ptr[1:] = np.cumsum([len(a) for a in tn])
+        t_all = np.ascontiguousarray(np.concatenate(tn))
+        T_all = np.ascontiguousarray(np.concatenate(Tn))
+        P64_ = lambda a: a.ctypes.data_as(POINTER(c_int64))
+        rows = c_int64(0)
+        fn = lib().kin_solve_ensemble_continuous
+        self._chk(fn(self._h, ctypes.byref(params), K, _pd(u0), P64_(ptr), _pd(t_all), _pd(T_all), ctypes.byref(rows), None, None, None,
+                     None, None))
+        M = rows.value
+        t = np.empty(M); u = np.empty((K, M, self.n)); ns = np.zeros(K, np.int64); rcs = np.zeros(K, np.int32)
+        stats = (KinStats * K)()
+        self._chk(fn(self._h, ctypes.byref(params), K, _pd(u0), P64_(ptr), _pd(t_all), _pd(T_all), ctypes.byref(rows), _pd(t), _pd(u),
+                     P64_(ns), rcs.ctypes.data_as(POINTER(c_int32)), stats))
         return t, u, ns, rcs, [s_.as_dict() for s_ in stats]
 
     def solve_continuous(self, params: KinParams, u0, t_nodes, T_nodes):

@@ -381,9 +381,12 @@ int replica_threads_max() {
 // Every member is, bit for bit, what kin_solve gives for its inputs. A chain of ~14 small dependent launches per step keeps one
 // trajectory at 6.7 solves/s (first 2 chunks of the 10k-species network) and K of them at 11 / 17 / 17 / 16 for K = 2 / 4 / 8 / 12 - the
 // dispatch rate of the chip's queues; the lockstep rounds of ensemble.cpp only overtake that from K = 16 on.
+// node_ptr != NULL: continuous rate updates, member m is the kin_solve_continuous of its own profile
+// (t_nodes, T_nodes)[node_ptr[m] .. node_ptr[m + 1]).
 void replica_ensemble(kin_network* h, const kin_params& p, int64_t K, const double* u0, const double* k, const double* T,
                       const double* tstops, const double* T_stops, const double* k_table, int64_t n_stops, int64_t* n_rows,
-                      double* out_t, double* out_u, int64_t* n_saved, int32_t* retcodes, kin_stats* stats) {
+                      double* out_t, double* out_u, int64_t* n_saved, int32_t* retcodes, kin_stats* stats,
+                      const int64_t* node_ptr = nullptr, const double* t_nodes = nullptr, const double* T_nodes = nullptr) {
   const int64_t N = h->host.N, R = h->host.R;
   const int64_t cap = make_res_grid(p).cap;
   if (n_rows) *n_rows = cap;
@@ -433,7 +436,7 @@ void replica_ensemble(kin_network* h, const kin_params& p, int64_t K, const doub
           c->has_arrhenius = true; c->has_kmax = h->has_kmax; c->k_max = h->k_max; c->t_mult = h->t_mult;
         }
         for (int64_t m = t; m < K; m += Tn) {
-          if (n_stops == 0) {
+          if (n_stops == 0 && !node_ptr) {
             if (k) KIN_HIP(hipMemcpyAsync(c->k.p, k + m * R, (size_t)R * sizeof(double), hipMemcpyHostToDevice, s));
             else if (T) launch_arrhenius(R, c->Ea.p, c->A.p, c->has_kmax, c->k_max, c->t_mult, T[m], c->k.p, s);
             else KIN_HIP(hipMemcpyAsync(c->k.p, h->k.p, (size_t)R * sizeof(double), hipMemcpyDeviceToDevice, s));
@@ -441,7 +444,9 @@ void replica_ensemble(kin_network* h, const kin_params& p, int64_t K, const doub
           }
           KIN_HIP(hipStreamSynchronize(s));
           kin_stats st{};
-          const int rc = solve_entry(c, p, u0 + m * N, tstops, T_stops, k_table, n_stops, &st);
+          const int rc = node_ptr ? solve_entry(c, p, u0 + m * N, nullptr, nullptr, nullptr, 0, &st, t_nodes + node_ptr[m],
+                                                T_nodes + node_ptr[m], node_ptr[m + 1] - node_ptr[m])
+                                  : solve_entry(c, p, u0 + m * N, tstops, T_stops, k_table, n_stops, &st);
           if (retcodes) retcodes[m] = rc;
           if (stats) stats[m] = st;
           const int64_t ns = std::min<int64_t>(c->n_saved, cap);
@@ -499,6 +504,37 @@ int kin_solve_ensemble(kin_network* h, const kin_params* params, int64_t K, cons
       replica_ensemble(h, *params, K, u0, k, T, tstops, T_stops, k_table, n_stops, n_rows, out_t, out_u, n_saved, retcodes, stats);
     else
       batched_ensemble(h, *params, K, u0, k, T, tstops, T_stops, k_table, n_stops, n_rows, out_t, out_u, n_saved, retcodes, stats);
+  }
+  KIN_CATCH(h)
+}
+
+int kin_solve_ensemble_continuous(kin_network* h, const kin_params* params, int64_t K, const double* u0,
+                                  const int64_t* node_ptr, const double* t_nodes, const double* T_nodes,
+                                  int64_t* n_rows, double* out_t, double* out_u, int64_t* n_saved,
+                                  int32_t* retcodes, kin_stats* stats) {
+  if (!h) return KIN_ERR_INVALID_ARG;
+  KIN_TRY(h)
+  require(params && u0 && K >= 1, ERR_INVALID_ARG, "params / u0 is null, or K < 1");
+  require(node_ptr && t_nodes && T_nodes, ERR_INVALID_ARG, "node_ptr / t_nodes / T_nodes is null");
+  require(res_has_grid(*params), ERR_INVALID_ARG, "an ensemble solve needs a save grid (solve_chunks or save_interval)");
+  for (int64_t m = 0; m < K; m++) {
+    // every member needs a profile of its own: an empty one would leave the controller's T(t) nothing to read
+    require(node_ptr[m] >= 0 && node_ptr[m + 1] - node_ptr[m] >= 2, ERR_INVALID_ARG, "need >= 2 (t, T) nodes per member");
+    validate_solve(h, *params, nullptr, nullptr, nullptr, 0, t_nodes + node_ptr[m], T_nodes + node_ptr[m], node_ptr[m + 1] - node_ptr[m], false);
+  }
+  if (n_rows && !out_u && !n_saved) { *n_rows = make_res_grid(*params).cap; }   // size query
+  else {
+    // the lockstep form has no continuous rate updates; networks the resident kernel takes use it, larger ones (or
+    // KIN_ENSEMBLE_ROUTE=threads) are kin_solve_continuous calls on host threads
+    const char* route = getenv("KIN_ENSEMBLE_ROUTE");
+    require(!(route && !strcmp(route, "lockstep")), ERR_UNSUPPORTED, "the lockstep ensemble has no continuous rate updates");
+    const bool threads = route && !strcmp(route, "threads");
+    if (!threads && resident_ensemble_route(h, K))
+      resident_ensemble(h, *params, K, u0, nullptr, nullptr, nullptr, nullptr, nullptr, 0, n_rows, out_t, out_u, n_saved, retcodes, stats,
+                        node_ptr, t_nodes, T_nodes);
+    else
+      replica_ensemble(h, *params, K, u0, nullptr, nullptr, nullptr, nullptr, nullptr, 0, n_rows, out_t, out_u, n_saved, retcodes, stats,
+                       node_ptr, t_nodes, T_nodes);
   }
   KIN_CATCH(h)
 }

@@ -29,7 +29,7 @@ struct ResidentSolver {
   // workspaces (grown on demand)
   int K_cap = 0, n_slots = 0;
   size_t per_traj = 0;
-  DevBuf<double> work, Wbuf, jdbuf, gjbuf, d_u0, d_sol, d_solt, d_save, d_tstops, d_Tstops;
+  DevBuf<double> work, Wbuf, jdbuf, gjbuf, d_u0, d_sol, d_solt, d_save, d_tstops, d_Tstops, d_tnodes, d_Tnodes;
   DevBuf<ResTrajDev> d_traj;
   DevBuf<ResResult> d_res;
   DevBuf<ResParams> d_par;
@@ -162,8 +162,9 @@ void stats_from(const ResidentSolver& RS, const ResResult& r, int slots, double 
 }
 
 // common part: parameters, tables of the variable conditions, launch, results
+// continuous: rate_mode 3, every member's profile already in its ResTrajDev
 void run_resident(kin_network* h, ResidentSolver& RS, const kin_params& p, const ResGrid& g, int K, int slots, const double* tstops,
-                  const double* T_stops, const double* k_table, int64_t n_stops, std::vector<ResResult>& res) {
+                  const double* T_stops, const double* k_table, int64_t n_stops, std::vector<ResResult>& res, bool continuous = false) {
   hipStream_t s = h->stream;
   const int64_t R = h->host.R;
   ResParams P{};
@@ -173,7 +174,7 @@ void run_resident(kin_network* h, ResidentSolver& RS, const kin_params& p, const
   RS.d_save.upload(g.save_local, s);
   P.save_local = RS.d_save.p;
   P.n_stops = (int32_t)n_stops;
-  P.rate_mode = n_stops > 0 ? (k_table ? 1 : 2) : 0;
+  P.rate_mode = continuous ? 3 : (n_stops > 0 ? (k_table ? 1 : 2) : 0);
   if (n_stops > 0) {
     RS.d_tstops.upload(tstops, (size_t)n_stops, s);
     P.tstops = RS.d_tstops.p;
@@ -277,11 +278,13 @@ int resident_solve(kin_network* h, const kin_params& p, const double* u0, const 
 
 // K independent trajectories of one network in ONE launch (one workgroup each): u0[K][N]; rate constants k[K][R], or
 // temperatures T[K] (Arrhenius on the device), or the handle's current rates for all; optional discrete rate updates shared by
-// the ensemble (tstops + T_stops or k_table). Outputs: out_t[cap], out_u[K][cap][N] (cap = rows of the save grid),
-// n_saved[K], retcodes[K], stats[K].
+// the ensemble (tstops + T_stops or k_table); or, with node_ptr, continuous rate updates: member m's rates are formed at
+// T(t) of every step attempt from its own profile (t_nodes, T_nodes)[node_ptr[m] .. node_ptr[m + 1]), uploaded once.
+// Outputs: out_t[cap], out_u[K][cap][N] (cap = rows of the save grid), n_saved[K], retcodes[K], stats[K].
 void resident_ensemble(kin_network* h, const kin_params& p, int64_t K, const double* u0, const double* k, const double* T,
                        const double* tstops, const double* T_stops, const double* k_table, int64_t n_stops, int64_t* out_rows,
-                       double* out_t, double* out_u, int64_t* n_saved, int32_t* retcodes, kin_stats* stats) {
+                       double* out_t, double* out_u, int64_t* n_saved, int32_t* retcodes, kin_stats* stats, const int64_t* node_ptr,
+                       const double* t_nodes, const double* T_nodes) {
   auto wall0 = std::chrono::steady_clock::now();
   ResidentSolver& RS = *get_resident(h);
   if (!RS.ok) throw KinError(ERR_UNSUPPORTED, "network does not fit the resident integrator: " + RS.why);
@@ -292,7 +295,17 @@ void resident_ensemble(kin_network* h, const kin_params& p, int64_t K, const dou
   const int slots = clamp_slots(RS, (int)K);
   RS.ensure((int)K, slots, g.cap, true);
   RS.d_u0.upload(u0, (size_t)K * N, s);
-  if (n_stops == 0) {
+  const bool continuous = node_ptr != nullptr;
+  if (continuous) {
+    const size_t n_all = (size_t)(node_ptr[K] - node_ptr[0]);
+    RS.d_tnodes.upload(t_nodes + node_ptr[0], n_all, s);
+    RS.d_Tnodes.upload(T_nodes + node_ptr[0], n_all, s);
+    for (int64_t t = 0; t < K; t++) {
+      RS.h_traj[t].t_nodes = RS.d_tnodes.p + (node_ptr[t] - node_ptr[0]);
+      RS.h_traj[t].T_nodes = RS.d_Tnodes.p + (node_ptr[t] - node_ptr[0]);
+      RS.h_traj[t].n_nodes = node_ptr[t + 1] - node_ptr[t];
+    }
+  } else if (n_stops == 0) {
     for (int64_t t = 0; t < K; t++) {
       if (k) KIN_HIP(hipMemcpyAsync(RS.h_traj[t].k, k + t * R, (size_t)R * sizeof(double), hipMemcpyHostToDevice, s));
       else if (T) launch_arrhenius(R, h->Ea.p, h->A.p, h->has_kmax, h->k_max, h->t_mult, T[t], RS.h_traj[t].k, s);
@@ -300,7 +313,7 @@ void resident_ensemble(kin_network* h, const kin_params& p, int64_t K, const dou
     }
   }
   std::vector<ResResult> res;
-  run_resident(h, RS, p, g, (int)K, slots, tstops, T_stops, k_table, n_stops, res);
+  run_resident(h, RS, p, g, (int)K, slots, tstops, T_stops, k_table, n_stops, res, continuous);
   const double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - wall0).count();
   if (out_u) RS.d_sol.download(out_u, (size_t)K * (size_t)g.cap * N, s);
   if (out_t) {   // the save times are the same for every member: taken from the one that got furthest

@@ -336,6 +336,18 @@ RES_PHASE void ph_apply_rates(long long stop) {
   __syncthreads();
 }
 
+// rate_mode 3: the rate constants at temperature T (the Arrhenius loop of ph_apply_rates' mode 2), before every step attempt
+RES_PHASE void ph_apply_T(double T) {
+  const int R = uni(g_cx.R);
+  gd_t* k = glob(g_cx.T.k);
+  const ResNetDev* net = g_cx.net;
+  const double RT = 8.314462618 * T;
+  gcd_t* Ea = glob(net->Ea); gcd_t* A = glob(net->A);
+  const int has_kmax = g_cx.has_kmax; const double k_max = g_cx.k_max, t_mult = g_cx.t_mult;
+  for (int r = threadIdx.x; r < R; r += RES_WG) k[r] = arrhenius_one(Ea[r], A[r], RT, has_kmax, k_max, t_mult);
+  __syncthreads();
+}
+
 // mass-action rates of state u into the LDS rate array (make_rs, solve_utils.jl:318-334); no barrier inside
 template <class UP>
 __device__ __forceinline__ void rates_into(UP u) {
@@ -879,7 +891,7 @@ RES_PHASE ResAttempt ph_corrector() {
 // table of the LU cache in its registers
 // ------------------------------------------------------------------------------------------------------------------
 enum CmdOp : int { OP_EXIT = 0, OP_VEC, OP_SAVE_Y, OP_APPLY_RATES, OP_RHS, OP_JAC, OP_NORMS, OP_INIT_D, OP_PREDICT, OP_CHANGE_D, OP_ACCEPT,
-                   OP_INTERP, OP_DRIFT, OP_FACTOR, OP_CORRECTOR };
+                   OP_INTERP, OP_DRIFT, OP_FACTOR, OP_CORRECTOR, OP_APPLY_T };
 struct DevBackend {
   __device__ int lane() const { return threadIdx.x & 63; }
   __device__ int n_species() const { return g_cx.N; }
@@ -903,10 +915,12 @@ struct DevBackend {
     if (reset) { g_sl.c_fact[lane()] = 0.0; g_sl.last_use[lane()] = 0; g_sl.crate[lane()] = 1.0; g_sl.crate_step[lane()] = 0; g_sl.crate_restart[lane()] = -1;
                  g_sl.jac_stamp[lane()] = 0; g_sl.step_stamp[lane()] = 0; }
   }
-  // slot whose c_fact is closest (in ratio) to c and within the band, lowest index on ties; -1: none (Solver::nearest_slot)
-  __device__ int nearest_slot(double c, double band, long long n_restarts, long long max_age) const {
+  // slot whose c_fact is closest (in ratio) to c and within the band, lowest index on ties; -1: none (Solver::nearest_slot).
+  // step_age >= 0 (continuous rates): only slots whose Jacobian is at most step_age accepted steps old
+  __device__ int nearest_slot(double c, double band, long long n_restarts, long long max_age, long long n_steps = 0, long long step_age = -1) const {
     const double cf = g_sl.c_fact[lane()];
-    const bool ok = lane() < g_cx.n_slots && g_sl.valid[lane()] && n_restarts - g_sl.jac_stamp[lane()] <= max_age && fabs(c / cf - 1.0) <= band;
+    const bool ok = lane() < g_cx.n_slots && g_sl.valid[lane()] && n_restarts - g_sl.jac_stamp[lane()] <= max_age && fabs(c / cf - 1.0) <= band &&
+                    (step_age < 0 || n_steps - g_sl.step_stamp[lane()] <= step_age);
     double r = ok ? fabs(log(c / cf)) : 1e300;
     if (!(r < 1e300)) r = 1e300;
     int idx = lane();
@@ -964,6 +978,7 @@ struct DevBackend {
   __device__ void save_y(long long row, double time) { post(OP_SAVE_Y, 0, 0, 0, row, time); ph_save_y(row, time); }
   __device__ void set_time(long long row, double time) { if (threadIdx.x == 0) glob(g_cx.T.sol_t)[row] = time; }
   __device__ void apply_rates(long long stop) { post(OP_APPLY_RATES, 0, 0, 0, stop); ph_apply_rates(stop); }
+  __device__ void apply_T(double T) { post(OP_APPLY_T, 0, 0, 0, 0, T); ph_apply_T(T); }
   __device__ void rhs_y_to_f0() { post(OP_RHS, RO_Y_TO_F0); ph_rhs(RO_Y_TO_F0); }
   __device__ void rhs_ytmp_to_f1() { post(OP_RHS, RO_YTMP_TO_F1); ph_rhs(RO_YTMP_TO_F1); }
   __device__ void rhs_ytmp_to_f0() { post(OP_RHS, RO_YTMP_TO_F0); ph_rhs(RO_YTMP_TO_F0); }
@@ -1023,6 +1038,7 @@ __device__ void worker_loop() {
       case OP_DRIFT: ph_drift(); break;
       case OP_FACTOR: (void)ph_factor(i0, d0, i1 != 0); break;
       case OP_CORRECTOR: (void)ph_corrector(); break;
+      case OP_APPLY_T: ph_apply_T(d0); break;
       default: break;
     }
   }
@@ -1055,6 +1071,7 @@ __global__ __launch_bounds__(RES_WG) __attribute__((amdgpu_waves_per_eu(RES_WAVE
     const ResNetDev& n = *net_p;
     g_par = *par_p;
     g_cx.T = traj[blockIdx.x];
+    if (g_par.rate_mode == 3) { g_par.t_nodes = g_cx.T.t_nodes; g_par.T_nodes = g_cx.T.T_nodes; g_par.n_nodes = g_cx.T.n_nodes; }   // this member's profile
     g_cx.net = net_p;
     g_cx.plan[PL_RHS] = n.rhs_plan; g_cx.plan[PL_JAC] = n.jac_plan; g_cx.plan[PL_RESID] = n.resid_plan;
     g_cx.plan[PL_LZ] = n.lz_build; g_cx.plan[PL_NVU] = n.nvu_build; g_cx.plan[PL_STAGEA] = n.stageA; g_cx.plan[PL_STAGEC] = n.stageC;

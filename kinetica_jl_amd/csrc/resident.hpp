@@ -37,6 +37,8 @@ struct ResTrajDev {
   double* jd;      // n_slots copies of diag(J) (drift guard of the LU cache)
   double *sol, *sol_t;
   ResResult* result;
+  const double *t_nodes, *T_nodes;   // rate_mode 3: this member's temperature profile (ResParams::t_nodes ...)
+  int64_t n_nodes;
 };
 
 // enqueues the solve of K trajectories (grid = K workgroups of RES_WG = 512 threads)

@@ -53,7 +53,8 @@ struct ResParams {
   int64_t maxiters, n_chunks;
   int32_t L;                       // points of the per-chunk (or whole-span) save grid
   const double* save_local;        // L local save times (solver.cpp: save_local)
-  int32_t n_stops, rate_mode;      // rate_mode 0: static k; 1: k_table[n_stops][R]; 2: Arrhenius at T_stops[n_stops]
+  int32_t n_stops, rate_mode;      // rate_mode 0: static k; 1: k_table[n_stops][R]; 2: Arrhenius at T_stops[n_stops];
+                                   // 3: Arrhenius at T(t) of every step attempt (continuous, nodes below)
   const double* tstops;
   // integrator settings (the same defaults and environment switches as solver.cpp)
   double lu_band, reuse_rate_max, crate_dy_max, lu_drift_max, newton_frac;
@@ -61,7 +62,19 @@ struct ResParams {
   int32_t n_slots, carry_rate;
   int64_t sol_cap;                 // rows of the solution buffer
   int32_t profile, pad0;           // device: fill ResResult::prof (KIN_RESIDENT_PROFILE)
+  // rate_mode 3: T(t) = linear interpolation of (t_nodes, T_nodes)[n_nodes] in global time (the device kernel's prologue sets
+  // them per member from ResTrajDev)
+  const double *t_nodes, *T_nodes;
+  int64_t n_nodes;
 };
+
+// The continuous rate mode needs a backend operation the other modes do not: apply_T(T), the rate constants at one
+// temperature. Backends without it (the CPU replay of tests/native/resident_host.cpp) compile as before and never run mode 3.
+template <class B, class = void> struct ResHasApplyT { static constexpr bool value = false; };
+template <class B> struct ResHasApplyT<B, decltype((void)static_cast<B*>(nullptr)->apply_T(0.0))> { static constexpr bool value = true; };
+// continuous rate updates: the Jacobian behind a reused LU-cache slot is at most this many accepted steps old (CVODE's bound;
+// solver.cpp: Solver::nearest_slot, oracle/bdf.py: _nearest_slot)
+constexpr int64_t RES_CONT_JAC_AGE = 50;
 
 struct ResStats {
   int64_t n_steps, n_rejected, n_rhs, n_jac, n_factor, n_linsolve, n_newton_fail, n_chunks, n_restarts, n_retries,
@@ -150,6 +163,7 @@ struct ResidentBdf {
        first_selection = false;   // the next step-size selection is the first since a (re)initialisation: growth cap 1e4 (CVODE's ETAMX1), 10 afterwards
   int64_t steps_since_jac = 0, jac_stamp_now = 0, use_clock = 0, iters_left = 0;
   double err_m = 0, err_p = 0, err_o = 0, safety_o = 0.9;
+  double seg_origin = 0;   // global time of the current segment's local time 0 (rate_mode 3)
   ResStats st;
 
   KIN_HD ResidentBdf(B& bb, const ResParams& pp) : b(bb), P(pp) {
@@ -195,6 +209,42 @@ struct ResidentBdf {
         RU[a][q2] = v;
       }
     b.change_D(ord, RU);
+  }
+
+  KIN_HD bool continuous() const { return ResHasApplyT<B>::value && P.rate_mode == 3; }
+
+  // rate_mode 3: the temperature at global time tg - the arithmetic of solver.cpp's T_of, so that this controller and the
+  // host-driven integrator form their rates at the same temperatures bit for bit: clamped to the first / last node, else the
+  // linear interpolation inside [t[i-1], t[i]) with i = upper_bound(t, tg). Every thread runs it on the same scalars.
+  KIN_HD double T_of(double tg) const {
+#pragma clang fp contract(off)
+    const double* tn = P.t_nodes;
+    const double* Tn = P.T_nodes;
+    const int64_t n = P.n_nodes;
+    if (tg <= tn[0]) return Tn[0];
+    if (tg >= tn[n - 1]) return Tn[n - 1];
+    int64_t lo = 0, hi = n;   // first node with t > tg (std::upper_bound)
+    while (lo < hi) {
+      const int64_t mid = lo + (hi - lo) / 2;
+      if (tg < tn[mid]) hi = mid; else lo = mid + 1;
+    }
+    const int64_t i = lo;
+    const double dt = tn[i] - tn[i - 1];
+    const double th = dt > 0 ? (tg - tn[i - 1]) / dt : 1.0;
+    return (1.0 - th) * Tn[i - 1] + th * Tn[i];
+  }
+  // rate_mode 3: the rate constants at the conditions of segment-local time tau (Solver::pre_attempt, bdf.py's hook)
+  KIN_HD void rates_at(double tau) {
+    if constexpr (ResHasApplyT<B>::value) b.apply_T(T_of(seg_origin + tau));
+  }
+  // LU-cache lookup; under continuous rate updates only slots whose Jacobian is at most RES_CONT_JAC_AGE accepted steps old
+  KIN_HD int nearest_slot(double c, double band) {
+    if constexpr (ResHasApplyT<B>::value) {
+      const bool cont = continuous();
+      return b.nearest_slot(c, band, st.n_restarts, P.lu_max_age, cont ? st.n_steps : 0, cont ? RES_CONT_JAC_AGE : -1);
+    } else {
+      return b.nearest_slot(c, band, st.n_restarts, P.lu_max_age);
+    }
   }
 
   KIN_HD void eval_jac() { b.eval_jac_y(); st.n_jac++; lu_valid = false; steps_since_jac = 0; jac_stamp_now = st.n_restarts; }
@@ -330,12 +380,13 @@ struct ResidentBdf {
       const double hh = t_new - t;
       h_abs = fabs(hh);
       const double c = hh / alpha[order];
+      if (continuous()) rates_at(t_new);
       bool converged = false;
       if (force_jac_refresh) { predict(); eval_jac(); jac_current = true; force_jac_refresh = false; }
       bool fresh = false, bad = false;
       const double band = cache_suspended ? 0.0 : P.lu_band;
       if (band > 0.0) {
-        const int hit = b.nearest_slot(c, band, st.n_restarts, P.lu_max_age);
+        const int hit = nearest_slot(c, band);
         if (hit >= 0 && !force_fresh_lu) { cur_slot = hit; b.slot_touch(hit, ++use_clock); st.n_lu_reused++; }
         else {
           if (force_fresh_lu && !jac_current && steps_since_jac > 20) { predict(); eval_jac(); jac_current = true; }
@@ -513,7 +564,10 @@ struct ResidentBdf {
           }
           if (seg_end > t_seg) {
             const double seg_len = seg_end - t_seg;
-            if (P.solve_chunks == 2 && have_history && !rates_changed) resume();
+            seg_origin = t_seg + shift;
+            if (continuous()) rates_at(0.0);   // rates at the segment start for f0 / J of the restart
+            // (continuous rates: every chunk start re-initialises, solve_chunks == 2 is 1 - solver.cpp does the same)
+            if (P.solve_chunks == 2 && have_history && !rates_changed && !continuous()) resume();
             else if (!restart(seg_len)) { retcode = RES_RET_UNSTABLE; failed = true; break; }
             have_history = true;
             rates_changed = false;

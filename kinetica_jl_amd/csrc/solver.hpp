@@ -27,7 +27,10 @@ int resident_solve(kin_network* h, const kin_params& p, const double* u0, const 
                    const double* k_table, int64_t n_stops, kin_stats* stats);
 void resident_ensemble(kin_network* h, const kin_params& p, int64_t K, const double* u0, const double* k, const double* T,
                        const double* tstops, const double* T_stops, const double* k_table, int64_t n_stops, int64_t* out_rows,
-                       double* out_t, double* out_u, int64_t* n_saved, int32_t* retcodes, kin_stats* stats);
+                       double* out_t, double* out_u, int64_t* n_saved, int32_t* retcodes, kin_stats* stats,
+                       const int64_t* node_ptr = nullptr, const double* t_nodes = nullptr, const double* T_nodes = nullptr);
+// (node_ptr: continuous rate updates, member m's temperature profile (t_nodes, T_nodes)[node_ptr[m] .. node_ptr[m + 1]) -
+// kin_solve_ensemble_continuous)
 // does the network fit the resident kernel (its state, rates and solve vectors in one compute unit's LDS)?
 bool resident_fits(kin_network* h);
 // ... and does an ensemble of K members take the one-launch form (resident.cpp: not few members of a network at the kernel's upper end)?

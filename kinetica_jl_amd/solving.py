@@ -10,6 +10,7 @@ shim in INTEGRATION.md; this module is the runnable twin used by the parity test
 from __future__ import annotations
 
 import copy
+import dataclasses
 import math
 from dataclasses import dataclass, field
 from typing import Callable, Dict, List, Optional, Sequence, Union
@@ -25,7 +26,8 @@ __all__ = ["SpeciesData", "RxData", "RxFilter", "get_filter_mask", "DummyKinetic
            "PrecalculatedArrheniusCalculator", "PrecalculatedLindemannCalculator", "allows_continuous",
            "has_conditions", "setup_network", "ODESimulationParams", "StaticODESolve", "VariableODESolve",
            "HIPBDF", "HIPRK45", "ArrheniusRates", "solve_network", "identify_next_seeds", "insert_inert", "ODESolveOutput", "ODESolution", "tconvert", "make_u0", "apply_low_k_cutoff",
-           "get_max_rates", "get_initial_rates", "calculate_discrete_rates"]
+           "get_max_rates", "get_initial_rates", "calculate_discrete_rates",
+           "solve_network_ensemble"]   # EXTENSION: the reference has no ensemble call
 
 _T_UNIT = {  # src/utils.jl:77-97
     "picoseconds": 1.0e-12, "ps": 1.0e-12, "nanoseconds": 1.0e-9, "ns": 1.0e-9, "microseconds": 1.0e-6, "us": 1.0e-6,
@@ -659,6 +661,118 @@ def solve_network(method, sd, rd, copy_network=True, return_integrator=False):
             h.close()
     sol = ODESolution(t, u, capi.RETCODE_NAMES[rc], k=sol_k, stats=st, umax=umax)
     return ODESolveOutput(sd_a, rd_a, sol, sol_k, sol_vcs, pars, conditions)
+
+
+def _same_filter(a, b):
+    """Do two RxFilters select the same reactions by construction (the same object, or the same filter functions -
+    a default RxFilter() of each method counts as the same)?"""
+    if a is b:
+        return True
+    if a.keep_filtered != b.keep_filtered or len(a.filters) != len(b.filters):
+        return False
+    for f, g in zip(a.filters, b.filters):
+        code_f, code_g = getattr(f, "__code__", None), getattr(g, "__code__", None)
+        if not (f is g or (code_f is not None and code_f is code_g and not f.__closure__ and not g.__closure__)):
+            return False
+    return True
+
+
+def _same_calculator(a, b):
+    return a is b or (type(a) is type(b) and np.array_equal(a.Ea, b.Ea) and np.array_equal(a.A, b.A) and a.k_max == b.k_max
+                      and a.t_mult == b.t_mult)
+
+
+def apply_ensemble_low_k_cutoff(rd, calc, pars, condition_sets):
+    """apply_low_k_cutoff! over an ensemble (EXTENSION, solve_network_ensemble): a reaction is removed only if every condition
+    set's cutoff removes it. Mutates rd and the calculator as apply_low_k_cutoff does; returns the removed positions."""
+    if pars.low_k_cutoff == "none":
+        return np.zeros(0, dtype=int)
+    k_cutoff = pars.reltol / pars.tspan[-1] if pars.low_k_cutoff == "auto" else float(pars.low_k_cutoff)
+    low = np.ones(rd.nr, bool)
+    for cs in condition_sets:
+        low &= get_max_rates(cs, calc) * pars.low_k_maxconc ** 2 < k_cutoff
+    rids = np.nonzero(low)[0]
+    rd.splice(rids)
+    calc.splice(rids)
+    return rids
+
+
+def solve_network_ensemble(methods, sd, rd, copy_network=True):
+    """EXTENSION (the reference has no ensemble call: it solves member after member through solve_network): K
+    `VariableODESolve`s with continuous Arrhenius condition sets - one temperature profile each, e.g. a set of heating rates or
+    start temperatures - on one network in ONE kin_solve_ensemble_continuous call. Returns one ODESolveOutput per member.
+
+    The methods must share the calculator, the filter and every ODESimulationParams field except u0 (ValueError otherwise,
+    before anything touches the GPU). solve_network's pipeline runs once: every member's solve_variable_conditions, filter,
+    splice, setup_network!, low-k cutoff, then the members' u0. The low-k cutoff removes a reaction only if EVERY member's
+    cutoff (its own condition set's maximum rates, apply_low_k_cutoff) removes it: when the members agree, the network is
+    exactly the one solve_network builds for each; otherwise a member may keep reactions its own solve_network would have
+    dropped (rates below its cutoff, which is the cutoff's own criterion for negligible). Every member's calculator object is
+    spliced as solve_network splices it (once per distinct object).
+    Per member: sol_vcs (the variable conditions at the saved times) and sol.umax as solve_network fills them, sol.retcode
+    the member's own (a failed member does not raise: the others' results stand), update_tols writes the member's final
+    tolerances into its own `pars`. Static, discrete-update and non-Arrhenius sets raise ValueError: use
+    HipNetwork.solve_ensemble (kin_solve_ensemble) or solve_network for those."""
+    methods = list(methods)
+    if not methods:
+        raise ValueError("solve_network_ensemble needs at least one method")
+    m0 = methods[0]
+    for m in methods:
+        if not isinstance(m, VariableODESolve) or m.conditions.discrete_updates or \
+                not isinstance(m.calculator, PrecalculatedArrheniusCalculator):
+            raise ValueError("solve_network_ensemble takes VariableODESolves with continuous condition sets and the Arrhenius "
+                             "calculator; for static or discrete-update solves use HipNetwork.solve_ensemble (kin_solve_ensemble) "
+                             "or solve_network")
+        if m.pars.explicit:
+            raise ValueError("solver='RK45' is not available with continuous rate updates; use the default BDF")
+        if not _same_calculator(m.calculator, m0.calculator):
+            raise ValueError("the methods of an ensemble must share the calculator")
+        if not _same_filter(m.filter, m0.filter):
+            raise ValueError("the methods of an ensemble must share the filter")
+        for f in dataclasses.fields(ODESimulationParams):
+            if f.name != "u0" and getattr(m.pars, f.name) != getattr(m0.pars, f.name):
+                raise ValueError(f"the methods of an ensemble must share every ODESimulationParams field except u0 ({f.name} differs)")
+    pars, calc = m0.pars, m0.calculator
+    sd_a, rd_a = (copy.deepcopy(sd), copy.deepcopy(rd)) if copy_network else (sd, rd)
+    for m in methods:
+        solve_variable_conditions(m.conditions, m.pars)
+    mask = get_filter_mask(m0.filter, sd_a, rd_a)
+    rd_a.splice(np.nonzero(mask)[0])
+    setup_network(sd_a, rd_a, calc)
+    rids = apply_ensemble_low_k_cutoff(rd_a, calc, pars, [m.conditions for m in methods])
+    # members may carry distinct (equal) calculator objects: each is spliced, as its own solve_network would splice it
+    spliced = [calc]
+    for m in methods:
+        if not any(m.calculator is c for c in spliced):
+            m.calculator.splice(rids)
+            spliced.append(m.calculator)
+    U0 = np.array([make_u0(sd_a, m.pars) for m in methods])
+    nodes = []
+    for m in methods:
+        prof = m.conditions.profiles[m.conditions.symbols.index("T")]
+        if isstatic(prof):
+            nodes.append((np.array([pars.tspan[0], pars.tspan[1]]), np.array([prof.value, prof.value], dtype=float)))
+        else:
+            nodes.append((np.asarray(prof.sol.t, dtype=float), np.asarray(prof.sol.u, dtype=float)))
+    h = capi.HipNetwork(*rd_a.flat(sd_a.n), index_base=1)
+    try:
+        h.set_arrhenius(calc.Ea, calc.A, calc.k_max, calc.t_mult)
+        t, u, ns, rcs, sts = h.solve_ensemble_continuous(pars.to_kin_params(), U0, nodes)
+    finally:
+        h.close()
+    out = []
+    for i, m in enumerate(methods):
+        n_i = int(ns[i])
+        ti, ui = t[:n_i].copy(), u[i, :n_i].copy()
+        sol_vcs = {sym: np.interp(ti, prof.sol.t, prof.sol.u) for sym, prof in zip(m.conditions.symbols, m.conditions.profiles)
+                   if not isstatic(prof)}
+        st = sts[i]
+        if m.pars.update_tols and st["final_abstol"] != m.pars.abstol:
+            m.pars.abstol, m.pars.reltol = st["final_abstol"], st["final_reltol"]   # solve_utils.jl:397-401
+        umax = ui.max(axis=0) if n_i else np.zeros(sd_a.n)
+        sol = ODESolution(ti, ui, capi.RETCODE_NAMES[int(rcs[i])], k=None, stats=st, umax=umax)
+        out.append(ODESolveOutput(sd_a, rd_a, sol, None, sol_vcs, m.pars, m.conditions))
+    return out
 
 
 # ---- the consumer of a level's solve (src/exploration/explore_utils.jl:338-406) ---------------------------

@@ -1,0 +1,63 @@
+// TEST INFRASTRUCTURE - not a product path, never loaded by kinetica_jl_amd.
+// CPU replay of the resident integrator's continuous rate mode (ResParams::rate_mode 3: the rates re-formed at T(t) of every
+// step attempt, resident_core.hpp): the sequential backend of tests/native/resident_host.cpp, unchanged, extended by the two
+// operations that mode needs - apply_T (the Arrhenius rates at one temperature, what resident.hip's ph_apply_T does) and the
+// LU-cache lookup with the bound on the age of a slot's Jacobian in accepted steps.
+#include "../native/resident_host.cpp"
+
+namespace {
+
+struct ContBackend : HostBackend {
+  using HostBackend::HostBackend;
+  void apply_T(double T) {
+    const double RT = 8.314462618 * T;
+    for (int r = 0; r < R; r++) {
+      const double kr = net.A[r] * std::exp(-net.Ea[r] / RT) * 6.02214076e23 * net.t_mult;
+      k[r] = net.has_kmax ? 1.0 / (1.0 / net.k_max + 1.0 / kr) : kr;
+    }
+  }
+  int nearest_slot(double c, double band, long long n_restarts, long long max_age, long long n_steps, long long step_age) const {
+    int best = -1; double bd = 1e300;
+    for (int i = 0; i < (int)slots.size(); i++) {
+      const Slot& q = slots[i];
+      if (!q.valid || n_restarts - q.jac_stamp > max_age) continue;
+      if (step_age >= 0 && n_steps - q.step_stamp > step_age) continue;
+      const double r = std::fabs(std::log(c / q.c_fact));
+      if (r < bd && std::fabs(c / q.c_fact - 1.0) <= band) { bd = r; best = i; }
+    }
+    return best;
+  }
+};
+static_assert(ResHasApplyT<ContBackend>::value, "the continuous backend is detected");
+static_assert(!ResHasApplyT<HostBackend>::value, "the plain replay backend runs without apply_T");
+
+}  // namespace
+
+extern "C" {
+
+// a continuous solve: kin_solve_continuous's arguments (the handle made by res_host_create, Arrhenius parameters set by
+// res_host_set_arrhenius); out_t / out_u sized by res_host_rows
+int res_cont_solve(void* hv, const kin_params* p, const double* u0, const double* t_nodes, const double* T_nodes, int64_t n_nodes,
+                   int n_slots, double* out_t, double* out_u, int64_t* n_saved, ResResult* result) {
+  HostNet* n = (HostNet*)hv;
+  const ResGrid g = make_res_grid(*p);
+  ResParams P{};
+  res_fill_params(P, *p, g);
+  res_default_settings(P, n_slots > 0 ? n_slots : RES_MAX_SLOTS);
+  P.save_local = g.save_local.data();
+  P.n_stops = 0;
+  P.rate_mode = 3;
+  P.t_nodes = t_nodes; P.T_nodes = T_nodes; P.n_nodes = n_nodes;
+  ContBackend B(*n, P);
+  B.u0 = u0;
+  ResidentBdf<ContBackend> ctl(B, P);
+  const ResResult r = ctl.run();
+  const int64_t rows = std::min<int64_t>(r.n_saved, g.cap);
+  if (out_t) std::copy(B.sol_t.begin(), B.sol_t.begin() + rows, out_t);
+  if (out_u) std::copy(B.sol.begin(), B.sol.begin() + (size_t)rows * n->H.N, out_u);
+  if (n_saved) *n_saved = rows;
+  if (result) *result = r;
+  return r.retcode;
+}
+
+}  // extern "C"

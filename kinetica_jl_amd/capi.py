@@ -390,16 +390,8 @@ class HipNetwork:
             tstops = _f64(tstops); n_stops = len(tstops)
             T_stops = None if T_stops is None else _f64(T_stops)
             k_table = None if k_table is None else np.ascontiguousarray(_f64(k_table).reshape(n_stops, self.nr))
-        rows = c_int64(0)
-        fn = lib().kin_solve_ensemble
-        self._chk(fn(self._h, ctypes.byref(params), K, _pd(u0), _pd(k), _pd(T), _pd(tstops), _pd(T_stops), _pd(k_table), n_stops,
-                     ctypes.byref(rows), None, None, None, None, None))
-        M = rows.value
-        t = np.empty(M); u = np.empty((K, M, self.n)); ns = np.zeros(K, np.int64); rcs = np.zeros(K, np.int32)
-        stats = (KinStats * K)()
-        self._chk(fn(self._h, ctypes.byref(params), K, _pd(u0), _pd(k), _pd(T), _pd(tstops), _pd(T_stops), _pd(k_table), n_stops,
-                     ctypes.byref(rows), _pd(t), _pd(u), ns.ctypes.data_as(POINTER(c_int64)), rcs.ctypes.data_as(POINTER(c_int32)), stats))
-        return t, u, ns, rcs, [s_.as_dict() for s_ in stats]
+        return self._ensemble(lib().kin_solve_ensemble, params, K, _pd(u0), _pd(k), _pd(T), _pd(tstops), _pd(T_stops), _pd(k_table),
+                              n_stops)
 
     def solve_ensemble_continuous(self, params: KinParams, u0, nodes):
         """kin_solve_ensemble_continuous: K trajectories under continuous rate updates, member m's rates at T(t) of its own
@@ -415,16 +407,18 @@ class HipNetwork:
         ptr[1:] = np.cumsum([len(a) for a in tn])
         t_all = np.ascontiguousarray(np.concatenate(tn))
         T_all = np.ascontiguousarray(np.concatenate(Tn))
-        P64_ = lambda a: a.ctypes.data_as(POINTER(c_int64))
+        return self._ensemble(lib().kin_solve_ensemble_continuous, params, K, _pd(u0), _p64(ptr), _pd(t_all), _pd(T_all))
+
+    def _ensemble(self, fn, params, K, *inputs):
+        """The two calls of an ensemble entry point `fn`: the size query, then the solve into fresh outputs. `inputs`: its
+        arguments between K and n_rows. Returns (t[M], u[K][M][N], n_saved[K], retcodes[K], [stats dict] * K)."""
         rows = c_int64(0)
-        fn = lib().kin_solve_ensemble_continuous
-        self._chk(fn(self._h, ctypes.byref(params), K, _pd(u0), P64_(ptr), _pd(t_all), _pd(T_all), ctypes.byref(rows), None, None, None,
-                     None, None))
+        self._chk(fn(self._h, ctypes.byref(params), K, *inputs, ctypes.byref(rows), None, None, None, None, None))
         M = rows.value
         t = np.empty(M); u = np.empty((K, M, self.n)); ns = np.zeros(K, np.int64); rcs = np.zeros(K, np.int32)
         stats = (KinStats * K)()
-        self._chk(fn(self._h, ctypes.byref(params), K, _pd(u0), P64_(ptr), _pd(t_all), _pd(T_all), ctypes.byref(rows), _pd(t), _pd(u),
-                     P64_(ns), rcs.ctypes.data_as(POINTER(c_int32)), stats))
+        self._chk(fn(self._h, ctypes.byref(params), K, *inputs, ctypes.byref(rows), _pd(t), _pd(u), _p64(ns),
+                     rcs.ctypes.data_as(POINTER(c_int32)), stats))
         return t, u, ns, rcs, [s_.as_dict() for s_ in stats]
 
     def solve_continuous(self, params: KinParams, u0, t_nodes, T_nodes):

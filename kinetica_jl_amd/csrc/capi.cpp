@@ -368,10 +368,6 @@ kin_network* clone_for_solves(kin_network* h) {
   return c.release();
 }
 
-int replica_threads_max();
-int64_t replica_members_max() {
-  return (int64_t)replica_threads_max();
-}
 int replica_threads_max() {
   const char* e = getenv("KIN_ENSEMBLE_THREADS");   // (read per call: tests change it)
   return std::max(1, e ? atoi(e) : 12);
@@ -381,15 +377,11 @@ int replica_threads_max() {
 // Every member is, bit for bit, what kin_solve gives for its inputs. A chain of ~14 small dependent launches per step keeps one
 // trajectory at 6.7 solves/s (first 2 chunks of the 10k-species network) and K of them at 11 / 17 / 17 / 16 for K = 2 / 4 / 8 / 12 - the
 // dispatch rate of the chip's queues; the lockstep rounds of ensemble.cpp only overtake that from K = 16 on.
-// node_ptr != NULL: continuous rate updates, member m is the kin_solve_continuous of its own profile
-// (t_nodes, T_nodes)[node_ptr[m] .. node_ptr[m + 1]).
-void replica_ensemble(kin_network* h, const kin_params& p, int64_t K, const double* u0, const double* k, const double* T,
-                      const double* tstops, const double* T_stops, const double* k_table, int64_t n_stops, int64_t* n_rows,
-                      double* out_t, double* out_u, int64_t* n_saved, int32_t* retcodes, kin_stats* stats,
-                      const int64_t* node_ptr = nullptr, const double* t_nodes = nullptr, const double* T_nodes = nullptr) {
-  const int64_t N = h->host.N, R = h->host.R;
-  const int64_t cap = make_res_grid(p).cap;
-  if (n_rows) *n_rows = cap;
+// A continuous call's member m is the kin_solve_continuous of its own profile.
+void replica_ensemble(kin_network* h, const EnsembleCall& c) {
+  const int64_t N = h->host.N, R = h->host.R, K = c.K;
+  const int64_t cap = make_res_grid(c.p).cap;
+  if (c.n_rows) *c.n_rows = cap;
   // EMPIRICAL (ROCm 7.2, MI355X; tools/replica_sequence.py): members whose streams are among the first ~4 streams of the
   // process slow each other down when they run together - K = 4: 11.4 solves/s, with three or more streams created BEFORE theirs
   // (and kept alive; destroyed ones do not count) 17.0; K = 8: 13.3 -> 16.7; K = 12: 13.9 -> 16.3. Which thread creates a
@@ -418,49 +410,42 @@ void replica_ensemble(kin_network* h, const kin_params& p, int64_t K, const doub
   KIN_HIP(hipStreamSynchronize(h->stream));
   std::vector<std::string> errs((size_t)Tn);
   std::vector<std::thread> th;
-  // the save times are the members' common grid: those of the member that got furthest (the first of them)
-  std::mutex grid_mu;
-  int64_t grid_n = -1;
+  std::vector<int64_t> rows((size_t)K, 0);              // every member's saved rows ...
+  std::vector<std::vector<double>> times((size_t)K);    // ... and their times (out_t: those of res_furthest)
   th.reserve((size_t)Tn);
   std::string spawn_err;
   for (int64_t t = 0; t < Tn && spawn_err.empty(); t++) try {
     th.emplace_back([&, t] {
       try {
-        kin_network* c = h->replicas[(size_t)t];
-        KIN_HIP(hipSetDevice(c->device));
-        hipStream_t s = c->stream;
+        kin_network* rep = h->replicas[(size_t)t];
+        KIN_HIP(hipSetDevice(rep->device));
+        hipStream_t s = rep->stream;
         if (h->has_arrhenius) {
-          c->Ea.alloc(R); c->A.alloc(R);
-          KIN_HIP(hipMemcpyAsync(c->Ea.p, h->Ea.p, (size_t)R * sizeof(double), hipMemcpyDeviceToDevice, s));
-          KIN_HIP(hipMemcpyAsync(c->A.p, h->A.p, (size_t)R * sizeof(double), hipMemcpyDeviceToDevice, s));
-          c->has_arrhenius = true; c->has_kmax = h->has_kmax; c->k_max = h->k_max; c->t_mult = h->t_mult;
+          rep->Ea.alloc(R); rep->A.alloc(R);
+          KIN_HIP(hipMemcpyAsync(rep->Ea.p, h->Ea.p, (size_t)R * sizeof(double), hipMemcpyDeviceToDevice, s));
+          KIN_HIP(hipMemcpyAsync(rep->A.p, h->A.p, (size_t)R * sizeof(double), hipMemcpyDeviceToDevice, s));
+          rep->has_arrhenius = true; rep->has_kmax = h->has_kmax; rep->k_max = h->k_max; rep->t_mult = h->t_mult;
         }
         for (int64_t m = t; m < K; m += Tn) {
-          if (n_stops == 0 && !node_ptr) {
-            if (k) KIN_HIP(hipMemcpyAsync(c->k.p, k + m * R, (size_t)R * sizeof(double), hipMemcpyHostToDevice, s));
-            else if (T) launch_arrhenius(R, c->Ea.p, c->A.p, c->has_kmax, c->k_max, c->t_mult, T[m], c->k.p, s);
-            else KIN_HIP(hipMemcpyAsync(c->k.p, h->k.p, (size_t)R * sizeof(double), hipMemcpyDeviceToDevice, s));
-            c->has_rates = true; c->k_pending = false;
+          if (c.static_rates()) {
+            stage_member_rates(h, c, m, rep->Ea.p, rep->A.p, rep->k.p, s);
+            rep->has_rates = true; rep->k_pending = false;
           }
           KIN_HIP(hipStreamSynchronize(s));
           kin_stats st{};
-          const int rc = node_ptr ? solve_entry(c, p, u0 + m * N, nullptr, nullptr, nullptr, 0, &st, t_nodes + node_ptr[m],
-                                                T_nodes + node_ptr[m], node_ptr[m + 1] - node_ptr[m])
-                                  : solve_entry(c, p, u0 + m * N, tstops, T_stops, k_table, n_stops, &st);
-          if (retcodes) retcodes[m] = rc;
-          if (stats) stats[m] = st;
-          const int64_t ns = std::min<int64_t>(c->n_saved, cap);
-          if (n_saved) n_saved[m] = ns;
-          if (out_u && ns > 0) c->d_sol_u.download(out_u + (size_t)m * cap * N, (size_t)ns * N, s);
-          if (out_u && ns < cap) std::memset(out_u + ((size_t)m * cap + (size_t)ns) * N, 0, (size_t)(cap - ns) * N * sizeof(double));   // rows a failed member never wrote
+          const int64_t* ptr = c.node_ptr;
+          const int rc = ptr ? solve_entry(rep, c.p, c.u0 + m * N, nullptr, nullptr, nullptr, 0, &st, c.t_nodes + ptr[m], c.T_nodes + ptr[m],
+                                           ptr[m + 1] - ptr[m])
+                             : solve_entry(rep, c.p, c.u0 + m * N, c.tstops, c.T_stops, c.k_table, c.n_stops, &st);
+          if (c.retcodes) c.retcodes[m] = rc;
+          if (c.stats) c.stats[m] = st;
+          const int64_t ns = std::min<int64_t>(rep->n_saved, cap);
+          rows[(size_t)m] = ns;
+          if (c.n_saved) c.n_saved[m] = ns;
+          if (c.out_u && ns > 0) rep->d_sol_u.download(c.out_u + (size_t)m * cap * N, (size_t)ns * N, s);
+          if (c.out_u && ns < cap) std::memset(c.out_u + ((size_t)m * cap + (size_t)ns) * N, 0, (size_t)(cap - ns) * N * sizeof(double));   // rows a failed member never wrote
           KIN_HIP(hipStreamSynchronize(s));
-          if (out_t) {
-            std::lock_guard<std::mutex> lock(grid_mu);
-            if (ns > grid_n) {
-              grid_n = ns;
-              for (int64_t i = 0; i < ns && i < (int64_t)c->sol_t.size(); i++) out_t[i] = c->sol_t[(size_t)i];
-            }
-          }
+          if (c.out_t) times[(size_t)m].assign(rep->sol_t.begin(), rep->sol_t.begin() + std::min<int64_t>(ns, (int64_t)rep->sol_t.size()));
         }
       } catch (const std::exception& e) { errs[(size_t)t] = e.what(); }
     });
@@ -468,6 +453,30 @@ void replica_ensemble(kin_network* h, const kin_params& p, int64_t K, const doub
   for (auto& x : th) x.join();
   if (!spawn_err.empty()) throw KinError(ERR_DEVICE, "ensemble: could not start a member thread: " + spawn_err);
   for (auto& e : errs) if (!e.empty()) throw KinError(ERR_DEVICE, "ensemble member failed: " + e);
+  if (c.out_t) { const std::vector<double>& tb = times[(size_t)res_furthest(rows)]; std::copy(tb.begin(), tb.end(), c.out_t); }
+}
+
+// Which form an ensemble call takes. Networks whose trajectory fits one compute unit: one workgroup per member, one launch
+// (resident.cpp); larger ones: kin_solve calls on host threads (replica_ensemble) or lockstep rounds of batched launches
+// (ensemble.cpp). KIN_ENSEMBLE_ROUTE = threads | lockstep forces a form (A/B runs: tools/ensemble_route_crossover.py);
+// KIN_ENSEMBLE_BATCHED=1 forces the lockstep form of a static call. The lockstep form has no continuous rate updates.
+void run_ensemble(kin_network* h, const EnsembleCall& c) {
+  const char* e = getenv("KIN_ENSEMBLE_ROUTE");
+  const std::string route = e ? e : "";
+  const bool force_batched = getenv("KIN_ENSEMBLE_BATCHED") && atoi(getenv("KIN_ENSEMBLE_BATCHED")) != 0;
+  if (route == "threads") return replica_ensemble(h, c);
+  if (c.continuous()) {
+    require(route != "lockstep", ERR_UNSUPPORTED, "the lockstep ensemble has no continuous rate updates");
+    return resident_ensemble_route(h, c.K) ? resident_ensemble(h, c) : replica_ensemble(h, c);
+  }
+  if (route == "lockstep" || force_batched) return batched_ensemble(h, c);
+  if (resident_ensemble_route(h, c.K)) return resident_ensemble(h, c);
+  // few members of a network too large for a compute unit: kin_solve calls on host threads, one member per thread up to the
+  // thread limit (beyond it the lockstep rounds are ahead at 3 000 and 10 000 species: profiles/r04_ensemble_route_crossover.jsonl)
+  // ... and ANY number of members when the lockstep form does not take the network's factorisation (it needs the fused solve
+  // with a dense Schur block; KIN_LU_FUSED=0 or a network without hubs has none): the threads then take several members each
+  if (c.K <= replica_threads_max() || !ensemble_batched_supported(h, nullptr)) return replica_ensemble(h, c);
+  batched_ensemble(h, c);
 }
 
 }  // namespace
@@ -486,24 +495,8 @@ int kin_solve_ensemble(kin_network* h, const kin_params* params, int64_t K, cons
   if (n_rows && !out_u && !n_saved) { *n_rows = make_res_grid(*params).cap; }   // size query
   else {
     if (h->k_pending) h->flush_pending_T(h->stream);
-    // networks whose trajectory fits one compute unit: one workgroup per member, one launch (resident.cpp); larger ones:
-    // lockstep rounds of batched launches (ensemble.cpp). KIN_ENSEMBLE_BATCHED=1 forces the second form.
-    const bool force_batched = getenv("KIN_ENSEMBLE_BATCHED") && atoi(getenv("KIN_ENSEMBLE_BATCHED")) != 0;
-    const char* route = getenv("KIN_ENSEMBLE_ROUTE");   // resident | threads | lockstep: A/B runs (tools/ensemble_route_crossover.py)
-    if (route && !strcmp(route, "threads"))
-      replica_ensemble(h, *params, K, u0, k, T, tstops, T_stops, k_table, n_stops, n_rows, out_t, out_u, n_saved, retcodes, stats);
-    else if (route && !strcmp(route, "lockstep"))
-      batched_ensemble(h, *params, K, u0, k, T, tstops, T_stops, k_table, n_stops, n_rows, out_t, out_u, n_saved, retcodes, stats);
-    else if (!force_batched && resident_ensemble_route(h, K))
-      resident_ensemble(h, *params, K, u0, k, T, tstops, T_stops, k_table, n_stops, n_rows, out_t, out_u, n_saved, retcodes, stats);
-    // few members of a network too large for a compute unit: kin_solve calls on host threads, one member per thread up to the
-    // thread limit (beyond it the lockstep rounds are ahead at 3 000 and 10 000 species: profiles/r04_ensemble_route_crossover.jsonl)
-    // ... and ANY number of members when the lockstep form does not take the network's factorisation (it needs the fused solve
-    // with a dense Schur block; KIN_LU_FUSED=0 or a network without hubs has none): the threads then take several members each
-    else if (!force_batched && (K <= replica_members_max() || !ensemble_batched_supported(h, nullptr)))
-      replica_ensemble(h, *params, K, u0, k, T, tstops, T_stops, k_table, n_stops, n_rows, out_t, out_u, n_saved, retcodes, stats);
-    else
-      batched_ensemble(h, *params, K, u0, k, T, tstops, T_stops, k_table, n_stops, n_rows, out_t, out_u, n_saved, retcodes, stats);
+    run_ensemble(h, {*params, K, u0, k, T, tstops, T_stops, k_table, n_stops, nullptr, nullptr, nullptr, n_rows, out_t, out_u, n_saved,
+                     retcodes, stats});
   }
   KIN_CATCH(h)
 }
@@ -523,19 +516,8 @@ int kin_solve_ensemble_continuous(kin_network* h, const kin_params* params, int6
     validate_solve(h, *params, nullptr, nullptr, nullptr, 0, t_nodes + node_ptr[m], T_nodes + node_ptr[m], node_ptr[m + 1] - node_ptr[m], false);
   }
   if (n_rows && !out_u && !n_saved) { *n_rows = make_res_grid(*params).cap; }   // size query
-  else {
-    // the lockstep form has no continuous rate updates; networks the resident kernel takes use it, larger ones (or
-    // KIN_ENSEMBLE_ROUTE=threads) are kin_solve_continuous calls on host threads
-    const char* route = getenv("KIN_ENSEMBLE_ROUTE");
-    require(!(route && !strcmp(route, "lockstep")), ERR_UNSUPPORTED, "the lockstep ensemble has no continuous rate updates");
-    const bool threads = route && !strcmp(route, "threads");
-    if (!threads && resident_ensemble_route(h, K))
-      resident_ensemble(h, *params, K, u0, nullptr, nullptr, nullptr, nullptr, nullptr, 0, n_rows, out_t, out_u, n_saved, retcodes, stats,
-                        node_ptr, t_nodes, T_nodes);
-    else
-      replica_ensemble(h, *params, K, u0, nullptr, nullptr, nullptr, nullptr, nullptr, 0, n_rows, out_t, out_u, n_saved, retcodes, stats,
-                       node_ptr, t_nodes, T_nodes);
-  }
+  else run_ensemble(h, {*params, K, u0, nullptr, nullptr, nullptr, nullptr, nullptr, 0, node_ptr, t_nodes, T_nodes, n_rows, out_t, out_u,
+                        n_saved, retcodes, stats});
   KIN_CATCH(h)
 }
 

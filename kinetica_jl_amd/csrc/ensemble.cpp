@@ -639,74 +639,30 @@ bool ensemble_batched_supported(kin_network* h, std::string* why) {
   return E->ok;
 }
 
-// K members of one (large) network, advanced in lockstep rounds; arguments and outputs as resident_ensemble (resident.cpp)
-static void batched_ensemble_block(kin_network* h, const kin_params& p, int64_t K, const double* u0, const double* k, const double* T,
-                                   const double* tstops, const double* T_stops, const double* k_table, int64_t n_stops, int64_t* out_rows,
-                                   double* out_t, double* out_u, int64_t* n_saved, int32_t* retcodes, kin_stats* stats);
-
-// Every member's controller runs on a host thread of its own: an ensemble of more members than KIN_ENSEMBLE_MAX_MEMBERS
-// (default 128) is integrated block after block (the device is saturated long before that many members of a large network)
-void batched_ensemble(kin_network* h, const kin_params& p, int64_t K, const double* u0, const double* k, const double* T,
-                      const double* tstops, const double* T_stops, const double* k_table, int64_t n_stops, int64_t* out_rows,
-                      double* out_t, double* out_u, int64_t* n_saved, int32_t* retcodes, kin_stats* stats) {
-  int64_t block = 128;
-  if (const char* e = getenv("KIN_ENSEMBLE_MAX_MEMBERS")) block = std::max(1, atoi(e));
-  const int64_t N = h->host.N, R = h->host.R;
-  const int64_t cap = make_res_grid(p).cap;
-  if (K <= block) {
-    batched_ensemble_block(h, p, K, u0, k, T, tstops, T_stops, k_table, n_stops, out_rows, out_t, out_u, n_saved, retcodes, stats);
-    return;
-  }
-  // the save times are the members' common grid: they are taken from the block whose best member got furthest
-  std::vector<double> tt((size_t)cap);
-  std::vector<int64_t> ns((size_t)K, 0);
-  int64_t best = -1;
-  for (int64_t m0 = 0; m0 < K; m0 += block) {
-    const int64_t n = std::min(block, K - m0);
-    batched_ensemble_block(h, p, n, u0 + m0 * N, k ? k + m0 * R : nullptr, T ? T + m0 : nullptr, tstops, T_stops, k_table, n_stops, out_rows,
-                           tt.data(), out_u ? out_u + m0 * cap * N : nullptr, ns.data() + m0, retcodes ? retcodes + m0 : nullptr,
-                           stats ? stats + m0 : nullptr);
-    const int64_t b = *std::max_element(ns.begin() + m0, ns.begin() + m0 + n);
-    if (out_t && b > best) { std::copy(tt.begin(), tt.end(), out_t); best = b; }
-  }
-  if (n_saved) std::copy(ns.begin(), ns.end(), n_saved);
-}
-
-static void batched_ensemble_block(kin_network* h, const kin_params& p, int64_t K, const double* u0, const double* k, const double* T,
-                                   const double* tstops, const double* T_stops, const double* k_table, int64_t n_stops, int64_t* out_rows,
-                                   double* out_t, double* out_u, int64_t* n_saved, int32_t* retcodes, kin_stats* stats) {
+// K members of one (large) network, advanced in lockstep rounds; returns the saved rows of the member whose save times are
+// those in out_t
+static int64_t batched_ensemble_block(kin_network* h, const EnsembleCall& c) {
   auto wall0 = std::chrono::steady_clock::now();
   EnsembleSolver& E = *get_ensemble(h);
   if (!E.ok) throw KinError(ERR_UNSUPPORTED, E.why);
   hipStream_t s = h->stream;
-  const int64_t N = h->host.N, R = h->host.R;
-  const ResGrid g = make_res_grid(p);
-  if (out_rows) *out_rows = g.cap;
-  // LU-cache slots per member: as the resident path, bounded by KIN_LU_CACHE_MB over all members
-  size_t budget_mb = 32768;
-  if (const char* e = getenv("KIN_LU_CACHE_MB")) budget_mb = (size_t)std::max(1, atoi(e));
-  const size_t fit = std::max<size_t>(1, budget_mb * 1024 * 1024 / std::max<size_t>(1, E.lu.slot_bytes() * (size_t)K));
-  int want = RES_MAX_SLOTS;
-  if (const char* e = getenv("KIN_LU_CACHE_SLOTS")) want = std::max(1, atoi(e));
-  const int slots = (int)std::min<size_t>((size_t)std::min(want, RES_MAX_SLOTS), fit);
+  const int64_t N = h->host.N, R = h->host.R, K = c.K;
+  const ResGrid g = make_res_grid(c.p);
+  if (c.n_rows) *c.n_rows = g.cap;
+  const int slots = res_lu_slots(E.lu.slot_bytes(), K);
   E.prepare((int)K, slots, g.cap);
   ResParams P{};
-  res_fill_params(P, p, g);
+  res_fill_params(P, c.p, g);
   res_default_settings(P, slots);
   P.save_local = g.save_local.data();
-  P.n_stops = (int32_t)n_stops;
-  P.rate_mode = n_stops > 0 ? (k_table ? 1 : 2) : 0;
-  P.tstops = tstops;
+  P.n_stops = (int32_t)c.n_stops;
+  P.rate_mode = c.n_stops > 0 ? (c.k_table ? 1 : 2) : 0;
+  P.tstops = c.tstops;
   DevBuf<double> d_u0;
-  d_u0.upload(u0, (size_t)K * N, s);
-  if (n_stops > 0 && k_table) { h->table.upload(k_table, (size_t)n_stops * R, s); h->table_rows = n_stops; }
-  if (n_stops == 0) {
-    for (int64_t t = 0; t < K; t++) {
-      if (k) KIN_HIP(hipMemcpyAsync(E.reps[t].k, k + t * R, (size_t)R * sizeof(double), hipMemcpyHostToDevice, s));
-      else if (T) launch_arrhenius(R, h->Ea.p, h->A.p, h->has_kmax, h->k_max, h->t_mult, T[t], E.reps[t].k, s);
-      else KIN_HIP(hipMemcpyAsync(E.reps[t].k, h->k.p, (size_t)R * sizeof(double), hipMemcpyDeviceToDevice, s));
-    }
-  }
+  d_u0.upload(c.u0, (size_t)K * N, s);
+  if (c.n_stops > 0 && c.k_table) { h->table.upload(c.k_table, (size_t)c.n_stops * R, s); h->table_rows = c.n_stops; }
+  if (c.static_rates())
+    for (int64_t t = 0; t < K; t++) stage_member_rates(h, c, t, h->Ea.p, h->A.p, E.reps[t].k, s);
   KIN_HIP(hipStreamSynchronize(s));
   std::vector<ResResult> res((size_t)K);
   std::vector<std::string> errs((size_t)K);
@@ -719,7 +675,7 @@ static void batched_ensemble_block(kin_network* h, const kin_params& p, int64_t 
       th.emplace_back([&, t] {
         try {
           (void)hipSetDevice(h->device);
-          MemberBackend b(E, (int)t, P, d_u0.p + (size_t)t * N, n_stops > 0 && k_table ? h->table.p : nullptr, T_stops);
+          MemberBackend b(E, (int)t, P, d_u0.p + (size_t)t * N, c.n_stops > 0 && c.k_table ? h->table.p : nullptr, c.T_stops);
           ResidentBdf<MemberBackend> ctl(b, P);
           res[t] = ctl.run();
         } catch (const std::exception& e) {
@@ -742,11 +698,10 @@ static void batched_ensemble_block(kin_network* h, const kin_params& p, int64_t 
   if (!spawn_err.empty()) throw KinError(ERR_DEVICE, "ensemble: could not start a member thread: " + spawn_err);
   for (auto& e : errs) if (!e.empty()) throw KinError(ERR_DEVICE, "ensemble member failed: " + e);
   const double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - wall0).count();
-  if (out_u) E.sol.download(out_u, (size_t)K * (size_t)g.cap * N, s);
+  if (c.out_u) E.sol.download(c.out_u, (size_t)K * (size_t)g.cap * N, s);
   KIN_HIP(hipStreamSynchronize(s));
-  int64_t best = 0;
-  for (int64_t t = 1; t < K; t++) if (res[t].n_saved > res[best].n_saved) best = t;
-  if (out_t) std::copy(E.sol_t[best].begin(), E.sol_t[best].begin() + g.cap, out_t);
+  const int64_t best = res_member_outputs(res, g.cap, E.lu, slots, wall, c.n_saved, c.retcodes, c.stats);
+  if (c.out_t) std::copy(E.sol_t[best].begin(), E.sol_t[best].begin() + g.cap, c.out_t);
   if (getenv("KIN_TIMING")) {
     fprintf(stderr, "[ensemble] %lld members, %lld rounds, wall %.4f s: inside rounds %.4f s (enqueue %.4f, waiting for the device %.4f), "
             "between rounds %.4f s\n", (long long)K, (long long)E.n_rounds, wall, E.t_round, E.t_enqueue, E.t_sync, wall - E.t_round);
@@ -757,20 +712,32 @@ static void batched_ensemble_block(kin_network* h, const kin_params& p, int64_t 
             (long long)E.n_ops[K_VEC], (long long)E.n_ops[K_APPLY_RATES], (long long)E.n_ops[K_RHS], (long long)E.n_ops[K_JAC], (long long)E.n_ops[K_NORMS],
             (long long)E.n_ops[K_INIT_D], (long long)E.n_ops[K_DRIFT], (long long)E.n_ops[K_FACTOR], (long long)E.n_ops[K_CORRECTOR], (long long)E.n_ops[K_CORRECTOR_CONT]);
   }
-  for (int64_t t = 0; t < K; t++) {
-    if (n_saved) n_saved[t] = std::min<int64_t>(res[t].n_saved, g.cap);
-    if (retcodes) retcodes[t] = res[t].retcode;
-    if (stats) {
-      kin_stats& st = stats[t];
-      st = kin_stats{};
-      const ResStats& q = res[t].st;
-      st.n_steps = q.n_steps; st.n_rejected = q.n_rejected; st.n_rhs = q.n_rhs; st.n_jac = q.n_jac; st.n_factor = q.n_factor;
-      st.n_linsolve = q.n_linsolve; st.n_newton_fail = q.n_newton_fail; st.n_chunks = q.n_chunks; st.n_restarts = q.n_restarts;
-      st.n_retries = q.n_retries; st.final_abstol = res[t].final_abstol; st.final_reltol = res[t].final_reltol; st.wall_seconds = wall;
-      st.lu_dense_dim = E.lu.m; st.lu_sparse_rows = E.lu.ns; st.lu_rounds = E.lu.nrounds;
-      st.lu_nnz = 2 * E.lu.nnzU + E.lu.ns + (int64_t)E.lu.m * E.lu.m;
-      st.n_lu_reused = q.n_lu_reused; st.lu_slots = slots; st.n_bad_pivot = q.n_bad_pivot; st.n_lu_dropped = q.n_lu_dropped;
-    }
+  return res[best].n_saved;
+}
+
+// Every member's controller runs on a host thread of its own: an ensemble of more members than KIN_ENSEMBLE_MAX_MEMBERS
+// (default 128) is integrated block after block (the device is saturated long before that many members of a large network);
+// the save times are the members' common grid, taken from the block whose best member got furthest
+void batched_ensemble(kin_network* h, const EnsembleCall& c) {
+  int64_t block = 128;
+  if (const char* e = getenv("KIN_ENSEMBLE_MAX_MEMBERS")) block = std::max(1, atoi(e));
+  const int64_t N = h->host.N, R = h->host.R;
+  const int64_t cap = make_res_grid(c.p).cap;
+  std::vector<double> tt((size_t)cap);
+  int64_t best = -1;
+  for (int64_t m0 = 0; m0 < c.K; m0 += block) {
+    EnsembleCall b = c;
+    b.K = std::min(block, c.K - m0);
+    b.u0 = c.u0 + m0 * N;
+    if (c.k) b.k = c.k + m0 * R;
+    if (c.T) b.T = c.T + m0;
+    b.out_t = tt.data();
+    if (c.out_u) b.out_u = c.out_u + m0 * cap * N;
+    if (c.n_saved) b.n_saved = c.n_saved + m0;
+    if (c.retcodes) b.retcodes = c.retcodes + m0;
+    if (c.stats) b.stats = c.stats + m0;
+    const int64_t rows = batched_ensemble_block(h, b);
+    if (c.out_t && rows > best) { std::copy(tt.begin(), tt.end(), c.out_t); best = rows; }
   }
 }
 

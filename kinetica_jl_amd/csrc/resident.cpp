@@ -149,18 +149,6 @@ ResidentSolver* get_resident(kin_network* h) {
   return h->resident.get();
 }
 
-void stats_from(const ResidentSolver& RS, const ResResult& r, int slots, double wall, kin_stats* st) {
-  if (!st) return;
-  *st = kin_stats{};
-  st->n_steps = r.st.n_steps; st->n_rejected = r.st.n_rejected; st->n_rhs = r.st.n_rhs; st->n_jac = r.st.n_jac;
-  st->n_factor = r.st.n_factor; st->n_linsolve = r.st.n_linsolve; st->n_newton_fail = r.st.n_newton_fail;
-  st->n_chunks = r.st.n_chunks; st->n_restarts = r.st.n_restarts; st->n_retries = r.st.n_retries;
-  st->final_abstol = r.final_abstol; st->final_reltol = r.final_reltol; st->wall_seconds = wall;
-  st->lu_dense_dim = RS.lu.m; st->lu_sparse_rows = RS.lu.ns; st->lu_rounds = RS.lu.nrounds;
-  st->lu_nnz = 2 * RS.lu.nnzU + RS.lu.ns + (int64_t)RS.lu.m * RS.lu.m;
-  st->n_lu_reused = r.st.n_lu_reused; st->lu_slots = slots; st->n_bad_pivot = r.st.n_bad_pivot; st->n_lu_dropped = r.st.n_lu_dropped;
-}
-
 // common part: parameters, tables of the variable conditions, launch, results
 // continuous: rate_mode 3, every member's profile already in its ResTrajDev
 void run_resident(kin_network* h, ResidentSolver& RS, const kin_params& p, const ResGrid& g, int K, int slots, const double* tstops,
@@ -195,16 +183,6 @@ void run_resident(kin_network* h, ResidentSolver& RS, const kin_params& p, const
   res.resize(K);
   RS.d_res.download(res.data(), (size_t)K, s);
   KIN_HIP(hipStreamSynchronize(s));
-}
-
-int clamp_slots(const ResidentSolver& RS, int K) {
-  // LU-cache slots per trajectory: up to RES_MAX_SLOTS, bounded by KIN_LU_CACHE_MB (default 32768) over all trajectories
-  size_t budget_mb = 32768;
-  if (const char* e = getenv("KIN_LU_CACHE_MB")) budget_mb = (size_t)std::max(1, atoi(e));
-  const size_t fit = std::max<size_t>(1, budget_mb * 1024 * 1024 / std::max<size_t>(1, RS.slot_bytes() * (size_t)K));
-  int want = RES_MAX_SLOTS;
-  if (const char* e = getenv("KIN_LU_CACHE_SLOTS")) want = std::max(1, atoi(e));
-  return (int)std::min<size_t>((size_t)std::min(want, RES_MAX_SLOTS), fit);
 }
 
 }  // namespace
@@ -247,7 +225,7 @@ int resident_solve(kin_network* h, const kin_params& p, const double* u0, const 
   hipStream_t s = h->stream;
   const int64_t N = h->host.N, R = h->host.R;
   const ResGrid g = make_res_grid(p);
-  const int slots = clamp_slots(RS, 1);
+  const int slots = res_lu_slots(RS.slot_bytes(), 1);
   // the solution goes straight into the handle's buffer (kin_solution_copy / _max / _dot read it there)
   h->d_sol_u.alloc((size_t)g.cap * N);
   RS.ensure(1, slots, g.cap, false);
@@ -263,7 +241,7 @@ int resident_solve(kin_network* h, const kin_params& p, const double* u0, const 
   // the rates in force at the end of the solve are what the handle holds afterwards, as on the host-driven path
   if (n_stops > 0) { KIN_HIP(hipMemcpyAsync(h->k.p, RS.h_traj[0].k, (size_t)R * sizeof(double), hipMemcpyDeviceToDevice, s)); h->has_rates = true; h->k_pending = false; }
   KIN_HIP(hipStreamSynchronize(s));
-  stats_from(RS, r, slots, std::chrono::duration<double>(std::chrono::steady_clock::now() - wall0).count(), stats);
+  if (stats) *stats = res_stats(r, RS.lu, slots, std::chrono::duration<double>(std::chrono::steady_clock::now() - wall0).count());
   if (getenv("KIN_RESIDENT_PROFILE")) {
     static const char* names[20] = {"kernel", "factor", "(of which dense inverse)", "corrector attempts", "(solve)", "predict", "change_D",
                                     "accept", "jacobian", "rhs", "(rates + residual)", "(update + sums)", "((rates))", "((stage A))", "((gemv))",
@@ -276,57 +254,46 @@ int resident_solve(kin_network* h, const kin_params& p, const double* u0, const 
   return r.retcode;
 }
 
-// K independent trajectories of one network in ONE launch (one workgroup each): u0[K][N]; rate constants k[K][R], or
-// temperatures T[K] (Arrhenius on the device), or the handle's current rates for all; optional discrete rate updates shared by
-// the ensemble (tstops + T_stops or k_table); or, with node_ptr, continuous rate updates: member m's rates are formed at
-// T(t) of every step attempt from its own profile (t_nodes, T_nodes)[node_ptr[m] .. node_ptr[m + 1]), uploaded once.
-// Outputs: out_t[cap], out_u[K][cap][N] (cap = rows of the save grid), n_saved[K], retcodes[K], stats[K].
-void resident_ensemble(kin_network* h, const kin_params& p, int64_t K, const double* u0, const double* k, const double* T,
-                       const double* tstops, const double* T_stops, const double* k_table, int64_t n_stops, int64_t* out_rows,
-                       double* out_t, double* out_u, int64_t* n_saved, int32_t* retcodes, kin_stats* stats, const int64_t* node_ptr,
-                       const double* t_nodes, const double* T_nodes) {
+void stage_member_rates(kin_network* h, const EnsembleCall& c, int64_t m, const double* Ea, const double* A, double* d_k, hipStream_t s) {
+  const int64_t R = h->host.R;
+  if (c.k) KIN_HIP(hipMemcpyAsync(d_k, c.k + m * R, (size_t)R * sizeof(double), hipMemcpyHostToDevice, s));
+  else if (c.T) launch_arrhenius(R, Ea, A, h->has_kmax, h->k_max, h->t_mult, c.T[m], d_k, s);
+  else KIN_HIP(hipMemcpyAsync(d_k, h->k.p, (size_t)R * sizeof(double), hipMemcpyDeviceToDevice, s));
+}
+
+// K independent trajectories of one network in ONE launch (one workgroup each); a continuous call's member profiles are
+// uploaded once
+void resident_ensemble(kin_network* h, const EnsembleCall& c) {
   auto wall0 = std::chrono::steady_clock::now();
   ResidentSolver& RS = *get_resident(h);
   if (!RS.ok) throw KinError(ERR_UNSUPPORTED, "network does not fit the resident integrator: " + RS.why);
   hipStream_t s = h->stream;
-  const int64_t N = h->host.N, R = h->host.R;
-  const ResGrid g = make_res_grid(p);
-  if (out_rows) *out_rows = g.cap;
-  const int slots = clamp_slots(RS, (int)K);
+  const int64_t N = h->host.N, K = c.K;
+  const ResGrid g = make_res_grid(c.p);
+  if (c.n_rows) *c.n_rows = g.cap;
+  const int slots = res_lu_slots(RS.slot_bytes(), K);
   RS.ensure((int)K, slots, g.cap, true);
-  RS.d_u0.upload(u0, (size_t)K * N, s);
-  const bool continuous = node_ptr != nullptr;
-  if (continuous) {
-    const size_t n_all = (size_t)(node_ptr[K] - node_ptr[0]);
-    RS.d_tnodes.upload(t_nodes + node_ptr[0], n_all, s);
-    RS.d_Tnodes.upload(T_nodes + node_ptr[0], n_all, s);
+  RS.d_u0.upload(c.u0, (size_t)K * N, s);
+  if (c.continuous()) {
+    const int64_t* ptr = c.node_ptr;
+    const size_t n_all = (size_t)(ptr[K] - ptr[0]);
+    RS.d_tnodes.upload(c.t_nodes + ptr[0], n_all, s);
+    RS.d_Tnodes.upload(c.T_nodes + ptr[0], n_all, s);
     for (int64_t t = 0; t < K; t++) {
-      RS.h_traj[t].t_nodes = RS.d_tnodes.p + (node_ptr[t] - node_ptr[0]);
-      RS.h_traj[t].T_nodes = RS.d_Tnodes.p + (node_ptr[t] - node_ptr[0]);
-      RS.h_traj[t].n_nodes = node_ptr[t + 1] - node_ptr[t];
+      RS.h_traj[t].t_nodes = RS.d_tnodes.p + (ptr[t] - ptr[0]);
+      RS.h_traj[t].T_nodes = RS.d_Tnodes.p + (ptr[t] - ptr[0]);
+      RS.h_traj[t].n_nodes = ptr[t + 1] - ptr[t];
     }
-  } else if (n_stops == 0) {
-    for (int64_t t = 0; t < K; t++) {
-      if (k) KIN_HIP(hipMemcpyAsync(RS.h_traj[t].k, k + t * R, (size_t)R * sizeof(double), hipMemcpyHostToDevice, s));
-      else if (T) launch_arrhenius(R, h->Ea.p, h->A.p, h->has_kmax, h->k_max, h->t_mult, T[t], RS.h_traj[t].k, s);
-      else KIN_HIP(hipMemcpyAsync(RS.h_traj[t].k, h->k.p, (size_t)R * sizeof(double), hipMemcpyDeviceToDevice, s));
-    }
+  } else if (c.static_rates()) {
+    for (int64_t t = 0; t < K; t++) stage_member_rates(h, c, t, h->Ea.p, h->A.p, RS.h_traj[t].k, s);
   }
   std::vector<ResResult> res;
-  run_resident(h, RS, p, g, (int)K, slots, tstops, T_stops, k_table, n_stops, res, continuous);
+  run_resident(h, RS, c.p, g, (int)K, slots, c.tstops, c.T_stops, c.k_table, c.n_stops, res, c.continuous());
   const double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - wall0).count();
-  if (out_u) RS.d_sol.download(out_u, (size_t)K * (size_t)g.cap * N, s);
-  if (out_t) {   // the save times are the same for every member: taken from the one that got furthest
-    int64_t best = 0;
-    for (int64_t t = 1; t < K; t++) if (res[t].n_saved > res[best].n_saved) best = t;
-    KIN_HIP(hipMemcpyAsync(out_t, RS.d_solt.p + (size_t)best * (size_t)g.cap, (size_t)g.cap * sizeof(double), hipMemcpyDeviceToHost, s));
-  }
+  if (c.out_u) RS.d_sol.download(c.out_u, (size_t)K * (size_t)g.cap * N, s);
+  const int64_t best = res_member_outputs(res, g.cap, RS.lu, slots, wall, c.n_saved, c.retcodes, c.stats);
+  if (c.out_t) KIN_HIP(hipMemcpyAsync(c.out_t, RS.d_solt.p + (size_t)best * (size_t)g.cap, (size_t)g.cap * sizeof(double), hipMemcpyDeviceToHost, s));
   KIN_HIP(hipStreamSynchronize(s));
-  for (int64_t t = 0; t < K; t++) {
-    if (n_saved) n_saved[t] = std::min<int64_t>(res[t].n_saved, g.cap);
-    if (retcodes) retcodes[t] = res[t].retcode;
-    if (stats) stats_from(RS, res[t], slots, wall, stats + t);
-  }
 }
 
 }  // namespace kin

@@ -68,6 +68,25 @@ struct ResParams {
   int64_t n_nodes;
 };
 
+// Continuous rate updates: the temperature at global time tg of the profile (tn, Tn)[n] (n >= 2) - the linear interpolation of
+// the DiffEqArray functor of src/utils.jl:135-139, clamped to the first / last node, else inside [tn[i-1], tn[i]) with
+// i = upper_bound(tn, tg). The one copy every integrator calls (this controller on the device and in its CPU replay, solver.cpp's
+// solve_entry and manual integrator), so that all of them form their rates at the same temperatures; no contraction into FMAs.
+KIN_HD inline double res_T_of(const double* tn, const double* Tn, int64_t n, double tg) {
+#pragma clang fp contract(off)
+  if (tg <= tn[0]) return Tn[0];
+  if (tg >= tn[n - 1]) return Tn[n - 1];
+  int64_t lo = 0, hi = n;   // first node with t > tg (std::upper_bound)
+  while (lo < hi) {
+    const int64_t mid = lo + (hi - lo) / 2;
+    if (tg < tn[mid]) hi = mid; else lo = mid + 1;
+  }
+  const int64_t i = lo;
+  const double dt = tn[i] - tn[i - 1];
+  const double th = dt > 0 ? (tg - tn[i - 1]) / dt : 1.0;
+  return (1.0 - th) * Tn[i - 1] + th * Tn[i];
+}
+
 // The continuous rate mode needs a backend operation the other modes do not: apply_T(T), the rate constants at one
 // temperature. Backends without it (the CPU replay of tests/native/resident_host.cpp) compile as before and never run mode 3.
 template <class B, class = void> struct ResHasApplyT { static constexpr bool value = false; };
@@ -213,29 +232,9 @@ struct ResidentBdf {
 
   KIN_HD bool continuous() const { return ResHasApplyT<B>::value && P.rate_mode == 3; }
 
-  // rate_mode 3: the temperature at global time tg - the arithmetic of solver.cpp's T_of, so that this controller and the
-  // host-driven integrator form their rates at the same temperatures bit for bit: clamped to the first / last node, else the
-  // linear interpolation inside [t[i-1], t[i]) with i = upper_bound(t, tg). Every thread runs it on the same scalars.
-  KIN_HD double T_of(double tg) const {
-#pragma clang fp contract(off)
-    const double* tn = P.t_nodes;
-    const double* Tn = P.T_nodes;
-    const int64_t n = P.n_nodes;
-    if (tg <= tn[0]) return Tn[0];
-    if (tg >= tn[n - 1]) return Tn[n - 1];
-    int64_t lo = 0, hi = n;   // first node with t > tg (std::upper_bound)
-    while (lo < hi) {
-      const int64_t mid = lo + (hi - lo) / 2;
-      if (tg < tn[mid]) hi = mid; else lo = mid + 1;
-    }
-    const int64_t i = lo;
-    const double dt = tn[i] - tn[i - 1];
-    const double th = dt > 0 ? (tg - tn[i - 1]) / dt : 1.0;
-    return (1.0 - th) * Tn[i - 1] + th * Tn[i];
-  }
   // rate_mode 3: the rate constants at the conditions of segment-local time tau (Solver::pre_attempt, bdf.py's hook)
   KIN_HD void rates_at(double tau) {
-    if constexpr (ResHasApplyT<B>::value) b.apply_T(T_of(seg_origin + tau));
+    if constexpr (ResHasApplyT<B>::value) b.apply_T(res_T_of(P.t_nodes, P.T_nodes, P.n_nodes, seg_origin + tau));
   }
   // LU-cache lookup; under continuous rate updates only slots whose Jacobian is at most RES_CONT_JAC_AGE accepted steps old
   KIN_HD int nearest_slot(double c, double band) {

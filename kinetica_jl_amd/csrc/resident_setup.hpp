@@ -2,6 +2,7 @@
 // the save grid, chunk count and dtmin of a solve exactly as solve_entry derives them (solver.cpp; reference
 // src/solving/methods.jl:756-758, 829-846, 164, 232, 694, 770), and the integrator settings with their environment switches.
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <limits>
@@ -19,12 +20,24 @@ struct ResGrid {
   double dtmin = 0.0;
 };
 
+// dtmin handed to the integrator: the caller's value, else what the reference passes - eps(solve_chunkstep) for chunkwise
+// solves (methods.jl:232, 770), eps(tspan[end]) for complete-timespan ones (methods.jl:164, 694); Julia's eps(x) is the
+// spacing of the doubles at x
+inline double res_dtmin(const kin_params& p) {
+  if (p.dtmin > 0.0) return p.dtmin;
+  const double x = std::fabs(p.solve_chunks != 0 ? p.solve_chunkstep : p.tspan1);
+  return std::nextafter(x, std::numeric_limits<double>::infinity()) - x;
+}
+
 // requires a save grid (chunkwise, or a save_interval): the resident path writes into a solution buffer of known size
 inline bool res_has_grid(const kin_params& p) { return p.solve_chunks != 0 || p.save_interval >= 0; }
 
+// per-chunk local save grid: 0:save_interval:chunkstep (methods.jl:756-758); element i is the correctly rounded i*save_interval as
+// produced by Julia's float ranges. Chunkwise, saveat_local = collect(0:save_interval:chunkstep) is a VECTOR, so the chunk end is
+// saved only when it is a grid point (save_hits_end; methods.jl:756-758, 829-846). Needs res_has_grid(p): without a grid and
+// without chunks, solve_chunkstep may be 0.
 inline ResGrid make_res_grid(const kin_params& p) {
   ResGrid g;
-  const double INF = std::numeric_limits<double>::infinity();
   const bool chunks = p.solve_chunks != 0, has_save = p.save_interval >= 0;
   if (chunks) g.n_chunks = (int64_t)(p.tspan1 / p.solve_chunkstep);
   const double span_len = chunks ? p.solve_chunkstep : (p.tspan1 - p.tspan0);
@@ -38,11 +51,7 @@ inline ResGrid make_res_grid(const kin_params& p) {
   const int64_t L = (int64_t)g.save_local.size();
   g.save_hits_end = chunks && L > 0 && g.save_local.back() == p.solve_chunkstep;
   g.cap = chunks ? (L - 1) * g.n_chunks + 1 : L;
-  if (p.dtmin > 0.0) g.dtmin = p.dtmin;
-  else {
-    const double x = std::fabs(chunks ? p.solve_chunkstep : p.tspan1);
-    g.dtmin = std::nextafter(x, INF) - x;
-  }
+  g.dtmin = res_dtmin(p);
   return g;
 }
 
@@ -73,6 +82,51 @@ inline void res_fill_params(ResParams& P, const kin_params& p, const ResGrid& g)
   P.maxiters = p.maxiters; P.n_chunks = g.n_chunks;
   P.L = (int32_t)g.save_local.size();
   P.sol_cap = g.cap;
+}
+
+// LU-cache slots per member of K: up to RES_MAX_SLOTS (KIN_LU_CACHE_SLOTS), bounded by KIN_LU_CACHE_MB (default 32768) over
+// all members; slot_bytes = one slot's factorisation values and diag(J) copy
+inline int res_lu_slots(size_t slot_bytes, int64_t K) {
+  size_t budget_mb = 32768;
+  if (const char* e = getenv("KIN_LU_CACHE_MB")) budget_mb = (size_t)std::max(1, atoi(e));
+  const size_t fit = std::max<size_t>(1, budget_mb * 1024 * 1024 / std::max<size_t>(1, slot_bytes * (size_t)K));
+  int want = RES_MAX_SLOTS;
+  if (const char* e = getenv("KIN_LU_CACHE_SLOTS")) want = std::max(1, atoi(e));
+  return (int)std::min<size_t>((size_t)std::min(want, RES_MAX_SLOTS), fit);
+}
+
+// the kin_stats of a controller's result; `lu`: the SparseLU it factorised with (lu.hpp), `slots` its LU-cache slots
+template <class LU>
+kin_stats res_stats(const ResResult& r, const LU& lu, int slots, double wall) {
+  kin_stats st{};
+  st.n_steps = r.st.n_steps; st.n_rejected = r.st.n_rejected; st.n_rhs = r.st.n_rhs; st.n_jac = r.st.n_jac;
+  st.n_factor = r.st.n_factor; st.n_linsolve = r.st.n_linsolve; st.n_newton_fail = r.st.n_newton_fail;
+  st.n_chunks = r.st.n_chunks; st.n_restarts = r.st.n_restarts; st.n_retries = r.st.n_retries;
+  st.final_abstol = r.final_abstol; st.final_reltol = r.final_reltol; st.wall_seconds = wall;
+  st.lu_dense_dim = lu.m; st.lu_sparse_rows = lu.ns; st.lu_rounds = lu.nrounds;
+  st.lu_nnz = 2 * lu.nnzU + lu.ns + (int64_t)lu.m * lu.m;
+  st.n_lu_reused = r.st.n_lu_reused; st.lu_slots = slots; st.n_bad_pivot = r.st.n_bad_pivot; st.n_lu_dropped = r.st.n_lu_dropped;
+  return st;
+}
+
+// the member whose save times are an ensemble's common grid: the one with the most saved rows (the first of them)
+inline int64_t res_furthest(const std::vector<int64_t>& n_saved) {
+  return std::max_element(n_saved.begin(), n_saved.end()) - n_saved.begin();
+}
+
+// an ensemble's per-member outputs from its members' results: n_saved (clamped to the save grid's `cap` rows), retcodes and
+// stats (each may be null); returns res_furthest of the members
+template <class LU>
+int64_t res_member_outputs(const std::vector<ResResult>& res, int64_t cap, const LU& lu, int slots, double wall, int64_t* n_saved,
+                           int32_t* retcodes, kin_stats* stats) {
+  std::vector<int64_t> rows(res.size());
+  for (size_t t = 0; t < res.size(); t++) {
+    rows[t] = res[t].n_saved;
+    if (n_saved) n_saved[t] = std::min<int64_t>(res[t].n_saved, cap);
+    if (retcodes) retcodes[t] = res[t].retcode;
+    if (stats) stats[t] = res_stats(res[t], lu, slots, wall);
+  }
+  return res_furthest(rows);
 }
 
 }  // namespace kin

@@ -28,6 +28,7 @@
 #include <thread>
 
 #include "lu.hpp"
+#include "resident_setup.hpp"
 #include "solver_kernels.hpp"
 
 namespace kin {
@@ -952,15 +953,6 @@ struct SaveBuf {
   void push_time(double t) { h->sol_t.push_back(t); h->n_saved++; }
 };
 
-// dtmin handed to the integrator: the caller's value, else what the reference passes - eps(solve_chunkstep) for
-// chunkwise solves (methods.jl:232, 770), eps(tspan[end]) for complete-timespan ones (methods.jl:164, 694);
-// Julia's eps(x) is the spacing of the doubles at x
-double resolve_dtmin(const kin_params& p) {
-  if (p.dtmin > 0.0) return p.dtmin;
-  const double x = std::fabs(p.solve_chunks != 0 ? p.solve_chunkstep : p.tspan1);
-  return std::nextafter(x, INF) - x;
-}
-
 // sets the handle's current rates for time-stop index si
 void apply_rates(kin_network* h, const double* T_stops, bool have_table, int64_t si) {
   const int64_t R = h->host.R;
@@ -1015,10 +1007,7 @@ int solve_entry(kin_network* h, const kin_params& p, const double* u0, const dou
   auto wall0 = std::chrono::steady_clock::now();
   const int64_t N = h->host.N, R = h->host.R;
   validate_solve(h, p, tstops, T_stops, k_table, n_stops, t_nodes, T_nodes, n_nodes, true);
-  int64_t n_chunks = 1;
   const bool chunks = p.solve_chunks != 0;
-  const bool has_save = p.save_interval >= 0;
-  if (chunks) n_chunks = (int64_t)(p.tspan1 / p.solve_chunkstep);
   const bool continuous = n_nodes > 0;
   const bool variable = n_stops > 0;
   // small networks: the whole solve in one launch, one workgroup owns the trajectory (resident.cpp)
@@ -1048,7 +1037,7 @@ int solve_entry(kin_network* h, const kin_params& p, const double* u0, const dou
   S.sync_wait_s = 0.0;
   std::fill(S.iter_hist, S.iter_hist + 8, 0);
   S.ban_negatives = p.ban_negatives != 0;
-  S.dtmin = resolve_dtmin(p);
+  S.dtmin = res_dtmin(p);
   double abstol = p.abstol, reltol = p.reltol;
   S.set_tols(abstol, reltol);
 
@@ -1062,44 +1051,24 @@ int solve_entry(kin_network* h, const kin_params& p, const double* u0, const dou
   h->sol_t.clear();
   h->n_saved = 0;
   SaveBuf sb{h, (int)N};
-  // per-chunk local save grid: 0:save_interval:chunkstep (methods.jl:756-758); element i is the
-  // correctly rounded i*save_interval as produced by Julia's float ranges
-  std::vector<double> save_local;
-  double span_len = chunks ? p.solve_chunkstep : (p.tspan1 - p.tspan0);
-  if (chunks || has_save) {
-    const double si = has_save ? p.save_interval : p.solve_chunkstep;
-    const double base = chunks ? 0.0 : p.tspan0;
-    const double last = chunks ? p.solve_chunkstep : p.tspan1;
-    const int64_t cnt = (int64_t)std::floor(span_len / si + 1e-9) + 1;
-    for (int64_t i = 0; i < cnt; i++) save_local.push_back(std::min(base + (double)i * si, last));
-    if (!chunks && save_local.back() < last) save_local.push_back(last);  // save_end
-    // chunkwise: saveat_local = collect(0:save_interval:chunkstep) is a VECTOR, so the chunk end is saved only when it
-    // is a grid point; otherwise the chunk's last saved point lies before the chunk end (methods.jl:756-758, 829-846)
-    if (chunks && std::fabs(save_local.back() - last) <= 1e-9 * last) save_local.back() = last;
-  }
-  const int64_t L = (int64_t)save_local.size();
-  // true: the chunk end is the last local save point (the usual case). false (save_interval does not divide the
-  // chunk): the final chunk's last output is the dense-output value at its last local save point. (The reference
-  // then also restarts every chunk from integ.sol.u[end] = the state at that last SAVED point while labelling it
-  // as the chunk end - a defect that is not copied: chunks always continue from the state at the chunk end.)
-  const bool save_hits_end = chunks && L > 0 && save_local.back() == p.solve_chunkstep;
-  if (chunks) sb.reserve((L - 1) * n_chunks + 1);
-  else sb.reserve(has_save ? L : 1024);
+  // the save grid (resident_setup.hpp; none: every step is saved). save_hits_end true: the chunk end is the last local save point
+  // (the usual case). false (save_interval does not divide the chunk): the final chunk's last output is the dense-output value at
+  // its last local save point. (The reference then also restarts every chunk from integ.sol.u[end] = the state at that last
+  // SAVED point while labelling it as the chunk end - a defect that is not copied: chunks always continue from the state at the
+  // chunk end.)
+  const bool has_grid = res_has_grid(p);
+  const ResGrid grid = has_grid ? make_res_grid(p) : ResGrid{};
+  const std::vector<double>& save_local = grid.save_local;
+  const int64_t L = (int64_t)save_local.size(), n_chunks = grid.n_chunks;
+  const bool save_hits_end = grid.save_hits_end;
+  sb.reserve(has_grid ? grid.cap : 1024);
 
-  // continuous rates: T(t) = linear interpolation of the profile solution (what the DiffEqArray
-  // functor of src/utils.jl:135-139 does), k = calculator(T(t)) re-evaluated on the device
-  auto T_of = [&](double tg) {
-    if (tg <= t_nodes[0]) return T_nodes[0];
-    if (tg >= t_nodes[n_nodes - 1]) return T_nodes[n_nodes - 1];
-    const int64_t i = std::upper_bound(t_nodes, t_nodes + n_nodes, tg) - t_nodes;   // t_nodes[i-1] <= tg < t_nodes[i]
-    const double dt = t_nodes[i] - t_nodes[i - 1];
-    const double th = dt > 0 ? (tg - t_nodes[i - 1]) / dt : 1.0;
-    return (1.0 - th) * T_nodes[i - 1] + th * T_nodes[i];
-  };
+  // continuous rates: T(t) = linear interpolation of the profile solution (resident_core.hpp), k = calculator(T(t)) re-evaluated
+  // on the device
   double seg_origin = 0.0;   // global time of the current segment's tau = 0
   if (continuous) {
     // (no launch: the first kernel of the attempt that reads k forms it from this temperature, handle.hpp)
-    S.pre_attempt = [&](double tau) { h->set_pending_T(T_of(seg_origin + tau)); };
+    S.pre_attempt = [&](double tau) { h->set_pending_T(res_T_of(t_nodes, T_nodes, n_nodes, seg_origin + tau)); };
     h->has_rates = true;
   } else {
     S.pre_attempt = nullptr;
@@ -1305,15 +1274,6 @@ struct IntegratorState {
   std::vector<double> t_nodes, T_nodes;   // continuous rate updates: T(t) = linear interpolation of these (global time)
   int64_t stop_i = 0;
   int retcode = KIN_RETCODE_SUCCESS;
-  double T_of(double tg) const {
-    const int64_t n = (int64_t)t_nodes.size();
-    if (tg <= t_nodes[0]) return T_nodes[0];
-    if (tg >= t_nodes[n - 1]) return T_nodes[n - 1];
-    const int64_t i = std::upper_bound(t_nodes.begin(), t_nodes.end(), tg) - t_nodes.begin();
-    const double dt = t_nodes[i] - t_nodes[i - 1];
-    const double th = dt > 0 ? (tg - t_nodes[i - 1]) / dt : 1.0;
-    return (1.0 - th) * T_nodes[i - 1] + th * T_nodes[i];
-  }
 };
 
 void integrator_init(kin_network* h, const kin_params& p, const double* u0, const double* tstops, const double* T_stops,
@@ -1356,7 +1316,7 @@ void integrator_init(kin_network* h, const kin_params& p, const double* u0, cons
   S.spec = Solver::Spec{};
   S.explicit_mode = false;
   S.ban_negatives = p.ban_negatives != 0;
-  S.dtmin = resolve_dtmin(p);
+  S.dtmin = res_dtmin(p);
   S.set_tols(p.abstol, p.reltol);
   S.pre_attempt = nullptr;
   S.iters_left = p.maxiters;
@@ -1396,7 +1356,9 @@ int64_t integrator_step(kin_network* h, int64_t max_steps) {
   // continuous rate updates: the Arrhenius rates are re-evaluated at T(global time) of every step attempt, as in
   // solve_entry (the integrator's span starts at global time t_loc0, its segments run in local time)
   if (!I.t_nodes.empty())
-    S.pre_attempt = [h, &I](double tau) { h->set_pending_T(I.T_of(I.t_seg + tau)); };
+    S.pre_attempt = [h, &I](double tau) {
+      h->set_pending_T(res_T_of(I.t_nodes.data(), I.T_nodes.data(), (int64_t)I.t_nodes.size(), I.t_seg + tau));
+    };
   struct ClearHook {
     kin_network* h; Solver& S;
     ~ClearHook() {

@@ -6,6 +6,29 @@
 
 namespace kin {
 
+// One ensemble call (kin_solve_ensemble / kin_solve_ensemble_continuous), validated, as every route takes it (resident.cpp,
+// ensemble.cpp, capi.cpp: replica_ensemble): K members of the handle's network from u0[K][N]; per-member rate constants k[K][R],
+// or temperatures T[K] (Arrhenius), or else the handle's current rates for all; optional discrete rate updates shared by the
+// members (tstops + T_stops or k_table); or, with node_ptr, continuous rate updates: member m's rates at T(t) of its own profile
+// (t_nodes, T_nodes)[node_ptr[m] .. node_ptr[m + 1]).
+// Outputs (each may be null): n_rows = cap (rows of the save grid), out_t[cap], out_u[K][cap][N], n_saved[K], retcodes[K], stats[K].
+struct EnsembleCall {
+  kin_params p;
+  int64_t K;
+  const double *u0, *k, *T;
+  const double *tstops, *T_stops, *k_table;
+  int64_t n_stops;
+  const int64_t* node_ptr;
+  const double *t_nodes, *T_nodes;
+  int64_t* n_rows;
+  double *out_t, *out_u;
+  int64_t* n_saved;
+  int32_t* retcodes;
+  kin_stats* stats;
+  bool continuous() const { return node_ptr != nullptr; }
+  bool static_rates() const { return n_stops == 0 && !node_ptr; }   // the members' own k / T / the handle's k for the whole span
+};
+
 // Runs the whole solve (chunk loop, discrete rate updates, retry loop); stores the solution in
 // the handle; returns the final KIN_RETCODE_*.
 int solve_entry(kin_network* h, const kin_params& p, const double* u0, const double* tstops,
@@ -25,22 +48,19 @@ void integrator_state(kin_network* h, double* t, double* u, int32_t* retcode, ki
 bool resident_eligible(kin_network* h, const kin_params& p, bool continuous, bool explicit_solver);
 int resident_solve(kin_network* h, const kin_params& p, const double* u0, const double* tstops, const double* T_stops,
                    const double* k_table, int64_t n_stops, kin_stats* stats);
-void resident_ensemble(kin_network* h, const kin_params& p, int64_t K, const double* u0, const double* k, const double* T,
-                       const double* tstops, const double* T_stops, const double* k_table, int64_t n_stops, int64_t* out_rows,
-                       double* out_t, double* out_u, int64_t* n_saved, int32_t* retcodes, kin_stats* stats,
-                       const int64_t* node_ptr = nullptr, const double* t_nodes = nullptr, const double* T_nodes = nullptr);
-// (node_ptr: continuous rate updates, member m's temperature profile (t_nodes, T_nodes)[node_ptr[m] .. node_ptr[m + 1]) -
-// kin_solve_ensemble_continuous)
+// K members of one network in ONE launch (one workgroup each)
+void resident_ensemble(kin_network* h, const EnsembleCall& c);
 // does the network fit the resident kernel (its state, rates and solve vectors in one compute unit's LDS)?
 bool resident_fits(kin_network* h);
 // ... and does an ensemble of K members take the one-launch form (resident.cpp: not few members of a network at the kernel's upper end)?
 bool resident_ensemble_route(kin_network* h, int64_t K);
 // can the lockstep form (ensemble.cpp) take this network's factorisation? (fused solve with a dense Schur block)
 bool ensemble_batched_supported(kin_network* h, std::string* why);
-// K members of a network beyond that, advanced in lockstep rounds of batched launches (ensemble.cpp); same arguments
-void batched_ensemble(kin_network* h, const kin_params& p, int64_t K, const double* u0, const double* k, const double* T,
-                      const double* tstops, const double* T_stops, const double* k_table, int64_t n_stops, int64_t* out_rows,
-                      double* out_t, double* out_u, int64_t* n_saved, int32_t* retcodes, kin_stats* stats);
+// K members of a network beyond that, advanced in lockstep rounds of batched launches (ensemble.cpp)
+void batched_ensemble(kin_network* h, const EnsembleCall& c);
+// member m's rate constants into d_k (R doubles) on stream s: its row of c.k, Arrhenius at c.T[m] from (Ea, A) - the caller's
+// copy of the handle's parameters -, else the handle's current k (resident.cpp)
+void stage_member_rates(kin_network* h, const EnsembleCall& c, int64_t m, const double* Ea, const double* A, double* d_k, hipStream_t s);
 // validation of a solve's arguments (ODESimulationParams constructor, params.jl:77-104, and the rate inputs); throws
 void validate_solve(kin_network* h, const kin_params& p, const double* tstops, const double* T_stops, const double* k_table,
                     int64_t n_stops, const double* t_nodes, const double* T_nodes, int64_t n_nodes, bool need_handle_rates);

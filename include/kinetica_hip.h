@@ -282,6 +282,18 @@ int kin_solve_ensemble_continuous(kin_network* h, const kin_params* params, int6
                                   const int64_t* node_ptr, const double* t_nodes, const double* T_nodes,
                                   int64_t* n_rows, double* out_t, double* out_u, int64_t* n_saved,
                                   int32_t* retcodes, kin_stats* stats);
+/* An ENSEMBLE of K trajectories under discrete rate updates, one stop schedule per member (reference: a VariableODESolve whose
+ * ConditionSet has ts_update, solve_utils.jl:435-509, swept over heating rates / start temperatures). Member m's rates are the
+ * Arrhenius rates (handle's parameters) at T_stops[j], held from tstops[j] on, j in [stop_ptr[m], stop_ptr[m + 1]) -
+ * exactly kin_solve's zero-order hold with that member's (tstops, T_stops). Stop counts may differ.
+ * Per member as kin_solve: >= 1 stop, strictly increasing tstops (else KIN_ERR_INVALID_ARG), Arrhenius parameters set on the
+ * handle (else KIN_ERR_STATE); a null stop_ptr / tstops / T_stops is KIN_ERR_INVALID_ARG. u0, the save-grid requirement, the
+ * outputs, the size query and the return value are those of kin_solve_ensemble. Added without a KIN_ABI_VERSION change
+ * (purely additive, structs unchanged): a binding detects it by symbol lookup. */
+int kin_solve_ensemble_discrete(kin_network* h, const kin_params* params, int64_t K, const double* u0,
+                                const int64_t* stop_ptr, const double* tstops, const double* T_stops,
+                                int64_t* n_rows, double* out_t, double* out_u, int64_t* n_saved,
+                                int32_t* retcodes, kin_stats* stats);
 /* N1: return_integrator=true (methods.jl:105-106, 175-178, 242-246, 706-709): `init(oprob, solver; kwargs...)`
  * without solve!. The integrator spans the whole tspan (solve_chunks = 0) or the first chunk
  * [0, solve_chunkstep] (solve_chunks = 1, what the reference hands back); tstops / T_stops / k_table as
@@ -341,7 +353,7 @@ const char* kin_version(void);
  * struct sizes) with the values it was written against before the first call: kin_params / kin_stats have grown between
  * versions (1: round 1; 2: + dtmin and the LU-cache counters; 3: + the library-order sweep entry points; 4: + kin_solve_ensemble,
  * kin_lu_analyze_host - structs unchanged; 5: + kin_rhs_batched_klib_dev - structs unchanged; 6: + kin_solve_ensemble_continuous -
- * structs unchanged). */
+ * structs unchanged; kin_solve_ensemble_discrete came later under 6, found by symbol lookup). */
 #define KIN_ABI_VERSION 6
 int kin_abi_version(void);
 int64_t kin_struct_size(int which); /* 0: sizeof(kin_params), 1: sizeof(kin_stats), else -1 */

@@ -29,7 +29,7 @@ SYMBOLS = [
     "kin_solution_max_dev", "kin_rate_table_dev", "kin_rhs_block_dev",
     "kin_lib_layout", "kin_lib_layout_host", "kin_states_to_lib_dev", "kin_states_from_lib_dev", "kin_rates_to_lib_dev", "kin_rate_table_lib_dev",
     "kin_rhs_tiled_dev", "kin_rhs_batched_T_dev", "kin_rhs_batched_klib_dev", "kin_abi_version", "kin_struct_size",
-    "kin_solve_ensemble", "kin_lu_analyze_host", "kin_solve_ensemble_continuous",
+    "kin_solve_ensemble", "kin_lu_analyze_host", "kin_solve_ensemble_continuous", "kin_solve_ensemble_discrete",
 ]
 ABI_VERSION = 6   # include/kinetica_hip.h: KIN_ABI_VERSION this binding was written against
 
@@ -110,6 +110,9 @@ def lib():
                                            POINTER(KinStats)]
         L.kin_solve_ensemble_continuous.argtypes = [c_void_p, POINTER(KinParams), c_int64, PD, P64, PD, PD, P64, PD, PD, P64,
                                                     POINTER(c_int32), POINTER(KinStats)]
+        if hasattr(L, "kin_solve_ensemble_discrete"):   # added under ABI 6: found by symbol lookup, an earlier build lacks it
+            L.kin_solve_ensemble_discrete.argtypes = [c_void_p, POINTER(KinParams), c_int64, PD, P64, PD, PD, P64, PD, PD, P64,
+                                                      POINTER(c_int32), POINTER(KinStats)]
         L.kin_solve_ensemble.argtypes = [c_void_p, POINTER(KinParams), c_int64, PD, PD, PD, PD, PD, PD, c_int64, P64, PD, PD, P64,
                                          POINTER(c_int32), POINTER(KinStats)]
         L.kin_integrator_init.argtypes = [c_void_p, POINTER(KinParams), PD, PD, PD, PD, c_int64]
@@ -408,6 +411,23 @@ class HipNetwork:
         t_all = np.ascontiguousarray(np.concatenate(tn))
         T_all = np.ascontiguousarray(np.concatenate(Tn))
         return self._ensemble(lib().kin_solve_ensemble_continuous, params, K, _pd(u0), _p64(ptr), _pd(t_all), _pd(T_all))
+
+    def solve_ensemble_discrete(self, params: KinParams, u0, stops):
+        """kin_solve_ensemble_discrete: K trajectories under discrete rate updates, member m's rates the Arrhenius rates at
+        T_stops held from tstops on (kin_solve's zero-order hold) of its own schedule. u0[K][N]; stops: K pairs
+        (tstops, T_stops) in global time (stop counts may differ).
+        Returns what solve_ensemble returns: (t[M], u[K][M][N], n_saved[K], retcodes[K], [stats dict] * K)."""
+        u0 = np.ascontiguousarray(np.atleast_2d(_f64(u0)))
+        K = u0.shape[0]
+        assert u0.shape == (K, self.n) and len(stops) == K
+        ts = [_f64(a).ravel() for a, _ in stops]
+        Ts = [_f64(b).ravel() for _, b in stops]
+        assert all(len(a) == len(b) for a, b in zip(ts, Ts))
+        ptr = np.zeros(K + 1, np.int64)
+        ptr[1:] = np.cumsum([len(a) for a in ts])
+        t_all = np.ascontiguousarray(np.concatenate(ts))
+        T_all = np.ascontiguousarray(np.concatenate(Ts))
+        return self._ensemble(lib().kin_solve_ensemble_discrete, params, K, _pd(u0), _p64(ptr), _pd(t_all), _pd(T_all))
 
     def _ensemble(self, fn, params, K, *inputs):
         """The two calls of an ensemble entry point `fn`: the size query, then the solve into fresh outputs. `inputs`: its

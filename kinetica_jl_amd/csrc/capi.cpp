@@ -377,7 +377,8 @@ int replica_threads_max() {
 // Every member is, bit for bit, what kin_solve gives for its inputs. A chain of ~14 small dependent launches per step keeps one
 // trajectory at 6.7 solves/s (first 2 chunks of the 10k-species network) and K of them at 11 / 17 / 17 / 16 for K = 2 / 4 / 8 / 12 - the
 // dispatch rate of the chip's queues; the lockstep rounds of ensemble.cpp only overtake that from K = 16 on.
-// A continuous call's member m is the kin_solve_continuous of its own profile.
+// A continuous call's member m is the kin_solve_continuous of its own profile, a per-member-stops call's the kin_solve of its
+// own (tstops, T_stops).
 void replica_ensemble(kin_network* h, const EnsembleCall& c) {
   const int64_t N = h->host.N, R = h->host.R, K = c.K;
   const int64_t cap = make_res_grid(c.p).cap;
@@ -434,9 +435,10 @@ void replica_ensemble(kin_network* h, const EnsembleCall& c) {
           KIN_HIP(hipStreamSynchronize(s));
           kin_stats st{};
           const int64_t* ptr = c.node_ptr;
+          const EnsembleCall::Stops ms = c.member_stops(m);
           const int rc = ptr ? solve_entry(rep, c.p, c.u0 + m * N, nullptr, nullptr, nullptr, 0, &st, c.t_nodes + ptr[m], c.T_nodes + ptr[m],
                                            ptr[m + 1] - ptr[m])
-                             : solve_entry(rep, c.p, c.u0 + m * N, c.tstops, c.T_stops, c.k_table, c.n_stops, &st);
+                             : solve_entry(rep, c.p, c.u0 + m * N, ms.tstops, ms.T_stops, c.k_table, ms.n, &st);
           if (c.retcodes) c.retcodes[m] = rc;
           if (c.stats) c.stats[m] = st;
           const int64_t ns = std::min<int64_t>(rep->n_saved, cap);
@@ -495,7 +497,7 @@ int kin_solve_ensemble(kin_network* h, const kin_params* params, int64_t K, cons
   if (n_rows && !out_u && !n_saved) { *n_rows = make_res_grid(*params).cap; }   // size query
   else {
     if (h->k_pending) h->flush_pending_T(h->stream);
-    run_ensemble(h, {*params, K, u0, k, T, tstops, T_stops, k_table, n_stops, nullptr, nullptr, nullptr, n_rows, out_t, out_u, n_saved,
+    run_ensemble(h, {*params, K, u0, k, T, tstops, T_stops, k_table, n_stops, nullptr, nullptr, nullptr, nullptr, n_rows, out_t, out_u, n_saved,
                      retcodes, stats});
   }
   KIN_CATCH(h)
@@ -516,8 +518,28 @@ int kin_solve_ensemble_continuous(kin_network* h, const kin_params* params, int6
     validate_solve(h, *params, nullptr, nullptr, nullptr, 0, t_nodes + node_ptr[m], T_nodes + node_ptr[m], node_ptr[m + 1] - node_ptr[m], false);
   }
   if (n_rows && !out_u && !n_saved) { *n_rows = make_res_grid(*params).cap; }   // size query
-  else run_ensemble(h, {*params, K, u0, nullptr, nullptr, nullptr, nullptr, nullptr, 0, node_ptr, t_nodes, T_nodes, n_rows, out_t, out_u,
+  else run_ensemble(h, {*params, K, u0, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, node_ptr, t_nodes, T_nodes, n_rows, out_t, out_u,
                         n_saved, retcodes, stats});
+  KIN_CATCH(h)
+}
+
+int kin_solve_ensemble_discrete(kin_network* h, const kin_params* params, int64_t K, const double* u0,
+                                const int64_t* stop_ptr, const double* tstops, const double* T_stops,
+                                int64_t* n_rows, double* out_t, double* out_u, int64_t* n_saved,
+                                int32_t* retcodes, kin_stats* stats) {
+  if (!h) return KIN_ERR_INVALID_ARG;
+  KIN_TRY(h)
+  require(params && u0 && K >= 1, ERR_INVALID_ARG, "params / u0 is null, or K < 1");
+  require(stop_ptr && tstops && T_stops, ERR_INVALID_ARG, "stop_ptr / tstops / T_stops is null");
+  require(res_has_grid(*params), ERR_INVALID_ARG, "an ensemble solve needs a save grid (solve_chunks or save_interval)");
+  for (int64_t m = 0; m < K; m++) {
+    // every member needs a stop of its own: the controller's rates in force before the first stop are those of stop 0
+    require(stop_ptr[m] >= 0 && stop_ptr[m + 1] - stop_ptr[m] >= 1, ERR_INVALID_ARG, "need >= 1 stop per member");
+    validate_solve(h, *params, tstops + stop_ptr[m], T_stops + stop_ptr[m], nullptr, stop_ptr[m + 1] - stop_ptr[m], nullptr, nullptr, 0, false);
+  }
+  if (n_rows && !out_u && !n_saved) { *n_rows = make_res_grid(*params).cap; }   // size query
+  else run_ensemble(h, {*params, K, u0, nullptr, nullptr, tstops, T_stops, nullptr, 0, stop_ptr, nullptr, nullptr, nullptr, n_rows, out_t,
+                        out_u, n_saved, retcodes, stats});
   KIN_CATCH(h)
 }
 

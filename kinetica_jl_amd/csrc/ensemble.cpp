@@ -474,7 +474,7 @@ struct MemberBackend {
   const ResParams& P;
   const double* u0_dev;       // this member's initial state (device)
   const double* table_dev;    // shared rate table (device) or null
-  const double* T_stops;      // shared temperatures of the stops (host) or null
+  const double* T_stops;      // this member's temperatures of its stops (host) or null
   // deferred operations on the difference array D: the accept of the last step, then step-size changes (composed)
   bool pend_accept = false, pend_change = false;
   int pend_accept_order = 0;
@@ -655,9 +655,7 @@ static int64_t batched_ensemble_block(kin_network* h, const EnsembleCall& c) {
   res_fill_params(P, c.p, g);
   res_default_settings(P, slots);
   P.save_local = g.save_local.data();
-  P.n_stops = (int32_t)c.n_stops;
-  P.rate_mode = c.n_stops > 0 ? (c.k_table ? 1 : 2) : 0;
-  P.tstops = c.tstops;
+  P.rate_mode = c.static_rates() ? 0 : (c.k_table ? 1 : 2);   // (P.tstops / P.n_stops: each member's copy below)
   DevBuf<double> d_u0;
   d_u0.upload(c.u0, (size_t)K * N, s);
   if (c.n_stops > 0 && c.k_table) { h->table.upload(c.k_table, (size_t)c.n_stops * R, s); h->table_rows = c.n_stops; }
@@ -675,8 +673,12 @@ static int64_t batched_ensemble_block(kin_network* h, const EnsembleCall& c) {
       th.emplace_back([&, t] {
         try {
           (void)hipSetDevice(h->device);
-          MemberBackend b(E, (int)t, P, d_u0.p + (size_t)t * N, c.n_stops > 0 && c.k_table ? h->table.p : nullptr, c.T_stops);
-          ResidentBdf<MemberBackend> ctl(b, P);
+          // the member's own parameters: its stops (the shared ones, or its slice of a per-member call's)
+          const EnsembleCall::Stops ms = c.member_stops(t);
+          ResParams Pm = P;
+          Pm.tstops = ms.tstops; Pm.n_stops = (int32_t)ms.n;
+          MemberBackend b(E, (int)t, Pm, d_u0.p + (size_t)t * N, c.n_stops > 0 && c.k_table ? h->table.p : nullptr, ms.T_stops);
+          ResidentBdf<MemberBackend> ctl(b, Pm);
           res[t] = ctl.run();
         } catch (const std::exception& e) {
           errs[t] = e.what();
@@ -731,6 +733,7 @@ void batched_ensemble(kin_network* h, const EnsembleCall& c) {
     b.u0 = c.u0 + m0 * N;
     if (c.k) b.k = c.k + m0 * R;
     if (c.T) b.T = c.T + m0;
+    if (c.stop_ptr) b.stop_ptr = c.stop_ptr + m0;   // (member_stops reads tstops / T_stops at the absolute offsets)
     b.out_t = tt.data();
     if (c.out_u) b.out_u = c.out_u + m0 * cap * N;
     if (c.n_saved) b.n_saved = c.n_saved + m0;

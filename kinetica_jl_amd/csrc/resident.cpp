@@ -149,25 +149,34 @@ ResidentSolver* get_resident(kin_network* h) {
   return h->resident.get();
 }
 
-// common part: parameters, tables of the variable conditions, launch, results
-// continuous: rate_mode 3, every member's profile already in its ResTrajDev
-void run_resident(kin_network* h, ResidentSolver& RS, const kin_params& p, const ResGrid& g, int K, int slots, const double* tstops,
-                  const double* T_stops, const double* k_table, int64_t n_stops, std::vector<ResResult>& res, bool continuous = false) {
+// common part: parameters, the members' stops, tables of the variable conditions, launch, results. `c`: the call whose
+// member_stops every member reads (resident_solve: a call of its one member); a continuous call (rate_mode 3) has every member's
+// profile in its ResTrajDev already
+void run_resident(kin_network* h, ResidentSolver& RS, const EnsembleCall& c, const ResGrid& g, int K, int slots, std::vector<ResResult>& res) {
   hipStream_t s = h->stream;
   const int64_t R = h->host.R;
   ResParams P{};
-  res_fill_params(P, p, g);
+  res_fill_params(P, c.p, g);
   res_default_settings(P, slots);
   P.profile = getenv("KIN_RESIDENT_PROFILE") ? 1 : 0;
   RS.d_save.upload(g.save_local, s);
   P.save_local = RS.d_save.p;
-  P.n_stops = (int32_t)n_stops;
-  P.rate_mode = continuous ? 3 : (n_stops > 0 ? (k_table ? 1 : 2) : 0);
-  if (n_stops > 0) {
-    RS.d_tstops.upload(tstops, (size_t)n_stops, s);
-    P.tstops = RS.d_tstops.p;
-    if (k_table) { h->table.upload(k_table, (size_t)n_stops * R, s); h->table_rows = n_stops; RS.hn.k_table = h->table.p; }
-    else { RS.d_Tstops.upload(T_stops, (size_t)n_stops, s); RS.hn.T_stops = RS.d_Tstops.p; }
+  const bool stops = !c.static_rates() && !c.continuous();
+  P.rate_mode = c.continuous() ? 3 : (stops ? (c.k_table ? 1 : 2) : 0);
+  if (stops) {
+    // one upload of every member's stops - the concatenated arrays of a per-member call, the shared ones else - and each member
+    // pointed at its own (the kernel's prologue copies them into its ResParams: P.tstops / P.n_stops stay unset here)
+    const EnsembleCall::Stops s0 = c.member_stops(0);
+    const size_t n_all = c.stop_ptr ? (size_t)(c.stop_ptr[K] - c.stop_ptr[0]) : (size_t)c.n_stops;
+    RS.d_tstops.upload(s0.tstops, n_all, s);
+    if (c.k_table) { h->table.upload(c.k_table, (size_t)c.n_stops * R, s); h->table_rows = c.n_stops; RS.hn.k_table = h->table.p; }
+    else RS.d_Tstops.upload(s0.T_stops, n_all, s);
+    for (int t = 0; t < K; t++) {
+      const EnsembleCall::Stops ms = c.member_stops(t);
+      RS.h_traj[t].tstops = RS.d_tstops.p + (ms.tstops - s0.tstops);
+      RS.h_traj[t].T_stops = c.k_table ? nullptr : RS.d_Tstops.p + (ms.T_stops - s0.T_stops);
+      RS.h_traj[t].n_stops = ms.n;
+    }
   }
   RS.hn.Ea = h->Ea.p; RS.hn.A = h->A.p; RS.hn.has_kmax = h->has_kmax ? 1 : 0; RS.hn.k_max = h->k_max; RS.hn.t_mult = h->t_mult;
   RS.d_net.upload(&RS.hn, 1, s);
@@ -232,8 +241,10 @@ int resident_solve(kin_network* h, const kin_params& p, const double* u0, const 
   RS.h_traj[0].sol = h->d_sol_u.p;
   RS.d_u0.upload(u0, (size_t)N, s);
   if (n_stops == 0) KIN_HIP(hipMemcpyAsync(RS.h_traj[0].k, h->k.p, (size_t)R * sizeof(double), hipMemcpyDeviceToDevice, s));
+  EnsembleCall c{};
+  c.p = p; c.K = 1; c.u0 = u0; c.tstops = tstops; c.T_stops = T_stops; c.k_table = k_table; c.n_stops = n_stops;
   std::vector<ResResult> res;
-  run_resident(h, RS, p, g, 1, slots, tstops, T_stops, k_table, n_stops, res);
+  run_resident(h, RS, c, g, 1, slots, res);
   const ResResult& r = res[0];
   h->n_saved = std::min<int64_t>(r.n_saved, g.cap);
   h->sol_t.resize((size_t)h->n_saved);
@@ -261,8 +272,8 @@ void stage_member_rates(kin_network* h, const EnsembleCall& c, int64_t m, const 
   else KIN_HIP(hipMemcpyAsync(d_k, h->k.p, (size_t)R * sizeof(double), hipMemcpyDeviceToDevice, s));
 }
 
-// K independent trajectories of one network in ONE launch (one workgroup each); a continuous call's member profiles are
-// uploaded once
+// K independent trajectories of one network in ONE launch (one workgroup each); a continuous call's member profiles and a
+// per-member-stops call's schedules are uploaded once
 void resident_ensemble(kin_network* h, const EnsembleCall& c) {
   auto wall0 = std::chrono::steady_clock::now();
   ResidentSolver& RS = *get_resident(h);
@@ -288,7 +299,7 @@ void resident_ensemble(kin_network* h, const EnsembleCall& c) {
     for (int64_t t = 0; t < K; t++) stage_member_rates(h, c, t, h->Ea.p, h->A.p, RS.h_traj[t].k, s);
   }
   std::vector<ResResult> res;
-  run_resident(h, RS, c.p, g, (int)K, slots, c.tstops, c.T_stops, c.k_table, c.n_stops, res, c.continuous());
+  run_resident(h, RS, c, g, (int)K, slots, res);
   const double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - wall0).count();
   if (c.out_u) RS.d_sol.download(c.out_u, (size_t)K * (size_t)g.cap * N, s);
   const int64_t best = res_member_outputs(res, g.cap, RS.lu, slots, wall, c.n_saved, c.retcodes, c.stats);

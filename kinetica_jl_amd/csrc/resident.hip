@@ -328,7 +328,7 @@ RES_PHASE void ph_apply_rates(long long stop) {
     gcd_t* src = glob(net->k_table) + (size_t)stop * R;
     for (int r = threadIdx.x; r < R; r += RES_WG) k[r] = src[r];
   } else if (g_cx.rate_mode == 2) {
-    const double RT = 8.314462618 * glob(net->T_stops)[stop];
+    const double RT = 8.314462618 * glob(g_cx.T.T_stops)[stop];
     gcd_t* Ea = glob(net->Ea); gcd_t* A = glob(net->A);
     const int has_kmax = g_cx.has_kmax; const double k_max = g_cx.k_max, t_mult = g_cx.t_mult;
     for (int r = threadIdx.x; r < R; r += RES_WG) k[r] = arrhenius_one(Ea[r], A[r], RT, has_kmax, k_max, t_mult);
@@ -1072,6 +1072,7 @@ __global__ __launch_bounds__(RES_WG) __attribute__((amdgpu_waves_per_eu(RES_WAVE
     g_par = *par_p;
     g_cx.T = traj[blockIdx.x];
     if (g_par.rate_mode == 3) { g_par.t_nodes = g_cx.T.t_nodes; g_par.T_nodes = g_cx.T.T_nodes; g_par.n_nodes = g_cx.T.n_nodes; }   // this member's profile
+    if (g_par.rate_mode == 1 || g_par.rate_mode == 2) { g_par.tstops = g_cx.T.tstops; g_par.n_stops = (int32_t)g_cx.T.n_stops; }   // ... stops
     g_cx.net = net_p;
     g_cx.plan[PL_RHS] = n.rhs_plan; g_cx.plan[PL_JAC] = n.jac_plan; g_cx.plan[PL_RESID] = n.resid_plan;
     g_cx.plan[PL_LZ] = n.lz_build; g_cx.plan[PL_NVU] = n.nvu_build; g_cx.plan[PL_STAGEA] = n.stageA; g_cx.plan[PL_STAGEC] = n.stageC;

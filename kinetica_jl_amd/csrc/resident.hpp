@@ -22,7 +22,7 @@ struct ResNetDev {
   const int32_t *mono_ent_ptr, *mono_ptr, *mono_fac, *mono_dst;
   const float* mono_sign;
   const double *Ea, *A;            // rate_mode 2
-  const double *k_table, *T_stops; // rate_mode 1 / 2
+  const double* k_table;           // rate_mode 1 (rate_mode 2 reads each member's ResTrajDev::T_stops)
   int32_t round_e0[RES_MAX_ROUNDS + 1];   // first L entry of every elimination round
   SegPlanView rhs_plan, jac_plan, resid_plan, lz_build, nvu_build, stageA, stageC, fwdZ, fwd_dense, bwdT, bwdV;
   SegPlanView schur[RES_MAX_ROUNDS], fwd[RES_MAX_ROUNDS], bwd[RES_MAX_ROUNDS];
@@ -39,6 +39,8 @@ struct ResTrajDev {
   ResResult* result;
   const double *t_nodes, *T_nodes;   // rate_mode 3: this member's temperature profile (ResParams::t_nodes ...)
   int64_t n_nodes;
+  const double *tstops, *T_stops;    // rate_mode 1 / 2: this member's stops (ResParams::tstops, n_stops); T_stops: rate_mode 2
+  int64_t n_stops;
 };
 
 // enqueues the solve of K trajectories (grid = K workgroups of RES_WG = 512 threads)

@@ -6,11 +6,12 @@
 
 namespace kin {
 
-// One ensemble call (kin_solve_ensemble / kin_solve_ensemble_continuous), validated, as every route takes it (resident.cpp,
+// One ensemble call (kin_solve_ensemble / _continuous / _discrete), validated, as every route takes it (resident.cpp,
 // ensemble.cpp, capi.cpp: replica_ensemble): K members of the handle's network from u0[K][N]; per-member rate constants k[K][R],
 // or temperatures T[K] (Arrhenius), or else the handle's current rates for all; optional discrete rate updates shared by the
-// members (tstops + T_stops or k_table); or, with node_ptr, continuous rate updates: member m's rates at T(t) of its own profile
-// (t_nodes, T_nodes)[node_ptr[m] .. node_ptr[m + 1]).
+// members (tstops + T_stops or k_table, n_stops of them); with stop_ptr, discrete rate updates of each member's own: member m
+// holds the Arrhenius rates at T_stops[j] from tstops[j] on, j in [stop_ptr[m], stop_ptr[m + 1]) of the concatenated arrays; or,
+// with node_ptr, continuous rate updates: member m's rates at T(t) of its own profile (t_nodes, T_nodes)[node_ptr[m] .. node_ptr[m + 1]).
 // Outputs (each may be null): n_rows = cap (rows of the save grid), out_t[cap], out_u[K][cap][N], n_saved[K], retcodes[K], stats[K].
 struct EnsembleCall {
   kin_params p;
@@ -18,6 +19,7 @@ struct EnsembleCall {
   const double *u0, *k, *T;
   const double *tstops, *T_stops, *k_table;
   int64_t n_stops;
+  const int64_t* stop_ptr;
   const int64_t* node_ptr;
   const double *t_nodes, *T_nodes;
   int64_t* n_rows;
@@ -26,7 +28,13 @@ struct EnsembleCall {
   int32_t* retcodes;
   kin_stats* stats;
   bool continuous() const { return node_ptr != nullptr; }
-  bool static_rates() const { return n_stops == 0 && !node_ptr; }   // the members' own k / T / the handle's k for the whole span
+  bool static_rates() const { return n_stops == 0 && !stop_ptr && !node_ptr; }   // the members' own k / T / the handle's k for the whole span
+  // member m's discrete rate updates: its slice of the concatenated stops, else the shared ones (n = 0: none)
+  struct Stops { const double *tstops, *T_stops; int64_t n; };
+  Stops member_stops(int64_t m) const {
+    if (!stop_ptr) return {tstops, T_stops, n_stops};
+    return {tstops + stop_ptr[m], T_stops + stop_ptr[m], stop_ptr[m + 1] - stop_ptr[m]};
+  }
 };
 
 // Runs the whole solve (chunk loop, discrete rate updates, retry loop); stores the solution in

@@ -699,32 +699,40 @@ def apply_ensemble_low_k_cutoff(rd, calc, pars, condition_sets):
 
 def solve_network_ensemble(methods, sd, rd, copy_network=True):
     """EXTENSION (the reference has no ensemble call: it solves member after member through solve_network): K
-    `VariableODESolve`s with continuous Arrhenius condition sets - one temperature profile each, e.g. a set of heating rates or
-    start temperatures - on one network in ONE kin_solve_ensemble_continuous call. Returns one ODESolveOutput per member.
+    `VariableODESolve`s with Arrhenius condition sets - one temperature profile each, e.g. a set of heating rates or start
+    temperatures - on one network in ONE ensemble call: kin_solve_ensemble_continuous when every set is continuous,
+    kin_solve_ensemble_discrete when every set has ts_update (discrete rate updates: each member its own stops and the
+    temperatures at them, discrete_stop_temperatures - stop grids of different lengths included). Returns one ODESolveOutput
+    per member.
 
-    The methods must share the calculator, the filter and every ODESimulationParams field except u0 (ValueError otherwise,
-    before anything touches the GPU). solve_network's pipeline runs once: every member's solve_variable_conditions, filter,
-    splice, setup_network!, low-k cutoff, then the members' u0. The low-k cutoff removes a reaction only if EVERY member's
-    cutoff (its own condition set's maximum rates, apply_low_k_cutoff) removes it: when the members agree, the network is
-    exactly the one solve_network builds for each; otherwise a member may keep reactions its own solve_network would have
-    dropped (rates below its cutoff, which is the cutoff's own criterion for negligible). Every member's calculator object is
-    spliced as solve_network splices it (once per distinct object).
-    Per member: sol_vcs (the variable conditions at the saved times) and sol.umax as solve_network fills them, sol.retcode
-    the member's own (a failed member does not raise: the others' results stand), update_tols writes the member's final
-    tolerances into its own `pars`. Static, discrete-update and non-Arrhenius sets raise ValueError: use
-    HipNetwork.solve_ensemble (kin_solve_ensemble) or solve_network for those."""
+    The methods must share the calculator, the filter and every ODESimulationParams field except u0, and all be continuous or
+    all discrete-update sets (ValueError otherwise, before anything touches the GPU). solve_network's pipeline runs once: every
+    member's solve_variable_conditions, filter, splice, setup_network!, low-k cutoff, then the members' u0. The low-k cutoff
+    removes a reaction only if EVERY member's cutoff (its own condition set's maximum rates, apply_low_k_cutoff) removes it:
+    when the members agree, the network is exactly the one solve_network builds for each; otherwise a member may keep
+    reactions its own solve_network would have dropped (rates below its cutoff, which is the cutoff's own criterion for
+    negligible). Every member's calculator object is spliced as solve_network splices it (once per distinct object).
+    Per member as solve_network fills them: continuous sets give sol_vcs (the variable conditions at the saved times) and
+    sol_k = None, discrete-update sets sol_vcs = None and sol_k = sol.k = ArrheniusRates of the member's own stops; sol.umax;
+    sol.retcode the member's own (a failed member does not raise: the others' results stand); update_tols writes the
+    member's final tolerances into its own `pars`. Ensembles are BDF only (pars.explicit raises ValueError). Static and
+    non-Arrhenius sets raise ValueError: use HipNetwork.solve_ensemble (kin_solve_ensemble) or solve_network for those."""
     methods = list(methods)
     if not methods:
         raise ValueError("solve_network_ensemble needs at least one method")
     m0 = methods[0]
     for m in methods:
-        if not isinstance(m, VariableODESolve) or m.conditions.discrete_updates or \
-                not isinstance(m.calculator, PrecalculatedArrheniusCalculator):
-            raise ValueError("solve_network_ensemble takes VariableODESolves with continuous condition sets and the Arrhenius "
-                             "calculator; for static or discrete-update solves use HipNetwork.solve_ensemble (kin_solve_ensemble) "
-                             "or solve_network")
+        if not isinstance(m, VariableODESolve) or not isinstance(m.calculator, PrecalculatedArrheniusCalculator):
+            raise ValueError("solve_network_ensemble takes VariableODESolves with the Arrhenius calculator; for static solves or "
+                             "other calculators use HipNetwork.solve_ensemble (kin_solve_ensemble) or solve_network")
+        if m.conditions.discrete_updates != m0.conditions.discrete_updates:
+            raise ValueError("the methods of an ensemble must all have continuous or all discrete-update condition sets (one "
+                             "kin_solve_ensemble_continuous / _discrete call); solve the others with HipNetwork.solve_ensemble "
+                             "(kin_solve_ensemble) or solve_network")
         if m.pars.explicit:
-            raise ValueError("solver='RK45' is not available with continuous rate updates; use the default BDF")
+            raise ValueError("solver='RK45' is not available with continuous rate updates; use the default BDF"
+                             if not m.conditions.discrete_updates else
+                             "solver='RK45' is not available in an ensemble (BDF only); use the default BDF or solve_network")
         if not _same_calculator(m.calculator, m0.calculator):
             raise ValueError("the methods of an ensemble must share the calculator")
         if not _same_filter(m.filter, m0.filter):
@@ -732,6 +740,7 @@ def solve_network_ensemble(methods, sd, rd, copy_network=True):
         for f in dataclasses.fields(ODESimulationParams):
             if f.name != "u0" and getattr(m.pars, f.name) != getattr(m0.pars, f.name):
                 raise ValueError(f"the methods of an ensemble must share every ODESimulationParams field except u0 ({f.name} differs)")
+    discrete = m0.conditions.discrete_updates
     pars, calc = m0.pars, m0.calculator
     sd_a, rd_a = (copy.deepcopy(sd), copy.deepcopy(rd)) if copy_network else (sd, rd)
     for m in methods:
@@ -747,31 +756,43 @@ def solve_network_ensemble(methods, sd, rd, copy_network=True):
             m.calculator.splice(rids)
             spliced.append(m.calculator)
     U0 = np.array([make_u0(sd_a, m.pars) for m in methods])
-    nodes = []
-    for m in methods:
-        prof = m.conditions.profiles[m.conditions.symbols.index("T")]
-        if isstatic(prof):
-            nodes.append((np.array([pars.tspan[0], pars.tspan[1]]), np.array([prof.value, prof.value], dtype=float)))
-        else:
-            nodes.append((np.asarray(prof.sol.t, dtype=float), np.asarray(prof.sol.u, dtype=float)))
+    if discrete:
+        # each member's (tstops, T(tstops)), as solve_network hands them to kin_solve
+        stops = [discrete_stop_temperatures(m.conditions) for m in methods]
+    else:
+        nodes = []
+        for m in methods:
+            prof = m.conditions.profiles[m.conditions.symbols.index("T")]
+            if isstatic(prof):
+                nodes.append((np.array([pars.tspan[0], pars.tspan[1]]), np.array([prof.value, prof.value], dtype=float)))
+            else:
+                nodes.append((np.asarray(prof.sol.t, dtype=float), np.asarray(prof.sol.u, dtype=float)))
     h = capi.HipNetwork(*rd_a.flat(sd_a.n), index_base=1)
     try:
         h.set_arrhenius(calc.Ea, calc.A, calc.k_max, calc.t_mult)
-        t, u, ns, rcs, sts = h.solve_ensemble_continuous(pars.to_kin_params(), U0, nodes)
+        if discrete:
+            t, u, ns, rcs, sts = h.solve_ensemble_discrete(pars.to_kin_params(), U0, stops)
+        else:
+            t, u, ns, rcs, sts = h.solve_ensemble_continuous(pars.to_kin_params(), U0, nodes)
     finally:
         h.close()
     out = []
     for i, m in enumerate(methods):
         n_i = int(ns[i])
         ti, ui = t[:n_i].copy(), u[i, :n_i].copy()
-        sol_vcs = {sym: np.interp(ti, prof.sol.t, prof.sol.u) for sym, prof in zip(m.conditions.symbols, m.conditions.profiles)
-                   if not isstatic(prof)}
+        if discrete:
+            sol_vcs = None
+            sol_k = ArrheniusRates(stops[i][0], stops[i][1], m.calculator.Ea, m.calculator.A, m.calculator.k_max, m.calculator.t_mult)
+        else:
+            sol_vcs = {sym: np.interp(ti, prof.sol.t, prof.sol.u) for sym, prof in zip(m.conditions.symbols, m.conditions.profiles)
+                       if not isstatic(prof)}
+            sol_k = None
         st = sts[i]
         if m.pars.update_tols and st["final_abstol"] != m.pars.abstol:
             m.pars.abstol, m.pars.reltol = st["final_abstol"], st["final_reltol"]   # solve_utils.jl:397-401
         umax = ui.max(axis=0) if n_i else np.zeros(sd_a.n)
-        sol = ODESolution(ti, ui, capi.RETCODE_NAMES[int(rcs[i])], k=None, stats=st, umax=umax)
-        out.append(ODESolveOutput(sd_a, rd_a, sol, None, sol_vcs, m.pars, m.conditions))
+        sol = ODESolution(ti, ui, capi.RETCODE_NAMES[int(rcs[i])], k=sol_k, stats=st, umax=umax)
+        out.append(ODESolveOutput(sd_a, rd_a, sol, sol_k, sol_vcs, m.pars, m.conditions))
     return out
 
 

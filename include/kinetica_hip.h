@@ -341,6 +341,15 @@ int kin_rate_table_rows(kin_network* h, const int64_t* rows, int64_t n_rows, dou
  * through exactly the factorisation / substitution kernels kin_solve uses (what KLU does for
  * CVODE in the reference's documented setup, docs/src/getting-started.md:69). */
 int kin_newton_solve(kin_network* h, double c, const double* u, const double* b, double* x);
+/* Diagnostic: the resident integrator's own phases (one workgroup per trajectory, kin_solve's path for small networks and every
+ * one-launch ensemble), run once for K members in one launch with the current rates. Member m (arrays row-major, m-th row):
+ * du[m] = f(u[m]); jac[m] = J(u[m]) in kin_jac_pattern order; x[m] = (I - c[m] J(u[m]))^-1 b[m] through the kernel's
+ * factorisation and its solve form; bad[m] = 1 when a pivot of that factorisation vanished (x[m] is then meaningless).
+ * info (8 + n_species entries): dense Schur block size m, sparse rows ns, elimination rounds, solve form (0 fused,
+ * 1 explicit, 2 plain), task descriptors in LDS (0/1), dynamic LDS bytes, padded dense size, 0; then the species at dense
+ * positions 0 .. m-1. KIN_ERR_UNSUPPORTED when the network does not fit the resident kernel, KIN_ERR_STATE without rates. */
+int kin_resident_probe(kin_network* h, int64_t K, const double* u, const double* c, const double* b, double* du, double* jac,
+                       double* x, int32_t* bad, int64_t* info);
 
 /* ---- device / build information ------------------------------------------------------- */
 int kin_device_count(int* n);
@@ -353,7 +362,7 @@ const char* kin_version(void);
  * struct sizes) with the values it was written against before the first call: kin_params / kin_stats have grown between
  * versions (1: round 1; 2: + dtmin and the LU-cache counters; 3: + the library-order sweep entry points; 4: + kin_solve_ensemble,
  * kin_lu_analyze_host - structs unchanged; 5: + kin_rhs_batched_klib_dev - structs unchanged; 6: + kin_solve_ensemble_continuous -
- * structs unchanged; kin_solve_ensemble_discrete came later under 6, found by symbol lookup). */
+ * structs unchanged; kin_solve_ensemble_discrete and kin_resident_probe came later under 6, found by symbol lookup). */
 #define KIN_ABI_VERSION 6
 int kin_abi_version(void);
 int64_t kin_struct_size(int which); /* 0: sizeof(kin_params), 1: sizeof(kin_stats), else -1 */

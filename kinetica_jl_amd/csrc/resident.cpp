@@ -307,4 +307,43 @@ void resident_ensemble(kin_network* h, const EnsembleCall& c) {
   KIN_HIP(hipStreamSynchronize(s));
 }
 
+// Diagnostic: the kernel's own phases once per member on given inputs (resident_probe.hip), with the handle's current rates and
+// the ResidentSolver every resident solve of this handle uses (analysis, plans, descriptors-in-LDS decision, LDS size)
+void resident_probe(kin_network* h, int64_t K, const double* u, const double* c, const double* b, double* du, double* jac, double* x,
+                    int32_t* bad, int64_t* info) {
+  if (!resident_can_fit(h)) throw KinError(ERR_UNSUPPORTED, "network does not fit the resident integrator: its state and rates exceed the LDS");
+  ResidentSolver& RS = *get_resident(h);
+  if (!RS.ok) throw KinError(ERR_UNSUPPORTED, "network does not fit the resident integrator: " + RS.why);
+  hipStream_t s = h->stream;
+  const int64_t N = h->host.N, R = h->host.R, nnz = h->host.nnz();
+  RS.ensure((int)K, 1, 1, false);
+  RS.d_u0.upload(u, (size_t)K * N, s);
+  DevBuf<double> d_c, d_b, d_x, d_du, d_jac;
+  DevBuf<int32_t> d_bad;
+  d_c.upload(c, (size_t)K, s);
+  d_b.upload(b, (size_t)K * N, s);
+  d_x.alloc((size_t)K * N); d_du.alloc((size_t)K * N); d_jac.alloc((size_t)K * std::max<int64_t>(nnz, 1)); d_bad.alloc((size_t)K);
+  for (int64_t t = 0; t < K; t++) {
+    ResTrajDev& q = RS.h_traj[t];
+    KIN_HIP(hipMemcpyAsync(q.k, h->k.p, (size_t)R * sizeof(double), hipMemcpyDeviceToDevice, s));
+    q.f0 = d_du.p + t * N;
+    q.jv = d_jac.p + t * nnz;
+  }
+  ResParams P{};
+  P.n_slots = 1;
+  RS.hn.Ea = h->Ea.p; RS.hn.A = h->A.p; RS.hn.has_kmax = h->has_kmax ? 1 : 0; RS.hn.k_max = h->k_max; RS.hn.t_mult = h->t_mult;
+  RS.d_net.upload(&RS.hn, 1, s);
+  RS.d_par.upload(&P, 1, s);
+  RS.d_traj.upload(RS.h_traj.data(), (size_t)K, s);
+  launch_resident_probe((int)K, RS.dyn_lds, RS.d_net.p, RS.d_traj.p, RS.d_par.p, ResProbeIO{d_c.p, d_b.p, d_x.p, d_bad.p}, s);
+  d_du.download(du, (size_t)K * N, s);
+  d_jac.download(jac, (size_t)K * nnz, s);
+  d_x.download(x, (size_t)K * N, s);
+  d_bad.download(bad, (size_t)K, s);
+  KIN_HIP(hipStreamSynchronize(s));
+  info[0] = RS.lu.m; info[1] = RS.lu.ns; info[2] = RS.lu.nrounds; info[3] = RS.hn.solve_mode; info[4] = RS.hn.desc_in_lds;
+  info[5] = (int64_t)RS.dyn_lds; info[6] = RS.lu.mpad; info[7] = 0;
+  for (int32_t j = 0; j < RS.lu.m; j++) info[8 + j] = RS.lu.perm[RS.lu.ns + j];
+}
+
 }  // namespace kin

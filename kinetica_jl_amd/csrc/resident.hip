@@ -1009,6 +1009,7 @@ struct DevBackend {
   }
 };
 
+#ifndef RES_LINALG_PROBE   // (the probe kernel runs its phases directly)
 // what the seven other wavefronts do: wait for a command, run its phase, until the leader posts OP_EXIT
 __device__ void worker_loop() {
   // (profile: what the first worker wavefront spends waiting for the next command = the controller's own time between
@@ -1043,6 +1044,7 @@ __device__ void worker_loop() {
     }
   }
 }
+#endif
 
 // counts of medium rows with more than 64 / more than 32 entries (the rows are sorted longest first); all threads
 __device__ __forceinline__ void count_splits(int id) {
@@ -1062,46 +1064,14 @@ __shared__ __attribute__((aligned(16))) unsigned char g_ctl_mem[sizeof(ResidentB
 //   4: 128 VGPRs (a few spills in the corrector, the factorisation and the order change), TWO workgroups share a compute
 //      unit and hide each other's latencies: an ensemble of more members than compute units gets 20-40 % more solves/s at
 //      300 species (4 000-4 600 against 3 300-3 600), a single member is 10-15 % slower (resident.cpp picks per launch).
+// A third, diagnostic build (resident_probe.hip: RES_LINALG_PROBE) has resident_probe_kernel in place of resident_bdf_kernel.
 #ifndef RES_WAVES_PER_EU
 #define RES_WAVES_PER_EU 2
 #endif
+#ifndef RES_LINALG_PROBE
 __global__ __launch_bounds__(RES_WG) __attribute__((amdgpu_waves_per_eu(RES_WAVES_PER_EU, RES_WAVES_PER_EU))) void resident_bdf_kernel(const ResNetDev* __restrict__ net_p, const ResTrajDev* __restrict__ traj,
                                                                const ResParams* __restrict__ par_p) {
-  if (threadIdx.x == 0) {
-    const ResNetDev& n = *net_p;
-    g_par = *par_p;
-    g_cx.T = traj[blockIdx.x];
-    if (g_par.rate_mode == 3) { g_par.t_nodes = g_cx.T.t_nodes; g_par.T_nodes = g_cx.T.T_nodes; g_par.n_nodes = g_cx.T.n_nodes; }   // this member's profile
-    if (g_par.rate_mode == 1 || g_par.rate_mode == 2) { g_par.tstops = g_cx.T.tstops; g_par.n_stops = (int32_t)g_cx.T.n_stops; }   // ... stops
-    g_cx.net = net_p;
-    g_cx.plan[PL_RHS] = n.rhs_plan; g_cx.plan[PL_JAC] = n.jac_plan; g_cx.plan[PL_RESID] = n.resid_plan;
-    g_cx.plan[PL_LZ] = n.lz_build; g_cx.plan[PL_NVU] = n.nvu_build; g_cx.plan[PL_STAGEA] = n.stageA; g_cx.plan[PL_STAGEC] = n.stageC;
-    g_cx.plan[PL_FWDZ] = n.fwdZ; g_cx.plan[PL_FWD_DENSE] = n.fwd_dense; g_cx.plan[PL_BWDT] = n.bwdT; g_cx.plan[PL_BWDV] = n.bwdV;
-    for (int i = 0; i < PL_COUNT; i++) { g_cx.split[i][0] = 0; g_cx.split[i][1] = 0; }
-    g_cx.profile = par_p->profile;
-    g_cx.N = n.N; g_cx.R = n.R; g_cx.nnzJ = n.nnzJ; g_cx.ns = n.ns; g_cx.m = n.m; g_cx.m16 = (n.m + 15) / 16 * 16; g_cx.mpad = n.mpad;
-    g_cx.nrounds = n.nrounds; g_cx.n_mono_ent = n.n_mono_ent; g_cx.solve_mode = n.solve_mode; g_cx.has_kmax = n.has_kmax;
-    g_cx.n_slots = par_p->n_slots; g_cx.rate_mode = par_p->rate_mode;
-    g_cx.off_diag = n.off_diag; g_cx.off_U = n.off_U; g_cx.off_L = n.off_L; g_cx.off_S = n.off_S; g_cx.off_y = n.off_y; g_cx.off_x = n.off_x;
-    g_cx.off_dinv = n.off_dinv; g_cx.w_size = n.w_size;
-    g_cx.k_max = n.k_max; g_cx.t_mult = n.t_mult;
-    g_cx.off_vec_end = n.off_vec_end;
-    const int win = (int)(n.off_vec_end - n.off_y);
-    g_cx.l_y = 0; g_cx.l_d = n.N; g_cx.l_psi = 2 * n.N; g_cx.l_scale = 3 * n.N; g_cx.l_win = 4 * n.N; g_cx.l_rate = 4 * n.N + win;
-    // task descriptors of the corrector's three plans behind the vectors (the host provisioned the LDS for them or did not)
-    g_cx.desc_on = n.desc_in_lds;
-    const int m16_ = (n.m + 15) / 16 * 16;
-    const int tail = n.R > 16 * (m16_ + 1) ? n.R : 16 * (m16_ + 1);
-    int off = 2 * (4 * n.N + win + tail);       // in int32
-    g_cx.desc_off[0] = off; off += desc_ints(n.resid_plan);
-    g_cx.desc_off[1] = off; off += desc_ints(n.stageA);
-    g_cx.desc_off[2] = off;
-  }
-  if (threadIdx.x < 20) g_sh.prof[threadIdx.x] = 0;
-  __syncthreads();
-  for (int id = 0; id < PL_COUNT; id++) count_splits(id);
-  __syncthreads();
-  if (g_cx.desc_on) { stage_descriptors(0, PL_RESID); stage_descriptors(1, PL_STAGEA); stage_descriptors(2, PL_STAGEC); __syncthreads(); }
+#include "resident_prologue.inc"
   if (threadIdx.x >= 64) { worker_loop(); return; }
   // the leader wavefront: controller state and parameters live in LDS (one wavefront in lockstep: no hazards), not in
   // registers that would be spilled around every phase call
@@ -1116,9 +1086,54 @@ __global__ __launch_bounds__(RES_WG) __attribute__((amdgpu_waves_per_eu(RES_WAVE
   (void)c_begin;
   if (threadIdx.x == 0) *g_cx.T.result = r;
 }
+#else
+// The diagnostic build (resident_probe.hip): the phases of one Newton-matrix solve, run once per member on given inputs by all
+// eight wavefronts, set up by the same prologue and launched like resident_bdf_kernel (kin_resident_probe). Member m:
+//   du = f(u) (ph_rhs), jv = J(u) (ph_jac: T.f0 / T.jv point at the caller's output rows), M = I - c J(u) factorised into slot 0
+//   (ph_factor), then M x = b through the network's solve form (solve_wg) with b scattered into the zeroed LDS window at yloc
+//   and x gathered from xloc, and the factorisation's vanished-pivot flag.
+__global__ __launch_bounds__(RES_WG) __attribute__((amdgpu_waves_per_eu(RES_WAVES_PER_EU, RES_WAVES_PER_EU))) void resident_probe_kernel(const ResNetDev* __restrict__ net_p, const ResTrajDev* __restrict__ traj,
+                                                                 const ResParams* __restrict__ par_p, ResProbeIO io) {
+#include "resident_prologue.inc"
+  const int N = uni(g_cx.N), tid = threadIdx.x;
+  const size_t mb = blockIdx.x;
+  ph_vec(VO_LOAD_U0, 0.0);
+  ph_rhs(RO_Y_TO_F0);
+  ph_jac();
+  const bool bad = ph_factor(0, glob(io.c)[mb], false);
+  double* win = L_win();
+  const long long off_y = uni((long long)g_cx.off_y), off_end = uni((long long)g_cx.off_vec_end);
+  for (long long p = off_y + tid; p < off_end; p += RES_WG) win[p] = 0.0;
+  __syncthreads();
+  gci_t* yloc = glob(g_cx.net->yloc); gci_t* xloc = glob(g_cx.net->xloc);
+  gcd_t* b = glob(io.b) + mb * N;
+  for (int i = tid; i < N; i += RES_WG) win[yloc[i]] = b[i];
+  __syncthreads();
+  solve_wg(glob((const double*)g_cx.T.W));
+  gd_t* x = glob(io.x) + mb * N;
+  for (int i = tid; i < N; i += RES_WG) x[i] = win[xloc[i]];
+  if (tid == 0) glob(io.bad)[mb] = bad ? 1 : 0;
+}
+#endif
 
 }  // namespace
 
+#ifdef RES_LINALG_PROBE
+void launch_resident_probe(int K, size_t dyn_lds, const ResNetDev* d_net, const ResTrajDev* d_traj, const ResParams* d_par, const ResProbeIO& io,
+                           hipStream_t s) {
+  if (K <= 0) return;
+  static std::atomic<unsigned long long> attr_set{0};   // (per device, as launch_resident)
+  int dev = 0;
+  KIN_HIP(hipGetDevice(&dev));
+  const unsigned long long bit = 1ull << (dev & 63);
+  if (!(attr_set.load(std::memory_order_acquire) & bit)) {
+    KIN_HIP(hipFuncSetAttribute((const void*)resident_probe_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)RES_LDS_BUDGET));
+    attr_set.fetch_or(bit, std::memory_order_release);
+  }
+  hipLaunchKernelGGL(resident_probe_kernel, dim3((unsigned)K), dim3(RES_WG), dyn_lds, s, d_net, d_traj, d_par, io);
+  KIN_HIP(hipGetLastError());
+}
+#else
 #if RES_WAVES_PER_EU == 2
 size_t resident_dyn_lds(int N, int R, int m, int64_t window) {
   const int m16 = (m + 15) / 16 * 16;
@@ -1153,4 +1168,5 @@ void RES_LAUNCH_NAME(int K, size_t dyn_lds, const ResNetDev* d_net, const ResTra
   KIN_HIP(hipGetLastError());
 }
 
+#endif
 }  // namespace kin

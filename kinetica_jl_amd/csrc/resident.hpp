@@ -54,5 +54,10 @@ void launch_resident(int K, size_t dyn_lds, const ResNetDev* d_net, const ResTra
 // the same kernel built with half the registers per lane: two workgroups share a compute unit (resident_w4.hip)
 void launch_resident_shared_cu(int K, size_t dyn_lds, const ResNetDev* d_net, const ResTrajDev* d_traj, const ResParams* d_par, hipStream_t s);
 size_t resident_static_lds();    // static LDS of the kernel (what two co-resident workgroups need twice, next to 2 x dyn_lds)
+// diagnostic (resident_probe.hip: resident.hip built with RES_LINALG_PROBE): the phases of one Newton-matrix solve per member -
+// f(u) into T.f0, J(u) into T.jv, M = I - c[m] J(u) into slot 0 of T.W, x[m] = M^-1 b[m], bad[m] = the vanished-pivot flag
+struct ResProbeIO { const double *c, *b; double* x; int32_t* bad; };
+void launch_resident_probe(int K, size_t dyn_lds, const ResNetDev* d_net, const ResTrajDev* d_traj, const ResParams* d_par, const ResProbeIO& io,
+                           hipStream_t s);
 
 }  // namespace kin

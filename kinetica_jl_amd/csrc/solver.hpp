@@ -62,6 +62,9 @@ void resident_ensemble(kin_network* h, const EnsembleCall& c);
 bool resident_fits(kin_network* h);
 // ... and does an ensemble of K members take the one-launch form (resident.cpp: not few members of a network at the kernel's upper end)?
 bool resident_ensemble_route(kin_network* h, int64_t K);
+// diagnostic: the resident kernel's RHS, Jacobian, factorisation and solve once per member (kin_resident_probe)
+void resident_probe(kin_network* h, int64_t K, const double* u, const double* c, const double* b, double* du, double* jac, double* x,
+                    int32_t* bad, int64_t* info);
 // can the lockstep form (ensemble.cpp) take this network's factorisation? (fused solve with a dense Schur block)
 bool ensemble_batched_supported(kin_network* h, std::string* why);
 // K members of a network beyond that, advanced in lockstep rounds of batched launches (ensemble.cpp)

@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 from kinetica_jl_amd import capi
-from kinetica_jl_amd.synth import from_lists, synthetic_crn
+from kinetica_jl_amd.synth import SEED, from_lists, synthetic_crn
 from oracle import bdf as obdf
 from oracle import oracle as orc
 
@@ -209,13 +209,14 @@ def test_newton_matrix_solve_against_sparse_direct(mode):
     """(I - c J(u)) x = b through the on-device LU against SciPy's sparse direct solver, for the three solve paths of
     csrc/lu.cpp: the fused three-launch solve (default), the five-launch solve with explicit triangular inverses
     (KIN_LU_FUSED=0) and the round-by-round substitution (KIN_LU_EXPLICIT=0). 1k and 3k species (hub rows long enough
-    for the whole-workgroup gather path), c from the first steps of a restart to the end of a chunk."""
+    for the whole-workgroup gather path) and the 10k network of the headline numbers (m = 1 173, inverted by the
+    multi-workgroup Gauss-Jordan), c from the first steps of a restart to the end of a chunk."""
     import scipy.sparse as sp
     import scipy.sparse.linalg as spl
     env = {"fused": {}, "explicit": {"KIN_LU_FUSED": "0"}, "rounds": {"KIN_LU_EXPLICIT": "0"}}[mode]
     os.environ.update(env)
     try:
-        for n, r, seed in ((1000, 5000, 3), (3000, 15000, 4)):
+        for n, r, seed in ((1000, 5000, 3), (3000, 15000, 4), (10000, 50000, SEED)):
             net, Ea, A = synthetic_crn(n, r, seed=seed)
             h = capi.HipNetwork.from_flat(net)
             h.set_arrhenius(Ea, A, k_max=1e12)

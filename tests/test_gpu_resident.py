@@ -1,7 +1,9 @@
 """GPU parity tests of the resident integrator (kinetica_jl_amd/csrc/resident.hip: one workgroup owns one trajectory for the
 whole solve) through the C ABI: kin_solve on small networks (routed there automatically), kin_solve_ensemble. References: the
 committed Radau truths, the compiled CPU port at tight tolerances, the host-driven multi-kernel integrator (KIN_RESIDENT=0),
-and the CPU replay of the very controller the kernel runs (tests/res_host.py). Reference semantics: solve_network's chunk
+and the CPU replay of the very controller the kernel runs (tests/res_host.py). Trajectories cannot see a subtly wrong Jacobian
+or inverse (the corrector iterates on the true residual): the kernel's RHS, Jacobian, factorisation, dense inverse and solve
+are compared with references phase by phase in tests/test_gpu_resident_linalg.py (kin_resident_probe). Reference semantics: solve_network's chunk
 loop, discrete rate updates and adaptive_solve! retries (methods.jl:185-303, 717-865; solve_utils.jl:376-424, 435-509)."""
 import numpy as np
 import pytest
@@ -225,6 +227,31 @@ def test_more_members_than_compute_units_take_the_shared_cu_build(monkeypatch):
     h.close()
 
 
+def test_shared_cu_build_is_bit_identical_without_look_ahead(monkeypatch):
+    """The two builds (KIN_RESIDENT_SHARED_CU=1 / 0) bit for bit at a dense block of nb = 8 block steps, where the Gauss-Jordan
+    runs without look-ahead, on a network that fits two workgroups per compute unit (else the switch falls back silently)."""
+    from tests.test_gpu_resident_linalg import core_net
+    net = core_net(120)
+    assert capi.lu_analyze_host(net, min_round=2)["m"] == 120                 # nb = 8
+    rng = np.random.default_rng(120)
+    k = 10.0 ** rng.uniform(0.0, 3.0, net.n_reactions)
+    h = capi.HipNetwork.from_flat(net)
+    h.set_rates(k)
+    n = net.n_species
+    info = h.resident_probe(np.ones(n), 1e-3, np.ones(n))["info"]
+    assert info["m"] == 120 and 2 * (info["dyn_lds"] + 16 * 1024) <= 160 * 1024   # (static LDS of the kernel < 16 KiB)
+    K = 16
+    U0 = np.zeros((K, n)); U0[:, :120] = rng.uniform(0.0, 1.0, (K, 120))
+    ks = k[None, :] * rng.uniform(0.5, 2.0, (K, 1))
+    monkeypatch.setenv("KIN_RESIDENT_SHARED_CU", "0")
+    t0, u0_, _, rcs0, sts0 = h.solve_ensemble(kp(2e-3), U0, k=ks)
+    monkeypatch.setenv("KIN_RESIDENT_SHARED_CU", "1")
+    t1, u1_, _, rcs1, sts1 = h.solve_ensemble(kp(2e-3), U0, k=ks)
+    assert (rcs0 == 0).all() and (rcs1 == 0).all() and sts0[0]["n_factor"] > 0
+    assert np.array_equal(t0, t1) and np.array_equal(u0_, u1_) and [q["n_steps"] for q in sts0] == [q["n_steps"] for q in sts1]
+    h.close()
+
+
 def test_warm_chunk_continuation_in_all_three_drivers(monkeypatch):
     """kin_params.solve_chunks = 2 through the resident kernel, the host-driven integrator and - as ensemble members - the
     resident ensemble and the lockstep rounds: same save times as the re-initialising run, fewer steps, results within the
@@ -272,10 +299,11 @@ def test_mid_size_network_through_the_ensemble_entry_point():
     h = capi.HipNetwork.from_flat(net)
     h.set_arrhenius(Ea, A, k_max=1e12)
     u0 = np.zeros(1000); u0[0] = 1.0
-    T = np.array([1000.0, 1100.0])
-    t, u, ns, rcs, sts = h.solve_ensemble(kp(2e-3), np.tile(u0, (2, 1)), T=T)
+    T = np.linspace(1000.0, 1100.0, 32)                           # 32 members: below that the call goes to kin_solve on threads
+    t, u, ns, rcs, sts = h.solve_ensemble(kp(2e-3), np.tile(u0, (32, 1)), T=T)
     assert (rcs == 0).all() and sts[0]["lu_dense_dim"] > 100
-    for i in range(2):
+    assert all(q["lu_slots"] <= 64 for q in sts)                  # the resident kernel (a thread member: kin_solve, > 64 slots)
+    for i in (0, 31):
         h.rates_at(float(T[i]))
         ts, us, rc, st, _ = h.solve(kp(2e-3), u0)
         assert rc == 0 and st["lu_slots"] > 64                    # host-driven path
@@ -370,7 +398,12 @@ def test_lockstep_ensemble_of_a_large_network(monkeypatch):
     h.set_arrhenius(Ea, A, k_max=1e12)
     u0 = np.zeros(1000); u0[0] = 1.0
     T = np.array([950.0, 1050.0, 1150.0, 1250.0])
-    tr, ur, _, rcr, _ = h.solve_ensemble(kp(2e-3), np.tile(u0, (4, 1)), T=T)          # fits the resident kernel: one launch
+    # the resident kernel takes 1 000 species in one launch from 32 members on (fewer go to kin_solve on threads); its first four
+    # members are the four the lockstep rounds run below
+    T32 = np.concatenate([T, np.linspace(950.0, 1250.0, 28)])
+    tr, ur, _, rcr, str_ = h.solve_ensemble(kp(2e-3), np.tile(u0, (32, 1)), T=T32)
+    assert all(q["lu_slots"] <= 64 for q in str_)
+    tr, ur, rcr = tr, ur[:4], rcr[:4]
     monkeypatch.setenv("KIN_ENSEMBLE_BATCHED", "1")
     tb, ub, _, rcb, stb = h.solve_ensemble(kp(2e-3), np.tile(u0, (4, 1)), T=T)
     assert (rcr == 0).all() and (rcb == 0).all() and np.array_equal(tr, tb)

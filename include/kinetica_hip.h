@@ -341,6 +341,18 @@ int kin_rate_table_rows(kin_network* h, const int64_t* rows, int64_t n_rows, dou
  * through exactly the factorisation / substitution kernels kin_solve uses (what KLU does for
  * CVODE in the reference's documented setup, docs/src/getting-started.md:69). */
 int kin_newton_solve(kin_network* h, double c, const double* u, const double* b, double* x);
+/* Diagnostic: K Newton-matrix solves through the host-driven factorisation and solve kernels (kin_solve's path above the resident
+ * kernel's size, and every thread / lockstep ensemble), with the current rates and the handle's own analysis (the KIN_LU_EXPLICIT /
+ * KIN_LU_FUSED switches are read when that analysis first runs). Member i (arrays row-major): I - c[i] J(u[i]) is factorised into a
+ * slot of its own, x[i] = (I - c[i] J(u[i]))^-1 b[i]; bad[i] = 1 when a pivot of that factorisation vanished (the call still returns
+ * KIN_OK, x[i] is then meaningless). batched = 0: every dense Schur block is inverted by the single-matrix Gauss-Jordan chain, as in
+ * kin_solve; batched = 1: the dense blocks of up to 16 members at a time are inverted by ONE batched chain, as in the lockstep
+ * ensemble. info (8 + n_species entries): sparse rows ns, dense block size m, its padded size, elimination rounds, solve form
+ * (0 fused, 1 explicit, 2 round by round), Gauss-Jordan block steps (padded size / 32), whole-workgroup gather rows over all
+ * plans, longest gather row over all plans; then the species at dense positions 0 .. m-1. KIN_ERR_STATE without rates,
+ * KIN_ERR_INVALID_ARG for K < 1 or a null buffer. Added under KIN_ABI_VERSION 6: look the symbol up before calling it. */
+int kin_newton_probe(kin_network* h, int64_t K, int32_t batched, const double* u, const double* c, const double* b,
+                     double* x, int32_t* bad, int64_t* info);
 /* Diagnostic: the resident integrator's own phases (one workgroup per trajectory, kin_solve's path for small networks and every
  * one-launch ensemble), run once for K members in one launch with the current rates. Member m (arrays row-major, m-th row):
  * du[m] = f(u[m]); jac[m] = J(u[m]) in kin_jac_pattern order; x[m] = (I - c[m] J(u[m]))^-1 b[m] through the kernel's
@@ -362,7 +374,7 @@ const char* kin_version(void);
  * struct sizes) with the values it was written against before the first call: kin_params / kin_stats have grown between
  * versions (1: round 1; 2: + dtmin and the LU-cache counters; 3: + the library-order sweep entry points; 4: + kin_solve_ensemble,
  * kin_lu_analyze_host - structs unchanged; 5: + kin_rhs_batched_klib_dev - structs unchanged; 6: + kin_solve_ensemble_continuous -
- * structs unchanged; kin_solve_ensemble_discrete and kin_resident_probe came later under 6, found by symbol lookup). */
+ * structs unchanged; kin_solve_ensemble_discrete, kin_resident_probe and kin_newton_probe came later under 6, found by symbol lookup). */
 #define KIN_ABI_VERSION 6
 int kin_abi_version(void);
 int64_t kin_struct_size(int which); /* 0: sizeof(kin_params), 1: sizeof(kin_stats), else -1 */

@@ -30,7 +30,7 @@ SYMBOLS = [
     "kin_lib_layout", "kin_lib_layout_host", "kin_states_to_lib_dev", "kin_states_from_lib_dev", "kin_rates_to_lib_dev", "kin_rate_table_lib_dev",
     "kin_rhs_tiled_dev", "kin_rhs_batched_T_dev", "kin_rhs_batched_klib_dev", "kin_abi_version", "kin_struct_size",
     "kin_solve_ensemble", "kin_lu_analyze_host", "kin_solve_ensemble_continuous", "kin_solve_ensemble_discrete",
-    "kin_resident_probe",
+    "kin_resident_probe", "kin_newton_probe",
 ]
 ABI_VERSION = 6   # include/kinetica_hip.h: KIN_ABI_VERSION this binding was written against
 
@@ -116,6 +116,8 @@ def lib():
                                                       POINTER(c_int32), POINTER(KinStats)]
         if hasattr(L, "kin_resident_probe"):   # (also under ABI 6)
             L.kin_resident_probe.argtypes = [c_void_p, c_int64, PD, PD, PD, PD, PD, PD, POINTER(c_int32), P64]
+        if hasattr(L, "kin_newton_probe"):   # (also under ABI 6)
+            L.kin_newton_probe.argtypes = [c_void_p, c_int64, c_int32, PD, PD, PD, PD, POINTER(c_int32), P64]
         L.kin_solve_ensemble.argtypes = [c_void_p, POINTER(KinParams), c_int64, PD, PD, PD, PD, PD, PD, c_int64, P64, PD, PD, P64,
                                          POINTER(c_int32), POINTER(KinStats)]
         L.kin_integrator_init.argtypes = [c_void_p, POINTER(KinParams), PD, PD, PD, PD, c_int64]
@@ -520,6 +522,25 @@ class HipNetwork:
         inf = {k: int(v) for k, v in zip(keys, info[:7])}
         inf["dense_species"] = info[8:8 + m].copy()
         return dict(du=du, jac=jac[:, :nnz.value], x=x, bad=bad, info=inf)
+
+    def newton_probe(self, u, c, b, batched=False):
+        """K Newton-matrix solves through the host-driven factorisation and solve kernels (diagnostic, kin_newton_probe). u, b:
+        (K, N) or (N,); c: (K,) or scalar; batched: the dense inverses of up to 16 members as one batched Gauss-Jordan chain.
+        Returns dict(x: (K, N); bad: (K,) int; info: dict of ns, m, mpad, rounds, solve_form, gj_steps, long_rows, max_row,
+        dense_species)."""
+        u = np.atleast_2d(_f64(u)); b = np.atleast_2d(_f64(b))
+        K = u.shape[0]
+        c = _f64(np.broadcast_to(np.asarray(c, dtype=np.float64), (K,)))
+        assert u.shape == (K, self.n) and b.shape == (K, self.n)
+        x = np.empty((K, self.n))
+        bad = np.zeros(K, np.int32)
+        info = np.zeros(8 + self.n, np.int64)
+        self._chk(lib().kin_newton_probe(self._h, K, 1 if batched else 0, _pd(u), _pd(c), _pd(b), _pd(x),
+                                         bad.ctypes.data_as(POINTER(c_int32)), _p64(info)))
+        keys = ("ns", "m", "mpad", "rounds", "solve_form", "gj_steps", "long_rows", "max_row")
+        inf = {k: int(v) for k, v in zip(keys, info[:8])}
+        inf["dense_species"] = info[8:8 + inf["m"]].copy()
+        return dict(x=x, bad=bad, info=inf)
 
     def solution_max_dev(self, d_out):
         """kin_solution_max into a device buffer (pointer as int) of N doubles."""

@@ -552,6 +552,17 @@ int kin_newton_solve(kin_network* h, double c, const double* u, const double* b,
   KIN_CATCH(h)
 }
 
+int kin_newton_probe(kin_network* h, int64_t K, int32_t batched, const double* u, const double* c, const double* b,
+                     double* x, int32_t* bad, int64_t* info) {
+  if (!h) return KIN_ERR_INVALID_ARG;
+  KIN_TRY(h)
+  require(K >= 1 && K <= (1 << 20), ERR_INVALID_ARG, "K outside 1 .. 2^20");
+  require(u && c && b && x && bad && info, ERR_INVALID_ARG, "null buffer");
+  require(h->has_rates, ERR_STATE, "rates were never set");
+  newton_probe(h, K, batched, u, c, b, x, bad, info);
+  KIN_CATCH(h)
+}
+
 int kin_resident_probe(kin_network* h, int64_t K, const double* u, const double* c, const double* b, double* du, double* jac,
                        double* x, int32_t* bad, int64_t* info) {
   if (!h) return KIN_ERR_INVALID_ARG;

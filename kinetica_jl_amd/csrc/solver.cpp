@@ -1457,6 +1457,88 @@ void newton_solve(kin_network* h, double c, const double* u, const double* b, do
   for (int i = 0; i < N; i++) x[i] = tail[xl[i] - S.lu.off_y];
 }
 
+// Diagnostic counterpart of resident_probe for the host-driven path: K Newton-matrix solves through the solver's own analysis
+// and the product kernels, each member factorised into a slot of its own with a flag word of its own. batched == 0: every member
+// through factor_into (launch_gauss_jordan), as kin_solve does; batched == 1: the sparse part per member, then ONE
+// launch_gauss_jordan_batched chain over the dense blocks of up to GJ_BMAX members, as the lockstep ensemble's server does.
+void newton_probe(kin_network* h, int64_t K, int32_t batched, const double* u, const double* c, const double* b, double* x,
+                  int32_t* bad, int64_t* info) {
+  if (!h->solver) h->solver.reset(new Solver(h));
+  Solver& S = *h->solver;
+  SparseLU& lu = S.lu;
+  hipStream_t s = h->stream;
+  const int N = S.N;
+  S.flush_accept();
+  S.spec = Solver::Spec{};
+  const int G = (int)std::min<int64_t>(K, GJ_BMAX);
+  lu.ensure_slots(G, s);
+  DevBuf<int> d_bad;                        // one flag word per member
+  d_bad.alloc((size_t)K);
+  d_bad.zero(s);
+  DevBuf<double> gpinv;                     // pivot scratch of a batched chain (2 x 32 x 32 doubles per matrix)
+  if (batched) gpinv.alloc((size_t)GJ_BMAX * 2 * 32 * 32);
+  std::vector<int32_t> yl(N), xl(N);
+  lu.yloc.download(yl.data(), N, s);
+  lu.xloc.download(xl.data(), N, s);
+  KIN_HIP(hipStreamSynchronize(s));
+  const size_t tail_n = (size_t)(lu.off_x + lu.mpad + 8 - lu.off_y);   // the solve vectors only
+  std::vector<double> tails((size_t)G * tail_n);
+  for (int64_t g0 = 0; g0 < K; g0 += G) {
+    const int n = (int)std::min<int64_t>(G, K - g0);
+    double* Sp[GJ_BMAX]; double* S2p[GJ_BMAX]; int* badp[GJ_BMAX];
+    for (int i = 0; i < n; i++) {
+      const int64_t t = g0 + i;
+      SparseLU::Slot& q = lu.slots[i];
+      S.y.upload(u + t * N, N, s);
+      S.eval_jac(S.y.p);
+      if (batched) lu.factor_sparse_into(c[t], S.jv.p, q, d_bad.p + t, s);
+      else lu.factor_into(c[t], S.jv.p, q, lu.pinv.p, d_bad.p + t, s);
+      Sp[i] = q.W.p + lu.off_S; S2p[i] = q.S2.p; badp[i] = d_bad.p + t;
+    }
+    if (batched && lu.m > 0) {
+      const int where = launch_gauss_jordan_batched(n, Sp, S2p, lu.mpad, gpinv.p, badp, s);
+      for (int i = 0; i < n; i++) lu.slots[i].sinv = where ? S2p[i] : Sp[i];
+    }
+    std::fill(tails.begin(), tails.end(), 0.0);
+    for (int i = 0; i < n; i++) {
+      double* tail = tails.data() + (size_t)i * tail_n;
+      for (int v = 0; v < N; v++) tail[yl[v] - lu.off_y] = b[(g0 + i) * N + v];
+      KIN_HIP(hipMemcpyAsync(lu.slots[i].W.p + lu.off_y, tail, tail_n * sizeof(double), hipMemcpyHostToDevice, s));
+      lu.solve(nullptr, i, s);
+      KIN_HIP(hipMemcpyAsync(tail, lu.slots[i].W.p + lu.off_y, tail_n * sizeof(double), hipMemcpyDeviceToHost, s));
+    }
+    KIN_HIP(hipStreamSynchronize(s));
+    for (int i = 0; i < n; i++)
+      for (int v = 0; v < N; v++) x[(g0 + i) * N + v] = tails[(size_t)i * tail_n + (xl[v] - lu.off_y)];
+  }
+  std::vector<int> hb((size_t)K);
+  d_bad.download(hb.data(), (size_t)K, s);
+  d_bad.zero(s);
+  KIN_HIP(hipStreamSynchronize(s));
+  for (int64_t t = 0; t < K; t++) bad[t] = hb[t] ? 1 : 0;
+  S.cur_slot = 0;
+  S.invalidate_lu();
+  info[0] = lu.ns; info[1] = lu.m; info[2] = lu.mpad; info[3] = lu.nrounds;
+  info[4] = lu.fused_tri ? 0 : lu.explicit_tri ? 1 : 2;
+  // whole-workgroup rows and the longest row over every gather plan of the analysis, read back from the plans on the device
+  int64_t long_rows = 0, max_row = 0;
+  auto scan = [&](const SegPlanDev& p) {
+    std::vector<int32_t> off((size_t)p.G + 1), sb((size_t)p.S), se((size_t)p.S), bb((size_t)p.B), be((size_t)p.B);
+    if (p.G > 0) p.grp_off.download(off.data(), off.size(), s);
+    p.seg_beg.download(sb.data(), sb.size(), s); p.seg_end.download(se.data(), se.size(), s);
+    p.blk_beg.download(bb.data(), bb.size(), s); p.blk_end.download(be.data(), be.size(), s);
+    KIN_HIP(hipStreamSynchronize(s));
+    for (int g = 0; g < p.G; g++) max_row = std::max<int64_t>(max_row, off[g + 1] - off[g]);
+    for (int q = 0; q < p.S; q++) max_row = std::max<int64_t>(max_row, se[q] - sb[q]);
+    for (int q = 0; q < p.B; q++) max_row = std::max<int64_t>(max_row, be[q] - bb[q]);
+    long_rows += p.B;
+  };
+  for (const auto* v : {&lu.schur, &lu.fwd, &lu.bwd}) for (const SegPlanDev& p : *v) scan(p);
+  for (const SegPlanDev* p : {&lu.fwd_dense, &lu.fwdZ, &lu.bwdT, &lu.bwdV, &lu.lz_build, &lu.nvu_build, &lu.stageA, &lu.stageC}) scan(*p);
+  info[5] = lu.mpad / 32; info[6] = long_rows; info[7] = max_row;
+  for (int32_t j = 0; j < lu.m; j++) info[8 + j] = lu.perm[lu.ns + j];
+}
+
 }  // namespace kin
 
 kin_network::kin_network() {}

@@ -79,5 +79,9 @@ void validate_solve(kin_network* h, const kin_params& p, const double* tstops, c
 void solution_max(kin_network* h, double* out_umax);
 // diagnostic: (I - c J(u)) x = b through the solver's LU
 void newton_solve(kin_network* h, double c, const double* u, const double* b, double* x);
+// diagnostic: K such solves through the product kernels, each member with a slot and a pivot flag of its own; batched: the dense
+// inverses of up to GJ_BMAX members as one launch_gauss_jordan_batched chain (kin_newton_probe)
+void newton_probe(kin_network* h, int64_t K, int32_t batched, const double* u, const double* c, const double* b, double* x,
+                  int32_t* bad, int64_t* info);
 
 }  // namespace kin

@@ -9,15 +9,15 @@ module (pytest -s)."""
 import numpy as np
 import pytest
 import scipy.sparse as sp
-import scipy.sparse.linalg as spl
 
 from kinetica_jl_amd import capi
 from kinetica_jl_amd.synth import from_lists, synthetic_crn
 from oracle import oracle as orc
+from tests.linalg_cases import (C_VALUES, SYNTH_COND, SYNTH_U, core_net, dense_pivot_net as _dense_pivot_net, record, solve_errors,
+                                static_handle, with_special_stoichiometries)
 
 pytestmark = pytest.mark.gpu
 
-C_VALUES = (1e-12, 1e-8, 1e-5, 1e-3)
 MEASURED = {}
 
 
@@ -30,39 +30,6 @@ def _report():
             print(f"  {case:40s} rhs {v[0]:.2e}  jac {v[1]:.2e}  bwd {v[2]:.2e}  fwd {v[3]:.2e}")
 
 
-def core_net(q, n_chain=3):
-    """A core of q species that the symbolic analysis never eliminates (each has more than 8 non-hub neighbours: all pairs for
-    q <= 20, else neighbours i +- 1 .. 5), reversible unimolecular reactions between neighbours, and sparse chains hanging off it
-    (prev -> c, 2 c -> prev: the 2A Jacobian term). The dense Schur block is the core in ascending species order (m = q)."""
-    reacs, prods = [], []
-    pairs = [(i, j) for i in range(q) for j in range(i + 1, q)] if q <= 20 else [(i, (i + o) % q) for i in range(q) for o in range(1, 6)]
-    for i, j in pairs:
-        reacs += [[(i, 1)], [(j, 1)]]; prods += [[(j, 1)], [(i, 1)]]
-    n = q
-    for i in range(0, q, max(1, q // 12)):
-        prev = i
-        for _ in range(n_chain):
-            reacs += [[(prev, 1)], [(n, 2)]]; prods += [[(n, 1)], [(prev, 1)]]
-            prev = n; n += 1
-    return from_lists(n, reacs, prods)
-
-
-def with_special_stoichiometries(net):
-    """net plus 2A -> B, A -> 2B, A + C -> B + C (inert collider C) and B -> A + B (a product that is also a reactant)."""
-    rs = [net.reaction(r) for r in range(net.n_reactions)]
-    extra = [([(0, 2)], [(1, 1)]), ([(0, 1)], [(1, 2)]), ([(0, 1), (2, 1)], [(1, 1), (2, 1)]), ([(1, 1)], [(0, 1), (1, 1)])]
-    return from_lists(net.n_species, [r for r, _ in rs] + [r for r, _ in extra], [p for _, p in rs] + [p for _, p in extra])
-
-
-def residual_ld(M, x, b):
-    """M x - b with every product and sum in extended precision (np.longdouble)."""
-    M = M.tocsr()
-    prod = M.data.astype(np.longdouble) * x[M.indices].astype(np.longdouble)
-    r = np.zeros(M.shape[0], np.longdouble)
-    np.add.at(r, np.repeat(np.arange(M.shape[0]), np.diff(M.indptr)), prod)
-    return r - b.astype(np.longdouble)
-
-
 def check_member(h, on, k, u, c, b, out, i, case, fwd_cond_max=None):
     """member i of a probe against the references; returns (rhs, jac, backward, forward) errors. fwd_cond_max: the forward error
     is bounded only where cond(M) is at most this (the backward error always)."""
@@ -73,13 +40,8 @@ def check_member(h, on, k, u, c, b, out, i, case, fwd_cond_max=None):
     Jo = on.jac(k, u)
     e_jac = float(abs(Jd - Jo).max() / abs(Jo).max())
     M = (sp.identity(n, format="csr") - c * Jo).tocsr()
-    x = out["x"][i]
-    r = residual_ld(M, x, b)
-    e_bwd = float(np.max(np.abs(r))) / (float(np.max(abs(M) @ np.abs(x))) + float(np.max(np.abs(b))))
-    xr = spl.splu(M.tocsc()).solve(b)
-    e_fwd = float(np.max(np.abs(x - xr)) / np.max(np.abs(xr)))
-    prev = MEASURED.get(case, (0.0, 0.0, 0.0, 0.0))
-    MEASURED[case] = tuple(max(a, bb) for a, bb in zip(prev, (e_rhs, e_jac, e_bwd, e_fwd)))
+    e_bwd, e_fwd = solve_errors(M, out["x"][i], b)
+    record(MEASURED, case, (e_rhs, e_jac, e_bwd, e_fwd))
     assert e_rhs < 1e-13, (case, c, e_rhs)
     assert e_jac < 1e-13, (case, c, e_jac)
     assert e_bwd < 1e-13, (case, c, e_bwd)
@@ -100,26 +62,11 @@ def probe_all_c(h, on, k, u_rng, n, case, cs=C_VALUES, u_decades=(-4, 0), fwd_co
     return out
 
 
-def static_handle(net, seed, lo=0.0, hi=4.0):
-    k = 10.0 ** np.random.default_rng(seed).uniform(lo, hi, net.n_reactions)
-    h = capi.HipNetwork.from_flat(net)
-    h.set_rates(k)
-    return h, orc.OracleNetwork.from_flat(net), k
-
-
 def look_ahead(nb):
     """gj_blocked: the last wavefront forms and inverts the next pivot block when the strips spread over 7 wavefronts in as many
     rounds as over 8"""
     return (nb + 6) // 7 == (nb + 7) // 8
 
-
-# Synthetic networks at 1000 K (rate constants up to k_max = 1e12) take the states of the host path's test
-# (test_gpu_boundary_r2.py: test_newton_matrix_solve_against_sparse_direct), 1e-8 .. 1e-2. At c = 1e-3 their Newton matrices
-# have condition numbers of 1e11 .. 5e12: there the kernel (static diagonal pivoting, explicit inverses) differed from SuperLU by
-# up to 5.7e-8 of max|x| at backward errors below 1e-13 (LAPACK's pivoted dense solve differs from SuperLU by up to 6e-10 on the
-# same matrices). The forward bound of 1e-9 holds for these networks where cond(M) <= 1e10; the backward bound everywhere.
-SYNTH_U = (-8, -2)
-SYNTH_COND = 1e10
 
 # m: every nb from 1 to 9, nb = 15, 16, 17, 23 and the RES_MAX_DENSE end; m % 16 in {0, 1, 15} throughout. nb = 8, 15, 16, 23, 32
 # run the Gauss-Jordan without look-ahead, odd nb copy the inverse back from the scratch block, m > 128 takes the 16-lane GEMV.
@@ -252,18 +199,6 @@ def test_vanished_pivot_of_the_autocatalytic_pair(order, c_sing, where):
     assert out["bad"][0] == 1 and out["bad"][1] == 0
     check_member(h, orc.OracleNetwork.from_flat(net), k, u, 0.125, rhs, out, 1, f"pair {where} c=0.125")
     h.close()
-
-
-def _dense_pivot_net(q, p):
-    """core_net(q) with weak coupling everywhere and A_p + B -> 2 A_p on the species at dense position p (B: a new species): the
-    Schur pivot of A_p is (1 + c k (u_A - u_B)) / (1 + c k u_A) up to the weak terms, zero at c* = 1 / (k (u_B - u_A))"""
-    base = core_net(q)
-    B = base.n_species
-    rs = [base.reaction(r) for r in range(base.n_reactions)]
-    net = from_lists(B + 1, [r for r, _ in rs] + [[(p, 1), (B, 1)]], [pp for _, pp in rs] + [[(p, 2)]])
-    k = np.full(net.n_reactions, 1e-12); k[-1] = 1.0
-    u = np.full(net.n_species, 0.1); u[p] = 0.5; u[B] = 2.0
-    return net, k, u, 1.0 / (1.0 * (2.0 - 0.5))
 
 
 @pytest.mark.parametrize("q,p", [(48, 37), (128, 117)], ids=["look_ahead_nb3", "no_look_ahead_nb8"])

@@ -120,9 +120,7 @@ struct EnsembleSolver {
     const NetworkHost& H = h->host;
     hipStream_t s = h->stream;
     N = (int)H.N; R = (int)H.R; nnz = H.nnz();
-    LUOptions opt;
-    if (N >= 4000) { opt.max_tail_degree = 32; opt.max_rounds = 16; opt.max_degree = 400; }   // as Solver (solver.cpp)
-    lu.analyze(N, H.j_ptr, H.j_col, opt, s);
+    lu.analyze(N, H.j_ptr, H.j_col, lu_options_for(N), s);
     lu.slots.clear();
     if (!(lu.fused_tri && lu.m > 0)) { why = "the batched ensemble needs the fused solve form (a network with a dense Schur block)"; return; }
     std::vector<int32_t> yl(N), ident(N);
@@ -134,12 +132,7 @@ struct EnsembleSolver {
     T.N = N; T.R = R; T.m = lu.m; T.mpad = lu.mpad; T.ns = lu.ns; T.off_y = lu.off_y; T.off_x = lu.off_x;
     T.x0 = h->x0.p; T.x1 = h->x1.p; T.xloc = lu.xloc.p; T.x2_species = lu.x2_species.p;
     T.resid = resid_plan.view(); T.stageA = lu.stageA.view(); T.stageC = lu.stageC.view();
-    const double KAPPA[6] = {0.0, -0.1850, -1.0 / 9.0, -0.0823, -0.0415, 0.0};
-    T.cf.gamma[0] = 0.0;
-    for (int j = 1; j <= BDF_MAX_ORDER; j++) T.cf.gamma[j] = T.cf.gamma[j - 1] + 1.0 / j;
-    for (int j = 0; j <= BDF_MAX_ORDER; j++) T.cf.alpha[j] = (1.0 - KAPPA[j]) * T.cf.gamma[j];
-    for (int j = 0; j <= BDF_MAX_ORDER; j++) T.cf.error_const[j] = KAPPA[j] * T.cf.gamma[j] + 1.0 / (j + 1);
-    T.cf.error_const[BDF_MAX_ORDER + 1] = 0.0;
+    bdf_fill_coef(T.cf.gamma, T.cf.alpha, T.cf.error_const);
     ok = true;
   }
   ~EnsembleSolver() {
@@ -280,11 +273,8 @@ struct EnsembleSolver {
       bool any_drift = false;
       for (int t = 0; t < K; t++) {
         Pending& p = pend[t];
-        if (p.kind == K_DRIFT) {
-          SlotDriftArgs a;
-          const int ns = (int)slots[t].size();
-          for (int i = 0; i < ns; i++) { a.jd[i] = slots[t][i].valid ? slots[t][i].jd.p : nullptr; a.c[i] = slots[t][i].c_fact; }
-          launch_slot_drift(N, ns, reps[t].jv, d_jdiag.p, a, d_drift.p + (size_t)t * LU_MAX_SLOTS, s);
+        if (p.kind == K_DRIFT) {   // (the results of all members come back in one copy below)
+          launch_drift_test(N, slots[t], reps[t].jv, d_jdiag.p, d_drift.p + (size_t)t * LU_MAX_SLOTS, nullptr, s);
           any_drift = true;
         }
       }
@@ -313,11 +303,7 @@ struct EnsembleSolver {
       for (int t = 0; t < K; t++) {
         Pending& p = pend[t];
         if (p.kind == K_NONE) continue;
-        if (p.kind == K_DRIFT) {
-          p.dropped = 0;
-          for (int i = 0; i < (int)slots[t].size(); i++)
-            if (slots[t][i].valid && !(h_drift[(size_t)t * LU_MAX_SLOTS + i] <= p.max_drift)) { slots[t][i].valid = false; p.dropped++; }
-        }
+        if (p.kind == K_DRIFT) p.dropped = drop_drifted(slots[t], (int)slots[t].size(), h_drift + (size_t)t * LU_MAX_SLOTS, p.max_drift);
         ctrl_of[t] = h_ctrl[t];
         results[t] = p;
         done[t] = 1;
@@ -514,20 +500,11 @@ struct MemberBackend {
   }
   void slots_invalidate(bool reset) { for (auto& q : sl()) { q.valid = false; if (reset) { q.c_fact = 0.0; q.last_use = 0; } } }
   int nearest_slot(double c, double band, long long n_restarts, long long max_age) const {
-    int best = -1; double bd = 1e300;
-    for (int i = 0; i < (int)sl().size(); i++) {
-      const SparseLU::Slot& q = sl()[i];
-      if (!q.valid || n_restarts - q.jac_stamp > max_age) continue;
-      const double r = std::fabs(std::log(c / q.c_fact));
-      if (r < bd && std::fabs(c / q.c_fact - 1.0) <= band) { bd = r; best = i; }
-    }
-    return best;
+    return slot_nearest(sl().data(), (int)sl().size(), c, band, n_restarts, max_age);
   }
   int victim_slot(long long n_restarts, long long max_age, int n_slots) const {
-    for (int i = 0; i < n_slots; i++) if (!sl()[i].valid || n_restarts - sl()[i].jac_stamp > max_age) return i;
-    int v = 0;
-    for (int i = 1; i < n_slots; i++) if (sl()[i].last_use < sl()[v].last_use) v = i;
-    return v;
+    const int free_ = slot_first_free(sl().data(), n_slots, n_restarts, max_age);
+    return free_ >= 0 ? free_ : slot_lru(sl().data(), n_slots);
   }
 
   // ---- vectors

@@ -712,4 +712,21 @@ void SparseLU::solve(const int* skip, int slot, hipStream_t s) {
   for (int r = nrounds - 1; r >= 0; r--) launch_segsum(bwd[r].view(), SEG_PROD_SUB_DIV, W, W, ex, s);
 }
 
+int launch_drift_test(int N, const std::vector<SparseLU::Slot>& slots, const double* jv, const int32_t* j_diag, double* d_out,
+                      double* h_out, hipStream_t s) {
+  SlotDriftArgs a;
+  const int n = (int)slots.size();
+  for (int i = 0; i < n; i++) { a.jd[i] = slots[i].valid ? slots[i].jd.p : nullptr; a.c[i] = slots[i].c_fact; }
+  launch_slot_drift(N, n, jv, j_diag, a, d_out, s);
+  if (h_out) KIN_HIP(hipMemcpyAsync(h_out, d_out, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
+  return n;
+}
+
+int drop_drifted(std::vector<SparseLU::Slot>& slots, int n, const double* h_drift, double max_drift) {
+  int dropped = 0;
+  for (int i = 0; i < n; i++)
+    if (slots[i].valid && !(h_drift[i] <= max_drift)) { slots[i].valid = false; dropped++; }
+  return dropped;
+}
+
 }  // namespace kin

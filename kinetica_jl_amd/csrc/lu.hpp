@@ -37,6 +37,15 @@ struct LUOptions {
   int min_round = 8;         // a round with fewer pivots than this ends the sparse elimination (it no longer pays for its two
                              // dependent launches; inside the resident integrator a round is two barriers, and 2 is enough)
 };
+// The options the integrators analyse an N-species network with. Larger networks: eliminate more of the tail sparsely (more
+// rounds, more fill allowed) - every Gauss-Jordan step moves the whole dense block, so its dimension dominates there (C5:
+// 3870 -> 3126, solve -32 %; C3: 1173 -> 981, -10 %); small networks keep few rounds, their cost is the number of dependent
+// launches (C2: the loose setting is 15 % slower). Measured with tools/c5_lu_params.py and bench.py.
+inline LUOptions lu_options_for(int N) {
+  LUOptions opt;
+  if (N >= 4000) { opt.max_tail_degree = 32; opt.max_rounds = 16; opt.max_degree = 400; }
+  return opt;
+}
 
 struct SparseLU {
   // structure (new = elimination order, old = species index)
@@ -132,6 +141,14 @@ struct SparseLU {
   int newton_grid() const { return stagec_newton_grid(stageC.view(), m); }   // workgroups of that last launch
   DevBuf<int32_t> x2_species;               // species behind the dense block's rows
 };
+
+// Drift guard of the LU cache: launches the drift test (launch_slot_drift) of every slot of `slots` against today's Jacobian
+// values jv into d_out[slot]; with h_out, also enqueues the copy of those results to the host. Returns the number of slots
+// tested. After the stream has been waited for, drop_drifted() invalidates the first n slots whose result exceeds max_drift
+// (or is not a number) and returns how many it dropped.
+int launch_drift_test(int N, const std::vector<SparseLU::Slot>& slots, const double* jv, const int32_t* j_diag, double* d_out,
+                      double* h_out, hipStream_t s);
+int drop_drifted(std::vector<SparseLU::Slot>& slots, int n, const double* h_drift, double max_drift);
 
 // dense / LU helper kernels (solver_kernels.hip)
 void launch_lu_assemble(int64_t nnzJ, const int32_t* jmap, const double* jvals, double c, double* W,

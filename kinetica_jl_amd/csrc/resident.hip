@@ -915,8 +915,8 @@ struct DevBackend {
     if (reset) { g_sl.c_fact[lane()] = 0.0; g_sl.last_use[lane()] = 0; g_sl.crate[lane()] = 1.0; g_sl.crate_step[lane()] = 0; g_sl.crate_restart[lane()] = -1;
                  g_sl.jac_stamp[lane()] = 0; g_sl.step_stamp[lane()] = 0; }
   }
-  // slot whose c_fact is closest (in ratio) to c and within the band, lowest index on ties; -1: none (Solver::nearest_slot).
-  // step_age >= 0 (continuous rates): only slots whose Jacobian is at most step_age accepted steps old
+  // slot whose c_fact is closest (in ratio) to c and within the band, lowest index on ties; -1: none - the rule of slot_nearest
+  // (bdf_rules.hpp), one slot per lane. step_age >= 0 (continuous rates): only slots whose Jacobian is at most step_age accepted steps old
   __device__ int nearest_slot(double c, double band, long long n_restarts, long long max_age, long long n_steps = 0, long long step_age = -1) const {
     const double cf = g_sl.c_fact[lane()];
     const bool ok = lane() < g_cx.n_slots && g_sl.valid[lane()] && n_restarts - g_sl.jac_stamp[lane()] <= max_age && fabs(c / cf - 1.0) <= band &&
@@ -932,7 +932,8 @@ struct DevBackend {
     }
     return r < 1e300 ? idx : -1;
   }
-  // a slot for a new factorisation: the first unused or expired one, else the least recently used (Solver::victim_slot)
+  // a slot for a new factorisation: the first unused or expired one, else the least recently used (bdf_rules.hpp: slot_first_free,
+  // slot_lru - one slot per lane here)
   __device__ int victim_slot(long long n_restarts, long long max_age, int n_slots) const {
     const bool in = lane() < n_slots;
     const bool free_ = in && (!g_sl.valid[lane()] || n_restarts - g_sl.jac_stamp[lane()] > max_age);

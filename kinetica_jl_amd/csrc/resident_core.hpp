@@ -19,34 +19,19 @@
 #include <cmath>
 #include <cstdint>
 
-#if defined(__HIPCC__)
-#define KIN_HD __host__ __device__
-#else
-#define KIN_HD
-#endif
+#include "bdf_rules.hpp"
 
 namespace kin {
 
-constexpr int RES_MAX_ORDER = 5;
-constexpr int RES_NEWTON_MAXITER = 4;
-constexpr int RES_D_ROWS = RES_MAX_ORDER + 3;
+// (the scalar rules and their constants: bdf_rules.hpp)
+constexpr int RES_MAX_ORDER = BDF_MAX_ORDER;
+constexpr int RES_NEWTON_MAXITER = BDF_NEWTON_MAXITER;
+constexpr int RES_D_ROWS = BDF_D_ROWS;
 constexpr int RES_MAX_SLOTS = 64;   // one LU-cache slot per lane of a wavefront (resident.hip keeps the slot table in registers)
 
 enum : int { RES_RET_SUCCESS = 0, RES_RET_MAXITERS = 1, RES_RET_DTLESSTHANMIN = 2, RES_RET_UNSTABLE = 3 };   // = KIN_RETCODE_*
 
-// corrector tolerance as a fraction of the error weight: solver_kernels.hpp bdf_newton_frac has the rule and its measurements
-KIN_HD inline double res_newton_frac(double rtol) { return fmin(0.1, fmax(0.03, 1e-10 / rtol)); }
-
 // what a solve needs besides the network (plain data; pointers are device pointers in the product, host pointers in the test)
-// largest power of ten <= h by exact IEEE operations only (solver.cpp: decade_floor)
-KIN_HD inline double res_decade_floor(double h) {
-  if (!(h > 0.0) || !(h < 1e300)) return h;
-  double p = 1.0;
-  while (p > h) p /= 10.0;
-  while (p * 10.0 <= h) p *= 10.0;
-  return p;
-}
-
 struct ResParams {
   double tspan0, tspan1, abstol, reltol, chunkstep, dtmin;
   int32_t solve_chunks, adaptive_tols, ban_negatives, save_hits_end;
@@ -91,9 +76,6 @@ KIN_HD inline double res_T_of(const double* tn, const double* Tn, int64_t n, dou
 // temperature. Backends without it (the CPU replay of tests/native/resident_host.cpp) compile as before and never run mode 3.
 template <class B, class = void> struct ResHasApplyT { static constexpr bool value = false; };
 template <class B> struct ResHasApplyT<B, decltype((void)static_cast<B*>(nullptr)->apply_T(0.0))> { static constexpr bool value = true; };
-// continuous rate updates: the Jacobian behind a reused LU-cache slot is at most this many accepted steps old (CVODE's bound;
-// solver.cpp: Solver::nearest_slot, oracle/bdf.py: _nearest_slot)
-constexpr int64_t RES_CONT_JAC_AGE = 50;
 
 struct ResStats {
   int64_t n_steps, n_rejected, n_rhs, n_jac, n_factor, n_linsolve, n_newton_fail, n_chunks, n_restarts, n_retries,
@@ -112,18 +94,13 @@ struct ResResult {
 struct ResNorms { double d0, d1, d2, dmax; int nonfinite; };
 struct ResSums { double s, se, sm, sp, neg; };   // update, error test of order / order - 1 / order + 1, negative entries
 
-KIN_HD inline double res_inf() { return HUGE_VAL; }
-// spacing of the doubles above x (x >= 0, finite): what std::nextafter(x, inf) - x gives on the host
-KIN_HD inline double res_ulp_above(double x) { return nextafter(x, res_inf()) - x; }
-
 // one corrector attempt: what the controller hands to the backend, and what it gets back
 struct ResCorrIn {
   int32_t slot, order;
   double c, upd, rate_max, crate0, tol_first, newton_tol, dy_first_max, ec, ec_m, ec_p, atol, rtol, alpha_o;
 };
 struct ResAttempt { bool done, converged, nonfinite, any_negative, deep_negative; int n_iter; double err, err_m, err_p, crate; };
-// solver_kernels.hpp BDF_NEG_DEEP / BDF_NEG_MARK: an accepted step with a species below -1e3 error weights ends the segment
-constexpr double RES_NEG_DEEP = 1e3, RES_NEG_MARK = 4294967296.0;
+constexpr double RES_NEG_DEEP = BDF_NEG_DEEP, RES_NEG_MARK = BDF_NEG_MARK;
 
 // Predictor + corrector iterations until decided: the decisions of newton_decide (solver_kernels.hip), taken in sequence.
 // `I` supplies predict_inner / newton_iter_inner (the CPU replay: the backend itself; the device: the phase's own inlined
@@ -186,48 +163,21 @@ struct ResidentBdf {
   ResStats st;
 
   KIN_HD ResidentBdf(B& bb, const ResParams& pp) : b(bb), P(pp) {
-    const double KAPPA[6] = {0.0, -0.1850, -1.0 / 9.0, -0.0823, -0.0415, 0.0};
-    gamma[0] = 0.0;
-    for (int j = 1; j <= RES_MAX_ORDER; j++) gamma[j] = gamma[j - 1] + 1.0 / j;
-    for (int j = 0; j <= RES_MAX_ORDER; j++) alpha[j] = (1.0 - KAPPA[j]) * gamma[j];
-    for (int j = 0; j <= RES_MAX_ORDER; j++) errc[j] = KAPPA[j] * gamma[j] + 1.0 / (j + 1);
-    errc[RES_MAX_ORDER + 1] = 0.0;
+    bdf_fill_coef(gamma, alpha, errc);
     st = ResStats{};
   }
 
   KIN_HD void set_tols(double a, double r) {
     atol = a; rtol = r;
-    const double lo = 10.0 * 2.220446049250313e-16 / r;
-    const double frac = P.newton_frac > 0.0 ? P.newton_frac : res_newton_frac(r);
-    newton_tol = lo > frac ? lo : frac;
+    newton_tol = bdf_newton_tol(r, P.newton_frac);
   }
 
   // work matrices of change_D: MEMBERS, not locals - on the device the controller object lives in LDS, dynamically indexed
   // local arrays would live in scratch (= global memory: a dependent store / load pair there costs microseconds)
   double wM[6][6], wR[6][6], wU[6][6], wRU[6][6], wp[RES_MAX_ORDER + 1];
-  KIN_HD void compute_R(int ord, double factor, double R[6][6]) {
-    double (&M)[6][6] = wM;
-    for (int i = 0; i <= ord; i++)
-      for (int j = 0; j <= ord; j++) M[i][j] = 0.0;
-    for (int j = 0; j <= ord; j++) M[0][j] = 1.0;
-    for (int i = 1; i <= ord; i++)
-      for (int j = 1; j <= ord; j++) M[i][j] = ((double)i - 1.0 - factor * (double)j) / (double)i;
-    for (int j = 0; j <= ord; j++) {
-      double p = 1.0;
-      for (int i = 0; i <= ord; i++) { p *= M[i][j]; R[i][j] = p; }
-    }
-  }
   KIN_HD void change_D(int ord, double factor) {
-    double (&R)[6][6] = wR; double (&U)[6][6] = wU; double (&RU)[6][6] = wRU;
-    compute_R(ord, factor, R);
-    compute_R(ord, 1.0, U);
-    for (int a = 0; a <= ord; a++)
-      for (int q2 = 0; q2 <= ord; q2++) {
-        double v = 0.0;
-        for (int q = 0; q <= ord; q++) v += R[a][q] * U[q][q2];
-        RU[a][q2] = v;
-      }
-    b.change_D(ord, RU);
+    bdf_change_D_matrix(ord, factor, wM, wR, wU, wRU);
+    b.change_D(ord, wRU);
   }
 
   KIN_HD bool continuous() const { return ResHasApplyT<B>::value && P.rate_mode == 3; }
@@ -236,11 +186,12 @@ struct ResidentBdf {
   KIN_HD void rates_at(double tau) {
     if constexpr (ResHasApplyT<B>::value) b.apply_T(res_T_of(P.t_nodes, P.T_nodes, P.n_nodes, seg_origin + tau));
   }
-  // LU-cache lookup; under continuous rate updates only slots whose Jacobian is at most RES_CONT_JAC_AGE accepted steps old
+  // LU-cache lookup; under continuous rate updates only slots whose Jacobian is at most BDF_CONT_JAC_AGE accepted steps old
+  // (a backend without apply_T never runs that mode and offers the lookup without the step-age arguments)
   KIN_HD int nearest_slot(double c, double band) {
     if constexpr (ResHasApplyT<B>::value) {
       const bool cont = continuous();
-      return b.nearest_slot(c, band, st.n_restarts, P.lu_max_age, cont ? st.n_steps : 0, cont ? RES_CONT_JAC_AGE : -1);
+      return b.nearest_slot(c, band, st.n_restarts, P.lu_max_age, cont ? st.n_steps : 0, cont ? BDF_CONT_JAC_AGE : -1);
     } else {
       return b.nearest_slot(c, band, st.n_restarts, P.lu_max_age);
     }
@@ -260,14 +211,8 @@ struct ResidentBdf {
     if (P.lu_band > 0.0 && P.lu_drift_max > 0.0) st.n_lu_dropped += b.drift_check(P.lu_drift_max);
   }
 
-  // (re)start at segment-local time 0 from the state in y: order 1, fresh initial step, fresh Jacobian (Solver::restart).
-  // Initial step = CVODE's (cvode.c: cvHin, cvUpperBoundH0, cvYddNorm - the documented solver of the reference,
-  // docs/src/getting-started.md:69, re-initialised at every chunk start and rate update, methods.jl:260, 819): the h with
-  // ||h^2 y'' / 2||_WRMS = 1, y'' from a difference quotient of f along the Euler direction, iterated (at most 4 evaluations)
-  // until two successive estimates agree within a factor of 2, halved (H_BIAS), kept inside [hlb, hub]: hlb = 100 ulp of the
-  // segment, hub = a tenth of the segment but no step over which ANY component moves by more than a tenth of itself plus its
-  // error weight (`dmax` of the norms). Then rounded DOWN to a power of ten: the step size climbs through the same values after
-  // every restart, so the iteration matrices of the previous segment's climb are found in the LU cache again.
+  // (re)start at segment-local time 0 from the state in y: order 1, fresh Jacobian, CVODE's initial step on the decade grid
+  // (bdf_rules.hpp: bdf_h0_begin / _update / _finish)
   KIN_HD bool restart(double t_bound) {
     t = 0.0;
     st.n_restarts++;
@@ -278,30 +223,17 @@ struct ResidentBdf {
     ResNorms n0 = b.norms(false, atol, rtol);
     if (n0.nonfinite) return false;
     const double tdist = fabs(t_bound);
-    const double hlb = 100.0 * 2.220446049250313e-16 * tdist;
-    double hub = 0.1 * tdist;
-    if (hub * n0.dmax > 1.0) hub = 1.0 / n0.dmax;
-    double hg = sqrt(hlb * hub), hnew = hg;
-    if (hub >= hlb) {
-      for (int count = 1; count <= 4; count++) {
-        b.ytmp_axpy(hg);
+    BdfFirstStep fs = bdf_h0_begin(tdist, tdist, n0.dmax);
+    if (fs.iterate()) {
+      for (int count = 1; count <= BDF_H0_EVALS; count++) {
+        b.ytmp_axpy(fs.hg);
         b.rhs_ytmp_to_f1(); st.n_rhs++;
         ResNorms n1 = b.norms(true, atol, rtol);
         if (n1.nonfinite) return false;
-        const double ydd = n1.d2 / hg;
-        hnew = ydd * hub * hub > 2.0 ? sqrt(2.0 / ydd) : sqrt(hg * hub);
-        if (count == 4) break;
-        const double hrat = hnew / hg;
-        if (hrat > 0.5 && hrat < 2.0) break;
-        if (count > 1 && hrat > 2.0) { hnew = hg; break; }
-        hg = hnew;
+        if (bdf_h0_update(fs, count, n1.d2)) break;
       }
     }
-    double h0 = 0.5 * hnew;
-    h0 = h0 < hlb ? hlb : h0;
-    h0 = h0 > hub ? hub : h0;
-    h0 = h0 < tdist ? h0 : tdist;
-    h_abs = res_decade_floor(h0);
+    h_abs = bdf_h0_finish(fs, tdist);
     b.init_D(false, h_abs);
     order = 1; n_equal = 0; fail_score = 0.0;
     first_selection = true;
@@ -362,8 +294,7 @@ struct ResidentBdf {
     ResAttempt a{};
     while (!accepted) {
       if (iters_left-- <= 0) return STEP_OK;   // caller checks iters_left < 0 -> MaxIters
-      const double ulp10 = 10.0 * res_ulp_above(t);
-      const double min_step = dtmin > ulp10 ? dtmin : ulp10;
+      const double min_step = bdf_min_step(dtmin, t);
       if (h_abs < min_step) {
         if (!first_attempt) return STEP_DT_MIN;
         change_D(order, min_step / h_abs);
@@ -441,11 +372,10 @@ struct ResidentBdf {
         continue;
       }
       if (band > 0.0 && !fresh && a.n_iter >= RES_NEWTON_MAXITER) b.slot_drop(cur_slot);
-      safety = 0.9 * (2.0 * RES_NEWTON_MAXITER + 1.0) / (2.0 * RES_NEWTON_MAXITER + a.n_iter);
+      safety = bdf_safety(a.n_iter);
       err_norm = a.err;
       if (err_norm > 1.0) {
-        const double f0 = safety * pow(err_norm, -1.0 / (order + 1));
-        const double factor = f0 > 0.2 ? f0 : 0.2;
+        const double factor = bdf_reject_factor(safety, err_norm, order);
         h_abs *= factor;
         change_D(order, factor);
         n_equal = 0;
@@ -455,7 +385,7 @@ struct ResidentBdf {
         fail_score += 1.0;
         if (fail_score >= 3.0 && order > 1) reset_history();
       } else {
-        if (a.deep_negative) return STEP_UNSTABLE;   // solver_kernels.hpp BDF_NEG_DEEP: the negative excursion, given up early
+        if (a.deep_negative) return STEP_UNSTABLE;   // BDF_NEG_DEEP: the negative excursion, given up early
         accepted = true;
       }
     }
@@ -468,8 +398,8 @@ struct ResidentBdf {
     jac_current = false;
     pending_order_change = (n_equal >= order + 1);
     if (pending_order_change) {
-      err_m = order > 1 ? a.err_m : res_inf();
-      err_p = order < RES_MAX_ORDER ? a.err_p : res_inf();
+      err_m = order > 1 ? a.err_m : bdf_inf();
+      err_p = order < RES_MAX_ORDER ? a.err_p : bdf_inf();
       err_o = err_norm;
       safety_o = safety;
     }
@@ -479,37 +409,19 @@ struct ResidentBdf {
   KIN_HD void select_order() {
     if (!pending_order_change) return;
     pending_order_change = false;
-    const double norms[3] = {err_m, err_o, err_p};
-    double best = -1.0;
-    int arg = 1;
-    for (int i = 0; i < 3; i++) {
-      double f;
-      if (norms[i] == 0.0) f = res_inf();
-      else if (norms[i] == res_inf()) f = 0.0;
-      else f = pow(norms[i], -1.0 / (order + i));
-      if (f > best) { best = f; arg = i; }
-    }
-    order += arg - 1;
-    const double f1 = safety_o * best;
-    const double cap = first_selection ? 1e4 : 10.0;
+    const BdfOrderChoice ch = bdf_select_order(order, err_m, err_o, err_p, safety_o, first_selection);
+    order += ch.d_order;
     first_selection = false;
-    const double factor = f1 < cap ? f1 : cap;
-    h_abs *= factor;
-    change_D(order, factor);
+    h_abs *= ch.factor;
+    change_D(order, ch.factor);
     n_equal = 0;
     lu_valid = false;
   }
 
   // dense output of the step that ended at t into solution row `row`
   KIN_HD void interpolate(double ts, int64_t row) {
-    double (&p)[RES_MAX_ORDER + 1] = wp;
-    double prod = 1.0;
-    p[0] = 0.0;
-    for (int j = 0; j < order; j++) {
-      prod *= (ts - (t - h_abs * j)) / (h_abs * (1.0 + j));
-      p[j + 1] = prod;
-    }
-    b.interp(order, p, row);
+    bdf_interp_weights(order, ts, t, h_abs, wp);
+    b.interp(order, wp, row);
   }
 
   // ---- the driver (solve_entry, solver.cpp); returns the result block

@@ -33,35 +33,11 @@
 
 namespace kin {
 
-// largest power of ten <= h, by exact IEEE operations only (the same double on the host, on the device and in Python:
-// resident_core.hpp res_decade_floor, oracle/cpu_bdf.cpp, oracle/bdf.py); h <= 0 or not finite: h itself
-static inline double decade_floor(double h) {
-  if (!(h > 0.0) || !std::isfinite(h)) return h;
-  double p = 1.0;
-  while (p > h) p /= 10.0;
-  while (p * 10.0 <= h) p *= 10.0;
-  return p;
-}
-
 namespace {
-constexpr double MIN_FACTOR = 0.2, MAX_FACTOR = 10.0, FIRST_MAX_FACTOR = 1e4;
-const double KAPPA[6] = {0.0, -0.1850, -1.0 / 9.0, -0.0823, -0.0415, 0.0};
+constexpr double MIN_FACTOR = 0.2, MAX_FACTOR = 10.0;   // the explicit pair's step-size factors (the BDF's rules: bdf_rules.hpp)
 constexpr double INF = std::numeric_limits<double>::infinity();
 
 enum StepStatus { STEP_OK = 0, STEP_DT_MIN = 1, STEP_UNSTABLE = 2 };
-
-void compute_R(int order, double factor, double R[6][6]) {
-  double M[6][6];
-  for (int i = 0; i <= order; i++)
-    for (int j = 0; j <= order; j++) M[i][j] = 0.0;
-  for (int j = 0; j <= order; j++) M[0][j] = 1.0;
-  for (int i = 1; i <= order; i++)
-    for (int j = 1; j <= order; j++) M[i][j] = ((double)i - 1.0 - factor * (double)j) / (double)i;
-  for (int j = 0; j <= order; j++) {
-    double p = 1.0;
-    for (int i = 0; i <= order; i++) { p *= M[i][j]; R[i][j] = p; }
-  }
-}
 }  // namespace
 
 struct Solver {
@@ -102,13 +78,7 @@ struct Solver {
 
   explicit Solver(kin_network* hh) : h(hh), N((int)hh->host.N), s(hh->stream) {
     const NetworkHost& H = h->host;
-    LUOptions opt;
-    // Larger networks: eliminate more of the tail sparsely (more rounds, more fill allowed) - every Gauss-Jordan
-    // step moves the whole dense block, so its dimension dominates there (C5: 3870 -> 3126, solve -32 %; C3:
-    // 1173 -> 981, -10 %); small networks keep few rounds, their cost is the number of dependent launches
-    // (C2: the loose setting is 15 % slower). Measured with tools/c5_lu_params.py and bench.py.
-    if (N >= 4000) { opt.max_tail_degree = 32; opt.max_rounds = 16; opt.max_degree = 400; }
-    lu.analyze(N, H.j_ptr, H.j_col, opt, s);
+    lu.analyze(N, H.j_ptr, H.j_col, lu_options_for(N), s);
     {
       // cache size: KIN_LU_CACHE_SLOTS (default 128), bounded by KIN_LU_CACHE_MB (default 32768) of device memory. A
       // restart replays a ramp of step sizes over up to ~12 decades of c; slots sit >= 35 % apart, i.e. ~8 per decade:
@@ -158,20 +128,26 @@ struct Solver {
       (void)hipGetLastError();
       fast_sync = false; fast_sync_allowed = false; hc_dev = nullptr; hseq_dev = nullptr;
     }
-    cf.gamma[0] = 0.0;
-    for (int j = 1; j <= BDF_MAX_ORDER; j++) cf.gamma[j] = cf.gamma[j - 1] + 1.0 / j;
-    for (int j = 0; j <= BDF_MAX_ORDER; j++) cf.alpha[j] = (1.0 - KAPPA[j]) * cf.gamma[j];
-    for (int j = 0; j <= BDF_MAX_ORDER; j++) cf.error_const[j] = KAPPA[j] * cf.gamma[j] + 1.0 / (j + 1);
-    cf.error_const[BDF_MAX_ORDER + 1] = 0.0;
+    bdf_fill_coef(cf.gamma, cf.alpha, cf.error_const);
   }
   ~Solver() { if (hc_buf) (void)hipHostFree(hc_buf); if (hseq) (void)hipHostFree(hseq); if (h_drift) (void)hipHostFree(h_drift); }
 
   void set_tols(double a, double r) {
     atol = a; rtol = r;
-    // corrector tolerance in the style of ode15s / CVODE: a fixed fraction of the error weight, not RADAU5's sqrt(rtol); see
-    // oracle/bdf.py (set_tols). ode15s uses 0.05, CVODE 0.1 (nlscoef). Here 0.03 at the default tolerances, rising to 0.1
-    // where the relative tolerance goes below 3e-9 - bdf_newton_frac() in solver_kernels.hpp has the rule and what it rests on.
-    newton_tol = std::max(10.0 * std::numeric_limits<double>::epsilon() / rtol, bdf_newton_frac(rtol));
+    newton_tol = bdf_newton_tol(rtol);
+  }
+
+  // the reset every call on the handle starts with (solve_entry, integrator_init). The LU cache lives within one call:
+  // identical calls give identical results; nothing pending of an earlier call survives (its solution buffer may be gone)
+  void begin_call(const kin_params& p, bool explicit_solver) {
+    st = kin_stats{};
+    invalidate_lu();
+    accept_pending = false; accept_copy = nullptr;
+    spec = Spec{};
+    explicit_mode = explicit_solver;
+    ban_negatives = p.ban_negatives != 0;
+    dtmin = res_dtmin(p);
+    set_tols(p.abstol, p.reltol);
   }
 
   // step-end hand-over without a stream synchronisation: the corrector launch that decides the attempt publishes the
@@ -258,16 +234,9 @@ struct Solver {
 
   void change_D(int ord, double factor) {
     flush_accept();
-    double R[6][6], U[6][6];
-    compute_R(ord, factor, R);
-    compute_R(ord, 1.0, U);
+    double M[6][6], R[6][6], U[6][6];
     BdfMat ru;
-    for (int a = 0; a <= ord; a++)
-      for (int b = 0; b <= ord; b++) {
-        double v = 0.0;
-        for (int q = 0; q <= ord; q++) v += R[a][q] * U[q][b];
-        ru.v[a][b] = v;
-      }
+    bdf_change_D_matrix(ord, factor, M, R, U, ru.v);
     launch_bdf_change_D(N, ord, ru, D.p, s);
   }
 
@@ -284,19 +253,12 @@ struct Solver {
     if (!explicit_mode) {
       eval_jac(y.p);
       jac_current = true;
-      if (lu_band > 0.0 && lu_drift_max > 0.0) {
-        SlotDriftArgs a;
-        n_checked = (int)lu.slots.size();
-        for (int i = 0; i < n_checked; i++) { a.jd[i] = lu.slots[i].valid ? lu.slots[i].jd.p : nullptr; a.c[i] = lu.slots[i].c_fact; }
-        launch_slot_drift(N, n_checked, jv.p, d_jdiag.p, a, d_drift.p, s);
-        KIN_HIP(hipMemcpyAsync(h_drift, d_drift.p, (size_t)n_checked * sizeof(double), hipMemcpyDeviceToHost, s));
-      }
+      if (lu_band > 0.0 && lu_drift_max > 0.0) n_checked = launch_drift_test(N, lu.slots, jv.p, d_jdiag.p, d_drift.p, h_drift, s);
     }
     rhs(y.p, f0.p);
     launch_bdf_norms(N, y.p, f0.p, nullptr, atol, rtol, ctrl.p, s);
     sync_ctrl();
-    for (int i = 0; i < n_checked; i++)
-      if (lu.slots[i].valid && !(h_drift[i] <= lu_drift_max)) { lu.slots[i].valid = false; st.n_lu_dropped++; }
+    st.n_lu_dropped += drop_drifted(lu.slots, n_checked, h_drift, lu_drift_max);
     if (hc->nonfinite) return false;
     const double interval = std::fabs(t_bound - t0);
     if (explicit_mode) {
@@ -313,33 +275,19 @@ struct Solver {
       const double h1 = (d1 <= 1e-15 && d2 <= 1e-15) ? std::max(1e-6, h0 * 1e-3) : std::pow(0.01 / std::max(d1, d2), 0.2);
       h_abs = std::min({100.0 * h0, h1, interval});
     } else {
-      // CVODE's initial step (cvode.c: cvHin / cvUpperBoundH0 / cvYddNorm; resident_core.hpp restart() has the description),
-      // rounded down to a power of ten: every restart's climb passes through the same step sizes, so the matrices of the
-      // previous segment's climb are found in the LU cache again (C3, 100 chunks: 363 -> 269 factorisations in round 4's A/B,
-      // profiles/r04_h0_decade_ab.txt - round 4's A/B of the grid as an opt-in; the rms deviations from the truths do not move)
-      const double hlb = 100.0 * std::numeric_limits<double>::epsilon() * std::max(std::fabs(t0), std::fabs(t_bound));
-      double hub = 0.1 * interval;
-      if (hub * hc->scratch[3] > 1.0) hub = 1.0 / hc->scratch[3];
-      double hg = std::sqrt(hlb * hub), hnew = hg;
-      if (hub >= hlb) {
-        for (int count = 1; count <= 4; count++) {
-          launch_axpy_out(N, y.p, hg, f0.p, ytmp.p, s);
+      // CVODE's initial step on the decade grid (bdf_rules.hpp: bdf_h0_begin / _update / _finish)
+      BdfFirstStep fs = bdf_h0_begin(std::max(std::fabs(t0), std::fabs(t_bound)), interval, hc->scratch[3]);
+      if (fs.iterate()) {
+        for (int count = 1; count <= BDF_H0_EVALS; count++) {
+          launch_axpy_out(N, y.p, fs.hg, f0.p, ytmp.p, s);
           rhs(ytmp.p, f1.p);
           launch_bdf_norms(N, y.p, f0.p, f1.p, atol, rtol, ctrl.p, s);
           sync_ctrl();
           if (hc->nonfinite) return false;
-          const double ydd = hc->scratch[2] / hg;
-          hnew = ydd * hub * hub > 2.0 ? std::sqrt(2.0 / ydd) : std::sqrt(hg * hub);
-          if (count == 4) break;
-          const double hrat = hnew / hg;
-          if (hrat > 0.5 && hrat < 2.0) break;
-          if (count > 1 && hrat > 2.0) { hnew = hg; break; }
-          hg = hnew;
+          if (bdf_h0_update(fs, count, hc->scratch[2])) break;
         }
       }
-      double h0 = 0.5 * hnew;
-      h0 = std::min(std::max(h0, hlb), hub);
-      h_abs = decade_floor(std::min(h0, interval));
+      h_abs = bdf_h0_finish(fs, interval);
     }
     if (explicit_mode) {
       rk_K.alloc((size_t)7 * N); rk_yold.alloc(N); rk_ynew.alloc(N);
@@ -386,14 +334,9 @@ struct Solver {
     eval_jac(y.p);
     jac_current = true;
     if (lu_band > 0.0 && lu_drift_max > 0.0) {
-      SlotDriftArgs a;
-      const int n_checked = (int)lu.slots.size();
-      for (int i = 0; i < n_checked; i++) { a.jd[i] = lu.slots[i].valid ? lu.slots[i].jd.p : nullptr; a.c[i] = lu.slots[i].c_fact; }
-      launch_slot_drift(N, n_checked, jv.p, d_jdiag.p, a, d_drift.p, s);
-      KIN_HIP(hipMemcpyAsync(h_drift, d_drift.p, (size_t)n_checked * sizeof(double), hipMemcpyDeviceToHost, s));
+      const int n_checked = launch_drift_test(N, lu.slots, jv.p, d_jdiag.p, d_drift.p, h_drift, s);
       KIN_HIP(hipStreamSynchronize(s));
-      for (int i = 0; i < n_checked; i++)
-        if (lu.slots[i].valid && !(h_drift[i] <= lu_drift_max)) { lu.slots[i].valid = false; st.n_lu_dropped++; }
+      st.n_lu_dropped += drop_drifted(lu.slots, n_checked, h_drift, lu_drift_max);
     }
   }
 
@@ -510,7 +453,7 @@ struct Solver {
     if (iters_left < 1) return;
     const double t2 = t_new + h_abs;
     if (t2 - t_bound > 0.0) return;                    // would be cut at the segment end
-    if (h_abs < std::max(dtmin, 10.0 * (std::nextafter(t_new, INF) - t_new))) return;
+    if (h_abs < bdf_min_step(dtmin, t_new)) return;
     const double hh2 = t2 - t_new, c2 = hh2 / cf.alpha[order];
     if (nearest_slot(c2) != cur_slot) return;          // (the slot can only drop out by the rule that also clears spec_go)
     const SparseLU::Slot& q = lu.slots[cur_slot];
@@ -535,30 +478,19 @@ struct Solver {
     for (auto& q : lu.slots) { q.valid = false; q.c_fact = 0.0; q.last_use = 0; }
     lu_valid = false; cur_slot = 0; use_clock = 0; attempt_no = 0; force_fresh_lu = false; steps_since_jac = 0; cache_suspended = false;
   }
-  // slot whose c_fact is closest (in ratio) to c and within the band; -1: none
+  // slot whose c_fact is closest (in ratio) to c and within the band; -1: none (continuous rate updates: with the bound on
+  // the age of a slot's Jacobian in accepted steps)
   int nearest_slot(double c) const {
-    int best = -1;
-    double bd = 1e300;
-    for (int i = 0; i < (int)lu.slots.size(); i++) {
-      const SparseLU::Slot& q = lu.slots[i];
-      if (!q.valid || st.n_restarts - q.jac_stamp > lu_max_age) continue;
-      // continuous rate updates: k(t) moves inside a segment and no restart re-validates the slots - the Jacobian behind
-      // a slot may be at most 50 accepted steps old (CVODE's bound on the age of its Jacobian)
-      if (pre_attempt && st.n_steps - q.step_stamp > 50) continue;
-      const double r = std::fabs(std::log(c / q.c_fact));
-      const bool ok = std::fabs(c / q.c_fact - 1.0) <= lu_band;
-      if (r < bd && ok) { bd = r; best = i; }
-    }
-    return best;
+    return slot_nearest(lu.slots.data(), (int)lu.slots.size(), c, lu_band, st.n_restarts, lu_max_age, st.n_steps,
+                        pre_attempt ? BDF_CONT_JAC_AGE : -1);
   }
-  // a slot for a new factorisation: an unused one (allocated on demand), else the least recently used
+  // a slot for a new factorisation: an unused or expired one, else a new one (allocated on demand), else the least recently used
   int victim_slot() {
-    for (int i = 0; i < (int)lu.slots.size(); i++)
-      if (!lu.slots[i].valid || st.n_restarts - lu.slots[i].jac_stamp > lu_max_age) return i;
-    if ((int)lu.slots.size() < lu_slots) { lu.ensure_slots((int)lu.slots.size() + 1, s); return (int)lu.slots.size() - 1; }
-    int v = 0;
-    for (int i = 1; i < (int)lu.slots.size(); i++) if (lu.slots[i].last_use < lu.slots[v].last_use) v = i;
-    return v;
+    const int n = (int)lu.slots.size();
+    const int free_ = slot_first_free(lu.slots.data(), n, st.n_restarts, lu_max_age);
+    if (free_ >= 0) return free_;
+    if (n < lu_slots) { lu.ensure_slots(n + 1, s); return n; }
+    return slot_lru(lu.slots.data(), n);
   }
   // ---- a convergence failure (CVODE: cvHandleNFlag / cvSetEta): a failed corrector cuts the step by ETACF = 0.25 (0.5 until round
   // 3) and does not count towards the history reset (CVODE rebuilds its history only after repeated ERROR-TEST failures: after a
@@ -606,7 +538,7 @@ struct Solver {
     bool rejected = false;
     for (;;) {
       if (iters_left-- <= 0) return STEP_OK;   // caller checks iters_left < 0 -> MaxIters
-      const double min_step = std::max(dtmin, 10.0 * (std::nextafter(t, INF) - t));
+      const double min_step = bdf_min_step(dtmin, t);
       if (h_abs < min_step) {
         if (rejected) return STEP_DT_MIN;
         h_abs = min_step;                       // SciPy clips the proposed step to [min_step, max_step] once per step
@@ -675,7 +607,7 @@ struct Solver {
     spec.alive = false; spec.enq = false;
     while (!accepted) {
       if (iters_left-- <= 0) return STEP_OK;  // caller checks iters_left < 0 -> MaxIters
-      const double min_step = std::max(dtmin, 10.0 * (std::nextafter(t, INF) - t));
+      const double min_step = bdf_min_step(dtmin, t);
       if (h_abs < min_step) {
         if (!first_attempt) return STEP_DT_MIN;
         // a step that merely STARTS below the resolution of t is raised to it (it only fails if
@@ -827,10 +759,10 @@ struct Solver {
       iter_hist[std::min(hc->n_iter, 7)]++;
       // a reused factorisation that needed every allowed iteration is too stale to be offered again
       if (lu_band > 0.0 && !fresh && hc->n_iter >= BDF_NEWTON_MAXITER) lu.slots[cur_slot].valid = false;
-      safety = 0.9 * (2.0 * BDF_NEWTON_MAXITER + 1.0) / (2.0 * BDF_NEWTON_MAXITER + hc->n_iter);
+      safety = bdf_safety(hc->n_iter);
       err_norm = hc->err_norm;
       if (err_norm > 1.0) {
-        const double factor = std::max(MIN_FACTOR, safety * std::pow(err_norm, -1.0 / (order + 1)));
+        const double factor = bdf_reject_factor(safety, err_norm, order);
         h_abs *= factor;
         change_D(order, factor);
         n_equal = 0;
@@ -842,7 +774,7 @@ struct Solver {
         fail_score += 1.0;
         if (fail_score >= 3.0 && order > 1) reset_history();
       } else {
-        if (hc->any_negative & 2) return STEP_UNSTABLE;   // solver_kernels.hpp BDF_NEG_DEEP: the negative excursion, given up early
+        if (hc->any_negative & 2) return STEP_UNSTABLE;   // BDF_NEG_DEEP: the negative excursion, given up early
         accepted = true;
       }
     }
@@ -875,22 +807,11 @@ struct Solver {
   void select_order() {
     if (explicit_mode || !pending_order_change) return;
     pending_order_change = false;
-    const double norms[3] = {err_m, err_o, err_p};
-    double best = -1.0;
-    int arg = 1;
-    for (int i = 0; i < 3; i++) {
-      double f;
-      if (norms[i] == 0.0) f = INF;
-      else if (std::isinf(norms[i])) f = 0.0;
-      else f = std::pow(norms[i], -1.0 / (order + i));
-      if (f > best) { best = f; arg = i; }
-    }
-    order += arg - 1;
-    // growth cap 1e4 at the first selection after a (re)initialisation, 10 afterwards (CVODE: ETAMX1, ETAMX2 / ETAMX3)
-    double factor = std::min(first_selection ? FIRST_MAX_FACTOR : MAX_FACTOR, safety_o * best);
+    const BdfOrderChoice ch = bdf_select_order(order, err_m, err_o, err_p, safety_o, first_selection);
+    order += ch.d_order;
     first_selection = false;
-    h_abs *= factor;
-    change_D(order, factor);
+    h_abs *= ch.factor;
+    change_D(order, ch.factor);
     n_equal = 0;
     lu_valid = false;
   }
@@ -919,11 +840,7 @@ struct Solver {
     }
     flush_accept();
     BdfVec p;
-    double prod = 1.0;
-    for (int j = 0; j < order; j++) {
-      prod *= (ts - (t - h_abs * j)) / (h_abs * (1.0 + j));
-      p.v[j + 1] = prod;
-    }
+    bdf_interp_weights(order, ts, t, h_abs, p.v);
     launch_bdf_interp(N, order, D.p, p, out, s);
   }
 };
@@ -932,6 +849,19 @@ struct Solver {
 // orchestration
 // ------------------------------------------------------------------------------------------
 namespace {
+
+// Whatever way a call that drives the integrator ends (a throw included): no temperature stays pending on the handle (kin_rhs /
+// kin_jac and the batched sweeps would otherwise see rate constants of different temperatures), the hook that captures the
+// call's locals is gone, and no speculative batch is left half-taken-up or held back
+struct CallGuard {
+  kin_network* h; Solver& S;
+  ~CallGuard() {
+    S.pre_attempt = nullptr;
+    S.spec = Solver::Spec{};
+    S.hold_speculation = false;
+    if (h->k_pending) { try { h->flush_pending_T(h->stream); } catch (...) { h->k_pending = false; } }
+  }
+};
 
 struct SaveBuf {
   kin_network* h;
@@ -967,19 +897,25 @@ void apply_rates(kin_network* h, const double* T_stops, bool have_table, int64_t
 
 }  // namespace
 
+// the save grid of a chunkwise solve (params.jl:89-99); a call that saves nothing on a grid (kin_integrator_init) skips it
+static void validate_save_grid(const kin_params& p) {
+  const bool has_save = p.save_interval >= 0;
+  if (has_save && p.save_interval > p.solve_chunkstep) throw KinError(ERR_INVALID_ARG, "Solution save interval must be less than chunkwise simulation step size");
+  if (has_save && !(p.save_interval > 0)) throw KinError(ERR_INVALID_ARG, "save_interval must be positive");
+}
+
 void validate_solve(kin_network* h, const kin_params& p, const double* tstops, const double* T_stops, const double* k_table,
-                    int64_t n_stops, const double* t_nodes, const double* T_nodes, int64_t n_nodes, bool need_handle_rates) {
+                    int64_t n_stops, const double* t_nodes, const double* T_nodes, int64_t n_nodes, bool need_handle_rates,
+                    bool with_save_grid) {
   // ---- validation (ODESimulationParams constructor, params.jl:77-104)
   if (!(p.tspan0 < p.tspan1)) throw KinError(ERR_INVALID_ARG, "Invalid time span");
   if (!(p.abstol > 0) || !(p.reltol > 0)) throw KinError(ERR_INVALID_ARG, "tolerances must be positive");
   const bool chunks = p.solve_chunks != 0;
-  const bool has_save = p.save_interval >= 0;
   if (chunks) {
     if (!(p.solve_chunkstep > 0)) throw KinError(ERR_INVALID_ARG, "solve_chunkstep must be positive");
     const double q = p.tspan1 / p.solve_chunkstep;   // Int(tspan[2] / solve_chunkstep) must be exact (params.jl:89-99)
     if (q != std::floor(q) || q < 1) throw KinError(ERR_INVALID_ARG, "Simulation timespan is not divisible by requested chunkwise simulation step size");
-    if (has_save && p.save_interval > p.solve_chunkstep) throw KinError(ERR_INVALID_ARG, "Solution save interval must be less than chunkwise simulation step size");
-    if (has_save && !(p.save_interval > 0)) throw KinError(ERR_INVALID_ARG, "save_interval must be positive");
+    if (with_save_grid) validate_save_grid(p);
   }
   const bool continuous = n_nodes > 0;
   if (continuous) {
@@ -1018,28 +954,11 @@ int solve_entry(kin_network* h, const kin_params& p, const double* u0, const dou
   if (!h->solver) h->solver.reset(new Solver(h));
   Solver& S = *h->solver;
   hipStream_t s = h->stream;
-  // whatever way this call ends (a throw included): no temperature stays pending on the handle (kin_rhs / kin_jac and the
-  // batched sweeps would otherwise see rate constants of different temperatures), the hook that captures this call's
-  // locals is gone, and no speculative batch is left half-taken-up
-  struct ExitGuard {
-    kin_network* h; Solver& S;
-    ~ExitGuard() {
-      S.pre_attempt = nullptr;
-      S.spec = Solver::Spec{};
-      if (h->k_pending) { try { h->flush_pending_T(h->stream); } catch (...) { h->k_pending = false; } }
-    }
-  } exit_guard{h, S};
-  S.st = kin_stats{};
-  S.invalidate_lu();   // the LU cache lives within one solve: identical calls give identical results
-  S.accept_pending = false; S.accept_copy = nullptr;   // nothing of an earlier call (its solution buffer may be gone)
-  S.spec = Solver::Spec{};
-  S.explicit_mode = explicit_solver;
+  CallGuard exit_guard{h, S};
+  S.begin_call(p, explicit_solver);
   S.sync_wait_s = 0.0;
   std::fill(S.iter_hist, S.iter_hist + 8, 0);
-  S.ban_negatives = p.ban_negatives != 0;
-  S.dtmin = res_dtmin(p);
   double abstol = p.abstol, reltol = p.reltol;
-  S.set_tols(abstol, reltol);
 
   const bool have_table = variable && k_table != nullptr;
   if (have_table) {
@@ -1077,7 +996,6 @@ int solve_entry(kin_network* h, const kin_params& p, const double* u0, const dou
   S.y.upload(u0, N, s);
   int64_t next_stop = 0;      // first tstop not yet applied
   int retcode = KIN_RETCODE_SUCCESS;
-  const double t_origin = chunks ? 0.0 : p.tspan0;
   DevBuf<double> chunk_start;
   chunk_start.alloc(N);
   bool have_history = false, rates_changed = false;
@@ -1085,10 +1003,6 @@ int solve_entry(kin_network* h, const kin_params& p, const double* u0, const dou
   // every segment start re-initialises like the reference (reinit!, methods.jl:260, 819), except the chunk starts of
   // kin_params.solve_chunks == 2 whose rates did not change (resume_chunk). Carrying the history across RATE UPDATES was built and
   // measured in round 4 (3 180 rejected steps and 4x the time on the C4 prefix) and is gone (docs/DESIGN_HISTORY.md R4).
-
-  // initial rates = calculator at the initial conditions (methods.jl:672, 734); a tstop at the
-  // very start overrides it below
-  if (variable && !have_table) { /* rates at T_stops[0] are applied by the loop when tstops[0] == start */ }
 
   // KIN_PROGRESS=<seconds>: a status line on stderr at most that often (the reference's `progress` option drives a
   // progress bar from the same place, methods.jl:822-827)
@@ -1112,7 +1026,6 @@ int solve_entry(kin_network* h, const kin_params& p, const double* u0, const dou
     const double shift = chunks ? (double)nc * p.solve_chunkstep : 0.0;   // global = local + shift
     const double t_loc0 = chunks ? 0.0 : p.tspan0;
     const double t_loc1 = chunks ? p.solve_chunkstep : p.tspan1;
-    (void)t_origin;
     // local stops of this chunk: tg - nc*chunkstep for tstops in [t_start, t_end) (methods.jl:798-800);
     // the complete-timespan variant takes all of them (methods.jl:697)
     const int64_t stop_first = next_stop;
@@ -1279,45 +1192,14 @@ struct IntegratorState {
 void integrator_init(kin_network* h, const kin_params& p, const double* u0, const double* tstops, const double* T_stops,
                      const double* k_table, int64_t n_stops, const double* t_nodes, const double* T_nodes, int64_t n_nodes) {
   const int64_t N = h->host.N, R = h->host.R;
-  const bool continuous = n_nodes > 0;
-  if (continuous) {
-    if (n_stops > 0) throw KinError(ERR_INVALID_ARG, "continuous and discrete rate updates are mutually exclusive");
-    if (!t_nodes || !T_nodes || n_nodes < 2) throw KinError(ERR_INVALID_ARG, "need >= 2 (t, T) nodes");
-    if (!h->has_arrhenius) throw KinError(ERR_STATE, "continuous rates need the Arrhenius parameters");
-    for (int64_t i = 1; i < n_nodes; i++)
-      if (!(t_nodes[i] >= t_nodes[i - 1])) throw KinError(ERR_INVALID_ARG, "t_nodes must be non-decreasing");
-  }
-  if (!(p.tspan0 < p.tspan1)) throw KinError(ERR_INVALID_ARG, "Invalid time span");
-  if (!(p.abstol > 0) || !(p.reltol > 0)) throw KinError(ERR_INVALID_ARG, "tolerances must be positive");
-  const bool chunks = p.solve_chunks != 0;
-  if (chunks) {
-    if (!(p.solve_chunkstep > 0)) throw KinError(ERR_INVALID_ARG, "solve_chunkstep must be positive");
-    const double q = p.tspan1 / p.solve_chunkstep;
-    if (q != std::floor(q) || q < 1) throw KinError(ERR_INVALID_ARG, "Simulation timespan is not divisible by requested chunkwise simulation step size");
-  }
-  const bool variable = n_stops > 0;
-  if (variable) {
-    if (!tstops) throw KinError(ERR_INVALID_ARG, "tstops is null");
-    if (!k_table && !T_stops) throw KinError(ERR_INVALID_ARG, "need k_table or T_stops with tstops");
-    if (!k_table && !h->has_arrhenius) throw KinError(ERR_STATE, "T_stops given but Arrhenius parameters were never set");
-    for (int64_t i = 1; i < n_stops; i++)
-      if (!(tstops[i] > tstops[i - 1])) throw KinError(ERR_INVALID_ARG, "tstops must be strictly increasing");
-  } else if (!continuous && !h->has_rates) {
-    throw KinError(ERR_STATE, "rates were never set");
-  }
+  validate_solve(h, p, tstops, T_stops, k_table, n_stops, t_nodes, T_nodes, n_nodes, true, false);
+  const bool continuous = n_nodes > 0, chunks = p.solve_chunks != 0, variable = n_stops > 0;
   if (!h->solver) h->solver.reset(new Solver(h));
   if (!h->integ) h->integ.reset(new IntegratorState());
   Solver& S = *h->solver;
   IntegratorState& I = *h->integ;
   hipStream_t s = h->stream;
-  S.st = kin_stats{};
-  S.invalidate_lu();
-  S.accept_pending = false; S.accept_copy = nullptr;
-  S.spec = Solver::Spec{};
-  S.explicit_mode = false;
-  S.ban_negatives = p.ban_negatives != 0;
-  S.dtmin = res_dtmin(p);
-  S.set_tols(p.abstol, p.reltol);
+  S.begin_call(p, false);
   S.pre_attempt = nullptr;
   S.iters_left = p.maxiters;
   I = IntegratorState{};
@@ -1359,13 +1241,7 @@ int64_t integrator_step(kin_network* h, int64_t max_steps) {
     S.pre_attempt = [h, &I](double tau) {
       h->set_pending_T(res_T_of(I.t_nodes.data(), I.T_nodes.data(), (int64_t)I.t_nodes.size(), I.t_seg + tau));
     };
-  struct ClearHook {
-    kin_network* h; Solver& S;
-    ~ClearHook() {
-      S.pre_attempt = nullptr; S.hold_speculation = false;
-      if (h->k_pending) { try { h->flush_pending_T(h->stream); } catch (...) { h->k_pending = false; } }
-    }
-  } clear_hook{h, S};
+  CallGuard exit_guard{h, S};
   while (I.retcode == KIN_RETCODE_SUCCESS && I.t_seg < I.t_loc1 && (max_steps <= 0 || taken < max_steps)) {
     if (!I.in_segment) {
       I.seg_end = I.t_loc1;

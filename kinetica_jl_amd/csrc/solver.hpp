@@ -72,9 +72,11 @@ void batched_ensemble(kin_network* h, const EnsembleCall& c);
 // member m's rate constants into d_k (R doubles) on stream s: its row of c.k, Arrhenius at c.T[m] from (Ea, A) - the caller's
 // copy of the handle's parameters -, else the handle's current k (resident.cpp)
 void stage_member_rates(kin_network* h, const EnsembleCall& c, int64_t m, const double* Ea, const double* A, double* d_k, hipStream_t s);
-// validation of a solve's arguments (ODESimulationParams constructor, params.jl:77-104, and the rate inputs); throws
+// validation of a solve's arguments (ODESimulationParams constructor, params.jl:77-104, and the rate inputs); throws.
+// with_save_grid false: save_interval is not looked at (kin_integrator_init saves nothing on a grid)
 void validate_solve(kin_network* h, const kin_params& p, const double* tstops, const double* T_stops, const double* k_table,
-                    int64_t n_stops, const double* t_nodes, const double* T_nodes, int64_t n_nodes, bool need_handle_rates);
+                    int64_t n_stops, const double* t_nodes, const double* T_nodes, int64_t n_nodes, bool need_handle_rates,
+                    bool with_save_grid = true);
 // max over saved times per species, reduced on the device
 void solution_max(kin_network* h, double* out_umax);
 // diagnostic: (I - c J(u)) x = b through the solver's LU

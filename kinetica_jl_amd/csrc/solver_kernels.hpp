@@ -2,45 +2,12 @@
 #pragma once
 #include <cmath>
 
+#include "bdf_rules.hpp"
 #include "common.hpp"
 
 namespace kin {
 
-constexpr int BDF_MAX_ORDER = 5;
-constexpr int BDF_NEWTON_MAXITER = 4;
-constexpr int BDF_D_ROWS = BDF_MAX_ORDER + 3;
-
-// Corrector tolerance as a fraction of the error weight atol + rtol |y| (the estimated iteration error must get below it):
-// 0.03 at the default relative tolerance 1e-8 and looser ones, 0.1 (CVODE's nlscoef) from 1e-9 down, 1e-10 / rtol between.
-// What it rests on (profiles/r05_newton_tol_ab.txt, one MI355X):
-//  * at rtol <= 1e-9 an iteration asked to converge to 0.03 of the weight asks for less than the rounding of the right-hand
-//    side's sums leaves (~1e-10 relative on these networks): it fails, and every failure restarts the step at a quarter. With 0.1
-//    the 200-species solve at 1e-12 / 1e-10 ends 2-7 x closer to its Radau truth in half the steps (resident kernel rms 385 -> 55
-//    tight units, host-driven 885 -> 394, CPU port 153 -> 61), C3 at 1e-11 / 1e-9 takes 0.60 s instead of 0.90 s;
-//  * at 1e-8 a flat 0.1 is 7 % faster on C3 (0.350 -> 0.325 s) and passes every sweep with the default switches, but over the 140
-//    solves of tools/robustness_sweep.py wide under four perturbed configurations (corrector fused, reuse band 0.3, 8 and 1
-//    factorisation slots) 10 of 560 needed a tolerance retry after a step-size collapse, against 3 of 560 at 0.03 and 5 at 0.05
-//    (ode15s) - all on 1 000-species networks, the ones that collapsed under 0.05 in round 2: not adopted there.
-// Same rule: resident_core.hpp res_newton_frac, oracle/bdf.py, oracle/cpu_bdf.cpp.
-// An ACCEPTED step (corrector converged, error test passed) that leaves a species below -BDF_NEG_DEEP error weights ends the
-// segment as Unstable. The error test bounds what ONE step can do to one species at sqrt(N) / error constant weights in the worst
-// case (~300 at 1 000 species; more only if a step's whole error sat on a single species of a larger network), so such a state
-// has been growing over many accepted steps: it is the negative excursion of DESIGN 4 - below zero some species are unstable
-// under mass-action kinetics, |u| grows with an e-folding time of ~0.1 ms and h follows it down for 500-1 400 more steps until
-// dtmin or a non-finite state ends the attempt anyway. The chunk's tolerance retry (negative entries of its start state zeroed)
-// carries the solve in either case; a false alarm costs one such retry (docs/DESIGN_HISTORY.md R5.12 has the measurements). The flag
-// rides in the sum that counts negative entries: a thread contributes 1 for a negative entry, BDF_NEG_MARK for a deep one.
-constexpr double BDF_NEG_DEEP = 1e3;
-constexpr double BDF_NEG_MARK = 4294967296.0;   // 2^32 > any count of species
-inline double bdf_newton_frac(double rtol) { return std::fmin(0.1, std::fmax(0.03, 1e-10 / rtol)); }
-
-struct BdfCoef {  // passed to kernels by value
-  double gamma[BDF_MAX_ORDER + 1];
-  double alpha[BDF_MAX_ORDER + 1];
-  double error_const[BDF_MAX_ORDER + 2];
-};
-struct BdfMat { double v[BDF_MAX_ORDER + 1][BDF_MAX_ORDER + 1]; };
-struct BdfVec { double v[BDF_MAX_ORDER + 1]; };
+// (orders, iteration and row counts, the negative-excursion marks and BdfCoef / BdfMat / BdfVec: bdf_rules.hpp)
 struct RkVec { double v[7]; };   // per-stage weights of the explicit Dormand-Prince path
 
 // device-resident control block, copied to the host once per step attempt

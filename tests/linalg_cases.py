@@ -129,7 +129,7 @@ def record(measured, case, errs):
 
 
 def host_lu_options(n_species):
-    """the elimination parameters the host-driven solver analyses with (solver.cpp: Solver), as arguments of capi.lu_analyze_host"""
+    """the elimination parameters the host-driven solver analyses with (lu.hpp: lu_options_for), as arguments of capi.lu_analyze_host"""
     return dict(max_tail_degree=32, max_rounds=16, max_degree=400) if n_species >= 4000 else {}
 
 

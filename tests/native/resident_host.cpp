@@ -117,21 +117,13 @@ struct HostBackend {
     Slot& q = slots[i]; q.c_fact = c; q.crate = 1.0; q.valid = 1; q.last_use = clock; q.jac_stamp = js; q.step_stamp = ss;
   }
   void slots_invalidate(bool reset) { for (auto& q : slots) { q.valid = 0; if (reset) { q.c_fact = 0.0; q.last_use = 0; } } }
-  int nearest_slot(double c, double band, long long n_restarts, long long max_age) const {
-    int best = -1; double bd = 1e300;
-    for (int i = 0; i < (int)slots.size(); i++) {
-      const Slot& q = slots[i];
-      if (!q.valid || n_restarts - q.jac_stamp > max_age) continue;
-      const double r = std::fabs(std::log(c / q.c_fact));
-      if (r < bd && std::fabs(c / q.c_fact - 1.0) <= band) { bd = r; best = i; }
-    }
-    return best;
+  // (step_age >= 0 only under continuous rate updates: tests/native_cont)
+  int nearest_slot(double c, double band, long long n_restarts, long long max_age, long long n_steps = 0, long long step_age = -1) const {
+    return slot_nearest(slots.data(), (int)slots.size(), c, band, n_restarts, max_age, n_steps, step_age);
   }
   int victim_slot(long long n_restarts, long long max_age, int n_slots) const {
-    for (int i = 0; i < n_slots; i++) if (!slots[i].valid || n_restarts - slots[i].jac_stamp > max_age) return i;
-    int v = 0;
-    for (int i = 1; i < n_slots; i++) if (slots[i].last_use < slots[v].last_use) v = i;
-    return v;
+    const int free_ = slot_first_free(slots.data(), n_slots, n_restarts, max_age);
+    return free_ >= 0 ? free_ : slot_lru(slots.data(), n_slots);
   }
   // vectors
   void load_u0() { std::copy(u0, u0 + N, y.begin()); }

@@ -1,8 +1,8 @@
 // TEST INFRASTRUCTURE - not a product path, never loaded by kinetica_jl_amd.
 // CPU replay of the resident integrator's continuous rate mode (ResParams::rate_mode 3: the rates re-formed at T(t) of every
-// step attempt, resident_core.hpp): the sequential backend of tests/native/resident_host.cpp, unchanged, extended by the two
-// operations that mode needs - apply_T (the Arrhenius rates at one temperature, what resident.hip's ph_apply_T does) and the
-// LU-cache lookup with the bound on the age of a slot's Jacobian in accepted steps.
+// step attempt, resident_core.hpp): the sequential backend of tests/native/resident_host.cpp, unchanged, extended by the
+// operation that mode needs - apply_T (the Arrhenius rates at one temperature, what resident.hip's ph_apply_T does). The
+// LU-cache lookup with the bound on the age of a slot's Jacobian in accepted steps is the shared slot_nearest already.
 #include "../native/resident_host.cpp"
 
 namespace {
@@ -15,17 +15,6 @@ struct ContBackend : HostBackend {
       const double kr = net.A[r] * std::exp(-net.Ea[r] / RT) * 6.02214076e23 * net.t_mult;
       k[r] = net.has_kmax ? 1.0 / (1.0 / net.k_max + 1.0 / kr) : kr;
     }
-  }
-  int nearest_slot(double c, double band, long long n_restarts, long long max_age, long long n_steps, long long step_age) const {
-    int best = -1; double bd = 1e300;
-    for (int i = 0; i < (int)slots.size(); i++) {
-      const Slot& q = slots[i];
-      if (!q.valid || n_restarts - q.jac_stamp > max_age) continue;
-      if (step_age >= 0 && n_steps - q.step_stamp > step_age) continue;
-      const double r = std::fabs(std::log(c / q.c_fact));
-      if (r < bd && std::fabs(c / q.c_fact - 1.0) <= band) { bd = r; best = i; }
-    }
-    return best;
   }
 };
 static_assert(ResHasApplyT<ContBackend>::value, "the continuous backend is detected");

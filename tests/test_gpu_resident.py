@@ -74,7 +74,7 @@ def test_tight_tolerances_against_a_radau_truth(golden_dir, monkeypatch):
     (tests/golden/make_truth_tight.py; its 1e-10 sibling sits 8.5 units away) - in units of the TIGHT tolerances
     (1e-12 + 1e-10 |u|). Every implementation runs on the rounding floor of the right-hand side there (most steps are corrector
     failures) and lands by the accuracy of its linear algebra and by how far its corrector is asked to converge: with the corrector
-    tolerance at 0.1 of the error weight (round 5, where rtol <= 1e-9: solver_kernels.hpp bdf_newton_frac) the CPU port (pivoted LU) ends rms 61 / max 378 in 4 073 steps, the resident kernel
+    tolerance at 0.1 of the error weight (round 5, where rtol <= 1e-9: bdf_rules.hpp bdf_newton_frac) the CPU port (pivoted LU) ends rms 61 / max 378 in 4 073 steps, the resident kernel
     55 / p99.9 496 / max 757 in 5 656, the host-driven path 394 / 3 758 / 5 572 in 9 785 (profiles/r05_tight_tol_truth.jsonl; at
     0.03 they were 153, 385 and 885 in 6 692, 9 531 and 17 618 steps, profiles/r05_newton_tol_ab.txt). Bounds: 2x the measurement.
     In DEFAULT units (100x larger) all of them are within 60 - a tolerance below ~1e-9 buys little on these networks in FP64

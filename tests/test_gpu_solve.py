@@ -83,7 +83,7 @@ def test_restart_rules_take_the_same_steps_in_every_implementation(monkeypatch):
 
 def test_a_species_deep_below_zero_ends_the_segment_as_unstable(monkeypatch):
     """2A -> B with A(0) = -1e-3 (blow-up at 0.5 ms): an accepted step that leaves a species below -1e3 error weights ends the
-    segment as Unstable (solver_kernels.hpp BDF_NEG_DEEP) - resident kernel and host-driven integrator, same retcode and step
+    segment as Unstable (bdf_rules.hpp BDF_NEG_DEEP) - resident kernel and host-driven integrator, same retcode and step
     count as the CPU implementations (tests/test_resident_replay.py has those); with `adaptive_tols` the chunk's retry zeroes the
     negative entry and the solve ends with Success."""
     net = from_lists(2, [[(0, 2)]], [[(1, 1)]])

@@ -195,7 +195,7 @@ def test_robertson_and_failure_semantics(golden_dir):
 def test_a_species_deep_below_zero_ends_the_segment_as_unstable():
     """2A -> B with A(0) = -1e-3 runs to -infinity in finite time (1 / (2 k |A0|) = 0.5 ms): the negative excursion of DESIGN 4 in
     two species. An ACCEPTED step that leaves a species below -1e3 error weights ends the segment as Unstable in every
-    implementation (kinetica_jl_amd/csrc/solver_kernels.hpp BDF_NEG_DEEP) instead of following the blow-up down to dtmin: same
+    implementation (kinetica_jl_amd/csrc/bdf_rules.hpp BDF_NEG_DEEP) instead of following the blow-up down to dtmin: same
     retcode and the same handful of steps from the resident controller's CPU replay, oracle/cpu_bdf.cpp and oracle/bdf.py; with
     `adaptive_tols` the retry zeroes the negative entry of the chunk's start state and the solve ends with Success."""
     from oracle import bdf as obdf

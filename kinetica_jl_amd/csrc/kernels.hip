@@ -384,7 +384,8 @@ __global__ __launch_bounds__(1024) void sweep_lds_kernel(int N, int R, int P, in
 // ------------------------------------------------------------------------------------------
 // Register-resident variant (adjacent pairs, state fits LDS): the reaction records a thread works on
 // are the same for every state, so they are loaded ONCE into registers and the only per-state global
-// traffic left is the algorithmic one: k[b] streamed as double2, u[b] in, du[b] out.
+// traffic left is the algorithmic one: k[b] streamed as double2, u[b] in, du[b] out (k and du non-temporal:
+// each is touched once, the records and the staged states are what L2 should keep).
 // Record = four 14-bit species labels with fixed roles (fields 0, 1: reactant instances of the forward
 // reaction, fields 2, 3: its product instances; network.cpp) - no coefficients, no side flags, no
 // branches: SQ counters of the previous format (2-bit codes per slot, empty-slot tests) showed ~100
@@ -392,6 +393,10 @@ __global__ __launch_bounds__(1024) void sweep_lds_kernel(int N, int R, int P, in
 // point at a per-lane dummy entry (u = 1, du discarded) behind the N real ones.
 // ------------------------------------------------------------------------------------------
 constexpr int SWEEP_DUMMY = 64;   // dummy entries behind u_s / du_s, one per lane
+// rows per batch of sweep_reg_kernel (ILP); a build-time knob for the depth comparison in docs/DESIGN_HISTORY.md
+#ifndef KIN_SWEEP_ILP
+#define KIN_SWEEP_ILP 4
+#endif
 __device__ __forceinline__ void sweep_apply(uint2 w, double2 kk, const double* u_s, double* du_s) {
   const uint32_t l0 = w.x & 0x3fffu, l1 = (w.x >> 14) & 0x3fffu, l2 = (w.x >> 28) | ((w.y & 0x3ffu) << 4), l3 = (w.y >> 10) & 0x3fffu;
 #if defined(KIN_SWEEP_PROBE) && KIN_SWEEP_PROBE == 1   // timing only (wrong results): no LDS operand reads
@@ -413,16 +418,61 @@ __device__ __forceinline__ void sweep_apply(uint2 w, double2 kk, const double* u
 // rate constants of pair p: adjacent layout = one double2 at k[2p]; block layout (BLK: all forward reactions
 // first, their reverses in the same order behind them - what duplicate_reverse produces, cde.jl:299-309) =
 // k[p] and k[P + p], two coalesced 8-byte streams
+// (unsigned 32-bit byte offsets from the state's row - a wave-uniform base - so that the loads take the
+// scalar-base + 32-bit-offset form and no 64-bit address pair per row in flight; launch_sweep checks 8 R < 2^32.
+// Non-temporal: a state's rate constants are read once, by one workgroup; streamed with the default policy they
+// push the records and the states' u - the lines that ARE re-read - out of L2)
+typedef double kin_d2 __attribute__((ext_vector_type(2)));
 template <bool BLK>
 __device__ __forceinline__ double2 load_kpair(const double* __restrict__ kb, int p, int P) {
-  if (BLK) return make_double2(kb[p], kb[(size_t)P + p]);
-  return *reinterpret_cast<const double2*>(kb + 2 * (size_t)p);
+  const char* base = reinterpret_cast<const char*>(kb);
+  if (BLK) return make_double2(__builtin_nontemporal_load(reinterpret_cast<const double*>(base + (uint32_t)p * 8u)),
+                               __builtin_nontemporal_load(reinterpret_cast<const double*>(base + ((uint32_t)P + (uint32_t)p) * 8u)));
+  const kin_d2 v = __builtin_nontemporal_load(reinterpret_cast<const kin_d2*>(base + (uint32_t)p * 16u));
+  return make_double2(v.x, v.y);
+}
+__device__ __forceinline__ uint2 load_rec64(const uint2* __restrict__ rec64, int p) {
+  return *reinterpret_cast<const uint2*>(reinterpret_cast<const char*>(rec64) + (uint32_t)p * 8u);
+}
+
+// One batch of NB streamed rows: rows p0, p0 + BS, ... of the (host-padded) record array and their rate constants.
+// All 2 NB loads are issued before the first wait; the scheduling barriers keep the compiler from sinking a load
+// below the first use (it does so under register pressure, re-using a loaded word's registers for the next address),
+// so the waits that follow count down vmcnt(2 NB - 2), (2 NB - 4), ... while the later rows are still in flight.
+template <int NB, bool BLK, int BS>
+__device__ __forceinline__ void sweep_stream_batch(const double* __restrict__ kb, const uint2* __restrict__ rec64, int p0, int Pm1,
+                                                   int P, const double* u_s, double* du_s) {
+  double2 kk[NB];
+  uint2 w[NB];
+#pragma unroll
+  for (int x = 0; x < NB; x++) {
+    const int p = p0 + x * BS;
+    w[x] = load_rec64(rec64, p);
+    kk[x] = load_kpair<BLK>(kb, min(p, Pm1), P);
+    __builtin_amdgcn_sched_barrier(0);   // rows are requested in the order they are used
+  }
+#pragma unroll
+  for (int x = 0; x < NB; x++) sweep_apply(w[x], kk[x], u_s, du_s);
+  __builtin_amdgcn_sched_barrier(0);
+}
+
+// Batch plan of the streamed rows (host side): `rows` record rows of BS records, the first TR of them register-
+// resident; the S = rows - TR streamed ones run as n_a batches of ILP and n_b batches of ILP + 1, in the fewest
+// rounds ceil(S / (ILP + 1)) - a remainder row rides in a wider batch instead of costing a load round of its own
+// (C3, BS = 1024: 17 streamed rows = 4 + 4 + 4 + 5, not 4 x 4 + a fifth batch of one real row and three padding rows).
+// Rows past `rows` that the last ILP-batch covers (S < ILP * rounds) are padding records.
+struct SweepStreamPlan { int n_a, n_b; };
+static SweepStreamPlan sweep_stream_plan(int64_t P, int bs, int tr, int ilp) {
+  const int64_t rows = ceil_div(P, (int64_t)bs), S = std::max<int64_t>(0, rows - tr);
+  const int64_t rounds = ceil_div(S, (int64_t)(ilp + 1));
+  const int64_t n_b = std::max<int64_t>(0, S - ilp * rounds);
+  return {(int)(rounds - n_b), (int)n_b};
 }
 
 // TR = records per thread kept in registers (compile time, fully unrolled); records beyond
-// TR*1024 are streamed as 8-byte words. ILP = records whose loads are issued together.
+// TR*BS are streamed as 8-byte words. ILP = records whose loads are issued together.
 template <int TR, int ILP, bool BLK, int BS>
-__global__ __launch_bounds__(BS) void sweep_reg_kernel(int N, int R, int P, int B, int tile,
+__global__ __launch_bounds__(BS) void sweep_reg_kernel(int N, int R, int P, int B, int tile, int n_a, int n_b,
                                                          const uint2* __restrict__ rec64, const int32_t* __restrict__ copy_species,
                                                          int n_copy, const double* __restrict__ u,
                                                          const double* __restrict__ k_b, const double* __restrict__ k_1,
@@ -432,28 +482,21 @@ __global__ __launch_bounds__(BS) void sweep_reg_kernel(int N, int R, int P, int 
   double* u_s = lds + tile;
   const int tid = threadIdx.x;
   constexpr int UPT = 5;            // double2 per thread of the staged state (N <= BS0)
-  // padding record of this lane: all four fields on the lane's dummy entry
-  const uint64_t dl = (uint64_t)N + (uint64_t)(tid & 63);
-  const uint64_t ew = dl | (dl << 14) | (dl << 28) | (dl << 42);
-  const uint2 EMPTY = {(uint32_t)ew, (uint32_t)(ew >> 32)};
   if (tid < SWEEP_DUMMY) { u_s[N + tid] = 1.0; du_s[N + tid] = 0.0; }
   // split accumulators of the most referenced species (network.cpp): entry N + 64 + tid mirrors species csp
   const int csp = tid < n_copy ? copy_species[min(tid, max(n_copy - 1, 0))] : -1;
   if (csp >= 0) du_s[N + SWEEP_DUMMY + tid] = 0.0;
-  // Every global load below is UNCONDITIONAL (indices clamped into valid memory; a record beyond the end is the lane's
-  // padding record, whose rate constants meet dummy entries): a load behind a branch makes the compiler wait for
-  // vmcnt(0) wherever it cannot count the loads in flight - before the state's barrier (draining the prefetched rate
-  // constants), between the batches of the register-resident records and in the streamed loop (tiled_kernels.hip has
-  // the same rule and the measurement behind it).
+  // Every global load below is UNCONDITIONAL and no loaded VALUE decides what is loaded next. Rate-constant indices are
+  // clamped into valid memory (address arithmetic only); the record array is padded on the host with all-dummy records
+  // behind the P real ones (network.cpp, SWEEP_REC_PAD), so a record beyond the end is read as it stands and its rate
+  // constants meet dummy entries. A load behind a branch makes the compiler wait for vmcnt(0) wherever it cannot count
+  // the loads in flight; a select on a loaded record word (the former `p < P ? q : EMPTY`) made it wait for that word
+  // in the middle of a batch - and, loads returning in order, for every rate-constant load queued ahead of it
+  // (tiled_kernels.hip has the same rule and the measurement behind it).
   const int Pm1 = P - 1, Bm1 = B - 1, csp_c = max(csp, 0);
   uint2 rc[TR > 0 ? TR : 1];
 #pragma unroll
-  for (int i = 0; i < TR; i++) {
-    const int p = tid + i * BS;
-    const uint2 w = rec64[min(p, Pm1)];
-    rc[i].x = p < P ? w.x : EMPTY.x;
-    rc[i].y = p < P ? w.y : EMPTY.y;
-  }
+  for (int i = 0; i < TR; i++) rc[i] = rec64[tid + i * BS];   // TR <= P / BS full rows (launch_sweep)
   // software pipeline over states: the next state's u travels HBM -> registers while this state's
   // reactions are processed; du is written out and re-zeroed in one pass. N is even (host check).
   double2 un[UPT];
@@ -469,14 +512,15 @@ __global__ __launch_bounds__(BS) void sweep_reg_kernel(int N, int R, int P, int 
   }
   for (int i = tid * 2; i < N; i += (2 * BS)) *reinterpret_cast<double2*>(du_s + i) = make_double2(0.0, 0.0);
   double ucn = u[(size_t)min(b, Bm1) * N + csp_c];
-  // the first batch of rate constants of a state is requested before the previous state's barrier /
-  // write-out / staging, so the k stream does not drain at state boundaries
+  // the rate constants of a state's register-resident rows (both batches) are requested before the previous
+  // state's barrier / write-out / staging, so the k stream does not drain at state boundaries
   constexpr bool KPRE = TR >= ILP;
-  double2 k0[KPRE ? ILP : 1];
+  constexpr int KP = TR >= 2 * ILP ? 2 * ILP : ILP;
+  double2 k0[KPRE ? KP : 1];
   if (KPRE) {
     const double* kb = k_b ? k_b + (size_t)min(b, Bm1) * R : k_1;
 #pragma unroll
-    for (int x = 0; x < ILP; x++) k0[x] = load_kpair<BLK>(kb, min(tid + x * BS, Pm1), P);
+    for (int x = 0; x < KP; x++) k0[x] = load_kpair<BLK>(kb, min(tid + x * BS, Pm1), P);
   }
   for (; b < B; b += gridDim.x) {
     const double* kb = k_b ? k_b + (size_t)b * R : k_1;
@@ -498,14 +542,18 @@ __global__ __launch_bounds__(BS) void sweep_reg_kernel(int N, int R, int P, int 
         un[x].x = t.x; un[x].y = t.y;
       }
     }
+    // (the lane's row offsets do not depend on the state: opaque, or they are all hoisted out of the state loop and
+    // held in registers - one per row in flight - next to the records)
+    int tl = tid;
+    asm volatile("" : "+v"(tl));
     // register-resident records
 #pragma unroll
     for (int i0 = 0; i0 < TR; i0 += ILP) {
       double2 kk[ILP];
 #pragma unroll
       for (int x = 0; x < ILP; x++) {
-        if (KPRE && i0 == 0) kk[x] = k0[x];
-        else kk[x] = load_kpair<BLK>(kb, min(tid + (i0 + x) * BS, Pm1), P);
+        if (KPRE && i0 + x < KP) kk[x] = k0[i0 + x];
+        else kk[x] = load_kpair<BLK>(kb, min(tl + (i0 + x) * BS, Pm1), P);
       }
 #pragma unroll
       for (int x = 0; x < ILP; x++) {
@@ -516,26 +564,16 @@ __global__ __launch_bounds__(BS) void sweep_reg_kernel(int N, int R, int P, int 
         sweep_apply(w, kk[x], u_s, du_s);
       }
     }
-    // streamed records
-    for (int p0 = tid + TR * BS; p0 < P; p0 += BS * ILP) {
-      double2 kk[ILP];
-      uint2 w[ILP];
-#pragma unroll
-      for (int x = 0; x < ILP; x++) {
-        const int p = p0 + x * BS;
-        const bool ok = p < P;
-        kk[x] = load_kpair<BLK>(kb, min(p, Pm1), P);
-        const uint2 q = rec64[min(p, Pm1)];
-        w[x].x = ok ? q.x : EMPTY.x;
-        w[x].y = ok ? q.y : EMPTY.y;
-      }
-#pragma unroll
-      for (int x = 0; x < ILP; x++) sweep_apply(w[x], kk[x], u_s, du_s);
+    // streamed records: n_a batches of ILP rows, then n_b batches of ILP + 1 (sweep_stream_plan)
+    {
+      int p0 = tl + TR * BS;
+      for (int r = 0; r < n_a; r++, p0 += BS * ILP) sweep_stream_batch<ILP, BLK, BS>(kb, rec64, p0, Pm1, P, u_s, du_s);
+      for (int r = 0; r < n_b; r++, p0 += BS * (ILP + 1)) sweep_stream_batch<ILP + 1, BLK, BS>(kb, rec64, p0, Pm1, P, u_s, du_s);
     }
     if (KPRE) {
       const double* kn = k_b ? k_b + (size_t)min(bn, Bm1) * R : k_1;
 #pragma unroll
-      for (int x = 0; x < ILP; x++) k0[x] = load_kpair<BLK>(kn, min(tid + x * BS, Pm1), P);
+      for (int x = 0; x < KP; x++) k0[x] = load_kpair<BLK>(kn, min(tl + x * BS, Pm1), P);
     }
     __syncthreads();
     if (n_copy > 0) {   // fold the split accumulators back into their species
@@ -546,9 +584,25 @@ __global__ __launch_bounds__(BS) void sweep_reg_kernel(int N, int R, int P, int 
       }
       __syncthreads();
     }
-    for (int i = tid * 2; i < N; i += (2 * BS)) {
-      *reinterpret_cast<double2*>(dub + i) = *reinterpret_cast<double2*>(du_s + i);
-      *reinterpret_cast<double2*>(du_s + i) = make_double2(0.0, 0.0);
+    // Write-out: a fixed number of rounds, the LDS reads of all of them first, then the stores. A loop of unknown
+    // trip count leaves the compiler unable to count the stores in flight, and the next trip's staging - which waits
+    // for `un`, requested before everything else - then also waits for the rate constants prefetched above. du is
+    // written once and never read by this kernel: non-temporal, like the k stream, so that neither pushes the records
+    // and the next states' u out of L2.
+    {
+      double2 v[UPT];
+#pragma unroll
+      for (int x = 0; x < UPT; x++) v[x] = *reinterpret_cast<double2*>(du_s + min((tid + x * BS) * 2, N - 2));
+#pragma unroll
+      for (int x = 0; x < UPT; x++) {
+        const int i = (tid + x * BS) * 2;
+        if (i < N) {
+          kin_d2 t;
+          t.x = v[x].x; t.y = v[x].y;
+          __builtin_nontemporal_store(t, reinterpret_cast<kin_d2*>(dub + i));
+          *reinterpret_cast<double2*>(du_s + i) = make_double2(0.0, 0.0);
+        }
+      }
     }
     // no barrier needed here: the next trip only touches u_s before its own barrier
   }
@@ -560,8 +614,10 @@ static void launch_sweep_reg_t(int grid, size_t smem, int N, int R, int P, int B
                                double* du, hipStream_t s) {
   // per launch, not cached: the attribute belongs to the (function, device) pair and costs ~1 us
   KIN_HIP(hipFuncSetAttribute((const void*)sweep_reg_kernel<TR, ILP, BLK, BS>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  hipLaunchKernelGGL((sweep_reg_kernel<TR, ILP, BLK, BS>), dim3(grid), dim3(BS), smem, s, N, R, P, B, tile, (const uint2*)rec64,
-                     copy_species, n_copy, u, k_b, k_1, du);
+  const SweepStreamPlan plan = sweep_stream_plan(P, BS, TR, ILP);
+  static_assert(2 * ILP <= SWEEP_REC_PAD / 1024, "a batch that starts in the last row must stay inside the padded record array");
+  hipLaunchKernelGGL((sweep_reg_kernel<TR, ILP, BLK, BS>), dim3(grid), dim3(BS), smem, s, N, R, P, B, tile, plan.n_a, plan.n_b,
+                     (const uint2*)rec64, copy_species, n_copy, u, k_b, k_1, du);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -576,7 +632,8 @@ static void launch_sweep_reg_t(int grid, size_t smem, int N, int R, int P, int B
 // ------------------------------------------------------------------------------------------
 template <int BS>
 __global__ __launch_bounds__(BS) void sweep_gen_kernel(int N, int R, int P, int B, int tile, const uint2* __restrict__ rec8,
-                                                         const int2* __restrict__ pair_k, const SweepRec* __restrict__ rec,
+                                                         const int2* __restrict__ gen_k, const int2* __restrict__ pair_k,
+                                                         const SweepRec* __restrict__ rec,
                                                          const int32_t* __restrict__ expl, int n_expl,
                                                          const double* __restrict__ u, const double* __restrict__ k_b,
                                                          const double* __restrict__ k_1, double* __restrict__ du) {
@@ -585,8 +642,6 @@ __global__ __launch_bounds__(BS) void sweep_gen_kernel(int N, int R, int P, int 
   double* u_s = lds + tile;
   const int tid = threadIdx.x;
   constexpr int ILP = 4;
-  const uint32_t dl = (uint32_t)(N + (tid & 63));
-  const uint2 EMPTY = {dl | (dl << 16), dl | (dl << 16)};
   if (tid < SWEEP_DUMMY) { u_s[N + tid] = 1.0; du_s[N + tid] = 0.0; }
   for (int i = tid; i < N; i += BS) du_s[i] = 0.0;
   // the next state's u travels HBM -> registers while this state's records are processed (N <= 10176)
@@ -594,7 +649,7 @@ __global__ __launch_bounds__(BS) void sweep_gen_kernel(int N, int R, int P, int 
   double un[UPT];
   int b = blockIdx.x;
 #pragma unroll
-  for (int x = 0; x < UPT; x++) { const int i = tid + x * BS; un[x] = (b < B && i < N) ? u[(size_t)b * N + i] : 0.0; }
+  for (int x = 0; x < UPT; x++) un[x] = u[(size_t)min(b, B - 1) * N + min(tid + x * BS, N - 1)];   // clamped, never behind a branch
   for (; b < B; b += gridDim.x) {
     const double* kb = k_b ? k_b + (size_t)b * R : k_1;
     double* dub = du + (size_t)b * N;
@@ -603,7 +658,11 @@ __global__ __launch_bounds__(BS) void sweep_gen_kernel(int N, int R, int P, int 
     __syncthreads();
     const int bn = b + gridDim.x;
 #pragma unroll
-    for (int x = 0; x < UPT; x++) { const int i = tid + x * BS; un[x] = (bn < B && i < N) ? u[(size_t)bn * N + i] : 0.0; }
+    for (int x = 0; x < UPT; x++) un[x] = u[(size_t)min(bn, B - 1) * N + min(tid + x * BS, N - 1)];
+    // Same rules as sweep_reg_kernel: rec8 and gen_k are padded on the host behind the P real records (all-dummy
+    // labels, reaction indices (0, -1)), so the first load group - records and index pairs of the whole batch - is
+    // unconditional and issued back to back; the dependent gather kb[index] is the second group, its index clamped
+    // (kr = -1: no reverse) and the 0.0 of a missing reverse selected only after the last load has been issued.
     for (int qq = tid; qq < P; qq += BS * ILP) {
       uint2 w[ILP];
       int2 ki[ILP];
@@ -611,14 +670,18 @@ __global__ __launch_bounds__(BS) void sweep_gen_kernel(int N, int R, int P, int 
 #pragma unroll
       for (int x = 0; x < ILP; x++) {
         const int p = qq + x * BS;
-        w[x] = p < P ? rec8[p] : EMPTY;
-        ki[x] = p < P ? pair_k[p] : make_int2(-1, -1);
+        w[x] = rec8[p];
+        ki[x] = gen_k[p];
       }
+      __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int x = 0; x < ILP; x++) {
-        kf[x] = ki[x].x >= 0 ? kb[ki[x].x] : 0.0;
-        kr[x] = ki[x].y >= 0 ? kb[ki[x].y] : 0.0;
+        kf[x] = kb[ki[x].x];
+        kr[x] = kb[max(ki[x].y, 0)];
       }
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int x = 0; x < ILP; x++) kr[x] = ki[x].y >= 0 ? kr[x] : 0.0;
 #pragma unroll
       for (int x = 0; x < ILP; x++) {
         const uint32_t l0 = w[x].x & 0xffffu, l1 = w[x].x >> 16, l2 = w[x].y & 0xffffu, l3 = w[x].y >> 16;
@@ -635,6 +698,7 @@ __global__ __launch_bounds__(BS) void sweep_gen_kernel(int N, int R, int P, int 
         __hip_atomic_fetch_add(du_s + l2, net, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         __hip_atomic_fetch_add(du_s + l3, net, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
       }
+      __builtin_amdgcn_sched_barrier(0);
     }
     // reactions with a species on both sides: net = kf u[a] u[c], coefficients from the 16-byte record
     for (int i = tid; i < n_expl; i += BS) {
@@ -858,8 +922,9 @@ static void launch_sweep_t(int grid, size_t smem, int N, int R, int P, int B, in
 }
 
 void launch_sweep(int n_cu, int64_t N, int64_t R, int64_t P, int64_t B, bool adjacent, bool block, const void* rec, const void* pair_k,
-                  const void* rec64, const int32_t* copy_species, int n_copy, const void* gen_rec8, const int32_t* gen_expl,
-                  int n_gen_expl, const double* u, const double* k_b, const double* k_1, double* du, hipStream_t s) {
+                  const void* rec64, const int32_t* copy_species, int n_copy, const void* gen_rec8, const void* gen_k,
+                  const int32_t* gen_expl, int n_gen_expl, const double* u, const double* k_b, const double* k_1, double* du,
+                  hipStream_t s) {
   if (B == 0) return;
   const size_t lds_max = 160 * 1024;
   const int grid = (int)std::min<int64_t>(B, n_cu);
@@ -868,10 +933,7 @@ void launch_sweep(int n_cu, int64_t N, int64_t R, int64_t P, int64_t B, bool adj
   if ((size_t)(2 * N) * 8 <= lds_max) {
     const int tile = (int)((N + 1) / 2 * 2);
     const size_t smem = (size_t)(tile + N) * 8;
-    constexpr int use_reg = 8;
-    // register-resident path: both LDS arrays carry SWEEP_DUMMY extra entries (per-lane dummy species)
-    // register-resident path: reactions paired as (2p, 2p+1) [adjacent] or (p, P+p) [block]
-    if ((adj || block) && rec64 && use_reg >= 0 && ((((uintptr_t)u) | ((uintptr_t)du)) & 15) == 0 && N % 2 == 0 &&
+    if ((adj || block) && rec64 && R < ((int64_t)1 << 29) && ((((uintptr_t)u) | ((uintptr_t)du)) & 15) == 0 && N % 2 == 0 &&
         (size_t)(2 * (N + SWEEP_DUMMY + n_copy)) * 8 <= lds_max && n_copy <= 1024) {
       const int rtile = (int)N + SWEEP_DUMMY + n_copy + (n_copy & 1);   // even: keeps u_s 16-byte aligned
       const size_t rsmem = (size_t)2 * rtile * 8;
@@ -888,13 +950,11 @@ void launch_sweep(int n_cu, int64_t N, int64_t R, int64_t P, int64_t B, bool adj
     else if (bs == 512) { if (adj) launch_sweep_reg_t<TT, II, false, 512>(KIN_REG_ARGS); else launch_sweep_reg_t<TT, II, true, 512>(KIN_REG_ARGS); } \
     else { if (adj) launch_sweep_reg_t<TT, II, false, 1024>(KIN_REG_ARGS); else launch_sweep_reg_t<TT, II, true, 1024>(KIN_REG_ARGS); }       \
   } while (0)
-      const int want = (int)std::min<int64_t>(use_reg, Tr);
-      if (want >= 16) KIN_REG_GO(16, 4);
-      else if (want >= 12) KIN_REG_GO(12, 4);
-      else if (want >= 8) KIN_REG_GO(8, 4);
-      else if (want >= 4) KIN_REG_GO(4, 4);
-      else if (use_reg == 1) KIN_REG_GO(0, 8);
-      else KIN_REG_GO(0, 4);
+      // two register-resident batches where the network has the rows for them, else one, else none
+      constexpr int I = KIN_SWEEP_ILP;
+      if (Tr >= 2 * I) KIN_REG_GO(2 * I, I);
+      else if (Tr >= I) KIN_REG_GO(I, I);
+      else KIN_REG_GO(0, I);
 #undef KIN_REG_GO
 #undef KIN_REG_ARGS
       KIN_HIP(hipGetLastError());
@@ -910,7 +970,8 @@ void launch_sweep(int n_cu, int64_t N, int64_t R, int64_t P, int64_t B, bool adj
   do {                                                                                                                                  \
     KIN_HIP(hipFuncSetAttribute((const void*)sweep_gen_kernel<BSZ>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));           \
     hipLaunchKernelGGL(sweep_gen_kernel<BSZ>, dim3(ggrid), dim3(BSZ), gsmem, s, (int)N, (int)R, (int)P, (int)B, gtile,                  \
-                       (const uint2*)gen_rec8, (const int2*)pair_k, (const SweepRec*)rec, gen_expl, n_gen_expl, u, k_b, k_1, du);       \
+                       (const uint2*)gen_rec8, (const int2*)gen_k, (const int2*)pair_k, (const SweepRec*)rec, gen_expl, n_gen_expl,     \
+                       u, k_b, k_1, du);                                                                                                \
   } while (0)
       if (bs == 256) KIN_GEN_GO(256);
       else if (bs == 512) KIN_GEN_GO(512);

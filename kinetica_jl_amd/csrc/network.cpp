@@ -286,6 +286,12 @@ NetworkHost compile_network(int64_t N, int64_t R, const int64_t* reac_ptr, const
           H.pair_rec64.push_back((uint32_t)w);
           H.pair_rec64.push_back((uint32_t)(w >> 32));
         }
+        for (int64_t p = P; P > 0 && p < P + SWEEP_REC_PAD; p++) {   // padding records (network.hpp)
+          const uint64_t d = (uint64_t)N + (uint64_t)(p & 63);
+          const uint64_t w = d | (d << 14) | (d << 28) | (d << 42);
+          H.pair_rec64.push_back((uint32_t)w);
+          H.pair_rec64.push_back((uint32_t)(w >> 32));
+        }
       }
     }
     // ---- general fixed-role records (state fits LDS, pairing irregular): kernels.hip sweep_gen_kernel
@@ -309,6 +315,14 @@ NetworkHost compile_network(int64_t N, int64_t R, const int64_t* reac_ptr, const
         }
         H.gen_rec8.push_back(side[0][0] | (side[0][1] << 16));
         H.gen_rec8.push_back(side[1][0] | (side[1][1] << 16));
+      }
+      H.gen_k = H.pair_k;
+      for (int64_t p = P; P > 0 && p < P + SWEEP_REC_PAD; p++) {   // padding records (network.hpp)
+        const uint32_t d = (uint32_t)N + (uint32_t)(p & 63);
+        H.gen_rec8.push_back(d | (d << 16));
+        H.gen_rec8.push_back(d | (d << 16));
+        H.gen_k.push_back(0);
+        H.gen_k.push_back(-1);
       }
     }
     // ---- large-N sweep tables (only when the state cannot live in LDS)

@@ -59,6 +59,10 @@ SegPlanHost build_seg_plan(int64_t n_rows, const int32_t* ptr, const int32_t* ds
                            const int32_t* b, const float* c, bool skip_empty, const int32_t* aux = nullptr,
                            std::vector<int32_t>* slot_of_entry = nullptr);
 
+// records of padding behind the streamed sweep arrays: 16 rows of the widest workgroup (1024 threads), twice what the widest
+// batch plan reads past the last record (kernels.hip: a batch of at most 8 rows)
+constexpr int64_t SWEEP_REC_PAD = 16 * 1024;
+
 struct NetworkHost {
   int64_t N = 0, R = 0;
   // per reaction: rate operands, rate = k * u[x0] * (x1 >= 0 ? u[x1] : 1)   (2A: x0 == x1)
@@ -78,7 +82,12 @@ struct NetworkHost {
   // pair_k[2p+1]'s companion word pair_ops (explicit operands).
   std::vector<uint32_t> pair_rec;  // 4 words per record: s01, s23, coefs, ops (explicit operands for unpaired records)
   std::vector<int32_t> pair_k;     // 2 per record: kf, kr
+  // The arrays the LDS sweeps stream without bounds tests (pair_rec64, gen_rec8, gen_k) carry SWEEP_REC_PAD all-dummy
+  // records behind the n_pairs() real ones: all four labels N + (p mod 64) - the rule unused fields follow - and, in
+  // gen_k, reaction indices (0, -1). A batch of rows that reaches past the last record reads them as they stand
+  // (kernels.hip). n_pairs() and everything derived from it count pair_k, which is never padded.
   std::vector<uint32_t> gen_rec8;   // 2 words per record: fixed-role 16-bit labels for the general LDS sweep (state fits LDS)
+  std::vector<int32_t> gen_k;       // 2 per record: pair_k, padded for the same sweep
   std::vector<int32_t> gen_expl;    // records with explicit operands
   std::vector<int32_t> sweep_copy_species;   // species behind every extra accumulator entry (7 per split hub)
   std::vector<uint32_t> pair_rec64; // 2 words per record (four 14-bit labels with fixed roles, network.cpp); only when pairs_adjacent or pairs_block

@@ -54,6 +54,13 @@ def build():
         f"{rf['avg_launch_ms']:.4f} ms = {rf['achieved']:.0f} GB/s = **{rf['frac']:.3f} of 8 TB/s**", f"{src_b} `roofline`")
     add("headline sweep", "RHS evaluations per second (`value`)", f"{b['value'] / 1e6:.2f} M/s", f"{src_b} `value`")
     add("headline sweep", "HBM traffic (PMC, same run) / algorithmic bytes", f"{rf['traffic_over_algorithmic']:.3f}", f"{src_b} `roofline.traffic_over_algorithmic`")
+    ab = open(os.path.join(P, "sweep_issue_order_ab.txt")).read()
+    mp = re.search(r"parent: median ([\d.]+) ms, fastest ([\d.]+), slowest ([\d.]+)", ab)
+    mn = re.search(r"new:    median ([\d.]+) ms, fastest ([\d.]+), slowest ([\d.]+)", ab)
+    alg = rf["algorithmic_bytes_per_launch"]
+    add("headline sweep", "... after the batch issue order / state boundary change, 6 alternating plain runs on one machine: parent → new (median launch; slowest new < fastest parent)",
+        f"{float(mp.group(1)):.4f} → {float(mn.group(1)):.4f} ms = {alg / float(mp.group(1)) / 8e9:.3f} → **{alg / float(mn.group(1)) / 8e9:.3f} of 8 TB/s** ({mn.group(3)} < {mp.group(2)})",
+        "sweep_issue_order_ab.txt")
     pm = load(pick("sweep_pmc.json"))
     add("headline sweep", f"rocprofv3 average over {pm['calls']} launches (spin-up + timed + sustained)",
         f"{pm['avg_ns_rocprof'] / 1e3:.1f} µs (bench events in that run {pm['avg_launch_ms_bench_events'] * 1e3:.1f} µs)", pick("sweep_pmc.json"))

@@ -165,6 +165,34 @@ int kin_rhs_batched_T_dev(kin_network* h, int64_t B, const double* d_u, const do
  * correct at every size but cannot stream k once when the state does not fit LDS. Enqueue only. */
 int kin_rhs_batched_klib_dev(kin_network* h, int64_t B, const double* d_u, const double* d_k_lib, double* d_du, void* stream);
 
+/* ---- N6: reaction-flux analysis (the "which reactions matter" companion of identify_next_seeds; the reference's
+ *      analysis/ works on sol.u after the solve) -------------------------------------------------------------------
+ * rate_r(u; k) = k_r u[x0_r] (x1_r >= 0 ? u[x1_r] : 1): the mass action of make_rs (solve_utils.jl:318-334) without 1/s!
+ * (2A gives u_a^2, an inert collider is an ordinary operand). For B states u[b][N]:
+ *   rates[b][r] = rate_r(u_b; k of state b)            (optional, unweighted)
+ *   flux[r]     = sum_b w[b] rates[b][r]               (optional; w == NULL: weights 1; B == 0 writes zeros)
+ * both in the caller's reaction order; at least one must be requested. State b's rate constants come from exactly one of
+ *   - row k_row[b] of k[rows][R] (k_row == NULL: row b),
+ *   - the handle's Arrhenius law at T[b] (evaluated as kin_rates_at does, inside the pass),
+ *   - the handle's current rates, when neither k nor T is given (a pending continuous-rate temperature is formed first).
+ * One pass over the states: per state the k row is streamed once, u is staged on chip, flux is reduced in a fixed order
+ * (bitwise reproducible for given B, R, N and device). The partial sums live in the handle and are grown on demand: the
+ * entry serves ONE stream per handle at a time and may allocate when B grows; afterwards it only enqueues.
+ * KIN_ERR_INVALID_ARG: both k and T; k_row without a k source; a row index out of range (host entries); neither output;
+ * B < 0. KIN_ERR_STATE: T without Arrhenius parameters; no rates at all; no stored solution; table rows asked for with no
+ * resident table. Added under KIN_ABI_VERSION 6: look the symbols up before calling them. */
+/* device buffers (d_k_row: B int64 row indices, not validated); enqueue only once the workspace has its size */
+int kin_flux_batched_dev(kin_network* h, int64_t B, const double* d_u, const double* d_k, const int64_t* d_k_row, const double* d_T,
+                         const double* d_w, double* d_flux, double* d_rates, void* stream);
+/* host buffers; k has n_k_rows rows (k_row validated against it; k_row == NULL needs n_k_rows == B) */
+int kin_flux_batched(kin_network* h, int64_t B, const double* u, const double* k, int64_t n_k_rows, const int64_t* k_row,
+                     const double* T, const double* w, double* flux, double* rates);
+/* the saved states of the last kin_solve / kin_solve_continuous / kin_solve_explicit, where they live (on the device):
+ * no copy of the trajectory. w[n_saved], T_rows[n_saved], k_row[n_saved]. k == NULL with k_row != NULL reads rows of the
+ * device-resident rate table (what kin_solve(k_table) / kin_rate_table left there). */
+int kin_solution_flux(kin_network* h, const double* w, const double* k, int64_t n_k_rows, const int64_t* k_row,
+                      const double* T_rows, double* flux, double* rates);
+
 /* ---- A3: analytic sparse Jacobian ---------------------------------------------------- */
 /* Replaces ODEProblem(...; jac=true, sparse=true) (methods.jl:157-158): pattern (CSR,
  * sorted columns, diagonal always present) and values for the current rates. The reference

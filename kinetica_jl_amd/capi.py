@@ -31,6 +31,7 @@ SYMBOLS = [
     "kin_rhs_tiled_dev", "kin_rhs_batched_T_dev", "kin_rhs_batched_klib_dev", "kin_abi_version", "kin_struct_size",
     "kin_solve_ensemble", "kin_lu_analyze_host", "kin_solve_ensemble_continuous", "kin_solve_ensemble_discrete",
     "kin_resident_probe", "kin_newton_probe",
+    "kin_flux_batched", "kin_flux_batched_dev", "kin_solution_flux",
 ]
 ABI_VERSION = 6   # include/kinetica_hip.h: KIN_ABI_VERSION this binding was written against
 
@@ -118,6 +119,10 @@ def lib():
             L.kin_resident_probe.argtypes = [c_void_p, c_int64, PD, PD, PD, PD, PD, PD, POINTER(c_int32), P64]
         if hasattr(L, "kin_newton_probe"):   # (also under ABI 6)
             L.kin_newton_probe.argtypes = [c_void_p, c_int64, c_int32, PD, PD, PD, PD, POINTER(c_int32), P64]
+        if hasattr(L, "kin_flux_batched"):   # (also under ABI 6: the reaction-flux pass)
+            L.kin_flux_batched.argtypes = [c_void_p, c_int64, PD, PD, c_int64, P64, PD, PD, PD, PD]
+            L.kin_flux_batched_dev.argtypes = [c_void_p, c_int64] + [c_void_p] * 8
+            L.kin_solution_flux.argtypes = [c_void_p, PD, PD, c_int64, P64, PD, PD, PD]
         L.kin_solve_ensemble.argtypes = [c_void_p, POINTER(KinParams), c_int64, PD, PD, PD, PD, PD, PD, c_int64, P64, PD, PD, P64,
                                          POINTER(c_int32), POINTER(KinStats)]
         L.kin_integrator_init.argtypes = [c_void_p, POINTER(KinParams), PD, PD, PD, PD, c_int64]
@@ -298,6 +303,60 @@ class HipNetwork:
         """Device pointers (ints), state-major u[b][N], k[b][R] or 0, du[b][N]; only enqueues."""
         self._chk(lib().kin_rhs_batched_dev(self._h, int(B), c_void_p(d_u), c_void_p(d_k) if d_k else None,
                                             c_void_p(d_du), c_void_p(stream) if stream else None))
+
+    # --- reaction fluxes ---------------------------------------------------------------------
+    def _flux_inputs(self, B, k, k_row, T, w):
+        """Contiguous float64 / int64 views of the optional inputs of the flux entries, shapes checked against B."""
+        n_rows = 0
+        if k is not None:
+            k = np.ascontiguousarray(np.atleast_2d(_f64(k)))
+            assert k.ndim == 2 and k.shape[1] == self.nr
+            n_rows = k.shape[0]
+        if k_row is not None:
+            k_row = np.ascontiguousarray(k_row, dtype=np.int64).ravel()
+            assert len(k_row) == B
+        if T is not None:
+            T = np.ascontiguousarray(_f64(T).ravel())
+            assert len(T) == B
+        if w is not None:
+            w = np.ascontiguousarray(_f64(w).ravel())
+            assert len(w) == B
+        return k, n_rows, k_row, T, w
+
+    def flux_batched(self, u, k=None, k_row=None, T=None, w=None, want_rates=False, want_flux=True):
+        """kin_flux_batched on host arrays: per-reaction rates of the states u[B][N], rate_r = k_r u[x0_r] u[x1_r], and their
+        weighted sum flux[R] = sum_b w[b] rate_r(u_b) (w=None: weights 1). Rate constants of state b: row k_row[b] of k
+        (k_row=None: row b), or the Arrhenius law at T[b], or the handle's current rates. Returns flux[R], or
+        (flux, rates[B][R]) with want_rates (flux is None with want_flux=False)."""
+        u = np.ascontiguousarray(np.atleast_2d(_f64(u)))
+        B = u.shape[0]
+        assert u.shape == (B, self.n)
+        k, n_rows, k_row, T, w = self._flux_inputs(B, k, k_row, T, w)
+        flux = np.empty(self.nr) if want_flux else None
+        rates = np.empty((B, self.nr)) if want_rates else None
+        self._chk(lib().kin_flux_batched(self._h, B, _pd(u), _pd(k), n_rows, None if k_row is None else _p64(k_row), _pd(T), _pd(w),
+                                         _pd(flux), _pd(rates)))
+        return (flux, rates) if want_rates else flux
+
+    def flux_batched_dev(self, B, d_u, d_k=0, d_k_row=0, d_T=0, d_w=0, d_flux=0, d_rates=0, stream=0):
+        """kin_flux_batched_dev: device pointers (ints; 0 = not given), u[B][N], k rows / k_row[B] (int64) / T[B], w[B],
+        flux[R] and / or rates[B][R]. One stream per handle at a time; allocates only when the workspace has to grow."""
+        p = lambda x: c_void_p(x) if x else None
+        self._chk(lib().kin_flux_batched_dev(self._h, int(B), p(d_u), p(d_k), p(d_k_row), p(d_T), p(d_w), p(d_flux), p(d_rates),
+                                             p(stream)))
+
+    def solution_flux(self, w=None, k=None, k_row=None, T_rows=None, want_rates=False, want_flux=True):
+        """kin_solution_flux: flux_batched over the saved states of the last solve, read where they live on the device.
+        k=None with k_row reads rows of the device-resident rate table (solve(k_table=...) / rate_table leave it there)."""
+        n_saved = c_int64(0)
+        self._chk(lib().kin_solution_size(self._h, ctypes.byref(n_saved), None))
+        B = n_saved.value
+        k, n_rows, k_row, T_rows, w = self._flux_inputs(B, k, k_row, T_rows, w)
+        flux = np.empty(self.nr) if want_flux else None
+        rates = np.empty((B, self.nr)) if want_rates else None
+        self._chk(lib().kin_solution_flux(self._h, _pd(w), _pd(k), n_rows, None if k_row is None else _p64(k_row), _pd(T_rows),
+                                          _pd(flux), _pd(rates)))
+        return (flux, rates) if want_rates else flux
 
     # --- library order (tiled sweep) --------------------------------------------------------
     def lib_layout(self):

@@ -1,0 +1,143 @@
+// extern "C" entry points of the reaction-flux pass (declarations: include/kinetica_hip.h; kernels: flux_kernels.hip).
+#include "../../include/kinetica_hip.h"
+
+#include <algorithm>
+
+#include "flux_kernels.hpp"
+#include "handle.hpp"
+
+using namespace kin;
+
+namespace {
+
+void require(bool c, int code, const char* msg) {
+  if (!c) throw KinError(code, msg);
+}
+
+// where a call's rate constants come from: rows of k (k_stride doubles apart; 0 = one shared row) or the Arrhenius law at T[b]
+struct FluxSource { const double* k; int64_t k_stride; const int64_t* k_row; const double* T; };
+
+// checks shared by the three entry points (have_k: a rate-constant array or, for kin_solution_flux, the resident table)
+void flux_check(kin_network* h, int64_t B, bool have_k, bool have_row, bool have_T, bool have_out) {
+  require(B >= 0, ERR_INVALID_ARG, "B < 0");
+  require(have_out, ERR_INVALID_ARG, "neither flux nor rates requested");
+  require(!(have_k && have_T), ERR_INVALID_ARG, "give rate constants or temperatures, not both");
+  require(!have_row || have_k, ERR_INVALID_ARG, "k_row given without rate constants to index");
+  require(!have_T || h->has_arrhenius, ERR_STATE, "temperatures given but Arrhenius parameters were never set");
+  require(have_k || have_T || h->has_rates, ERR_STATE, "rates were never set and neither k nor T given");
+  require(h->host.R < ((int64_t)1 << 28) && B < ((int64_t)1 << 31), ERR_UNSUPPORTED, "flux pass: B or R beyond 32-bit offsets");
+}
+
+// The pass itself on device buffers: grows the handle's workspace (may allocate when B or the plan grows), then enqueues.
+void flux_run(kin_network* h, int64_t B, const double* d_u, const FluxSource& src, const double* d_w, double* d_flux,
+              double* d_rates, hipStream_t s) {
+  const int64_t N = h->host.N, R = h->host.R;
+  if (B == 0 || R == 0) {
+    if (d_flux && R > 0) KIN_HIP(hipMemsetAsync(d_flux, 0, (size_t)R * sizeof(double), s));
+    return;
+  }
+  if (!h->flux_ready) {
+    const FluxTables t = build_flux_tables(h->host);
+    if (!t.idx16.empty()) h->flux_idx16.upload(t.idx16, s);
+    h->flux_idx32.upload(t.idx32, s);
+    KIN_HIP(hipStreamSynchronize(s));   // the host vectors die here
+    h->flux_ready = true;
+  }
+  if (!src.k && !src.T) h->flush_pending_T(s);   // the handle's own k is about to be read
+  const FluxPlan plan = flux_plan(B, R, N, h->n_cu, src.T != nullptr, (reinterpret_cast<uintptr_t>(d_u) & 15) == 0);
+  if (d_flux) h->flux_part.alloc((size_t)plan.G * (size_t)R);
+  FluxArgs a{};
+  a.N = (int)N; a.R = (int)R; a.P = (int)((R + 1) / 2); a.B = (int)B;
+  a.idx16 = reinterpret_cast<const uint2*>(h->flux_idx16.p);
+  a.idx32 = reinterpret_cast<const int4*>(h->flux_idx32.p);
+  a.u = d_u;
+  if (src.T) a.T = src.T;
+  else if (src.k) { a.k = src.k; a.k_stride = src.k_stride; a.k_row = src.k_row; }
+  else { a.k = h->k.p; a.k_stride = 0; a.k_row = nullptr; }
+  a.Ea = h->Ea.p; a.A = h->A.p; a.has_kmax = h->has_kmax ? 1 : 0; a.k_max = h->k_max; a.t_mult = h->t_mult;
+  a.w = d_w;
+  a.part = d_flux ? h->flux_part.p : nullptr;
+  a.rates = d_rates;
+  launch_flux_sweep(plan, a, s);
+  if (d_flux) launch_flux_reduce(R, plan.G, h->flux_part.p, d_flux, s);
+}
+
+void check_rows(const int64_t* k_row, int64_t B, int64_t n_rows) {
+  for (int64_t b = 0; b < B; b++) require(k_row[b] >= 0 && k_row[b] < n_rows, ERR_INVALID_ARG, "k_row: row index out of range");
+}
+
+}  // namespace
+
+#define KIN_TRY(h) try { KIN_HIP(hipSetDevice((h)->device));
+#define KIN_CATCH(h)                                                        \
+  }                                                                         \
+  catch (const KinError& e) { (h)->err = e.what(); return e.code; }         \
+  catch (const std::exception& e) { (h)->err = e.what(); return KIN_ERR_DEVICE; } \
+  return KIN_OK;
+
+extern "C" {
+
+int kin_flux_batched_dev(kin_network* h, int64_t B, const double* d_u, const double* d_k, const int64_t* d_k_row, const double* d_T,
+                         const double* d_w, double* d_flux, double* d_rates, void* stream) {
+  if (!h) return KIN_ERR_INVALID_ARG;
+  KIN_TRY(h)
+  flux_check(h, B, d_k != nullptr, d_k_row != nullptr, d_T != nullptr, d_flux || d_rates);
+  require(d_u != nullptr || B == 0, ERR_INVALID_ARG, "null state buffer");
+  hipStream_t s = stream ? (hipStream_t)stream : h->stream;
+  flux_run(h, B, d_u, FluxSource{d_k, h->host.R, d_k_row, d_T}, d_w, d_flux, d_rates, s);
+  KIN_CATCH(h)
+}
+
+int kin_flux_batched(kin_network* h, int64_t B, const double* u, const double* k, int64_t n_k_rows, const int64_t* k_row,
+                     const double* T, const double* w, double* flux, double* rates) {
+  if (!h) return KIN_ERR_INVALID_ARG;
+  KIN_TRY(h)
+  flux_check(h, B, k != nullptr, k_row != nullptr, T != nullptr, flux || rates);
+  require(u != nullptr || B == 0, ERR_INVALID_ARG, "null state buffer");
+  if (k && k_row) { require(n_k_rows >= 1 || B == 0, ERR_INVALID_ARG, "k has no rows"); check_rows(k_row, B, n_k_rows); }
+  else if (k) require(n_k_rows == B, ERR_INVALID_ARG, "k without k_row needs one row per state (n_k_rows == B)");
+  const int64_t N = h->host.N, R = h->host.R;
+  hipStream_t s = h->stream;
+  if (B > 0) h->f_u.upload(u, (size_t)B * N, s);
+  if (k && n_k_rows > 0) h->f_k.upload(k, (size_t)n_k_rows * R, s);
+  if (k_row && B > 0) h->f_krow.upload(k_row, (size_t)B, s);
+  if (T && B > 0) h->f_T.upload(T, (size_t)B, s);
+  if (w && B > 0) h->f_w.upload(w, (size_t)B, s);
+  if (flux) h->f_flux.alloc((size_t)R);
+  if (rates) h->f_rates.alloc((size_t)B * R);
+  flux_run(h, B, h->f_u.p, FluxSource{k ? h->f_k.p : nullptr, R, k_row ? h->f_krow.p : nullptr, T ? h->f_T.p : nullptr},
+           w ? h->f_w.p : nullptr, flux ? h->f_flux.p : nullptr, rates ? h->f_rates.p : nullptr, s);
+  if (flux) h->f_flux.download(flux, (size_t)R, s);
+  if (rates) h->f_rates.download(rates, (size_t)B * R, s);
+  KIN_HIP(hipStreamSynchronize(s));
+  KIN_CATCH(h)
+}
+
+int kin_solution_flux(kin_network* h, const double* w, const double* k, int64_t n_k_rows, const int64_t* k_row,
+                      const double* T_rows, double* flux, double* rates) {
+  if (!h) return KIN_ERR_INVALID_ARG;
+  KIN_TRY(h)
+  const int64_t B = h->n_saved, R = h->host.R;
+  const bool table = !k && k_row;    // rows of the device-resident rate table
+  flux_check(h, B, k != nullptr || table, k_row != nullptr, T_rows != nullptr, flux || rates);
+  require(B > 0, ERR_STATE, "no solution stored");
+  require(!table || h->table_rows > 0, ERR_STATE, "no rate table resident (kin_rate_table / kin_solve with a table first)");
+  if (k_row) check_rows(k_row, B, table ? h->table_rows : n_k_rows);
+  else if (k) require(n_k_rows == B, ERR_INVALID_ARG, "k without k_row needs one row per saved state (n_k_rows == n_saved)");
+  hipStream_t s = h->stream;
+  if (k) h->f_k.upload(k, (size_t)n_k_rows * R, s);
+  if (k_row) h->f_krow.upload(k_row, (size_t)B, s);
+  if (T_rows) h->f_T.upload(T_rows, (size_t)B, s);
+  if (w) h->f_w.upload(w, (size_t)B, s);
+  if (flux) h->f_flux.alloc((size_t)R);
+  if (rates) h->f_rates.alloc((size_t)B * R);
+  const double* ksrc = k ? h->f_k.p : (table ? h->table.p : nullptr);
+  flux_run(h, B, h->d_sol_u.p, FluxSource{ksrc, R, k_row ? h->f_krow.p : nullptr, T_rows ? h->f_T.p : nullptr},
+           w ? h->f_w.p : nullptr, flux ? h->f_flux.p : nullptr, rates ? h->f_rates.p : nullptr, s);
+  if (flux) h->f_flux.download(flux, (size_t)R, s);
+  if (rates) h->f_rates.download(rates, (size_t)B * R, s);
+  KIN_HIP(hipStreamSynchronize(s));
+  KIN_CATCH(h)
+}
+
+}  // extern "C"

@@ -55,6 +55,14 @@ struct kin_network {
   // batched sweep workspace
   kin::DevBuf<double> b_u, b_k, b_du;
 
+  // reaction-flux pass (flux_kernels.hpp, flux_api.cpp): index tables uploaded at the first call that needs them, the
+  // partial sums part[G][R] and the staging buffers of the host entries grown on demand
+  bool flux_ready = false;
+  kin::DevBuf<uint32_t> flux_idx16;
+  kin::DevBuf<int32_t> flux_idx32;
+  kin::DevBuf<double> flux_part, f_u, f_k, f_T, f_w, f_flux, f_rates;
+  kin::DevBuf<int64_t> f_krow;
+
   // tiled sweep in library order (tiled.hpp, tiled_api.cpp): built at the first call that needs it
   kin::TiledHost tiled;
   bool tiled_tried = false;

@@ -27,7 +27,8 @@ __all__ = ["SpeciesData", "RxData", "RxFilter", "get_filter_mask", "DummyKinetic
            "has_conditions", "setup_network", "ODESimulationParams", "StaticODESolve", "VariableODESolve",
            "HIPBDF", "HIPRK45", "ArrheniusRates", "solve_network", "identify_next_seeds", "insert_inert", "ODESolveOutput", "ODESolution", "tconvert", "make_u0", "apply_low_k_cutoff",
            "get_max_rates", "get_initial_rates", "calculate_discrete_rates",
-           "solve_network_ensemble"]   # EXTENSION: the reference has no ensemble call
+           "solve_network_ensemble",   # EXTENSION: the reference has no ensemble call
+           "flux_weights", "held_stop_index", "ReactionFluxes", "reaction_fluxes"]   # EXTENSION: post-hoc flux analysis
 
 _T_UNIT = {  # src/utils.jl:77-97
     "picoseconds": 1.0e-12, "ps": 1.0e-12, "nanoseconds": 1.0e-9, "ns": 1.0e-9, "microseconds": 1.0e-6, "us": 1.0e-6,
@@ -794,6 +795,114 @@ def solve_network_ensemble(methods, sd, rd, copy_network=True):
         sol = ODESolution(ti, ui, capi.RETCODE_NAMES[int(rcs[i])], k=sol_k, stats=st, umax=umax)
         out.append(ODESolveOutput(sd_a, rd_a, sol, sol_k, sol_vcs, m.pars, m.conditions))
     return out
+
+
+# ---- post-hoc reaction-flux analysis (EXTENSION, in the style of the reference's analysis/: works on an ODESolveOutput) ----
+def flux_weights(t):
+    """Trapezoid weights of the saved times t: sum_b w[b] f(t[b]) is the trapezoid rule for the integral of f over
+    [t[0], t[-1]]; the weights sum to t[-1] - t[0]. One row gives [0.0]. t must be strictly increasing (ValueError)."""
+    t = np.asarray(t, dtype=float).ravel()
+    if len(t) == 0:
+        raise ValueError("flux_weights needs at least one saved time")
+    dt = np.diff(t)
+    if np.any(dt <= 0):
+        raise ValueError("saved times must be strictly increasing")
+    w = np.zeros(len(t))
+    w[:-1] += 0.5 * dt
+    w[1:] += 0.5 * dt
+    return w
+
+
+def held_stop_index(t, tstops):
+    """Index of the stop whose rate constants hold at each saved time under kin_solve's zero-order hold:
+    searchsorted(tstops, t, side="right") - 1, clipped at 0 - a saved time equal to a stop takes that stop's rates, a time
+    before the first stop the first stop's."""
+    idx = np.searchsorted(np.asarray(tstops, dtype=float), np.asarray(t, dtype=float), side="right") - 1
+    return np.clip(idx, 0, None).astype(np.int64)
+
+
+@dataclass
+class ReactionFluxes:
+    """Result of reaction_fluxes: flux[R] = sum_b weights[b] rate_r(u_b) (time-integrated rate of every reaction of
+    `rd`), per species the gross production[N] = sum_r nu+_ir flux_r and consumption[N] = sum_r nu-_ir flux_r (their
+    difference is the net change the RHS integrates), the weights used and, if asked for, rates[B][R]."""
+    flux: np.ndarray
+    production: np.ndarray
+    consumption: np.ndarray
+    weights: np.ndarray
+    rates: Optional[np.ndarray] = None
+
+    def top(self, n):
+        """Ids (0-based positions in rd) of the n reactions of greatest |flux|, greatest first (ties: lower id first)."""
+        return np.argsort(-np.abs(self.flux), kind="stable")[:int(n)]
+
+    @classmethod
+    def from_flux(cls, flux, rd, n_species, weights, rates=None):
+        flux = np.asarray(flux, dtype=float)
+        prod, cons = np.zeros(n_species), np.zeros(n_species)
+        for r in range(rd.nr):
+            for sid, st in zip(rd.id_prods[r], rd.stoic_prods[r]):
+                prod[sid - 1] += st * flux[r]
+            for sid, st in zip(rd.id_reacs[r], rd.stoic_reacs[r]):
+                cons[sid - 1] += st * flux[r]
+        return cls(flux, prod, cons, np.asarray(weights, dtype=float), rates)
+
+
+def reaction_fluxes(out, calculator, weights="trapezoid", rates=False):
+    """Time-integrated rate of every reaction over the saved states of a solve - which reactions carried the flux, the
+    companion of identify_next_seeds' "which species matter". `out` is any ODESolveOutput (solve_network's, or one read
+    back by load_output); `calculator` must be the one the solve used: the low-k cutoff has already spliced it to `out.rd`
+    (lengths are checked as setup_network does, ValueError). `weights`: "trapezoid" (flux_weights(out.sol.t)), None
+    (weights 1: a plain sum over the saved states) or an array of one weight per saved time. `rates=True` also returns the
+    per-state rates[B][R].
+
+    The rate constants of a saved state are the ones the solve held there: a static solve (or a Dummy calculator, which is
+    constant) uses get_initial_rates; discrete updates use stop held_stop_index(t, tstops) - with the Arrhenius calculator
+    its temperature, evaluated on the device inside the pass, otherwise row k_row of sol_k.u; continuous updates use
+    T = sol_vcs["T"] at the saved times. One pass of the device's flux kernel (kin_flux_batched) over sol.u.
+
+    The trapezoid rule is exact to O(dt^2) between rate updates and first order across a stop, where k jumps: callers who
+    need more should save more often."""
+    sd, rd, conditions = out.sd, out.rd, out.conditions
+    setup_network(sd, rd, calculator)
+    t = np.asarray(out.sol.t, dtype=float)
+    u = np.ascontiguousarray(np.asarray(out.sol.u, dtype=float).reshape(len(t), sd.n))
+    if isinstance(weights, str):
+        if weights != "trapezoid":
+            raise ValueError('weights must be "trapezoid", None or an array of one weight per saved time')
+        w = flux_weights(t)
+    elif weights is None:
+        w = np.ones(len(t))
+    else:
+        w = np.asarray(weights, dtype=float).ravel()
+        if len(w) != len(t):
+            raise ValueError("weights must have one entry per saved time")
+    arr = isinstance(calculator, PrecalculatedArrheniusCalculator)
+    src = {}
+    if isstatic(conditions) or isinstance(calculator, DummyKineticCalculator):
+        src = dict(k=np.asarray(get_initial_rates(conditions, calculator), dtype=float)[None, :], k_row=np.zeros(len(t), np.int64))
+    elif conditions.discrete_updates:
+        if out.sol_k is None:
+            raise ValueError("a discrete-update solve output needs sol_k (the rate constants at the stops)")
+        held = held_stop_index(t, out.sol_k.t)
+        if arr and hasattr(out.sol_k, "T"):
+            src = dict(T=np.asarray(out.sol_k.T, dtype=float)[held])
+        else:
+            src = dict(k=np.asarray(out.sol_k.u, dtype=float), k_row=held)
+    elif arr:
+        prof = conditions.profiles[conditions.symbols.index("T")]
+        src = dict(T=np.full(len(t), float(prof.value)) if isstatic(prof) else np.asarray(out.sol_vcs["T"], dtype=float))
+    else:
+        raise ValueError("calculator does not support continuous rate updates")
+    h = capi.HipNetwork(*rd.flat(sd.n), index_base=1)
+    try:
+        if "T" in src:
+            h.set_arrhenius(calculator.Ea, calculator.A, calculator.k_max, calculator.t_mult)
+        res = h.flux_batched(u, w=w, want_rates=rates, **src)
+    finally:
+        h.close()
+    flux, rr = res if rates else (res, None)
+    return ReactionFluxes.from_flux(flux, rd, sd.n, w, rr)
 
 
 # ---- the consumer of a level's solve (src/exploration/explore_utils.jl:338-406) ---------------------------

@@ -390,6 +390,45 @@ int kin_newton_probe(kin_network* h, int64_t K, int32_t batched, const double* u
  * positions 0 .. m-1. KIN_ERR_UNSUPPORTED when the network does not fit the resident kernel, KIN_ERR_STATE without rates. */
 int kin_resident_probe(kin_network* h, int64_t K, const double* u, const double* c, const double* b, double* du, double* jac,
                        double* x, int32_t* bad, int64_t* info);
+/* Diagnostic: ONE operation of the BDF / Dormand-Prince step, run ONCE on the caller's state through the integrators' own launchers
+ * and kernels; everything the operation may write comes back (and everything it must not touch, so that can be checked too).
+ * path 0: the host-driven kernels (launch_bdf_*, launch_rk_*), K = n_entries = 1, n is the caller's (the handle gives the device
+ * and the stream); path 1: the corrector update fused into the solve's last gather launch (SparseLU::solve_newton), K = 1, n = the
+ * handle's species count, op = NEWTON only; path 2: the lockstep ensemble's batched kernels, K members and n_entries list entries
+ * in one launch (the list may permute the members or leave some out), n is the caller's.
+ *   state[K][KIN_STEP_ROWS][n], rows: 0-7 D; 8 y; 9 psi; 10 d; 11 scale; 12 f0; 13 f1; 14 ytmp; 15 cs; 16-22 the stage array
+ *     K[7]; 23 x (solution vector); 24 out; 25 y_new; 26 u; 27 b. Uploaded, operated on, downloaded whole.
+ *   ctrl[K][KIN_STEP_CTRL]: BdfCtrl as doubles - dy_norm_old, dy_norm, err_norm, err_m_norm, err_p_norm, crate, scratch[0..3],
+ *     newton_done, converged, n_iter, nonfinite, any_negative, ticket, lu_bad, spec_go. In and out.
+ *   iarg[n_entries][KIN_STEP_IARGS]: 0 member; 1 order; 2 aux (ACCEPT_PREDICT: order of the accepted step; INIT_D: 1 = from
+ *     ytmp; NORMS: 1 = with f1; RK_COMBINE: stages; VEC: the EnsVecOp; PREDICT on path 2: 1 = a predictor on its own);
+ *     3 copy_out (ACCEPT, ACCEPT_PREDICT: the new state also into row 24); 4 go (ACCEPT_PREDICT: 1 = the launch is given
+ *     &ctrl->spec_go as its go flag); 5 iter; 6 maxit; 7 publish_always; 8 crate_from_ctrl; 9 ban_negatives; 10 seq; 11 unused.
+ *     (NEWTON on path 2 takes iter from entry 0 and the ensemble's fixed iteration limit.)
+ *   darg[n_entries][KIN_STEP_DARGS]: 0 atol; 1 rtol; 2 h (INIT_D) / factor (CHANGE_D: the matrix is built by
+ *     bdf_change_D_matrix(order, factor)) / the scalar of VEC's axpy; 3 upd; 4 tol; 5 rate_max; 6 crate0; 7 tol_first;
+ *     8 dy_first_max; 9 c (path 1); 10-12 ts, t, h_abs (INTERP: weights from bdf_interp_weights); 13-19 stage weights
+ *     (RK_COMBINE, RK_ERROR); the rest unused.
+ *   xloc[n] (NEWTON on paths 0 and 2): a permutation of 0 .. n-1; row 23 is scattered into the W buffer through it.
+ *   Operands: INIT_D y (or ytmp), f0 -> D; PREDICT / ACCEPT / ACCEPT_PREDICT / CHANGE_D as the integrators call them; INTERP
+ *     -> row 24; NORMS y, f0, f1 -> ctrl; NEWTON row 23, scale, y, d, D -> y, d, ctrl; RK_COMBINE y, K -> row 24; RK_ERROR
+ *     y, row 25, K -> ctrl; VEC: `out` is row 24. Path 1: I - c J(u) (row 26, current rates) is factorised, b (row 27) placed, the
+ *     solve and the update run in solve_newton; the x that launch produced is returned in row 23.
+ *   pub[KIN_STEP_CTRL + 1] (paths 0 and 1, NEWTON and RK_ERROR): the block the launch published to pinned host memory and the
+ *     sequence word; unpublished: every integer field -1, every double NaN, sequence word 0.
+ *   info[8], path 1: the stage-C plan's ELL groups, one-wavefront rows, of those with more than 256 entries, whole-workgroup
+ *     rows, its longest row, the dense block size m, the launch's grid size and workgroup size. Other paths: zeros.
+ * KIN_ERR_UNSUPPORTED: path 1 on a handle whose analysis has no fused solve or m = 0, an op a path does not have;
+ * KIN_ERR_INVALID_ARG: sizes, orders, members or xloc out of range; KIN_ERR_STATE: path 1 without rates. The handle is usable
+ * afterwards (a later solve is bit for bit that of a fresh handle). Added under KIN_ABI_VERSION 6: look the symbol up. */
+#define KIN_STEP_ROWS 28
+#define KIN_STEP_CTRL 18
+#define KIN_STEP_IARGS 12
+#define KIN_STEP_DARGS 24
+enum { KIN_STEP_INIT_D = 0, KIN_STEP_PREDICT, KIN_STEP_ACCEPT, KIN_STEP_ACCEPT_PREDICT, KIN_STEP_CHANGE_D, KIN_STEP_INTERP,
+       KIN_STEP_NORMS, KIN_STEP_NEWTON, KIN_STEP_RK_COMBINE, KIN_STEP_RK_ERROR, KIN_STEP_VEC };
+int kin_step_probe(kin_network* h, int32_t path, int32_t op, int64_t n, int64_t K, int64_t n_entries, const int32_t* iarg,
+                   const double* darg, const int32_t* xloc, double* state, double* ctrl, double* pub, int64_t* info);
 
 /* ---- device / build information ------------------------------------------------------- */
 int kin_device_count(int* n);
@@ -402,7 +441,7 @@ const char* kin_version(void);
  * struct sizes) with the values it was written against before the first call: kin_params / kin_stats have grown between
  * versions (1: round 1; 2: + dtmin and the LU-cache counters; 3: + the library-order sweep entry points; 4: + kin_solve_ensemble,
  * kin_lu_analyze_host - structs unchanged; 5: + kin_rhs_batched_klib_dev - structs unchanged; 6: + kin_solve_ensemble_continuous -
- * structs unchanged; kin_solve_ensemble_discrete, kin_resident_probe and kin_newton_probe came later under 6, found by symbol lookup). */
+ * structs unchanged; kin_solve_ensemble_discrete, kin_resident_probe, kin_newton_probe and kin_step_probe came later under 6, found by symbol lookup). */
 #define KIN_ABI_VERSION 6
 int kin_abi_version(void);
 int64_t kin_struct_size(int which); /* 0: sizeof(kin_params), 1: sizeof(kin_stats), else -1 */

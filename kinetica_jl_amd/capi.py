@@ -30,10 +30,22 @@ SYMBOLS = [
     "kin_lib_layout", "kin_lib_layout_host", "kin_states_to_lib_dev", "kin_states_from_lib_dev", "kin_rates_to_lib_dev", "kin_rate_table_lib_dev",
     "kin_rhs_tiled_dev", "kin_rhs_batched_T_dev", "kin_rhs_batched_klib_dev", "kin_abi_version", "kin_struct_size",
     "kin_solve_ensemble", "kin_lu_analyze_host", "kin_solve_ensemble_continuous", "kin_solve_ensemble_discrete",
-    "kin_resident_probe", "kin_newton_probe",
+    "kin_resident_probe", "kin_newton_probe", "kin_step_probe",
     "kin_flux_batched", "kin_flux_batched_dev", "kin_solution_flux",
 ]
 ABI_VERSION = 6   # include/kinetica_hip.h: KIN_ABI_VERSION this binding was written against
+
+
+# kin_step_probe (include/kinetica_hip.h): rows of the state block, fields of the flattened control block, argument slots
+STEP_ROWS, STEP_CTRL, STEP_IARGS, STEP_DARGS = 28, 18, 12, 24
+STEP_ROW = dict(D=0, y=8, psi=9, d=10, scale=11, f0=12, f1=13, ytmp=14, cs=15, K=16, x=23, out=24, y_new=25, u=26, b=27)
+STEP_CTRL_FIELDS = ("dy_norm_old", "dy_norm", "err_norm", "err_m_norm", "err_p_norm", "crate", "scratch0", "scratch1", "scratch2",
+                    "scratch3", "newton_done", "converged", "n_iter", "nonfinite", "any_negative", "ticket", "lu_bad", "spec_go")
+STEP_OPS = dict(init_D=0, predict=1, accept=2, accept_predict=3, change_D=4, interp=5, norms=6, newton=7, rk_combine=8, rk_error=9, vec=10)
+STEP_VEC_OPS = dict(load_u0=0, cs_from_y=1, y_from_cs_clipped=2, y_from_d0=3, ytmp_from_d0=4, ytmp_axpy=5, save_y=6, interp=7)
+STEP_IARG_NAMES = ("member", "order", "aux", "copy_out", "go", "iter", "maxit", "publish_always", "crate_from_ctrl", "ban_negatives", "seq")
+STEP_DARG_NAMES = ("atol", "rtol", "h", "upd", "tol", "rate_max", "crate0", "tol_first", "dy_first_max", "c", "ts", "t", "h_abs")
+STEP_DARG_W = 13
 
 
 class KinParams(ctypes.Structure):
@@ -119,6 +131,9 @@ def lib():
             L.kin_resident_probe.argtypes = [c_void_p, c_int64, PD, PD, PD, PD, PD, PD, POINTER(c_int32), P64]
         if hasattr(L, "kin_newton_probe"):   # (also under ABI 6)
             L.kin_newton_probe.argtypes = [c_void_p, c_int64, c_int32, PD, PD, PD, PD, POINTER(c_int32), P64]
+        if hasattr(L, "kin_step_probe"):   # (also under ABI 6)
+            L.kin_step_probe.argtypes = [c_void_p, c_int32, c_int32, c_int64, c_int64, c_int64, POINTER(c_int32), PD, POINTER(c_int32),
+                                         PD, PD, PD, P64]
         if hasattr(L, "kin_flux_batched"):   # (also under ABI 6: the reaction-flux pass)
             L.kin_flux_batched.argtypes = [c_void_p, c_int64, PD, PD, c_int64, P64, PD, PD, PD, PD]
             L.kin_flux_batched_dev.argtypes = [c_void_p, c_int64] + [c_void_p] * 8
@@ -600,6 +615,45 @@ class HipNetwork:
         inf = {k: int(v) for k, v in zip(keys, info[:8])}
         inf["dense_species"] = info[8:8 + inf["m"]].copy()
         return dict(x=x, bad=bad, info=inf)
+
+    def step_probe(self, path, op, state, ctrl, entries, xloc=None):
+        """One operation of the step, once, on the caller's state (diagnostic, kin_step_probe; layouts: include/kinetica_hip.h).
+        path: 0 host-driven kernels, 1 the update fused into the solve, 2 the lockstep ensemble's kernels; op: a key of STEP_OPS;
+        state: (K, STEP_ROWS, n) or (STEP_ROWS, n); ctrl: (K, STEP_CTRL) or (STEP_CTRL,), in the order of STEP_CTRL_FIELDS;
+        entries: a list of dicts (one dict: a list of one) with the integer keys of STEP_IARGS and the scalar keys of STEP_DARGS
+        ("w": up to 7 stage weights), everything left out 0 except order = 1 and maxit = 4; xloc: permutation of 0 .. n-1.
+        Returns dict(state, ctrl: copies after the operation, shaped as given; pub: the published block, STEP_CTRL values; seq: the
+        published sequence word; info: dict of the stage-C plan's groups, wave_rows, wave_rows_long, block_rows, max_row, m, grid, wg)."""
+        st = np.array(state, dtype=np.float64, order="C")
+        ct = np.array(ctrl, dtype=np.float64, order="C")
+        single = st.ndim == 2
+        st3 = st.reshape((1,) + st.shape) if single else st
+        ct2 = ct.reshape(1, -1) if ct.ndim == 1 else ct
+        K, rows, n = st3.shape
+        assert rows == STEP_ROWS and ct2.shape == (K, STEP_CTRL)
+        entries = [entries] if isinstance(entries, dict) else list(entries)
+        ia = np.zeros((len(entries), STEP_IARGS), np.int32)
+        da = np.zeros((len(entries), STEP_DARGS))
+        for e, ent in enumerate(entries):
+            ia[e, STEP_IARG_NAMES.index("order")] = 1
+            ia[e, STEP_IARG_NAMES.index("maxit")] = 4
+            for q, v in ent.items():
+                if q in STEP_IARG_NAMES:
+                    ia[e, STEP_IARG_NAMES.index(q)] = int(v)
+                elif q == "w":
+                    da[e, STEP_DARG_W:STEP_DARG_W + len(v)] = v
+                else:
+                    da[e, STEP_DARG_NAMES.index(q)] = float(v)
+        P32 = POINTER(c_int32)
+        xl = None if xloc is None else np.ascontiguousarray(xloc, dtype=np.int32)
+        assert xl is None or xl.shape == (n,)
+        pub = np.zeros(STEP_CTRL + 1)
+        info = np.zeros(8, np.int64)
+        self._chk(lib().kin_step_probe(self._h, int(path), STEP_OPS[op], n, K, len(entries), ia.ctypes.data_as(P32), _pd(da),
+                                       None if xl is None else xl.ctypes.data_as(P32), _pd(st3), _pd(ct2), _pd(pub), _p64(info)))
+        keys = ("groups", "wave_rows", "wave_rows_long", "block_rows", "max_row", "m", "grid", "wg")
+        return dict(state=st3[0] if single else st3, ctrl=ct2[0] if ct.ndim == 1 else ct2, pub=pub[:STEP_CTRL], seq=int(pub[STEP_CTRL]),
+                    info={k: int(v) for k, v in zip(keys, info)})
 
     def solution_max_dev(self, d_out):
         """kin_solution_max into a device buffer (pointer as int) of N doubles."""

@@ -55,6 +55,9 @@ struct EnsSolveTables {
 };
 void ens_predict(const EnsSolveTables& T, const EnsRep* reps, const EnsOp* d_ops, int n, hipStream_t s);
 void ens_iterations(const EnsSolveTables& T, const EnsRep* reps, const EnsOp* d_ops, int n, int it0, int iters, hipStream_t s);
+// the last launch of an iteration on its own: update + decision of every entry from the solution in its W (xloc: species ->
+// position in W); ens_iterations launches it through here
+void ens_newton(int N, int iter, const int32_t* xloc, const BdfCoef& cf, const EnsRep* reps, const EnsOp* d_ops, int n, hipStream_t s);
 int ens_reduce_doubles(int N);   // doubles of EnsRep::part
 // the members' control blocks into pinned host memory + a sequence number behind them (a round's hand-over without a stream sync)
 void ens_publish(const BdfCtrl* ctrl, BdfCtrl* host_ctrl_dev, int K, unsigned long long* host_seq_dev, unsigned long long seq, hipStream_t s);

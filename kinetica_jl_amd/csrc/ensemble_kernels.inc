@@ -363,6 +363,9 @@ void ens_apply_rates(int R, const double* Ea, const double* A, int has_kmax, dou
 void ens_predict(const EnsSolveTables& T, const EnsRep* reps, const EnsOp* d_ops, int n, hipStream_t s) {
   if (n > 0) hipLaunchKernelGGL(e_predict_kernel, ENS_GRID(T.N, n), 0, s, T.N, T.cf, reps, d_ops);
 }
+void ens_newton(int N, int iter, const int32_t* xloc, const BdfCoef& cf, const EnsRep* reps, const EnsOp* d_ops, int n, hipStream_t s) {
+  if (n > 0) hipLaunchKernelGGL(e_newton_kernel, dim3((unsigned)bdf_reduce_blocks(N), (unsigned)n), dim3(256), 0, s, N, iter, xloc, cf, reps, d_ops);
+}
 void ens_iterations(const EnsSolveTables& T, const EnsRep* reps, const EnsOp* d_ops, int n, int it0, int iters, hipStream_t s) {
   if (n <= 0) return;
   for (int it = it0; it < it0 + iters; it++) {
@@ -372,7 +375,7 @@ void ens_iterations(const EnsSolveTables& T, const EnsRep* reps, const EnsOp* d_
     hipLaunchKernelGGL(e_gemv_kernel, dim3((unsigned)ceil_div(T.m, 4), (unsigned)n), dim3(256), 0, s, T.mpad, T.m, (long long)(T.off_y + T.ns),
                        (long long)T.off_x, reps, d_ops);
     launch_e_segsum<SEG_PROD_SET, 3>(T.stageC, reps, d_ops, n, s);
-    hipLaunchKernelGGL(e_newton_kernel, dim3((unsigned)bdf_reduce_blocks(T.N), (unsigned)n), dim3(256), 0, s, T.N, it, T.xloc, T.cf, reps, d_ops);
+    ens_newton(T.N, it, T.xloc, T.cf, reps, d_ops, n, s);
   }
   KIN_HIP(hipGetLastError());
 }

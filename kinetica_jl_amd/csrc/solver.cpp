@@ -1415,6 +1415,47 @@ void newton_probe(kin_network* h, int64_t K, int32_t batched, const double* u, c
   for (int32_t j = 0; j < lu.m; j++) info[8 + j] = lu.perm[lu.ns + j];
 }
 
+// Path 1 of kin_step_probe: the corrector update inside the solve's last gather launch, on the caller's step state
+void step_probe_fused(kin_network* h, double c, const double* u, const double* b, NewtonFuse& f, double* x, int64_t* info) {
+  if (!h->solver) h->solver.reset(new Solver(h));
+  Solver& S = *h->solver;
+  SparseLU& lu = S.lu;
+  if (!(lu.fused_tri && lu.m > 0)) throw KinError(ERR_UNSUPPORTED, "the analysis of this network has no fused solve with a dense block");
+  hipStream_t s = h->stream;
+  const int N = S.N;
+  S.flush_accept();
+  S.spec = Solver::Spec{};
+  lu.ensure_slots(1, s);
+  S.y.upload(u, N, s);
+  S.eval_jac(S.y.p);
+  lu.factor(c, S.jv.p, 0, &f.ctrl->lu_bad, s);   // (the flag of a vanished pivot goes where the integrator puts it)
+  std::vector<int32_t> yl(N), xl(N);
+  lu.yloc.download(yl.data(), N, s);
+  lu.xloc.download(xl.data(), N, s);
+  KIN_HIP(hipStreamSynchronize(s));
+  std::vector<double> tail((size_t)(lu.off_x + lu.mpad + 8 - lu.off_y), 0.0);   // the solve vectors only
+  for (int i = 0; i < N; i++) tail[yl[i] - lu.off_y] = b[i];
+  KIN_HIP(hipMemcpyAsync(lu.slots[0].W.p + lu.off_y, tail.data(), tail.size() * sizeof(double), hipMemcpyHostToDevice, s));
+  f.N = N; f.skip = &f.ctrl->newton_done; f.part = S.red.p;
+  lu.solve_newton(0, f, s);
+  KIN_HIP(hipMemcpyAsync(tail.data(), lu.slots[0].W.p + lu.off_y, tail.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+  const SegPlanDev& p = lu.stageC;
+  std::vector<int32_t> off((size_t)p.G + 1), sb((size_t)p.S), se((size_t)p.S), bb((size_t)p.B), be((size_t)p.B);
+  if (p.G > 0) p.grp_off.download(off.data(), off.size(), s);
+  p.seg_beg.download(sb.data(), sb.size(), s); p.seg_end.download(se.data(), se.size(), s);
+  p.blk_beg.download(bb.data(), bb.size(), s); p.blk_end.download(be.data(), be.size(), s);
+  KIN_HIP(hipStreamSynchronize(s));
+  for (int i = 0; i < N; i++) x[i] = tail[xl[i] - lu.off_y];
+  int64_t max_row = 0, s_long = 0;
+  for (int g = 0; g < p.G; g++) max_row = std::max<int64_t>(max_row, off[g + 1] - off[g]);
+  for (int q = 0; q < p.S; q++) { max_row = std::max<int64_t>(max_row, se[q] - sb[q]); if (se[q] - sb[q] > 256) s_long++; }
+  for (int q = 0; q < p.B; q++) max_row = std::max<int64_t>(max_row, be[q] - bb[q]);
+  info[0] = p.G; info[1] = p.S; info[2] = s_long; info[3] = p.B; info[4] = max_row; info[5] = lu.m;
+  info[6] = lu.newton_grid(); info[7] = stagec_newton_wg(p.view());
+  S.cur_slot = 0;
+  S.invalidate_lu();
+}
+
 }  // namespace kin
 
 kin_network::kin_network() {}

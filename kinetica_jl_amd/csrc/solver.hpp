@@ -85,5 +85,10 @@ void newton_solve(kin_network* h, double c, const double* u, const double* b, do
 // inverses of up to GJ_BMAX members as one launch_gauss_jordan_batched chain (kin_newton_probe)
 void newton_probe(kin_network* h, int64_t K, int32_t batched, const double* u, const double* c, const double* b, double* x,
                   int32_t* bad, int64_t* info);
+// diagnostic (kin_step_probe, path 1): I - c J(u) factorised into slot 0, b placed, then SparseLU::solve_newton with `f` - the
+// caller fills the device pointers of the step state, the control block, the publication targets and the scalars; N, the skip
+// flag and the partial-sum buffer (the Solver's own) are set here. x: the solution that launch left in W; info[8]: see the header
+struct NewtonFuse;
+void step_probe_fused(kin_network* h, double c, const double* u, const double* b, NewtonFuse& f, double* x, int64_t* info);
 
 }  // namespace kin

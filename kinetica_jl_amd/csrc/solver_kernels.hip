@@ -894,6 +894,7 @@ int stagec_newton_grid(const SegPlanView& p, int m) {
   const int tasks = p.G + p.S + (int)ceil_div(m, 64);
   return stagec_big_wg(p) ? p.B + (int)ceil_div(tasks, 16) : (int)ceil_div(tasks, 4);
 }
+int stagec_newton_wg(const SegPlanView& p) { return stagec_big_wg(p) ? 1024 : 256; }
 void launch_stagec_newton(const SegPlanView& p, double* W, const NewtonFuse& f, hipStream_t s) {
   const int grid = stagec_newton_grid(p, f.m);
   if (stagec_big_wg(p)) hipLaunchKernelGGL((stagec_newton_kernel<1024>), dim3(grid), dim3(1024), 0, s, p, W, f);

@@ -50,6 +50,7 @@ struct NewtonFuse {
 };
 struct SegPlanView;
 int stagec_newton_grid(const SegPlanView& p, int m);   // workgroups of the launch (5 partial sums each in `part`)
+int stagec_newton_wg(const SegPlanView& p);          // ... and their size: 1024 threads when the plan has whole-workgroup rows, else 256
 void launch_stagec_newton(const SegPlanView& p, double* W, const NewtonFuse& f, hipStream_t s);
 
 // One corrector iteration's update + decision + (folded in) the step's error estimate; the launch that decides publishes

@@ -13,8 +13,8 @@ fails when they exceed a tenth of all members checked. Every constructed case ha
 matrix is the identity to 1e-4 and a wrong off-diagonal tile would hardly show).
 
 Not covered: the limits at which the analysis gives up the explicit inverses (4 M monomials) or the fused products (16 M terms) -
-no network of a size this suite can afford reaches them; the corrector update fused into the solve's last launch
-(stagec_newton_kernel: test_corrector_update_fused_into_the_solve_and_separate); the lockstep ensemble's batched vector kernels.
+no network of a size this suite can afford reaches them. (The corrector update fused into the solve's last launch -
+stagec_newton_kernel - and the lockstep ensemble's batched vector kernels: tests/test_gpu_step_kernels.py, through kin_step_probe.)
 The largest errors each case measured are printed at the end of the module (pytest -s).
 
 Mutation check (value-only changes to the product kernels on a scratch build, one at a time, this file without the 3 000- and

@@ -430,6 +430,42 @@ enum { KIN_STEP_INIT_D = 0, KIN_STEP_PREDICT, KIN_STEP_ACCEPT, KIN_STEP_ACCEPT_P
 int kin_step_probe(kin_network* h, int32_t path, int32_t op, int64_t n, int64_t K, int64_t n_entries, const int32_t* iarg,
                    const double* darg, const int32_t* xloc, double* state, double* ctrl, double* pub, int64_t* info);
 
+/* ---- segmented flux pass and the analysis of a stored ensemble --------------------------------------------------- */
+/* The flux pass over S SEGMENTS of up to L states each (an ensemble's members, the chunks of a long trajectory): state
+ * b = s L + j at u[b][N], flux[s][r] = sum over j < seg_n[s] of w[b] rate_r(u_b; k of state b), rate_r as in kin_flux_batched,
+ * in the caller's reaction order. ONE launch: a workgroup owns (segment, part of the reactions), walks the segment's rows in
+ * order and writes flux[s][.] itself - a segment's result depends on its own rows only: it is bit-identical whatever other
+ * segments the call holds and whatever S is, and repeats bit for bit. Rows j >= seg_n[s] are never read (their u, k_row, T and
+ * w entries need not be valid); seg_n == NULL: every segment has L rows; seg_n[s] == 0 gives zeros. Rate constants of state b,
+ * exactly the rules of kin_flux_batched_dev: row k_row[b] of k (k_row NULL: row b), or the Arrhenius law at T[b], or the
+ * handle's current rates. A lane keeps its rate constants in registers from row to row of a segment and loads / evaluates
+ * them again only when k_row[b] (the bits of T[b]) differs from the previous row's - the same function of the same inputs:
+ * no bit changes. Statuses as kin_flux_batched: KIN_ERR_INVALID_ARG for both k and T, k_row without k, S or L < 0, a null
+ * output (host entry: a k_row of a row j < seg_n[s] outside [0, n_k_rows), a seg_n outside [0, L], k without k_row and
+ * n_k_rows != S L); KIN_ERR_STATE for T without Arrhenius parameters or no rates at all; S L = 0 or R = 0 writes zeros.
+ * The device entry only enqueues (d_seg_n: S int64 on the device, or NULL); one stream per handle at a time, as for the
+ * per-state pass. Added under KIN_ABI_VERSION 6: look the symbols up. */
+int kin_flux_segmented_dev(kin_network* h, int64_t S, int64_t L, const int64_t* d_seg_n, const double* d_u,
+                           const double* d_k, const int64_t* d_k_row, const double* d_T, const double* d_w,
+                           double* d_flux /* [S][R] */, void* stream);
+int kin_flux_segmented(kin_network* h, int64_t S, int64_t L, const int64_t* seg_n, const double* u, const double* k,
+                       int64_t n_k_rows, const int64_t* k_row, const double* T, const double* w, double* flux /* [S][R] */);
+/* After a successful kin_solve_ensemble* call the handle remembers where the members' saved states live on the device,
+ * [K][n_rows][N] with zeros past n_saved[m] - whether or not out_u was given (out_u == NULL with n_saved != NULL is a
+ * solve that downloads no trajectory). The next ensemble call on the handle replaces the record; a failed one leaves
+ * none; kin_solve and the other entries leave it alone. Without a stored ensemble the four calls return KIN_ERR_STATE. */
+int kin_ensemble_size(const kin_network* h, int64_t* K, int64_t* n_rows, int64_t* n_species, int64_t* n_saved /* [K] or NULL */);
+/* out_umax[m][i] = max over member m's saved rows of species i (kin_solution_max per member; the zero rows past n_saved take no
+ * part; a member without saved rows gives zeros). One launch. */
+int kin_ensemble_max(kin_network* h, double* out_umax /* [K][N] */);
+/* out[m][j] = sum_i w[i] u_m(t_j)[i] for j < n_saved[m], zeros beyond (kin_solution_dot per member). One launch. */
+int kin_ensemble_dot(kin_network* h, const double* w /* [N] */, double* out /* [K][n_rows] */);
+/* kin_flux_segmented over the stored ensemble (S = K, L = n_rows, seg_n = n_saved), read where it lives: flux[m][R] of every
+ * member. w, k_row and T_rows have one entry per (member, row of the save grid); entries of rows j >= n_saved[m] are ignored.
+ * k without k_row needs n_k_rows == K n_rows. */
+int kin_ensemble_flux(kin_network* h, const double* w /* [K*n_rows] or NULL */, const double* k, int64_t n_k_rows,
+                      const int64_t* k_row /* [K*n_rows] */, const double* T_rows /* [K*n_rows] */, double* flux /* [K][R] */);
+
 /* ---- device / build information ------------------------------------------------------- */
 int kin_device_count(int* n);
 /* Selects the device for handles created afterwards by this thread; a handle remembers the device it was created on
@@ -441,7 +477,8 @@ const char* kin_version(void);
  * struct sizes) with the values it was written against before the first call: kin_params / kin_stats have grown between
  * versions (1: round 1; 2: + dtmin and the LU-cache counters; 3: + the library-order sweep entry points; 4: + kin_solve_ensemble,
  * kin_lu_analyze_host - structs unchanged; 5: + kin_rhs_batched_klib_dev - structs unchanged; 6: + kin_solve_ensemble_continuous -
- * structs unchanged; kin_solve_ensemble_discrete, kin_resident_probe, kin_newton_probe and kin_step_probe came later under 6, found by symbol lookup). */
+ * structs unchanged; kin_solve_ensemble_discrete, kin_resident_probe, kin_newton_probe, kin_step_probe, the flux pass (kin_flux_*, kin_solution_flux) and
+ * kin_ensemble_size / _max / _dot / _flux came later under 6, found by symbol lookup). */
 #define KIN_ABI_VERSION 6
 int kin_abi_version(void);
 int64_t kin_struct_size(int which); /* 0: sizeof(kin_params), 1: sizeof(kin_stats), else -1 */

@@ -32,6 +32,7 @@ SYMBOLS = [
     "kin_solve_ensemble", "kin_lu_analyze_host", "kin_solve_ensemble_continuous", "kin_solve_ensemble_discrete",
     "kin_resident_probe", "kin_newton_probe", "kin_step_probe",
     "kin_flux_batched", "kin_flux_batched_dev", "kin_solution_flux",
+    "kin_flux_segmented", "kin_flux_segmented_dev", "kin_ensemble_size", "kin_ensemble_max", "kin_ensemble_dot", "kin_ensemble_flux",
 ]
 ABI_VERSION = 6   # include/kinetica_hip.h: KIN_ABI_VERSION this binding was written against
 
@@ -138,6 +139,13 @@ def lib():
             L.kin_flux_batched.argtypes = [c_void_p, c_int64, PD, PD, c_int64, P64, PD, PD, PD, PD]
             L.kin_flux_batched_dev.argtypes = [c_void_p, c_int64] + [c_void_p] * 8
             L.kin_solution_flux.argtypes = [c_void_p, PD, PD, c_int64, P64, PD, PD, PD]
+        if hasattr(L, "kin_flux_segmented"):   # (also under ABI 6: the segmented pass and the analysis of a stored ensemble)
+            L.kin_flux_segmented.argtypes = [c_void_p, c_int64, c_int64, P64, PD, PD, c_int64, P64, PD, PD, PD]
+            L.kin_flux_segmented_dev.argtypes = [c_void_p, c_int64, c_int64] + [c_void_p] * 8
+            L.kin_ensemble_size.argtypes = [c_void_p, P64, P64, P64, P64]
+            L.kin_ensemble_max.argtypes = [c_void_p, PD]
+            L.kin_ensemble_dot.argtypes = [c_void_p, PD, PD]
+            L.kin_ensemble_flux.argtypes = [c_void_p, PD, PD, c_int64, P64, PD, PD]
         L.kin_solve_ensemble.argtypes = [c_void_p, POINTER(KinParams), c_int64, PD, PD, PD, PD, PD, PD, c_int64, P64, PD, PD, P64,
                                          POINTER(c_int32), POINTER(KinStats)]
         L.kin_integrator_init.argtypes = [c_void_p, POINTER(KinParams), PD, PD, PD, PD, c_int64]
@@ -373,6 +381,66 @@ class HipNetwork:
                                           _pd(flux), _pd(rates)))
         return (flux, rates) if want_rates else flux
 
+    def flux_segmented(self, u, seg_n=None, k=None, k_row=None, T=None, w=None):
+        """kin_flux_segmented on host arrays: u[S][L][N] (S segments of up to L states), flux[S][R] with
+        flux[s] = sum over j < seg_n[s] of w[s][j] rate(u[s][j]) - one launch, every segment summed in row order by a workgroup
+        of its own (bit-identical whatever else the call holds). seg_n[S] (None: L rows each); rate constants of a state as in
+        flux_batched with k_row / T / w of shape [S][L] (entries of rows j >= seg_n[s] are ignored)."""
+        u = np.ascontiguousarray(_f64(u))
+        assert u.ndim == 3 and u.shape[2] == self.n
+        S, Lr = u.shape[0], u.shape[1]
+        if seg_n is not None:
+            seg_n = np.ascontiguousarray(seg_n, dtype=np.int64).ravel()
+            assert len(seg_n) == S
+        k, n_rows, k_row, T, w = self._flux_inputs(S * Lr, k, k_row, T, w)
+        flux = np.empty((S, self.nr))
+        self._chk(lib().kin_flux_segmented(self._h, S, Lr, None if seg_n is None else _p64(seg_n), _pd(u), _pd(k), n_rows,
+                                           None if k_row is None else _p64(k_row), _pd(T), _pd(w), _pd(flux)))
+        return flux
+
+    def flux_segmented_dev(self, S, L, d_u, d_flux, d_seg_n=0, d_k=0, d_k_row=0, d_T=0, d_w=0, stream=0):
+        """kin_flux_segmented_dev: device pointers (ints; 0 = not given), u[S L][N], seg_n[S] (int64), k rows / k_row[S L] (int64)
+        / T[S L], w[S L], flux[S][R]. Only enqueues; one stream per handle at a time."""
+        p = lambda x: c_void_p(x) if x else None
+        self._chk(lib().kin_flux_segmented_dev(self._h, int(S), int(L), p(d_seg_n), p(d_u), p(d_k), p(d_k_row), p(d_T), p(d_w),
+                                               p(d_flux), p(stream)))
+
+    # --- the last ensemble call's saved states, analysed where they live ------------------------
+    def ensemble_size(self):
+        """kin_ensemble_size: (K, n_rows, n_species, n_saved[K]) of the stored ensemble (KIN_ERR_STATE without one)."""
+        K, rows, n = c_int64(0), c_int64(0), c_int64(0)
+        self._chk(lib().kin_ensemble_size(self._h, ctypes.byref(K), ctypes.byref(rows), ctypes.byref(n), None))
+        ns = np.zeros(K.value, np.int64)
+        self._chk(lib().kin_ensemble_size(self._h, None, None, None, _p64(ns)))
+        return K.value, rows.value, n.value, ns
+
+    def ensemble_max(self):
+        """kin_ensemble_max: umax[K][N], every member's maximum over its own saved rows."""
+        K = self.ensemble_size()[0]
+        out = np.empty((K, self.n))
+        self._chk(lib().kin_ensemble_max(self._h, _pd(out)))
+        return out
+
+    def ensemble_dot(self, w):
+        """kin_ensemble_dot: out[K][n_rows] = sum_i w[i] u_m(t_j)[i], zeros past a member's saved rows."""
+        w = _f64(w)
+        assert len(w) == self.n
+        K, rows = self.ensemble_size()[:2]
+        out = np.empty((K, rows))
+        self._chk(lib().kin_ensemble_dot(self._h, _pd(w), _pd(out)))
+        return out
+
+    def ensemble_flux(self, w=None, k=None, k_row=None, T_rows=None):
+        """kin_ensemble_flux: flux[K][R] of every member of the stored ensemble, the segmented pass over the saved states where
+        they live. w / k_row / T_rows: [K][n_rows] (entries past a member's saved rows are ignored); k: rows for k_row to
+        index, or one row per (member, row); none of k / T_rows: the handle's current rates."""
+        K, rows = self.ensemble_size()[:2]
+        k, n_rows, k_row, T_rows, w = self._flux_inputs(K * rows, k, k_row, T_rows, w)
+        flux = np.empty((K, self.nr))
+        self._chk(lib().kin_ensemble_flux(self._h, _pd(w), _pd(k), n_rows, None if k_row is None else _p64(k_row), _pd(T_rows),
+                                          _pd(flux)))
+        return flux
+
     # --- library order (tiled sweep) --------------------------------------------------------
     def lib_layout(self):
         """dict(k_len, species_of_lib[N], slot_of_reaction[R], identity, hubs, windows, records, entries, copies, block)."""
@@ -458,10 +526,11 @@ class HipNetwork:
             self._chk(lib().kin_solution_copy(self._h, _pd(t), _pd(u)))
         return t, u, rc.value, stats.as_dict(), st
 
-    def solve_ensemble(self, params: KinParams, u0, k=None, T=None, tstops=None, T_stops=None, k_table=None):
+    def solve_ensemble(self, params: KinParams, u0, k=None, T=None, tstops=None, T_stops=None, k_table=None, trajectories=True):
         """kin_solve_ensemble: K trajectories of this network in ONE launch (one workgroup per trajectory, resident on the GPU).
         u0[K][N]; k[K][R] or T[K] (or neither: the handle's current rates); tstops / T_stops / k_table are shared by the members.
-        Returns (t[M], u[K][M][N], n_saved[K], retcodes[K], [stats dict] * K)."""
+        Returns (t[M], u[K][M][N], n_saved[K], retcodes[K], [stats dict] * K). trajectories=False: no state is downloaded
+        (out_u = NULL) and u is None - the members' states stay on the device for ensemble_max / _dot / _flux."""
         u0 = np.ascontiguousarray(np.atleast_2d(_f64(u0)))
         K = u0.shape[0]
         assert u0.shape == (K, self.n)
@@ -473,12 +542,12 @@ class HipNetwork:
             T_stops = None if T_stops is None else _f64(T_stops)
             k_table = None if k_table is None else np.ascontiguousarray(_f64(k_table).reshape(n_stops, self.nr))
         return self._ensemble(lib().kin_solve_ensemble, params, K, _pd(u0), _pd(k), _pd(T), _pd(tstops), _pd(T_stops), _pd(k_table),
-                              n_stops)
+                              n_stops, trajectories=trajectories)
 
-    def solve_ensemble_continuous(self, params: KinParams, u0, nodes):
+    def solve_ensemble_continuous(self, params: KinParams, u0, nodes, trajectories=True):
         """kin_solve_ensemble_continuous: K trajectories under continuous rate updates, member m's rates at T(t) of its own
         profile. u0[K][N]; nodes: K pairs (t_nodes, T_nodes) in global time (node counts may differ).
-        Returns what solve_ensemble returns: (t[M], u[K][M][N], n_saved[K], retcodes[K], [stats dict] * K)."""
+        Returns what solve_ensemble returns: (t[M], u[K][M][N], n_saved[K], retcodes[K], [stats dict] * K); trajectories as there."""
         u0 = np.ascontiguousarray(np.atleast_2d(_f64(u0)))
         K = u0.shape[0]
         assert u0.shape == (K, self.n) and len(nodes) == K
@@ -489,13 +558,14 @@ class HipNetwork:
         ptr[1:] = np.cumsum([len(a) for a in tn])
         t_all = np.ascontiguousarray(np.concatenate(tn))
         T_all = np.ascontiguousarray(np.concatenate(Tn))
-        return self._ensemble(lib().kin_solve_ensemble_continuous, params, K, _pd(u0), _p64(ptr), _pd(t_all), _pd(T_all))
+        return self._ensemble(lib().kin_solve_ensemble_continuous, params, K, _pd(u0), _p64(ptr), _pd(t_all), _pd(T_all),
+                              trajectories=trajectories)
 
-    def solve_ensemble_discrete(self, params: KinParams, u0, stops):
+    def solve_ensemble_discrete(self, params: KinParams, u0, stops, trajectories=True):
         """kin_solve_ensemble_discrete: K trajectories under discrete rate updates, member m's rates the Arrhenius rates at
         T_stops held from tstops on (kin_solve's zero-order hold) of its own schedule. u0[K][N]; stops: K pairs
         (tstops, T_stops) in global time (stop counts may differ).
-        Returns what solve_ensemble returns: (t[M], u[K][M][N], n_saved[K], retcodes[K], [stats dict] * K)."""
+        Returns what solve_ensemble returns: (t[M], u[K][M][N], n_saved[K], retcodes[K], [stats dict] * K); trajectories as there."""
         u0 = np.ascontiguousarray(np.atleast_2d(_f64(u0)))
         K = u0.shape[0]
         assert u0.shape == (K, self.n) and len(stops) == K
@@ -506,15 +576,17 @@ class HipNetwork:
         ptr[1:] = np.cumsum([len(a) for a in ts])
         t_all = np.ascontiguousarray(np.concatenate(ts))
         T_all = np.ascontiguousarray(np.concatenate(Ts))
-        return self._ensemble(lib().kin_solve_ensemble_discrete, params, K, _pd(u0), _p64(ptr), _pd(t_all), _pd(T_all))
+        return self._ensemble(lib().kin_solve_ensemble_discrete, params, K, _pd(u0), _p64(ptr), _pd(t_all), _pd(T_all),
+                              trajectories=trajectories)
 
-    def _ensemble(self, fn, params, K, *inputs):
+    def _ensemble(self, fn, params, K, *inputs, trajectories=True):
         """The two calls of an ensemble entry point `fn`: the size query, then the solve into fresh outputs. `inputs`: its
-        arguments between K and n_rows. Returns (t[M], u[K][M][N], n_saved[K], retcodes[K], [stats dict] * K)."""
+        arguments between K and n_rows. Returns (t[M], u[K][M][N], n_saved[K], retcodes[K], [stats dict] * K); u is None with
+        trajectories=False (out_u = NULL: nothing but the times and the members' counters crosses the bus)."""
         rows = c_int64(0)
         self._chk(fn(self._h, ctypes.byref(params), K, *inputs, ctypes.byref(rows), None, None, None, None, None))
         M = rows.value
-        t = np.empty(M); u = np.empty((K, M, self.n)); ns = np.zeros(K, np.int64); rcs = np.zeros(K, np.int32)
+        t = np.empty(M); u = np.empty((K, M, self.n)) if trajectories else None; ns = np.zeros(K, np.int64); rcs = np.zeros(K, np.int32)
         stats = (KinStats * K)()
         self._chk(fn(self._h, ctypes.byref(params), K, *inputs, ctypes.byref(rows), _pd(t), _pd(u), _p64(ns),
                      rcs.ctypes.data_as(POINTER(c_int32)), stats))

@@ -408,6 +408,8 @@ void replica_ensemble(kin_network* h, const EnsembleCall& c) {
     h->replicas.push_back(clone_for_solves(h));
     h->replicas.back()->lu_budget_mb = std::max<size_t>(64, (size_t)((double)free_b * 0.7 / (1024.0 * 1024.0)) / (size_t)replica_threads_max());
   }
+  // kin_ensemble_*: every member's saved rows are copied device-to-device into the handle's own [K][cap][N], zeros past n_saved
+  h->ens_sol.alloc((size_t)K * (size_t)cap * (size_t)N);
   KIN_HIP(hipStreamSynchronize(h->stream));
   std::vector<std::string> errs((size_t)Tn);
   std::vector<std::thread> th;
@@ -446,6 +448,10 @@ void replica_ensemble(kin_network* h, const EnsembleCall& c) {
           if (c.n_saved) c.n_saved[m] = ns;
           if (c.out_u && ns > 0) rep->d_sol_u.download(c.out_u + (size_t)m * cap * N, (size_t)ns * N, s);
           if (c.out_u && ns < cap) std::memset(c.out_u + ((size_t)m * cap + (size_t)ns) * N, 0, (size_t)(cap - ns) * N * sizeof(double));   // rows a failed member never wrote
+          // (on the replica's stream, before its next member overwrites d_sol_u; drained by the synchronisation below)
+          double* keep = h->ens_sol.p + (size_t)m * (size_t)cap * (size_t)N;
+          if (ns > 0) KIN_HIP(hipMemcpyAsync(keep, rep->d_sol_u.p, (size_t)ns * N * sizeof(double), hipMemcpyDeviceToDevice, s));
+          if (ns < cap) KIN_HIP(hipMemsetAsync(keep + (size_t)ns * N, 0, (size_t)(cap - ns) * N * sizeof(double), s));
           KIN_HIP(hipStreamSynchronize(s));
           if (c.out_t) times[(size_t)m].assign(rep->sol_t.begin(), rep->sol_t.begin() + std::min<int64_t>(ns, (int64_t)rep->sol_t.size()));
         }
@@ -456,6 +462,7 @@ void replica_ensemble(kin_network* h, const EnsembleCall& c) {
   if (!spawn_err.empty()) throw KinError(ERR_DEVICE, "ensemble: could not start a member thread: " + spawn_err);
   for (auto& e : errs) if (!e.empty()) throw KinError(ERR_DEVICE, "ensemble member failed: " + e);
   if (c.out_t) { const std::vector<double>& tb = times[(size_t)res_furthest(rows)]; std::copy(tb.begin(), tb.end(), c.out_t); }
+  h->set_ensemble_record(h->ens_sol.p, K, cap, std::move(rows));
 }
 
 // Which form an ensemble call takes. Networks whose trajectory fits one compute unit: one workgroup per member, one launch
@@ -463,6 +470,7 @@ void replica_ensemble(kin_network* h, const EnsembleCall& c) {
 // (ensemble.cpp). KIN_ENSEMBLE_ROUTE = threads | lockstep forces a form (A/B runs: tools/ensemble_route_crossover.py);
 // KIN_ENSEMBLE_BATCHED=1 forces the lockstep form of a static call. The lockstep form has no continuous rate updates.
 void run_ensemble(kin_network* h, const EnsembleCall& c) {
+  h->ens.clear();   // (whatever route: its buffers are about to be reallocated or overwritten; set again by a call that succeeds)
   const char* e = getenv("KIN_ENSEMBLE_ROUTE");
   const std::string route = e ? e : "";
   const bool force_batched = getenv("KIN_ENSEMBLE_BATCHED") && atoi(getenv("KIN_ENSEMBLE_BATCHED")) != 0;

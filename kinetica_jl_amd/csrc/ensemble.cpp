@@ -618,7 +618,7 @@ bool ensemble_batched_supported(kin_network* h, std::string* why) {
 
 // K members of one (large) network, advanced in lockstep rounds; returns the saved rows of the member whose save times are
 // those in out_t
-static int64_t batched_ensemble_block(kin_network* h, const EnsembleCall& c) {
+static int64_t batched_ensemble_block(kin_network* h, const EnsembleCall& c, int64_t* rows_out, const double** sol_out) {
   auto wall0 = std::chrono::steady_clock::now();
   EnsembleSolver& E = *get_ensemble(h);
   if (!E.ok) throw KinError(ERR_UNSUPPORTED, E.why);
@@ -679,6 +679,8 @@ static int64_t batched_ensemble_block(kin_network* h, const EnsembleCall& c) {
   const double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - wall0).count();
   if (c.out_u) E.sol.download(c.out_u, (size_t)K * (size_t)g.cap * N, s);
   KIN_HIP(hipStreamSynchronize(s));
+  for (int64_t t = 0; t < K; t++) rows_out[t] = std::min<int64_t>(res[(size_t)t].n_saved, g.cap);
+  *sol_out = E.sol.p;
   const int64_t best = res_member_outputs(res, g.cap, E.lu, slots, wall, c.n_saved, c.retcodes, c.stats);
   if (c.out_t) std::copy(E.sol_t[best].begin(), E.sol_t[best].begin() + g.cap, c.out_t);
   if (getenv("KIN_TIMING")) {
@@ -704,6 +706,12 @@ void batched_ensemble(kin_network* h, const EnsembleCall& c) {
   const int64_t cap = make_res_grid(c.p).cap;
   std::vector<double> tt((size_t)cap);
   int64_t best = -1;
+  // kin_ensemble_*: one block's states stay in the solver's buffer; several blocks reuse it, so each block's rows are copied
+  // device-to-device into the handle's own [K][cap][N]
+  std::vector<int64_t> saved((size_t)c.K, 0);
+  const double* sol = nullptr;
+  const bool several = c.K > block;
+  if (several) h->ens_sol.alloc((size_t)c.K * (size_t)cap * (size_t)N);
   for (int64_t m0 = 0; m0 < c.K; m0 += block) {
     EnsembleCall b = c;
     b.K = std::min(block, c.K - m0);
@@ -716,9 +724,15 @@ void batched_ensemble(kin_network* h, const EnsembleCall& c) {
     if (c.n_saved) b.n_saved = c.n_saved + m0;
     if (c.retcodes) b.retcodes = c.retcodes + m0;
     if (c.stats) b.stats = c.stats + m0;
-    const int64_t rows = batched_ensemble_block(h, b);
+    const int64_t rows = batched_ensemble_block(h, b, saved.data() + m0, &sol);
     if (c.out_t && rows > best) { std::copy(tt.begin(), tt.end(), c.out_t); best = rows; }
+    if (several) {
+      KIN_HIP(hipMemcpyAsync(h->ens_sol.p + (size_t)m0 * (size_t)cap * (size_t)N, sol, (size_t)b.K * (size_t)cap * (size_t)N * sizeof(double),
+                             hipMemcpyDeviceToDevice, h->stream));
+      KIN_HIP(hipStreamSynchronize(h->stream));
+    }
   }
+  h->set_ensemble_record(several ? h->ens_sol.p : sol, c.K, cap, std::move(saved));
 }
 
 }  // namespace kin

@@ -28,6 +28,16 @@ void flux_check(kin_network* h, int64_t B, bool have_k, bool have_row, bool have
   require(h->host.R < ((int64_t)1 << 28) && B < ((int64_t)1 << 31), ERR_UNSUPPORTED, "flux pass: B or R beyond 32-bit offsets");
 }
 
+// the index tables of both passes: uploaded at the first call that needs them
+void ensure_flux_tables(kin_network* h, hipStream_t s) {
+  if (h->flux_ready) return;
+  const FluxTables t = build_flux_tables(h->host);
+  if (!t.idx16.empty()) h->flux_idx16.upload(t.idx16, s);
+  h->flux_idx32.upload(t.idx32, s);
+  KIN_HIP(hipStreamSynchronize(s));   // the host vectors die here
+  h->flux_ready = true;
+}
+
 // The pass itself on device buffers: grows the handle's workspace (may allocate when B or the plan grows), then enqueues.
 void flux_run(kin_network* h, int64_t B, const double* d_u, const FluxSource& src, const double* d_w, double* d_flux,
               double* d_rates, hipStream_t s) {
@@ -36,13 +46,7 @@ void flux_run(kin_network* h, int64_t B, const double* d_u, const FluxSource& sr
     if (d_flux && R > 0) KIN_HIP(hipMemsetAsync(d_flux, 0, (size_t)R * sizeof(double), s));
     return;
   }
-  if (!h->flux_ready) {
-    const FluxTables t = build_flux_tables(h->host);
-    if (!t.idx16.empty()) h->flux_idx16.upload(t.idx16, s);
-    h->flux_idx32.upload(t.idx32, s);
-    KIN_HIP(hipStreamSynchronize(s));   // the host vectors die here
-    h->flux_ready = true;
-  }
+  ensure_flux_tables(h, s);
   if (!src.k && !src.T) h->flush_pending_T(s);   // the handle's own k is about to be read
   const FluxPlan plan = flux_plan(B, R, N, h->n_cu, src.T != nullptr, (reinterpret_cast<uintptr_t>(d_u) & 15) == 0);
   if (d_flux) h->flux_part.alloc((size_t)plan.G * (size_t)R);
@@ -64,6 +68,54 @@ void flux_run(kin_network* h, int64_t B, const double* d_u, const FluxSource& sr
 
 void check_rows(const int64_t* k_row, int64_t B, int64_t n_rows) {
   for (int64_t b = 0; b < B; b++) require(k_row[b] >= 0 && k_row[b] < n_rows, ERR_INVALID_ARG, "k_row: row index out of range");
+}
+
+// The segmented pass on device buffers (kin_flux_segmented*, kin_ensemble_flux): ONE launch that writes d_flux[S][R] itself.
+void flux_seg_run(kin_network* h, int64_t S, int64_t L, const int64_t* d_seg_n, const double* d_u, const FluxSource& src,
+                  const double* d_w, double* d_flux, hipStream_t s) {
+  const int64_t N = h->host.N, R = h->host.R;
+  if (S * L == 0 || R == 0) {
+    if (S * R > 0) KIN_HIP(hipMemsetAsync(d_flux, 0, (size_t)S * (size_t)R * sizeof(double), s));
+    return;
+  }
+  ensure_flux_tables(h, s);
+  if (!src.k && !src.T) h->flush_pending_T(s);   // the handle's own k is about to be read
+  // (every row of a segment must be aligned for path 0: the base and, N being even there, every row behind it)
+  const FluxPlan plan = flux_plan(S * L, R, N, h->n_cu, src.T != nullptr, (reinterpret_cast<uintptr_t>(d_u) & 15) == 0, FLUX_SEG_MAX_ROWS);
+  FluxSegArgs a{};
+  a.N = (int)N; a.R = (int)R; a.P = (int)((R + 1) / 2); a.S = S; a.L = L;
+  a.seg_n = d_seg_n;
+  a.idx16 = reinterpret_cast<const uint2*>(h->flux_idx16.p);
+  a.idx32 = reinterpret_cast<const int4*>(h->flux_idx32.p);
+  a.u = d_u;
+  if (src.T) a.T = src.T;
+  else if (src.k) { a.k = src.k; a.k_stride = src.k_stride; a.k_row = src.k_row; }
+  else { a.k = h->k.p; a.k_stride = 0; a.k_row = nullptr; }
+  a.Ea = h->Ea.p; a.A = h->A.p; a.has_kmax = h->has_kmax ? 1 : 0; a.k_max = h->k_max; a.t_mult = h->t_mult;
+  a.w = d_w;
+  a.flux = d_flux;
+  launch_flux_seg(plan, a, s);
+}
+
+void flux_seg_check(kin_network* h, int64_t S, int64_t L, bool have_k, bool have_row, bool have_T, bool have_out) {
+  require(S >= 0 && L >= 0, ERR_INVALID_ARG, "S or L < 0");
+  require(have_out, ERR_INVALID_ARG, "null output buffer");
+  require(L < ((int64_t)1 << 31) && S < ((int64_t)1 << 31) && S * L < ((int64_t)1 << 31), ERR_UNSUPPORTED,
+          "segmented flux pass: S L beyond 32-bit offsets");
+  flux_check(h, S * L, have_k, have_row, have_T, true);
+}
+
+// host-side checks of per-state keys: only the rows a segment really has are looked at
+void check_seg_rows(const int64_t* k_row, int64_t S, int64_t L, const int64_t* seg_n, int64_t n_rows) {
+  for (int64_t s = 0; s < S; s++) {
+    const int64_t n = seg_n ? seg_n[s] : L;
+    for (int64_t j = 0; j < n; j++)
+      require(k_row[s * L + j] >= 0 && k_row[s * L + j] < n_rows, ERR_INVALID_ARG, "k_row: row index out of range");
+  }
+}
+
+void require_ensemble(const kin_network* h) {
+  require(h->ens.valid(), ERR_STATE, "no ensemble stored (kin_solve_ensemble* first)");
 }
 
 }  // namespace
@@ -136,6 +188,111 @@ int kin_solution_flux(kin_network* h, const double* w, const double* k, int64_t 
            w ? h->f_w.p : nullptr, flux ? h->f_flux.p : nullptr, rates ? h->f_rates.p : nullptr, s);
   if (flux) h->f_flux.download(flux, (size_t)R, s);
   if (rates) h->f_rates.download(rates, (size_t)B * R, s);
+  KIN_HIP(hipStreamSynchronize(s));
+  KIN_CATCH(h)
+}
+
+int kin_flux_segmented_dev(kin_network* h, int64_t S, int64_t L, const int64_t* d_seg_n, const double* d_u, const double* d_k,
+                           const int64_t* d_k_row, const double* d_T, const double* d_w, double* d_flux, void* stream) {
+  if (!h) return KIN_ERR_INVALID_ARG;
+  KIN_TRY(h)
+  flux_seg_check(h, S, L, d_k != nullptr, d_k_row != nullptr, d_T != nullptr, d_flux != nullptr);
+  require(d_u != nullptr || S * L == 0, ERR_INVALID_ARG, "null state buffer");
+  hipStream_t s = stream ? (hipStream_t)stream : h->stream;
+  flux_seg_run(h, S, L, d_seg_n, d_u, FluxSource{d_k, h->host.R, d_k_row, d_T}, d_w, d_flux, s);
+  KIN_CATCH(h)
+}
+
+int kin_flux_segmented(kin_network* h, int64_t S, int64_t L, const int64_t* seg_n, const double* u, const double* k, int64_t n_k_rows,
+                       const int64_t* k_row, const double* T, const double* w, double* flux) {
+  if (!h) return KIN_ERR_INVALID_ARG;
+  KIN_TRY(h)
+  flux_seg_check(h, S, L, k != nullptr, k_row != nullptr, T != nullptr, flux != nullptr);
+  const int64_t B = S * L, N = h->host.N, R = h->host.R;
+  require(u != nullptr || B == 0, ERR_INVALID_ARG, "null state buffer");
+  if (seg_n) for (int64_t i = 0; i < S; i++) require(seg_n[i] >= 0 && seg_n[i] <= L, ERR_INVALID_ARG, "seg_n outside [0, L]");
+  if (k && k_row) { require(n_k_rows >= 1 || B == 0, ERR_INVALID_ARG, "k has no rows"); check_seg_rows(k_row, S, L, seg_n, n_k_rows); }
+  else if (k) require(n_k_rows == B, ERR_INVALID_ARG, "k without k_row needs one row per state (n_k_rows == S L)");
+  hipStream_t s = h->stream;
+  if (B > 0) h->f_u.upload(u, (size_t)B * N, s);
+  if (seg_n && S > 0) h->f_segn.upload(seg_n, (size_t)S, s);
+  if (k && n_k_rows > 0) h->f_k.upload(k, (size_t)n_k_rows * R, s);
+  if (k_row && B > 0) h->f_krow.upload(k_row, (size_t)B, s);
+  if (T && B > 0) h->f_T.upload(T, (size_t)B, s);
+  if (w && B > 0) h->f_w.upload(w, (size_t)B, s);
+  h->f_flux.alloc((size_t)S * R);
+  flux_seg_run(h, S, L, seg_n ? h->f_segn.p : nullptr, h->f_u.p, FluxSource{k ? h->f_k.p : nullptr, R, k_row ? h->f_krow.p : nullptr, T ? h->f_T.p : nullptr},
+               w ? h->f_w.p : nullptr, h->f_flux.p, s);
+  h->f_flux.download(flux, (size_t)S * R, s);
+  KIN_HIP(hipStreamSynchronize(s));
+  KIN_CATCH(h)
+}
+
+int kin_ensemble_size(const kin_network* h, int64_t* K, int64_t* n_rows, int64_t* n_species, int64_t* n_saved) {
+  if (!h) return KIN_ERR_INVALID_ARG;
+  if (!h->ens.valid()) {
+    const_cast<kin_network*>(h)->err = "no ensemble stored (kin_solve_ensemble* first)";
+    return KIN_ERR_STATE;
+  }
+  if (K) *K = h->ens.K;
+  if (n_rows) *n_rows = h->ens.cap;
+  if (n_species) *n_species = h->host.N;
+  if (n_saved) std::copy(h->ens.n_saved.begin(), h->ens.n_saved.end(), n_saved);
+  return KIN_OK;
+}
+
+int kin_ensemble_max(kin_network* h, double* out_umax) {
+  if (!h) return KIN_ERR_INVALID_ARG;
+  KIN_TRY(h)
+  require(out_umax != nullptr, ERR_INVALID_ARG, "null output buffer");
+  require_ensemble(h);
+  const int64_t K = h->ens.K, N = h->host.N;
+  hipStream_t s = h->stream;
+  h->ens_segn.upload(h->ens.n_saved, s);
+  h->ens_out.alloc((size_t)K * N);
+  launch_seg_max((int)N, K, h->ens.cap, h->ens_segn.p, h->ens.sol, h->ens_out.p, s);
+  h->ens_out.download(out_umax, (size_t)K * N, s);
+  KIN_HIP(hipStreamSynchronize(s));
+  KIN_CATCH(h)
+}
+
+int kin_ensemble_dot(kin_network* h, const double* w, double* out) {
+  if (!h) return KIN_ERR_INVALID_ARG;
+  KIN_TRY(h)
+  require(w && out, ERR_INVALID_ARG, "null buffer");
+  require_ensemble(h);
+  const int64_t K = h->ens.K, N = h->host.N, cap = h->ens.cap;
+  require(K * cap < ((int64_t)1 << 31), ERR_UNSUPPORTED, "ensemble dot: K n_rows beyond 32-bit offsets");
+  hipStream_t s = h->stream;
+  h->ens_segn.upload(h->ens.n_saved, s);
+  h->ens_w.upload(w, (size_t)N, s);
+  h->ens_out.alloc((size_t)K * cap);
+  launch_seg_dot((int)N, K, cap, h->ens_segn.p, h->ens.sol, h->ens_w.p, h->ens_out.p, s);
+  h->ens_out.download(out, (size_t)K * cap, s);
+  KIN_HIP(hipStreamSynchronize(s));
+  KIN_CATCH(h)
+}
+
+int kin_ensemble_flux(kin_network* h, const double* w, const double* k, int64_t n_k_rows, const int64_t* k_row, const double* T_rows,
+                      double* flux) {
+  if (!h) return KIN_ERR_INVALID_ARG;
+  KIN_TRY(h)
+  require(flux != nullptr, ERR_INVALID_ARG, "null output buffer");
+  require_ensemble(h);
+  const int64_t K = h->ens.K, cap = h->ens.cap, B = K * cap, R = h->host.R;
+  flux_seg_check(h, K, cap, k != nullptr, k_row != nullptr, T_rows != nullptr, true);
+  if (k && k_row) { require(n_k_rows >= 1, ERR_INVALID_ARG, "k has no rows"); check_seg_rows(k_row, K, cap, h->ens.n_saved.data(), n_k_rows); }
+  else if (k) require(n_k_rows == B, ERR_INVALID_ARG, "k without k_row needs one row per saved row (n_k_rows == K n_rows)");
+  hipStream_t s = h->stream;
+  h->ens_segn.upload(h->ens.n_saved, s);
+  if (k && n_k_rows > 0) h->f_k.upload(k, (size_t)n_k_rows * R, s);
+  if (k_row) h->f_krow.upload(k_row, (size_t)B, s);
+  if (T_rows) h->f_T.upload(T_rows, (size_t)B, s);
+  if (w) h->f_w.upload(w, (size_t)B, s);
+  h->f_flux.alloc((size_t)K * R);
+  flux_seg_run(h, K, cap, h->ens_segn.p, h->ens.sol, FluxSource{k ? h->f_k.p : nullptr, R, k_row ? h->f_krow.p : nullptr, T_rows ? h->f_T.p : nullptr},
+               w ? h->f_w.p : nullptr, h->f_flux.p, s);
+  h->f_flux.download(flux, (size_t)K * R, s);
   KIN_HIP(hipStreamSynchronize(s));
   KIN_CATCH(h)
 }

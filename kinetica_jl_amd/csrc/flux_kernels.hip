@@ -2,6 +2,8 @@
 // out per state and / or summed over the states with weights w_b. FP64, bandwidth shaped like the batched RHS sweep
 // (kernels.hip) minus its accumulator: per state the k row streams once (16-byte non-temporal loads), u is staged in
 // LDS (8 N bytes), nothing is scattered - no LDS atomics.
+// Segmented form (flux_seg_kernel): one workgroup per (segment of states, part of the reactions) sums its segment itself and
+// keeps the rate constants in registers while a segment's key does not change; seg_max_kernel / seg_dot_kernel next to it.
 #include "flux_kernels.hpp"
 
 #include "exp_tab.hpp"
@@ -37,7 +39,7 @@ constexpr int FLUX_BS = 1024;
 constexpr size_t FLUX_LDS_MAX = 160 * 1024;
 constexpr int FLUX_UPT2 = 5;     // double2 per thread of a staged state on path 0 (N <= 10 240)
 
-FluxPlan flux_plan(int64_t B, int64_t R, int64_t N, int n_cu, bool temperature_form, bool u_aligned) {
+FluxPlan flux_plan(int64_t B, int64_t R, int64_t N, int n_cu, bool temperature_form, bool u_aligned, int max_rows) {
   FluxPlan p;
   const int64_t P = std::max<int64_t>((R + 1) / 2, 1);
   const bool lds = flux_env_int("KIN_FLUX_LDS", 1) != 0 && (size_t)(N + 2) * 8 <= FLUX_LDS_MAX && N + 1 < 65536;
@@ -46,7 +48,8 @@ FluxPlan flux_plan(int64_t B, int64_t R, int64_t N, int n_cu, bool temperature_f
   // ids) index registers and 4 for its rate constants in flight; the temperature form also keeps (Ea, A) of its reactions -
   // 8 more per row - and the exponential's temporaries. The caps are the largest counts that compile without scratch
   // (DESIGN 3.1c has the resource report).
-  const int cap = temperature_form ? 2 : (p.path != 0 ? 4 : 8);
+  // (max_rows: the segmented pass also keeps its rate constants across states and stops at 4 rows)
+  const int cap = std::min(max_rows, temperature_form ? 2 : (p.path != 0 ? 4 : 8));
   const int64_t need = ceil_div(P, (int64_t)FLUX_BS);   // rows that cover every pair
   int rows = flux_env_int("KIN_FLUX_ROWS", 0);
   if (rows <= 0) rows = (int)ceil_div(need, ceil_div(need, (int64_t)cap));   // fewest parts, then the fewest rows for them
@@ -209,6 +212,164 @@ __global__ __launch_bounds__(256) void flux_reduce_kernel(int R, int G, const do
   flux[r] = s;
 }
 
+// ---- segmented pass ---------------------------------------------------------------------------------------------------
+// A workgroup = (segment s, part y of the reactions); it walks the segment's rows j = 0 .. seg_n[s] - 1 in order and writes
+// flux[s][.] of its part itself. Staging, labels, clamping and the rate are flux_sweep_kernel's. What the per-state pass cannot do:
+// the lane's rate constants stay in registers from row to row and are loaded (k rows) or evaluated (temperatures) again
+// only when the row's key - k_row[b], or the bits of T[b] - differs from the previous row's. The key is read through an address
+// that depends on (s, j) only, so every lane of the workgroup takes the same side of that branch. The first row always
+// loads. Rows j >= seg_n[s] are never read (the prefetch of the row behind the last is clamped onto the last).
+template <int ROWS, int MODE, int PATH>
+__global__ __launch_bounds__(FLUX_BS) void flux_seg_kernel(FluxSegArgs a) {
+  constexpr int BS = FLUX_BS;
+  constexpr bool LDS = PATH != 2;
+  constexpr int NU = FLUX_UPT2;
+  extern __shared__ double u_s[];
+  const int tid = threadIdx.x;
+  const int N = a.N, R = a.R, P = a.P, Pm1 = P - 1, Rm1 = R - 1;
+  const int64_t L = a.L;
+  const size_t b0 = (size_t)blockIdx.x * (size_t)L;      // first state of the segment
+  int64_t n64 = a.seg_n ? a.seg_n[blockIdx.x] : L;
+  n64 = n64 < 0 ? 0 : (n64 > L ? L : n64);
+  const int n = (int)n64;
+  const int j0 = (int)blockIdx.y * ROWS * BS + tid;     // pair of row i: j0 + i * BS
+  uint2 ix[LDS ? ROWS : 1];
+  int4 jx[LDS ? 1 : ROWS];
+  double2 ea[MODE == FLUX_T ? ROWS : 1], aa[MODE == FLUX_T ? ROWS : 1];
+#pragma unroll
+  for (int i = 0; i < ROWS; i++) {
+    const int jc = min(j0 + i * BS, Pm1);
+    if (LDS) ix[i] = a.idx16[jc]; else jx[i] = a.idx32[jc];
+    if (MODE == FLUX_T) {
+      const int r0 = min(2 * jc, Rm1), r1 = min(2 * jc + 1, Rm1);
+      ea[i] = make_double2(a.Ea[r0], a.Ea[r1]);
+      aa[i] = make_double2(a.A[r0], a.A[r1]);
+    }
+  }
+  double2 acc[ROWS], kk[ROWS];
+#pragma unroll
+  for (int i = 0; i < ROWS; i++) { acc[i] = make_double2(0.0, 0.0); kk[i] = make_double2(0.0, 0.0); }
+  if (LDS && tid == 0) u_s[N] = 1.0;     // the dummy operand: serves x1 < 0
+  double2 un2[PATH == 0 ? NU : 1];
+  (void)un2;
+  auto request = [&](int j) {           // row j of the segment, j < n (the caller clamps)
+    const double* ub = a.u + (b0 + (size_t)j) * N;
+    if (PATH == 0) {
+#pragma unroll
+      for (int x = 0; x < NU; x++) {
+        const double2 t = *reinterpret_cast<const double2*>(ub + min((tid + x * BS) * 2, N - 2));
+        un2[x].x = t.x; un2[x].y = t.y;
+      }
+    }
+  };
+  if (n > 0) request(0);
+  long long key_prev = 0;
+  for (int j = 0; j < n; j++) {
+    const size_t b = b0 + (size_t)j;
+    if (PATH == 0) {
+#pragma unroll
+      for (int x = 0; x < NU; x++) { const int i = (tid + x * BS) * 2; if (i < N) *reinterpret_cast<double2*>(u_s + i) = un2[x]; }
+    }
+    const double* ub = a.u + b * N;
+    if (PATH == 1) for (int i = tid; i < N; i += BS) u_s[i] = ub[i];
+    if (LDS) __syncthreads();
+    request(min(j + 1, n - 1));
+    const double w = *(a.w ? a.w + b : kFluxOne);
+    // the row's key (the same address in every lane)
+    long long key;
+    if (MODE == FLUX_T) key = __double_as_longlong(a.T[b]);
+    else key = a.k_stride == 0 ? 0ll : (a.k_row ? (long long)a.k_row[b] : (long long)b);
+    if (j == 0 || key != key_prev) {
+      int jl = j0;
+      asm volatile("" : "+v"(jl));     // (the row offsets: not hoisted out of the loop into one register per row)
+      if (MODE == FLUX_T) {
+        const double RT = 8.314462618 * __longlong_as_double(key);
+#pragma unroll
+        for (int i = 0; i < ROWS; i++) {
+          kk[i].x = arrhenius_one(ea[i].x, aa[i].x, RT, a.has_kmax, a.k_max, a.t_mult);
+          kk[i].y = arrhenius_one(ea[i].y, aa[i].y, RT, a.has_kmax, a.k_max, a.t_mult);
+        }
+      } else {
+        const double* kb = a.k + (size_t)key * (size_t)a.k_stride;
+#pragma unroll
+        for (int i = 0; i < ROWS; i++) {    // every load of the part is requested before the first one is used
+          const int jc = min(jl + i * BS, Pm1);
+          if (MODE == FLUX_K16) {
+            const flux_d2 v = __builtin_nontemporal_load(reinterpret_cast<const flux_d2*>(reinterpret_cast<const char*>(kb) + (uint32_t)jc * 16u));
+            kk[i].x = v.x; kk[i].y = v.y;
+          } else {
+            kk[i].x = __builtin_nontemporal_load(kb + min(2 * jc, Rm1));
+            kk[i].y = __builtin_nontemporal_load(kb + min(2 * jc + 1, Rm1));
+          }
+        }
+      }
+    }
+    key_prev = key;
+#pragma unroll
+    for (int i = 0; i < ROWS; i++) {
+      double ua0, ub0, ua1, ub1;
+      if (LDS) {
+        uint2 q = ix[i];
+        asm volatile("" : "+v"(q.x), "+v"(q.y));   // (the loop-invariant decode stays two packed words, as in flux_sweep_kernel)
+        ua0 = u_s[q.x & 0xffffu]; ub0 = u_s[q.x >> 16];
+        ua1 = u_s[q.y & 0xffffu]; ub1 = u_s[q.y >> 16];
+      } else {
+        const int4 q = jx[i];
+        ua0 = ub[q.x]; ub0 = *(q.y >= 0 ? ub + q.y : kFluxOne);
+        ua1 = ub[q.z]; ub1 = *(q.w >= 0 ? ub + q.w : kFluxOne);
+      }
+      const double r0 = kk[i].x * ua0 * ub0, r1 = kk[i].y * ua1 * ub1;
+      acc[i].x = __builtin_fma(w, r0, acc[i].x);
+      acc[i].y = __builtin_fma(w, r1, acc[i].y);
+    }
+    if (LDS) __syncthreads();    // u_s is overwritten at the top of the next trip
+  }
+  double* fs = a.flux + (size_t)blockIdx.x * R;
+#pragma unroll
+  for (int i = 0; i < ROWS; i++) {
+    const int j = j0 + i * BS;
+    if (2 * j < R) fs[2 * j] = acc[i].x;
+    if (2 * j + 1 < R) fs[2 * j + 1] = acc[i].y;
+  }
+}
+
+// umax[s][i]: one thread per species, the segment's rows in order (colmax_kernel per segment); an empty segment gives zeros
+__global__ __launch_bounds__(256) void seg_max_kernel(int N, long long L, const int64_t* __restrict__ seg_n, const double* __restrict__ U,
+                                                       double* __restrict__ out) {
+  const int i = blockIdx.y * 256 + threadIdx.x;
+  if (i >= N) return;
+  long long n = seg_n ? seg_n[blockIdx.x] : L;
+  n = n < 0 ? 0 : (n > L ? L : n);
+  const double* us = U + (size_t)blockIdx.x * (size_t)L * N;
+  double v = 0.0;
+  if (n > 0) {
+    v = us[i];
+    for (long long t = 1; t < n; t++) v = fmax(v, us[(size_t)t * N + i]);
+  }
+  out[(size_t)blockIdx.x * N + i] = v;
+}
+
+// dot[b] = sum_i w[i] U[b][i] for the rows of a segment, zeros beyond them: one 256-thread workgroup per state, the summation
+// order of rowdot_kernel (lane sums, a shuffle tree per wavefront, the four wavefronts in order)
+__global__ __launch_bounds__(256) void seg_dot_kernel(int N, long long L, const int64_t* __restrict__ seg_n, const double* __restrict__ U,
+                                                       const double* __restrict__ w, double* __restrict__ out) {
+  __shared__ double sh[4];
+  const long long s = blockIdx.x / L, j = blockIdx.x % L;
+  long long n = seg_n ? seg_n[s] : L;
+  if (j >= n) {                       // (the same in every lane)
+    if (threadIdx.x == 0) out[blockIdx.x] = 0.0;
+    return;
+  }
+  const double* row = U + (size_t)blockIdx.x * N;
+  double acc = 0.0;
+  for (int i = threadIdx.x; i < N; i += 256) acc += w[i] * row[i];
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) acc += __shfl_down(acc, off, 64);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) out[blockIdx.x] = sh[0] + sh[1] + sh[2] + sh[3];
+}
+
 template <int ROWS, int MODE, int PATH, int RATES>
 static void flux_go_t(const FluxPlan& p, const FluxArgs& a, hipStream_t s) {
   const size_t smem = PATH == 2 ? 0 : (size_t)(a.N + 2) * 8;
@@ -255,6 +416,52 @@ void launch_flux_sweep(const FluxPlan& p, const FluxArgs& a, hipStream_t s) {
 void launch_flux_reduce(int64_t R, int G, const double* part, double* flux, hipStream_t s) {
   if (R == 0) return;
   hipLaunchKernelGGL(flux_reduce_kernel, dim3((unsigned)ceil_div(R, 256)), dim3(256), 0, s, (int)R, G, part, flux);
+  KIN_HIP(hipGetLastError());
+}
+
+template <int ROWS, int MODE, int PATH>
+static void flux_seg_go(const FluxPlan& p, const FluxSegArgs& a, hipStream_t s) {
+  const size_t smem = PATH == 2 ? 0 : (size_t)(a.N + 2) * 8;
+  if (PATH != 2) KIN_HIP(hipFuncSetAttribute((const void*)flux_seg_kernel<ROWS, MODE, PATH>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FLUX_LDS_MAX));
+  hipLaunchKernelGGL((flux_seg_kernel<ROWS, MODE, PATH>), dim3((unsigned)a.S, (unsigned)p.parts), dim3(FLUX_BS), smem, s, a);
+}
+
+template <int MODE, int PATH>
+static void flux_seg_go_rows(const FluxPlan& p, const FluxSegArgs& a, hipStream_t s) {
+  if (p.rows == 1) return flux_seg_go<1, MODE, PATH>(p, a, s);
+  if (p.rows == 2) return flux_seg_go<2, MODE, PATH>(p, a, s);
+  if constexpr (MODE != FLUX_T) {   // (flux_plan with FLUX_SEG_MAX_ROWS: the temperature form stops at 2 rows, the others at 4)
+    if (p.rows == 4) return flux_seg_go<4, MODE, PATH>(p, a, s);
+  }
+  throw KinError(ERR_INVALID_ARG, "segmented flux pass: no instantiation for this row count");
+}
+
+void launch_flux_seg(const FluxPlan& p, const FluxSegArgs& a, hipStream_t s) {
+  if (a.S == 0 || a.R == 0) return;
+  int mode = FLUX_T;
+  if (!a.T) mode = (a.R % 2 == 0 && (a.k_stride % 2 == 0) && ((reinterpret_cast<uintptr_t>(a.k) & 15) == 0)) ? FLUX_K16 : FLUX_K8;
+#define KIN_FLUX_SEG_PATHS(MODE)                                    \
+  do {                                                              \
+    if (p.path == 0) flux_seg_go_rows<MODE, 0>(p, a, s);            \
+    else if (p.path == 1) flux_seg_go_rows<MODE, 1>(p, a, s);       \
+    else flux_seg_go_rows<MODE, 2>(p, a, s);                        \
+  } while (0)
+  if (mode == FLUX_K16) KIN_FLUX_SEG_PATHS(FLUX_K16);
+  else if (mode == FLUX_K8) KIN_FLUX_SEG_PATHS(FLUX_K8);
+  else KIN_FLUX_SEG_PATHS(FLUX_T);
+#undef KIN_FLUX_SEG_PATHS
+  KIN_HIP(hipGetLastError());
+}
+
+void launch_seg_max(int N, int64_t S, int64_t L, const int64_t* seg_n, const double* u, double* umax, hipStream_t s) {
+  if (S == 0 || N == 0) return;
+  hipLaunchKernelGGL(seg_max_kernel, dim3((unsigned)S, (unsigned)ceil_div(N, 256)), dim3(256), 0, s, N, (long long)L, seg_n, u, umax);
+  KIN_HIP(hipGetLastError());
+}
+
+void launch_seg_dot(int N, int64_t S, int64_t L, const int64_t* seg_n, const double* u, const double* w, double* dot, hipStream_t s) {
+  if (S * L == 0) return;
+  hipLaunchKernelGGL(seg_dot_kernel, dim3((unsigned)(S * L)), dim3(256), 0, s, N, (long long)L, seg_n, u, w, dot);
   KIN_HIP(hipGetLastError());
 }
 

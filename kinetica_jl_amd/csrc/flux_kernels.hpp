@@ -25,7 +25,7 @@ FluxTables build_flux_tables(const NetworkHost& h);
 //          2: u gathered from global memory (8 (N + 1) bytes do not fit LDS, or KIN_FLUX_LDS=0)
 struct FluxPlan { int rows, parts, G, path; };
 enum FluxMode : int { FLUX_K16 = 0, FLUX_K8 = 1, FLUX_T = 2 };   // k rows as double2 / as doubles / Arrhenius law at T[b]
-FluxPlan flux_plan(int64_t B, int64_t R, int64_t N, int n_cu, bool temperature_form, bool u_aligned);
+FluxPlan flux_plan(int64_t B, int64_t R, int64_t N, int n_cu, bool temperature_form, bool u_aligned, int max_rows = 8);
 
 struct FluxArgs {
   int N, R, P, B;                  // P = ceil(R / 2) pairs
@@ -45,5 +45,29 @@ struct FluxArgs {
 void launch_flux_sweep(const FluxPlan& plan, const FluxArgs& a, hipStream_t s);
 // flux[r] = part[0][r] + part[1][r] + ... + part[G - 1][r], in that order
 void launch_flux_reduce(int64_t R, int G, const double* part, double* flux, hipStream_t s);
+
+// Segmented flux pass (kin_flux_segmented*, kin_ensemble_flux): S segments of up to L states each, state b = s L + j at
+// u[b][N]; flux[s][r] = sum over j < seg_n[s] of w[b] rate_r(u_b; k of state b), summed in row order by the ONE workgroup
+// that owns (segment, part of the reactions) - no partial sums, no reduce launch; a segment's result depends on its own
+// rows only. rows / parts / path are flux_plan's with max_rows = FLUX_SEG_MAX_ROWS - eight rows AND their rate constants held
+// across states do not fit 128 registers - and its G is not used: the grid is (S, parts).
+constexpr int FLUX_SEG_MAX_ROWS = 4;
+struct FluxSegArgs {
+  int N, R, P;                     // P = ceil(R / 2) pairs
+  int64_t S, L;
+  const int64_t* seg_n;            // seg_n[S] (clamped to [0, L]) or null: every segment has L rows
+  const uint2* idx16; const int4* idx32;
+  const double* u;                 // u[S L][N]
+  const double* k; int64_t k_stride; const int64_t* k_row;   // as FluxArgs
+  const double* T;                 // T[S L]
+  const double* Ea; const double* A; int has_kmax; double k_max, t_mult;
+  const double* w;                 // w[S L] or null (weights 1)
+  double* flux;                    // flux[S][R]
+};
+void launch_flux_seg(const FluxPlan& plan, const FluxSegArgs& a, hipStream_t s);
+// umax[s][i] = max over j < seg_n[s] of u[s L + j][i]; zeros for an empty segment
+void launch_seg_max(int N, int64_t S, int64_t L, const int64_t* seg_n, const double* u, double* umax, hipStream_t s);
+// dot[s][j] = sum_i w[i] u[s L + j][i] for j < seg_n[s] (rowdot_kernel's summation order), zeros beyond
+void launch_seg_dot(int N, int64_t S, int64_t L, const int64_t* seg_n, const double* u, const double* w, double* dot, hipStream_t s);
 
 }  // namespace kin

@@ -61,7 +61,7 @@ struct kin_network {
   kin::DevBuf<uint32_t> flux_idx16;
   kin::DevBuf<int32_t> flux_idx32;
   kin::DevBuf<double> flux_part, f_u, f_k, f_T, f_w, f_flux, f_rates;
-  kin::DevBuf<int64_t> f_krow;
+  kin::DevBuf<int64_t> f_krow, f_segn;
 
   // tiled sweep in library order (tiled.hpp, tiled_api.cpp): built at the first call that needs it
   kin::TiledHost tiled;
@@ -86,6 +86,23 @@ struct kin_network {
   std::vector<double> sol_t, sol_u;
   kin::DevBuf<double> d_sol_u;   // saved states on the device, [n_saved][N]
   int64_t n_saved = 0;
+
+  // The last ensemble call's saved states, where they live: sol[K][cap][N] (rows past n_saved[m] are zeros) in the resident
+  // solver's or the lockstep ensemble's own buffer, or in ens_sol (thread route, lockstep calls of several blocks: the members'
+  // rows copied device-to-device). Cleared when an ensemble call starts, set when it succeeded; the buffers it may point to are
+  // reallocated by ensemble calls only (ResidentSolver::ensure with own_sol, EnsembleSolver::prepare, replica_ensemble).
+  struct EnsembleRecord {
+    const double* sol = nullptr;
+    int64_t K = 0, cap = 0;
+    std::vector<int64_t> n_saved;
+    bool valid() const { return sol != nullptr && K > 0; }
+    void clear() { sol = nullptr; K = 0; cap = 0; n_saved.clear(); }
+  } ens;
+  kin::DevBuf<double> ens_sol, ens_w, ens_out;   // handle-owned copy of the saved states; workspaces of kin_ensemble_max / _dot
+  kin::DevBuf<int64_t> ens_segn;                 // n_saved[K] on the device
+  void set_ensemble_record(const double* sol, int64_t K, int64_t cap, std::vector<int64_t> n_saved) {
+    ens.sol = sol; ens.K = K; ens.cap = cap; ens.n_saved = std::move(n_saved);
+  }
 
   kin_network();
   ~kin_network();

@@ -28,7 +28,7 @@ __all__ = ["SpeciesData", "RxData", "RxFilter", "get_filter_mask", "DummyKinetic
            "HIPBDF", "HIPRK45", "ArrheniusRates", "solve_network", "identify_next_seeds", "insert_inert", "ODESolveOutput", "ODESolution", "tconvert", "make_u0", "apply_low_k_cutoff",
            "get_max_rates", "get_initial_rates", "calculate_discrete_rates",
            "solve_network_ensemble",   # EXTENSION: the reference has no ensemble call
-           "flux_weights", "held_stop_index", "ReactionFluxes", "reaction_fluxes"]   # EXTENSION: post-hoc flux analysis
+           "flux_weights", "held_stop_index", "ReactionFluxes", "reaction_fluxes", "ensemble_flux_sources"]   # EXTENSION: post-hoc flux analysis
 
 _T_UNIT = {  # src/utils.jl:77-97
     "picoseconds": 1.0e-12, "ps": 1.0e-12, "nanoseconds": 1.0e-9, "ns": 1.0e-9, "microseconds": 1.0e-6, "us": 1.0e-6,
@@ -441,6 +441,7 @@ class ODESolution:
     k: Optional[object] = None
     stats: dict = field(default_factory=dict)
     umax: Optional[np.ndarray] = None    # max over saved times per species, reduced on the device (kin_solution_max)
+    fluxes: Optional[object] = None      # ReactionFluxes of the solve (solve_network_ensemble(fluxes=True)), else None
 
     def __call__(self, tq):
         """Linear interpolation res.sol(t) (docs/src/getting-started.md:232-236)."""
@@ -698,7 +699,7 @@ def apply_ensemble_low_k_cutoff(rd, calc, pars, condition_sets):
     return rids
 
 
-def solve_network_ensemble(methods, sd, rd, copy_network=True):
+def solve_network_ensemble(methods, sd, rd, copy_network=True, fluxes=False, trajectories=True):
     """EXTENSION (the reference has no ensemble call: it solves member after member through solve_network): K
     `VariableODESolve`s with Arrhenius condition sets - one temperature profile each, e.g. a set of heating rates or start
     temperatures - on one network in ONE ensemble call: kin_solve_ensemble_continuous when every set is continuous,
@@ -717,7 +718,13 @@ def solve_network_ensemble(methods, sd, rd, copy_network=True):
     sol_k = None, discrete-update sets sol_vcs = None and sol_k = sol.k = ArrheniusRates of the member's own stops; sol.umax;
     sol.retcode the member's own (a failed member does not raise: the others' results stand); update_tols writes the
     member's final tolerances into its own `pars`. Ensembles are BDF only (pars.explicit raises ValueError). Static and
-    non-Arrhenius sets raise ValueError: use HipNetwork.solve_ensemble (kin_solve_ensemble) or solve_network for those."""
+    non-Arrhenius sets raise ValueError: use HipNetwork.solve_ensemble (kin_solve_ensemble) or solve_network for those.
+
+    fluxes=True: every member's sol.fluxes is its ReactionFluxes - what reaction_fluxes(out, calculator) gives, trapezoid
+    weights over the member's own saved times and the rate constants the solve held there - from ONE segmented pass over the
+    members' states where they live on the device (kin_ensemble_flux), before the handle closes. trajectories=False: no
+    state is downloaded; sol.u is None, sol.t the member's saved times, sol.umax kin_ensemble_max's. With the defaults the
+    function does what it did before either existed."""
     methods = list(methods)
     if not methods:
         raise ValueError("solve_network_ensemble needs at least one method")
@@ -771,16 +778,23 @@ def solve_network_ensemble(methods, sd, rd, copy_network=True):
     h = capi.HipNetwork(*rd_a.flat(sd_a.n), index_base=1)
     try:
         h.set_arrhenius(calc.Ea, calc.A, calc.k_max, calc.t_mult)
+        kw = {} if trajectories else dict(trajectories=False)   # (the defaults: the call as it always was)
         if discrete:
-            t, u, ns, rcs, sts = h.solve_ensemble_discrete(pars.to_kin_params(), U0, stops)
+            t, u, ns, rcs, sts = h.solve_ensemble_discrete(pars.to_kin_params(), U0, stops, **kw)
         else:
-            t, u, ns, rcs, sts = h.solve_ensemble_continuous(pars.to_kin_params(), U0, nodes)
+            t, u, ns, rcs, sts = h.solve_ensemble_continuous(pars.to_kin_params(), U0, nodes, **kw)
+        dev_umax = None if trajectories else h.ensemble_max()
+        F = None
+        if fluxes:
+            src = ensemble_flux_sources("discrete_members", t, ns, stops=stops) if discrete else \
+                ensemble_flux_sources("continuous", t, ns, nodes=nodes)
+            F = h.ensemble_flux(w=src["w"], T_rows=src["T_rows"])
     finally:
         h.close()
     out = []
     for i, m in enumerate(methods):
         n_i = int(ns[i])
-        ti, ui = t[:n_i].copy(), u[i, :n_i].copy()
+        ti, ui = t[:n_i].copy(), (u[i, :n_i].copy() if trajectories else None)
         if discrete:
             sol_vcs = None
             sol_k = ArrheniusRates(stops[i][0], stops[i][1], m.calculator.Ea, m.calculator.A, m.calculator.k_max, m.calculator.t_mult)
@@ -791,8 +805,12 @@ def solve_network_ensemble(methods, sd, rd, copy_network=True):
         st = sts[i]
         if m.pars.update_tols and st["final_abstol"] != m.pars.abstol:
             m.pars.abstol, m.pars.reltol = st["final_abstol"], st["final_reltol"]   # solve_utils.jl:397-401
-        umax = ui.max(axis=0) if n_i else np.zeros(sd_a.n)
-        sol = ODESolution(ti, ui, capi.RETCODE_NAMES[int(rcs[i])], k=sol_k, stats=st, umax=umax)
+        if trajectories:
+            umax = ui.max(axis=0) if n_i else np.zeros(sd_a.n)
+        else:
+            umax = dev_umax[i]
+        fl = None if F is None else ReactionFluxes.from_flux(F[i], rd_a, sd_a.n, src["w"][i, :n_i])
+        sol = ODESolution(ti, ui, capi.RETCODE_NAMES[int(rcs[i])], k=sol_k, stats=st, umax=umax, fluxes=fl)
         out.append(ODESolveOutput(sd_a, rd_a, sol, sol_k, sol_vcs, m.pars, m.conditions))
     return out
 
@@ -819,6 +837,57 @@ def held_stop_index(t, tstops):
     before the first stop the first stop's."""
     idx = np.searchsorted(np.asarray(tstops, dtype=float), np.asarray(t, dtype=float), side="right") - 1
     return np.clip(idx, 0, None).astype(np.int64)
+
+
+def ensemble_flux_sources(kind, t, n_saved, T=None, tstops=None, T_stops=None, stops=None, nodes=None):
+    """What kin_ensemble_flux needs per (member, row of the save grid) of an ensemble call, pure NumPy. t[M]: the call's save
+    grid (its out_t), n_saved[K]: the members' saved rows. Returns dict(w=[K][M], and k_row=[K][M] (int64) or T_rows=[K][M]):
+      w       flux_weights(t[:n_saved[m]]) in member m's first n_saved[m] entries, zeros beyond (no saved row: all zeros);
+      the rate constants a member's solve held at each saved time, by `kind`:
+        "static"            T=None: k_row = m (kin_solve_ensemble's per-member k[K][R] handed on as the table); T[K]: T_rows = T[m]
+        "discrete"          stops shared by the members (tstops): held_stop_index(t, tstops), as T_rows = T_stops[held] or, without
+                            T_stops, as k_row = held (rows of the k_table)
+        "discrete_members"  stops: K pairs (tstops_m, T_stops_m): T_rows[m] = T_stops_m[held_stop_index(t, tstops_m)]
+        "continuous"        nodes: K pairs (t_nodes_m, T_nodes_m): T_rows[m] = np.interp(t, t_nodes_m, T_nodes_m)
+    Keys are formed for every row of the grid; the pass ignores those past a member's saved rows."""
+    t = np.asarray(t, dtype=float).ravel()
+    n_saved = np.asarray(n_saved, dtype=np.int64).ravel()
+    K, M = len(n_saved), len(t)
+    if np.any(n_saved < 0) or np.any(n_saved > M):
+        raise ValueError("n_saved must lie in [0, len(t)]")
+    w = np.zeros((K, M))
+    for m in range(K):
+        n = int(n_saved[m])
+        if n >= 1:
+            w[m, :n] = flux_weights(t[:n])
+    out = dict(w=w)
+    if kind == "static":
+        if T is None:
+            out["k_row"] = np.repeat(np.arange(K, dtype=np.int64)[:, None], M, axis=1)
+        else:
+            T = np.asarray(T, dtype=float).ravel()
+            if len(T) != K:
+                raise ValueError("T must have one entry per member")
+            out["T_rows"] = np.repeat(T[:, None], M, axis=1)
+    elif kind == "discrete":
+        if tstops is None:
+            raise ValueError('kind "discrete" needs tstops')
+        held = held_stop_index(t, tstops)
+        if T_stops is None:
+            out["k_row"] = np.repeat(held[None, :], K, axis=0)
+        else:
+            out["T_rows"] = np.repeat(np.asarray(T_stops, dtype=float)[held][None, :], K, axis=0)
+    elif kind == "discrete_members":
+        if stops is None or len(stops) != K:
+            raise ValueError('kind "discrete_members" needs one (tstops, T_stops) pair per member')
+        out["T_rows"] = np.stack([np.asarray(Ts, dtype=float)[held_stop_index(t, ts)] for ts, Ts in stops]) if K else np.zeros((0, M))
+    elif kind == "continuous":
+        if nodes is None or len(nodes) != K:
+            raise ValueError('kind "continuous" needs one (t_nodes, T_nodes) pair per member')
+        out["T_rows"] = np.stack([np.interp(t, np.asarray(tn, dtype=float), np.asarray(Tn, dtype=float)) for tn, Tn in nodes]) if K else np.zeros((0, M))
+    else:
+        raise ValueError('kind must be "static", "discrete", "discrete_members" or "continuous"')
+    return out
 
 
 @dataclass

@@ -73,7 +73,7 @@ const char* kin_last_error(const kin_network* h);
 int kin_set_rates(kin_network* h, const double* k);
 int kin_get_rates(kin_network* h, double* k_out);
 /* PrecalculatedArrheniusCalculator parameters (calculator.jl:164-198). k_max = NaN means
- * `k_max = nothing`; t_mult = tconvert(t_unit, "s") (calculator.jl:196, utils.jl:21-30). */
+ * `k_max = nothing`, and so does k_max = +inf (1 / (0 + 1/k_r) = k_r; also in kin_arrhenius_eval); t_mult = tconvert(t_unit, "s") (calculator.jl:196, utils.jl:21-30). */
 int kin_set_arrhenius(kin_network* h, const double* Ea, const double* A, double k_max, double t_mult);
 /* k = calculator(; T) (calculator.jl:223-232) evaluated on the device; becomes the
  * handle's current rate vector; k_out (host, R doubles) may be NULL. */

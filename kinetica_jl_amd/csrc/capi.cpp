@@ -221,7 +221,8 @@ int kin_set_arrhenius(kin_network* h, const double* Ea, const double* A, double 
   h->Ea.upload(Ea, h->host.R, h->stream);
   h->A.upload(A, h->host.R, h->stream);
   KIN_HIP(hipStreamSynchronize(h->stream));
-  h->has_kmax = !std::isnan(k_max);
+  // a cap at +inf is no cap (1 / (0 + 1/k_r) = k_r): the capped fast form would take the reciprocal of x = 0 where k_r overflows
+  h->has_kmax = !std::isnan(k_max) && !std::isinf(k_max);
   h->k_max = h->has_kmax ? k_max : 1.0;
   h->t_mult = t_mult;
   h->has_arrhenius = true;
@@ -248,7 +249,7 @@ int kin_arrhenius_eval(const double* Ea, const double* A, int64_t n, double k_ma
   require(Ea && A && k_out && n >= 0, ERR_INVALID_ARG, "bad arguments");
   DevBuf<double> dEa, dA, dk;
   dEa.upload(Ea, n); dA.upload(A, n); dk.alloc(n);
-  const bool has = !std::isnan(k_max);
+  const bool has = !std::isnan(k_max) && !std::isinf(k_max);   // (as kin_set_arrhenius)
   launch_arrhenius(n, dEa.p, dA.p, has, has ? k_max : 1.0, t_mult, T, dk.p, nullptr);
   dk.download(k_out, n);
   KIN_HIP(hipStreamSynchronize(nullptr));

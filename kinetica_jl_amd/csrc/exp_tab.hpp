@@ -1,7 +1,13 @@
 // Table-driven exp and the division-free Arrhenius evaluation shared by the rate-table kernels (kernels.hip,
 // tiled_kernels.hip) and the sweep that forms its rate constants itself (tiled_kernels.hip, TMODE).
 #pragma once
+#ifdef __HIPCC__
 #include <hip/hip_runtime.h>
+#define KIN_RCP_F64(x) __builtin_amdgcn_rcp(x)
+#else
+// host replay (tests/native_exp defines __device__ / __forceinline__ itself): the reciprocal seed as a division
+#define KIN_RCP_F64(x) (1.0 / (x))
+#endif
 
 namespace kin {
 
@@ -25,7 +31,9 @@ __device__ __forceinline__ double arrhenius_one(double Ea, double A, double RT, 
 // r = x - n ln2/512 (two-part constant, n * hi exact: hi has 31 significant bits, |n| < 2^21 after the clamp),
 // |r| <= ln2/1024 = 6.8e-4, e^r - 1 = r (1 + r (1/2 + r (1/6 + r/24))) (remainder r^5/120 < 1.3e-18 relative),
 // T[j] = 2^(j/512) correctly rounded (exp2_tab.inc), kept in LDS. 11 FP64 operations instead of the 19 of exp_lean
-// (degree-13 polynomial): the table kernel is FP64-VALU bound under sustained load. <= 1 ulp.
+// (degree-13 polynomial): the table kernel is FP64-VALU bound under sustained load. <= 2 x 2^-53 relative
+// for normal results (measured 1.98 for this table, 1.86 for the 128-entry one, against long double over [-708, 708]); a
+// subnormal result is within one quantum 2^-1074.
 static __device__ const double kExp2Tab[512] = {
 #include "exp2_tab.inc"
 };
@@ -52,16 +60,25 @@ __device__ __forceinline__ double exp_tab_t(double x, const double* __restrict__
 }
 __device__ __forceinline__ double exp_tab(double x, const double* __restrict__ tab_s) { return exp_tab_t<512>(x, tab_s); }
 
+// 1 / (R T) of a row or a state for arrhenius_fast_t, finite at T = 0: with inv_RT = inf the quotient's residual correction
+// is inf * 0 = NaN for every Ea and k = 0 even where the law's limit is k_max (Ea < 0). With 1e300 the quotient is +-huge
+// (clamped: k = 0 for Ea > 0, the upper limit for Ea < 0) and 0 for Ea = 0 (k = A N_A t_mult, the value at every T > 0).
+// Taken once per row / per state, outside the element loop.
+__device__ __forceinline__ double arrhenius_inv_RT(double RT) { return fmin(1.0 / RT, 1e300); }
+
 // c = A N_A t_mult, inv_c = 1 / c
 template <int TAB>
 __device__ __forceinline__ double arrhenius_fast_t(double Ea, double c, double inv_c, double RT, double inv_RT, int has_kmax,
                                                    double inv_kmax, const double* __restrict__ tab_s) {
   double q = Ea * inv_RT;
   q = fma(fma(-q, RT, Ea), inv_RT, q);
-  q = fmin(q, 800.0);                                     // e^800 overflows anyway; keeps n inside the table arithmetic
+  // e^800 overflows and e^-800 vanishes anyway; the clamp keeps n inside the table arithmetic at BOTH ends: below
+  // q = -2^31 ln2 / TAB the conversion (int)n is out of range (undefined in C++; right before only because v_cvt_i32_f64
+  // saturates), and an overflowing n makes the reduction inf - inf. inv_RT comes from arrhenius_inv_RT: finite at T = 0
+  q = fmax(fmin(q, 800.0), -800.0);
   if (!has_kmax) return c * exp_tab_t<TAB>(-q, tab_s);
   const double x = fma(inv_c, exp_tab_t<TAB>(q, tab_s), inv_kmax);     // 1/k_max + 1/k_r
-  double y = __builtin_amdgcn_rcp(x);
+  double y = KIN_RCP_F64(x);
   y = fma(fma(-x, y, 1.0), y, y);
   y = fma(fma(-x, y, 1.0), y, y);
   return x < 1e300 ? y : 0.0;

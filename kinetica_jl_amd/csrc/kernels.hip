@@ -225,7 +225,7 @@ __global__ __launch_bounds__(256) void rate_table_kernel(int n, int n_stops, con
   if ((int)threadIdx.x < s1 - s0) {
     const double RT = 8.314462618 * T[s0 + threadIdx.x];
     rt_s[threadIdx.x] = RT;
-    irt_s[threadIdx.x] = 1.0 / RT;
+    irt_s[threadIdx.x] = arrhenius_inv_RT(RT);
   }
   __syncthreads();
   const int r = (blockIdx.x * 256 + threadIdx.x) * 2;

@@ -222,7 +222,7 @@ __global__ __launch_bounds__(BS) void tiled_sweep_kernel(TiledView v, int B, con
   for (; b < B; b += gridDim.x) {
     double* dub = du + (size_t)b * N;
     const int bn = b + gridDim.x;
-    if (TMODE) { RT = 8.314462618 * Tn; inv_RT = 1.0 / RT; }
+    if (TMODE) { RT = 8.314462618 * Tn; inv_RT = arrhenius_inv_RT(RT); }
 #if defined(KIN_TILED_PROBE) && KIN_TILED_PROBE == 3   // timing only: the record / k queue alone, no staging, barriers or write-out
     for (int s = 0; s < T; s++) {
       pn = v.seginfo[ps + 1 == T ? 0 : ps + 1];
@@ -440,7 +440,7 @@ __global__ __launch_bounds__(256) void rate_table_lib_kernel(int P, int64_t KL, 
   if ((int)threadIdx.x < s1 - s0) {
     const double RT = 8.314462618 * T[s0 + threadIdx.x];
     rt_s[threadIdx.x] = RT;
-    irt_s[threadIdx.x] = 1.0 / RT;
+    irt_s[threadIdx.x] = arrhenius_inv_RT(RT);
   }
   __syncthreads();
   const int p = blockIdx.x * 256 + threadIdx.x;

@@ -6,6 +6,7 @@
 
 #include "exp_tab.hpp"
 #include "segsum_dev.hpp"
+#include "step_dev.hpp"
 
 #include <algorithm>
 
@@ -32,69 +33,10 @@ SegPlanView SegPlanDev::view() const {
 // ------------------------------------------------------------------------------------------
 // deterministic segmented gather-sum
 // ------------------------------------------------------------------------------------------
-// grid of 1024-thread workgroups: the first p.B take one LONG row each (whole workgroup, BLK_PASS entries per pass, so
-// that all but the very longest rows are ONE round of index loads + gathers), the others sixteen wavefront tasks each
-// (an ELL group of 64 short rows, or one medium row)
-// (plans without long rows are launched with 256-thread workgroups: small workgroups start ~1.5 us sooner)
+// (the traversal of the plan by the grid: segsum_dev.hpp, seg_traverse)
 template <int OP, int SEG_WG>
 __global__ __launch_bounds__(SEG_WG) void segsum_kernel(SegPlanView p, const double* src, double* out, SegExtra ex) {
-  constexpr int SEG_WAVES = SEG_WG / 64, BLK_PER_THREAD = SegPlanHost::BLK_PASS / 1024;
-  const int skip = ex.skip ? *ex.skip : 0;
-  const int lane = threadIdx.x & 63;
-  const bool impl = p.val_base >= 0;                    // value-ordered plan: first factor of slot q = src[val_base + q]
-  if (SEG_WG == 1024 && (int)blockIdx.x < p.B) {
-    __shared__ double sh[SEG_WAVES];
-    const int r = blockIdx.x;
-    const int32_t e0 = p.blk_beg[r], e1 = p.blk_end[r];
-    const int32_t bdst = p.blk_dst[r];
-    const int32_t baux = p.blk_aux[r];
-    if (skip) return;      // (whole workgroup: the flag is uniform) tested once the first round of loads is back, see above
-    const SegPre pre = seg_pre<OP>(out, src, threadIdx.x == 0 ? bdst : -1, baux, ex);
-    double acc = 0.0;
-    for (int32_t base = e0; base < e1; base += SegPlanHost::BLK_PASS)
-      acc += seg_gather<OP, BLK_PER_THREAD, false>(p, src, ex, impl, [&](int x) {
-        const int32_t e = base + (int32_t)threadIdx.x + 1024 * x;
-        return e < e1 ? e : -1;
-      });
-    acc = wave_sum(acc);
-    if (lane == 0) sh[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      double tot = 0.0;
-#pragma unroll
-      for (int w = 0; w < SEG_WAVES; w++) tot += sh[w];     // fixed order
-      seg_store<OP>(out, bdst, tot, pre, ex);
-    }
-    return;
-  }
-  const int task = ((int)blockIdx.x - p.B) * SEG_WAVES + (threadIdx.x >> 6);
-  if (task < p.G) {
-    const int32_t dst = p.grp_dst[task * 64 + lane];
-    const int32_t aux = p.grp_aux[task * 64 + lane];
-    const int32_t c0 = p.grp_off[task], c1 = p.grp_off[task + 1];
-    if (skip) return;
-    const SegPre pre = seg_pre<OP>(out, src, dst, aux, ex);
-    double acc = 0.0;
-    for (int32_t col = c0; col < c1; col += 8)       // a whole ELL group in one round: rows have <= 8 entries
-      acc += seg_gather<OP, 8, true>(p, src, ex, impl, [&](int x) { return col + x < c1 ? (col + x) * 64 + lane : -1; });
-    if (dst >= 0) seg_store<OP>(out, dst, acc, pre, ex);
-  } else if (task < p.G + p.S) {
-    const int sidx = task - p.G;
-    const int32_t e0 = p.seg_beg[sidx], e1 = p.seg_end[sidx];
-    const int32_t sdst = p.seg_dst[sidx];
-    const int32_t saux = p.seg_aux[sidx];
-    if (skip) return;
-    const SegPre pre = seg_pre<OP>(out, src, lane == 0 ? sdst : -1, saux, ex);
-    // up to 256 entries: four per lane; up to 1024: sixteen per lane - either way ONE round of index loads and ONE
-    // round of gathers, all in flight together
-    double acc;
-    if (e1 - e0 <= 256)
-      acc = seg_gather<OP, 4, false>(p, src, ex, impl, [&](int x) { const int32_t e = e0 + lane + 64 * x; return e < e1 ? e : -1; });
-    else
-      acc = seg_gather<OP, 16, false>(p, src, ex, impl, [&](int x) { const int32_t e = e0 + lane + 64 * x; return e < e1 ? e : -1; });
-    acc = wave_sum(acc);
-    if (lane == 0) seg_store<OP>(out, sdst, acc, pre, ex);
-  }
+  seg_traverse<OP, SEG_WG>(p, src, out, ex, ex.skip);
 }
 
 void launch_segsum(const SegPlanView& p, SegOp op, const double* src, double* out, const SegExtra& ex, hipStream_t s) {
@@ -119,14 +61,14 @@ void launch_segsum(const SegPlanView& p, SegOp op, const double* src, double* ou
 // ------------------------------------------------------------------------------------------
 // per-reaction rates and operand derivatives (make_rs mass action, solve_utils.jl:318-334)
 // ------------------------------------------------------------------------------------------
+// (the arithmetic of one reaction: step_dev.hpp, mass_action_rate / mass_action_drates)
 __global__ __launch_bounds__(256) void rates_kernel(int R, const double* __restrict__ k, const double* __restrict__ u,
                                                     const int32_t* __restrict__ x0, const int32_t* __restrict__ x1,
                                                     double* __restrict__ rate) {
   const int r = blockIdx.x * 256 + threadIdx.x;
   if (r >= R) return;
   const int32_t a = x0[r], b = x1[r];
-  const double ub = b >= 0 ? u[b] : 1.0;
-  rate[r] = k[r] * u[a] * ub;
+  rate[r] = mass_action_rate(k[r], u, a, b);
 }
 
 // dr[2r]   = d rate_r / d u[x0]   (2A: 2 k u, single column)
@@ -136,13 +78,7 @@ __global__ __launch_bounds__(256) void drates_kernel(int R, const double* __rest
                                                      double* __restrict__ dr) {
   const int r = blockIdx.x * 256 + threadIdx.x;
   if (r >= R) return;
-  const int32_t a = x0[r], b = x1[r];
-  const double kk = k[r];
-  double d0, d1 = 0.0;
-  if (b < 0) d0 = kk;
-  else if (b == a) d0 = 2.0 * kk * u[a];
-  else { d0 = kk * u[b]; d1 = kk * u[a]; }
-  reinterpret_cast<double2*>(dr)[r] = make_double2(d0, d1);
+  reinterpret_cast<double2*>(dr)[r] = mass_action_drates(k[r], u, x0[r], x1[r]);
 }
 
 // The same two kernels with the rate constants formed on the spot from a temperature (continuous-rate solves: the first
@@ -156,8 +92,7 @@ __global__ __launch_bounds__(256) void rates_T_kernel(int R, ArrheniusAt at, dou
   const int32_t a = x0[r], b = x1[r];
   const double kk = arrhenius_one(at.Ea[r], at.A[r], 8.314462618 * at.T, at.has_kmax, at.k_max, at.t_mult);
   k[r] = kk;
-  const double ub = b >= 0 ? u[b] : 1.0;
-  rate[r] = kk * u[a] * ub;
+  rate[r] = mass_action_rate(kk, u, a, b);
 }
 __global__ __launch_bounds__(256) void drates_T_kernel(int R, ArrheniusAt at, double* __restrict__ k, const double* __restrict__ u,
                                                        const int32_t* __restrict__ x0, const int32_t* __restrict__ x1,
@@ -167,11 +102,7 @@ __global__ __launch_bounds__(256) void drates_T_kernel(int R, ArrheniusAt at, do
   const int32_t a = x0[r], b = x1[r];
   const double kk = arrhenius_one(at.Ea[r], at.A[r], 8.314462618 * at.T, at.has_kmax, at.k_max, at.t_mult);
   k[r] = kk;
-  double d0, d1 = 0.0;
-  if (b < 0) d0 = kk;
-  else if (b == a) d0 = 2.0 * kk * u[a];
-  else { d0 = kk * u[b]; d1 = kk * u[a]; }
-  reinterpret_cast<double2*>(dr)[r] = make_double2(d0, d1);
+  reinterpret_cast<double2*>(dr)[r] = mass_action_drates(kk, u, a, b);
 }
 void launch_rates_T(int64_t R, const ArrheniusAt& at, double* k, const double* u, const int32_t* x0, const int32_t* x1, double* rate, hipStream_t s) {
   if (R == 0) return;

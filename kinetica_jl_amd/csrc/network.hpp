@@ -21,8 +21,8 @@ struct SegPlanHost {
   // longest dependent chain per wavefront: ELL rows are walked 4 columns at a time with all loads
   // in flight, a segment is consumed in ONE pass of 4 entries per lane.
   static constexpr int SHORT_MAX = 8;    // rows up to this many entries go to the ELL groups
-  static constexpr int SEG_LEN = 256;    // longest row one wavefront takes (4 entries per lane; the kernel also handles up to 1024 at 16 per lane,
-                                         // measured slower than a workgroup per row: 0.650 vs 0.614 s on the C3 solve)
+  static constexpr int SEG_LEN = 256;    // longest row one wavefront takes (4 entries per lane: seg_traverse asserts it; up to 1024 at 16 per
+                                         // lane was measured slower than a workgroup per row: 0.650 vs 0.614 s on the C3 solve)
   static constexpr int BLK_PASS = 12288; // entries a 1024-thread workgroup consumes per pass of a long row (12 per thread)
   // ELL groups
   std::vector<int32_t> grp_off;  // G+1: first ELL column of each group

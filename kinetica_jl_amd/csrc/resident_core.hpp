@@ -102,7 +102,7 @@ struct ResCorrIn {
 struct ResAttempt { bool done, converged, nonfinite, any_negative, deep_negative; int n_iter; double err, err_m, err_p, crate; };
 constexpr double RES_NEG_DEEP = BDF_NEG_DEEP, RES_NEG_MARK = BDF_NEG_MARK;
 
-// Predictor + corrector iterations until decided: the decisions of newton_decide (solver_kernels.hip), taken in sequence.
+// Predictor + corrector iterations until decided: the decisions of newton_decide (step_dev.hpp), taken in sequence.
 // `I` supplies predict_inner / newton_iter_inner (the CPU replay: the backend itself; the device: the phase's own inlined
 // operations, run by all wavefronts).
 template <class I>

@@ -11,6 +11,7 @@
 #include "gj_dev.hpp"
 #include "kernels.hpp"
 #include "segsum_dev.hpp"
+#include "step_dev.hpp"
 
 #include <utility>
 
@@ -442,31 +443,9 @@ int launch_gauss_jordan_batched(int n, double* const* S, double* const* S2, int3
 __global__ __launch_bounds__(256) void gemv_kernel(const double* __restrict__ S, int ld, int m, const double* __restrict__ y,
                                                    double* __restrict__ x, const int* skip) {
   const int sk = skip ? *skip : 0;
-  const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= m) return;
-  const double* a = S + (size_t)row * ld;
-  // four independent partial sums per lane: all loads of a trip are in flight together (the row is read once,
-  // the kernel is one dependent-latency chain per row otherwise); fixed order -> bitwise reproducible
-  double acc0 = 0.0, acc1 = 0.0, acc2 = 0.0, acc3 = 0.0;
-  int j = lane;
-  if (j + 192 < m) {   // first trip issued before the flag is tested: an active launch does not wait for the flag alone
-    const double a0 = a[j], a1 = a[j + 64], a2 = a[j + 128], a3 = a[j + 192];
-    const double y0 = y[j], y1 = y[j + 64], y2 = y[j + 128], y3 = y[j + 192];
-    if (sk) return;
-    acc0 += a0 * y0; acc1 += a1 * y1; acc2 += a2 * y2; acc3 += a3 * y3;
-    j += 256;
-  } else if (sk) return;
-  for (; j + 192 < m; j += 256) {
-    const double a0 = a[j], a1 = a[j + 64], a2 = a[j + 128], a3 = a[j + 192];
-    const double y0 = y[j], y1 = y[j + 64], y2 = y[j + 128], y3 = y[j + 192];
-    acc0 += a0 * y0; acc1 += a1 * y1; acc2 += a2 * y2; acc3 += a3 * y3;
-  }
-  for (; j < m; j += 64) acc0 += a[j] * y[j];
-  double acc = (acc0 + acc1) + (acc2 + acc3);
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) acc += __shfl_down(acc, off, 64);
-  if (lane == 0) x[row] = acc;
+  gemv_row(S + (size_t)row * ld, y, m, sk, x + row);
 }
 
 void launch_gemv(const double* S, int32_t ld, int32_t m, const double* y, double* x, const int* skip, hipStream_t s) {
@@ -478,200 +457,15 @@ void launch_gemv(const double* S, int32_t ld, int32_t m, const double* y, double
 // ------------------------------------------------------------------------------------------
 // BDF vector kernels (algorithm: solver.cpp). D is the backward-difference array [MAXD][N].
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ double block_sum_1024(double v, double* sh) {
-  // fixed-order reduction over a 1024-thread workgroup
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off, 64);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) sh[w] = v;
-  __syncthreads();
-  double t = 0.0;
-  if (threadIdx.x == 0) {
-    for (int i = 0; i < 16; i++) t += sh[i];
-    sh[16] = t;
-  }
-  __syncthreads();
-  return sh[16];
-}
-
-// the same shape for a maximum of non-negative values (NaN entries are ignored: the callers report them separately)
-__device__ __forceinline__ double block_max_1024(double v, double* sh) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v = fmax(v, __shfl_down(v, off, 64));
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) sh[w] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double t = 0.0;
-    for (int i = 0; i < 16; i++) t = fmax(t, sh[i]);
-    sh[16] = t;
-  }
-  __syncthreads();
-  return sh[16];
-}
-
+// (the bodies of these kernels, element by element, and the reductions' hand-over: step_dev.hpp)
 __global__ __launch_bounds__(256) void bdf_predict_kernel(int N, int order, const double* __restrict__ D, BdfCoef cf,
                                                           double atol, double rtol, double* __restrict__ y,
                                                           double* __restrict__ psi, double* __restrict__ d,
                                                           double* __restrict__ scale, BdfCtrl* ctrl) {
   const int i = blockIdx.x * 256 + threadIdx.x;
-  // the predictor opens a corrector attempt: it also clears the attempt's control block (what a
-  // separate one-thread launch used to do)
-  if (i == 0) {
-    ctrl->newton_done = 0; ctrl->converged = 0; ctrl->n_iter = 0; ctrl->nonfinite = 0; ctrl->any_negative = 0; ctrl->ticket = 0;
-    ctrl->dy_norm_old = 0.0; ctrl->dy_norm = 0.0; ctrl->err_norm = 0.0; ctrl->err_m_norm = 0.0; ctrl->err_p_norm = 0.0;
-  }
+  if (i == 0) open_attempt(ctrl, 0);
   if (i >= N) return;
-  double yp = D[i], ps = 0.0;
-  for (int j = 1; j <= order; j++) {
-    const double dj = D[(size_t)j * N + i];
-    yp += dj;
-    ps += dj * cf.gamma[j];
-  }
-  y[i] = yp;
-  psi[i] = ps / cf.alpha[order];
-  d[i] = 0.0;
-  scale[i] = atol + rtol * fabs(yp);
-}
-
-// Reductions over the state are spread over ceil(N / 1024) workgroups of 256 threads (four elements per
-// thread, all loads in flight): each workgroup stores its partial sums, the last one to arrive (ticket in
-// BdfCtrl) adds them in workgroup order - bitwise reproducible - and takes the decision. A single
-// 1024-thread workgroup walking the whole state took 17 us at N = 10k, most of it load latency.
-#ifndef KIN_RED_ELEMS
-#define KIN_RED_ELEMS 1024
-#endif
-constexpr int RED_ELEMS = KIN_RED_ELEMS;   // elements per workgroup
-constexpr int RED_PT = RED_ELEMS / 256;     // per thread
-
-__device__ __forceinline__ double block_sum_256(double v, double* sh) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off, 64);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) sh[w] = v;
-  __syncthreads();
-  return sh[0] + sh[1] + sh[2] + sh[3];
-}
-
-// Hand-over of the per-workgroup partial sums to the workgroup that arrives last, without a cache-flushing fence
-// (`__threadfence()` = buffer_wbl2 + buffer_inv, ~3.5 us on gfx950 - a third of these kernels' duration): the partials
-// are stored write-through past L2 (relaxed agent-scope stores = `sc1`), the storing lane drains them (`s_waitcnt
-// vmcnt(0)`) and then takes its ticket with an agent-scope atomic; the workgroup whose ticket is the last one reads
-// the partials with `sc1` loads (sum_partials) after its atomic has returned. One storing lane per workgroup, 8-byte
-// granules, one workgroup per CU: the form MI355X_MICROARCH.md lists as valid for inter-workgroup hand-offs.
-__device__ __forceinline__ void store_partial(double* p, double v) {
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// true in exactly one workgroup per launch: the one that arrives last, after every partial is visible.
-// Call from all threads; thread 0 must be the one that stored the partials (store_partial).
-__device__ __forceinline__ bool last_block_arrives(BdfCtrl* ctrl, int* flag) {
-  if (threadIdx.x == 0) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const int t = __hip_atomic_fetch_add(&ctrl->ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    *flag = (t == (int)gridDim.x - 1);
-    if (*flag) __hip_atomic_store(&ctrl->ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // for the next launch
-  }
-  __syncthreads();
-  return *flag != 0;
-}
-
-__device__ __forceinline__ double sum_partials(const double* part, int n) {
-  double t = 0.0;
-  for (int g = 0; g < n; g++) t += __hip_atomic_load(part + g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // past this CU's L1
-  return t;
-}
-
-// A workgroup's five partial sums sit in ONE 128-byte line of their own (RED_SLOT doubles apart): write-through stores of 60
-// workgroups into shared lines serialise at the memory side - 325 stores took ~45 us of a 55 us launch with the sums of all
-// workgroups interleaved (part[q * G + g]), and ~7 of the 10.7 us of the 10-workgroup launch before it.
-constexpr int RED_SLOT = 16;
-// The five sums of a corrector launch from the workgroups' partial sums: by the first wavefront of the workgroup that arrived
-// last, one partial per lane and round (all loads in flight together), fixed butterfly order - bitwise reproducible. (A
-// single thread adding them one `sc1` load after the other was fine for 10 workgroups and is ~0.2-1 us per partial: the
-// fused launch below has 60 workgroups at 10k species.)
-__device__ __forceinline__ void newton_totals(const double* part, int G, double (&tot)[5]) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int q = 0; q < 5; q++) {
-    double v = 0.0;
-    for (int g = lane; g < G; g += 64) v += __hip_atomic_load(part + g * RED_SLOT + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    tot[q] = wave_sum(v);
-  }
-}
-
-// The decision of a corrector iteration, taken by ONE thread of the workgroup that arrived last (all partial sums are
-// visible to it): norm of the update, contraction rate, converged / diverged / go on, and - when converged - the step's
-// error-test norms; publishes the control block to the host when the attempt is decided (or `publish_always`).
-struct NewtonDecide {
-  int N, iter, maxit;
-  double tol, rate_max, crate0, tol_first, dy_first_max;
-  int crate_from_ctrl, ban_negatives;
-  BdfCtrl* ctrl; const double* tot;   // tot[5]: the launch's sums (update, error test of order / -1 / +1, negative entries)
-  BdfCtrl* host_ctrl; unsigned long long* host_seq; unsigned long long seq; int publish_always;
-};
-__device__ __forceinline__ void newton_decide(const NewtonDecide& a) {
-  const int N = a.N, iter = a.iter, maxit = a.maxit, publish_always = a.publish_always;
-  const double tol = a.tol, rate_max = a.rate_max, tol_first = a.tol_first, dy_first_max = a.dy_first_max;
-  BdfCtrl* ctrl = a.ctrl; BdfCtrl* host_ctrl = a.host_ctrl;
-  const double crate0 = (a.crate_from_ctrl && iter == 0) ? ctrl->crate : a.crate0;
-  unsigned long long* host_seq = a.host_seq; const unsigned long long seq = a.seq;
-  {
-    const double tot = a.tot[0];
-    const double old = ctrl->dy_norm_old;
-    const double dy_norm = sqrt(tot / (double)N);
-    const bool nonfinite = !isfinite(tot);
-    const bool have_rate = iter > 0;
-    const double rate = have_rate ? dy_norm / old : 0.0;
-    // CVODE's carried convergence rate: every factorisation keeps the contraction it has shown (crate <- max(0.3 crate,
-    // rate) after each iteration with a rate; 1 = unknown, set by the host when the factorisation is made). It lets the
-    // FIRST iteration of a step be judged like the later ones instead of always being followed by a second one.
-    double crate = iter == 0 ? crate0 : ctrl->crate;
-    if (have_rate && !nonfinite) crate = fmax(0.3 * crate, rate);
-    ctrl->crate = crate;
-    bool diverged = nonfinite;
-    // rate_max < 1 (a reused factorisation): a contraction slower than that means the matrix no longer matches the
-    // Jacobian well enough for the error of the iteration to be judged from two or three corrections
-    if (!diverged && have_rate) {
-      double rp = rate;                                     // rate^(maxit - iter), 1 <= maxit - iter <= 3
-      for (int e = 1; e < maxit - iter; e++) rp *= rate;
-      if (rate >= rate_max || rp / (1.0 - rate) * dy_norm > tol) diverged = true;
-    }
-    ctrl->n_iter = iter + 1;
-    ctrl->dy_norm = dy_norm;
-    bool done = true, converged = false;
-    if (diverged) { ctrl->nonfinite = nonfinite; }
-    else if (dy_norm == 0.0 || (have_rate && rate / (1.0 - rate) * dy_norm < tol) ||
-             (!have_rate && (dy_norm < tol || (crate0 < 1.0 && dy_norm <= dy_first_max && crate0 / (1.0 - crate0) * dy_norm < tol_first)))) {
-      converged = true;                             // (first-iteration acceptance as in ode15s / CVODE)
-    }
-    else {
-      ctrl->dy_norm_old = dy_norm;
-      done = iter == maxit - 1;
-    }
-    if (converged) {
-      const double te = a.tot[1];
-      ctrl->err_norm = sqrt(te / (double)N);
-      ctrl->err_m_norm = sqrt(a.tot[2] / (double)N);
-      ctrl->err_p_norm = sqrt(a.tot[3] / (double)N);
-      ctrl->any_negative = a.tot[4] > 0.0 ? (a.tot[4] >= BDF_NEG_MARK ? 3 : 1) : 0;   // bit 1: a species below -BDF_NEG_DEEP weights
-      if (!isfinite(te)) ctrl->nonfinite = 1;
-    }
-    ctrl->converged = converged ? 1 : 0;
-    ctrl->newton_done = done ? 1 : 0;
-    // the verdict the host will reach from the same numbers (solver.cpp, step()): an accepted step with nothing that makes
-    // the next one more than a continuation (every allowed iteration used = the host may drop the factorisation)
-    ctrl->spec_go = (done && converged && !ctrl->nonfinite && !ctrl->lu_bad && !(a.ban_negatives && ctrl->any_negative) && !(ctrl->any_negative & 2) &&
-                     !(ctrl->err_norm > 1.0) && iter + 1 < maxit) ? 1 : 0;
-    if ((done || publish_always) && host_ctrl) {
-      *host_ctrl = *ctrl;
-      __threadfence_system();
-      *(volatile unsigned long long*)host_seq = seq;
-    }
-  }
+  predict_elem(D, N, i, order, cf.gamma, PredictOut{y, psi, d, scale, cf.alpha[order], atol, rtol});
 }
 
 // One Newton update: y += dy, d += dy, ||dy||, convergence decision - and, folded in, the step's error estimate: every
@@ -690,70 +484,13 @@ __global__ __launch_bounds__(256) void bdf_newton_kernel(int N, int iter, int ma
                                                          BdfCtrl* ctrl, double* __restrict__ part, BdfCtrl* host_ctrl,
                                                          unsigned long long* host_seq, unsigned long long seq, int publish_always,
                                                          int crate_from_ctrl, int ban_negatives) {
-  __shared__ double sh[20];
-  __shared__ int last;
   // the "already decided" flag travels with the first round of loads instead of in front of it (a dependent load of its own is
   // ~1.5 us of every launch, segsum_dev.hpp): a launch behind the decision ends after ONE round of loads
   const int decided = __hip_atomic_load(&ctrl->newton_done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  const int G = gridDim.x;
-  // A non-finite update makes the sum of squares non-finite: one reduction carries both the norm and the flag.
-  double s = 0.0, se = 0.0, sm = 0.0, sp = 0.0, neg = 0.0;
-  const int i0 = blockIdx.x * RED_ELEMS + threadIdx.x;
-  int32_t xl[RED_PT]; double dy[RED_PT], sc[RED_PT], yy[RED_PT], dd[RED_PT], dm[RED_PT], dp[RED_PT];
-#pragma unroll
-  for (int x = 0; x < RED_PT; x++) {
-    const int i = i0 + 256 * x;
-    const bool ok = i < N;
-    xl[x] = ok ? xloc[i] : -1; sc[x] = ok ? scale[i] : 1.0;
-    yy[x] = ok ? y[i] : 0.0; dd[x] = ok ? d[i] : 0.0;
-    dm[x] = (ok && order > 1) ? D[(size_t)order * N + i] : 0.0;
-    dp[x] = (ok && order < 5) ? D[(size_t)(order + 1) * N + i] : 0.0;
-  }
-  if (decided) return;
-#pragma unroll
-  for (int x = 0; x < RED_PT; x++) dy[x] = xl[x] >= 0 ? upd * W[xl[x]] : 0.0;   // upd = 2 / (1 + c / c_fact): reused factorisation
-#pragma unroll
-  for (int x = 0; x < RED_PT; x++) {
-    const double q = dy[x] / sc[x];
-    s += q * q;
-    yy[x] += dy[x]; dd[x] += dy[x];
-    if (i0 + 256 * x >= N) continue;
-    // error test of the state after this iteration (a non-finite state makes the sum non-finite)
-    const double sce = atol + rtol * fabs(yy[x]);
-    if (yy[x] < 0.0) neg = fmax(neg, yy[x] < -BDF_NEG_DEEP * sce ? BDF_NEG_MARK : 1.0);
-    const double e = cf.error_const[order] * dd[x] / sce;
-    se += e * e + (isfinite(yy[x]) ? 0.0 : INFINITY);
-    if (order > 1) { const double em = cf.error_const[order - 1] * (dm[x] + dd[x]) / sce; sm += em * em; }
-    if (order < 5) { const double ep = cf.error_const[order + 1] * (dd[x] - dp[x]) / sce; sp += ep * ep; }
-  }
-  // five sums, one pair of barriers
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    s += __shfl_down(s, off, 64); se += __shfl_down(se, off, 64); sm += __shfl_down(sm, off, 64);
-    sp += __shfl_down(sp, off, 64); neg += __shfl_down(neg, off, 64);
-  }
-  {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) { sh[5 * w] = s; sh[5 * w + 1] = se; sh[5 * w + 2] = sm; sh[5 * w + 3] = sp; sh[5 * w + 4] = neg; }
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int q = 0; q < 5; q++) store_partial(part + blockIdx.x * RED_SLOT + q, (sh[q] + sh[5 + q]) + (sh[10 + q] + sh[15 + q]));
-  }
-  const bool is_last = last_block_arrives(ctrl, &last);
-  // the state update is off the critical path of the decision: its stores go out while the ticket travels
-#pragma unroll
-  for (int x = 0; x < RED_PT; x++) {
-    const int i = i0 + 256 * x;
-    if (i < N) { y[i] = yy[x]; d[i] = dd[x]; }
-  }
-  if (!is_last || threadIdx.x >= 64) return;
-  double tot[5];
-  newton_totals(part, G, tot);
-  if (threadIdx.x == 0)
-    newton_decide(NewtonDecide{N, iter, maxit, tol, rate_max, crate0, tol_first, dy_first_max, crate_from_ctrl, ban_negatives, ctrl, tot,
-                               host_ctrl, host_seq, seq, publish_always});
+  const NewtonOps f{N, order, scale, y, d, D, atol, rtol, cf.error_const[order], cf.error_const[order - 1], cf.error_const[order + 1]};
+  newton_rows(f, xloc, W, upd, decided, part,
+              NewtonDecide{N, iter, maxit, tol, rate_max, crate0, tol_first, dy_first_max, crate_from_ctrl, ban_negatives, ctrl, nullptr,
+                           host_ctrl, host_seq, seq, publish_always});
 }
 
 // ------------------------------------------------------------------------------------------
@@ -764,127 +501,26 @@ __global__ __launch_bounds__(256) void bdf_newton_kernel(int N, int iter, int ma
 // as in bdf_newton_kernel. One launch of ~11 us and its dependency gap less per corrector iteration (C3: 5.4 + 10.7 us
 // -> see DESIGN 3.3). The plan's `aux` entries hold the species index of each row (lu.cpp: build_C).
 // ------------------------------------------------------------------------------------------
-struct NewtonElem { double sc, yy, dd, dm, dp; };
-struct NewtonSums { double s = 0.0, se = 0.0, sm = 0.0, sp = 0.0, neg = 0.0; };
-
-__device__ __forceinline__ NewtonElem newton_pre(const NewtonFuse& f, int32_t sp) {
-  NewtonElem e{1.0, 0.0, 0.0, 0.0, 0.0};
-  if (sp < 0) return e;
-  e.sc = f.scale[sp]; e.yy = f.y[sp]; e.dd = f.d[sp];
-  if (f.order > 1) e.dm = f.D[(size_t)f.order * f.N + sp];
-  if (f.order < 5) e.dp = f.D[(size_t)(f.order + 1) * f.N + sp];
-  return e;
-}
-// the update of species sp with solution component x (the arithmetic of bdf_newton_kernel, element by element)
-__device__ __forceinline__ void newton_apply(const NewtonFuse& f, int32_t sp, double x, NewtonElem e, NewtonSums& t) {
-  const double dy = f.upd * x;
-  const double q = dy / e.sc;
-  t.s += q * q;
-  e.yy += dy; e.dd += dy;
-  const double sce = f.atol + f.rtol * fabs(e.yy);
-  if (e.yy < 0.0) t.neg = fmax(t.neg, e.yy < -BDF_NEG_DEEP * sce ? BDF_NEG_MARK : 1.0);
-  const double er = f.ec * e.dd / sce;
-  t.se += er * er + (isfinite(e.yy) ? 0.0 : INFINITY);
-  if (f.order > 1) { const double em = f.ec_m * (e.dm + e.dd) / sce; t.sm += em * em; }
-  if (f.order < 5) { const double ep = f.ec_p * (e.dd - e.dp) / sce; t.sp += ep * ep; }
-  f.y[sp] = e.yy; f.d[sp] = e.dd;
-}
-
 template <int SEG_WG>
 __global__ __launch_bounds__(SEG_WG) void stagec_newton_kernel(SegPlanView p, double* W, NewtonFuse f) {
-  constexpr int OP = SEG_PROD_SET;
-  constexpr int SEG_WAVES = SEG_WG / 64, BLK_PER_THREAD = SegPlanHost::BLK_PASS / 1024;
-  __shared__ double sh[5 * SEG_WAVES];
-  __shared__ double shb[SEG_WAVES];
-  __shared__ int last;
-  const int skip = *f.skip;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const bool impl = p.val_base >= 0;
-  const SegExtra ex;
   NewtonSums t;
-  if (SEG_WG == 1024 && (int)blockIdx.x < p.B) {       // one long row for the whole workgroup
-    const int r = blockIdx.x;
-    const int32_t e0 = p.blk_beg[r], e1 = p.blk_end[r];
-    const int32_t bdst = p.blk_dst[r];
-    const int32_t bsp = p.blk_aux[r];
-    if (skip) return;      // (whole grid: the flag is uniform and only this launch's LAST workgroup can raise it)
-    const NewtonElem pre = newton_pre(f, threadIdx.x == 0 ? bsp : -1);
-    double acc = 0.0;
-    for (int32_t base = e0; base < e1; base += SegPlanHost::BLK_PASS)
-      acc += seg_gather<OP, BLK_PER_THREAD, false>(p, W, ex, impl, [&](int x) {
-        const int32_t e = base + (int32_t)threadIdx.x + 1024 * x;
-        return e < e1 ? e : -1;
+  // the update of species sp with solution component x
+  const auto update = [&](int32_t sp, double x, NewtonElem e) { newton_apply(f, f.upd * x, e, t); newton_store(f, sp, e); };
+  const bool active = seg_traverse<SEG_PROD_SET, SEG_WG>(
+      p, W, SegExtra{}, f.skip, [&](int32_t dst, int32_t sp) { return newton_pre(f, dst >= 0 ? sp : -1); },
+      [&](int32_t dst, int32_t sp, double acc, const NewtonElem& e) { W[dst] = acc; update(sp, acc, e); },
+      [&](int task) {                                   // the dense block's species: x2 is in place since the GEMV
+        const int j = task * 64 + (threadIdx.x & 63);
+        if (j < f.m) {
+          const int32_t sp = f.x2_species[j];
+          update(sp, W[f.off_x + j], newton_pre(f, sp));
+        }
       });
-    acc = wave_sum(acc);
-    if (lane == 0) shb[wv] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      double tot = 0.0;
-#pragma unroll
-      for (int w = 0; w < SEG_WAVES; w++) tot += shb[w];     // fixed order
-      W[bdst] = tot;
-      newton_apply(f, bsp, tot, pre, t);
-    }
-  } else {
-    const int task = ((int)blockIdx.x - p.B) * SEG_WAVES + wv;
-    if (task < p.G) {                                   // an ELL group: one short row per lane
-      const int32_t dst = p.grp_dst[task * 64 + lane];
-      const int32_t sp = dst >= 0 ? p.grp_aux[task * 64 + lane] : -1;
-      const int32_t c0 = p.grp_off[task], c1 = p.grp_off[task + 1];
-      if (skip) return;
-      const NewtonElem pre = newton_pre(f, sp);
-      double acc = 0.0;
-      for (int32_t col = c0; col < c1; col += 8)
-        acc += seg_gather<OP, 8, true>(p, W, ex, impl, [&](int x) { return col + x < c1 ? (col + x) * 64 + lane : -1; });
-      if (dst >= 0) { W[dst] = acc; newton_apply(f, sp, acc, pre, t); }
-    } else if (task < p.G + p.S) {                      // one medium row per wavefront
-      const int sidx = task - p.G;
-      const int32_t e0 = p.seg_beg[sidx], e1 = p.seg_end[sidx];
-      const int32_t sdst = p.seg_dst[sidx];
-      const int32_t ssp = p.seg_aux[sidx];
-      if (skip) return;
-      const NewtonElem pre = newton_pre(f, lane == 0 ? ssp : -1);
-      double acc;
-      if (e1 - e0 <= 256)
-        acc = seg_gather<OP, 4, false>(p, W, ex, impl, [&](int x) { const int32_t e = e0 + lane + 64 * x; return e < e1 ? e : -1; });
-      else
-        acc = seg_gather<OP, 16, false>(p, W, ex, impl, [&](int x) { const int32_t e = e0 + lane + 64 * x; return e < e1 ? e : -1; });
-      acc = wave_sum(acc);
-      if (lane == 0) { W[sdst] = acc; newton_apply(f, ssp, acc, pre, t); }
-    } else {                                            // the dense block's species: x2 is in place since the GEMV
-      if (skip) return;
-      const int j = (task - p.G - p.S) * 64 + lane;
-      if (j < f.m) {
-        const int32_t sp = f.x2_species[j];
-        const NewtonElem pre = newton_pre(f, sp);
-        newton_apply(f, sp, W[f.off_x + j], pre, t);
-      }
-    }
-  }
-  // five sums over the workgroup, one pair of barriers
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    t.s += __shfl_down(t.s, off, 64); t.se += __shfl_down(t.se, off, 64); t.sm += __shfl_down(t.sm, off, 64);
-    t.sp += __shfl_down(t.sp, off, 64); t.neg += __shfl_down(t.neg, off, 64);
-  }
-  if (lane == 0) { sh[5 * wv] = t.s; sh[5 * wv + 1] = t.se; sh[5 * wv + 2] = t.sm; sh[5 * wv + 3] = t.sp; sh[5 * wv + 4] = t.neg; }
-  __syncthreads();
-  const int G = gridDim.x;
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int q = 0; q < 5; q++) {
-      double tot = 0.0;
-#pragma unroll
-      for (int w = 0; w < SEG_WAVES; w++) tot += sh[5 * w + q];     // fixed order
-      store_partial(f.part + blockIdx.x * RED_SLOT + q, tot);
-    }
-  }
-  if (!last_block_arrives(f.ctrl, &last) || threadIdx.x >= 64) return;
-  double tot[5];
-  newton_totals(f.part, G, tot);
-  if (threadIdx.x == 0)
-    newton_decide(NewtonDecide{f.N, f.iter, f.maxit, f.tol, f.rate_max, f.crate0, f.tol_first, f.dy_first_max, f.crate_from_ctrl,
-                               f.ban_negatives, f.ctrl, tot, f.host_ctrl, f.host_seq, f.seq, f.publish_always});
+  if (!active) return;      // (whole grid: the flag is uniform and only this launch's LAST workgroup can raise it)
+  newton_finish<SEG_WG / 64, false>(t, f.part,
+                                    NewtonDecide{f.N, f.iter, f.maxit, f.tol, f.rate_max, f.crate0, f.tol_first, f.dy_first_max, f.crate_from_ctrl,
+                                                 f.ban_negatives, f.ctrl, nullptr, f.host_ctrl, f.host_seq, f.seq, f.publish_always},
+                                    [] {});
 }
 
 static bool stagec_big_wg(const SegPlanView& p) {
@@ -906,14 +542,7 @@ __global__ __launch_bounds__(256) void bdf_accept_kernel(int N, int order, doubl
                                                          double* __restrict__ copy_out) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= N) return;
-  const double di = d[i];
-  D[(size_t)(order + 2) * N + i] = di - D[(size_t)(order + 1) * N + i];
-  D[(size_t)(order + 1) * N + i] = di;
-  double carry = di;
-  for (int j = order; j >= 0; j--) {
-    carry += D[(size_t)j * N + i];
-    D[(size_t)j * N + i] = carry;
-  }
+  const double carry = accept_elem(D, N, i, order, d[i]);
   if (copy_out) copy_out[i] = carry;     // the new state D[0]
 }
 
@@ -933,16 +562,13 @@ __global__ __launch_bounds__(256) void bdf_accept_predict_kernel(int N, int ao, 
     if (i == 0) ctrl->newton_done = 1;
     return;
   }
-  if (i == 0) {
-    ctrl->newton_done = 0; ctrl->converged = 0; ctrl->n_iter = 0; ctrl->nonfinite = 0; ctrl->any_negative = 0; ctrl->ticket = 0;
-    ctrl->dy_norm_old = 0.0; ctrl->dy_norm = 0.0; ctrl->err_norm = 0.0; ctrl->err_m_norm = 0.0; ctrl->err_p_norm = 0.0;
-  }
+  if (i == 0) open_attempt(ctrl, 0);
   if (i >= N) return;
   double col[BDF_D_ROWS];
   const double di = d[i];
 #pragma unroll
   for (int j = 0; j < BDF_D_ROWS; j++) col[j] = j <= ao + 1 ? D[(size_t)j * N + i] : 0.0;
-  // accept (bdf_accept_kernel)
+  // accept (accept_elem, on the column in registers: every row index is a compile-time constant)
 #pragma unroll
   for (int j = BDF_D_ROWS - 1; j >= 1; j--) {
     if (j == ao + 2) col[j] = di - col[j - 1];
@@ -957,16 +583,13 @@ __global__ __launch_bounds__(256) void bdf_accept_predict_kernel(int N, int ao, 
 #pragma unroll
   for (int j = 0; j < BDF_D_ROWS; j++) if (j <= ao + 2) D[(size_t)j * N + i] = col[j];
   if (copy_out) copy_out[i] = col[0];
-  // predict (bdf_predict_kernel), order <= ao + 1
+  // predict (predict_elem, from the same registers), order <= ao + 1
   double yp = col[0], ps = 0.0;
 #pragma unroll
   for (int j = 1; j < BDF_D_ROWS; j++) {
     if (j <= order) { yp += col[j]; ps += col[j] * cf.gamma[j]; }
   }
-  y[i] = yp;
-  psi[i] = ps / cf.alpha[order];
-  d[i] = 0.0;
-  scale[i] = atol + rtol * fabs(yp);
+  predict_store(PredictOut{y, psi, d, scale, cf.alpha[order], atol, rtol}, i, yp, ps);
 }
 
 // D[0..order] <- (R U)^T D[0..order]   (step-size change by `factor`, matrix built on the host)
@@ -986,19 +609,12 @@ __global__ __launch_bounds__(256) void bdf_change_D_kernel(int N, int order, Bdf
 __global__ __launch_bounds__(256) void bdf_init_D_kernel(int N, int nrows, const double* __restrict__ y0, const double* __restrict__ f0,
                                                          double h, double* __restrict__ D) {
   const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= N) return;
-  D[i] = y0[i];
-  D[(size_t)N + i] = f0[i] * h;
-  for (int j = 2; j < nrows; j++) D[(size_t)j * N + i] = 0.0;
+  if (i < N) init_D_elem(D, N, i, nrows, y0[i], f0[i] * h);
 }
 
-// dense output: out = D[0] + sum_j p[j] D[j]
 __global__ __launch_bounds__(256) void bdf_interp_kernel(int N, int order, const double* __restrict__ D, BdfVec p, double* __restrict__ out) {
   const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= N) return;
-  double v = D[i];
-  for (int j = 1; j <= order; j++) v += p.v[j] * D[(size_t)j * N + i];
-  out[i] = v;
+  if (i < N) out[i] = interp_elem(D, N, i, order, p.v);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1063,31 +679,10 @@ __global__ __launch_bounds__(256) void axpy_out_kernel(int N, const double* __re
   if (i < N) out[i] = a[i] + s * b[i];
 }
 
-// norms for the initial step size: rms(y0/sc), rms(f0/sc), rms((f1-f0)/sc), max |f0| / (0.1 |y0| + sc), sc = atol + rtol |y0|;
-// f1 may be null. Also reports non-finite f.
+// norms for the initial step size (norms_body)
 __global__ __launch_bounds__(1024) void bdf_norms_kernel(int N, const double* __restrict__ y0, const double* __restrict__ f0,
                                                          const double* __restrict__ f1, double atol, double rtol, BdfCtrl* ctrl) {
-  __shared__ double sh[17];
-  double s0 = 0.0, s1 = 0.0, s2 = 0.0, vm = 0.0;
-  int bad = 0;
-  for (int i = threadIdx.x; i < N; i += 1024) {
-    const double sc = atol + rtol * fabs(y0[i]);
-    const double a = y0[i] / sc, b = f0[i] / sc;
-    s0 += a * a; s1 += b * b;
-    vm = fmax(vm, fabs(f0[i]) / (0.1 * fabs(y0[i]) + sc));
-    if (!isfinite(f0[i])) bad = 1;
-    if (f1) { const double c = (f1[i] - f0[i]) / sc; s2 += c * c; if (!isfinite(f1[i])) bad = 1; }
-  }
-  const double t0 = block_sum_1024(s0, sh), t1 = block_sum_1024(s1, sh), t2 = block_sum_1024(s2, sh);
-  const double tb = block_sum_1024((double)bad, sh);
-  const double tm = block_max_1024(vm, sh);
-  if (threadIdx.x == 0) {
-    ctrl->scratch[0] = sqrt(t0 / (double)N);
-    ctrl->scratch[1] = sqrt(t1 / (double)N);
-    ctrl->scratch[2] = sqrt(t2 / (double)N);
-    ctrl->scratch[3] = tm;
-    ctrl->nonfinite = tb > 0.0;
-  }
+  norms_body(N, y0, f0, f1, atol, rtol, ctrl);
 }
 
 // per-species running maximum over saved states (identify_next_seeds' reduction)
@@ -1120,8 +715,7 @@ __global__ __launch_bounds__(256) void rates_skip_kernel(int R, const double* __
   const int32_t a = x0[r], b = x1[r];
   const double kr = k[r];
   if (sk) return;            // tested when the operand indices are back: a skipped launch never issues the gathers
-  const double ub = b >= 0 ? u[b] : 1.0;
-  rate[r] = kr * u[a] * ub;
+  rate[r] = mass_action_rate(kr, u, a, b);
 }
 
 // the same with the rate constants formed from a temperature and stored for the readers behind this launch (kernels.hpp: ArrheniusAt)
@@ -1136,8 +730,7 @@ __global__ __launch_bounds__(256) void rates_skip_T_kernel(int R, ArrheniusAt at
   const double kr = arrhenius_one(at.Ea[r], at.A[r], 8.314462618 * at.T, at.has_kmax, at.k_max, at.t_mult);
   k[r] = kr;
   if (sk) return;
-  const double ub = b >= 0 ? u[b] : 1.0;
-  rate[r] = kr * u[a] * ub;
+  rate[r] = mass_action_rate(kr, u, a, b);
 }
 
 #define GRID1(n) dim3((unsigned)ceil_div((n), 256)), dim3(256)

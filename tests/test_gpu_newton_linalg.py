@@ -1,5 +1,5 @@
-"""GPU tests of the host-driven Newton-matrix linear algebra (kinetica_jl_amd/csrc/lu.cpp, solver_kernels.hip: every solve above the
-resident kernel's size, the thread and lockstep ensembles) through kin_newton_probe: the scatter of I - c J with the identity on
+"""GPU tests of the host-driven Newton-matrix linear algebra (kinetica_jl_amd/csrc/lu.cpp, solver_kernels.hip, the gather
+traversal seg_traverse of segsum_dev.hpp and gemv_row of step_dev.hpp: every solve above the resident kernel's size, the thread and lockstep ensembles) through kin_newton_probe: the scatter of I - c J with the identity on
 the dense block's padding rows, the sparse elimination rounds and their gather plans, the monomial kernel and the LZ / NVU
 products, the blocked Gauss-Jordan inverse on the FP64 matrix cores (single-matrix and batched chains, the look-ahead workgroup,
 the vanished-pivot flag), the one-wavefront-per-row GEMV and the three solve forms. Every member of every case is compared with
@@ -23,12 +23,12 @@ Mutation check (value-only changes to the product kernels on a scratch build, on
     every vanished_pivot_in_the_dense_block, batched_inverse_* K = 1 / 16 / 17, pivot_inside_a_full_batched_chain, both slot
     reuse tests, newton_solve_is_the_probe, synthetic 1000. Before: the first failure was a trajectory comparison
     (test_synchronising_hand_over_gives_the_same_trajectory).
-  2 the GEMV's final add drops acc3: 17 fail - dense_block_sweep m = 193 .. 1025, vanished_pivot_in_the_dense_block q = 200, both
+  2 the GEMV's (now gemv_row's) final add drops acc3: 17 fail - dense_block_sweep m = 193 .. 1025, vanished_pivot_in_the_dense_block q = 200, both
     slot reuse tests, newton_solve_is_the_probe, synthetic 1000. Before: test_newton_matrix_solve_against_sparse_direct (m = 501).
   3 gj_update_batched_kernel reads B.pinv[0]: 15 fail - every batched case with more than one member (vanished pivots, the pair,
     m = 0 / ns = 0, batched_inverse_* K = 16 / 17, pivot_inside_a_full_batched_chain, slot reuse, synthetic 1000); K = 1 and all
     single-matrix cases pass. Before: test_lockstep_ensemble_of_a_large_network, whose chains depend on thread timing.
-  4 segsum_kernel skips the second pass of a whole-workgroup row: 3 fail - gather_row_lengths L = 12289 in the three forms
+  4 segsum_kernel (now seg_traverse, which it wraps) skips the second pass of a whole-workgroup row: 3 fail - gather_row_lengths L = 12289 in the three forms
     (L = 12288 passes). Before: no failure in the 68 tests that ran before a time limit ended that run; not determined further.
   5 lu_assemble_kernel writes the padding identity one row off: 62 fail - everything with padding rows (m % 64 != 0);
     dense_block_sweep m = 64, 128, 192, 256 and vanished_pivot q = 64 pass. Before: the same trajectory comparison as 1."""

@@ -1,6 +1,8 @@
 """GPU tests of the vector kernels between the phases of a step and of the corrector's decision (solver_kernels.hip:
-bdf_init_D / predict / accept / accept_predict / change_D / interp / norms / newton kernels, stagec_newton_kernel, newton_decide,
-rk_combine / rk_error; ensemble_kernels.inc: e_vec / e_accept / e_change_D / e_init_D / e_norms / e_predict / e_newton), each
+bdf_init_D / predict / accept / accept_predict / change_D / interp / norms / newton kernels, stagec_newton_kernel, rk_combine /
+rk_error; ensemble_kernels.inc: e_vec / e_accept / e_change_D / e_init_D / e_norms / e_predict / e_newton; and the bodies both
+sets of kernels call, step_dev.hpp: open_attempt, predict_elem, accept_elem, init_D_elem, interp_elem, norms_body, newton_pre /
+newton_apply / newton_rows / newton_finish, newton_decide), each
 run ONCE through kin_step_probe on constructed state and compared with the extended-precision references of
 tests/step_cases.py - never with another device path. Everything the probe returns is compared: what an operation writes within
 the bound derived next to its reference, everything else (the other buffers of the block, the rows of D above those the
@@ -8,15 +10,18 @@ operation may touch - filled with a sentinel -, the other fields of the control 
 bit for bit. Flags and counters must be equal; every decision case asserts the branch of the decision it reached, every fused
 case the task kinds of its stage-C plan (from the probe's `info`).
 
-Not reached: a one-wavefront stage-C row of more than 256 entries - build_seg_plan gives every row above SegPlanHost::SEG_LEN =
-256 entries a whole workgroup, so that branch of stagec_newton_kernel (16 entries per lane) is dead with the plans the analysis
-builds; no network can reach it. The long-row path that test_corrector_update_fused_into_the_solve_and_separate mentions at
+No plan has a one-wavefront row of more than 256 entries - build_seg_plan gives every row above SegPlanHost::SEG_LEN = 256
+entries a whole workgroup, and seg_traverse (segsum_dev.hpp), which stagec_newton_kernel runs its rows through, asserts that bound
+at compile time next to its one round of four entries per lane (the 16-entries-per-lane branch the kernels once carried for
+longer rows was unreachable and is gone). The long-row path that test_corrector_update_fused_into_the_solve_and_separate mentions at
 10 000 species is not reached there with the present analysis (stage C of synthetic_crn(10000, 50000): 54 ELL groups, 5 615
 one-wavefront rows, longest 173, no whole-workgroup row). A sparse species gets a stage-C row above 256 entries only where the
 elimination admits degrees above 256, i.e. from 4 000 species on (lu_options_for: max_degree 400): star_net below, 4 000
 species, is the smallest such network of this suite (11 whole-workgroup rows, the 1024-thread build of the kernel).
 A diverged attempt's y and d are not compared: the update is applied unconditionally and the next predictor rebuilds both
 (solver_kernels.hip, above bdf_newton_kernel), so that state is never read.
+Paths 0, 1 and 2 share the corrector's arithmetic since the bodies moved into step_dev.hpp; each path is still compared with the
+references only.
 
 Measured on one MI355X, largest error / bound per case group (printed at the end of the module, pytest -s); the file takes 7 s
 (321 tests, the reports of the module's own clock and of pytest agree):
@@ -29,11 +34,17 @@ Mutation check (one change at a time on a scratch build, selected through KIN_LI
 file fail, and what test_gpu_solve.py + test_gpu_ensemble.py (23 tests) - the suite's view of these kernels before - did.
   1 bdf_newton_kernel reads D[order - 1] for the order - 1 sum: 79 fail - corrector_sums at orders 3 and 5 on both paths (52),
     every converged corrector_decision case (26), chained_iterations. Before: all 23 passed.
+    With the one body (newton_pre reads D[order - 1]): 164 fail - corrector_sums at orders 3 and 5 on paths 0 and 2 (52 + 52),
+    corrector_decision on both (26 + 22), chained_iterations (2), corrector_update_inside_the_solve (path 1, all 7),
+    ensemble_entry_lists (3).
   2 error_const[order] in the order + 1 sum: 66 fail - corrector_sums at orders 1 and 3 (39), corrector_decision (26),
     chained_iterations. Before: 1 failed (test_c2_synthetic_matches_oracle, a trajectory comparison).
+    With the one body (newton_apply uses ec for ec_p): 138 fail - corrector_sums at orders 1 and 3 on paths 0 and 2 (39 + 39),
+    corrector_decision (26 + 22), chained_iterations (2), corrector_update_inside_the_solve (7), ensemble_entry_lists (3).
   3 newton_totals without the += 64 rounds: 10 fail - corrector_sums at n = 65537 (65 workgroups), all five cases on both paths;
     n = 65536 passes. Before: test_corrector_update_fused_into_the_solve_and_separate (2 cases).
   4 e_newton_kernel indexes reps[blockIdx.y]: 2 fail - ensemble_entry_lists K = 3 and 17 (K = 1 passes). Before: all 23 passed.
+    The same two with the kernel as a wrapper of newton_rows.
   5 stagec_newton_kernel skips newton_apply in the dense block's last, partly filled wavefront: 5 fail -
     corrector_update_inside_the_solve dense 1, 63, 65, 129 and synthetic 300 (m = 108); dense 64 and star 4000 (m = 320) pass.
     Before: 6 failed (trajectory and step-count comparisons).

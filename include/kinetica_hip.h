@@ -466,6 +466,48 @@ int kin_ensemble_dot(kin_network* h, const double* w /* [N] */, double* out /* [
 int kin_ensemble_flux(kin_network* h, const double* w /* [K*n_rows] or NULL */, const double* k, int64_t n_k_rows,
                       const int64_t* k_row /* [K*n_rows] */, const double* T_rows /* [K*n_rows] */, double* flux /* [K][R] */);
 
+/* ---- directed relation graph (Lu & Law) of the network over batched states: which species matter for which ------------- */
+/* Reaction rates are the flux pass's, q_r = k_r u[x0_r] (x1_r >= 0 ? u[x1_r] : 1). RECORDS group the reactions: with
+ * pairing != 0 a record is a reaction kf together with its exact reverse kr as the network compiler pairs them for the
+ * batched sweep (reactions in order; a reaction whose operands and products are another, earlier, still unpaired one's
+ * products and operands joins the latest such reaction; reactions with a species on both sides stay alone) and progresses
+ * at w = q_kf - q_kr; with pairing == 0 every reaction is a record, w = q_r. nu_A is the net stoichiometric coefficient of
+ * species A in the record's forward reaction, S the species on either side of it (a collider with zero net coefficient
+ * belongs to S). For a state b
+ *   den_A(b)  = sum over records with nu_A != 0                    of |nu_A| |w(b)|
+ *   num_AB(b) = sum over records with nu_A != 0, B in S, B != A    of |nu_A| |w(b)|
+ *   r_AB(b)   = num_AB / den_A  (exactly 0.0 where den_A == 0: never NaN or Inf for finite inputs)
+ *   coef_AB   = max over the B states of r_AB(b)
+ * The EDGES are the pairs (A, B) that have a contribution to num_AB: a CSR over A with sorted columns and no diagonal that
+ * depends on the topology and on pairing only (a collider M of A + M -> B + M is the head of edges A -> M and B -> M and the
+ * tail of none). coef has one entry per edge, in CSR order. Sums are formed in a fixed order and the maximum is exact: the
+ * result is bit-identical from call to call and does not depend on how the states are cut into blocks (a workspace of at
+ * most 256 MB of per-state rates; KIN_DRG_BLOCK_STATES=n forces blocks of at most n states). accumulate != 0: the current
+ * contents of coef take part in the maximum (several solves or conditions folded into one graph). Rate constants and
+ * statuses are exactly kin_flux_batched[_dev]'s; B == 0 writes zeros, or leaves coef alone when accumulating.
+ * KIN_ERR_UNSUPPORTED for pairing != 0 on a network without pair records (n_species >= 65535).
+ * Added under KIN_ABI_VERSION 6: look the symbols up before calling them. */
+/* Pattern and plan sizes without a device or a handle. rowptr[n_species + 1] / colidx[edges], both may be NULL (sizes only).
+ * info[9]: edges, denominator contributions, edge contributions, then the rows of the denominator plan with <= 8, 9 .. 256 and
+ * > 256 contributions and the edges of the edge plan in the same three classes. */
+int kin_drg_pattern_host(int64_t n_species, int64_t n_reactions, const int64_t* reac_ptr, const int64_t* reac_idx,
+                         const int64_t* reac_sto, const int64_t* prod_ptr, const int64_t* prod_idx, const int64_t* prod_sto,
+                         int index_base, int pairing, int64_t* info, int64_t* rowptr, int64_t* colidx);
+/* The handle's pattern (built at the first call per pairing mode; no device call). Any of nnz / rowptr / colidx may be NULL. */
+int kin_drg_pattern(kin_network* h, int pairing, int index_base, int64_t* nnz, int64_t* rowptr, int64_t* colidx);
+/* Device pointers; only enqueues on `stream` (NULL: the handle's); allocates when the workspace has to grow. */
+int kin_drg_batched_dev(kin_network* h, int pairing, int64_t B, const double* d_u, const double* d_k, const int64_t* d_k_row,
+                        const double* d_T, int accumulate, double* d_coef /* [edges] */, void* stream);
+int kin_drg_batched(kin_network* h, int pairing, int64_t B, const double* u, const double* k, int64_t n_k_rows, const int64_t* k_row,
+                    const double* T, int accumulate, double* coef /* [edges] */);
+/* Over the saved states of the last kin_solve, read where they live (arguments as kin_solution_flux). */
+int kin_solution_drg(kin_network* h, int pairing, const double* k, int64_t n_k_rows, const int64_t* k_row, const double* T_rows,
+                     int accumulate, double* coef /* [edges] */);
+/* Over the stored ensemble, all members and rows at once (arguments as kin_ensemble_flux; the rows past n_saved[m] and their
+ * k_row / T_rows entries take no part). */
+int kin_ensemble_drg(kin_network* h, int pairing, const double* k, int64_t n_k_rows, const int64_t* k_row /* [K*n_rows] */,
+                     const double* T_rows /* [K*n_rows] */, int accumulate, double* coef /* [edges] */);
+
 /* ---- device / build information ------------------------------------------------------- */
 int kin_device_count(int* n);
 /* Selects the device for handles created afterwards by this thread; a handle remembers the device it was created on
@@ -478,7 +520,8 @@ const char* kin_version(void);
  * versions (1: round 1; 2: + dtmin and the LU-cache counters; 3: + the library-order sweep entry points; 4: + kin_solve_ensemble,
  * kin_lu_analyze_host - structs unchanged; 5: + kin_rhs_batched_klib_dev - structs unchanged; 6: + kin_solve_ensemble_continuous -
  * structs unchanged; kin_solve_ensemble_discrete, kin_resident_probe, kin_newton_probe, kin_step_probe, the flux pass (kin_flux_*, kin_solution_flux) and
- * kin_ensemble_size / _max / _dot / _flux came later under 6, found by symbol lookup). */
+ * kin_ensemble_size / _max / _dot / _flux and the directed relation graph (kin_drg_*, kin_solution_drg, kin_ensemble_drg) came
+ * later under 6, found by symbol lookup). */
 #define KIN_ABI_VERSION 6
 int kin_abi_version(void);
 int64_t kin_struct_size(int which); /* 0: sizeof(kin_params), 1: sizeof(kin_stats), else -1 */

@@ -33,6 +33,7 @@ SYMBOLS = [
     "kin_resident_probe", "kin_newton_probe", "kin_step_probe",
     "kin_flux_batched", "kin_flux_batched_dev", "kin_solution_flux",
     "kin_flux_segmented", "kin_flux_segmented_dev", "kin_ensemble_size", "kin_ensemble_max", "kin_ensemble_dot", "kin_ensemble_flux",
+    "kin_drg_pattern_host", "kin_drg_pattern", "kin_drg_batched", "kin_drg_batched_dev", "kin_solution_drg", "kin_ensemble_drg",
 ]
 ABI_VERSION = 6   # include/kinetica_hip.h: KIN_ABI_VERSION this binding was written against
 
@@ -146,6 +147,13 @@ def lib():
             L.kin_ensemble_max.argtypes = [c_void_p, PD]
             L.kin_ensemble_dot.argtypes = [c_void_p, PD, PD]
             L.kin_ensemble_flux.argtypes = [c_void_p, PD, PD, c_int64, P64, PD, PD]
+        if hasattr(L, "kin_drg_batched"):   # (also under ABI 6: the directed relation graph)
+            L.kin_drg_pattern_host.argtypes = [c_int64, c_int64] + [P64] * 6 + [c_int, c_int, P64, P64, P64]
+            L.kin_drg_pattern.argtypes = [c_void_p, c_int, c_int, P64, P64, P64]
+            L.kin_drg_batched.argtypes = [c_void_p, c_int, c_int64, PD, PD, c_int64, P64, PD, c_int, PD]
+            L.kin_drg_batched_dev.argtypes = [c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]
+            L.kin_solution_drg.argtypes = [c_void_p, c_int, PD, c_int64, P64, PD, c_int, PD]
+            L.kin_ensemble_drg.argtypes = [c_void_p, c_int, PD, c_int64, P64, PD, c_int, PD]
         L.kin_solve_ensemble.argtypes = [c_void_p, POINTER(KinParams), c_int64, PD, PD, PD, PD, PD, PD, c_int64, P64, PD, PD, P64,
                                          POINTER(c_int32), POINTER(KinStats)]
         L.kin_integrator_init.argtypes = [c_void_p, POINTER(KinParams), PD, PD, PD, PD, c_int64]
@@ -228,6 +236,28 @@ def lu_analyze_host(net, hub_degree=0, max_rounds=0, max_tail_degree=0, max_degr
         raise KineticaHipError(st, "symbolic LU analysis failed")
     keys = ("ns", "m", "rounds", "nnzU", "nnzZ", "nnzV", "nnzLZ", "nnzNVU", "w_size", "fused_products", "plan_entries", "plan_tasks")
     return {k: int(v) for k, v in zip(keys, info)}
+
+
+DRG_INFO = ("edges", "den_contributions", "edge_contributions", "den_short", "den_medium", "den_long", "edge_short", "edge_medium",
+            "edge_long")
+
+
+def drg_pattern_host(net, pairing=True):
+    """kin_drg_pattern_host of a FlatNetwork, computed on the host (no device): (rowptr[N + 1], colidx[edges], info) - the edge
+    CSR of the directed relation graph (0-based, sorted columns, no diagonal) and a dict of the DRG_INFO sizes: edges,
+    contributions, and the rows / edges of the two gather plans by class (<= 8, 9 .. 256, > 256 contributions)."""
+    L = lib()
+    arrs = [np.ascontiguousarray(a, dtype=np.int64) for a in (net.reac_ptr, net.reac_idx, net.reac_sto, net.prod_ptr,
+                                                              net.prod_idx, net.prod_sto)]
+    head = [int(net.n_species), int(net.n_reactions)] + [_p64(a) for a in arrs] + [0, 1 if pairing else 0]
+    info = np.zeros(len(DRG_INFO), np.int64)
+    st = L.kin_drg_pattern_host(*head, _p64(info), None, None)
+    if st != KIN_OK:
+        raise KineticaHipError(st, L.kin_last_error(None).decode())
+    rowptr, colidx = np.empty(net.n_species + 1, np.int64), np.empty(max(int(info[0]), 1), np.int64)
+    st = L.kin_drg_pattern_host(*head, _p64(info), _p64(rowptr), _p64(colidx))
+    assert st == KIN_OK
+    return rowptr, colidx[:int(info[0])], {k: int(v) for k, v in zip(DRG_INFO, info)}
 
 
 def arrhenius_eval(Ea, A, T, k_max=None, t_mult=1.0):
@@ -440,6 +470,69 @@ class HipNetwork:
         self._chk(lib().kin_ensemble_flux(self._h, _pd(w), _pd(k), n_rows, None if k_row is None else _p64(k_row), _pd(T_rows),
                                           _pd(flux)))
         return flux
+
+    # --- directed relation graph ---------------------------------------------------------------
+    def drg_pattern(self, pairing=True):
+        """kin_drg_pattern: (rowptr[N + 1], colidx[edges]) of the handle's directed relation graph, 0-based (no device call)."""
+        nnz = c_int64(0)
+        self._chk(lib().kin_drg_pattern(self._h, int(bool(pairing)), 0, ctypes.byref(nnz), None, None))
+        rowptr, colidx = np.empty(self.n + 1, np.int64), np.empty(max(nnz.value, 1), np.int64)
+        self._chk(lib().kin_drg_pattern(self._h, int(bool(pairing)), 0, None, _p64(rowptr), _p64(colidx)))
+        return rowptr, colidx[:nnz.value]
+
+    def _drg_coef(self, pairing, coef):
+        """The output buffer of a DRG entry: a fresh one, or (accumulate) a contiguous copy of `coef` that takes part in the maximum."""
+        nnz = c_int64(0)
+        self._chk(lib().kin_drg_pattern(self._h, int(bool(pairing)), 0, ctypes.byref(nnz), None, None))
+        if coef is None:
+            return np.empty(max(nnz.value, 1)), nnz.value, 0
+        out = np.empty(max(nnz.value, 1))
+        c = _f64(coef).ravel()
+        assert len(c) == nnz.value
+        out[:nnz.value] = c
+        return out, nnz.value, 1
+
+    def drg_batched(self, u, k=None, k_row=None, T=None, pairing=True, coef=None):
+        """kin_drg_batched on host arrays: coef[edges] (CSR order of drg_pattern) = max over the states u[B][N] of
+        num_AB / den_A, the directed-relation-graph coefficients of the network's records (pairing: a reaction with its exact
+        reverse; else every reaction alone). Rate constants of state b as in flux_batched. coef given: its values take part
+        in the maximum (the result is returned, the argument is left alone)."""
+        u = np.ascontiguousarray(np.atleast_2d(_f64(u)))
+        B = u.shape[0]
+        assert u.shape == (B, self.n)
+        k, n_rows, k_row, T, _ = self._flux_inputs(B, k, k_row, T, None)
+        out, nnz, acc = self._drg_coef(pairing, coef)
+        self._chk(lib().kin_drg_batched(self._h, int(bool(pairing)), B, _pd(u), _pd(k), n_rows, None if k_row is None else _p64(k_row),
+                                        _pd(T), acc, _pd(out)))
+        return out[:nnz]
+
+    def drg_batched_dev(self, B, d_u, d_coef, d_k=0, d_k_row=0, d_T=0, pairing=True, accumulate=False, stream=0):
+        """kin_drg_batched_dev: device pointers (ints; 0 = not given), u[B][N], k rows / k_row[B] (int64) / T[B], coef[edges].
+        One stream per handle at a time; allocates only when the workspace has to grow."""
+        p = lambda x: c_void_p(x) if x else None
+        self._chk(lib().kin_drg_batched_dev(self._h, int(bool(pairing)), int(B), p(d_u), p(d_k), p(d_k_row), p(d_T),
+                                            1 if accumulate else 0, p(d_coef), p(stream)))
+
+    def solution_drg(self, k=None, k_row=None, T_rows=None, pairing=True, coef=None):
+        """kin_solution_drg: drg_batched over the saved states of the last solve, read where they live on the device
+        (rate-constant sources as solution_flux)."""
+        n_saved = c_int64(0)
+        self._chk(lib().kin_solution_size(self._h, ctypes.byref(n_saved), None))
+        k, n_rows, k_row, T_rows, _ = self._flux_inputs(n_saved.value, k, k_row, T_rows, None)
+        out, nnz, acc = self._drg_coef(pairing, coef)
+        self._chk(lib().kin_solution_drg(self._h, int(bool(pairing)), _pd(k), n_rows, None if k_row is None else _p64(k_row),
+                                         _pd(T_rows), acc, _pd(out)))
+        return out[:nnz]
+
+    def ensemble_drg(self, k=None, k_row=None, T_rows=None, pairing=True, coef=None):
+        """kin_ensemble_drg: one graph over every saved row of every member of the stored ensemble (k_row / T_rows: [K][n_rows],
+        entries past a member's saved rows are ignored)."""
+        K, rows = self.ensemble_size()[:2]
+        k, n_rows, k_row, T_rows, _ = self._flux_inputs(K * rows, k, k_row, T_rows, None)
+        out, nnz, acc = self._drg_coef(pairing, coef)
+        self._chk(lib().kin_ensemble_drg(self._h, int(bool(pairing)), _pd(k), n_rows, None if k_row is None else _p64(k_row),
+                                         _pd(T_rows), acc, _pd(out)))
+        return out[:nnz]
 
     # --- library order (tiled sweep) --------------------------------------------------------
     def lib_layout(self):

@@ -1,0 +1,51 @@
+// Directed relation graph (Lu & Law) of a network over batched states (kin_drg_*): host tables (drg.cpp), the gather
+// kernels and their launchers (drg_kernels.hip).
+//
+// Records group the reactions: with pairing a record is a reaction kf and its exact reverse kr as compile_network pairs
+// them (NetworkHost::pair_k; kr = -1: no partner) and progresses at w = q_kf - q_kr; without pairing every reaction is a
+// record (kr = -1, w = q_r). Per record nu_A is the forward reaction's net coefficient of species A (slot_sp / slot_co)
+// and S its species on either side (operands and slots: a collider with zero net coefficient belongs to S). For a state
+//   den_A  = sum over records with nu_A != 0                     of |nu_A| |w|
+//   num_AB = sum over records with nu_A != 0, B in S, B != A     of |nu_A| |w|
+//   r_AB   = num_AB / den_A  (0 where den_A == 0),   coef_AB = max over the states of r_AB.
+// An edge (A, B) exists when some record contributes to num_AB: a CSR over A, columns sorted, no diagonal.
+#pragma once
+#include "common.hpp"
+#include "kernels.hpp"
+#include "network.hpp"
+
+namespace kin {
+
+// Both sums are gather plans of build_seg_plan with payload (a, b) = (kf, kr) - laid out as a product plan, but b < 0
+// is a record without a reverse here, not padding - and the coefficients |nu| in arrays of their own, addressed by the
+// plan's payload slot (0.0f: padding). The edge plan's aux is the edge's row A, where its divisor den_A lives.
+struct DrgTables {
+  int64_t N = 0, E = 0, n_den = 0, n_num = 0;
+  std::vector<int32_t> rowptr, colidx;          // N + 1, E
+  int64_t den_cls[3] = {0, 0, 0};               // rows of the denominator plan with <= SHORT_MAX, <= SEG_LEN, more contributions
+  int64_t edge_cls[3] = {0, 0, 0};              // edges of the edge plan likewise
+  bool have_plans = false;
+  SegPlanHost den_plan, edge_plan;
+  std::vector<float> den_ell_c, den_long_c, edge_ell_c, edge_long_c;
+};
+// pairing != 0 needs the pair records (compile_network builds them for N < 65535): KinError(ERR_UNSUPPORTED) without
+DrgTables build_drg_tables(const NetworkHost& h, int pairing, bool with_plans);
+
+struct DrgArgs {
+  SegPlanView p;
+  const float* ell_c; const float* long_c;
+  int N, R, E, nb;                 // nb: states of this block, rates[nb][R]
+  const double* rates;
+  int64_t b0;                      // global index of the block's first state (for seg_n)
+  const int64_t* seg_n; int64_t L; // state b counts only when b % L < seg_n[b / L] (seg_n null: every state counts)
+  double* den;                     // den[nb][N]: written by the denominator launch, read by the edge launch
+  double* part;                    // part[Y][E]: the edge launch's maxima per slice of the states
+};
+// slices of the states a launch is cut into so that the device is filled (depends on the plan, nb and n_cu only)
+int drg_slices(const SegPlanView& p, int64_t nb, int n_cu);
+void launch_drg_den(const DrgArgs& a, int Y, hipStream_t s);
+void launch_drg_edges(const DrgArgs& a, int Y, hipStream_t s);
+// coef[e] = max(use_prev ? coef[e] : 0, part[0][e], ..., part[Y - 1][e])
+void launch_drg_max(int64_t E, int Y, const double* part, double* coef, int use_prev, hipStream_t s);
+
+}  // namespace kin

@@ -1,0 +1,210 @@
+// extern "C" entry points of the directed-relation-graph pass (declarations: include/kinetica_hip.h; tables: drg.cpp;
+// kernels: drg_kernels.hip). kin_drg_pattern_host, which needs no handle, sits with the other host-only entries in capi.cpp.
+#include "../../include/kinetica_hip.h"
+
+#include <algorithm>
+#include <cstdlib>
+
+#include "drg.hpp"
+#include "flux_api.hpp"
+#include "handle.hpp"
+
+using namespace kin;
+
+namespace {
+
+void require(bool c, int code, const char* msg) {
+  if (!c) throw KinError(code, msg);
+}
+
+constexpr size_t DRG_RATES_BYTES = (size_t)256 << 20;   // bound of the stage-1 workspace rates[nb][R]
+
+DrgTables& drg_host(kin_network* h, int pairing) {
+  auto& m = h->drg[pairing ? 1 : 0];
+  if (!m.host) m.host = std::make_unique<DrgTables>(build_drg_tables(h->host, pairing, true));
+  return *m.host;
+}
+
+kin_network::DrgMode& drg_dev(kin_network* h, int pairing, hipStream_t s) {
+  auto& m = h->drg[pairing ? 1 : 0];
+  const DrgTables& t = drg_host(h, pairing);
+  if (!m.dev_ready) {
+    m.den_plan.upload(t.den_plan, s); m.edge_plan.upload(t.edge_plan, s);
+    m.den_ell_c.upload(t.den_ell_c, s); m.den_long_c.upload(t.den_long_c, s);
+    m.edge_ell_c.upload(t.edge_ell_c, s); m.edge_long_c.upload(t.edge_long_c, s);
+    KIN_HIP(hipStreamSynchronize(s));
+    m.dev_ready = true;
+  }
+  return m;
+}
+
+// The pass on device buffers. States b0, b0 + nb, ... are taken block by block: stage 1 (the flux sweep) writes the block's
+// rates, stage 2 its denominators and the maxima of the ratios, folded into d_coef. seg_n / L: see DrgArgs.
+void drg_run(kin_network* h, int pairing, int64_t B, const double* d_u, const FluxSource& src, const int64_t* d_seg_n, int64_t L,
+             int accumulate, double* d_coef, hipStream_t s) {
+  const int64_t N = h->host.N, R = h->host.R;
+  auto& m = drg_dev(h, pairing, s);
+  const int64_t E = m.host->E;
+  if (E == 0) return;
+  if (B == 0) {
+    if (!accumulate) KIN_HIP(hipMemsetAsync(d_coef, 0, (size_t)E * sizeof(double), s));
+    return;
+  }
+  int64_t nb_max = std::max<int64_t>(1, (int64_t)(DRG_RATES_BYTES / ((size_t)R * sizeof(double))));
+  if (const char* e = getenv("KIN_DRG_BLOCK_STATES")) {   // (read per call: tests change it)
+    const int64_t v = atoll(e);
+    if (v >= 1) nb_max = std::min(nb_max, v);
+  }
+  nb_max = std::min(nb_max, B);
+  h->drg_rates.alloc((size_t)nb_max * R);
+  h->drg_den.alloc((size_t)nb_max * N);
+  const SegPlanView dv = m.den_plan.view(), ev = m.edge_plan.view();
+  const int Ye_max = drg_slices(ev, nb_max, h->n_cu);
+  h->drg_part.alloc((size_t)Ye_max * E);
+  for (int64_t b0 = 0; b0 < B; b0 += nb_max) {
+    const int64_t nb = std::min(nb_max, B - b0);
+    FluxSource bs = src;
+    if (bs.k && !bs.k_row) bs.k += (size_t)b0 * (size_t)bs.k_stride;
+    if (bs.k_row) bs.k_row += b0;
+    if (bs.T) bs.T += b0;
+    flux_run(h, nb, d_u + (size_t)b0 * N, bs, nullptr, nullptr, h->drg_rates.p, s);
+    DrgArgs a{};
+    a.N = (int)N; a.R = (int)R; a.E = (int)E; a.nb = (int)nb;
+    a.rates = h->drg_rates.p; a.b0 = b0; a.seg_n = d_seg_n; a.L = L;
+    a.den = h->drg_den.p; a.part = h->drg_part.p;
+    a.p = dv; a.ell_c = m.den_ell_c.p; a.long_c = m.den_long_c.p;
+    launch_drg_den(a, drg_slices(dv, nb, h->n_cu), s);
+    a.p = ev; a.ell_c = m.edge_ell_c.p; a.long_c = m.edge_long_c.p;
+    const int Ye = drg_slices(ev, nb, h->n_cu);
+    launch_drg_edges(a, Ye, s);
+    launch_drg_max(E, Ye, h->drg_part.p, d_coef, (accumulate || b0 > 0) ? 1 : 0, s);
+  }
+}
+
+void drg_check(kin_network* h, int64_t B, bool have_k, bool have_row, bool have_T, bool have_out) {
+  flux_check(h, B, have_k, have_row, have_T, true);
+  require(have_out, ERR_INVALID_ARG, "null output buffer");
+  require(h->host.N < ((int64_t)1 << 31) / 2, ERR_UNSUPPORTED, "DRG pass: N beyond 32-bit offsets");
+}
+
+// host entries: coef staged through the handle's buffer (uploaded first when it takes part in the maximum)
+void drg_host_call(kin_network* h, int pairing, int64_t B, const double* d_u, const FluxSource& src, const int64_t* d_seg_n, int64_t L,
+                   int accumulate, double* coef, hipStream_t s) {
+  const int64_t E = drg_host(h, pairing).E;
+  h->drg_coef.alloc((size_t)E);
+  if (accumulate && E > 0) h->drg_coef.upload(coef, (size_t)E, s);
+  drg_run(h, pairing, B, d_u, src, d_seg_n, L, accumulate, h->drg_coef.p, s);
+  if (E > 0) h->drg_coef.download(coef, (size_t)E, s);
+  KIN_HIP(hipStreamSynchronize(s));
+}
+
+}  // namespace
+
+#define KIN_TRY(h) try { KIN_HIP(hipSetDevice((h)->device));
+#define KIN_CATCH(h)                                                        \
+  }                                                                         \
+  catch (const KinError& e) { (h)->err = e.what(); return e.code; }         \
+  catch (const std::exception& e) { (h)->err = e.what(); return KIN_ERR_DEVICE; } \
+  return KIN_OK;
+
+extern "C" {
+
+int kin_drg_pattern(kin_network* h, int pairing, int index_base, int64_t* nnz, int64_t* rowptr, int64_t* colidx) {
+  if (!h) return KIN_ERR_INVALID_ARG;
+  try {     // (host tables only: no device call)
+    const DrgTables& t = drg_host(h, pairing);
+    if (nnz) *nnz = t.E;
+    if (rowptr) for (int64_t i = 0; i <= t.N; i++) rowptr[i] = t.rowptr[i] + index_base;
+    if (colidx) for (int64_t e = 0; e < t.E; e++) colidx[e] = t.colidx[e] + index_base;
+  } catch (const KinError& e) { h->err = e.what(); return e.code; }
+  catch (const std::exception& e) { h->err = e.what(); return KIN_ERR_INVALID_ARG; }
+  return KIN_OK;
+}
+
+int kin_drg_batched_dev(kin_network* h, int pairing, int64_t B, const double* d_u, const double* d_k, const int64_t* d_k_row,
+                        const double* d_T, int accumulate, double* d_coef, void* stream) {
+  if (!h) return KIN_ERR_INVALID_ARG;
+  KIN_TRY(h)
+  drg_check(h, B, d_k != nullptr, d_k_row != nullptr, d_T != nullptr, d_coef != nullptr);
+  require(d_u != nullptr || B == 0, ERR_INVALID_ARG, "null state buffer");
+  hipStream_t s = stream ? (hipStream_t)stream : h->stream;
+  drg_run(h, pairing, B, d_u, FluxSource{d_k, h->host.R, d_k_row, d_T}, nullptr, 0, accumulate, d_coef, s);
+  KIN_CATCH(h)
+}
+
+int kin_drg_batched(kin_network* h, int pairing, int64_t B, const double* u, const double* k, int64_t n_k_rows, const int64_t* k_row,
+                    const double* T, int accumulate, double* coef) {
+  if (!h) return KIN_ERR_INVALID_ARG;
+  KIN_TRY(h)
+  drg_check(h, B, k != nullptr, k_row != nullptr, T != nullptr, coef != nullptr);
+  require(u != nullptr || B == 0, ERR_INVALID_ARG, "null state buffer");
+  if (k && k_row) { require(n_k_rows >= 1 || B == 0, ERR_INVALID_ARG, "k has no rows"); flux_check_rows(k_row, B, n_k_rows); }
+  else if (k) require(n_k_rows == B, ERR_INVALID_ARG, "k without k_row needs one row per state (n_k_rows == B)");
+  const int64_t N = h->host.N, R = h->host.R;
+  hipStream_t s = h->stream;
+  if (B > 0) h->f_u.upload(u, (size_t)B * N, s);
+  if (k && n_k_rows > 0) h->f_k.upload(k, (size_t)n_k_rows * R, s);
+  if (k_row && B > 0) h->f_krow.upload(k_row, (size_t)B, s);
+  if (T && B > 0) h->f_T.upload(T, (size_t)B, s);
+  drg_host_call(h, pairing, B, h->f_u.p, FluxSource{k ? h->f_k.p : nullptr, R, k_row ? h->f_krow.p : nullptr, T ? h->f_T.p : nullptr},
+                nullptr, 0, accumulate, coef, s);
+  KIN_CATCH(h)
+}
+
+int kin_solution_drg(kin_network* h, int pairing, const double* k, int64_t n_k_rows, const int64_t* k_row, const double* T_rows,
+                     int accumulate, double* coef) {
+  if (!h) return KIN_ERR_INVALID_ARG;
+  KIN_TRY(h)
+  const int64_t B = h->n_saved, R = h->host.R;
+  const bool table = !k && k_row;    // rows of the device-resident rate table
+  drg_check(h, B, k != nullptr || table, k_row != nullptr, T_rows != nullptr, coef != nullptr);
+  require(B > 0, ERR_STATE, "no solution stored");
+  require(!table || h->table_rows > 0, ERR_STATE, "no rate table resident (kin_rate_table / kin_solve with a table first)");
+  if (k_row) flux_check_rows(k_row, B, table ? h->table_rows : n_k_rows);
+  else if (k) require(n_k_rows == B, ERR_INVALID_ARG, "k without k_row needs one row per saved state (n_k_rows == n_saved)");
+  hipStream_t s = h->stream;
+  if (k) h->f_k.upload(k, (size_t)n_k_rows * R, s);
+  if (k_row) h->f_krow.upload(k_row, (size_t)B, s);
+  if (T_rows) h->f_T.upload(T_rows, (size_t)B, s);
+  const double* ksrc = k ? h->f_k.p : (table ? h->table.p : nullptr);
+  drg_host_call(h, pairing, B, h->d_sol_u.p, FluxSource{ksrc, R, k_row ? h->f_krow.p : nullptr, T_rows ? h->f_T.p : nullptr}, nullptr, 0,
+                accumulate, coef, s);
+  KIN_CATCH(h)
+}
+
+int kin_ensemble_drg(kin_network* h, int pairing, const double* k, int64_t n_k_rows, const int64_t* k_row, const double* T_rows,
+                     int accumulate, double* coef) {
+  if (!h) return KIN_ERR_INVALID_ARG;
+  KIN_TRY(h)
+  require(h->ens.valid(), ERR_STATE, "no ensemble stored (kin_solve_ensemble* first)");
+  const int64_t K = h->ens.K, cap = h->ens.cap, B = K * cap, R = h->host.R;
+  require(cap < ((int64_t)1 << 31) && K < ((int64_t)1 << 31) && B < ((int64_t)1 << 31), ERR_UNSUPPORTED,
+          "ensemble DRG pass: K n_rows beyond 32-bit offsets");
+  drg_check(h, B, k != nullptr, k_row != nullptr, T_rows != nullptr, coef != nullptr);
+  if (k && k_row) require(n_k_rows >= 1, ERR_INVALID_ARG, "k has no rows");
+  else if (k) require(n_k_rows == B, ERR_INVALID_ARG, "k without k_row needs one row per saved row (n_k_rows == K n_rows)");
+  // Stage 1 runs over every row of the record; the keys of the rows past a member's saved ones are ignored by contract, so
+  // they are replaced by harmless ones here (row 0, 1000 K) and stage 2 leaves those states out.
+  std::vector<int64_t> rows;
+  std::vector<double> Ts;
+  if (k_row) rows.assign(k_row, k_row + B);
+  if (T_rows) Ts.assign(T_rows, T_rows + B);
+  for (int64_t m = 0; m < K; m++) {
+    const int64_t n = h->ens.n_saved[m];
+    for (int64_t j = 0; j < cap; j++) {
+      const int64_t b = m * cap + j;
+      if (j < n) { if (k_row) require(rows[b] >= 0 && rows[b] < n_k_rows, ERR_INVALID_ARG, "k_row: row index out of range"); }
+      else { if (k_row) rows[b] = 0; if (T_rows) Ts[b] = 1000.0; }
+    }
+  }
+  hipStream_t s = h->stream;
+  h->ens_segn.upload(h->ens.n_saved, s);
+  if (k && n_k_rows > 0) h->f_k.upload(k, (size_t)n_k_rows * R, s);
+  if (k_row) h->f_krow.upload(rows, s);
+  if (T_rows) h->f_T.upload(Ts, s);
+  drg_host_call(h, pairing, B, h->ens.sol, FluxSource{k ? h->f_k.p : nullptr, R, k_row ? h->f_krow.p : nullptr, T_rows ? h->f_T.p : nullptr},
+                h->ens_segn.p, cap, accumulate, coef, s);
+  KIN_CATCH(h)
+}
+
+}  // extern "C"

@@ -3,6 +3,7 @@
 
 #include <algorithm>
 
+#include "flux_api.hpp"
 #include "flux_kernels.hpp"
 #include "handle.hpp"
 
@@ -14,8 +15,9 @@ void require(bool c, int code, const char* msg) {
   if (!c) throw KinError(code, msg);
 }
 
-// where a call's rate constants come from: rows of k (k_stride doubles apart; 0 = one shared row) or the Arrhenius law at T[b]
-struct FluxSource { const double* k; int64_t k_stride; const int64_t* k_row; const double* T; };
+}  // namespace
+
+namespace kin {
 
 // checks shared by the three entry points (have_k: a rate-constant array or, for kin_solution_flux, the resident table)
 void flux_check(kin_network* h, int64_t B, bool have_k, bool have_row, bool have_T, bool have_out) {
@@ -29,7 +31,7 @@ void flux_check(kin_network* h, int64_t B, bool have_k, bool have_row, bool have
 }
 
 // the index tables of both passes: uploaded at the first call that needs them
-void ensure_flux_tables(kin_network* h, hipStream_t s) {
+static void ensure_flux_tables(kin_network* h, hipStream_t s) {
   if (h->flux_ready) return;
   const FluxTables t = build_flux_tables(h->host);
   if (!t.idx16.empty()) h->flux_idx16.upload(t.idx16, s);
@@ -66,9 +68,13 @@ void flux_run(kin_network* h, int64_t B, const double* d_u, const FluxSource& sr
   if (d_flux) launch_flux_reduce(R, plan.G, h->flux_part.p, d_flux, s);
 }
 
-void check_rows(const int64_t* k_row, int64_t B, int64_t n_rows) {
+void flux_check_rows(const int64_t* k_row, int64_t B, int64_t n_rows) {
   for (int64_t b = 0; b < B; b++) require(k_row[b] >= 0 && k_row[b] < n_rows, ERR_INVALID_ARG, "k_row: row index out of range");
 }
+
+}  // namespace kin
+
+namespace {
 
 // The segmented pass on device buffers (kin_flux_segmented*, kin_ensemble_flux): ONE launch that writes d_flux[S][R] itself.
 void flux_seg_run(kin_network* h, int64_t S, int64_t L, const int64_t* d_seg_n, const double* d_u, const FluxSource& src,
@@ -146,7 +152,7 @@ int kin_flux_batched(kin_network* h, int64_t B, const double* u, const double* k
   KIN_TRY(h)
   flux_check(h, B, k != nullptr, k_row != nullptr, T != nullptr, flux || rates);
   require(u != nullptr || B == 0, ERR_INVALID_ARG, "null state buffer");
-  if (k && k_row) { require(n_k_rows >= 1 || B == 0, ERR_INVALID_ARG, "k has no rows"); check_rows(k_row, B, n_k_rows); }
+  if (k && k_row) { require(n_k_rows >= 1 || B == 0, ERR_INVALID_ARG, "k has no rows"); flux_check_rows(k_row, B, n_k_rows); }
   else if (k) require(n_k_rows == B, ERR_INVALID_ARG, "k without k_row needs one row per state (n_k_rows == B)");
   const int64_t N = h->host.N, R = h->host.R;
   hipStream_t s = h->stream;
@@ -174,7 +180,7 @@ int kin_solution_flux(kin_network* h, const double* w, const double* k, int64_t 
   flux_check(h, B, k != nullptr || table, k_row != nullptr, T_rows != nullptr, flux || rates);
   require(B > 0, ERR_STATE, "no solution stored");
   require(!table || h->table_rows > 0, ERR_STATE, "no rate table resident (kin_rate_table / kin_solve with a table first)");
-  if (k_row) check_rows(k_row, B, table ? h->table_rows : n_k_rows);
+  if (k_row) flux_check_rows(k_row, B, table ? h->table_rows : n_k_rows);
   else if (k) require(n_k_rows == B, ERR_INVALID_ARG, "k without k_row needs one row per saved state (n_k_rows == n_saved)");
   hipStream_t s = h->stream;
   if (k) h->f_k.upload(k, (size_t)n_k_rows * R, s);

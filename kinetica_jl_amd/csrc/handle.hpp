@@ -4,6 +4,7 @@
 #include <string>
 
 #include "common.hpp"
+#include "drg.hpp"
 #include "kernels.hpp"
 #include "network.hpp"
 #include "tiled.hpp"
@@ -62,6 +63,17 @@ struct kin_network {
   kin::DevBuf<int32_t> flux_idx32;
   kin::DevBuf<double> flux_part, f_u, f_k, f_T, f_w, f_flux, f_rates;
   kin::DevBuf<int64_t> f_krow, f_segn;
+
+  // directed-relation-graph pass (drg.hpp, drg_api.cpp): host tables and device plans per pairing mode, built at the first
+  // call that needs them; the block of per-state rates (stage 1), its denominators, the maxima per slice and the staging
+  // buffer of the host entries' coefficients, grown on demand
+  struct DrgMode {
+    std::unique_ptr<kin::DrgTables> host;
+    bool dev_ready = false;
+    kin::SegPlanDev den_plan, edge_plan;
+    kin::DevBuf<float> den_ell_c, den_long_c, edge_ell_c, edge_long_c;
+  } drg[2];
+  kin::DevBuf<double> drg_rates, drg_den, drg_part, drg_coef;
 
   // tiled sweep in library order (tiled.hpp, tiled_api.cpp): built at the first call that needs it
   kin::TiledHost tiled;

@@ -58,6 +58,17 @@ class SpeciesData:
         xyz = None if n_atoms is None else {i + 1: {"N_atoms": int(a)} for i, a in enumerate(n_atoms)}
         return cls({s: i + 1 for i, s in enumerate(names)}, {i + 1: s for i, s in enumerate(names)}, len(names), xyz)
 
+    def subset(self, ids):
+        """(sd_new, new_id): the species `ids` (1-based) renumbered 1 .. len(ids) in ascending order of their old ids, and the
+        dict old id -> new id. EXTENSION (the reference only ever grows a SpeciesData): what a reduced network is solved with."""
+        ids = sorted(set(int(i) for i in ids))
+        if ids and (ids[0] < 1 or ids[-1] > self.n):
+            raise ValueError("species id out of range")
+        new_id = {old: i + 1 for i, old in enumerate(ids)}
+        xyz = None if self.xyz is None else {new_id[old]: self.xyz[old] for old in ids if old in self.xyz}
+        return SpeciesData({self.toStr[old]: new for old, new in new_id.items()}, {new: self.toStr[old] for old, new in new_id.items()},
+                           len(ids), xyz), new_id
+
 
 @dataclass
 class RxData:
@@ -96,6 +107,16 @@ class RxData:
         if self.dH is not None:
             self.dH = [self.dH[i] for i in keep]
         self.nr = len(keep)
+
+    def subset_species(self, new_id):
+        """(rd_new, kept): the reactions ALL of whose species, on both sides, are keys of `new_id` (old id -> new id, as
+        SpeciesData.subset returns it), renumbered, and their 0-based positions in this RxData. EXTENSION next to splice,
+        which only removes reactions."""
+        kept = [r for r in range(self.nr) if all(i in new_id for i in self.id_reacs[r]) and all(i in new_id for i in self.id_prods[r])]
+        ren = lambda L: [[new_id[i] for i in L[r]] for r in kept]
+        cp = lambda L: [L[r][:] for r in kept]
+        return RxData(len(kept), ren(self.id_reacs), ren(self.id_prods), cp(self.stoic_reacs), cp(self.stoic_prods),
+                      None if self.dH is None else [self.dH[r] for r in kept]), kept
 
     def flat(self, n_species):
         """Flat arrays for kin_network_create (index_base = 1)."""
@@ -917,6 +938,30 @@ class ReactionFluxes:
         return cls(flux, prod, cons, np.asarray(weights, dtype=float), rates)
 
 
+def saved_state_rate_source(out, calculator, t):
+    """The rate constants a solve held at each of its saved times t, as the keywords of HipNetwork.flux_batched /
+    drg_batched: dict(k=, k_row=) or dict(T=) (reaction_fluxes documents the rules)."""
+    conditions = out.conditions
+    arr = isinstance(calculator, PrecalculatedArrheniusCalculator)
+    src = {}
+    if isstatic(conditions) or isinstance(calculator, DummyKineticCalculator):
+        src = dict(k=np.asarray(get_initial_rates(conditions, calculator), dtype=float)[None, :], k_row=np.zeros(len(t), np.int64))
+    elif conditions.discrete_updates:
+        if out.sol_k is None:
+            raise ValueError("a discrete-update solve output needs sol_k (the rate constants at the stops)")
+        held = held_stop_index(t, out.sol_k.t)
+        if arr and hasattr(out.sol_k, "T"):
+            src = dict(T=np.asarray(out.sol_k.T, dtype=float)[held])
+        else:
+            src = dict(k=np.asarray(out.sol_k.u, dtype=float), k_row=held)
+    elif arr:
+        prof = conditions.profiles[conditions.symbols.index("T")]
+        src = dict(T=np.full(len(t), float(prof.value)) if isstatic(prof) else np.asarray(out.sol_vcs["T"], dtype=float))
+    else:
+        raise ValueError("calculator does not support continuous rate updates")
+    return src
+
+
 def reaction_fluxes(out, calculator, weights="trapezoid", rates=False):
     """Time-integrated rate of every reaction over the saved states of a solve - which reactions carried the flux, the
     companion of identify_next_seeds' "which species matter". `out` is any ODESolveOutput (solve_network's, or one read
@@ -946,23 +991,7 @@ def reaction_fluxes(out, calculator, weights="trapezoid", rates=False):
         w = np.asarray(weights, dtype=float).ravel()
         if len(w) != len(t):
             raise ValueError("weights must have one entry per saved time")
-    arr = isinstance(calculator, PrecalculatedArrheniusCalculator)
-    src = {}
-    if isstatic(conditions) or isinstance(calculator, DummyKineticCalculator):
-        src = dict(k=np.asarray(get_initial_rates(conditions, calculator), dtype=float)[None, :], k_row=np.zeros(len(t), np.int64))
-    elif conditions.discrete_updates:
-        if out.sol_k is None:
-            raise ValueError("a discrete-update solve output needs sol_k (the rate constants at the stops)")
-        held = held_stop_index(t, out.sol_k.t)
-        if arr and hasattr(out.sol_k, "T"):
-            src = dict(T=np.asarray(out.sol_k.T, dtype=float)[held])
-        else:
-            src = dict(k=np.asarray(out.sol_k.u, dtype=float), k_row=held)
-    elif arr:
-        prof = conditions.profiles[conditions.symbols.index("T")]
-        src = dict(T=np.full(len(t), float(prof.value)) if isstatic(prof) else np.asarray(out.sol_vcs["T"], dtype=float))
-    else:
-        raise ValueError("calculator does not support continuous rate updates")
+    src = saved_state_rate_source(out, calculator, t)
     h = capi.HipNetwork(*rd.flat(sd.n), index_base=1)
     try:
         if "T" in src:
@@ -972,6 +1001,104 @@ def reaction_fluxes(out, calculator, weights="trapezoid", rates=False):
         h.close()
     flux, rr = res if rates else (res, None)
     return ReactionFluxes.from_flux(flux, rd, sd.n, w, rr)
+
+
+# ---- directed-relation-graph reduction (EXTENSION: Lu & Law's DRG over the saved states of a solve) ---------------------
+def drg_coefficients(out, calculator, pairing=True):
+    """(rowptr[N + 1], colidx[E], coef[E]): the directed relation graph of `out.rd` over the saved states of a solve - edge
+    (A, B) in CSR form (0-based, sorted columns, no diagonal) with coef_AB = max over the saved states of num_AB / den_A, the
+    share of species A's turnover that runs through records B takes part in (include/kinetica_hip.h has the definition;
+    pairing: a reaction and its exact reverse are one record progressing at their net rate). `calculator` and the rate
+    constants of every saved state are chosen as reaction_fluxes chooses them. One device pass (kin_drg_batched) over sol.u."""
+    sd, rd = out.sd, out.rd
+    setup_network(sd, rd, calculator)
+    t = np.asarray(out.sol.t, dtype=float)
+    u = np.ascontiguousarray(np.asarray(out.sol.u, dtype=float).reshape(len(t), sd.n))
+    src = saved_state_rate_source(out, calculator, t)
+    h = capi.HipNetwork(*rd.flat(sd.n), index_base=1)
+    try:
+        if "T" in src:
+            h.set_arrhenius(calculator.Ea, calculator.A, calculator.k_max, calculator.t_mult)
+        rowptr, colidx = h.drg_pattern(pairing)
+        coef = h.drg_batched(u, pairing=pairing, **src)
+    finally:
+        h.close()
+    return rowptr, colidx, coef
+
+
+def drg_select(rowptr, colidx, coef, targets, eps):
+    """Species (0-based, sorted) reachable from `targets` over the edges with coef >= eps: the targets themselves and, from
+    every kept species A, every B with coef_AB >= eps. Pure NumPy."""
+    rowptr, colidx, coef = np.asarray(rowptr, dtype=np.int64), np.asarray(colidx, dtype=np.int64), np.asarray(coef, dtype=float)
+    n = len(rowptr) - 1
+    keep = np.zeros(n, bool)
+    front = np.unique(np.asarray(list(targets), dtype=np.int64))
+    if len(front) and (front[0] < 0 or front[-1] >= n):
+        raise ValueError("target species id out of range")
+    keep[front] = True
+    strong = coef >= float(eps)
+    while len(front):
+        idx = np.concatenate([np.arange(rowptr[a], rowptr[a + 1]) for a in front]) if len(front) else np.zeros(0, np.int64)
+        nxt = np.unique(colidx[idx[strong[idx]]]) if len(idx) else np.zeros(0, np.int64)
+        front = nxt[~keep[nxt]]
+        keep[front] = True
+    return np.flatnonzero(keep).astype(np.int64)
+
+
+@dataclass
+class DRGReduction:
+    """Result of reduce_network: the kept species / reactions (0-based positions in the full sd / rd, ascending), the
+    renumbered sd and rd, the calculator spliced to rd, and the graph the selection was made on."""
+    species_kept: np.ndarray
+    reactions_kept: np.ndarray
+    sd: SpeciesData
+    rd: RxData
+    calculator: object
+    rowptr: np.ndarray
+    colidx: np.ndarray
+    coef: np.ndarray
+    targets: np.ndarray
+    eps: float
+
+    def map_u0(self, u0):
+        """A u0 specification of the full network (ODESimulationParams.u0: dict name -> concentration, or a vector over the
+        full species) in the reduced numbering. A non-zero concentration of a dropped species is an error."""
+        if isinstance(u0, dict):
+            lost = [sp for sp, c in u0.items() if sp not in self.sd.toInt and c != 0]
+            if lost:
+                raise ValueError(f"u0 gives a concentration to species the reduction dropped: {lost}")
+            return {sp: c for sp, c in u0.items() if sp in self.sd.toInt}
+        u0 = np.asarray(u0, dtype=float)
+        dropped = np.ones(len(u0), bool)
+        dropped[self.species_kept[self.species_kept < len(u0)]] = False
+        if np.any(u0[dropped] != 0):
+            raise ValueError("u0 gives a concentration to species the reduction dropped")
+        out = np.zeros(len(self.species_kept))
+        inside = self.species_kept < len(u0)
+        out[inside] = u0[self.species_kept[inside]]
+        return out
+
+
+def reduce_network(out, calculator, targets, eps, pairing=True, coef=None):
+    """DRG reduction of the network of a solve: keeps the species reachable from `targets` (names or 0-based ids) over the
+    edges with coefficient >= eps - the species non-zero in the first saved state always count as targets - and the
+    reactions ALL of whose species, on both sides, are kept. `coef`: (rowptr, colidx, coef) of an earlier drg_coefficients
+    call (or several solves folded into one graph), else computed here. `calculator` is left alone; the DRGReduction
+    carries a copy spliced to the reduced rd, ready for solve_network / solve_network_ensemble."""
+    sd, rd = out.sd, out.rd
+    rowptr, colidx, cf = drg_coefficients(out, calculator, pairing) if coef is None else coef
+    tg = [sd.toInt[x] - 1 if isinstance(x, str) else int(x) for x in targets]
+    u_first = np.asarray(out.sol.u, dtype=float).reshape(len(out.sol.t), sd.n)[0]
+    tg = np.unique(np.concatenate([np.asarray(tg, dtype=np.int64), np.flatnonzero(u_first != 0)]))
+    kept_sp = drg_select(rowptr, colidx, cf, tg, eps)
+    sd_new, new_id = sd.subset(kept_sp + 1)
+    rd_new, kept_rx = rd.subset_species(new_id)
+    kill = np.setdiff1d(np.arange(rd.nr), np.asarray(kept_rx, dtype=np.int64))
+    calc = copy.deepcopy(calculator)
+    if len(kill):
+        calc.splice(kill)
+    return DRGReduction(kept_sp, np.asarray(kept_rx, dtype=np.int64), sd_new, rd_new, calc, np.asarray(rowptr), np.asarray(colidx),
+                        np.asarray(cf), tg, float(eps))
 
 
 # ---- the consumer of a level's solve (src/exploration/explore_utils.jl:338-406) ---------------------------

@@ -1,0 +1,239 @@
+"""GPU tests of the directed-relation-graph pass (kin_drg_batched and its solution / ensemble forms) against the NumPy
+reference of drg_cases.py (oracle rates, math.fsum for every sum).
+
+Bound (derived, not measured), per (edge, state), eps = 2^-53:
+  a rate              q is two products on either side: |q_got - q_ref| <= 4 eps |q|; the temperature form adds
+                      (2 |Ea / (R T)| + 16) eps |q| (the device-side Arrhenius law, as in test_gpu_flux.py)
+  a term              t = |nu| |q_f - q_r|: the rates' errors, one subtraction and one product on either side:
+                      dt <= |nu| ((6 eps + ex_f) |q_f| + (6 eps + ex_r) |q_r|)
+  a sum of n terms    (non-negative, any order):  dS <= sum of the dt + n eps S
+  the quotient        |r_got - r_ref| <= (dnum + r_ref dden) / den + 2 eps
+  the maximum         |coef_got - coef_ref| <= the largest per-state bound
+Where den_ref is 0 and every rate behind it is exactly 0 the device's den is 0 too and the bound is 0; where den is pure
+cancellation the bound is vacuous. test_drg_host.py checks on the CPU that at most 1 % of the (edge, state) entries of the
+synthetic cases have a bound above 1e-9; the tests here repeat that check on what they compare."""
+import numpy as np
+import pytest
+
+import drg_cases as dc
+from kinetica_jl_amd import capi
+
+pytestmark = pytest.mark.gpu
+
+_handles = {}
+
+
+def handle(name):
+    if name not in _handles:
+        _handles[name] = capi.HipNetwork.from_flat(dc.synth_case(name).net)
+    return _handles[name]
+
+
+def device(name, mode, pairing, B, coef=None, lo=0):
+    """drg_batched of states lo .. B - 1 of a synthetic case."""
+    case, h = dc.synth_case(name), handle(name)
+    if mode == "shared":
+        h.set_rates(case.k0)
+    elif mode.startswith("T"):
+        h.set_arrhenius(case.Ea, case.A, k_max=1e12 if mode == "T_kmax" else None)
+    src = {k: (v[lo:] if k != "k" or mode == "per_state" else v) for k, v in case.source(mode, B).items()}
+    return h.drg_batched(case.U[lo:B], pairing=pairing, coef=coef, **src)
+
+
+def check(name, mode, pairing, B, got):
+    ref, bound, bounds = dc.synth_case(name).ref(mode, pairing, B)
+    frac = float(np.mean(bounds > 1e-9))
+    err = np.abs(got - ref)
+    print(f"{name} {mode} pairing={pairing} B={B}: edges {len(ref)}, max err {err.max():.3e}, max err/bound "
+          f"{np.max(err / np.maximum(bound, 1e-300)):.3f}, {100 * frac:.3f} % of the bounds above 1e-9")
+    assert frac <= 0.01
+    assert np.all(np.isfinite(got)) and np.all(got >= 0.0)
+    assert np.all(err <= bound)
+
+
+@pytest.mark.parametrize("pairing", [1, 0])
+@pytest.mark.parametrize("name", sorted(dc.hand_networks()))
+def test_hand_networks(name, pairing):
+    net, k, U, want = dc.hand_networks()[name]
+    h = capi.HipNetwork.from_flat(net)
+    h.set_rates(k)
+    rowptr, colidx = h.drg_pattern(pairing)
+    edges = [(a, int(b)) for a in range(net.n_species) for b in colidx[rowptr[a]:rowptr[a + 1]]]
+    assert edges == sorted(want[pairing])
+    coef = h.drg_batched(U, pairing=pairing)
+    assert coef.tolist() == [want[pairing][e] for e in edges]        # dyadic inputs: exact
+    zero = h.drg_batched(np.zeros((1, net.n_species)), pairing=pairing)
+    assert zero.tolist() == [0.0] * len(edges)                       # den = 0 everywhere: exactly 0.0, never NaN
+    h.close()
+
+
+def test_row_classes_of_the_case_list():
+    """The cases below reach the short, the medium and the long rows of both gather plans."""
+    seen = {k: 0 for k in capi.DRG_INFO[3:]}
+    nets = [dc.hub_network()] + [dc.synth_case(n).net for n in ("300x1500", "1000x5000", "300x1500_cut")]
+    for net in nets:
+        for pairing in (0, 1):
+            info = capi.drg_pattern_host(net, pairing)[2]
+            for k in seen:
+                seen[k] += info[k]
+    assert all(v > 0 for v in seen.values()), seen
+
+
+@pytest.mark.parametrize("pairing", [1, 0])
+def test_hub_network_long_and_medium_rows(pairing):
+    from oracle import oracle as orc
+    net = dc.hub_network()
+    rng = np.random.default_rng(4)
+    B = 7
+    U = dc.states(net.n_species, B, seed=3)
+    K = 10.0 ** rng.uniform(-2, 2, (B, net.n_reactions))
+    on = orc.OracleNetwork.from_flat(net)
+    g = dc.DrgRef(net, pairing)
+    ref, bound, _, _ = g.coefficients(np.stack([on.rates(K[b], U[b]) for b in range(B)]))
+    h = capi.HipNetwork.from_flat(net)
+    got = h.drg_batched(U, k=K, pairing=pairing)
+    h.close()
+    assert g.info()["den_long"] == 2 and g.info()["edge_long"] == 2 and g.info()["den_medium"] >= 2 and g.info()["edge_medium"] >= 2
+    assert np.all(np.abs(got - ref) <= bound)
+    # every record of A runs through B: the long edge is 1 to rounding
+    e = g.rowptr[0] + list(g.colidx[g.rowptr[0]:g.rowptr[1]]).index(1)
+    assert abs(got[e] - 1.0) <= bound[e]
+
+
+@pytest.mark.parametrize("pairing", [1, 0])
+@pytest.mark.parametrize("B", [1, 7, 130])
+def test_300x1500_matches_reference(B, pairing):
+    check("300x1500", "per_state", pairing, B, device("300x1500", "per_state", pairing, B))
+
+
+@pytest.mark.parametrize("pairing", [1, 0])
+@pytest.mark.parametrize("mode", dc.MODES)
+def test_every_rate_constant_source(mode, pairing):
+    check("300x1500", mode, pairing, 7, device("300x1500", mode, pairing, 7))
+
+
+@pytest.mark.parametrize("pairing", [1, 0])
+def test_1000x5000_matches_reference(pairing):
+    check("1000x5000", "per_state", pairing, 7, device("1000x5000", "per_state", pairing, 7))
+
+
+@pytest.mark.parametrize("pairing", [1, 0])
+@pytest.mark.parametrize("mode", ["per_state", "T_kmax"])
+def test_post_cutoff_odd_reaction_count(mode, pairing):
+    case = dc.synth_case("300x1500_cut")
+    assert case.net.n_reactions % 2 == 1
+    if pairing:
+        recs = dc.records(case.net, 1)
+        assert any(kr < 0 for _, kr, _, _ in recs) and any(kr >= 0 for _, kr, _, _ in recs)
+    check("300x1500_cut", mode, pairing, 7, device("300x1500_cut", mode, pairing, 7))
+
+
+@pytest.mark.parametrize("mode", ["per_state", "k_row", "T"])
+def test_maximum_crosses_blocks_of_three_states(mode, monkeypatch):
+    whole = device("300x1500", mode, 1, 7)
+    monkeypatch.setenv("KIN_DRG_BLOCK_STATES", "3")
+    blocks = device("300x1500", mode, 1, 7)
+    check("300x1500", mode, 1, 7, blocks)
+    assert np.array_equal(blocks, whole)
+
+
+@pytest.mark.parametrize("pairing", [1, 0])
+def test_accumulate_folds_two_halves_bit_for_bit(pairing):
+    whole = device("300x1500", "per_state", pairing, 130)
+    first = device("300x1500", "per_state", pairing, 60)
+    both = device("300x1500", "per_state", pairing, 130, coef=first, lo=60)
+    assert np.array_equal(both, whole)
+    assert np.array_equal(device("300x1500", "per_state", pairing, 130), whole)       # two identical calls
+    # accumulating over no states leaves coef alone; without accumulation no states give zeros
+    h, n = handle("300x1500"), dc.synth_case("300x1500").net.n_species
+    assert np.array_equal(h.drg_batched(np.empty((0, n)), k=np.empty((0, 1500)), pairing=pairing, coef=whole), whole)
+    assert np.all(h.drg_batched(np.empty((0, n)), k=np.empty((0, 1500)), pairing=pairing) == 0.0)
+    # values above every ratio survive
+    big = np.full(len(whole), 2.0)
+    assert np.array_equal(device("300x1500", "per_state", pairing, 7, coef=big), big)
+
+
+def test_device_pointers_equal_host_arrays():
+    import torch
+    case, h, B = dc.synth_case("1000x5000"), handle("1000x5000"), 7
+    want = device("1000x5000", "per_state", 1, B)
+    dev = "cuda:0"
+    d_u, d_k = (torch.tensor(x, dtype=torch.float64, device=dev) for x in (case.U[:B], case.K[:B]))
+    d_c = torch.full((len(want),), float("nan"), dtype=torch.float64, device=dev)
+    torch.cuda.synchronize()      # torch's fills run on torch's stream, the library on the handle's own
+    h.drg_batched_dev(B, d_u.data_ptr(), d_c.data_ptr(), d_k=d_k.data_ptr(), stream=torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    assert np.array_equal(d_c.cpu().numpy(), want)
+    h.drg_batched_dev(3, d_u.data_ptr(), d_c.data_ptr(), d_k=d_k.data_ptr(), accumulate=True, stream=torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    assert np.array_equal(d_c.cpu().numpy(), want)
+
+
+def _pars(t1, chunks):
+    return capi.KinParams(tspan0=0.0, tspan1=t1, abstol=1e-10, reltol=1e-8, adaptive_tols=1, update_tols=0, solve_chunks=1 if chunks else 0,
+                          ban_negatives=0, solve_chunkstep=t1 / max(chunks, 1), maxiters=100000, save_interval=-1.0)
+
+
+@pytest.mark.parametrize("pairing", [1, 0])
+def test_solution_and_ensemble_forms_equal_the_batched_call(pairing):
+    net, Ea, A = dc.synth(300, 1500)
+    case = dc.synth_case("300x1500")
+    h = capi.HipNetwork.from_flat(net)
+    u0 = np.zeros(300); u0[0] = 1.0
+    h.set_rates(case.k0)
+    t, us, rc, st, status = h.solve(_pars(2e-3, 2), u0)
+    assert rc == 0 and len(t) >= 3
+    want = h.drg_batched(us, pairing=pairing)
+    assert np.any(want > 0)
+    assert np.array_equal(h.solution_drg(pairing=pairing), want)
+    krow = np.zeros(len(t), np.int64)
+    assert np.array_equal(h.solution_drg(k=case.k0[None, :], k_row=krow, pairing=pairing), want)
+    assert np.array_equal(h.solution_drg(pairing=pairing, coef=want), want)
+    # an ensemble of three members with their own rate constants; rows past n_saved are zeros and take no part
+    K = 3
+    k = case.K[:K]
+    u0s = np.repeat(u0[None, :], K, axis=0)
+    res = h.solve_ensemble(_pars(2e-3, 2), u0s, k=k)
+    Ke, rows, n, n_saved = h.ensemble_size()
+    assert Ke == K and np.all(n_saved >= 2)
+    us_e = np.asarray(res[1]).reshape(K, -1, n)
+    k_row = np.repeat(np.arange(K, dtype=np.int64)[:, None], rows, axis=1)
+    k_row_junk = k_row.copy()
+    for m in range(K):
+        k_row_junk[m, n_saved[m]:] = 10 ** 9          # keys of rows that do not exist are ignored
+    got = h.ensemble_drg(k=k, k_row=k_row_junk, pairing=pairing)
+    flat = np.concatenate([us_e[m, :n_saved[m]] for m in range(K)])
+    flat_row = np.concatenate([np.full(n_saved[m], m, np.int64) for m in range(K)])
+    assert np.array_equal(got, h.drg_batched(flat, k=k, k_row=flat_row, pairing=pairing))
+    with pytest.raises(capi.KineticaHipError) as e:
+        k_row_bad = k_row.copy(); k_row_bad[1, 0] = K
+        h.ensemble_drg(k=k, k_row=k_row_bad, pairing=pairing)
+    assert e.value.code == capi.KIN_ERR_INVALID_ARG
+    h.close()
+
+
+def test_error_statuses():
+    from kinetica_jl_amd.synth import synthetic_crn
+    net, Ea, A = synthetic_crn(50, 200, seed=3)
+    h = capi.HipNetwork.from_flat(net)
+    U = np.ones((4, 50)); K = np.ones((4, 200)); T = np.full(4, 800.0)
+
+    def code(fn):
+        with pytest.raises(capi.KineticaHipError) as e:
+            fn()
+        return e.value.code
+
+    INV, STATE = capi.KIN_ERR_INVALID_ARG, capi.KIN_ERR_STATE
+    assert code(lambda: h.drg_batched(U)) == STATE                                        # no rates at all
+    assert code(lambda: h.drg_batched(U, T=T)) == STATE                                   # T without Arrhenius parameters
+    assert code(lambda: h.solution_drg(k=K[:1], k_row=np.zeros(0, np.int64))) == STATE    # no stored solution
+    assert code(lambda: h.ensemble_drg()) == STATE                                        # no stored ensemble
+    h.set_arrhenius(Ea, A)
+    assert code(lambda: h.drg_batched(U, k=K, T=T)) == INV                                # both k and T
+    assert code(lambda: h.drg_batched(U, k_row=np.zeros(4, np.int64))) == INV             # k_row without a k source
+    assert code(lambda: h.drg_batched(U, k=K, k_row=np.array([0, 1, 4, 2]))) == INV       # row index out of range
+    assert code(lambda: h.drg_batched(U, k=K[:3])) == INV                                 # k_row == NULL needs n_k_rows == B
+    L = capi.lib()
+    assert L.kin_drg_batched(h.handle, 1, 4, capi._pd(U), capi._pd(K), 4, None, None, 0, None) == INV          # null output
+    assert L.kin_drg_batched_dev(h.handle, 1, -1, None, None, None, None, 0, None, None) == INV               # B < 0
+    h.close()

@@ -508,6 +508,62 @@ int kin_solution_drg(kin_network* h, int pairing, const double* k, int64_t n_k_r
 int kin_ensemble_drg(kin_network* h, int pairing, const double* k, int64_t n_k_rows, const int64_t* k_row /* [K*n_rows] */,
                      const double* T_rows /* [K*n_rows] */, int accumulate, double* coef /* [edges] */);
 
+/* ---- DRG with error propagation (DRGEP, Pepiot-Desjardins & Pitsch 2008): one importance per species ------------------- */
+/* Rates q_r, records, pairing, nu_A and S are exactly those of the "directed relation graph" block above.
+ * With pairing, w = q_kf - q_kr; without pairing, w = q_r.
+ *
+ * For one state:
+ *
+ *   P_A   = sum over records with nu_A != 0 of max( nu_A w, 0)
+ *   C_A   = sum over records with nu_A != 0 of max(-nu_A w, 0)
+ *   den_A = max(P_A, C_A)
+ *   s_AB  = sum over records with nu_A != 0, B in S, B != A of nu_A w          (signed)
+ *   r_AB  = min(1, |s_AB| / den_A), exactly 0.0 where den_A == 0
+ *   R_t   = 1 for every target t
+ *   R_B   = max over edges (A, B) of fl(R_A * r_AB), iterated to the fixed point (R_B = 0 if unreachable)
+ *
+ * Over the states, importance_B is the exact maximum over the counted states of R_B.
+ *
+ * The edge set and its CSR order are those of kin_drg_pattern(pairing); no new pattern is defined.
+ *
+ * Floating-point multiplication by a number in [0, 1] is monotone.
+ * Hence the fixed point is unique: R_B is the maximum over paths of the left-to-right product along the path.
+ * It does not depend on relaxation order, on Jacobi versus in-place updates, or on the number of rounds beyond convergence.
+ * Given r, R is therefore bit-identical to any correct CPU search doing the same multiplications.
+ *
+ * The sums of r are formed in the fixed order of the DRG pass; the search runs per state on that state's r, one workgroup
+ * per state, at most n_species rounds (rounds counts the last one, which changes nothing). States are taken in blocks as in
+ * the DRG pass (no per-state array of a block above 256 MB; KIN_DRG_BLOCK_STATES=n); the result does not depend on the
+ * blocks, nor on where the search keeps R (LDS up to 4080 species, else global memory; KIN_DRGEP_LDS_SPECIES=n forces the
+ * global form above n species; KIN_DRGEP_STAGES=1 or 2 ends every block after that stage and leaves importance alone - a knob
+ * for timing the stages, never for results). accumulate != 0: the current contents of importance take part in the maximum. targets:
+ * n_targets >= 1 species ids (index_base as given; the device entry: 0-based int64 on the device, ids outside [0, N) are
+ * passed over there), duplicates allowed; a target outside [0, N) or n_targets < 1: KIN_ERR_INVALID_ARG. Rate constants
+ * and statuses are exactly kin_flux_batched[_dev]'s and kin_drg_batched's; B == 0 writes zeros, or leaves importance alone
+ * when accumulating. For finite inputs every output is finite and in [0, 1], and a target's importance is exactly 1.0
+ * whenever at least one state counts. Added under KIN_ABI_VERSION 6: look the symbols up before calling them. */
+/* Device pointers; only enqueues on `stream` (NULL: the handle's) once the workspace has its size. */
+int kin_drgep_batched_dev(kin_network* h, int pairing, int64_t B, const double* d_u, const double* d_k, const int64_t* d_k_row,
+                          const double* d_T, const int64_t* d_targets, int64_t n_targets, int accumulate,
+                          double* d_importance /* [N] */, void* stream);
+/* Host arrays. The optional outputs show every stage: r_out[b][e] the coefficients, R_out[b][i] the per-state importances,
+ * rounds_out[b] the rounds of the search. */
+int kin_drgep_batched(kin_network* h, int pairing, int64_t B, const double* u, const double* k, int64_t n_k_rows, const int64_t* k_row,
+                      const double* T, const int64_t* targets, int64_t n_targets, int index_base, int accumulate,
+                      double* importance /* [N] */, double* r_out /* [B][edges] or NULL */, double* R_out /* [B][N] or NULL */,
+                      int32_t* rounds_out /* [B] or NULL */);
+/* The path stage alone on the caller's coefficients r[B][edges] (CSR order of kin_drg_pattern(pairing)).
+ * KIN_ERR_INVALID_ARG for an r outside [0, 1] or non-finite. */
+int kin_drgep_paths(kin_network* h, int pairing, int64_t B, const double* r, const int64_t* targets, int64_t n_targets, int index_base,
+                    int accumulate, double* importance /* [N] */, double* R_out /* [B][N] or NULL */, int32_t* rounds_out /* [B] or NULL */);
+/* Over the saved states of the last kin_solve / over the stored ensemble, read where they live: arguments and statuses of
+ * kin_solution_drg / kin_ensemble_drg, plus the targets. Rows past n_saved[m] take no part. */
+int kin_solution_drgep(kin_network* h, int pairing, const double* k, int64_t n_k_rows, const int64_t* k_row, const double* T_rows,
+                       const int64_t* targets, int64_t n_targets, int index_base, int accumulate, double* importance /* [N] */);
+int kin_ensemble_drgep(kin_network* h, int pairing, const double* k, int64_t n_k_rows, const int64_t* k_row /* [K*n_rows] */,
+                       const double* T_rows /* [K*n_rows] */, const int64_t* targets, int64_t n_targets, int index_base, int accumulate,
+                       double* importance /* [N] */);
+
 /* ---- device / build information ------------------------------------------------------- */
 int kin_device_count(int* n);
 /* Selects the device for handles created afterwards by this thread; a handle remembers the device it was created on
@@ -521,7 +577,7 @@ const char* kin_version(void);
  * kin_lu_analyze_host - structs unchanged; 5: + kin_rhs_batched_klib_dev - structs unchanged; 6: + kin_solve_ensemble_continuous -
  * structs unchanged; kin_solve_ensemble_discrete, kin_resident_probe, kin_newton_probe, kin_step_probe, the flux pass (kin_flux_*, kin_solution_flux) and
  * kin_ensemble_size / _max / _dot / _flux and the directed relation graph (kin_drg_*, kin_solution_drg, kin_ensemble_drg) came
- * later under 6, found by symbol lookup). */
+ * later under 6, found by symbol lookup; so did DRGEP: kin_drgep_*, kin_solution_drgep, kin_ensemble_drgep). */
 #define KIN_ABI_VERSION 6
 int kin_abi_version(void);
 int64_t kin_struct_size(int which); /* 0: sizeof(kin_params), 1: sizeof(kin_stats), else -1 */

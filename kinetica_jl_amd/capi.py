@@ -34,7 +34,10 @@ SYMBOLS = [
     "kin_flux_batched", "kin_flux_batched_dev", "kin_solution_flux",
     "kin_flux_segmented", "kin_flux_segmented_dev", "kin_ensemble_size", "kin_ensemble_max", "kin_ensemble_dot", "kin_ensemble_flux",
     "kin_drg_pattern_host", "kin_drg_pattern", "kin_drg_batched", "kin_drg_batched_dev", "kin_solution_drg", "kin_ensemble_drg",
+    "kin_drgep_batched", "kin_drgep_batched_dev", "kin_drgep_paths", "kin_solution_drgep", "kin_ensemble_drgep",
 ]
+# in-degree classes of the DRGEP path search (drg.hpp: IN_SHORT_MAX, IN_WAVE_MAX): a lane, a wavefront, the workgroup
+DRGEP_IN_SHORT_MAX, DRGEP_IN_WAVE_MAX = 32, 256
 ABI_VERSION = 6   # include/kinetica_hip.h: KIN_ABI_VERSION this binding was written against
 
 
@@ -154,6 +157,13 @@ def lib():
             L.kin_drg_batched_dev.argtypes = [c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]
             L.kin_solution_drg.argtypes = [c_void_p, c_int, PD, c_int64, P64, PD, c_int, PD]
             L.kin_ensemble_drg.argtypes = [c_void_p, c_int, PD, c_int64, P64, PD, c_int, PD]
+        if hasattr(L, "kin_drgep_batched"):   # (also under ABI 6: DRG with error propagation)
+            P32 = POINTER(c_int32)
+            L.kin_drgep_batched_dev.argtypes = [c_void_p, c_int, c_int64] + [c_void_p] * 5 + [c_int64, c_int, c_void_p, c_void_p]
+            L.kin_drgep_batched.argtypes = [c_void_p, c_int, c_int64, PD, PD, c_int64, P64, PD, P64, c_int64, c_int, c_int, PD, PD, PD, P32]
+            L.kin_drgep_paths.argtypes = [c_void_p, c_int, c_int64, PD, P64, c_int64, c_int, c_int, PD, PD, P32]
+            L.kin_solution_drgep.argtypes = [c_void_p, c_int, PD, c_int64, P64, PD, P64, c_int64, c_int, c_int, PD]
+            L.kin_ensemble_drgep.argtypes = [c_void_p, c_int, PD, c_int64, P64, PD, P64, c_int64, c_int, c_int, PD]
         L.kin_solve_ensemble.argtypes = [c_void_p, POINTER(KinParams), c_int64, PD, PD, PD, PD, PD, PD, c_int64, P64, PD, PD, P64,
                                          POINTER(c_int32), POINTER(KinStats)]
         L.kin_integrator_init.argtypes = [c_void_p, POINTER(KinParams), PD, PD, PD, PD, c_int64]
@@ -533,6 +543,82 @@ class HipNetwork:
         self._chk(lib().kin_ensemble_drg(self._h, int(bool(pairing)), _pd(k), n_rows, None if k_row is None else _p64(k_row),
                                          _pd(T_rows), acc, _pd(out)))
         return out[:nnz]
+
+    # --- DRG with error propagation -----------------------------------------------------------
+    def _drgep_io(self, targets, importance):
+        """(targets int64, n_targets, output buffer, accumulate): a fresh buffer, or a copy of `importance` that takes part."""
+        tg = np.ascontiguousarray(np.asarray(targets, dtype=np.int64).ravel())
+        out = np.zeros(max(self.n, 1))
+        if importance is None:
+            return tg, len(tg), out, 0
+        c = _f64(importance).ravel()
+        assert len(c) == self.n
+        out[:self.n] = c
+        return tg, len(tg), out, 1
+
+    def drgep_batched(self, u, targets, k=None, k_row=None, T=None, pairing=True, importance=None, stages=False):
+        """kin_drgep_batched on host arrays: importance[N] = max over the states u[B][N] of R_B, the largest product of the
+        direct-interaction coefficients r_AB along any path from a target (0-based ids) to B (include/kinetica_hip.h has the
+        definition). Rate constants of state b as in flux_batched. importance given: its values take part in the maximum (the
+        result is returned, the argument is left alone). stages=True: (importance, r[B][edges], R[B][N], rounds[B])."""
+        u = np.ascontiguousarray(np.atleast_2d(_f64(u)))
+        B = u.shape[0]
+        assert u.shape == (B, self.n)
+        k, n_rows, k_row, T, _ = self._flux_inputs(B, k, k_row, T, None)
+        tg, nt, out, acc = self._drgep_io(targets, importance)
+        r = R = rounds = None
+        if stages:
+            nnz = c_int64(0)
+            self._chk(lib().kin_drg_pattern(self._h, int(bool(pairing)), 0, ctypes.byref(nnz), None, None))
+            r, R, rounds = np.zeros((B, nnz.value)), np.zeros((B, self.n)), np.zeros(B, np.int32)
+        p32 = lambda a: None if a is None else a.ctypes.data_as(POINTER(c_int32))
+        self._chk(lib().kin_drgep_batched(self._h, int(bool(pairing)), B, _pd(u), _pd(k), n_rows, None if k_row is None else _p64(k_row),
+                                          _pd(T), _p64(tg), nt, 0, acc, _pd(out), _pd(r) if stages and r.size else None,
+                                          _pd(R) if stages and R.size else None, p32(rounds) if stages and B else None))
+        return (out[:self.n], r, R, rounds) if stages else out[:self.n]
+
+    def drgep_batched_dev(self, B, d_u, d_targets, n_targets, d_importance, d_k=0, d_k_row=0, d_T=0, pairing=True, accumulate=False,
+                          stream=0):
+        """kin_drgep_batched_dev: device pointers (ints; 0 = not given), u[B][N], k rows / k_row[B] (int64) / T[B],
+        targets[n_targets] (int64, 0-based), importance[N]. One stream per handle at a time."""
+        p = lambda x: c_void_p(x) if x else None
+        self._chk(lib().kin_drgep_batched_dev(self._h, int(bool(pairing)), int(B), p(d_u), p(d_k), p(d_k_row), p(d_T), p(d_targets),
+                                              int(n_targets), 1 if accumulate else 0, p(d_importance), p(stream)))
+
+    def drgep_paths(self, r, targets, pairing=True, importance=None, stages=False):
+        """kin_drgep_paths: the path search alone on the caller's coefficients r[B][edges] in [0, 1] (CSR order of drg_pattern).
+        stages=True: (importance, R[B][N], rounds[B])."""
+        nnz = c_int64(0)
+        self._chk(lib().kin_drg_pattern(self._h, int(bool(pairing)), 0, ctypes.byref(nnz), None, None))
+        r = np.ascontiguousarray(_f64(r)).reshape(-1, nnz.value) if nnz.value else np.zeros((len(r), 0))
+        B = r.shape[0]
+        tg, nt, out, acc = self._drgep_io(targets, importance)
+        R, rounds = np.zeros((B, self.n)), np.zeros(B, np.int32)
+        self._chk(lib().kin_drgep_paths(self._h, int(bool(pairing)), B, _pd(r) if r.size else None, _p64(tg), nt, 0, acc, _pd(out),
+                                        _pd(R) if stages and R.size else None,
+                                        rounds.ctypes.data_as(POINTER(c_int32)) if stages and B else None))
+        return (out[:self.n], R, rounds) if stages else out[:self.n]
+
+    def solution_drgep(self, targets, k=None, k_row=None, T_rows=None, pairing=True, importance=None):
+        """kin_solution_drgep: drgep_batched over the saved states of the last solve, read where they live on the device
+        (rate-constant sources as solution_flux)."""
+        n_saved = c_int64(0)
+        self._chk(lib().kin_solution_size(self._h, ctypes.byref(n_saved), None))
+        k, n_rows, k_row, T_rows, _ = self._flux_inputs(n_saved.value, k, k_row, T_rows, None)
+        tg, nt, out, acc = self._drgep_io(targets, importance)
+        self._chk(lib().kin_solution_drgep(self._h, int(bool(pairing)), _pd(k), n_rows, None if k_row is None else _p64(k_row),
+                                           _pd(T_rows), _p64(tg), nt, 0, acc, _pd(out)))
+        return out[:self.n]
+
+    def ensemble_drgep(self, targets, k=None, k_row=None, T_rows=None, pairing=True, importance=None):
+        """kin_ensemble_drgep: one importance vector over every saved row of every member of the stored ensemble (k_row / T_rows:
+        [K][n_rows], entries past a member's saved rows are ignored)."""
+        K, rows = self.ensemble_size()[:2]
+        k, n_rows, k_row, T_rows, _ = self._flux_inputs(K * rows, k, k_row, T_rows, None)
+        tg, nt, out, acc = self._drgep_io(targets, importance)
+        self._chk(lib().kin_ensemble_drgep(self._h, int(bool(pairing)), _pd(k), n_rows, None if k_row is None else _p64(k_row),
+                                           _pd(T_rows), _p64(tg), nt, 0, acc, _pd(out)))
+        return out[:self.n]
 
     # --- library order (tiled sweep) --------------------------------------------------------
     def lib_layout(self):

@@ -7,7 +7,7 @@ namespace kin {
 
 namespace {
 
-struct Contrib { int32_t A, B, kf, kr; float c; };
+struct Contrib { int32_t A, B, kf, kr; float c, s; };   // c = |nu_A|, s = nu_A
 
 // the plan's coefficients by payload slot (ELL slots first, the medium and long rows' payload behind them)
 void place_coefs(const SegPlanHost& p, const std::vector<int32_t>& slot, const std::vector<float>& c, std::vector<float>& ell_c,
@@ -53,8 +53,8 @@ DrgTables build_drg_tables(const NetworkHost& h, int pairing, bool with_plans) {
       if (A < 0) continue;
       const int nu = (int)(int8_t)((uint32_t)h.slot_co[kf] >> (8 * j));
       const float c = (float)(nu < 0 ? -nu : nu);
-      den.push_back({A, -1, kf, kr, c});
-      for (int q = 0; q < nS; q++) if (S[q] != A) num.push_back({A, S[q], kf, kr, c});
+      den.push_back({A, -1, kf, kr, c, (float)nu});
+      for (int q = 0; q < nS; q++) if (S[q] != A) num.push_back({A, S[q], kf, kr, c, (float)nu});
     }
   }
   // (stable: the contributions of a row / an edge stay in record order)
@@ -81,15 +81,37 @@ DrgTables build_drg_tables(const NetworkHost& h, int pairing, bool with_plans) {
   classify(edge_ptr, t.edge_cls);
   if (!with_plans) return t;
   auto plan = [&](const std::vector<Contrib>& v, const std::vector<int32_t>& ptr, const int32_t* aux, SegPlanHost& out,
-                  std::vector<float>& ell_c, std::vector<float>& long_c) {
+                  std::vector<float>& ell_c, std::vector<float>& long_c, std::vector<float>& ell_s, std::vector<float>& long_s) {
     std::vector<int32_t> a(v.size()), b(v.size()), slot;
-    std::vector<float> c(v.size());
-    for (size_t e = 0; e < v.size(); e++) { a[e] = v[e].kf; b[e] = v[e].kr; c[e] = v[e].c; }
+    std::vector<float> c(v.size()), sg(v.size());
+    for (size_t e = 0; e < v.size(); e++) { a[e] = v[e].kf; b[e] = v[e].kr; c[e] = v[e].c; sg[e] = v[e].s; }
     out = build_seg_plan((int64_t)ptr.size() - 1, ptr.data(), nullptr, a.data(), b.data(), nullptr, false, aux, &slot);
     place_coefs(out, slot, c, ell_c, long_c);
+    place_coefs(out, slot, sg, ell_s, long_s);
   };
-  plan(den, den_ptr, nullptr, t.den_plan, t.den_ell_c, t.den_long_c);
-  plan(num, edge_ptr, edge_row.data(), t.edge_plan, t.edge_ell_c, t.edge_long_c);
+  plan(den, den_ptr, nullptr, t.den_plan, t.den_ell_c, t.den_long_c, t.den_ell_s, t.den_long_s);
+  plan(num, edge_ptr, edge_row.data(), t.edge_plan, t.edge_ell_c, t.edge_long_c, t.edge_ell_s, t.edge_long_s);
+  // the transpose of the pattern (a counting sort by head: the sources of a species stay ascending)
+  t.in_ptr.assign((size_t)N + 1, 0);
+  for (int64_t e = 0; e < t.E; e++) t.in_ptr[t.colidx[e] + 1]++;
+  for (int64_t i = 0; i < N; i++) t.in_ptr[i + 1] += t.in_ptr[i];
+  t.in_src.resize((size_t)t.E); t.in_edge.resize((size_t)t.E);
+  {
+    std::vector<int32_t> fill(t.in_ptr.begin(), t.in_ptr.end() - 1);
+    for (int64_t A = 0; A < N; A++)
+      for (int32_t e = t.rowptr[A]; e < t.rowptr[A + 1]; e++) {
+        const int32_t j = fill[t.colidx[e]]++;
+        t.in_src[j] = (int32_t)A; t.in_edge[j] = e;
+      }
+  }
+  auto in_class = [&](int64_t i) {
+    const int32_t len = t.in_ptr[i + 1] - t.in_ptr[i];
+    return len <= DrgTables::IN_SHORT_MAX ? 0 : (len <= DrgTables::IN_WAVE_MAX ? 1 : 2);
+  };
+  t.in_order.reserve((size_t)N);
+  for (int c = 0; c < 3; c++)
+    for (int64_t i = 0; i < N; i++)
+      if (in_class(i) == c) { t.in_order.push_back((int32_t)i); t.in_cls[c]++; }
   t.have_plans = true;
   return t;
 }

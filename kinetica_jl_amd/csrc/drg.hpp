@@ -9,6 +9,10 @@
 //   num_AB = sum over records with nu_A != 0, B in S, B != A     of |nu_A| |w|
 //   r_AB   = num_AB / den_A  (0 where den_A == 0),   coef_AB = max over the states of r_AB.
 // An edge (A, B) exists when some record contributes to num_AB: a CSR over A, columns sorted, no diagonal.
+//
+// DRG with error propagation (kin_drgep_*; definition: include/kinetica_hip.h) walks the same plans with the SIGNED
+// coefficients nu_A (stage 2: r[nb][E], no maximum over the states) and then searches, per state, the largest product of
+// r along any path from a target (drgep_kernels.hip) over the transpose of the pattern.
 #pragma once
 #include "common.hpp"
 #include "kernels.hpp"
@@ -27,6 +31,14 @@ struct DrgTables {
   bool have_plans = false;
   SegPlanHost den_plan, edge_plan;
   std::vector<float> den_ell_c, den_long_c, edge_ell_c, edge_long_c;
+  // DRGEP: nu_A with its sign in the same payload slots, and the incoming edges of every species (the transpose of the
+  // pattern: in_src[j] -> B over edge in_edge[j] for j in [in_ptr[B], in_ptr[B + 1]), sources ascending). in_order lists the
+  // species by in-degree class - <= IN_SHORT_MAX (a lane each), <= IN_WAVE_MAX (a wavefront), more (the workgroup) - in_cls
+  // counts them. (The gather plans' SHORT_MAX = 8 was measured against 32 for the lanes: profiles/drgep_ab.txt.)
+  static constexpr int IN_SHORT_MAX = 32, IN_WAVE_MAX = SegPlanHost::SEG_LEN;
+  std::vector<float> den_ell_s, den_long_s, edge_ell_s, edge_long_s;
+  std::vector<int32_t> in_ptr, in_src, in_edge, in_order;
+  int64_t in_cls[3] = {0, 0, 0};
 };
 // pairing != 0 needs the pair records (compile_network builds them for N < 65535): KinError(ERR_UNSUPPORTED) without
 DrgTables build_drg_tables(const NetworkHost& h, int pairing, bool with_plans);
@@ -40,6 +52,7 @@ struct DrgArgs {
   const int64_t* seg_n; int64_t L; // state b counts only when b % L < seg_n[b / L] (seg_n null: every state counts)
   double* den;                     // den[nb][N]: written by the denominator launch, read by the edge launch
   double* part;                    // part[Y][E]: the edge launch's maxima per slice of the states
+  double* r;                       // r[nb][E]: the signed edge launch's per-state coefficients (rows of states that do not count: untouched)
 };
 // slices of the states a launch is cut into so that the device is filled (depends on the plan, nb and n_cu only)
 int drg_slices(const SegPlanView& p, int64_t nb, int n_cu);
@@ -47,5 +60,27 @@ void launch_drg_den(const DrgArgs& a, int Y, hipStream_t s);
 void launch_drg_edges(const DrgArgs& a, int Y, hipStream_t s);
 // coef[e] = max(use_prev ? coef[e] : 0, part[0][e], ..., part[Y - 1][e])
 void launch_drg_max(int64_t E, int Y, const double* part, double* coef, int use_prev, hipStream_t s);
+// DRGEP stage 2 (ell_c / long_c: the SIGNED coefficients): den[bl][A] = max(P_A, C_A); r[bl][e] = min(1, |s_AB| / den_A)
+void launch_drgep_den(const DrgArgs& a, int Y, hipStream_t s);
+void launch_drgep_edges(const DrgArgs& a, int Y, hipStream_t s);
+
+// DRGEP path stage (drgep_kernels.hip): one workgroup per state relaxes R_B = max(R_B, R_A r_AB) over the incoming edges
+// until nothing changes (at most N rounds). R is double-buffered in LDS (in_lds: N <= DRGEP_LDS_SPECIES), else in work.
+struct DrgepPathArgs {
+  int N, E, nb, n_targets;
+  const int32_t *in_ptr, *in_src, *in_edge, *in_order;
+  int n_short, n_wave, n_long;     // in_order: the short species first, then the wavefront ones, then the long ones
+  const int64_t* targets;         // 0-based; one outside [0, N) is passed over
+  const double* r;                 // r[nb][E]
+  int64_t b0; const int64_t* seg_n; int64_t L;     // as DrgArgs: a state that does not count gets R = 0 and 0 rounds
+  double* R;                       // R[nb][N]
+  double* work;                    // work[nb][2][N] (global form only)
+  int32_t* rounds;                 // rounds[nb]
+};
+// 64 KB of LDS per workgroup, less the kernel's own few words: two buffers of N doubles fit up to this N
+constexpr int64_t DRGEP_LDS_SPECIES = ((64 << 10) - 256) / 16;
+void launch_drgep_paths(const DrgepPathArgs& a, bool in_lds, hipStream_t s);
+// imp[i] = max(use_prev ? imp[i] : 0, R[0][i], ..., R[nb - 1][i])
+void launch_drgep_max(int64_t N, int64_t nb, const double* R, double* imp, int use_prev, hipStream_t s);
 
 }  // namespace kin

@@ -5,8 +5,7 @@
 #include <algorithm>
 #include <cstdlib>
 
-#include "drg.hpp"
-#include "flux_api.hpp"
+#include "drg_api.hpp"
 #include "handle.hpp"
 
 using namespace kin;
@@ -17,7 +16,9 @@ void require(bool c, int code, const char* msg) {
   if (!c) throw KinError(code, msg);
 }
 
-constexpr size_t DRG_RATES_BYTES = (size_t)256 << 20;   // bound of the stage-1 workspace rates[nb][R]
+}  // namespace
+
+namespace kin {
 
 DrgTables& drg_host(kin_network* h, int pairing) {
   auto& m = h->drg[pairing ? 1 : 0];
@@ -37,6 +38,10 @@ kin_network::DrgMode& drg_dev(kin_network* h, int pairing, hipStream_t s) {
   }
   return m;
 }
+
+}  // namespace kin
+
+namespace {
 
 // The pass on device buffers. States b0, b0 + nb, ... are taken block by block: stage 1 (the flux sweep) writes the block's
 // rates, stage 2 its denominators and the maxima of the ratios, folded into d_coef. seg_n / L: see DrgArgs.
@@ -81,11 +86,66 @@ void drg_run(kin_network* h, int pairing, int64_t B, const double* d_u, const Fl
   }
 }
 
+}  // namespace
+
+namespace kin {
+
 void drg_check(kin_network* h, int64_t B, bool have_k, bool have_row, bool have_T, bool have_out) {
   flux_check(h, B, have_k, have_row, have_T, true);
   require(have_out, ERR_INVALID_ARG, "null output buffer");
   require(h->host.N < ((int64_t)1 << 31) / 2, ERR_UNSUPPORTED, "DRG pass: N beyond 32-bit offsets");
 }
+
+FluxSource drg_solution_source(kin_network* h, const double* k, int64_t n_k_rows, const int64_t* k_row, const double* T_rows,
+                               bool have_out, hipStream_t s) {
+  const int64_t B = h->n_saved, R = h->host.R;
+  const bool table = !k && k_row;    // rows of the device-resident rate table
+  drg_check(h, B, k != nullptr || table, k_row != nullptr, T_rows != nullptr, have_out);
+  require(B > 0, ERR_STATE, "no solution stored");
+  require(!table || h->table_rows > 0, ERR_STATE, "no rate table resident (kin_rate_table / kin_solve with a table first)");
+  if (k_row) flux_check_rows(k_row, B, table ? h->table_rows : n_k_rows);
+  else if (k) require(n_k_rows == B, ERR_INVALID_ARG, "k without k_row needs one row per saved state (n_k_rows == n_saved)");
+  if (k) h->f_k.upload(k, (size_t)n_k_rows * R, s);
+  if (k_row) h->f_krow.upload(k_row, (size_t)B, s);
+  if (T_rows) h->f_T.upload(T_rows, (size_t)B, s);
+  const double* ksrc = k ? h->f_k.p : (table ? h->table.p : nullptr);
+  return FluxSource{ksrc, R, k_row ? h->f_krow.p : nullptr, T_rows ? h->f_T.p : nullptr};
+}
+
+FluxSource drg_ensemble_source(kin_network* h, const double* k, int64_t n_k_rows, const int64_t* k_row, const double* T_rows,
+                               bool have_out, hipStream_t s) {
+  require(h->ens.valid(), ERR_STATE, "no ensemble stored (kin_solve_ensemble* first)");
+  const int64_t K = h->ens.K, cap = h->ens.cap, B = K * cap, R = h->host.R;
+  require(cap < ((int64_t)1 << 31) && K < ((int64_t)1 << 31) && B < ((int64_t)1 << 31), ERR_UNSUPPORTED,
+          "ensemble DRG pass: K n_rows beyond 32-bit offsets");
+  drg_check(h, B, k != nullptr, k_row != nullptr, T_rows != nullptr, have_out);
+  if (k && k_row) require(n_k_rows >= 1, ERR_INVALID_ARG, "k has no rows");
+  else if (k) require(n_k_rows == B, ERR_INVALID_ARG, "k without k_row needs one row per saved row (n_k_rows == K n_rows)");
+  // Stage 1 runs over every row of the record; the keys of the rows past a member's saved ones are ignored by contract, so
+  // they are replaced by harmless ones here (row 0, 1000 K) and stage 2 leaves those states out.
+  std::vector<int64_t> rows;
+  std::vector<double> Ts;
+  if (k_row) rows.assign(k_row, k_row + B);
+  if (T_rows) Ts.assign(T_rows, T_rows + B);
+  for (int64_t m = 0; m < K; m++) {
+    const int64_t n = h->ens.n_saved[m];
+    for (int64_t j = 0; j < cap; j++) {
+      const int64_t b = m * cap + j;
+      if (j < n) { if (k_row) require(rows[b] >= 0 && rows[b] < n_k_rows, ERR_INVALID_ARG, "k_row: row index out of range"); }
+      else { if (k_row) rows[b] = 0; if (T_rows) Ts[b] = 1000.0; }
+    }
+  }
+  h->ens_segn.upload(h->ens.n_saved, s);
+  if (k && n_k_rows > 0) h->f_k.upload(k, (size_t)n_k_rows * R, s);
+  if (k_row) h->f_krow.upload(rows, s);
+  if (T_rows) h->f_T.upload(Ts, s);
+  KIN_HIP(hipStreamSynchronize(s));      // (rows and Ts leave scope)
+  return FluxSource{k ? h->f_k.p : nullptr, R, k_row ? h->f_krow.p : nullptr, T_rows ? h->f_T.p : nullptr};
+}
+
+}  // namespace kin
+
+namespace {
 
 // host entries: coef staged through the handle's buffer (uploaded first when it takes part in the maximum)
 void drg_host_call(kin_network* h, int pairing, int64_t B, const double* d_u, const FluxSource& src, const int64_t* d_seg_n, int64_t L,
@@ -155,20 +215,9 @@ int kin_solution_drg(kin_network* h, int pairing, const double* k, int64_t n_k_r
                      int accumulate, double* coef) {
   if (!h) return KIN_ERR_INVALID_ARG;
   KIN_TRY(h)
-  const int64_t B = h->n_saved, R = h->host.R;
-  const bool table = !k && k_row;    // rows of the device-resident rate table
-  drg_check(h, B, k != nullptr || table, k_row != nullptr, T_rows != nullptr, coef != nullptr);
-  require(B > 0, ERR_STATE, "no solution stored");
-  require(!table || h->table_rows > 0, ERR_STATE, "no rate table resident (kin_rate_table / kin_solve with a table first)");
-  if (k_row) flux_check_rows(k_row, B, table ? h->table_rows : n_k_rows);
-  else if (k) require(n_k_rows == B, ERR_INVALID_ARG, "k without k_row needs one row per saved state (n_k_rows == n_saved)");
   hipStream_t s = h->stream;
-  if (k) h->f_k.upload(k, (size_t)n_k_rows * R, s);
-  if (k_row) h->f_krow.upload(k_row, (size_t)B, s);
-  if (T_rows) h->f_T.upload(T_rows, (size_t)B, s);
-  const double* ksrc = k ? h->f_k.p : (table ? h->table.p : nullptr);
-  drg_host_call(h, pairing, B, h->d_sol_u.p, FluxSource{ksrc, R, k_row ? h->f_krow.p : nullptr, T_rows ? h->f_T.p : nullptr}, nullptr, 0,
-                accumulate, coef, s);
+  const FluxSource src = drg_solution_source(h, k, n_k_rows, k_row, T_rows, coef != nullptr, s);
+  drg_host_call(h, pairing, h->n_saved, h->d_sol_u.p, src, nullptr, 0, accumulate, coef, s);
   KIN_CATCH(h)
 }
 
@@ -176,34 +225,9 @@ int kin_ensemble_drg(kin_network* h, int pairing, const double* k, int64_t n_k_r
                      int accumulate, double* coef) {
   if (!h) return KIN_ERR_INVALID_ARG;
   KIN_TRY(h)
-  require(h->ens.valid(), ERR_STATE, "no ensemble stored (kin_solve_ensemble* first)");
-  const int64_t K = h->ens.K, cap = h->ens.cap, B = K * cap, R = h->host.R;
-  require(cap < ((int64_t)1 << 31) && K < ((int64_t)1 << 31) && B < ((int64_t)1 << 31), ERR_UNSUPPORTED,
-          "ensemble DRG pass: K n_rows beyond 32-bit offsets");
-  drg_check(h, B, k != nullptr, k_row != nullptr, T_rows != nullptr, coef != nullptr);
-  if (k && k_row) require(n_k_rows >= 1, ERR_INVALID_ARG, "k has no rows");
-  else if (k) require(n_k_rows == B, ERR_INVALID_ARG, "k without k_row needs one row per saved row (n_k_rows == K n_rows)");
-  // Stage 1 runs over every row of the record; the keys of the rows past a member's saved ones are ignored by contract, so
-  // they are replaced by harmless ones here (row 0, 1000 K) and stage 2 leaves those states out.
-  std::vector<int64_t> rows;
-  std::vector<double> Ts;
-  if (k_row) rows.assign(k_row, k_row + B);
-  if (T_rows) Ts.assign(T_rows, T_rows + B);
-  for (int64_t m = 0; m < K; m++) {
-    const int64_t n = h->ens.n_saved[m];
-    for (int64_t j = 0; j < cap; j++) {
-      const int64_t b = m * cap + j;
-      if (j < n) { if (k_row) require(rows[b] >= 0 && rows[b] < n_k_rows, ERR_INVALID_ARG, "k_row: row index out of range"); }
-      else { if (k_row) rows[b] = 0; if (T_rows) Ts[b] = 1000.0; }
-    }
-  }
   hipStream_t s = h->stream;
-  h->ens_segn.upload(h->ens.n_saved, s);
-  if (k && n_k_rows > 0) h->f_k.upload(k, (size_t)n_k_rows * R, s);
-  if (k_row) h->f_krow.upload(rows, s);
-  if (T_rows) h->f_T.upload(Ts, s);
-  drg_host_call(h, pairing, B, h->ens.sol, FluxSource{k ? h->f_k.p : nullptr, R, k_row ? h->f_krow.p : nullptr, T_rows ? h->f_T.p : nullptr},
-                h->ens_segn.p, cap, accumulate, coef, s);
+  const FluxSource src = drg_ensemble_source(h, k, n_k_rows, k_row, T_rows, coef != nullptr, s);
+  drg_host_call(h, pairing, h->ens.K * h->ens.cap, h->ens.sol, src, h->ens_segn.p, h->ens.cap, accumulate, coef, s);
   KIN_CATCH(h)
 }
 

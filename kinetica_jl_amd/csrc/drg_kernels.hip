@@ -7,6 +7,9 @@
 // lane, a shuffle tree per wavefront, the four wavefronts in order), the maximum over the states is kept in a register
 // by the task that owns the edge and across slices of the states through part[Y][E] and drg_max_kernel: no atomics, the
 // result does not depend on how the states are cut into blocks or slices.
+// SIGNED = true is DRGEP's stage 2 on the same plans and in the same order of summation, with c = nu_A carrying its sign:
+// the denominator launch forms P = sum max(c w, 0) and C = sum max(-c w, 0) and writes den = max(P, C), the edge launch
+// forms s = sum c w and writes r[bl][e] = min(1, |s| / den) for every state that counts - no maximum over the states.
 #include "drg.hpp"
 
 #include "segsum_dev.hpp"
@@ -35,8 +38,47 @@ __device__ __forceinline__ double drg_terms(const double* __restrict__ rb, const
   return acc;
 }
 
-// EDGE = false: den[bl][dst] = row sum. EDGE = true: m = max over the slice's states of (row sum / den[bl][aux]), part[y][dst] = m.
+// The signed sums of one lane: EDGE the plain sum s of c (qa - qb) in p, else its positive and negative parts in p and n.
+struct DrgSigned { double p, n; };
+template <int NX, bool EDGE>
+__device__ __forceinline__ DrgSigned drg_terms_signed(const double* __restrict__ rb, const int32_t (&ia)[NX], const int32_t (&ib)[NX],
+                                                      const float (&c)[NX]) {
+  double qa[NX], qb[NX];
+#pragma unroll
+  for (int x = 0; x < NX; x++) {
+    const bool on = c[x] != 0.0f;
+    qa[x] = on ? rb[ia[x]] : 0.0;
+    qb[x] = (on && ib[x] >= 0) ? rb[ib[x]] : 0.0;
+  }
+  DrgSigned acc{0.0, 0.0};
+#pragma unroll
+  for (int x = 0; x < NX; x++) {
+    const double t = (double)c[x] * (qa[x] - qb[x]);
+    if (EDGE) acc.p += t;
+    else { acc.p += fmax(t, 0.0); acc.n += fmax(-t, 0.0); }
+  }
+  return acc;
+}
 template <bool EDGE>
+__device__ __forceinline__ DrgSigned wave_sum(DrgSigned v) {
+  v.p = wave_sum(v.p);
+  if (!EDGE) v.n = wave_sum(v.n);
+  return v;
+}
+// what a signed row stores for state bl: den = max(P, C), or r = min(1, |s| / den) (exactly 0.0 where den == 0)
+template <bool EDGE>
+__device__ __forceinline__ void drg_store_signed(const DrgArgs& a, int bl, int32_t dst, int32_t aux, const DrgSigned& v) {
+  if (EDGE) {
+    const double d = a.den[(size_t)bl * a.N + aux];
+    a.r[(size_t)bl * a.E + dst] = d > 0.0 ? fmin(1.0, fabs(v.p) / d) : 0.0;
+  } else {
+    a.den[(size_t)bl * a.N + dst] = fmax(v.p, v.n);
+  }
+}
+
+// EDGE = false: den[bl][dst] = row sum. EDGE = true: m = max over the slice's states of (row sum / den[bl][aux]), part[y][dst] = m.
+// SIGNED: see the head of the file (part and the maximum take no part).
+template <bool EDGE, bool SIGNED = false>
 __global__ __launch_bounds__(DRG_WG) void drg_gather_kernel(DrgArgs a) {
   const SegPlanView& p = a.p;
   const int tid = threadIdx.x, lane = tid & 63, Y = gridDim.y, y = blockIdx.y;
@@ -52,6 +94,7 @@ __global__ __launch_bounds__(DRG_WG) void drg_gather_kernel(DrgArgs a) {
   };
   if ((int)blockIdx.x < p.B) {        // a long row: the whole workgroup, its payload read again for every state
     __shared__ double sh[DRG_WAVES];
+    __shared__ double shn[SIGNED ? DRG_WAVES : 1];
     const int r = blockIdx.x;
     const int32_t e0 = p.blk_beg[r], e1 = p.blk_end[r], dst = p.blk_dst[r], aux = p.blk_aux[r];
     double m = 0.0;
@@ -59,6 +102,7 @@ __global__ __launch_bounds__(DRG_WG) void drg_gather_kernel(DrgArgs a) {
       if (!counts(bl)) continue;
       const double* rb = a.rates + (size_t)bl * R;
       double acc = 0.0;
+      DrgSigned sg{0.0, 0.0};
       for (int32_t base = e0; base < e1; base += DRG_WG * DRG_LONG_NX) {
         int32_t ia[DRG_LONG_NX], ib[DRG_LONG_NX]; float c[DRG_LONG_NX];
 #pragma unroll
@@ -67,7 +111,25 @@ __global__ __launch_bounds__(DRG_WG) void drg_gather_kernel(DrgArgs a) {
           const bool ok = e < e1;
           ia[x] = ok ? p.long_a[e] : 0; ib[x] = ok ? p.long_b[e] : -1; c[x] = ok ? a.long_c[e] : 0.0f;
         }
-        acc += drg_terms<DRG_LONG_NX>(rb, ia, ib, c);
+        if (SIGNED) {
+          const DrgSigned t = drg_terms_signed<DRG_LONG_NX, EDGE>(rb, ia, ib, c);
+          sg.p += t.p; sg.n += t.n;
+        } else {
+          acc += drg_terms<DRG_LONG_NX>(rb, ia, ib, c);
+        }
+      }
+      if (SIGNED) {
+        sg = wave_sum<EDGE>(sg);
+        if (lane == 0) { sh[tid >> 6] = sg.p; shn[tid >> 6] = sg.n; }
+        __syncthreads();
+        if (tid == 0) {
+          DrgSigned tot{0.0, 0.0};
+#pragma unroll
+          for (int w = 0; w < DRG_WAVES; w++) { tot.p += sh[w]; tot.n += shn[w]; }
+          drg_store_signed<EDGE>(a, bl, dst, aux, tot);
+        }
+        __syncthreads();
+        continue;
       }
       acc = wave_sum(acc);
       if (lane == 0) sh[tid >> 6] = acc;
@@ -80,7 +142,7 @@ __global__ __launch_bounds__(DRG_WG) void drg_gather_kernel(DrgArgs a) {
       }
       __syncthreads();     // sh is written again for the next state
     }
-    if (EDGE && tid == 0) a.part[(size_t)y * a.E + dst] = m;
+    if (EDGE && !SIGNED && tid == 0) a.part[(size_t)y * a.E + dst] = m;
     return;
   }
   const int task = ((int)blockIdx.x - p.B) * DRG_WAVES + (tid >> 6);
@@ -98,12 +160,17 @@ __global__ __launch_bounds__(DRG_WG) void drg_gather_kernel(DrgArgs a) {
     double m = 0.0;
     for (int bl = y; bl < nb; bl += Y) {
       if (!counts(bl)) continue;
+      if (SIGNED) {
+        const DrgSigned sg = drg_terms_signed<8, EDGE>(a.rates + (size_t)bl * R, ia, ib, c);
+        if (dst >= 0) drg_store_signed<EDGE>(a, bl, dst, aux, sg);
+        continue;
+      }
       const double acc = drg_terms<8>(a.rates + (size_t)bl * R, ia, ib, c);
       if (dst >= 0) {
         if (EDGE) m = fmax(m, ratio(bl, aux, acc)); else a.den[(size_t)bl * N + dst] = acc;
       }
     }
-    if (EDGE && dst >= 0) a.part[(size_t)y * a.E + dst] = m;
+    if (EDGE && !SIGNED && dst >= 0) a.part[(size_t)y * a.E + dst] = m;
   } else if (task < p.G + p.S) {      // a medium row: four entries per lane
     const int sidx = task - p.G;
     const int32_t e0 = p.seg_beg[sidx], e1 = p.seg_end[sidx], dst = p.seg_dst[sidx], aux = p.seg_aux[sidx];
@@ -118,12 +185,17 @@ __global__ __launch_bounds__(DRG_WG) void drg_gather_kernel(DrgArgs a) {
     double m = 0.0;
     for (int bl = y; bl < nb; bl += Y) {
       if (!counts(bl)) continue;
+      if (SIGNED) {
+        const DrgSigned sg = wave_sum<EDGE>(drg_terms_signed<4, EDGE>(a.rates + (size_t)bl * R, ia, ib, c));
+        if (lane == 0) drg_store_signed<EDGE>(a, bl, dst, aux, sg);
+        continue;
+      }
       const double acc = wave_sum(drg_terms<4>(a.rates + (size_t)bl * R, ia, ib, c));
       if (lane == 0) {
         if (EDGE) m = fmax(m, ratio(bl, aux, acc)); else a.den[(size_t)bl * N + dst] = acc;
       }
     }
-    if (EDGE && lane == 0) a.part[(size_t)y * a.E + dst] = m;
+    if (EDGE && !SIGNED && lane == 0) a.part[(size_t)y * a.E + dst] = m;
   }
 }
 
@@ -154,6 +226,18 @@ void launch_drg_den(const DrgArgs& a, int Y, hipStream_t s) {
 void launch_drg_edges(const DrgArgs& a, int Y, hipStream_t s) {
   if (drg_blocks(a.p) == 0 || a.nb == 0) return;
   hipLaunchKernelGGL((drg_gather_kernel<true>), dim3(drg_blocks(a.p), (unsigned)Y), dim3(DRG_WG), 0, s, a);
+  KIN_HIP(hipGetLastError());
+}
+
+void launch_drgep_den(const DrgArgs& a, int Y, hipStream_t s) {
+  if (drg_blocks(a.p) == 0 || a.nb == 0) return;
+  hipLaunchKernelGGL((drg_gather_kernel<false, true>), dim3(drg_blocks(a.p), (unsigned)Y), dim3(DRG_WG), 0, s, a);
+  KIN_HIP(hipGetLastError());
+}
+
+void launch_drgep_edges(const DrgArgs& a, int Y, hipStream_t s) {
+  if (drg_blocks(a.p) == 0 || a.nb == 0) return;
+  hipLaunchKernelGGL((drg_gather_kernel<true, true>), dim3(drg_blocks(a.p), (unsigned)Y), dim3(DRG_WG), 0, s, a);
   KIN_HIP(hipGetLastError());
 }
 

@@ -72,8 +72,17 @@ struct kin_network {
     bool dev_ready = false;
     kin::SegPlanDev den_plan, edge_plan;
     kin::DevBuf<float> den_ell_c, den_long_c, edge_ell_c, edge_long_c;
+    // DRGEP (drgep_api.cpp): the signed coefficients and the transposed pattern, uploaded at the first DRGEP call
+    bool ep_ready = false;
+    kin::DevBuf<float> den_ell_s, den_long_s, edge_ell_s, edge_long_s;
+    kin::DevBuf<int32_t> in_ptr, in_src, in_edge, in_order;
   } drg[2];
   kin::DevBuf<double> drg_rates, drg_den, drg_part, drg_coef;
+  // DRGEP: the block's coefficients r[nb][E], importances R[nb][N], the global form's work[nb][2][N], rounds[nb]; the
+  // targets and the staging buffer of the host entries' importance
+  kin::DevBuf<double> drgep_r, drgep_R, drgep_work, drgep_imp;
+  kin::DevBuf<int32_t> drgep_rounds;
+  kin::DevBuf<int64_t> drgep_targets;
 
   // tiled sweep in library order (tiled.hpp, tiled_api.cpp): built at the first call that needs it
   kin::TiledHost tiled;

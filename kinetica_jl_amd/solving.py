@@ -1045,6 +1045,41 @@ def drg_select(rowptr, colidx, coef, targets, eps):
     return np.flatnonzero(keep).astype(np.int64)
 
 
+def drgep_importance(out, calculator, targets, pairing=True, importance=None):
+    """importance[N] of DRG with error propagation (Pepiot-Desjardins & Pitsch) over the saved states of a solve: R_B = the
+    largest product, over any path from a target (names or 0-based ids) to B, of the signed net direct-interaction
+    coefficients r_AB = |sum nu_A w| / max(P_A, C_A) of the state, maximised over the saved states (include/kinetica_hip.h has
+    the definition; pairing as in drg_coefficients). `importance`: the result of an earlier call, which takes part in the
+    maximum (several solves folded into one ranking). `calculator` and the rate constants of every saved state are chosen as
+    reaction_fluxes chooses them. One device pass (kin_drgep_batched) over sol.u."""
+    sd, rd = out.sd, out.rd
+    setup_network(sd, rd, calculator)
+    t = np.asarray(out.sol.t, dtype=float)
+    u = np.ascontiguousarray(np.asarray(out.sol.u, dtype=float).reshape(len(t), sd.n))
+    tg = [sd.toInt[x] - 1 if isinstance(x, str) else int(x) for x in targets]
+    src = saved_state_rate_source(out, calculator, t)
+    h = capi.HipNetwork(*rd.flat(sd.n), index_base=1)
+    try:
+        if "T" in src:
+            h.set_arrhenius(calculator.Ea, calculator.A, calculator.k_max, calculator.t_mult)
+        imp = h.drgep_batched(u, tg, pairing=pairing, importance=importance, **src)
+    finally:
+        h.close()
+    return imp
+
+
+def drgep_select(importance, targets, eps):
+    """Species (0-based, sorted) with importance >= eps, the targets always among them. Pure NumPy."""
+    importance = np.asarray(importance, dtype=float)
+    n = len(importance)
+    tg = np.unique(np.asarray(list(targets), dtype=np.int64))
+    if len(tg) and (tg[0] < 0 or tg[-1] >= n):
+        raise ValueError("target species id out of range")
+    keep = importance >= float(eps)
+    keep[tg] = True
+    return np.flatnonzero(keep).astype(np.int64)
+
+
 @dataclass
 class DRGReduction:
     """Result of reduce_network: the kept species / reactions (0-based positions in the full sd / rd, ascending), the
@@ -1059,6 +1094,7 @@ class DRGReduction:
     coef: np.ndarray
     targets: np.ndarray
     eps: float
+    importance: Optional[np.ndarray] = None       # method="drgep": the importance the selection was made on
 
     def map_u0(self, u0):
         """A u0 specification of the full network (ODESimulationParams.u0: dict name -> concentration, or a vector over the
@@ -1079,18 +1115,32 @@ class DRGReduction:
         return out
 
 
-def reduce_network(out, calculator, targets, eps, pairing=True, coef=None):
+def reduce_network(out, calculator, targets, eps, pairing=True, coef=None, method="drg", importance=None):
     """DRG reduction of the network of a solve: keeps the species reachable from `targets` (names or 0-based ids) over the
     edges with coefficient >= eps - the species non-zero in the first saved state always count as targets - and the
     reactions ALL of whose species, on both sides, are kept. `coef`: (rowptr, colidx, coef) of an earlier drg_coefficients
     call (or several solves folded into one graph), else computed here. `calculator` is left alone; the DRGReduction
-    carries a copy spliced to the reduced rd, ready for solve_network / solve_network_ensemble."""
+    carries a copy spliced to the reduced rd, ready for solve_network / solve_network_ensemble.
+
+    method="drgep" keeps instead the species whose DRGEP importance (drgep_importance, with the same targets) is >= eps;
+    `importance`: the vector of an earlier drgep_importance call made with these targets (or several solves folded into one),
+    else computed here. The reaction rule and the splicing are the same; the result carries `importance` and no graph."""
+    if method not in ("drg", "drgep"):
+        raise ValueError('method must be "drg" or "drgep"')
     sd, rd = out.sd, out.rd
-    rowptr, colidx, cf = drg_coefficients(out, calculator, pairing) if coef is None else coef
     tg = [sd.toInt[x] - 1 if isinstance(x, str) else int(x) for x in targets]
     u_first = np.asarray(out.sol.u, dtype=float).reshape(len(out.sol.t), sd.n)[0]
     tg = np.unique(np.concatenate([np.asarray(tg, dtype=np.int64), np.flatnonzero(u_first != 0)]))
-    kept_sp = drg_select(rowptr, colidx, cf, tg, eps)
+    imp = None
+    if method == "drgep":
+        imp = np.asarray(drgep_importance(out, calculator, tg, pairing) if importance is None else importance, dtype=float)
+        if len(imp) != sd.n:
+            raise ValueError("importance must have one entry per species")
+        rowptr = colidx = cf = np.zeros(0)
+        kept_sp = drgep_select(imp, tg, eps)
+    else:
+        rowptr, colidx, cf = drg_coefficients(out, calculator, pairing) if coef is None else coef
+        kept_sp = drg_select(rowptr, colidx, cf, tg, eps)
     sd_new, new_id = sd.subset(kept_sp + 1)
     rd_new, kept_rx = rd.subset_species(new_id)
     kill = np.setdiff1d(np.arange(rd.nr), np.asarray(kept_rx, dtype=np.int64))
@@ -1098,7 +1148,7 @@ def reduce_network(out, calculator, targets, eps, pairing=True, coef=None):
     if len(kill):
         calc.splice(kill)
     return DRGReduction(kept_sp, np.asarray(kept_rx, dtype=np.int64), sd_new, rd_new, calc, np.asarray(rowptr), np.asarray(colidx),
-                        np.asarray(cf), tg, float(eps))
+                        np.asarray(cf), tg, float(eps), imp)
 
 
 # ---- the consumer of a level's solve (src/exploration/explore_utils.jl:338-406) ---------------------------

@@ -430,6 +430,40 @@ enum { KIN_STEP_INIT_D = 0, KIN_STEP_PREDICT, KIN_STEP_ACCEPT, KIN_STEP_ACCEPT_P
 int kin_step_probe(kin_network* h, int32_t path, int32_t op, int64_t n, int64_t K, int64_t n_entries, const int32_t* iarg,
                    const double* darg, const int32_t* xloc, double* state, double* ctrl, double* pub, int64_t* info);
 
+/* Diagnostic: the right-hand side, the Jacobian values or the Newton residual of a BDF step, formed ONCE on the caller's states
+ * through the integrators' own launchers and kernels, every value of the output returned (and what must not be touched, so that
+ * can be checked too).
+ * path 0: the single-state kernels as kin_rhs / kin_jac_values and the host-driven corrector launch them, with the handle's rate
+ *   constants (k must be NULL), K = n_entries = 1. T > 0: that temperature is made pending first, so the evaluation runs the
+ *   kernels that form k from it on the spot and store it (kin_get_rates reads it afterwards); needs kin_set_arrhenius.
+ * path 2: the lockstep ensemble's batched kernels: K members (1 .. 64) with buffers of the probe's own and rate constants
+ *   k[K][R] per member, members[n_entries] of them (distinct) in one launch; members not named keep their buffers.
+ * op KIN_EVAL_RHS: u[K][N] -> out. Path 0: out[N]. Path 2: mode is the source mode of ens_rhs (0: y -> f0, 1: ytmp -> f1,
+ *     2: ytmp -> f0; the state is placed in the source the mode reads, the other source holds the sentinel),
+ *     out[K][out_len] = f0 | f1 of each member (out_len >= 2 N); rate[K][R], when given, the members' rate buffers.
+ *   KIN_EVAL_JAC: out[K][out_len], out_len >= nnz: the values in kin_jac_pattern order. Path 2: rate[K][2 R], when given, the
+ *     members' operand-derivative buffers (filled with the sentinel first).
+ *   KIN_EVAL_RESID: the rates with the corrector's skip flag, then c f(u) - psi - d gathered into the permuted solve vector through
+ *     the solver's (path 0) or the ensemble's (path 2) own residual plan. c[K], psi[K][N], d[K][N]; done[K]: the value of
+ *     newton_done the kernels find (non-zero: both launches are no-ops). The rate buffer and the window of W that holds the solve
+ *     vectors are filled with `sentinel` first and come back as they stand: rate[K][R], out[K][out_len] (out_len >= the window's
+ *     length), with yloc[N]: the position of species i's residual inside that window (the analysis's yloc less the window's start).
+ *   KIN_EVAL_SIZES: no launch; info only (the residual plan of the path).
+ * Output buffers of RHS and JAC are the probe's own on the device, pre-filled with NaN: an entry no kernel wrote comes back NaN.
+ * info[8]: of the gather plan the operation used - ELL groups G, one-wavefront rows S, whole-workgroup rows B, its longest row,
+ *   the rows in the ELL groups, the workgroup size the launcher takes for the plan (segsum_wg: 256 / 1024); RESID and SIZES: the solve-vector window's length,
+ *   else 0; the Jacobian's nnz.
+ * KIN_ERR_INVALID_ARG: sizes, members, mode or T out of range, k given on path 0 or missing on path 2; KIN_ERR_CAPACITY: out_len too
+ * small; KIN_ERR_STATE: no rates, or T without Arrhenius parameters; a refused call leaves the handle as it was. Path 0 works in the
+ * handle's own buffers: the residual overwrites the host-driven solver's step vectors y, psi, d (slot 0's solve vectors and the control
+ * block are restored), and T > 0 replaces the handle's rate constants for good. A later kin_solve is bit for bit that of a fresh handle
+ * with those rates; an integrator opened with kin_integrator_init does NOT survive a path 0 call and has to be initialised again.
+ * Added under KIN_ABI_VERSION 6: look the symbol up before calling it. */
+enum { KIN_EVAL_RHS = 0, KIN_EVAL_JAC, KIN_EVAL_RESID, KIN_EVAL_SIZES };
+int kin_eval_probe(kin_network* h, int32_t path, int32_t op, int32_t mode, int64_t K, int64_t n_entries, const int32_t* members,
+                   const double* u, const double* k, double T, const double* c, const double* psi, const double* d,
+                   const int32_t* done, double sentinel, double* out, int64_t out_len, double* rate, int32_t* yloc, int64_t* info);
+
 /* ---- segmented flux pass and the analysis of a stored ensemble --------------------------------------------------- */
 /* The flux pass over S SEGMENTS of up to L states each (an ensemble's members, the chunks of a long trajectory): state
  * b = s L + j at u[b][N], flux[s][r] = sum over j < seg_n[s] of w[b] rate_r(u_b; k of state b), rate_r as in kin_flux_batched,
@@ -575,7 +609,7 @@ const char* kin_version(void);
  * struct sizes) with the values it was written against before the first call: kin_params / kin_stats have grown between
  * versions (1: round 1; 2: + dtmin and the LU-cache counters; 3: + the library-order sweep entry points; 4: + kin_solve_ensemble,
  * kin_lu_analyze_host - structs unchanged; 5: + kin_rhs_batched_klib_dev - structs unchanged; 6: + kin_solve_ensemble_continuous -
- * structs unchanged; kin_solve_ensemble_discrete, kin_resident_probe, kin_newton_probe, kin_step_probe, the flux pass (kin_flux_*, kin_solution_flux) and
+ * structs unchanged; kin_solve_ensemble_discrete, kin_resident_probe, kin_newton_probe, kin_step_probe, kin_eval_probe, the flux pass (kin_flux_*, kin_solution_flux) and
  * kin_ensemble_size / _max / _dot / _flux and the directed relation graph (kin_drg_*, kin_solution_drg, kin_ensemble_drg) came
  * later under 6, found by symbol lookup; so did DRGEP: kin_drgep_*, kin_solution_drgep, kin_ensemble_drgep). */
 #define KIN_ABI_VERSION 6

@@ -30,7 +30,7 @@ SYMBOLS = [
     "kin_lib_layout", "kin_lib_layout_host", "kin_states_to_lib_dev", "kin_states_from_lib_dev", "kin_rates_to_lib_dev", "kin_rate_table_lib_dev",
     "kin_rhs_tiled_dev", "kin_rhs_batched_T_dev", "kin_rhs_batched_klib_dev", "kin_abi_version", "kin_struct_size",
     "kin_solve_ensemble", "kin_lu_analyze_host", "kin_solve_ensemble_continuous", "kin_solve_ensemble_discrete",
-    "kin_resident_probe", "kin_newton_probe", "kin_step_probe",
+    "kin_resident_probe", "kin_newton_probe", "kin_step_probe", "kin_eval_probe",
     "kin_flux_batched", "kin_flux_batched_dev", "kin_solution_flux",
     "kin_flux_segmented", "kin_flux_segmented_dev", "kin_ensemble_size", "kin_ensemble_max", "kin_ensemble_dot", "kin_ensemble_flux",
     "kin_drg_pattern_host", "kin_drg_pattern", "kin_drg_batched", "kin_drg_batched_dev", "kin_solution_drg", "kin_ensemble_drg",
@@ -139,6 +139,10 @@ def lib():
         if hasattr(L, "kin_step_probe"):   # (also under ABI 6)
             L.kin_step_probe.argtypes = [c_void_p, c_int32, c_int32, c_int64, c_int64, c_int64, POINTER(c_int32), PD, POINTER(c_int32),
                                          PD, PD, PD, P64]
+        if hasattr(L, "kin_eval_probe"):   # (also under ABI 6)
+            P32 = POINTER(c_int32)
+            L.kin_eval_probe.argtypes = [c_void_p, c_int32, c_int32, c_int32, c_int64, c_int64, P32, PD, PD, c_double, PD, PD, PD, P32,
+                                         c_double, PD, c_int64, PD, P32, P64]
         if hasattr(L, "kin_flux_batched"):   # (also under ABI 6: the reaction-flux pass)
             L.kin_flux_batched.argtypes = [c_void_p, c_int64, PD, PD, c_int64, P64, PD, PD, PD, PD]
             L.kin_flux_batched_dev.argtypes = [c_void_p, c_int64] + [c_void_p] * 8
@@ -905,6 +909,56 @@ class HipNetwork:
         keys = ("groups", "wave_rows", "wave_rows_long", "block_rows", "max_row", "m", "grid", "wg")
         return dict(state=st3[0] if single else st3, ctrl=ct2[0] if ct.ndim == 1 else ct2, pub=pub[:STEP_CTRL], seq=int(pub[STEP_CTRL]),
                     info={k: int(v) for k, v in zip(keys, info)})
+
+    def eval_probe(self, path, op, u, k=None, T=0.0, c=None, psi=None, d=None, done=None, members=None, mode=0, sentinel=-3.5e200):
+        """The right-hand side, the Jacobian values or the Newton residual once through the integrators' launchers (diagnostic,
+        kin_eval_probe; include/kinetica_hip.h). path 0: the single-state kernels with the handle's rates (T > 0: formed from that
+        pending temperature on the spot); path 2: the lockstep ensemble's kernels, k: (K, R) per member, members: the entries of
+        the launch (default: all), mode: ens_rhs's source mode. op: 'rhs' | 'jac' | 'resid' | 'sizes'; u: (K, N) or (N,); resid: c (K,)
+        or scalar, psi, d shaped as u, done (K,) or scalar = the value of newton_done.
+        Returns dict(out: (K, ...) - rhs: N values (path 2: f0, f1 of N each), jac: nnz, resid: the solve-vector window; rate: (K, R)
+        the rate buffers (rhs on path 2, resid), on path 2 jac (K, 2 R) the operand-derivative buffers; yloc: (N,) positions of the residual inside the window; info: dict of the plan's
+        G, S, B, max_row, short, wg, and vec_len, nnz)."""
+        ops = dict(rhs=0, jac=1, resid=2, sizes=3)
+        keys = ("G", "S", "B", "max_row", "short", "wg", "vec_len", "nnz")
+        info = np.zeros(8, np.int64)
+        P32 = POINTER(c_int32)
+        if op == "sizes":
+            self._chk(lib().kin_eval_probe(self._h, int(path), 3, 0, 0, 0, None, None, None, 0.0, None, None, None, None, 0.0, None, 0,
+                                           None, None, _p64(info)))
+            return dict(info={q: int(v) for q, v in zip(keys, info)})
+        u = np.atleast_2d(_f64(u))
+        K = u.shape[0]
+        assert u.shape == (K, self.n)
+        mem = np.arange(K, dtype=np.int32) if members is None else np.ascontiguousarray(members, dtype=np.int32)
+        kk = None if k is None else np.atleast_2d(_f64(k))
+        assert kk is None or kk.shape == (K, self.nr)
+        cc = pp = dd = dn = None
+        rate = yloc = None
+        if op == "resid":
+            sz = self.eval_probe(path, "sizes", None)["info"]
+            out_len = sz["vec_len"]
+            cc = _f64(np.broadcast_to(np.asarray(c, dtype=np.float64), (K,)))
+            pp, dd = np.atleast_2d(_f64(psi)), np.atleast_2d(_f64(d))
+            assert pp.shape == u.shape and dd.shape == u.shape
+            dn = np.ascontiguousarray(np.broadcast_to(np.asarray(done, dtype=np.int32), (K,)))
+            yloc = np.zeros(self.n, np.int32)
+        elif op == "jac":
+            nnz = c_int64(0)
+            self._chk(lib().kin_jac_nnz(self._h, ctypes.byref(nnz)))
+            out_len = nnz.value
+        else:
+            out_len = self.n * (2 if path == 2 else 1)
+        if op == "resid" or (op == "rhs" and path == 2):
+            rate = np.full((K, self.nr), np.nan)
+        elif op == "jac" and path == 2:
+            rate = np.full((K, 2 * self.nr), np.nan)      # the members' operand-derivative buffers
+        out = np.full((K, max(out_len, 1)), np.nan)
+        self._chk(lib().kin_eval_probe(self._h, int(path), ops[op], int(mode), K, len(mem), mem.ctypes.data_as(P32), _pd(u), _pd(kk),
+                                       float(T), _pd(cc), _pd(pp), _pd(dd), None if dn is None else dn.ctypes.data_as(P32),
+                                       float(sentinel), _pd(out), out.shape[1], _pd(rate),
+                                       None if yloc is None else yloc.ctypes.data_as(P32), _p64(info)))
+        return dict(out=out[:, :out_len], rate=rate, yloc=yloc, info={q: int(v) for q, v in zip(keys, info)})
 
     def solution_max_dev(self, d_out):
         """kin_solution_max into a device buffer (pointer as int) of N doubles."""

@@ -122,12 +122,13 @@ struct EnsembleSolver {
     N = (int)H.N; R = (int)H.R; nnz = H.nnz();
     lu.analyze(N, H.j_ptr, H.j_col, lu_options_for(N), s);
     lu.slots.clear();
-    if (!(lu.fused_tri && lu.m > 0)) { why = "the batched ensemble needs the fused solve form (a network with a dense Schur block)"; return; }
+    // (the residual plan needs the analysis only, not the fused form: kin_eval_probe reads it from here for every network)
     std::vector<int32_t> yl(N), ident(N);
     lu.yloc.download(yl.data(), N, s);
     KIN_HIP(hipStreamSynchronize(s));
     for (int i = 0; i < N; i++) ident[i] = i;
     resid_plan.upload(build_seg_plan(N, H.sp_ptr.data(), yl.data(), H.sp_rxn.data(), nullptr, H.sp_coef.data(), false, ident.data()), s);
+    if (!(lu.fused_tri && lu.m > 0)) { why = "the batched ensemble needs the fused solve form (a network with a dense Schur block)"; return; }
     d_jdiag.upload(H.j_diag, s);
     T.N = N; T.R = R; T.m = lu.m; T.mpad = lu.mpad; T.ns = lu.ns; T.off_y = lu.off_y; T.off_x = lu.off_x;
     T.x0 = h->x0.p; T.x1 = h->x1.p; T.xloc = lu.xloc.p; T.x2_species = lu.x2_species.p;
@@ -608,6 +609,11 @@ struct MemberBackend {
 EnsembleSolver* get_ensemble(kin_network* h) {
   if (!h->ensemble) h->ensemble.reset(new EnsembleSolver(h));
   return h->ensemble.get();
+}
+
+EvalResidPlan eval_probe_ensemble_plan(kin_network* h) {
+  EnsembleSolver* E = get_ensemble(h);
+  return EvalResidPlan{&E->resid_plan, E->lu.yloc.p, E->lu.off_y, E->lu.off_vec_end - E->lu.off_y};
 }
 
 bool ensemble_batched_supported(kin_network* h, std::string* why) {

@@ -55,6 +55,9 @@ struct EnsSolveTables {
 };
 void ens_predict(const EnsSolveTables& T, const EnsRep* reps, const EnsOp* d_ops, int n, hipStream_t s);
 void ens_iterations(const EnsSolveTables& T, const EnsRep* reps, const EnsOp* d_ops, int n, int it0, int iters, hipStream_t s);
+// the first two launches of an iteration on their own: the rates of every entry's y (unless its attempt is decided) and the Newton
+// residual c f(y) - psi - d into its W at the positions of the plan `resid`; ens_iterations launches them through here
+void ens_resid(int R, const int32_t* x0, const int32_t* x1, const SegPlanView& resid, const EnsRep* reps, const EnsOp* d_ops, int n, hipStream_t s);
 // the last launch of an iteration on its own: update + decision of every entry from the solution in its W (xloc: species ->
 // position in W); ens_iterations launches it through here
 void ens_newton(int N, int iter, const int32_t* xloc, const BdfCoef& cf, const EnsRep* reps, const EnsOp* d_ops, int n, hipStream_t s);

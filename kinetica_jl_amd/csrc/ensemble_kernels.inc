@@ -115,7 +115,7 @@ template <int OP, int SEL>
 static void launch_e_segsum(const SegPlanView& p, const EnsRep* reps, const EnsOp* d_ops, int n, hipStream_t s) {
   const int tasks = p.G + p.S;
   if (tasks + p.B == 0 || n == 0) return;
-  if (p.B > 0) hipLaunchKernelGGL((e_segsum_kernel<OP, 1024, SEL>), dim3((unsigned)(p.B + ceil_div(tasks, 16)), (unsigned)n), dim3(1024), 0, s, p, reps, d_ops);
+  if (segsum_wg(p) == 1024) hipLaunchKernelGGL((e_segsum_kernel<OP, 1024, SEL>), dim3((unsigned)(p.B + ceil_div(tasks, 16)), (unsigned)n), dim3(1024), 0, s, p, reps, d_ops);
   else hipLaunchKernelGGL((e_segsum_kernel<OP, 256, SEL>), dim3((unsigned)ceil_div(tasks, 4), (unsigned)n), dim3(256), 0, s, p, reps, d_ops);
   KIN_HIP(hipGetLastError());
 }
@@ -191,11 +191,15 @@ void ens_predict(const EnsSolveTables& T, const EnsRep* reps, const EnsOp* d_ops
 void ens_newton(int N, int iter, const int32_t* xloc, const BdfCoef& cf, const EnsRep* reps, const EnsOp* d_ops, int n, hipStream_t s) {
   if (n > 0) hipLaunchKernelGGL(e_newton_kernel, dim3((unsigned)bdf_reduce_blocks(N), (unsigned)n), dim3(256), 0, s, N, iter, xloc, cf, reps, d_ops);
 }
+void ens_resid(int R, const int32_t* x0, const int32_t* x1, const SegPlanView& resid, const EnsRep* reps, const EnsOp* d_ops, int n, hipStream_t s) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL((e_rates_kernel<2>), ENS_GRID(R, n), 0, s, R, x0, x1, reps, d_ops);
+  launch_e_segsum<SEG_COEF_BDF, 2>(resid, reps, d_ops, n, s);
+}
 void ens_iterations(const EnsSolveTables& T, const EnsRep* reps, const EnsOp* d_ops, int n, int it0, int iters, hipStream_t s) {
   if (n <= 0) return;
   for (int it = it0; it < it0 + iters; it++) {
-    hipLaunchKernelGGL((e_rates_kernel<2>), ENS_GRID(T.R, n), 0, s, T.R, T.x0, T.x1, reps, d_ops);
-    launch_e_segsum<SEG_COEF_BDF, 2>(T.resid, reps, d_ops, n, s);
+    ens_resid(T.R, T.x0, T.x1, T.resid, reps, d_ops, n, s);
     launch_e_segsum<SEG_PROD_AUXSUB, 3>(T.stageA, reps, d_ops, n, s);
     hipLaunchKernelGGL(e_gemv_kernel, dim3((unsigned)ceil_div(T.m, 4), (unsigned)n), dim3(256), 0, s, T.mpad, T.m, (long long)(T.off_y + T.ns),
                        (long long)T.off_x, reps, d_ops);

@@ -43,7 +43,7 @@ void launch_segsum(const SegPlanView& p, SegOp op, const double* src, double* ou
   const int tasks = p.G + p.S;
   if (tasks + p.B == 0) return;
 #define KIN_SEG_LAUNCH(OPX)                                                                                              \
-  if (p.B > 0) hipLaunchKernelGGL((segsum_kernel<OPX, 1024>), dim3((unsigned)(p.B + ceil_div(tasks, 16))), dim3(1024), 0, s, p, src, out, ex); \
+  if (segsum_wg(p) == 1024) hipLaunchKernelGGL((segsum_kernel<OPX, 1024>), dim3((unsigned)(p.B + ceil_div(tasks, 16))), dim3(1024), 0, s, p, src, out, ex); \
   else hipLaunchKernelGGL((segsum_kernel<OPX, 256>), dim3((unsigned)ceil_div(tasks, 4)), dim3(256), 0, s, p, src, out, ex);
   switch (op) {
     case SEG_COEF_SET: KIN_SEG_LAUNCH(SEG_COEF_SET) break;

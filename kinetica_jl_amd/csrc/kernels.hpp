@@ -40,6 +40,9 @@ struct SegExtra {  // extra operands of SEG_COEF_BDF
   const int* skip = nullptr;   // optional device flag: the kernel returns immediately when *skip != 0
 };
 
+// workgroup size of a gather launch over plan p (launch_segsum and the lockstep ensemble's launch_e_segsum choose by it): whole-
+// workgroup rows need 1024 threads, plans without them start sooner with 256
+inline int segsum_wg(const SegPlanView& p) { return p.B > 0 ? 1024 : 256; }
 void launch_segsum(const SegPlanView& p, SegOp op, const double* src, double* out, const SegExtra& ex, hipStream_t s);
 
 // per-reaction rate and operand derivatives (single state)

@@ -394,16 +394,21 @@ struct Solver {
   // `spec_it`: an iteration of a speculatively enqueued step - the carried rate comes from the device's control block (the
   // host does not know yet what the step before leaves there), it counts as fresh (enqueue_speculative checked that it will
   // be whatever that step does)
-  void newton_iteration(int it, double c, unsigned long long seq, bool last, bool spec_it = false) {
-    const int* skip = &ctrl.p->newton_done;
-    SparseLU::Slot& q = lu.slots[cur_slot];
+  // the residual pair of a corrector iteration: the rates of y and c f(y) - psi - d into the permuted solve vector inside W;
+  // both no-ops once *skip is set (a pending temperature's rate constants are stored all the same)
+  void launch_residual(double c, const int* skip, double* W) {
     SegExtra ex;
     ex.psi = psi.p; ex.d = d.p; ex.cscal = c; ex.skip = skip;
     // (forming the rates inside the residual gather - three gathers per entry instead of one, no rate launch - was
     // measured slower: 0.565 against 0.553 s on the C3 solve)
     if (h->k_pending) { launch_rates_skip_T(h->host.R, h->pending_at(), h->k.p, y.p, h->x0.p, h->x1.p, h->rate.p, skip, s); h->k_pending = false; }
     else launch_rates_skip(h->host.R, h->k.p, y.p, h->x0.p, h->x1.p, h->rate.p, skip, s);
-    launch_segsum(resid_plan.view(), SEG_COEF_BDF, h->rate.p, q.W.p, ex, s);
+    launch_segsum(resid_plan.view(), SEG_COEF_BDF, h->rate.p, W, ex, s);
+  }
+  void newton_iteration(int it, double c, unsigned long long seq, bool last, bool spec_it = false) {
+    const int* skip = &ctrl.p->newton_done;
+    SparseLU::Slot& q = lu.slots[cur_slot];
+    launch_residual(c, skip, q.W.p);
     // a factorisation made for another c: the update is scaled by 2 / (1 + c / c_fact)
     // (a slot taken under the absolute rule, outside the ratio band: no scaling - it belongs to the stiff limit, where the
     // matrix is c J, and the absolute rule only admits slots whose matrix and this attempt's are both close to the identity)
@@ -1452,6 +1457,46 @@ void step_probe_fused(kin_network* h, double c, const double* u, const double* b
   for (int q = 0; q < p.B; q++) max_row = std::max<int64_t>(max_row, be[q] - bb[q]);
   info[0] = p.G; info[1] = p.S; info[2] = s_long; info[3] = p.B; info[4] = max_row; info[5] = lu.m;
   info[6] = lu.newton_grid(); info[7] = stagec_newton_wg(p.view());
+  S.cur_slot = 0;
+  S.invalidate_lu();
+}
+
+// kin_eval_probe, path 0: the residual pair as newton_iteration launches it, on the caller's y, psi, d and flag value
+EvalResidPlan eval_probe_solver_plan(kin_network* h) {
+  if (!h->solver) h->solver.reset(new Solver(h));
+  Solver& S = *h->solver;
+  return EvalResidPlan{&S.resid_plan, S.lu.yloc.p, S.lu.off_y, S.lu.off_vec_end - S.lu.off_y};
+}
+void eval_probe_solver_resid(kin_network* h, const double* u, double c, const double* psi, const double* d, int done, double sentinel,
+                             double* vec, double* rate) {
+  const EvalResidPlan pl = eval_probe_solver_plan(h);
+  Solver& S = *h->solver;
+  SparseLU& lu = S.lu;
+  hipStream_t s = h->stream;
+  const int N = S.N;
+  const int64_t R = h->host.R;
+  S.flush_accept();
+  S.spec = Solver::Spec{};
+  lu.ensure_slots(1, s);
+  double* W = lu.slots[0].W.p;
+  // what the probe overwrites and a solve expects as it left it: the solve vectors of slot 0 and the control block
+  std::vector<double> keep((size_t)pl.vec_len), fill((size_t)std::max<int64_t>(pl.vec_len, R), sentinel);
+  BdfCtrl keep_ctrl, c_in{};
+  KIN_HIP(hipMemcpyAsync(keep.data(), W + pl.off_y, keep.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+  KIN_HIP(hipMemcpyAsync(&keep_ctrl, S.ctrl.p, sizeof(BdfCtrl), hipMemcpyDeviceToHost, s));
+  KIN_HIP(hipStreamSynchronize(s));
+  c_in.newton_done = done;
+  KIN_HIP(hipMemcpyAsync(S.ctrl.p, &c_in, sizeof(BdfCtrl), hipMemcpyHostToDevice, s));
+  KIN_HIP(hipMemcpyAsync(W + pl.off_y, fill.data(), (size_t)pl.vec_len * sizeof(double), hipMemcpyHostToDevice, s));
+  if (R > 0) KIN_HIP(hipMemcpyAsync(h->rate.p, fill.data(), (size_t)R * sizeof(double), hipMemcpyHostToDevice, s));
+  S.y.upload(u, N, s); S.psi.upload(psi, N, s); S.d.upload(d, N, s);
+  S.launch_residual(c, &S.ctrl.p->newton_done, W);
+  KIN_HIP(hipGetLastError());
+  KIN_HIP(hipMemcpyAsync(vec, W + pl.off_y, (size_t)pl.vec_len * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (R > 0) h->rate.download(rate, (size_t)R, s);
+  KIN_HIP(hipMemcpyAsync(W + pl.off_y, keep.data(), keep.size() * sizeof(double), hipMemcpyHostToDevice, s));
+  KIN_HIP(hipMemcpyAsync(S.ctrl.p, &keep_ctrl, sizeof(BdfCtrl), hipMemcpyHostToDevice, s));
+  KIN_HIP(hipStreamSynchronize(s));
   S.cur_slot = 0;
   S.invalidate_lu();
 }

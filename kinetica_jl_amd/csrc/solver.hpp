@@ -90,5 +90,16 @@ void newton_probe(kin_network* h, int64_t K, int32_t batched, const double* u, c
 // flag and the partial-sum buffer (the Solver's own) are set here. x: the solution that launch left in W; info[8]: see the header
 struct NewtonFuse;
 void step_probe_fused(kin_network* h, double c, const double* u, const double* b, NewtonFuse& f, double* x, int64_t* info);
+// diagnostic (kin_eval_probe): the residual plan of the host-driven solver (path 0: solver.cpp) and of the lockstep ensemble
+// (path 2: ensemble.cpp; built from the analysis whether or not the network takes the batched form), the device copy of yloc, and
+// the window [off_y, off_y + vec_len) of W that holds the solve vectors. The first call on a handle runs the analysis.
+struct EvalResidPlan { const SegPlanDev* plan; const int32_t* yloc; int64_t off_y, vec_len; };
+EvalResidPlan eval_probe_solver_plan(kin_network* h);
+EvalResidPlan eval_probe_ensemble_plan(kin_network* h);
+// ... path 0's residual pair through Solver::launch_residual (what newton_iteration calls) on y = u, psi, d, c and the flag value
+// `done`: slot 0's solve vectors and the handle's rate buffer are filled with `sentinel` first and come back in vec[vec_len] and
+// rate[R]; the slot's vectors and the control block are restored afterwards
+void eval_probe_solver_resid(kin_network* h, const double* u, double c, const double* psi, const double* d, int done, double sentinel,
+                             double* vec, double* rate);
 
 }  // namespace kin

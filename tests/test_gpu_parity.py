@@ -11,6 +11,7 @@ import scipy.sparse as sp
 from kinetica_jl_amd import capi
 from kinetica_jl_amd.synth import from_lists, synthetic_crn
 from oracle import oracle as orc
+from tests.jac_cases import assert_jac_entrywise
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-13
@@ -61,6 +62,9 @@ def test_jacobian_matches_oracle(case):
     Jo = on.jac(k, u)
     D = abs(Jd - Jo)
     assert D.max() <= TOL * abs(Jo).max()
+    # ... and every entry inside its own bound (tests/jac_cases.py): the normwise measure above does not see an entry that is
+    # small against the largest one
+    assert_jac_entrywise(net, k, u, Jd.data, rowptr, col, "test_jacobian_matches_oracle")
     # finite-difference check of the device Jacobian against the device RHS (independent of the oracle)
     # (mass action is at most quadratic in u_j, so a central difference is exact up to round-off)
     j = 5
@@ -263,6 +267,7 @@ def test_full_size_properties_c5_tiled_sweep():
     Jd = sp.csr_matrix((h.jac_values(U[0]), col, rowptr), shape=(50000, 50000))
     Jo = on.jac(k, U[0])
     assert abs(Jd - Jo).max() <= TOL * abs(Jo).max()
+    assert_jac_entrywise(net, k, U[0], Jd.data, rowptr, col, "C5")       # entry by entry as well
     h.close()
 
 

@@ -464,6 +464,34 @@ int kin_eval_probe(kin_network* h, int32_t path, int32_t op, int32_t mode, int64
                    const double* u, const double* k, double T, const double* c, const double* psi, const double* d,
                    const int32_t* done, double sentinel, double* out, int64_t out_len, double* rate, int32_t* yloc, int64_t* info);
 
+/* Diagnostic: the LU cache's drift guard and slot rules, run ONCE on the caller's values through the integrators' own launchers,
+ * kernels and backends. The probe computes nothing itself, and every index array the kernels use is the handle's own.
+ * mode KIN_CACHE_DRIFT: n_slots slots are made from the Jacobian value arrays jv_slots[n_slots][nnz] (kin_jac_pattern order) at
+ *   c_fact[n_slots], with flags valid[n_slots] (0: the slot counts as unused), and tested against today's values jv_now[nnz] with
+ *   the threshold max_drift.
+ *   path 0 (host-driven: Solver::restart / resume_chunk and the lockstep ensemble), n_slots 1 .. 128: each slot's diagonal by
+ *     launch_jac_diag; launch_drift_test once with the pinned host target and once without (the ensemble's form: results at a
+ *     member's offset of a larger buffer, copied afterwards); then drop_drifted. jd[n_slots][N]: the saved diagonals;
+ *     drift[2][n_slots]: the results of the two forms; out_i[n_slots]: the slots' valid flags afterwards; info[0]: the number
+ *     drop_drifted dropped, info[1]: the number of slots launch_drift_test tested, info[2]: the number dropped on the second
+ *     form's results, info[6]: 1 when nothing outside the slots' results was written.
+ *   path 1 (the resident kernel, its diagnostic build), n_slots 1 .. 64: slot s by ph_factor(s, c_fact[s], keep_diag) on
+ *     jv_slots[s], then today's values and DevBackend::drift_check(max_drift) by wavefront 0 with ph_drift on all eight.
+ *     jd as above; drift[n_slots]: the kernel's per-slot results (-7: ph_drift wrote none); out_i[n_slots]: the slot table's
+ *     valid flags afterwards; info[0] (= info[2]): drift_check's return value; info[1] = n_slots.
+ * mode KIN_CACHE_RULES (path 1 only): the slot table valid[n_slots], c_fact[n_slots], stamps[3][n_slots] = jac_stamp, step_stamp,
+ *   last_use (n_slots 0 .. 64; the kernel's other slots are unused), and n_queries queries qd[q][2] = c, band;
+ *   qi[q][5] = n_restarts, max_age, n_steps, step_age (-1: off), the launch's slot count (0 .. 64). out_i[q][2] =
+ *   DevBackend::nearest_slot and DevBackend::victim_slot as the controller calls them.
+ * info has 8 entries; path 1 also returns the dense block size, the sparse rows and the dynamic LDS bytes in info[3 .. 5].
+ * KIN_ERR_INVALID_ARG: path, mode, n_slots, n_queries or a query's slot count out of range, a null buffer;
+ * KIN_ERR_UNSUPPORTED: path 1 on a network the resident kernel does not take. Needs no rate constants; a later solve on the handle
+ * is that of a fresh handle. Added under KIN_ABI_VERSION 6: look the symbol up before calling it. */
+enum { KIN_CACHE_DRIFT = 0, KIN_CACHE_RULES = 1 };
+int kin_cache_probe(kin_network* h, int32_t path, int32_t mode, int64_t n_slots, const double* jv_slots, const double* c_fact,
+                    const int32_t* valid, const double* jv_now, double max_drift, const int64_t* stamps, int64_t n_queries,
+                    const double* qd, const int64_t* qi, double* jd, double* drift, int32_t* out_i, int64_t* info);
+
 /* ---- segmented flux pass and the analysis of a stored ensemble --------------------------------------------------- */
 /* The flux pass over S SEGMENTS of up to L states each (an ensemble's members, the chunks of a long trajectory): state
  * b = s L + j at u[b][N], flux[s][r] = sum over j < seg_n[s] of w[b] rate_r(u_b; k of state b), rate_r as in kin_flux_batched,
@@ -609,7 +637,7 @@ const char* kin_version(void);
  * struct sizes) with the values it was written against before the first call: kin_params / kin_stats have grown between
  * versions (1: round 1; 2: + dtmin and the LU-cache counters; 3: + the library-order sweep entry points; 4: + kin_solve_ensemble,
  * kin_lu_analyze_host - structs unchanged; 5: + kin_rhs_batched_klib_dev - structs unchanged; 6: + kin_solve_ensemble_continuous -
- * structs unchanged; kin_solve_ensemble_discrete, kin_resident_probe, kin_newton_probe, kin_step_probe, kin_eval_probe, the flux pass (kin_flux_*, kin_solution_flux) and
+ * structs unchanged; kin_solve_ensemble_discrete, kin_resident_probe, kin_newton_probe, kin_step_probe, kin_eval_probe, kin_cache_probe, the flux pass (kin_flux_*, kin_solution_flux) and
  * kin_ensemble_size / _max / _dot / _flux and the directed relation graph (kin_drg_*, kin_solution_drg, kin_ensemble_drg) came
  * later under 6, found by symbol lookup; so did DRGEP: kin_drgep_*, kin_solution_drgep, kin_ensemble_drgep). */
 #define KIN_ABI_VERSION 6

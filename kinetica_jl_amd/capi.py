@@ -30,7 +30,7 @@ SYMBOLS = [
     "kin_lib_layout", "kin_lib_layout_host", "kin_states_to_lib_dev", "kin_states_from_lib_dev", "kin_rates_to_lib_dev", "kin_rate_table_lib_dev",
     "kin_rhs_tiled_dev", "kin_rhs_batched_T_dev", "kin_rhs_batched_klib_dev", "kin_abi_version", "kin_struct_size",
     "kin_solve_ensemble", "kin_lu_analyze_host", "kin_solve_ensemble_continuous", "kin_solve_ensemble_discrete",
-    "kin_resident_probe", "kin_newton_probe", "kin_step_probe", "kin_eval_probe",
+    "kin_resident_probe", "kin_newton_probe", "kin_step_probe", "kin_eval_probe", "kin_cache_probe",
     "kin_flux_batched", "kin_flux_batched_dev", "kin_solution_flux",
     "kin_flux_segmented", "kin_flux_segmented_dev", "kin_ensemble_size", "kin_ensemble_max", "kin_ensemble_dot", "kin_ensemble_flux",
     "kin_drg_pattern_host", "kin_drg_pattern", "kin_drg_batched", "kin_drg_batched_dev", "kin_solution_drg", "kin_ensemble_drg",
@@ -143,6 +143,9 @@ def lib():
             P32 = POINTER(c_int32)
             L.kin_eval_probe.argtypes = [c_void_p, c_int32, c_int32, c_int32, c_int64, c_int64, P32, PD, PD, c_double, PD, PD, PD, P32,
                                          c_double, PD, c_int64, PD, P32, P64]
+        if hasattr(L, "kin_cache_probe"):   # (also under ABI 6)
+            P32 = POINTER(c_int32)
+            L.kin_cache_probe.argtypes = [c_void_p, c_int32, c_int32, c_int64, PD, PD, P32, PD, c_double, P64, c_int64, PD, P64, PD, PD, P32, P64]
         if hasattr(L, "kin_flux_batched"):   # (also under ABI 6: the reaction-flux pass)
             L.kin_flux_batched.argtypes = [c_void_p, c_int64, PD, PD, c_int64, P64, PD, PD, PD, PD]
             L.kin_flux_batched_dev.argtypes = [c_void_p, c_int64] + [c_void_p] * 8
@@ -851,6 +854,39 @@ class HipNetwork:
         inf = {k: int(v) for k, v in zip(keys, info[:7])}
         inf["dense_species"] = info[8:8 + m].copy()
         return dict(du=du, jac=jac[:, :nnz.value], x=x, bad=bad, info=inf)
+
+    def cache_probe(self, path, jv_slots=None, c_fact=None, valid=None, jv_now=None, max_drift=1.0, table=None, queries=None):
+        """The LU cache's drift guard or slot rules once through the integrators' own code (diagnostic, kin_cache_probe;
+        include/kinetica_hip.h). Drift: jv_slots (ns, nnz), c_fact (ns,), valid (ns,), jv_now (nnz,) ->
+        dict(jd (ns, N), drift (ns,) [path 0: also drift_offset, the ensemble's form], valid_after (ns,), dropped (ns,) bool,
+        n_dropped, n_tested, n_dropped_offset, clean, info). Slot rules (path 1): table = dict of valid, c_fact, jac_stamp, step_stamp,
+        last_use; queries = list of dicts c, band, n_restarts, max_age, n_steps, step_age, n_slots -> (Q, 2) array of nearest, victim."""
+        P32 = POINTER(c_int32)
+        info = np.zeros(8, np.int64)
+        if table is not None:
+            v = np.ascontiguousarray(table["valid"], np.int32); cf = _f64(table["c_fact"])
+            st = np.ascontiguousarray(np.stack([np.asarray(table[k], np.int64) for k in ("jac_stamp", "step_stamp", "last_use")]))
+            qd = _f64(np.array([[q["c"], q["band"]] for q in queries]))
+            qi = np.ascontiguousarray(np.array([[q["n_restarts"], q["max_age"], q["n_steps"], q["step_age"], q["n_slots"]] for q in queries], np.int64))
+            out = np.full((len(queries), 2), -2, np.int32)
+            self._chk(lib().kin_cache_probe(self._h, int(path), 1, len(v), None, _pd(cf), v.ctypes.data_as(P32), None, 0.0, _p64(st), len(queries),
+                                            _pd(qd), _p64(qi), None, None, out.ctypes.data_as(P32), _p64(info)))
+            return out
+        jv_slots = np.atleast_2d(_f64(jv_slots)); jv_now = _f64(jv_now)
+        ns = jv_slots.shape[0]
+        c_fact = _f64(np.broadcast_to(np.asarray(c_fact, np.float64), (ns,)))
+        valid = np.ascontiguousarray(np.broadcast_to(np.asarray(valid, np.int32), (ns,)))
+        nnz = c_int64(0)
+        self._chk(lib().kin_jac_nnz(self._h, ctypes.byref(nnz)))
+        assert jv_slots.shape == (ns, nnz.value) and jv_now.shape == (nnz.value,)
+        jd = np.full((ns, self.n), np.nan); drift = np.full((2, ns), np.nan); after = np.full(ns, -2, np.int32)
+        self._chk(lib().kin_cache_probe(self._h, int(path), 0, ns, _pd(jv_slots), _pd(c_fact), valid.ctypes.data_as(P32), _pd(jv_now),
+                                        float(max_drift), None, 0, None, None, _pd(jd), _pd(drift), after.ctypes.data_as(P32), _p64(info)))
+        out = dict(jd=jd, drift=drift[0], valid_after=after, dropped=(valid != 0) & (after == 0), n_dropped=int(info[0]), n_tested=int(info[1]),
+                   n_dropped_offset=int(info[2]), info=info)
+        if int(path) == 0:
+            out.update(drift_offset=drift[1], clean=bool(info[6]))
+        return out
 
     def newton_probe(self, u, c, b, batched=False):
         """K Newton-matrix solves through the host-driven factorisation and solve kernels (diagnostic, kin_newton_probe). u, b:

@@ -349,4 +349,61 @@ void resident_probe(kin_network* h, int64_t K, const double* u, const double* c,
   for (int32_t j = 0; j < RS.lu.m; j++) info[8 + j] = RS.lu.perm[RS.lu.ns + j];
 }
 
+// Diagnostic (kin_cache_probe, path 1): the LU cache's drift guard or its slot rules through the kernel's own phases and backend
+// (resident_probe.hip, modes RES_PROBE_DRIFT / RES_PROBE_RULES), in the workspaces of the ResidentSolver every resident solve of
+// this handle uses, sized for n_slots slots. Sizes were checked by the caller; the kernel indexes with the handle's tables only.
+void resident_cache_probe(kin_network* h, int mode, int64_t n_slots, const double* jv_slots, const double* c_fact, const int32_t* valid,
+                          const double* jv_now, double max_drift, const int64_t* stamps, int64_t n_queries, const double* qd, const int64_t* qi,
+                          double* jd, double* drift, int32_t* out_i, int64_t* info) {
+  if (!resident_can_fit(h)) throw KinError(ERR_UNSUPPORTED, "network does not fit the resident integrator: its state and rates exceed the LDS");
+  ResidentSolver& RS = *get_resident(h);
+  if (!RS.ok) throw KinError(ERR_UNSUPPORTED, "network does not fit the resident integrator: " + RS.why);
+  hipStream_t s = h->stream;
+  const int64_t N = h->host.N, nnz = h->host.nnz();
+  const bool drift_mode = mode == RES_PROBE_DRIFT;
+  const int slots = drift_mode ? (int)n_slots : 1;
+  RS.ensure(1, slots, 1, false);
+  DevBuf<double> d_jvs, d_now, d_c, d_qd, d_drift;
+  DevBuf<int32_t> d_valid, d_out;
+  DevBuf<long long> d_stamps, d_qi;
+  ResProbeIO io{};
+  io.mode = mode; io.n_slots = (int32_t)n_slots; io.n_queries = (int32_t)n_queries; io.max_drift = max_drift;
+  const size_t n_out = drift_mode ? (size_t)RES_MAX_SLOTS + 1 : (size_t)2 * n_queries;
+  std::vector<int32_t> h_out(n_out, -2);
+  d_out.upload(h_out, s);
+  d_c.upload(c_fact, (size_t)n_slots, s); d_valid.upload(valid, (size_t)n_slots, s);
+  io.c_fact = d_c.p; io.valid = d_valid.p; io.out_i = d_out.p;
+  if (drift_mode) {
+    d_jvs.upload(jv_slots, (size_t)(n_slots * nnz), s); d_now.upload(jv_now, (size_t)nnz, s);
+    d_drift.alloc((size_t)RES_MAX_SLOTS);
+    io.jv_slots = d_jvs.p; io.jv_now = d_now.p; io.drift = d_drift.p;
+  } else {
+    static_assert(sizeof(long long) == sizeof(int64_t), "stamps travel as they are");
+    d_stamps.upload(reinterpret_cast<const long long*>(stamps), (size_t)(3 * n_slots), s);
+    d_qd.upload(qd, (size_t)(2 * n_queries), s); d_qi.upload(reinterpret_cast<const long long*>(qi), (size_t)(5 * n_queries), s);
+    io.stamps = d_stamps.p; io.qd = d_qd.p; io.qi = d_qi.p;
+  }
+  ResParams P{};
+  P.n_slots = slots;
+  RS.hn.Ea = h->Ea.p; RS.hn.A = h->A.p; RS.hn.has_kmax = h->has_kmax ? 1 : 0; RS.hn.k_max = h->k_max; RS.hn.t_mult = h->t_mult;
+  RS.d_net.upload(&RS.hn, 1, s);
+  RS.d_par.upload(&P, 1, s);
+  RS.d_traj.upload(RS.h_traj.data(), 1, s);
+  launch_resident_probe(1, RS.dyn_lds, RS.d_net.p, RS.d_traj.p, RS.d_par.p, io, s);
+  d_out.download(h_out.data(), n_out, s);
+  if (drift_mode) {
+    RS.jdbuf.download(jd, (size_t)(n_slots * N), s);
+    d_drift.download(drift, (size_t)n_slots, s);
+  }
+  KIN_HIP(hipStreamSynchronize(s));
+  std::fill(info, info + 8, (int64_t)0);
+  if (drift_mode) {
+    std::copy(h_out.begin(), h_out.begin() + n_slots, out_i);
+    info[0] = h_out[RES_MAX_SLOTS]; info[1] = n_slots; info[2] = info[0];
+  } else {
+    std::copy(h_out.begin(), h_out.end(), out_i);
+  }
+  info[3] = RS.lu.m; info[4] = RS.lu.ns; info[5] = (int64_t)RS.dyn_lds;
+}
+
 }  // namespace kin

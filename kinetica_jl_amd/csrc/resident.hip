@@ -1093,9 +1093,71 @@ __global__ __launch_bounds__(RES_WG) __attribute__((amdgpu_waves_per_eu(RES_WAVE
 //   du = f(u) (ph_rhs), jv = J(u) (ph_jac: T.f0 / T.jv point at the caller's output rows), M = I - c J(u) factorised into slot 0
 //   (ph_factor), then M x = b through the network's solve form (solve_wg) with b scattered into the zeroed LDS window at yloc
 //   and x gathered from xloc, and the factorisation's vanished-pivot flag.
+// The LU cache's modes of the probe (kin_cache_probe, path 1), one workgroup.
+// RES_PROBE_DRIFT: slot s is made from the caller's Jacobian values jv_slots[s] by ph_factor(s, c_fact[s], true) - the
+// factorisation the controller asks for, which saves the diagonal in T.jd -, today's values are loaded, the slot table gets the
+// caller's valid flags and c_fact, and wavefront 0 runs DevBackend::drift_check exactly as the controller does at a restart; the
+// other wavefronts meet the barrier of its command and run ph_drift with it (what worker_loop does on OP_DRIFT). g_sh.drift
+// holds RES_PROBE_SENTINEL first: a slot ph_drift did not write shows.
+constexpr double RES_PROBE_SENTINEL = -7.0;
+__device__ void probe_drift(const ResProbeIO& io) {
+  const int tid = threadIdx.x, nnz = uni(g_cx.nnzJ), ns = uni(g_cx.n_slots);
+  gd_t* jv = glob(g_cx.T.jv);
+  for (int s = 0; s < ns; s++) {
+    gcd_t* src = glob(io.jv_slots) + (size_t)s * nnz;
+    for (int e = tid; e < nnz; e += RES_WG) jv[e] = src[e];
+    __syncthreads();
+    (void)ph_factor(s, glob(io.c_fact)[s], true);
+  }
+  gcd_t* now = glob(io.jv_now);
+  for (int e = tid; e < nnz; e += RES_WG) jv[e] = now[e];
+  if (tid < 64) {
+    const bool in = tid < ns;
+    g_sl.valid[tid] = in ? io.valid[tid] : 0; g_sl.c_fact[tid] = in ? io.c_fact[tid] : 0.0; g_sl.crate[tid] = 1.0;
+    g_sl.crate_step[tid] = 0; g_sl.crate_restart[tid] = -1; g_sl.last_use[tid] = 0; g_sl.jac_stamp[tid] = 0; g_sl.step_stamp[tid] = 0;
+    g_sh.drift[tid] = RES_PROBE_SENTINEL;
+  }
+  __syncthreads();
+  if (tid < 64) {
+    DevBackend b;
+    const int n = b.drift_check(io.max_drift);
+    if (tid < ns) { io.drift[tid] = g_sh.drift[tid]; io.out_i[tid] = g_sl.valid[tid]; }
+    if (tid == 0) io.out_i[RES_MAX_SLOTS] = n;
+  } else {
+    __syncthreads();   // (DevBackend::post)
+    ph_drift();
+  }
+}
+// RES_PROBE_RULES: the slot table from the caller (n_slots entries; the rest unused), then per query q the controller's two
+// lookups: out_i[2 q] = DevBackend::nearest_slot(c, band, n_restarts, max_age, n_steps, step_age) with g_cx.n_slots = the query's
+// slot count, out_i[2 q + 1] = DevBackend::victim_slot(n_restarts, max_age, that count)
+__device__ void probe_rules(const ResProbeIO& io) {
+  const int tid = threadIdx.x, nt = io.n_slots;
+  if (tid < 64) {
+    const bool in = tid < nt;
+    g_sl.valid[tid] = in ? io.valid[tid] : 0; g_sl.c_fact[tid] = in ? io.c_fact[tid] : 0.0; g_sl.crate[tid] = 1.0;
+    g_sl.crate_step[tid] = 0; g_sl.crate_restart[tid] = -1;
+    g_sl.jac_stamp[tid] = in ? io.stamps[tid] : 0; g_sl.step_stamp[tid] = in ? io.stamps[nt + tid] : 0; g_sl.last_use[tid] = in ? io.stamps[2 * nt + tid] : 0;
+  }
+  for (int q = 0; q < io.n_queries; q++) {
+    const long long* qi = io.qi + 5 * q;
+    if (tid == 0) g_cx.n_slots = (int)qi[4];
+    __syncthreads();
+    if (tid < 64) {
+      DevBackend b;
+      const int near = b.nearest_slot(io.qd[2 * q], io.qd[2 * q + 1], qi[0], qi[1], qi[2], qi[3]);
+      const int victim = b.victim_slot(qi[0], qi[1], (int)qi[4]);
+      if (tid == 0) { io.out_i[2 * q] = near; io.out_i[2 * q + 1] = victim; }
+    }
+    __syncthreads();
+  }
+}
+
 __global__ __launch_bounds__(RES_WG) __attribute__((amdgpu_waves_per_eu(RES_WAVES_PER_EU, RES_WAVES_PER_EU))) void resident_probe_kernel(const ResNetDev* __restrict__ net_p, const ResTrajDev* __restrict__ traj,
                                                                  const ResParams* __restrict__ par_p, ResProbeIO io) {
 #include "resident_prologue.inc"
+  if (io.mode == RES_PROBE_DRIFT) { probe_drift(io); return; }
+  if (io.mode == RES_PROBE_RULES) { probe_rules(io); return; }
   const int N = uni(g_cx.N), tid = threadIdx.x;
   const size_t mb = blockIdx.x;
   ph_vec(VO_LOAD_U0, 0.0);

@@ -55,8 +55,21 @@ void launch_resident(int K, size_t dyn_lds, const ResNetDev* d_net, const ResTra
 void launch_resident_shared_cu(int K, size_t dyn_lds, const ResNetDev* d_net, const ResTrajDev* d_traj, const ResParams* d_par, hipStream_t s);
 size_t resident_static_lds();    // static LDS of the kernel (what two co-resident workgroups need twice, next to 2 x dyn_lds)
 // diagnostic (resident_probe.hip: resident.hip built with RES_LINALG_PROBE): the phases of one Newton-matrix solve per member -
-// f(u) into T.f0, J(u) into T.jv, M = I - c[m] J(u) into slot 0 of T.W, x[m] = M^-1 b[m], bad[m] = the vanished-pivot flag
-struct ResProbeIO { const double *c, *b; double* x; int32_t* bad; };
+// f(u) into T.f0, J(u) into T.jv, M = I - c[m] J(u) into slot 0 of T.W, x[m] = M^-1 b[m], bad[m] = the vanished-pivot flag (mode
+// RES_PROBE_NEWTON, the zero-initialised default).
+// The cache modes (kin_cache_probe, path 1; one workgroup): RES_PROBE_DRIFT - n_slots slots made from jv_slots[n_slots][nnz] at
+// c_fact[n_slots] (ph_factor with keep_diag), flags valid[n_slots], then DevBackend::drift_check(max_drift) against jv_now[nnz]:
+// drift[n_slots] = g_sh.drift, out_i[n_slots] = the slot table's valid flags afterwards, out_i[RES_MAX_SLOTS] = its return value;
+// RES_PROBE_RULES - the slot table valid / c_fact / stamps[3][n_slots] (jac_stamp, step_stamp, last_use), n_queries queries
+// qd[q][2] = c, band, qi[q][5] = n_restarts, max_age, n_steps, step_age, slot count: out_i[q][2] = nearest_slot, victim_slot.
+enum : int { RES_PROBE_NEWTON = 0, RES_PROBE_DRIFT = 1, RES_PROBE_RULES = 2 };
+struct ResProbeIO {
+  const double *c, *b; double* x; int32_t* bad;
+  int32_t mode, n_slots, n_queries;
+  const double *jv_slots, *jv_now, *c_fact; const int32_t* valid; double max_drift;
+  const long long* stamps; const double* qd; const long long* qi;
+  double* drift; int32_t* out_i;
+};
 void launch_resident_probe(int K, size_t dyn_lds, const ResNetDev* d_net, const ResTrajDev* d_traj, const ResParams* d_par, const ResProbeIO& io,
                            hipStream_t s);
 

@@ -410,8 +410,6 @@ struct Solver {
     SparseLU::Slot& q = lu.slots[cur_slot];
     launch_residual(c, skip, q.W.p);
     // a factorisation made for another c: the update is scaled by 2 / (1 + c / c_fact)
-    // (a slot taken under the absolute rule, outside the ratio band: no scaling - it belongs to the stiff limit, where the
-    // matrix is c J, and the absolute rule only admits slots whose matrix and this attempt's are both close to the identity)
     const double upd = (q.c_fact != c && std::fabs(c / q.c_fact - 1.0) <= lu_band) ? 2.0 / (1.0 + c / q.c_fact) : 1.0;
     const double rate_max = (lu_band > 0.0 && !cache_suspended && !slot_is_fresh) ? reuse_rate_max : 1.0;
     const double crate0 = q.crate, tol_first = (spec_it || crate_fresh(q)) ? newton_tol : -1.0;

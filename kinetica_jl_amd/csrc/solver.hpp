@@ -65,6 +65,11 @@ bool resident_ensemble_route(kin_network* h, int64_t K);
 // diagnostic: the resident kernel's RHS, Jacobian, factorisation and solve once per member (kin_resident_probe)
 void resident_probe(kin_network* h, int64_t K, const double* u, const double* c, const double* b, double* du, double* jac, double* x,
                     int32_t* bad, int64_t* info);
+// diagnostic: the LU cache's drift guard (mode 1) or slot rules (mode 2) through the resident kernel (kin_cache_probe, path 1;
+// resident.hpp: ResProbeIO has the argument layout)
+void resident_cache_probe(kin_network* h, int mode, int64_t n_slots, const double* jv_slots, const double* c_fact, const int32_t* valid,
+                          const double* jv_now, double max_drift, const int64_t* stamps, int64_t n_queries, const double* qd, const int64_t* qi,
+                          double* jd, double* drift, int32_t* out_i, int64_t* info);
 // can the lockstep form (ensemble.cpp) take this network's factorisation? (fused solve with a dense Schur block)
 bool ensemble_batched_supported(kin_network* h, std::string* why);
 // K members of a network beyond that, advanced in lockstep rounds of batched launches (ensemble.cpp)

@@ -67,6 +67,32 @@ def change_D(D, order, factor):
     D[:order + 1] = RU.T.dot(D[:order + 1])
 
 
+def slot_drift(c_fact, jd_old, jd_now):
+    """Drift of diag(I - c J) since a slot was made at c_fact with diag(J) = jd_old, against today's diagonal jd_now:
+    max_i max(q, 1 / q) - 1, q = (1 - c jd_old[i]) / (1 - c jd_now[i]); a sign change or a NaN counts as 1e300."""
+    with np.errstate(all="ignore"):
+        q = (1.0 - c_fact * jd_old) / (1.0 - c_fact * jd_now)
+        dev = np.where(q > 0.0, np.maximum(q, 1.0 / q), 1e300)
+        dev = np.where(np.isnan(dev), 1e300, dev)
+    return dev.max() - 1.0
+
+
+def nearest_slot(slots, c, band, n_restarts, max_age, n_steps=0, step_age=-1):
+    """Index of the slot (dicts with c_fact, jac_stamp, step_stamp) whose c_fact is closest in ratio to c and within the band,
+    the first of equals; -1: none. A slot is on offer for max_age restarts after its Jacobian was evaluated and, with
+    step_age >= 0, for step_age accepted steps."""
+    best, bd = -1, 1e300
+    for i, sl in enumerate(slots):
+        if n_restarts - sl["jac_stamp"] > max_age:
+            continue
+        if step_age >= 0 and n_steps - sl["step_stamp"] > step_age:
+            continue
+        r = abs(math.log(c / sl["c_fact"]))
+        if r < bd and abs(c / sl["c_fact"] - 1.0) <= band:
+            best, bd = i, r
+    return best
+
+
 class OracleBDF:
     """fun(y) -> f, jac(y) -> scipy CSR (autonomous system: the rate constants are frozen
     between restarts, exactly as in the discrete-rate solves of methods.jl:655-865)."""
@@ -106,7 +132,7 @@ class OracleBDF:
         self.ban_negatives = ban_negatives
         self.set_tols(atol, rtol)
         self.stats = dict(n_steps=0, n_rejected=0, n_rhs=0, n_jac=0, n_factor=0, n_linsolve=0, n_newton_fail=0,
-                          n_restarts=0, n_lu_reused=0)
+                          n_restarts=0, n_lu_reused=0, n_lu_dropped=0)
         self.I = sp.identity(n, format="csc")
         self.iters_left = 0
         self.first_selection = False
@@ -141,16 +167,10 @@ class OracleBDF:
         self.LU = None
 
     def _nearest_slot(self, c):
-        best, bd = None, 1e300
-        for sl in self.slots:
-            if self.stats["n_restarts"] - sl["jac_stamp"] > self.lu_max_age:
-                continue
-            if self.pre_attempt is not None and self.stats["n_steps"] - sl["step_stamp"] > 50:
-                continue          # continuous rate updates: the Jacobian behind a slot is at most 50 accepted steps old
-            r = abs(math.log(c / sl["c_fact"]))
-            if r < bd and abs(c / sl["c_fact"] - 1.0) <= self.lu_band:
-                best, bd = sl, r
-        return best
+        # continuous rate updates: the Jacobian behind a slot is at most 50 accepted steps old
+        i = nearest_slot(self.slots, c, self.lu_band, self.stats["n_restarts"], self.lu_max_age, self.stats["n_steps"],
+                         50 if self.pre_attempt is not None else -1)
+        return None if i < 0 else self.slots[i]
 
     def _factor_into(self, sl, c):
         if sl is None:
@@ -297,14 +317,8 @@ class OracleBDF:
         if self.lu_band > 0 and self.lu_drift_max > 0 and self.slots:
             # drift of diag(I - c_s J) of every slot against today's Jacobian at the same c_s
             jd_now = self.J.diagonal()
-            keep = []
-            for sl in self.slots:
-                with np.errstate(all="ignore"):
-                    q = (1.0 - sl["c_fact"] * sl["jd"]) / (1.0 - sl["c_fact"] * jd_now)
-                    dev = np.where(q > 0.0, np.maximum(q, 1.0 / q), 1e300)
-                    dev = np.where(np.isnan(dev), 1e300, dev)
-                if dev.max() - 1.0 <= self.lu_drift_max:
-                    keep.append(sl)
+            keep = [sl for sl in self.slots if slot_drift(sl["c_fact"], sl["jd"], jd_now) <= self.lu_drift_max]
+            self.stats["n_lu_dropped"] += len(self.slots) - len(keep)
             self.slots = keep
         self.LU = None
         self.jac_current = True

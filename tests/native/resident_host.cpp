@@ -400,6 +400,44 @@ int res_host_newton_solve(void* hv, double c, const double* k, const double* u, 
   return bad ? 1 : 0;
 }
 
+// The LU cache's slot rules through the templates of bdf_rules.hpp over HostBackend's slot records, as HostBackend (and, with the
+// same calls over its own records, Solver and the ensemble's MemberBackend) asks them: table[n_table] (entries beyond it read as
+// unused slots), out[0] = slot_nearest over the first n_slots, out[1] = slot_first_free, else slot_lru, over the same
+void res_host_slot_rules(int n_table, const int32_t* valid, const double* c_fact, const int64_t* jac_stamp, const int64_t* step_stamp,
+                         const int64_t* last_use, int n_slots, double c, double band, int64_t n_restarts, int64_t max_age, int64_t n_steps,
+                         int64_t step_age, int32_t* out) {
+  std::vector<HostBackend::Slot> sl((size_t)std::max(std::max(n_table, n_slots), 1));
+  for (int i = 0; i < n_table; i++) {
+    sl[i].valid = valid[i]; sl[i].c_fact = c_fact[i]; sl[i].jac_stamp = jac_stamp[i]; sl[i].step_stamp = step_stamp[i]; sl[i].last_use = last_use[i];
+  }
+  out[0] = slot_nearest(sl.data(), n_slots, c, band, n_restarts, max_age, n_steps, step_age);
+  const int free_ = slot_first_free(sl.data(), n_slots, n_restarts, max_age);
+  out[1] = free_ >= 0 ? free_ : slot_lru(sl.data(), n_slots);
+}
+
+// HostBackend::drift_check on given Jacobian values: slot s is made from jv_slots[s] at c_fact[s] by HostBackend::factor with
+// keep_diag (valid[s] = 0: marked unused afterwards), then today's values jv_now are checked. jd_out[n_slots][N]: the saved
+// diagonals; valid_out[n_slots]: the slots' flags afterwards; returns the number dropped
+int res_host_drift_check(void* hv, int n_slots, const double* jv_slots, const double* c_fact, const int32_t* valid, const double* jv_now,
+                         double max_drift, double* jd_out, int32_t* valid_out) {
+  HostNet* n = (HostNet*)hv;
+  ResParams P{};
+  P.n_slots = n_slots; P.sol_cap = 1;
+  HostBackend B(*n, P);
+  const size_t nnz = (size_t)n->H.nnz();
+  for (int s = 0; s < n_slots; s++) {
+    std::copy(jv_slots + (size_t)s * nnz, jv_slots + (size_t)(s + 1) * nnz, B.jv.begin());
+    (void)B.factor(s, c_fact[s], true);
+    B.slot_made(s, c_fact[s], s + 1, 0, 0);
+    if (!valid[s]) B.slot_drop(s);
+  }
+  std::copy(jv_now, jv_now + nnz, B.jv.begin());
+  const int dropped = B.drift_check(max_drift);
+  std::copy(B.jd.begin(), B.jd.end(), jd_out);
+  for (int s = 0; s < n_slots; s++) valid_out[s] = B.slots[s].valid;
+  return dropped;
+}
+
 // the solve: same arguments as kin_solve (static rates k0 when n_stops == 0); out_t / out_u sized by res_host_rows
 int64_t res_host_rows(const kin_params* p) { return make_res_grid(*p).cap; }
 int res_host_solve(void* hv, const kin_params* p, const double* u0, const double* k0, const double* tstops, const double* T_stops,

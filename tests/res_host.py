@@ -10,7 +10,7 @@ import numpy as np
 from kinetica_jl_amd import capi
 
 _HERE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "native")
-_LIB = os.path.join(_HERE, "libkin_resident_host.so")
+_LIB = os.environ.get("KIN_RES_HOST_PATH", os.path.join(_HERE, "libkin_resident_host.so"))   # (override: mutation checks)
 _lib = None
 
 
@@ -43,12 +43,29 @@ def lib():
         L.res_host_rows.restype = c_int64
         L.res_host_rows.argtypes = [POINTER(capi.KinParams)]
         L.res_host_solve.argtypes = [c_void_p, POINTER(capi.KinParams), PD, PD, PD, PD, PD, c_int64, c_int, PD, PD, P64, POINTER(ResResult)]
+        P32 = POINTER(c_int32)
+        L.res_host_slot_rules.restype = None
+        L.res_host_slot_rules.argtypes = [c_int, P32, PD, P64, P64, P64, c_int, c_double, c_double, c_int64, c_int64, c_int64, c_int64, P32]
+        L.res_host_drift_check.argtypes = [c_void_p, c_int, PD, PD, P32, PD, c_double, PD, P32]
         _lib = L
     return _lib
 
 
 def _pd(a):
     return None if a is None else a.ctypes.data_as(POINTER(c_double))
+
+
+def slot_rules(table, q):
+    """(nearest, victim) of bdf_rules.hpp's slot_nearest / slot_first_free / slot_lru over HostBackend's slot records. table: dict of
+    valid, c_fact, jac_stamp, step_stamp, last_use arrays; q: dict of c, band, n_restarts, max_age, n_steps, step_age, n_slots"""
+    v = np.ascontiguousarray(table["valid"], np.int32)
+    cf = np.ascontiguousarray(table["c_fact"], np.float64)
+    st = [np.ascontiguousarray(table[k], np.int64) for k in ("jac_stamp", "step_stamp", "last_use")]
+    out = np.zeros(2, np.int32)
+    P32, P64 = POINTER(c_int32), POINTER(c_int64)
+    lib().res_host_slot_rules(len(v), v.ctypes.data_as(P32), _pd(cf), *[a.ctypes.data_as(P64) for a in st], int(q["n_slots"]), q["c"], q["band"],
+                              int(q["n_restarts"]), int(q["max_age"]), int(q["n_steps"]), int(q["step_age"]), out.ctypes.data_as(P32))
+    return int(out[0]), int(out[1])
 
 
 class HostResident:
@@ -77,6 +94,19 @@ class HostResident:
         x = np.empty(self.n)
         bad = lib().res_host_newton_solve(self._h, c, _pd(k), _pd(u), _pd(b), _pd(x))
         return x, bad
+
+    def drift_check(self, jv_slots, c_fact, valid, jv_now, max_drift):
+        """HostBackend::drift_check on slots made from the given Jacobian values (pattern order): (jd[ns][N], valid afterwards[ns],
+        number dropped)"""
+        jv_slots = np.ascontiguousarray(jv_slots, np.float64); jv_now = np.ascontiguousarray(jv_now, np.float64)
+        c_fact = np.ascontiguousarray(c_fact, np.float64); valid = np.ascontiguousarray(valid, np.int32)
+        ns = len(c_fact)
+        assert jv_slots.shape == (ns, len(jv_now))
+        jd = np.empty((ns, self.n)); after = np.zeros(ns, np.int32)
+        P32 = POINTER(c_int32)
+        n = lib().res_host_drift_check(self._h, ns, _pd(jv_slots), _pd(c_fact), valid.ctypes.data_as(P32), _pd(jv_now), float(max_drift),
+                                       _pd(jd), after.ctypes.data_as(P32))
+        return jd, after, n
 
     def solve(self, pars, u0, k0=None, tstops=None, T_stops=None, k_table=None, n_slots=0):
         u0 = np.ascontiguousarray(u0, np.float64)

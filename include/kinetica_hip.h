@@ -395,7 +395,12 @@ int kin_resident_probe(kin_network* h, int64_t K, const double* u, const double*
  * path 0: the host-driven kernels (launch_bdf_*, launch_rk_*), K = n_entries = 1, n is the caller's (the handle gives the device
  * and the stream); path 1: the corrector update fused into the solve's last gather launch (SparseLU::solve_newton), K = 1, n = the
  * handle's species count, op = NEWTON only; path 2: the lockstep ensemble's batched kernels, K members and n_entries list entries
- * in one launch (the list may permute the members or leave some out), n is the caller's.
+ * in one launch (the list may permute the members or leave some out), n is the caller's; paths 3 and 4: the resident kernel (one
+ * 512-thread workgroup per member, K members in one launch, n_entries = K, n = the handle's species count, the network must fit
+ * the kernel) in its default build (3: 256 registers per lane, phases as functions) and its shared-CU build (4: 128 registers,
+ * phases inlined), through the kernel's real dispatch - wavefront 0 builds the controller and calls ITS method (predict, change_D
+ * and interpolate form their coefficients and matrices on the device), the other seven wavefronts decode the posted command in
+ * worker_loop. See "Paths 3 and 4" below.
  *   state[K][KIN_STEP_ROWS][n], rows: 0-7 D; 8 y; 9 psi; 10 d; 11 scale; 12 f0; 13 f1; 14 ytmp; 15 cs; 16-22 the stage array
  *     K[7]; 23 x (solution vector); 24 out; 25 y_new; 26 u; 27 b. Uploaded, operated on, downloaded whole.
  *   ctrl[K][KIN_STEP_CTRL]: BdfCtrl as doubles - dy_norm_old, dy_norm, err_norm, err_m_norm, err_p_norm, crate, scratch[0..3],
@@ -403,12 +408,13 @@ int kin_resident_probe(kin_network* h, int64_t K, const double* u, const double*
  *   iarg[n_entries][KIN_STEP_IARGS]: 0 member; 1 order; 2 aux (ACCEPT_PREDICT: order of the accepted step; INIT_D: 1 = from
  *     ytmp; NORMS: 1 = with f1; RK_COMBINE: stages; VEC: the EnsVecOp; PREDICT on path 2: 1 = a predictor on its own);
  *     3 copy_out (ACCEPT, ACCEPT_PREDICT: the new state also into row 24); 4 go (ACCEPT_PREDICT: 1 = the launch is given
- *     &ctrl->spec_go as its go flag); 5 iter; 6 maxit; 7 publish_always; 8 crate_from_ctrl; 9 ban_negatives; 10 seq; 11 unused.
+ *     &ctrl->spec_go as its go flag); 5 iter; 6 maxit; 7 publish_always; 8 crate_from_ctrl; 9 ban_negatives; 10 seq; 11 row (paths
+ *     3 and 4: the solution row, 0 or 1, of INTERP and of VEC's save_y / set_time).
  *     (NEWTON on path 2 takes iter from entry 0 and the ensemble's fixed iteration limit.)
  *   darg[n_entries][KIN_STEP_DARGS]: 0 atol; 1 rtol; 2 h (INIT_D) / factor (CHANGE_D: the matrix is built by
  *     bdf_change_D_matrix(order, factor)) / the scalar of VEC's axpy; 3 upd; 4 tol; 5 rate_max; 6 crate0; 7 tol_first;
  *     8 dy_first_max; 9 c (path 1); 10-12 ts, t, h_abs (INTERP: weights from bdf_interp_weights); 13-19 stage weights
- *     (RK_COMBINE, RK_ERROR); the rest unused.
+ *     (RK_COMBINE, RK_ERROR); paths 3 and 4: 9 c; 20 c_fact; 21-23 ec, ec_m, ec_p (error constants of order, order - 1, order + 1).
  *   xloc[n] (NEWTON on paths 0 and 2): a permutation of 0 .. n-1; row 23 is scattered into the W buffer through it.
  *   Operands: INIT_D y (or ytmp), f0 -> D; PREDICT / ACCEPT / ACCEPT_PREDICT / CHANGE_D as the integrators call them; INTERP
  *     -> row 24; NORMS y, f0, f1 -> ctrl; NEWTON row 23, scale, y, d, D -> y, d, ctrl; RK_COMBINE y, K -> row 24; RK_ERROR
@@ -418,7 +424,25 @@ int kin_resident_probe(kin_network* h, int64_t K, const double* u, const double*
  *     sequence word; unpublished: every integer field -1, every double NaN, sequence word 0.
  *   info[8], path 1: the stage-C plan's ELL groups, one-wavefront rows, of those with more than 256 entries, whole-workgroup
  *     rows, its longest row, the dense block size m, the launch's grid size and workgroup size. Other paths: zeros.
- * KIN_ERR_UNSUPPORTED: path 1 on a handle whose analysis has no fused solve or m = 0, an op a path does not have;
+ *   Paths 3 and 4. Rows 0-7 ARE the member's T.D, 12-15 its f0 / f1 / ytmp / chunk_start, 24-25 rows 0 / 1 of its solution buffer,
+ *     26 its u0; rows 8-11 are loaded into the kernel's LDS arrays y / psi / d / scale before the operation and stored back after
+ *     it. Operations: VEC (aux: 0 load_u0 .. 5 ytmp_axpy with h; 6 save_y(row, t); 8 set_time(row, t)), NORMS (aux: with f1),
+ *     INIT_D (aux: from ytmp), PREDICT (ctl->predict()), ACCEPT, CHANGE_D (ctl->change_D(order, factor)), INTERP
+ *     (ctl->interpolate(ts, row) with t, h_abs, order from the entry, then set_time(row, ts)), NEWTON and CORRECTOR: the Jacobian
+ *     at the state in row 26 with the handle's rates, I - c_fact J factorised into slot 0 (the vanished-pivot flag comes back in
+ *     lu_bad), then NEWTON: ONE iteration of the corrector (residual from y, psi, d at c; solve; update with upd), the x it used
+ *     in row 23; CORRECTOR (paths 3 and 4 only): the whole attempt b.corrector(in) - predictor from D, up to four iterations and
+ *     their decisions -, `in` from order, c, upd, rate_max, crate0, tol_first, tol, dy_first_max, ec*, atol, rtol.
+ *     ctrl: NORMS -> scratch0-3 = rms(y/w), rms(f0/w), rms((f1-f0)/w), max |f0|/(0.1|y|+w), nonfinite; NEWTON -> dy_norm,
+ *     err_norm, err_m_norm, err_p_norm = the RAW SUMS s, se, sm, sp of the iteration (not norms), any_negative = 0 / 1 shallow /
+ *     3 deep; CORRECTOR -> newton_done, converged, n_iter, nonfinite, any_negative (0 / 1 / 3), err_norm, err_m_norm, err_p_norm
+ *     (norms; 0 unless converged), crate; VEC's save_y / set_time and INTERP: scratch0 / scratch1 carry the times of solution rows
+ *     0 / 1 in and out. Every other field comes back as given. pub: unpublished.
+ *     info[8]: species N, trips of a 512-stride loop and wavefronts that own a species - all three counted by the kernel (-1:
+ *     the members disagree) -, dense block size
+ *     m, solve form (0 fused, 1 explicit, 2 plain), task descriptors in LDS (0/1), dynamic LDS bytes, waves per SIMD (2 or 4).
+ * KIN_ERR_UNSUPPORTED: path 1 on a handle whose analysis has no fused solve or m = 0, an op a path does not have (CORRECTOR on
+ * paths 0-2), a network that does not fit the resident kernel (paths 3 and 4);
  * KIN_ERR_INVALID_ARG: sizes, orders, members or xloc out of range; KIN_ERR_STATE: path 1 without rates. The handle is usable
  * afterwards (a later solve is bit for bit that of a fresh handle). Added under KIN_ABI_VERSION 6: look the symbol up. */
 #define KIN_STEP_ROWS 28
@@ -426,7 +450,7 @@ int kin_resident_probe(kin_network* h, int64_t K, const double* u, const double*
 #define KIN_STEP_IARGS 12
 #define KIN_STEP_DARGS 24
 enum { KIN_STEP_INIT_D = 0, KIN_STEP_PREDICT, KIN_STEP_ACCEPT, KIN_STEP_ACCEPT_PREDICT, KIN_STEP_CHANGE_D, KIN_STEP_INTERP,
-       KIN_STEP_NORMS, KIN_STEP_NEWTON, KIN_STEP_RK_COMBINE, KIN_STEP_RK_ERROR, KIN_STEP_VEC };
+       KIN_STEP_NORMS, KIN_STEP_NEWTON, KIN_STEP_RK_COMBINE, KIN_STEP_RK_ERROR, KIN_STEP_VEC, KIN_STEP_CORRECTOR };
 int kin_step_probe(kin_network* h, int32_t path, int32_t op, int64_t n, int64_t K, int64_t n_entries, const int32_t* iarg,
                    const double* darg, const int32_t* xloc, double* state, double* ctrl, double* pub, int64_t* info);
 

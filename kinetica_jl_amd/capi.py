@@ -46,9 +46,13 @@ STEP_ROWS, STEP_CTRL, STEP_IARGS, STEP_DARGS = 28, 18, 12, 24
 STEP_ROW = dict(D=0, y=8, psi=9, d=10, scale=11, f0=12, f1=13, ytmp=14, cs=15, K=16, x=23, out=24, y_new=25, u=26, b=27)
 STEP_CTRL_FIELDS = ("dy_norm_old", "dy_norm", "err_norm", "err_m_norm", "err_p_norm", "crate", "scratch0", "scratch1", "scratch2",
                     "scratch3", "newton_done", "converged", "n_iter", "nonfinite", "any_negative", "ticket", "lu_bad", "spec_go")
-STEP_OPS = dict(init_D=0, predict=1, accept=2, accept_predict=3, change_D=4, interp=5, norms=6, newton=7, rk_combine=8, rk_error=9, vec=10)
-STEP_VEC_OPS = dict(load_u0=0, cs_from_y=1, y_from_cs_clipped=2, y_from_d0=3, ytmp_from_d0=4, ytmp_axpy=5, save_y=6, interp=7)
-STEP_IARG_NAMES = ("member", "order", "aux", "copy_out", "go", "iter", "maxit", "publish_always", "crate_from_ctrl", "ban_negatives", "seq")
+STEP_OPS = dict(init_D=0, predict=1, accept=2, accept_predict=3, change_D=4, interp=5, norms=6, newton=7, rk_combine=8, rk_error=9, vec=10,
+                corrector=11)
+STEP_VEC_OPS = dict(load_u0=0, cs_from_y=1, y_from_cs_clipped=2, y_from_d0=3, ytmp_from_d0=4, ytmp_axpy=5, save_y=6, interp=7,
+                    set_time=8)      # (set_time: the resident kernel's paths only)
+STEP_IARG_NAMES = ("member", "order", "aux", "copy_out", "go", "iter", "maxit", "publish_always", "crate_from_ctrl", "ban_negatives", "seq",
+                   "row")
+STEP_DARG_TAIL = dict(c_fact=20, ec=21, ec_m=22, ec_p=23)      # (paths 3 and 4)
 STEP_DARG_NAMES = ("atol", "rtol", "h", "upd", "tol", "rate_max", "crate0", "tol_first", "dy_first_max", "c", "ts", "t", "h_abs")
 STEP_DARG_W = 13
 
@@ -909,12 +913,14 @@ class HipNetwork:
 
     def step_probe(self, path, op, state, ctrl, entries, xloc=None):
         """One operation of the step, once, on the caller's state (diagnostic, kin_step_probe; layouts: include/kinetica_hip.h).
-        path: 0 host-driven kernels, 1 the update fused into the solve, 2 the lockstep ensemble's kernels; op: a key of STEP_OPS;
+        path: 0 host-driven kernels, 1 the update fused into the solve, 2 the lockstep ensemble's kernels, 3 / 4 the resident kernel's
+        dispatch in its default / shared-CU build (one entry per member, n = the handle's species count); op: a key of STEP_OPS;
         state: (K, STEP_ROWS, n) or (STEP_ROWS, n); ctrl: (K, STEP_CTRL) or (STEP_CTRL,), in the order of STEP_CTRL_FIELDS;
         entries: a list of dicts (one dict: a list of one) with the integer keys of STEP_IARGS and the scalar keys of STEP_DARGS
         ("w": up to 7 stage weights), everything left out 0 except order = 1 and maxit = 4; xloc: permutation of 0 .. n-1.
         Returns dict(state, ctrl: copies after the operation, shaped as given; pub: the published block, STEP_CTRL values; seq: the
-        published sequence word; info: dict of the stage-C plan's groups, wave_rows, wave_rows_long, block_rows, max_row, m, grid, wg)."""
+        published sequence word; info: dict of the stage-C plan's groups, wave_rows, wave_rows_long, block_rows, max_row, m, grid, wg; on
+        paths 3 and 4 of N, trips, waves_owning, m, solve_form, desc_in_lds, dyn_lds, waves_per_eu)."""
         st = np.array(state, dtype=np.float64, order="C")
         ct = np.array(ctrl, dtype=np.float64, order="C")
         single = st.ndim == 2
@@ -933,6 +939,8 @@ class HipNetwork:
                     ia[e, STEP_IARG_NAMES.index(q)] = int(v)
                 elif q == "w":
                     da[e, STEP_DARG_W:STEP_DARG_W + len(v)] = v
+                elif q in STEP_DARG_TAIL:
+                    da[e, STEP_DARG_TAIL[q]] = float(v)
                 else:
                     da[e, STEP_DARG_NAMES.index(q)] = float(v)
         P32 = POINTER(c_int32)
@@ -942,7 +950,8 @@ class HipNetwork:
         info = np.zeros(8, np.int64)
         self._chk(lib().kin_step_probe(self._h, int(path), STEP_OPS[op], n, K, len(entries), ia.ctypes.data_as(P32), _pd(da),
                                        None if xl is None else xl.ctypes.data_as(P32), _pd(st3), _pd(ct2), _pd(pub), _p64(info)))
-        keys = ("groups", "wave_rows", "wave_rows_long", "block_rows", "max_row", "m", "grid", "wg")
+        keys = (("groups", "wave_rows", "wave_rows_long", "block_rows", "max_row", "m", "grid", "wg") if path < 3 else
+                ("N", "trips", "waves_owning", "m", "solve_form", "desc_in_lds", "dyn_lds", "waves_per_eu"))
         return dict(state=st3[0] if single else st3, ctrl=ct2[0] if ct.ndim == 1 else ct2, pub=pub[:STEP_CTRL], seq=int(pub[STEP_CTRL]),
                     info={k: int(v) for k, v in zip(keys, info)})
 

@@ -406,4 +406,65 @@ void resident_cache_probe(kin_network* h, int mode, int64_t n_slots, const doubl
   info[3] = RS.lu.m; info[4] = RS.lu.ns; info[5] = (int64_t)RS.dyn_lds;
 }
 
+// Diagnostic (kin_step_probe, paths 3 and 4): one operation of the step per member through the kernel's own dispatch
+// (resident_probe.hip / resident_probe_w4.hip, mode RES_PROBE_STEP), in the workspaces of the ResidentSolver every resident solve
+// of this handle uses. Each member's ResTrajDev points into its block of the caller's state: D at rows 0-7, f0 / f1 / ytmp /
+// chunk_start at rows 12-15, the two solution rows at 24-25, u0 at row 26; the times of the two solution rows travel in ctrl's
+// scratch0 / scratch1 for the operations that write them (VEC's save_y and set_time, INTERP). Arguments were checked by the caller.
+void resident_step_probe(kin_network* h, int waves_per_eu, int op, int64_t K, const ResStepArg* args, double* state, double* ctrl,
+                         int64_t* info) {
+  if (!resident_can_fit(h)) throw KinError(ERR_UNSUPPORTED, "network does not fit the resident integrator: its state and rates exceed the LDS");
+  ResidentSolver& RS = *get_resident(h);
+  if (!RS.ok) throw KinError(ERR_UNSUPPORTED, "network does not fit the resident integrator: " + RS.why);
+  hipStream_t s = h->stream;
+  const int64_t N = h->host.N, R = h->host.R;
+  const size_t per = (size_t)RES_STEP_ROWS * N;
+  const bool times = op == RES_STEP_SAVE_Y || op == RES_STEP_SET_TIME || op == RES_STEP_INTERP;
+  RS.ensure((int)K, 1, 2, false);
+  DevBuf<double> d_state, d_ctrl;
+  DevBuf<ResStepArg> d_args;
+  DevBuf<int32_t> d_shape;
+  std::vector<int32_t> h_shape((size_t)3 * K, 0);
+  d_shape.upload(h_shape, s);
+  d_state.upload(state, (size_t)K * per, s);
+  d_ctrl.upload(ctrl, (size_t)K * RES_STEP_CTRL, s);
+  d_args.upload(args, (size_t)K, s);
+  std::vector<double> solt((size_t)2 * K);
+  for (int64_t t = 0; t < K; t++) { solt[2 * t] = ctrl[t * RES_STEP_CTRL + 6]; solt[2 * t + 1] = ctrl[t * RES_STEP_CTRL + 7]; }
+  RS.d_solt.upload(solt.data(), solt.size(), s);
+  for (int64_t t = 0; t < K; t++) {
+    ResTrajDev& q = RS.h_traj[t];
+    double* blk = d_state.p + (size_t)t * per;
+    if (h->has_rates) KIN_HIP(hipMemcpyAsync(q.k, h->k.p, (size_t)R * sizeof(double), hipMemcpyDeviceToDevice, s));
+    q.D = blk;
+    q.f0 = blk + 12 * N; q.f1 = blk + 13 * N; q.ytmp = blk + 14 * N; q.chunk_start = blk + 15 * N;
+    q.sol = blk + 24 * N;
+    q.u0 = blk + 26 * N;
+  }
+  ResParams P{};
+  P.n_slots = 1;
+  RS.hn.Ea = h->Ea.p; RS.hn.A = h->A.p; RS.hn.has_kmax = h->has_kmax ? 1 : 0; RS.hn.k_max = h->k_max; RS.hn.t_mult = h->t_mult;
+  RS.d_net.upload(&RS.hn, 1, s);
+  RS.d_par.upload(&P, 1, s);
+  RS.d_traj.upload(RS.h_traj.data(), (size_t)K, s);
+  ResProbeIO io{};
+  io.mode = RES_PROBE_STEP; io.step_op = op; io.step_arg = d_args.p; io.state = d_state.p; io.ctrl = d_ctrl.p; io.out_i = d_shape.p;
+  if (waves_per_eu == 4) launch_resident_probe_shared_cu((int)K, RS.dyn_lds, RS.d_net.p, RS.d_traj.p, RS.d_par.p, io, s);
+  else launch_resident_probe((int)K, RS.dyn_lds, RS.d_net.p, RS.d_traj.p, RS.d_par.p, io, s);
+  d_state.download(state, (size_t)K * per, s);
+  d_ctrl.download(ctrl, (size_t)K * RES_STEP_CTRL, s);
+  RS.d_solt.download(solt.data(), solt.size(), s);
+  d_shape.download(h_shape.data(), h_shape.size(), s);
+  KIN_HIP(hipStreamSynchronize(s));
+  if (times)
+    for (int64_t t = 0; t < K; t++) { ctrl[t * RES_STEP_CTRL + 6] = solt[2 * t]; ctrl[t * RES_STEP_CTRL + 7] = solt[2 * t + 1]; }
+  // N, trips and owning wavefronts as the kernel counted them (every member must report the same: -1 otherwise)
+  for (int q = 0; q < 3; q++) {
+    info[q] = h_shape[q];
+    for (int64_t t = 1; t < K; t++) if (h_shape[3 * t + q] != h_shape[q]) info[q] = -1;
+  }
+  info[3] = RS.lu.m; info[4] = RS.hn.solve_mode;
+  info[5] = RS.hn.desc_in_lds; info[6] = (int64_t)RS.dyn_lds; info[7] = waves_per_eu;
+}
+
 }  // namespace kin

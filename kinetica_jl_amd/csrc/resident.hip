@@ -1010,8 +1010,8 @@ struct DevBackend {
   }
 };
 
-#ifndef RES_LINALG_PROBE   // (the probe kernel runs its phases directly)
-// what the seven other wavefronts do: wait for a command, run its phase, until the leader posts OP_EXIT
+// what the seven other wavefronts do: wait for a command, run its phase, until the leader posts OP_EXIT (the probe builds run it
+// in their step mode)
 __device__ void worker_loop() {
   // (profile: what the first worker wavefront spends waiting for the next command = the controller's own time between
   // two phases, incl. the calls' register saves and the posting)
@@ -1045,7 +1045,6 @@ __device__ void worker_loop() {
     }
   }
 }
-#endif
 
 // counts of medium rows with more than 64 / more than 32 entries (the rows are sorted longest first); all threads
 __device__ __forceinline__ void count_splits(int id) {
@@ -1065,7 +1064,8 @@ __shared__ __attribute__((aligned(16))) unsigned char g_ctl_mem[sizeof(ResidentB
 //   4: 128 VGPRs (a few spills in the corrector, the factorisation and the order change), TWO workgroups share a compute
 //      unit and hide each other's latencies: an ensemble of more members than compute units gets 20-40 % more solves/s at
 //      300 species (4 000-4 600 against 3 300-3 600), a single member is 10-15 % slower (resident.cpp picks per launch).
-// A third, diagnostic build (resident_probe.hip: RES_LINALG_PROBE) has resident_probe_kernel in place of resident_bdf_kernel.
+// The diagnostic builds (resident_probe.hip, resident_probe_w4.hip: RES_LINALG_PROBE at either register budget) have
+// resident_probe_kernel in place of resident_bdf_kernel.
 #ifndef RES_WAVES_PER_EU
 #define RES_WAVES_PER_EU 2
 #endif
@@ -1153,11 +1153,102 @@ __device__ void probe_rules(const ResProbeIO& io) {
   }
 }
 
+// RES_PROBE_STEP (resident.hpp): one operation of the step on the member's block, through the product's dispatch. The LDS arrays
+// are loaded from rows 8-11 by all threads, then wavefronts 1-7 enter worker_loop and wavefront 0 builds the controller in
+// g_ctl_mem, fills g_sh.gamma as resident_bdf_kernel does, calls ONE method of the controller or the backend and posts OP_EXIT on
+// every way out (a leader that returned without it would leave seven wavefronts at worker_loop's barrier); all threads then store
+// the LDS arrays back. NEWTON and CORRECTOR first make slot 0 from the state in T.u0 (row 26): ph_jac, ph_factor(0, c_fact, false)
+// by all threads, its vanished-pivot flag into ctrl's lu_bad. A single newton_body iteration is no command of the product (an
+// attempt's iterations run inside OP_CORRECTOR): NEWTON calls it with all threads directly and returns the x it used in row 23.
+// ctrl fields (BdfCtrl as doubles): 1 dy_norm, 2 err_norm, 3 err_m_norm, 4 err_p_norm, 5 crate, 6-9 scratch, 10 newton_done,
+// 11 converged, 12 n_iter, 13 nonfinite, 14 any_negative, 16 lu_bad.
+__device__ void probe_step(const ResProbeIO& io) {
+  const int N = uni(g_cx.N), tid = threadIdx.x, op = uni(io.step_op);
+  const ResStepArg A = io.step_arg[blockIdx.x];
+  gd_t* blk = glob(io.state) + (size_t)blockIdx.x * RES_STEP_ROWS * N;
+  gd_t* ctrl = glob(io.ctrl) + (size_t)blockIdx.x * RES_STEP_CTRL;
+  double* lds[4] = {L_y(), L_psi(), L_d(), L_scale()};
+  // the shape this workgroup has, counted by the kernel itself (out_i[3] per member, zeroed by the host): N as the phases read it,
+  // thread 0's trips through a 512-stride loop, the wavefronts whose first lane owns a species
+  {
+    int32_t* shape = io.out_i + 3 * blockIdx.x;
+    if ((tid & 63) == 0 && tid < N) atomicAdd(&shape[2], 1);
+    if (tid == 0) {
+      int trips = 0;
+      for (int i = tid; i < N; i += RES_WG) trips++;
+      shape[0] = N; shape[1] = trips;
+    }
+  }
+  const bool linalg = op == RES_STEP_NEWTON || op == RES_STEP_CORRECTOR;
+  if (linalg) {
+    ph_vec(VO_LOAD_U0, 0.0);
+    ph_jac();
+    const bool bad = ph_factor(0, A.c_fact, false);
+    if (tid == 0) ctrl[16] = bad ? 1.0 : 0.0;
+  }
+  for (int q = 0; q < 4; q++)
+    for (int i = tid; i < N; i += RES_WG) lds[q][i] = blk[(size_t)(RES_STEP_ROW_Y + q) * N + i];
+  __syncthreads();
+  if (op == RES_STEP_NEWTON) {
+    const ResCorrIn& in = A.in;
+    const ResSums q = newton_body(0, in.c, in.upd, in.order, in.ec, in.ec_m, in.ec_p, in.atol, in.rtol);
+    const double* win = L_win();
+    gci_t* xloc = glob(g_cx.net->xloc);
+    for (int i = tid; i < N; i += RES_WG) blk[(size_t)RES_STEP_ROW_X * N + i] = win[xloc[i]];
+    if (tid == 0) {   // the raw sums
+      ctrl[1] = q.s; ctrl[2] = q.se; ctrl[3] = q.sm; ctrl[4] = q.sp;
+      ctrl[14] = q.neg >= RES_NEG_MARK ? 3.0 : (q.neg > 0.0 ? 1.0 : 0.0);
+    }
+  } else if (tid >= 64) {
+    worker_loop();
+  } else {
+    DevBackend b;
+    ResidentBdf<DevBackend>* ctl = new (g_ctl_mem) ResidentBdf<DevBackend>(b, g_par);
+    if (tid <= RES_MAX_ORDER) g_sh.gamma[tid] = ctl->gamma[tid];   // (ordered by the first command's barrier)
+    const bool ok = A.order >= 1 && A.order <= RES_MAX_ORDER && (A.row == 0 || A.row == 1) && A.aux >= 0 && A.aux <= VO_YTMP_AXPY;
+    if (ok) {
+      ctl->order = A.order; ctl->atol = A.atol; ctl->rtol = A.rtol;
+      switch (op) {
+        case RES_STEP_VEC: b.vec(A.aux, A.h); break;
+        case RES_STEP_SAVE_Y: b.save_y(A.row, A.t); break;
+        case RES_STEP_SET_TIME: b.set_time(A.row, A.t); break;
+        case RES_STEP_NORMS: {
+          const ResNorms n = b.norms(A.aux != 0, A.atol, A.rtol);
+          if (tid == 0) { ctrl[6] = n.d0; ctrl[7] = n.d1; ctrl[8] = n.d2; ctrl[9] = n.dmax; ctrl[13] = n.nonfinite; }
+        } break;
+        case RES_STEP_INIT_D: b.init_D(A.aux != 0, A.h); break;
+        case RES_STEP_PREDICT: ctl->predict(); break;
+        case RES_STEP_ACCEPT: b.accept(A.order); break;
+        case RES_STEP_CHANGE_D: ctl->change_D(A.order, A.h); break;
+        case RES_STEP_INTERP:
+          ctl->t = A.t; ctl->h_abs = A.h_abs;
+          ctl->interpolate(A.ts, A.row);
+          b.set_time(A.row, A.ts);
+          break;
+        case RES_STEP_CORRECTOR: {
+          const ResAttempt a = b.corrector(A.in, ctl->gamma);
+          if (tid == 0) {
+            ctrl[2] = a.err; ctrl[3] = a.err_m; ctrl[4] = a.err_p; ctrl[5] = a.crate;
+            ctrl[10] = a.done; ctrl[11] = a.converged; ctrl[12] = a.n_iter; ctrl[13] = a.nonfinite;
+            ctrl[14] = a.deep_negative ? 3.0 : (a.any_negative ? 1.0 : 0.0);
+          }
+        } break;
+        default: break;
+      }
+    }
+    b.post(OP_EXIT);
+  }
+  __syncthreads();
+  for (int q = 0; q < 4; q++)
+    for (int i = tid; i < N; i += RES_WG) blk[(size_t)(RES_STEP_ROW_Y + q) * N + i] = lds[q][i];
+}
+
 __global__ __launch_bounds__(RES_WG) __attribute__((amdgpu_waves_per_eu(RES_WAVES_PER_EU, RES_WAVES_PER_EU))) void resident_probe_kernel(const ResNetDev* __restrict__ net_p, const ResTrajDev* __restrict__ traj,
                                                                  const ResParams* __restrict__ par_p, ResProbeIO io) {
 #include "resident_prologue.inc"
   if (io.mode == RES_PROBE_DRIFT) { probe_drift(io); return; }
   if (io.mode == RES_PROBE_RULES) { probe_rules(io); return; }
+  if (io.mode == RES_PROBE_STEP) { probe_step(io); return; }
   const int N = uni(g_cx.N), tid = threadIdx.x;
   const size_t mb = blockIdx.x;
   ph_vec(VO_LOAD_U0, 0.0);
@@ -1182,7 +1273,13 @@ __global__ __launch_bounds__(RES_WG) __attribute__((amdgpu_waves_per_eu(RES_WAVE
 }  // namespace
 
 #ifdef RES_LINALG_PROBE
-void launch_resident_probe(int K, size_t dyn_lds, const ResNetDev* d_net, const ResTrajDev* d_traj, const ResParams* d_par, const ResProbeIO& io,
+// (one probe launcher per register budget, as RES_LAUNCH_NAME below)
+#if RES_WAVES_PER_EU == 2
+#define RES_PROBE_LAUNCH_NAME launch_resident_probe
+#else
+#define RES_PROBE_LAUNCH_NAME launch_resident_probe_shared_cu
+#endif
+void RES_PROBE_LAUNCH_NAME(int K, size_t dyn_lds, const ResNetDev* d_net, const ResTrajDev* d_traj, const ResParams* d_par, const ResProbeIO& io,
                            hipStream_t s) {
   if (K <= 0) return;
   static std::atomic<unsigned long long> attr_set{0};   // (per device, as launch_resident)

@@ -62,15 +62,31 @@ size_t resident_static_lds();    // static LDS of the kernel (what two co-reside
 // drift[n_slots] = g_sh.drift, out_i[n_slots] = the slot table's valid flags afterwards, out_i[RES_MAX_SLOTS] = its return value;
 // RES_PROBE_RULES - the slot table valid / c_fact / stamps[3][n_slots] (jac_stamp, step_stamp, last_use), n_queries queries
 // qd[q][2] = c, band, qi[q][5] = n_restarts, max_age, n_steps, step_age, slot count: out_i[q][2] = nearest_slot, victim_slot.
-enum : int { RES_PROBE_NEWTON = 0, RES_PROBE_DRIFT = 1, RES_PROBE_RULES = 2 };
+// The step mode (kin_step_probe, paths 3 and 4; one workgroup per member): RES_PROBE_STEP - ONE operation of the step on the member's
+// block state[RES_STEP_ROWS][N] of the caller (kinetica_hip.h: rows 0-7 are T.D, 12-15 T.f0 / f1 / ytmp / chunk_start, 24-25 the two
+// rows of T.sol, 26 T.u0 - the host points the member's ResTrajDev there; rows 8-11 are loaded into the LDS arrays y / psi / d /
+// scale before the operation and stored back after it), run the way resident_bdf_kernel runs it: wavefronts 1-7 in worker_loop,
+// wavefront 0 with a controller in g_ctl_mem calling the controller's or the backend's method. Results that are scalars go to the
+// member's ctrl[RES_STEP_CTRL] (the fields of BdfCtrl as doubles); what an operation does not return stays as uploaded.
+enum : int { RES_PROBE_NEWTON = 0, RES_PROBE_DRIFT = 1, RES_PROBE_RULES = 2, RES_PROBE_STEP = 3 };
+constexpr int RES_STEP_ROWS = 28, RES_STEP_CTRL = 18, RES_STEP_ROW_Y = 8, RES_STEP_ROW_X = 23;
+enum : int { RES_STEP_VEC = 0, RES_STEP_SAVE_Y, RES_STEP_SET_TIME, RES_STEP_NORMS, RES_STEP_INIT_D, RES_STEP_PREDICT, RES_STEP_ACCEPT,
+             RES_STEP_CHANGE_D, RES_STEP_INTERP, RES_STEP_NEWTON, RES_STEP_CORRECTOR, RES_STEP_OP_COUNT };
+// one member's arguments: aux = the VecOp / with_f1 / from_ytmp; row = the solution row; h = VEC's h0, INIT_D's h, CHANGE_D's factor;
+// t, h_abs, ts: INTERP (t also the time of SAVE_Y / SET_TIME); c_fact: what slot 0 is factorised at (NEWTON, CORRECTOR: `in`)
+struct ResStepArg { int32_t order, aux, row, pad; double atol, rtol, h, t, h_abs, ts, c_fact; ResCorrIn in; };
 struct ResProbeIO {
   const double *c, *b; double* x; int32_t* bad;
   int32_t mode, n_slots, n_queries;
   const double *jv_slots, *jv_now, *c_fact; const int32_t* valid; double max_drift;
   const long long* stamps; const double* qd; const long long* qi;
   double* drift; int32_t* out_i;
+  int32_t step_op, pad_; const ResStepArg* step_arg; double *state, *ctrl;   // RES_PROBE_STEP
 };
 void launch_resident_probe(int K, size_t dyn_lds, const ResNetDev* d_net, const ResTrajDev* d_traj, const ResParams* d_par, const ResProbeIO& io,
                            hipStream_t s);
+// the same probe kernel in the shared-CU build (resident_probe_w4.hip: 128 VGPRs, phases inlined, as resident_w4.hip)
+void launch_resident_probe_shared_cu(int K, size_t dyn_lds, const ResNetDev* d_net, const ResTrajDev* d_traj, const ResParams* d_par,
+                                     const ResProbeIO& io, hipStream_t s);
 
 }  // namespace kin

@@ -70,6 +70,12 @@ void resident_probe(kin_network* h, int64_t K, const double* u, const double* c,
 void resident_cache_probe(kin_network* h, int mode, int64_t n_slots, const double* jv_slots, const double* c_fact, const int32_t* valid,
                           const double* jv_now, double max_drift, const int64_t* stamps, int64_t n_queries, const double* qd, const int64_t* qi,
                           double* jd, double* drift, int32_t* out_i, int64_t* info);
+// diagnostic (kin_step_probe, paths 3 and 4): one operation of the step (resident.hpp: RES_STEP_*) for K members through the resident
+// kernel's own dispatch, default build (waves_per_eu 2) or shared-CU build (4). args[K], state[K][RES_STEP_ROWS][N] and
+// ctrl[K][RES_STEP_CTRL] are indexed by member; state and ctrl are uploaded, operated on and downloaded whole. info[8]: the header
+struct ResStepArg;
+void resident_step_probe(kin_network* h, int waves_per_eu, int op, int64_t K, const ResStepArg* args, double* state, double* ctrl,
+                         int64_t* info);
 // can the lockstep form (ensemble.cpp) take this network's factorisation? (fused solve with a dense Schur block)
 bool ensemble_batched_supported(kin_network* h, std::string* why);
 // K members of a network beyond that, advanced in lockstep rounds of batched launches (ensemble.cpp)

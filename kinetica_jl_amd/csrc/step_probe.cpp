@@ -1,7 +1,9 @@
 // kin_step_probe (declaration and argument layout: include/kinetica_hip.h): one operation of the step, once, on the caller's
 // state, through the launchers the integrators use - launch_bdf_* / launch_rk_* (path 0), SparseLU::solve_newton (path 1,
-// solver.cpp: step_probe_fused), the ens_* launchers of the lockstep ensemble (path 2). Nothing here computes: the probe uploads,
-// fills the launchers' arguments the way Solver / MemberBackend fill them, launches, downloads.
+// solver.cpp: step_probe_fused), the ens_* launchers of the lockstep ensemble (path 2), the resident kernel's own dispatch in its
+// default and its shared-CU build (paths 3 and 4, resident.cpp: resident_step_probe - the kernel's leader wavefront calls the
+// controller's or the backend's method, the other seven decode the command in worker_loop). Nothing here computes: the probe
+// uploads, fills the launchers' arguments the way Solver / MemberBackend / ResidentBdf fill them, launches, downloads.
 #include "../../include/kinetica_hip.h"
 
 #include <algorithm>
@@ -10,6 +12,7 @@
 
 #include "ensemble.hpp"
 #include "handle.hpp"
+#include "resident.hpp"
 #include "solver.hpp"
 #include "solver_kernels.hpp"
 
@@ -25,8 +28,12 @@ enum Row : int { ROW_D = 0, ROW_Y = 8, ROW_PSI, ROW_DD, ROW_SCALE, ROW_F0, ROW_F
                  ROW_U, ROW_B };
 static_assert(ROW_B + 1 == KIN_STEP_ROWS && BDF_D_ROWS == 8, "row layout of kin_step_probe");
 // argument slots (kinetica_hip.h)
-enum : int { IA_REP = 0, IA_ORDER, IA_AUX, IA_COPY_OUT, IA_GO, IA_ITER, IA_MAXIT, IA_PUBLISH, IA_CRATE_CTRL, IA_BAN_NEG, IA_SEQ };
-enum : int { DA_ATOL = 0, DA_RTOL, DA_H, DA_UPD, DA_TOL, DA_RATE_MAX, DA_CRATE0, DA_TOL_FIRST, DA_DY_FIRST_MAX, DA_C, DA_TS, DA_T, DA_HABS, DA_W };
+enum : int { IA_REP = 0, IA_ORDER, IA_AUX, IA_COPY_OUT, IA_GO, IA_ITER, IA_MAXIT, IA_PUBLISH, IA_CRATE_CTRL, IA_BAN_NEG, IA_SEQ, IA_ROW };
+enum : int { DA_ATOL = 0, DA_RTOL, DA_H, DA_UPD, DA_TOL, DA_RATE_MAX, DA_CRATE0, DA_TOL_FIRST, DA_DY_FIRST_MAX, DA_C, DA_TS, DA_T, DA_HABS, DA_W,
+             DA_C_FACT = 20, DA_EC, DA_EC_M, DA_EC_P };
+static_assert(RES_STEP_ROWS == KIN_STEP_ROWS && RES_STEP_CTRL == KIN_STEP_CTRL && DA_EC_P + 1 == KIN_STEP_DARGS && IA_ROW + 1 == KIN_STEP_IARGS,
+              "layouts of the resident kernel's step mode");
+constexpr int VEC_SAVE_Y = 6, VEC_SET_TIME = 8;   // (EnsVecOp's EV_SAVE_Y; set_time exists on paths 3 and 4 only)
 
 void ctrl_from(const double* v, BdfCtrl& c) {
   c.dy_norm_old = v[0]; c.dy_norm = v[1]; c.err_norm = v[2]; c.err_m_norm = v[3]; c.err_p_norm = v[4]; c.crate = v[5];
@@ -264,6 +271,58 @@ void step_probe(kin_network* h, int path, int op, int64_t n64, int64_t K, int64_
   pub[KIN_STEP_CTRL] = (double)*pin.hseq;
 }
 
+// paths 3 and 4: the resident kernel's own dispatch (resident.cpp: resident_step_probe). Everything the kernel indexes with - orders,
+// solution rows, members, the operation - is checked here, before any launch; the entries are reordered by member.
+void step_probe_resident(kin_network* h, int path, int op, int64_t n, int64_t K, int64_t ne, const int32_t* iarg, const double* darg,
+                         double* state, double* ctrl, double* pub, int64_t* info) {
+  require(n == h->host.N, ERR_INVALID_ARG, "the resident paths run on the handle's network: n must be its species count");
+  require(ne == K, ERR_INVALID_ARG, "the resident paths take one entry per member");
+  std::vector<ResStepArg> args((size_t)K);
+  std::vector<char> seen((size_t)K, 0);
+  BdfCoef cf;
+  bdf_fill_coef(cf.gamma, cf.alpha, cf.error_const);
+  int rop = -1;
+  for (int64_t e = 0; e < ne; e++) {
+    const int32_t* ia = iarg + e * KIN_STEP_IARGS; const double* da = darg + e * KIN_STEP_DARGS;
+    require(ia[IA_REP] >= 0 && ia[IA_REP] < K && !seen[ia[IA_REP]], ERR_INVALID_ARG, "entry names no member, or one member twice");
+    seen[ia[IA_REP]] = 1;
+    require(ia[IA_ORDER] >= 1 && ia[IA_ORDER] <= BDF_MAX_ORDER, ERR_INVALID_ARG, "order outside 1 .. 5");
+    require(ia[IA_ROW] == 0 || ia[IA_ROW] == 1, ERR_INVALID_ARG, "solution row outside {0, 1}");
+    int aux = ia[IA_AUX], r = -1;
+    switch (op) {
+      case KIN_STEP_VEC:
+        require((aux >= 0 && aux <= VEC_SAVE_Y) || aux == VEC_SET_TIME, ERR_INVALID_ARG, "unknown vector operation");
+        r = aux == VEC_SAVE_Y ? RES_STEP_SAVE_Y : (aux == VEC_SET_TIME ? RES_STEP_SET_TIME : RES_STEP_VEC);
+        if (r != RES_STEP_VEC) aux = 0;
+        break;
+      case KIN_STEP_NORMS: r = RES_STEP_NORMS; aux = aux ? 1 : 0; break;
+      case KIN_STEP_INIT_D: r = RES_STEP_INIT_D; aux = aux ? 1 : 0; break;
+      case KIN_STEP_PREDICT: r = RES_STEP_PREDICT; aux = 0; break;
+      case KIN_STEP_ACCEPT: r = RES_STEP_ACCEPT; aux = 0; break;
+      case KIN_STEP_CHANGE_D: r = RES_STEP_CHANGE_D; aux = 0; break;
+      case KIN_STEP_INTERP: r = RES_STEP_INTERP; aux = 0; break;
+      case KIN_STEP_NEWTON: r = RES_STEP_NEWTON; aux = 0; break;
+      case KIN_STEP_CORRECTOR: r = RES_STEP_CORRECTOR; aux = 0; break;
+      default: throw KinError(ERR_UNSUPPORTED, "the resident kernel has no such operation");
+    }
+    require(rop < 0 || rop == r, ERR_INVALID_ARG, "the entries of one launch name different operations");
+    rop = r;
+    ResStepArg& a = args[ia[IA_REP]];
+    a = ResStepArg{};
+    a.order = ia[IA_ORDER]; a.aux = aux; a.row = ia[IA_ROW];
+    a.atol = da[DA_ATOL]; a.rtol = da[DA_RTOL]; a.h = da[DA_H]; a.t = da[DA_T]; a.h_abs = da[DA_HABS]; a.ts = da[DA_TS]; a.c_fact = da[DA_C_FACT];
+    ResCorrIn& in = a.in;   // (ResidentBdf::corrector)
+    in.slot = 0; in.order = a.order; in.c = da[DA_C]; in.upd = da[DA_UPD]; in.rate_max = da[DA_RATE_MAX]; in.crate0 = da[DA_CRATE0];
+    in.tol_first = da[DA_TOL_FIRST]; in.newton_tol = da[DA_TOL]; in.dy_first_max = da[DA_DY_FIRST_MAX];
+    in.ec = da[DA_EC]; in.ec_m = da[DA_EC_M]; in.ec_p = da[DA_EC_P];
+    in.atol = da[DA_ATOL]; in.rtol = da[DA_RTOL]; in.alpha_o = cf.alpha[a.order];
+  }
+  if (rop == RES_STEP_NEWTON || rop == RES_STEP_CORRECTOR) require(h->has_rates, ERR_STATE, "rates were never set");
+  resident_step_probe(h, path == 4 ? 4 : 2, rop, K, args.data(), state, ctrl, info);
+  for (int i = 0; i < KIN_STEP_CTRL; i++) pub[i] = i < 10 ? NAN : -1.0;   // (nothing is published on these paths)
+  pub[KIN_STEP_CTRL] = 0.0;
+}
+
 }  // namespace
 
 extern "C" int kin_step_probe(kin_network* h, int32_t path, int32_t op, int64_t n, int64_t K, int64_t n_entries, const int32_t* iarg,
@@ -271,10 +330,15 @@ extern "C" int kin_step_probe(kin_network* h, int32_t path, int32_t op, int64_t 
   if (!h) return KIN_ERR_INVALID_ARG;
   try {
     KIN_HIP(hipSetDevice(h->device));
-    require(path >= 0 && path <= 2 && op >= KIN_STEP_INIT_D && op <= KIN_STEP_VEC, ERR_INVALID_ARG, "unknown path or operation");
+    require(path >= 0 && path <= 4 && op >= KIN_STEP_INIT_D && op <= KIN_STEP_CORRECTOR, ERR_INVALID_ARG, "unknown path or operation");
     require(n >= 1 && n <= (1 << 24) && K >= 1 && K <= 64 && n_entries >= 1 && n_entries <= K, ERR_INVALID_ARG, "n, K or n_entries out of range");
-    require(path == 2 || (K == 1 && n_entries == 1), ERR_INVALID_ARG, "paths 0 and 1 take one member");
+    require(path >= 2 || (K == 1 && n_entries == 1), ERR_INVALID_ARG, "paths 0 and 1 take one member");
     require(iarg && darg && state && ctrl && pub && info, ERR_INVALID_ARG, "null buffer");
+    if (path >= 3) {
+      step_probe_resident(h, path, op, n, K, n_entries, iarg, darg, state, ctrl, pub, info);
+      return KIN_OK;
+    }
+    require(op != KIN_STEP_CORRECTOR, ERR_UNSUPPORTED, "a whole corrector attempt is an operation of the resident kernel (paths 3 and 4)");
     if (path == 1) {
       require(n == h->host.N, ERR_INVALID_ARG, "the fused path runs on the handle's network: n must be its species count");
       require(h->has_rates, ERR_STATE, "rates were never set");

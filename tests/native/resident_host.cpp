@@ -438,6 +438,110 @@ int res_host_drift_check(void* hv, int n_slots, const double* jv_slots, const do
   return dropped;
 }
 
+// ONE operation of HostBackend or of the controller over it, on a state block laid out as kin_step_probe's paths 3 and 4 take it
+// (include/kinetica_hip.h: rows 0-7 D, 8-11 y / psi / d / scale, 12-15 f0 / f1 / ytmp / chunk_start, 23 x, 24-25 the two solution
+// rows, 26 u0; ctrl = BdfCtrl as doubles, scratch0 / scratch1 carry the times of the two solution rows for the operations that
+// write them) and with that probe's operation numbers: 0 VEC (aux = the operation), 1 SAVE_Y, 2 SET_TIME, 3 NORMS, 4 INIT_D,
+// 5 PREDICT, 6 ACCEPT, 7 CHANGE_D and 8 INTERP through ResidentBdf, 9 NEWTON (Jacobian at row 26, slot 0 factorised at c_fact, one
+// newton_iter_inner, the x it used into row 23, the raw sums into dy_norm / err_norm / err_m_norm / err_p_norm), 10 CORRECTOR
+// (b.corrector: the whole attempt). ia: order, aux, row; da: atol, rtol, h, t, h_abs, ts, c_fact, c, upd, rate_max, crate0,
+// tol_first, newton_tol, dy_first_max, ec, ec_m, ec_p. Returns 0, -1 for arguments out of range.
+int res_host_step_op(void* hv, int op, const int32_t* ia, const double* da, const double* k, double* state, double* ctrl) {
+  HostNet* n = (HostNet*)hv;
+  const int N = (int)n->H.N;
+  const int order = ia[0], aux = ia[1], row = ia[2];
+  if (order < 1 || order > RES_MAX_ORDER || row < 0 || row > 1 || op < 0 || op > 10 || (op == 0 && (aux < 0 || aux > 5))) return -1;
+  ResParams P{};
+  P.n_slots = 1; P.sol_cap = 2;
+  HostBackend B(*n, P);
+  if (k) std::copy(k, k + n->H.R, B.k.begin());
+  auto rowp = [&](int r) { return state + (size_t)r * N; };
+  std::copy(rowp(0), rowp(RES_D_ROWS), B.D.begin());
+  std::vector<double>* vecs[8] = {&B.y, &B.psi, &B.d, &B.scale, &B.f0, &B.f1, &B.ytmp, &B.chunk_start};
+  auto load = [&]() { for (int q = 0; q < 8; q++) std::copy(rowp(8 + q), rowp(9 + q), vecs[q]->begin()); };
+  load();
+  std::copy(rowp(24), rowp(26), B.sol.begin());
+  B.sol_t[0] = ctrl[6]; B.sol_t[1] = ctrl[7];
+  B.u0 = rowp(26);
+  ResidentBdf<HostBackend> ctl(B, P);
+  ctl.order = order; ctl.atol = da[0]; ctl.rtol = da[1];
+  ResCorrIn in;
+  in.slot = 0; in.order = order; in.c = da[7]; in.upd = da[8]; in.rate_max = da[9]; in.crate0 = da[10]; in.tol_first = da[11];
+  in.newton_tol = da[12]; in.dy_first_max = da[13]; in.ec = da[14]; in.ec_m = da[15]; in.ec_p = da[16];
+  in.atol = da[0]; in.rtol = da[1]; in.alpha_o = ctl.alpha[order];
+  if (op >= 9) {
+    B.load_u0();
+    B.eval_jac_y();
+    ctrl[16] = B.factor(0, da[6], false) ? 1.0 : 0.0;
+    load();
+  }
+  switch (op) {
+    case 0:
+      switch (aux) {
+        case 0: B.load_u0(); break;
+        case 1: B.chunk_start_from_y(); break;
+        case 2: B.y_from_chunk_start_clipped(); break;
+        case 3: B.y_from_D0(); break;
+        case 4: B.ytmp_from_D0(); break;
+        default: B.ytmp_axpy(da[2]);
+      }
+      break;
+    case 1: B.save_y(row, da[3]); break;
+    case 2: B.set_time(row, da[3]); break;
+    case 3: {
+      const ResNorms q = B.norms(aux != 0, da[0], da[1]);
+      ctrl[6] = q.d0; ctrl[7] = q.d1; ctrl[8] = q.d2; ctrl[9] = q.dmax; ctrl[13] = q.nonfinite;
+    } break;
+    case 4: B.init_D(aux != 0, da[2]); break;
+    case 5: ctl.predict(); break;
+    case 6: B.accept(order); break;
+    case 7: ctl.change_D(order, da[2]); break;
+    case 8: ctl.t = da[3]; ctl.h_abs = da[4]; ctl.interpolate(da[5], row); B.set_time(row, da[5]); break;
+    case 9: {
+      const ResSums q = B.newton_iter_inner(0, in.c, in.upd, order, in.ec, in.ec_m, in.ec_p, in.atol, in.rtol);
+      const auto& xloc = n->I(n->lu.xloc);
+      for (int i = 0; i < N; i++) rowp(23)[i] = B.slot_W(0)[xloc[i]];
+      ctrl[1] = q.s; ctrl[2] = q.se; ctrl[3] = q.sm; ctrl[4] = q.sp;
+      ctrl[14] = q.neg >= RES_NEG_MARK ? 3.0 : (q.neg > 0.0 ? 1.0 : 0.0);
+    } break;
+    default: {
+      const ResAttempt a = B.corrector(in, ctl.gamma);
+      ctrl[2] = a.err; ctrl[3] = a.err_m; ctrl[4] = a.err_p; ctrl[5] = a.crate;
+      ctrl[10] = a.done; ctrl[11] = a.converged; ctrl[12] = a.n_iter; ctrl[13] = a.nonfinite;
+      ctrl[14] = a.deep_negative ? 3.0 : (a.any_negative ? 1.0 : 0.0);
+    }
+  }
+  std::copy(B.D.begin(), B.D.end(), rowp(0));
+  for (int q = 0; q < 8; q++) std::copy(vecs[q]->begin(), vecs[q]->end(), rowp(8 + q));
+  std::copy(B.sol.begin(), B.sol.end(), rowp(24));
+  if (op == 1 || op == 2 || op == 8) { ctrl[6] = B.sol_t[0]; ctrl[7] = B.sol_t[1]; }
+  return 0;
+}
+
+// res_corrector_loop alone, over a scripted backend: iteration i of the attempt gets sums[i] = (s, se, sm, sp, neg) whatever its
+// arguments are. cin: order, c, upd, rate_max, crate0, tol_first, newton_tol, dy_first_max (the rest of ResCorrIn does not enter the
+// decisions). out: done, converged, nonfinite, any_negative, deep_negative, n_iter, err, err_m, err_p, crate, then the number of
+// predictor calls and of iterations the loop asked for
+void res_host_corrector_loop(int n_species, int n_sums, const double* sums, const double* cin, double* out) {
+  struct Scripted {
+    const double* s; int n, it = 0, predicts = 0;
+    void predict_inner(int, const double*, double, double, double) { predicts++; }
+    ResSums newton_iter_inner(int, double, double, int, double, double, double, double, double) {
+      const double* q = s + 5 * (it < n ? it : n - 1);
+      it++;
+      return ResSums{q[0], q[1], q[2], q[3], q[4]};
+    }
+  } b{sums, n_sums};
+  ResCorrIn in{};
+  in.order = (int)cin[0]; in.c = cin[1]; in.upd = cin[2]; in.rate_max = cin[3]; in.crate0 = cin[4]; in.tol_first = cin[5];
+  in.newton_tol = cin[6]; in.dy_first_max = cin[7];
+  double gamma[RES_MAX_ORDER + 1] = {};
+  const ResAttempt a = res_corrector_loop(b, in, gamma, n_species);
+  const double o[12] = {(double)a.done, (double)a.converged, (double)a.nonfinite, (double)a.any_negative, (double)a.deep_negative, (double)a.n_iter,
+                        a.err, a.err_m, a.err_p, a.crate, (double)b.predicts, (double)b.it};
+  std::copy(o, o + 12, out);
+}
+
 // the solve: same arguments as kin_solve (static rates k0 when n_stops == 0); out_t / out_u sized by res_host_rows
 int64_t res_host_rows(const kin_params* p) { return make_res_grid(*p).cap; }
 int res_host_solve(void* hv, const kin_params* p, const double* u0, const double* k0, const double* tstops, const double* T_stops,

@@ -47,6 +47,9 @@ def lib():
         L.res_host_slot_rules.restype = None
         L.res_host_slot_rules.argtypes = [c_int, P32, PD, P64, P64, P64, c_int, c_double, c_double, c_int64, c_int64, c_int64, c_int64, P32]
         L.res_host_drift_check.argtypes = [c_void_p, c_int, PD, PD, P32, PD, c_double, PD, P32]
+        L.res_host_step_op.argtypes = [c_void_p, c_int, P32, PD, PD, PD, PD]
+        L.res_host_corrector_loop.restype = None
+        L.res_host_corrector_loop.argtypes = [c_int, c_int, PD, PD, PD]
         _lib = L
     return _lib
 
@@ -66,6 +69,23 @@ def slot_rules(table, q):
     lib().res_host_slot_rules(len(v), v.ctypes.data_as(P32), _pd(cf), *[a.ctypes.data_as(P64) for a in st], int(q["n_slots"]), q["c"], q["band"],
                               int(q["n_restarts"]), int(q["max_age"]), int(q["n_steps"]), int(q["step_age"]), out.ctypes.data_as(P32))
     return int(out[0]), int(out[1])
+
+
+STEP_OPS = dict(vec=0, save_y=1, set_time=2, norms=3, init_D=4, predict=5, accept=6, change_D=7, interp=8, newton=9, corrector=10)
+STEP_DARGS = ("atol", "rtol", "h", "t", "h_abs", "ts", "c_fact", "c", "upd", "rate_max", "crate0", "tol_first", "tol", "dy_first_max", "ec",
+              "ec_m", "ec_p")
+ATTEMPT_FIELDS = ("done", "converged", "nonfinite", "any_negative", "deep_negative", "n_iter", "err", "err_m", "err_p", "crate", "predicts",
+                  "iterations")
+
+
+def corrector_loop(n_species, sums, order=3, c=1.0, upd=1.0, rate_max=1.0, crate0=1.0, tol_first=-1.0, tol=0.03, dy_first_max=0.2):
+    """res_corrector_loop (resident_core.hpp) over a scripted backend whose iteration i returns sums[i] = (s, se, sm, sp, neg):
+    dict of ATTEMPT_FIELDS"""
+    sums = np.ascontiguousarray(sums, np.float64).reshape(-1, 5)
+    cin = np.array([order, c, upd, rate_max, crate0, tol_first, tol, dy_first_max], np.float64)
+    out = np.zeros(len(ATTEMPT_FIELDS))
+    lib().res_host_corrector_loop(int(n_species), len(sums), _pd(sums), _pd(cin), _pd(out))
+    return dict(zip(ATTEMPT_FIELDS, out))
 
 
 class HostResident:
@@ -94,6 +114,18 @@ class HostResident:
         x = np.empty(self.n)
         bad = lib().res_host_newton_solve(self._h, c, _pd(k), _pd(u), _pd(b), _pd(x))
         return x, bad
+
+    def step_op(self, op, state, ctrl, entry, k=None):
+        """one operation of the replay's backend or controller on a state block of kin_step_probe's layout (res_host_step_op):
+        op: a key of STEP_OPS (vec: entry['aux'] = the vector operation 0 .. 5); entry: order, aux, row and the keys of STEP_DARGS,
+        everything left out 0 except order = 1. Returns (state, ctrl) after the operation, or None for arguments out of range."""
+        st = np.array(state, dtype=np.float64, order="C"); ct = np.array(ctrl, dtype=np.float64, order="C")
+        assert st.shape == (capi.STEP_ROWS, self.n) and ct.shape == (capi.STEP_CTRL,)
+        ia = np.array([entry.get("order", 1), entry.get("aux", 0), entry.get("row", 0)], np.int32)
+        da = np.array([float(entry.get(q, 0.0)) for q in STEP_DARGS])
+        kk = None if k is None else np.ascontiguousarray(k, np.float64)
+        rc = lib().res_host_step_op(self._h, STEP_OPS[op], ia.ctypes.data_as(POINTER(c_int32)), _pd(da), _pd(kk), _pd(st), _pd(ct))
+        return (st, ct) if rc == 0 else None
 
     def drift_check(self, jv_slots, c_fact, valid, jv_now, max_drift):
         """HostBackend::drift_check on slots made from the given Jacobian values (pattern order): (jd[ns][N], valid afterwards[ns],

@@ -136,7 +136,13 @@ def ref_change_D(D, order, factor):
     """D[:order + 1] <- (R(factor) R(1))^T D[:order + 1]. The matrix is built on the host in double (bdf_change_D_matrix) from
     a dyadic factor: an entry of M is one rounding (the quotient), R[i][j] a product of i such entries (<= 2 i roundings), an
     entry of R U a sum of order + 1 products of two such (<= 4 order + order + 1); the kernel adds order + 1 products and
-    additions. In all at most 7 order + 3 operations on sums of magnitudes (|R| |U|)^T |D|."""
+    additions. In all at most 7 order + 3 operations on sums of magnitudes (|R| |U|)^T |D|, i.e. (7 order + 4) u by the
+    module's (k + 1) u rule.
+    The resident kernel builds the same matrix ON THE DEVICE (ResidentBdf::change_D: bdf_change_D_matrix compiled for gfx950, where
+    the compiler may contract a product and the addition behind it into one fused multiply-add): the operations and their order are
+    the host's, a contraction removes a rounding and adds none, and the numerators i - 1 - factor j stay exact for a dyadic factor
+    either way - the count above covers it unchanged. The kernel's sum runs over all six columns with zeros beyond `order`
+    (ph_change_D): adding an exact zero rounds nothing."""
     D = D.astype(LD)
     RU, A = ru_matrix(order, factor)
     new = RU.T.dot(D[:order + 1])
@@ -168,6 +174,19 @@ def ref_interp(D, order, ts, t, h_abs):
     return {ROW["out"]: (v, (4 * order + 1) * U * (np.abs(D[0]) + np.abs(p * D[1:order + 1]).sum(axis=0)))}
 
 
+def ref_clipped(v):
+    """y <- chunk_start with the negative entries replaced by 0 (`v < 0 ? 0 : v`): a copy, so -0.0 (not below zero) and NaN (no
+    comparison holds) come back as they are, bit for bit"""
+    v = np.asarray(v, np.float64)
+    return np.where(v < 0, 0.0, v)
+
+
+def ref_axpy(y, f0, h0):
+    """ytmp = y + h0 f0: a product and a sum (fused or not) -> 3 u (|y| + |h0 f0|)"""
+    y = y.astype(LD); t = LD(h0) * f0.astype(LD)
+    return y + t, 3 * U * (np.abs(y) + np.abs(t))
+
+
 def ref_rk_combine(y, K, w, stages):
     """out = y + sum_{j < stages} w_j K_j: stages products, stages additions (the sum starts at 0, the state comes last)"""
     y = y.astype(LD); K = K.astype(LD); w = np.asarray(w, LD)[:, None]
@@ -185,6 +204,15 @@ def norm_with_bound(terms, errs, n):
     if S == 0:
         return norm, np.sqrt(errs.sum() / n)
     return norm, (errs.sum() + (n + 1) * U * S) / (2 * np.sqrt(S * n)) + 3 * U * norm
+
+
+def sum_with_bound(terms, errs, n):
+    """the raw sum S of n non-negative terms and its bound sum e_i + (n + 1) u S (module docstring: reduced quantities, before
+    the division and the square root); a non-finite sum is compared as it is"""
+    S = terms.sum()
+    if not np.isfinite(S):
+        return S, LD(0)
+    return S, errs.sum() + (n + 1) * U * S
 
 
 def sq_term(num, num_err, den, den_err, k):
@@ -226,7 +254,7 @@ def ref_norms(y, f0, f1, atol, rtol):
     return out
 
 
-def ref_newton_sums(x, scale, y, d, D, order, upd, atol, rtol):
+def ref_newton_sums(x, scale, y, d, D, order, upd, atol, rtol, x_err=None, scale_err=None, y_err=None, d_err=None):
     """One corrector update (OracleBDF._newton: dy = upd x, y += dy, d += dy) and the five sums the decision needs:
       s  = sum (dy / scale)^2                                  (update norm, scale of the predictor)
       se = sum (ec[order] d / w)^2, w = atol + rtol |y_new|     (error test, OracleBDF.step; + inf when y_new is not finite)
@@ -234,17 +262,24 @@ def ref_newton_sums(x, scale, y, d, D, order, upd, atol, rtol):
       sp = sum (ec[order + 1] (d - D[order + 1]) / w)^2, order < 5
       negative entries of y_new: any, and any below -NEG_DEEP w.
     dy: one product (2 u); y_new, d_new: one more addition -> 3 u (|.| + |dy|); w: a product and a sum on the computed y_new;
-    numerators of sm, sp: one more addition. Returns dict(y, d: (ref, bound); s, se, sm, sp: (terms, errs); neg, deep: bool)."""
+    numerators of sm, sp: one more addition. Returns dict(y, d: (ref, bound); s, se, sm, sp: (terms, errs); neg, deep: bool).
+    Non-finite inputs: s is Inf or NaN as its terms are. se of a non-finite y_new is given as +inf here; the kernels add +inf to the
+    term ec d_new / w squared, which is 0 for an infinite y_new under a finite update (w is infinite) - se is then exactly +inf -
+    and Inf / Inf or a NaN otherwise: there, and for sm and sp, only `not finite` is specified (the attempt reads !isfinite(se), and
+    nothing but the flag once s is non-finite).
+    x_err, scale_err, y_err, d_err: absolute error bounds of inputs that are computed values themselves (an attempt's later
+    iterations: tests/resident_step_cases.py); they enter where the input enters, |upd| x_err next to dy's own rounding."""
     x = x.astype(LD); scale = scale.astype(LD); y = y.astype(LD); d = d.astype(LD); D = D.astype(LD)
     z = np.zeros(len(x), LD)
+    x_err, scale_err, y_err, d_err = (z if e is None else np.asarray(e, LD) for e in (x_err, scale_err, y_err, d_err))
     with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
         dy = LD(upd) * x
-        dye = 2 * U * np.abs(dy)
+        dye = 2 * U * np.abs(dy) + abs(LD(upd)) * x_err
         yn, dn = y + dy, d + dy
-        yne = dye + 2 * U * (np.abs(y) + np.abs(dy))
-        dne = dye + 2 * U * (np.abs(d) + np.abs(dy))
+        yne = dye + y_err + 2 * U * (np.abs(y) + np.abs(dy))
+        dne = dye + d_err + 2 * U * (np.abs(d) + np.abs(dy))
         out = dict(y=(yn, yne + U * np.abs(yn)), d=(dn, dne + U * np.abs(dn)))
-        out["s"] = sq_term(dy, dye, scale, z, 1)
+        out["s"] = sq_term(dy, dye, scale, scale_err, 1)
         w = LD(atol) + LD(rtol) * np.abs(yn)
         we = LD(rtol) * yne + 3 * U * w
         ec = [LD(v) for v in ERRC]
@@ -382,12 +417,13 @@ def unit_rms(rng, n):
     return z * np.sqrt(n / np.sum(z * z))
 
 
-def newton_inputs(n, seed, order, g, upd=1.0, d_weights=0.05, negative=None, x_bad=None, y_inf=False):
+def newton_inputs(n, seed, order, g, upd=1.0, d_weights=0.05, negative=None, x_bad=None, y_inf=False, y_hook=None):
     """state for one corrector update whose norm is g error weights: y >= 1e-12 (positive: the sign of y_new is under the case's
     control), scale = ATOL + RTOL |y|, d of d_weights error weights, D[order], D[order + 1] of about a weight, rows of D above
     order + 1 the sentinel (at order 5 row 6 too: the order + 1 sum has nothing to read there); x = g z scale / upd, rms(z) = 1.
     negative: None | 'shallow' (the LAST element ends at -3 weights) | 'deep' (element n // 2 at -1e4 weights);
-    x_bad: a non-finite value for x[n // 3]; y_inf: y[n // 3] = inf with a finite update."""
+    x_bad: a non-finite value for x[n // 3]; y_inf: y[n // 3] = inf with a finite update; y_hook: y <- y_hook(y) before anything
+    is derived from it (tests/resident_step_cases.py ties the two species of a pair together)."""
     rng = np.random.default_rng(seed)
     st = make_state(n, seed, d_rows=min(order + 2, D_ROWS) if order < 5 else 6)
     y = 10.0 ** rng.uniform(-12, 0, n)
@@ -397,6 +433,8 @@ def newton_inputs(n, seed, order, g, upd=1.0, d_weights=0.05, negative=None, x_b
         y[n // 2] = -1e4 * ATOL
     if y_inf:
         y[n // 3] = np.inf
+    if y_hook is not None:
+        y = y_hook(y)
     scale = ATOL + RTOL * np.abs(y)
     scale[~np.isfinite(scale)] = 1.0
     st[ROW["y"]] = y

@@ -650,6 +650,61 @@ int kin_ensemble_drgep(kin_network* h, int pairing, const double* k, int64_t n_k
                        const double* T_rows /* [K*n_rows] */, const int64_t* targets, int64_t n_targets, int index_base, int accumulate,
                        double* importance /* [N] */);
 
+/* ---- timescale analysis: batched Jacobians, species lifetimes, quasi-steady-state error --------------------------------- */
+/* For a state u_b with rate constants k_b, chosen exactly as kin_flux_batched[_dev] chooses them (rows of k, the Arrhenius
+ * law at T[b], or the handle's current rates):
+ *   q_r, dq_r/du   the mass-action rate and its operand derivatives: 2A has ONE operand column with 2 k u, a collider is an
+ *                  ordinary operand
+ *   f_i  = sum_r nu_ir q_r                          (the right-hand side)
+ *   J_ij                                            the CSR pattern of kin_jac_pattern (sorted columns, diagonal always present)
+ *   d_i  = J_ii
+ *   g_i  = sum_j |J_ij|                             over the stored entries of row i, diagonal included
+ *   norm(b) = max_i g_i = ||J(u_b)||_inf            (bounds the spectral radius: the stiffness along a run)
+ *   e_i(b)  = |f_i| / |d_i|                         the instantaneous quasi-steady-state error (Turanyi, Tomlin & Pilling 1993):
+ *             exactly 0.0 where f_i == 0 (0/0 included), +Inf where d_i == 0 and f_i != 0 (a species nothing consumes is
+ *             never quasi-steady); never NaN for finite inputs
+ * and over the states that count, summary[3][N]:
+ *   row 0: decay_max_i = max_b (-d_i)     (1 / decay_max: the shortest lifetime tau_i = -1 / J_ii, Turanyi & Tomlin)
+ *   row 1: decay_min_i = min_b (-d_i)
+ *   row 2: qss_err_i   = max_b e_i(b)
+ * Maxima and minima are exact. With no counting state and accumulate == 0 the rows hold the identities -Inf, +Inf, 0.0;
+ * accumulate != 0: the current contents of summary take part (several solves folded into one summary, as in kin_drg_*).
+ * Every sum is formed in a fixed order and there are no atomics: results are bit-identical from call to call and do not
+ * depend on how the states are cut into blocks or slices (a per-state workspace of at most 256 MB per block;
+ * KIN_TS_BLOCK_STATES=n forces blocks of at most n states; KIN_TS_STAGES=1 or 2 ends every block after the rates or after
+ * the Jacobian entries and leaves the outputs behind that stage alone - a knob for timing the stages, never for results).
+ * At least one output must be requested; statuses and argument
+ * checks are those of kin_flux_batched[_dev] / kin_drg_*. B == 0 writes the identities, or leaves summary alone when
+ * accumulating. Added under KIN_ABI_VERSION 6: look the symbols up before calling them. */
+/* The Jacobian values of B states, vals[b][nnz] in the CSR order of kin_jac_pattern (kin_jac_values for many states, each
+ * with its own rate constants). Device pointers: only enqueues on `stream` (NULL: the handle's) once the workspace has its
+ * size; one stream per handle at a time. */
+int kin_jac_batched_dev(kin_network* h, int64_t B, const double* d_u, const double* d_k, const int64_t* d_k_row, const double* d_T,
+                        double* d_vals /* [B][nnz] */, void* stream);
+int kin_jac_batched(kin_network* h, int64_t B, const double* u, const double* k, int64_t n_k_rows, const int64_t* k_row, const double* T,
+                    double* vals /* [B][nnz] */);
+/* summary[3][N], diag[b][i] = d_i(b), err[b][i] = e_i(b), norm[b]: any of them may be NULL, not all. */
+int kin_timescale_batched_dev(kin_network* h, int64_t B, const double* d_u, const double* d_k, const int64_t* d_k_row, const double* d_T,
+                              int accumulate, double* d_summary /* [3][N] or NULL */, double* d_diag /* [B][N] or NULL */,
+                              double* d_err /* [B][N] or NULL */, double* d_norm /* [B] or NULL */, void* stream);
+int kin_timescale_batched(kin_network* h, int64_t B, const double* u, const double* k, int64_t n_k_rows, const int64_t* k_row,
+                          const double* T, int accumulate, double* summary /* [3][N] or NULL */, double* diag /* [B][N] or NULL */,
+                          double* err /* [B][N] or NULL */, double* norm /* [B] or NULL */);
+/* Over the saved states of the last kin_solve / over the stored ensemble, read where they live (arguments and statuses of
+ * kin_solution_drg / kin_ensemble_drg). row_begin leaves out the induction period: saved rows with an index below it take no
+ * part (in an ensemble: of every member), nor do the rows past n_saved[m]; the norm entries of rows that take no part are
+ * written as 0.0. row_begin < 0: KIN_ERR_INVALID_ARG. */
+int kin_solution_timescale(kin_network* h, const double* k, int64_t n_k_rows, const int64_t* k_row, const double* T_rows,
+                           int64_t row_begin, int accumulate, double* summary /* [3][N] or NULL */, double* norm /* [n_saved] or NULL */);
+int kin_ensemble_timescale(kin_network* h, const double* k, int64_t n_k_rows, const int64_t* k_row /* [K*n_rows] */,
+                           const double* T_rows /* [K*n_rows] */, int64_t row_begin, int accumulate, double* summary /* [3][N] or NULL */,
+                           double* norm /* [K*n_rows] or NULL */);
+/* Plan sizes without a device or a handle. info[4]: the stored entries of J, then the rows of J with <= 8, 9 .. 256 and > 256
+ * stored entries: the three classes of the row pass (a lane, a wavefront, a workgroup per row). */
+int kin_timescale_plan_host(int64_t n_species, int64_t n_reactions, const int64_t* reac_ptr, const int64_t* reac_idx,
+                            const int64_t* reac_sto, const int64_t* prod_ptr, const int64_t* prod_idx, const int64_t* prod_sto,
+                            int index_base, int64_t* info /* [4] */);
+
 /* ---- device / build information ------------------------------------------------------- */
 int kin_device_count(int* n);
 /* Selects the device for handles created afterwards by this thread; a handle remembers the device it was created on
@@ -663,7 +718,8 @@ const char* kin_version(void);
  * kin_lu_analyze_host - structs unchanged; 5: + kin_rhs_batched_klib_dev - structs unchanged; 6: + kin_solve_ensemble_continuous -
  * structs unchanged; kin_solve_ensemble_discrete, kin_resident_probe, kin_newton_probe, kin_step_probe, kin_eval_probe, kin_cache_probe, the flux pass (kin_flux_*, kin_solution_flux) and
  * kin_ensemble_size / _max / _dot / _flux and the directed relation graph (kin_drg_*, kin_solution_drg, kin_ensemble_drg) came
- * later under 6, found by symbol lookup; so did DRGEP: kin_drgep_*, kin_solution_drgep, kin_ensemble_drgep). */
+ * later under 6, found by symbol lookup; so did DRGEP: kin_drgep_*, kin_solution_drgep, kin_ensemble_drgep, and the timescale analysis:
+ * kin_jac_batched*, kin_timescale_*, kin_solution_timescale, kin_ensemble_timescale). */
 #define KIN_ABI_VERSION 6
 int kin_abi_version(void);
 int64_t kin_struct_size(int which); /* 0: sizeof(kin_params), 1: sizeof(kin_stats), else -1 */

@@ -35,6 +35,8 @@ SYMBOLS = [
     "kin_flux_segmented", "kin_flux_segmented_dev", "kin_ensemble_size", "kin_ensemble_max", "kin_ensemble_dot", "kin_ensemble_flux",
     "kin_drg_pattern_host", "kin_drg_pattern", "kin_drg_batched", "kin_drg_batched_dev", "kin_solution_drg", "kin_ensemble_drg",
     "kin_drgep_batched", "kin_drgep_batched_dev", "kin_drgep_paths", "kin_solution_drgep", "kin_ensemble_drgep",
+    "kin_jac_batched", "kin_jac_batched_dev", "kin_timescale_batched", "kin_timescale_batched_dev", "kin_solution_timescale",
+    "kin_ensemble_timescale", "kin_timescale_plan_host",
 ]
 # in-degree classes of the DRGEP path search (drg.hpp: IN_SHORT_MAX, IN_WAVE_MAX): a lane, a wavefront, the workgroup
 DRGEP_IN_SHORT_MAX, DRGEP_IN_WAVE_MAX = 32, 256
@@ -175,6 +177,14 @@ def lib():
             L.kin_drgep_paths.argtypes = [c_void_p, c_int, c_int64, PD, P64, c_int64, c_int, c_int, PD, PD, P32]
             L.kin_solution_drgep.argtypes = [c_void_p, c_int, PD, c_int64, P64, PD, P64, c_int64, c_int, c_int, PD]
             L.kin_ensemble_drgep.argtypes = [c_void_p, c_int, PD, c_int64, P64, PD, P64, c_int64, c_int, c_int, PD]
+        if hasattr(L, "kin_timescale_batched"):   # (also under ABI 6: the timescale analysis)
+            L.kin_jac_batched_dev.argtypes = [c_void_p, c_int64] + [c_void_p] * 6
+            L.kin_jac_batched.argtypes = [c_void_p, c_int64, PD, PD, c_int64, P64, PD, PD]
+            L.kin_timescale_batched_dev.argtypes = [c_void_p, c_int64] + [c_void_p] * 4 + [c_int] + [c_void_p] * 5
+            L.kin_timescale_batched.argtypes = [c_void_p, c_int64, PD, PD, c_int64, P64, PD, c_int, PD, PD, PD, PD]
+            L.kin_solution_timescale.argtypes = [c_void_p, PD, c_int64, P64, PD, c_int64, c_int, PD, PD]
+            L.kin_ensemble_timescale.argtypes = [c_void_p, PD, c_int64, P64, PD, c_int64, c_int, PD, PD]
+            L.kin_timescale_plan_host.argtypes = [c_int64, c_int64] + [P64] * 6 + [c_int, P64]
         L.kin_solve_ensemble.argtypes = [c_void_p, POINTER(KinParams), c_int64, PD, PD, PD, PD, PD, PD, c_int64, P64, PD, PD, P64,
                                          POINTER(c_int32), POINTER(KinStats)]
         L.kin_integrator_init.argtypes = [c_void_p, POINTER(KinParams), PD, PD, PD, PD, c_int64]
@@ -279,6 +289,25 @@ def drg_pattern_host(net, pairing=True):
     st = L.kin_drg_pattern_host(*head, _p64(info), _p64(rowptr), _p64(colidx))
     assert st == KIN_OK
     return rowptr, colidx[:int(info[0])], {k: int(v) for k, v in zip(DRG_INFO, info)}
+
+
+TIMESCALE_INFO = ("nnz", "rows_short", "rows_medium", "rows_long")
+# classes of the timescale row pass by stored entries of a Jacobian row (timescale.hpp: TS_SHORT_MAX, TS_WAVE_MAX), and the
+# entries a workgroup takes per pass of a long row or a long contribution list (TS_WG * TS_LONG_NX)
+TIMESCALE_SHORT_MAX, TIMESCALE_WAVE_MAX, TIMESCALE_LONG_PASS = 8, 256, 1024
+
+
+def timescale_plan_host(net):
+    """kin_timescale_plan_host of a FlatNetwork, computed on the host (no device): a dict of the TIMESCALE_INFO sizes - the
+    stored entries of the Jacobian and its rows by class of the row pass (<= 8, 9 .. 256, > 256 stored entries)."""
+    L = lib()
+    arrs = [np.ascontiguousarray(a, dtype=np.int64) for a in (net.reac_ptr, net.reac_idx, net.reac_sto, net.prod_ptr,
+                                                              net.prod_idx, net.prod_sto)]
+    info = np.zeros(len(TIMESCALE_INFO), np.int64)
+    st = L.kin_timescale_plan_host(int(net.n_species), int(net.n_reactions), *[_p64(a) for a in arrs], 0, _p64(info))
+    if st != KIN_OK:
+        raise KineticaHipError(st, "network has no timescale plan")
+    return {k: int(v) for k, v in zip(TIMESCALE_INFO, info)}
 
 
 def arrhenius_eval(Ea, A, T, k_max=None, t_mult=1.0):
@@ -630,6 +659,89 @@ class HipNetwork:
         self._chk(lib().kin_ensemble_drgep(self._h, int(bool(pairing)), _pd(k), n_rows, None if k_row is None else _p64(k_row),
                                            _pd(T_rows), _p64(tg), nt, 0, acc, _pd(out)))
         return out[:self.n]
+
+    # --- timescale analysis ---------------------------------------------------------------------
+    def _jac_nnz(self):
+        nnz = c_int64(0)
+        self._chk(lib().kin_jac_nnz(self._h, ctypes.byref(nnz)))
+        return nnz.value
+
+    def _ts_summary(self, summary):
+        """The summary buffer of a timescale entry: a fresh one, or (accumulate) a contiguous copy of `summary` that takes part."""
+        out = np.empty((3, self.n))
+        if summary is None:
+            return out, 0
+        c = _f64(summary)
+        assert c.shape == (3, self.n)
+        out[:] = c
+        return out, 1
+
+    def jac_batched(self, u, k=None, k_row=None, T=None):
+        """kin_jac_batched on host arrays: vals[B][nnz], the Jacobian values of the states u[B][N] in the CSR order of
+        jac_pattern. Rate constants of state b as in flux_batched."""
+        u = np.ascontiguousarray(np.atleast_2d(_f64(u)))
+        B = u.shape[0]
+        assert u.shape == (B, self.n)
+        k, n_rows, k_row, T, _ = self._flux_inputs(B, k, k_row, T, None)
+        vals = np.empty((B, self._jac_nnz()))
+        self._chk(lib().kin_jac_batched(self._h, B, _pd(u), _pd(k), n_rows, None if k_row is None else _p64(k_row), _pd(T), _pd(vals)))
+        return vals
+
+    def jac_batched_dev(self, B, d_u, d_vals, d_k=0, d_k_row=0, d_T=0, stream=0):
+        """kin_jac_batched_dev: device pointers (ints; 0 = not given), u[B][N], k rows / k_row[B] (int64) / T[B], vals[B][nnz].
+        One stream per handle at a time; allocates only when the workspace has to grow."""
+        p = lambda x: c_void_p(x) if x else None
+        self._chk(lib().kin_jac_batched_dev(self._h, int(B), p(d_u), p(d_k), p(d_k_row), p(d_T), p(d_vals), p(stream)))
+
+    def timescale_batched(self, u, k=None, k_row=None, T=None, summary=None, want_summary=True, want_diag=False, want_err=False,
+                          want_norm=True):
+        """kin_timescale_batched on host arrays, over the states u[B][N]: a dict of the outputs asked for - summary[3][N] (rows
+        decay_max = max_b -J_ii, decay_min = min_b -J_ii, qss_err = max_b |f_i| / |J_ii|), diag[B][N] = J_ii, err[B][N] =
+        |f_i| / |J_ii|, norm[B] = the infinity norm of J(u_b). Rate constants of state b as in flux_batched. summary given: its
+        values take part in the extrema (the result is returned, the argument is left alone)."""
+        u = np.ascontiguousarray(np.atleast_2d(_f64(u)))
+        B = u.shape[0]
+        assert u.shape == (B, self.n)
+        k, n_rows, k_row, T, _ = self._flux_inputs(B, k, k_row, T, None)
+        out, acc = self._ts_summary(summary) if want_summary else (None, 0)
+        diag = np.empty((B, self.n)) if want_diag else None
+        err = np.empty((B, self.n)) if want_err else None
+        norm = np.empty(B) if want_norm else None
+        self._chk(lib().kin_timescale_batched(self._h, B, _pd(u), _pd(k), n_rows, None if k_row is None else _p64(k_row), _pd(T), acc,
+                                              _pd(out), _pd(diag), _pd(err), _pd(norm)))
+        return {q: v for q, v in (("summary", out), ("diag", diag), ("err", err), ("norm", norm)) if v is not None}
+
+    def timescale_batched_dev(self, B, d_u, d_summary=0, d_diag=0, d_err=0, d_norm=0, d_k=0, d_k_row=0, d_T=0, accumulate=False, stream=0):
+        """kin_timescale_batched_dev: device pointers (ints; 0 = not given), u[B][N], k rows / k_row[B] (int64) / T[B],
+        summary[3][N], diag[B][N], err[B][N], norm[B]. One stream per handle at a time."""
+        p = lambda x: c_void_p(x) if x else None
+        self._chk(lib().kin_timescale_batched_dev(self._h, int(B), p(d_u), p(d_k), p(d_k_row), p(d_T), 1 if accumulate else 0,
+                                                  p(d_summary), p(d_diag), p(d_err), p(d_norm), p(stream)))
+
+    def solution_timescale(self, k=None, k_row=None, T_rows=None, row_begin=0, summary=None, want_norm=True):
+        """kin_solution_timescale: timescale_batched over the saved states of the last solve from row_begin on, read where they
+        live on the device (rate-constant sources as solution_flux). Returns (summary[3][N], norm[n_saved] or None); the norm
+        of a row below row_begin is 0.0."""
+        n_saved = c_int64(0)
+        self._chk(lib().kin_solution_size(self._h, ctypes.byref(n_saved), None))
+        k, n_rows, k_row, T_rows, _ = self._flux_inputs(n_saved.value, k, k_row, T_rows, None)
+        out, acc = self._ts_summary(summary)
+        norm = np.empty(n_saved.value) if want_norm else None
+        self._chk(lib().kin_solution_timescale(self._h, _pd(k), n_rows, None if k_row is None else _p64(k_row), _pd(T_rows),
+                                               int(row_begin), acc, _pd(out), _pd(norm)))
+        return out, norm
+
+    def ensemble_timescale(self, k=None, k_row=None, T_rows=None, row_begin=0, summary=None, want_norm=True):
+        """kin_ensemble_timescale: one summary over the saved rows row_begin .. n_saved[m] - 1 of every member of the stored
+        ensemble (k_row / T_rows: [K][n_rows], entries of rows that take no part are ignored). Returns (summary[3][N],
+        norm[K][n_rows] or None); the norm of a row that takes no part is 0.0."""
+        K, rows = self.ensemble_size()[:2]
+        k, n_rows, k_row, T_rows, _ = self._flux_inputs(K * rows, k, k_row, T_rows, None)
+        out, acc = self._ts_summary(summary)
+        norm = np.empty((K, rows)) if want_norm else None
+        self._chk(lib().kin_ensemble_timescale(self._h, _pd(k), n_rows, None if k_row is None else _p64(k_row), _pd(T_rows),
+                                               int(row_begin), acc, _pd(out), _pd(norm)))
+        return out, norm
 
     # --- library order (tiled sweep) --------------------------------------------------------
     def lib_layout(self):

@@ -84,6 +84,14 @@ struct kin_network {
   kin::DevBuf<int32_t> drgep_rounds;
   kin::DevBuf<int64_t> drgep_targets;
 
+  // timescale pass (timescale.hpp, timescale_api.cpp): the row pass's tables, uploaded at the first call that needs them; the
+  // block's rates[nb][R], dr[nb][2R], jv[nb][nnz], g[nb][N], the extrema per slice part[Y][3][N] and the staging buffers of
+  // the host entries' outputs, grown on demand
+  bool ts_ready = false;
+  int32_t ts_G = 0, ts_S = 0, ts_Bl = 0;
+  kin::DevBuf<int32_t> ts_rows;
+  kin::DevBuf<double> ts_rates, ts_dr, ts_jv, ts_g, ts_part, ts_o_vals, ts_o_summary, ts_o_diag, ts_o_err, ts_o_norm;
+
   // tiled sweep in library order (tiled.hpp, tiled_api.cpp): built at the first call that needs it
   kin::TiledHost tiled;
   bool tiled_tried = false;

@@ -1151,6 +1151,86 @@ def reduce_network(out, calculator, targets, eps, pairing=True, coef=None, metho
                         np.asarray(cf), tg, float(eps), imp)
 
 
+# ---- timescale analysis (EXTENSION: species lifetimes, quasi-steady-state error and stiffness along a solve) ---------------
+@dataclass
+class Timescales:
+    """Result of species_timescales: the saved times that count, per species decay_max[N] = max over them of -J_ii,
+    decay_min[N] = min of -J_ii and qss_err[N] = max of |f_i| / |J_ii| (include/kinetica_hip.h has the definitions), and
+    norm = the infinity norm of the Jacobian at every counting state."""
+    t: np.ndarray
+    decay_max: np.ndarray
+    decay_min: np.ndarray
+    qss_err: np.ndarray
+    norm: np.ndarray
+
+    def lifetime_min(self):
+        """The shortest lifetime tau_i = -1 / J_ii of every species along the run: 1 / decay_max where that is positive, else inf."""
+        return _inverse_where_positive(self.decay_max)
+
+    def lifetime_max(self):
+        """The longest lifetime of every species along the run: 1 / decay_min where that is positive, else inf."""
+        return _inverse_where_positive(self.decay_min)
+
+    def stiffness(self):
+        """The largest ||J||_inf along the run, a bound of the spectral radius (0.0 without a counting state)."""
+        return float(np.max(self.norm)) if len(self.norm) else 0.0
+
+    @property
+    def summary(self):
+        return np.stack([self.decay_max, self.decay_min, self.qss_err])
+
+
+def _inverse_where_positive(x):
+    x = np.asarray(x, dtype=float)
+    out = np.full(x.shape, np.inf)
+    pos = x > 0
+    out[pos] = 1.0 / x[pos]
+    return out
+
+
+def species_timescales(out, calculator, t_min=None, summary=None):
+    """Timescales of `out.rd` over the saved states of a solve with t >= t_min (None: all of them; a t_min past the initial
+    layer leaves out the induction period, where nothing is quasi-steady yet). `summary`: an earlier Timescales, whose three
+    per-species arrays take part in the extrema (several solves folded into one). `calculator` and the rate constants of every
+    saved state are chosen as reaction_fluxes chooses them. One device pass (kin_timescale_batched) over the counting states."""
+    sd, rd = out.sd, out.rd
+    setup_network(sd, rd, calculator)
+    t = np.asarray(out.sol.t, dtype=float)
+    u = np.ascontiguousarray(np.asarray(out.sol.u, dtype=float).reshape(len(t), sd.n))
+    src = saved_state_rate_source(out, calculator, t)
+    keep = np.ones(len(t), bool) if t_min is None else t >= float(t_min)
+    for key in ("k_row", "T"):      # (one entry per saved time; k holds the rows k_row indexes)
+        if key in src:
+            src[key] = np.asarray(src[key])[keep]
+    h = capi.HipNetwork(*rd.flat(sd.n), index_base=1)
+    try:
+        if "T" in src:
+            h.set_arrhenius(calculator.Ea, calculator.A, calculator.k_max, calculator.t_mult)
+        res = h.timescale_batched(np.ascontiguousarray(u[keep]), summary=None if summary is None else summary.summary, **src)
+    finally:
+        h.close()
+    s = res["summary"]
+    return Timescales(t[keep], s[0], s[1], s[2], res["norm"])
+
+
+def qss_candidates(ts, tol, scale=None, max_lifetime=None):
+    """Species (0-based, sorted) that stayed in quasi-steady state over the states `ts` covers: qss_err / scale <= tol, consumed
+    at every state (decay_min > 0) and, with max_lifetime, never slower than it (1 / decay_min <= max_lifetime). `scale`: a
+    positive array of one concentration per species, e.g. the per-species maximum of the solve (None: 1, the absolute error in
+    concentration units); a non-positive entry raises ValueError. Pure NumPy."""
+    err = np.asarray(ts.qss_err, dtype=float)
+    dmin = np.asarray(ts.decay_min, dtype=float)
+    sc = np.ones(len(err)) if scale is None else np.asarray(scale, dtype=float).ravel()
+    if len(sc) != len(err):
+        raise ValueError("scale must have one entry per species")
+    if not np.all(sc > 0):
+        raise ValueError("scale must be positive")
+    keep = (err / sc <= float(tol)) & (dmin > 0)
+    if max_lifetime is not None:
+        keep &= _inverse_where_positive(dmin) <= float(max_lifetime)
+    return np.flatnonzero(keep).astype(np.int64)
+
+
 # ---- the consumer of a level's solve (src/exploration/explore_utils.jl:338-406) ---------------------------
 def identify_next_seeds(sol, sd: SpeciesData, seed_conc: Optional[float] = None, *, elim_small_na: int = 0,
                         ignore: Optional[Sequence[str]] = (), saveto: Optional[str] = None) -> List[str]:

@@ -650,6 +650,61 @@ int kin_ensemble_drgep(kin_network* h, int pairing, const double* k, int64_t n_k
                        const double* T_rows /* [K*n_rows] */, const int64_t* targets, int64_t n_targets, int index_base, int accumulate,
                        double* importance /* [N] */);
 
+/* ---- path flux analysis (PFA, Sun, Chen, Gou & Ju 2010): second-generation species coupling --------------------------- */
+/* The rates q, the records, pairing, the signed nu_A and the set S are exactly those of the "directed relation graph" block
+ * above. Per state, with w = q_kf - q_kr (pairing) or q_r:
+ *
+ *   P_A  = sum of max( nu_A w, 0)            C_A  = sum of max(-nu_A w, 0)      over the records with nu_A != 0
+ *   P_AB = the part of P_A whose records hold B (B in S, B != A)                C_AB likewise
+ *   den_A = max(P_A, C_A)
+ *   rp_AB = P_AB / den_A        rc_AB = C_AB / den_A        (0.0 where den_A == 0, never NaN)
+ *   rp2_AB = sum over M not in {A, B} with (A, M) and (M, B) in E of rp_AM * rp_MB         rc2_AB likewise with rc
+ *   r_AB  = rp_AB + rc_AB + rp2_AB + rc2_AB           coef_AB = max over the states of r_AB
+ *
+ * E is the DRG pattern of that pairing mode (kin_drg_pattern). The PFA pattern E2 holds (A, B), A != B, when (A, B) is in E
+ * or some M not in {A, B} has (A, M) in E and (M, B) in E; it is stored as CSR with sorted columns and no diagonal, and coef
+ * has one entry per pair of E2 in that order. r is not clipped: a reversible pair without pairing gives 1.5. Production and
+ * consumption never mix: rp_AM * rc_MB contributes nothing. States past n_saved[m] of a stored ensemble do not count.
+ *
+ * No floating-point atomics: P_AB and C_AB are formed in the fixed order of the DRG pass, the second-generation sums with M
+ * in pattern order, one writer per value, and the maximum is exact. The result is bit-identical from call to call and does
+ * not depend on how the states are cut into blocks or slices, on accumulate against one call, or on which rows a workgroup
+ * and which a single wavefront takes (the rows whose cost sum over M in out(A) of deg(M) is above 65536, and every row of a
+ * network above 2366 species, go to a workgroup; KIN_PFA_WG_COST=n sets the cost instead - a knob for timing, never for results). States are taken in blocks as in the DRG
+ * pass: none of rates[nb][R], rp[nb][E] + rc[nb][E] and, when asked for, r[nb][E2] above 256 MB; KIN_DRG_BLOCK_STATES=n forces
+ * blocks of at most n states; KIN_PFA_STAGES=1 or 2 ends every block after the rates or after the split stage and leaves
+ * coef alone - for timing the stages. accumulate != 0: the current contents of coef take part in the maximum. Rate
+ * constants and statuses are exactly kin_flux_batched[_dev]'s and kin_drg_batched's; B == 0 writes zeros, or leaves coef
+ * alone when accumulating. Size limit: the second-generation stage keeps one row of n_species doubles in LDS, which fits the
+ * 160 KB of a compute unit up to 20286 species; above that every entry but the two pattern ones returns KIN_ERR_UNSUPPORTED
+ * and kin_last_error names the limit. Added under KIN_ABI_VERSION 6: look the symbols up before calling them. */
+/* E2 and its sizes from the topology alone, no device or handle. rowptr[n_species + 1] / colidx[pairs], both may be NULL
+ * (sizes only). info[4]: the edges of E, the pairs of E2, the products per state (sum over the edges (A, M) of M's out-degree:
+ * each is two multiply-adds) and the largest row of E. */
+int kin_pfa_pattern_host(int64_t n_species, int64_t n_reactions, const int64_t* reac_ptr, const int64_t* reac_idx,
+                         const int64_t* reac_sto, const int64_t* prod_ptr, const int64_t* prod_idx, const int64_t* prod_sto,
+                         int index_base, int pairing, int64_t* info /* [4] */, int64_t* rowptr, int64_t* colidx);
+/* The handle's E2 (built at the first call per pairing mode; no device call). Any of nnz / rowptr / colidx may be NULL. */
+int kin_pfa_pattern(kin_network* h, int pairing, int index_base, int64_t* nnz, int64_t* rowptr, int64_t* colidx);
+/* Device pointers; only enqueues on `stream` (NULL: the handle's) once the workspace has its size. */
+int kin_pfa_batched_dev(kin_network* h, int pairing, int64_t B, const double* d_u, const double* d_k, const int64_t* d_k_row,
+                        const double* d_T, int accumulate, double* d_coef /* [pairs] */, void* stream);
+/* Host arrays. The optional outputs show every stage per state: rp_out[b][e] and rc_out[b][e] over the edges of E, r_out[b][z]
+ * over the pairs of E2. */
+int kin_pfa_batched(kin_network* h, int pairing, int64_t B, const double* u, const double* k, int64_t n_k_rows, const int64_t* k_row,
+                    const double* T, int accumulate, double* coef /* [pairs] */, double* rp_out /* [B][edges] or NULL */,
+                    double* rc_out /* [B][edges] or NULL */, double* r_out /* [B][pairs] or NULL */);
+/* The second-generation stage alone on the caller's coefficients rp[B][edges], rc[B][edges] (CSR order of
+ * kin_drg_pattern(pairing)). KIN_ERR_INVALID_ARG for a coefficient that is negative or not finite. */
+int kin_pfa_paths(kin_network* h, int pairing, int64_t B, const double* rp, const double* rc, int accumulate,
+                  double* coef /* [pairs] */, double* r_out /* [B][pairs] or NULL */);
+/* Over the saved states of the last kin_solve / over the stored ensemble, read where they live: arguments and statuses of
+ * kin_solution_drg / kin_ensemble_drg. Rows past n_saved[m] take no part. */
+int kin_solution_pfa(kin_network* h, int pairing, const double* k, int64_t n_k_rows, const int64_t* k_row, const double* T_rows,
+                     int accumulate, double* coef /* [pairs] */);
+int kin_ensemble_pfa(kin_network* h, int pairing, const double* k, int64_t n_k_rows, const int64_t* k_row /* [K*n_rows] */,
+                     const double* T_rows /* [K*n_rows] */, int accumulate, double* coef /* [pairs] */);
+
 /* ---- timescale analysis: batched Jacobians, species lifetimes, quasi-steady-state error --------------------------------- */
 /* For a state u_b with rate constants k_b, chosen exactly as kin_flux_batched[_dev] chooses them (rows of k, the Arrhenius
  * law at T[b], or the handle's current rates):
@@ -719,7 +774,8 @@ const char* kin_version(void);
  * structs unchanged; kin_solve_ensemble_discrete, kin_resident_probe, kin_newton_probe, kin_step_probe, kin_eval_probe, kin_cache_probe, the flux pass (kin_flux_*, kin_solution_flux) and
  * kin_ensemble_size / _max / _dot / _flux and the directed relation graph (kin_drg_*, kin_solution_drg, kin_ensemble_drg) came
  * later under 6, found by symbol lookup; so did DRGEP: kin_drgep_*, kin_solution_drgep, kin_ensemble_drgep, and the timescale analysis:
- * kin_jac_batched*, kin_timescale_*, kin_solution_timescale, kin_ensemble_timescale). */
+ * kin_jac_batched*, kin_timescale_*, kin_solution_timescale, kin_ensemble_timescale, and path flux analysis: kin_pfa_*,
+ * kin_solution_pfa, kin_ensemble_pfa). */
 #define KIN_ABI_VERSION 6
 int kin_abi_version(void);
 int64_t kin_struct_size(int which); /* 0: sizeof(kin_params), 1: sizeof(kin_stats), else -1 */

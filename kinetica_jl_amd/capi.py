@@ -35,6 +35,8 @@ SYMBOLS = [
     "kin_flux_segmented", "kin_flux_segmented_dev", "kin_ensemble_size", "kin_ensemble_max", "kin_ensemble_dot", "kin_ensemble_flux",
     "kin_drg_pattern_host", "kin_drg_pattern", "kin_drg_batched", "kin_drg_batched_dev", "kin_solution_drg", "kin_ensemble_drg",
     "kin_drgep_batched", "kin_drgep_batched_dev", "kin_drgep_paths", "kin_solution_drgep", "kin_ensemble_drgep",
+    "kin_pfa_pattern_host", "kin_pfa_pattern", "kin_pfa_batched", "kin_pfa_batched_dev", "kin_pfa_paths", "kin_solution_pfa",
+    "kin_ensemble_pfa",
     "kin_jac_batched", "kin_jac_batched_dev", "kin_timescale_batched", "kin_timescale_batched_dev", "kin_solution_timescale",
     "kin_ensemble_timescale", "kin_timescale_plan_host",
 ]
@@ -177,6 +179,14 @@ def lib():
             L.kin_drgep_paths.argtypes = [c_void_p, c_int, c_int64, PD, P64, c_int64, c_int, c_int, PD, PD, P32]
             L.kin_solution_drgep.argtypes = [c_void_p, c_int, PD, c_int64, P64, PD, P64, c_int64, c_int, c_int, PD]
             L.kin_ensemble_drgep.argtypes = [c_void_p, c_int, PD, c_int64, P64, PD, P64, c_int64, c_int, c_int, PD]
+        if hasattr(L, "kin_pfa_batched"):   # (also under ABI 6: path flux analysis)
+            L.kin_pfa_pattern_host.argtypes = [c_int64, c_int64] + [P64] * 6 + [c_int, c_int, P64, P64, P64]
+            L.kin_pfa_pattern.argtypes = [c_void_p, c_int, c_int, P64, P64, P64]
+            L.kin_pfa_batched_dev.argtypes = [c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]
+            L.kin_pfa_batched.argtypes = [c_void_p, c_int, c_int64, PD, PD, c_int64, P64, PD, c_int, PD, PD, PD, PD]
+            L.kin_pfa_paths.argtypes = [c_void_p, c_int, c_int64, PD, PD, c_int, PD, PD]
+            L.kin_solution_pfa.argtypes = [c_void_p, c_int, PD, c_int64, P64, PD, c_int, PD]
+            L.kin_ensemble_pfa.argtypes = [c_void_p, c_int, PD, c_int64, P64, PD, c_int, PD]
         if hasattr(L, "kin_timescale_batched"):   # (also under ABI 6: the timescale analysis)
             L.kin_jac_batched_dev.argtypes = [c_void_p, c_int64] + [c_void_p] * 6
             L.kin_jac_batched.argtypes = [c_void_p, c_int64, PD, PD, c_int64, P64, PD, PD]
@@ -289,6 +299,30 @@ def drg_pattern_host(net, pairing=True):
     st = L.kin_drg_pattern_host(*head, _p64(info), _p64(rowptr), _p64(colidx))
     assert st == KIN_OK
     return rowptr, colidx[:int(info[0])], {k: int(v) for k, v in zip(DRG_INFO, info)}
+
+
+PFA_INFO = ("edges", "pairs", "products", "max_row")
+# the largest network the second-generation stage takes (pfa.hpp: PFA_LDS_SPECIES) and the cost sum over M in out(A) of deg(M)
+# above which a workgroup, not a wavefront, takes row A (PFA_WG_COST)
+PFA_MAX_SPECIES, PFA_WG_COST = 20286, 65536
+
+
+def pfa_pattern_host(net, pairing=True):
+    """kin_pfa_pattern_host of a FlatNetwork, computed on the host (no device): (rowptr[N + 1], colidx[pairs], info) - the CSR of
+    the path-flux-analysis pattern E2 (the DRG edges and every two-hop pair; 0-based, sorted columns, no diagonal) and a dict
+    of the PFA_INFO sizes: the edges of E, the pairs of E2, the products per state and the largest row of E."""
+    L = lib()
+    arrs = [np.ascontiguousarray(a, dtype=np.int64) for a in (net.reac_ptr, net.reac_idx, net.reac_sto, net.prod_ptr,
+                                                              net.prod_idx, net.prod_sto)]
+    head = [int(net.n_species), int(net.n_reactions)] + [_p64(a) for a in arrs] + [0, 1 if pairing else 0]
+    info = np.zeros(len(PFA_INFO), np.int64)
+    st = L.kin_pfa_pattern_host(*head, _p64(info), None, None)
+    if st != KIN_OK:
+        raise KineticaHipError(st, L.kin_last_error(None).decode())
+    rowptr, colidx = np.empty(net.n_species + 1, np.int64), np.empty(max(int(info[1]), 1), np.int64)
+    st = L.kin_pfa_pattern_host(*head, _p64(info), _p64(rowptr), _p64(colidx))
+    assert st == KIN_OK
+    return rowptr, colidx[:int(info[1])], {k: int(v) for k, v in zip(PFA_INFO, info)}
 
 
 TIMESCALE_INFO = ("nnz", "rows_short", "rows_medium", "rows_long")
@@ -659,6 +693,93 @@ class HipNetwork:
         self._chk(lib().kin_ensemble_drgep(self._h, int(bool(pairing)), _pd(k), n_rows, None if k_row is None else _p64(k_row),
                                            _pd(T_rows), _p64(tg), nt, 0, acc, _pd(out)))
         return out[:self.n]
+
+    # --- path flux analysis ------------------------------------------------------------------------
+    def pfa_pattern(self, pairing=True):
+        """kin_pfa_pattern: (rowptr[N + 1], colidx[pairs]) of the handle's path-flux-analysis pattern E2, 0-based (no device call)."""
+        nnz = c_int64(0)
+        self._chk(lib().kin_pfa_pattern(self._h, int(bool(pairing)), 0, ctypes.byref(nnz), None, None))
+        rowptr, colidx = np.empty(self.n + 1, np.int64), np.empty(max(nnz.value, 1), np.int64)
+        self._chk(lib().kin_pfa_pattern(self._h, int(bool(pairing)), 0, None, _p64(rowptr), _p64(colidx)))
+        return rowptr, colidx[:nnz.value]
+
+    def _pfa_coef(self, pairing, coef):
+        """The output buffer of a PFA entry: a fresh one, or (accumulate) a contiguous copy of `coef` that takes part in the maximum."""
+        nnz = c_int64(0)
+        self._chk(lib().kin_pfa_pattern(self._h, int(bool(pairing)), 0, ctypes.byref(nnz), None, None))
+        out = np.zeros(max(nnz.value, 1))
+        if coef is None:
+            return out, nnz.value, 0
+        c = _f64(coef).ravel()
+        if len(c) != nnz.value:
+            raise KineticaHipError(KIN_ERR_INVALID_ARG, f"coef has {len(c)} entries, the PFA pattern {nnz.value} pairs")
+        out[:nnz.value] = c
+        return out, nnz.value, 1
+
+    def _drg_nnz(self, pairing):
+        nnz = c_int64(0)
+        self._chk(lib().kin_drg_pattern(self._h, int(bool(pairing)), 0, ctypes.byref(nnz), None, None))
+        return nnz.value
+
+    def pfa_batched(self, u, k=None, k_row=None, T=None, pairing=True, coef=None, stages=False):
+        """kin_pfa_batched on host arrays: coef[pairs] (CSR order of pfa_pattern) = max over the states u[B][N] of
+        r_AB = rp_AB + rc_AB + sum_M (rp_AM rp_MB + rc_AM rc_MB), the path-flux-analysis coefficients (include/kinetica_hip.h has
+        the definition). Rate constants of state b as in flux_batched. coef given: its values take part in the maximum (the
+        result is returned, the argument is left alone). stages=True: (coef, rp[B][edges], rc[B][edges], r[B][pairs])."""
+        u = np.ascontiguousarray(np.atleast_2d(_f64(u)))
+        B = u.shape[0]
+        assert u.shape == (B, self.n)
+        k, n_rows, k_row, T, _ = self._flux_inputs(B, k, k_row, T, None)
+        out, nnz, acc = self._pfa_coef(pairing, coef)
+        rp = rc = r = None
+        if stages:
+            E = self._drg_nnz(pairing)
+            rp, rc, r = np.zeros((B, E)), np.zeros((B, E)), np.zeros((B, nnz))
+        opt = lambda a: _pd(a) if stages and a.size else None
+        self._chk(lib().kin_pfa_batched(self._h, int(bool(pairing)), B, _pd(u), _pd(k), n_rows, None if k_row is None else _p64(k_row),
+                                        _pd(T), acc, _pd(out), opt(rp), opt(rc), opt(r)))
+        return (out[:nnz], rp, rc, r) if stages else out[:nnz]
+
+    def pfa_batched_dev(self, B, d_u, d_coef, d_k=0, d_k_row=0, d_T=0, pairing=True, accumulate=False, stream=0):
+        """kin_pfa_batched_dev: device pointers (ints; 0 = not given), u[B][N], k rows / k_row[B] (int64) / T[B], coef[pairs].
+        One stream per handle at a time; allocates only when the workspace has to grow."""
+        p = lambda x: c_void_p(x) if x else None
+        self._chk(lib().kin_pfa_batched_dev(self._h, int(bool(pairing)), int(B), p(d_u), p(d_k), p(d_k_row), p(d_T),
+                                            1 if accumulate else 0, p(d_coef), p(stream)))
+
+    def pfa_paths(self, rp, rc, pairing=True, coef=None, stages=False):
+        """kin_pfa_paths: the second-generation stage alone on the caller's coefficients rp[B][edges], rc[B][edges] >= 0 (CSR
+        order of drg_pattern). stages=True: (coef, r[B][pairs])."""
+        E = self._drg_nnz(pairing)
+        rp, rc = (np.ascontiguousarray(_f64(x)).reshape(-1, E) if E else np.zeros((len(x), 0)) for x in (rp, rc))
+        B = rp.shape[0]
+        assert rc.shape == rp.shape
+        out, nnz, acc = self._pfa_coef(pairing, coef)
+        r = np.zeros((B, nnz))
+        self._chk(lib().kin_pfa_paths(self._h, int(bool(pairing)), B, _pd(rp) if rp.size else None, _pd(rc) if rc.size else None, acc,
+                                      _pd(out), _pd(r) if stages and r.size else None))
+        return (out[:nnz], r) if stages else out[:nnz]
+
+    def solution_pfa(self, k=None, k_row=None, T_rows=None, pairing=True, coef=None):
+        """kin_solution_pfa: pfa_batched over the saved states of the last solve, read where they live on the device
+        (rate-constant sources as solution_flux)."""
+        n_saved = c_int64(0)
+        self._chk(lib().kin_solution_size(self._h, ctypes.byref(n_saved), None))
+        k, n_rows, k_row, T_rows, _ = self._flux_inputs(n_saved.value, k, k_row, T_rows, None)
+        out, nnz, acc = self._pfa_coef(pairing, coef)
+        self._chk(lib().kin_solution_pfa(self._h, int(bool(pairing)), _pd(k), n_rows, None if k_row is None else _p64(k_row),
+                                         _pd(T_rows), acc, _pd(out)))
+        return out[:nnz]
+
+    def ensemble_pfa(self, k=None, k_row=None, T_rows=None, pairing=True, coef=None):
+        """kin_ensemble_pfa: one set of coefficients over every saved row of every member of the stored ensemble (k_row / T_rows:
+        [K][n_rows], entries past a member's saved rows are ignored)."""
+        K, rows = self.ensemble_size()[:2]
+        k, n_rows, k_row, T_rows, _ = self._flux_inputs(K * rows, k, k_row, T_rows, None)
+        out, nnz, acc = self._pfa_coef(pairing, coef)
+        self._chk(lib().kin_ensemble_pfa(self._h, int(bool(pairing)), _pd(k), n_rows, None if k_row is None else _p64(k_row),
+                                         _pd(T_rows), acc, _pd(out)))
+        return out[:nnz]
 
     # --- timescale analysis ---------------------------------------------------------------------
     def _jac_nnz(self):

@@ -337,6 +337,26 @@ int kin_drg_pattern_host(int64_t n_species, int64_t n_reactions, const int64_t* 
   return KIN_OK;
 }
 
+int kin_pfa_pattern_host(int64_t n_species, int64_t n_reactions, const int64_t* reac_ptr, const int64_t* reac_idx,
+                         const int64_t* reac_sto, const int64_t* prod_ptr, const int64_t* prod_idx, const int64_t* prod_sto,
+                         int index_base, int pairing, int64_t* info, int64_t* rowptr, int64_t* colidx) {
+  try {
+    const NetworkHost H = compile_network(n_species, n_reactions, reac_ptr, reac_idx, reac_sto, prod_ptr, prod_idx, prod_sto, index_base);
+    const DrgTables g = build_drg_tables(H, pairing, false);
+    const PfaTables t = build_pfa_tables(g.N, g.rowptr, g.colidx);
+    if (info) { info[0] = t.E; info[1] = t.E2; info[2] = t.products; info[3] = t.max_row; }
+    if (rowptr) for (int64_t i = 0; i <= t.N; i++) rowptr[i] = t.rowptr2[i] + index_base;
+    if (colidx) for (int64_t e = 0; e < t.E2; e++) colidx[e] = t.colidx2[e] + index_base;
+  } catch (const KinError& e) {
+    g_create_err = e.what();
+    return e.code;
+  } catch (const std::exception& e) {
+    g_create_err = e.what();
+    return KIN_ERR_INVALID_ARG;
+  }
+  return KIN_OK;
+}
+
 int kin_jac_pattern(kin_network* h, int64_t* rowptr, int64_t* colidx, int index_base) {
   if (!h || !rowptr || !colidx) return KIN_ERR_INVALID_ARG;
   const NetworkHost& N = h->host;

@@ -13,6 +13,9 @@
 // DRG with error propagation (kin_drgep_*; definition: include/kinetica_hip.h) walks the same plans with the SIGNED
 // coefficients nu_A (stage 2: r[nb][E], no maximum over the states) and then searches, per state, the largest product of
 // r along any path from a target (drgep_kernels.hip) over the transpose of the pattern.
+//
+// Path flux analysis (kin_pfa_*; pfa.hpp) walks the edge plan with the signed coefficients a third way (SPLIT: the positive and
+// the negative part of every edge's sum apart, each over den_A) and multiplies the two sparse matrices per state.
 #pragma once
 #include "common.hpp"
 #include "kernels.hpp"
@@ -53,6 +56,7 @@ struct DrgArgs {
   double* den;                     // den[nb][N]: written by the denominator launch, read by the edge launch
   double* part;                    // part[Y][E]: the edge launch's maxima per slice of the states
   double* r;                       // r[nb][E]: the signed edge launch's per-state coefficients (rows of states that do not count: untouched)
+  double* rc;                      // rc[nb][E]: the split edge launch's consumption part (its production part goes to r)
 };
 // slices of the states a launch is cut into so that the device is filled (depends on the plan, nb and n_cu only)
 int drg_slices(const SegPlanView& p, int64_t nb, int n_cu);
@@ -63,6 +67,8 @@ void launch_drg_max(int64_t E, int Y, const double* part, double* coef, int use_
 // DRGEP stage 2 (ell_c / long_c: the SIGNED coefficients): den[bl][A] = max(P_A, C_A); r[bl][e] = min(1, |s_AB| / den_A)
 void launch_drgep_den(const DrgArgs& a, int Y, hipStream_t s);
 void launch_drgep_edges(const DrgArgs& a, int Y, hipStream_t s);
+// PFA split stage (pfa.hpp) on the signed plans, after launch_drgep_den: r[bl][e] = P_AB / den_A, rc[bl][e] = C_AB / den_A
+void launch_pfa_split(const DrgArgs& a, int Y, hipStream_t s);
 
 // DRGEP path stage (drgep_kernels.hip): one workgroup per state relaxes R_B = max(R_B, R_A r_AB) over the incoming edges
 // until nothing changes (at most N rounds). R is double-buffered in LDS (in_lds: N <= DRGEP_LDS_SPECIES), else in work.

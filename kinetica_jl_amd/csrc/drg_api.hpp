@@ -11,6 +11,8 @@ constexpr size_t DRG_RATES_BYTES = (size_t)256 << 20;   // bound of the stage-1 
 // the handle's tables of a pairing mode, built at the first call (throws KinError), and their device side
 DrgTables& drg_host(kin_network* h, int pairing);
 kin_network::DrgMode& drg_dev(kin_network* h, int pairing, hipStream_t s);
+// ... with the signed coefficients and the transposed pattern as well (DRGEP and PFA; drgep_api.cpp)
+kin_network::DrgMode& drgep_dev(kin_network* h, int pairing, hipStream_t s);
 // flux_check plus the pass's own limits; throws KinError
 void drg_check(kin_network* h, int64_t B, bool have_k, bool have_row, bool have_T, bool have_out);
 // Checks of the solution / ensemble forms and the upload of their rate-constant keys (f_k, f_krow, f_T; the ensemble's

@@ -10,6 +10,8 @@
 // SIGNED = true is DRGEP's stage 2 on the same plans and in the same order of summation, with c = nu_A carrying its sign:
 // the denominator launch forms P = sum max(c w, 0) and C = sum max(-c w, 0) and writes den = max(P, C), the edge launch
 // forms s = sum c w and writes r[bl][e] = min(1, |s| / den) for every state that counts - no maximum over the states.
+// SPLIT (with EDGE and SIGNED) is the first-generation stage of path flux analysis (pfa.hpp): the edge launch forms the two
+// parts P and C the way the denominator launch does and writes r[bl][e] = P / den and rc[bl][e] = C / den, not clipped.
 #include "drg.hpp"
 
 #include "segsum_dev.hpp"
@@ -66,9 +68,13 @@ __device__ __forceinline__ DrgSigned wave_sum(DrgSigned v) {
   return v;
 }
 // what a signed row stores for state bl: den = max(P, C), or r = min(1, |s| / den) (exactly 0.0 where den == 0)
-template <bool EDGE>
+template <bool EDGE, bool SPLIT>
 __device__ __forceinline__ void drg_store_signed(const DrgArgs& a, int bl, int32_t dst, int32_t aux, const DrgSigned& v) {
-  if (EDGE) {
+  if (SPLIT) {
+    const double d = a.den[(size_t)bl * a.N + aux];
+    a.r[(size_t)bl * a.E + dst] = d > 0.0 ? v.p / d : 0.0;
+    a.rc[(size_t)bl * a.E + dst] = d > 0.0 ? v.n / d : 0.0;
+  } else if (EDGE) {
     const double d = a.den[(size_t)bl * a.N + aux];
     a.r[(size_t)bl * a.E + dst] = d > 0.0 ? fmin(1.0, fabs(v.p) / d) : 0.0;
   } else {
@@ -78,8 +84,10 @@ __device__ __forceinline__ void drg_store_signed(const DrgArgs& a, int bl, int32
 
 // EDGE = false: den[bl][dst] = row sum. EDGE = true: m = max over the slice's states of (row sum / den[bl][aux]), part[y][dst] = m.
 // SIGNED: see the head of the file (part and the maximum take no part).
-template <bool EDGE, bool SIGNED = false>
+template <bool EDGE, bool SIGNED = false, bool SPLIT = false>
 __global__ __launch_bounds__(DRG_WG) void drg_gather_kernel(DrgArgs a) {
+  static_assert(!SPLIT || (EDGE && SIGNED), "the split stage is a signed edge launch");
+  constexpr bool PLAIN = EDGE && !SPLIT;      // the signed sum is the plain one s, not the two parts
   const SegPlanView& p = a.p;
   const int tid = threadIdx.x, lane = tid & 63, Y = gridDim.y, y = blockIdx.y;
   const int nb = a.nb, N = a.N, R = a.R;
@@ -112,21 +120,21 @@ __global__ __launch_bounds__(DRG_WG) void drg_gather_kernel(DrgArgs a) {
           ia[x] = ok ? p.long_a[e] : 0; ib[x] = ok ? p.long_b[e] : -1; c[x] = ok ? a.long_c[e] : 0.0f;
         }
         if (SIGNED) {
-          const DrgSigned t = drg_terms_signed<DRG_LONG_NX, EDGE>(rb, ia, ib, c);
+          const DrgSigned t = drg_terms_signed<DRG_LONG_NX, PLAIN>(rb, ia, ib, c);
           sg.p += t.p; sg.n += t.n;
         } else {
           acc += drg_terms<DRG_LONG_NX>(rb, ia, ib, c);
         }
       }
       if (SIGNED) {
-        sg = wave_sum<EDGE>(sg);
+        sg = wave_sum<PLAIN>(sg);
         if (lane == 0) { sh[tid >> 6] = sg.p; shn[tid >> 6] = sg.n; }
         __syncthreads();
         if (tid == 0) {
           DrgSigned tot{0.0, 0.0};
 #pragma unroll
           for (int w = 0; w < DRG_WAVES; w++) { tot.p += sh[w]; tot.n += shn[w]; }
-          drg_store_signed<EDGE>(a, bl, dst, aux, tot);
+          drg_store_signed<EDGE, SPLIT>(a, bl, dst, aux, tot);
         }
         __syncthreads();
         continue;
@@ -161,8 +169,8 @@ __global__ __launch_bounds__(DRG_WG) void drg_gather_kernel(DrgArgs a) {
     for (int bl = y; bl < nb; bl += Y) {
       if (!counts(bl)) continue;
       if (SIGNED) {
-        const DrgSigned sg = drg_terms_signed<8, EDGE>(a.rates + (size_t)bl * R, ia, ib, c);
-        if (dst >= 0) drg_store_signed<EDGE>(a, bl, dst, aux, sg);
+        const DrgSigned sg = drg_terms_signed<8, PLAIN>(a.rates + (size_t)bl * R, ia, ib, c);
+        if (dst >= 0) drg_store_signed<EDGE, SPLIT>(a, bl, dst, aux, sg);
         continue;
       }
       const double acc = drg_terms<8>(a.rates + (size_t)bl * R, ia, ib, c);
@@ -186,8 +194,8 @@ __global__ __launch_bounds__(DRG_WG) void drg_gather_kernel(DrgArgs a) {
     for (int bl = y; bl < nb; bl += Y) {
       if (!counts(bl)) continue;
       if (SIGNED) {
-        const DrgSigned sg = wave_sum<EDGE>(drg_terms_signed<4, EDGE>(a.rates + (size_t)bl * R, ia, ib, c));
-        if (lane == 0) drg_store_signed<EDGE>(a, bl, dst, aux, sg);
+        const DrgSigned sg = wave_sum<PLAIN>(drg_terms_signed<4, PLAIN>(a.rates + (size_t)bl * R, ia, ib, c));
+        if (lane == 0) drg_store_signed<EDGE, SPLIT>(a, bl, dst, aux, sg);
         continue;
       }
       const double acc = wave_sum(drg_terms<4>(a.rates + (size_t)bl * R, ia, ib, c));
@@ -238,6 +246,12 @@ void launch_drgep_den(const DrgArgs& a, int Y, hipStream_t s) {
 void launch_drgep_edges(const DrgArgs& a, int Y, hipStream_t s) {
   if (drg_blocks(a.p) == 0 || a.nb == 0) return;
   hipLaunchKernelGGL((drg_gather_kernel<true, true>), dim3(drg_blocks(a.p), (unsigned)Y), dim3(DRG_WG), 0, s, a);
+  KIN_HIP(hipGetLastError());
+}
+
+void launch_pfa_split(const DrgArgs& a, int Y, hipStream_t s) {
+  if (drg_blocks(a.p) == 0 || a.nb == 0) return;
+  hipLaunchKernelGGL((drg_gather_kernel<true, true, true>), dim3(drg_blocks(a.p), (unsigned)Y), dim3(DRG_WG), 0, s, a);
   KIN_HIP(hipGetLastError());
 }
 

@@ -17,19 +17,6 @@ void require(bool c, int code, const char* msg) {
   if (!c) throw KinError(code, msg);
 }
 
-kin_network::DrgMode& drgep_dev(kin_network* h, int pairing, hipStream_t s) {
-  auto& m = drg_dev(h, pairing, s);
-  if (!m.ep_ready) {
-    const DrgTables& t = *m.host;
-    m.den_ell_s.upload(t.den_ell_s, s); m.den_long_s.upload(t.den_long_s, s);
-    m.edge_ell_s.upload(t.edge_ell_s, s); m.edge_long_s.upload(t.edge_long_s, s);
-    m.in_ptr.upload(t.in_ptr, s); m.in_src.upload(t.in_src, s); m.in_edge.upload(t.in_edge, s); m.in_order.upload(t.in_order, s);
-    KIN_HIP(hipStreamSynchronize(s));
-    m.ep_ready = true;
-  }
-  return m;
-}
-
 // States per block: none of rates[nb][R], r[nb][E] and work[nb][2][N] above 256 MB; KIN_DRG_BLOCK_STATES as in the DRG pass.
 int64_t drgep_block(const kin_network* h, int64_t E, int64_t B) {
   const size_t row = (size_t)std::max<int64_t>(std::max<int64_t>(h->host.R, E), std::max<int64_t>(2 * h->host.N, 1)) * sizeof(double);
@@ -145,6 +132,23 @@ void drgep_host_call(kin_network* h, int accumulate, double* importance, hipStre
 }
 
 }  // namespace
+
+namespace kin {
+
+kin_network::DrgMode& drgep_dev(kin_network* h, int pairing, hipStream_t s) {
+  auto& m = drg_dev(h, pairing, s);
+  if (!m.ep_ready) {
+    const DrgTables& t = *m.host;
+    m.den_ell_s.upload(t.den_ell_s, s); m.den_long_s.upload(t.den_long_s, s);
+    m.edge_ell_s.upload(t.edge_ell_s, s); m.edge_long_s.upload(t.edge_long_s, s);
+    m.in_ptr.upload(t.in_ptr, s); m.in_src.upload(t.in_src, s); m.in_edge.upload(t.in_edge, s); m.in_order.upload(t.in_order, s);
+    KIN_HIP(hipStreamSynchronize(s));
+    m.ep_ready = true;
+  }
+  return m;
+}
+
+}  // namespace kin
 
 #define KIN_TRY(h) try { KIN_HIP(hipSetDevice((h)->device));
 #define KIN_CATCH(h)                                                        \

@@ -7,6 +7,7 @@
 #include "drg.hpp"
 #include "kernels.hpp"
 #include "network.hpp"
+#include "pfa.hpp"
 #include "tiled.hpp"
 
 namespace kin {
@@ -83,6 +84,15 @@ struct kin_network {
   kin::DevBuf<double> drgep_r, drgep_R, drgep_work, drgep_imp;
   kin::DevBuf<int32_t> drgep_rounds;
   kin::DevBuf<int64_t> drgep_targets;
+  // path flux analysis (pfa.hpp, pfa_api.cpp): the second-generation pattern per pairing mode and, on the device, both
+  // patterns and the order of the rows; the block's rp[nb][E], rc[nb][E], the per-state r[nb][E2] when asked for, the maxima
+  // per slice and the staging buffer of the host entries' coefficients
+  struct PfaMode {
+    std::unique_ptr<kin::PfaTables> host;
+    bool dev_ready = false;
+    kin::DevBuf<int32_t> rowptr, colidx, rowptr2, colidx2, order;
+  } pfa[2];
+  kin::DevBuf<double> pfa_rp, pfa_rc, pfa_r, pfa_part, pfa_coef;
 
   // timescale pass (timescale.hpp, timescale_api.cpp): the row pass's tables, uploaded at the first call that needs them; the
   // block's rates[nb][R], dr[nb][2R], jv[nb][nnz], g[nb][N], the extrema per slice part[Y][3][N] and the staging buffers of

@@ -1045,6 +1045,29 @@ def drg_select(rowptr, colidx, coef, targets, eps):
     return np.flatnonzero(keep).astype(np.int64)
 
 
+def pfa_coefficients(out, calculator, pairing=True):
+    """(rowptr[N + 1], colidx[E2], coef[E2]): path flux analysis (Sun, Chen, Gou & Ju) of `out.rd` over the saved states of a
+    solve - pair (A, B) in CSR form (0-based, sorted columns, no diagonal) on the pattern E2 of the DRG edges and every
+    two-hop pair A -> M -> B, with coef_AB = max over the saved states of rp_AB + rc_AB + sum_M (rp_AM rp_MB + rc_AM rc_MB):
+    the production and the consumption share of A's turnover that run through B, directly and over one intermediate
+    (include/kinetica_hip.h has the definition; pairing as in drg_coefficients). `calculator` and the rate constants of every
+    saved state are chosen as reaction_fluxes chooses them. One device pass (kin_pfa_batched) over sol.u."""
+    sd, rd = out.sd, out.rd
+    setup_network(sd, rd, calculator)
+    t = np.asarray(out.sol.t, dtype=float)
+    u = np.ascontiguousarray(np.asarray(out.sol.u, dtype=float).reshape(len(t), sd.n))
+    src = saved_state_rate_source(out, calculator, t)
+    h = capi.HipNetwork(*rd.flat(sd.n), index_base=1)
+    try:
+        if "T" in src:
+            h.set_arrhenius(calculator.Ea, calculator.A, calculator.k_max, calculator.t_mult)
+        rowptr, colidx = h.pfa_pattern(pairing)
+        coef = h.pfa_batched(u, pairing=pairing, **src)
+    finally:
+        h.close()
+    return rowptr, colidx, coef
+
+
 def drgep_importance(out, calculator, targets, pairing=True, importance=None):
     """importance[N] of DRG with error propagation (Pepiot-Desjardins & Pitsch) over the saved states of a solve: R_B = the
     largest product, over any path from a target (names or 0-based ids) to B, of the signed net direct-interaction
@@ -1124,9 +1147,12 @@ def reduce_network(out, calculator, targets, eps, pairing=True, coef=None, metho
 
     method="drgep" keeps instead the species whose DRGEP importance (drgep_importance, with the same targets) is >= eps;
     `importance`: the vector of an earlier drgep_importance call made with these targets (or several solves folded into one),
-    else computed here. The reaction rule and the splicing are the same; the result carries `importance` and no graph."""
-    if method not in ("drg", "drgep"):
-        raise ValueError('method must be "drg" or "drgep"')
+    else computed here. The reaction rule and the splicing are the same; the result carries `importance` and no graph.
+
+    method="pfa" is the DRG form on the path-flux-analysis graph: `coef` is (rowptr, colidx, coef) of pfa_coefficients, else
+    computed here, and the selection is drg_select's on it."""
+    if method not in ("drg", "drgep", "pfa"):
+        raise ValueError('method must be "drg", "drgep" or "pfa"')
     sd, rd = out.sd, out.rd
     tg = [sd.toInt[x] - 1 if isinstance(x, str) else int(x) for x in targets]
     u_first = np.asarray(out.sol.u, dtype=float).reshape(len(out.sol.t), sd.n)[0]
@@ -1139,7 +1165,8 @@ def reduce_network(out, calculator, targets, eps, pairing=True, coef=None, metho
         rowptr = colidx = cf = np.zeros(0)
         kept_sp = drgep_select(imp, tg, eps)
     else:
-        rowptr, colidx, cf = drg_coefficients(out, calculator, pairing) if coef is None else coef
+        graph = pfa_coefficients if method == "pfa" else drg_coefficients
+        rowptr, colidx, cf = graph(out, calculator, pairing) if coef is None else coef
         kept_sp = drg_select(rowptr, colidx, cf, tg, eps)
     sd_new, new_id = sd.subset(kept_sp + 1)
     rd_new, kept_rx = rd.subset_species(new_id)

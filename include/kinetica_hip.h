@@ -192,6 +192,20 @@ int kin_flux_batched(kin_network* h, int64_t B, const double* u, const double* k
  * device-resident rate table (what kin_solve(k_table) / kin_rate_table left there). */
 int kin_solution_flux(kin_network* h, const double* w, const double* k, int64_t n_k_rows, const int64_t* k_row,
                       const double* T_rows, double* flux, double* rates);
+/* Which kernel instantiation and grid a flux call takes, without a device or a handle: the launch plan of the per-state pass
+ * (segmented == 0) or of the segmented pass (segmented != 0, B = S L) for a network of n_species x n_reactions on a device of
+ * n_cu compute units (kin_network_compute_units). temperature_form != 0: temperatures given; else k rows k_stride doubles
+ * apart (0: one shared row; n_reactions for the entries above). u_bits, k_bits, rates_bits: the low four address bits of
+ * the state, rate-constant and per-state-rates buffers (rates_bits < 0: no rates asked for; the segmented pass has none).
+ * The KIN_FLUX_LDS / KIN_FLUX_ROWS switches of the calling process are honoured, as in a real call.
+ * info[6]: path (0 state staged in LDS as 16-byte words, 1 staged as it comes, 2 gathered from global memory), rows of
+ * reaction pairs per thread, reaction parts, state slices G, k mode (0 16-byte loads, 1 8-byte loads, 2 Arrhenius law in the
+ * kernel), rates mode (0 none, 1 16-byte stores, 2 8-byte stores). KIN_ERR_INVALID_ARG for sizes < 1 or bits outside 0 .. 15.
+ * Added under KIN_ABI_VERSION 6: look the symbols up before calling them. */
+int kin_flux_plan_host(int64_t n_species, int64_t n_reactions, int64_t B, int n_cu, int temperature_form, int segmented,
+                       int64_t k_stride, int u_bits, int k_bits, int rates_bits, int64_t* info);
+/* Compute units of the device the handle lives on (what its launch plans are sized by). */
+int kin_network_compute_units(const kin_network* h, int* n_cu);
 
 /* ---- A3: analytic sparse Jacobian ---------------------------------------------------- */
 /* Replaces ODEProblem(...; jac=true, sparse=true) (methods.jl:157-158): pattern (CSR,

@@ -39,6 +39,7 @@ SYMBOLS = [
     "kin_ensemble_pfa",
     "kin_jac_batched", "kin_jac_batched_dev", "kin_timescale_batched", "kin_timescale_batched_dev", "kin_solution_timescale",
     "kin_ensemble_timescale", "kin_timescale_plan_host",
+    "kin_flux_plan_host", "kin_network_compute_units",
 ]
 # in-degree classes of the DRGEP path search (drg.hpp: IN_SHORT_MAX, IN_WAVE_MAX): a lane, a wavefront, the workgroup
 DRGEP_IN_SHORT_MAX, DRGEP_IN_WAVE_MAX = 32, 256
@@ -158,6 +159,9 @@ def lib():
             L.kin_flux_batched.argtypes = [c_void_p, c_int64, PD, PD, c_int64, P64, PD, PD, PD, PD]
             L.kin_flux_batched_dev.argtypes = [c_void_p, c_int64] + [c_void_p] * 8
             L.kin_solution_flux.argtypes = [c_void_p, PD, PD, c_int64, P64, PD, PD, PD]
+        if hasattr(L, "kin_flux_plan_host"):   # (also under ABI 6: the flux passes' plan query)
+            L.kin_flux_plan_host.argtypes = [c_int64, c_int64, c_int64, c_int, c_int, c_int, c_int64, c_int, c_int, c_int, P64]
+            L.kin_network_compute_units.argtypes = [c_void_p, POINTER(c_int)]
         if hasattr(L, "kin_flux_segmented"):   # (also under ABI 6: the segmented pass and the analysis of a stored ensemble)
             L.kin_flux_segmented.argtypes = [c_void_p, c_int64, c_int64, P64, PD, PD, c_int64, P64, PD, PD, PD]
             L.kin_flux_segmented_dev.argtypes = [c_void_p, c_int64, c_int64] + [c_void_p] * 8
@@ -344,6 +348,25 @@ def timescale_plan_host(net):
     return {k: int(v) for k, v in zip(TIMESCALE_INFO, info)}
 
 
+FLUX_PLAN_INFO = ("path", "rows", "parts", "G", "k_mode", "rates_mode")
+FLUX_K16, FLUX_K8, FLUX_T = 0, 1, 2      # k modes of the flux kernels (flux_kernels.hpp: FluxMode)
+
+
+def flux_plan_host(n_species, n_reactions, B, n_cu, temperature_form=False, segmented=False, k_stride=None, u_bits=0, k_bits=0,
+                   rates_bits=None):
+    """kin_flux_plan_host (no device, no handle): a dict of the FLUX_PLAN_INFO values - the instantiation and grid a call of the
+    per-state flux pass (segmented: of the segmented pass, B = S L) takes on a device of n_cu compute units. k_stride: doubles
+    between k rows (None: n_reactions, 0: one shared row); u_bits / k_bits / rates_bits: the low four address bits of the
+    buffers (rates_bits None: no per-state rates). Reads KIN_FLUX_LDS / KIN_FLUX_ROWS as a real call does."""
+    info = np.zeros(len(FLUX_PLAN_INFO), np.int64)
+    st = lib().kin_flux_plan_host(int(n_species), int(n_reactions), int(B), int(n_cu), int(bool(temperature_form)), int(bool(segmented)),
+                                  int(n_reactions if k_stride is None else k_stride), int(u_bits), int(k_bits),
+                                  -1 if rates_bits is None else int(rates_bits), _p64(info))
+    if st != KIN_OK:
+        raise KineticaHipError(st, "flux plan query: argument out of range")
+    return {k: int(v) for k, v in zip(FLUX_PLAN_INFO, info)}
+
+
 def arrhenius_eval(Ea, A, T, k_max=None, t_mult=1.0):
     """calculator(; T) on the device without a network handle."""
     Ea, A = _f64(Ea), _f64(A)
@@ -389,6 +412,12 @@ class HipNetwork:
     @property
     def handle(self):
         return self._h
+
+    def compute_units(self):
+        """kin_network_compute_units: compute units of the handle's device (the n_cu of flux_plan_host)."""
+        n = c_int(0)
+        self._chk(lib().kin_network_compute_units(self._h, ctypes.byref(n)))
+        return n.value
 
     # --- rates -------------------------------------------------------------------------
     def set_rates(self, k):

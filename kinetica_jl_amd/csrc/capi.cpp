@@ -192,6 +192,12 @@ int kin_network_sizes(const kin_network* h, int64_t* n_species, int64_t* n_react
   return KIN_OK;
 }
 
+int kin_network_compute_units(const kin_network* h, int* n_cu) {
+  if (!h || !n_cu) return KIN_ERR_INVALID_ARG;
+  *n_cu = h->n_cu;
+  return KIN_OK;
+}
+
 int kin_set_rates(kin_network* h, const double* k) {
   if (!h) return KIN_ERR_INVALID_ARG;
   KIN_TRY(h)

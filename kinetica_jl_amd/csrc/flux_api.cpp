@@ -135,6 +135,19 @@ void require_ensemble(const kin_network* h) {
 
 extern "C" {
 
+int kin_flux_plan_host(int64_t n_species, int64_t n_reactions, int64_t B, int n_cu, int temperature_form, int segmented,
+                       int64_t k_stride, int u_bits, int k_bits, int rates_bits, int64_t* info) {
+  if (!info || n_species < 1 || n_reactions < 1 || B < 1 || n_cu < 1 || u_bits < 0 || u_bits > 15 || k_bits < 0 || k_bits > 15 ||
+      rates_bits > 15 || (segmented && rates_bits >= 0))
+    return KIN_ERR_INVALID_ARG;
+  // exactly what flux_run / flux_seg_run ask for
+  const FluxPlan p = flux_plan(B, n_reactions, n_species, n_cu, temperature_form != 0, u_bits == 0, segmented ? FLUX_SEG_MAX_ROWS : 8);
+  const FluxModes m = flux_modes(n_reactions, temperature_form != 0, k_stride, (unsigned)k_bits, rates_bits >= 0,
+                                 rates_bits >= 0 ? (unsigned)rates_bits : 0u);
+  info[0] = p.path; info[1] = p.rows; info[2] = p.parts; info[3] = p.G; info[4] = m.k_mode; info[5] = m.rates_mode;
+  return KIN_OK;
+}
+
 int kin_flux_batched_dev(kin_network* h, int64_t B, const double* d_u, const double* d_k, const int64_t* d_k_row, const double* d_T,
                          const double* d_w, double* d_flux, double* d_rates, void* stream) {
   if (!h) return KIN_ERR_INVALID_ARG;

@@ -61,6 +61,16 @@ FluxPlan flux_plan(int64_t B, int64_t R, int64_t N, int n_cu, bool temperature_f
   return p;
 }
 
+FluxModes flux_modes(int64_t R, bool temperature_form, int64_t k_stride, unsigned k_bits, bool want_rates, unsigned rates_bits) {
+  FluxModes m;
+  m.k_mode = FLUX_T;
+  if (!temperature_form) m.k_mode = (R % 2 == 0 && (k_stride % 2 == 0) && ((k_bits & 15) == 0)) ? FLUX_K16 : FLUX_K8;
+  if (!want_rates) m.rates_mode = 0;
+  else if (R % 2 == 0 && (rates_bits & 15) == 0) m.rates_mode = 1;
+  else m.rates_mode = 2;
+  return m;
+}
+
 static __device__ const double kFluxOne[1] = {1.0};
 typedef double flux_d2 __attribute__((ext_vector_type(2)));
 
@@ -379,32 +389,34 @@ static void flux_go_t(const FluxPlan& p, const FluxArgs& a, hipStream_t s) {
 }
 
 template <int ROWS, int MODE, int PATH>
-static void flux_go(const FluxPlan& p, const FluxArgs& a, hipStream_t s) {
-  if (!a.rates) return flux_go_t<ROWS, MODE, PATH, 0>(p, a, s);
-  if (a.R % 2 == 0 && (reinterpret_cast<uintptr_t>(a.rates) & 15) == 0) return flux_go_t<ROWS, MODE, PATH, 1>(p, a, s);
+static void flux_go(const FluxPlan& p, const FluxArgs& a, int rates_mode, hipStream_t s) {
+  if (rates_mode == 0) return flux_go_t<ROWS, MODE, PATH, 0>(p, a, s);
+  if (rates_mode == 1) return flux_go_t<ROWS, MODE, PATH, 1>(p, a, s);
   flux_go_t<ROWS, MODE, PATH, 2>(p, a, s);
 }
 
 template <int MODE, int PATH>
-static void flux_go_rows(const FluxPlan& p, const FluxArgs& a, hipStream_t s) {
-  if (p.rows == 1) return flux_go<1, MODE, PATH>(p, a, s);
-  if (p.rows == 2) return flux_go<2, MODE, PATH>(p, a, s);
+static void flux_go_rows(const FluxPlan& p, const FluxArgs& a, int rates_mode, hipStream_t s) {
+  if (p.rows == 1) return flux_go<1, MODE, PATH>(p, a, rates_mode, s);
+  if (p.rows == 2) return flux_go<2, MODE, PATH>(p, a, rates_mode, s);
   if constexpr (MODE != FLUX_T) {   // (flux_plan: the temperature form stops at 2 rows, paths 1 and 2 at 4)
-    if (p.rows == 4) return flux_go<4, MODE, PATH>(p, a, s);
-    if constexpr (PATH == 0) if (p.rows == 8) return flux_go<8, MODE, PATH>(p, a, s);
+    if (p.rows == 4) return flux_go<4, MODE, PATH>(p, a, rates_mode, s);
+    if constexpr (PATH == 0) if (p.rows == 8) return flux_go<8, MODE, PATH>(p, a, rates_mode, s);
   }
   throw KinError(ERR_INVALID_ARG, "flux sweep: no instantiation for this row count");
 }
 
+static unsigned flux_low_bits(const void* p) { return (unsigned)(reinterpret_cast<uintptr_t>(p) & 15); }
+
 void launch_flux_sweep(const FluxPlan& p, const FluxArgs& a, hipStream_t s) {
   if (a.B == 0 || a.R == 0) return;
-  int mode = FLUX_T;
-  if (!a.T) mode = (a.R % 2 == 0 && (a.k_stride % 2 == 0) && ((reinterpret_cast<uintptr_t>(a.k) & 15) == 0)) ? FLUX_K16 : FLUX_K8;
+  const FluxModes m = flux_modes(a.R, a.T != nullptr, a.k_stride, flux_low_bits(a.k), a.rates != nullptr, flux_low_bits(a.rates));
+  const int mode = m.k_mode;
 #define KIN_FLUX_PATHS(MODE)                                        \
   do {                                                              \
-    if (p.path == 0) flux_go_rows<MODE, 0>(p, a, s);                \
-    else if (p.path == 1) flux_go_rows<MODE, 1>(p, a, s);           \
-    else flux_go_rows<MODE, 2>(p, a, s);                            \
+    if (p.path == 0) flux_go_rows<MODE, 0>(p, a, m.rates_mode, s);  \
+    else if (p.path == 1) flux_go_rows<MODE, 1>(p, a, m.rates_mode, s); \
+    else flux_go_rows<MODE, 2>(p, a, m.rates_mode, s);              \
   } while (0)
   if (mode == FLUX_K16) KIN_FLUX_PATHS(FLUX_K16);
   else if (mode == FLUX_K8) KIN_FLUX_PATHS(FLUX_K8);
@@ -438,8 +450,7 @@ static void flux_seg_go_rows(const FluxPlan& p, const FluxSegArgs& a, hipStream_
 
 void launch_flux_seg(const FluxPlan& p, const FluxSegArgs& a, hipStream_t s) {
   if (a.S == 0 || a.R == 0) return;
-  int mode = FLUX_T;
-  if (!a.T) mode = (a.R % 2 == 0 && (a.k_stride % 2 == 0) && ((reinterpret_cast<uintptr_t>(a.k) & 15) == 0)) ? FLUX_K16 : FLUX_K8;
+  const int mode = flux_modes(a.R, a.T != nullptr, a.k_stride, flux_low_bits(a.k), false, 0).k_mode;
 #define KIN_FLUX_SEG_PATHS(MODE)                                    \
   do {                                                              \
     if (p.path == 0) flux_seg_go_rows<MODE, 0>(p, a, s);            \

@@ -27,6 +27,13 @@ struct FluxPlan { int rows, parts, G, path; };
 enum FluxMode : int { FLUX_K16 = 0, FLUX_K8 = 1, FLUX_T = 2 };   // k rows as double2 / as doubles / Arrhenius law at T[b]
 FluxPlan flux_plan(int64_t B, int64_t R, int64_t N, int n_cu, bool temperature_form, bool u_aligned, int max_rows = 8);
 
+// The rest of an instantiation, chosen from R and the alignment of the caller's pointers (their low four address bits):
+//   k_mode      FLUX_T with temperatures; else FLUX_K16 when every k row is 16-byte aligned and holds whole pairs (R even,
+//               k_stride even, aligned base), else FLUX_K8. The segmented pass takes the same rule.
+//   rates_mode  the kernel's RATES: 0 no per-state rates, 1 written as double2 (R even, aligned base), 2 as doubles
+struct FluxModes { int k_mode, rates_mode; };
+FluxModes flux_modes(int64_t R, bool temperature_form, int64_t k_stride, unsigned k_bits, bool want_rates, unsigned rates_bits);
+
 struct FluxArgs {
   int N, R, P, B;                  // P = ceil(R / 2) pairs
   const uint2* idx16; const int4* idx32;

@@ -664,6 +664,62 @@ int kin_ensemble_drgep(kin_network* h, int pairing, const double* k, int64_t n_k
                        const double* T_rows /* [K*n_rows] */, const int64_t* targets, int64_t n_targets, int index_base, int accumulate,
                        double* importance /* [N] */);
 
+/* ---- reaction elimination (Lu & Law 2008): one importance index per reaction -------------------------------------------- */
+/* Rates q_r, records, pairing, nu_A and den_A are exactly those of the "directed relation graph" block above: with pairing a
+ * record is a reaction with its exact reverse and w = q_kf - q_kr, without pairing every reaction is a record and w = q_r;
+ * den_A = sum over records with nu_A != 0 of |nu_A| |w|.
+ *
+ * For one state b and a record rho:
+ *
+ *   I_rho(b)      = max over species A with nu_A(rho) != 0 and A selected of  fl(fl(|nu_A| * |w(b)|) / den_A(b))
+ *                   (a species with den_A == 0 contributes exactly 0.0; no selected species with nu != 0: 0.0)
+ *   importance[r] = max over the counted states of I_rho(b),  for every reaction r of record rho
+ *
+ * The output has one entry per REACTION, in the caller's reaction order; the two reactions of a pair record carry the same
+ * bits. The species reduction passes above say which species to keep; this one says which reactions among the survivors
+ * carry a share >= eps of the turnover of at least one species the caller cares about.
+ *
+ * "Selected" means every species when no list is given (species == NULL), else the listed ids - the convention of DRGEP's
+ * targets: index_base as given on the host entries, 0-based int64 on the device; ids outside [0, N) are KIN_ERR_INVALID_ARG
+ * on the host and passed over on the device; duplicates allowed; a non-null list with n_sel < 1: KIN_ERR_INVALID_ARG. The
+ * denominators are always those of the WHOLE network: the list only restricts which species a reaction is judged by. A
+ * collider with zero net coefficient never counts.
+ *
+ * Every floating-point sum of non-negative terms is monotone, so den_A >= fl(|nu_A| |w|) whatever order the denominator pass
+ * uses: for finite inputs every output is finite and in [0, 1], and a record that is a selected species' only record gets
+ * exactly 1.0 whenever its |w| > 0 in at least one counted state. The maximum over the states is exact, there are no
+ * atomics, and the result is bit-identical from call to call and independent of how the states are cut into blocks (the
+ * workspace of at most 256 MB of per-state rates and KIN_DRG_BLOCK_STATES=n of the DRG pass). accumulate != 0: the current
+ * contents of importance take part in the maximum. B == 0 writes zeros, or leaves importance alone when accumulating. Rate
+ * constants and statuses are exactly kin_flux_batched[_dev]'s and kin_drg_batched's, KIN_ERR_UNSUPPORTED for pairing != 0 on a
+ * network without pair records included. The pass has no size limit beyond the DRG pass's and builds no edge plan.
+ * Added under KIN_ABI_VERSION 6: look the symbols up before calling them. */
+/* The per-reaction table the kernel reads, without a device or a handle; any output may be NULL. The outputs are 0-based whatever
+ * index_base the network was given in. partner[r]: the other reaction of r's pair record or -1; always -1 with pairing == 0.
+ * species[4 r + j], nu[4 r + j]: the record's up to four slots - species or -1, signed net coefficient (0 beside -1) - taken
+ * from the record's forward reaction, the sign flipped for the reverse member. info[3]: records, reactions that have a partner,
+ * reactions without any non-zero slot (their importance is always 0.0). */
+int kin_reaction_importance_plan_host(int64_t n_species, int64_t n_reactions, const int64_t* reac_ptr, const int64_t* reac_idx,
+                                      const int64_t* reac_sto, const int64_t* prod_ptr, const int64_t* prod_idx, const int64_t* prod_sto,
+                                      int index_base, int pairing, int64_t* info /* [3] */, int64_t* partner /* [R] or NULL */,
+                                      int64_t* species /* [4R] or NULL */, int64_t* nu /* [4R] or NULL */);
+/* Device pointers; only enqueues on `stream` (NULL: the handle's) once the workspace has its size. */
+int kin_reaction_importance_batched_dev(kin_network* h, int pairing, int64_t B, const double* d_u, const double* d_k, const int64_t* d_k_row,
+                                        const double* d_T, const int64_t* d_species /* [n_sel] or NULL */, int64_t n_sel, int accumulate,
+                                        double* d_importance /* [R] */, void* stream);
+/* Host arrays. per_state[b][r] = I_rho(b) of every state, for tests that check more than the maximum. */
+int kin_reaction_importance_batched(kin_network* h, int pairing, int64_t B, const double* u, const double* k, int64_t n_k_rows,
+                                    const int64_t* k_row, const double* T, const int64_t* species /* [n_sel] or NULL */, int64_t n_sel,
+                                    int index_base, int accumulate, double* importance /* [R] */, double* per_state /* [B][R] or NULL */);
+/* Over the saved states of the last kin_solve / over the stored ensemble, read where they live: arguments and statuses of
+ * kin_solution_drg / kin_ensemble_drg, plus the species list. Rows past n_saved[m] take no part. */
+int kin_solution_reaction_importance(kin_network* h, int pairing, const double* k, int64_t n_k_rows, const int64_t* k_row,
+                                     const double* T_rows, const int64_t* species, int64_t n_sel, int index_base, int accumulate,
+                                     double* importance /* [R] */);
+int kin_ensemble_reaction_importance(kin_network* h, int pairing, const double* k, int64_t n_k_rows, const int64_t* k_row /* [K*n_rows] */,
+                                     const double* T_rows /* [K*n_rows] */, const int64_t* species, int64_t n_sel, int index_base,
+                                     int accumulate, double* importance /* [R] */);
+
 /* ---- path flux analysis (PFA, Sun, Chen, Gou & Ju 2010): second-generation species coupling --------------------------- */
 /* The rates q, the records, pairing, the signed nu_A and the set S are exactly those of the "directed relation graph" block
  * above. Per state, with w = q_kf - q_kr (pairing) or q_r:
@@ -789,7 +845,8 @@ const char* kin_version(void);
  * kin_ensemble_size / _max / _dot / _flux and the directed relation graph (kin_drg_*, kin_solution_drg, kin_ensemble_drg) came
  * later under 6, found by symbol lookup; so did DRGEP: kin_drgep_*, kin_solution_drgep, kin_ensemble_drgep, and the timescale analysis:
  * kin_jac_batched*, kin_timescale_*, kin_solution_timescale, kin_ensemble_timescale, and path flux analysis: kin_pfa_*,
- * kin_solution_pfa, kin_ensemble_pfa). */
+ * kin_solution_pfa, kin_ensemble_pfa, and reaction elimination: kin_reaction_importance_*, kin_solution_reaction_importance,
+ * kin_ensemble_reaction_importance). */
 #define KIN_ABI_VERSION 6
 int kin_abi_version(void);
 int64_t kin_struct_size(int which); /* 0: sizeof(kin_params), 1: sizeof(kin_stats), else -1 */

@@ -37,6 +37,8 @@ SYMBOLS = [
     "kin_drgep_batched", "kin_drgep_batched_dev", "kin_drgep_paths", "kin_solution_drgep", "kin_ensemble_drgep",
     "kin_pfa_pattern_host", "kin_pfa_pattern", "kin_pfa_batched", "kin_pfa_batched_dev", "kin_pfa_paths", "kin_solution_pfa",
     "kin_ensemble_pfa",
+    "kin_reaction_importance_plan_host", "kin_reaction_importance_batched", "kin_reaction_importance_batched_dev",
+    "kin_solution_reaction_importance", "kin_ensemble_reaction_importance",
     "kin_jac_batched", "kin_jac_batched_dev", "kin_timescale_batched", "kin_timescale_batched_dev", "kin_solution_timescale",
     "kin_ensemble_timescale", "kin_timescale_plan_host",
     "kin_flux_plan_host", "kin_network_compute_units",
@@ -183,6 +185,12 @@ def lib():
             L.kin_drgep_paths.argtypes = [c_void_p, c_int, c_int64, PD, P64, c_int64, c_int, c_int, PD, PD, P32]
             L.kin_solution_drgep.argtypes = [c_void_p, c_int, PD, c_int64, P64, PD, P64, c_int64, c_int, c_int, PD]
             L.kin_ensemble_drgep.argtypes = [c_void_p, c_int, PD, c_int64, P64, PD, P64, c_int64, c_int, c_int, PD]
+        if hasattr(L, "kin_reaction_importance_batched"):   # (also under ABI 6: reaction elimination)
+            L.kin_reaction_importance_plan_host.argtypes = [c_int64, c_int64] + [P64] * 6 + [c_int, c_int, P64, P64, P64, P64]
+            L.kin_reaction_importance_batched_dev.argtypes = [c_void_p, c_int, c_int64] + [c_void_p] * 5 + [c_int64, c_int, c_void_p, c_void_p]
+            L.kin_reaction_importance_batched.argtypes = [c_void_p, c_int, c_int64, PD, PD, c_int64, P64, PD, P64, c_int64, c_int, c_int, PD, PD]
+            L.kin_solution_reaction_importance.argtypes = [c_void_p, c_int, PD, c_int64, P64, PD, P64, c_int64, c_int, c_int, PD]
+            L.kin_ensemble_reaction_importance.argtypes = [c_void_p, c_int, PD, c_int64, P64, PD, P64, c_int64, c_int, c_int, PD]
         if hasattr(L, "kin_pfa_batched"):   # (also under ABI 6: path flux analysis)
             L.kin_pfa_pattern_host.argtypes = [c_int64, c_int64] + [P64] * 6 + [c_int, c_int, P64, P64, P64]
             L.kin_pfa_pattern.argtypes = [c_void_p, c_int, c_int, P64, P64, P64]
@@ -303,6 +311,27 @@ def drg_pattern_host(net, pairing=True):
     st = L.kin_drg_pattern_host(*head, _p64(info), _p64(rowptr), _p64(colidx))
     assert st == KIN_OK
     return rowptr, colidx[:int(info[0])], {k: int(v) for k, v in zip(DRG_INFO, info)}
+
+
+REACTION_IMPORTANCE_INFO = ("records", "paired_reactions", "empty_reactions")
+
+
+def reaction_importance_plan_host(net, pairing=True):
+    """kin_reaction_importance_plan_host of a FlatNetwork, computed on the host (no device): (partner[R], species[R][4], nu[R][4],
+    info) - per reaction the other reaction of its pair record (-1: none; always -1 without pairing) and the record's up to
+    four slots (0-based species or -1, signed net coefficient: the forward reaction's, the sign flipped for the reverse member)
+    - and a dict of the REACTION_IMPORTANCE_INFO sizes: records, reactions with a partner, reactions without a non-zero slot."""
+    L = lib()
+    arrs = [np.ascontiguousarray(a, dtype=np.int64) for a in (net.reac_ptr, net.reac_idx, net.reac_sto, net.prod_ptr,
+                                                              net.prod_idx, net.prod_sto)]
+    head = [int(net.n_species), int(net.n_reactions)] + [_p64(a) for a in arrs] + [0, 1 if pairing else 0]
+    R = int(net.n_reactions)
+    info = np.zeros(len(REACTION_IMPORTANCE_INFO), np.int64)
+    partner, species, nu = np.empty(max(R, 1), np.int64), np.empty((max(R, 1), 4), np.int64), np.empty((max(R, 1), 4), np.int64)
+    st = L.kin_reaction_importance_plan_host(*head, _p64(info), _p64(partner), _p64(species), _p64(nu))
+    if st != KIN_OK:
+        raise KineticaHipError(st, L.kin_last_error(None).decode())
+    return partner[:R], species[:R], nu[:R], {k: int(v) for k, v in zip(REACTION_IMPORTANCE_INFO, info)}
 
 
 PFA_INFO = ("edges", "pairs", "products", "max_row")
@@ -722,6 +751,69 @@ class HipNetwork:
         self._chk(lib().kin_ensemble_drgep(self._h, int(bool(pairing)), _pd(k), n_rows, None if k_row is None else _p64(k_row),
                                            _pd(T_rows), _p64(tg), nt, 0, acc, _pd(out)))
         return out[:self.n]
+
+    # --- reaction elimination -------------------------------------------------------------------------
+    def _ri_io(self, species, importance):
+        """(species int64 or None, n_sel, output buffer, accumulate): a fresh buffer, or a copy of `importance` that takes part."""
+        sp, ns = None, 0
+        if species is not None:
+            sp = np.ascontiguousarray(np.asarray(species, dtype=np.int64).ravel())
+            ns = len(sp)
+            if ns == 0:
+                sp = np.zeros(1, np.int64)      # (an empty list stays a list - and an error - not "every species")
+        out = np.zeros(max(self.nr, 1))
+        if importance is None:
+            return sp, ns, out, 0
+        c = _f64(importance).ravel()
+        assert len(c) == self.nr
+        out[:self.nr] = c
+        return sp, ns, out, 1
+
+    def reaction_importance_batched(self, u, species=None, pairing=True, importance=None, per_state=False, k=None, k_row=None, T=None):
+        """kin_reaction_importance_batched on host arrays: importance[R] = max over the states u[B][N] of the largest share
+        |nu_A| |w| / den_A a reaction's record holds of the turnover of any species A it changes (include/kinetica_hip.h has
+        the definition) - A among `species` (0-based ids; None: every species), den_A always over the whole network. Rate
+        constants of state b as in flux_batched. importance given: its values take part in the maximum (the result is
+        returned, the argument is left alone). per_state=True: (importance, I[B][R])."""
+        u = np.ascontiguousarray(np.atleast_2d(_f64(u)))
+        B = u.shape[0]
+        assert u.shape == (B, self.n)
+        k, n_rows, k_row, T, _ = self._flux_inputs(B, k, k_row, T, None)
+        sp, ns, out, acc = self._ri_io(species, importance)
+        ps = np.zeros((B, self.nr)) if per_state else None
+        self._chk(lib().kin_reaction_importance_batched(self._h, int(bool(pairing)), B, _pd(u), _pd(k), n_rows,
+                                                        None if k_row is None else _p64(k_row), _pd(T), None if sp is None else _p64(sp),
+                                                        ns, 0, acc, _pd(out), _pd(ps) if per_state and ps.size else None))
+        return (out[:self.nr], ps) if per_state else out[:self.nr]
+
+    def reaction_importance_batched_dev(self, B, d_u, d_importance, d_species=0, n_sel=0, d_k=0, d_k_row=0, d_T=0, pairing=True,
+                                        accumulate=False, stream=0):
+        """kin_reaction_importance_batched_dev: device pointers (ints; 0 = not given), u[B][N], k rows / k_row[B] (int64) / T[B],
+        species[n_sel] (int64, 0-based; 0: every species), importance[R]. One stream per handle at a time."""
+        p = lambda x: c_void_p(x) if x else None
+        self._chk(lib().kin_reaction_importance_batched_dev(self._h, int(bool(pairing)), int(B), p(d_u), p(d_k), p(d_k_row), p(d_T),
+                                                            p(d_species), int(n_sel), 1 if accumulate else 0, p(d_importance), p(stream)))
+
+    def solution_reaction_importance(self, species=None, k=None, k_row=None, T_rows=None, pairing=True, importance=None):
+        """kin_solution_reaction_importance: reaction_importance_batched over the saved states of the last solve, read where
+        they live on the device (rate-constant sources as solution_flux)."""
+        n_saved = c_int64(0)
+        self._chk(lib().kin_solution_size(self._h, ctypes.byref(n_saved), None))
+        k, n_rows, k_row, T_rows, _ = self._flux_inputs(n_saved.value, k, k_row, T_rows, None)
+        sp, ns, out, acc = self._ri_io(species, importance)
+        self._chk(lib().kin_solution_reaction_importance(self._h, int(bool(pairing)), _pd(k), n_rows, None if k_row is None else _p64(k_row),
+                                                         _pd(T_rows), None if sp is None else _p64(sp), ns, 0, acc, _pd(out)))
+        return out[:self.nr]
+
+    def ensemble_reaction_importance(self, species=None, k=None, k_row=None, T_rows=None, pairing=True, importance=None):
+        """kin_ensemble_reaction_importance: one importance vector over every saved row of every member of the stored ensemble
+        (k_row / T_rows: [K][n_rows], entries past a member's saved rows are ignored)."""
+        K, rows = self.ensemble_size()[:2]
+        k, n_rows, k_row, T_rows, _ = self._flux_inputs(K * rows, k, k_row, T_rows, None)
+        sp, ns, out, acc = self._ri_io(species, importance)
+        self._chk(lib().kin_ensemble_reaction_importance(self._h, int(bool(pairing)), _pd(k), n_rows, None if k_row is None else _p64(k_row),
+                                                         _pd(T_rows), None if sp is None else _p64(sp), ns, 0, acc, _pd(out)))
+        return out[:self.nr]
 
     # --- path flux analysis ------------------------------------------------------------------------
     def pfa_pattern(self, pairing=True):

@@ -343,6 +343,26 @@ int kin_drg_pattern_host(int64_t n_species, int64_t n_reactions, const int64_t* 
   return KIN_OK;
 }
 
+int kin_reaction_importance_plan_host(int64_t n_species, int64_t n_reactions, const int64_t* reac_ptr, const int64_t* reac_idx,
+                                      const int64_t* reac_sto, const int64_t* prod_ptr, const int64_t* prod_idx, const int64_t* prod_sto,
+                                      int index_base, int pairing, int64_t* info, int64_t* partner, int64_t* species, int64_t* nu) {
+  try {
+    const NetworkHost H = compile_network(n_species, n_reactions, reac_ptr, reac_idx, reac_sto, prod_ptr, prod_idx, prod_sto, index_base);
+    const RiTables t = build_ri_tables(H, pairing);
+    if (info) { info[0] = t.n_records; info[1] = t.n_paired; info[2] = t.n_empty; }
+    if (partner) for (int64_t r = 0; r < t.R; r++) partner[r] = t.partner[r];
+    if (species) for (int64_t i = 0; i < 4 * t.R; i++) species[i] = t.species[i];
+    if (nu) for (int64_t i = 0; i < 4 * t.R; i++) nu[i] = t.nu[i];
+  } catch (const KinError& e) {
+    g_create_err = e.what();
+    return e.code;
+  } catch (const std::exception& e) {
+    g_create_err = e.what();
+    return KIN_ERR_INVALID_ARG;
+  }
+  return KIN_OK;
+}
+
 int kin_pfa_pattern_host(int64_t n_species, int64_t n_reactions, const int64_t* reac_ptr, const int64_t* reac_idx,
                          const int64_t* reac_sto, const int64_t* prod_ptr, const int64_t* prod_idx, const int64_t* prod_sto,
                          int index_base, int pairing, int64_t* info, int64_t* rowptr, int64_t* colidx) {

@@ -29,7 +29,7 @@ void classify(const std::vector<int32_t>& ptr, int64_t cls[3]) {
 
 }  // namespace
 
-DrgTables build_drg_tables(const NetworkHost& h, int pairing, bool with_plans) {
+DrgTables build_drg_tables(const NetworkHost& h, int pairing, bool with_plans, bool with_edges) {
   DrgTables t;
   const int64_t N = h.N, R = h.R;
   t.N = N;
@@ -37,7 +37,7 @@ DrgTables build_drg_tables(const NetworkHost& h, int pairing, bool with_plans) {
   const int64_t n_rec = pairing ? h.n_pairs() : R;
   std::vector<Contrib> den, num;
   den.reserve((size_t)n_rec * 4);
-  num.reserve((size_t)n_rec * 12);
+  if (with_edges) num.reserve((size_t)n_rec * 12);
   for (int64_t p = 0; p < n_rec; p++) {
     const int32_t kf = pairing ? h.pair_k[2 * p] : (int32_t)p, kr = pairing ? h.pair_k[2 * p + 1] : -1;
     int32_t S[6]; int nS = 0;
@@ -54,7 +54,7 @@ DrgTables build_drg_tables(const NetworkHost& h, int pairing, bool with_plans) {
       const int nu = (int)(int8_t)((uint32_t)h.slot_co[kf] >> (8 * j));
       const float c = (float)(nu < 0 ? -nu : nu);
       den.push_back({A, -1, kf, kr, c, (float)nu});
-      for (int q = 0; q < nS; q++) if (S[q] != A) num.push_back({A, S[q], kf, kr, c, (float)nu});
+      for (int q = 0; q < nS && with_edges; q++) if (S[q] != A) num.push_back({A, S[q], kf, kr, c, (float)nu});
     }
   }
   // (stable: the contributions of a row / an edge stay in record order)
@@ -90,6 +90,7 @@ DrgTables build_drg_tables(const NetworkHost& h, int pairing, bool with_plans) {
     place_coefs(out, slot, sg, ell_s, long_s);
   };
   plan(den, den_ptr, nullptr, t.den_plan, t.den_ell_c, t.den_long_c, t.den_ell_s, t.den_long_s);
+  if (!with_edges) { t.have_plans = true; return t; }
   plan(num, edge_ptr, edge_row.data(), t.edge_plan, t.edge_ell_c, t.edge_long_c, t.edge_ell_s, t.edge_long_s);
   // the transpose of the pattern (a counting sort by head: the sources of a species stay ascending)
   t.in_ptr.assign((size_t)N + 1, 0);
@@ -114,6 +115,47 @@ DrgTables build_drg_tables(const NetworkHost& h, int pairing, bool with_plans) {
       if (in_class(i) == c) { t.in_order.push_back((int32_t)i); t.in_cls[c]++; }
   t.have_plans = true;
   return t;
+}
+
+RiTables build_ri_tables(const NetworkHost& h, int pairing) {
+  RiTables t;
+  const int64_t R = h.R;
+  t.R = R;
+  if (pairing && R > 0 && h.pair_k.empty()) throw KinError(ERR_UNSUPPORTED, "reaction importance with pairing needs the pair records (N < 65535)");
+  t.n_records = pairing ? h.n_pairs() : R;
+  t.partner.assign((size_t)R, -1);
+  t.species.assign((size_t)4 * R, -1);
+  t.nu.assign((size_t)4 * R, 0);
+  for (int64_t p = 0; p < t.n_records; p++) {
+    const int32_t kf = pairing ? h.pair_k[2 * p] : (int32_t)p, kr = pairing ? h.pair_k[2 * p + 1] : -1;
+    if (kr >= 0) { t.partner[kf] = kr; t.partner[kr] = kf; t.n_paired += 2; }
+    bool any = false;
+    for (int j = 0; j < 4; j++) {
+      const int32_t A = h.slot_sp[4 * kf + j];
+      if (A < 0) continue;
+      const int nu = (int)(int8_t)((uint32_t)h.slot_co[kf] >> (8 * j));
+      t.species[4 * kf + j] = A; t.nu[4 * kf + j] = nu;
+      if (kr >= 0) { t.species[4 * kr + j] = A; t.nu[4 * kr + j] = -nu; }
+      any = any || nu != 0;
+    }
+    if (!any) t.n_empty += kr >= 0 ? 2 : 1;
+  }
+  return t;
+}
+
+std::vector<int32_t> RiTables::dev() const {
+  std::vector<int32_t> d((size_t)6 * R, 0);
+  for (int64_t r = 0; r < R; r++) {
+    d[r] = partner[r];
+    uint32_t co = 0;
+    for (int j = 0; j < 4; j++) {
+      const int32_t c = nu[4 * r + j];
+      d[(size_t)(1 + j) * R + r] = c != 0 ? species[4 * r + j] : -1;
+      co |= (uint32_t)(c < 0 ? -c : c) << (8 * j);
+    }
+    d[(size_t)5 * R + r] = (int32_t)co;
+  }
+  return d;
 }
 
 }  // namespace kin

@@ -43,8 +43,9 @@ struct DrgTables {
   std::vector<int32_t> in_ptr, in_src, in_edge, in_order;
   int64_t in_cls[3] = {0, 0, 0};
 };
-// pairing != 0 needs the pair records (compile_network builds them for N < 65535): KinError(ERR_UNSUPPORTED) without
-DrgTables build_drg_tables(const NetworkHost& h, int pairing, bool with_plans);
+// pairing != 0 needs the pair records (compile_network builds them for N < 65535): KinError(ERR_UNSUPPORTED) without.
+// with_edges = false (reaction importance): the denominator side alone - no edge pattern, edge plan or transpose (E = 0).
+DrgTables build_drg_tables(const NetworkHost& h, int pairing, bool with_plans, bool with_edges = true);
 
 struct DrgArgs {
   SegPlanView p;
@@ -69,6 +70,33 @@ void launch_drgep_den(const DrgArgs& a, int Y, hipStream_t s);
 void launch_drgep_edges(const DrgArgs& a, int Y, hipStream_t s);
 // PFA split stage (pfa.hpp) on the signed plans, after launch_drgep_den: r[bl][e] = P_AB / den_A, rc[bl][e] = C_AB / den_A
 void launch_pfa_split(const DrgArgs& a, int Y, hipStream_t s);
+
+// Reaction importance (kin_reaction_importance_*; definition: include/kinetica_hip.h; reaction_importance_kernels.hip): after
+// stage 1 and the denominator launch, one thread per REACTION forms max over its record's selected species of |nu_A| |w| / den_A.
+// The table it reads has one row per reaction: the other reaction of its pair (-1: none; always -1 without pairing) and the
+// record's up to four (species, nu) slots - the forward reaction's, the sign flipped for the reverse member.
+struct RiTables {
+  int64_t R = 0, n_records = 0, n_paired = 0, n_empty = 0;   // n_paired: reactions with a partner; n_empty: without a slot
+  std::vector<int32_t> partner;          // R
+  std::vector<int32_t> species, nu;      // 4 R each: 0-based species or -1, signed net coefficient (0 beside -1)
+  std::vector<int32_t> dev() const;      // the device form [6][R]: partner, the four species, |nu| in four packed bytes
+};
+RiTables build_ri_tables(const NetworkHost& h, int pairing);   // pairing without pair records: KinError(ERR_UNSUPPORTED)
+
+struct RiArgs {
+  int N, R, nb;
+  const int32_t* tab;              // RiTables::dev()
+  const uint8_t* mask;             // mask[N]: 1 for a selected species; null: all of them
+  const double* rates;             // rates[nb][R]
+  const double* den;               // den[nb][N] of launch_drg_den
+  int64_t b0; const int64_t* seg_n; int64_t L;     // as DrgArgs
+  double* part;                    // part[Y][R]: the maxima per slice of the states
+  double* per_state;               // per_state[nb][R] or null (a state that does not count: 0.0)
+};
+int ri_slices(int64_t R, int64_t nb, int n_cu);
+// mask[N] from n_sel species ids on the device (0-based; ids outside [0, N) are passed over)
+void launch_ri_mask(int64_t n_sel, const int64_t* sel, int64_t N, uint8_t* mask, hipStream_t s);
+void launch_ri(const RiArgs& a, int Y, hipStream_t s);
 
 // DRGEP path stage (drgep_kernels.hip): one workgroup per state relaxes R_B = max(R_B, R_A r_AB) over the incoming edges
 // until nothing changes (at most N rounds). R is double-buffered in LDS (in_lds: N <= DRGEP_LDS_SPECIES), else in work.

@@ -1,5 +1,7 @@
 // extern "C" entry points of the directed-relation-graph pass (declarations: include/kinetica_hip.h; tables: drg.cpp;
-// kernels: drg_kernels.hip). kin_drg_pattern_host, which needs no handle, sits with the other host-only entries in capi.cpp.
+// kernels: drg_kernels.hip) and of the reaction-importance pass, which runs that pass's first two stages (kernel:
+// reaction_importance_kernels.hip). kin_drg_pattern_host and kin_reaction_importance_plan_host, which need no handle, sit with the
+// other host-only entries in capi.cpp.
 #include "../../include/kinetica_hip.h"
 
 #include <algorithm>
@@ -84,6 +86,106 @@ void drg_run(kin_network* h, int pairing, int64_t B, const double* d_u, const Fl
     launch_drg_edges(a, Ye, s);
     launch_drg_max(E, Ye, h->drg_part.p, d_coef, (accumulate || b0 > 0) ? 1 : 0, s);
   }
+}
+
+// ---- reaction importance ------------------------------------------------------------------------------------------------
+RiTables& ri_host(kin_network* h, int pairing) {
+  auto& m = h->ri[pairing ? 1 : 0];
+  if (!m.host) m.host = std::make_unique<RiTables>(build_ri_tables(h->host, pairing));
+  return *m.host;
+}
+
+// the denominator plan of a pairing mode on the device: the DRG pass's when that has been uploaded, else one built without edges
+struct RiDen { SegPlanView p; const float* ell_c; const float* long_c; };
+RiDen ri_dev(kin_network* h, int pairing, hipStream_t s) {
+  auto& m = h->ri[pairing ? 1 : 0];
+  auto& g = h->drg[pairing ? 1 : 0];
+  if (!m.dev_ready) {
+    m.tab.upload(ri_host(h, pairing).dev(), s);
+    if (!g.dev_ready) {
+      m.den_host = std::make_unique<DrgTables>(build_drg_tables(h->host, pairing, true, false));
+      m.den_plan.upload(m.den_host->den_plan, s);
+      m.den_ell_c.upload(m.den_host->den_ell_c, s); m.den_long_c.upload(m.den_host->den_long_c, s);
+    }
+    KIN_HIP(hipStreamSynchronize(s));
+    m.dev_ready = true;
+  }
+  if (m.den_host) return RiDen{m.den_plan.view(), m.den_ell_c.p, m.den_long_c.p};
+  return RiDen{g.den_plan.view(), g.den_ell_c.p, g.den_long_c.p};
+}
+
+// The pass on device buffers, block by block: stage 1 (the flux sweep) writes the block's rates, the denominator launch
+// den[nb][N], the importance launch the maxima per slice, folded into d_imp. d_sel: the selected species on the device (null:
+// all). per_state: host rows [B][R] to download every block's values into, or null. seg_n / L: see DrgArgs.
+void ri_run(kin_network* h, int pairing, int64_t B, const double* d_u, const FluxSource& src, const int64_t* d_seg_n, int64_t L,
+            const int64_t* d_sel, int64_t n_sel, int accumulate, double* d_imp, double* per_state, hipStream_t s) {
+  const int64_t N = h->host.N, R = h->host.R;
+  const RiDen dn = ri_dev(h, pairing, s);
+  if (R == 0) return;
+  if (B == 0) {
+    if (!accumulate) KIN_HIP(hipMemsetAsync(d_imp, 0, (size_t)R * sizeof(double), s));
+    return;
+  }
+  int64_t nb_max = std::max<int64_t>(1, (int64_t)(DRG_RATES_BYTES / ((size_t)R * sizeof(double))));
+  if (const char* e = getenv("KIN_DRG_BLOCK_STATES")) {   // (read per call: tests change it)
+    const int64_t v = atoll(e);
+    if (v >= 1) nb_max = std::min(nb_max, v);
+  }
+  nb_max = std::min(nb_max, B);
+  h->drg_rates.alloc((size_t)nb_max * R);
+  h->drg_den.alloc((size_t)nb_max * N);
+  h->ri_part.alloc((size_t)ri_slices(R, nb_max, h->n_cu) * R);
+  if (per_state) h->ri_state.alloc((size_t)nb_max * R);
+  if (d_sel) { h->ri_mask.alloc((size_t)std::max<int64_t>(N, 1)); launch_ri_mask(n_sel, d_sel, N, h->ri_mask.p, s); }
+  for (int64_t b0 = 0; b0 < B; b0 += nb_max) {
+    const int64_t nb = std::min(nb_max, B - b0);
+    FluxSource bs = src;
+    if (bs.k && !bs.k_row) bs.k += (size_t)b0 * (size_t)bs.k_stride;
+    if (bs.k_row) bs.k_row += b0;
+    if (bs.T) bs.T += b0;
+    flux_run(h, nb, d_u + (size_t)b0 * N, bs, nullptr, nullptr, h->drg_rates.p, s);
+    DrgArgs a{};
+    a.N = (int)N; a.R = (int)R; a.E = 0; a.nb = (int)nb;
+    a.rates = h->drg_rates.p; a.b0 = b0; a.seg_n = d_seg_n; a.L = L;
+    a.den = h->drg_den.p;
+    a.p = dn.p; a.ell_c = dn.ell_c; a.long_c = dn.long_c;
+    launch_drg_den(a, drg_slices(dn.p, nb, h->n_cu), s);
+    RiArgs ra{};
+    ra.N = (int)N; ra.R = (int)R; ra.nb = (int)nb;
+    ra.tab = h->ri[pairing ? 1 : 0].tab.p; ra.mask = d_sel ? h->ri_mask.p : nullptr;
+    ra.rates = h->drg_rates.p; ra.den = h->drg_den.p;
+    ra.b0 = b0; ra.seg_n = d_seg_n; ra.L = L;
+    ra.part = h->ri_part.p; ra.per_state = per_state ? h->ri_state.p : nullptr;
+    const int Y = ri_slices(R, nb, h->n_cu);
+    launch_ri(ra, Y, s);
+    launch_drg_max(R, Y, h->ri_part.p, d_imp, (accumulate || b0 > 0) ? 1 : 0, s);
+    if (per_state) h->ri_state.download(per_state + (size_t)b0 * R, (size_t)nb * R, s);
+  }
+}
+
+// the species list of a host entry: null = all species; else checked, made 0-based and uploaded
+const int64_t* ri_species(kin_network* h, const int64_t* species, int64_t n_sel, int index_base, hipStream_t s) {
+  if (!species) return nullptr;
+  require(n_sel >= 1 && n_sel < ((int64_t)1 << 31), ERR_INVALID_ARG, "a species list needs at least one entry");
+  std::vector<int64_t> t(species, species + n_sel);
+  for (int64_t& x : t) {
+    x -= index_base;
+    require(x >= 0 && x < h->host.N, ERR_INVALID_ARG, "species out of range");
+  }
+  h->ri_sel.upload(t, s);
+  KIN_HIP(hipStreamSynchronize(s));      // (t leaves scope)
+  return h->ri_sel.p;
+}
+
+// host entries: importance staged through the handle's buffer (uploaded first when it takes part in the maximum)
+void ri_host_call(kin_network* h, int pairing, int64_t B, const double* d_u, const FluxSource& src, const int64_t* d_seg_n, int64_t L,
+                  const int64_t* d_sel, int64_t n_sel, int accumulate, double* importance, double* per_state, hipStream_t s) {
+  const int64_t R = h->host.R;
+  h->ri_imp.alloc((size_t)R);
+  if (accumulate && R > 0) h->ri_imp.upload(importance, (size_t)R, s);
+  ri_run(h, pairing, B, d_u, src, d_seg_n, L, d_sel, n_sel, accumulate, h->ri_imp.p, per_state, s);
+  if (R > 0) h->ri_imp.download(importance, (size_t)R, s);
+  KIN_HIP(hipStreamSynchronize(s));
 }
 
 }  // namespace
@@ -228,6 +330,65 @@ int kin_ensemble_drg(kin_network* h, int pairing, const double* k, int64_t n_k_r
   hipStream_t s = h->stream;
   const FluxSource src = drg_ensemble_source(h, k, n_k_rows, k_row, T_rows, coef != nullptr, s);
   drg_host_call(h, pairing, h->ens.K * h->ens.cap, h->ens.sol, src, h->ens_segn.p, h->ens.cap, accumulate, coef, s);
+  KIN_CATCH(h)
+}
+
+int kin_reaction_importance_batched_dev(kin_network* h, int pairing, int64_t B, const double* d_u, const double* d_k, const int64_t* d_k_row,
+                                        const double* d_T, const int64_t* d_species, int64_t n_sel, int accumulate, double* d_importance,
+                                        void* stream) {
+  if (!h) return KIN_ERR_INVALID_ARG;
+  KIN_TRY(h)
+  drg_check(h, B, d_k != nullptr, d_k_row != nullptr, d_T != nullptr, d_importance != nullptr);
+  require(d_u != nullptr || B == 0, ERR_INVALID_ARG, "null state buffer");
+  require(d_species == nullptr || (n_sel >= 1 && n_sel < ((int64_t)1 << 31)), ERR_INVALID_ARG, "a species list needs at least one entry");
+  hipStream_t s = stream ? (hipStream_t)stream : h->stream;
+  ri_run(h, pairing, B, d_u, FluxSource{d_k, h->host.R, d_k_row, d_T}, nullptr, 0, d_species, n_sel, accumulate, d_importance, nullptr, s);
+  KIN_CATCH(h)
+}
+
+int kin_reaction_importance_batched(kin_network* h, int pairing, int64_t B, const double* u, const double* k, int64_t n_k_rows,
+                                    const int64_t* k_row, const double* T, const int64_t* species, int64_t n_sel, int index_base,
+                                    int accumulate, double* importance, double* per_state) {
+  if (!h) return KIN_ERR_INVALID_ARG;
+  KIN_TRY(h)
+  drg_check(h, B, k != nullptr, k_row != nullptr, T != nullptr, importance != nullptr);
+  require(u != nullptr || B == 0, ERR_INVALID_ARG, "null state buffer");
+  if (k && k_row) { require(n_k_rows >= 1 || B == 0, ERR_INVALID_ARG, "k has no rows"); flux_check_rows(k_row, B, n_k_rows); }
+  else if (k) require(n_k_rows == B, ERR_INVALID_ARG, "k without k_row needs one row per state (n_k_rows == B)");
+  const int64_t N = h->host.N, R = h->host.R;
+  hipStream_t s = h->stream;
+  const int64_t* d_sel = ri_species(h, species, n_sel, index_base, s);
+  if (B > 0) h->f_u.upload(u, (size_t)B * N, s);
+  if (k && n_k_rows > 0) h->f_k.upload(k, (size_t)n_k_rows * R, s);
+  if (k_row && B > 0) h->f_krow.upload(k_row, (size_t)B, s);
+  if (T && B > 0) h->f_T.upload(T, (size_t)B, s);
+  ri_host_call(h, pairing, B, h->f_u.p, FluxSource{k ? h->f_k.p : nullptr, R, k_row ? h->f_krow.p : nullptr, T ? h->f_T.p : nullptr},
+               nullptr, 0, d_sel, n_sel, accumulate, importance, per_state, s);
+  KIN_CATCH(h)
+}
+
+int kin_solution_reaction_importance(kin_network* h, int pairing, const double* k, int64_t n_k_rows, const int64_t* k_row,
+                                     const double* T_rows, const int64_t* species, int64_t n_sel, int index_base, int accumulate,
+                                     double* importance) {
+  if (!h) return KIN_ERR_INVALID_ARG;
+  KIN_TRY(h)
+  hipStream_t s = h->stream;
+  const FluxSource src = drg_solution_source(h, k, n_k_rows, k_row, T_rows, importance != nullptr, s);
+  const int64_t* d_sel = ri_species(h, species, n_sel, index_base, s);
+  ri_host_call(h, pairing, h->n_saved, h->d_sol_u.p, src, nullptr, 0, d_sel, n_sel, accumulate, importance, nullptr, s);
+  KIN_CATCH(h)
+}
+
+int kin_ensemble_reaction_importance(kin_network* h, int pairing, const double* k, int64_t n_k_rows, const int64_t* k_row,
+                                     const double* T_rows, const int64_t* species, int64_t n_sel, int index_base, int accumulate,
+                                     double* importance) {
+  if (!h) return KIN_ERR_INVALID_ARG;
+  KIN_TRY(h)
+  hipStream_t s = h->stream;
+  const FluxSource src = drg_ensemble_source(h, k, n_k_rows, k_row, T_rows, importance != nullptr, s);
+  const int64_t* d_sel = ri_species(h, species, n_sel, index_base, s);
+  ri_host_call(h, pairing, h->ens.K * h->ens.cap, h->ens.sol, src, h->ens_segn.p, h->ens.cap, d_sel, n_sel, accumulate, importance,
+               nullptr, s);
   KIN_CATCH(h)
 }
 

@@ -84,6 +84,22 @@ struct kin_network {
   kin::DevBuf<double> drgep_r, drgep_R, drgep_work, drgep_imp;
   kin::DevBuf<int32_t> drgep_rounds;
   kin::DevBuf<int64_t> drgep_targets;
+  // reaction importance (drg.hpp, drg_api.cpp): the per-reaction table per pairing mode and, where the DRG pass has not
+  // uploaded its plans yet, a denominator plan of its own (no edge plan is built for this pass); the species mask and the
+  // staged list behind it, the maxima per slice, the block's per-state values when asked for and the staging buffer of the
+  // host entries' importance
+  struct RiMode {
+    std::unique_ptr<kin::RiTables> host;
+    std::unique_ptr<kin::DrgTables> den_host;
+    bool dev_ready = false;
+    kin::DevBuf<int32_t> tab;
+    kin::SegPlanDev den_plan;
+    kin::DevBuf<float> den_ell_c, den_long_c;
+  } ri[2];
+  kin::DevBuf<uint8_t> ri_mask;
+  kin::DevBuf<int64_t> ri_sel;
+  kin::DevBuf<double> ri_part, ri_state, ri_imp;
+
   // path flux analysis (pfa.hpp, pfa_api.cpp): the second-generation pattern per pairing mode and, on the device, both
   // patterns and the order of the rows; the block's rp[nb][E], rc[nb][E], the per-state r[nb][E2] when asked for, the maxima
   // per slice and the staging buffer of the host entries' coefficients

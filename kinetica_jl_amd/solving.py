@@ -1103,6 +1103,47 @@ def drgep_select(importance, targets, eps):
     return np.flatnonzero(keep).astype(np.int64)
 
 
+def reaction_importance(out, calculator, species=None, pairing=True, importance=None):
+    """importance[R] of reaction elimination (Lu & Law 2008) over the saved states of a solve: per reaction of `out.rd` the
+    largest share |nu_A| |w| / den_A its record holds of the turnover of any species A it changes, maximised over the saved
+    states (include/kinetica_hip.h has the definition; pairing as in drg_coefficients; the two reactions of a pair carry the
+    same value). `species` (names or 0-based ids; None: every species): the species a reaction is judged by - the
+    denominators are always the whole network's. `importance`: the result of an earlier call, which takes part in the
+    maximum (several solves folded into one ranking). `calculator` and the rate constants of every saved state are chosen as
+    reaction_fluxes chooses them. One device pass (kin_reaction_importance_batched) over sol.u."""
+    sd, rd = out.sd, out.rd
+    setup_network(sd, rd, calculator)
+    t = np.asarray(out.sol.t, dtype=float)
+    u = np.ascontiguousarray(np.asarray(out.sol.u, dtype=float).reshape(len(t), sd.n))
+    sp = None if species is None else [sd.toInt[x] - 1 if isinstance(x, str) else int(x) for x in species]
+    src = saved_state_rate_source(out, calculator, t)
+    h = capi.HipNetwork(*rd.flat(sd.n), index_base=1)
+    try:
+        if "T" in src:
+            h.set_arrhenius(calculator.Ea, calculator.A, calculator.k_max, calculator.t_mult)
+        imp = h.reaction_importance_batched(u, species=sp, pairing=pairing, importance=importance, **src)
+    finally:
+        h.close()
+    return imp
+
+
+_reaction_importance = reaction_importance      # (reduce_network has a keyword of the same name)
+
+
+def reaction_select(importance, eps, candidates=None):
+    """Reactions (0-based, sorted) with importance >= eps, among `candidates` (0-based ids) when given. Pure NumPy."""
+    importance = np.asarray(importance, dtype=float)
+    keep = importance >= float(eps)
+    if candidates is not None:
+        cand = np.unique(np.asarray(list(candidates), dtype=np.int64))
+        if len(cand) and (cand[0] < 0 or cand[-1] >= len(importance)):
+            raise ValueError("candidate reaction id out of range")
+        inside = np.zeros(len(importance), bool)
+        inside[cand] = True
+        keep &= inside
+    return np.flatnonzero(keep).astype(np.int64)
+
+
 @dataclass
 class DRGReduction:
     """Result of reduce_network: the kept species / reactions (0-based positions in the full sd / rd, ascending), the
@@ -1118,6 +1159,11 @@ class DRGReduction:
     targets: np.ndarray
     eps: float
     importance: Optional[np.ndarray] = None       # method="drgep": the importance the selection was made on
+    # Reaction elimination (None: the species rule alone): the threshold and the importance, one entry per reaction of the
+    # FULL network. Plain attributes that reduce_network sets, not dataclass fields: `importance` stays the last field, as
+    # callers that build or unpack a DRGReduction by position (and tests/test_drgep_host.py) expect.
+    reaction_eps = None
+    reaction_importance = None
 
     def map_u0(self, u0):
         """A u0 specification of the full network (ODESimulationParams.u0: dict name -> concentration, or a vector over the
@@ -1138,7 +1184,8 @@ class DRGReduction:
         return out
 
 
-def reduce_network(out, calculator, targets, eps, pairing=True, coef=None, method="drg", importance=None):
+def reduce_network(out, calculator, targets, eps, pairing=True, coef=None, method="drg", importance=None, reaction_eps=None,
+                   reaction_importance=None):
     """DRG reduction of the network of a solve: keeps the species reachable from `targets` (names or 0-based ids) over the
     edges with coefficient >= eps - the species non-zero in the first saved state always count as targets - and the
     reactions ALL of whose species, on both sides, are kept. `coef`: (rowptr, colidx, coef) of an earlier drg_coefficients
@@ -1150,7 +1197,14 @@ def reduce_network(out, calculator, targets, eps, pairing=True, coef=None, metho
     else computed here. The reaction rule and the splicing are the same; the result carries `importance` and no graph.
 
     method="pfa" is the DRG form on the path-flux-analysis graph: `coef` is (rowptr, colidx, coef) of pfa_coefficients, else
-    computed here, and the selection is drg_select's on it."""
+    computed here, and the selection is drg_select's on it.
+
+    reaction_eps (None: nothing below happens) adds reaction elimination as a second step: of the reactions the species rule
+    keeps, only those with importance >= reaction_eps stay, the importance being that of the FULL network judged by the kept
+    species (the function reaction_importance with species = the kept species and the same pairing); the argument
+    `reaction_importance`: that vector from an earlier call, one entry per reaction of out.rd, used as it is. No species is
+    dropped in this step: a kept species that loses all its reactions stays as an inert entry, so map_u0 and the numbering mean
+    what they meant. The result carries reaction_eps and the vector."""
     if method not in ("drg", "drgep", "pfa"):
         raise ValueError('method must be "drg", "drgep" or "pfa"')
     sd, rd = out.sd, out.rd
@@ -1170,12 +1224,24 @@ def reduce_network(out, calculator, targets, eps, pairing=True, coef=None, metho
         kept_sp = drg_select(rowptr, colidx, cf, tg, eps)
     sd_new, new_id = sd.subset(kept_sp + 1)
     rd_new, kept_rx = rd.subset_species(new_id)
-    kill = np.setdiff1d(np.arange(rd.nr), np.asarray(kept_rx, dtype=np.int64))
+    kept_rx = np.asarray(kept_rx, dtype=np.int64)
+    rx_imp = None
+    if reaction_eps is not None:
+        rx_imp = np.asarray(_reaction_importance(out, calculator, kept_sp, pairing) if reaction_importance is None
+                            else reaction_importance, dtype=float)
+        if rx_imp.shape != (rd.nr,):
+            raise ValueError("reaction_importance must have one entry per reaction of the full network")
+        strong = reaction_select(rx_imp, reaction_eps, kept_rx)
+        rd_new.splice(np.flatnonzero(~np.isin(kept_rx, strong)))
+        kept_rx = strong
+    kill = np.setdiff1d(np.arange(rd.nr), kept_rx)
     calc = copy.deepcopy(calculator)
     if len(kill):
         calc.splice(kill)
-    return DRGReduction(kept_sp, np.asarray(kept_rx, dtype=np.int64), sd_new, rd_new, calc, np.asarray(rowptr), np.asarray(colidx),
-                        np.asarray(cf), tg, float(eps), imp)
+    red = DRGReduction(kept_sp, kept_rx, sd_new, rd_new, calc, np.asarray(rowptr), np.asarray(colidx), np.asarray(cf), tg, float(eps), imp)
+    if reaction_eps is not None:
+        red.reaction_eps, red.reaction_importance = float(reaction_eps), rx_imp
+    return red
 
 
 # ---- timescale analysis (EXTENSION: species lifetimes, quasi-steady-state error and stiffness along a solve) ---------------

@@ -1,0 +1,334 @@
+"""GPU tests of the reaction-importance pass (kin_reaction_importance_batched and its device, solution and ensemble forms)
+against the NumPy reference of reaction_importance_cases.py (oracle rates, math.fsum for every denominator). The bound per
+(reaction, state) is derived there, not measured; where the denominator is pure cancellation it is vacuous, and the tests
+check that at most 1 % of the entries they compare have a bound above 1e-9 (test_reaction_importance_host.py repeats that on
+the CPU)."""
+import numpy as np
+import pytest
+
+import drg_cases as dc
+import reaction_importance_cases as rc
+from kinetica_jl_amd import capi
+
+pytestmark = pytest.mark.gpu
+
+_handles = {}
+
+
+def handle(name):
+    if name not in _handles:
+        _handles[name] = capi.HipNetwork.from_flat(dc.synth_case(name).net)
+    return _handles[name]
+
+
+def device(name, mode, pairing, B, importance=None, lo=0, species=None, per_state=False):
+    """reaction_importance_batched of states lo .. B - 1 of a synthetic case."""
+    case, h = dc.synth_case(name), handle(name)
+    if mode == "shared":
+        h.set_rates(case.k0)
+    elif mode.startswith("T"):
+        h.set_arrhenius(case.Ea, case.A, k_max=1e12 if mode == "T_kmax" else None)
+    src = {k: (v[lo:] if k != "k" or mode == "per_state" else v) for k, v in case.source(mode, B).items()}
+    return h.reaction_importance_batched(case.U[lo:B], species=species, pairing=pairing, importance=importance, per_state=per_state, **src)
+
+
+def check(name, mode, pairing, B, got, per_state=None, species=None):
+    case = dc.synth_case(name)
+    ref, bound, I, bounds = rc.ref_of(name, pairing).importance(rc.case_rates(name, mode, B), case.ex(mode, B), species)
+    frac = float(np.mean(bounds > 1e-9))
+    err = np.abs(got - ref)
+    print(f"{name} {mode} pairing={pairing} B={B}: reactions {len(ref)}, max err {err.max():.3e}, max err/bound "
+          f"{np.max(err / np.maximum(bound, 1e-300)):.3f}, {100 * frac:.3f} % of the bounds above 1e-9")
+    assert frac <= 0.01
+    assert np.all(np.isfinite(got)) and np.all(got >= 0.0) and np.all(got <= 1.0)
+    assert np.all(err <= bound)
+    if per_state is not None:
+        assert per_state.shape == I.shape
+        assert np.all(per_state >= 0.0) and np.all(per_state <= 1.0)
+        assert np.all(np.abs(per_state - I) <= bounds)
+        assert np.array_equal(got, per_state.max(axis=0))       # the maximum over the states is exact
+
+
+def pair_members_agree(net, pairing, imp):
+    partner = capi.reaction_importance_plan_host(net, pairing)[0]
+    r = np.flatnonzero(partner >= 0)
+    assert np.array_equal(imp[r], imp[partner[r]])
+    return len(r)
+
+
+@pytest.mark.parametrize("pairing", [1, 0])
+@pytest.mark.parametrize("name", sorted(rc.HAND))
+def test_hand_networks(name, pairing):
+    net, k, U, _ = dc.hand_networks()[name]
+    h = capi.HipNetwork.from_flat(net)
+    h.set_rates(k)
+    for species, want in rc.HAND[name]:
+        imp, I = h.reaction_importance_batched(U, species=species, pairing=pairing, per_state=True)
+        assert imp.tolist() == want[pairing]                             # dyadic inputs: exact
+        assert I[0].tolist() == want[pairing] and I[-1].tolist() == [0.0] * net.n_reactions
+        assert h.reaction_importance_batched(U[:-1], species=species, pairing=pairing).tolist() == want[pairing]   # the zero state changes nothing
+        zero = h.reaction_importance_batched(np.zeros((1, net.n_species)), species=species, pairing=pairing)
+        assert zero.tolist() == [0.0] * net.n_reactions                  # den = 0 everywhere: exactly 0.0, never NaN
+    h.close()
+
+
+def hub_with_products(n_long=300, n_mid=20):
+    """hub_network with a product of its own per long reaction, A + X_i -> P_i + X_i: A's denominator row stays long, C's and
+    D's medium, and every P_i has that one record - the reaction is P_i's only one."""
+    from kinetica_jl_amd.synth import from_lists
+    n = 4 + n_long
+    reacs = [[(0, 1), (4 + i, 1)] for i in range(n_long)] + [[(2, 1), (4 + i, 1)] for i in range(n_mid)]
+    prods = [[(n + i, 1), (4 + i, 1)] for i in range(n_long)] + [[(3, 1), (4 + i, 1)] for i in range(n_mid)]
+    return from_lists(n + n_long, reacs, prods)
+
+
+@pytest.mark.parametrize("pairing", [1, 0])
+@pytest.mark.parametrize("variant", ["hub", "hub_with_products"])
+def test_hub_network_long_and_medium_rows(variant, pairing):
+    """hub_network(300, 20): A and B have 300 records each, C and D 20, and the colliders X_i have zero net coefficient, so the
+    hub itself has no species with a single record; the variant gives every long reaction one."""
+    from oracle import oracle as orc
+    net = dc.hub_network(300, 20) if variant == "hub" else hub_with_products(300, 20)
+    rng = np.random.default_rng(4)
+    B = 7
+    U = dc.states(net.n_species, B, seed=3)
+    K = 10.0 ** rng.uniform(-2, 2, (B, net.n_reactions))
+    on = orc.OracleNetwork.from_flat(net)
+    ref = rc.RiRef(net, pairing)
+    info = ref.graph.info()
+    assert info["den_long"] == (2 if variant == "hub" else 1) and info["den_medium"] >= 2
+    rates = np.stack([on.rates(K[b], U[b]) for b in range(B)])
+    want, bound, I, bounds = ref.importance(rates)
+    h = capi.HipNetwork.from_flat(net)
+    got, ps = h.reaction_importance_batched(U, k=K, pairing=pairing, per_state=True)
+    h.close()
+    assert np.all(np.abs(got - want) <= bound) and np.all(np.abs(ps - I) <= bounds)
+    assert np.all(got >= 0.0) and np.all(got <= 1.0) and np.array_equal(got, ps.max(axis=0))
+    assert np.all(got[300:] > 0.0)           # the medium rows: twenty records share C's and D's turnover
+    # every reaction that is a species' only record: exactly 1.0 in every state in which it runs at all
+    single = from_single_record_species(net, pairing)
+    assert sorted(single) == ([] if variant == "hub" else list(range(300)))
+    for r in single:
+        assert np.array_equal(ps[:, r], np.where(rates[:, r] != 0, 1.0, 0.0))
+        assert got[r] == 1.0
+
+
+def from_single_record_species(net, pairing):
+    """Reactions that are the only record of some species they change."""
+    ref = rc.RiRef(net, pairing)
+    count = np.bincount(ref.ent[:, 1], minlength=net.n_species)
+    recs = set(int(i) for i, A in zip(ref.ent[:, 0], ref.ent[:, 1]) if count[A] == 1)
+    return [r for r in range(net.n_reactions) if int(ref.rec_of[r]) in recs]
+
+
+@pytest.mark.parametrize("pairing", [1, 0])
+@pytest.mark.parametrize("B", [1, 7, 130])
+def test_300x1500_matches_reference_state_by_state(B, pairing):
+    got, ps = device("300x1500", "per_state", pairing, B, per_state=True)
+    check("300x1500", "per_state", pairing, B, got, ps)
+    n = pair_members_agree(dc.synth_case("300x1500").net, pairing, got)
+    assert (n > 0) == bool(pairing)
+    # a record that is a species' only record: exactly 1.0 wherever it progresses at all
+    rates = rc.case_rates("300x1500", "per_state", B)
+    ref = rc.ref_of("300x1500", pairing)
+    for r in from_single_record_species(ref.net, pairing):
+        qr = rates[:, ref.partner[r]] if ref.partner[r] >= 0 else np.zeros(B)
+        clear = np.abs(rates[:, r] - qr) > 1e-6 * (np.abs(rates[:, r]) + np.abs(qr))      # (no cancellation: the device's w is non-zero too)
+        assert np.all(ps[clear, r] == 1.0)
+
+
+@pytest.mark.parametrize("pairing", [1, 0])
+@pytest.mark.parametrize("mode", dc.MODES)
+def test_every_rate_constant_source(mode, pairing):
+    got, ps = device("300x1500", mode, pairing, 7, per_state=True)
+    check("300x1500", mode, pairing, 7, got, ps)
+
+
+@pytest.mark.parametrize("pairing", [1, 0])
+@pytest.mark.parametrize("mode", ["per_state", "T_kmax"])
+def test_post_cutoff_odd_reaction_count(mode, pairing):
+    case = dc.synth_case("300x1500_cut")
+    assert case.net.n_reactions % 2 == 1
+    got, ps = device("300x1500_cut", mode, pairing, 7, per_state=True)
+    check("300x1500_cut", mode, pairing, 7, got, ps)
+    if pairing:
+        partner = capi.reaction_importance_plan_host(case.net, 1)[0]
+        assert np.any(partner < 0) and np.any(partner >= 0)
+        pair_members_agree(case.net, 1, got)
+
+
+@pytest.mark.parametrize("pairing", [1, 0])
+def test_species_list_restricts_the_judging_species(pairing):
+    import torch
+    case, h, B = dc.synth_case("300x1500"), handle("300x1500"), 7
+    n = case.net.n_species
+    rng = np.random.default_rng(8)
+    third = rng.choice(n, n // 3, replace=False)
+    species = np.concatenate([third, third[:17], third[:3]])          # duplicates
+    rng.shuffle(species)
+    got, ps = device("300x1500", "per_state", pairing, B, species=species, per_state=True)
+    check("300x1500", "per_state", pairing, B, got, ps, species=species)
+    everything = device("300x1500", "per_state", pairing, B)
+    assert np.all(got <= everything) and np.any(got < everything)
+    assert np.array_equal(device("300x1500", "per_state", pairing, B, species=np.unique(species)), got)
+    assert np.array_equal(device("300x1500", "per_state", pairing, B, species=np.arange(n)), everything)
+    # reactions that change no listed species: exactly 0.0
+    ref = rc.ref_of("300x1500", pairing)
+    inside = np.zeros(n, bool); inside[species] = True
+    untouched = [r for r in range(ref.R) if not any(inside[s] for s in ref.slots[r])]
+    assert len(untouched) > 0 and np.all(got[untouched] == 0.0)
+    # the device entry passes ids outside [0, N) over
+    dev = "cuda:0"
+    junk = np.concatenate([species, [-1, n, 10 ** 12, -(10 ** 12)]]).astype(np.int64)
+    d_u, d_k = (torch.tensor(x, dtype=torch.float64, device=dev) for x in (case.U[:B], case.K[:B]))
+    d_s = torch.tensor(junk, dtype=torch.int64, device=dev)
+    d_i = torch.full((ref.R,), float("nan"), dtype=torch.float64, device=dev)
+    torch.cuda.synchronize()
+    h.reaction_importance_batched_dev(B, d_u.data_ptr(), d_i.data_ptr(), d_species=d_s.data_ptr(), n_sel=len(junk), d_k=d_k.data_ptr(),
+                                      pairing=pairing, stream=torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    assert np.array_equal(d_i.cpu().numpy(), got)
+
+
+@pytest.mark.parametrize("mode", ["per_state", "k_row", "T"])
+@pytest.mark.parametrize("pairing", [1, 0])
+def test_maximum_crosses_blocks_of_three_states(mode, pairing, monkeypatch):
+    whole, ps_whole = device("300x1500", mode, pairing, 7, per_state=True)
+    monkeypatch.setenv("KIN_DRG_BLOCK_STATES", "3")
+    blocks, ps_blocks = device("300x1500", mode, pairing, 7, per_state=True)
+    check("300x1500", mode, pairing, 7, blocks, ps_blocks)
+    assert np.array_equal(blocks, whole) and np.array_equal(ps_blocks, ps_whole)
+
+
+@pytest.mark.parametrize("pairing", [1, 0])
+def test_accumulate_folds_two_halves_bit_for_bit(pairing):
+    whole = device("300x1500", "per_state", pairing, 130)
+    first = device("300x1500", "per_state", pairing, 60)
+    both = device("300x1500", "per_state", pairing, 130, importance=first, lo=60)
+    assert np.array_equal(both, whole)
+    assert np.array_equal(device("300x1500", "per_state", pairing, 130), whole)       # two identical calls
+    # accumulating over no states leaves importance alone; without accumulation no states give zeros
+    h, n = handle("300x1500"), dc.synth_case("300x1500").net.n_species
+    assert np.array_equal(h.reaction_importance_batched(np.empty((0, n)), k=np.empty((0, 1500)), pairing=pairing, importance=whole), whole)
+    assert np.all(h.reaction_importance_batched(np.empty((0, n)), k=np.empty((0, 1500)), pairing=pairing) == 0.0)
+    # values above every quotient survive
+    big = np.full(len(whole), 2.0)
+    assert np.array_equal(device("300x1500", "per_state", pairing, 7, importance=big), big)
+
+
+@pytest.mark.parametrize("pairing", [1, 0])
+def test_device_pointers_equal_host_arrays(pairing):
+    import torch
+    case, h, B = dc.synth_case("300x1500"), handle("300x1500"), 130
+    want = device("300x1500", "per_state", pairing, B)
+    dev = "cuda:0"
+    d_u, d_k = (torch.tensor(x, dtype=torch.float64, device=dev) for x in (case.U[:B], case.K[:B]))
+    d_i = torch.full((len(want),), float("nan"), dtype=torch.float64, device=dev)
+    torch.cuda.synchronize()      # torch's fills run on torch's stream, the library on the handle's own
+    stream = torch.cuda.current_stream().cuda_stream
+    h.reaction_importance_batched_dev(B, d_u.data_ptr(), d_i.data_ptr(), d_k=d_k.data_ptr(), pairing=pairing, stream=stream)
+    torch.cuda.synchronize()
+    assert np.array_equal(d_i.cpu().numpy(), want)
+    h.reaction_importance_batched_dev(3, d_u.data_ptr(), d_i.data_ptr(), d_k=d_k.data_ptr(), pairing=pairing, accumulate=True, stream=stream)
+    torch.cuda.synchronize()
+    assert np.array_equal(d_i.cpu().numpy(), want)
+
+
+def _pars(t1, chunks):
+    return capi.KinParams(tspan0=0.0, tspan1=t1, abstol=1e-10, reltol=1e-8, adaptive_tols=1, update_tols=0, solve_chunks=1 if chunks else 0,
+                          ban_negatives=0, solve_chunkstep=t1 / max(chunks, 1), maxiters=100000, save_interval=-1.0)
+
+
+@pytest.mark.parametrize("pairing", [1, 0])
+def test_solution_and_ensemble_forms_equal_the_batched_call(pairing):
+    net, Ea, A = dc.synth(300, 1500)
+    case = dc.synth_case("300x1500")
+    h = capi.HipNetwork.from_flat(net)
+    u0 = np.zeros(300); u0[0] = 1.0
+    h.set_rates(case.k0)
+    t, us, rcode, st, status = h.solve(_pars(2e-3, 2), u0)
+    assert rcode == 0 and len(t) >= 3
+    species = np.arange(0, 300, 3)
+    for sp in (None, species):
+        want = h.reaction_importance_batched(us, species=sp, pairing=pairing)
+        assert np.any(want > 0)
+        assert np.array_equal(h.solution_reaction_importance(species=sp, pairing=pairing), want)
+        krow = np.zeros(len(t), np.int64)
+        assert np.array_equal(h.solution_reaction_importance(species=sp, k=case.k0[None, :], k_row=krow, pairing=pairing), want)
+        assert np.array_equal(h.solution_reaction_importance(species=sp, pairing=pairing, importance=want), want)
+    # an ensemble of three members with their own rate constants; rows past n_saved are zeros and take no part
+    K = 3
+    k = case.K[:K]
+    u0s = np.repeat(u0[None, :], K, axis=0)
+    res = h.solve_ensemble(_pars(2e-3, 2), u0s, k=k)
+    Ke, rows, n, n_saved = h.ensemble_size()
+    assert Ke == K and np.all(n_saved >= 2)
+    us_e = np.asarray(res[1]).reshape(K, -1, n)
+    k_row = np.repeat(np.arange(K, dtype=np.int64)[:, None], rows, axis=1)
+    k_row_junk = k_row.copy()
+    for m in range(K):
+        k_row_junk[m, n_saved[m]:] = 10 ** 9          # keys of rows that do not exist are ignored
+    flat = np.concatenate([us_e[m, :n_saved[m]] for m in range(K)])
+    flat_row = np.concatenate([np.full(n_saved[m], m, np.int64) for m in range(K)])
+    for sp in (None, species):
+        got = h.ensemble_reaction_importance(species=sp, k=k, k_row=k_row_junk, pairing=pairing)
+        assert np.array_equal(got, h.reaction_importance_batched(flat, species=sp, k=k, k_row=flat_row, pairing=pairing))
+    with pytest.raises(capi.KineticaHipError) as e:
+        k_row_bad = k_row.copy(); k_row_bad[1, 0] = K
+        h.ensemble_reaction_importance(k=k, k_row=k_row_bad, pairing=pairing)
+    assert e.value.code == capi.KIN_ERR_INVALID_ARG
+    h.close()
+
+
+def test_error_statuses():
+    from kinetica_jl_amd.synth import synthetic_crn
+    net, Ea, A = synthetic_crn(50, 200, seed=3)
+    h = capi.HipNetwork.from_flat(net)
+    U = np.ones((4, 50)); K = np.ones((4, 200)); T = np.full(4, 800.0)
+
+    def code(fn):
+        with pytest.raises(capi.KineticaHipError) as e:
+            fn()
+        return e.value.code
+
+    INV, STATE, UNS = capi.KIN_ERR_INVALID_ARG, capi.KIN_ERR_STATE, capi.KIN_ERR_UNSUPPORTED
+    ri = h.reaction_importance_batched
+    assert code(lambda: ri(U)) == STATE                                                    # no rates at all
+    assert code(lambda: ri(U, T=T)) == STATE                                               # T without Arrhenius parameters
+    assert code(lambda: h.solution_reaction_importance(k=K[:1], k_row=np.zeros(0, np.int64))) == STATE    # no stored solution
+    assert code(lambda: h.ensemble_reaction_importance()) == STATE                         # no stored ensemble
+    h.set_arrhenius(Ea, A)
+    assert code(lambda: ri(U, k=K, T=T)) == INV                                            # both k and T
+    assert code(lambda: ri(U, k_row=np.zeros(4, np.int64))) == INV                         # k_row without a k source
+    assert code(lambda: ri(U, k=K, k_row=np.array([0, 1, 4, 2]))) == INV                   # row index out of range
+    assert code(lambda: ri(U, k=K[:3])) == INV                                             # k_row == NULL needs n_k_rows == B
+    assert code(lambda: ri(U, k=K, species=[])) == INV                                     # an empty species list
+    assert code(lambda: ri(U, k=K, species=[0, 50])) == INV                                # species out of range
+    assert code(lambda: ri(U, k=K, species=[-1])) == INV
+    assert ri(U, k=K, species=[0, 49, 49]).shape == (200,)
+    L = capi.lib()
+    sp = np.zeros(1, np.int64)
+    assert L.kin_reaction_importance_batched(h.handle, 1, 4, capi._pd(U), capi._pd(K), 4, None, None, None, 0, 0, 0, None, None) == INV   # null output
+    assert L.kin_reaction_importance_batched_dev(h.handle, 1, -1, None, None, None, None, None, 0, 0, None, None) == INV           # B < 0
+    out = np.zeros(200)
+    assert L.kin_reaction_importance_batched(h.handle, 1, 4, capi._pd(U), capi._pd(K), 4, None, None, capi._p64(sp), 0, 0, 0,
+                                             capi._pd(out), None) == INV                                                          # a list with n < 1
+    assert L.kin_reaction_importance_batched(h.handle, 1, 4, capi._pd(U), capi._pd(K), 4, None, None, capi._p64(sp + 1), 1, 1, 0,
+                                             capi._pd(out), None) == capi.KIN_OK                                                  # index_base 1
+    assert np.array_equal(out, ri(U, k=K, species=[0]))
+    h.close()
+    # pairing on a network without pair records (n_species >= 65535); without pairing the same network is served
+    n = 65535
+    from kinetica_jl_amd.synth import from_lists
+    big = from_lists(n, [[(0, 1)], [(1, 1)], [(n - 1, 1)]], [[(1, 1)], [(0, 1)], [(0, 1)]])
+    hb = capi.HipNetwork.from_flat(big)
+    Ub = np.zeros((2, n)); Ub[0, 0] = 0.5; Ub[0, 1] = 0.25; Ub[1, n - 1] = 1.0
+    kb = np.array([[2.0, 4.0, 1.0]])
+    rows = np.zeros(2, np.int64)
+    assert code(lambda: hb.reaction_importance_batched(Ub, k=kb, k_row=rows, pairing=1)) == UNS
+    with pytest.raises(capi.KineticaHipError) as e:
+        capi.reaction_importance_plan_host(big, 1)
+    assert e.value.code == UNS
+    # unpaired: state 0 has q = (1, 1, 0): den_0 = den_1 = 2; state 1 has q = (0, 0, 1): den_0 = den_{n-1} = 1
+    assert hb.reaction_importance_batched(Ub, k=kb, k_row=rows, pairing=0).tolist() == [0.5, 0.5, 1.0]
+    hb.close()

@@ -99,6 +99,22 @@ int kin_rhs_batched(kin_network* h, int64_t B, const double* u, const double* k,
  * stream of its own: work the caller has queued on OTHER streams (fills, arithmetic on these buffers) is not ordered
  * before the sweep - pass the stream that work runs on, or synchronise first. The same holds for every *_dev entry point. */
 int kin_rhs_batched_dev(kin_network* h, int64_t B, const double* d_u, const double* d_k, double* d_du, void* stream);
+/* Which kernel instantiation and launch configuration kin_rhs_batched_dev takes for these buffers (nothing is launched, the
+ * pointers are only inspected for their 16-byte alignment; d_k == NULL: the handle's own rate constants), and the same
+ * without a device or a handle from the flat network lists (kin_network_create's), the compute units n_cu of a device
+ * (kin_network_compute_units) and the low four address bits of u, of the rate constants in effect and of du.
+ * info[KIN_SWEEP_PLAN_INFO]: kernel (0 register-resident records, 1 general, 2 coefficient records in LDS, 3 large-N hub /
+ * tail, 4 the single-state kernels state after state: N >= 65535), workgroup size, register-resident record rows TR, record
+ * rows per batch ILP, 1 if the block pairing (p, P + p) is read, 1 if rate constants travel as adjacent 16-byte pairs, 1 if
+ * the state is staged in LDS, streamed batches of ILP rows n_a, of ILP + 1 rows n_b, grid, workgroups per compute unit,
+ * split-accumulator entries, explicit-operand records, tail tiles, 1 if tail operands are addressed by species, dynamic LDS
+ * bytes, species tiles, hubs, records (a reaction with its reverse, or a single reaction). Entries a kernel does not have are 0.
+ * Added under KIN_ABI_VERSION 6: look the symbols up before calling them. */
+#define KIN_SWEEP_PLAN_INFO 19
+int kin_sweep_plan(kin_network* h, int64_t B, const double* d_u, const double* d_k, const double* d_du, int64_t* info);
+int kin_sweep_plan_host(int64_t n_species, int64_t n_reactions, const int64_t* reac_ptr, const int64_t* reac_idx,
+                        const int64_t* reac_sto, const int64_t* prod_ptr, const int64_t* prod_idx, const int64_t* prod_sto,
+                        int index_base, int n_cu, int64_t B, int u_bits, int k_bits, int du_bits, int64_t* info);
 
 /* ---- A2 in the library's own data layout ("library order"): the bandwidth path of the batched sweep --------------
  * The reference evaluates its RHS one state at a time inside the integrator; the batched sweep (ensembles, flux
@@ -129,6 +145,18 @@ int kin_lib_layout_host(int64_t n_species, int64_t n_reactions, const int64_t* r
                         int index_base, int hubs, int64_t* info, int64_t* species_of_lib, int64_t* slot_of_reaction,
                         uint64_t* rec, int32_t* rowtab, int32_t* seg_q, int32_t* win_off, int32_t* win_cnt, int32_t* copy_src,
                         int32_t* seg_k);
+/* Which instantiation of the tiled sweep a call over B states takes (temperature_form != 0: rate constants formed in the
+ * sweep; else the k stream), on the handle's device or - host variant, no device - on one of n_cu compute units.
+ * info[KIN_TILED_PLAN_INFO]: workgroup size, 1 for the temperature form, staged doubles per thread UN (5 / 10), 1 for the
+ * one-slot-record form SINGLES, record rows per batch NB, grid, workgroups per compute unit, dynamic LDS bytes, 1 if the
+ * library species order is the caller's, windows, split-accumulator entries, 1 if some window ends in one-slot records.
+ * The layout switches KIN_TILED_ENTRIES / KIN_TILED_SINGLES of the calling process are honoured, as when a handle builds
+ * its layout. Added under KIN_ABI_VERSION 6: look the symbols up before calling them. */
+#define KIN_TILED_PLAN_INFO 12
+int kin_tiled_sweep_plan(kin_network* h, int64_t B, int temperature_form, int64_t* info);
+int kin_tiled_sweep_plan_host(int64_t n_species, int64_t n_reactions, const int64_t* reac_ptr, const int64_t* reac_idx,
+                              const int64_t* reac_sto, const int64_t* prod_ptr, const int64_t* prod_idx, const int64_t* prod_sto,
+                              int index_base, int n_cu, int64_t B, int temperature_form, int64_t* info);
 /* Symbolic analysis of the Newton-matrix factorisation (I - c J; the reference's solver does this inside KLU,
  * docs/src/getting-started.md:69) WITHOUT a device: sizes only. Arguments <= 0 take the library's defaults.
  * info[0..11] = sparse pivots, dense block dimension, elimination rounds, nnz(U), nnz(L11^-1), nnz(U11^-1), nnz(L21 L11^-1),

@@ -42,6 +42,7 @@ SYMBOLS = [
     "kin_jac_batched", "kin_jac_batched_dev", "kin_timescale_batched", "kin_timescale_batched_dev", "kin_solution_timescale",
     "kin_ensemble_timescale", "kin_timescale_plan_host",
     "kin_flux_plan_host", "kin_network_compute_units",
+    "kin_sweep_plan", "kin_sweep_plan_host", "kin_tiled_sweep_plan", "kin_tiled_sweep_plan_host",
 ]
 # in-degree classes of the DRGEP path search (drg.hpp: IN_SHORT_MAX, IN_WAVE_MAX): a lane, a wavefront, the workgroup
 DRGEP_IN_SHORT_MAX, DRGEP_IN_WAVE_MAX = 32, 256
@@ -207,6 +208,11 @@ def lib():
             L.kin_solution_timescale.argtypes = [c_void_p, PD, c_int64, P64, PD, c_int64, c_int, PD, PD]
             L.kin_ensemble_timescale.argtypes = [c_void_p, PD, c_int64, P64, PD, c_int64, c_int, PD, PD]
             L.kin_timescale_plan_host.argtypes = [c_int64, c_int64] + [P64] * 6 + [c_int, P64]
+        if hasattr(L, "kin_sweep_plan"):   # (also under ABI 6: the plan queries of the two batched sweeps)
+            L.kin_sweep_plan.argtypes = [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, P64]
+            L.kin_sweep_plan_host.argtypes = [c_int64, c_int64] + [P64] * 6 + [c_int, c_int, c_int64, c_int, c_int, c_int, P64]
+            L.kin_tiled_sweep_plan.argtypes = [c_void_p, c_int64, c_int, P64]
+            L.kin_tiled_sweep_plan_host.argtypes = [c_int64, c_int64] + [P64] * 6 + [c_int, c_int, c_int64, c_int, P64]
         L.kin_solve_ensemble.argtypes = [c_void_p, POINTER(KinParams), c_int64, PD, PD, PD, PD, PD, PD, c_int64, P64, PD, PD, P64,
                                          POINTER(c_int32), POINTER(KinStats)]
         L.kin_integrator_init.argtypes = [c_void_p, POINTER(KinParams), PD, PD, PD, PD, c_int64]
@@ -396,6 +402,50 @@ def flux_plan_host(n_species, n_reactions, B, n_cu, temperature_form=False, segm
     return {k: int(v) for k, v in zip(FLUX_PLAN_INFO, info)}
 
 
+SWEEP_PLAN_INFO = ("kernel", "BS", "TR", "ILP", "BLK", "ADJ", "U_IN_LDS", "n_a", "n_b", "grid", "per_cu", "n_copy", "n_expl",
+                   "tail_tiles", "tail_by_species", "lds_bytes", "n_tiles", "hubs", "records")
+SWEEP_KERNELS = ("reg", "gen", "lds", "big", "per_state")      # sweep_plan.hpp: SweepKernel
+TILED_PLAN_INFO = ("BS", "TMODE", "UN", "SINGLES", "NB", "grid", "per_cu", "lds_bytes", "identity", "windows", "n_copy",
+                   "has_singles")
+
+
+def _plan_dict(names, info):
+    d = {k: int(v) for k, v in zip(names, info)}
+    if "kernel" in d:
+        d["kernel"] = SWEEP_KERNELS[d["kernel"]]
+    return d
+
+
+def _net_lists(net):
+    return [np.ascontiguousarray(a, dtype=np.int64) for a in (net.reac_ptr, net.reac_idx, net.reac_sto, net.prod_ptr,
+                                                              net.prod_idx, net.prod_sto)]
+
+
+def sweep_plan_host(net, n_cu, B, u_bits=0, k_bits=0, du_bits=0):
+    """kin_sweep_plan_host (no device, no handle): a dict of the SWEEP_PLAN_INFO values - the kernel instantiation and launch
+    configuration kin_rhs_batched_dev takes for a FlatNetwork on a device of n_cu compute units; u_bits / k_bits / du_bits are
+    the low four address bits of the buffers."""
+    arrs = _net_lists(net)
+    info = np.zeros(len(SWEEP_PLAN_INFO), np.int64)
+    st = lib().kin_sweep_plan_host(int(net.n_species), int(net.n_reactions), *[_p64(a) for a in arrs], 0, int(n_cu), int(B),
+                                   int(u_bits), int(k_bits), int(du_bits), _p64(info))
+    if st != KIN_OK:
+        raise KineticaHipError(st, "sweep plan query: " + lib().kin_last_error(None).decode())
+    return _plan_dict(SWEEP_PLAN_INFO, info)
+
+
+def tiled_sweep_plan_host(net, n_cu, B, temperature_form=False):
+    """kin_tiled_sweep_plan_host (no device, no handle): a dict of the TILED_PLAN_INFO values for a FlatNetwork (under the
+    caller's KIN_TILED_ENTRIES / KIN_TILED_SINGLES, as a handle would build the layout)."""
+    arrs = _net_lists(net)
+    info = np.zeros(len(TILED_PLAN_INFO), np.int64)
+    st = lib().kin_tiled_sweep_plan_host(int(net.n_species), int(net.n_reactions), *[_p64(a) for a in arrs], 0, int(n_cu), int(B),
+                                         int(bool(temperature_form)), _p64(info))
+    if st != KIN_OK:
+        raise KineticaHipError(st, "network has no tiled layout")
+    return _plan_dict(TILED_PLAN_INFO, info)
+
+
 def arrhenius_eval(Ea, A, T, k_max=None, t_mult=1.0):
     """calculator(; T) on the device without a network handle."""
     Ea, A = _f64(Ea), _f64(A)
@@ -498,6 +548,18 @@ class HipNetwork:
         """Device pointers (ints), state-major u[b][N], k[b][R] or 0, du[b][N]; only enqueues."""
         self._chk(lib().kin_rhs_batched_dev(self._h, int(B), c_void_p(d_u), c_void_p(d_k) if d_k else None,
                                             c_void_p(d_du), c_void_p(stream) if stream else None))
+
+    def sweep_plan(self, B, d_u, d_k, d_du):
+        """kin_sweep_plan: what rhs_batched_dev launches for these device pointers (ints; d_k 0: the handle's rates)."""
+        info = np.zeros(len(SWEEP_PLAN_INFO), np.int64)
+        self._chk(lib().kin_sweep_plan(self._h, int(B), c_void_p(d_u), c_void_p(d_k) if d_k else None, c_void_p(d_du), _p64(info)))
+        return _plan_dict(SWEEP_PLAN_INFO, info)
+
+    def tiled_sweep_plan(self, B, temperature_form=False):
+        """kin_tiled_sweep_plan: the tiled sweep's instantiation and grid for B states on this handle's device."""
+        info = np.zeros(len(TILED_PLAN_INFO), np.int64)
+        self._chk(lib().kin_tiled_sweep_plan(self._h, int(B), int(bool(temperature_form)), _p64(info)))
+        return _plan_dict(TILED_PLAN_INFO, info)
 
     # --- reaction fluxes ---------------------------------------------------------------------
     def _flux_inputs(self, B, k, k_row, T, w):

@@ -34,24 +34,27 @@ void kin_network::rhs_dev(const double* d_u, double* d_du) {
   launch_segsum(rhs_plan.view(), SEG_COEF_SET, rate.p, d_du, SegExtra{}, stream);
 }
 
+SweepPlan kin_network::sweep_plan_dev(int64_t B, const double* d_u, const double* d_k, const double* d_du) const {
+  const auto bits = [](const void* p) { return (unsigned)(reinterpret_cast<uintptr_t>(p) & 15); };
+  return sweep_plan(sweep_net_info(host), n_cu, B, SweepAlign{bits(d_u), bits(d_k ? d_k : k.p), bits(d_du)});
+}
+
 void kin_network::sweep_dev(int64_t B, const double* d_u, const double* d_k, double* d_du, hipStream_t s) {
   if (!d_k) flush_pending_T(s);   // the handle's own k is about to be read: a temperature still pending is formed first
-  if (host.N >= 65535) {
-    // the packed sweep records hold species ids in 16 bits; wider networks take the single-state kernels
-    // (32-bit ids) state after state on the same stream - correct at any size, one state per launch pair
+  const SweepPlan plan = sweep_plan_dev(B, d_u, d_k, d_du);
+  if (plan.kernel == SWEEP_PER_STATE) {
+    // (sweep_plan.hpp: species ids beyond 16 bits) the single-state kernels, state after state on the same stream
     for (int64_t b = 0; b < B; b++) {
       launch_rates(host.R, d_k ? d_k + b * host.R : k.p, d_u + b * host.N, x0.p, x1.p, rate.p, s);
       launch_segsum(rhs_plan.view(), SEG_COEF_SET, rate.p, d_du + b * host.N, SegExtra{}, s);
     }
-  } else if (host.big_H > 0) {
-    big_scratch.alloc((size_t)std::min<int64_t>(B, n_cu) * (size_t)(host.N - host.big_H + host.n_pairs()));
-    launch_sweep_big(n_cu, host.N, host.R, host.n_pairs(), B, host.pairs_adjacent, host.big_H, (int32_t)host.big_tail_ptr.size() - 1,
-                     big_rec8.p, big_rec.p, big_expl.p, (int32_t)host.big_expl.size(), sweep_k.p, big_spec.p, big_tptr.p, big_tent.p,
-                     big_scratch.p, d_u, d_k, k.p, d_du, host.big_tail_by_species, s);
+  } else if (plan.kernel == SWEEP_BIG) {
+    big_scratch.alloc((size_t)plan.grid * (size_t)(host.N - host.big_H + host.n_pairs()));
+    launch_sweep_big(plan, host.N, host.R, host.n_pairs(), B, big_rec8.p, big_rec.p, big_expl.p, sweep_k.p, big_spec.p, big_tptr.p,
+                     big_tent.p, big_scratch.p, d_u, d_k, k.p, d_du, s);
   } else
-    launch_sweep(n_cu, host.N, host.R, host.n_pairs(), B, host.pairs_adjacent, host.pairs_block, sweep_rec.p, sweep_k.p,
-                 host.pair_rec64.empty() ? nullptr : sweep_rec64.p, sweep_copy.p, (int)host.sweep_copy_species.size(),
-                 host.gen_rec8.empty() ? nullptr : gen_rec8.p, gen_k.p, gen_expl.p, (int)host.gen_expl.size(), d_u, d_k, k.p, d_du, s);
+    launch_sweep(plan, host.N, host.R, host.n_pairs(), B, sweep_rec.p, sweep_k.p, host.pair_rec64.empty() ? nullptr : sweep_rec64.p,
+                 sweep_copy.p, host.gen_rec8.empty() ? nullptr : gen_rec8.p, gen_k.p, gen_expl.p, d_u, d_k, k.p, d_du, s);
 }
 
 void kin_network::jac_dev(const double* d_u, double* d_vals) {
@@ -297,6 +300,38 @@ int kin_rhs_batched_dev(kin_network* h, int64_t B, const double* d_u, const doub
   hipStream_t s = stream ? (hipStream_t)stream : h->stream;
   h->sweep_dev(B, d_u, d_k, d_du, s);
   KIN_CATCH(h)
+}
+
+static void sweep_plan_info(const SweepPlan& p, int64_t* info) {
+  const int64_t v[KIN_SWEEP_PLAN_INFO] = {p.kernel, p.bs, p.tr, p.ilp, p.blk, p.adj, p.u_in_lds, p.n_a, p.n_b, p.grid, p.per_cu,
+                                          p.n_copy, p.n_expl, p.tail_tiles, p.tail_by_species, (int64_t)p.smem, p.n_tiles, p.H, p.P};
+  std::copy(v, v + KIN_SWEEP_PLAN_INFO, info);
+}
+
+int kin_sweep_plan(kin_network* h, int64_t B, const double* d_u, const double* d_k, const double* d_du, int64_t* info) {
+  if (!h) return KIN_ERR_INVALID_ARG;
+  KIN_TRY(h)
+  require(B > 0 && info, ERR_INVALID_ARG, "bad arguments");
+  sweep_plan_info(h->sweep_plan_dev(B, d_u, d_k, d_du), info);   // exactly what kin_rhs_batched_dev asks for
+  KIN_CATCH(h)
+}
+
+int kin_sweep_plan_host(int64_t n_species, int64_t n_reactions, const int64_t* reac_ptr, const int64_t* reac_idx,
+                        const int64_t* reac_sto, const int64_t* prod_ptr, const int64_t* prod_idx, const int64_t* prod_sto,
+                        int index_base, int n_cu, int64_t B, int u_bits, int k_bits, int du_bits, int64_t* info) {
+  if (!info || n_cu < 1 || B < 1 || u_bits < 0 || u_bits > 15 || k_bits < 0 || k_bits > 15 || du_bits < 0 || du_bits > 15)
+    return KIN_ERR_INVALID_ARG;
+  try {
+    const NetworkHost H = compile_network(n_species, n_reactions, reac_ptr, reac_idx, reac_sto, prod_ptr, prod_idx, prod_sto, index_base);
+    sweep_plan_info(sweep_plan(sweep_net_info(H), n_cu, B, SweepAlign{(unsigned)u_bits, (unsigned)k_bits, (unsigned)du_bits}), info);
+  } catch (const KinError& e) {
+    g_create_err = e.what();
+    return e.code;
+  } catch (const std::exception& e) {
+    g_create_err = e.what();
+    return KIN_ERR_INVALID_ARG;
+  }
+  return KIN_OK;
 }
 
 int kin_rhs_batched(kin_network* h, int64_t B, const double* u, const double* k, double* du) {

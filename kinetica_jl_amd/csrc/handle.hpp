@@ -164,4 +164,6 @@ struct kin_network {
   void rhs_dev(const double* d_u, double* d_du);        // du = f(u) with current k
   void jac_dev(const double* d_u, double* d_vals);      // CSR values with current k
   void sweep_dev(int64_t B, const double* d_u, const double* d_k, double* d_du, hipStream_t s);   // batched RHS
+  // the launch plan sweep_dev executes for these buffers (d_k null: the handle's own rate constants)
+  kin::SweepPlan sweep_plan_dev(int64_t B, const double* d_u, const double* d_k, const double* d_du) const;
 };

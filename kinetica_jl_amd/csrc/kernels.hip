@@ -323,11 +323,7 @@ __global__ __launch_bounds__(1024) void sweep_lds_kernel(int N, int R, int P, in
 // VALU + ~50 SALU instructions per record and the VALU 47 % busy next to a 54 % busy LDS. Unused fields
 // point at a per-lane dummy entry (u = 1, du discarded) behind the N real ones.
 // ------------------------------------------------------------------------------------------
-constexpr int SWEEP_DUMMY = 64;   // dummy entries behind u_s / du_s, one per lane
-// rows per batch of sweep_reg_kernel (ILP); a build-time knob for the depth comparison in docs/DESIGN_HISTORY.md
-#ifndef KIN_SWEEP_ILP
-#define KIN_SWEEP_ILP 4
-#endif
+// (SWEEP_DUMMY dummy entries behind u_s / du_s, one per lane, and KIN_SWEEP_ILP, the rows per batch: sweep_plan.hpp)
 __device__ __forceinline__ void sweep_apply(uint2 w, double2 kk, const double* u_s, double* du_s) {
   const uint32_t l0 = w.x & 0x3fffu, l1 = (w.x >> 14) & 0x3fffu, l2 = (w.x >> 28) | ((w.y & 0x3ffu) << 4), l3 = (w.y >> 10) & 0x3fffu;
 #if defined(KIN_SWEEP_PROBE) && KIN_SWEEP_PROBE == 1   // timing only (wrong results): no LDS operand reads
@@ -385,19 +381,6 @@ __device__ __forceinline__ void sweep_stream_batch(const double* __restrict__ kb
 #pragma unroll
   for (int x = 0; x < NB; x++) sweep_apply(w[x], kk[x], u_s, du_s);
   __builtin_amdgcn_sched_barrier(0);
-}
-
-// Batch plan of the streamed rows (host side): `rows` record rows of BS records, the first TR of them register-
-// resident; the S = rows - TR streamed ones run as n_a batches of ILP and n_b batches of ILP + 1, in the fewest
-// rounds ceil(S / (ILP + 1)) - a remainder row rides in a wider batch instead of costing a load round of its own
-// (C3, BS = 1024: 17 streamed rows = 4 + 4 + 4 + 5, not 4 x 4 + a fifth batch of one real row and three padding rows).
-// Rows past `rows` that the last ILP-batch covers (S < ILP * rounds) are padding records.
-struct SweepStreamPlan { int n_a, n_b; };
-static SweepStreamPlan sweep_stream_plan(int64_t P, int bs, int tr, int ilp) {
-  const int64_t rows = ceil_div(P, (int64_t)bs), S = std::max<int64_t>(0, rows - tr);
-  const int64_t rounds = ceil_div(S, (int64_t)(ilp + 1));
-  const int64_t n_b = std::max<int64_t>(0, S - ilp * rounds);
-  return {(int)(rounds - n_b), (int)n_b};
 }
 
 // TR = records per thread kept in registers (compile time, fully unrolled); records beyond
@@ -540,14 +523,13 @@ __global__ __launch_bounds__(BS) void sweep_reg_kernel(int N, int R, int P, int 
 }
 
 template <int TR, int ILP, bool BLK, int BS>
-static void launch_sweep_reg_t(int grid, size_t smem, int N, int R, int P, int B, int tile, const void* rec64,
+static void launch_sweep_reg_t(int grid, size_t smem, int N, int R, int P, int B, int tile, int n_a, int n_b, const void* rec64,
                                const int32_t* copy_species, int n_copy, const double* u, const double* k_b, const double* k_1,
                                double* du, hipStream_t s) {
   // per launch, not cached: the attribute belongs to the (function, device) pair and costs ~1 us
   KIN_HIP(hipFuncSetAttribute((const void*)sweep_reg_kernel<TR, ILP, BLK, BS>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  const SweepStreamPlan plan = sweep_stream_plan(P, BS, TR, ILP);
   static_assert(2 * ILP <= SWEEP_REC_PAD / 1024, "a batch that starts in the last row must stay inside the padded record array");
-  hipLaunchKernelGGL((sweep_reg_kernel<TR, ILP, BLK, BS>), dim3(grid), dim3(BS), smem, s, N, R, P, B, tile, plan.n_a, plan.n_b,
+  hipLaunchKernelGGL((sweep_reg_kernel<TR, ILP, BLK, BS>), dim3(grid), dim3(BS), smem, s, N, R, P, B, tile, n_a, n_b,
                      (const uint2*)rec64, copy_species, n_copy, u, k_b, k_1, du);
 }
 
@@ -830,16 +812,15 @@ static void launch_sweep_big_t(int grid, int N, int R, int P, int B, int H, int 
                      tail_ptr, (const uint2*)tail_ent, scratch, u, k_b, k_1, du, by_species);
 }
 
-// `scratch` holds min(B, n_cu) rows of (N - H) + P doubles; n_cu = compute units of the handle's device
-void launch_sweep_big(int n_cu, int64_t N, int64_t R, int64_t P, int64_t B, bool adjacent, int32_t H, int32_t n_tail_tiles, const void* rec8,
-                      const void* rec, const int32_t* expl, int32_t n_expl, const void* pair_k, const int32_t* spec_of_label,
+// `scratch` holds plan.grid = min(B, n_cu) rows of (N - H) + P doubles
+void launch_sweep_big(const SweepPlan& plan, int64_t N, int64_t R, int64_t P, int64_t B, const void* rec8,
+                      const void* rec, const int32_t* expl, const void* pair_k, const int32_t* spec_of_label,
                       const int32_t* tail_ptr, const void* tail_ent, double* scratch, const double* u, const double* k_b,
-                      const double* k_1, double* du, bool tail_by_species, hipStream_t s) {
+                      const double* k_1, double* du, hipStream_t s) {
   if (B == 0) return;
-  const int grid = (int)std::min<int64_t>(B, n_cu);
-  const bool adj = adjacent && ((((uintptr_t)(k_b ? k_b : k_1)) & 15) == 0);
-  if (adj) launch_sweep_big_t<true>(grid, (int)N, (int)R, (int)P, (int)B, H, n_tail_tiles, rec8, rec, expl, n_expl, pair_k, spec_of_label, tail_ptr, tail_ent, scratch, u, k_b, k_1, du, tail_by_species ? 1 : 0, s);
-  else launch_sweep_big_t<false>(grid, (int)N, (int)R, (int)P, (int)B, H, n_tail_tiles, rec8, rec, expl, n_expl, pair_k, spec_of_label, tail_ptr, tail_ent, scratch, u, k_b, k_1, du, tail_by_species ? 1 : 0, s);
+  const int by_species = plan.tail_by_species ? 1 : 0;
+  if (plan.adj) launch_sweep_big_t<true>(plan.grid, (int)N, (int)R, (int)P, (int)B, plan.H, plan.tail_tiles, rec8, rec, expl, plan.n_expl, pair_k, spec_of_label, tail_ptr, tail_ent, scratch, u, k_b, k_1, du, by_species, s);
+  else launch_sweep_big_t<false>(plan.grid, (int)N, (int)R, (int)P, (int)B, plan.H, plan.tail_tiles, rec8, rec, expl, plan.n_expl, pair_k, spec_of_label, tail_ptr, tail_ent, scratch, u, k_b, k_1, du, by_species, s);
   KIN_HIP(hipGetLastError());
 }
 
@@ -852,72 +833,50 @@ static void launch_sweep_t(int grid, size_t smem, int N, int R, int P, int B, in
                      (const SweepRec*)rec, (const int2*)pair_k, u, k_b, k_1, du);
 }
 
-void launch_sweep(int n_cu, int64_t N, int64_t R, int64_t P, int64_t B, bool adjacent, bool block, const void* rec, const void* pair_k,
-                  const void* rec64, const int32_t* copy_species, int n_copy, const void* gen_rec8, const void* gen_k,
-                  const int32_t* gen_expl, int n_gen_expl, const double* u, const double* k_b, const double* k_1, double* du,
-                  hipStream_t s) {
+void launch_sweep(const SweepPlan& plan, int64_t N, int64_t R, int64_t P, int64_t B, const void* rec, const void* pair_k,
+                  const void* rec64, const int32_t* copy_species, const void* gen_rec8, const void* gen_k,
+                  const int32_t* gen_expl, const double* u, const double* k_b, const double* k_1, double* du, hipStream_t s) {
   if (B == 0) return;
-  const size_t lds_max = 160 * 1024;
-  const int grid = (int)std::min<int64_t>(B, n_cu);
-  // the double2 fast path also needs 16-byte aligned rows of k: R even (checked by the host) and an aligned base
-  const bool adj = adjacent && ((((uintptr_t)(k_b ? k_b : k_1)) & 15) == 0);
-  if ((size_t)(2 * N) * 8 <= lds_max) {
-    const int tile = (int)((N + 1) / 2 * 2);
-    const size_t smem = (size_t)(tile + N) * 8;
-    if ((adj || block) && rec64 && R < ((int64_t)1 << 29) && ((((uintptr_t)u) | ((uintptr_t)du)) & 15) == 0 && N % 2 == 0 &&
-        (size_t)(2 * (N + SWEEP_DUMMY + n_copy)) * 8 <= lds_max && n_copy <= 1024) {
-      const int rtile = (int)N + SWEEP_DUMMY + n_copy + (n_copy & 1);   // even: keeps u_s 16-byte aligned
-      const size_t rsmem = (size_t)2 * rtile * 8;
-      // smaller states run in smaller workgroups, several per CU (LDS permitting): more states in flight per CU and
-      // enough records per thread to keep them register-resident (C2, N = 1000: 0.073 -> 0.050 ms)
-      const int bs = (N <= 2560 && n_copy <= 256) ? 256 : ((N <= 5120 && n_copy <= 512) ? 512 : 1024);
-      const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(2048 / bs, lds_max / rsmem));
-      const int rgrid = (int)std::min<int64_t>(B, (int64_t)n_cu * per_cu);
-      const int64_t Tr = P / bs;   // full record rows available for residency
-#define KIN_REG_ARGS rgrid, rsmem, (int)N, (int)R, (int)P, (int)B, rtile, rec64, copy_species, n_copy, u, k_b, k_1, du, s
+  const int grid = plan.grid, tile = plan.tile, bs = plan.bs;
+  const size_t smem = plan.smem;
+  if (plan.kernel == SWEEP_REG) {
+    const bool adj = plan.adj;
+#define KIN_REG_ARGS grid, smem, (int)N, (int)R, (int)P, (int)B, tile, plan.n_a, plan.n_b, rec64, copy_species, plan.n_copy, u, k_b, k_1, du, s
 #define KIN_REG_GO(TT, II)                                                                   \
   do {                                                                                       \
     if (bs == 256) { if (adj) launch_sweep_reg_t<TT, II, false, 256>(KIN_REG_ARGS); else launch_sweep_reg_t<TT, II, true, 256>(KIN_REG_ARGS); }   \
     else if (bs == 512) { if (adj) launch_sweep_reg_t<TT, II, false, 512>(KIN_REG_ARGS); else launch_sweep_reg_t<TT, II, true, 512>(KIN_REG_ARGS); } \
     else { if (adj) launch_sweep_reg_t<TT, II, false, 1024>(KIN_REG_ARGS); else launch_sweep_reg_t<TT, II, true, 1024>(KIN_REG_ARGS); }       \
   } while (0)
-      // two register-resident batches where the network has the rows for them, else one, else none
-      constexpr int I = KIN_SWEEP_ILP;
-      if (Tr >= 2 * I) KIN_REG_GO(2 * I, I);
-      else if (Tr >= I) KIN_REG_GO(I, I);
-      else KIN_REG_GO(0, I);
+    constexpr int I = KIN_SWEEP_ILP;
+    if (plan.tr == 2 * I) KIN_REG_GO(2 * I, I);
+    else if (plan.tr == I) KIN_REG_GO(I, I);
+    else KIN_REG_GO(0, I);
 #undef KIN_REG_GO
 #undef KIN_REG_ARGS
-      KIN_HIP(hipGetLastError());
-      return;
-    }
-    if (gen_rec8 && (size_t)(2 * (N + SWEEP_DUMMY)) * 8 <= lds_max) {
-      const int gtile = (int)N + SWEEP_DUMMY;
-      const size_t gsmem = (size_t)2 * gtile * 8;
-      const int bs = N <= 2560 ? 256 : (N <= 5120 ? 512 : 1024);     // smaller states: smaller workgroups, several per CU
-      const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(2048 / bs, lds_max / gsmem));
-      const int ggrid = (int)std::min<int64_t>(B, (int64_t)n_cu * per_cu);
+  } else if (plan.kernel == SWEEP_GEN) {
 #define KIN_GEN_GO(BSZ)                                                                                                                 \
   do {                                                                                                                                  \
     KIN_HIP(hipFuncSetAttribute((const void*)sweep_gen_kernel<BSZ>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));           \
-    hipLaunchKernelGGL(sweep_gen_kernel<BSZ>, dim3(ggrid), dim3(BSZ), gsmem, s, (int)N, (int)R, (int)P, (int)B, gtile,                  \
-                       (const uint2*)gen_rec8, (const int2*)gen_k, (const int2*)pair_k, (const SweepRec*)rec, gen_expl, n_gen_expl,     \
+    hipLaunchKernelGGL(sweep_gen_kernel<BSZ>, dim3(grid), dim3(BSZ), smem, s, (int)N, (int)R, (int)P, (int)B, tile,                     \
+                       (const uint2*)gen_rec8, (const int2*)gen_k, (const int2*)pair_k, (const SweepRec*)rec, gen_expl, plan.n_expl,    \
                        u, k_b, k_1, du);                                                                                                \
   } while (0)
-      if (bs == 256) KIN_GEN_GO(256);
-      else if (bs == 512) KIN_GEN_GO(512);
-      else KIN_GEN_GO(1024);
+    if (bs == 256) KIN_GEN_GO(256);
+    else if (bs == 512) KIN_GEN_GO(512);
+    else KIN_GEN_GO(1024);
 #undef KIN_GEN_GO
-      KIN_HIP(hipGetLastError());
-      return;
+  } else if (plan.kernel == SWEEP_LDS) {
+    const int nt = plan.n_tiles;
+    if (plan.u_in_lds) {
+      if (plan.adj) launch_sweep_t<true, true>(grid, smem, (int)N, (int)R, (int)P, (int)B, tile, nt, rec, pair_k, u, k_b, k_1, du, s);
+      else launch_sweep_t<true, false>(grid, smem, (int)N, (int)R, (int)P, (int)B, tile, nt, rec, pair_k, u, k_b, k_1, du, s);
+    } else {
+      if (plan.adj) launch_sweep_t<false, true>(grid, smem, (int)N, (int)R, (int)P, (int)B, tile, nt, rec, pair_k, u, k_b, k_1, du, s);
+      else launch_sweep_t<false, false>(grid, smem, (int)N, (int)R, (int)P, (int)B, tile, nt, rec, pair_k, u, k_b, k_1, du, s);
     }
-    if (adj) launch_sweep_t<true, true>(grid, smem, (int)N, (int)R, (int)P, (int)B, tile, 1, rec, pair_k, u, k_b, k_1, du, s);
-    else launch_sweep_t<true, false>(grid, smem, (int)N, (int)R, (int)P, (int)B, tile, 1, rec, pair_k, u, k_b, k_1, du, s);
   } else {
-    const int tile = 16 * 1024;   // 128 kB of accumulators per pass
-    const int n_tiles = (int)ceil_div(N, tile);
-    if (adj) launch_sweep_t<false, true>(grid, (size_t)tile * 8, (int)N, (int)R, (int)P, (int)B, tile, n_tiles, rec, pair_k, u, k_b, k_1, du, s);
-    else launch_sweep_t<false, false>(grid, (size_t)tile * 8, (int)N, (int)R, (int)P, (int)B, tile, n_tiles, rec, pair_k, u, k_b, k_1, du, s);
+    throw KinError(ERR_INVALID_ARG, "launch_sweep: not a plan of the LDS sweeps");
   }
   KIN_HIP(hipGetLastError());
 }

@@ -2,6 +2,7 @@
 #pragma once
 #include "common.hpp"
 #include "network.hpp"
+#include "sweep_plan.hpp"
 
 namespace kin {
 
@@ -60,21 +61,31 @@ void launch_arrhenius(int64_t n, const double* Ea, const double* A, int has_kmax
 void launch_rate_table(int64_t n, int64_t n_stops, const double* Ea, const double* A, int has_kmax, double k_max,
                        double t_mult, const double* T, double* table, hipStream_t s);
 
-// batched sweep over B states, state-major layouts (see kin_rhs_batched_dev); rec = packed 16-byte records
-// `adjacent`: pair p = reactions (2p, 2p+1); `block`: pair p = reactions (p, P+p) (forwards first, reverses behind)
-// n_cu: compute units of the device the handle lives on (per handle, not cached per process)
+// batched sweep over B states, state-major layouts (see kin_rhs_batched_dev); rec = packed 16-byte records.
+// `plan` = sweep_plan() of the network and the call's buffers (sweep_plan.hpp): the launchers execute it and decide nothing.
 // rec64, gen_rec8 and gen_k are the host-padded arrays (NetworkHost: SWEEP_REC_PAD all-dummy records behind the P real
 // ones), read without bounds tests; rec and pair_k hold exactly P records
-void launch_sweep(int n_cu, int64_t N, int64_t R, int64_t P, int64_t B, bool adjacent, bool block, const void* rec, const void* pair_k,
-                  const void* rec64, const int32_t* copy_species, int n_copy, const void* gen_rec8, const void* gen_k,
-                  const int32_t* gen_expl, int n_gen_expl, const double* u, const double* k_b, const double* k_1, double* du,
-                  hipStream_t s);
+void launch_sweep(const SweepPlan& plan, int64_t N, int64_t R, int64_t P, int64_t B, const void* rec, const void* pair_k,
+                  const void* rec64, const int32_t* copy_species, const void* gen_rec8, const void* gen_k,
+                  const int32_t* gen_expl, const double* u, const double* k_b, const double* k_1, double* du, hipStream_t s);
+
+// the part of a compiled network the caller-layout sweep's plan depends on
+inline SweepNetInfo sweep_net_info(const NetworkHost& H) {
+  SweepNetInfo n{};
+  n.N = H.N; n.R = H.R; n.P = H.n_pairs();
+  n.adjacent = H.pairs_adjacent; n.block = H.pairs_block;
+  n.has_rec64 = !H.pair_rec64.empty(); n.has_gen = !H.gen_rec8.empty();
+  n.n_copy = (int)H.sweep_copy_species.size(); n.n_gen_expl = (int)H.gen_expl.size();
+  n.big_H = H.big_H; n.big_tail_tiles = H.big_H > 0 ? (int32_t)H.big_tail_ptr.size() - 1 : 0;
+  n.big_n_expl = (int32_t)H.big_expl.size(); n.big_tail_by_species = H.big_tail_by_species;
+  return n;
+}
 
 // large-N sweep (state too large for LDS): hubs in LDS, tail via a per-workgroup scratch row and tail-entry lists;
-// `scratch` holds min(B, n_cu) rows of (N - H) + P doubles
-void launch_sweep_big(int n_cu, int64_t N, int64_t R, int64_t P, int64_t B, bool adjacent, int32_t H, int32_t n_tail_tiles, const void* rec8,
-                      const void* rec, const int32_t* expl, int32_t n_expl, const void* pair_k, const int32_t* spec_of_label,
+// `scratch` holds plan.grid rows of (N - H) + P doubles
+void launch_sweep_big(const SweepPlan& plan, int64_t N, int64_t R, int64_t P, int64_t B, const void* rec8,
+                      const void* rec, const int32_t* expl, const void* pair_k, const int32_t* spec_of_label,
                       const int32_t* tail_ptr, const void* tail_ent, double* scratch, const double* u, const double* k_b,
-                      const double* k_1, double* du, bool tail_by_species, hipStream_t s);
+                      const double* k_1, double* du, hipStream_t s);
 
 }  // namespace kin

@@ -53,13 +53,26 @@ void ensure_params(kin_network* h, hipStream_t) {
   h->t_par_valid = true;
 }
 
-TiledView view_of(kin_network* h) {
-  const TiledHost& L = h->tiled;
+// the sizes of a layout's view (all the sweep's launch plan reads); view_of adds the device pointers
+TiledView sizes_of(const TiledHost& L) {
   TiledView v{};
   v.KL = L.KL; v.has_singles = L.has_singles ? 1 : 0;
   v.N = L.N; v.P = L.P; v.h = L.h; v.n_copy = L.n_copy; v.wbase = L.wbase; v.E = L.E; v.T = L.T;
   v.win_cnt_max = 0;
   for (int32_t c : L.win_cnt) v.win_cnt_max = std::max(v.win_cnt_max, c);
+  return v;
+}
+
+void tiled_plan_info(const TiledHost& L, int n_cu, int64_t B, bool tmode, int64_t* info) {
+  const TiledSweepPlan p = tiled_plan_of(sizes_of(L), L.BS, n_cu, B, tmode);
+  const int64_t v[KIN_TILED_PLAN_INFO] = {p.bs, p.tmode, p.un, p.singles, p.nb, p.grid, p.per_cu, (int64_t)p.smem,
+                                          L.identity, L.T, L.n_copy, L.has_singles};
+  std::copy(v, v + KIN_TILED_PLAN_INFO, info);
+}
+
+TiledView view_of(kin_network* h) {
+  const TiledHost& L = h->tiled;
+  TiledView v = sizes_of(L);
   v.rec = (const uint2*)h->t_rec.p;
   for (int32_t t = 0; t < L.T; t++) {
     v.seginfo[t] = make_int4(L.seginfo[4 * t], L.seginfo[4 * t + 1], L.seginfo[4 * t + 2], L.seginfo[4 * t + 3]);
@@ -134,6 +147,32 @@ int kin_lib_layout_host(int64_t n_species, int64_t n_reactions, const int64_t* r
     if (win_cnt) std::copy(L.win_cnt.begin(), L.win_cnt.end(), win_cnt);
     if (copy_src) std::copy(L.copy_src.begin(), L.copy_src.end(), copy_src);
     if (seg_k) std::copy(L.seg_k.begin(), L.seg_k.end(), seg_k);
+  } catch (const KinError& e) {
+    return e.code;
+  } catch (const std::exception&) {
+    return KIN_ERR_INVALID_ARG;
+  }
+  return KIN_OK;
+}
+
+int kin_tiled_sweep_plan(kin_network* h, int64_t B, int temperature_form, int64_t* info) {
+  if (!h) return KIN_ERR_INVALID_ARG;
+  KIN_TRY(h)
+  require(B > 0 && info, ERR_INVALID_ARG, "bad arguments");
+  ensure_tiled(h);
+  tiled_plan_info(h->tiled, h->n_cu, B, temperature_form != 0, info);
+  KIN_CATCH(h)
+}
+
+int kin_tiled_sweep_plan_host(int64_t n_species, int64_t n_reactions, const int64_t* reac_ptr, const int64_t* reac_idx,
+                              const int64_t* reac_sto, const int64_t* prod_ptr, const int64_t* prod_idx, const int64_t* prod_sto,
+                              int index_base, int n_cu, int64_t B, int temperature_form, int64_t* info) {
+  if (!info || n_cu < 1 || B < 1) return KIN_ERR_INVALID_ARG;
+  try {
+    const NetworkHost H = compile_network(n_species, n_reactions, reac_ptr, reac_idx, reac_sto, prod_ptr, prod_idx, prod_sto, index_base);
+    const TiledHost L = build_tiled(H, tiled_block_size(H.N), 0);
+    if (!L.ok) return KIN_ERR_UNSUPPORTED;
+    tiled_plan_info(L, n_cu, B, temperature_form != 0, info);
   } catch (const KinError& e) {
     return e.code;
   } catch (const std::exception&) {

@@ -519,15 +519,17 @@ static void launch_tiled_t(const TiledView& v, int grid, size_t smem, int B, con
   hipLaunchKernelGGL((tiled_sweep_kernel<BS, TMODE, UN, SINGLES>), dim3(grid), dim3(BS), smem, s, v, B, u, k_lib, Tb, du);
 }
 
+TiledSweepPlan tiled_plan_of(const TiledView& v, int bs, int n_cu, int64_t B, bool tmode) {
+  return tiled_sweep_plan(bs, v.E, v.h, v.win_cnt_max, v.has_singles != 0, TILED_EXP_TAB, n_cu, B, tmode);
+}
+
 void launch_tiled_sweep(const TiledView& v, int bs, int n_cu, int64_t B, const double* u, const double* k_lib, const double* Tb,
                         double* du, hipStream_t s) {
   if (B == 0) return;
-  const bool tmode = k_lib == nullptr;
-  const size_t smem = ((size_t)2 * v.E + (tmode ? TILED_EXP_TAB : 0)) * 8;
-  const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(2048 / bs, (160 * 1024) / smem));
-  const int grid = (int)std::min<int64_t>(B, (int64_t)n_cu * per_cu);
-  const bool un5 = std::max(v.h, v.win_cnt_max) <= 5 * bs;
-  const bool singles = !tmode && v.has_singles;   // (the temperature form reads no rate constants: one instantiation)
+  const TiledSweepPlan plan = tiled_plan_of(v, bs, n_cu, B, k_lib == nullptr);
+  const bool tmode = plan.tmode, un5 = plan.un == 5, singles = plan.singles;
+  const int grid = plan.grid;
+  const size_t smem = plan.smem;
 #define KIN_TILED_GO(BSZ)                                                                                  \
   do {                                                                                                     \
     if (tmode) { if (un5) launch_tiled_t<BSZ, true, 5, false>(v, grid, smem, (int)B, u, k_lib, Tb, du, s);           \

@@ -1,6 +1,7 @@
 // Device view and launchers of the tiled batched sweep (tiled_kernels.hip; layout: tiled.hpp).
 #pragma once
 #include "common.hpp"
+#include "sweep_plan.hpp"
 #include "tiled.hpp"
 
 namespace kin {
@@ -26,6 +27,8 @@ struct TiledView {   // passed to the kernel by value
 // u, du: B x N in library species order. n_cu: compute units of the device the stream belongs to.
 void launch_tiled_sweep(const TiledView& v, int bs, int n_cu, int64_t B, const double* u, const double* k_lib, const double* Tb,
                         double* du, hipStream_t s);
+// the plan launch_tiled_sweep executes (sweep_plan.hpp); only the sizes of `v` are read, no device pointer
+TiledSweepPlan tiled_plan_of(const TiledView& v, int bs, int n_cu, int64_t B, bool tmode);
 // dst[b][j] = map[j] >= 0 ? src[b][map[j]] : 0 for b < B (rows of n_dst / n_src doubles): the layout conversions
 void launch_gather_rows(int64_t n_dst, int64_t n_src, int64_t B, const int32_t* map, const double* src, double* dst, hipStream_t s);
 // The species permutation through LDS (tiled.hpp: stage_lib / stage_off): every global access is part of a coalesced stream -

@@ -297,6 +297,9 @@ def lu_analyze_host(net, hub_degree=0, max_rounds=0, max_tail_degree=0, max_degr
     return {k: int(v) for k, v in zip(keys, info)}
 
 
+# classes of the DRG gather plans by contributions of a row (drg.hpp: SegPlanHost::SHORT_MAX, SEG_LEN), and the entries a
+# workgroup takes per pass of a long row (drg_kernels.hip: DRG_WG * DRG_LONG_NX)
+DRG_SHORT_MAX, DRG_SEG_LEN, DRG_LONG_PASS = 8, 256, 1024
 DRG_INFO = ("edges", "den_contributions", "edge_contributions", "den_short", "den_medium", "den_long", "edge_short", "edge_medium",
             "edge_long")
 
@@ -344,6 +347,9 @@ PFA_INFO = ("edges", "pairs", "products", "max_row")
 # the largest network the second-generation stage takes (pfa.hpp: PFA_LDS_SPECIES) and the cost sum over M in out(A) of deg(M)
 # above which a workgroup, not a wavefront, takes row A (PFA_WG_COST)
 PFA_MAX_SPECIES, PFA_WG_COST = 20286, 65536
+# the second-generation stage (pfa.hpp, pfa_kernels.hip): out-edges of a row staged at a time, rows M whose loads are in flight
+# together, and the columns of the E2 row per thread whose maximum lives in registers (of a wavefront of 64 or a workgroup of 256)
+PFA_CHUNK, PFA_AHEAD, PFA_KEEP = 64, 4, 6
 
 
 def pfa_pattern_host(net, pairing=True):

@@ -66,7 +66,7 @@ void drg_run(kin_network* h, int pairing, int64_t B, const double* d_u, const Fl
   h->drg_rates.alloc((size_t)nb_max * R);
   h->drg_den.alloc((size_t)nb_max * N);
   const SegPlanView dv = m.den_plan.view(), ev = m.edge_plan.view();
-  const int Ye_max = drg_slices(ev, nb_max, h->n_cu);
+  const int Ye_max = slices_cap(drg_slices(ev, nb_max, h->n_cu));
   h->drg_part.alloc((size_t)Ye_max * E);
   for (int64_t b0 = 0; b0 < B; b0 += nb_max) {
     const int64_t nb = std::min(nb_max, B - b0);
@@ -80,9 +80,9 @@ void drg_run(kin_network* h, int pairing, int64_t B, const double* d_u, const Fl
     a.rates = h->drg_rates.p; a.b0 = b0; a.seg_n = d_seg_n; a.L = L;
     a.den = h->drg_den.p; a.part = h->drg_part.p;
     a.p = dv; a.ell_c = m.den_ell_c.p; a.long_c = m.den_long_c.p;
-    launch_drg_den(a, drg_slices(dv, nb, h->n_cu), s);
+    launch_drg_den(a, slices_cap(drg_slices(dv, nb, h->n_cu)), s);
     a.p = ev; a.ell_c = m.edge_ell_c.p; a.long_c = m.edge_long_c.p;
-    const int Ye = drg_slices(ev, nb, h->n_cu);
+    const int Ye = slices_cap(drg_slices(ev, nb, h->n_cu));
     launch_drg_edges(a, Ye, s);
     launch_drg_max(E, Ye, h->drg_part.p, d_coef, (accumulate || b0 > 0) ? 1 : 0, s);
   }
@@ -134,7 +134,7 @@ void ri_run(kin_network* h, int pairing, int64_t B, const double* d_u, const Flu
   nb_max = std::min(nb_max, B);
   h->drg_rates.alloc((size_t)nb_max * R);
   h->drg_den.alloc((size_t)nb_max * N);
-  h->ri_part.alloc((size_t)ri_slices(R, nb_max, h->n_cu) * R);
+  h->ri_part.alloc((size_t)slices_cap(ri_slices(R, nb_max, h->n_cu)) * R);
   if (per_state) h->ri_state.alloc((size_t)nb_max * R);
   if (d_sel) { h->ri_mask.alloc((size_t)std::max<int64_t>(N, 1)); launch_ri_mask(n_sel, d_sel, N, h->ri_mask.p, s); }
   for (int64_t b0 = 0; b0 < B; b0 += nb_max) {
@@ -149,14 +149,14 @@ void ri_run(kin_network* h, int pairing, int64_t B, const double* d_u, const Flu
     a.rates = h->drg_rates.p; a.b0 = b0; a.seg_n = d_seg_n; a.L = L;
     a.den = h->drg_den.p;
     a.p = dn.p; a.ell_c = dn.ell_c; a.long_c = dn.long_c;
-    launch_drg_den(a, drg_slices(dn.p, nb, h->n_cu), s);
+    launch_drg_den(a, slices_cap(drg_slices(dn.p, nb, h->n_cu)), s);
     RiArgs ra{};
     ra.N = (int)N; ra.R = (int)R; ra.nb = (int)nb;
     ra.tab = h->ri[pairing ? 1 : 0].tab.p; ra.mask = d_sel ? h->ri_mask.p : nullptr;
     ra.rates = h->drg_rates.p; ra.den = h->drg_den.p;
     ra.b0 = b0; ra.seg_n = d_seg_n; ra.L = L;
     ra.part = h->ri_part.p; ra.per_state = per_state ? h->ri_state.p : nullptr;
-    const int Y = ri_slices(R, nb, h->n_cu);
+    const int Y = slices_cap(ri_slices(R, nb, h->n_cu));
     launch_ri(ra, Y, s);
     launch_drg_max(R, Y, h->ri_part.p, d_imp, (accumulate || b0 > 0) ? 1 : 0, s);
     if (per_state) h->ri_state.download(per_state + (size_t)b0 * R, (size_t)nb * R, s);

@@ -98,9 +98,9 @@ void drgep_run(kin_network* h, int pairing, int64_t B, const double* d_u, const 
       a.rates = h->drg_rates.p; a.b0 = b0; a.seg_n = d_seg_n; a.L = L;
       a.den = h->drg_den.p; a.r = h->drgep_r.p;
       a.p = dv; a.ell_c = m.den_ell_s.p; a.long_c = m.den_long_s.p;
-      launch_drgep_den(a, drg_slices(dv, nb, h->n_cu), s);
+      launch_drgep_den(a, slices_cap(drg_slices(dv, nb, h->n_cu)), s);
       a.p = ev; a.ell_c = m.edge_ell_s.p; a.long_c = m.edge_long_s.p;
-      launch_drgep_edges(a, drg_slices(ev, nb, h->n_cu), s);
+      launch_drgep_edges(a, slices_cap(drg_slices(ev, nb, h->n_cu)), s);
     }
     if (upto < 3) continue;
     drgep_paths_block(h, m, b0, nb, d_seg_n, L, d_targets, n_targets, (accumulate || b0 > 0) ? 1 : 0, d_imp, out, s);

@@ -74,7 +74,7 @@ void pfa_alloc(kin_network* h, const PfaTables& t, int64_t nb_max, bool want_r) 
   h->pfa_rp.alloc((size_t)nb_max * t.E);
   h->pfa_rc.alloc((size_t)nb_max * t.E);
   if (want_r) h->pfa_r.alloc((size_t)nb_max * t.E2);
-  h->pfa_part.alloc((size_t)pfa_slices(t, nb_max, h->n_cu) * t.E2);
+  h->pfa_part.alloc((size_t)slices_cap(pfa_slices(t, nb_max, h->n_cu)) * t.E2);
 }
 
 // The second-generation stage of one block whose coefficients are in h->pfa_rp / pfa_rc, folded into d_coef.
@@ -87,7 +87,7 @@ void pfa_second_block(kin_network* h, kin_network::PfaMode& m, int64_t b0, int64
   a.rp = h->pfa_rp.p; a.rc = h->pfa_rc.p;
   a.b0 = b0; a.seg_n = d_seg_n; a.L = L;
   a.part = h->pfa_part.p; a.r = out.r ? h->pfa_r.p : nullptr;
-  const int Y = pfa_slices(t, nb, h->n_cu);
+  const int Y = slices_cap(pfa_slices(t, nb, h->n_cu));
   launch_pfa_second(t, a, pfa_wg_cost(t.N), Y, s);
   launch_drg_max(t.E2, Y, h->pfa_part.p, d_coef, use_prev, s);
   if (out.rp) h->pfa_rp.download(out.rp + (size_t)b0 * t.E, (size_t)nb * t.E, s);
@@ -128,9 +128,9 @@ void pfa_run(kin_network* h, int pairing, int64_t B, const double* d_u, const Fl
     a.rates = h->drg_rates.p; a.b0 = b0; a.seg_n = d_seg_n; a.L = L;
     a.den = h->drg_den.p; a.r = h->pfa_rp.p; a.rc = h->pfa_rc.p;
     a.p = dv; a.ell_c = g.den_ell_s.p; a.long_c = g.den_long_s.p;
-    launch_drgep_den(a, drg_slices(dv, nb, h->n_cu), s);
+    launch_drgep_den(a, slices_cap(drg_slices(dv, nb, h->n_cu)), s);
     a.p = ev; a.ell_c = g.edge_ell_s.p; a.long_c = g.edge_long_s.p;
-    launch_pfa_split(a, drg_slices(ev, nb, h->n_cu), s);
+    launch_pfa_split(a, slices_cap(drg_slices(ev, nb, h->n_cu)), s);
     if (upto < 3) continue;
     pfa_second_block(h, m, b0, nb, d_seg_n, L, (accumulate || b0 > 0) ? 1 : 0, d_coef, out, s);
   }

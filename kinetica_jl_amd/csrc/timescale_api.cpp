@@ -63,7 +63,7 @@ void ts_run(kin_network* h, int64_t B, const double* d_u, const FluxSource& src,
   ra.rows = reinterpret_cast<const int4*>(h->ts_rows.p); ra.sp_rxn = h->sp_rxn.p; ra.sp_coef = h->sp_coef.p;
   if (o.summary) {
     ra.nb = (int)nb_max;
-    h->ts_part.alloc((size_t)ts_row_slices(ra, h->n_cu) * 3 * N);
+    h->ts_part.alloc((size_t)slices_cap(ts_row_slices(ra, h->n_cu)) * 3 * N);
   }
   for (int64_t b0 = 0; b0 < B; b0 += nb_max) {
     const int64_t nb = std::min(nb_max, B - b0);
@@ -82,12 +82,12 @@ void ts_run(kin_network* h, int64_t B, const double* d_u, const FluxSource& src,
     TsEntryArgs ea{};
     ea.p = jp; ea.R = (int)R; ea.nb = (int)nb; ea.nnz = nnz; ea.dr = h->ts_dr.p;
     ea.jv = o.vals ? o.vals + (size_t)b0 * nnz : h->ts_jv.p; ea.cnt = cnt;
-    launch_ts_entries(ea, ts_entry_slices(jp, nb, h->n_cu), s);
+    launch_ts_entries(ea, slices_cap(ts_entry_slices(jp, nb, h->n_cu)), s);
     if (!rows || stages == 2) continue;
     ra.nb = (int)nb; ra.jv = ea.jv; ra.rates = h->ts_rates.p; ra.cnt = cnt;
     ra.part = o.summary ? h->ts_part.p : nullptr; ra.g = o.norm ? h->ts_g.p : nullptr;
     ra.diag = o.diag ? o.diag + (size_t)b0 * N : nullptr; ra.err = o.err ? o.err + (size_t)b0 * N : nullptr;
-    const int Y = ts_row_slices(ra, h->n_cu);
+    const int Y = slices_cap(ts_row_slices(ra, h->n_cu));
     launch_ts_rows(ra, Y, s);
     if (o.summary) launch_ts_fold(N, Y, h->ts_part.p, o.summary, (accumulate || b0 > 0) ? 1 : 0, s);
     if (o.norm) launch_ts_norm(N, nb, h->ts_g.p, cnt, o.norm + b0, s);

@@ -33,14 +33,17 @@ EPS = dc.EPS
 
 
 class PfaRef:
-    """E2 of one (network, pairing), the split coefficients of given per-state rates with their bounds, and the second stage."""
+    """E2 of one (network, pairing), the split coefficients of given per-state rates with their bounds, and the second stage.
+    second=False leaves E2 and the second stage out (the split stage alone, where E2 would be millions of pairs)."""
 
-    def __init__(self, net, pairing):
+    def __init__(self, net, pairing, second=True):
         self.s = s = ec.DrgepRef(net, pairing)          # the signed contribution lists on DrgRef's pattern
         self.g = g = s.g
         self.n, self.E, self.rows, self.cols, self.rowptr = g.n, g.E, g.rows, g.cols, g.rowptr
         n, deg = self.n, np.diff(g.rowptr)
         self.deg = deg
+        if not second:
+            return
         # every product: the edges e1 = (A, M) and e2 = (M, B), B != A
         cnt = deg[self.cols] if self.E else np.zeros(0, np.int64)
         e1 = np.repeat(np.arange(self.E, dtype=np.int64), cnt)

@@ -101,6 +101,28 @@ def test_hub_network_long_and_medium_rows(pairing):
 
 
 @pytest.mark.parametrize("pairing", [1, 0])
+def test_hub_whose_long_edge_is_not_its_whole_row(pairing):
+    """In hub_network every record of A holds B: num_AB and den_A are the same sum, formed by the same branch of the gather
+    kernel, and their ratio is 1 whatever that branch does. The collider hubs of reduction_edge_cases.py have two records of
+    A beside the n that hold B, A -> C and D -> A: den_A != num_AB, and on their exact inputs (every sum exact in any order)
+    the coefficient of the long edges is the reference's bit for bit, strictly between 0 and 1."""
+    import reduction_edge_cases as rx
+    c = rx.gather_case("collider")
+    g = c.drg(pairing)
+    coef, r = c.ref("drg", pairing)
+    h = capi.HipNetwork.from_flat(c.net)
+    got = h.drg_batched(c.U, k=c.K, pairing=pairing)
+    h.close()
+    long_hubs = [hub for hub in c.hubs if hub["n"] > capi.DRG_SEG_LEN]
+    assert len(long_hubs) >= 4 and g.info()["edge_long"] == 2 * len(long_hubs)
+    for hub in long_hubs:
+        e = rx.edge_of(g, hub["A"], hub["B"])
+        assert g.den_ptr[hub["A"] + 1] - g.den_ptr[hub["A"]] == g.edge_ptr[e + 1] - g.edge_ptr[e] + rx.SIDE
+        assert 0.0 < coef[e] < 1.0 and got[e] == coef[e]
+    assert np.array_equal(got, coef)
+
+
+@pytest.mark.parametrize("pairing", [1, 0])
 @pytest.mark.parametrize("B", [1, 7, 130])
 def test_300x1500_matches_reference(B, pairing):
     check("300x1500", "per_state", pairing, B, device("300x1500", "per_state", pairing, B))
@@ -174,8 +196,12 @@ def _pars(t1, chunks):
                           ban_negatives=0, solve_chunkstep=t1 / max(chunks, 1), maxiters=100000, save_interval=-1.0)
 
 
-@pytest.mark.parametrize("pairing", [1, 0])
-def test_solution_and_ensemble_forms_equal_the_batched_call(pairing):
+# cap 2: KIN_SLICES_MAX = 2, so that a task walks every other row of the record and skips, inside its walk, the rows a short
+# member has not saved
+@pytest.mark.parametrize("pairing,cap", [(1, None), (0, None), (1, 2), (0, 2)], ids=["1", "0", "1-cap2", "0-cap2"])
+def test_solution_and_ensemble_forms_equal_the_batched_call(pairing, cap, monkeypatch):
+    if cap:
+        monkeypatch.setenv("KIN_SLICES_MAX", str(cap))
     net, Ea, A = dc.synth(300, 1500)
     case = dc.synth_case("300x1500")
     h = capi.HipNetwork.from_flat(net)

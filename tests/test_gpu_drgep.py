@@ -209,8 +209,12 @@ def _pars(t1, chunks, save=-1.0, maxiters=100000):
                           ban_negatives=0, solve_chunkstep=t1 / max(chunks, 1), maxiters=maxiters, save_interval=save, dtmin=0.0)
 
 
-@pytest.mark.parametrize("pairing", [1, 0])
-def test_solution_and_ensemble_forms_equal_the_batched_call(pairing):
+# cap 2: KIN_SLICES_MAX = 2, so that a task walks every other row of the record and skips, inside its walk, the rows a short
+# member has not saved
+@pytest.mark.parametrize("pairing,cap", [(1, None), (0, None), (1, 2), (0, 2)], ids=["1", "0", "1-cap2", "0-cap2"])
+def test_solution_and_ensemble_forms_equal_the_batched_call(pairing, cap, monkeypatch):
+    if cap:
+        monkeypatch.setenv("KIN_SLICES_MAX", str(cap))
     net, Ea, A = dc.synth(300, 1500)
     case = dc.synth_case("300x1500")
     h = capi.HipNetwork.from_flat(net)

@@ -248,6 +248,17 @@ def _pars(t1, chunks, save=-1.0, maxiters=100000):
 
 
 def test_solution_and_ensemble_forms_equal_the_batched_call():
+    solution_and_ensemble_forms()
+
+
+def test_solution_and_ensemble_forms_equal_the_batched_call_in_two_slices(monkeypatch):
+    """KIN_SLICES_MAX = 2: a task walks every other row of the record and skips, inside its walk, the rows below row_begin and
+    those a short member has not saved"""
+    monkeypatch.setenv("KIN_SLICES_MAX", "2")
+    solution_and_ensemble_forms()
+
+
+def solution_and_ensemble_forms():
     c = synth(300, 1500)
     h = capi.HipNetwork.from_flat(c.net)
     u0 = np.zeros(300); u0[0] = 1.0

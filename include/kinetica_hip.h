@@ -858,6 +858,81 @@ int kin_timescale_plan_host(int64_t n_species, int64_t n_reactions, const int64_
                             const int64_t* reac_sto, const int64_t* prod_ptr, const int64_t* prod_idx, const int64_t* prod_sto,
                             int index_base, int64_t* info /* [4] */);
 
+/* ---- cross-member statistics of an ensemble: moments, quantiles, correlations with the sampled inputs --------------------- */
+/* The passes above reduce along a member's rows. These reduce ACROSS the members of a block of states u[K][L][N] (member, row
+ * of the save grid, species: the stored ensemble's layout) - what a Monte-Carlo run over uncertain rate parameters, a sweep
+ * of heating rates or a set of start compositions is made for: mean and spread of every species at every saved time, the
+ * 5 / 50 / 95 % envelope, and which sampled input drives which species (Pearson and Spearman correlation: the sampling-based
+ * global sensitivity).
+ *
+ * PARTICIPANTS. use[K] is int32; member m takes part iff use[m] != 0; the n participants are the same for every row and
+ * species and are always visited in member order. use == NULL: all K members (kin_members_*), the members that completed
+ * the save grid, n_saved[m] == n_rows (kin_ensemble_*). Over the stored ensemble use[m] != 0 for a member with
+ * n_saved[m] < n_rows is KIN_ERR_INVALID_ARG: rows past n_saved are never read, as in the other ensemble entries.
+ *
+ * MOMENTS per (row j, species i) over the participants' x = u[m][j][i]:
+ *   count = n;  mean = sum x / n;  var = sum (x - mean)^2 / (n - 1) (two passes, unbiased; exactly 0.0 for n == 1);  min and
+ *   max exact. n == 0 writes zeros everywhere.
+ * QUANTILES for probabilities p[Q] in [0, 1] (anything else, NaN included: KIN_ERR_INVALID_ARG) over the sorted participant
+ * values x[0..n):  h = (n - 1) p, lo = floor(h), g = h - lo;  the value is x[lo] when g == 0, else x[lo] + (x[lo+1] - x[lo]) g
+ * with a separately rounded multiply and add (no fused multiply-add) - numpy.quantile's "linear" method up to the form of the
+ * interpolation. n == 0 gives 0.0.
+ * RANKS are 1-based, ties get the average rank (multiples of 0.5: exact); -0.0 and +0.0 tie.
+ * CORRELATION with the inputs X[K][P] (one row per member: a log-multiplier of a rate constant, a temperature, a heating rate,
+ * a u0 entry ...), for every row j, selected species i and input p, over the participants' y = u[m][j][i] and x = X[m][p]:
+ *   r = sum (x - xbar)(y - ybar) / sqrt(sum (x - xbar)^2 sum (y - ybar)^2)
+ * rank != 0: both sides are replaced by their ranks among the participants (Spearman's coefficient). r is exactly 0.0 where
+ * either sum of squares is 0 or n < 2, never NaN or Inf for finite inputs (sums of squares that under- or overflow the double
+ * range count as 0 / Inf: value correlations of subnormal columns come out 0.0; rank correlations have no such limit).
+ * NON-FINITE VALUES: a NaN among the participating values of a (row, species) makes every statistic of that (row, species)
+ * NaN; +-Inf sort as the extremes they are and otherwise follow IEEE arithmetic (a mean of Inf, a NaN variance).
+ *
+ * How it is computed, and the order of every sum (member_stats.hpp): the moments in one launch, lanes along the species, the
+ * participants split over the eight wavefronts of a workgroup (wave w adds q = w, w + 8, ... in order, the eight partial sums
+ * are added in the order of w). The selected columns (j, i) are gathered tile by tile into LDS and sorted there; quantiles
+ * come from the sorted column, ranks from two binary searches in it. A correlation is out[j][i][p] = sum over the
+ * participants, in order, of Xhat[q][p] Yhat[(j, i)][q], with Xhat = (x - xbar) / sqrt(sum (x - xbar)^2) (or the same of the
+ * ranks) from kin_members_inputs_host and Yhat the same of y, written by the column pass to a workspace of at most 256 MB;
+ * larger requests are cut into blocks of columns (KIN_MEMBERS_BLOCK_COLUMNS=n forces blocks of at most n columns). Every
+ * statistic is a function of its own column with one fixed order of operations: results are bit-identical from call to
+ * call, between a kin_ensemble_* entry and the kin_members_* entry fed the downloaded states, and under any blocking.
+ * The sorted passes (quantiles, rank correlation) take at most KIN_MEMBERS_MAX_SORTED participants (KIN_ERR_UNSUPPORTED
+ * beyond, with the limit in the message); moments and value correlations have no limit on K.
+ *
+ * species[n_sel]: the selected species in the index base the handle was created with (kin_network_create's index_base);
+ * NULL: all N (n_sel is ignored). Statuses: KIN_ERR_INVALID_ARG for K, L, n_sel, Q or P < 0, a species outside the network,
+ * a null u with K L > 0, a null output (moments: every output null), a null p with Q > 0 or X with P > 0;
+ * KIN_ERR_STATE from the kin_ensemble_* entries without a stored ensemble. In the _dev entries u and the outputs are device
+ * pointers and the call only enqueues on `stream` (NULL: the handle's) once the workspace has its size; use, species, p, X
+ * and count are HOST pointers, read (count: written) before the call returns. One stream per handle at a time. Added under
+ * KIN_ABI_VERSION 6: look the symbols up before calling them. */
+#define KIN_MEMBERS_MAX_SORTED 4096
+/* The inputs' side of a correlation, on the host (no handle, no device): *n = the participants, Xhat[q][p] for the q-th
+ * participant in member order = (x - xbar) / sqrt(sum (x - xbar)^2) of input p over the participants, x replaced by its
+ * average-tie rank when rank != 0; a column whose sum of squares is 0, and any column for n < 2, gives zeros; a column
+ * holding a NaN gives NaNs. Sums are carried in extended precision: the values are within a few ulp of the exact ones.
+ * Xhat may be NULL (only *n is wanted); K or P < 0, a null X with K P > 0: KIN_ERR_INVALID_ARG. */
+int kin_members_inputs_host(int64_t K, int64_t P, const double* X /* [K][P] */, const int32_t* use /* [K] or NULL */, int rank,
+                            int64_t* n, double* Xhat /* [n][P] (at most [K][P]) or NULL */);
+int kin_members_moments(kin_network* h, int64_t K, int64_t L, const double* u /* [K][L][N] */, const int32_t* use, int64_t* count,
+                        double* mean, double* var, double* min, double* max /* [L][N] each; any may be NULL, not all five */);
+int kin_members_moments_dev(kin_network* h, int64_t K, int64_t L, const double* d_u, const int32_t* use, int64_t* count, double* d_mean,
+                            double* d_var, double* d_min, double* d_max, void* stream);
+int kin_members_quantiles(kin_network* h, int64_t K, int64_t L, const double* u, const int32_t* use, const int64_t* species,
+                          int64_t n_sel, const double* p /* [Q] */, int64_t Q, double* out /* [Q][L][n_sel] */);
+int kin_members_quantiles_dev(kin_network* h, int64_t K, int64_t L, const double* d_u, const int32_t* use, const int64_t* species,
+                              int64_t n_sel, const double* p, int64_t Q, double* d_out, void* stream);
+int kin_members_correlate(kin_network* h, int64_t K, int64_t L, const double* u, const int32_t* use, const int64_t* species,
+                          int64_t n_sel, const double* X /* [K][P] */, int64_t P, int rank, double* out /* [L][n_sel][P] */);
+int kin_members_correlate_dev(kin_network* h, int64_t K, int64_t L, const double* d_u, const int32_t* use, const int64_t* species,
+                              int64_t n_sel, const double* X, int64_t P, int rank, double* d_out, void* stream);
+/* The same over the stored ensemble, read where it lives (K, L = n_rows of kin_ensemble_size); host outputs. */
+int kin_ensemble_moments(kin_network* h, const int32_t* use, int64_t* count, double* mean, double* var, double* min, double* max);
+int kin_ensemble_quantiles(kin_network* h, const int32_t* use, const int64_t* species, int64_t n_sel, const double* p, int64_t Q,
+                           double* out /* [Q][n_rows][n_sel] */);
+int kin_ensemble_correlate(kin_network* h, const int32_t* use, const int64_t* species, int64_t n_sel, const double* X /* [K][P] */,
+                           int64_t P, int rank, double* out /* [n_rows][n_sel][P] */);
+
 /* ---- device / build information ------------------------------------------------------- */
 int kin_device_count(int* n);
 /* Selects the device for handles created afterwards by this thread; a handle remembers the device it was created on
@@ -874,7 +949,8 @@ const char* kin_version(void);
  * later under 6, found by symbol lookup; so did DRGEP: kin_drgep_*, kin_solution_drgep, kin_ensemble_drgep, and the timescale analysis:
  * kin_jac_batched*, kin_timescale_*, kin_solution_timescale, kin_ensemble_timescale, and path flux analysis: kin_pfa_*,
  * kin_solution_pfa, kin_ensemble_pfa, and reaction elimination: kin_reaction_importance_*, kin_solution_reaction_importance,
- * kin_ensemble_reaction_importance). */
+ * kin_ensemble_reaction_importance, and the cross-member statistics: kin_members_*, kin_ensemble_moments / _quantiles /
+ * _correlate). */
 #define KIN_ABI_VERSION 6
 int kin_abi_version(void);
 int64_t kin_struct_size(int which); /* 0: sizeof(kin_params), 1: sizeof(kin_stats), else -1 */

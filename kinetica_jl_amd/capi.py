@@ -41,11 +41,14 @@ SYMBOLS = [
     "kin_solution_reaction_importance", "kin_ensemble_reaction_importance",
     "kin_jac_batched", "kin_jac_batched_dev", "kin_timescale_batched", "kin_timescale_batched_dev", "kin_solution_timescale",
     "kin_ensemble_timescale", "kin_timescale_plan_host",
+    "kin_members_inputs_host", "kin_members_moments", "kin_members_moments_dev", "kin_members_quantiles", "kin_members_quantiles_dev",
+    "kin_members_correlate", "kin_members_correlate_dev", "kin_ensemble_moments", "kin_ensemble_quantiles", "kin_ensemble_correlate",
     "kin_flux_plan_host", "kin_network_compute_units",
     "kin_sweep_plan", "kin_sweep_plan_host", "kin_tiled_sweep_plan", "kin_tiled_sweep_plan_host",
 ]
 # in-degree classes of the DRGEP path search (drg.hpp: IN_SHORT_MAX, IN_WAVE_MAX): a lane, a wavefront, the workgroup
 DRGEP_IN_SHORT_MAX, DRGEP_IN_WAVE_MAX = 32, 256
+MEMBERS_MAX_SORTED = 4096   # include/kinetica_hip.h: KIN_MEMBERS_MAX_SORTED, the participants quantiles and rank correlations take
 ABI_VERSION = 6   # include/kinetica_hip.h: KIN_ABI_VERSION this binding was written against
 
 
@@ -208,6 +211,19 @@ def lib():
             L.kin_solution_timescale.argtypes = [c_void_p, PD, c_int64, P64, PD, c_int64, c_int, PD, PD]
             L.kin_ensemble_timescale.argtypes = [c_void_p, PD, c_int64, P64, PD, c_int64, c_int, PD, PD]
             L.kin_timescale_plan_host.argtypes = [c_int64, c_int64] + [P64] * 6 + [c_int, P64]
+        if hasattr(L, "kin_members_moments"):   # (also under ABI 6: cross-member statistics)
+            P32 = POINTER(c_int32)
+            L.kin_members_inputs_host.argtypes = [c_int64, c_int64, PD, P32, c_int, P64, PD]
+            L.kin_members_moments.argtypes = [c_void_p, c_int64, c_int64, PD, P32, P64, PD, PD, PD, PD]
+            L.kin_members_moments_dev.argtypes = [c_void_p, c_int64, c_int64, c_void_p, P32, P64] + [c_void_p] * 5
+            L.kin_members_quantiles.argtypes = [c_void_p, c_int64, c_int64, PD, P32, P64, c_int64, PD, c_int64, PD]
+            L.kin_members_quantiles_dev.argtypes = [c_void_p, c_int64, c_int64, c_void_p, P32, P64, c_int64, PD, c_int64, c_void_p, c_void_p]
+            L.kin_members_correlate.argtypes = [c_void_p, c_int64, c_int64, PD, P32, P64, c_int64, PD, c_int64, c_int, PD]
+            L.kin_members_correlate_dev.argtypes = [c_void_p, c_int64, c_int64, c_void_p, P32, P64, c_int64, PD, c_int64, c_int, c_void_p,
+                                                    c_void_p]
+            L.kin_ensemble_moments.argtypes = [c_void_p, P32, P64, PD, PD, PD, PD]
+            L.kin_ensemble_quantiles.argtypes = [c_void_p, P32, P64, c_int64, PD, c_int64, PD]
+            L.kin_ensemble_correlate.argtypes = [c_void_p, P32, P64, c_int64, PD, c_int64, c_int, PD]
         if hasattr(L, "kin_sweep_plan"):   # (also under ABI 6: the plan queries of the two batched sweeps)
             L.kin_sweep_plan.argtypes = [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, P64]
             L.kin_sweep_plan_host.argtypes = [c_int64, c_int64] + [P64] * 6 + [c_int, c_int, c_int64, c_int, c_int, c_int, P64]
@@ -247,6 +263,37 @@ def _p64(a):
 
 def _f64(a):
     return np.ascontiguousarray(a, dtype=np.float64)
+
+
+def _p32(a):
+    return None if a is None else a.ctypes.data_as(POINTER(c_int32))
+
+
+def _use32(use, K):
+    """A participant mask as the kin_members_* / kin_ensemble_* entries take it: int32[K] (truthy: takes part) or None."""
+    if use is None:
+        return None
+    use = np.ascontiguousarray(np.asarray(use).ravel() != 0, dtype=np.int32)
+    if len(use) != K:
+        raise ValueError(f"use must have one entry per member ({K}); got {len(use)}")
+    return use
+
+
+def members_inputs(X, use=None, rank=True):
+    """kin_members_inputs_host (no handle, no device): the inputs' side of a correlation. X[K][P], one row per member; returns
+    (n, Xhat[n][P]): per input the participants' (x - mean) / sqrt(sum (x - mean)^2) in member order, of the average-tie ranks when
+    rank; zeros for a column without spread or n < 2."""
+    X = np.ascontiguousarray(_f64(X))
+    if X.ndim != 2:
+        raise ValueError(f"inputs must be [K][P] (one row per member); got {X.shape}")
+    K, P = X.shape
+    use = _use32(use, K)
+    n = c_int64(0)
+    out = np.zeros((max(K, 1), max(P, 1)))
+    st = lib().kin_members_inputs_host(K, P, _pd(X), _p32(use), int(bool(rank)), ctypes.byref(n), _pd(out))
+    if st != KIN_OK:
+        raise KineticaHipError(st, "kin_members_inputs_host: invalid argument")
+    return n.value, out.ravel()[:n.value * P].reshape(n.value, P).copy()
 
 
 def device_count():
@@ -1052,6 +1099,130 @@ class HipNetwork:
         self._chk(lib().kin_ensemble_timescale(self._h, _pd(k), n_rows, None if k_row is None else _p64(k_row), _pd(T_rows),
                                                int(row_begin), acc, _pd(out), _pd(norm)))
         return out, norm
+
+    # --- cross-member statistics ------------------------------------------------------------------
+    def _ms_species(self, species):
+        """(species int64 or None, n_sel as the C entries take it, number of selected species)."""
+        if species is None:
+            return None, 0, self.n
+        sp = np.ascontiguousarray(np.asarray(species, dtype=np.int64).ravel())
+        ns = len(sp)
+        return (sp if ns else np.zeros(1, np.int64)), ns, ns      # (an empty list stays a list, not "all species")
+
+    @staticmethod
+    def _ms_block(u, n_species):
+        u = np.ascontiguousarray(_f64(u))
+        if u.ndim != 3 or u.shape[2] != n_species:
+            raise ValueError(f"u must be [K][L][{n_species}] (member, row, species); got {u.shape}")
+        return u, u.shape[0], u.shape[1]
+
+    @staticmethod
+    def _ms_moment_buffers(L, N, want):
+        names = ("mean", "var", "min", "max")
+        bad = [w for w in want if w not in names + ("count",)]
+        if bad:
+            raise ValueError(f"unknown moments {bad}; choose among {names + ('count',)}")
+        return {w: np.empty((L, N)) for w in names if w in want}
+
+    def members_moments(self, u, use=None, want=("count", "mean", "var", "min", "max")):
+        """kin_members_moments over a block u[K][L][N] on the host: dict of count (int) and mean / var / min / max [L][N] over the
+        members use[m] != 0 (None: all), those `want` names (include/kinetica_hip.h has the definitions)."""
+        u, K, L = self._ms_block(u, self.n)
+        use = _use32(use, K)
+        out = self._ms_moment_buffers(L, self.n, want)
+        cnt = c_int64(0)
+        self._chk(lib().kin_members_moments(self._h, K, L, _pd(u), _p32(use), ctypes.byref(cnt), *[_pd(out.get(w)) for w in ("mean", "var", "min", "max")]))
+        if "count" in want:
+            out["count"] = cnt.value
+        return out
+
+    def members_moments_dev(self, K, L, d_u, use=None, d_mean=0, d_var=0, d_min=0, d_max=0, stream=0):
+        """kin_members_moments_dev: device pointers (ints; 0 = not wanted) u[K][L][N] and mean / var / min / max [L][N]; `use` is a
+        host mask. Only enqueues; returns the number of participants."""
+        p = lambda x: c_void_p(x) if x else None
+        use = _use32(use, K)
+        cnt = c_int64(0)
+        self._chk(lib().kin_members_moments_dev(self._h, int(K), int(L), p(d_u), _p32(use), ctypes.byref(cnt), p(d_mean), p(d_var), p(d_min),
+                                                p(d_max), p(stream)))
+        return cnt.value
+
+    def ensemble_moments(self, use=None, want=("count", "mean", "var", "min", "max")):
+        """kin_ensemble_moments: members_moments over the stored ensemble, read where it lives (use None: the members that
+        completed the save grid)."""
+        K, L = self.ensemble_size()[:2]
+        use = _use32(use, K)
+        out = self._ms_moment_buffers(L, self.n, want)
+        cnt = c_int64(0)
+        self._chk(lib().kin_ensemble_moments(self._h, _p32(use), ctypes.byref(cnt), *[_pd(out.get(w)) for w in ("mean", "var", "min", "max")]))
+        if "count" in want:
+            out["count"] = cnt.value
+        return out
+
+    def members_quantiles(self, u, p, species=None, use=None):
+        """kin_members_quantiles: out[Q][L][n_sel], the quantiles p[Q] (in [0, 1]) over the participants of the selected species
+        (ids in the handle's index base; None: all N) at every row."""
+        u, K, L = self._ms_block(u, self.n)
+        use = _use32(use, K)
+        p = np.ascontiguousarray(np.atleast_1d(_f64(p)))
+        sp, ns, nsel = self._ms_species(species)
+        out = np.empty((len(p), L, nsel))
+        self._chk(lib().kin_members_quantiles(self._h, K, L, _pd(u), _p32(use), None if sp is None else _p64(sp), ns, _pd(p), len(p), _pd(out)))
+        return out
+
+    def members_quantiles_dev(self, K, L, d_u, p, d_out, species=None, use=None, stream=0):
+        """kin_members_quantiles_dev: device pointers u[K][L][N] and out[Q][L][n_sel]; p, species and use are host arrays."""
+        use = _use32(use, K)
+        p = np.ascontiguousarray(np.atleast_1d(_f64(p)))
+        sp, ns, _ = self._ms_species(species)
+        self._chk(lib().kin_members_quantiles_dev(self._h, int(K), int(L), c_void_p(d_u), _p32(use), None if sp is None else _p64(sp), ns,
+                                                  _pd(p), len(p), c_void_p(d_out), c_void_p(stream) if stream else None))
+
+    def ensemble_quantiles(self, p, species=None, use=None):
+        """kin_ensemble_quantiles: members_quantiles over the stored ensemble, out[Q][n_rows][n_sel]."""
+        K, L = self.ensemble_size()[:2]
+        use = _use32(use, K)
+        p = np.ascontiguousarray(np.atleast_1d(_f64(p)))
+        sp, ns, nsel = self._ms_species(species)
+        out = np.empty((len(p), L, nsel))
+        self._chk(lib().kin_ensemble_quantiles(self._h, _p32(use), None if sp is None else _p64(sp), ns, _pd(p), len(p), _pd(out)))
+        return out
+
+    @staticmethod
+    def _ms_inputs(X, K):
+        X = np.ascontiguousarray(_f64(X))
+        if X.ndim != 2 or X.shape[0] != K:
+            raise ValueError(f"inputs must be [K = {K}][P] (one row per member); got {X.shape}")
+        return X, X.shape[1]
+
+    def members_correlate(self, u, X, species=None, rank=True, use=None):
+        """kin_members_correlate: out[L][n_sel][P], the correlation of input X[:, p] (X[K][P], one row per member) with the selected
+        species at every row over the participants: Spearman's coefficient (rank=True) or Pearson's."""
+        u, K, L = self._ms_block(u, self.n)
+        use = _use32(use, K)
+        X, P = self._ms_inputs(X, K)
+        sp, ns, nsel = self._ms_species(species)
+        out = np.empty((L, nsel, P))
+        self._chk(lib().kin_members_correlate(self._h, K, L, _pd(u), _p32(use), None if sp is None else _p64(sp), ns, _pd(X), P,
+                                              int(bool(rank)), _pd(out)))
+        return out
+
+    def members_correlate_dev(self, K, L, d_u, X, d_out, species=None, rank=True, use=None, stream=0):
+        """kin_members_correlate_dev: device pointers u[K][L][N] and out[L][n_sel][P]; X, species and use are host arrays."""
+        use = _use32(use, K)
+        X, P = self._ms_inputs(X, K)
+        sp, ns, _ = self._ms_species(species)
+        self._chk(lib().kin_members_correlate_dev(self._h, int(K), int(L), c_void_p(d_u), _p32(use), None if sp is None else _p64(sp), ns,
+                                                  _pd(X), P, int(bool(rank)), c_void_p(d_out), c_void_p(stream) if stream else None))
+
+    def ensemble_correlate(self, X, species=None, rank=True, use=None):
+        """kin_ensemble_correlate: members_correlate over the stored ensemble, out[n_rows][n_sel][P]."""
+        K, L = self.ensemble_size()[:2]
+        use = _use32(use, K)
+        X, P = self._ms_inputs(X, K)
+        sp, ns, nsel = self._ms_species(species)
+        out = np.empty((L, nsel, P))
+        self._chk(lib().kin_ensemble_correlate(self._h, _p32(use), None if sp is None else _p64(sp), ns, _pd(X), P, int(bool(rank)), _pd(out)))
+        return out
 
     # --- library order (tiled sweep) --------------------------------------------------------
     def lib_layout(self):

@@ -118,6 +118,7 @@ int kin_network_create(int64_t n_species, int64_t n_reactions, const int64_t* re
       throw KinError(ERR_DEVICE, "no HIP device available (libkinetica_hip has no CPU fallback)");
     h = new kin_network();
     h->host = std::move(H);
+    h->index_base = index_base;
     KIN_HIP(hipGetDevice(&h->device));
     KIN_HIP(hipDeviceGetAttribute(&h->n_cu, hipDeviceAttributeMultiprocessorCount, h->device));
     KIN_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));

@@ -159,6 +159,16 @@ struct kin_network {
     ens.sol = sol; ens.K = K; ens.cap = cap; ens.n_saved = std::move(n_saved);
   }
 
+  // cross-member statistics (member_stats.hpp, member_stats_api.cpp): the index base kin_network_create was given (species
+  // lists of these entries are in it); the participants, the selected species, the probabilities and the normalised inputs
+  // on the device with the host copies the uploads read; the workspace Yhat[columns][n] of a block of columns; the staging
+  // buffers of the host entries' states and outputs
+  int index_base = 0;
+  std::vector<int32_t> ms_h_idx, ms_h_sel;
+  std::vector<double> ms_h_p, ms_h_xhat;
+  kin::DevBuf<int32_t> ms_idx, ms_sel;
+  kin::DevBuf<double> ms_p, ms_xhat, ms_yhat, ms_u, ms_o[4];
+
   kin_network();
   ~kin_network();
   void rhs_dev(const double* d_u, double* d_du);        // du = f(u) with current k

@@ -28,7 +28,8 @@ __all__ = ["SpeciesData", "RxData", "RxFilter", "get_filter_mask", "DummyKinetic
            "HIPBDF", "HIPRK45", "ArrheniusRates", "solve_network", "identify_next_seeds", "insert_inert", "ODESolveOutput", "ODESolution", "tconvert", "make_u0", "apply_low_k_cutoff",
            "get_max_rates", "get_initial_rates", "calculate_discrete_rates",
            "solve_network_ensemble",   # EXTENSION: the reference has no ensemble call
-           "flux_weights", "held_stop_index", "ReactionFluxes", "reaction_fluxes", "ensemble_flux_sources"]   # EXTENSION: post-hoc flux analysis
+           "flux_weights", "held_stop_index", "ReactionFluxes", "reaction_fluxes", "ensemble_flux_sources",   # EXTENSION: post-hoc flux analysis
+           "EnsembleStatistics", "ensemble_statistics"]   # EXTENSION: statistics across the members of an ensemble
 
 _T_UNIT = {  # src/utils.jl:77-97
     "picoseconds": 1.0e-12, "ps": 1.0e-12, "nanoseconds": 1.0e-9, "ns": 1.0e-9, "microseconds": 1.0e-6, "us": 1.0e-6,
@@ -463,6 +464,7 @@ class ODESolution:
     stats: dict = field(default_factory=dict)
     umax: Optional[np.ndarray] = None    # max over saved times per species, reduced on the device (kin_solution_max)
     fluxes: Optional[object] = None      # ReactionFluxes of the solve (solve_network_ensemble(fluxes=True)), else None
+    ensemble_stats: Optional[object] = None   # the ensemble's one EnsembleStatistics (solve_network_ensemble(statistics=...)), else None
 
     def __call__(self, tq):
         """Linear interpolation res.sol(t) (docs/src/getting-started.md:232-236)."""
@@ -720,7 +722,7 @@ def apply_ensemble_low_k_cutoff(rd, calc, pars, condition_sets):
     return rids
 
 
-def solve_network_ensemble(methods, sd, rd, copy_network=True, fluxes=False, trajectories=True):
+def solve_network_ensemble(methods, sd, rd, copy_network=True, fluxes=False, trajectories=True, statistics=None):
     """EXTENSION (the reference has no ensemble call: it solves member after member through solve_network): K
     `VariableODESolve`s with Arrhenius condition sets - one temperature profile each, e.g. a set of heating rates or start
     temperatures - on one network in ONE ensemble call: kin_solve_ensemble_continuous when every set is continuous,
@@ -745,10 +747,17 @@ def solve_network_ensemble(methods, sd, rd, copy_network=True, fluxes=False, tra
     weights over the member's own saved times and the rate constants the solve held there - from ONE segmented pass over the
     members' states where they live on the device (kin_ensemble_flux), before the handle closes. trajectories=False: no
     state is downloaded; sol.u is None, sol.t the member's saved times, sol.umax kin_ensemble_max's. With the defaults the
-    function does what it did before either existed."""
+    function does what it did before either existed.
+
+    statistics=True or a dict of ensemble_statistics' keyword arguments (quantiles, species, inputs, rank, use; species are
+    0-based ids of the network as it is solved, inputs[K][P] one row per method): every member's sol.ensemble_stats refers to
+    ONE shared EnsembleStatistics over the members that completed the save grid, computed from the states where they live on
+    the device before the handle closes (with trajectories=False no state is downloaded). A malformed `statistics` raises
+    ValueError before anything touches the GPU. None (the default): nothing is computed."""
     methods = list(methods)
     if not methods:
         raise ValueError("solve_network_ensemble needs at least one method")
+    stat_kw = _statistics_arguments(statistics, len(methods))
     m0 = methods[0]
     for m in methods:
         if not isinstance(m, VariableODESolve) or not isinstance(m.calculator, PrecalculatedArrheniusCalculator):
@@ -785,6 +794,8 @@ def solve_network_ensemble(methods, sd, rd, copy_network=True, fluxes=False, tra
             m.calculator.splice(rids)
             spliced.append(m.calculator)
     U0 = np.array([make_u0(sd_a, m.pars) for m in methods])
+    if stat_kw is not None and stat_kw["species"] is not None and stat_kw["species"].max(initial=-1) >= sd_a.n:
+        raise ValueError(f"statistics: species ids must be below the {sd_a.n} species of the network as it is solved")
     if discrete:
         # each member's (tstops, T(tstops)), as solve_network hands them to kin_solve
         stops = [discrete_stop_temperatures(m.conditions) for m in methods]
@@ -810,6 +821,11 @@ def solve_network_ensemble(methods, sd, rd, copy_network=True, fluxes=False, tra
             src = ensemble_flux_sources("discrete_members", t, ns, stops=stops) if discrete else \
                 ensemble_flux_sources("continuous", t, ns, nodes=nodes)
             F = h.ensemble_flux(w=src["w"], T_rows=src["T_rows"])
+        stats = None
+        if stat_kw is not None:
+            sp0 = stat_kw["species"]
+            stats = ensemble_statistics(h, t, **dict(stat_kw, species=None if sp0 is None else sp0 + 1))   # (the handle's base is 1)
+            stats.species = sp0
     finally:
         h.close()
     out = []
@@ -832,8 +848,103 @@ def solve_network_ensemble(methods, sd, rd, copy_network=True, fluxes=False, tra
             umax = dev_umax[i]
         fl = None if F is None else ReactionFluxes.from_flux(F[i], rd_a, sd_a.n, src["w"][i, :n_i])
         sol = ODESolution(ti, ui, capi.RETCODE_NAMES[int(rcs[i])], k=sol_k, stats=st, umax=umax, fluxes=fl)
+        if stat_kw is not None:
+            sol.ensemble_stats = stats
         out.append(ODESolveOutput(sd_a, rd_a, sol, sol_k, sol_vcs, m.pars, m.conditions))
     return out
+
+
+# ---- statistics across the members of an ensemble (EXTENSION) -------------------------------------------------------------
+@dataclass
+class EnsembleStatistics:
+    """Result of ensemble_statistics: what the members of an ensemble say together. Over the n = count participants, per row j
+    of the save grid t and species i: mean, var (unbiased), min, max [n_rows][N]; quantiles[Q][n_rows][n_sel] at the
+    probabilities p[Q] for the selected `species` (None: all; ids as the caller gave them); corr[n_rows][n_sel][P], the
+    correlation of each sampled input with each selected species - Spearman's coefficient when `rank`, else Pearson's - or
+    None when no inputs were given (include/kinetica_hip.h has every definition)."""
+    t: np.ndarray
+    count: int
+    mean: np.ndarray
+    var: np.ndarray
+    min: np.ndarray
+    max: np.ndarray
+    quantiles: Optional[np.ndarray] = None
+    p: Optional[np.ndarray] = None
+    species: Optional[np.ndarray] = None
+    corr: Optional[np.ndarray] = None
+    rank: bool = True
+
+    @property
+    def std(self):
+        return np.sqrt(self.var)
+
+    def envelope(self, lo=0.05, hi=0.95):
+        """(quantiles at lo, at hi), both [n_rows][n_sel]; the probabilities must be among p (ValueError otherwise)."""
+        out = []
+        for q in (lo, hi):
+            at = np.nonzero(self.p == q)[0] if self.p is not None else []
+            if len(at) == 0:
+                raise ValueError(f"probability {q} is not among the computed quantiles {None if self.p is None else list(self.p)}")
+            out.append(self.quantiles[at[0]])
+        return tuple(out)
+
+
+def _statistics_arguments(statistics, K):
+    """solve_network_ensemble's `statistics` as keyword arguments of ensemble_statistics (None: no statistics); ValueError for
+    anything malformed - nothing here touches the device."""
+    if statistics is None or statistics is False:
+        return None
+    if statistics is True:
+        statistics = {}
+    if not isinstance(statistics, dict):
+        raise ValueError("statistics must be None, True or a dict of ensemble_statistics' keyword arguments")
+    known = ("quantiles", "species", "inputs", "rank", "use")
+    bad = [k for k in statistics if k not in known]
+    if bad:
+        raise ValueError(f"statistics: unknown keys {bad}; choose among {known}")
+    kw = dict(quantiles=(0.05, 0.5, 0.95), species=None, inputs=None, rank=True, use=None)
+    kw.update(statistics)
+    try:
+        q = np.atleast_1d(np.asarray(() if kw["quantiles"] is None else kw["quantiles"], dtype=float))
+    except (TypeError, ValueError):
+        raise ValueError("statistics: quantiles must be numbers in [0, 1]") from None
+    if q.ndim != 1 or not np.all((q >= 0.0) & (q <= 1.0)):
+        raise ValueError("statistics: quantiles must be numbers in [0, 1]")
+    kw["quantiles"] = q
+    if kw["species"] is not None:
+        sp = np.asarray(kw["species"])
+        if sp.ndim != 1 or sp.dtype.kind not in "iu" or (sp < 0).any():
+            raise ValueError("statistics: species must be a list of 0-based integer ids")
+        kw["species"] = sp.astype(np.int64)
+    if kw["inputs"] is not None:
+        try:
+            X = np.asarray(kw["inputs"], dtype=float)
+        except (TypeError, ValueError):
+            raise ValueError("statistics: inputs must be a [K][P] array of numbers") from None
+        if X.ndim != 2 or X.shape[0] != K:
+            raise ValueError(f"statistics: inputs must be [K][P] with one row per method ({K}); got {X.shape}")
+        kw["inputs"] = X
+    if kw["use"] is not None:
+        use = np.asarray(kw["use"])
+        if use.shape != (K,):
+            raise ValueError(f"statistics: use must have one entry per method ({K})")
+    kw["rank"] = bool(kw["rank"])
+    return kw
+
+
+def ensemble_statistics(h, t, quantiles=(0.05, 0.5, 0.95), species=None, inputs=None, rank=True, use=None):
+    """Statistics across the members of the ensemble stored in the handle `h` (a capi.HipNetwork after a solve_ensemble* call,
+    trajectories downloaded or not), read where the states live on the device: kin_ensemble_moments, kin_ensemble_quantiles
+    (quantiles: probabilities in [0, 1]; None or empty: none) and, with inputs[K][P] (one row per member: whatever was sampled -
+    log-multipliers of rate constants, temperatures, heating rates, u0 entries), kin_ensemble_correlate. species: ids in the
+    handle's index base, None for all. use: a mask over the members, None for those that completed the save grid `t`."""
+    m = h.ensemble_moments(use=use)
+    p = np.atleast_1d(np.asarray(() if quantiles is None else quantiles, dtype=float))
+    sp = None if species is None else np.asarray(species, dtype=np.int64)
+    qv = h.ensemble_quantiles(p, species=sp, use=use) if len(p) else None
+    corr = None if inputs is None else h.ensemble_correlate(inputs, species=sp, rank=rank, use=use)
+    return EnsembleStatistics(np.asarray(t, dtype=float), m["count"], m["mean"], m["var"], m["min"], m["max"], quantiles=qv,
+                              p=p if len(p) else None, species=sp, corr=corr, rank=bool(rank))
 
 
 # ---- post-hoc reaction-flux analysis (EXTENSION, in the style of the reference's analysis/: works on an ODESolveOutput) ----

@@ -933,6 +933,53 @@ int kin_ensemble_quantiles(kin_network* h, const int32_t* use, const int64_t* sp
 int kin_ensemble_correlate(kin_network* h, const int32_t* use, const int64_t* species, int64_t n_sel, const double* X /* [K][P] */,
                            int64_t P, int rank, double* out /* [n_rows][n_sel][P] */);
 
+/* ---- Sobol sensitivity indices across the members of a Saltelli design ------------------------------------------------------ */
+/* A correlation measures monotone, additive influence. The variance-based indices answer what a Monte-Carlo run over uncertain
+ * inputs is set up for: how much of the variance of species i at time t does input p carry alone (first order, S1) and with
+ * its interactions (total effect, ST).
+ *
+ * DESIGN LAYOUT. K = M (P + 2) members, M >= 1 base samples, P >= 1 inputs. Member b M + m is sample m of block b: block 0 is
+ * A, block 1 is B, block 2 + p is AB_p - A with input p taken from B. For one column (row j, species i) a_m, b_m and c_pm are
+ * the values of sample m in A, B and AB_p.
+ *
+ * WEIGHTS. w[M] is int32: values >= 0 are multiplicities - 0: the sample takes no part, above 1: a bootstrap replicate; a
+ * negative entry is KIN_ERR_INVALID_ARG. w == NULL: all ones (kin_members_sobol*); over the stored ensemble 1 where all P + 2
+ * members of sample m completed the save grid (n_saved == n_rows), else 0, and w[m] != 0 for a sample with an incomplete
+ * member is KIN_ERR_INVALID_ARG (rows past n_saved are never read). The participants are the samples with w > 0, always
+ * visited in ascending m; n = sum w.
+ *
+ * QUANTITIES per column, sums over the participants:
+ *   mu   = (sum w a + sum w b) / (2 n)
+ *   V    = (sum w (a - mu)^2 + sum w (b - mu)^2) / (2 n)      the population variance over A u B (Saltelli et al. 2010)
+ *   S1_p = (sum w (b - mu)(c_p - a) / n) / V                  (Saltelli et al. 2010)
+ *   ST_p = (sum w (a - c_p)^2 / (2 n)) / V                    (Jansen 1999)
+ * EDGE RULES. n < 2 or V == 0 gives exactly 0.0 for S1 and ST; V is exactly 0.0 for a column whose participating a and b are
+ * all equal (whatever the sum of n equal values rounds to). n == 0 writes zeros everywhere, mu and V included. Otherwise IEEE
+ * arithmetic: a NaN in a participating a or b makes the column's mu, V and every S1_p, ST_p NaN (n >= 2), a NaN in c_p that
+ * p's two values (V != 0); never NaN or Inf for finite inputs with V > 0 short of overflow. Squares that
+ * underflow the double range count as 0, as for the correlations: a column of values near 1e-160 or below has V == 0.
+ *
+ * How it is computed, and the order of every sum (member_stats.hpp): one launch, lanes along the species, the participants
+ * split over the eight wavefronts of a workgroup (wave w adds q = w, w + 8, ... in order, the partials are added in the order
+ * of w); mu first, then the centred sums by fused multiply-add; the weight enters as one multiplication, exact for w = 1; P is
+ * taken eight inputs per workgroup. Results are bit-identical from call to call, between kin_ensemble_sobol and
+ * kin_members_sobol fed the downloaded states, and a 0/1 weight vector gives the bits of the call on the block with the
+ * dropped samples removed.
+ *
+ * Outputs S1, ST [L][n_sel][P], mean (mu), var (V) [L][n_sel]; any may be NULL, not all four. species as above. Statuses as
+ * kin_members_correlate: KIN_ERR_INVALID_ARG for M or P < 1, L or n_sel < 0, a negative weight, a species outside the
+ * network, a null u with L N > 0, every output null, and from kin_ensemble_sobol a stored K != M (P + 2);
+ * KIN_ERR_UNSUPPORTED for M (P + 2) >= 2^31; KIN_ERR_STATE from kin_ensemble_sobol without a stored ensemble. In the _dev
+ * entry u and the outputs are device pointers and the call only enqueues on `stream`; w and species are HOST pointers read
+ * before it returns. Added under KIN_ABI_VERSION 6: look the symbols up before calling them. */
+int kin_members_sobol(kin_network* h, int64_t M, int64_t P, int64_t L, const double* u /* [M (P + 2)][L][N] */,
+                      const int32_t* w /* [M] or NULL */, const int64_t* species, int64_t n_sel, double* S1, double* ST,
+                      double* mean, double* var);
+int kin_members_sobol_dev(kin_network* h, int64_t M, int64_t P, int64_t L, const double* d_u, const int32_t* w, const int64_t* species,
+                          int64_t n_sel, double* d_S1, double* d_ST, double* d_mean, double* d_var, void* stream);
+int kin_ensemble_sobol(kin_network* h, int64_t M, int64_t P, const int32_t* w, const int64_t* species, int64_t n_sel, double* S1,
+                       double* ST, double* mean, double* var /* L = n_rows */);
+
 /* ---- device / build information ------------------------------------------------------- */
 int kin_device_count(int* n);
 /* Selects the device for handles created afterwards by this thread; a handle remembers the device it was created on
@@ -950,7 +997,7 @@ const char* kin_version(void);
  * kin_jac_batched*, kin_timescale_*, kin_solution_timescale, kin_ensemble_timescale, and path flux analysis: kin_pfa_*,
  * kin_solution_pfa, kin_ensemble_pfa, and reaction elimination: kin_reaction_importance_*, kin_solution_reaction_importance,
  * kin_ensemble_reaction_importance, and the cross-member statistics: kin_members_*, kin_ensemble_moments / _quantiles /
- * _correlate). */
+ * _correlate, and the Sobol indices: kin_members_sobol, kin_members_sobol_dev, kin_ensemble_sobol). */
 #define KIN_ABI_VERSION 6
 int kin_abi_version(void);
 int64_t kin_struct_size(int which); /* 0: sizeof(kin_params), 1: sizeof(kin_stats), else -1 */

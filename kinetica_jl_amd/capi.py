@@ -43,6 +43,7 @@ SYMBOLS = [
     "kin_ensemble_timescale", "kin_timescale_plan_host",
     "kin_members_inputs_host", "kin_members_moments", "kin_members_moments_dev", "kin_members_quantiles", "kin_members_quantiles_dev",
     "kin_members_correlate", "kin_members_correlate_dev", "kin_ensemble_moments", "kin_ensemble_quantiles", "kin_ensemble_correlate",
+    "kin_members_sobol", "kin_members_sobol_dev", "kin_ensemble_sobol",
     "kin_flux_plan_host", "kin_network_compute_units",
     "kin_sweep_plan", "kin_sweep_plan_host", "kin_tiled_sweep_plan", "kin_tiled_sweep_plan_host",
 ]
@@ -224,6 +225,11 @@ def lib():
             L.kin_ensemble_moments.argtypes = [c_void_p, P32, P64, PD, PD, PD, PD]
             L.kin_ensemble_quantiles.argtypes = [c_void_p, P32, P64, c_int64, PD, c_int64, PD]
             L.kin_ensemble_correlate.argtypes = [c_void_p, P32, P64, c_int64, PD, c_int64, c_int, PD]
+        if hasattr(L, "kin_members_sobol"):   # (also under ABI 6: Sobol indices of a Saltelli design)
+            P32 = POINTER(c_int32)
+            L.kin_members_sobol.argtypes = [c_void_p, c_int64, c_int64, c_int64, PD, P32, P64, c_int64, PD, PD, PD, PD]
+            L.kin_members_sobol_dev.argtypes = [c_void_p, c_int64, c_int64, c_int64, c_void_p, P32, P64, c_int64] + [c_void_p] * 5
+            L.kin_ensemble_sobol.argtypes = [c_void_p, c_int64, c_int64, P32, P64, c_int64, PD, PD, PD, PD]
         if hasattr(L, "kin_sweep_plan"):   # (also under ABI 6: the plan queries of the two batched sweeps)
             L.kin_sweep_plan.argtypes = [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, P64]
             L.kin_sweep_plan_host.argtypes = [c_int64, c_int64] + [P64] * 6 + [c_int, c_int, c_int64, c_int, c_int, c_int, P64]
@@ -1222,6 +1228,67 @@ class HipNetwork:
         sp, ns, nsel = self._ms_species(species)
         out = np.empty((L, nsel, P))
         self._chk(lib().kin_ensemble_correlate(self._h, _p32(use), None if sp is None else _p64(sp), ns, _pd(X), P, int(bool(rank)), _pd(out)))
+        return out
+
+    # --- Sobol indices of a Saltelli design ---------------------------------------------------------
+    @staticmethod
+    def _sobol_weights(w, M):
+        """Sample weights as the kin_*_sobol entries take them: int32[M] multiplicities or None (negative ones are the entry's
+        KIN_ERR_INVALID_ARG)."""
+        if w is None:
+            return None
+        w = np.asarray(w)
+        if w.shape != (M,) or w.dtype.kind not in "iub":
+            raise ValueError(f"w must be {M} integer multiplicities, one per base sample; got {w.dtype} {w.shape}")
+        return np.ascontiguousarray(w, dtype=np.int32)
+
+    def ensemble_sobol_weights(self, M, P):
+        """The default weights of ensemble_sobol: int32[M], 1 where all P + 2 members of sample m completed the save grid."""
+        K, L, _, ns = self.ensemble_size()
+        if M < 1 or P < 1 or K != M * (P + 2):
+            raise KineticaHipError(KIN_ERR_INVALID_ARG, f"the stored ensemble has {K} members, not M (P + 2) = {M * (P + 2)}")
+        return np.all(ns.reshape(P + 2, M) == L, axis=0).astype(np.int32)
+
+    @staticmethod
+    def _sobol_result(L, nsel, P, count):
+        return dict(first=np.empty((L, nsel, P)), total=np.empty((L, nsel, P)), mean=np.empty((L, nsel)), var=np.empty((L, nsel)),
+                    count=int(count))
+
+    def members_sobol(self, u, M, P, species=None, w=None):
+        """kin_members_sobol over the Saltelli design u[M (P + 2)][L][N] (member b M + m: sample m of block A, B, AB_0 ..): dict of
+        first, total [L][n_sel][P] (S1, ST), mean, var [L][n_sel] (over A and B) and count = sum w. w: int multiplicities per base
+        sample (None: all ones); species: ids in the handle's index base (None: all)."""
+        M, P = int(M), int(P)
+        u, K, L = self._ms_block(u, self.n)
+        if M >= 1 and P >= 1 and K != M * (P + 2):
+            raise ValueError(f"u must hold M (P + 2) = {M * (P + 2)} members; got {K}")
+        w = self._sobol_weights(w, M)
+        sp, ns, nsel = self._ms_species(species)
+        out = self._sobol_result(L, nsel, max(P, 0), M if w is None else int(np.maximum(w, 0).sum()))
+        self._chk(lib().kin_members_sobol(self._h, M, P, L, _pd(u), _p32(w), None if sp is None else _p64(sp), ns,
+                                          *[_pd(out[k]) for k in ("first", "total", "mean", "var")]))
+        return out
+
+    def members_sobol_dev(self, M, P, L, d_u, d_first=0, d_total=0, d_mean=0, d_var=0, species=None, w=None, stream=0):
+        """kin_members_sobol_dev: device pointers (ints; 0 = not wanted) u[M (P + 2)][L][N], first / total [L][n_sel][P] and
+        mean / var [L][n_sel]; w and species are host arrays. Only enqueues."""
+        p = lambda x: c_void_p(x) if x else None
+        w = self._sobol_weights(w, int(M))
+        sp, ns, _ = self._ms_species(species)
+        self._chk(lib().kin_members_sobol_dev(self._h, int(M), int(P), int(L), p(d_u), _p32(w), None if sp is None else _p64(sp), ns,
+                                              p(d_first), p(d_total), p(d_mean), p(d_var), p(stream)))
+
+    def ensemble_sobol(self, M, P, species=None, w=None):
+        """kin_ensemble_sobol: members_sobol over the stored ensemble, read where it lives (w None: the samples all of whose
+        members completed the save grid)."""
+        M, P = int(M), int(P)
+        L = self.ensemble_size()[1]
+        w = self._sobol_weights(w, M)
+        sp, ns, nsel = self._ms_species(species)
+        out = self._sobol_result(L, nsel, max(P, 0), 0)
+        self._chk(lib().kin_ensemble_sobol(self._h, M, P, _p32(w), None if sp is None else _p64(sp), ns,
+                                           *[_pd(out[k]) for k in ("first", "total", "mean", "var")]))
+        out["count"] = int((self.ensemble_sobol_weights(M, P) if w is None else w).sum())
         return out
 
     # --- library order (tiled sweep) --------------------------------------------------------

@@ -162,11 +162,11 @@ struct kin_network {
   // cross-member statistics (member_stats.hpp, member_stats_api.cpp): the index base kin_network_create was given (species
   // lists of these entries are in it); the participants, the selected species, the probabilities and the normalised inputs
   // on the device with the host copies the uploads read; the workspace Yhat[columns][n] of a block of columns; the staging
-  // buffers of the host entries' states and outputs
+  // buffers of the host entries' states and outputs; the weights of the Sobol pass's participants
   int index_base = 0;
-  std::vector<int32_t> ms_h_idx, ms_h_sel;
+  std::vector<int32_t> ms_h_idx, ms_h_sel, ms_h_wt;
   std::vector<double> ms_h_p, ms_h_xhat;
-  kin::DevBuf<int32_t> ms_idx, ms_sel;
+  kin::DevBuf<int32_t> ms_idx, ms_sel, ms_wt;
   kin::DevBuf<double> ms_p, ms_xhat, ms_yhat, ms_u, ms_o[4];
 
   kin_network();

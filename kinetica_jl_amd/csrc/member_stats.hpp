@@ -62,4 +62,38 @@ void launch_ms_values(const MsColArgs& a, hipStream_t s);
 // participants, plain FMA loops
 void launch_ms_corr(int64_t nc, int32_t n, int32_t P, const double* xhat, const double* yhat, double* out, hipStream_t s);
 
+// Sobol indices of a Saltelli design (include/kinetica_hip.h: the definition; kernel: sobol_kernels.hip). The block holds
+// K = M (P + 2) members, member b M + m = sample m of block b (0: A, 1: B, 2 + p: AB_p). The PARTICIPANTS are the samples with
+// a weight > 0, ascending: idx[q] is the q-th one's m, wt[q] its weight, np of them, n = sum wt. For one column (the selected
+// columns c = j n_sel + s of MsColArgs) and participant q write a, b, c_p for the values of sample idx[q] in A, B, AB_p and
+// wq = (double)wt[q]. Every product with wq is rounded on its own (exact for wq == 1); every fma below is one rounding.
+//
+// Lanes along the columns; the participants split over the SB_WAVES wavefronts of a workgroup: wave w takes q = w, w + W, ...
+// in that order, every accumulator starts at 0.0, and the W partials of a quantity are added in the order w = 0..W-1,
+// starting from wave 0's.
+//   pass 1   TA = sum (TA + wq a), TB = sum (TB + wq b);  mu = (TA + TB) / (2 n).  Beside it the exact minimum and maximum of
+//            the participants' a and b: the column is FLAT when max - min == 0 and mu is not NaN.
+//   pass 2   da = a - mu, db = b - mu;  SA = fma(wq da, da, SA), SB = fma(wq db, db, SB);
+//            per input p:  C1_p = fma(wq db, c_p - a, C1_p);  e = a - c_p, C2_p = fma(wq e, e, C2_p).
+//   result   V = (SA + SB) / (2 n), exactly 0.0 for a flat column (the sum of n equal values need not be n times the value:
+//            without the rule a constant column would get a V of rounding noise);
+//            S1_p = (C1_p / n) / V,  ST_p = (C2_p / (2 n)) / V;  both exactly 0.0 when n < 2 or V == 0.
+// A launch takes SB_CHUNK inputs per workgroup (the accumulators 2 + 2 SB_CHUNK live in registers; the chunks of a larger P
+// are further workgroups, grid.y, each repeating pass 1 and SA, SB in the same order: nothing depends on the chunking).
+// n == 0 is the caller's case (zeros), never launched.
+constexpr int SB_WAVES = 8;
+constexpr int SB_CHUNK = 8;
+struct SobolArgs {
+  const double* u;
+  const int32_t* idx;    // [np] participating samples m, ascending
+  const int32_t* wt;     // [np] their weights (> 0)
+  const int32_t* sel;    // [n_sel] 0-based species or null
+  int32_t np, M, P, N, n_sel;
+  int64_t n;             // sum wt
+  int64_t stride, c_total;   // doubles between two members (L N); selected columns L n_sel
+  double *S1, *ST;       // [c_total][P] or null
+  double *mean, *var;    // [c_total] or null
+};
+void launch_sobol(const SobolArgs& a, hipStream_t s);
+
 }  // namespace kin

@@ -260,6 +260,71 @@ void correlate_to_host(kin_network* h, const MsBlock& b, const int64_t* species,
   KIN_HIP(hipStreamSynchronize(s));
 }
 
+// ---- Sobol indices of a Saltelli design -------------------------------------------------------------------------------------
+// K = M (P + 2) of a design, checked
+int64_t design_members(int64_t M, int64_t P) {
+  require(M >= 1 && P >= 1, ERR_INVALID_ARG, "sobol: M or P < 1");
+  require(M < ((int64_t)1 << 31) && P < (int64_t)SB_CHUNK * 65535, ERR_UNSUPPORTED, "sobol: M or P beyond the launch's grid");
+  return M * (P + 2);
+}
+
+// The participating samples and their weights on the device; returns n = sum w. complete: null (every sample may take part) or
+// [M], the samples all of whose members completed the save grid - the default weights, and the only ones a caller may name.
+int64_t upload_weights(kin_network* h, int64_t M, const int32_t* w, const std::vector<char>* complete, hipStream_t s) {
+  std::vector<int32_t> idx, wt;
+  int64_t n = 0;
+  for (int64_t m = 0; m < M; m++) {
+    const bool ok = !complete || (*complete)[(size_t)m];
+    if (w) {
+      require(w[m] >= 0, ERR_INVALID_ARG, "sobol: a negative weight");
+      require(w[m] == 0 || ok, ERR_INVALID_ARG, "sobol: w names a sample with a member that did not complete the save grid (n_saved < n_rows)");
+    }
+    const int32_t v = w ? w[m] : (ok ? 1 : 0);
+    if (v > 0) { idx.push_back((int32_t)m); wt.push_back(v); n += v; }
+  }
+  h->ms_h_wt = std::move(wt);
+  h->ms_wt.upload(h->ms_h_wt, s);
+  upload_participants(h, std::move(idx), s);
+  return n;
+}
+
+// the pass over a block on the device into device outputs (any null)
+void sobol_run(kin_network* h, const double* d_u, int64_t M, int64_t P, int64_t L, int64_t n, const int64_t* species, int64_t n_sel,
+               double* d_S1, double* d_ST, double* d_mean, double* d_var, hipStream_t s) {
+  const int32_t* d_sel;
+  n_sel = upload_species(h, species, n_sel, &d_sel, s);
+  require(n_sel < ((int64_t)1 << 31) && L * n_sel < ((int64_t)1 << 36), ERR_UNSUPPORTED, "sobol: too many selected columns");
+  const int64_t total = L * n_sel;
+  if (total == 0) return;
+  if (n == 0) {
+    for (double* o : {d_S1, d_ST})
+      if (o) KIN_HIP(hipMemsetAsync(o, 0, (size_t)(total * P) * sizeof(double), s));
+    for (double* o : {d_mean, d_var})
+      if (o) KIN_HIP(hipMemsetAsync(o, 0, (size_t)total * sizeof(double), s));
+    return;
+  }
+  SobolArgs a{};
+  a.u = d_u; a.idx = h->ms_idx.p; a.wt = h->ms_wt.p; a.sel = d_sel;
+  a.np = (int32_t)h->ms_h_idx.size(); a.M = (int32_t)M; a.P = (int32_t)P; a.N = (int32_t)h->host.N; a.n_sel = (int32_t)n_sel;
+  a.n = n; a.stride = L * h->host.N; a.c_total = total;
+  a.S1 = d_S1; a.ST = d_ST; a.mean = d_mean; a.var = d_var;
+  launch_sobol(a, s);
+}
+
+void sobol_to_host(kin_network* h, const double* d_u, int64_t M, int64_t P, int64_t L, int64_t n, const int64_t* species, int64_t n_sel,
+                   double* S1, double* ST, double* mean, double* var, hipStream_t s) {
+  const size_t C = (size_t)std::max<int64_t>(L * (species ? n_sel : h->host.N), 0);
+  double* host[4] = {S1, ST, mean, var};
+  const size_t len[4] = {C * (size_t)P, C * (size_t)P, C, C};
+  double* dev[4] = {};
+  for (int i = 0; i < 4; i++)
+    if (host[i]) { h->ms_o[i].alloc(len[i]); dev[i] = h->ms_o[i].p; }
+  sobol_run(h, d_u, M, P, L, n, species, n_sel, dev[0], dev[1], dev[2], dev[3], s);
+  for (int i = 0; i < 4; i++)
+    if (host[i]) h->ms_o[i].download(host[i], len[i], s);
+  KIN_HIP(hipStreamSynchronize(s));
+}
+
 }  // namespace
 
 #define KIN_TRY(h) try { KIN_HIP(hipSetDevice((h)->device));
@@ -376,6 +441,55 @@ int kin_ensemble_correlate(kin_network* h, const int32_t* use, const int64_t* sp
   require((!species || n_sel >= 0) && P >= 0, ERR_INVALID_ARG, "n_sel or P < 0");
   hipStream_t s = h->stream;
   correlate_to_host(h, ensemble_block(h, use, s), species, n_sel, X, P, rank, out, s);
+  KIN_CATCH(h)
+}
+
+int kin_members_sobol_dev(kin_network* h, int64_t M, int64_t P, int64_t L, const double* d_u, const int32_t* w, const int64_t* species,
+                          int64_t n_sel, double* d_S1, double* d_ST, double* d_mean, double* d_var, void* stream) {
+  if (!h) return KIN_ERR_INVALID_ARG;
+  KIN_TRY(h)
+  require(d_S1 || d_ST || d_mean || d_var, ERR_INVALID_ARG, "no output requested");
+  hipStream_t s = stream ? (hipStream_t)stream : h->stream;
+  const int64_t K = design_members(M, P);
+  check_shape(h, K, L);
+  require(d_u != nullptr || L * h->host.N == 0, ERR_INVALID_ARG, "null state buffer");
+  const int64_t n = upload_weights(h, M, w, nullptr, s);
+  sobol_run(h, d_u, M, P, L, n, species, n_sel, d_S1, d_ST, d_mean, d_var, s);
+  KIN_CATCH(h)
+}
+
+int kin_members_sobol(kin_network* h, int64_t M, int64_t P, int64_t L, const double* u, const int32_t* w, const int64_t* species,
+                      int64_t n_sel, double* S1, double* ST, double* mean, double* var) {
+  if (!h) return KIN_ERR_INVALID_ARG;
+  KIN_TRY(h)
+  require(S1 || ST || mean || var, ERR_INVALID_ARG, "no output requested");
+  require(!species || n_sel >= 0, ERR_INVALID_ARG, "n_sel < 0");
+  hipStream_t s = h->stream;
+  const int64_t K = design_members(M, P);
+  check_shape(h, K, L);
+  const size_t len = (size_t)K * (size_t)L * (size_t)h->host.N;
+  require(u != nullptr || len == 0, ERR_INVALID_ARG, "null state buffer");
+  const int64_t n = upload_weights(h, M, w, nullptr, s);
+  h->ms_u.upload(u, len, s);
+  sobol_to_host(h, h->ms_u.p, M, P, L, n, species, n_sel, S1, ST, mean, var, s);
+  KIN_CATCH(h)
+}
+
+int kin_ensemble_sobol(kin_network* h, int64_t M, int64_t P, const int32_t* w, const int64_t* species, int64_t n_sel, double* S1, double* ST,
+                       double* mean, double* var) {
+  if (!h) return KIN_ERR_INVALID_ARG;
+  KIN_TRY(h)
+  require(S1 || ST || mean || var, ERR_INVALID_ARG, "no output requested");
+  require(!species || n_sel >= 0, ERR_INVALID_ARG, "n_sel < 0");
+  require(h->ens.valid(), ERR_STATE, "no ensemble stored (kin_solve_ensemble* first)");
+  hipStream_t s = h->stream;
+  require(design_members(M, P) == h->ens.K, ERR_INVALID_ARG, "sobol: the stored ensemble does not have M (P + 2) members");
+  check_shape(h, h->ens.K, h->ens.cap);
+  std::vector<char> complete((size_t)M, 1);
+  for (int64_t k = 0; k < h->ens.K; k++)
+    if (h->ens.n_saved[(size_t)k] != h->ens.cap) complete[(size_t)(k % M)] = 0;
+  const int64_t n = upload_weights(h, M, w, &complete, s);
+  sobol_to_host(h, h->ens.sol, M, P, h->ens.cap, n, species, n_sel, S1, ST, mean, var, s);
   KIN_CATCH(h)
 }
 

@@ -29,7 +29,8 @@ __all__ = ["SpeciesData", "RxData", "RxFilter", "get_filter_mask", "DummyKinetic
            "get_max_rates", "get_initial_rates", "calculate_discrete_rates",
            "solve_network_ensemble",   # EXTENSION: the reference has no ensemble call
            "flux_weights", "held_stop_index", "ReactionFluxes", "reaction_fluxes", "ensemble_flux_sources",   # EXTENSION: post-hoc flux analysis
-           "EnsembleStatistics", "ensemble_statistics"]   # EXTENSION: statistics across the members of an ensemble
+           "EnsembleStatistics", "ensemble_statistics",   # EXTENSION: statistics across the members of an ensemble
+           "SobolIndices", "sobol_design", "sobol_indices"]   # EXTENSION: variance-based sensitivity of a Saltelli design
 
 _T_UNIT = {  # src/utils.jl:77-97
     "picoseconds": 1.0e-12, "ps": 1.0e-12, "nanoseconds": 1.0e-9, "ns": 1.0e-9, "microseconds": 1.0e-6, "us": 1.0e-6,
@@ -752,7 +753,9 @@ def solve_network_ensemble(methods, sd, rd, copy_network=True, fluxes=False, tra
     statistics=True or a dict of ensemble_statistics' keyword arguments (quantiles, species, inputs, rank, use; species are
     0-based ids of the network as it is solved, inputs[K][P] one row per method): every member's sol.ensemble_stats refers to
     ONE shared EnsembleStatistics over the members that completed the save grid, computed from the states where they live on
-    the device before the handle closes (with trajectories=False no state is downloaded). A malformed `statistics` raises
+    the device before the handle closes (with trajectories=False no state is downloaded). The key sobol=dict(M=, P=, ...) -
+    sobol_indices' keyword arguments, species again 0-based - declares the methods a Saltelli design in sobol_design's layout
+    (len(methods) == M (P + 2)) and fills ensemble_stats.sobol with its SobolIndices. A malformed `statistics` raises
     ValueError before anything touches the GPU. None (the default): nothing is computed."""
     methods = list(methods)
     if not methods:
@@ -796,6 +799,9 @@ def solve_network_ensemble(methods, sd, rd, copy_network=True, fluxes=False, tra
     U0 = np.array([make_u0(sd_a, m.pars) for m in methods])
     if stat_kw is not None and stat_kw["species"] is not None and stat_kw["species"].max(initial=-1) >= sd_a.n:
         raise ValueError(f"statistics: species ids must be below the {sd_a.n} species of the network as it is solved")
+    sob_kw = None if stat_kw is None else stat_kw.get("sobol")
+    if sob_kw is not None and sob_kw["species"] is not None and sob_kw["species"].max(initial=-1) >= sd_a.n:
+        raise ValueError(f"statistics: sobol species ids must be below the {sd_a.n} species of the network as it is solved")
     if discrete:
         # each member's (tstops, T(tstops)), as solve_network hands them to kin_solve
         stops = [discrete_stop_temperatures(m.conditions) for m in methods]
@@ -824,8 +830,13 @@ def solve_network_ensemble(methods, sd, rd, copy_network=True, fluxes=False, tra
         stats = None
         if stat_kw is not None:
             sp0 = stat_kw["species"]
-            stats = ensemble_statistics(h, t, **dict(stat_kw, species=None if sp0 is None else sp0 + 1))   # (the handle's base is 1)
+            if sob_kw is not None:
+                sb0 = sob_kw["species"]
+                sob_kw = dict(sob_kw, species=None if sb0 is None else sb0 + 1)
+            stats = ensemble_statistics(h, t, **dict(stat_kw, species=None if sp0 is None else sp0 + 1, sobol=sob_kw))   # (the handle's base is 1)
             stats.species = sp0
+            if sob_kw is not None:
+                stats.sobol.species = sb0
     finally:
         h.close()
     out = []
@@ -873,6 +884,9 @@ class EnsembleStatistics:
     species: Optional[np.ndarray] = None
     corr: Optional[np.ndarray] = None
     rank: bool = True
+    # the design's SobolIndices (ensemble_statistics(sobol=...)), else None: a plain attribute set after construction, not a
+    # dataclass field - the constructor and dataclasses.fields() stay as they were
+    sobol = None
 
     @property
     def std(self):
@@ -898,12 +912,16 @@ def _statistics_arguments(statistics, K):
         statistics = {}
     if not isinstance(statistics, dict):
         raise ValueError("statistics must be None, True or a dict of ensemble_statistics' keyword arguments")
-    known = ("quantiles", "species", "inputs", "rank", "use")
+    known = ("quantiles", "species", "inputs", "rank", "use", "sobol")
     bad = [k for k in statistics if k not in known]
     if bad:
         raise ValueError(f"statistics: unknown keys {bad}; choose among {known}")
     kw = dict(quantiles=(0.05, 0.5, 0.95), species=None, inputs=None, rank=True, use=None)
     kw.update(statistics)
+    if kw.get("sobol") is not None:
+        kw["sobol"] = _sobol_arguments(kw["sobol"], K)
+    else:
+        kw.pop("sobol", None)
     try:
         q = np.atleast_1d(np.asarray(() if kw["quantiles"] is None else kw["quantiles"], dtype=float))
     except (TypeError, ValueError):
@@ -932,19 +950,172 @@ def _statistics_arguments(statistics, K):
     return kw
 
 
-def ensemble_statistics(h, t, quantiles=(0.05, 0.5, 0.95), species=None, inputs=None, rank=True, use=None):
+def ensemble_statistics(h, t, quantiles=(0.05, 0.5, 0.95), species=None, inputs=None, rank=True, use=None, sobol=None):
     """Statistics across the members of the ensemble stored in the handle `h` (a capi.HipNetwork after a solve_ensemble* call,
     trajectories downloaded or not), read where the states live on the device: kin_ensemble_moments, kin_ensemble_quantiles
     (quantiles: probabilities in [0, 1]; None or empty: none) and, with inputs[K][P] (one row per member: whatever was sampled -
     log-multipliers of rate constants, temperatures, heating rates, u0 entries), kin_ensemble_correlate. species: ids in the
-    handle's index base, None for all. use: a mask over the members, None for those that completed the save grid `t`."""
+    handle's index base, None for all. use: a mask over the members, None for those that completed the save grid `t`.
+    sobol: a dict of sobol_indices' keyword arguments (M, P, ...) when the ensemble is a Saltelli design; fills `.sobol`."""
     m = h.ensemble_moments(use=use)
     p = np.atleast_1d(np.asarray(() if quantiles is None else quantiles, dtype=float))
     sp = None if species is None else np.asarray(species, dtype=np.int64)
     qv = h.ensemble_quantiles(p, species=sp, use=use) if len(p) else None
     corr = None if inputs is None else h.ensemble_correlate(inputs, species=sp, rank=rank, use=use)
-    return EnsembleStatistics(np.asarray(t, dtype=float), m["count"], m["mean"], m["var"], m["min"], m["max"], quantiles=qv,
-                              p=p if len(p) else None, species=sp, corr=corr, rank=bool(rank))
+    sob = None if sobol is None else sobol_indices(h, t, **sobol)
+    st = EnsembleStatistics(np.asarray(t, dtype=float), m["count"], m["mean"], m["var"], m["min"], m["max"], quantiles=qv,
+                            p=p if len(p) else None, species=sp, corr=corr, rank=bool(rank))
+    st.sobol = sob
+    return st
+
+
+# ---- variance-based sensitivity: Sobol indices of a Saltelli design (EXTENSION) ---------------------------------------------
+def sobol_design(M, P, seed=0, A=None, B=None):
+    """The Saltelli design X[M (P + 2)][P] on the unit cube in the layout of kin_members_sobol / kin_ensemble_sobol: row
+    b M + m is sample m of block b; block 0 is A, block 1 is B, block 2 + p is A with column p taken from B. Without A / B the
+    base samples are A = rng.random((M, P)) and then B = rng.random((M, P)) of np.random.default_rng(seed); a caller with a
+    sampler of their own (Latin hypercube, a low-discrepancy sequence) passes both as [M][P] arrays.
+
+    Building the ensemble from it: map every column to its parameter with any per-column transform - a log-multiplier
+    k[:, r] = k0[r] * exp(s * (X[:, p] - 0.5)), a temperature T = T_lo + (T_hi - T_lo) * X[:, p], a heating rate - and give the
+    K rows to the ensemble call IN THIS ORDER: k[K][R] (and T[K]) to HipNetwork.solve_ensemble, or one VariableODESolve per
+    row to solve_network_ensemble(methods, ..., statistics=dict(sobol=dict(M=M, P=P)))."""
+    if int(M) != M or int(P) != P or M < 1 or P < 1:
+        raise ValueError(f"sobol_design: M and P must be integers >= 1; got {M!r}, {P!r}")
+    M, P = int(M), int(P)
+    if (A is None) != (B is None):
+        raise ValueError("sobol_design: give both A and B or neither")
+    if A is None:
+        rng = np.random.default_rng(seed)
+        A = rng.random((M, P))
+        B = rng.random((M, P))
+    else:
+        A, B = np.asarray(A, dtype=float), np.asarray(B, dtype=float)
+        if A.shape != (M, P) or B.shape != (M, P):
+            raise ValueError(f"sobol_design: A and B must be [M = {M}][P = {P}]; got {A.shape} and {B.shape}")
+    X = np.empty((M * (P + 2), P))
+    X[:M], X[M:2 * M] = A, B
+    for p in range(P):
+        blk = X[(2 + p) * M:(3 + p) * M]
+        blk[:] = A
+        blk[:, p] = B[:, p]
+    return X
+
+
+@dataclass
+class SobolIndices:
+    """Result of sobol_indices. Over the n = count base samples (sum of the weights), per row j of `t` (one row for of="max")
+    and selected species: first[n_rows][n_sel][P] the first-order index S1 of every input, total[n_rows][n_sel][P] the
+    total-effect index ST, mean and var [n_rows][n_sel] over the design's blocks A and B (include/kinetica_hip.h has the
+    estimators). first_ci / total_ci [2][n_rows][n_sel][P]: bootstrap percentile interval (lower, upper), or None."""
+    t: np.ndarray
+    count: int
+    first: np.ndarray
+    total: np.ndarray
+    mean: np.ndarray
+    var: np.ndarray
+    species: Optional[np.ndarray] = None
+    first_ci: Optional[np.ndarray] = None
+    total_ci: Optional[np.ndarray] = None
+
+    def ranking(self, row=-1, species=None):
+        """The inputs ordered by their total-effect index at `row`, the most influential first (ties and NaN keep the inputs'
+        order, NaN last). species: one of the selected ids (as the caller gave them), or None for the mean over the selected
+        species that have a value."""
+        st = self.total[row]
+        if species is None:
+            with np.errstate(all="ignore"):
+                ok = ~np.isnan(st)
+                v = np.where(ok.any(axis=0), np.where(ok, st, 0.0).sum(axis=0) / np.maximum(ok.sum(axis=0), 1), np.nan)
+        else:
+            ids = np.arange(st.shape[0]) if self.species is None else np.asarray(self.species)
+            at = np.nonzero(ids == species)[0]
+            if len(at) == 0:
+                raise ValueError(f"species {species} is not among the selected species")
+            v = st[at[0]]
+        return np.argsort(np.where(np.isnan(v), -np.inf, v) * -1.0, kind="stable")
+
+
+_SOBOL_KEYS = ("M", "P", "species", "w", "of", "n_boot", "seed", "level")
+
+
+def _sobol_arguments(sobol, K):
+    """The `sobol` entry of solve_network_ensemble's statistics as keyword arguments of sobol_indices; ValueError for anything
+    malformed, a design that does not match the K methods included - nothing here touches the device."""
+    if not isinstance(sobol, dict):
+        raise ValueError("statistics: sobol must be a dict of sobol_indices' keyword arguments (M, P, ...)")
+    bad = [k for k in sobol if k not in _SOBOL_KEYS]
+    if bad:
+        raise ValueError(f"statistics: unknown sobol keys {bad}; choose among {_SOBOL_KEYS}")
+    kw = dict(species=None, w=None, of="states", n_boot=0, seed=0, level=0.95)
+    kw.update(sobol)
+    for name in ("M", "P"):
+        v = kw.get(name)
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
+            raise ValueError(f"statistics: sobol needs an integer {name} >= 1")
+        kw[name] = int(v)
+    if kw["M"] * (kw["P"] + 2) != K:
+        raise ValueError(f"statistics: a sobol design with M = {kw['M']}, P = {kw['P']} has {kw['M'] * (kw['P'] + 2)} members; "
+                         f"there are {K} methods")
+    if kw["species"] is not None:
+        sp = np.asarray(kw["species"])
+        if sp.ndim != 1 or sp.dtype.kind not in "iu" or (sp < 0).any():
+            raise ValueError("statistics: sobol species must be a list of 0-based integer ids")
+        kw["species"] = sp.astype(np.int64)
+    if kw["w"] is not None:
+        w = np.asarray(kw["w"])
+        if w.shape != (kw["M"],) or w.dtype.kind not in "iu" or (w < 0).any():
+            raise ValueError(f"statistics: sobol w must be {kw['M']} integer multiplicities >= 0")
+        kw["w"] = w.astype(np.int32)
+    if kw["of"] not in ("states", "max"):
+        raise ValueError("statistics: sobol of must be 'states' or 'max'")
+    nb = kw["n_boot"]
+    if isinstance(nb, bool) or not isinstance(nb, (int, np.integer)) or nb < 0:
+        raise ValueError("statistics: sobol n_boot must be an integer >= 0")
+    kw["n_boot"] = int(nb)
+    if not isinstance(kw["level"], (int, float)) or not 0.0 < kw["level"] < 1.0:
+        raise ValueError("statistics: sobol level must lie in (0, 1)")
+    return kw
+
+
+def sobol_indices(h, t, M, P, species=None, w=None, of="states", n_boot=0, seed=0, level=0.95):
+    """First-order and total-effect Sobol indices of the Saltelli design stored in the handle `h` (a capi.HipNetwork after a
+    solve_ensemble* call over the K = M (P + 2) members of sobol_design, trajectories downloaded or not), read where the states
+    live on the device (kin_ensemble_sobol). species: ids in the handle's index base, None for all. w: int multiplicities per
+    base sample, None for 1 where all P + 2 members of a sample completed the save grid `t`, else 0.
+    of="states": the indices of every species at every saved time; of="max": of every species' peak value over a member's own
+    rows (kin_ensemble_max's [K][N] handed to kin_members_sobol as one row; `t` is kept as given).
+    n_boot > 0: bootstrap percentile intervals at `level` - n_boot replicates, each the multinomial multiplicities of
+    resampling the participants with replacement (np.random.default_rng(seed)), one device pass per replicate."""
+    if of not in ("states", "max"):
+        raise ValueError("of must be 'states' or 'max'")
+    if of == "max":
+        umax = h.ensemble_max()[:, None, :]
+        base = h.ensemble_sobol_weights(M, P) if w is None else np.asarray(w)
+        run = lambda wt: h.members_sobol(umax, M, P, species=species, w=wt)
+        r = run(base)      # (a failed member's peak is no peak: its sample is dropped here as over the states)
+    else:
+        base = h.ensemble_sobol_weights(M, P) if w is None else np.asarray(w)
+        run = lambda wt: h.ensemble_sobol(M, P, species=species, w=wt)
+        r = run(w)
+    ci = [None, None]
+    if n_boot > 0:
+        rng = np.random.default_rng(seed)
+        at = np.flatnonzero(base > 0)
+        prob = base[at] / base[at].sum() if len(at) else None
+        reps = ([], [])
+        for _ in range(int(n_boot)):
+            wt = np.zeros(int(M), np.int32)
+            if len(at):
+                wt[at] = rng.multinomial(int(base[at].sum()), prob)
+            b = run(wt)
+            reps[0].append(b["first"]); reps[1].append(b["total"])
+        q = [(1.0 - level) / 2.0, (1.0 + level) / 2.0]
+        with np.errstate(all="ignore"):
+            ci = [np.quantile(np.stack(x), q, axis=0) for x in reps]
+    sp = None if species is None else np.asarray(species, dtype=np.int64)
+    return SobolIndices(np.asarray(t, dtype=float), r["count"], r["first"], r["total"], r["mean"], r["var"], species=sp,
+                        first_ci=ci[0], total_ci=ci[1])
 
 
 # ---- post-hoc reaction-flux analysis (EXTENSION, in the style of the reference's analysis/: works on an ODESolveOutput) ----

@@ -364,6 +364,30 @@ int kin_solve_ensemble_discrete(kin_network* h, const kin_params* params, int64_
                                 const int64_t* stop_ptr, const double* tstops, const double* T_stops,
                                 int64_t* n_rows, double* out_t, double* out_u, int64_t* n_saved,
                                 int32_t* retcodes, kin_stats* stats);
+/* The two calls above with Arrhenius parameters of each member's own (uncertain barriers and prefactors under a temperature
+ * programme: a design over rate parameters in ONE ensemble call). Ea[K][R], A[K][R]: member m's rates are
+ * arrhenius_one(Ea[m][r], A[m][r], R T, ...) with has_kmax / k_max / t_mult of the handle, so kin_set_arrhenius is still
+ * required (else KIN_ERR_STATE); the handle's own Ea / A are neither read nor changed. Ea == NULL and A == NULL: exactly the
+ * call above (same code path, same bits); exactly one of them NULL: KIN_ERR_INVALID_ARG. Every route takes them: the resident
+ * kernel reads each member's rows (a member is bit-identical to a K = 1 call on a handle set to its parameters), the thread
+ * route solves member m on a replica holding its parameters (bit-identical to kin_solve / kin_solve_continuous on such a
+ * handle), the lockstep rounds (discrete only) form each member's rates from its rows. The blocks cost 16 K R bytes on the
+ * device, stay with the stored ensemble and are reused by later calls (a failed allocation: KIN_ERR_DEVICE, the size in
+ * kin_last_error). The stored ensemble remembers it was solved this way: kin_ensemble_flux with T_rows evaluates every
+ * member's rate constants from its own rows; kin_ensemble_drg / _drgep / _pfa / _reaction_importance / _timescale with T_rows
+ * return KIN_ERR_UNSUPPORTED on such a record (they would use the handle's one pair) - give them k / k_row, one
+ * kin_arrhenius_eval row per member and temperature; everything that reads states only (kin_ensemble_max / _dot / _moments /
+ * _quantiles / _correlate / _sobol) works on either record. A later shared call leaves a shared record again. All other
+ * arguments, the size query and the return values are those of the calls above. Added without a KIN_ABI_VERSION change
+ * (purely additive, structs unchanged): a binding detects them by symbol lookup. */
+int kin_solve_ensemble_continuous_params(kin_network* h, const kin_params* params, int64_t K, const double* u0,
+                                         const double* Ea, const double* A, const int64_t* node_ptr, const double* t_nodes,
+                                         const double* T_nodes, int64_t* n_rows, double* out_t, double* out_u,
+                                         int64_t* n_saved, int32_t* retcodes, kin_stats* stats);
+int kin_solve_ensemble_discrete_params(kin_network* h, const kin_params* params, int64_t K, const double* u0,
+                                       const double* Ea, const double* A, const int64_t* stop_ptr, const double* tstops,
+                                       const double* T_stops, int64_t* n_rows, double* out_t, double* out_u,
+                                       int64_t* n_saved, int32_t* retcodes, kin_stats* stats);
 /* N1: return_integrator=true (methods.jl:105-106, 175-178, 242-246, 706-709): `init(oprob, solver; kwargs...)`
  * without solve!. The integrator spans the whole tspan (solve_chunks = 0) or the first chunk
  * [0, solve_chunkstep] (solve_chunks = 1, what the reference hands back); tstops / T_stops / k_table as
@@ -997,7 +1021,8 @@ const char* kin_version(void);
  * kin_jac_batched*, kin_timescale_*, kin_solution_timescale, kin_ensemble_timescale, and path flux analysis: kin_pfa_*,
  * kin_solution_pfa, kin_ensemble_pfa, and reaction elimination: kin_reaction_importance_*, kin_solution_reaction_importance,
  * kin_ensemble_reaction_importance, and the cross-member statistics: kin_members_*, kin_ensemble_moments / _quantiles /
- * _correlate, and the Sobol indices: kin_members_sobol, kin_members_sobol_dev, kin_ensemble_sobol). */
+ * _correlate, and the Sobol indices: kin_members_sobol, kin_members_sobol_dev, kin_ensemble_sobol, and the
+ * per-member Arrhenius parameters: kin_solve_ensemble_continuous_params, kin_solve_ensemble_discrete_params). */
 #define KIN_ABI_VERSION 6
 int kin_abi_version(void);
 int64_t kin_struct_size(int which); /* 0: sizeof(kin_params), 1: sizeof(kin_stats), else -1 */

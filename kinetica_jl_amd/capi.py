@@ -30,6 +30,7 @@ SYMBOLS = [
     "kin_lib_layout", "kin_lib_layout_host", "kin_states_to_lib_dev", "kin_states_from_lib_dev", "kin_rates_to_lib_dev", "kin_rate_table_lib_dev",
     "kin_rhs_tiled_dev", "kin_rhs_batched_T_dev", "kin_rhs_batched_klib_dev", "kin_abi_version", "kin_struct_size",
     "kin_solve_ensemble", "kin_lu_analyze_host", "kin_solve_ensemble_continuous", "kin_solve_ensemble_discrete",
+    "kin_solve_ensemble_continuous_params", "kin_solve_ensemble_discrete_params",
     "kin_resident_probe", "kin_newton_probe", "kin_step_probe", "kin_eval_probe", "kin_cache_probe",
     "kin_flux_batched", "kin_flux_batched_dev", "kin_solution_flux",
     "kin_flux_segmented", "kin_flux_segmented_dev", "kin_ensemble_size", "kin_ensemble_max", "kin_ensemble_dot", "kin_ensemble_flux",
@@ -148,6 +149,10 @@ def lib():
         if hasattr(L, "kin_solve_ensemble_discrete"):   # added under ABI 6: found by symbol lookup, an earlier build lacks it
             L.kin_solve_ensemble_discrete.argtypes = [c_void_p, POINTER(KinParams), c_int64, PD, P64, PD, PD, P64, PD, PD, P64,
                                                       POINTER(c_int32), POINTER(KinStats)]
+        for name in ("kin_solve_ensemble_continuous_params", "kin_solve_ensemble_discrete_params"):   # (also under ABI 6)
+            if hasattr(L, name):
+                getattr(L, name).argtypes = [c_void_p, POINTER(KinParams), c_int64, PD, PD, PD, P64, PD, PD, P64, PD, PD, P64,
+                                             POINTER(c_int32), POINTER(KinStats)]
         if hasattr(L, "kin_resident_probe"):   # (also under ABI 6)
             L.kin_resident_probe.argtypes = [c_void_p, c_int64, PD, PD, PD, PD, PD, PD, POINTER(c_int32), P64]
         if hasattr(L, "kin_newton_probe"):   # (also under ABI 6)
@@ -1394,13 +1399,33 @@ class HipNetwork:
         return self._ensemble(lib().kin_solve_ensemble, params, K, _pd(u0), _pd(k), _pd(T), _pd(tstops), _pd(T_stops), _pd(k_table),
                               n_stops, trajectories=trajectories)
 
-    def solve_ensemble_continuous(self, params: KinParams, u0, nodes, trajectories=True):
+    def _member_arrhenius(self, K, Ea, A):
+        """Per-member Arrhenius parameters of an ensemble call as contiguous float64 [K][R] arrays, or (None, None); ValueError
+        for one without the other, a wrong shape or a dtype that is not real numbers - before the library is called."""
+        if Ea is None and A is None:
+            return None, None
+        if Ea is None or A is None:
+            raise ValueError("per-member Arrhenius parameters: give both Ea and A, or neither")
+        out = []
+        for name, x in (("Ea", Ea), ("A", A)):
+            x = np.asarray(x)
+            if x.dtype.kind not in "fiu":
+                raise ValueError(f"per-member {name} must be real numbers, got dtype {x.dtype}")
+            if x.shape != (K, self.nr):
+                raise ValueError(f"per-member {name} must be [K][R] = {(K, self.nr)}, got {x.shape}")
+            out.append(np.ascontiguousarray(x, dtype=np.float64))
+        return out[0], out[1]
+
+    def solve_ensemble_continuous(self, params: KinParams, u0, nodes, trajectories=True, Ea=None, A=None):
         """kin_solve_ensemble_continuous: K trajectories under continuous rate updates, member m's rates at T(t) of its own
-        profile. u0[K][N]; nodes: K pairs (t_nodes, T_nodes) in global time (node counts may differ).
+        profile. u0[K][N]; nodes: K pairs (t_nodes, T_nodes) in global time (node counts may differ). Ea[K][R], A[K][R] (both or
+        neither; ValueError for a wrong shape or dtype): Arrhenius parameters of each member's own
+        (kin_solve_ensemble_continuous_params; k_max and t_mult are the handle's); without them the call is the one it always was.
         Returns what solve_ensemble returns: (t[M], u[K][M][N], n_saved[K], retcodes[K], [stats dict] * K); trajectories as there."""
         u0 = np.ascontiguousarray(np.atleast_2d(_f64(u0)))
         K = u0.shape[0]
         assert u0.shape == (K, self.n) and len(nodes) == K
+        Ea, A = self._member_arrhenius(K, Ea, A)
         tn = [_f64(a).ravel() for a, _ in nodes]
         Tn = [_f64(b).ravel() for _, b in nodes]
         assert all(len(a) == len(b) for a, b in zip(tn, Tn))
@@ -1408,17 +1433,22 @@ class HipNetwork:
         ptr[1:] = np.cumsum([len(a) for a in tn])
         t_all = np.ascontiguousarray(np.concatenate(tn))
         T_all = np.ascontiguousarray(np.concatenate(Tn))
+        if Ea is not None:
+            return self._ensemble(lib().kin_solve_ensemble_continuous_params, params, K, _pd(u0), _pd(Ea), _pd(A), _p64(ptr), _pd(t_all),
+                                  _pd(T_all), trajectories=trajectories)
         return self._ensemble(lib().kin_solve_ensemble_continuous, params, K, _pd(u0), _p64(ptr), _pd(t_all), _pd(T_all),
                               trajectories=trajectories)
 
-    def solve_ensemble_discrete(self, params: KinParams, u0, stops, trajectories=True):
+    def solve_ensemble_discrete(self, params: KinParams, u0, stops, trajectories=True, Ea=None, A=None):
         """kin_solve_ensemble_discrete: K trajectories under discrete rate updates, member m's rates the Arrhenius rates at
         T_stops held from tstops on (kin_solve's zero-order hold) of its own schedule. u0[K][N]; stops: K pairs
-        (tstops, T_stops) in global time (stop counts may differ).
+        (tstops, T_stops) in global time (stop counts may differ). Ea[K][R], A[K][R]: as in solve_ensemble_continuous
+        (kin_solve_ensemble_discrete_params).
         Returns what solve_ensemble returns: (t[M], u[K][M][N], n_saved[K], retcodes[K], [stats dict] * K); trajectories as there."""
         u0 = np.ascontiguousarray(np.atleast_2d(_f64(u0)))
         K = u0.shape[0]
         assert u0.shape == (K, self.n) and len(stops) == K
+        Ea, A = self._member_arrhenius(K, Ea, A)
         ts = [_f64(a).ravel() for a, _ in stops]
         Ts = [_f64(b).ravel() for _, b in stops]
         assert all(len(a) == len(b) for a, b in zip(ts, Ts))
@@ -1426,6 +1456,9 @@ class HipNetwork:
         ptr[1:] = np.cumsum([len(a) for a in ts])
         t_all = np.ascontiguousarray(np.concatenate(ts))
         T_all = np.ascontiguousarray(np.concatenate(Ts))
+        if Ea is not None:
+            return self._ensemble(lib().kin_solve_ensemble_discrete_params, params, K, _pd(u0), _pd(Ea), _pd(A), _p64(ptr), _pd(t_all),
+                                  _pd(T_all), trajectories=trajectories)
         return self._ensemble(lib().kin_solve_ensemble_discrete, params, K, _pd(u0), _p64(ptr), _pd(t_all), _pd(T_all),
                               trajectories=trajectories)
 

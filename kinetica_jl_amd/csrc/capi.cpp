@@ -535,6 +535,13 @@ void replica_ensemble(kin_network* h, const EnsembleCall& c) {
           rep->has_arrhenius = true; rep->has_kmax = h->has_kmax; rep->k_max = h->k_max; rep->t_mult = h->t_mult;
         }
         for (int64_t m = t; m < K; m += Tn) {
+          if (c.member_params()) {
+            // the member's own (Ea, A) into the replica's arrays, which the next call's copy of the handle's overwrites again;
+            // the handle's own are never written
+            const EnsembleCall::Arrhenius pm = c.member_arrhenius(h, m);
+            KIN_HIP(hipMemcpyAsync(rep->Ea.p, pm.Ea, (size_t)R * sizeof(double), hipMemcpyDeviceToDevice, s));
+            KIN_HIP(hipMemcpyAsync(rep->A.p, pm.A, (size_t)R * sizeof(double), hipMemcpyDeviceToDevice, s));
+          }
           if (c.static_rates()) {
             stage_member_rates(h, c, m, rep->Ea.p, rep->A.p, rep->k.p, s);
             rep->has_rates = true; rep->k_pending = false;
@@ -574,8 +581,7 @@ void replica_ensemble(kin_network* h, const EnsembleCall& c) {
 // (resident.cpp); larger ones: kin_solve calls on host threads (replica_ensemble) or lockstep rounds of batched launches
 // (ensemble.cpp). KIN_ENSEMBLE_ROUTE = threads | lockstep forces a form (A/B runs: tools/ensemble_route_crossover.py);
 // KIN_ENSEMBLE_BATCHED=1 forces the lockstep form of a static call. The lockstep form has no continuous rate updates.
-void run_ensemble(kin_network* h, const EnsembleCall& c) {
-  h->ens.clear();   // (whatever route: its buffers are about to be reallocated or overwritten; set again by a call that succeeds)
+void route_ensemble(kin_network* h, const EnsembleCall& c) {
   const char* e = getenv("KIN_ENSEMBLE_ROUTE");
   const std::string route = e ? e : "";
   const bool force_batched = getenv("KIN_ENSEMBLE_BATCHED") && atoi(getenv("KIN_ENSEMBLE_BATCHED")) != 0;
@@ -592,6 +598,78 @@ void run_ensemble(kin_network* h, const EnsembleCall& c) {
   // with a dense Schur block; KIN_LU_FUSED=0 or a network without hubs has none): the threads then take several members each
   if (c.K <= replica_threads_max() || !ensemble_batched_supported(h, nullptr)) return replica_ensemble(h, c);
   batched_ensemble(h, c);
+}
+
+// A call with per-member Arrhenius parameters has its Ea[K][R], A[K][R] uploaded once, here, into the buffers that stay with the
+// ensemble record (16 K R bytes; reused by later calls); every route reads them through EnsembleCall::member_arrhenius, and
+// kin_ensemble_flux reads them from the record. A shared call takes the route as it is and leaves a shared record.
+void run_ensemble(kin_network* h, const EnsembleCall& c) {
+  h->ens.clear();   // (whatever route: its buffers are about to be reallocated or overwritten; set again by a call that succeeds)
+  if (!c.member_params()) return route_ensemble(h, c);
+  const size_t n = (size_t)c.K * (size_t)h->host.R;
+  try {
+    h->ens_Ea.alloc(n); h->ens_A.alloc(n);
+  } catch (const std::exception& e) {
+    (void)hipGetLastError();
+    throw KinError(ERR_DEVICE, "ensemble: no device memory for the per-member Arrhenius parameters (" + std::to_string(2 * n * sizeof(double)) +
+                                   " bytes): " + e.what());
+  }
+  KIN_HIP(hipMemcpyAsync(h->ens_Ea.p, c.Ea, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  KIN_HIP(hipMemcpyAsync(h->ens_A.p, c.A, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  KIN_HIP(hipStreamSynchronize(h->stream));   // (the thread route's replicas read the blocks on streams of their own)
+  EnsembleCall m = c;
+  m.d_Ea = h->ens_Ea.p; m.d_A = h->ens_A.p;
+  route_ensemble(h, m);
+  if (h->ens.valid()) { h->ens.Ea = h->ens_Ea.p; h->ens.A = h->ens_A.p; }
+}
+
+// kin_solve_ensemble_continuous / _discrete and their _params forms (Ea == A == null: the shared call, bit for bit)
+int ensemble_continuous_entry(kin_network* h, const kin_params* params, int64_t K, const double* u0, const double* Ea, const double* A,
+                              const int64_t* node_ptr, const double* t_nodes, const double* T_nodes, int64_t* n_rows, double* out_t,
+                              double* out_u, int64_t* n_saved, int32_t* retcodes, kin_stats* stats) {
+  if (!h) return KIN_ERR_INVALID_ARG;
+  KIN_TRY(h)
+  require(params && u0 && K >= 1, ERR_INVALID_ARG, "params / u0 is null, or K < 1");
+  require(node_ptr && t_nodes && T_nodes, ERR_INVALID_ARG, "node_ptr / t_nodes / T_nodes is null");
+  require((Ea == nullptr) == (A == nullptr), ERR_INVALID_ARG, "give both per-member Ea and A, or neither");
+  require(res_has_grid(*params), ERR_INVALID_ARG, "an ensemble solve needs a save grid (solve_chunks or save_interval)");
+  for (int64_t m = 0; m < K; m++) {
+    // every member needs a profile of its own: an empty one would leave the controller's T(t) nothing to read
+    require(node_ptr[m] >= 0 && node_ptr[m + 1] - node_ptr[m] >= 2, ERR_INVALID_ARG, "need >= 2 (t, T) nodes per member");
+    validate_solve(h, *params, nullptr, nullptr, nullptr, 0, t_nodes + node_ptr[m], T_nodes + node_ptr[m], node_ptr[m + 1] - node_ptr[m], false);
+  }
+  if (n_rows && !out_u && !n_saved) { *n_rows = make_res_grid(*params).cap; }   // size query
+  else {
+    EnsembleCall c{*params, K, u0, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, node_ptr, t_nodes, T_nodes, n_rows, out_t, out_u,
+                   n_saved, retcodes, stats};
+    c.Ea = Ea; c.A = A;
+    run_ensemble(h, c);
+  }
+  KIN_CATCH(h)
+}
+
+int ensemble_discrete_entry(kin_network* h, const kin_params* params, int64_t K, const double* u0, const double* Ea, const double* A,
+                            const int64_t* stop_ptr, const double* tstops, const double* T_stops, int64_t* n_rows, double* out_t,
+                            double* out_u, int64_t* n_saved, int32_t* retcodes, kin_stats* stats) {
+  if (!h) return KIN_ERR_INVALID_ARG;
+  KIN_TRY(h)
+  require(params && u0 && K >= 1, ERR_INVALID_ARG, "params / u0 is null, or K < 1");
+  require(stop_ptr && tstops && T_stops, ERR_INVALID_ARG, "stop_ptr / tstops / T_stops is null");
+  require((Ea == nullptr) == (A == nullptr), ERR_INVALID_ARG, "give both per-member Ea and A, or neither");
+  require(res_has_grid(*params), ERR_INVALID_ARG, "an ensemble solve needs a save grid (solve_chunks or save_interval)");
+  for (int64_t m = 0; m < K; m++) {
+    // every member needs a stop of its own: the controller's rates in force before the first stop are those of stop 0
+    require(stop_ptr[m] >= 0 && stop_ptr[m + 1] - stop_ptr[m] >= 1, ERR_INVALID_ARG, "need >= 1 stop per member");
+    validate_solve(h, *params, tstops + stop_ptr[m], T_stops + stop_ptr[m], nullptr, stop_ptr[m + 1] - stop_ptr[m], nullptr, nullptr, 0, false);
+  }
+  if (n_rows && !out_u && !n_saved) { *n_rows = make_res_grid(*params).cap; }   // size query
+  else {
+    EnsembleCall c{*params, K, u0, nullptr, nullptr, tstops, T_stops, nullptr, 0, stop_ptr, nullptr, nullptr, nullptr, n_rows, out_t,
+                   out_u, n_saved, retcodes, stats};
+    c.Ea = Ea; c.A = A;
+    run_ensemble(h, c);
+  }
+  KIN_CATCH(h)
 }
 
 }  // namespace
@@ -620,40 +698,28 @@ int kin_solve_ensemble_continuous(kin_network* h, const kin_params* params, int6
                                   const int64_t* node_ptr, const double* t_nodes, const double* T_nodes,
                                   int64_t* n_rows, double* out_t, double* out_u, int64_t* n_saved,
                                   int32_t* retcodes, kin_stats* stats) {
-  if (!h) return KIN_ERR_INVALID_ARG;
-  KIN_TRY(h)
-  require(params && u0 && K >= 1, ERR_INVALID_ARG, "params / u0 is null, or K < 1");
-  require(node_ptr && t_nodes && T_nodes, ERR_INVALID_ARG, "node_ptr / t_nodes / T_nodes is null");
-  require(res_has_grid(*params), ERR_INVALID_ARG, "an ensemble solve needs a save grid (solve_chunks or save_interval)");
-  for (int64_t m = 0; m < K; m++) {
-    // every member needs a profile of its own: an empty one would leave the controller's T(t) nothing to read
-    require(node_ptr[m] >= 0 && node_ptr[m + 1] - node_ptr[m] >= 2, ERR_INVALID_ARG, "need >= 2 (t, T) nodes per member");
-    validate_solve(h, *params, nullptr, nullptr, nullptr, 0, t_nodes + node_ptr[m], T_nodes + node_ptr[m], node_ptr[m + 1] - node_ptr[m], false);
-  }
-  if (n_rows && !out_u && !n_saved) { *n_rows = make_res_grid(*params).cap; }   // size query
-  else run_ensemble(h, {*params, K, u0, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, node_ptr, t_nodes, T_nodes, n_rows, out_t, out_u,
-                        n_saved, retcodes, stats});
-  KIN_CATCH(h)
+  return ensemble_continuous_entry(h, params, K, u0, nullptr, nullptr, node_ptr, t_nodes, T_nodes, n_rows, out_t, out_u, n_saved, retcodes, stats);
+}
+
+int kin_solve_ensemble_continuous_params(kin_network* h, const kin_params* params, int64_t K, const double* u0, const double* Ea,
+                                         const double* A, const int64_t* node_ptr, const double* t_nodes, const double* T_nodes,
+                                         int64_t* n_rows, double* out_t, double* out_u, int64_t* n_saved, int32_t* retcodes,
+                                         kin_stats* stats) {
+  return ensemble_continuous_entry(h, params, K, u0, Ea, A, node_ptr, t_nodes, T_nodes, n_rows, out_t, out_u, n_saved, retcodes, stats);
 }
 
 int kin_solve_ensemble_discrete(kin_network* h, const kin_params* params, int64_t K, const double* u0,
                                 const int64_t* stop_ptr, const double* tstops, const double* T_stops,
                                 int64_t* n_rows, double* out_t, double* out_u, int64_t* n_saved,
                                 int32_t* retcodes, kin_stats* stats) {
-  if (!h) return KIN_ERR_INVALID_ARG;
-  KIN_TRY(h)
-  require(params && u0 && K >= 1, ERR_INVALID_ARG, "params / u0 is null, or K < 1");
-  require(stop_ptr && tstops && T_stops, ERR_INVALID_ARG, "stop_ptr / tstops / T_stops is null");
-  require(res_has_grid(*params), ERR_INVALID_ARG, "an ensemble solve needs a save grid (solve_chunks or save_interval)");
-  for (int64_t m = 0; m < K; m++) {
-    // every member needs a stop of its own: the controller's rates in force before the first stop are those of stop 0
-    require(stop_ptr[m] >= 0 && stop_ptr[m + 1] - stop_ptr[m] >= 1, ERR_INVALID_ARG, "need >= 1 stop per member");
-    validate_solve(h, *params, tstops + stop_ptr[m], T_stops + stop_ptr[m], nullptr, stop_ptr[m + 1] - stop_ptr[m], nullptr, nullptr, 0, false);
-  }
-  if (n_rows && !out_u && !n_saved) { *n_rows = make_res_grid(*params).cap; }   // size query
-  else run_ensemble(h, {*params, K, u0, nullptr, nullptr, tstops, T_stops, nullptr, 0, stop_ptr, nullptr, nullptr, nullptr, n_rows, out_t,
-                        out_u, n_saved, retcodes, stats});
-  KIN_CATCH(h)
+  return ensemble_discrete_entry(h, params, K, u0, nullptr, nullptr, stop_ptr, tstops, T_stops, n_rows, out_t, out_u, n_saved, retcodes, stats);
+}
+
+int kin_solve_ensemble_discrete_params(kin_network* h, const kin_params* params, int64_t K, const double* u0, const double* Ea,
+                                       const double* A, const int64_t* stop_ptr, const double* tstops, const double* T_stops,
+                                       int64_t* n_rows, double* out_t, double* out_u, int64_t* n_saved, int32_t* retcodes,
+                                       kin_stats* stats) {
+  return ensemble_discrete_entry(h, params, K, u0, Ea, A, stop_ptr, tstops, T_stops, n_rows, out_t, out_u, n_saved, retcodes, stats);
 }
 
 int kin_newton_solve(kin_network* h, double c, const double* u, const double* b, double* x) {

@@ -221,6 +221,10 @@ FluxSource drg_ensemble_source(kin_network* h, const double* k, int64_t n_k_rows
   require(cap < ((int64_t)1 << 31) && K < ((int64_t)1 << 31) && B < ((int64_t)1 << 31), ERR_UNSUPPORTED,
           "ensemble DRG pass: K n_rows beyond 32-bit offsets");
   drg_check(h, B, k != nullptr, k_row != nullptr, T_rows != nullptr, have_out);
+  // stage 1 forms the rate constants of all K n_rows states in one unsegmented pass from the handle's one (Ea, A)
+  require(!(T_rows && h->ens.member_params()), ERR_UNSUPPORTED,
+          "the stored ensemble was solved with per-member Arrhenius parameters: T_rows would use the handle's; give the rate "
+          "constants explicitly (k with k_row, one kin_arrhenius_eval row per member and temperature)");
   if (k && k_row) require(n_k_rows >= 1, ERR_INVALID_ARG, "k has no rows");
   else if (k) require(n_k_rows == B, ERR_INVALID_ARG, "k without k_row needs one row per saved row (n_k_rows == K n_rows)");
   // Stage 1 runs over every row of the record; the keys of the rows past a member's saved ones are ignored by contract, so

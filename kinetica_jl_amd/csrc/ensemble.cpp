@@ -149,7 +149,7 @@ struct EnsembleSolver {
     if (h_drift) (void)hipHostFree(h_drift);
   }
 
-  void prepare(int K_, int slots_, int64_t cap_) {
+  void prepare(int K_, int slots_, int64_t cap_, const EnsembleCall& call) {
     hipStream_t s = h->stream;
     auto al = [](size_t x) { return (x + 7) / 8 * 8; };
     const size_t n = (size_t)N, r = (size_t)R;
@@ -196,6 +196,8 @@ struct EnsembleSolver {
       q.k = w; w += al(r);
       q.part = w;
       q.ctrl = d_ctrl.p + t;
+      const EnsembleCall::Arrhenius pm = call.member_arrhenius(h, t);
+      q.Ea = pm.Ea; q.A = pm.A;
     }
     d_reps.upload(reps.data(), (size_t)K, s);
     slots.resize(K);
@@ -259,7 +261,7 @@ struct EnsembleSolver {
       ens_change_D(N, d_reps.p, d_ops.p + K, nc, s);
       const EnsOp* dO = d_ops.p + 2 * K;
       ens_vec(N, d_reps.p, dO + first[K_VEC], count(K_VEC), s);
-      ens_apply_rates(R, h->Ea.p, h->A.p, h->has_kmax ? 1 : 0, h->k_max, h->t_mult, d_reps.p, dO + first[K_APPLY_RATES], count(K_APPLY_RATES), s);
+      ens_apply_rates(R, h->has_kmax ? 1 : 0, h->k_max, h->t_mult, d_reps.p, dO + first[K_APPLY_RATES], count(K_APPLY_RATES), s);
       ens_rhs(N, R, h->x0.p, h->x1.p, h->rhs_plan.view(), d_reps.p, dO + first[K_RHS], count(K_RHS), s);
       ens_jac(R, h->x0.p, h->x1.p, h->jac_plan.view(), d_reps.p, dO + first[K_JAC], count(K_JAC), s);
       ens_norms(N, d_reps.p, dO + first[K_NORMS], count(K_NORMS), s);
@@ -633,7 +635,7 @@ static int64_t batched_ensemble_block(kin_network* h, const EnsembleCall& c, int
   const ResGrid g = make_res_grid(c.p);
   if (c.n_rows) *c.n_rows = g.cap;
   const int slots = res_lu_slots(E.lu.slot_bytes(), K);
-  E.prepare((int)K, slots, g.cap);
+  E.prepare((int)K, slots, g.cap, c);
   ResParams P{};
   res_fill_params(P, c.p, g);
   res_default_settings(P, slots);
@@ -725,6 +727,7 @@ void batched_ensemble(kin_network* h, const EnsembleCall& c) {
     if (c.k) b.k = c.k + m0 * R;
     if (c.T) b.T = c.T + m0;
     if (c.stop_ptr) b.stop_ptr = c.stop_ptr + m0;   // (member_stops reads tstops / T_stops at the absolute offsets)
+    if (c.d_Ea) { b.Ea = c.Ea + m0 * R; b.A = c.A + m0 * R; b.d_Ea = c.d_Ea + m0 * R; b.d_A = c.d_A + m0 * R; }
     b.out_t = tt.data();
     if (c.out_u) b.out_u = c.out_u + m0 * cap * N;
     if (c.n_saved) b.n_saved = c.n_saved + m0;

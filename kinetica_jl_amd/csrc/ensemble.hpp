@@ -17,6 +17,7 @@ namespace kin {
 struct EnsRep {
   double *D, *y, *psi, *d, *scale, *f0, *f1, *ytmp, *cs, *jv, *rate, *dr, *k, *part;
   BdfCtrl* ctrl;
+  const double *Ea, *A;   // the member's Arrhenius parameters: its rows of a per-member call's blocks, else the handle's arrays
 };
 
 // one entry of a round's list
@@ -42,8 +43,8 @@ void ens_norms(int N, const EnsRep* reps, const EnsOp* d_ops, int n, hipStream_t
 // right-hand side: i0 = 0: y -> f0, 1: ytmp -> f1, 2: ytmp -> f0
 void ens_rhs(int N, int R, const int32_t* x0, const int32_t* x1, const SegPlanView& rhs_plan, const EnsRep* reps, const EnsOp* d_ops, int n, hipStream_t s);
 void ens_jac(int R, const int32_t* x0, const int32_t* x1, const SegPlanView& jac_plan, const EnsRep* reps, const EnsOp* d_ops, int n, hipStream_t s);
-// rate constants: i0 = 1: copy of the row `out`; 2: Arrhenius at temperature d0
-void ens_apply_rates(int R, const double* Ea, const double* A, int has_kmax, double k_max, double t_mult, const EnsRep* reps, const EnsOp* d_ops, int n, hipStream_t s);
+// rate constants: i0 = 1: copy of the row `out`; 2: Arrhenius at temperature d0 from the member's EnsRep::Ea / A
+void ens_apply_rates(int R, int has_kmax, double k_max, double t_mult, const EnsRep* reps, const EnsOp* d_ops, int n, hipStream_t s);
 // a corrector attempt of every entry: predictor + `iters` iterations (each: rates, residual, the fused solve's three stages,
 // update + decision; launches behind a member's decision are no-ops for it)
 struct EnsSolveTables {

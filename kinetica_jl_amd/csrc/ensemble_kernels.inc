@@ -86,14 +86,14 @@ __global__ __launch_bounds__(256) void e_drates_kernel(int R, const int32_t* __r
   reinterpret_cast<double2*>(r.dr)[q] = mass_action_drates(r.k[q], r.y, x0[q], x1[q]);
 }
 
-__global__ __launch_bounds__(256) void e_apply_rates_kernel(int R, const double* __restrict__ Ea, const double* __restrict__ A, int has_kmax,
+__global__ __launch_bounds__(256) void e_apply_rates_kernel(int R, int has_kmax,
                                                             double k_max, double t_mult, const EnsRep* __restrict__ reps,
                                                             const EnsOp* __restrict__ ops) {
   ENS_ENTRY;
   const int q = blockIdx.x * 256 + threadIdx.x;
   if (q >= R) return;
   if (o.i0 == 1) r.k[q] = o.out[q];
-  else r.k[q] = arrhenius_one(Ea[q], A[q], 8.314462618 * o.d0, has_kmax, k_max, t_mult);
+  else r.k[q] = arrhenius_one(r.Ea[q], r.A[q], 8.314462618 * o.d0, has_kmax, k_max, t_mult);
 }
 
 // segmented gather-sum of the entry (kernels.hip: segsum_kernel). SEL 0: rates -> f0 / f1 (i0 == 1: f1); 1: operand
@@ -182,8 +182,8 @@ void ens_jac(int R, const int32_t* x0, const int32_t* x1, const SegPlanView& jac
   hipLaunchKernelGGL(e_drates_kernel, ENS_GRID(R, n), 0, s, R, x0, x1, reps, d_ops);
   launch_e_segsum<SEG_COEF_SET, 1>(jac_plan, reps, d_ops, n, s);
 }
-void ens_apply_rates(int R, const double* Ea, const double* A, int has_kmax, double k_max, double t_mult, const EnsRep* reps, const EnsOp* d_ops, int n, hipStream_t s) {
-  if (n > 0) hipLaunchKernelGGL(e_apply_rates_kernel, ENS_GRID(R, n), 0, s, R, Ea, A, has_kmax, k_max, t_mult, reps, d_ops);
+void ens_apply_rates(int R, int has_kmax, double k_max, double t_mult, const EnsRep* reps, const EnsOp* d_ops, int n, hipStream_t s) {
+  if (n > 0) hipLaunchKernelGGL(e_apply_rates_kernel, ENS_GRID(R, n), 0, s, R, has_kmax, k_max, t_mult, reps, d_ops);
 }
 void ens_predict(const EnsSolveTables& T, const EnsRep* reps, const EnsOp* d_ops, int n, hipStream_t s) {
   if (n > 0) hipLaunchKernelGGL(e_predict_kernel, ENS_GRID(T.N, n), 0, s, T.N, T.cf, reps, d_ops);

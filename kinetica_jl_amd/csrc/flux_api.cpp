@@ -77,8 +77,10 @@ void flux_check_rows(const int64_t* k_row, int64_t B, int64_t n_rows) {
 namespace {
 
 // The segmented pass on device buffers (kin_flux_segmented*, kin_ensemble_flux): ONE launch that writes d_flux[S][R] itself.
+// member_Ea / member_A: per-segment Arrhenius parameters [S][R] for the temperature form (a per-member ensemble record); null:
+// the handle's own
 void flux_seg_run(kin_network* h, int64_t S, int64_t L, const int64_t* d_seg_n, const double* d_u, const FluxSource& src,
-                  const double* d_w, double* d_flux, hipStream_t s) {
+                  const double* d_w, double* d_flux, hipStream_t s, const double* member_Ea = nullptr, const double* member_A = nullptr) {
   const int64_t N = h->host.N, R = h->host.R;
   if (S * L == 0 || R == 0) {
     if (S * R > 0) KIN_HIP(hipMemsetAsync(d_flux, 0, (size_t)S * (size_t)R * sizeof(double), s));
@@ -98,6 +100,7 @@ void flux_seg_run(kin_network* h, int64_t S, int64_t L, const int64_t* d_seg_n, 
   else if (src.k) { a.k = src.k; a.k_stride = src.k_stride; a.k_row = src.k_row; }
   else { a.k = h->k.p; a.k_stride = 0; a.k_row = nullptr; }
   a.Ea = h->Ea.p; a.A = h->A.p; a.has_kmax = h->has_kmax ? 1 : 0; a.k_max = h->k_max; a.t_mult = h->t_mult;
+  if (member_Ea) { a.Ea = member_Ea; a.A = member_A; a.par_stride = R; }
   a.w = d_w;
   a.flux = d_flux;
   launch_flux_seg(plan, a, s);
@@ -310,7 +313,7 @@ int kin_ensemble_flux(kin_network* h, const double* w, const double* k, int64_t 
   if (w) h->f_w.upload(w, (size_t)B, s);
   h->f_flux.alloc((size_t)K * R);
   flux_seg_run(h, K, cap, h->ens_segn.p, h->ens.sol, FluxSource{k ? h->f_k.p : nullptr, R, k_row ? h->f_krow.p : nullptr, T_rows ? h->f_T.p : nullptr},
-               w ? h->f_w.p : nullptr, h->f_flux.p, s);
+               w ? h->f_w.p : nullptr, h->f_flux.p, s, h->ens.Ea, h->ens.A);   // (a per-member record: each member's own Ea / A)
   h->f_flux.download(flux, (size_t)K * R, s);
   KIN_HIP(hipStreamSynchronize(s));
   KIN_CATCH(h)

@@ -252,8 +252,11 @@ __global__ __launch_bounds__(FLUX_BS) void flux_seg_kernel(FluxSegArgs a) {
     if (LDS) ix[i] = a.idx16[jc]; else jx[i] = a.idx32[jc];
     if (MODE == FLUX_T) {
       const int r0 = min(2 * jc, Rm1), r1 = min(2 * jc + 1, Rm1);
-      ea[i] = make_double2(a.Ea[r0], a.Ea[r1]);
-      aa[i] = make_double2(a.A[r0], a.A[r1]);
+      // (the segment's own parameters: blockIdx.x par_stride doubles behind the base; stride 0: the shared rows)
+      const double* Ea = a.Ea + (size_t)blockIdx.x * (size_t)a.par_stride;
+      const double* A = a.A + (size_t)blockIdx.x * (size_t)a.par_stride;
+      ea[i] = make_double2(Ea[r0], Ea[r1]);
+      aa[i] = make_double2(A[r0], A[r1]);
     }
   }
   double2 acc[ROWS], kk[ROWS];

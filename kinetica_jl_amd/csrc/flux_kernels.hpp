@@ -70,6 +70,7 @@ struct FluxSegArgs {
   const double* Ea; const double* A; int has_kmax; double k_max, t_mult;
   const double* w;                 // w[S L] or null (weights 1)
   double* flux;                    // flux[S][R]
+  int64_t par_stride;              // MODE T: segment s reads Ea / A from s par_stride doubles behind the base (0: one shared pair of rows)
 };
 void launch_flux_seg(const FluxPlan& plan, const FluxSegArgs& a, hipStream_t s);
 // umax[s][i] = max over j < seg_n[s] of u[s L + j][i]; zeros for an empty segment

@@ -150,10 +150,15 @@ struct kin_network {
     const double* sol = nullptr;
     int64_t K = 0, cap = 0;
     std::vector<int64_t> n_saved;
+    // solved with per-member Arrhenius parameters (kin_solve_ensemble_*_params): Ea[K][R], A[K][R] on the device (ens_Ea / ens_A,
+    // which only the next per-member call overwrites); null for a record of shared parameters
+    const double *Ea = nullptr, *A = nullptr;
     bool valid() const { return sol != nullptr && K > 0; }
-    void clear() { sol = nullptr; K = 0; cap = 0; n_saved.clear(); }
+    bool member_params() const { return Ea != nullptr; }
+    void clear() { sol = nullptr; K = 0; cap = 0; n_saved.clear(); Ea = nullptr; A = nullptr; }
   } ens;
   kin::DevBuf<double> ens_sol, ens_w, ens_out;   // handle-owned copy of the saved states; workspaces of kin_ensemble_max / _dot
+  kin::DevBuf<double> ens_Ea, ens_A;             // the per-member parameter blocks of a kin_solve_ensemble_*_params call, reused across calls
   kin::DevBuf<int64_t> ens_segn;                 // n_saved[K] on the device
   void set_ensemble_record(const double* sol, int64_t K, int64_t cap, std::vector<int64_t> n_saved) {
     ens.sol = sol; ens.K = K; ens.cap = cap; ens.n_saved = std::move(n_saved);

@@ -124,6 +124,7 @@ struct ResidentSolver {
       q.sol = own_sol ? d_sol.p + (size_t)t * (size_t)sol_rows * N : nullptr;
       q.sol_t = d_solt.p + (size_t)t * (size_t)sol_rows;
       q.result = d_res.p + t;
+      q.Ea = h->Ea.p; q.A = h->A.p;   // (run_resident points a per-member call's members at their own rows)
     }
   }
 };
@@ -177,6 +178,11 @@ void run_resident(kin_network* h, ResidentSolver& RS, const EnsembleCall& c, con
       RS.h_traj[t].T_stops = c.k_table ? nullptr : RS.d_Tstops.p + (ms.T_stops - s0.T_stops);
       RS.h_traj[t].n_stops = ms.n;
     }
+  }
+  // each member's Arrhenius parameters: its rows of a per-member call's blocks, the handle's arrays for a shared call
+  for (int t = 0; t < K; t++) {
+    const EnsembleCall::Arrhenius pm = c.member_arrhenius(h, t);
+    RS.h_traj[t].Ea = pm.Ea; RS.h_traj[t].A = pm.A;
   }
   RS.hn.Ea = h->Ea.p; RS.hn.A = h->A.p; RS.hn.has_kmax = h->has_kmax ? 1 : 0; RS.hn.k_max = h->k_max; RS.hn.t_mult = h->t_mult;
   RS.d_net.upload(&RS.hn, 1, s);

@@ -329,7 +329,7 @@ RES_PHASE void ph_apply_rates(long long stop) {
     for (int r = threadIdx.x; r < R; r += RES_WG) k[r] = src[r];
   } else if (g_cx.rate_mode == 2) {
     const double RT = 8.314462618 * glob(g_cx.T.T_stops)[stop];
-    gcd_t* Ea = glob(net->Ea); gcd_t* A = glob(net->A);
+    gcd_t* Ea = glob(g_cx.T.Ea); gcd_t* A = glob(g_cx.T.A);
     const int has_kmax = g_cx.has_kmax; const double k_max = g_cx.k_max, t_mult = g_cx.t_mult;
     for (int r = threadIdx.x; r < R; r += RES_WG) k[r] = arrhenius_one(Ea[r], A[r], RT, has_kmax, k_max, t_mult);
   }
@@ -340,9 +340,8 @@ RES_PHASE void ph_apply_rates(long long stop) {
 RES_PHASE void ph_apply_T(double T) {
   const int R = uni(g_cx.R);
   gd_t* k = glob(g_cx.T.k);
-  const ResNetDev* net = g_cx.net;
   const double RT = 8.314462618 * T;
-  gcd_t* Ea = glob(net->Ea); gcd_t* A = glob(net->A);
+  gcd_t* Ea = glob(g_cx.T.Ea); gcd_t* A = glob(g_cx.T.A);
   const int has_kmax = g_cx.has_kmax; const double k_max = g_cx.k_max, t_mult = g_cx.t_mult;
   for (int r = threadIdx.x; r < R; r += RES_WG) k[r] = arrhenius_one(Ea[r], A[r], RT, has_kmax, k_max, t_mult);
   __syncthreads();

@@ -21,7 +21,7 @@ struct ResNetDev {
   const int32_t *x0, *x1, *jmap, *ent_pivot, *yloc, *xloc, *j_diag;
   const int32_t *mono_ent_ptr, *mono_ptr, *mono_fac, *mono_dst;
   const float* mono_sign;
-  const double *Ea, *A;            // rate_mode 2
+  const double *Ea, *A;            // the handle's Arrhenius parameters (the kernel reads each member's ResTrajDev::Ea / A)
   const double* k_table;           // rate_mode 1 (rate_mode 2 reads each member's ResTrajDev::T_stops)
   int32_t round_e0[RES_MAX_ROUNDS + 1];   // first L entry of every elimination round
   SegPlanView rhs_plan, jac_plan, resid_plan, lz_build, nvu_build, stageA, stageC, fwdZ, fwd_dense, bwdT, bwdV;
@@ -41,6 +41,10 @@ struct ResTrajDev {
   int64_t n_nodes;
   const double *tstops, *T_stops;    // rate_mode 1 / 2: this member's stops (ResParams::tstops, n_stops); T_stops: rate_mode 2
   int64_t n_stops;
+  // rate_mode 2 / 3: this member's Arrhenius parameters - its rows of a per-member call's blocks, else the handle's arrays
+  // (run_resident sets them for every member; appended, so code that fills the fields above stays as it is, and without
+  // initialisers: the kernel keeps a copy of this struct in LDS, which takes no constructor)
+  const double *Ea, *A;
 };
 
 // enqueues the solve of K trajectories (grid = K workgroups of RES_WG = 512 threads)

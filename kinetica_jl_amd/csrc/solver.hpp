@@ -12,6 +12,8 @@ namespace kin {
 // members (tstops + T_stops or k_table, n_stops of them); with stop_ptr, discrete rate updates of each member's own: member m
 // holds the Arrhenius rates at T_stops[j] from tstops[j] on, j in [stop_ptr[m], stop_ptr[m + 1]) of the concatenated arrays; or,
 // with node_ptr, continuous rate updates: member m's rates at T(t) of its own profile (t_nodes, T_nodes)[node_ptr[m] .. node_ptr[m + 1]).
+// The last two forms may carry Arrhenius parameters of each member's own, Ea[K][R] / A[K][R] (kin_solve_ensemble_*_params): every
+// route reads a member's parameters through member_arrhenius only, as it reads its stops through member_stops.
 // Outputs (each may be null): n_rows = cap (rows of the save grid), out_t[cap], out_u[K][cap][N], n_saved[K], retcodes[K], stats[K].
 struct EnsembleCall {
   kin_params p;
@@ -27,6 +29,17 @@ struct EnsembleCall {
   int64_t* n_saved;
   int32_t* retcodes;
   kin_stats* stats;
+  // per-member Arrhenius parameters of a continuous / per-member-stops call (kin_solve_ensemble_*_params): the caller's
+  // Ea[K][R], A[K][R] (both or neither), and their device copies, which run_ensemble uploads before a route sees the call
+  const double *Ea = nullptr, *A = nullptr;
+  const double *d_Ea = nullptr, *d_A = nullptr;
+  bool member_params() const { return Ea != nullptr; }
+  // member m's Arrhenius parameters on the device: its rows of the per-member blocks, else the handle's own arrays
+  struct Arrhenius { const double *Ea, *A; };
+  Arrhenius member_arrhenius(const kin_network* h, int64_t m) const {
+    if (!d_Ea) return {h->Ea.p, h->A.p};
+    return {d_Ea + m * h->host.R, d_A + m * h->host.R};
+  }
   bool continuous() const { return node_ptr != nullptr; }
   bool static_rates() const { return n_stops == 0 && !stop_ptr && !node_ptr; }   // the members' own k / T / the handle's k for the whole span
   // member m's discrete rate updates: its slice of the concatenated stops, else the shared ones (n = 0: none)

@@ -25,7 +25,7 @@ from .synth import FlatNetwork, from_lists
 __all__ = ["SpeciesData", "RxData", "RxFilter", "get_filter_mask", "DummyKineticCalculator",
            "PrecalculatedArrheniusCalculator", "PrecalculatedLindemannCalculator", "allows_continuous",
            "has_conditions", "setup_network", "ODESimulationParams", "StaticODESolve", "VariableODESolve",
-           "HIPBDF", "HIPRK45", "ArrheniusRates", "solve_network", "identify_next_seeds", "insert_inert", "ODESolveOutput", "ODESolution", "tconvert", "make_u0", "apply_low_k_cutoff",
+           "HIPBDF", "HIPRK45", "ArrheniusRates", "solve_network", "sample_arrhenius", "identify_next_seeds", "insert_inert", "ODESolveOutput", "ODESolution", "tconvert", "make_u0", "apply_low_k_cutoff",
            "get_max_rates", "get_initial_rates", "calculate_discrete_rates",
            "solve_network_ensemble",   # EXTENSION: the reference has no ensemble call
            "flux_weights", "held_stop_index", "ReactionFluxes", "reaction_fluxes", "ensemble_flux_sources",   # EXTENSION: post-hoc flux analysis
@@ -708,22 +708,39 @@ def _same_calculator(a, b):
                       and a.t_mult == b.t_mult)
 
 
-def apply_ensemble_low_k_cutoff(rd, calc, pars, condition_sets):
+def _calculator_mismatch(a, b):
+    """What keeps two Arrhenius calculators out of one ensemble call (None: nothing; they may differ in the VALUES of Ea / A):
+    the type, the number of reactions, k_max and t_mult are the handle's, one for all members."""
+    if type(a) is not type(b):
+        return "type"
+    if len(a.Ea) != len(b.Ea) or len(a.A) != len(b.A):
+        return "length"
+    if a.k_max != b.k_max:
+        return "k_max"
+    if a.t_mult != b.t_mult:
+        return "t_mult"
+    return None
+
+
+def apply_ensemble_low_k_cutoff(rd, calc, pars, condition_sets, calculators=None):
     """apply_low_k_cutoff! over an ensemble (EXTENSION, solve_network_ensemble): a reaction is removed only if every condition
-    set's cutoff removes it. Mutates rd and the calculator as apply_low_k_cutoff does; returns the removed positions."""
+    set's cutoff removes it. calculators: one per condition set when the members' Arrhenius parameters differ (each member's
+    maximum rates are then its own calculator's); None: `calc` for all. Mutates rd and `calc` as apply_low_k_cutoff does;
+    returns the removed positions."""
     if pars.low_k_cutoff == "none":
         return np.zeros(0, dtype=int)
     k_cutoff = pars.reltol / pars.tspan[-1] if pars.low_k_cutoff == "auto" else float(pars.low_k_cutoff)
     low = np.ones(rd.nr, bool)
-    for cs in condition_sets:
-        low &= get_max_rates(cs, calc) * pars.low_k_maxconc ** 2 < k_cutoff
+    for i, cs in enumerate(condition_sets):
+        low &= get_max_rates(cs, calc if calculators is None else calculators[i]) * pars.low_k_maxconc ** 2 < k_cutoff
     rids = np.nonzero(low)[0]
     rd.splice(rids)
     calc.splice(rids)
     return rids
 
 
-def solve_network_ensemble(methods, sd, rd, copy_network=True, fluxes=False, trajectories=True, statistics=None):
+def solve_network_ensemble(methods, sd, rd, copy_network=True, fluxes=False, trajectories=True, statistics=None,
+                           member_calculators=False):
     """EXTENSION (the reference has no ensemble call: it solves member after member through solve_network): K
     `VariableODESolve`s with Arrhenius condition sets - one temperature profile each, e.g. a set of heating rates or start
     temperatures - on one network in ONE ensemble call: kin_solve_ensemble_continuous when every set is continuous,
@@ -732,7 +749,14 @@ def solve_network_ensemble(methods, sd, rd, copy_network=True, fluxes=False, tra
     per member.
 
     The methods must share the calculator, the filter and every ODESimulationParams field except u0, and all be continuous or
-    all discrete-update sets (ValueError otherwise, before anything touches the GPU). solve_network's pipeline runs once: every
+    all discrete-update sets (ValueError otherwise, before anything touches the GPU).
+
+    member_calculators=True: the methods' calculators must agree in type, length, k_max and t_mult only (ValueError otherwise)
+    and may differ in the VALUES of Ea / A - uncertain barriers and prefactors; sample_arrhenius builds such calculators from a
+    design. Every member is then solved with its own parameters (kin_solve_ensemble_*_params), its low-k cutoff uses its own
+    calculator's maximum rates, sol_k of a discrete member and fluxes=True (kin_ensemble_flux on the per-member record) use its
+    own parameters too. With calculators equal in value the call is exactly the one made without the flag, no Ea / A passed.
+    The default keeps the refusal: calculators that differ by mistake are not silently solved as a design. solve_network's pipeline runs once: every
     member's solve_variable_conditions, filter, splice, setup_network!, low-k cutoff, then the members' u0. The low-k cutoff
     removes a reaction only if EVERY member's cutoff (its own condition set's maximum rates, apply_low_k_cutoff) removes it:
     when the members agree, the network is exactly the one solve_network builds for each; otherwise a member may keep
@@ -774,8 +798,13 @@ def solve_network_ensemble(methods, sd, rd, copy_network=True, fluxes=False, tra
             raise ValueError("solver='RK45' is not available with continuous rate updates; use the default BDF"
                              if not m.conditions.discrete_updates else
                              "solver='RK45' is not available in an ensemble (BDF only); use the default BDF or solve_network")
-        if not _same_calculator(m.calculator, m0.calculator):
-            raise ValueError("the methods of an ensemble must share the calculator")
+        why = _calculator_mismatch(m.calculator, m0.calculator)
+        if why is not None:
+            raise ValueError(f"the calculators of an ensemble's methods may differ in the values of Ea / A only ({why} differs: the "
+                             "handle has one k_max, one t_mult and one network for all members)")
+        if not member_calculators and not _same_calculator(m.calculator, m0.calculator):
+            raise ValueError("the methods of an ensemble must share the calculator; pass member_calculators=True to solve every "
+                             "member with the Ea / A of its own calculator")
         if not _same_filter(m.filter, m0.filter):
             raise ValueError("the methods of an ensemble must share the filter")
         for f in dataclasses.fields(ODESimulationParams):
@@ -783,13 +812,16 @@ def solve_network_ensemble(methods, sd, rd, copy_network=True, fluxes=False, tra
                 raise ValueError(f"the methods of an ensemble must share every ODESimulationParams field except u0 ({f.name} differs)")
     discrete = m0.conditions.discrete_updates
     pars, calc = m0.pars, m0.calculator
+    # calculators that differ in value: every member's own (Ea, A) goes to the call; all equal: the call as it always was
+    per_member = member_calculators and not all(_same_calculator(m.calculator, calc) for m in methods)
     sd_a, rd_a = (copy.deepcopy(sd), copy.deepcopy(rd)) if copy_network else (sd, rd)
     for m in methods:
         solve_variable_conditions(m.conditions, m.pars)
     mask = get_filter_mask(m0.filter, sd_a, rd_a)
     rd_a.splice(np.nonzero(mask)[0])
     setup_network(sd_a, rd_a, calc)
-    rids = apply_ensemble_low_k_cutoff(rd_a, calc, pars, [m.conditions for m in methods])
+    rids = apply_ensemble_low_k_cutoff(rd_a, calc, pars, [m.conditions for m in methods],
+                                       calculators=[m.calculator for m in methods] if per_member else None)
     # members may carry distinct (equal) calculator objects: each is spliced, as its own solve_network would splice it
     spliced = [calc]
     for m in methods:
@@ -817,6 +849,8 @@ def solve_network_ensemble(methods, sd, rd, copy_network=True, fluxes=False, tra
     try:
         h.set_arrhenius(calc.Ea, calc.A, calc.k_max, calc.t_mult)
         kw = {} if trajectories else dict(trajectories=False)   # (the defaults: the call as it always was)
+        if per_member:      # gathered after splicing: row i is member i's calculator as the network is solved
+            kw.update(Ea=np.array([m.calculator.Ea for m in methods]), A=np.array([m.calculator.A for m in methods]))
         if discrete:
             t, u, ns, rcs, sts = h.solve_ensemble_discrete(pars.to_kin_params(), U0, stops, **kw)
         else:
@@ -979,7 +1013,10 @@ def sobol_design(M, P, seed=0, A=None, B=None):
     Building the ensemble from it: map every column to its parameter with any per-column transform - a log-multiplier
     k[:, r] = k0[r] * exp(s * (X[:, p] - 0.5)), a temperature T = T_lo + (T_hi - T_lo) * X[:, p], a heating rate - and give the
     K rows to the ensemble call IN THIS ORDER: k[K][R] (and T[K]) to HipNetwork.solve_ensemble, or one VariableODESolve per
-    row to solve_network_ensemble(methods, ..., statistics=dict(sobol=dict(M=M, P=P)))."""
+    row to solve_network_ensemble(methods, ..., statistics=dict(sobol=dict(M=M, P=P))). A design over RATE PARAMETERS under a
+    temperature programme - barriers off by a few kJ/mol, prefactors by an order of magnitude - goes through
+    sample_arrhenius(calc, X, spec): one calculator per row, one VariableODESolve each, one ensemble call
+    (solve_network_ensemble(..., member_calculators=True))."""
     if int(M) != M or int(P) != P or M < 1 or P < 1:
         raise ValueError(f"sobol_design: M and P must be integers >= 1; got {M!r}, {P!r}")
     M, P = int(M), int(P)
@@ -1000,6 +1037,50 @@ def sobol_design(M, P, seed=0, A=None, B=None):
         blk[:] = A
         blk[:, p] = B[:, p]
     return X
+
+
+def sample_arrhenius(calc, X, spec):
+    """K PrecalculatedArrheniusCalculators from samples X[K][P] on the unit cube, one per row, for solve_network_ensemble (a
+    Saltelli design from sobol_design, or any other sample). spec[p] = (kind, reaction_ids, half_width) says what column p
+    moves: kind "Ea" shifts the barriers of the listed reactions by half_width (2 x - 1) (the units of calc.Ea), kind "lnA"
+    multiplies their prefactors by exp(half_width (2 x - 1)); x = 0.5 leaves them as they are. reaction_ids are 0-based
+    positions in calc.Ea / calc.A - the reactions of `rd` as it is passed to solve_network_ensemble(member_calculators=True),
+    before filter and cutoff -
+    and may be empty (a dummy input: its indices measure the estimator's noise). A reaction listed under several columns
+    gets every shift. `calc` is not modified; k_max and t_unit are its own."""
+    if not isinstance(calc, PrecalculatedArrheniusCalculator):
+        raise ValueError("sample_arrhenius needs a PrecalculatedArrheniusCalculator")
+    X = np.asarray(X, dtype=float)
+    if X.ndim != 2 or X.shape[1] != len(spec):
+        raise ValueError(f"sample_arrhenius: X must be [K][P] with P = len(spec) = {len(spec)}; got {X.shape}")
+    if not np.all((X >= 0.0) & (X <= 1.0)):
+        raise ValueError("sample_arrhenius: X must lie on the unit cube")
+    R = len(calc.Ea)
+    cols = []
+    for p, item in enumerate(spec):
+        try:
+            kind, ids, hw = item
+            ids = np.asarray(ids, dtype=np.int64).reshape(-1)
+            hw = float(hw)
+        except (TypeError, ValueError):
+            raise ValueError(f"sample_arrhenius: spec[{p}] must be (kind, reaction_ids, half_width)") from None
+        if kind not in ("Ea", "lnA"):
+            raise ValueError(f"sample_arrhenius: spec[{p}]: kind must be 'Ea' or 'lnA', got {kind!r}")
+        if len(ids) and (ids.min() < 0 or ids.max() >= R):
+            raise ValueError(f"sample_arrhenius: spec[{p}]: reaction ids must be in [0, {R})")
+        cols.append((kind, ids, hw))
+    out = []
+    for x in X:
+        Ea, A = calc.Ea.copy(), calc.A.copy()
+        for (kind, ids, hw), xp in zip(cols, x):
+            s = hw * (2.0 * xp - 1.0)
+            for r in ids:      # (one by one: an id listed twice is shifted twice)
+                if kind == "Ea":
+                    Ea[r] += s
+                else:
+                    A[r] *= np.exp(s)
+        out.append(PrecalculatedArrheniusCalculator(Ea, A, k_max=calc.k_max, t_unit=calc.t_unit))
+    return out
 
 
 @dataclass

@@ -17,10 +17,6 @@ using namespace kin;
 
 namespace {
 
-void require(bool c, int code, const char* msg) {
-  if (!c) throw KinError(code, msg);
-}
-
 constexpr double SENTINEL = -7.0;   // fills the drift results before a launch: a slot no workgroup wrote shows
 
 struct Pinned {   // the drift test's host target (Solver::h_drift is pinned as well)

@@ -63,8 +63,9 @@ void kin_network::jac_dev(const double* d_u, double* d_vals) {
   launch_segsum(jac_plan.view(), SEG_COEF_SET, dr.p, d_vals, SegExtra{}, stream);
 }
 
-// every entry point runs on the handle's own device (the one current at kin_network_create), whatever the calling
-// thread's current device is: K handles on K host threads can share one GPU or sit on different ones
+// handle.hpp's guard, but for entries that may run without a handle (kin_network_create): the message then goes to g_create_err
+#undef KIN_TRY
+#undef KIN_CATCH
 #define KIN_TRY(h) try { if (h) KIN_HIP(hipSetDevice((h)->device));
 #define KIN_CATCH(h)                                                        \
   }                                                                         \
@@ -77,10 +78,6 @@ void kin_network::jac_dev(const double* d_u, double* d_vals) {
     return KIN_ERR_DEVICE;                                                  \
   }                                                                         \
   return KIN_OK;
-
-static void require(bool c, int code, const char* msg) {
-  if (!c) throw KinError(code, msg);
-}
 
 extern "C" {
 

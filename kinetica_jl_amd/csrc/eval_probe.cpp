@@ -17,10 +17,6 @@ using namespace kin;
 
 namespace {
 
-void require(bool c, int code, const char* msg) {
-  if (!c) throw KinError(code, msg);
-}
-
 // G, S, B, the longest row and the rows of the ELL groups, read back from the plan on the device; the workgroup size the
 // launchers take for it (segsum_wg: what launch_segsum / launch_e_segsum branch on)
 void plan_info(const SegPlanDev& p, hipStream_t s, int64_t* info) {

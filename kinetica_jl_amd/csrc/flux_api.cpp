@@ -1,21 +1,13 @@
-// extern "C" entry points of the reaction-flux pass (declarations: include/kinetica_hip.h; kernels: flux_kernels.hip).
+// extern "C" entry points of the reaction-flux pass (declarations: include/kinetica_hip.h; kernels: flux_kernels.hip), and
+// the batch-of-states layer every analysis pass's host side is written with (flux_api.hpp).
 #include "../../include/kinetica_hip.h"
 
 #include <algorithm>
 
 #include "flux_api.hpp"
 #include "flux_kernels.hpp"
-#include "handle.hpp"
 
 using namespace kin;
-
-namespace {
-
-void require(bool c, int code, const char* msg) {
-  if (!c) throw KinError(code, msg);
-}
-
-}  // namespace
 
 namespace kin {
 
@@ -72,6 +64,93 @@ void flux_check_rows(const int64_t* k_row, int64_t B, int64_t n_rows) {
   for (int64_t b = 0; b < B; b++) require(k_row[b] >= 0 && k_row[b] < n_rows, ERR_INVALID_ARG, "k_row: row index out of range");
 }
 
+void drg_limit(const kin_network* h) {
+  require(h->host.N < ((int64_t)1 << 31) / 2, ERR_UNSUPPORTED, "DRG pass: N beyond 32-bit offsets");
+}
+
+void drg_check(kin_network* h, int64_t B, bool have_k, bool have_row, bool have_T, bool have_out) {
+  flux_check(h, B, have_k, have_row, have_T, true);
+  require(have_out, ERR_INVALID_ARG, "null output buffer");
+  drg_limit(h);
+}
+
+FluxSource stage_source(kin_network* h, int64_t B, const double* k, int64_t n_k_rows, const int64_t* k_row, const double* T, hipStream_t s) {
+  const int64_t R = h->host.R;
+  if (k && n_k_rows > 0) h->f_k.upload(k, (size_t)n_k_rows * R, s);
+  if (k_row && B > 0) h->f_krow.upload(k_row, (size_t)B, s);
+  if (T && B > 0) h->f_T.upload(T, (size_t)B, s);
+  return FluxSource{k ? h->f_k.p : nullptr, R, k_row ? h->f_krow.p : nullptr, T ? h->f_T.p : nullptr};
+}
+
+StateBatch host_batch(kin_network* h, int64_t B, const double* u, const double* k, int64_t n_k_rows, const int64_t* k_row,
+                      const double* T, hipStream_t s) {
+  require(u != nullptr || B == 0, ERR_INVALID_ARG, "null state buffer");
+  if (k && k_row) { require(n_k_rows >= 1 || B == 0, ERR_INVALID_ARG, "k has no rows"); flux_check_rows(k_row, B, n_k_rows); }
+  else if (k) require(n_k_rows == B, ERR_INVALID_ARG, "k without k_row needs one row per state (n_k_rows == B)");
+  if (B > 0) h->f_u.upload(u, (size_t)B * h->host.N, s);
+  return StateBatch{B, h->f_u.p, stage_source(h, B, k, n_k_rows, k_row, T, s), nullptr, 0};
+}
+
+StateBatch solution_batch(kin_network* h, PassCheck check, const double* k, int64_t n_k_rows, const int64_t* k_row,
+                          const double* T_rows, bool have_out, hipStream_t s) {
+  const int64_t B = h->n_saved;
+  const bool table = !k && k_row;    // rows of the device-resident rate table
+  check(h, B, k != nullptr || table, k_row != nullptr, T_rows != nullptr, have_out);
+  require(B > 0, ERR_STATE, "no solution stored");
+  require(!table || h->table_rows > 0, ERR_STATE, "no rate table resident (kin_rate_table / kin_solve with a table first)");
+  if (k_row) flux_check_rows(k_row, B, table ? h->table_rows : n_k_rows);
+  else if (k) require(n_k_rows == B, ERR_INVALID_ARG, "k without k_row needs one row per saved state (n_k_rows == n_saved)");
+  FluxSource src = stage_source(h, B, k, n_k_rows, k_row, T_rows, s);
+  if (table) src.k = h->table.p;
+  return StateBatch{B, h->d_sol_u.p, src, nullptr, 0};
+}
+
+StateBatch ensemble_batch(kin_network* h, PassCheck check, const double* k, int64_t n_k_rows, const int64_t* k_row,
+                          const double* T_rows, bool have_out, hipStream_t s) {
+  require(h->ens.valid(), ERR_STATE, "no ensemble stored (kin_solve_ensemble* first)");
+  const int64_t K = h->ens.K, cap = h->ens.cap, B = K * cap;
+  require(cap < ((int64_t)1 << 31) && K < ((int64_t)1 << 31) && B < ((int64_t)1 << 31), ERR_UNSUPPORTED,
+          "ensemble DRG pass: K n_rows beyond 32-bit offsets");
+  check(h, B, k != nullptr, k_row != nullptr, T_rows != nullptr, have_out);
+  // stage 1 forms the rate constants of all K n_rows states in one unsegmented pass from the handle's one (Ea, A)
+  require(!(T_rows && h->ens.member_params()), ERR_UNSUPPORTED,
+          "the stored ensemble was solved with per-member Arrhenius parameters: T_rows would use the handle's; give the rate "
+          "constants explicitly (k with k_row, one kin_arrhenius_eval row per member and temperature)");
+  if (k && k_row) require(n_k_rows >= 1, ERR_INVALID_ARG, "k has no rows");
+  else if (k) require(n_k_rows == B, ERR_INVALID_ARG, "k without k_row needs one row per saved row (n_k_rows == K n_rows)");
+  // Stage 1 runs over every row of the record; the keys of the rows past a member's saved ones are ignored by contract, so
+  // they are replaced by harmless ones here (row 0, 1000 K) and the later stages leave those states out.
+  std::vector<int64_t> rows;
+  std::vector<double> Ts;
+  if (k_row) rows.assign(k_row, k_row + B);
+  if (T_rows) Ts.assign(T_rows, T_rows + B);
+  for (int64_t m = 0; m < K; m++) {
+    const int64_t n = h->ens.n_saved[m];
+    for (int64_t j = 0; j < cap; j++) {
+      const int64_t b = m * cap + j;
+      if (j < n) { if (k_row) require(rows[b] >= 0 && rows[b] < n_k_rows, ERR_INVALID_ARG, "k_row: row index out of range"); }
+      else { if (k_row) rows[b] = 0; if (T_rows) Ts[b] = 1000.0; }
+    }
+  }
+  h->ens_segn.upload(h->ens.n_saved, s);
+  const FluxSource src = stage_source(h, B, k, n_k_rows, k_row ? rows.data() : nullptr, T_rows ? Ts.data() : nullptr, s);
+  KIN_HIP(hipStreamSynchronize(s));      // (rows and Ts leave scope)
+  return StateBatch{B, h->ens.sol, src, h->ens_segn.p, cap};
+}
+
+const int64_t* species_list(kin_network* h, const int64_t* list, int64_t n, int index_base, const char* none_msg, const char* range_msg,
+                            hipStream_t s) {
+  require(list != nullptr && n >= 1 && n < ((int64_t)1 << 31), ERR_INVALID_ARG, none_msg);
+  std::vector<int64_t> t(list, list + n);
+  for (int64_t& x : t) {
+    x -= index_base;
+    require(x >= 0 && x < h->host.N, ERR_INVALID_ARG, range_msg);
+  }
+  h->f_sel.upload(t, s);
+  KIN_HIP(hipStreamSynchronize(s));      // (t leaves scope)
+  return h->f_sel.p;
+}
+
 }  // namespace kin
 
 namespace {
@@ -123,18 +202,23 @@ void check_seg_rows(const int64_t* k_row, int64_t S, int64_t L, const int64_t* s
   }
 }
 
+// the unsegmented host entries: weights up, flux[R] and / or rates[B][R] staged through the handle's buffers
+void flux_host_call(kin_network* h, const StateBatch& b, const double* w, double* flux, double* rates, hipStream_t s) {
+  const size_t R = (size_t)h->host.R;
+  if (w && b.B > 0) h->f_w.upload(w, (size_t)b.B, s);
+  if (flux) h->f_flux.alloc(R);
+  if (rates) h->f_rates.alloc((size_t)b.B * R);
+  flux_run(h, b.B, b.u, b.src, w ? h->f_w.p : nullptr, flux ? h->f_flux.p : nullptr, rates ? h->f_rates.p : nullptr, s);
+  if (flux) h->f_flux.download(flux, R, s);
+  if (rates) h->f_rates.download(rates, (size_t)b.B * R, s);
+  KIN_HIP(hipStreamSynchronize(s));
+}
+
 void require_ensemble(const kin_network* h) {
   require(h->ens.valid(), ERR_STATE, "no ensemble stored (kin_solve_ensemble* first)");
 }
 
 }  // namespace
-
-#define KIN_TRY(h) try { KIN_HIP(hipSetDevice((h)->device));
-#define KIN_CATCH(h)                                                        \
-  }                                                                         \
-  catch (const KinError& e) { (h)->err = e.what(); return e.code; }         \
-  catch (const std::exception& e) { (h)->err = e.what(); return KIN_ERR_DEVICE; } \
-  return KIN_OK;
 
 extern "C" {
 
@@ -167,23 +251,8 @@ int kin_flux_batched(kin_network* h, int64_t B, const double* u, const double* k
   if (!h) return KIN_ERR_INVALID_ARG;
   KIN_TRY(h)
   flux_check(h, B, k != nullptr, k_row != nullptr, T != nullptr, flux || rates);
-  require(u != nullptr || B == 0, ERR_INVALID_ARG, "null state buffer");
-  if (k && k_row) { require(n_k_rows >= 1 || B == 0, ERR_INVALID_ARG, "k has no rows"); flux_check_rows(k_row, B, n_k_rows); }
-  else if (k) require(n_k_rows == B, ERR_INVALID_ARG, "k without k_row needs one row per state (n_k_rows == B)");
-  const int64_t N = h->host.N, R = h->host.R;
   hipStream_t s = h->stream;
-  if (B > 0) h->f_u.upload(u, (size_t)B * N, s);
-  if (k && n_k_rows > 0) h->f_k.upload(k, (size_t)n_k_rows * R, s);
-  if (k_row && B > 0) h->f_krow.upload(k_row, (size_t)B, s);
-  if (T && B > 0) h->f_T.upload(T, (size_t)B, s);
-  if (w && B > 0) h->f_w.upload(w, (size_t)B, s);
-  if (flux) h->f_flux.alloc((size_t)R);
-  if (rates) h->f_rates.alloc((size_t)B * R);
-  flux_run(h, B, h->f_u.p, FluxSource{k ? h->f_k.p : nullptr, R, k_row ? h->f_krow.p : nullptr, T ? h->f_T.p : nullptr},
-           w ? h->f_w.p : nullptr, flux ? h->f_flux.p : nullptr, rates ? h->f_rates.p : nullptr, s);
-  if (flux) h->f_flux.download(flux, (size_t)R, s);
-  if (rates) h->f_rates.download(rates, (size_t)B * R, s);
-  KIN_HIP(hipStreamSynchronize(s));
+  flux_host_call(h, host_batch(h, B, u, k, n_k_rows, k_row, T, s), w, flux, rates, s);
   KIN_CATCH(h)
 }
 
@@ -191,26 +260,8 @@ int kin_solution_flux(kin_network* h, const double* w, const double* k, int64_t 
                       const double* T_rows, double* flux, double* rates) {
   if (!h) return KIN_ERR_INVALID_ARG;
   KIN_TRY(h)
-  const int64_t B = h->n_saved, R = h->host.R;
-  const bool table = !k && k_row;    // rows of the device-resident rate table
-  flux_check(h, B, k != nullptr || table, k_row != nullptr, T_rows != nullptr, flux || rates);
-  require(B > 0, ERR_STATE, "no solution stored");
-  require(!table || h->table_rows > 0, ERR_STATE, "no rate table resident (kin_rate_table / kin_solve with a table first)");
-  if (k_row) flux_check_rows(k_row, B, table ? h->table_rows : n_k_rows);
-  else if (k) require(n_k_rows == B, ERR_INVALID_ARG, "k without k_row needs one row per saved state (n_k_rows == n_saved)");
   hipStream_t s = h->stream;
-  if (k) h->f_k.upload(k, (size_t)n_k_rows * R, s);
-  if (k_row) h->f_krow.upload(k_row, (size_t)B, s);
-  if (T_rows) h->f_T.upload(T_rows, (size_t)B, s);
-  if (w) h->f_w.upload(w, (size_t)B, s);
-  if (flux) h->f_flux.alloc((size_t)R);
-  if (rates) h->f_rates.alloc((size_t)B * R);
-  const double* ksrc = k ? h->f_k.p : (table ? h->table.p : nullptr);
-  flux_run(h, B, h->d_sol_u.p, FluxSource{ksrc, R, k_row ? h->f_krow.p : nullptr, T_rows ? h->f_T.p : nullptr},
-           w ? h->f_w.p : nullptr, flux ? h->f_flux.p : nullptr, rates ? h->f_rates.p : nullptr, s);
-  if (flux) h->f_flux.download(flux, (size_t)R, s);
-  if (rates) h->f_rates.download(rates, (size_t)B * R, s);
-  KIN_HIP(hipStreamSynchronize(s));
+  flux_host_call(h, solution_batch(h, flux_check, k, n_k_rows, k_row, T_rows, flux || rates, s), w, flux, rates, s);
   KIN_CATCH(h)
 }
 
@@ -238,13 +289,10 @@ int kin_flux_segmented(kin_network* h, int64_t S, int64_t L, const int64_t* seg_
   hipStream_t s = h->stream;
   if (B > 0) h->f_u.upload(u, (size_t)B * N, s);
   if (seg_n && S > 0) h->f_segn.upload(seg_n, (size_t)S, s);
-  if (k && n_k_rows > 0) h->f_k.upload(k, (size_t)n_k_rows * R, s);
-  if (k_row && B > 0) h->f_krow.upload(k_row, (size_t)B, s);
-  if (T && B > 0) h->f_T.upload(T, (size_t)B, s);
+  const FluxSource src = stage_source(h, B, k, n_k_rows, k_row, T, s);
   if (w && B > 0) h->f_w.upload(w, (size_t)B, s);
   h->f_flux.alloc((size_t)S * R);
-  flux_seg_run(h, S, L, seg_n ? h->f_segn.p : nullptr, h->f_u.p, FluxSource{k ? h->f_k.p : nullptr, R, k_row ? h->f_krow.p : nullptr, T ? h->f_T.p : nullptr},
-               w ? h->f_w.p : nullptr, h->f_flux.p, s);
+  flux_seg_run(h, S, L, seg_n ? h->f_segn.p : nullptr, h->f_u.p, src, w ? h->f_w.p : nullptr, h->f_flux.p, s);
   h->f_flux.download(flux, (size_t)S * R, s);
   KIN_HIP(hipStreamSynchronize(s));
   KIN_CATCH(h)
@@ -307,13 +355,11 @@ int kin_ensemble_flux(kin_network* h, const double* w, const double* k, int64_t 
   else if (k) require(n_k_rows == B, ERR_INVALID_ARG, "k without k_row needs one row per saved row (n_k_rows == K n_rows)");
   hipStream_t s = h->stream;
   h->ens_segn.upload(h->ens.n_saved, s);
-  if (k && n_k_rows > 0) h->f_k.upload(k, (size_t)n_k_rows * R, s);
-  if (k_row) h->f_krow.upload(k_row, (size_t)B, s);
-  if (T_rows) h->f_T.upload(T_rows, (size_t)B, s);
+  const FluxSource src = stage_source(h, B, k, n_k_rows, k_row, T_rows, s);
   if (w) h->f_w.upload(w, (size_t)B, s);
   h->f_flux.alloc((size_t)K * R);
-  flux_seg_run(h, K, cap, h->ens_segn.p, h->ens.sol, FluxSource{k ? h->f_k.p : nullptr, R, k_row ? h->f_krow.p : nullptr, T_rows ? h->f_T.p : nullptr},
-               w ? h->f_w.p : nullptr, h->f_flux.p, s, h->ens.Ea, h->ens.A);   // (a per-member record: each member's own Ea / A)
+  // (T_rows is not refused on a per-member record as ensemble_batch refuses it: this pass takes each member's own Ea / A)
+  flux_seg_run(h, K, cap, h->ens_segn.p, h->ens.sol, src, w ? h->f_w.p : nullptr, h->f_flux.p, s, h->ens.Ea, h->ens.A);
   h->f_flux.download(flux, (size_t)K * R, s);
   KIN_HIP(hipStreamSynchronize(s));
   KIN_CATCH(h)

@@ -1,4 +1,5 @@
-// The object behind the opaque kin_network handle of include/kinetica_hip.h.
+// The object behind the opaque kin_network handle of include/kinetica_hip.h, and what every extern "C" entry point that
+// takes one is written with: require and the KIN_TRY / KIN_CATCH guard.
 #pragma once
 #include <memory>
 #include <string>
@@ -14,7 +15,21 @@ namespace kin {
 struct Solver; struct IntegratorState; struct ResidentSolver; struct EnsembleSolver;
 struct ResidentDeleter { void operator()(ResidentSolver* p) const; };   // resident.cpp (the type is complete there only)
 struct EnsembleDeleter { void operator()(EnsembleSolver* p) const; };   // ensemble.cpp
+
+inline void require(bool c, int code, const char* msg) {
+  if (!c) throw KinError(code, msg);
 }
+}
+
+// The body of an entry point that has checked its handle: it runs on the handle's own device (the one current at
+// kin_network_create), whatever the calling thread's current device is - K handles on K host threads can share one GPU or sit
+// on different ones - and a KinError becomes its code, with the message left in the handle for kin_last_error.
+#define KIN_TRY(h) try { KIN_HIP(hipSetDevice((h)->device));
+#define KIN_CATCH(h)                                                        \
+  }                                                                         \
+  catch (const ::kin::KinError& e) { (h)->err = e.what(); return e.code; }  \
+  catch (const std::exception& e) { (h)->err = e.what(); return ::kin::ERR_DEVICE; } \
+  return ::kin::OK;
 
 struct kin_network {
   kin::NetworkHost host;
@@ -58,16 +73,17 @@ struct kin_network {
   kin::DevBuf<double> b_u, b_k, b_du;
 
   // reaction-flux pass (flux_kernels.hpp, flux_api.cpp): index tables uploaded at the first call that needs them, the
-  // partial sums part[G][R] and the staging buffers of the host entries grown on demand
+  // partial sums part[G][R] and the staging buffers of the host entries grown on demand. The host entries of every analysis
+  // pass stage through the same ones (flux_api.hpp): states f_u, rate-constant keys f_k / f_krow / f_T, a species list f_sel
+  // and an accumulating result f_result
   bool flux_ready = false;
   kin::DevBuf<uint32_t> flux_idx16;
   kin::DevBuf<int32_t> flux_idx32;
-  kin::DevBuf<double> flux_part, f_u, f_k, f_T, f_w, f_flux, f_rates;
-  kin::DevBuf<int64_t> f_krow, f_segn;
+  kin::DevBuf<double> flux_part, f_u, f_k, f_T, f_w, f_flux, f_rates, f_result;
+  kin::DevBuf<int64_t> f_krow, f_segn, f_sel;
 
   // directed-relation-graph pass (drg.hpp, drg_api.cpp): host tables and device plans per pairing mode, built at the first
-  // call that needs them; the block of per-state rates (stage 1), its denominators, the maxima per slice and the staging
-  // buffer of the host entries' coefficients, grown on demand
+  // call that needs them; the block of per-state rates (stage 1), its denominators and the maxima per slice, grown on demand
   struct DrgMode {
     std::unique_ptr<kin::DrgTables> host;
     bool dev_ready = false;
@@ -78,16 +94,13 @@ struct kin_network {
     kin::DevBuf<float> den_ell_s, den_long_s, edge_ell_s, edge_long_s;
     kin::DevBuf<int32_t> in_ptr, in_src, in_edge, in_order;
   } drg[2];
-  kin::DevBuf<double> drg_rates, drg_den, drg_part, drg_coef;
-  // DRGEP: the block's coefficients r[nb][E], importances R[nb][N], the global form's work[nb][2][N], rounds[nb]; the
-  // targets and the staging buffer of the host entries' importance
-  kin::DevBuf<double> drgep_r, drgep_R, drgep_work, drgep_imp;
+  kin::DevBuf<double> drg_rates, drg_den, drg_part;
+  // DRGEP: the block's coefficients r[nb][E], importances R[nb][N], the global form's work[nb][2][N], rounds[nb]
+  kin::DevBuf<double> drgep_r, drgep_R, drgep_work;
   kin::DevBuf<int32_t> drgep_rounds;
-  kin::DevBuf<int64_t> drgep_targets;
   // reaction importance (drg.hpp, drg_api.cpp): the per-reaction table per pairing mode and, where the DRG pass has not
-  // uploaded its plans yet, a denominator plan of its own (no edge plan is built for this pass); the species mask and the
-  // staged list behind it, the maxima per slice, the block's per-state values when asked for and the staging buffer of the
-  // host entries' importance
+  // uploaded its plans yet, a denominator plan of its own (no edge plan is built for this pass); the species mask, the maxima
+  // per slice and the block's per-state values when asked for
   struct RiMode {
     std::unique_ptr<kin::RiTables> host;
     std::unique_ptr<kin::DrgTables> den_host;
@@ -97,26 +110,25 @@ struct kin_network {
     kin::DevBuf<float> den_ell_c, den_long_c;
   } ri[2];
   kin::DevBuf<uint8_t> ri_mask;
-  kin::DevBuf<int64_t> ri_sel;
-  kin::DevBuf<double> ri_part, ri_state, ri_imp;
+  kin::DevBuf<double> ri_part, ri_state;
 
   // path flux analysis (pfa.hpp, pfa_api.cpp): the second-generation pattern per pairing mode and, on the device, both
-  // patterns and the order of the rows; the block's rp[nb][E], rc[nb][E], the per-state r[nb][E2] when asked for, the maxima
-  // per slice and the staging buffer of the host entries' coefficients
+  // patterns and the order of the rows; the block's rp[nb][E], rc[nb][E], the per-state r[nb][E2] when asked for and the
+  // maxima per slice
   struct PfaMode {
     std::unique_ptr<kin::PfaTables> host;
     bool dev_ready = false;
     kin::DevBuf<int32_t> rowptr, colidx, rowptr2, colidx2, order;
   } pfa[2];
-  kin::DevBuf<double> pfa_rp, pfa_rc, pfa_r, pfa_part, pfa_coef;
+  kin::DevBuf<double> pfa_rp, pfa_rc, pfa_r, pfa_part;
 
   // timescale pass (timescale.hpp, timescale_api.cpp): the row pass's tables, uploaded at the first call that needs them; the
   // block's rates[nb][R], dr[nb][2R], jv[nb][nnz], g[nb][N], the extrema per slice part[Y][3][N] and the staging buffers of
-  // the host entries' outputs, grown on demand
+  // the host entries' per-state outputs, grown on demand
   bool ts_ready = false;
   int32_t ts_G = 0, ts_S = 0, ts_Bl = 0;
   kin::DevBuf<int32_t> ts_rows;
-  kin::DevBuf<double> ts_rates, ts_dr, ts_jv, ts_g, ts_part, ts_o_vals, ts_o_summary, ts_o_diag, ts_o_err, ts_o_norm;
+  kin::DevBuf<double> ts_rates, ts_dr, ts_jv, ts_g, ts_part, ts_o_vals, ts_o_diag, ts_o_err, ts_o_norm;
 
   // tiled sweep in library order (tiled.hpp, tiled_api.cpp): built at the first call that needs it
   kin::TiledHost tiled;

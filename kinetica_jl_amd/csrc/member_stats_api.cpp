@@ -16,10 +16,6 @@ static_assert(MS_MAX_SORTED == KIN_MEMBERS_MAX_SORTED, "the header states the li
 
 namespace {
 
-void require(bool c, int code, const char* msg) {
-  if (!c) throw KinError(code, msg);
-}
-
 // the members a mask names, ascending (null: all K)
 std::vector<int32_t> participants(int64_t K, const int32_t* use) {
   std::vector<int32_t> idx;
@@ -326,13 +322,6 @@ void sobol_to_host(kin_network* h, const double* d_u, int64_t M, int64_t P, int6
 }
 
 }  // namespace
-
-#define KIN_TRY(h) try { KIN_HIP(hipSetDevice((h)->device));
-#define KIN_CATCH(h)                                                        \
-  }                                                                         \
-  catch (const KinError& e) { (h)->err = e.what(); return e.code; }         \
-  catch (const std::exception& e) { (h)->err = e.what(); return KIN_ERR_DEVICE; } \
-  return KIN_OK;
 
 extern "C" {
 

@@ -1,12 +1,11 @@
 // extern "C" entry points of path flux analysis (declarations: include/kinetica_hip.h; tables: pfa.cpp; split stage:
-// drg_kernels.hip, SPLIT; second-generation stage: pfa_kernels.hip). Stage 1, the checks, the rate-constant sources and the
-// fold over slices, blocks and the caller's coefficients are the directed-relation-graph pass's (drg_api.hpp).
+// drg_kernels.hip, SPLIT; second-generation stage: pfa_kernels.hip). Batches, blocks and staging: flux_api.hpp; stage 1 with
+// the denominators, the tables of a pairing mode and the fold over slices are the DRG family's (drg_api.hpp).
 // kin_pfa_pattern_host, which needs no handle, sits with the other host-only entries in capi.cpp.
 #include "../../include/kinetica_hip.h"
 
 #include <algorithm>
 #include <cmath>
-#include <cstdlib>
 #include <string>
 
 #include "drg_api.hpp"
@@ -15,10 +14,6 @@
 using namespace kin;
 
 namespace {
-
-void require(bool c, int code, const char* msg) {
-  if (!c) throw KinError(code, msg);
-}
 
 void pfa_check_size(const kin_network* h) {
   if (h->host.N > PFA_LDS_SPECIES)
@@ -48,16 +43,10 @@ kin_network::PfaMode& pfa_dev(kin_network* h, int pairing, hipStream_t s) {
   return m;
 }
 
-// States per block: none of rates[nb][R], rp[nb][E] + rc[nb][E] and (when asked for) r[nb][E2] above 256 MB;
-// KIN_DRG_BLOCK_STATES as in the DRG pass.
+// States per block: none of rates[nb][R], rp[nb][E] + rc[nb][E] and (when asked for) r[nb][E2] above the bound
 int64_t pfa_block(const kin_network* h, const PfaTables& t, int64_t B, bool want_r) {
-  const size_t row = (size_t)std::max<int64_t>(std::max<int64_t>(h->host.R, 2 * t.E), std::max<int64_t>(want_r ? t.E2 : 0, 1)) * sizeof(double);
-  int64_t nb_max = std::max<int64_t>(1, (int64_t)(DRG_RATES_BYTES / row));
-  if (const char* e = getenv("KIN_DRG_BLOCK_STATES")) {   // (read per call: tests change it)
-    const int64_t v = atoll(e);
-    if (v >= 1) nb_max = std::min(nb_max, v);
-  }
-  return std::min(nb_max, B);
+  return block_states((size_t)std::max<int64_t>(std::max<int64_t>(h->host.R, 2 * t.E), std::max<int64_t>(want_r ? t.E2 : 0, 1)), B,
+                      DRG_BLOCK_ENV);
 }
 
 int64_t pfa_wg_cost(int64_t N) {
@@ -97,64 +86,36 @@ void pfa_second_block(kin_network* h, kin_network::PfaMode& m, int64_t b0, int64
 
 // The pass on device buffers, block by block: stage 1 (the flux sweep) writes the block's rates, the signed denominator
 // launch den = max(P, C), the split stage rp and rc, the second-generation stage the maxima of r, folded into d_coef.
-void pfa_run(kin_network* h, int pairing, int64_t B, const double* d_u, const FluxSource& src, const int64_t* d_seg_n, int64_t L,
-             int accumulate, double* d_coef, const PfaOut& out, hipStream_t s) {
-  const int64_t N = h->host.N, R = h->host.R;
+void pfa_run(kin_network* h, int pairing, const StateBatch& b, int accumulate, double* d_coef, const PfaOut& out, hipStream_t s) {
   auto& g = drgep_dev(h, pairing, s);
   auto& m = pfa_dev(h, pairing, s);
   const PfaTables& t = *m.host;
-  if (t.E2 == 0) return;
-  if (B == 0) {
-    if (!accumulate) KIN_HIP(hipMemsetAsync(d_coef, 0, (size_t)t.E2 * sizeof(double), s));
-    return;
-  }
+  if (t.E2 == 0 || empty_batch(b.B, d_coef, t.E2, accumulate, s)) return;
   int upto = 3;      // KIN_PFA_STAGES=1 / 2 ends every block after stage 1 / the split stage and leaves d_coef alone: for timing the stages only
   if (const char* e = getenv("KIN_PFA_STAGES")) upto = atoi(e) >= 1 ? atoi(e) : 3;
-  const int64_t nb_max = pfa_block(h, t, B, out.r != nullptr);
-  h->drg_rates.alloc((size_t)nb_max * R);
-  h->drg_den.alloc((size_t)nb_max * N);
+  const int64_t nb_max = pfa_block(h, t, b.B, out.r != nullptr);
+  drg_stage_alloc(h, nb_max);
   pfa_alloc(h, t, nb_max, out.r != nullptr);
-  const SegPlanView dv = g.den_plan.view(), ev = g.edge_plan.view();
-  for (int64_t b0 = 0; b0 < B; b0 += nb_max) {
-    const int64_t nb = std::min(nb_max, B - b0);
-    FluxSource bs = src;
-    if (bs.k && !bs.k_row) bs.k += (size_t)b0 * (size_t)bs.k_stride;
-    if (bs.k_row) bs.k_row += b0;
-    if (bs.T) bs.T += b0;
-    flux_run(h, nb, d_u + (size_t)b0 * N, bs, nullptr, nullptr, h->drg_rates.p, s);
-    if (upto < 2) continue;
+  const DrgPlan den = signed_den_plan(g), edge = signed_edge_plan(g);
+  for_blocks(b.B, nb_max, accumulate, [&](int64_t b0, int64_t nb, int use_prev) {
     DrgArgs a{};
-    a.N = (int)N; a.R = (int)R; a.E = (int)t.E; a.nb = (int)nb;
-    a.rates = h->drg_rates.p; a.b0 = b0; a.seg_n = d_seg_n; a.L = L;
-    a.den = h->drg_den.p; a.r = h->pfa_rp.p; a.rc = h->pfa_rc.p;
-    a.p = dv; a.ell_c = g.den_ell_s.p; a.long_c = g.den_long_s.p;
-    launch_drgep_den(a, slices_cap(drg_slices(dv, nb, h->n_cu)), s);
-    a.p = ev; a.ell_c = g.edge_ell_s.p; a.long_c = g.edge_long_s.p;
-    launch_pfa_split(a, slices_cap(drg_slices(ev, nb, h->n_cu)), s);
-    if (upto < 3) continue;
-    pfa_second_block(h, m, b0, nb, d_seg_n, L, (accumulate || b0 > 0) ? 1 : 0, d_coef, out, s);
-  }
+    a.E = (int)t.E; a.r = h->pfa_rp.p; a.rc = h->pfa_rc.p;
+    drg_rates_den(h, b, b0, nb, den, true, upto, a, s);
+    if (upto < 2) return;
+    edge.into(a);
+    launch_pfa_split(a, slices_cap(drg_slices(edge.p, nb, h->n_cu)), s);
+    if (upto < 3) return;
+    pfa_second_block(h, m, b0, nb, b.seg_n, b.L, use_prev, d_coef, out, s);
+  });
 }
 
-// host entries: coef staged through the handle's buffer (uploaded first when it takes part in the maximum)
-template <class F>
-void pfa_host_call(kin_network* h, int pairing, int accumulate, double* coef, hipStream_t s, F run) {
-  const int64_t E2 = pfa_host(h, pairing).E2;
-  h->pfa_coef.alloc((size_t)E2);
-  if (accumulate && E2 > 0) h->pfa_coef.upload(coef, (size_t)E2, s);
-  run(h->pfa_coef.p);
-  if (E2 > 0) h->pfa_coef.download(coef, (size_t)E2, s);
-  KIN_HIP(hipStreamSynchronize(s));
+// host entries of a batch: coef staged through the handle
+void pfa_host_call(kin_network* h, int pairing, const StateBatch& b, int accumulate, double* coef, const PfaOut& out, hipStream_t s) {
+  staged_result(h, pfa_host(h, pairing).E2, coef, accumulate, s,
+                [&](double* d_coef) { pfa_run(h, pairing, b, accumulate, d_coef, out, s); });
 }
 
 }  // namespace
-
-#define KIN_TRY(h) try { KIN_HIP(hipSetDevice((h)->device));
-#define KIN_CATCH(h)                                                        \
-  }                                                                         \
-  catch (const KinError& e) { (h)->err = e.what(); return e.code; }         \
-  catch (const std::exception& e) { (h)->err = e.what(); return KIN_ERR_DEVICE; } \
-  return KIN_OK;
 
 extern "C" {
 
@@ -178,7 +139,8 @@ int kin_pfa_batched_dev(kin_network* h, int pairing, int64_t B, const double* d_
   pfa_check_size(h);
   require(d_u != nullptr || B == 0, ERR_INVALID_ARG, "null state buffer");
   hipStream_t s = stream ? (hipStream_t)stream : h->stream;
-  pfa_run(h, pairing, B, d_u, FluxSource{d_k, h->host.R, d_k_row, d_T}, nullptr, 0, accumulate, d_coef, PfaOut{nullptr, nullptr, nullptr}, s);
+  pfa_run(h, pairing, StateBatch{B, d_u, FluxSource{d_k, h->host.R, d_k_row, d_T}, nullptr, 0}, accumulate, d_coef,
+          PfaOut{nullptr, nullptr, nullptr}, s);
   KIN_CATCH(h)
 }
 
@@ -188,19 +150,8 @@ int kin_pfa_batched(kin_network* h, int pairing, int64_t B, const double* u, con
   KIN_TRY(h)
   drg_check(h, B, k != nullptr, k_row != nullptr, T != nullptr, coef != nullptr);
   pfa_check_size(h);
-  require(u != nullptr || B == 0, ERR_INVALID_ARG, "null state buffer");
-  if (k && k_row) { require(n_k_rows >= 1 || B == 0, ERR_INVALID_ARG, "k has no rows"); flux_check_rows(k_row, B, n_k_rows); }
-  else if (k) require(n_k_rows == B, ERR_INVALID_ARG, "k without k_row needs one row per state (n_k_rows == B)");
-  const int64_t N = h->host.N, R = h->host.R;
   hipStream_t s = h->stream;
-  if (B > 0) h->f_u.upload(u, (size_t)B * N, s);
-  if (k && n_k_rows > 0) h->f_k.upload(k, (size_t)n_k_rows * R, s);
-  if (k_row && B > 0) h->f_krow.upload(k_row, (size_t)B, s);
-  if (T && B > 0) h->f_T.upload(T, (size_t)B, s);
-  const FluxSource src{k ? h->f_k.p : nullptr, R, k_row ? h->f_krow.p : nullptr, T ? h->f_T.p : nullptr};
-  pfa_host_call(h, pairing, accumulate, coef, s, [&](double* d_coef) {
-    pfa_run(h, pairing, B, h->f_u.p, src, nullptr, 0, accumulate, d_coef, PfaOut{rp_out, rc_out, r_out}, s);
-  });
+  pfa_host_call(h, pairing, host_batch(h, B, u, k, n_k_rows, k_row, T, s), accumulate, coef, PfaOut{rp_out, rc_out, r_out}, s);
   KIN_CATCH(h)
 }
 
@@ -209,7 +160,7 @@ int kin_pfa_paths(kin_network* h, int pairing, int64_t B, const double* rp, cons
   KIN_TRY(h)
   require(B >= 0 && B < ((int64_t)1 << 31), ERR_INVALID_ARG, "B out of range");
   require(coef != nullptr, ERR_INVALID_ARG, "null output buffer");
-  require(h->host.N < ((int64_t)1 << 31) / 2, ERR_UNSUPPORTED, "DRG pass: N beyond 32-bit offsets");
+  drg_limit(h);
   pfa_check_size(h);
   hipStream_t s = h->stream;
   const PfaTables& t = pfa_host(h, pairing);
@@ -217,21 +168,16 @@ int kin_pfa_paths(kin_network* h, int pairing, int64_t B, const double* rp, cons
   for (size_t i = 0, n = (size_t)B * (size_t)t.E; i < n; i++)
     require(std::isfinite(rp[i]) && rp[i] >= 0.0 && std::isfinite(rc[i]) && rc[i] >= 0.0, ERR_INVALID_ARG,
             "rp, rc: coefficients must be finite and not negative");
-  pfa_host_call(h, pairing, accumulate, coef, s, [&](double* d_coef) {
+  staged_result(h, t.E2, coef, accumulate, s, [&](double* d_coef) {
     auto& m = pfa_dev(h, pairing, s);
-    if (t.E2 == 0) return;
-    if (B == 0) {
-      if (!accumulate) KIN_HIP(hipMemsetAsync(d_coef, 0, (size_t)t.E2 * sizeof(double), s));
-      return;
-    }
+    if (t.E2 == 0 || empty_batch(B, d_coef, t.E2, accumulate, s)) return;
     const int64_t nb_max = pfa_block(h, t, B, r_out != nullptr);
     pfa_alloc(h, t, nb_max, r_out != nullptr);
-    for (int64_t b0 = 0; b0 < B; b0 += nb_max) {
-      const int64_t nb = std::min(nb_max, B - b0);
+    for_blocks(B, nb_max, accumulate, [&](int64_t b0, int64_t nb, int use_prev) {
       h->pfa_rp.upload(rp + (size_t)b0 * t.E, (size_t)nb * t.E, s);
       h->pfa_rc.upload(rc + (size_t)b0 * t.E, (size_t)nb * t.E, s);
-      pfa_second_block(h, m, b0, nb, nullptr, 0, (accumulate || b0 > 0) ? 1 : 0, d_coef, PfaOut{nullptr, nullptr, r_out}, s);
-    }
+      pfa_second_block(h, m, b0, nb, nullptr, 0, use_prev, d_coef, PfaOut{nullptr, nullptr, r_out}, s);
+    });
   });
   KIN_CATCH(h)
 }
@@ -241,11 +187,9 @@ int kin_solution_pfa(kin_network* h, int pairing, const double* k, int64_t n_k_r
   if (!h) return KIN_ERR_INVALID_ARG;
   KIN_TRY(h)
   hipStream_t s = h->stream;
-  const FluxSource src = drg_solution_source(h, k, n_k_rows, k_row, T_rows, coef != nullptr, s);
+  const StateBatch b = solution_batch(h, drg_check, k, n_k_rows, k_row, T_rows, coef != nullptr, s);
   pfa_check_size(h);
-  pfa_host_call(h, pairing, accumulate, coef, s, [&](double* d_coef) {
-    pfa_run(h, pairing, h->n_saved, h->d_sol_u.p, src, nullptr, 0, accumulate, d_coef, PfaOut{nullptr, nullptr, nullptr}, s);
-  });
+  pfa_host_call(h, pairing, b, accumulate, coef, PfaOut{nullptr, nullptr, nullptr}, s);
   KIN_CATCH(h)
 }
 
@@ -254,12 +198,9 @@ int kin_ensemble_pfa(kin_network* h, int pairing, const double* k, int64_t n_k_r
   if (!h) return KIN_ERR_INVALID_ARG;
   KIN_TRY(h)
   hipStream_t s = h->stream;
-  const FluxSource src = drg_ensemble_source(h, k, n_k_rows, k_row, T_rows, coef != nullptr, s);
+  const StateBatch b = ensemble_batch(h, drg_check, k, n_k_rows, k_row, T_rows, coef != nullptr, s);
   pfa_check_size(h);
-  pfa_host_call(h, pairing, accumulate, coef, s, [&](double* d_coef) {
-    pfa_run(h, pairing, h->ens.K * h->ens.cap, h->ens.sol, src, h->ens_segn.p, h->ens.cap, accumulate, d_coef,
-            PfaOut{nullptr, nullptr, nullptr}, s);
-  });
+  pfa_host_call(h, pairing, b, accumulate, coef, PfaOut{nullptr, nullptr, nullptr}, s);
   KIN_CATCH(h)
 }
 

@@ -20,10 +20,6 @@ using namespace kin;
 
 namespace {
 
-void require(bool c, int code, const char* msg) {
-  if (!c) throw KinError(code, msg);
-}
-
 enum Row : int { ROW_D = 0, ROW_Y = 8, ROW_PSI, ROW_DD, ROW_SCALE, ROW_F0, ROW_F1, ROW_YTMP, ROW_CS, ROW_K = 16, ROW_X = 23, ROW_OUT, ROW_YNEW,
                  ROW_U, ROW_B };
 static_assert(ROW_B + 1 == KIN_STEP_ROWS && BDF_D_ROWS == 8, "row layout of kin_step_probe");

@@ -86,10 +86,6 @@ TiledView view_of(kin_network* h) {
   return v;
 }
 
-void require(bool c, int code, const char* msg) {
-  if (!c) throw KinError(code, msg);
-}
-
 // caller's species order <-> library order for B states (only called when the two differ or the caller asks for a copy)
 void states_convert(kin_network* h, int64_t B, bool to_lib, const double* d_in, double* d_out, hipStream_t s) {
   const int64_t N = h->host.N;
@@ -98,13 +94,6 @@ void states_convert(kin_network* h, int64_t B, bool to_lib, const double* d_in, 
 }
 
 }  // namespace
-
-#define KIN_TRY(h) try { KIN_HIP(hipSetDevice((h)->device));
-#define KIN_CATCH(h)                                                        \
-  }                                                                         \
-  catch (const KinError& e) { (h)->err = e.what(); return e.code; }         \
-  catch (const std::exception& e) { (h)->err = e.what(); return KIN_ERR_DEVICE; } \
-  return KIN_OK;
 
 extern "C" {
 

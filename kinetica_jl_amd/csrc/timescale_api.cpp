@@ -1,23 +1,15 @@
 // extern "C" entry points of the timescale analysis (declarations: include/kinetica_hip.h; kernels: timescale_kernels.hip).
+// Batches, blocks and staging: flux_api.hpp.
 #include "../../include/kinetica_hip.h"
 
 #include <algorithm>
-#include <cstdlib>
 
-#include "drg_api.hpp"
 #include "flux_api.hpp"
-#include "handle.hpp"
 #include "timescale.hpp"
 
 using namespace kin;
 
 namespace {
-
-void require(bool c, int code, const char* msg) {
-  if (!c) throw KinError(code, msg);
-}
-
-constexpr size_t TS_WORK_BYTES = (size_t)256 << 20;   // bound of the per-state workspace of a block (rates, dr, jv, g)
 
 // which outputs a call wants (device pointers; null: not wanted)
 struct TsOut { double* vals; double* summary; double* diag; double* err; double* norm; };
@@ -31,24 +23,22 @@ void ensure_ts_tables(kin_network* h, hipStream_t s) {
   h->ts_ready = true;
 }
 
-// The pass on device buffers, block of states by block: stage 1 (rates and operand derivatives), the entry gather into the
+// The pass on the device, block of states by block: stage 1 (rates and operand derivatives), the entry gather into the
 // caller's vals or the handle's jv, and - when any of summary / diag / err / norm is wanted - the row pass with its closing
-// launches. cnt.b0 is set per block here.
-void ts_run(kin_network* h, int64_t B, const double* d_u, const FluxSource& src, TsCount cnt, int accumulate, const TsOut& o,
-            hipStream_t s) {
-  const int64_t N = h->host.N, R = h->host.R, nnz = h->host.nnz();
+// launches. Of the batch's states those from row_begin on in their segment count (TsCount; its b0 is set per block here).
+void ts_run(kin_network* h, const StateBatch& b, int64_t row_begin, int accumulate, const TsOut& o, hipStream_t s) {
+  const int64_t N = h->host.N, R = h->host.R, nnz = h->host.nnz(), B = b.B;
+  const FluxSource& src = b.src;
+  // (the passes hold the number of rows below 2^31)
+  TsCount cnt{0, b.seg_n, (int32_t)b.L, (int32_t)std::min<int64_t>(row_begin, INT32_MAX)};
   if (B == 0) {
     if (o.summary && !accumulate) launch_ts_identity(N, o.summary, s);
     return;
   }
   const bool rows = o.summary || o.diag || o.err || o.norm;
+  // the per-state workspace of a block: dr, rates, jv, g
   const size_t per_state = (size_t)2 * R + (rows ? (size_t)R : 0) + (o.vals ? 0 : (size_t)nnz) + (o.norm ? (size_t)N : 0);
-  int64_t nb_max = std::max<int64_t>(1, (int64_t)(TS_WORK_BYTES / (std::max<size_t>(per_state, 1) * sizeof(double))));
-  if (const char* e = getenv("KIN_TS_BLOCK_STATES")) {   // (read per call: tests change it)
-    const int64_t v = atoll(e);
-    if (v >= 1) nb_max = std::min(nb_max, v);
-  }
-  nb_max = std::min(nb_max, B);
+  const int64_t nb_max = block_states(per_state, B, "KIN_TS_BLOCK_STATES");
   int stages = 3;      // KIN_TS_STAGES=1|2 ends every block after stage 1 / the entry gather: a knob for timing, never for results
   if (const char* e = getenv("KIN_TS_STAGES")) { const int v = atoi(e); if (v == 1 || v == 2) stages = v; }
   h->ts_dr.alloc((size_t)nb_max * 2 * R);
@@ -65,37 +55,32 @@ void ts_run(kin_network* h, int64_t B, const double* d_u, const FluxSource& src,
     ra.nb = (int)nb_max;
     h->ts_part.alloc((size_t)slices_cap(ts_row_slices(ra, h->n_cu)) * 3 * N);
   }
-  for (int64_t b0 = 0; b0 < B; b0 += nb_max) {
-    const int64_t nb = std::min(nb_max, B - b0);
+  for_blocks(B, nb_max, accumulate, [&](int64_t b0, int64_t nb, int use_prev) {
     cnt.b0 = (int32_t)b0;
     TsRateArgs q{};
-    q.N = (int)N; q.R = (int)R; q.nb = (int)nb; q.x0 = h->x0.p; q.x1 = h->x1.p; q.u = d_u + (size_t)b0 * N;
-    if (src.T) q.T = src.T + b0;
-    else if (src.k) {
-      q.k = src.k_row ? src.k : src.k + (size_t)b0 * (size_t)src.k_stride;
-      q.k_stride = src.k_stride; q.k_row = src.k_row ? src.k_row + b0 : nullptr;
-    } else { q.k = h->k.p; q.k_stride = 0; q.k_row = nullptr; }
+    q.N = (int)N; q.R = (int)R; q.nb = (int)nb; q.x0 = h->x0.p; q.x1 = h->x1.p; q.u = b.u + (size_t)b0 * N;
+    const FluxSource bs = src.at(b0);
+    if (bs.T) q.T = bs.T;
+    else if (bs.k) { q.k = bs.k; q.k_stride = bs.k_stride; q.k_row = bs.k_row; }
+    else { q.k = h->k.p; q.k_stride = 0; q.k_row = nullptr; }
     q.Ea = h->Ea.p; q.A = h->A.p; q.has_kmax = h->has_kmax ? 1 : 0; q.k_max = h->k_max; q.t_mult = h->t_mult;
     q.rates = rows ? h->ts_rates.p : nullptr; q.dr = h->ts_dr.p;
     launch_ts_rates(q, s);
-    if (stages == 1) continue;
+    if (stages == 1) return;
     TsEntryArgs ea{};
     ea.p = jp; ea.R = (int)R; ea.nb = (int)nb; ea.nnz = nnz; ea.dr = h->ts_dr.p;
     ea.jv = o.vals ? o.vals + (size_t)b0 * nnz : h->ts_jv.p; ea.cnt = cnt;
     launch_ts_entries(ea, slices_cap(ts_entry_slices(jp, nb, h->n_cu)), s);
-    if (!rows || stages == 2) continue;
+    if (!rows || stages == 2) return;
     ra.nb = (int)nb; ra.jv = ea.jv; ra.rates = h->ts_rates.p; ra.cnt = cnt;
     ra.part = o.summary ? h->ts_part.p : nullptr; ra.g = o.norm ? h->ts_g.p : nullptr;
     ra.diag = o.diag ? o.diag + (size_t)b0 * N : nullptr; ra.err = o.err ? o.err + (size_t)b0 * N : nullptr;
     const int Y = slices_cap(ts_row_slices(ra, h->n_cu));
     launch_ts_rows(ra, Y, s);
-    if (o.summary) launch_ts_fold(N, Y, h->ts_part.p, o.summary, (accumulate || b0 > 0) ? 1 : 0, s);
+    if (o.summary) launch_ts_fold(N, Y, h->ts_part.p, o.summary, use_prev, s);
     if (o.norm) launch_ts_norm(N, nb, h->ts_g.p, cnt, o.norm + b0, s);
-  }
+  });
 }
-
-// row_begin of the solution / ensemble forms as the kernels take it (the passes hold the number of rows below 2^31)
-int32_t ts_row_begin(int64_t row_begin) { return (int32_t)std::min<int64_t>(row_begin, INT32_MAX); }
 
 void ts_limits(kin_network* h) {
   require(h->host.nnz() < ((int64_t)1 << 31), ERR_UNSUPPORTED, "timescale pass: nnz beyond 32-bit offsets");
@@ -107,40 +92,22 @@ void ts_check(kin_network* h, int64_t B, bool have_k, bool have_row, bool have_T
   ts_limits(h);
 }
 
-// host entries of the timescale form: the outputs staged through the handle's buffers (summary uploaded first when it takes
-// part); B states of which those cnt names count
-void ts_host_call(kin_network* h, int64_t B, const double* d_u, const FluxSource& src, const TsCount& cnt, int accumulate, double* summary,
-                  double* diag, double* err, double* norm, hipStream_t s) {
-  const size_t N = (size_t)h->host.N;
-  TsOut o{};
-  if (summary) {
-    h->ts_o_summary.alloc(3 * N);
-    if (accumulate) h->ts_o_summary.upload(summary, 3 * N, s);
-    o.summary = h->ts_o_summary.p;
-  }
-  if (diag) { h->ts_o_diag.alloc((size_t)B * N); o.diag = h->ts_o_diag.p; }
-  if (err) { h->ts_o_err.alloc((size_t)B * N); o.err = h->ts_o_err.p; }
-  if (norm) { h->ts_o_norm.alloc((size_t)B); o.norm = h->ts_o_norm.p; }
-  ts_run(h, B, d_u, src, cnt, accumulate, o, s);
-  if (summary) h->ts_o_summary.download(summary, 3 * N, s);
-  if (diag) h->ts_o_diag.download(diag, (size_t)B * N, s);
-  if (err) h->ts_o_err.download(err, (size_t)B * N, s);
-  if (norm) h->ts_o_norm.download(norm, (size_t)B, s);
-  KIN_HIP(hipStreamSynchronize(s));
-}
-
-// the host forms' inputs on the device (as kin_flux_batched stages them)
-FluxSource ts_upload(kin_network* h, int64_t B, const double* u, const double* k, int64_t n_k_rows, const int64_t* k_row, const double* T,
-                     hipStream_t s) {
-  require(u != nullptr || B == 0, ERR_INVALID_ARG, "null state buffer");
-  if (k && k_row) { require(n_k_rows >= 1 || B == 0, ERR_INVALID_ARG, "k has no rows"); flux_check_rows(k_row, B, n_k_rows); }
-  else if (k) require(n_k_rows == B, ERR_INVALID_ARG, "k without k_row needs one row per state (n_k_rows == B)");
-  const int64_t N = h->host.N, R = h->host.R;
-  if (B > 0) h->f_u.upload(u, (size_t)B * N, s);
-  if (k && n_k_rows > 0) h->f_k.upload(k, (size_t)n_k_rows * R, s);
-  if (k_row && B > 0) h->f_krow.upload(k_row, (size_t)B, s);
-  if (T && B > 0) h->f_T.upload(T, (size_t)B, s);
-  return FluxSource{k ? h->f_k.p : nullptr, R, k_row ? h->f_krow.p : nullptr, T ? h->f_T.p : nullptr};
+// host entries of the timescale form: summary (optional, accumulating) staged through the handle as every pass's result, the
+// per-state outputs through the pass's own buffers
+void ts_host_call(kin_network* h, const StateBatch& b, int64_t row_begin, int accumulate, double* summary, double* diag, double* err,
+                  double* norm, hipStream_t s) {
+  const size_t N = (size_t)h->host.N, B = (size_t)b.B;
+  staged_result(h, 3 * (int64_t)N, summary, accumulate, s, [&](double* d_summary) {
+    TsOut o{};
+    o.summary = d_summary;
+    if (diag) { h->ts_o_diag.alloc(B * N); o.diag = h->ts_o_diag.p; }
+    if (err) { h->ts_o_err.alloc(B * N); o.err = h->ts_o_err.p; }
+    if (norm) { h->ts_o_norm.alloc(B); o.norm = h->ts_o_norm.p; }
+    ts_run(h, b, row_begin, accumulate, o, s);
+    if (diag) h->ts_o_diag.download(diag, B * N, s);
+    if (err) h->ts_o_err.download(err, B * N, s);
+    if (norm) h->ts_o_norm.download(norm, B, s);
+  });
 }
 
 }  // namespace
@@ -170,13 +137,6 @@ TsTables build_ts_tables(const NetworkHost& h) {
 
 }  // namespace kin
 
-#define KIN_TRY(h) try { KIN_HIP(hipSetDevice((h)->device));
-#define KIN_CATCH(h)                                                        \
-  }                                                                         \
-  catch (const KinError& e) { (h)->err = e.what(); return e.code; }         \
-  catch (const std::exception& e) { (h)->err = e.what(); return KIN_ERR_DEVICE; } \
-  return KIN_OK;
-
 extern "C" {
 
 int kin_timescale_plan_host(int64_t n_species, int64_t n_reactions, const int64_t* reac_ptr, const int64_t* reac_idx,
@@ -200,7 +160,7 @@ int kin_jac_batched_dev(kin_network* h, int64_t B, const double* d_u, const doub
   ts_check(h, B, d_k != nullptr, d_k_row != nullptr, d_T != nullptr, d_vals != nullptr);
   require(d_u != nullptr || B == 0, ERR_INVALID_ARG, "null state buffer");
   hipStream_t s = stream ? (hipStream_t)stream : h->stream;
-  ts_run(h, B, d_u, FluxSource{d_k, h->host.R, d_k_row, d_T}, TsCount{0, nullptr, 0, 0}, 0, TsOut{d_vals, nullptr, nullptr, nullptr, nullptr}, s);
+  ts_run(h, StateBatch{B, d_u, FluxSource{d_k, h->host.R, d_k_row, d_T}, nullptr, 0}, 0, 0, TsOut{d_vals, nullptr, nullptr, nullptr, nullptr}, s);
   KIN_CATCH(h)
 }
 
@@ -210,10 +170,10 @@ int kin_jac_batched(kin_network* h, int64_t B, const double* u, const double* k,
   KIN_TRY(h)
   ts_check(h, B, k != nullptr, k_row != nullptr, T != nullptr, vals != nullptr);
   hipStream_t s = h->stream;
-  const FluxSource src = ts_upload(h, B, u, k, n_k_rows, k_row, T, s);
+  const StateBatch b = host_batch(h, B, u, k, n_k_rows, k_row, T, s);
   const size_t n = (size_t)B * (size_t)h->host.nnz();
   h->ts_o_vals.alloc(n);
-  ts_run(h, B, h->f_u.p, src, TsCount{0, nullptr, 0, 0}, 0, TsOut{h->ts_o_vals.p, nullptr, nullptr, nullptr, nullptr}, s);
+  ts_run(h, b, 0, 0, TsOut{h->ts_o_vals.p, nullptr, nullptr, nullptr, nullptr}, s);
   h->ts_o_vals.download(vals, n, s);
   KIN_HIP(hipStreamSynchronize(s));
   KIN_CATCH(h)
@@ -226,7 +186,7 @@ int kin_timescale_batched_dev(kin_network* h, int64_t B, const double* d_u, cons
   ts_check(h, B, d_k != nullptr, d_k_row != nullptr, d_T != nullptr, d_summary || d_diag || d_err || d_norm);
   require(d_u != nullptr || B == 0, ERR_INVALID_ARG, "null state buffer");
   hipStream_t s = stream ? (hipStream_t)stream : h->stream;
-  ts_run(h, B, d_u, FluxSource{d_k, h->host.R, d_k_row, d_T}, TsCount{0, nullptr, 0, 0}, accumulate,
+  ts_run(h, StateBatch{B, d_u, FluxSource{d_k, h->host.R, d_k_row, d_T}, nullptr, 0}, 0, accumulate,
          TsOut{nullptr, d_summary, d_diag, d_err, d_norm}, s);
   KIN_CATCH(h)
 }
@@ -237,8 +197,7 @@ int kin_timescale_batched(kin_network* h, int64_t B, const double* u, const doub
   KIN_TRY(h)
   ts_check(h, B, k != nullptr, k_row != nullptr, T != nullptr, summary || diag || err || norm);
   hipStream_t s = h->stream;
-  const FluxSource src = ts_upload(h, B, u, k, n_k_rows, k_row, T, s);
-  ts_host_call(h, B, h->f_u.p, src, TsCount{0, nullptr, 0, 0}, accumulate, summary, diag, err, norm, s);
+  ts_host_call(h, host_batch(h, B, u, k, n_k_rows, k_row, T, s), 0, accumulate, summary, diag, err, norm, s);
   KIN_CATCH(h)
 }
 
@@ -248,9 +207,9 @@ int kin_solution_timescale(kin_network* h, const double* k, int64_t n_k_rows, co
   KIN_TRY(h)
   require(row_begin >= 0, ERR_INVALID_ARG, "row_begin < 0");
   hipStream_t s = h->stream;
-  const FluxSource src = drg_solution_source(h, k, n_k_rows, k_row, T_rows, summary || norm, s);
+  const StateBatch b = solution_batch(h, drg_check, k, n_k_rows, k_row, T_rows, summary || norm, s);
   ts_limits(h);
-  ts_host_call(h, h->n_saved, h->d_sol_u.p, src, TsCount{0, nullptr, 0, ts_row_begin(row_begin)}, accumulate, summary, nullptr, nullptr, norm, s);
+  ts_host_call(h, b, row_begin, accumulate, summary, nullptr, nullptr, norm, s);
   KIN_CATCH(h)
 }
 
@@ -260,10 +219,9 @@ int kin_ensemble_timescale(kin_network* h, const double* k, int64_t n_k_rows, co
   KIN_TRY(h)
   require(row_begin >= 0, ERR_INVALID_ARG, "row_begin < 0");
   hipStream_t s = h->stream;
-  const FluxSource src = drg_ensemble_source(h, k, n_k_rows, k_row, T_rows, summary || norm, s);
+  const StateBatch b = ensemble_batch(h, drg_check, k, n_k_rows, k_row, T_rows, summary || norm, s);
   ts_limits(h);
-  ts_host_call(h, h->ens.K * h->ens.cap, h->ens.sol, src, TsCount{0, h->ens_segn.p, (int32_t)h->ens.cap, ts_row_begin(row_begin)}, accumulate, summary, nullptr,
-               nullptr, norm, s);
+  ts_host_call(h, b, row_begin, accumulate, summary, nullptr, nullptr, norm, s);
   KIN_CATCH(h)
 }
 

@@ -94,6 +94,101 @@ class KineticaHipError(RuntimeError):
         self.code = code
 
 
+# ---- the argument types of every entry include/kinetica_hip.h declares that takes arguments, by name -----------------------------
+P64, PD, P32, PV = POINTER(c_int64), POINTER(c_double), POINTER(c_int32), c_void_p
+_NET = [c_int64, c_int64] + [P64] * 6 + [c_int]     # a *_host entry's leading arguments: sizes, the six index lists, index base
+_SOLVED = [P64, POINTER(c_int32), POINTER(KinStats)]      # n_saved, retcode, stats of a solve
+_MEMBERS = [P64, PD, PD, P64, POINTER(c_int32), POINTER(KinStats)]      # n_rows, out_t, out_u, n_saved, retcodes, stats of an ensemble
+_KSRC = [PD, c_int64, P64, PD]      # the rate constants of a pass on host arrays: k, n_k_rows, k_row, T
+ARGTYPES = {
+    "kin_struct_size": [c_int], "kin_last_error": [PV],
+    "kin_network_create": _NET + [POINTER(PV)], "kin_network_destroy": [PV], "kin_network_sizes": [PV, P64, P64],
+    "kin_set_rates": [PV, PD], "kin_get_rates": [PV, PD], "kin_set_arrhenius": [PV, PD, PD, c_double, c_double],
+    "kin_rates_at": [PV, c_double, PD], "kin_arrhenius_eval": [PD, PD, c_int64, c_double, c_double, c_double, PD],
+    "kin_rate_table": [PV, PD, c_int64, PD], "kin_rate_table_rows": [PV, P64, c_int64, PD], "kin_rate_table_dev": [PV, PD, c_int64, PV],
+    "kin_rhs": [PV, PD, PD], "kin_rhs_batched": [PV, c_int64, PD, PD, PD], "kin_rhs_batched_dev": [PV, c_int64] + [PV] * 4,
+    "kin_rhs_block_dev": [PV, c_int64, c_int64, PV, PV, PV],
+    "kin_jac_nnz": [PV, P64], "kin_jac_pattern": [PV, P64, P64, c_int], "kin_jac_values": [PV, PD, PD],
+    "kin_solve": [PV, POINTER(KinParams), PD, PD, PD, PD, c_int64] + _SOLVED,
+    "kin_solve_explicit": [PV, POINTER(KinParams), PD, PD, PD, PD, c_int64] + _SOLVED,
+    "kin_solve_continuous": [PV, POINTER(KinParams), PD, PD, PD, c_int64] + _SOLVED,
+    "kin_solve_ensemble": [PV, POINTER(KinParams), c_int64, PD, PD, PD, PD, PD, PD, c_int64] + _MEMBERS,
+    "kin_solve_ensemble_continuous": [PV, POINTER(KinParams), c_int64, PD, P64, PD, PD] + _MEMBERS,
+    "kin_solve_ensemble_discrete": [PV, POINTER(KinParams), c_int64, PD, P64, PD, PD] + _MEMBERS,
+    "kin_solve_ensemble_continuous_params": [PV, POINTER(KinParams), c_int64, PD, PD, PD, P64, PD, PD] + _MEMBERS,
+    "kin_solve_ensemble_discrete_params": [PV, POINTER(KinParams), c_int64, PD, PD, PD, P64, PD, PD] + _MEMBERS,
+    "kin_integrator_init": [PV, POINTER(KinParams), PD, PD, PD, PD, c_int64],
+    "kin_integrator_init_continuous": [PV, POINTER(KinParams), PD, PD, PD, c_int64],
+    "kin_integrator_step": [PV, c_int64, P64], "kin_integrator_state": [PV, PD, PD, POINTER(c_int32), POINTER(KinStats)],
+    "kin_solution_size": [PV, P64, P64], "kin_solution_copy": [PV, PD, PD], "kin_solution_max": [PV, PD],
+    "kin_solution_max_dev": [PV, PV], "kin_solution_dot": [PV, PD, PD],
+    "kin_newton_solve": [PV, c_double, PD, PD, PD], "kin_device_count": [POINTER(c_int)], "kin_set_device": [c_int],
+    # diagnostics
+    "kin_resident_probe": [PV, c_int64, PD, PD, PD, PD, PD, PD, P32, P64],
+    "kin_newton_probe": [PV, c_int64, c_int32, PD, PD, PD, PD, P32, P64],
+    "kin_step_probe": [PV, c_int32, c_int32, c_int64, c_int64, c_int64, P32, PD, P32, PD, PD, PD, P64],
+    "kin_eval_probe": [PV, c_int32, c_int32, c_int32, c_int64, c_int64, P32, PD, PD, c_double, PD, PD, PD, P32, c_double, PD, c_int64, PD,
+                       P32, P64],
+    "kin_cache_probe": [PV, c_int32, c_int32, c_int64, PD, PD, P32, PD, c_double, P64, c_int64, PD, P64, PD, PD, P32, P64],
+    "kin_lu_analyze_host": _NET + [c_int] * 5 + [P64],
+    # library order (tiled sweep) and the plan queries of the two batched sweeps
+    "kin_lib_layout": [PV, c_int, P64, P64, P64, P32, P64],
+    "kin_lib_layout_host": _NET + [c_int, P64, P64, P64, POINTER(ctypes.c_uint64)] + [P32] * 6,
+    "kin_states_to_lib_dev": [PV, c_int64, PV, PV, PV], "kin_states_from_lib_dev": [PV, c_int64, PV, PV, PV],
+    "kin_rates_to_lib_dev": [PV, c_int64, PV, PV, PV], "kin_rate_table_lib_dev": [PV, PD, c_int64, PV],
+    "kin_rhs_tiled_dev": [PV, c_int64] + [PV] * 5, "kin_rhs_batched_T_dev": [PV, c_int64] + [PV] * 4,
+    "kin_rhs_batched_klib_dev": [PV, c_int64] + [PV] * 4,
+    "kin_sweep_plan": [PV, c_int64, PV, PV, PV, P64], "kin_sweep_plan_host": _NET + [c_int, c_int64, c_int, c_int, c_int, P64],
+    "kin_tiled_sweep_plan": [PV, c_int64, c_int, P64], "kin_tiled_sweep_plan_host": _NET + [c_int, c_int64, c_int, P64],
+    # reaction fluxes, per state and segmented, and the stored ensemble
+    "kin_flux_batched": [PV, c_int64, PD] + _KSRC + [PD, PD, PD], "kin_flux_batched_dev": [PV, c_int64] + [PV] * 8,
+    "kin_solution_flux": [PV, PD] + _KSRC + [PD, PD],
+    "kin_flux_plan_host": [c_int64, c_int64, c_int64, c_int, c_int, c_int, c_int64, c_int, c_int, c_int, P64],
+    "kin_network_compute_units": [PV, POINTER(c_int)],
+    "kin_flux_segmented": [PV, c_int64, c_int64, P64, PD] + _KSRC + [PD, PD], "kin_flux_segmented_dev": [PV, c_int64, c_int64] + [PV] * 8,
+    "kin_ensemble_size": [PV, P64, P64, P64, P64], "kin_ensemble_max": [PV, PD], "kin_ensemble_dot": [PV, PD, PD],
+    "kin_ensemble_flux": [PV, PD] + _KSRC + [PD],
+    # directed relation graph, DRGEP, reaction elimination, path flux analysis
+    "kin_drg_pattern_host": _NET + [c_int, P64, P64, P64], "kin_drg_pattern": [PV, c_int, c_int, P64, P64, P64],
+    "kin_drg_batched": [PV, c_int, c_int64, PD] + _KSRC + [c_int, PD],
+    "kin_drg_batched_dev": [PV, c_int, c_int64, PV, PV, PV, PV, c_int, PV, PV],
+    "kin_solution_drg": [PV, c_int] + _KSRC + [c_int, PD], "kin_ensemble_drg": [PV, c_int] + _KSRC + [c_int, PD],
+    "kin_drgep_batched": [PV, c_int, c_int64, PD] + _KSRC + [P64, c_int64, c_int, c_int, PD, PD, PD, P32],
+    "kin_drgep_batched_dev": [PV, c_int, c_int64] + [PV] * 5 + [c_int64, c_int, PV, PV],
+    "kin_drgep_paths": [PV, c_int, c_int64, PD, P64, c_int64, c_int, c_int, PD, PD, P32],
+    "kin_solution_drgep": [PV, c_int] + _KSRC + [P64, c_int64, c_int, c_int, PD],
+    "kin_ensemble_drgep": [PV, c_int] + _KSRC + [P64, c_int64, c_int, c_int, PD],
+    "kin_reaction_importance_plan_host": _NET + [c_int, P64, P64, P64, P64],
+    "kin_reaction_importance_batched": [PV, c_int, c_int64, PD] + _KSRC + [P64, c_int64, c_int, c_int, PD, PD],
+    "kin_reaction_importance_batched_dev": [PV, c_int, c_int64] + [PV] * 5 + [c_int64, c_int, PV, PV],
+    "kin_solution_reaction_importance": [PV, c_int] + _KSRC + [P64, c_int64, c_int, c_int, PD],
+    "kin_ensemble_reaction_importance": [PV, c_int] + _KSRC + [P64, c_int64, c_int, c_int, PD],
+    "kin_pfa_pattern_host": _NET + [c_int, P64, P64, P64], "kin_pfa_pattern": [PV, c_int, c_int, P64, P64, P64],
+    "kin_pfa_batched": [PV, c_int, c_int64, PD] + _KSRC + [c_int, PD, PD, PD, PD],
+    "kin_pfa_batched_dev": [PV, c_int, c_int64, PV, PV, PV, PV, c_int, PV, PV],
+    "kin_pfa_paths": [PV, c_int, c_int64, PD, PD, c_int, PD, PD],
+    "kin_solution_pfa": [PV, c_int] + _KSRC + [c_int, PD], "kin_ensemble_pfa": [PV, c_int] + _KSRC + [c_int, PD],
+    # timescale analysis
+    "kin_jac_batched": [PV, c_int64, PD] + _KSRC + [PD], "kin_jac_batched_dev": [PV, c_int64] + [PV] * 6,
+    "kin_timescale_batched": [PV, c_int64, PD] + _KSRC + [c_int, PD, PD, PD, PD],
+    "kin_timescale_batched_dev": [PV, c_int64] + [PV] * 4 + [c_int] + [PV] * 5,
+    "kin_solution_timescale": [PV] + _KSRC + [c_int64, c_int, PD, PD], "kin_ensemble_timescale": [PV] + _KSRC + [c_int64, c_int, PD, PD],
+    "kin_timescale_plan_host": _NET + [P64],
+    # cross-member statistics and the Sobol indices of a Saltelli design
+    "kin_members_inputs_host": [c_int64, c_int64, PD, P32, c_int, P64, PD],
+    "kin_members_moments": [PV, c_int64, c_int64, PD, P32, P64, PD, PD, PD, PD],
+    "kin_members_moments_dev": [PV, c_int64, c_int64, PV, P32, P64] + [PV] * 5,
+    "kin_members_quantiles": [PV, c_int64, c_int64, PD, P32, P64, c_int64, PD, c_int64, PD],
+    "kin_members_quantiles_dev": [PV, c_int64, c_int64, PV, P32, P64, c_int64, PD, c_int64, PV, PV],
+    "kin_members_correlate": [PV, c_int64, c_int64, PD, P32, P64, c_int64, PD, c_int64, c_int, PD],
+    "kin_members_correlate_dev": [PV, c_int64, c_int64, PV, P32, P64, c_int64, PD, c_int64, c_int, PV, PV],
+    "kin_ensemble_moments": [PV, P32, P64, PD, PD, PD, PD], "kin_ensemble_quantiles": [PV, P32, P64, c_int64, PD, c_int64, PD],
+    "kin_ensemble_correlate": [PV, P32, P64, c_int64, PD, c_int64, c_int, PD],
+    "kin_members_sobol": [PV, c_int64, c_int64, c_int64, PD, P32, P64, c_int64, PD, PD, PD, PD],
+    "kin_members_sobol_dev": [PV, c_int64, c_int64, c_int64, PV, P32, P64, c_int64] + [PV] * 5,
+    "kin_ensemble_sobol": [PV, c_int64, c_int64, P32, P64, c_int64, PD, PD, PD, PD],
+}
+
 _lib = None
 
 
@@ -113,153 +208,17 @@ def lib():
             except Exception:
                 pass
         L = ctypes.CDLL(LIB_PATH)
-        P64, PD = POINTER(c_int64), POINTER(c_double)
+        for name, argtypes in ARGTYPES.items():
+            fn = getattr(L, name, None)     # entries added under ABI 6 are found by symbol lookup: an earlier build lacks some
+            if fn is not None:
+                fn.argtypes = argtypes
         L.kin_struct_size.restype = c_int64
-        L.kin_struct_size.argtypes = [c_int]
         if L.kin_abi_version() != ABI_VERSION or L.kin_struct_size(0) != ctypes.sizeof(KinParams) or \
                 L.kin_struct_size(1) != ctypes.sizeof(KinStats):
             raise ImportError(f"{LIB_PATH}: ABI version {L.kin_abi_version()} / struct sizes do not match this binding "
                               f"(version {ABI_VERSION}); rebuild the library")
         L.kin_version.restype = c_char_p
         L.kin_last_error.restype = c_char_p
-        L.kin_last_error.argtypes = [c_void_p]
-        L.kin_network_create.argtypes = [c_int64, c_int64, P64, P64, P64, P64, P64, P64, c_int, POINTER(c_void_p)]
-        L.kin_network_destroy.argtypes = [c_void_p]
-        L.kin_network_sizes.argtypes = [c_void_p, P64, P64]
-        L.kin_set_rates.argtypes = [c_void_p, PD]
-        L.kin_get_rates.argtypes = [c_void_p, PD]
-        L.kin_set_arrhenius.argtypes = [c_void_p, PD, PD, c_double, c_double]
-        L.kin_rates_at.argtypes = [c_void_p, c_double, PD]
-        L.kin_arrhenius_eval.argtypes = [PD, PD, c_int64, c_double, c_double, c_double, PD]
-        L.kin_rate_table.argtypes = [c_void_p, PD, c_int64, PD]
-        L.kin_rhs.argtypes = [c_void_p, PD, PD]
-        L.kin_rhs_batched.argtypes = [c_void_p, c_int64, PD, PD, PD]
-        L.kin_rhs_batched_dev.argtypes = [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]
-        L.kin_jac_nnz.argtypes = [c_void_p, P64]
-        L.kin_jac_pattern.argtypes = [c_void_p, P64, P64, c_int]
-        L.kin_jac_values.argtypes = [c_void_p, PD, PD]
-        L.kin_solve.argtypes = [c_void_p, POINTER(KinParams), PD, PD, PD, PD, c_int64, P64, POINTER(c_int32),
-                                POINTER(KinStats)]
-        L.kin_solve_explicit.argtypes = [c_void_p, POINTER(KinParams), PD, PD, PD, PD, c_int64, P64, POINTER(c_int32),
-                                POINTER(KinStats)]
-        L.kin_solve_continuous.argtypes = [c_void_p, POINTER(KinParams), PD, PD, PD, c_int64, P64, POINTER(c_int32),
-                                           POINTER(KinStats)]
-        L.kin_solve_ensemble_continuous.argtypes = [c_void_p, POINTER(KinParams), c_int64, PD, P64, PD, PD, P64, PD, PD, P64,
-                                                    POINTER(c_int32), POINTER(KinStats)]
-        if hasattr(L, "kin_solve_ensemble_discrete"):   # added under ABI 6: found by symbol lookup, an earlier build lacks it
-            L.kin_solve_ensemble_discrete.argtypes = [c_void_p, POINTER(KinParams), c_int64, PD, P64, PD, PD, P64, PD, PD, P64,
-                                                      POINTER(c_int32), POINTER(KinStats)]
-        for name in ("kin_solve_ensemble_continuous_params", "kin_solve_ensemble_discrete_params"):   # (also under ABI 6)
-            if hasattr(L, name):
-                getattr(L, name).argtypes = [c_void_p, POINTER(KinParams), c_int64, PD, PD, PD, P64, PD, PD, P64, PD, PD, P64,
-                                             POINTER(c_int32), POINTER(KinStats)]
-        if hasattr(L, "kin_resident_probe"):   # (also under ABI 6)
-            L.kin_resident_probe.argtypes = [c_void_p, c_int64, PD, PD, PD, PD, PD, PD, POINTER(c_int32), P64]
-        if hasattr(L, "kin_newton_probe"):   # (also under ABI 6)
-            L.kin_newton_probe.argtypes = [c_void_p, c_int64, c_int32, PD, PD, PD, PD, POINTER(c_int32), P64]
-        if hasattr(L, "kin_step_probe"):   # (also under ABI 6)
-            L.kin_step_probe.argtypes = [c_void_p, c_int32, c_int32, c_int64, c_int64, c_int64, POINTER(c_int32), PD, POINTER(c_int32),
-                                         PD, PD, PD, P64]
-        if hasattr(L, "kin_eval_probe"):   # (also under ABI 6)
-            P32 = POINTER(c_int32)
-            L.kin_eval_probe.argtypes = [c_void_p, c_int32, c_int32, c_int32, c_int64, c_int64, P32, PD, PD, c_double, PD, PD, PD, P32,
-                                         c_double, PD, c_int64, PD, P32, P64]
-        if hasattr(L, "kin_cache_probe"):   # (also under ABI 6)
-            P32 = POINTER(c_int32)
-            L.kin_cache_probe.argtypes = [c_void_p, c_int32, c_int32, c_int64, PD, PD, P32, PD, c_double, P64, c_int64, PD, P64, PD, PD, P32, P64]
-        if hasattr(L, "kin_flux_batched"):   # (also under ABI 6: the reaction-flux pass)
-            L.kin_flux_batched.argtypes = [c_void_p, c_int64, PD, PD, c_int64, P64, PD, PD, PD, PD]
-            L.kin_flux_batched_dev.argtypes = [c_void_p, c_int64] + [c_void_p] * 8
-            L.kin_solution_flux.argtypes = [c_void_p, PD, PD, c_int64, P64, PD, PD, PD]
-        if hasattr(L, "kin_flux_plan_host"):   # (also under ABI 6: the flux passes' plan query)
-            L.kin_flux_plan_host.argtypes = [c_int64, c_int64, c_int64, c_int, c_int, c_int, c_int64, c_int, c_int, c_int, P64]
-            L.kin_network_compute_units.argtypes = [c_void_p, POINTER(c_int)]
-        if hasattr(L, "kin_flux_segmented"):   # (also under ABI 6: the segmented pass and the analysis of a stored ensemble)
-            L.kin_flux_segmented.argtypes = [c_void_p, c_int64, c_int64, P64, PD, PD, c_int64, P64, PD, PD, PD]
-            L.kin_flux_segmented_dev.argtypes = [c_void_p, c_int64, c_int64] + [c_void_p] * 8
-            L.kin_ensemble_size.argtypes = [c_void_p, P64, P64, P64, P64]
-            L.kin_ensemble_max.argtypes = [c_void_p, PD]
-            L.kin_ensemble_dot.argtypes = [c_void_p, PD, PD]
-            L.kin_ensemble_flux.argtypes = [c_void_p, PD, PD, c_int64, P64, PD, PD]
-        if hasattr(L, "kin_drg_batched"):   # (also under ABI 6: the directed relation graph)
-            L.kin_drg_pattern_host.argtypes = [c_int64, c_int64] + [P64] * 6 + [c_int, c_int, P64, P64, P64]
-            L.kin_drg_pattern.argtypes = [c_void_p, c_int, c_int, P64, P64, P64]
-            L.kin_drg_batched.argtypes = [c_void_p, c_int, c_int64, PD, PD, c_int64, P64, PD, c_int, PD]
-            L.kin_drg_batched_dev.argtypes = [c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]
-            L.kin_solution_drg.argtypes = [c_void_p, c_int, PD, c_int64, P64, PD, c_int, PD]
-            L.kin_ensemble_drg.argtypes = [c_void_p, c_int, PD, c_int64, P64, PD, c_int, PD]
-        if hasattr(L, "kin_drgep_batched"):   # (also under ABI 6: DRG with error propagation)
-            P32 = POINTER(c_int32)
-            L.kin_drgep_batched_dev.argtypes = [c_void_p, c_int, c_int64] + [c_void_p] * 5 + [c_int64, c_int, c_void_p, c_void_p]
-            L.kin_drgep_batched.argtypes = [c_void_p, c_int, c_int64, PD, PD, c_int64, P64, PD, P64, c_int64, c_int, c_int, PD, PD, PD, P32]
-            L.kin_drgep_paths.argtypes = [c_void_p, c_int, c_int64, PD, P64, c_int64, c_int, c_int, PD, PD, P32]
-            L.kin_solution_drgep.argtypes = [c_void_p, c_int, PD, c_int64, P64, PD, P64, c_int64, c_int, c_int, PD]
-            L.kin_ensemble_drgep.argtypes = [c_void_p, c_int, PD, c_int64, P64, PD, P64, c_int64, c_int, c_int, PD]
-        if hasattr(L, "kin_reaction_importance_batched"):   # (also under ABI 6: reaction elimination)
-            L.kin_reaction_importance_plan_host.argtypes = [c_int64, c_int64] + [P64] * 6 + [c_int, c_int, P64, P64, P64, P64]
-            L.kin_reaction_importance_batched_dev.argtypes = [c_void_p, c_int, c_int64] + [c_void_p] * 5 + [c_int64, c_int, c_void_p, c_void_p]
-            L.kin_reaction_importance_batched.argtypes = [c_void_p, c_int, c_int64, PD, PD, c_int64, P64, PD, P64, c_int64, c_int, c_int, PD, PD]
-            L.kin_solution_reaction_importance.argtypes = [c_void_p, c_int, PD, c_int64, P64, PD, P64, c_int64, c_int, c_int, PD]
-            L.kin_ensemble_reaction_importance.argtypes = [c_void_p, c_int, PD, c_int64, P64, PD, P64, c_int64, c_int, c_int, PD]
-        if hasattr(L, "kin_pfa_batched"):   # (also under ABI 6: path flux analysis)
-            L.kin_pfa_pattern_host.argtypes = [c_int64, c_int64] + [P64] * 6 + [c_int, c_int, P64, P64, P64]
-            L.kin_pfa_pattern.argtypes = [c_void_p, c_int, c_int, P64, P64, P64]
-            L.kin_pfa_batched_dev.argtypes = [c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]
-            L.kin_pfa_batched.argtypes = [c_void_p, c_int, c_int64, PD, PD, c_int64, P64, PD, c_int, PD, PD, PD, PD]
-            L.kin_pfa_paths.argtypes = [c_void_p, c_int, c_int64, PD, PD, c_int, PD, PD]
-            L.kin_solution_pfa.argtypes = [c_void_p, c_int, PD, c_int64, P64, PD, c_int, PD]
-            L.kin_ensemble_pfa.argtypes = [c_void_p, c_int, PD, c_int64, P64, PD, c_int, PD]
-        if hasattr(L, "kin_timescale_batched"):   # (also under ABI 6: the timescale analysis)
-            L.kin_jac_batched_dev.argtypes = [c_void_p, c_int64] + [c_void_p] * 6
-            L.kin_jac_batched.argtypes = [c_void_p, c_int64, PD, PD, c_int64, P64, PD, PD]
-            L.kin_timescale_batched_dev.argtypes = [c_void_p, c_int64] + [c_void_p] * 4 + [c_int] + [c_void_p] * 5
-            L.kin_timescale_batched.argtypes = [c_void_p, c_int64, PD, PD, c_int64, P64, PD, c_int, PD, PD, PD, PD]
-            L.kin_solution_timescale.argtypes = [c_void_p, PD, c_int64, P64, PD, c_int64, c_int, PD, PD]
-            L.kin_ensemble_timescale.argtypes = [c_void_p, PD, c_int64, P64, PD, c_int64, c_int, PD, PD]
-            L.kin_timescale_plan_host.argtypes = [c_int64, c_int64] + [P64] * 6 + [c_int, P64]
-        if hasattr(L, "kin_members_moments"):   # (also under ABI 6: cross-member statistics)
-            P32 = POINTER(c_int32)
-            L.kin_members_inputs_host.argtypes = [c_int64, c_int64, PD, P32, c_int, P64, PD]
-            L.kin_members_moments.argtypes = [c_void_p, c_int64, c_int64, PD, P32, P64, PD, PD, PD, PD]
-            L.kin_members_moments_dev.argtypes = [c_void_p, c_int64, c_int64, c_void_p, P32, P64] + [c_void_p] * 5
-            L.kin_members_quantiles.argtypes = [c_void_p, c_int64, c_int64, PD, P32, P64, c_int64, PD, c_int64, PD]
-            L.kin_members_quantiles_dev.argtypes = [c_void_p, c_int64, c_int64, c_void_p, P32, P64, c_int64, PD, c_int64, c_void_p, c_void_p]
-            L.kin_members_correlate.argtypes = [c_void_p, c_int64, c_int64, PD, P32, P64, c_int64, PD, c_int64, c_int, PD]
-            L.kin_members_correlate_dev.argtypes = [c_void_p, c_int64, c_int64, c_void_p, P32, P64, c_int64, PD, c_int64, c_int, c_void_p,
-                                                    c_void_p]
-            L.kin_ensemble_moments.argtypes = [c_void_p, P32, P64, PD, PD, PD, PD]
-            L.kin_ensemble_quantiles.argtypes = [c_void_p, P32, P64, c_int64, PD, c_int64, PD]
-            L.kin_ensemble_correlate.argtypes = [c_void_p, P32, P64, c_int64, PD, c_int64, c_int, PD]
-        if hasattr(L, "kin_members_sobol"):   # (also under ABI 6: Sobol indices of a Saltelli design)
-            P32 = POINTER(c_int32)
-            L.kin_members_sobol.argtypes = [c_void_p, c_int64, c_int64, c_int64, PD, P32, P64, c_int64, PD, PD, PD, PD]
-            L.kin_members_sobol_dev.argtypes = [c_void_p, c_int64, c_int64, c_int64, c_void_p, P32, P64, c_int64] + [c_void_p] * 5
-            L.kin_ensemble_sobol.argtypes = [c_void_p, c_int64, c_int64, P32, P64, c_int64, PD, PD, PD, PD]
-        if hasattr(L, "kin_sweep_plan"):   # (also under ABI 6: the plan queries of the two batched sweeps)
-            L.kin_sweep_plan.argtypes = [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, P64]
-            L.kin_sweep_plan_host.argtypes = [c_int64, c_int64] + [P64] * 6 + [c_int, c_int, c_int64, c_int, c_int, c_int, P64]
-            L.kin_tiled_sweep_plan.argtypes = [c_void_p, c_int64, c_int, P64]
-            L.kin_tiled_sweep_plan_host.argtypes = [c_int64, c_int64] + [P64] * 6 + [c_int, c_int, c_int64, c_int, P64]
-        L.kin_solve_ensemble.argtypes = [c_void_p, POINTER(KinParams), c_int64, PD, PD, PD, PD, PD, PD, c_int64, P64, PD, PD, P64,
-                                         POINTER(c_int32), POINTER(KinStats)]
-        L.kin_integrator_init.argtypes = [c_void_p, POINTER(KinParams), PD, PD, PD, PD, c_int64]
-        L.kin_integrator_init_continuous.argtypes = [c_void_p, POINTER(KinParams), PD, PD, PD, c_int64]
-        L.kin_integrator_step.argtypes = [c_void_p, c_int64, P64]
-        L.kin_integrator_state.argtypes = [c_void_p, PD, PD, POINTER(c_int32), POINTER(KinStats)]
-        L.kin_solution_size.argtypes = [c_void_p, P64, P64]
-        L.kin_solution_copy.argtypes = [c_void_p, PD, PD]
-        L.kin_solution_max.argtypes = [c_void_p, PD]
-        L.kin_newton_solve.argtypes = [c_void_p, c_double, PD, PD, PD]
-        L.kin_lib_layout.argtypes = [c_void_p, c_int, P64, P64, P64, POINTER(c_int32), P64]
-        L.kin_states_to_lib_dev.argtypes = [c_void_p, c_int64, c_void_p, c_void_p, c_void_p]
-        L.kin_states_from_lib_dev.argtypes = [c_void_p, c_int64, c_void_p, c_void_p, c_void_p]
-        L.kin_rates_to_lib_dev.argtypes = [c_void_p, c_int64, c_void_p, c_void_p, c_void_p]
-        L.kin_rate_table_lib_dev.argtypes = [c_void_p, PD, c_int64, c_void_p]
-        L.kin_rhs_tiled_dev.argtypes = [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
-        L.kin_rhs_batched_T_dev.argtypes = [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]
-        L.kin_rhs_batched_klib_dev.argtypes = [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]
-        L.kin_device_count.argtypes = [POINTER(c_int)]
-        L.kin_set_device.argtypes = [c_int]
         _lib = L
     return _lib
 
@@ -269,7 +228,7 @@ def _pd(a):
 
 
 def _p64(a):
-    return a.ctypes.data_as(POINTER(c_int64))
+    return None if a is None else a.ctypes.data_as(POINTER(c_int64))
 
 
 def _f64(a):
@@ -278,6 +237,37 @@ def _f64(a):
 
 def _p32(a):
     return None if a is None else a.ctypes.data_as(POINTER(c_int32))
+
+
+def _dp(x):
+    """A device pointer or a stream given as an int: the c_void_p of it, NULL for 0."""
+    return c_void_p(x) if x else None
+
+
+def _nonempty(a):
+    """a, or None for None and for an array without entries: an optional output the library is not handed."""
+    return a if a is not None and a.size else None
+
+
+def _net_head(net):
+    """The leading C arguments of a *_host entry for a FlatNetwork: n_species, n_reactions, its six index lists as int64 and
+    index base 0 (a pointer made by data_as keeps its array alive)."""
+    return [int(net.n_species), int(net.n_reactions)] + \
+        [_p64(np.ascontiguousarray(a, dtype=np.int64)) for a in (net.reac_ptr, net.reac_idx, net.reac_sto, net.prod_ptr, net.prod_idx,
+                                                                 net.prod_sto)] + [0]
+
+
+def _acc_buffer(length, given, what):
+    """(buffer, accumulate) of an output the library can fold an earlier result into: max(length, 1) zeros and 0, or - `given`,
+    the caller's `what` of `length` values - a copy of it, which then takes part, and 1. The caller's array is left alone; the
+    result is the buffer's first `length` entries."""
+    out = np.zeros(max(length, 1))
+    if given is None:
+        return out, 0
+    c = _f64(given).ravel()
+    assert len(c) == length, f"{what} has {len(c)} entries, not {length}"
+    out[:length] = c
+    return out, 1
 
 
 def _use32(use, K):
@@ -316,13 +306,8 @@ def device_count():
 def lib_layout_host(net, hubs=0):
     """The tiled sweep's library order of a FlatNetwork, computed on the host (no device): dict of the layout tables."""
     L = lib()
-    arrs = [np.ascontiguousarray(a, dtype=np.int64) for a in (net.reac_ptr, net.reac_idx, net.reac_sto, net.prod_ptr,
-                                                              net.prod_idx, net.prod_sto)]
-    P32, PU64 = POINTER(c_int32), POINTER(ctypes.c_uint64)
-    L.kin_lib_layout_host.argtypes = [c_int64, c_int64] + [POINTER(c_int64)] * 6 + [c_int, c_int, POINTER(c_int64), POINTER(c_int64),
-                                                                                  POINTER(c_int64), PU64, P32, P32, P32, P32, P32, P32]
     info = np.zeros(10, np.int64)
-    head = [int(net.n_species), int(net.n_reactions)] + [_p64(a) for a in arrs] + [0, int(hubs), _p64(info)]
+    head = _net_head(net) + [int(hubs), _p64(info)]
     st = L.kin_lib_layout_host(*head, None, None, None, None, None, None, None, None, None)
     if st != KIN_OK:
         raise KineticaHipError(st, "network has no tiled layout")
@@ -331,9 +316,8 @@ def lib_layout_host(net, hubs=0):
     rec = np.empty(max(P, 1), np.uint64); rowtab = np.empty(max(2 * Q, 1), np.int32); seg_q = np.empty(T + 1, np.int32)
     woff = np.empty(T, np.int32); wcnt = np.empty(T, np.int32); copy_src = np.empty(max(n_copy, 1), np.int32)
     seg_k = np.empty(2 * T, np.int32)
-    i32 = lambda a: a.ctypes.data_as(P32)
-    st = L.kin_lib_layout_host(*head, _p64(sp), _p64(slot), rec.ctypes.data_as(PU64), i32(rowtab), i32(seg_q), i32(woff), i32(wcnt),
-                               i32(copy_src), i32(seg_k))
+    st = L.kin_lib_layout_host(*head, _p64(sp), _p64(slot), rec.ctypes.data_as(POINTER(ctypes.c_uint64)), _p32(rowtab), _p32(seg_q),
+                               _p32(woff), _p32(wcnt), _p32(copy_src), _p32(seg_k))
     assert st == KIN_OK
     return dict(k_len=k_len, has_singles=bool(has_singles), seg_k=seg_k.reshape(T, 2), h=h, T=T, P=P, E=E, n_copy=n_copy, BS=BS, wbase=wbase, Q=Q, species_of_lib=sp, slot_of_reaction=slot,
                 rec=rec[:P], rowtab=rowtab[:2 * Q].reshape(Q, 2), seg_q=seg_q, win_off=woff, win_cnt=wcnt, copy_src=copy_src[:n_copy])
@@ -342,13 +326,9 @@ def lib_layout_host(net, hubs=0):
 def lu_analyze_host(net, hub_degree=0, max_rounds=0, max_tail_degree=0, max_degree=0, min_round=0):
     """Sizes of the symbolic Newton-matrix factorisation of a FlatNetwork, computed on the host (no device). Arguments left at 0
     take the library's defaults (lu.hpp: LUOptions)."""
-    L = lib()
-    arrs = [np.ascontiguousarray(a, dtype=np.int64) for a in (net.reac_ptr, net.reac_idx, net.reac_sto, net.prod_ptr,
-                                                              net.prod_idx, net.prod_sto)]
-    L.kin_lu_analyze_host.argtypes = [c_int64, c_int64] + [POINTER(c_int64)] * 6 + [c_int] * 6 + [POINTER(c_int64)]
     info = np.zeros(12, np.int64)
-    st = L.kin_lu_analyze_host(int(net.n_species), int(net.n_reactions), *[_p64(a) for a in arrs], 0, int(hub_degree), int(max_rounds),
-                               int(max_tail_degree), int(max_degree), int(min_round), _p64(info))
+    st = lib().kin_lu_analyze_host(*_net_head(net), int(hub_degree), int(max_rounds), int(max_tail_degree), int(max_degree),
+                                   int(min_round), _p64(info))
     if st != KIN_OK:
         raise KineticaHipError(st, "symbolic LU analysis failed")
     keys = ("ns", "m", "rounds", "nnzU", "nnzZ", "nnzV", "nnzLZ", "nnzNVU", "w_size", "fused_products", "plan_entries", "plan_tasks")
@@ -366,18 +346,22 @@ def drg_pattern_host(net, pairing=True):
     """kin_drg_pattern_host of a FlatNetwork, computed on the host (no device): (rowptr[N + 1], colidx[edges], info) - the edge
     CSR of the directed relation graph (0-based, sorted columns, no diagonal) and a dict of the DRG_INFO sizes: edges,
     contributions, and the rows / edges of the two gather plans by class (<= 8, 9 .. 256, > 256 contributions)."""
-    L = lib()
-    arrs = [np.ascontiguousarray(a, dtype=np.int64) for a in (net.reac_ptr, net.reac_idx, net.reac_sto, net.prod_ptr,
-                                                              net.prod_idx, net.prod_sto)]
-    head = [int(net.n_species), int(net.n_reactions)] + [_p64(a) for a in arrs] + [0, 1 if pairing else 0]
-    info = np.zeros(len(DRG_INFO), np.int64)
-    st = L.kin_drg_pattern_host(*head, _p64(info), None, None)
+    return _pattern_host("kin_drg_pattern_host", DRG_INFO, 0, net, pairing)
+
+
+def _pattern_host(entry, names, count, net, pairing):
+    """(rowptr[N + 1], colidx[nnz], info) of a host pattern entry: the sizes `names` first (nnz is info[count]), then the arrays."""
+    fn = getattr(lib(), entry)
+    head = _net_head(net) + [1 if pairing else 0]
+    info = np.zeros(len(names), np.int64)
+    st = fn(*head, _p64(info), None, None)
     if st != KIN_OK:
-        raise KineticaHipError(st, L.kin_last_error(None).decode())
-    rowptr, colidx = np.empty(net.n_species + 1, np.int64), np.empty(max(int(info[0]), 1), np.int64)
-    st = L.kin_drg_pattern_host(*head, _p64(info), _p64(rowptr), _p64(colidx))
+        raise KineticaHipError(st, lib().kin_last_error(None).decode())
+    nnz = int(info[count])
+    rowptr, colidx = np.empty(net.n_species + 1, np.int64), np.empty(max(nnz, 1), np.int64)
+    st = fn(*head, _p64(info), _p64(rowptr), _p64(colidx))
     assert st == KIN_OK
-    return rowptr, colidx[:int(info[0])], {k: int(v) for k, v in zip(DRG_INFO, info)}
+    return rowptr, colidx[:nnz], {k: int(v) for k, v in zip(names, info)}
 
 
 REACTION_IMPORTANCE_INFO = ("records", "paired_reactions", "empty_reactions")
@@ -388,16 +372,12 @@ def reaction_importance_plan_host(net, pairing=True):
     info) - per reaction the other reaction of its pair record (-1: none; always -1 without pairing) and the record's up to
     four slots (0-based species or -1, signed net coefficient: the forward reaction's, the sign flipped for the reverse member)
     - and a dict of the REACTION_IMPORTANCE_INFO sizes: records, reactions with a partner, reactions without a non-zero slot."""
-    L = lib()
-    arrs = [np.ascontiguousarray(a, dtype=np.int64) for a in (net.reac_ptr, net.reac_idx, net.reac_sto, net.prod_ptr,
-                                                              net.prod_idx, net.prod_sto)]
-    head = [int(net.n_species), int(net.n_reactions)] + [_p64(a) for a in arrs] + [0, 1 if pairing else 0]
     R = int(net.n_reactions)
     info = np.zeros(len(REACTION_IMPORTANCE_INFO), np.int64)
     partner, species, nu = np.empty(max(R, 1), np.int64), np.empty((max(R, 1), 4), np.int64), np.empty((max(R, 1), 4), np.int64)
-    st = L.kin_reaction_importance_plan_host(*head, _p64(info), _p64(partner), _p64(species), _p64(nu))
+    st = lib().kin_reaction_importance_plan_host(*_net_head(net), 1 if pairing else 0, _p64(info), _p64(partner), _p64(species), _p64(nu))
     if st != KIN_OK:
-        raise KineticaHipError(st, L.kin_last_error(None).decode())
+        raise KineticaHipError(st, lib().kin_last_error(None).decode())
     return partner[:R], species[:R], nu[:R], {k: int(v) for k, v in zip(REACTION_IMPORTANCE_INFO, info)}
 
 
@@ -414,18 +394,7 @@ def pfa_pattern_host(net, pairing=True):
     """kin_pfa_pattern_host of a FlatNetwork, computed on the host (no device): (rowptr[N + 1], colidx[pairs], info) - the CSR of
     the path-flux-analysis pattern E2 (the DRG edges and every two-hop pair; 0-based, sorted columns, no diagonal) and a dict
     of the PFA_INFO sizes: the edges of E, the pairs of E2, the products per state and the largest row of E."""
-    L = lib()
-    arrs = [np.ascontiguousarray(a, dtype=np.int64) for a in (net.reac_ptr, net.reac_idx, net.reac_sto, net.prod_ptr,
-                                                              net.prod_idx, net.prod_sto)]
-    head = [int(net.n_species), int(net.n_reactions)] + [_p64(a) for a in arrs] + [0, 1 if pairing else 0]
-    info = np.zeros(len(PFA_INFO), np.int64)
-    st = L.kin_pfa_pattern_host(*head, _p64(info), None, None)
-    if st != KIN_OK:
-        raise KineticaHipError(st, L.kin_last_error(None).decode())
-    rowptr, colidx = np.empty(net.n_species + 1, np.int64), np.empty(max(int(info[1]), 1), np.int64)
-    st = L.kin_pfa_pattern_host(*head, _p64(info), _p64(rowptr), _p64(colidx))
-    assert st == KIN_OK
-    return rowptr, colidx[:int(info[1])], {k: int(v) for k, v in zip(PFA_INFO, info)}
+    return _pattern_host("kin_pfa_pattern_host", PFA_INFO, 1, net, pairing)
 
 
 TIMESCALE_INFO = ("nnz", "rows_short", "rows_medium", "rows_long")
@@ -437,11 +406,8 @@ TIMESCALE_SHORT_MAX, TIMESCALE_WAVE_MAX, TIMESCALE_LONG_PASS = 8, 256, 1024
 def timescale_plan_host(net):
     """kin_timescale_plan_host of a FlatNetwork, computed on the host (no device): a dict of the TIMESCALE_INFO sizes - the
     stored entries of the Jacobian and its rows by class of the row pass (<= 8, 9 .. 256, > 256 stored entries)."""
-    L = lib()
-    arrs = [np.ascontiguousarray(a, dtype=np.int64) for a in (net.reac_ptr, net.reac_idx, net.reac_sto, net.prod_ptr,
-                                                              net.prod_idx, net.prod_sto)]
     info = np.zeros(len(TIMESCALE_INFO), np.int64)
-    st = L.kin_timescale_plan_host(int(net.n_species), int(net.n_reactions), *[_p64(a) for a in arrs], 0, _p64(info))
+    st = lib().kin_timescale_plan_host(*_net_head(net), _p64(info))
     if st != KIN_OK:
         raise KineticaHipError(st, "network has no timescale plan")
     return {k: int(v) for k, v in zip(TIMESCALE_INFO, info)}
@@ -480,19 +446,12 @@ def _plan_dict(names, info):
     return d
 
 
-def _net_lists(net):
-    return [np.ascontiguousarray(a, dtype=np.int64) for a in (net.reac_ptr, net.reac_idx, net.reac_sto, net.prod_ptr,
-                                                              net.prod_idx, net.prod_sto)]
-
-
 def sweep_plan_host(net, n_cu, B, u_bits=0, k_bits=0, du_bits=0):
     """kin_sweep_plan_host (no device, no handle): a dict of the SWEEP_PLAN_INFO values - the kernel instantiation and launch
     configuration kin_rhs_batched_dev takes for a FlatNetwork on a device of n_cu compute units; u_bits / k_bits / du_bits are
     the low four address bits of the buffers."""
-    arrs = _net_lists(net)
     info = np.zeros(len(SWEEP_PLAN_INFO), np.int64)
-    st = lib().kin_sweep_plan_host(int(net.n_species), int(net.n_reactions), *[_p64(a) for a in arrs], 0, int(n_cu), int(B),
-                                   int(u_bits), int(k_bits), int(du_bits), _p64(info))
+    st = lib().kin_sweep_plan_host(*_net_head(net), int(n_cu), int(B), int(u_bits), int(k_bits), int(du_bits), _p64(info))
     if st != KIN_OK:
         raise KineticaHipError(st, "sweep plan query: " + lib().kin_last_error(None).decode())
     return _plan_dict(SWEEP_PLAN_INFO, info)
@@ -501,10 +460,8 @@ def sweep_plan_host(net, n_cu, B, u_bits=0, k_bits=0, du_bits=0):
 def tiled_sweep_plan_host(net, n_cu, B, temperature_form=False):
     """kin_tiled_sweep_plan_host (no device, no handle): a dict of the TILED_PLAN_INFO values for a FlatNetwork (under the
     caller's KIN_TILED_ENTRIES / KIN_TILED_SINGLES, as a handle would build the layout)."""
-    arrs = _net_lists(net)
     info = np.zeros(len(TILED_PLAN_INFO), np.int64)
-    st = lib().kin_tiled_sweep_plan_host(int(net.n_species), int(net.n_reactions), *[_p64(a) for a in arrs], 0, int(n_cu), int(B),
-                                         int(bool(temperature_form)), _p64(info))
+    st = lib().kin_tiled_sweep_plan_host(*_net_head(net), int(n_cu), int(B), int(bool(temperature_form)), _p64(info))
     if st != KIN_OK:
         raise KineticaHipError(st, "network has no tiled layout")
     return _plan_dict(TILED_PLAN_INFO, info)
@@ -610,13 +567,13 @@ class HipNetwork:
 
     def rhs_batched_dev(self, B, d_u, d_k, d_du, stream=0):
         """Device pointers (ints), state-major u[b][N], k[b][R] or 0, du[b][N]; only enqueues."""
-        self._chk(lib().kin_rhs_batched_dev(self._h, int(B), c_void_p(d_u), c_void_p(d_k) if d_k else None,
-                                            c_void_p(d_du), c_void_p(stream) if stream else None))
+        self._chk(lib().kin_rhs_batched_dev(self._h, int(B), c_void_p(d_u), _dp(d_k),
+                                            c_void_p(d_du), _dp(stream)))
 
     def sweep_plan(self, B, d_u, d_k, d_du):
         """kin_sweep_plan: what rhs_batched_dev launches for these device pointers (ints; d_k 0: the handle's rates)."""
         info = np.zeros(len(SWEEP_PLAN_INFO), np.int64)
-        self._chk(lib().kin_sweep_plan(self._h, int(B), c_void_p(d_u), c_void_p(d_k) if d_k else None, c_void_p(d_du), _p64(info)))
+        self._chk(lib().kin_sweep_plan(self._h, int(B), c_void_p(d_u), _dp(d_k), c_void_p(d_du), _p64(info)))
         return _plan_dict(SWEEP_PLAN_INFO, info)
 
     def tiled_sweep_plan(self, B, temperature_form=False):
@@ -625,9 +582,27 @@ class HipNetwork:
         self._chk(lib().kin_tiled_sweep_plan(self._h, int(B), int(bool(temperature_form)), _p64(info)))
         return _plan_dict(TILED_PLAN_INFO, info)
 
-    # --- reaction fluxes ---------------------------------------------------------------------
-    def _flux_inputs(self, B, k, k_row, T, w):
-        """Contiguous float64 / int64 views of the optional inputs of the flux entries, shapes checked against B."""
+    # --- where the states of an analysis pass come from: (B, the C arguments that hand them over) ----------------------------
+    def _batched(self, u):
+        """Host states u[B][N]: the entry takes B, u."""
+        u = np.ascontiguousarray(np.atleast_2d(_f64(u)))
+        B = u.shape[0]
+        assert u.shape == (B, self.n)
+        return B, (B, _pd(u))
+
+    def _solution(self):
+        """The saved states of the last solve, read where they live: B = n_saved, nothing to hand over."""
+        n_saved = c_int64(0)
+        self._chk(lib().kin_solution_size(self._h, ctypes.byref(n_saved), None))
+        return n_saved.value, ()
+
+    def _stored_ensemble(self):
+        """Every row of every member of the stored ensemble: B = K n_rows, nothing to hand over."""
+        K, rows = self.ensemble_size()[:2]
+        return K * rows, ()
+
+    def _k_args(self, B, k, k_row, T):
+        """The C arguments (k, n_k_rows, k_row, T) of a pass over B states: contiguous float64 / int64, shapes checked against B."""
         n_rows = 0
         if k is not None:
             k = np.ascontiguousarray(np.atleast_2d(_f64(k)))
@@ -639,45 +614,55 @@ class HipNetwork:
         if T is not None:
             T = np.ascontiguousarray(_f64(T).ravel())
             assert len(T) == B
+        return _pd(k), n_rows, _p64(k_row), _pd(T)
+
+    def _pattern_nnz(self, entry, pairing):
+        """Entries of the handle's kin_drg_pattern / kin_pfa_pattern (no device call)."""
+        nnz = c_int64(0)
+        self._chk(getattr(lib(), entry)(self._h, int(bool(pairing)), 0, ctypes.byref(nnz), None, None))
+        return nnz.value
+
+    def _pattern(self, entry, pairing):
+        nnz = self._pattern_nnz(entry, pairing)
+        rowptr, colidx = np.empty(self.n + 1, np.int64), np.empty(max(nnz, 1), np.int64)
+        self._chk(getattr(lib(), entry)(self._h, int(bool(pairing)), 0, None, _p64(rowptr), _p64(colidx)))
+        return rowptr, colidx[:nnz]
+
+    # --- reaction fluxes ---------------------------------------------------------------------
+    @staticmethod
+    def _weights(B, w):
         if w is not None:
             w = np.ascontiguousarray(_f64(w).ravel())
             assert len(w) == B
-        return k, n_rows, k_row, T, w
+        return _pd(w)
+
+    def _flux(self, entry, states, k, k_row, T, w, want_rates, want_flux):
+        B, given = states
+        ks = self._k_args(B, k, k_row, T)
+        w = self._weights(B, w)
+        flux = np.empty(self.nr) if want_flux else None
+        rates = np.empty((B, self.nr)) if want_rates else None
+        args = given + ks + (w,) if given else (w,) + ks      # (kin_solution_flux takes w before the rate constants)
+        self._chk(getattr(lib(), entry)(self._h, *args, _pd(flux), _pd(rates)))
+        return (flux, rates) if want_rates else flux
 
     def flux_batched(self, u, k=None, k_row=None, T=None, w=None, want_rates=False, want_flux=True):
         """kin_flux_batched on host arrays: per-reaction rates of the states u[B][N], rate_r = k_r u[x0_r] u[x1_r], and their
         weighted sum flux[R] = sum_b w[b] rate_r(u_b) (w=None: weights 1). Rate constants of state b: row k_row[b] of k
         (k_row=None: row b), or the Arrhenius law at T[b], or the handle's current rates. Returns flux[R], or
         (flux, rates[B][R]) with want_rates (flux is None with want_flux=False)."""
-        u = np.ascontiguousarray(np.atleast_2d(_f64(u)))
-        B = u.shape[0]
-        assert u.shape == (B, self.n)
-        k, n_rows, k_row, T, w = self._flux_inputs(B, k, k_row, T, w)
-        flux = np.empty(self.nr) if want_flux else None
-        rates = np.empty((B, self.nr)) if want_rates else None
-        self._chk(lib().kin_flux_batched(self._h, B, _pd(u), _pd(k), n_rows, None if k_row is None else _p64(k_row), _pd(T), _pd(w),
-                                         _pd(flux), _pd(rates)))
-        return (flux, rates) if want_rates else flux
+        return self._flux("kin_flux_batched", self._batched(u), k, k_row, T, w, want_rates, want_flux)
 
     def flux_batched_dev(self, B, d_u, d_k=0, d_k_row=0, d_T=0, d_w=0, d_flux=0, d_rates=0, stream=0):
         """kin_flux_batched_dev: device pointers (ints; 0 = not given), u[B][N], k rows / k_row[B] (int64) / T[B], w[B],
         flux[R] and / or rates[B][R]. One stream per handle at a time; allocates only when the workspace has to grow."""
-        p = lambda x: c_void_p(x) if x else None
-        self._chk(lib().kin_flux_batched_dev(self._h, int(B), p(d_u), p(d_k), p(d_k_row), p(d_T), p(d_w), p(d_flux), p(d_rates),
-                                             p(stream)))
+        self._chk(lib().kin_flux_batched_dev(self._h, int(B), _dp(d_u), _dp(d_k), _dp(d_k_row), _dp(d_T), _dp(d_w), _dp(d_flux),
+                                             _dp(d_rates), _dp(stream)))
 
     def solution_flux(self, w=None, k=None, k_row=None, T_rows=None, want_rates=False, want_flux=True):
         """kin_solution_flux: flux_batched over the saved states of the last solve, read where they live on the device.
         k=None with k_row reads rows of the device-resident rate table (solve(k_table=...) / rate_table leave it there)."""
-        n_saved = c_int64(0)
-        self._chk(lib().kin_solution_size(self._h, ctypes.byref(n_saved), None))
-        B = n_saved.value
-        k, n_rows, k_row, T_rows, w = self._flux_inputs(B, k, k_row, T_rows, w)
-        flux = np.empty(self.nr) if want_flux else None
-        rates = np.empty((B, self.nr)) if want_rates else None
-        self._chk(lib().kin_solution_flux(self._h, _pd(w), _pd(k), n_rows, None if k_row is None else _p64(k_row), _pd(T_rows),
-                                          _pd(flux), _pd(rates)))
-        return (flux, rates) if want_rates else flux
+        return self._flux("kin_solution_flux", self._solution(), k, k_row, T_rows, w, want_rates, want_flux)
 
     def flux_segmented(self, u, seg_n=None, k=None, k_row=None, T=None, w=None):
         """kin_flux_segmented on host arrays: u[S][L][N] (S segments of up to L states), flux[S][R] with
@@ -690,18 +675,16 @@ class HipNetwork:
         if seg_n is not None:
             seg_n = np.ascontiguousarray(seg_n, dtype=np.int64).ravel()
             assert len(seg_n) == S
-        k, n_rows, k_row, T, w = self._flux_inputs(S * Lr, k, k_row, T, w)
+        ks = self._k_args(S * Lr, k, k_row, T)
         flux = np.empty((S, self.nr))
-        self._chk(lib().kin_flux_segmented(self._h, S, Lr, None if seg_n is None else _p64(seg_n), _pd(u), _pd(k), n_rows,
-                                           None if k_row is None else _p64(k_row), _pd(T), _pd(w), _pd(flux)))
+        self._chk(lib().kin_flux_segmented(self._h, S, Lr, _p64(seg_n), _pd(u), *ks, self._weights(S * Lr, w), _pd(flux)))
         return flux
 
     def flux_segmented_dev(self, S, L, d_u, d_flux, d_seg_n=0, d_k=0, d_k_row=0, d_T=0, d_w=0, stream=0):
         """kin_flux_segmented_dev: device pointers (ints; 0 = not given), u[S L][N], seg_n[S] (int64), k rows / k_row[S L] (int64)
         / T[S L], w[S L], flux[S][R]. Only enqueues; one stream per handle at a time."""
-        p = lambda x: c_void_p(x) if x else None
-        self._chk(lib().kin_flux_segmented_dev(self._h, int(S), int(L), p(d_seg_n), p(d_u), p(d_k), p(d_k_row), p(d_T), p(d_w),
-                                               p(d_flux), p(stream)))
+        self._chk(lib().kin_flux_segmented_dev(self._h, int(S), int(L), _dp(d_seg_n), _dp(d_u), _dp(d_k), _dp(d_k_row), _dp(d_T), _dp(d_w),
+                                               _dp(d_flux), _dp(stream)))
 
     # --- the last ensemble call's saved states, analysed where they live ------------------------
     def ensemble_size(self):
@@ -733,167 +716,109 @@ class HipNetwork:
         they live. w / k_row / T_rows: [K][n_rows] (entries past a member's saved rows are ignored); k: rows for k_row to
         index, or one row per (member, row); none of k / T_rows: the handle's current rates."""
         K, rows = self.ensemble_size()[:2]
-        k, n_rows, k_row, T_rows, w = self._flux_inputs(K * rows, k, k_row, T_rows, w)
+        ks = self._k_args(K * rows, k, k_row, T_rows)
         flux = np.empty((K, self.nr))
-        self._chk(lib().kin_ensemble_flux(self._h, _pd(w), _pd(k), n_rows, None if k_row is None else _p64(k_row), _pd(T_rows),
-                                          _pd(flux)))
+        self._chk(lib().kin_ensemble_flux(self._h, self._weights(K * rows, w), *ks, _pd(flux)))
         return flux
 
     # --- directed relation graph ---------------------------------------------------------------
     def drg_pattern(self, pairing=True):
         """kin_drg_pattern: (rowptr[N + 1], colidx[edges]) of the handle's directed relation graph, 0-based (no device call)."""
-        nnz = c_int64(0)
-        self._chk(lib().kin_drg_pattern(self._h, int(bool(pairing)), 0, ctypes.byref(nnz), None, None))
-        rowptr, colidx = np.empty(self.n + 1, np.int64), np.empty(max(nnz.value, 1), np.int64)
-        self._chk(lib().kin_drg_pattern(self._h, int(bool(pairing)), 0, None, _p64(rowptr), _p64(colidx)))
-        return rowptr, colidx[:nnz.value]
+        return self._pattern("kin_drg_pattern", pairing)
 
-    def _drg_coef(self, pairing, coef):
-        """The output buffer of a DRG entry: a fresh one, or (accumulate) a contiguous copy of `coef` that takes part in the maximum."""
-        nnz = c_int64(0)
-        self._chk(lib().kin_drg_pattern(self._h, int(bool(pairing)), 0, ctypes.byref(nnz), None, None))
-        if coef is None:
-            return np.empty(max(nnz.value, 1)), nnz.value, 0
-        out = np.empty(max(nnz.value, 1))
-        c = _f64(coef).ravel()
-        assert len(c) == nnz.value
-        out[:nnz.value] = c
-        return out, nnz.value, 1
+    def _drg(self, entry, states, k, k_row, T, pairing, coef):
+        B, given = states
+        ks = self._k_args(B, k, k_row, T)
+        nnz = self._pattern_nnz("kin_drg_pattern", pairing)
+        out, acc = _acc_buffer(nnz, coef, "coef")
+        self._chk(getattr(lib(), entry)(self._h, int(bool(pairing)), *given, *ks, acc, _pd(out)))
+        return out[:nnz]
 
     def drg_batched(self, u, k=None, k_row=None, T=None, pairing=True, coef=None):
         """kin_drg_batched on host arrays: coef[edges] (CSR order of drg_pattern) = max over the states u[B][N] of
         num_AB / den_A, the directed-relation-graph coefficients of the network's records (pairing: a reaction with its exact
         reverse; else every reaction alone). Rate constants of state b as in flux_batched. coef given: its values take part
         in the maximum (the result is returned, the argument is left alone)."""
-        u = np.ascontiguousarray(np.atleast_2d(_f64(u)))
-        B = u.shape[0]
-        assert u.shape == (B, self.n)
-        k, n_rows, k_row, T, _ = self._flux_inputs(B, k, k_row, T, None)
-        out, nnz, acc = self._drg_coef(pairing, coef)
-        self._chk(lib().kin_drg_batched(self._h, int(bool(pairing)), B, _pd(u), _pd(k), n_rows, None if k_row is None else _p64(k_row),
-                                        _pd(T), acc, _pd(out)))
-        return out[:nnz]
+        return self._drg("kin_drg_batched", self._batched(u), k, k_row, T, pairing, coef)
 
     def drg_batched_dev(self, B, d_u, d_coef, d_k=0, d_k_row=0, d_T=0, pairing=True, accumulate=False, stream=0):
         """kin_drg_batched_dev: device pointers (ints; 0 = not given), u[B][N], k rows / k_row[B] (int64) / T[B], coef[edges].
         One stream per handle at a time; allocates only when the workspace has to grow."""
-        p = lambda x: c_void_p(x) if x else None
-        self._chk(lib().kin_drg_batched_dev(self._h, int(bool(pairing)), int(B), p(d_u), p(d_k), p(d_k_row), p(d_T),
-                                            1 if accumulate else 0, p(d_coef), p(stream)))
+        self._chk(lib().kin_drg_batched_dev(self._h, int(bool(pairing)), int(B), _dp(d_u), _dp(d_k), _dp(d_k_row), _dp(d_T),
+                                            1 if accumulate else 0, _dp(d_coef), _dp(stream)))
 
     def solution_drg(self, k=None, k_row=None, T_rows=None, pairing=True, coef=None):
         """kin_solution_drg: drg_batched over the saved states of the last solve, read where they live on the device
         (rate-constant sources as solution_flux)."""
-        n_saved = c_int64(0)
-        self._chk(lib().kin_solution_size(self._h, ctypes.byref(n_saved), None))
-        k, n_rows, k_row, T_rows, _ = self._flux_inputs(n_saved.value, k, k_row, T_rows, None)
-        out, nnz, acc = self._drg_coef(pairing, coef)
-        self._chk(lib().kin_solution_drg(self._h, int(bool(pairing)), _pd(k), n_rows, None if k_row is None else _p64(k_row),
-                                         _pd(T_rows), acc, _pd(out)))
-        return out[:nnz]
+        return self._drg("kin_solution_drg", self._solution(), k, k_row, T_rows, pairing, coef)
 
     def ensemble_drg(self, k=None, k_row=None, T_rows=None, pairing=True, coef=None):
         """kin_ensemble_drg: one graph over every saved row of every member of the stored ensemble (k_row / T_rows: [K][n_rows],
         entries past a member's saved rows are ignored)."""
-        K, rows = self.ensemble_size()[:2]
-        k, n_rows, k_row, T_rows, _ = self._flux_inputs(K * rows, k, k_row, T_rows, None)
-        out, nnz, acc = self._drg_coef(pairing, coef)
-        self._chk(lib().kin_ensemble_drg(self._h, int(bool(pairing)), _pd(k), n_rows, None if k_row is None else _p64(k_row),
-                                         _pd(T_rows), acc, _pd(out)))
-        return out[:nnz]
+        return self._drg("kin_ensemble_drg", self._stored_ensemble(), k, k_row, T_rows, pairing, coef)
 
     # --- DRG with error propagation -----------------------------------------------------------
-    def _drgep_io(self, targets, importance):
-        """(targets int64, n_targets, output buffer, accumulate): a fresh buffer, or a copy of `importance` that takes part."""
+    def _drgep(self, entry, states, targets, k, k_row, T, pairing, importance, stages=None):
+        """stages: None for an entry without the stage outputs (the stored forms)."""
+        B, given = states
+        ks = self._k_args(B, k, k_row, T)
         tg = np.ascontiguousarray(np.asarray(targets, dtype=np.int64).ravel())
-        out = np.zeros(max(self.n, 1))
-        if importance is None:
-            return tg, len(tg), out, 0
-        c = _f64(importance).ravel()
-        assert len(c) == self.n
-        out[:self.n] = c
-        return tg, len(tg), out, 1
+        out, acc = _acc_buffer(self.n, importance, "importance")
+        shown = () if stages is None else (None, None, None)
+        if stages:
+            shown = (np.zeros((B, self._pattern_nnz("kin_drg_pattern", pairing))), np.zeros((B, self.n)), np.zeros(B, np.int32))
+        self._chk(getattr(lib(), entry)(self._h, int(bool(pairing)), *given, *ks, _p64(tg), len(tg), 0, acc, _pd(out),
+                                        *[(_p32 if i == 2 else _pd)(_nonempty(a)) for i, a in enumerate(shown)]))
+        return (out[:self.n], *shown) if stages else out[:self.n]
 
     def drgep_batched(self, u, targets, k=None, k_row=None, T=None, pairing=True, importance=None, stages=False):
         """kin_drgep_batched on host arrays: importance[N] = max over the states u[B][N] of R_B, the largest product of the
         direct-interaction coefficients r_AB along any path from a target (0-based ids) to B (include/kinetica_hip.h has the
         definition). Rate constants of state b as in flux_batched. importance given: its values take part in the maximum (the
         result is returned, the argument is left alone). stages=True: (importance, r[B][edges], R[B][N], rounds[B])."""
-        u = np.ascontiguousarray(np.atleast_2d(_f64(u)))
-        B = u.shape[0]
-        assert u.shape == (B, self.n)
-        k, n_rows, k_row, T, _ = self._flux_inputs(B, k, k_row, T, None)
-        tg, nt, out, acc = self._drgep_io(targets, importance)
-        r = R = rounds = None
-        if stages:
-            nnz = c_int64(0)
-            self._chk(lib().kin_drg_pattern(self._h, int(bool(pairing)), 0, ctypes.byref(nnz), None, None))
-            r, R, rounds = np.zeros((B, nnz.value)), np.zeros((B, self.n)), np.zeros(B, np.int32)
-        p32 = lambda a: None if a is None else a.ctypes.data_as(POINTER(c_int32))
-        self._chk(lib().kin_drgep_batched(self._h, int(bool(pairing)), B, _pd(u), _pd(k), n_rows, None if k_row is None else _p64(k_row),
-                                          _pd(T), _p64(tg), nt, 0, acc, _pd(out), _pd(r) if stages and r.size else None,
-                                          _pd(R) if stages and R.size else None, p32(rounds) if stages and B else None))
-        return (out[:self.n], r, R, rounds) if stages else out[:self.n]
+        return self._drgep("kin_drgep_batched", self._batched(u), targets, k, k_row, T, pairing, importance, bool(stages))
 
     def drgep_batched_dev(self, B, d_u, d_targets, n_targets, d_importance, d_k=0, d_k_row=0, d_T=0, pairing=True, accumulate=False,
                           stream=0):
         """kin_drgep_batched_dev: device pointers (ints; 0 = not given), u[B][N], k rows / k_row[B] (int64) / T[B],
         targets[n_targets] (int64, 0-based), importance[N]. One stream per handle at a time."""
-        p = lambda x: c_void_p(x) if x else None
-        self._chk(lib().kin_drgep_batched_dev(self._h, int(bool(pairing)), int(B), p(d_u), p(d_k), p(d_k_row), p(d_T), p(d_targets),
-                                              int(n_targets), 1 if accumulate else 0, p(d_importance), p(stream)))
+        self._chk(lib().kin_drgep_batched_dev(self._h, int(bool(pairing)), int(B), _dp(d_u), _dp(d_k), _dp(d_k_row), _dp(d_T),
+                                              _dp(d_targets), int(n_targets), 1 if accumulate else 0, _dp(d_importance), _dp(stream)))
 
     def drgep_paths(self, r, targets, pairing=True, importance=None, stages=False):
         """kin_drgep_paths: the path search alone on the caller's coefficients r[B][edges] in [0, 1] (CSR order of drg_pattern).
         stages=True: (importance, R[B][N], rounds[B])."""
-        nnz = c_int64(0)
-        self._chk(lib().kin_drg_pattern(self._h, int(bool(pairing)), 0, ctypes.byref(nnz), None, None))
-        r = np.ascontiguousarray(_f64(r)).reshape(-1, nnz.value) if nnz.value else np.zeros((len(r), 0))
+        E = self._pattern_nnz("kin_drg_pattern", pairing)
+        r = np.ascontiguousarray(_f64(r)).reshape(-1, E) if E else np.zeros((len(r), 0))
         B = r.shape[0]
-        tg, nt, out, acc = self._drgep_io(targets, importance)
+        tg = np.ascontiguousarray(np.asarray(targets, dtype=np.int64).ravel())
+        out, acc = _acc_buffer(self.n, importance, "importance")
         R, rounds = np.zeros((B, self.n)), np.zeros(B, np.int32)
-        self._chk(lib().kin_drgep_paths(self._h, int(bool(pairing)), B, _pd(r) if r.size else None, _p64(tg), nt, 0, acc, _pd(out),
-                                        _pd(R) if stages and R.size else None,
-                                        rounds.ctypes.data_as(POINTER(c_int32)) if stages and B else None))
+        self._chk(lib().kin_drgep_paths(self._h, int(bool(pairing)), B, _pd(_nonempty(r)), _p64(tg), len(tg), 0, acc, _pd(out),
+                                        _pd(_nonempty(R)) if stages else None, _p32(_nonempty(rounds)) if stages else None))
         return (out[:self.n], R, rounds) if stages else out[:self.n]
 
     def solution_drgep(self, targets, k=None, k_row=None, T_rows=None, pairing=True, importance=None):
         """kin_solution_drgep: drgep_batched over the saved states of the last solve, read where they live on the device
         (rate-constant sources as solution_flux)."""
-        n_saved = c_int64(0)
-        self._chk(lib().kin_solution_size(self._h, ctypes.byref(n_saved), None))
-        k, n_rows, k_row, T_rows, _ = self._flux_inputs(n_saved.value, k, k_row, T_rows, None)
-        tg, nt, out, acc = self._drgep_io(targets, importance)
-        self._chk(lib().kin_solution_drgep(self._h, int(bool(pairing)), _pd(k), n_rows, None if k_row is None else _p64(k_row),
-                                           _pd(T_rows), _p64(tg), nt, 0, acc, _pd(out)))
-        return out[:self.n]
+        return self._drgep("kin_solution_drgep", self._solution(), targets, k, k_row, T_rows, pairing, importance)
 
     def ensemble_drgep(self, targets, k=None, k_row=None, T_rows=None, pairing=True, importance=None):
         """kin_ensemble_drgep: one importance vector over every saved row of every member of the stored ensemble (k_row / T_rows:
         [K][n_rows], entries past a member's saved rows are ignored)."""
-        K, rows = self.ensemble_size()[:2]
-        k, n_rows, k_row, T_rows, _ = self._flux_inputs(K * rows, k, k_row, T_rows, None)
-        tg, nt, out, acc = self._drgep_io(targets, importance)
-        self._chk(lib().kin_ensemble_drgep(self._h, int(bool(pairing)), _pd(k), n_rows, None if k_row is None else _p64(k_row),
-                                           _pd(T_rows), _p64(tg), nt, 0, acc, _pd(out)))
-        return out[:self.n]
+        return self._drgep("kin_ensemble_drgep", self._stored_ensemble(), targets, k, k_row, T_rows, pairing, importance)
 
     # --- reaction elimination -------------------------------------------------------------------------
-    def _ri_io(self, species, importance):
-        """(species int64 or None, n_sel, output buffer, accumulate): a fresh buffer, or a copy of `importance` that takes part."""
-        sp, ns = None, 0
-        if species is not None:
-            sp = np.ascontiguousarray(np.asarray(species, dtype=np.int64).ravel())
-            ns = len(sp)
-            if ns == 0:
-                sp = np.zeros(1, np.int64)      # (an empty list stays a list - and an error - not "every species")
-        out = np.zeros(max(self.nr, 1))
-        if importance is None:
-            return sp, ns, out, 0
-        c = _f64(importance).ravel()
-        assert len(c) == self.nr
-        out[:self.nr] = c
-        return sp, ns, out, 1
+    def _reaction_importance(self, entry, states, species, k, k_row, T, pairing, importance, per_state=None):
+        """per_state: None for an entry without the per-state output (the stored forms)."""
+        B, given = states
+        ks = self._k_args(B, k, k_row, T)
+        sp, ns, _ = self._ms_species(species)
+        out, acc = _acc_buffer(self.nr, importance, "importance")
+        shown = () if per_state is None else (np.zeros((B, self.nr)) if per_state else None,)
+        self._chk(getattr(lib(), entry)(self._h, int(bool(pairing)), *given, *ks, _p64(sp), ns, 0, acc, _pd(out),
+                                        *[_pd(_nonempty(a)) for a in shown]))
+        return (out[:self.nr], *shown) if per_state else out[:self.nr]
 
     def reaction_importance_batched(self, u, species=None, pairing=True, importance=None, per_state=False, k=None, k_row=None, T=None):
         """kin_reaction_importance_batched on host arrays: importance[R] = max over the states u[B][N] of the largest share
@@ -901,132 +826,88 @@ class HipNetwork:
         the definition) - A among `species` (0-based ids; None: every species), den_A always over the whole network. Rate
         constants of state b as in flux_batched. importance given: its values take part in the maximum (the result is
         returned, the argument is left alone). per_state=True: (importance, I[B][R])."""
-        u = np.ascontiguousarray(np.atleast_2d(_f64(u)))
-        B = u.shape[0]
-        assert u.shape == (B, self.n)
-        k, n_rows, k_row, T, _ = self._flux_inputs(B, k, k_row, T, None)
-        sp, ns, out, acc = self._ri_io(species, importance)
-        ps = np.zeros((B, self.nr)) if per_state else None
-        self._chk(lib().kin_reaction_importance_batched(self._h, int(bool(pairing)), B, _pd(u), _pd(k), n_rows,
-                                                        None if k_row is None else _p64(k_row), _pd(T), None if sp is None else _p64(sp),
-                                                        ns, 0, acc, _pd(out), _pd(ps) if per_state and ps.size else None))
-        return (out[:self.nr], ps) if per_state else out[:self.nr]
+        return self._reaction_importance("kin_reaction_importance_batched", self._batched(u), species, k, k_row, T, pairing, importance,
+                                         bool(per_state))
 
     def reaction_importance_batched_dev(self, B, d_u, d_importance, d_species=0, n_sel=0, d_k=0, d_k_row=0, d_T=0, pairing=True,
                                         accumulate=False, stream=0):
         """kin_reaction_importance_batched_dev: device pointers (ints; 0 = not given), u[B][N], k rows / k_row[B] (int64) / T[B],
         species[n_sel] (int64, 0-based; 0: every species), importance[R]. One stream per handle at a time."""
-        p = lambda x: c_void_p(x) if x else None
-        self._chk(lib().kin_reaction_importance_batched_dev(self._h, int(bool(pairing)), int(B), p(d_u), p(d_k), p(d_k_row), p(d_T),
-                                                            p(d_species), int(n_sel), 1 if accumulate else 0, p(d_importance), p(stream)))
+        self._chk(lib().kin_reaction_importance_batched_dev(self._h, int(bool(pairing)), int(B), _dp(d_u), _dp(d_k), _dp(d_k_row), _dp(d_T),
+                                                            _dp(d_species), int(n_sel), 1 if accumulate else 0, _dp(d_importance),
+                                                            _dp(stream)))
 
     def solution_reaction_importance(self, species=None, k=None, k_row=None, T_rows=None, pairing=True, importance=None):
         """kin_solution_reaction_importance: reaction_importance_batched over the saved states of the last solve, read where
         they live on the device (rate-constant sources as solution_flux)."""
-        n_saved = c_int64(0)
-        self._chk(lib().kin_solution_size(self._h, ctypes.byref(n_saved), None))
-        k, n_rows, k_row, T_rows, _ = self._flux_inputs(n_saved.value, k, k_row, T_rows, None)
-        sp, ns, out, acc = self._ri_io(species, importance)
-        self._chk(lib().kin_solution_reaction_importance(self._h, int(bool(pairing)), _pd(k), n_rows, None if k_row is None else _p64(k_row),
-                                                         _pd(T_rows), None if sp is None else _p64(sp), ns, 0, acc, _pd(out)))
-        return out[:self.nr]
+        return self._reaction_importance("kin_solution_reaction_importance", self._solution(), species, k, k_row, T_rows, pairing,
+                                         importance)
 
     def ensemble_reaction_importance(self, species=None, k=None, k_row=None, T_rows=None, pairing=True, importance=None):
         """kin_ensemble_reaction_importance: one importance vector over every saved row of every member of the stored ensemble
         (k_row / T_rows: [K][n_rows], entries past a member's saved rows are ignored)."""
-        K, rows = self.ensemble_size()[:2]
-        k, n_rows, k_row, T_rows, _ = self._flux_inputs(K * rows, k, k_row, T_rows, None)
-        sp, ns, out, acc = self._ri_io(species, importance)
-        self._chk(lib().kin_ensemble_reaction_importance(self._h, int(bool(pairing)), _pd(k), n_rows, None if k_row is None else _p64(k_row),
-                                                         _pd(T_rows), None if sp is None else _p64(sp), ns, 0, acc, _pd(out)))
-        return out[:self.nr]
+        return self._reaction_importance("kin_ensemble_reaction_importance", self._stored_ensemble(), species, k, k_row, T_rows, pairing,
+                                         importance)
 
     # --- path flux analysis ------------------------------------------------------------------------
     def pfa_pattern(self, pairing=True):
         """kin_pfa_pattern: (rowptr[N + 1], colidx[pairs]) of the handle's path-flux-analysis pattern E2, 0-based (no device call)."""
-        nnz = c_int64(0)
-        self._chk(lib().kin_pfa_pattern(self._h, int(bool(pairing)), 0, ctypes.byref(nnz), None, None))
-        rowptr, colidx = np.empty(self.n + 1, np.int64), np.empty(max(nnz.value, 1), np.int64)
-        self._chk(lib().kin_pfa_pattern(self._h, int(bool(pairing)), 0, None, _p64(rowptr), _p64(colidx)))
-        return rowptr, colidx[:nnz.value]
+        return self._pattern("kin_pfa_pattern", pairing)
 
-    def _pfa_coef(self, pairing, coef):
-        """The output buffer of a PFA entry: a fresh one, or (accumulate) a contiguous copy of `coef` that takes part in the maximum."""
-        nnz = c_int64(0)
-        self._chk(lib().kin_pfa_pattern(self._h, int(bool(pairing)), 0, ctypes.byref(nnz), None, None))
-        out = np.zeros(max(nnz.value, 1))
-        if coef is None:
-            return out, nnz.value, 0
-        c = _f64(coef).ravel()
-        if len(c) != nnz.value:
-            raise KineticaHipError(KIN_ERR_INVALID_ARG, f"coef has {len(c)} entries, the PFA pattern {nnz.value} pairs")
-        out[:nnz.value] = c
-        return out, nnz.value, 1
+    def _pfa_buffer(self, pairing, coef):
+        """(pairs, buffer, accumulate) of a PFA entry; a coef of another length is this pass's KIN_ERR_INVALID_ARG."""
+        nnz = self._pattern_nnz("kin_pfa_pattern", pairing)
+        if coef is not None and np.size(coef) != nnz:
+            raise KineticaHipError(KIN_ERR_INVALID_ARG, f"coef has {np.size(coef)} entries, the PFA pattern {nnz} pairs")
+        return (nnz,) + _acc_buffer(nnz, coef, "coef")
 
-    def _drg_nnz(self, pairing):
-        nnz = c_int64(0)
-        self._chk(lib().kin_drg_pattern(self._h, int(bool(pairing)), 0, ctypes.byref(nnz), None, None))
-        return nnz.value
+    def _pfa(self, entry, states, k, k_row, T, pairing, coef, stages=None):
+        """stages: None for an entry without the stage outputs (the stored forms)."""
+        B, given = states
+        ks = self._k_args(B, k, k_row, T)
+        nnz, out, acc = self._pfa_buffer(pairing, coef)
+        shown = () if stages is None else (None, None, None)
+        if stages:
+            E = self._pattern_nnz("kin_drg_pattern", pairing)
+            shown = (np.zeros((B, E)), np.zeros((B, E)), np.zeros((B, nnz)))
+        self._chk(getattr(lib(), entry)(self._h, int(bool(pairing)), *given, *ks, acc, _pd(out), *[_pd(_nonempty(a)) for a in shown]))
+        return (out[:nnz], *shown) if stages else out[:nnz]
 
     def pfa_batched(self, u, k=None, k_row=None, T=None, pairing=True, coef=None, stages=False):
         """kin_pfa_batched on host arrays: coef[pairs] (CSR order of pfa_pattern) = max over the states u[B][N] of
         r_AB = rp_AB + rc_AB + sum_M (rp_AM rp_MB + rc_AM rc_MB), the path-flux-analysis coefficients (include/kinetica_hip.h has
         the definition). Rate constants of state b as in flux_batched. coef given: its values take part in the maximum (the
         result is returned, the argument is left alone). stages=True: (coef, rp[B][edges], rc[B][edges], r[B][pairs])."""
-        u = np.ascontiguousarray(np.atleast_2d(_f64(u)))
-        B = u.shape[0]
-        assert u.shape == (B, self.n)
-        k, n_rows, k_row, T, _ = self._flux_inputs(B, k, k_row, T, None)
-        out, nnz, acc = self._pfa_coef(pairing, coef)
-        rp = rc = r = None
-        if stages:
-            E = self._drg_nnz(pairing)
-            rp, rc, r = np.zeros((B, E)), np.zeros((B, E)), np.zeros((B, nnz))
-        opt = lambda a: _pd(a) if stages and a.size else None
-        self._chk(lib().kin_pfa_batched(self._h, int(bool(pairing)), B, _pd(u), _pd(k), n_rows, None if k_row is None else _p64(k_row),
-                                        _pd(T), acc, _pd(out), opt(rp), opt(rc), opt(r)))
-        return (out[:nnz], rp, rc, r) if stages else out[:nnz]
+        return self._pfa("kin_pfa_batched", self._batched(u), k, k_row, T, pairing, coef, bool(stages))
 
     def pfa_batched_dev(self, B, d_u, d_coef, d_k=0, d_k_row=0, d_T=0, pairing=True, accumulate=False, stream=0):
         """kin_pfa_batched_dev: device pointers (ints; 0 = not given), u[B][N], k rows / k_row[B] (int64) / T[B], coef[pairs].
         One stream per handle at a time; allocates only when the workspace has to grow."""
-        p = lambda x: c_void_p(x) if x else None
-        self._chk(lib().kin_pfa_batched_dev(self._h, int(bool(pairing)), int(B), p(d_u), p(d_k), p(d_k_row), p(d_T),
-                                            1 if accumulate else 0, p(d_coef), p(stream)))
+        self._chk(lib().kin_pfa_batched_dev(self._h, int(bool(pairing)), int(B), _dp(d_u), _dp(d_k), _dp(d_k_row), _dp(d_T),
+                                            1 if accumulate else 0, _dp(d_coef), _dp(stream)))
 
     def pfa_paths(self, rp, rc, pairing=True, coef=None, stages=False):
         """kin_pfa_paths: the second-generation stage alone on the caller's coefficients rp[B][edges], rc[B][edges] >= 0 (CSR
         order of drg_pattern). stages=True: (coef, r[B][pairs])."""
-        E = self._drg_nnz(pairing)
+        E = self._pattern_nnz("kin_drg_pattern", pairing)
         rp, rc = (np.ascontiguousarray(_f64(x)).reshape(-1, E) if E else np.zeros((len(x), 0)) for x in (rp, rc))
         B = rp.shape[0]
         assert rc.shape == rp.shape
-        out, nnz, acc = self._pfa_coef(pairing, coef)
+        nnz, out, acc = self._pfa_buffer(pairing, coef)
         r = np.zeros((B, nnz))
-        self._chk(lib().kin_pfa_paths(self._h, int(bool(pairing)), B, _pd(rp) if rp.size else None, _pd(rc) if rc.size else None, acc,
-                                      _pd(out), _pd(r) if stages and r.size else None))
+        self._chk(lib().kin_pfa_paths(self._h, int(bool(pairing)), B, _pd(_nonempty(rp)), _pd(_nonempty(rc)), acc, _pd(out),
+                                      _pd(_nonempty(r)) if stages else None))
         return (out[:nnz], r) if stages else out[:nnz]
 
     def solution_pfa(self, k=None, k_row=None, T_rows=None, pairing=True, coef=None):
         """kin_solution_pfa: pfa_batched over the saved states of the last solve, read where they live on the device
         (rate-constant sources as solution_flux)."""
-        n_saved = c_int64(0)
-        self._chk(lib().kin_solution_size(self._h, ctypes.byref(n_saved), None))
-        k, n_rows, k_row, T_rows, _ = self._flux_inputs(n_saved.value, k, k_row, T_rows, None)
-        out, nnz, acc = self._pfa_coef(pairing, coef)
-        self._chk(lib().kin_solution_pfa(self._h, int(bool(pairing)), _pd(k), n_rows, None if k_row is None else _p64(k_row),
-                                         _pd(T_rows), acc, _pd(out)))
-        return out[:nnz]
+        return self._pfa("kin_solution_pfa", self._solution(), k, k_row, T_rows, pairing, coef)
 
     def ensemble_pfa(self, k=None, k_row=None, T_rows=None, pairing=True, coef=None):
         """kin_ensemble_pfa: one set of coefficients over every saved row of every member of the stored ensemble (k_row / T_rows:
         [K][n_rows], entries past a member's saved rows are ignored)."""
-        K, rows = self.ensemble_size()[:2]
-        k, n_rows, k_row, T_rows, _ = self._flux_inputs(K * rows, k, k_row, T_rows, None)
-        out, nnz, acc = self._pfa_coef(pairing, coef)
-        self._chk(lib().kin_ensemble_pfa(self._h, int(bool(pairing)), _pd(k), n_rows, None if k_row is None else _p64(k_row),
-                                         _pd(T_rows), acc, _pd(out)))
-        return out[:nnz]
+        return self._pfa("kin_ensemble_pfa", self._stored_ensemble(), k, k_row, T_rows, pairing, coef)
 
     # --- timescale analysis ---------------------------------------------------------------------
     def _jac_nnz(self):
@@ -1034,32 +915,25 @@ class HipNetwork:
         self._chk(lib().kin_jac_nnz(self._h, ctypes.byref(nnz)))
         return nnz.value
 
-    def _ts_summary(self, summary):
-        """The summary buffer of a timescale entry: a fresh one, or (accumulate) a contiguous copy of `summary` that takes part."""
-        out = np.empty((3, self.n))
-        if summary is None:
-            return out, 0
-        c = _f64(summary)
-        assert c.shape == (3, self.n)
-        out[:] = c
-        return out, 1
+    def _summary(self, summary):
+        """(summary[3][N], accumulate) of a timescale entry: a fresh buffer, or a copy of `summary` that takes part."""
+        assert summary is None or _f64(summary).shape == (3, self.n)
+        out, acc = _acc_buffer(3 * self.n, summary, "summary")
+        return out[:3 * self.n].reshape(3, self.n), acc
 
     def jac_batched(self, u, k=None, k_row=None, T=None):
         """kin_jac_batched on host arrays: vals[B][nnz], the Jacobian values of the states u[B][N] in the CSR order of
         jac_pattern. Rate constants of state b as in flux_batched."""
-        u = np.ascontiguousarray(np.atleast_2d(_f64(u)))
-        B = u.shape[0]
-        assert u.shape == (B, self.n)
-        k, n_rows, k_row, T, _ = self._flux_inputs(B, k, k_row, T, None)
+        B, given = self._batched(u)
+        ks = self._k_args(B, k, k_row, T)
         vals = np.empty((B, self._jac_nnz()))
-        self._chk(lib().kin_jac_batched(self._h, B, _pd(u), _pd(k), n_rows, None if k_row is None else _p64(k_row), _pd(T), _pd(vals)))
+        self._chk(lib().kin_jac_batched(self._h, *given, *ks, _pd(vals)))
         return vals
 
     def jac_batched_dev(self, B, d_u, d_vals, d_k=0, d_k_row=0, d_T=0, stream=0):
         """kin_jac_batched_dev: device pointers (ints; 0 = not given), u[B][N], k rows / k_row[B] (int64) / T[B], vals[B][nnz].
         One stream per handle at a time; allocates only when the workspace has to grow."""
-        p = lambda x: c_void_p(x) if x else None
-        self._chk(lib().kin_jac_batched_dev(self._h, int(B), p(d_u), p(d_k), p(d_k_row), p(d_T), p(d_vals), p(stream)))
+        self._chk(lib().kin_jac_batched_dev(self._h, int(B), _dp(d_u), _dp(d_k), _dp(d_k_row), _dp(d_T), _dp(d_vals), _dp(stream)))
 
     def timescale_batched(self, u, k=None, k_row=None, T=None, summary=None, want_summary=True, want_diag=False, want_err=False,
                           want_norm=True):
@@ -1067,49 +941,40 @@ class HipNetwork:
         decay_max = max_b -J_ii, decay_min = min_b -J_ii, qss_err = max_b |f_i| / |J_ii|), diag[B][N] = J_ii, err[B][N] =
         |f_i| / |J_ii|, norm[B] = the infinity norm of J(u_b). Rate constants of state b as in flux_batched. summary given: its
         values take part in the extrema (the result is returned, the argument is left alone)."""
-        u = np.ascontiguousarray(np.atleast_2d(_f64(u)))
-        B = u.shape[0]
-        assert u.shape == (B, self.n)
-        k, n_rows, k_row, T, _ = self._flux_inputs(B, k, k_row, T, None)
-        out, acc = self._ts_summary(summary) if want_summary else (None, 0)
+        B, given = self._batched(u)
+        ks = self._k_args(B, k, k_row, T)
+        out, acc = self._summary(summary) if want_summary else (None, 0)
         diag = np.empty((B, self.n)) if want_diag else None
         err = np.empty((B, self.n)) if want_err else None
         norm = np.empty(B) if want_norm else None
-        self._chk(lib().kin_timescale_batched(self._h, B, _pd(u), _pd(k), n_rows, None if k_row is None else _p64(k_row), _pd(T), acc,
-                                              _pd(out), _pd(diag), _pd(err), _pd(norm)))
+        self._chk(lib().kin_timescale_batched(self._h, *given, *ks, acc, _pd(out), _pd(diag), _pd(err), _pd(norm)))
         return {q: v for q, v in (("summary", out), ("diag", diag), ("err", err), ("norm", norm)) if v is not None}
 
     def timescale_batched_dev(self, B, d_u, d_summary=0, d_diag=0, d_err=0, d_norm=0, d_k=0, d_k_row=0, d_T=0, accumulate=False, stream=0):
         """kin_timescale_batched_dev: device pointers (ints; 0 = not given), u[B][N], k rows / k_row[B] (int64) / T[B],
         summary[3][N], diag[B][N], err[B][N], norm[B]. One stream per handle at a time."""
-        p = lambda x: c_void_p(x) if x else None
-        self._chk(lib().kin_timescale_batched_dev(self._h, int(B), p(d_u), p(d_k), p(d_k_row), p(d_T), 1 if accumulate else 0,
-                                                  p(d_summary), p(d_diag), p(d_err), p(d_norm), p(stream)))
+        self._chk(lib().kin_timescale_batched_dev(self._h, int(B), _dp(d_u), _dp(d_k), _dp(d_k_row), _dp(d_T), 1 if accumulate else 0,
+                                                  _dp(d_summary), _dp(d_diag), _dp(d_err), _dp(d_norm), _dp(stream)))
+
+    def _timescale(self, entry, shape, k, k_row, T, row_begin, summary, want_norm):
+        """A stored form of the pass; `shape`: of its states, and of their norms."""
+        ks = self._k_args(int(np.prod(shape)), k, k_row, T)
+        out, acc = self._summary(summary)
+        norm = np.empty(shape) if want_norm else None
+        self._chk(getattr(lib(), entry)(self._h, *ks, int(row_begin), acc, _pd(out), _pd(norm)))
+        return out, norm
 
     def solution_timescale(self, k=None, k_row=None, T_rows=None, row_begin=0, summary=None, want_norm=True):
         """kin_solution_timescale: timescale_batched over the saved states of the last solve from row_begin on, read where they
         live on the device (rate-constant sources as solution_flux). Returns (summary[3][N], norm[n_saved] or None); the norm
         of a row below row_begin is 0.0."""
-        n_saved = c_int64(0)
-        self._chk(lib().kin_solution_size(self._h, ctypes.byref(n_saved), None))
-        k, n_rows, k_row, T_rows, _ = self._flux_inputs(n_saved.value, k, k_row, T_rows, None)
-        out, acc = self._ts_summary(summary)
-        norm = np.empty(n_saved.value) if want_norm else None
-        self._chk(lib().kin_solution_timescale(self._h, _pd(k), n_rows, None if k_row is None else _p64(k_row), _pd(T_rows),
-                                               int(row_begin), acc, _pd(out), _pd(norm)))
-        return out, norm
+        return self._timescale("kin_solution_timescale", self._solution()[:1], k, k_row, T_rows, row_begin, summary, want_norm)
 
     def ensemble_timescale(self, k=None, k_row=None, T_rows=None, row_begin=0, summary=None, want_norm=True):
         """kin_ensemble_timescale: one summary over the saved rows row_begin .. n_saved[m] - 1 of every member of the stored
         ensemble (k_row / T_rows: [K][n_rows], entries of rows that take no part are ignored). Returns (summary[3][N],
         norm[K][n_rows] or None); the norm of a row that takes no part is 0.0."""
-        K, rows = self.ensemble_size()[:2]
-        k, n_rows, k_row, T_rows, _ = self._flux_inputs(K * rows, k, k_row, T_rows, None)
-        out, acc = self._ts_summary(summary)
-        norm = np.empty((K, rows)) if want_norm else None
-        self._chk(lib().kin_ensemble_timescale(self._h, _pd(k), n_rows, None if k_row is None else _p64(k_row), _pd(T_rows),
-                                               int(row_begin), acc, _pd(out), _pd(norm)))
-        return out, norm
+        return self._timescale("kin_ensemble_timescale", self.ensemble_size()[:2], k, k_row, T_rows, row_begin, summary, want_norm)
 
     # --- cross-member statistics ------------------------------------------------------------------
     def _ms_species(self, species):
@@ -1118,7 +983,7 @@ class HipNetwork:
             return None, 0, self.n
         sp = np.ascontiguousarray(np.asarray(species, dtype=np.int64).ravel())
         ns = len(sp)
-        return (sp if ns else np.zeros(1, np.int64)), ns, ns      # (an empty list stays a list, not "all species")
+        return (sp if ns else np.zeros(1, np.int64)), ns, ns      # (an empty list stays a list - and an error - not "all species")
 
     @staticmethod
     def _ms_block(u, n_species):
@@ -1127,76 +992,73 @@ class HipNetwork:
             raise ValueError(f"u must be [K][L][{n_species}] (member, row, species); got {u.shape}")
         return u, u.shape[0], u.shape[1]
 
-    @staticmethod
-    def _ms_moment_buffers(L, N, want):
+    def _members(self, u):
+        """(K, L, the C arguments that hand the block over): K, L, u of host states u[K][L][N]; nothing of the stored ensemble
+        (u None), read where it lives. (The public methods pass _f64(u): a caller's None is a wrong block, as it always was.)"""
+        if u is None:
+            K, L = self.ensemble_size()[:2]
+            return K, L, ()
+        u, K, L = self._ms_block(u, self.n)
+        return K, L, (K, L, _pd(u))
+
+    def _moments(self, entry, u, use, want):
+        K, L, given = self._members(u)
+        use = _use32(use, K)
         names = ("mean", "var", "min", "max")
         bad = [w for w in want if w not in names + ("count",)]
         if bad:
             raise ValueError(f"unknown moments {bad}; choose among {names + ('count',)}")
-        return {w: np.empty((L, N)) for w in names if w in want}
-
-    def members_moments(self, u, use=None, want=("count", "mean", "var", "min", "max")):
-        """kin_members_moments over a block u[K][L][N] on the host: dict of count (int) and mean / var / min / max [L][N] over the
-        members use[m] != 0 (None: all), those `want` names (include/kinetica_hip.h has the definitions)."""
-        u, K, L = self._ms_block(u, self.n)
-        use = _use32(use, K)
-        out = self._ms_moment_buffers(L, self.n, want)
+        out = {w: np.empty((L, self.n)) for w in names if w in want}
         cnt = c_int64(0)
-        self._chk(lib().kin_members_moments(self._h, K, L, _pd(u), _p32(use), ctypes.byref(cnt), *[_pd(out.get(w)) for w in ("mean", "var", "min", "max")]))
+        self._chk(getattr(lib(), entry)(self._h, *given, _p32(use), ctypes.byref(cnt), *[_pd(out.get(w)) for w in names]))
         if "count" in want:
             out["count"] = cnt.value
         return out
 
+    def members_moments(self, u, use=None, want=("count", "mean", "var", "min", "max")):
+        """kin_members_moments over a block u[K][L][N] on the host: dict of count (int) and mean / var / min / max [L][N] over the
+        members use[m] != 0 (None: all), those `want` names (include/kinetica_hip.h has the definitions)."""
+        return self._moments("kin_members_moments", _f64(u), use, want)
+
     def members_moments_dev(self, K, L, d_u, use=None, d_mean=0, d_var=0, d_min=0, d_max=0, stream=0):
         """kin_members_moments_dev: device pointers (ints; 0 = not wanted) u[K][L][N] and mean / var / min / max [L][N]; `use` is a
         host mask. Only enqueues; returns the number of participants."""
-        p = lambda x: c_void_p(x) if x else None
         use = _use32(use, K)
         cnt = c_int64(0)
-        self._chk(lib().kin_members_moments_dev(self._h, int(K), int(L), p(d_u), _p32(use), ctypes.byref(cnt), p(d_mean), p(d_var), p(d_min),
-                                                p(d_max), p(stream)))
+        self._chk(lib().kin_members_moments_dev(self._h, int(K), int(L), _dp(d_u), _p32(use), ctypes.byref(cnt), _dp(d_mean), _dp(d_var),
+                                                _dp(d_min), _dp(d_max), _dp(stream)))
         return cnt.value
 
     def ensemble_moments(self, use=None, want=("count", "mean", "var", "min", "max")):
         """kin_ensemble_moments: members_moments over the stored ensemble, read where it lives (use None: the members that
         completed the save grid)."""
-        K, L = self.ensemble_size()[:2]
+        return self._moments("kin_ensemble_moments", None, use, want)
+
+    def _quantiles(self, entry, u, p, species, use):
+        K, L, given = self._members(u)
         use = _use32(use, K)
-        out = self._ms_moment_buffers(L, self.n, want)
-        cnt = c_int64(0)
-        self._chk(lib().kin_ensemble_moments(self._h, _p32(use), ctypes.byref(cnt), *[_pd(out.get(w)) for w in ("mean", "var", "min", "max")]))
-        if "count" in want:
-            out["count"] = cnt.value
+        p = np.ascontiguousarray(np.atleast_1d(_f64(p)))
+        sp, ns, nsel = self._ms_species(species)
+        out = np.empty((len(p), L, nsel))
+        self._chk(getattr(lib(), entry)(self._h, *given, _p32(use), _p64(sp), ns, _pd(p), len(p), _pd(out)))
         return out
 
     def members_quantiles(self, u, p, species=None, use=None):
         """kin_members_quantiles: out[Q][L][n_sel], the quantiles p[Q] (in [0, 1]) over the participants of the selected species
         (ids in the handle's index base; None: all N) at every row."""
-        u, K, L = self._ms_block(u, self.n)
-        use = _use32(use, K)
-        p = np.ascontiguousarray(np.atleast_1d(_f64(p)))
-        sp, ns, nsel = self._ms_species(species)
-        out = np.empty((len(p), L, nsel))
-        self._chk(lib().kin_members_quantiles(self._h, K, L, _pd(u), _p32(use), None if sp is None else _p64(sp), ns, _pd(p), len(p), _pd(out)))
-        return out
+        return self._quantiles("kin_members_quantiles", _f64(u), p, species, use)
 
     def members_quantiles_dev(self, K, L, d_u, p, d_out, species=None, use=None, stream=0):
         """kin_members_quantiles_dev: device pointers u[K][L][N] and out[Q][L][n_sel]; p, species and use are host arrays."""
         use = _use32(use, K)
         p = np.ascontiguousarray(np.atleast_1d(_f64(p)))
         sp, ns, _ = self._ms_species(species)
-        self._chk(lib().kin_members_quantiles_dev(self._h, int(K), int(L), c_void_p(d_u), _p32(use), None if sp is None else _p64(sp), ns,
-                                                  _pd(p), len(p), c_void_p(d_out), c_void_p(stream) if stream else None))
+        self._chk(lib().kin_members_quantiles_dev(self._h, int(K), int(L), _dp(d_u), _p32(use), _p64(sp), ns, _pd(p), len(p), _dp(d_out),
+                                                  _dp(stream)))
 
     def ensemble_quantiles(self, p, species=None, use=None):
         """kin_ensemble_quantiles: members_quantiles over the stored ensemble, out[Q][n_rows][n_sel]."""
-        K, L = self.ensemble_size()[:2]
-        use = _use32(use, K)
-        p = np.ascontiguousarray(np.atleast_1d(_f64(p)))
-        sp, ns, nsel = self._ms_species(species)
-        out = np.empty((len(p), L, nsel))
-        self._chk(lib().kin_ensemble_quantiles(self._h, _p32(use), None if sp is None else _p64(sp), ns, _pd(p), len(p), _pd(out)))
-        return out
+        return self._quantiles("kin_ensemble_quantiles", None, p, species, use)
 
     @staticmethod
     def _ms_inputs(X, K):
@@ -1205,35 +1067,31 @@ class HipNetwork:
             raise ValueError(f"inputs must be [K = {K}][P] (one row per member); got {X.shape}")
         return X, X.shape[1]
 
-    def members_correlate(self, u, X, species=None, rank=True, use=None):
-        """kin_members_correlate: out[L][n_sel][P], the correlation of input X[:, p] (X[K][P], one row per member) with the selected
-        species at every row over the participants: Spearman's coefficient (rank=True) or Pearson's."""
-        u, K, L = self._ms_block(u, self.n)
+    def _correlate(self, entry, u, X, species, rank, use):
+        K, L, given = self._members(u)
         use = _use32(use, K)
         X, P = self._ms_inputs(X, K)
         sp, ns, nsel = self._ms_species(species)
         out = np.empty((L, nsel, P))
-        self._chk(lib().kin_members_correlate(self._h, K, L, _pd(u), _p32(use), None if sp is None else _p64(sp), ns, _pd(X), P,
-                                              int(bool(rank)), _pd(out)))
+        self._chk(getattr(lib(), entry)(self._h, *given, _p32(use), _p64(sp), ns, _pd(X), P, int(bool(rank)), _pd(out)))
         return out
+
+    def members_correlate(self, u, X, species=None, rank=True, use=None):
+        """kin_members_correlate: out[L][n_sel][P], the correlation of input X[:, p] (X[K][P], one row per member) with the selected
+        species at every row over the participants: Spearman's coefficient (rank=True) or Pearson's."""
+        return self._correlate("kin_members_correlate", _f64(u), X, species, rank, use)
 
     def members_correlate_dev(self, K, L, d_u, X, d_out, species=None, rank=True, use=None, stream=0):
         """kin_members_correlate_dev: device pointers u[K][L][N] and out[L][n_sel][P]; X, species and use are host arrays."""
         use = _use32(use, K)
         X, P = self._ms_inputs(X, K)
         sp, ns, _ = self._ms_species(species)
-        self._chk(lib().kin_members_correlate_dev(self._h, int(K), int(L), c_void_p(d_u), _p32(use), None if sp is None else _p64(sp), ns,
-                                                  _pd(X), P, int(bool(rank)), c_void_p(d_out), c_void_p(stream) if stream else None))
+        self._chk(lib().kin_members_correlate_dev(self._h, int(K), int(L), _dp(d_u), _p32(use), _p64(sp), ns, _pd(X), P, int(bool(rank)),
+                                                  _dp(d_out), _dp(stream)))
 
     def ensemble_correlate(self, X, species=None, rank=True, use=None):
         """kin_ensemble_correlate: members_correlate over the stored ensemble, out[n_rows][n_sel][P]."""
-        K, L = self.ensemble_size()[:2]
-        use = _use32(use, K)
-        X, P = self._ms_inputs(X, K)
-        sp, ns, nsel = self._ms_species(species)
-        out = np.empty((L, nsel, P))
-        self._chk(lib().kin_ensemble_correlate(self._h, _p32(use), None if sp is None else _p64(sp), ns, _pd(X), P, int(bool(rank)), _pd(out)))
-        return out
+        return self._correlate("kin_ensemble_correlate", None, X, species, rank, use)
 
     # --- Sobol indices of a Saltelli design ---------------------------------------------------------
     @staticmethod
@@ -1254,47 +1112,42 @@ class HipNetwork:
             raise KineticaHipError(KIN_ERR_INVALID_ARG, f"the stored ensemble has {K} members, not M (P + 2) = {M * (P + 2)}")
         return np.all(ns.reshape(P + 2, M) == L, axis=0).astype(np.int32)
 
-    @staticmethod
-    def _sobol_result(L, nsel, P, count):
-        return dict(first=np.empty((L, nsel, P)), total=np.empty((L, nsel, P)), mean=np.empty((L, nsel)), var=np.empty((L, nsel)),
-                    count=int(count))
+    def _sobol(self, entry, u, M, P, species, w):
+        M, P = int(M), int(P)
+        K, L, given = self._members(u)
+        if u is not None and M >= 1 and P >= 1 and K != M * (P + 2):
+            raise ValueError(f"u must hold M (P + 2) = {M * (P + 2)} members; got {K}")
+        w = self._sobol_weights(w, M)
+        sp, ns, nsel = self._ms_species(species)
+        shape = (L, nsel, max(P, 0))
+        out = dict(first=np.empty(shape), total=np.empty(shape), mean=np.empty((L, nsel)), var=np.empty((L, nsel)))
+        # (given[1:]: M and P stand for K = M (P + 2), so kin_members_sobol takes L, u after them)
+        self._chk(getattr(lib(), entry)(self._h, M, P, *given[1:], _p32(w), _p64(sp), ns,
+                                        *[_pd(out[q]) for q in ("first", "total", "mean", "var")]))
+        if u is not None:       # count = sum w; of the stored ensemble without w, of the samples whose members all completed the grid
+            out["count"] = M if w is None else int(np.maximum(w, 0).sum())
+        else:
+            out["count"] = int((self.ensemble_sobol_weights(M, P) if w is None else w).sum())
+        return out
 
     def members_sobol(self, u, M, P, species=None, w=None):
         """kin_members_sobol over the Saltelli design u[M (P + 2)][L][N] (member b M + m: sample m of block A, B, AB_0 ..): dict of
         first, total [L][n_sel][P] (S1, ST), mean, var [L][n_sel] (over A and B) and count = sum w. w: int multiplicities per base
         sample (None: all ones); species: ids in the handle's index base (None: all)."""
-        M, P = int(M), int(P)
-        u, K, L = self._ms_block(u, self.n)
-        if M >= 1 and P >= 1 and K != M * (P + 2):
-            raise ValueError(f"u must hold M (P + 2) = {M * (P + 2)} members; got {K}")
-        w = self._sobol_weights(w, M)
-        sp, ns, nsel = self._ms_species(species)
-        out = self._sobol_result(L, nsel, max(P, 0), M if w is None else int(np.maximum(w, 0).sum()))
-        self._chk(lib().kin_members_sobol(self._h, M, P, L, _pd(u), _p32(w), None if sp is None else _p64(sp), ns,
-                                          *[_pd(out[k]) for k in ("first", "total", "mean", "var")]))
-        return out
+        return self._sobol("kin_members_sobol", _f64(u), M, P, species, w)
 
     def members_sobol_dev(self, M, P, L, d_u, d_first=0, d_total=0, d_mean=0, d_var=0, species=None, w=None, stream=0):
         """kin_members_sobol_dev: device pointers (ints; 0 = not wanted) u[M (P + 2)][L][N], first / total [L][n_sel][P] and
         mean / var [L][n_sel]; w and species are host arrays. Only enqueues."""
-        p = lambda x: c_void_p(x) if x else None
         w = self._sobol_weights(w, int(M))
         sp, ns, _ = self._ms_species(species)
-        self._chk(lib().kin_members_sobol_dev(self._h, int(M), int(P), int(L), p(d_u), _p32(w), None if sp is None else _p64(sp), ns,
-                                              p(d_first), p(d_total), p(d_mean), p(d_var), p(stream)))
+        self._chk(lib().kin_members_sobol_dev(self._h, int(M), int(P), int(L), _dp(d_u), _p32(w), _p64(sp), ns, _dp(d_first), _dp(d_total),
+                                              _dp(d_mean), _dp(d_var), _dp(stream)))
 
     def ensemble_sobol(self, M, P, species=None, w=None):
         """kin_ensemble_sobol: members_sobol over the stored ensemble, read where it lives (w None: the samples all of whose
         members completed the save grid)."""
-        M, P = int(M), int(P)
-        L = self.ensemble_size()[1]
-        w = self._sobol_weights(w, M)
-        sp, ns, nsel = self._ms_species(species)
-        out = self._sobol_result(L, nsel, max(P, 0), 0)
-        self._chk(lib().kin_ensemble_sobol(self._h, M, P, _p32(w), None if sp is None else _p64(sp), ns,
-                                           *[_pd(out[k]) for k in ("first", "total", "mean", "var")]))
-        out["count"] = int((self.ensemble_sobol_weights(M, P) if w is None else w).sum())
-        return out
+        return self._sobol("kin_ensemble_sobol", None, M, P, species, w)
 
     # --- library order (tiled sweep) --------------------------------------------------------
     def lib_layout(self):
@@ -1308,13 +1161,13 @@ class HipNetwork:
                     windows=int(info[1]), records=int(info[2]), entries=int(info[3]), copies=int(info[4]), block=int(info[5]))
 
     def states_to_lib_dev(self, B, d_in, d_out, stream=0):
-        self._chk(lib().kin_states_to_lib_dev(self._h, int(B), c_void_p(d_in), c_void_p(d_out), c_void_p(stream) if stream else None))
+        self._chk(lib().kin_states_to_lib_dev(self._h, int(B), c_void_p(d_in), c_void_p(d_out), _dp(stream)))
 
     def states_from_lib_dev(self, B, d_in, d_out, stream=0):
-        self._chk(lib().kin_states_from_lib_dev(self._h, int(B), c_void_p(d_in), c_void_p(d_out), c_void_p(stream) if stream else None))
+        self._chk(lib().kin_states_from_lib_dev(self._h, int(B), c_void_p(d_in), c_void_p(d_out), _dp(stream)))
 
     def rates_to_lib_dev(self, B, d_k, d_k_lib, stream=0):
-        self._chk(lib().kin_rates_to_lib_dev(self._h, int(B), c_void_p(d_k), c_void_p(d_k_lib), c_void_p(stream) if stream else None))
+        self._chk(lib().kin_rates_to_lib_dev(self._h, int(B), c_void_p(d_k), c_void_p(d_k_lib), _dp(stream)))
 
     def rate_table_lib_dev(self, T_stops, d_out):
         """Rate table for T_stops in library order straight into a device buffer [len(T_stops)][k_len]."""
@@ -1323,33 +1176,29 @@ class HipNetwork:
 
     def rhs_tiled_dev(self, B, d_u_lib, d_du_lib, d_k_lib=0, d_T=0, stream=0):
         """Batched RHS in library order; exactly one of d_k_lib / d_T (device pointers as ints); only enqueues."""
-        self._chk(lib().kin_rhs_tiled_dev(self._h, int(B), c_void_p(d_u_lib), c_void_p(d_k_lib) if d_k_lib else None,
-                                          c_void_p(d_T) if d_T else None, c_void_p(d_du_lib), c_void_p(stream) if stream else None))
+        self._chk(lib().kin_rhs_tiled_dev(self._h, int(B), c_void_p(d_u_lib), _dp(d_k_lib),
+                                          _dp(d_T), c_void_p(d_du_lib), _dp(stream)))
 
     def rhs_batched_T_dev(self, B, d_u, d_T, d_du, stream=0):
         """Batched RHS on caller-order states with rate constants formed in the sweep from T[b]; only enqueues."""
         self._chk(lib().kin_rhs_batched_T_dev(self._h, int(B), c_void_p(d_u), c_void_p(d_T), c_void_p(d_du),
-                                              c_void_p(stream) if stream else None))
+                                              _dp(stream)))
 
     def rhs_batched_klib_dev(self, B, d_u, d_k_lib, d_du, stream=0):
         """Batched RHS on caller-order states u[b][N] -> du[b][N] with rate constants in the library's slot order k_lib[b][k_len]
         (from rate_table_lib_dev / rates_to_lib_dev); device pointers as ints; only enqueues."""
         self._chk(lib().kin_rhs_batched_klib_dev(self._h, int(B), c_void_p(d_u), c_void_p(d_k_lib), c_void_p(d_du),
-                                                 c_void_p(stream) if stream else None))
+                                                 _dp(stream)))
 
     def jac_pattern(self, index_base=0):
-        nnz = c_int64(0)
-        self._chk(lib().kin_jac_nnz(self._h, ctypes.byref(nnz)))
         rowptr = np.empty(self.n + 1, np.int64)
-        col = np.empty(nnz.value, np.int64)
+        col = np.empty(self._jac_nnz(), np.int64)
         self._chk(lib().kin_jac_pattern(self._h, _p64(rowptr), _p64(col), index_base))
         return rowptr, col
 
     def jac_values(self, u):
         u = _f64(u)
-        nnz = c_int64(0)
-        self._chk(lib().kin_jac_nnz(self._h, ctypes.byref(nnz)))
-        vals = np.empty(nnz.value)
+        vals = np.empty(self._jac_nnz())
         self._chk(lib().kin_jac_values(self._h, _pd(u), _pd(vals)))
         return vals
 
@@ -1369,10 +1218,14 @@ class HipNetwork:
             if k_table is not None:
                 k_table = _f64(k_table)
                 assert k_table.shape == (n_stops, self.nr)
-        n_saved, rc, stats = c_int64(0), c_int32(0), KinStats()
         fn = lib().kin_solve_explicit if explicit else lib().kin_solve
-        st = fn(self._h, ctypes.byref(params), _pd(u0), _pd(tstops), _pd(T_stops), _pd(k_table), n_stops,
-                ctypes.byref(n_saved), ctypes.byref(rc), ctypes.byref(stats))
+        return self._solved(fn, params, _pd(u0), _pd(tstops), _pd(T_stops), _pd(k_table), n_stops)
+
+    def _solved(self, fn, params, *inputs):
+        """A solve entry `fn` (`inputs`: its arguments between params and n_saved), then kin_solution_copy: (t[M], u[M][N],
+        retcode, stats dict, status) - also of a solve that failed (KIN_ERR_SOLVE_FAILED), with what it saved."""
+        n_saved, rc, stats = c_int64(0), c_int32(0), KinStats()
+        st = fn(self._h, ctypes.byref(params), *inputs, ctypes.byref(n_saved), ctypes.byref(rc), ctypes.byref(stats))
         if st not in (KIN_OK, KIN_ERR_SOLVE_FAILED):
             self._chk(st)
         t = np.empty(n_saved.value)
@@ -1422,22 +1275,7 @@ class HipNetwork:
         neither; ValueError for a wrong shape or dtype): Arrhenius parameters of each member's own
         (kin_solve_ensemble_continuous_params; k_max and t_mult are the handle's); without them the call is the one it always was.
         Returns what solve_ensemble returns: (t[M], u[K][M][N], n_saved[K], retcodes[K], [stats dict] * K); trajectories as there."""
-        u0 = np.ascontiguousarray(np.atleast_2d(_f64(u0)))
-        K = u0.shape[0]
-        assert u0.shape == (K, self.n) and len(nodes) == K
-        Ea, A = self._member_arrhenius(K, Ea, A)
-        tn = [_f64(a).ravel() for a, _ in nodes]
-        Tn = [_f64(b).ravel() for _, b in nodes]
-        assert all(len(a) == len(b) for a, b in zip(tn, Tn))
-        ptr = np.zeros(K + 1, np.int64)
-        ptr[1:] = np.cumsum([len(a) for a in tn])
-        t_all = np.ascontiguousarray(np.concatenate(tn))
-        T_all = np.ascontiguousarray(np.concatenate(Tn))
-        if Ea is not None:
-            return self._ensemble(lib().kin_solve_ensemble_continuous_params, params, K, _pd(u0), _pd(Ea), _pd(A), _p64(ptr), _pd(t_all),
-                                  _pd(T_all), trajectories=trajectories)
-        return self._ensemble(lib().kin_solve_ensemble_continuous, params, K, _pd(u0), _p64(ptr), _pd(t_all), _pd(T_all),
-                              trajectories=trajectories)
+        return self._member_ensemble("kin_solve_ensemble_continuous", params, u0, nodes, trajectories, Ea, A)
 
     def solve_ensemble_discrete(self, params: KinParams, u0, stops, trajectories=True, Ea=None, A=None):
         """kin_solve_ensemble_discrete: K trajectories under discrete rate updates, member m's rates the Arrhenius rates at
@@ -1445,22 +1283,25 @@ class HipNetwork:
         (tstops, T_stops) in global time (stop counts may differ). Ea[K][R], A[K][R]: as in solve_ensemble_continuous
         (kin_solve_ensemble_discrete_params).
         Returns what solve_ensemble returns: (t[M], u[K][M][N], n_saved[K], retcodes[K], [stats dict] * K); trajectories as there."""
+        return self._member_ensemble("kin_solve_ensemble_discrete", params, u0, stops, trajectories, Ea, A)
+
+    def _member_ensemble(self, entry, params, u0, pairs, trajectories, Ea, A):
+        """An ensemble whose member m has a time series (times, temperatures) = pairs[m] of its own: the pairs flattened to
+        ptr[K + 1], t, T for `entry`, or with Ea, A for its _params form."""
         u0 = np.ascontiguousarray(np.atleast_2d(_f64(u0)))
         K = u0.shape[0]
-        assert u0.shape == (K, self.n) and len(stops) == K
+        assert u0.shape == (K, self.n) and len(pairs) == K
         Ea, A = self._member_arrhenius(K, Ea, A)
-        ts = [_f64(a).ravel() for a, _ in stops]
-        Ts = [_f64(b).ravel() for _, b in stops]
+        ts = [_f64(a).ravel() for a, _ in pairs]
+        Ts = [_f64(b).ravel() for _, b in pairs]
         assert all(len(a) == len(b) for a, b in zip(ts, Ts))
         ptr = np.zeros(K + 1, np.int64)
         ptr[1:] = np.cumsum([len(a) for a in ts])
         t_all = np.ascontiguousarray(np.concatenate(ts))
         T_all = np.ascontiguousarray(np.concatenate(Ts))
-        if Ea is not None:
-            return self._ensemble(lib().kin_solve_ensemble_discrete_params, params, K, _pd(u0), _pd(Ea), _pd(A), _p64(ptr), _pd(t_all),
-                                  _pd(T_all), trajectories=trajectories)
-        return self._ensemble(lib().kin_solve_ensemble_discrete, params, K, _pd(u0), _p64(ptr), _pd(t_all), _pd(T_all),
-                              trajectories=trajectories)
+        own = () if Ea is None else (_pd(Ea), _pd(A))
+        return self._ensemble(getattr(lib(), entry + "_params" if own else entry), params, K, _pd(u0), *own, _p64(ptr), _pd(t_all),
+                              _pd(T_all), trajectories=trajectories)
 
     def _ensemble(self, fn, params, K, *inputs, trajectories=True):
         """The two calls of an ensemble entry point `fn`: the size query, then the solve into fresh outputs. `inputs`: its
@@ -1471,24 +1312,14 @@ class HipNetwork:
         M = rows.value
         t = np.empty(M); u = np.empty((K, M, self.n)) if trajectories else None; ns = np.zeros(K, np.int64); rcs = np.zeros(K, np.int32)
         stats = (KinStats * K)()
-        self._chk(fn(self._h, ctypes.byref(params), K, *inputs, ctypes.byref(rows), _pd(t), _pd(u), _p64(ns),
-                     rcs.ctypes.data_as(POINTER(c_int32)), stats))
+        self._chk(fn(self._h, ctypes.byref(params), K, *inputs, ctypes.byref(rows), _pd(t), _pd(u), _p64(ns), _p32(rcs), stats))
         return t, u, ns, rcs, [s_.as_dict() for s_ in stats]
 
     def solve_continuous(self, params: KinParams, u0, t_nodes, T_nodes):
         """kin_solve_continuous + kin_solution_copy: k(t) = Arrhenius(T(t)), T piecewise linear."""
         u0, t_nodes, T_nodes = _f64(u0), _f64(t_nodes), _f64(T_nodes)
         assert len(u0) == self.n and len(t_nodes) == len(T_nodes)
-        n_saved, rc, stats = c_int64(0), c_int32(0), KinStats()
-        st = lib().kin_solve_continuous(self._h, ctypes.byref(params), _pd(u0), _pd(t_nodes), _pd(T_nodes), len(t_nodes),
-                                        ctypes.byref(n_saved), ctypes.byref(rc), ctypes.byref(stats))
-        if st not in (KIN_OK, KIN_ERR_SOLVE_FAILED):
-            self._chk(st)
-        t = np.empty(n_saved.value)
-        u = np.empty((n_saved.value, self.n))
-        if n_saved.value:
-            self._chk(lib().kin_solution_copy(self._h, _pd(t), _pd(u)))
-        return t, u, rc.value, stats.as_dict(), st
+        return self._solved(lib().kin_solve_continuous, params, _pd(u0), _pd(t_nodes), _pd(T_nodes), len(t_nodes))
 
     def integrator_init(self, params: KinParams, u0, tstops=None, T_stops=None, k_table=None):
         """kin_integrator_init: init(oprob, solver; kwargs...) without solve! (return_integrator=true)."""
@@ -1710,15 +1541,13 @@ class HipNetwork:
     def rhs_block_dev(self, r_lo, r_hi, d_u, d_du, stream=0):
         """Partial RHS of reactions [r_lo, r_hi) on device buffers; only enqueues."""
         self._chk(lib().kin_rhs_block_dev(self._h, int(r_lo), int(r_hi), c_void_p(d_u), c_void_p(d_du),
-                                          c_void_p(stream) if stream else None))
+                                          _dp(stream)))
 
     def solution_dot(self, w):
         """sum_i w[i] u_i(t) at every saved time, reduced on the device (conserved quantities)."""
         w = _f64(w)
         assert len(w) == self.n
-        n_saved = c_int64(0)
-        self._chk(lib().kin_solution_size(self._h, ctypes.byref(n_saved), None))
-        out = np.empty(n_saved.value)
+        out = np.empty(self._solution()[0])
         self._chk(lib().kin_solution_dot(self._h, _pd(w), _pd(out)))
         return out
 

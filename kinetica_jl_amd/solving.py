@@ -1325,6 +1325,36 @@ def saved_state_rate_source(out, calculator, t):
     return src
 
 
+def _saved_state_pass(out, calculator, run, t_min=None):
+    """One analysis pass over the saved states of a solve, (t, run(h, u, src)): `calculator` is checked against out.rd as
+    setup_network does; t, u[B][N] are the saved times and states, of t >= t_min alone when that is given; src the keywords of
+    the rate constants the solve held at each of them (saved_state_rate_source); h a handle of out.rd (species ids in rd are
+    1-based) that holds the calculator's Arrhenius law when temperatures are the source, closed whatever `run` does."""
+    sd, rd = out.sd, out.rd
+    setup_network(sd, rd, calculator)
+    t = np.asarray(out.sol.t, dtype=float)
+    u = np.ascontiguousarray(np.asarray(out.sol.u, dtype=float).reshape(len(t), sd.n))
+    src = saved_state_rate_source(out, calculator, t)
+    if t_min is not None:
+        keep = t >= float(t_min)
+        t, u = t[keep], np.ascontiguousarray(u[keep])
+        for key in ("k_row", "T"):      # (one entry per saved time; k holds the rows k_row indexes)
+            if key in src:
+                src[key] = np.asarray(src[key])[keep]
+    h = capi.HipNetwork(*rd.flat(sd.n), index_base=1)
+    try:
+        if "T" in src:
+            h.set_arrhenius(calculator.Ea, calculator.A, calculator.k_max, calculator.t_mult)
+        return t, run(h, u, src)
+    finally:
+        h.close()
+
+
+def _species_ids(sd, species):
+    """0-based ids of species given by name or by 0-based id."""
+    return [sd.toInt[x] - 1 if isinstance(x, str) else int(x) for x in species]
+
+
 def reaction_fluxes(out, calculator, weights="trapezoid", rates=False):
     """Time-integrated rate of every reaction over the saved states of a solve - which reactions carried the flux, the
     companion of identify_next_seeds' "which species matter". `out` is any ODESolveOutput (solve_network's, or one read
@@ -1340,10 +1370,8 @@ def reaction_fluxes(out, calculator, weights="trapezoid", rates=False):
 
     The trapezoid rule is exact to O(dt^2) between rate updates and first order across a stop, where k jumps: callers who
     need more should save more often."""
-    sd, rd, conditions = out.sd, out.rd, out.conditions
-    setup_network(sd, rd, calculator)
+    setup_network(out.sd, out.rd, calculator)      # (before the weights are looked at; the pass below checks again)
     t = np.asarray(out.sol.t, dtype=float)
-    u = np.ascontiguousarray(np.asarray(out.sol.u, dtype=float).reshape(len(t), sd.n))
     if isinstance(weights, str):
         if weights != "trapezoid":
             raise ValueError('weights must be "trapezoid", None or an array of one weight per saved time')
@@ -1354,16 +1382,9 @@ def reaction_fluxes(out, calculator, weights="trapezoid", rates=False):
         w = np.asarray(weights, dtype=float).ravel()
         if len(w) != len(t):
             raise ValueError("weights must have one entry per saved time")
-    src = saved_state_rate_source(out, calculator, t)
-    h = capi.HipNetwork(*rd.flat(sd.n), index_base=1)
-    try:
-        if "T" in src:
-            h.set_arrhenius(calculator.Ea, calculator.A, calculator.k_max, calculator.t_mult)
-        res = h.flux_batched(u, w=w, want_rates=rates, **src)
-    finally:
-        h.close()
+    _, res = _saved_state_pass(out, calculator, lambda h, u, src: h.flux_batched(u, w=w, want_rates=rates, **src))
     flux, rr = res if rates else (res, None)
-    return ReactionFluxes.from_flux(flux, rd, sd.n, w, rr)
+    return ReactionFluxes.from_flux(flux, out.rd, out.sd.n, w, rr)
 
 
 # ---- directed-relation-graph reduction (EXTENSION: Lu & Law's DRG over the saved states of a solve) ---------------------
@@ -1373,20 +1394,8 @@ def drg_coefficients(out, calculator, pairing=True):
     share of species A's turnover that runs through records B takes part in (include/kinetica_hip.h has the definition;
     pairing: a reaction and its exact reverse are one record progressing at their net rate). `calculator` and the rate
     constants of every saved state are chosen as reaction_fluxes chooses them. One device pass (kin_drg_batched) over sol.u."""
-    sd, rd = out.sd, out.rd
-    setup_network(sd, rd, calculator)
-    t = np.asarray(out.sol.t, dtype=float)
-    u = np.ascontiguousarray(np.asarray(out.sol.u, dtype=float).reshape(len(t), sd.n))
-    src = saved_state_rate_source(out, calculator, t)
-    h = capi.HipNetwork(*rd.flat(sd.n), index_base=1)
-    try:
-        if "T" in src:
-            h.set_arrhenius(calculator.Ea, calculator.A, calculator.k_max, calculator.t_mult)
-        rowptr, colidx = h.drg_pattern(pairing)
-        coef = h.drg_batched(u, pairing=pairing, **src)
-    finally:
-        h.close()
-    return rowptr, colidx, coef
+    _, graph = _saved_state_pass(out, calculator, lambda h, u, src: h.drg_pattern(pairing) + (h.drg_batched(u, pairing=pairing, **src),))
+    return graph
 
 
 def drg_select(rowptr, colidx, coef, targets, eps):
@@ -1415,20 +1424,8 @@ def pfa_coefficients(out, calculator, pairing=True):
     the production and the consumption share of A's turnover that run through B, directly and over one intermediate
     (include/kinetica_hip.h has the definition; pairing as in drg_coefficients). `calculator` and the rate constants of every
     saved state are chosen as reaction_fluxes chooses them. One device pass (kin_pfa_batched) over sol.u."""
-    sd, rd = out.sd, out.rd
-    setup_network(sd, rd, calculator)
-    t = np.asarray(out.sol.t, dtype=float)
-    u = np.ascontiguousarray(np.asarray(out.sol.u, dtype=float).reshape(len(t), sd.n))
-    src = saved_state_rate_source(out, calculator, t)
-    h = capi.HipNetwork(*rd.flat(sd.n), index_base=1)
-    try:
-        if "T" in src:
-            h.set_arrhenius(calculator.Ea, calculator.A, calculator.k_max, calculator.t_mult)
-        rowptr, colidx = h.pfa_pattern(pairing)
-        coef = h.pfa_batched(u, pairing=pairing, **src)
-    finally:
-        h.close()
-    return rowptr, colidx, coef
+    _, graph = _saved_state_pass(out, calculator, lambda h, u, src: h.pfa_pattern(pairing) + (h.pfa_batched(u, pairing=pairing, **src),))
+    return graph
 
 
 def drgep_importance(out, calculator, targets, pairing=True, importance=None):
@@ -1438,19 +1435,8 @@ def drgep_importance(out, calculator, targets, pairing=True, importance=None):
     the definition; pairing as in drg_coefficients). `importance`: the result of an earlier call, which takes part in the
     maximum (several solves folded into one ranking). `calculator` and the rate constants of every saved state are chosen as
     reaction_fluxes chooses them. One device pass (kin_drgep_batched) over sol.u."""
-    sd, rd = out.sd, out.rd
-    setup_network(sd, rd, calculator)
-    t = np.asarray(out.sol.t, dtype=float)
-    u = np.ascontiguousarray(np.asarray(out.sol.u, dtype=float).reshape(len(t), sd.n))
-    tg = [sd.toInt[x] - 1 if isinstance(x, str) else int(x) for x in targets]
-    src = saved_state_rate_source(out, calculator, t)
-    h = capi.HipNetwork(*rd.flat(sd.n), index_base=1)
-    try:
-        if "T" in src:
-            h.set_arrhenius(calculator.Ea, calculator.A, calculator.k_max, calculator.t_mult)
-        imp = h.drgep_batched(u, tg, pairing=pairing, importance=importance, **src)
-    finally:
-        h.close()
+    tg = _species_ids(out.sd, targets)
+    _, imp = _saved_state_pass(out, calculator, lambda h, u, src: h.drgep_batched(u, tg, pairing=pairing, importance=importance, **src))
     return imp
 
 
@@ -1474,19 +1460,9 @@ def reaction_importance(out, calculator, species=None, pairing=True, importance=
     denominators are always the whole network's. `importance`: the result of an earlier call, which takes part in the
     maximum (several solves folded into one ranking). `calculator` and the rate constants of every saved state are chosen as
     reaction_fluxes chooses them. One device pass (kin_reaction_importance_batched) over sol.u."""
-    sd, rd = out.sd, out.rd
-    setup_network(sd, rd, calculator)
-    t = np.asarray(out.sol.t, dtype=float)
-    u = np.ascontiguousarray(np.asarray(out.sol.u, dtype=float).reshape(len(t), sd.n))
-    sp = None if species is None else [sd.toInt[x] - 1 if isinstance(x, str) else int(x) for x in species]
-    src = saved_state_rate_source(out, calculator, t)
-    h = capi.HipNetwork(*rd.flat(sd.n), index_base=1)
-    try:
-        if "T" in src:
-            h.set_arrhenius(calculator.Ea, calculator.A, calculator.k_max, calculator.t_mult)
-        imp = h.reaction_importance_batched(u, species=sp, pairing=pairing, importance=importance, **src)
-    finally:
-        h.close()
+    sp = None if species is None else _species_ids(out.sd, species)
+    _, imp = _saved_state_pass(out, calculator, lambda h, u, src: h.reaction_importance_batched(u, species=sp, pairing=pairing,
+                                                                                            importance=importance, **src))
     return imp
 
 
@@ -1649,24 +1625,10 @@ def species_timescales(out, calculator, t_min=None, summary=None):
     layer leaves out the induction period, where nothing is quasi-steady yet). `summary`: an earlier Timescales, whose three
     per-species arrays take part in the extrema (several solves folded into one). `calculator` and the rate constants of every
     saved state are chosen as reaction_fluxes chooses them. One device pass (kin_timescale_batched) over the counting states."""
-    sd, rd = out.sd, out.rd
-    setup_network(sd, rd, calculator)
-    t = np.asarray(out.sol.t, dtype=float)
-    u = np.ascontiguousarray(np.asarray(out.sol.u, dtype=float).reshape(len(t), sd.n))
-    src = saved_state_rate_source(out, calculator, t)
-    keep = np.ones(len(t), bool) if t_min is None else t >= float(t_min)
-    for key in ("k_row", "T"):      # (one entry per saved time; k holds the rows k_row indexes)
-        if key in src:
-            src[key] = np.asarray(src[key])[keep]
-    h = capi.HipNetwork(*rd.flat(sd.n), index_base=1)
-    try:
-        if "T" in src:
-            h.set_arrhenius(calculator.Ea, calculator.A, calculator.k_max, calculator.t_mult)
-        res = h.timescale_batched(np.ascontiguousarray(u[keep]), summary=None if summary is None else summary.summary, **src)
-    finally:
-        h.close()
+    earlier = None if summary is None else summary.summary
+    t, res = _saved_state_pass(out, calculator, lambda h, u, src: h.timescale_batched(u, summary=earlier, **src), t_min=t_min)
     s = res["summary"]
-    return Timescales(t[keep], s[0], s[1], s[2], res["norm"])
+    return Timescales(t, s[0], s[1], s[2], res["norm"])
 
 
 def qss_candidates(ts, tol, scale=None, max_lifetime=None):

@@ -1,15 +1,16 @@
-// The resident integrator's controller: the whole of kin_solve's orchestration (chunk loop, discrete rate updates, save
-// grid, adaptive_solve! retries - reference src/solving/methods.jl:185-303, 717-865; solve_utils.jl:376-424, 435-509) and of
-// the BDF integrator that stands in for the reference's CVODE_BDF (solver.cpp: Solver::restart / step / select_order /
-// interpolate, including the LU cache and its guards), written ONCE against a backend `B` that supplies the vector
-// operations, the Jacobian, the factorisation and the corrector iteration:
+// Two things, each written once. (1) The solve driver res_drive<D>: the whole of kin_solve's orchestration (chunk loop, discrete
+// rate updates, save grid, adaptive_solve! retries - reference src/solving/methods.jl:185-303, 717-865; solve_utils.jl:376-424,
+// 435-509) around an integrator D - the controller below, and solver.cpp's host-driven Solver through its HostDriven adapter.
+// (2) The resident integrator's controller ResidentBdf<B>: the BDF integrator that stands in for the reference's CVODE_BDF
+// (the algorithm of solver.cpp: Solver::restart / step / select_order / interpolate, including the LU cache and its guards),
+// against a backend `B` that supplies the vector operations, the Jacobian, the factorisation and the corrector iteration:
 //   * resident.hip compiles it for the device: ONE 512-thread workgroup owns one trajectory for the whole solve - every
 //     thread runs this controller redundantly on identical scalars (reduction results are broadcast), the backend's
 //     operations are workgroup-wide phases separated by barriers; no host round trip, no kernel boundary per step;
 //   * tests/native/resident_host.cpp compiles it for the CPU with a sequential backend over the same tables: the
 //     controller's logic is checked without a GPU (test infrastructure, not a product path).
 // The host-driven integrator of solver.cpp stays the path for large networks; both implement the same algorithm with the
-// same constants. At the default tolerances (1e-10 / 1e-8) their trajectories agree within the step-sequence
+// same constants (the settings: resident_setup.hpp) under the same driver. At the default tolerances (1e-10 / 1e-8) their trajectories agree within the step-sequence
 // tolerance (<= 201 units over the 312 solves of profiles/r05_robustness_resident.jsonl), not bit for bit. At rtol = 1e-10 every
 // implementation runs on the rounding floor of the right-hand side and they differ by the accuracy of their LINEAR ALGEBRA: against
 // a Radau truth (tests/golden/truth_tight_200.npz) the CPU port's pivoted LU lands at rms 61 / max 378 tight units in 4 073
@@ -30,6 +31,7 @@ constexpr int RES_D_ROWS = BDF_D_ROWS;
 constexpr int RES_MAX_SLOTS = 64;   // one LU-cache slot per lane of a wavefront (resident.hip keeps the slot table in registers)
 
 enum : int { RES_RET_SUCCESS = 0, RES_RET_MAXITERS = 1, RES_RET_DTLESSTHANMIN = 2, RES_RET_UNSTABLE = 3 };   // = KIN_RETCODE_*
+enum StepStatus { STEP_OK = 0, STEP_DT_MIN = 1, STEP_UNSTABLE = 2 };   // how an integrator's step() ended (res_step_retcode)
 
 // what a solve needs besides the network (plain data; pointers are device pointers in the product, host pointers in the test)
 struct ResParams {
@@ -37,11 +39,11 @@ struct ResParams {
   int32_t solve_chunks, adaptive_tols, ban_negatives, save_hits_end;
   int64_t maxiters, n_chunks;
   int32_t L;                       // points of the per-chunk (or whole-span) save grid
-  const double* save_local;        // L local save times (solver.cpp: save_local)
+  const double* save_local;        // L local save times (resident_setup.hpp: make_res_grid)
   int32_t n_stops, rate_mode;      // rate_mode 0: static k; 1: k_table[n_stops][R]; 2: Arrhenius at T_stops[n_stops];
                                    // 3: Arrhenius at T(t) of every step attempt (continuous, nodes below)
   const double* tstops;
-  // integrator settings (the same defaults and environment switches as solver.cpp)
+  // integrator settings of the resident controller (resident_setup.hpp: res_default_settings; Solver keeps its own members)
   double lu_band, reuse_rate_max, crate_dy_max, lu_drift_max, newton_frac;
   int64_t crate_max_age, lu_max_age;
   int32_t n_slots, carry_rate;
@@ -56,7 +58,7 @@ struct ResParams {
 // Continuous rate updates: the temperature at global time tg of the profile (tn, Tn)[n] (n >= 2) - the linear interpolation of
 // the DiffEqArray functor of src/utils.jl:135-139, clamped to the first / last node, else inside [tn[i-1], tn[i]) with
 // i = upper_bound(tn, tg). The one copy every integrator calls (this controller on the device and in its CPU replay, solver.cpp's
-// solve_entry and manual integrator), so that all of them form their rates at the same temperatures; no contraction into FMAs.
+// kin_solve and manual integrator), so that all of them form their rates at the same temperatures; no contraction into FMAs.
 KIN_HD inline double res_T_of(const double* tn, const double* Tn, int64_t n, double tg) {
 #pragma clang fp contract(off)
   if (tg <= tn[0]) return Tn[0];
@@ -285,8 +287,6 @@ struct ResidentBdf {
     return b.corrector(in, gamma);
   }
 
-  enum StepStatus { STEP_OK = 0, STEP_DT_MIN = 1, STEP_UNSTABLE = 2 };
-
   // one accepted step towards t_bound (Solver::step without the asynchronous machinery)
   KIN_HD StepStatus step(double t_bound) {
     bool accepted = false, first_attempt = true;
@@ -424,112 +424,185 @@ struct ResidentBdf {
     b.interp(order, wp, row);
   }
 
-  // ---- the driver (solve_entry, solver.cpp); returns the result block
-  KIN_HD ResResult run() {
-    const bool chunks = P.solve_chunks != 0;
-    const bool variable = P.n_stops > 0;
-    const int L = P.L;
-    double abstol = P.abstol, reltol = P.reltol;
-    set_tols(abstol, reltol);
-    dtmin = P.dtmin;
-    invalidate_lu();
-    b.load_u0();
-    int64_t next_stop = 0, n_saved = 0, rates_in_force = -1;
-    bool have_history = false, rates_changed = false;   // warm continuation across chunk starts (solve_chunks == 2)
-    int retcode = RES_RET_SUCCESS;
-    for (int64_t nc = 0; nc < P.n_chunks && retcode == RES_RET_SUCCESS; nc++) {
-      st.n_chunks++;
-      cache_suspended = false;
-      const double t_start_global = chunks ? P.chunkstep * (double)nc : P.tspan0;
-      const double t_end_global = chunks ? t_start_global + P.chunkstep : P.tspan1;
-      const double shift = chunks ? (double)nc * P.chunkstep : 0.0;
-      const double t_loc0 = chunks ? 0.0 : P.tspan0;
-      const double t_loc1 = chunks ? P.chunkstep : P.tspan1;
-      const int64_t stop_first = next_stop;
-      b.chunk_start_from_y();
-      const int64_t saved_at_chunk_start = n_saved;
-      int attempts = 0;
-      for (;;) {   // adaptive_solve! (solve_utils.jl:376-424)
-        attempts++;
-        if (attempts > 1) have_history = false;   // a retry starts cold from the chunk's first state
-        retcode = RES_RET_SUCCESS;
-        iters_left = P.maxiters;
-        int64_t stop_i = stop_first;
-        while (variable && stop_i < P.n_stops && P.tstops[stop_i] <= t_start_global) stop_i++;
-        if (variable) {
-          const int64_t want = stop_i > 0 ? stop_i - 1 : 0;
-          if (want != rates_in_force) { b.apply_rates(want); rates_in_force = want; rates_changed = true; }
-        }
-        int save_i = 0;
-        double t_seg = t_loc0;
-        bool failed = false;
-        if (n_saved < P.sol_cap) { b.save_y(n_saved, P.save_local[0] + shift); }
-        n_saved++;
-        save_i = 1;
-        while (t_seg < t_loc1 && !failed) {
-          double seg_end = t_loc1;
-          bool ends_at_stop = false;
-          if (variable && stop_i < P.n_stops && P.tstops[stop_i] < t_end_global) {
-            const double loc = P.tstops[stop_i] - shift;
-            if (loc < t_loc1) { seg_end = loc; ends_at_stop = true; }
-          }
-          if (seg_end > t_seg) {
-            const double seg_len = seg_end - t_seg;
-            seg_origin = t_seg + shift;
-            if (continuous()) rates_at(0.0);   // rates at the segment start for f0 / J of the restart
-            // (continuous rates: every chunk start re-initialises, solve_chunks == 2 is 1 - solver.cpp does the same)
-            if (P.solve_chunks == 2 && have_history && !rates_changed && !continuous()) resume();
-            else if (!restart(seg_len)) { retcode = RES_RET_UNSTABLE; failed = true; break; }
-            have_history = true;
-            rates_changed = false;
-            while (t < seg_len) {
-              const StepStatus ss = step(seg_len);
-              if (iters_left < 0) { retcode = RES_RET_MAXITERS; failed = true; break; }
-              if (ss == STEP_DT_MIN) { retcode = RES_RET_DTLESSTHANMIN; failed = true; break; }
-              if (ss == STEP_UNSTABLE) { retcode = RES_RET_UNSTABLE; failed = true; break; }
-              const double t_abs = t >= seg_len ? seg_end : t_seg + t;
-              const int last = (chunks && !(nc == P.n_chunks - 1 && !P.save_hits_end)) ? L - 1 : L;
-              while (save_i < last && P.save_local[save_i] <= t_abs) {
-                const double tl = P.save_local[save_i] - t_seg;
-                if (n_saved < P.sol_cap) { interpolate(tl < t ? tl : t, n_saved); b.set_time(n_saved, P.save_local[save_i] + shift); }
-                n_saved++;
-                save_i++;
-              }
-              select_order();
-            }
-            if (failed) break;
-            b.y_from_D0();
-          }
-          t_seg = seg_end;
-          if (ends_at_stop) { b.apply_rates(stop_i); rates_in_force = stop_i; stop_i++; rates_changed = true; }
-        }
-        if (!failed) {
-          if (chunks && nc == P.n_chunks - 1 && L > 1 && P.save_hits_end) {
-            if (n_saved < P.sol_cap) b.save_y(n_saved, P.save_local[L - 1] + shift);
-            n_saved++;
-          }
-          next_stop = stop_i;
-          break;
-        }
-        // failure: tighten the tolerances and redo this chunk from its (clipped) start state
-        rates_in_force = -1;
-        const double mintol = 2.220446049250313e-16;
-        if (!P.adaptive_tols || attempts >= 5 || abstol / 10 <= mintol || reltol / 10 <= mintol) break;
-        abstol /= 10; reltol /= 10;
-        set_tols(abstol, reltol);
-        st.n_retries++;
-        invalidate_lu_keep_counters();
-        cache_suspended = true;
-        b.y_from_chunk_start_clipped();
-        n_saved = saved_at_chunk_start;
-      }
-    }
-    ResResult r;
-    r.retcode = retcode; r.pad = 0; r.n_saved = n_saved; r.final_abstol = abstol; r.final_reltol = reltol; r.st = st;
-    for (int i = 0; i < 20; i++) r.prof[i] = 0;
-    b.profile_out(r.prof);
-    return r;
+  // ---- what res_drive (below) asks of an integrator; solver.cpp's HostDriven is the other one
+  static constexpr bool saves_every_step = false;   // there is always a save grid (resident_setup.hpp: res_has_grid)
+  KIN_HD void begin() { set_tols(P.abstol, P.reltol); dtmin = P.dtmin; invalidate_lu(); b.load_u0(); }   // the call's reset, state <- u0
+  KIN_HD double time() const { return t; }
+  KIN_HD int64_t iters() const { return iters_left; }
+  KIN_HD void chunk_begin(int64_t) { st.n_chunks++; cache_suspended = false; b.chunk_start_from_y(); }
+  KIN_HD void attempt_begin(int64_t maxiters) { iters_left = maxiters; }
+  KIN_HD void apply_rates(int64_t stop) { b.apply_rates(stop); }
+  // rows past the solution buffer are counted, not written
+  KIN_HD void save_y(int64_t row, double tg) { if (row < P.sol_cap) b.save_y(row, tg); }
+  KIN_HD void save_interp(int64_t row, double tl, double tg) { if (row < P.sol_cap) { interpolate(tl, row); b.set_time(row, tg); } }
+  KIN_HD bool segment_start(double origin, double seg_len, bool warm) {
+    seg_origin = origin;
+    if (continuous()) rates_at(0.0);   // rates at the segment start for f0 / J of the restart
+    // (continuous rates: every chunk start re-initialises, solve_chunks == 2 is 1)
+    if (warm && !continuous()) { resume(); return true; }
+    return restart(seg_len);
   }
+  KIN_HD void segment_end(bool failed) { if (!failed) b.y_from_D0(); }
+  KIN_HD void attempt_failed(int64_t, int, int, double, double, double) {}
+  KIN_HD void retry(double a, double r, int64_t) {
+    set_tols(a, r);
+    st.n_retries++;
+    invalidate_lu_keep_counters();
+    cache_suspended = true;
+    b.y_from_chunk_start_clipped();
+  }
+
+  // the whole solve; returns the result block
+  KIN_HD ResResult run();
 };
+
+// ---- The solve driver: kin_solve's orchestration around an integrator `d`, written once. Chunk loop in local time, discrete rate
+// updates at tstops with zero-order hold, segments, the per-chunk save grid with its dropped last point, warm chunk starts
+// (solve_chunks == 2) and the adaptive_solve! tolerance retries. `D` integrates and stores: ResidentBdf<B> above (device kernel,
+// CPU replays, lockstep ensemble members) and solver.cpp's HostDriven around Solver. What differs between them is an operation
+// of D: where rows go (save_y / save_interp / retry's rewind), how a segment starts and ends, the host's diagnostics
+// (chunk_begin, attempt_failed). D::saves_every_step: without a save grid (P.L == 0) every accepted step is a row (save_step).
+// The solve's parameters are D's member P, read as d.P at every use: the device kernel's controller lives in LDS, and a copy
+// of the reference held across the loop costs it registers (scratch grew by 32 bytes per lane with one).
+
+// stops [from, result) lie at or before global time tg: the first stop not yet applied at tg
+KIN_HD inline int64_t res_stops_passed(const double* tstops, int64_t n_stops, int64_t from, double tg) {
+  while (from < n_stops && tstops[from] <= tg) from++;
+  return from;
+}
+// index of the rates in force when `stop_i` is the first stop not yet applied: the last stop passed (zero-order hold); before
+// the first stop: the initial conditions, stop 0
+KIN_HD inline int64_t res_rates_at_stop(int64_t stop_i) { return stop_i > 0 ? stop_i - 1 : 0; }
+
+// end, in chunk-local time (= global - shift), of the segment whose next stop is stop_i: that stop if it lies before the chunk's
+// end (t_end_global, locally t_loc1), else the chunk's end
+struct ResSegEnd { double end; bool at_stop; };
+KIN_HD inline ResSegEnd res_segment_end(const double* tstops, int64_t n_stops, int64_t stop_i, double t_end_global, double shift,
+                                        double t_loc1) {
+  if (stop_i < n_stops && tstops[stop_i] < t_end_global) {
+    const double loc = tstops[stop_i] - shift;
+    if (loc < t_loc1) return ResSegEnd{loc, true};
+  }
+  return ResSegEnd{t_loc1, false};
+}
+
+// a step's outcome as a return code: D::step's status, D::iters() afterwards
+KIN_HD inline int res_step_retcode(StepStatus ss, int64_t iters_left) {
+  if (iters_left < 0) return RES_RET_MAXITERS;
+  if (ss == STEP_DT_MIN) return RES_RET_DTLESSTHANMIN;
+  if (ss == STEP_UNSTABLE) return RES_RET_UNSTABLE;
+  return RES_RET_SUCCESS;
+}
+
+struct ResDriven { int retcode; int64_t n_saved; double abstol, reltol; };   // (the tolerances: as tightened by the retries)
+
+template <class D>
+KIN_HD ResDriven res_drive(D& d) {
+  const bool chunks = d.P.solve_chunks != 0;
+  const int L = d.P.L;
+  bool every_step = false;
+  if constexpr (D::saves_every_step) every_step = L == 0;
+  d.begin();
+  double abstol = d.P.abstol, reltol = d.P.reltol;
+  int64_t next_stop = 0, n_saved = 0, rates_in_force = -1;
+  bool have_history = false, rates_changed = false;   // warm continuation across chunk starts (solve_chunks == 2)
+  int retcode = RES_RET_SUCCESS;
+  for (int64_t nc = 0; nc < d.P.n_chunks && retcode == RES_RET_SUCCESS; nc++) {
+    const double t_start_global = chunks ? d.P.chunkstep * (double)nc : d.P.tspan0;
+    const double t_end_global = chunks ? t_start_global + d.P.chunkstep : d.P.tspan1;
+    const double shift = chunks ? (double)nc * d.P.chunkstep : 0.0;   // global = local + shift
+    const double t_loc0 = chunks ? 0.0 : d.P.tspan0;
+    const double t_loc1 = chunks ? d.P.chunkstep : d.P.tspan1;
+    // local stops of this chunk: tg - nc*chunkstep for tstops in [t_start, t_end) (methods.jl:798-800); the complete-timespan
+    // variant takes all of them (methods.jl:697)
+    const int64_t stop_first = next_stop;
+    d.chunk_begin(nc);
+    const int64_t saved_at_chunk_start = n_saved;
+    int attempts = 0;
+    for (;;) {   // adaptive_solve! (solve_utils.jl:376-424)
+      attempts++;
+      if (attempts > 1) have_history = false;   // a retry starts cold from the chunk's first state
+      retcode = RES_RET_SUCCESS;
+      d.attempt_begin(d.P.maxiters);
+      int64_t stop_i = res_stops_passed(d.P.tstops, d.P.n_stops, stop_first, t_start_global);
+      if (d.P.n_stops > 0) {
+        const int64_t want = res_rates_at_stop(stop_i);
+        if (want != rates_in_force) { d.apply_rates(want); rates_in_force = want; rates_changed = true; }
+      }
+      double t_seg = t_loc0;
+      bool failed = false;
+      // the chunk's first point (saveat = []: every step, starting with the initial state)
+      d.save_y(n_saved, (every_step ? t_loc0 : d.P.save_local[0]) + shift);
+      n_saved++;
+      int save_i = 1;
+      while (t_seg < t_loc1 && !failed) {
+        const ResSegEnd seg = res_segment_end(d.P.tstops, d.P.n_stops, stop_i, t_end_global, shift, t_loc1);
+        if (seg.end > t_seg) {
+          // Every segment is integrated in segment-local time tau in [0, seg_len]: the rates are constant inside a segment
+          // (autonomous system), and restarting at tau = 0 keeps the tiny first steps of a restart (1e-20 s is common) above the
+          // floating-point resolution of the time variable - the underflow the reference's chunking exists to avoid
+          // (docs/src/development/implementation-details.md:5-28) but re-creates at tstops > 0.
+          const double seg_len = seg.end - t_seg;
+          // every segment start re-initialises like the reference (reinit!, methods.jl:260, 819), except a chunk start of
+          // solve_chunks == 2 whose rates did not change (a StaticODESolve's chunk boundaries)
+          const bool warm = d.P.solve_chunks == 2 && have_history && !rates_changed;
+          if (!d.segment_start(t_seg + shift, seg_len, warm)) { retcode = RES_RET_UNSTABLE; failed = true; break; }
+          have_history = true;
+          rates_changed = false;
+          while (d.time() < seg_len) {
+            retcode = res_step_retcode(d.step(seg_len), d.iters());
+            if (retcode != RES_RET_SUCCESS) { failed = true; break; }
+            const double t_abs = d.time() >= seg_len ? seg.end : t_seg + d.time();   // chunk-local time reached
+            // saves covered by this step. The chunk's last local point: dropped except on the final chunk (methods.jl:829-846),
+            // where it is the chunk's end state (saved below) or, off the grid, a dense-output value
+            const int last = (chunks && !(nc == d.P.n_chunks - 1 && !d.P.save_hits_end)) ? L - 1 : L;
+            while (save_i < last && d.P.save_local[save_i] <= t_abs) {
+              const double tl = d.P.save_local[save_i] - t_seg;
+              d.save_interp(n_saved, tl < d.time() ? tl : d.time(), d.P.save_local[save_i] + shift);
+              n_saved++;
+              save_i++;
+            }
+            if constexpr (D::saves_every_step) {
+              if (every_step) { d.save_step(n_saved, t_abs + shift); n_saved++; }
+            }
+            d.select_order();
+          }
+          d.segment_end(failed);   // state at the segment end = D[0]
+          if (failed) break;
+        }
+        t_seg = seg.end;
+        if (seg.at_stop) { d.apply_rates(stop_i); rates_in_force = stop_i; stop_i++; rates_changed = true; }
+      }
+      if (!failed) {
+        // the chunk's last save point goes to the output only on the final chunk; its value is the state at the chunk end
+        if (chunks && nc == d.P.n_chunks - 1 && L > 1 && d.P.save_hits_end) {
+          d.save_y(n_saved, d.P.save_local[L - 1] + shift);
+          n_saved++;
+        }
+        next_stop = stop_i;
+        break;
+      }
+      // failure: tighten the tolerances and redo this chunk from its (clipped) start state
+      d.attempt_failed(nc, attempts, retcode, t_seg, abstol, reltol);
+      rates_in_force = -1;
+      const double mintol = 2.220446049250313e-16;
+      if (!d.P.adaptive_tols || attempts >= 5 || abstol / 10 <= mintol || reltol / 10 <= mintol) break;
+      abstol /= 10; reltol /= 10;
+      n_saved = saved_at_chunk_start;
+      d.retry(abstol, reltol, n_saved);
+    }
+  }
+  return ResDriven{retcode, n_saved, abstol, reltol};
+}
+
+template <class B>
+KIN_HD ResResult ResidentBdf<B>::run() {
+  const ResDriven o = res_drive(*this);
+  ResResult r;
+  r.retcode = o.retcode; r.pad = 0; r.n_saved = o.n_saved; r.final_abstol = o.abstol; r.final_reltol = o.reltol; r.st = st;
+  for (int i = 0; i < 20; i++) r.prof[i] = 0;
+  b.profile_out(r.prof);
+  return r;
+}
 
 }  // namespace kin

@@ -1,6 +1,7 @@
-// Host-side preparation shared by the resident integrator's owner (resident.cpp) and its CPU replay (tests/native/):
-// the save grid, chunk count and dtmin of a solve exactly as solve_entry derives them (solver.cpp; reference
-// src/solving/methods.jl:756-758, 829-846, 164, 232, 694, 770), and the integrator settings with their environment switches.
+// Host-side preparation of a solve, shared by every owner of an integrator (solver.cpp, resident.cpp, ensemble.cpp) and the CPU
+// replays (tests/native/): the save grid, chunk count and dtmin (reference src/solving/methods.jl:756-758, 829-846, 164, 232,
+// 694, 770) and the ResParams the solve driver reads (resident_core.hpp: res_drive), and the integrator settings with their
+// environment switches.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -55,22 +56,31 @@ inline ResGrid make_res_grid(const kin_params& p) {
   return g;
 }
 
-// integrator settings: the constants of solver.cpp (Solver) and its two cache switches (KIN_LU_CACHE_SLOTS, KIN_LU_BAND)
+// The integrator settings of the LU cache and the carried convergence rate, one definition each: Solver's members (solver.cpp,
+// where each value's reason is written down) and res_default_settings initialise from them
+constexpr double LU_REUSE_RATE_MAX = 0.15, LU_CRATE_DY_MAX = 0.2, LU_DRIFT_MAX = 1.0, LU_BAND = 0.35;
+constexpr int64_t LU_CRATE_MAX_AGE = 10, LU_MAX_AGE = 50;
+constexpr size_t LU_CACHE_MB = 32768;
+
+// ... and the cache's environment switches, each read in one place. KIN_LU_CACHE_SLOTS: slots wanted (`dflt` without it; the
+// caller applies its own cap), KIN_LU_CACHE_MB: device memory the slots may take, KIN_LU_BAND: the reuse band
+inline int lu_env_slots(int dflt) { const char* e = getenv("KIN_LU_CACHE_SLOTS"); return e ? std::max(1, atoi(e)) : dflt; }
+inline size_t lu_env_budget_mb() { const char* e = getenv("KIN_LU_CACHE_MB"); return e ? (size_t)std::max(1, atoi(e)) : LU_CACHE_MB; }
+// the reuse band of a cache of n_slots: a single slot keeps a band only if KIN_LU_BAND is set (CVODE's own scheme)
+inline double lu_env_band(int n_slots) {
+  const char* e = getenv("KIN_LU_BAND");
+  return e ? atof(e) : (n_slots > 1 ? LU_BAND : 0.0);
+}
+
 inline void res_default_settings(ResParams& P, int n_slots_max) {
-  auto envd = [](const char* n, double d) { const char* e = getenv(n); return e ? atof(e) : d; };
-  auto envi = [](const char* n, long long d) { const char* e = getenv(n); return e ? atoll(e) : d; };
-  int want = (int)envi("KIN_LU_CACHE_SLOTS", RES_MAX_SLOTS);
-  want = std::max(1, std::min(want, std::min(n_slots_max, RES_MAX_SLOTS)));
-  const double band = envd("KIN_LU_BAND", 0.35);
-  P.n_slots = want;
-  P.lu_band = want > 1 ? band : (getenv("KIN_LU_BAND") ? band : 0.0);
-  // the constants of solver.cpp (Solver): reuse_rate_max, crate_dy_max, lu_drift_max, corrector tolerance, crate_max_age, lu_max_age
-  P.reuse_rate_max = 0.15;
-  P.crate_dy_max = 0.2;
-  P.lu_drift_max = 1.0;
+  P.n_slots = std::max(1, std::min(lu_env_slots(RES_MAX_SLOTS), std::min(n_slots_max, RES_MAX_SLOTS)));
+  P.lu_band = lu_env_band(P.n_slots);
+  P.reuse_rate_max = LU_REUSE_RATE_MAX;
+  P.crate_dy_max = LU_CRATE_DY_MAX;
+  P.lu_drift_max = LU_DRIFT_MAX;
   P.newton_frac = -1.0;   // < 0: bdf_newton_frac(rtol), the rule of bdf_rules.hpp (a test may pin a value here)
-  P.crate_max_age = 10;
-  P.lu_max_age = 50;
+  P.crate_max_age = LU_CRATE_MAX_AGE;
+  P.lu_max_age = LU_MAX_AGE;
   P.carry_rate = 1;
 }
 
@@ -84,15 +94,11 @@ inline void res_fill_params(ResParams& P, const kin_params& p, const ResGrid& g)
   P.sol_cap = g.cap;
 }
 
-// LU-cache slots per member of K: up to RES_MAX_SLOTS (KIN_LU_CACHE_SLOTS), bounded by KIN_LU_CACHE_MB (default 32768) over
+// LU-cache slots per member of K: up to RES_MAX_SLOTS (KIN_LU_CACHE_SLOTS), bounded by KIN_LU_CACHE_MB over
 // all members; slot_bytes = one slot's factorisation values and diag(J) copy
 inline int res_lu_slots(size_t slot_bytes, int64_t K) {
-  size_t budget_mb = 32768;
-  if (const char* e = getenv("KIN_LU_CACHE_MB")) budget_mb = (size_t)std::max(1, atoi(e));
-  const size_t fit = std::max<size_t>(1, budget_mb * 1024 * 1024 / std::max<size_t>(1, slot_bytes * (size_t)K));
-  int want = RES_MAX_SLOTS;
-  if (const char* e = getenv("KIN_LU_CACHE_SLOTS")) want = std::max(1, atoi(e));
-  return (int)std::min<size_t>((size_t)std::min(want, RES_MAX_SLOTS), fit);
+  const size_t fit = std::max<size_t>(1, lu_env_budget_mb() * 1024 * 1024 / std::max<size_t>(1, slot_bytes * (size_t)K));
+  return (int)std::min<size_t>((size_t)std::min(lu_env_slots(RES_MAX_SLOTS), RES_MAX_SLOTS), fit);
 }
 
 // the kin_stats of a controller's result; `lu`: the SparseLU it factorised with (lu.hpp), `slots` its LU-cache slots

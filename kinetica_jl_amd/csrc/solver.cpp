@@ -13,6 +13,9 @@
 // order selection from the error estimates one order down/up). oracle/bdf.py restates the
 // same algorithm on the CPU; both are checked against closed-form and high-accuracy truths.
 //
+// The orchestration itself is the solve driver shared with the resident integrator (resident_core.hpp: res_drive); this file
+// holds the integrator it drives here (Solver), the adapter between the two (HostDriven) and what surrounds the loop.
+//
 // Control flow lives on the host; every vector operation, the RHS, the Jacobian, the LU and
 // the triangular solves are device kernels on one stream. A step attempt enqueues predictor +
 // two Newton iterations + error estimate blind (kernels turn into no-ops once the device-side
@@ -36,8 +39,6 @@ namespace kin {
 namespace {
 constexpr double MIN_FACTOR = 0.2, MAX_FACTOR = 10.0;   // the explicit pair's step-size factors (the BDF's rules: bdf_rules.hpp)
 constexpr double INF = std::numeric_limits<double>::infinity();
-
-enum StepStatus { STEP_OK = 0, STEP_DT_MIN = 1, STEP_UNSTABLE = 2 };
 }  // namespace
 
 struct Solver {
@@ -80,29 +81,23 @@ struct Solver {
     const NetworkHost& H = h->host;
     lu.analyze(N, H.j_ptr, H.j_col, lu_options_for(N), s);
     {
-      // cache size: KIN_LU_CACHE_SLOTS (default 128), bounded by KIN_LU_CACHE_MB (default 32768) of device memory. A
+      // cache size: KIN_LU_CACHE_SLOTS (default 128), bounded by KIN_LU_CACHE_MB of device memory (resident_setup.hpp). A
       // restart replays a ramp of step sizes over up to ~12 decades of c; slots sit >= 35 % apart, i.e. ~8 per decade:
       // the cache must hold the whole ramp (~90 slots), or the cyclic sweep evicts every slot just before its next
       // use (32 slots: the full C4 run made 405 k factorisations; its first second, a narrower ramp, only 446)
-      int want = 128;
-      double band = 0.35;
-      size_t budget_mb = 32768;
+      size_t budget_mb = lu_env_budget_mb();
       if (const char* e = getenv("KIN_INJECT_BAD_PIVOT")) inject_bad_pivot_at = atoll(e);
       if (const char* e = getenv("KIN_SPECULATE")) speculate = atoi(e) != 0;
       fuse_newton = lu.fused_tri && lu.m > 0 && lu.newton_grid() <= 10;
       if (const char* e = getenv("KIN_FUSE_NEWTON")) fuse_newton = atoi(e) != 0 && lu.fused_tri && lu.m > 0;
-      if (const char* e = getenv("KIN_LU_CACHE_SLOTS")) want = std::max(1, atoi(e));
-      if (const char* e = getenv("KIN_LU_BAND")) band = atof(e);
-      if (const char* e = getenv("KIN_LU_CACHE_MB")) budget_mb = (size_t)std::max(1, atoi(e));
       if (h->lu_budget_mb > 0) budget_mb = std::min(budget_mb, h->lu_budget_mb);   // a replica's share (capi.cpp: replica_ensemble)
       const size_t fit = std::max<size_t>(1, budget_mb * 1024 * 1024 / std::max<size_t>(1, lu.slot_bytes()));
-      lu_slots = (int)std::min<size_t>(std::min<size_t>((size_t)want, fit), (size_t)LU_MAX_SLOTS);
+      lu_slots = (int)std::min<size_t>(std::min<size_t>((size_t)lu_env_slots(128), fit), (size_t)LU_MAX_SLOTS);
       d_jdiag.upload(H.j_diag, s);
       d_drift.alloc(LU_MAX_SLOTS + 1);
       KIN_HIP(hipHostMalloc((void**)&h_drift, (LU_MAX_SLOTS + 1) * sizeof(double), hipHostMallocDefault));
       h_drift[LU_MAX_SLOTS] = 0.0;
-      lu_band = lu_slots > 1 ? band : 0.0;
-      if (lu_slots == 1 && getenv("KIN_LU_BAND")) lu_band = band;   // single slot with a reuse band: CVODE's own scheme
+      lu_band = lu_env_band(lu_slots);
     }
     std::vector<int32_t> yl(N), ident(N);
     lu.yloc.download(yl.data(), N, s);
@@ -353,7 +348,7 @@ struct Solver {
   // with a Jacobian at most 50 steps old. Without a bound a slot whose contraction has degraded is never found out -
   // one-iteration steps measure nothing - and the unconverged iterates pile up in the difference history until the
   // error test collapses the step size (seen on the first segment of the C4 ramp).
-  int64_t crate_max_age = 10;
+  int64_t crate_max_age = LU_CRATE_MAX_AGE;
   // is the slot's remembered rate fresh enough for the first-iteration test? (it keeps being carried and updated either way)
   bool crate_fresh(const SparseLU::Slot& q) const {
     return q.crate < 1.0 && q.crate_restart == st.n_restarts && st.n_steps - q.crate_step <= crate_max_age;
@@ -362,17 +357,18 @@ struct Solver {
   // contraction is worse than the remembered one - up to the 0.2 that a measurement would still accept - the error left behind is
   // 0.25 dy: 0.2 keeps that at the corrector tolerance. (With 1.0 a static 1 400 K solve of a 1k-species network accepted first
   // corrections of 0.66 units on a stale rate, poisoned its difference history and ended in DtLessThanMin at every tolerance.)
-  double crate_dy_max = 0.2;
+  double crate_dy_max = LU_CRATE_DY_MAX;
   int last_iters = 0, last_iter_slot = -1;
-  double reuse_rate_max = 0.15;  // KIN_LU_RATE_MAX: slowest contraction accepted from a reused factorisation (0.1: C3 11 % slower, in
-                                 // refreshes that were not needed; 0.2: not robust, see set_tols; 0.5: 17 % slower on the C4 ramp)
+  // 0.15, the slowest contraction accepted from a reused factorisation (0.1: C3 11 % slower, in refreshes that were not needed;
+  // 0.2: not robust, see set_tols; 0.5: 17 % slower on the C4 ramp)
+  double reuse_rate_max = LU_REUSE_RATE_MAX;
   // KIN_LU_MAX_AGE: a slot is offered for that many restarts after its Jacobian was evaluated. Unlimited reuse is
   // UNSAFE: a direction that was stiff when the slot was made (c J ~ 1e6) and is not any more (its species consumed) is
   // damped to nothing by the old matrix - the corrections vanish, the corrector "converges" at once, and both the
   // convergence test and the error test (which only see the corrections) are blind to the component being left at its
   // predictor; the full C4 ramp then ran into DtLessThanMin a few hundred restarts later (with 5 restarts it runs
   // through). CVODE bounds the same staleness by re-evaluating J at least every 50 steps.
-  int64_t lu_max_age = 50;
+  int64_t lu_max_age = LU_MAX_AGE;
   // Drift guard: at every restart the Jacobian is fresh; one kernel compares, for every slot, diag(I - c_s J) as it was when
   // the slot was made with what today's Jacobian gives at the same c_s, and slots whose diagonal moved by more than a factor
   // of 1 + lu_drift_max (either way) are dropped. For mass-action kinetics a column's off-diagonal entries are bounded by its
@@ -382,7 +378,7 @@ struct Solver {
   // matrices the guard had dropped although the corrector - whose contraction is watched anyway, reuse_rate_max - converged
   // with them): a factor of 2 keeps the protection and takes 307 -> 242 factorisations, 0.388 -> 0.346 s, C4's 20 chunks
   // 516 -> 291 and 1.51 -> 1.39 s, deviations from the truths inside the spread of the reuse-band study.
-  double lu_drift_max = 1.0;
+  double lu_drift_max = LU_DRIFT_MAX;
   DevBuf<int32_t> d_jdiag;
   DevBuf<double> d_drift;
   double* h_drift = nullptr;     // pinned
@@ -898,6 +894,88 @@ void apply_rates(kin_network* h, const double* T_stops, bool have_table, int64_t
   h->k_pending = false;
 }
 
+// The host-driven integrator as the solve driver sees it (resident_core.hpp: res_drive): Solver integrates, rows go to the
+// handle's solution buffer, which grows, and their times to h->sol_t
+struct HostDriven {
+  static constexpr bool saves_every_step = true;   // no save grid (saveat = []): every accepted step is a row
+  kin_network* h;
+  Solver& S;
+  const ResParams& P;
+  const double* T_stops;
+  bool have_table;
+  std::chrono::steady_clock::time_point wall0;
+  int64_t N = h->host.N;
+  hipStream_t s = h->stream;
+  SaveBuf sb{h, (int)N};
+  DevBuf<double> chunk_start;   // the chunk's first state, for its retries
+  double seg_origin = 0.0;      // global time of the current segment's tau = 0 (continuous rates: S.pre_attempt reads it)
+  // KIN_PROGRESS=<seconds>: a status line on stderr at most that often (the reference's `progress` option drives a progress
+  // bar from the same place, methods.jl:822-827); KIN_TRACE_CHUNK=n: Solver::trace during chunk n
+  const double progress_every = getenv("KIN_PROGRESS") ? std::max(1.0, atof(getenv("KIN_PROGRESS"))) : 0.0;
+  std::chrono::steady_clock::time_point progress_last = wall0;
+  const long long trace_chunk = getenv("KIN_TRACE_CHUNK") ? atoll(getenv("KIN_TRACE_CHUNK")) : -1;
+
+  void begin() {}   // (Solver::begin_call and the upload of u0: solve_entry, before the driver)
+  double time() const { return S.t; }
+  int64_t iters() const { return S.iters_left; }
+  StepStatus step(double t_bound) { return S.step(t_bound); }
+  void select_order() { S.select_order(); }
+  void chunk_begin(int64_t nc) {
+    S.st.n_chunks++;
+    S.cache_suspended = false;
+    S.trace = (nc == trace_chunk);
+    if (progress_every > 0.0 &&
+        std::chrono::duration<double>(std::chrono::steady_clock::now() - progress_last).count() >= progress_every) {
+      progress_last = std::chrono::steady_clock::now();
+      fprintf(stderr, "[kin_solve] chunk %lld / %lld, %.1f s, %lld steps, %lld factorisations, %lld restarts\n", (long long)nc,
+              (long long)P.n_chunks, std::chrono::duration<double>(progress_last - wall0).count(), (long long)S.st.n_steps,
+              (long long)S.st.n_factor, (long long)S.st.n_restarts);
+      fflush(stderr);
+    }
+    KIN_HIP(hipMemcpyAsync(chunk_start.p, S.y.p, N * sizeof(double), hipMemcpyDeviceToDevice, s));
+  }
+  void attempt_begin(int64_t maxiters) { S.iters_left = maxiters; }
+  void apply_rates(int64_t si) { kin::apply_rates(h, T_stops, have_table, si); }
+  // row `row` (= h->n_saved) at global time tg joins the solution; returns where its state goes
+  double* new_row(int64_t row, double tg) { sb.reserve(row + 1); sb.push_time(tg); return sb.row(row); }
+  void save_y(int64_t row, double tg) { KIN_HIP(hipMemcpyAsync(new_row(row, tg), S.y.p, N * sizeof(double), hipMemcpyDeviceToDevice, s)); }
+  void save_interp(int64_t row, double tl, double tg) { S.interpolate(tl, new_row(row, tg)); }
+  void save_step(int64_t row, double tg) { S.save_state(new_row(row, tg)); }   // (rides in the pending accept)
+  bool segment_start(double origin, double seg_len, bool warm) {
+    seg_origin = origin;
+    if (S.pre_attempt) S.pre_attempt(0.0);   // rates at the segment start for f0 / J of the restart
+    // (carrying the history across RATE UPDATES was built and measured in round 4 - 3 180 rejected steps and 4x the time on the
+    // C4 prefix - and is gone, docs/DESIGN_HISTORY.md R4)
+    if (warm && !S.pre_attempt && !S.explicit_mode) { S.resume_chunk(); return true; }
+    return S.restart(0.0, seg_len);
+  }
+  void segment_end(bool failed) {
+    // a failed attempt leaves the accept of its last good step (and the copy of that state into the solution buffer, whose
+    // time is already recorded) pending: it must not outlive the buffers it points into
+    if (failed) S.flush_accept();
+    else KIN_HIP(hipMemcpyAsync(S.y.p, S.state_ptr(), N * sizeof(double), hipMemcpyDeviceToDevice, s));
+  }
+  void attempt_failed(int64_t nc, int attempts, int retcode, double t_seg, double abstol, double reltol) {
+    if (progress_every > 0.0 || getenv("KIN_TIMING"))
+      fprintf(stderr, "[kin_solve] chunk %lld attempt %d failed with retcode %d at local t = %.6e (h = %.3e, order %d); tolerances %.1e / %.1e\n",
+              (long long)nc, attempts, retcode, t_seg + S.t, S.h_abs, S.order, abstol, reltol);
+  }
+  void retry(double abstol, double reltol, int64_t rows) {
+    S.set_tols(abstol, reltol);
+    S.st.n_retries++;
+    S.invalidate_lu_keep_counters();
+    S.cache_suspended = true;
+    // The retried chunk starts from its start state with NEGATIVE entries set to zero. A chunk can inherit concentrations
+    // of -1e-9 (tolerance-sized, 10 x abstol is common) from its predecessor, and mass-action kinetics is unstable under
+    // them - a bimolecular term flips its sign - up to a finite-time blow-up of the exact solution from that state: every
+    // retry then dies at the same local time whatever its tolerances (3k species, 1 500 K: five attempts, all at
+    // t = 7.0e-4). The first attempt of a chunk is untouched (reference semantics); only the rescue path clips.
+    launch_clip_negative(N, chunk_start.p, S.y.p, s);
+    h->n_saved = rows;
+    h->sol_t.resize((size_t)rows);
+  }
+};
+
 }  // namespace
 
 // the save grid of a chunkwise solve (params.jl:89-99); a call that saves nothing on a grid (kin_integrator_init) skips it
@@ -946,7 +1024,6 @@ int solve_entry(kin_network* h, const kin_params& p, const double* u0, const dou
   auto wall0 = std::chrono::steady_clock::now();
   const int64_t N = h->host.N, R = h->host.R;
   validate_solve(h, p, tstops, T_stops, k_table, n_stops, t_nodes, T_nodes, n_nodes, true);
-  const bool chunks = p.solve_chunks != 0;
   const bool continuous = n_nodes > 0;
   const bool variable = n_stops > 0;
   // small networks: the whole solve in one launch, one workgroup owns the trajectory (resident.cpp)
@@ -961,8 +1038,6 @@ int solve_entry(kin_network* h, const kin_params& p, const double* u0, const dou
   S.begin_call(p, explicit_solver);
   S.sync_wait_s = 0.0;
   std::fill(S.iter_hist, S.iter_hist + 8, 0);
-  double abstol = p.abstol, reltol = p.reltol;
-
   const bool have_table = variable && k_table != nullptr;
   if (have_table) {
     h->table.upload(k_table, (size_t)n_stops * R, s);
@@ -972,7 +1047,6 @@ int solve_entry(kin_network* h, const kin_params& p, const double* u0, const dou
   // ---- output storage
   h->sol_t.clear();
   h->n_saved = 0;
-  SaveBuf sb{h, (int)N};
   // the save grid (resident_setup.hpp; none: every step is saved). save_hits_end true: the chunk end is the last local save point
   // (the usual case). false (save_interval does not divide the chunk): the final chunk's last output is the dense-output value at
   // its last local save point. (The reference then also restarts every chunk from integ.sol.u[end] = the state at that last
@@ -980,181 +1054,34 @@ int solve_entry(kin_network* h, const kin_params& p, const double* u0, const dou
   // chunk end.)
   const bool has_grid = res_has_grid(p);
   const ResGrid grid = has_grid ? make_res_grid(p) : ResGrid{};
-  const std::vector<double>& save_local = grid.save_local;
-  const int64_t L = (int64_t)save_local.size(), n_chunks = grid.n_chunks;
-  const bool save_hits_end = grid.save_hits_end;
-  sb.reserve(has_grid ? grid.cap : 1024);
+  ResParams P{};
+  res_fill_params(P, p, grid);
+  P.save_local = grid.save_local.data();
+  P.n_stops = (int32_t)n_stops;
+  P.tstops = tstops;
+  HostDriven drv{h, S, P, T_stops, have_table, wall0};
+  drv.sb.reserve(has_grid ? grid.cap : 1024);
+  drv.chunk_start.alloc(N);
 
   // continuous rates: T(t) = linear interpolation of the profile solution (resident_core.hpp), k = calculator(T(t)) re-evaluated
   // on the device
-  double seg_origin = 0.0;   // global time of the current segment's tau = 0
   if (continuous) {
     // (no launch: the first kernel of the attempt that reads k forms it from this temperature, handle.hpp)
-    S.pre_attempt = [&](double tau) { h->set_pending_T(res_T_of(t_nodes, T_nodes, n_nodes, seg_origin + tau)); };
+    S.pre_attempt = [&](double tau) { h->set_pending_T(res_T_of(t_nodes, T_nodes, n_nodes, drv.seg_origin + tau)); };
     h->has_rates = true;
   } else {
     S.pre_attempt = nullptr;
   }
   // initial state
   S.y.upload(u0, N, s);
-  int64_t next_stop = 0;      // first tstop not yet applied
-  int retcode = KIN_RETCODE_SUCCESS;
-  DevBuf<double> chunk_start;
-  chunk_start.alloc(N);
-  bool have_history = false, rates_changed = false;
-  int64_t rates_in_force = -1;
-  // every segment start re-initialises like the reference (reinit!, methods.jl:260, 819), except the chunk starts of
-  // kin_params.solve_chunks == 2 whose rates did not change (resume_chunk). Carrying the history across RATE UPDATES was built and
-  // measured in round 4 (3 180 rejected steps and 4x the time on the C4 prefix) and is gone (docs/DESIGN_HISTORY.md R4).
-
-  // KIN_PROGRESS=<seconds>: a status line on stderr at most that often (the reference's `progress` option drives a
-  // progress bar from the same place, methods.jl:822-827)
-  const double progress_every = getenv("KIN_PROGRESS") ? std::max(1.0, atof(getenv("KIN_PROGRESS"))) : 0.0;
-  auto progress_last = wall0;
-  const long long trace_chunk = getenv("KIN_TRACE_CHUNK") ? atoll(getenv("KIN_TRACE_CHUNK")) : -1;
-  for (int64_t nc = 0; nc < n_chunks && retcode == KIN_RETCODE_SUCCESS; nc++) {
-    S.st.n_chunks++;
-    S.cache_suspended = false;
-    S.trace = (nc == trace_chunk);
-    if (progress_every > 0.0 &&
-        std::chrono::duration<double>(std::chrono::steady_clock::now() - progress_last).count() >= progress_every) {
-      progress_last = std::chrono::steady_clock::now();
-      fprintf(stderr, "[kin_solve] chunk %lld / %lld, %.1f s, %lld steps, %lld factorisations, %lld restarts\n", (long long)nc,
-              (long long)n_chunks, std::chrono::duration<double>(progress_last - wall0).count(), (long long)S.st.n_steps,
-              (long long)S.st.n_factor, (long long)S.st.n_restarts);
-      fflush(stderr);
-    }
-    const double t_start_global = chunks ? p.solve_chunkstep * (double)nc : p.tspan0;
-    const double t_end_global = chunks ? t_start_global + p.solve_chunkstep : p.tspan1;
-    const double shift = chunks ? (double)nc * p.solve_chunkstep : 0.0;   // global = local + shift
-    const double t_loc0 = chunks ? 0.0 : p.tspan0;
-    const double t_loc1 = chunks ? p.solve_chunkstep : p.tspan1;
-    // local stops of this chunk: tg - nc*chunkstep for tstops in [t_start, t_end) (methods.jl:798-800);
-    // the complete-timespan variant takes all of them (methods.jl:697)
-    const int64_t stop_first = next_stop;
-    KIN_HIP(hipMemcpyAsync(chunk_start.p, S.y.p, N * sizeof(double), hipMemcpyDeviceToDevice, s));
-    const int64_t saved_at_chunk_start = h->n_saved;
-    const size_t times_at_chunk_start = h->sol_t.size();
-
-    int attempts = 0;
-    for (;;) {  // adaptive_solve! (solve_utils.jl:376-424)
-      attempts++;
-      if (attempts > 1) have_history = false;   // a retry starts cold from the chunk's first state
-      retcode = KIN_RETCODE_SUCCESS;
-      S.iters_left = p.maxiters;
-      int64_t stop_i = stop_first;
-      // rates in force at the chunk start: the last stop at or before it (zero-order hold)
-      while (variable && stop_i < n_stops && tstops[stop_i] <= t_start_global) {
-        stop_i++;
-      }
-      if (variable) {
-        const int64_t want = stop_i > 0 ? stop_i - 1 : 0;   // before the first stop: initial conditions
-        if (want != rates_in_force) { apply_rates(h, T_stops, have_table, want); rates_in_force = want; rates_changed = true; }
-      }
-      int64_t save_i = 0;
-      double t_seg = t_loc0;
-      bool failed = false;
-      // save the chunk's first point (local t = 0)
-      auto save_state_now = [&](double t_local) {
-        sb.reserve(h->n_saved + 1);
-        KIN_HIP(hipMemcpyAsync(sb.row(h->n_saved), S.y.p, N * sizeof(double), hipMemcpyDeviceToDevice, s));
-        sb.push_time(t_local + shift);
-      };
-      if (L > 0) { save_state_now(save_local[0]); save_i = 1; }
-      else save_state_now(t_loc0);   // saveat = []: every step, starting with the initial state
-
-      while (t_seg < t_loc1 && !failed) {
-        // segment end: next tstop inside this chunk, else the chunk end
-        double seg_end = t_loc1;
-        bool ends_at_stop = false;
-        if (variable && stop_i < n_stops && tstops[stop_i] < t_end_global) {
-          const double loc = tstops[stop_i] - shift;
-          if (loc < t_loc1) { seg_end = loc; ends_at_stop = true; }
-        }
-        if (seg_end > t_seg) {
-          // Every segment is integrated in segment-local time tau in [0, seg_len]: the rates are
-          // constant inside a segment (autonomous system), and restarting at tau = 0 keeps the tiny
-          // first steps of a restart (1e-20 s is common) above the floating-point resolution of the
-          // time variable - the underflow the reference's chunking exists to avoid
-          // (docs/src/development/implementation-details.md:5-28) but re-creates at tstops > 0.
-          const double seg_len = seg_end - t_seg;
-          seg_origin = t_seg + shift;
-          if (continuous) S.pre_attempt(0.0);   // rates at the segment start for f0 / J of the restart
-          // kin_params.solve_chunks == 2: warm continuation at a chunk start whose rates did not change (a StaticODESolve's
-          // chunk boundaries; between the rate updates of a ramp the integrator is re-initialised as the reference does)
-          const bool warm_chunk = p.solve_chunks == 2 && have_history && !rates_changed && !continuous && !S.explicit_mode;
-          if (warm_chunk) S.resume_chunk();
-          else if (!S.restart(0.0, seg_len)) { retcode = KIN_RETCODE_UNSTABLE; failed = true; break; }
-          have_history = true;
-          rates_changed = false;
-          while (S.t < seg_len) {
-            StepStatus ss = S.step(seg_len);
-            if (S.iters_left < 0) { retcode = KIN_RETCODE_MAXITERS; failed = true; break; }
-            if (ss == STEP_DT_MIN) { retcode = KIN_RETCODE_DTLESSTHANMIN; failed = true; break; }
-            if (ss == STEP_UNSTABLE) { retcode = KIN_RETCODE_UNSTABLE; failed = true; break; }
-            const double t_abs = S.t >= seg_len ? seg_end : t_seg + S.t;   // chunk-local time reached
-            // saves covered by this step
-            if (L > 0) {
-              // the chunk's last local point: dropped except on the final chunk (methods.jl:829-846), where it is the
-              // chunk's end state (saved below) or, off the grid, a dense-output value
-              const int64_t last = (chunks && !(nc == n_chunks - 1 && !save_hits_end)) ? L - 1 : L;
-              while (save_i < last && save_local[save_i] <= t_abs) {
-                sb.reserve(h->n_saved + 1);
-                S.interpolate(std::min(save_local[save_i] - t_seg, S.t), sb.row(h->n_saved));
-                sb.push_time(save_local[save_i] + shift);
-                save_i++;
-              }
-            } else {
-              sb.reserve(h->n_saved + 1);
-              S.save_state(sb.row(h->n_saved));
-              sb.push_time(t_abs + shift);
-            }
-            S.select_order();
-          }
-          // a failed attempt leaves the accept of its last good step (and the copy of that state into the solution
-          // buffer, whose time is already recorded) pending: it must not outlive the buffers it points into
-          if (failed) { S.flush_accept(); break; }
-          // state at the segment end = D[0]
-          KIN_HIP(hipMemcpyAsync(S.y.p, S.state_ptr(), N * sizeof(double), hipMemcpyDeviceToDevice, s));
-        }
-        t_seg = seg_end;
-        if (ends_at_stop) { apply_rates(h, T_stops, have_table, stop_i); rates_in_force = stop_i; stop_i++; rates_changed = true; }
-      }
-      if (!failed) {
-        // all but the chunk's last save point go to the output, the last only on the final chunk
-        // (methods.jl:829-846); its value is the state at the chunk end
-        if (chunks && nc == n_chunks - 1 && L > 1 && save_hits_end) save_state_now(save_local[L - 1]);
-        next_stop = stop_i;
-        break;
-      }
-      // ---- failure: tighten tolerances and redo this chunk from its start state
-      if (progress_every > 0.0 || getenv("KIN_TIMING"))
-        fprintf(stderr, "[kin_solve] chunk %lld attempt %d failed with retcode %d at local t = %.6e (h = %.3e, order %d); tolerances %.1e / %.1e\n",
-                (long long)nc, attempts, retcode, t_seg + S.t, S.h_abs, S.order, abstol, reltol);
-      rates_in_force = -1;
-      const double mintol = std::numeric_limits<double>::epsilon();
-      if (!p.adaptive_tols || attempts >= 5 || abstol / 10 <= mintol || reltol / 10 <= mintol) break;
-      abstol /= 10; reltol /= 10;
-      S.set_tols(abstol, reltol);
-      S.st.n_retries++;
-      S.invalidate_lu_keep_counters();
-      S.cache_suspended = true;
-      // The retried chunk starts from its start state with NEGATIVE entries set to zero. A chunk can inherit concentrations
-      // of -1e-9 (tolerance-sized, 10 x abstol is common) from its predecessor, and mass-action kinetics is unstable under
-      // them - a bimolecular term flips its sign - up to a finite-time blow-up of the exact solution from that state: every
-      // retry then dies at the same local time whatever its tolerances (3k species, 1 500 K: five attempts, all at
-      // t = 7.0e-4). The first attempt of a chunk is untouched (reference semantics); only the rescue path clips.
-      launch_clip_negative(N, chunk_start.p, S.y.p, s);
-      h->n_saved = saved_at_chunk_start;
-      h->sol_t.resize(times_at_chunk_start);
-    }
-  }
+  const ResDriven out = res_drive(drv);
+  const int retcode = out.retcode;
   S.flush_accept();
   h->flush_pending_T(s);     // a temperature no kernel has consumed yet: k is what the caller may read next
   KIN_HIP(hipStreamSynchronize(s));
   S.pre_attempt = nullptr;   // the lambda captures locals of this call
-  S.st.final_abstol = abstol;
-  S.st.final_reltol = reltol;
+  S.st.final_abstol = out.abstol;
+  S.st.final_reltol = out.reltol;
   S.st.lu_dense_dim = S.lu.m; S.st.lu_sparse_rows = S.lu.ns; S.st.lu_rounds = S.lu.nrounds;
   S.st.lu_nnz = 2 * S.lu.nnzU + S.lu.ns + (int64_t)S.lu.m * S.lu.m;
   S.st.lu_slots = S.lu_slots;
@@ -1184,8 +1111,8 @@ int solve_entry(kin_network* h, const kin_params& p, const double* u0, const dou
 // ------------------------------------------------------------------------------------------
 struct IntegratorState {
   bool active = false, in_segment = false, have_table = false;
-  double t_loc0 = 0, t_loc1 = 0, t_seg = 0, seg_end = 0;
-  bool ends_at_stop = false;
+  double t_loc0 = 0, t_loc1 = 0, t_seg = 0;
+  ResSegEnd seg{0.0, false};   // the current segment's end
   std::vector<double> tstops, T_stops;
   std::vector<double> t_nodes, T_nodes;   // continuous rate updates: T(t) = linear interpolation of these (global time)
   int64_t stop_i = 0;
@@ -1221,10 +1148,9 @@ void integrator_init(kin_network* h, const kin_params& p, const double* u0, cons
   I.t_loc1 = chunks ? p.solve_chunkstep : p.tspan1;
   I.t_seg = I.t_loc0;
   S.y.upload(u0, N, s);
-  // rates in force at the start: the last stop at or before it, else the initial conditions (stop 0)
-  const double t_start_global = chunks ? 0.0 : p.tspan0;
-  while (variable && I.stop_i < n_stops && I.tstops[I.stop_i] <= t_start_global) I.stop_i++;
-  if (variable) apply_rates(h, I.T_stops.data(), I.have_table, I.stop_i > 0 ? I.stop_i - 1 : 0);
+  // rates in force at the start (the driver's rules, resident_core.hpp)
+  I.stop_i = res_stops_passed(I.tstops.data(), n_stops, 0, chunks ? 0.0 : p.tspan0);
+  if (variable) apply_rates(h, I.T_stops.data(), I.have_table, res_rates_at_stop(I.stop_i));
   I.active = true;
   S.t = 0.0;
   KIN_HIP(hipStreamSynchronize(s));
@@ -1247,29 +1173,26 @@ int64_t integrator_step(kin_network* h, int64_t max_steps) {
   CallGuard exit_guard{h, S};
   while (I.retcode == KIN_RETCODE_SUCCESS && I.t_seg < I.t_loc1 && (max_steps <= 0 || taken < max_steps)) {
     if (!I.in_segment) {
-      I.seg_end = I.t_loc1;
-      I.ends_at_stop = false;
-      if (I.stop_i < (int64_t)I.tstops.size() && I.tstops[I.stop_i] < I.t_loc1) { I.seg_end = I.tstops[I.stop_i]; I.ends_at_stop = true; }
+      I.seg = res_segment_end(I.tstops.data(), (int64_t)I.tstops.size(), I.stop_i, I.t_loc1, 0.0, I.t_loc1);   // (local = global time)
       if (S.pre_attempt) S.pre_attempt(0.0);   // rates at the segment start for f0 / J of the restart
-      if (!S.restart(0.0, I.seg_end - I.t_seg)) { I.retcode = KIN_RETCODE_UNSTABLE; break; }
+      if (!S.restart(0.0, I.seg.end - I.t_seg)) { I.retcode = KIN_RETCODE_UNSTABLE; break; }
       I.in_segment = true;
     }
-    const double seg_len = I.seg_end - I.t_seg;
+    const double seg_len = I.seg.end - I.t_seg;
     // the last step of this call gets no speculative batch behind it: other entry points on the handle (kin_set_rates,
     // kin_rates_at, kin_newton_solve) may run before the next call and must not find a half-run step
     S.hold_speculation = max_steps > 0 && taken + 1 >= max_steps;
-    StepStatus ss = S.step(seg_len);
-    if (S.iters_left < 0) { I.retcode = KIN_RETCODE_MAXITERS; S.flush_accept(); break; }
-    if (ss == STEP_DT_MIN) { I.retcode = KIN_RETCODE_DTLESSTHANMIN; S.flush_accept(); break; }
-    if (ss == STEP_UNSTABLE) { I.retcode = KIN_RETCODE_UNSTABLE; S.flush_accept(); break; }
+    const StepStatus ss = S.step(seg_len);
+    I.retcode = res_step_retcode(ss, S.iters_left);
+    if (I.retcode != KIN_RETCODE_SUCCESS) { S.flush_accept(); break; }
     S.select_order();
     taken++;
     if (S.t >= seg_len) {   // segment finished: state = D[0]; switch the rates at a tstop
       KIN_HIP(hipMemcpyAsync(S.y.p, S.state_ptr(), N * sizeof(double), hipMemcpyDeviceToDevice, s));
-      I.t_seg = I.seg_end;
+      I.t_seg = I.seg.end;
       I.in_segment = false;
       S.t = 0.0;
-      if (I.ends_at_stop) { apply_rates(h, I.T_stops.data(), I.have_table, I.stop_i); I.stop_i++; }
+      if (I.seg.at_stop) { apply_rates(h, I.T_stops.data(), I.have_table, I.stop_i); I.stop_i++; }
     }
   }
   h->flush_pending_T(s);

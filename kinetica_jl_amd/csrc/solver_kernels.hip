@@ -647,7 +647,7 @@ __global__ __launch_bounds__(256) void rk_error_kernel(int N, RkVec e, const dou
 }
 
 // out = a + s*b
-// out[i] = max(a[i], 0): the start state of a RETRIED chunk (see solve_entry)
+// out[i] = max(a[i], 0): the start state of a RETRIED chunk (solver.cpp: HostDriven::retry)
 __global__ __launch_bounds__(256) void clip_negative_kernel(int N, const double* __restrict__ a, double* __restrict__ out) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i < N) { const double v = a[i]; out[i] = v < 0.0 ? 0.0 : v; }

@@ -1,5 +1,5 @@
 // The scalar step-control rules of the BDF integrator, defined ONCE for every implementation inside the library: the
-// host-driven Solver (solver.cpp), the resident controller ResidentBdf<B> (resident_core.hpp: on the device, on the host
+// host-driven integrator's explicit mode (solver.cpp), the controller ResidentBdf<B> (resident_core.hpp: on the device, on the host
 // threads of the lockstep ensemble, in the CPU replays under tests/native*) and the set-up of EnsembleSolver (ensemble.cpp).
 // Plain C++17, no HIP headers; every function is KIN_HD, so the same text compiles in the device pass, in hipcc's host pass
 // and with a plain host compiler. The expressions are kept operation by operation as the integrators had them (a fused

@@ -1,8 +1,8 @@
 // kin_cache_probe (declaration and argument layout: include/kinetica_hip.h): the LU cache's drift guard once, on the caller's
-// Jacobian values, through the launchers the integrators use - launch_jac_diag, launch_drift_test and drop_drifted of Solver::restart
+// Jacobian values, through the launchers the integrators use - launch_jac_diag, launch_drift_test and drop_drifted of HostBackend::drift_launch / drift_collect
 // and the lockstep ensemble (path 0), ph_factor's saved diagonal, DevBackend::drift_check / ph_drift and the slot lookups of the
 // resident kernel (path 1: resident.cpp, resident_probe.hip). Nothing here computes: the probe uploads, fills the launchers'
-// arguments the way Solver / EnsembleSolver fill them, launches, downloads. Every index array is the handle's own.
+// arguments the way HostBackend / EnsembleSolver fill them, launches, downloads. Every index array is the handle's own.
 #include "../../include/kinetica_hip.h"
 
 #include <algorithm>
@@ -19,7 +19,7 @@ namespace {
 
 constexpr double SENTINEL = -7.0;   // fills the drift results before a launch: a slot no workgroup wrote shows
 
-struct Pinned {   // the drift test's host target (Solver::h_drift is pinned as well)
+struct Pinned {   // the drift test's host target (HostBackend::h_drift is pinned as well)
   double* p = nullptr;
   explicit Pinned(size_t n) { KIN_HIP(hipHostMalloc((void**)&p, n * sizeof(double), hipHostMallocDefault)); }
   ~Pinned() { if (p) (void)hipHostFree(p); }
@@ -35,7 +35,7 @@ void host_drift(kin_network* h, int64_t n_slots, const double* jv_slots, const d
   d_jdiag.upload(h->host.j_diag, s);
   d_jvs.upload(jv_slots, (size_t)(n_slots * nnz), s);
   d_now.upload(jv_now, (size_t)nnz, s);
-  // slots as Solver::factor_into leaves them: the diagonal of the Jacobian behind each by launch_jac_diag (an unused slot's too, so
+  // slots as HostBackend::factor leaves them: the diagonal of the Jacobian behind each by launch_jac_diag (an unused slot's too, so
   // that every row can be compared; launch_drift_test hands the kernel no pointer for it)
   std::vector<SparseLU::Slot> slots((size_t)n);
   for (int i = 0; i < n; i++) {
@@ -46,7 +46,7 @@ void host_drift(kin_network* h, int64_t n_slots, const double* jv_slots, const d
   }
   KIN_HIP(hipGetLastError());
   for (int i = 0; i < n; i++) slots[i].jd.download(jd + (size_t)i * N, (size_t)N, s);
-  // (a) Solver::restart / resume_chunk: results copied to the pinned host target by the launcher
+  // (a) HostBackend::drift_launch: results copied to the pinned host target by the launcher
   Pinned pin((size_t)LU_MAX_SLOTS + 1);
   std::vector<double> fill((size_t)2 * LU_MAX_SLOTS, SENTINEL);
   std::copy(fill.begin(), fill.begin() + LU_MAX_SLOTS + 1, pin.p);

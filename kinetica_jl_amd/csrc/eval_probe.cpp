@@ -1,7 +1,7 @@
 // kin_eval_probe (declaration and argument layout: include/kinetica_hip.h): the right-hand side, the Jacobian values or the
 // Newton residual once, on the caller's states, through the launchers the integrators use - kin_network::rhs_dev / jac_dev and
-// Solver::launch_residual (path 0), ens_rhs / ens_jac / ens_resid of the lockstep ensemble (path 2). Nothing here computes: the
-// probe uploads, fills the launchers' arguments the way Solver / EnsembleSolver fill them, launches, downloads.
+// HostBackend::launch_residual (path 0), ens_rhs / ens_jac / ens_resid of the lockstep ensemble (path 2). Nothing here computes: the
+// probe uploads, fills the launchers' arguments the way HostBackend / EnsembleSolver fill them, launches, downloads.
 #include "../../include/kinetica_hip.h"
 
 #include <algorithm>

@@ -1,16 +1,24 @@
 // Two things, each written once. (1) The solve driver res_drive<D>: the whole of kin_solve's orchestration (chunk loop, discrete
 // rate updates, save grid, adaptive_solve! retries - reference src/solving/methods.jl:185-303, 717-865; solve_utils.jl:376-424,
-// 435-509) around an integrator D - the controller below, and solver.cpp's host-driven Solver through its HostDriven adapter.
-// (2) The resident integrator's controller ResidentBdf<B>: the BDF integrator that stands in for the reference's CVODE_BDF
-// (the algorithm of solver.cpp: Solver::restart / step / select_order / interpolate, including the LU cache and its guards),
-// against a backend `B` that supplies the vector operations, the Jacobian, the factorisation and the corrector iteration:
-//   * resident.hip compiles it for the device: ONE 512-thread workgroup owns one trajectory for the whole solve - every
-//     thread runs this controller redundantly on identical scalars (reduction results are broadcast), the backend's
+// 435-509) around an integrator D - the controller below, or solver.cpp's HostDriven adapter around it and the explicit mode.
+// (2) The controller ResidentBdf<B>: the BDF integrator that stands in for the reference's CVODE_BDF - restart, warm continuation,
+// step, order selection, dense output, the LU cache's slot policy and its guards (the settings: resident_setup.hpp) -
+// the ONE copy of the step algorithm in the library (oracle/ restates it as its independent check). It runs against a backend
+// `B` that supplies the vector operations, the Jacobian, the factorisation and the corrector iteration. There are four:
+//   * resident.hip (DevBackend) compiles it for the device: ONE 512-thread workgroup owns one trajectory for the whole solve -
+//     every thread runs this controller redundantly on identical scalars (reduction results are broadcast), the backend's
 //     operations are workgroup-wide phases separated by barriers; no host round trip, no kernel boundary per step;
+//   * solver.cpp (HostBackend): the host-driven integrator, the path for large networks - every operation is a launch on the
+//     handle's stream, the corrector a blind batch of launches with one hand-over, the next step enqueued speculatively;
+//   * ensemble.cpp (MemberBackend): one controller per member on a host thread, its operations batched into lockstep rounds;
 //   * tests/native/resident_host.cpp compiles it for the CPU with a sequential backend over the same tables: the
 //     controller's logic is checked without a GPU (test infrastructure, not a product path).
-// The host-driven integrator of solver.cpp stays the path for large networks; both implement the same algorithm with the
-// same constants (the settings: resident_setup.hpp) under the same driver. At the default tolerances (1e-10 / 1e-8) their trajectories agree within the step-sequence
+// Where the backends need different things of the controller, the difference is written down once: ResParams::upd_in_band (when
+// the Newton update is scaled), ResAttempt::bad_pivot (a vanished pivot reported with the corrector's result instead of by
+// factor()), and the operations of a backend whose work is in flight while the controller goes on (ResIsAsync, below):
+// drift_launch / drift_collect in place of drift_check, and attempt_begin at every step attempt.
+// The paths share the algorithm and its constants, not their linear algebra: at the default tolerances (1e-10 / 1e-8) resident and
+// host-driven trajectories agree within the step-sequence
 // tolerance (<= 201 units over the 312 solves of profiles/r05_robustness_resident.jsonl), not bit for bit. At rtol = 1e-10 every
 // implementation runs on the rounding floor of the right-hand side and they differ by the accuracy of their LINEAR ALGEBRA: against
 // a Radau truth (tests/golden/truth_tight_200.npz) the CPU port's pivoted LU lands at rms 61 / max 378 tight units in 4 073
@@ -43,12 +51,14 @@ struct ResParams {
   int32_t n_stops, rate_mode;      // rate_mode 0: static k; 1: k_table[n_stops][R]; 2: Arrhenius at T_stops[n_stops];
                                    // 3: Arrhenius at T(t) of every step attempt (continuous, nodes below)
   const double* tstops;
-  // integrator settings of the resident controller (resident_setup.hpp: res_default_settings; Solver keeps its own members)
+  // integrator settings of the controller, the same fields for every backend (resident_setup.hpp: res_default_settings)
   double lu_band, reuse_rate_max, crate_dy_max, lu_drift_max, newton_frac;
   int64_t crate_max_age, lu_max_age;
   int32_t n_slots, carry_rate;
   int64_t sol_cap;                 // rows of the solution buffer
-  int32_t profile, pad0;           // device: fill ResResult::prof (KIN_RESIDENT_PROFILE)
+  int32_t profile;                 // device: fill ResResult::prof (KIN_RESIDENT_PROFILE)
+  int32_t upd_in_band;             // the Newton update is scaled for a factorisation made at another c (res_update_scale) only
+                                   // when c lies within lu_band of it (the host-driven backend); 0: whenever c differs
   // rate_mode 3: T(t) = linear interpolation of (t_nodes, T_nodes)[n_nodes] in global time (the device kernel's prologue sets
   // them per member from ResTrajDev)
   const double *t_nodes, *T_nodes;
@@ -78,6 +88,16 @@ KIN_HD inline double res_T_of(const double* tn, const double* Tn, int64_t n, dou
 // temperature. Backends without it (the CPU replay of tests/native/resident_host.cpp) compile as before and never run mode 3.
 template <class B, class = void> struct ResHasApplyT { static constexpr bool value = false; };
 template <class B> struct ResHasApplyT<B, decltype((void)static_cast<B*>(nullptr)->apply_T(0.0))> { static constexpr bool value = true; };
+// A backend that enqueues its work and reads results later (solver.cpp's HostBackend) has three operations the synchronous ones
+// do not: attempt_begin(t_new, t_bound) at every step attempt, and the drift guard as drift_launch(max_drift) behind the restart's
+// Jacobian + drift_collect(max_drift) after the next wait, in place of drift_check(max_drift). Detected - as a set: a backend is
+// asynchronous when it has ALL THREE, one of them alone changes nothing - because the CPU replay cannot compile otherwise: the
+// replay sources (tests/native*) are held fixed across a change of this file, so that its tests check the controller and not
+// an edit of their own backend; they know drift_check only.
+template <class B, class = void> struct ResIsAsync { static constexpr bool value = false; };
+template <class B>
+struct ResIsAsync<B, decltype((void)static_cast<B*>(nullptr)->attempt_begin(0.0, 0.0), (void)static_cast<B*>(nullptr)->drift_launch(0.0),
+                              (void)static_cast<B*>(nullptr)->drift_collect(0.0))> { static constexpr bool value = true; };
 
 struct ResStats {
   int64_t n_steps, n_rejected, n_rhs, n_jac, n_factor, n_linsolve, n_newton_fail, n_chunks, n_restarts, n_retries,
@@ -101,15 +121,23 @@ struct ResCorrIn {
   int32_t slot, order;
   double c, upd, rate_max, crate0, tol_first, newton_tol, dy_first_max, ec, ec_m, ec_p, atol, rtol, alpha_o;
 };
-struct ResAttempt { bool done, converged, nonfinite, any_negative, deep_negative; int n_iter; double err, err_m, err_p, crate; };
+// (bad_pivot: a pivot of the factorisation in hand vanished - for a backend whose factor() cannot say so yet, because the
+// flag comes back with the corrector's result)
+struct ResAttempt { bool done, converged, nonfinite, any_negative, deep_negative, bad_pivot; int n_iter; double err, err_m, err_p, crate; };
 constexpr double RES_NEG_DEEP = BDF_NEG_DEEP, RES_NEG_MARK = BDF_NEG_MARK;
+
+// A factorisation made for c_fact used at c: the Newton update is scaled by 2 / (1 + c / c_fact) (CVODE's gamrat correction),
+// if c lies within `band` of c_fact (ResParams::upd_in_band)
+KIN_HD inline double res_update_scale(double c_fact, double c, double band) {
+  return (c_fact != c && fabs(c / c_fact - 1.0) <= band) ? 2.0 / (1.0 + c / c_fact) : 1.0;
+}
 
 // Predictor + corrector iterations until decided: the decisions of newton_decide (step_dev.hpp), taken in sequence.
 // `I` supplies predict_inner / newton_iter_inner (the CPU replay: the backend itself; the device: the phase's own inlined
 // operations, run by all wavefronts).
 template <class I>
 KIN_HD ResAttempt res_corrector_loop(I& b, const ResCorrIn& in, const double* gamma, int n_species) {
-  ResAttempt a{false, false, false, false, false, 0, 0.0, 0.0, 0.0, 1.0};
+  ResAttempt a{false, false, false, false, false, false, 0, 0.0, 0.0, 0.0, 1.0};
   b.predict_inner(in.order, gamma, in.alpha_o, in.atol, in.rtol);
   const double N = (double)n_species;
   double crate = in.crate0, dy_old = 0.0;
@@ -153,7 +181,7 @@ struct ResidentBdf {
   B& b;
   const ResParams& P;
   double gamma[RES_MAX_ORDER + 1], alpha[RES_MAX_ORDER + 1], errc[RES_MAX_ORDER + 2];
-  // integrator state (Solver, solver.cpp)
+  // integrator state
   double t = 0, h_abs = 0, atol = 0, rtol = 0, newton_tol = 0, dtmin = 0, fail_score = 0;
   int order = 1, n_equal = 0, cur_slot = 0;
   bool lu_valid = false, jac_current = false, force_jac_refresh = false, force_fresh_lu = false, cache_suspended = false,
@@ -184,7 +212,7 @@ struct ResidentBdf {
 
   KIN_HD bool continuous() const { return ResHasApplyT<B>::value && P.rate_mode == 3; }
 
-  // rate_mode 3: the rate constants at the conditions of segment-local time tau (Solver::pre_attempt, bdf.py's hook)
+  // rate_mode 3: the rate constants at the conditions of segment-local time tau (bdf.py's hook)
   KIN_HD void rates_at(double tau) {
     if constexpr (ResHasApplyT<B>::value) b.apply_T(res_T_of(P.t_nodes, P.T_nodes, P.n_nodes, seg_origin + tau));
   }
@@ -202,7 +230,7 @@ struct ResidentBdf {
   KIN_HD void eval_jac() { b.eval_jac_y(); st.n_jac++; lu_valid = false; steps_since_jac = 0; jac_stamp_now = st.n_restarts; }
   KIN_HD void predict() { b.predict(order, gamma, alpha[order], atol, rtol); }
 
-  // Warm continuation at a chunk start whose rates did not change (kin_params.solve_chunks == 2; Solver::resume): the system
+  // Warm continuation at a chunk start whose rates did not change (kin_params.solve_chunks == 2): the system
   // is autonomous and chunks run in local time, so difference history, order and step size stay valid. The Jacobian is
   // evaluated at the chunk's first state and the LU cache's drift guard runs, as at a re-initialisation.
   KIN_HD void resume() {
@@ -210,7 +238,19 @@ struct ResidentBdf {
     st.n_restarts++;
     eval_jac();
     jac_current = true;
-    if (P.lu_band > 0.0 && P.lu_drift_max > 0.0) st.n_lu_dropped += b.drift_check(P.lu_drift_max);
+    drift_launch(); drift_collect();
+  }
+  // The LU cache's drift guard, after every fresh Jacobian of a (re)start: the slots are tested against that Jacobian and the
+  // drifted ones dropped. An asynchronous backend launches the test right behind the Jacobian and reads it after the next
+  // wait it has anyway; the others do the whole test when it is collected (where it runs changes no value)
+  KIN_HD bool drift_guard() const { return P.lu_band > 0.0 && P.lu_drift_max > 0.0; }
+  KIN_HD void drift_launch() {
+    if constexpr (ResIsAsync<B>::value) { if (drift_guard()) b.drift_launch(P.lu_drift_max); }
+  }
+  KIN_HD void drift_collect() {
+    if (!drift_guard()) return;
+    if constexpr (ResIsAsync<B>::value) st.n_lu_dropped += b.drift_collect(P.lu_drift_max);
+    else st.n_lu_dropped += b.drift_check(P.lu_drift_max);
   }
 
   // (re)start at segment-local time 0 from the state in y: order 1, fresh Jacobian, CVODE's initial step on the decade grid
@@ -220,9 +260,10 @@ struct ResidentBdf {
     st.n_restarts++;
     eval_jac();
     jac_current = true;
-    if (P.lu_band > 0.0 && P.lu_drift_max > 0.0) st.n_lu_dropped += b.drift_check(P.lu_drift_max);
+    drift_launch();
     b.rhs_y_to_f0(); st.n_rhs++;
     ResNorms n0 = b.norms(false, atol, rtol);
+    drift_collect();
     if (n0.nonfinite) return false;
     const double tdist = fabs(t_bound);
     BdfFirstStep fs = bdf_h0_begin(tdist, tdist, n0.dmax);
@@ -277,7 +318,7 @@ struct ResidentBdf {
     ResCorrIn in;
     const double cf = b.slot_c_fact(cur_slot);
     in.slot = cur_slot; in.order = order; in.c = c;
-    in.upd = cf != c ? 2.0 / (1.0 + c / cf) : 1.0;
+    in.upd = res_update_scale(cf, c, P.upd_in_band ? P.lu_band : bdf_inf());
     in.rate_max = (P.lu_band > 0.0 && !cache_suspended && !slot_is_fresh) ? P.reuse_rate_max : 1.0;
     in.crate0 = P.carry_rate ? b.slot_crate(cur_slot) : 1.0;
     in.tol_first = crate_fresh(cur_slot) ? newton_tol : -1.0;
@@ -287,7 +328,7 @@ struct ResidentBdf {
     return b.corrector(in, gamma);
   }
 
-  // one accepted step towards t_bound (Solver::step without the asynchronous machinery)
+  // one accepted step towards t_bound (what is asynchronous on the host-driven path is inside its backend's operations)
   KIN_HD StepStatus step(double t_bound) {
     bool accepted = false, first_attempt = true;
     double safety = 0.9, err_norm = 0.0, t_new = t;
@@ -311,6 +352,7 @@ struct ResidentBdf {
       h_abs = fabs(hh);
       const double c = hh / alpha[order];
       if (continuous()) rates_at(t_new);
+      if constexpr (ResIsAsync<B>::value) b.attempt_begin(t_new, t_bound);
       bool converged = false;
       if (force_jac_refresh) { predict(); eval_jac(); jac_current = true; force_jac_refresh = false; }
       bool fresh = false, bad = false;
@@ -335,7 +377,7 @@ struct ResidentBdf {
         st.n_rhs += a.n_iter; st.n_linsolve += a.n_iter;
         if (a.n_iter > 1) b.slot_rate(cur_slot, a.crate, st.n_steps, st.n_restarts);
         converged = a.done && a.converged && !a.nonfinite;
-        if (bad) {
+        if (bad || a.bad_pivot) {
           // a pivot of the factorisation in hand vanished (static pivoting): the slot is dropped, the step is retried at
           // half the size from a Jacobian at its own predictor
           b.slot_drop(cur_slot);
@@ -359,7 +401,9 @@ struct ResidentBdf {
       }
       if (!converged || (P.ban_negatives && a.any_negative)) {
         // a failed corrector cuts the step to a quarter and does not count towards the history reset (CVODE: ETACF = 0.25,
-        // history rebuilt only after repeated error-test failures - solver.cpp: cf_eta / cf_resets); a banned negative state
+        // history rebuilt only after repeated error-test failures: after a reset the order-1 predictor is explicit Euler, far
+        // outside the corrector's convergence region at the step sizes of a late, slowly varying solution -
+        // docs/DESIGN_HISTORY.md R4 has the A/B); a banned negative state
         // (isoutofdomain, methods.jl:169-171) halves it and counts
         const double eta = !converged ? 0.25 : 0.5;
         h_abs *= eta;
@@ -424,7 +468,8 @@ struct ResidentBdf {
     b.interp(order, wp, row);
   }
 
-  // ---- what res_drive (below) asks of an integrator; solver.cpp's HostDriven is the other one
+  // ---- what res_drive (below) asks of an integrator; solver.cpp's HostDriven (this controller or the explicit mode, rows into a
+  // buffer that grows) is the other one
   static constexpr bool saves_every_step = false;   // there is always a save grid (resident_setup.hpp: res_has_grid)
   KIN_HD void begin() { set_tols(P.abstol, P.reltol); dtmin = P.dtmin; invalidate_lu(); b.load_u0(); }   // the call's reset, state <- u0
   KIN_HD double time() const { return t; }
@@ -459,7 +504,7 @@ struct ResidentBdf {
 // ---- The solve driver: kin_solve's orchestration around an integrator `d`, written once. Chunk loop in local time, discrete rate
 // updates at tstops with zero-order hold, segments, the per-chunk save grid with its dropped last point, warm chunk starts
 // (solve_chunks == 2) and the adaptive_solve! tolerance retries. `D` integrates and stores: ResidentBdf<B> above (device kernel,
-// CPU replays, lockstep ensemble members) and solver.cpp's HostDriven around Solver. What differs between them is an operation
+// CPU replays, lockstep ensemble members) and solver.cpp's HostDriven. What differs between them is an operation
 // of D: where rows go (save_y / save_interp / retry's rewind), how a segment starts and ends, the host's diagnostics
 // (chunk_begin, attempt_failed). D::saves_every_step: without a save grid (P.L == 0) every accepted step is a row (save_step).
 // The solve's parameters are D's member P, read as d.P at every use: the device kernel's controller lives in LDS, and a copy

@@ -56,8 +56,30 @@ inline ResGrid make_res_grid(const kin_params& p) {
   return g;
 }
 
-// The integrator settings of the LU cache and the carried convergence rate, one definition each: Solver's members (solver.cpp,
-// where each value's reason is written down) and res_default_settings initialise from them
+// The integrator settings of the LU cache and the carried convergence rate, one definition each; res_default_settings puts
+// them into the ResParams of every controller.
+// LU_REUSE_RATE_MAX 0.15: the slowest contraction accepted from a reused factorisation (0.1: C3 11 % slower, in refreshes that
+// were not needed; 0.2: not robust; 0.5: 17 % slower on the C4 ramp).
+// LU_CRATE_MAX_AGE: the remembered rate is trusted for that many accepted steps after it was last measured and never across a
+// restart (new rates, new Jacobian): CVODE resets crate at every linear-solver setup, i.e. at least every 20 steps, with a
+// Jacobian at most 50 steps old. Without a bound a slot whose contraction has degraded is never found out - one-iteration steps
+// measure nothing - and the unconverged iterates pile up in the difference history until the error test collapses the step
+// size (seen on the first segment of the C4 ramp).
+// LU_CRATE_DY_MAX: a first correction larger than this (in error-weight units) always gets a second iteration. If the true
+// contraction is worse than the remembered one - up to the 0.2 that a measurement would still accept - the error left behind is
+// 0.25 dy: 0.2 keeps that at the corrector tolerance. (With 1.0 a static 1 400 K solve of a 1k-species network accepted first
+// corrections of 0.66 units on a stale rate, poisoned its difference history and ended in DtLessThanMin at every tolerance.)
+// LU_MAX_AGE: a slot is offered for that many restarts after its Jacobian was evaluated. Unlimited reuse is UNSAFE: a direction
+// that was stiff when the slot was made (c J ~ 1e6) and is not any more (its species consumed) is damped to nothing by the old
+// matrix - the corrections vanish, the corrector "converges" at once, and both the convergence test and the error test (which
+// only see the corrections) are blind to the component being left at its predictor; the full C4 ramp then ran into
+// DtLessThanMin a few hundred restarts later. CVODE bounds the same staleness by re-evaluating J at least every 50 steps.
+// LU_DRIFT_MAX: at every restart the Jacobian is fresh; one test compares, for every slot, diag(I - c_s J) as it was when the slot
+// was made with what today's Jacobian gives at the same c_s, and slots whose diagonal moved by more than a factor of
+// 1 + LU_DRIFT_MAX (either way) are dropped. For mass-action kinetics a column's off-diagonal entries are bounded by its diagonal
+// (a reactant's loss terms), so the diagonal is a sound proxy for the unsafe case above, which is a change by ORDERS of
+// magnitude. 25 % until round 4; profiles/r05_lu_drift_ab.txt has what that cost (157 of the 307 factorisations of the
+// 100-chunk C3 solve re-made matrices the guard had dropped although the corrector converged with them).
 constexpr double LU_REUSE_RATE_MAX = 0.15, LU_CRATE_DY_MAX = 0.2, LU_DRIFT_MAX = 1.0, LU_BAND = 0.35;
 constexpr int64_t LU_CRATE_MAX_AGE = 10, LU_MAX_AGE = 50;
 constexpr size_t LU_CACHE_MB = 32768;
@@ -75,6 +97,7 @@ inline double lu_env_band(int n_slots) {
 inline void res_default_settings(ResParams& P, int n_slots_max) {
   P.n_slots = std::max(1, std::min(lu_env_slots(RES_MAX_SLOTS), std::min(n_slots_max, RES_MAX_SLOTS)));
   P.lu_band = lu_env_band(P.n_slots);
+  P.upd_in_band = 0;   // (1: the host-driven path, solver.cpp)
   P.reuse_rate_max = LU_REUSE_RATE_MAX;
   P.crate_dy_max = LU_CRATE_DY_MAX;
   P.lu_drift_max = LU_DRIFT_MAX;

@@ -13,8 +13,10 @@
 // order selection from the error estimates one order down/up). oracle/bdf.py restates the
 // same algorithm on the CPU; both are checked against closed-form and high-accuracy truths.
 //
-// The orchestration itself is the solve driver shared with the resident integrator (resident_core.hpp: res_drive); this file
-// holds the integrator it drives here (Solver), the adapter between the two (HostDriven) and what surrounds the loop.
+// Neither the orchestration nor the step algorithm is written here: the solve driver (resident_core.hpp: res_drive) and the
+// BDF controller (ResidentBdf<B>) are shared with the resident integrator and the lockstep ensemble. This file holds the
+// controller's host-driven backend (HostBackend: what an operation of the controller launches, and how its result comes
+// back), the explicit Dormand-Prince mode, the adapter between driver and integrator (HostDriven) and what surrounds the loop.
 //
 // Control flow lives on the host; every vector operation, the RHS, the Jacobian, the LU and
 // the triangular solves are device kernels on one stream. A step attempt enqueues predictor +
@@ -26,7 +28,6 @@
 #include <atomic>
 #include <chrono>
 #include <cmath>
-#include <functional>
 #include <limits>
 #include <thread>
 
@@ -38,74 +39,47 @@ namespace kin {
 
 namespace {
 constexpr double MIN_FACTOR = 0.2, MAX_FACTOR = 10.0;   // the explicit pair's step-size factors (the BDF's rules: bdf_rules.hpp)
-constexpr double INF = std::numeric_limits<double>::infinity();
 }  // namespace
 
-struct Solver {
+struct HostBackend;
+using HostBdf = ResidentBdf<HostBackend>;
+
+// The backend of the host-driven integrator's controller (resident_core.hpp: ResidentBdf<HostBackend>): every operation is a
+// launch (or a few) on the handle's stream; results come back through a pinned control block. What is asynchronous - the
+// deferred accept, the blind corrector batches, the speculatively enqueued next step - lives here and nowhere else.
+struct HostBackend {
   kin_network* h;
+  const ResParams& P;
+  const HostBdf* ctl = nullptr;           // the controller that drives this backend, to read (Solver's constructor sets it)
   int N;
   hipStream_t s;
   SparseLU lu;
   SegPlanDev resid_plan;                  // Newton residual written straight into the permuted solve vector
-  DevBuf<double> D, y, psi, d, scale, f0, f1, ytmp, jv, umax, red;
+  DevBuf<double> D, y, psi, d, scale, f0, f1, ytmp, jv, red;
+  DevBuf<double> chunk_start;             // the chunk's first state, for its retries
   DevBuf<BdfCtrl> ctrl;
   BdfCtrl* hc = nullptr;                  // pinned host mirror: the block of the hand-over last waited for (hc_buf[seq & 1])
   BdfCtrl* hc_buf = nullptr;
   BdfCoef cf;
-  // integrator state
-  double t = 0, h_abs = 0, atol = 0, rtol = 0, newton_tol = 0, dtmin = 0;
-  int order = 1, n_equal = 0;
-  bool lu_valid = false, jac_current = false, ban_negatives = false;
-  // LU cache (CVODE keeps ONE factorisation while gamma drifts < 30 %; with 288 GB of HBM this solver keeps MANY):
-  // factorisations stay resident in slots and are reused - across step-size changes AND across restarts (every chunk
-  // start and rate update replays the same ramp of step sizes) - whenever a slot's c_fact is within `lu_band` of the
-  // current c = h / alpha_k; the Newton update is then scaled by 2 / (1 + c / c_fact) (CVODE's gamrat correction).
-  // A slot is refreshed (Jacobian at the predictor + factorisation at the current c) only when a corrector that used
-  // it fails. lu_slots == 1 and lu_band == 0 give the round-1 behaviour (a new factorisation at every change of c).
-  int lu_slots = 1, cur_slot = 0;
-  double lu_band = 0.0;
-  int64_t use_clock = 0;
-  double fail_score = 0.0;   // leaky count of rejected attempts (history reset at 3, see reset_history)
-  kin_stats st{};
-  int64_t iters_left = 0;
-  // explicit Dormand-Prince 5(4) mode (kin_solve_explicit; SciPy's RK45 is the oracle): stage array K[7][N],
-  // state before the last step (dense output), FSAL derivative in K[0]
-  bool explicit_mode = false;
-  DevBuf<double> rk_K, rk_yold, rk_ynew;
-  double rk_h_last = 0.0;
-  // continuous-rate solves: called with the segment-local time of every step attempt BEFORE the
-  // corrector runs, re-evaluates the rate constants at the conditions of that time
-  std::function<void(double)> pre_attempt;
 
-  explicit Solver(kin_network* hh) : h(hh), N((int)hh->host.N), s(hh->stream) {
+  HostBackend(kin_network* hh, const ResParams& pp) : h(hh), P(pp), N((int)hh->host.N), s(hh->stream) {
     const NetworkHost& H = h->host;
     lu.analyze(N, H.j_ptr, H.j_col, lu_options_for(N), s);
-    {
-      // cache size: KIN_LU_CACHE_SLOTS (default 128), bounded by KIN_LU_CACHE_MB of device memory (resident_setup.hpp). A
-      // restart replays a ramp of step sizes over up to ~12 decades of c; slots sit >= 35 % apart, i.e. ~8 per decade:
-      // the cache must hold the whole ramp (~90 slots), or the cyclic sweep evicts every slot just before its next
-      // use (32 slots: the full C4 run made 405 k factorisations; its first second, a narrower ramp, only 446)
-      size_t budget_mb = lu_env_budget_mb();
-      if (const char* e = getenv("KIN_INJECT_BAD_PIVOT")) inject_bad_pivot_at = atoll(e);
-      if (const char* e = getenv("KIN_SPECULATE")) speculate = atoi(e) != 0;
-      fuse_newton = lu.fused_tri && lu.m > 0 && lu.newton_grid() <= 10;
-      if (const char* e = getenv("KIN_FUSE_NEWTON")) fuse_newton = atoi(e) != 0 && lu.fused_tri && lu.m > 0;
-      if (h->lu_budget_mb > 0) budget_mb = std::min(budget_mb, h->lu_budget_mb);   // a replica's share (capi.cpp: replica_ensemble)
-      const size_t fit = std::max<size_t>(1, budget_mb * 1024 * 1024 / std::max<size_t>(1, lu.slot_bytes()));
-      lu_slots = (int)std::min<size_t>(std::min<size_t>((size_t)lu_env_slots(128), fit), (size_t)LU_MAX_SLOTS);
-      d_jdiag.upload(H.j_diag, s);
-      d_drift.alloc(LU_MAX_SLOTS + 1);
-      KIN_HIP(hipHostMalloc((void**)&h_drift, (LU_MAX_SLOTS + 1) * sizeof(double), hipHostMallocDefault));
-      h_drift[LU_MAX_SLOTS] = 0.0;
-      lu_band = lu_env_band(lu_slots);
-    }
+    if (const char* e = getenv("KIN_INJECT_BAD_PIVOT")) inject_bad_pivot_at = atoll(e);
+    if (const char* e = getenv("KIN_SPECULATE")) speculate = atoi(e) != 0;
+    fuse_newton = lu.fused_tri && lu.m > 0 && lu.newton_grid() <= 10;
+    if (const char* e = getenv("KIN_FUSE_NEWTON")) fuse_newton = atoi(e) != 0 && lu.fused_tri && lu.m > 0;
+    d_jdiag.upload(H.j_diag, s);
+    d_drift.alloc(LU_MAX_SLOTS + 1);
+    KIN_HIP(hipHostMalloc((void**)&h_drift, (LU_MAX_SLOTS + 1) * sizeof(double), hipHostMallocDefault));
+    h_drift[LU_MAX_SLOTS] = 0.0;
     std::vector<int32_t> yl(N), ident(N);
     lu.yloc.download(yl.data(), N, s);
     KIN_HIP(hipStreamSynchronize(s));
     for (int i = 0; i < N; i++) ident[i] = i;
     resid_plan.upload(build_seg_plan(N, H.sp_ptr.data(), yl.data(), H.sp_rxn.data(), nullptr, H.sp_coef.data(), false, ident.data()), s);
     D.alloc((size_t)BDF_D_ROWS * N);
-    y.alloc(N); psi.alloc(N); d.alloc(N); scale.alloc(N); f0.alloc(N); f1.alloc(N); ytmp.alloc(N); umax.alloc(N);
+    y.alloc(N); psi.alloc(N); d.alloc(N); scale.alloc(N); f0.alloc(N); f1.alloc(N); ytmp.alloc(N); chunk_start.alloc(N);
     jv.alloc(H.nnz());
     ctrl.alloc(1);
     red.alloc((size_t)bdf_reduce_slot() * std::max(bdf_reduce_blocks(N), (lu.fused_tri && lu.m > 0) ? lu.newton_grid() : 0));
@@ -125,25 +99,33 @@ struct Solver {
     }
     bdf_fill_coef(cf.gamma, cf.alpha, cf.error_const);
   }
-  ~Solver() { if (hc_buf) (void)hipHostFree(hc_buf); if (hseq) (void)hipHostFree(hseq); if (h_drift) (void)hipHostFree(h_drift); }
+  ~HostBackend() { if (hc_buf) (void)hipHostFree(hc_buf); if (hseq) (void)hipHostFree(hseq); if (h_drift) (void)hipHostFree(h_drift); }
+  HostBackend(const HostBackend&) = delete;
 
-  void set_tols(double a, double r) {
-    atol = a; rtol = r;
-    newton_tol = bdf_newton_tol(rtol);
+  // LU cache (CVODE keeps ONE factorisation while gamma drifts < 30 %; with 288 GB of HBM this solver keeps MANY):
+  // factorisations stay resident in slots and are reused - across step-size changes AND across restarts (every chunk
+  // start and rate update replays the same ramp of step sizes) - whenever a slot's c_fact is within the band of the
+  // current c = h / alpha_k (the rules: the controller; the settings and their reasons: resident_setup.hpp).
+  // Cache size: KIN_LU_CACHE_SLOTS (default 128), bounded by KIN_LU_CACHE_MB of device memory. A restart replays a ramp of
+  // step sizes over up to ~12 decades of c; slots sit >= 35 % apart, i.e. ~8 per decade: the cache must hold the whole ramp
+  // (~90 slots), or the cyclic sweep evicts every slot just before its next use (32 slots: the full C4 run made 405 k
+  // factorisations; its first second, a narrower ramp, only 446)
+  int cache_slots() const {
+    size_t budget_mb = lu_env_budget_mb();
+    if (h->lu_budget_mb > 0) budget_mb = std::min(budget_mb, h->lu_budget_mb);   // a replica's share (capi.cpp: replica_ensemble)
+    const size_t fit = std::max<size_t>(1, budget_mb * 1024 * 1024 / std::max<size_t>(1, lu.slot_bytes()));
+    return (int)std::min<size_t>(std::min<size_t>((size_t)lu_env_slots(128), fit), (size_t)LU_MAX_SLOTS);
   }
 
-  // the reset every call on the handle starts with (solve_entry, integrator_init). The LU cache lives within one call:
-  // identical calls give identical results; nothing pending of an earlier call survives (its solution buffer may be gone)
-  void begin_call(const kin_params& p, bool explicit_solver) {
-    st = kin_stats{};
-    invalidate_lu();
+  // what every call on the handle starts with: nothing pending of an earlier call survives (its solution buffer may be gone)
+  void begin_call() {
     accept_pending = false; accept_copy = nullptr;
     spec = Spec{};
-    explicit_mode = explicit_solver;
-    ban_negatives = p.ban_negatives != 0;
-    dtmin = res_dtmin(p);
-    set_tols(p.abstol, p.reltol);
+    sync_wait_s = 0.0;
+    std::fill(iter_hist, iter_hist + 8, 0);
   }
+  // ... and every segment: no speculative batch, no deferred accept
+  void begin_segment() { spec = Spec{}; flush_accept(); }
 
   // step-end hand-over without a stream synchronisation: the corrector launch that decides the attempt publishes the
   // control block into pinned host memory and bumps `*hseq`; the host spins on it (bounded), else falls back to sync_ctrl()
@@ -195,12 +177,35 @@ struct Solver {
     auto t0 = std::chrono::steady_clock::now();
     KIN_HIP(hipStreamSynchronize(s));
     sync_wait_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    drift_landed = true;
   }
 
-  void rhs(const double* u, double* out) { h->rhs_dev(u, out); st.n_rhs++; }
+  // ---- slot table of the LU cache: SparseLU's slots, allocated on demand up to P.n_slots
+  double slot_c_fact(int i) const { return lu.slots[i].c_fact; }
+  double slot_crate(int i) const { return lu.slots[i].crate; }
+  long long slot_crate_step(int i) const { return lu.slots[i].crate_step; }
+  long long slot_crate_restart(int i) const { return lu.slots[i].crate_restart; }
+  void slot_touch(int i, long long clock) { lu.slots[i].last_use = clock; }
+  void slot_rate(int i, double cr, long long st, long long rs) { SparseLU::Slot& q = lu.slots[i]; q.crate = cr; q.crate_step = st; q.crate_restart = rs; }
+  void slot_drop(int i) { lu.slots[i].valid = false; }
+  void slot_made(int i, double c, long long clock, long long js, long long ss) {
+    SparseLU::Slot& q = lu.slots[i];
+    q.c_fact = c; q.crate = 1.0; q.valid = true; q.last_use = clock; q.jac_stamp = js; q.step_stamp = ss;
+  }
+  void slots_invalidate(bool reset) { for (auto& q : lu.slots) { q.valid = false; if (reset) { q.c_fact = 0.0; q.last_use = 0; } } }
+  int nearest_slot(double c, double band, long long n_restarts, long long max_age, long long n_steps = 0, long long step_age = -1) const {
+    return slot_nearest(lu.slots.data(), (int)lu.slots.size(), c, band, n_restarts, max_age, n_steps, step_age);
+  }
+  // a slot for a new factorisation: an unused or expired one, else a new one (allocated on demand), else the least recently used
+  int victim_slot(long long n_restarts, long long max_age, int n_slots) {
+    const int n = (int)lu.slots.size();
+    const int free_ = slot_first_free(lu.slots.data(), n, n_restarts, max_age);
+    if (free_ >= 0) return free_;
+    if (n < n_slots) { lu.ensure_slots(n + 1, s); return n; }
+    return slot_lru(lu.slots.data(), n);
+  }
 
-  void eval_jac(const double* u) { h->jac_dev(u, jv.p); st.n_jac++; lu_valid = false; steps_since_jac = 0; jac_stamp_now = st.n_restarts; }
-
+  // ---- vectors, right-hand sides, Jacobian
   // The accept of a step (D <- D + d, new difference rows) is deferred and rides in the next step's predictor launch
   // (bdf_accept_predict_kernel: both are one pass over the same columns of D); so does the copy of the new state into
   // the solution buffer when every step is saved. Everything else that reads D calls flush_accept() first.
@@ -212,7 +217,19 @@ struct Solver {
     launch_bdf_accept(N, accept_order, D.p, d.p, accept_copy, s);
     accept_pending = false; accept_copy = nullptr;
   }
-  void predict() {
+  void accept(int order) {
+    if (spec.enq) {   // the device has accepted this step and is computing the next one: nothing is pending
+      spec.alive = true; spec.enq = false;
+      accept_pending = false; accept_copy = nullptr;
+    } else {
+      accept_pending = true; accept_order = order; accept_copy = nullptr;   // rides in the next predictor launch
+    }
+  }
+  void predict(int order, const double*, double, double atol, double rtol) {
+    drop_take_up();
+    launch_predict(order, atol, rtol);
+  }
+  void launch_predict(int order, double atol, double rtol) {
     if (accept_pending) {
       launch_bdf_accept_predict(N, accept_order, order, D.p, cf, atol, rtol, y.p, psi.p, d.p, scale.p, ctrl.p, accept_copy, s);
       accept_pending = false; accept_copy = nullptr;
@@ -224,172 +241,85 @@ struct Solver {
   // copy of that state into `dst` (a row of the solution buffer): rides with the pending accept when there is one
   void save_state(double* dst) {
     if (accept_pending && !accept_copy) accept_copy = dst;
-    else KIN_HIP(hipMemcpyAsync(dst, state_ptr(), (size_t)N * sizeof(double), hipMemcpyDeviceToDevice, s));
+    else copy(dst, state_ptr());
   }
+  void copy(double* dst, const double* src) { KIN_HIP(hipMemcpyAsync(dst, src, (size_t)N * sizeof(double), hipMemcpyDeviceToDevice, s)); }
+  double* row(long long r) { return h->d_sol_u.p + (size_t)r * N; }   // of the handle's solution buffer (HostDriven reserves it)
 
-  void change_D(int ord, double factor) {
+  void chunk_start_from_y() { copy(chunk_start.p, y.p); }
+  // The retried chunk starts from its start state with NEGATIVE entries set to zero. A chunk can inherit concentrations
+  // of -1e-9 (tolerance-sized, 10 x abstol is common) from its predecessor, and mass-action kinetics is unstable under
+  // them - a bimolecular term flips its sign - up to a finite-time blow-up of the exact solution from that state: every
+  // retry then dies at the same local time whatever its tolerances (3k species, 1 500 K: five attempts, all at
+  // t = 7.0e-4). The first attempt of a chunk is untouched (reference semantics); only the rescue path clips.
+  void y_from_chunk_start_clipped() { launch_clip_negative(N, chunk_start.p, y.p, s); }
+  void y_from_D0() { copy(y.p, state_ptr()); }
+  void ytmp_from_D0() { copy(ytmp.p, state_ptr()); }
+  void ytmp_axpy(double h0) { launch_axpy_out(N, y.p, h0, f0.p, ytmp.p, s); }
+  void rhs_y_to_f0() { h->rhs_dev(y.p, f0.p); }
+  void rhs_ytmp_to_f1() { h->rhs_dev(ytmp.p, f1.p); }
+  void rhs_ytmp_to_f0() { h->rhs_dev(ytmp.p, f0.p); }
+  void eval_jac_y() { drop_take_up(); h->jac_dev(y.p, jv.p); }
+  // continuous rates: no launch - the first kernel of the attempt that reads k forms it from this temperature (handle.hpp)
+  void apply_T(double T) { h->set_pending_T(T); }
+  ResNorms norms(bool with_f1, double atol, double rtol) {
+    launch_bdf_norms(N, y.p, f0.p, with_f1 ? f1.p : nullptr, atol, rtol, ctrl.p, s);
+    sync_ctrl();
+    return ResNorms{hc->scratch[0], hc->scratch[1], hc->scratch[2], hc->scratch[3], hc->nonfinite};
+  }
+  void init_D(bool from_ytmp, double hh) {
+    drop_take_up();
+    launch_bdf_init_D(N, BDF_D_ROWS, from_ytmp ? ytmp.p : y.p, f0.p, hh, D.p, s);
+  }
+  void change_D(int ord, const double (*RU)[6]) {
+    drop_take_up();
     flush_accept();
-    double M[6][6], R[6][6], U[6][6];
     BdfMat ru;
-    bdf_change_D_matrix(ord, factor, M, R, U, ru.v);
+    for (int i = 0; i < 6; i++) for (int j = 0; j < 6; j++) ru.v[i][j] = RU[i][j];
     launch_bdf_change_D(N, ord, ru, D.p, s);
   }
-
-  // (re)start the integrator at time t0 from the state in y (reinit! semantics: order 1, fresh
-  // initial step, fresh Jacobian). Returns false when f(y0) is not finite.
-  bool restart(double t0, double t_bound) {
-    spec = Spec{};
+  void interp(int order, const double* p, long long r) {
     flush_accept();
-    t = t0;
-    st.n_restarts++;
-    // the Jacobian of the restart state first (it does not depend on the step size chosen below): the drift test of the
-    // LU cache then rides on the first synchronisation of the restart
-    int n_checked = 0;
-    if (!explicit_mode) {
-      eval_jac(y.p);
-      jac_current = true;
-      if (lu_band > 0.0 && lu_drift_max > 0.0) n_checked = launch_drift_test(N, lu.slots, jv.p, d_jdiag.p, d_drift.p, h_drift, s);
-    }
-    rhs(y.p, f0.p);
-    launch_bdf_norms(N, y.p, f0.p, nullptr, atol, rtol, ctrl.p, s);
-    sync_ctrl();
-    st.n_lu_dropped += drop_drifted(lu.slots, n_checked, h_drift, lu_drift_max);
-    if (hc->nonfinite) return false;
-    const double interval = std::fabs(t_bound - t0);
-    if (explicit_mode) {
-      // the explicit pair keeps SciPy's select_initial_step (its oracle is SciPy's own RK45): exponent 1 / (error order + 1)
-      const double d0 = hc->scratch[0], d1 = hc->scratch[1];
-      double h0 = (d0 < 1e-5 || d1 < 1e-5) ? 1e-6 : 0.01 * d0 / d1;
-      h0 = std::min(h0, interval);
-      launch_axpy_out(N, y.p, h0, f0.p, ytmp.p, s);
-      rhs(ytmp.p, f1.p);
-      launch_bdf_norms(N, y.p, f0.p, f1.p, atol, rtol, ctrl.p, s);
-      sync_ctrl();
-      if (hc->nonfinite) return false;
-      const double d2 = hc->scratch[2] / h0;
-      const double h1 = (d1 <= 1e-15 && d2 <= 1e-15) ? std::max(1e-6, h0 * 1e-3) : std::pow(0.01 / std::max(d1, d2), 0.2);
-      h_abs = std::min({100.0 * h0, h1, interval});
-    } else {
-      // CVODE's initial step on the decade grid (bdf_rules.hpp: bdf_h0_begin / _update / _finish)
-      BdfFirstStep fs = bdf_h0_begin(std::max(std::fabs(t0), std::fabs(t_bound)), interval, hc->scratch[3]);
-      if (fs.iterate()) {
-        for (int count = 1; count <= BDF_H0_EVALS; count++) {
-          launch_axpy_out(N, y.p, fs.hg, f0.p, ytmp.p, s);
-          rhs(ytmp.p, f1.p);
-          launch_bdf_norms(N, y.p, f0.p, f1.p, atol, rtol, ctrl.p, s);
-          sync_ctrl();
-          if (hc->nonfinite) return false;
-          if (bdf_h0_update(fs, count, hc->scratch[2])) break;
-        }
-      }
-      h_abs = bdf_h0_finish(fs, interval);
-    }
-    if (explicit_mode) {
-      rk_K.alloc((size_t)7 * N); rk_yold.alloc(N); rk_ynew.alloc(N);
-      KIN_HIP(hipMemcpyAsync(D.p, y.p, (size_t)N * sizeof(double), hipMemcpyDeviceToDevice, s));          // D[0] = current state
-      KIN_HIP(hipMemcpyAsync(rk_K.p, f0.p, (size_t)N * sizeof(double), hipMemcpyDeviceToDevice, s));      // FSAL: K[0] = f(y0)
-      KIN_HIP(hipMemcpyAsync(rk_yold.p, y.p, (size_t)N * sizeof(double), hipMemcpyDeviceToDevice, s));
-      rk_h_last = 0.0;
-      rk_fsal_pending = false;
-      return true;
-    }
-    launch_bdf_init_D(N, BDF_D_ROWS, y.p, f0.p, h_abs, D.p, s);
-    order = 1;
-    n_equal = 0;
-    fail_score = 0.0;
-    first_selection = true;
-    return true;
+    BdfVec pv;
+    for (int j = 0; j <= BDF_MAX_ORDER; j++) pv.v[j] = p[j];
+    launch_bdf_interp(N, order, D.p, pv, row(r), s);
   }
 
-  // After repeated step failures the interpolated difference history is not trusted any more: drop
-  // to order 1 and rebuild it from f at the current state, keeping the (already reduced) step size -
-  // CVODE's strategy after MXNEF1 error-test failures (oracle/bdf.py: _reset_history).
-  void reset_history() {
-    flush_accept();
-    KIN_HIP(hipMemcpyAsync(ytmp.p, D.p, (size_t)N * sizeof(double), hipMemcpyDeviceToDevice, s));
-    rhs(ytmp.p, f0.p);
-    launch_bdf_init_D(N, BDF_D_ROWS, ytmp.p, f0.p, h_abs, D.p, s);
-    order = 1;
-    n_equal = 0;
-    lu_valid = false;
-    fail_score = 0.0;
-    // three failed attempts in a row: nothing cached is trusted any more either
-    for (auto& q : lu.slots) q.valid = false;
-    force_jac_refresh = true;
+  // ---- drift guard of the LU cache (its reasons: resident_setup.hpp). The test is launched behind the Jacobian of a
+  // restart and read after the synchronisation the restart's norms need anyway; a warm chunk start has none and waits here
+  DevBuf<int32_t> d_jdiag;
+  DevBuf<double> d_drift;
+  double* h_drift = nullptr;     // pinned
+  int n_drift_checked = 0;
+  bool drift_landed = true;      // the stream has been waited for since the last drift test was launched
+  void drift_launch(double) {
+    n_drift_checked = launch_drift_test(N, lu.slots, jv.p, d_jdiag.p, d_drift.p, h_drift, s);
+    drift_landed = false;
+  }
+  int drift_collect(double max_drift) {
+    if (!drift_landed) { KIN_HIP(hipStreamSynchronize(s)); drift_landed = true; }
+    return drop_drifted(lu.slots, n_drift_checked, h_drift, max_drift);
   }
 
-  // Warm continuation at a chunk start with unchanged rates (kin_params.solve_chunks == 2): history, order and step size are
-  // kept; the Jacobian is evaluated at the chunk's first state and the LU cache's drift guard runs as at a restart
-  void resume_chunk() {
-    spec = Spec{};
-    t = 0.0;
-    st.n_restarts++;
-    flush_accept();
-    KIN_HIP(hipMemcpyAsync(y.p, D.p, (size_t)N * sizeof(double), hipMemcpyDeviceToDevice, s));
-    eval_jac(y.p);
-    jac_current = true;
-    if (lu_band > 0.0 && lu_drift_max > 0.0) {
-      const int n_checked = launch_drift_test(N, lu.slots, jv.p, d_jdiag.p, d_drift.p, h_drift, s);
-      KIN_HIP(hipStreamSynchronize(s));
-      st.n_lu_dropped += drop_drifted(lu.slots, n_checked, h_drift, lu_drift_max);
+  // the flag of a vanished pivot arrives with the corrector's control block (ResAttempt::bad_pivot), not here
+  bool factor(int slot, double c, bool keep_diag) {
+    drop_take_up();
+    lu.factor(c, jv.p, slot, &ctrl.p->lu_bad, s);
+    if (keep_diag) {
+      lu.slots[slot].jd.alloc(N);
+      launch_jac_diag(N, jv.p, d_jdiag.p, lu.slots[slot].jd.p, s);
     }
+    return false;
   }
 
-  // CVODE's carried convergence rate: each factorisation remembers the contraction its corrector iterations have shown, and
-  // the first iteration of a step is judged with it (solver_kernels.hip)
+  // ---- the corrector
   // The corrector update folded into the solve's last gather launch (stagec_newton_kernel). One launch less per iteration,
   // but every workgroup of the gather then takes part in the reduction hand-over (partial sums + arrival ticket), and that
   // costs ~0.3 us per workgroup: measured per 20-chunk solve, fused against separate: 300 species 0.101 / 0.110 s, 1 000
   // 0.107-0.110 / 0.116, 2 000 0.139 / 0.138, 5 000 0.204 / 0.174, 10 000 (65 workgroups) 0.572 / 0.449 s per 100 chunks.
   // Default: fused when the fused launch has at most 10 workgroups; KIN_FUSE_NEWTON=1 / 0 forces it on / off.
   bool fuse_newton = false;
-  // The remembered rate is trusted for `crate_max_age` accepted steps after it was last measured and never across a
-  // restart (new rates, new Jacobian): CVODE resets crate at every linear-solver setup, i.e. at least every 20 steps,
-  // with a Jacobian at most 50 steps old. Without a bound a slot whose contraction has degraded is never found out -
-  // one-iteration steps measure nothing - and the unconverged iterates pile up in the difference history until the
-  // error test collapses the step size (seen on the first segment of the C4 ramp).
-  int64_t crate_max_age = LU_CRATE_MAX_AGE;
-  // is the slot's remembered rate fresh enough for the first-iteration test? (it keeps being carried and updated either way)
-  bool crate_fresh(const SparseLU::Slot& q) const {
-    return q.crate < 1.0 && q.crate_restart == st.n_restarts && st.n_steps - q.crate_step <= crate_max_age;
-  }
-  // KIN_CRATE_DYMAX: a first correction larger than this (in error-weight units) always gets a second iteration. If the true
-  // contraction is worse than the remembered one - up to the 0.2 that a measurement would still accept - the error left behind is
-  // 0.25 dy: 0.2 keeps that at the corrector tolerance. (With 1.0 a static 1 400 K solve of a 1k-species network accepted first
-  // corrections of 0.66 units on a stale rate, poisoned its difference history and ended in DtLessThanMin at every tolerance.)
-  double crate_dy_max = LU_CRATE_DY_MAX;
   int last_iters = 0, last_iter_slot = -1;
-  // 0.15, the slowest contraction accepted from a reused factorisation (0.1: C3 11 % slower, in refreshes that were not needed;
-  // 0.2: not robust, see set_tols; 0.5: 17 % slower on the C4 ramp)
-  double reuse_rate_max = LU_REUSE_RATE_MAX;
-  // KIN_LU_MAX_AGE: a slot is offered for that many restarts after its Jacobian was evaluated. Unlimited reuse is
-  // UNSAFE: a direction that was stiff when the slot was made (c J ~ 1e6) and is not any more (its species consumed) is
-  // damped to nothing by the old matrix - the corrections vanish, the corrector "converges" at once, and both the
-  // convergence test and the error test (which only see the corrections) are blind to the component being left at its
-  // predictor; the full C4 ramp then ran into DtLessThanMin a few hundred restarts later (with 5 restarts it runs
-  // through). CVODE bounds the same staleness by re-evaluating J at least every 50 steps.
-  int64_t lu_max_age = LU_MAX_AGE;
-  // Drift guard: at every restart the Jacobian is fresh; one kernel compares, for every slot, diag(I - c_s J) as it was when
-  // the slot was made with what today's Jacobian gives at the same c_s, and slots whose diagonal moved by more than a factor
-  // of 1 + lu_drift_max (either way) are dropped. For mass-action kinetics a column's off-diagonal entries are bounded by its
-  // diagonal (a reactant's loss terms), so the diagonal is a sound proxy for "a direction that was stiff in the slot and is not
-  // any more" - the unsafe case described above, which is a change by ORDERS of magnitude. Rounds 2-4 dropped at 25 %; round 5
-  // measured what that costs (profiles/r05_lu_drift_ab.txt: 157 of the 307 factorisations of the 100-chunk C3 solve re-made
-  // matrices the guard had dropped although the corrector - whose contraction is watched anyway, reuse_rate_max - converged
-  // with them): a factor of 2 keeps the protection and takes 307 -> 242 factorisations, 0.388 -> 0.346 s, C4's 20 chunks
-  // 516 -> 291 and 1.51 -> 1.39 s, deviations from the truths inside the spread of the reuse-band study.
-  double lu_drift_max = LU_DRIFT_MAX;
-  DevBuf<int32_t> d_jdiag;
-  DevBuf<double> d_drift;
-  double* h_drift = nullptr;     // pinned
-  bool cache_suspended = false;  // a tolerance retry (adaptive_solve!) runs its chunk without the cache
-  int64_t jac_stamp_now = 0;     // restart counter at the last Jacobian evaluation
-  bool slot_is_fresh = false;
-  // `last`: the batch's last launch publishes the control block even when nothing is decided yet (seq = the number the
-  // host waits for; the launch that decides publishes it itself - there is no separate error-estimate launch)
-  // `spec_it`: an iteration of a speculatively enqueued step - the carried rate comes from the device's control block (the
-  // host does not know yet what the step before leaves there), it counts as fresh (enqueue_speculative checked that it will
-  // be whatever that step does)
   // the residual pair of a corrector iteration: the rates of y and c f(y) - psi - d into the permuted solve vector inside W;
   // both no-ops once *skip is set (a pending temperature's rate constants are stored all the same)
   void launch_residual(double c, const int* skip, double* W) {
@@ -401,30 +331,30 @@ struct Solver {
     else launch_rates_skip(h->host.R, h->k.p, y.p, h->x0.p, h->x1.p, h->rate.p, skip, s);
     launch_segsum(resid_plan.view(), SEG_COEF_BDF, h->rate.p, W, ex, s);
   }
-  void newton_iteration(int it, double c, unsigned long long seq, bool last, bool spec_it = false) {
+  // `last`: the batch's last launch publishes the control block even when nothing is decided yet (seq = the number the
+  // host waits for; the launch that decides publishes it itself - there is no separate error-estimate launch)
+  // `spec_it`: an iteration of a speculatively enqueued step - the carried rate comes from the device's control block (the
+  // host does not know yet what the step before leaves there)
+  void newton_iteration(int it, const ResCorrIn& in, unsigned long long seq, bool last, bool spec_it = false) {
     const int* skip = &ctrl.p->newton_done;
-    SparseLU::Slot& q = lu.slots[cur_slot];
-    launch_residual(c, skip, q.W.p);
-    // a factorisation made for another c: the update is scaled by 2 / (1 + c / c_fact)
-    const double upd = (q.c_fact != c && std::fabs(c / q.c_fact - 1.0) <= lu_band) ? 2.0 / (1.0 + c / q.c_fact) : 1.0;
-    const double rate_max = (lu_band > 0.0 && !cache_suspended && !slot_is_fresh) ? reuse_rate_max : 1.0;
-    const double crate0 = q.crate, tol_first = (spec_it || crate_fresh(q)) ? newton_tol : -1.0;
-    const bool from_ctrl = spec_it;
+    SparseLU::Slot& q = lu.slots[in.slot];
+    launch_residual(in.c, skip, q.W.p);
     if (fuse_newton) {
       // the solve's last gather stage and the corrector update in one launch
       NewtonFuse f;
       f.skip = skip; f.N = N; f.m = 0; f.off_x = 0; f.x2_species = nullptr;
-      f.scale = scale.p; f.y = y.p; f.d = d.p; f.D = D.p; f.order = order;
-      f.upd = upd; f.atol = atol; f.rtol = rtol;
-      f.ec = cf.error_const[order]; f.ec_m = order > 1 ? cf.error_const[order - 1] : 0.0; f.ec_p = cf.error_const[order + 1];
-      f.iter = it; f.maxit = BDF_NEWTON_MAXITER; f.tol = newton_tol; f.rate_max = rate_max; f.crate0 = crate0;
-      f.tol_first = tol_first; f.dy_first_max = crate_dy_max; f.crate_from_ctrl = from_ctrl ? 1 : 0; f.ban_negatives = ban_negatives ? 1 : 0;
+      f.scale = scale.p; f.y = y.p; f.d = d.p; f.D = D.p; f.order = in.order;
+      f.upd = in.upd; f.atol = in.atol; f.rtol = in.rtol;
+      f.ec = in.ec; f.ec_m = in.ec_m; f.ec_p = in.ec_p;
+      f.iter = it; f.maxit = BDF_NEWTON_MAXITER; f.tol = in.newton_tol; f.rate_max = in.rate_max; f.crate0 = in.crate0;
+      f.tol_first = in.tol_first; f.dy_first_max = in.dy_first_max; f.crate_from_ctrl = spec_it ? 1 : 0; f.ban_negatives = P.ban_negatives ? 1 : 0;
       f.ctrl = ctrl.p; f.part = red.p; f.host_ctrl = hc_dev_at(seq); f.host_seq = hseq_dev; f.seq = seq; f.publish_always = last ? 1 : 0;
-      lu.solve_newton(cur_slot, f, s);
+      lu.solve_newton(in.slot, f, s);
     } else {
-      lu.solve(skip, cur_slot, s);
-      launch_bdf_newton(N, it, BDF_NEWTON_MAXITER, newton_tol, lu.xloc.p, q.W.p, scale.p, y.p, d.p, upd, rate_max, crate0, tol_first,
-                        crate_dy_max, order, D.p, atol, rtol, cf, ctrl.p, red.p, hc_dev_at(seq), hseq_dev, seq, last, s, from_ctrl, ban_negatives);
+      lu.solve(skip, in.slot, s);
+      launch_bdf_newton(N, it, BDF_NEWTON_MAXITER, in.newton_tol, lu.xloc.p, q.W.p, scale.p, y.p, d.p, in.upd, in.rate_max, in.crate0,
+                        in.tol_first, in.dy_first_max, in.order, D.p, in.atol, in.rtol, cf, ctrl.p, red.p, hc_dev_at(seq), hseq_dev, seq, last, s,
+                        spec_it, P.ban_negatives != 0);
     }
   }
 
@@ -433,94 +363,225 @@ struct Solver {
   // accept + predictor launch and its first corrector batch are enqueued right behind this step's batch, before the host has
   // seen this step's result. The deciding corrector launch writes `spec_go` (1 = accepted, by the host's own rule); the
   // speculative predictor does nothing unless it reads 1, and then the iterations behind it stay no-ops as well. The host
-  // takes the batch up when it enters the next step (same arithmetic, bit-identical results) - the device no longer idles
-  // for the hand-over, the host's decision and the launch latency of the next predictor (~8-10 us of ~100 per step).
+  // takes the batch up when the controller asks for the next step's corrector (same arithmetic, bit-identical results) - the
+  // device no longer idles for the hand-over, the host's decision and the launch latency of the next predictor (~8-10 us of
+  // ~100 per step).
   bool speculate = true;
   bool hold_speculation = false;   // set by integrator_step for the LAST step of a call: nothing half-run may outlive the call
   struct Spec {
     bool enq = false;      // a speculative batch sits behind the batch being waited for
-    bool alive = false;    // ... and the device ran it: step() takes it up instead of enqueueing
+    bool alive = false;    // ... and the device ran it: the next corrector takes it up instead of enqueueing
     unsigned long long seq = 0;
     double t_new = 0.0, hh = 0.0, c = 0.0;
     int slot = -1, blind = 0, order = 0;
   } spec;
   int64_t n_spec = 0, n_spec_dead = 0;   // speculative batches taken up / enqueued for nothing (KIN_TIMING=1)
-  // called right after the blind batch of an attempt that ends at t_new (step size h_abs, order, slot cur_slot) is enqueued
-  void enqueue_speculative(double t_new, double t_bound, int blind) {
-    if (!speculate || hold_speculation || !fast_sync || pre_attempt || trace || inject_bad_pivot_at >= 0 || lu_band <= 0.0 || cache_suspended) return;
-    if (n_equal >= order) return;                      // the step after this one may change order / step size
-    if (iters_left < 1) return;
-    const double t2 = t_new + h_abs;
-    if (t2 - t_bound > 0.0) return;                    // would be cut at the segment end
-    if (h_abs < bdf_min_step(dtmin, t_new)) return;
-    const double hh2 = t2 - t_new, c2 = hh2 / cf.alpha[order];
-    if (nearest_slot(c2) != cur_slot) return;          // (the slot can only drop out by the rule that also clears spec_go)
-    const SparseLU::Slot& q = lu.slots[cur_slot];
-    // the carried rate must count as fresh in the next step whether or not this one measures it anew
-    if (!(q.crate < 1.0 && q.crate_restart == st.n_restarts && (st.n_steps + 1) - q.crate_step <= crate_max_age)) return;
-    spec.enq = true; spec.alive = false;
-    spec.t_new = t2; spec.hh = hh2; spec.c = c2; spec.slot = cur_slot; spec.blind = blind; spec.order = order;
-    spec.seq = ++seq_no;
-    launch_bdf_accept_predict(N, order, order, D.p, cf, atol, rtol, y.p, psi.p, d.p, scale.p, ctrl.p, nullptr, s, &ctrl.p->spec_go);
-    const bool keep = slot_is_fresh;
-    slot_is_fresh = q.c_fact == c2;
-    for (int b = 0; b < blind; b++) newton_iteration(b, c2, spec.seq, b == blind - 1, true);
-    slot_is_fresh = keep;
-  }
-  void drop_speculation() { if (spec.enq || spec.alive) n_spec_dead++; spec.enq = false; spec.alive = false; }
-
-  void invalidate_lu_keep_counters() {
-    for (auto& q : lu.slots) q.valid = false;
-    lu_valid = false; cur_slot = 0; force_fresh_lu = false;
-  }
-  void invalidate_lu() {
-    for (auto& q : lu.slots) { q.valid = false; q.c_fact = 0.0; q.last_use = 0; }
-    lu_valid = false; cur_slot = 0; use_clock = 0; attempt_no = 0; force_fresh_lu = false; steps_since_jac = 0; cache_suspended = false;
-  }
-  // slot whose c_fact is closest (in ratio) to c and within the band; -1: none (continuous rate updates: with the bound on
-  // the age of a slot's Jacobian in accepted steps)
-  int nearest_slot(double c) const {
-    return slot_nearest(lu.slots.data(), (int)lu.slots.size(), c, lu_band, st.n_restarts, lu_max_age, st.n_steps,
-                        pre_attempt ? BDF_CONT_JAC_AGE : -1);
-  }
-  // a slot for a new factorisation: an unused or expired one, else a new one (allocated on demand), else the least recently used
-  int victim_slot() {
-    const int n = (int)lu.slots.size();
-    const int free_ = slot_first_free(lu.slots.data(), n, st.n_restarts, lu_max_age);
-    if (free_ >= 0) return free_;
-    if (n < lu_slots) { lu.ensure_slots(n + 1, s); return n; }
-    return slot_lru(lu.slots.data(), n);
-  }
-  // ---- a convergence failure (CVODE: cvHandleNFlag / cvSetEta): a failed corrector cuts the step by ETACF = 0.25 (0.5 until round
-  // 3) and does not count towards the history reset (CVODE rebuilds its history only after repeated ERROR-TEST failures: after a
-  // reset the order-1 predictor is explicit Euler, which at the step sizes of a late, slowly varying solution is far outside the
-  // corrector's convergence region - the complete-timespan C3 solve then halved its step ten more times, each with a
-  // factorisation of its own; docs/DESIGN_HISTORY.md R4 has the A/B and the variants that were measured and dropped: a growth
-  // cap after a failure, a soft step-size ceiling)
-  static constexpr double cf_eta = 0.25;
-  bool force_jac_refresh = false;   // a vanished pivot: the next attempt starts from a Jacobian at its own predictor
-  // After an error-test rejection the retry gets a factorisation made for its own c (CVODE's rule: a failed error test
-  // forces a linear-solver setup): a converged corrector whose matrix was reused carries an iteration error that the
-  // rate estimate may understate, and a rejected step moves on to ever older slots at smaller c - without this rule the
-  // full C4 ramp spiralled into DtLessThanMin once the cache held the whole step-size ramp.
-  bool force_fresh_lu = false;
-  int64_t steps_since_jac = 0;
-  // fault injection for the tests (KIN_INJECT_BAD_PIVOT=n): the n-th step attempt of a solve finds the flag raised, as
+  double att_t_new = 0.0, att_t_bound = 0.0;   // the attempt under way ends at att_t_new, its segment at att_t_bound
+  // fault injection for the tests (KIN_INJECT_BAD_PIVOT=n): the n-th step attempt of a call finds the flag raised, as
   // if its factorisation had met a vanishing pivot (in accuracy-controlled integration of mass-action kinetics that
   // needs c J_ii ~ 1 on an autocatalytic species and practically never happens by itself)
   int64_t inject_bad_pivot_at = -1, attempt_no = 0;
   bool trace = false;   // KIN_TRACE_CHUNK=n: one line per corrector attempt of chunk n (diagnostic)
-  void factor_into(int slot, double c) {
-    lu.factor(c, jv.p, slot, &ctrl.p->lu_bad, s);
-    lu.slots[slot].last_use = ++use_clock;
-    lu.slots[slot].jac_stamp = jac_stamp_now;
-    lu.slots[slot].step_stamp = st.n_steps - steps_since_jac;
-    if (lu_band > 0.0) {
-      lu.slots[slot].jd.alloc(N);
-      launch_jac_diag(N, jv.p, d_jdiag.p, lu.slots[slot].jd.p, s);
+  // the controller's hook: a step attempt begins
+  void attempt_begin(double t_new, double t_bound) {
+    att_t_new = t_new; att_t_bound = t_bound;
+    if (attempt_no++ == inject_bad_pivot_at) KIN_HIP(hipMemsetAsync(&ctrl.p->lu_bad, 1, sizeof(int), s));
+  }
+  // called right after the blind batch of the attempt `in` is enqueued
+  void enqueue_speculative(const ResCorrIn& in, int blind) {
+    if (!speculate || hold_speculation || !fast_sync || ctl->continuous() || trace || inject_bad_pivot_at >= 0 || P.lu_band <= 0.0 ||
+        ctl->cache_suspended) return;
+    if (ctl->n_equal >= in.order) return;              // the step after this one may change order / step size
+    if (ctl->iters_left < 1) return;
+    const double h_abs = ctl->h_abs, t2 = att_t_new + h_abs;
+    if (t2 - att_t_bound > 0.0) return;                // would be cut at the segment end
+    if (h_abs < bdf_min_step(ctl->dtmin, att_t_new)) return;
+    const double hh2 = t2 - att_t_new, c2 = hh2 / cf.alpha[in.order];
+    // (the slot can only drop out by the rule that also clears spec_go)
+    if (nearest_slot(c2, P.lu_band, ctl->st.n_restarts, P.lu_max_age) != in.slot) return;
+    const SparseLU::Slot& q = lu.slots[in.slot];
+    // the carried rate must count as fresh in the next step whether or not this one measures it anew
+    if (!(q.crate < 1.0 && q.crate_restart == ctl->st.n_restarts && (ctl->st.n_steps + 1) - q.crate_step <= P.crate_max_age)) return;
+    spec.enq = true; spec.alive = false;
+    spec.t_new = t2; spec.hh = hh2; spec.c = c2; spec.slot = in.slot; spec.blind = blind; spec.order = in.order;
+    spec.seq = ++seq_no;
+    launch_bdf_accept_predict(N, in.order, in.order, D.p, cf, in.atol, in.rtol, y.p, psi.p, d.p, scale.p, ctrl.p, nullptr, s, &ctrl.p->spec_go);
+    // the next step's attempt as the controller will hand it in, except that its carried rate counts as fresh whatever this
+    // step does (checked above)
+    ResCorrIn in2 = in;
+    in2.c = c2;
+    in2.upd = res_update_scale(q.c_fact, c2, P.lu_band);
+    in2.rate_max = q.c_fact == c2 ? 1.0 : P.reuse_rate_max;
+    in2.tol_first = in.newton_tol;
+    for (int b = 0; b < blind; b++) newton_iteration(b, in2, spec.seq, b == blind - 1, true);
+  }
+  void drop_speculation() { if (spec.enq || spec.alive) n_spec_dead++; spec.enq = false; spec.alive = false; }
+  // an operation between two steps that the speculative batch did not foresee (cannot happen by the rules of
+  // enqueue_speculative; kept as a recovery, not a throw): the device HAS accepted the previous step, so D is current and
+  // nothing is pending - the next corrector re-runs the predictor (which clears the control block) and enqueues a batch of
+  // its own; what the speculative iterations left in y / d is rebuilt by that predictor
+  void drop_take_up() { if (spec.alive) drop_speculation(); }
+
+  // One corrector attempt: predictor + iterations until the device has decided, the next step's batch behind them.
+  ResAttempt corrector(const ResCorrIn& in, const double*) {
+    // Blind depth: two iterations are enqueued ahead of the decision, one when this factorisation converged the previous
+    // step in its first iteration (the carried rate makes that the common case; the second launch chain would be
+    // six no-ops). Whatever is not decided when the host looks gets up to two more iterations per hand-over.
+    int it = 0;
+    int blind = (last_iters == 1 && last_iter_slot == in.slot && ctl->crate_fresh(in.slot)) ? 1 : 2;
+    unsigned long long batch_seq;
+    // this attempt's first batch is on the device already (enqueued speculatively behind the previous step's), if the
+    // controller arrived at the step it was enqueued for
+    if (spec.alive && !(att_t_new == spec.t_new && ctl->h_abs == spec.hh && in.c == spec.c && in.order == spec.order && in.slot == spec.slot))
+      drop_take_up();
+    if (spec.alive) {       // predictor and `blind` iterations of this attempt are running already
+      spec.alive = false;
+      blind = spec.blind; it = blind; batch_seq = spec.seq;
+      n_spec++;
+    } else {
+      launch_predict(in.order, in.atol, in.rtol);
+      batch_seq = ++seq_no;
+      for (int b = 0; b < blind; b++, it++) newton_iteration(it, in, batch_seq, b == blind - 1);
     }
-    cur_slot = slot;
-    st.n_factor++;
+    enqueue_speculative(in, blind);
+    wait_ctrl(batch_seq);
+    while (!hc->newton_done && it < BDF_NEWTON_MAXITER) {
+      if (spec.enq) {       // undecided: the speculative batch behind has ended itself and left newton_done raised
+        KIN_HIP(hipMemsetAsync(&ctrl.p->newton_done, 0, sizeof(int), s));
+        drop_speculation();
+      }
+      const int more = std::min(2, BDF_NEWTON_MAXITER - it);
+      ++seq_no;
+      for (int b = 0; b < more; b++, it++) newton_iteration(it, in, seq_no, b == more - 1);
+      wait_ctrl(seq_no);
+    }
+    if (spec.enq && !(hc->newton_done && hc->spec_go)) drop_speculation();   // the device did not run it either
+    ResAttempt a{};
+    a.done = hc->newton_done != 0; a.converged = hc->converged != 0; a.nonfinite = hc->nonfinite != 0;
+    a.any_negative = hc->any_negative != 0; a.deep_negative = (hc->any_negative & 2) != 0; a.bad_pivot = hc->lu_bad != 0;
+    a.n_iter = hc->n_iter;   // iterations the device executed (blind launches behind the decision are no-ops)
+    a.err = hc->err_norm; a.err_m = hc->err_m_norm; a.err_p = hc->err_p_norm; a.crate = hc->crate;
+    last_iters = (a.done && a.converged) ? a.n_iter : 0;
+    last_iter_slot = in.slot;
+    if (trace)
+      fprintf(stderr, "[trace] t=%.6e h=%.3e order=%d c=%.3e slot=%d c_fact=%.3e slot_fresh=%d jac_cur=%d -> done=%d conv=%d iters=%d dy=%.3e err=%.3e nonfinite=%d lu_bad=%d\n",
+              ctl->t, ctl->h_abs, in.order, in.c, in.slot, lu.slots[in.slot].c_fact, (int)ctl->slot_is_fresh, (int)ctl->jac_current,
+              hc->newton_done, hc->converged, hc->n_iter, hc->dy_norm, hc->err_norm, hc->nonfinite, hc->lu_bad);
+    if (a.bad_pivot) KIN_HIP(hipMemsetAsync(&ctrl.p->lu_bad, 0, sizeof(int), s));   // (cleared by the host, not by the predictor)
+    else if (a.done && a.converged && !a.nonfinite && !(P.ban_negatives && a.any_negative)) iter_hist[std::min(a.n_iter, 7)]++;
+    return a;
+  }
+};
+
+static_assert(ResIsAsync<HostBackend>::value && ResHasApplyT<HostBackend>::value, "the controller must find this backend's own operations");
+
+// What a handle owns for its host-driven solves: the backend, the controller on it (its settings and the call's parameters in
+// P), and the explicit Dormand-Prince 5(4) mode (kin_solve_explicit; SciPy's RK45 is the oracle), which shares the backend's
+// vectors and control block and the controller's scalars (t, h_abs, tolerances, iters_left, the counters).
+struct Solver {
+  ResParams P{};
+  HostBackend b;
+  HostBdf ctl;
+  // explicit mode: stage array K[7][N], state before the last step (dense output), FSAL derivative in K[0]
+  bool explicit_mode = false;
+  DevBuf<double> rk_K, rk_yold, rk_ynew;
+  double rk_h_last = 0.0;
+
+  explicit Solver(kin_network* h) : b(h, P), ctl(b, P) {
+    b.ctl = &ctl;
+    // the controller's settings (resident_setup.hpp), with this path's cache size; the Newton update is scaled for a
+    // factorisation made at another c only inside the reuse band (a matrix kept across an error-test rejection with the cache
+    // off or suspended is used unscaled)
+    res_default_settings(P, LU_MAX_SLOTS);
+    P.n_slots = b.cache_slots();
+    P.lu_band = lu_env_band(P.n_slots);
+    P.upd_in_band = 1;
+  }
+
+  // the reset every call on the handle starts with (solve_entry, integrator_init). The LU cache lives within one call:
+  // identical calls give identical results. `g`: the call's save grid (none: ResGrid{})
+  void begin_call(const kin_params& p, const ResGrid& g, bool explicit_solver) {
+    forget_call();
+    res_fill_params(P, p, g);
+    P.dtmin = res_dtmin(p);
+    P.save_local = g.save_local.empty() ? nullptr : g.save_local.data();
+    explicit_mode = explicit_solver;
+    b.begin_call();
+    ctl.st = ResStats{};
+    reset_cache();
+    ctl.force_jac_refresh = false;
+    ctl.dtmin = P.dtmin;
+    ctl.set_tols(p.abstol, p.reltol);
+  }
+  // continuous rate updates: T(t) = linear interpolation of the nodes in global time (resident_core.hpp: res_T_of), the rate
+  // constants re-evaluated on the device at every step attempt
+  void set_profile(const double* t_nodes, const double* T_nodes, int64_t n_nodes) {
+    P.rate_mode = 3; P.t_nodes = t_nodes; P.T_nodes = T_nodes; P.n_nodes = n_nodes;
+    b.h->has_rates = true;
+  }
+
+  // P points into the call that filled it (its save grid, the caller's stops and profile nodes): nothing of a finished
+  // kin_solve stays behind (CallGuard). An integrator session's pointers are into its own IntegratorState and stay
+  void forget_call() {
+    P.save_local = nullptr; P.L = 0;
+    P.tstops = nullptr; P.n_stops = 0;
+    P.t_nodes = P.T_nodes = nullptr; P.n_nodes = 0;
+    P.rate_mode = 0;
+  }
+  // an empty LU cache; KIN_INJECT_BAD_PIVOT counts its attempts from here (every call, and the probes, which borrow slot 0)
+  void reset_cache() { ctl.invalidate_lu(); b.attempt_no = 0; }
+
+  // the controller's counters and the tolerances a call ended with, for res_stats (resident_setup.hpp)
+  ResResult result(int retcode, double abstol, double reltol) const {
+    ResResult r{};
+    r.retcode = retcode; r.final_abstol = abstol; r.final_reltol = reltol; r.st = ctl.st;
+    return r;
+  }
+
+  // (re)start at segment-local time 0 from the state in y, over a segment whose origin is global time `origin`; `warm`: the
+  // controller's warm continuation, if the mode allows. Returns false when f(y0) is not finite.
+  bool segment_start(double origin, double seg_len, bool warm) {
+    b.begin_segment();
+    if (!explicit_mode) return ctl.segment_start(origin, seg_len, warm);   // (y = D[0] since the segment before ended)
+    ctl.seg_origin = origin;
+    if (ctl.continuous()) ctl.rates_at(0.0);   // rates at the segment start for f0 of the restart
+    return rk_restart(seg_len);
+  }
+  StepStatus step(double t_bound) { return explicit_mode ? rk_step_fsal(t_bound) : ctl.step(t_bound); }
+  void select_order() { if (!explicit_mode) ctl.select_order(); }
+  // dense output of the step that ended at ctl.t into row `row` of the solution buffer
+  void interpolate(double ts, int64_t row) {
+    if (explicit_mode) rk_interpolate(ts, b.row(row));
+    else ctl.interpolate(ts, row);
+  }
+
+  void rhs(const double* u, double* out) { b.h->rhs_dev(u, out); ctl.st.n_rhs++; }
+
+  bool rk_restart(double t_bound) {
+    const int N = b.N;
+    ctl.t = 0.0;
+    ctl.st.n_restarts++;
+    rhs(b.y.p, b.f0.p);
+    const ResNorms n0 = b.norms(false, ctl.atol, ctl.rtol);
+    if (n0.nonfinite) return false;
+    const double interval = std::fabs(t_bound);
+    // the explicit pair keeps SciPy's select_initial_step (its oracle is SciPy's own RK45): exponent 1 / (error order + 1)
+    double h0 = (n0.d0 < 1e-5 || n0.d1 < 1e-5) ? 1e-6 : 0.01 * n0.d0 / n0.d1;
+    h0 = std::min(h0, interval);
+    b.ytmp_axpy(h0);
+    rhs(b.ytmp.p, b.f1.p);
+    const ResNorms n1 = b.norms(true, ctl.atol, ctl.rtol);
+    if (n1.nonfinite) return false;
+    const double d1 = n0.d1, d2 = n1.d2 / h0;
+    const double h1 = (d1 <= 1e-15 && d2 <= 1e-15) ? std::max(1e-6, h0 * 1e-3) : std::pow(0.01 / std::max(d1, d2), 0.2);
+    ctl.h_abs = std::min({100.0 * h0, h1, interval});
+    rk_K.alloc((size_t)7 * N); rk_yold.alloc(N); rk_ynew.alloc(N);
+    b.copy(b.D.p, b.y.p);          // D[0] = current state
+    b.copy(rk_K.p, b.f0.p);        // FSAL: K[0] = f(y0)
+    b.copy(rk_yold.p, b.y.p);
+    rk_h_last = 0.0;
+    rk_fsal_pending = false;
+    return true;
   }
 
   // One accepted explicit step (Dormand & Prince 1980, the RK5(4)7M pair; step-size control as in SciPy's
@@ -534,10 +595,15 @@ struct Solver {
                                    {9017.0 / 3168, -355.0 / 33, 46732.0 / 5247, 49.0 / 176, -5103.0 / 18656}};
     static const double Bw[6] = {35.0 / 384, 0, 500.0 / 1113, 125.0 / 192, -2187.0 / 6784, 11.0 / 84};
     static const double E[7] = {-71.0 / 57600, 0, 71.0 / 16695, -71.0 / 1920, 17253.0 / 339200, -22.0 / 525, 1.0 / 40};
+    const int N = b.N;
+    hipStream_t s = b.s;
+    double& t = ctl.t;
+    double& h_abs = ctl.h_abs;
+    const bool ban_negatives = P.ban_negatives != 0;
     bool rejected = false;
     for (;;) {
-      if (iters_left-- <= 0) return STEP_OK;   // caller checks iters_left < 0 -> MaxIters
-      const double min_step = bdf_min_step(dtmin, t);
+      if (ctl.iters_left-- <= 0) return STEP_OK;   // caller checks iters_left < 0 -> MaxIters
+      const double min_step = bdf_min_step(ctl.dtmin, t);
       if (h_abs < min_step) {
         if (rejected) return STEP_DT_MIN;
         h_abs = min_step;                       // SciPy clips the proposed step to [min_step, max_step] once per step
@@ -546,24 +612,25 @@ struct Solver {
       if (t_new - t_bound > 0.0) t_new = t_bound;
       const double hh = t_new - t;
       h_abs = std::fabs(hh);
-      if (pre_attempt) pre_attempt(t_new);
+      if (ctl.continuous()) ctl.rates_at(t_new);
       RkVec w;
       for (int st_i = 1; st_i < 6; st_i++) {
         for (int j = 0; j < 7; j++) w.v[j] = j < st_i ? hh * A[st_i][j] : 0.0;
-        launch_rk_combine(N, st_i, w, D.p, rk_K.p, ytmp.p, s);
-        rhs(ytmp.p, rk_K.p + (size_t)st_i * N);
+        launch_rk_combine(N, st_i, w, b.D.p, rk_K.p, b.ytmp.p, s);
+        rhs(b.ytmp.p, rk_K.p + (size_t)st_i * N);
       }
       for (int j = 0; j < 7; j++) w.v[j] = j < 6 ? hh * Bw[j] : 0.0;
-      launch_rk_combine(N, 6, w, D.p, rk_K.p, rk_ynew.p, s);
+      launch_rk_combine(N, 6, w, b.D.p, rk_K.p, rk_ynew.p, s);
       rhs(rk_ynew.p, rk_K.p + (size_t)6 * N);
       RkVec e;
       for (int j = 0; j < 7; j++) e.v[j] = hh * E[j];
-      ++seq_no;
-      launch_rk_error(N, e, D.p, rk_ynew.p, rk_K.p, atol, rtol, ctrl.p, red.p, hc_dev_at(seq_no), hseq_dev, seq_no, s);
-      wait_ctrl(seq_no);
+      const unsigned long long seq = ++b.seq_no;
+      launch_rk_error(N, e, b.D.p, rk_ynew.p, rk_K.p, ctl.atol, ctl.rtol, b.ctrl.p, b.red.p, b.hc_dev_at(seq), b.hseq_dev, seq, s);
+      b.wait_ctrl(seq);
+      const BdfCtrl* hc = b.hc;
       if (hc->nonfinite) {
         // SciPy would propagate the NaN; here a non-finite stage is treated like a failed step (halve)
-        h_abs *= 0.5; rejected = true; st.n_rejected++;
+        h_abs *= 0.5; rejected = true; ctl.st.n_rejected++;
         continue;
       }
       const double err = hc->err_norm;
@@ -571,276 +638,49 @@ struct Solver {
         double factor = err == 0.0 ? MAX_FACTOR : std::min(MAX_FACTOR, 0.9 * std::pow(err, -0.2));
         if (rejected) factor = std::min(1.0, factor);
         // accept: y_old <- D[0], D[0] <- y_new, K[0] <- K[6] (FSAL)
-        KIN_HIP(hipMemcpyAsync(rk_yold.p, D.p, (size_t)N * sizeof(double), hipMemcpyDeviceToDevice, s));
-        KIN_HIP(hipMemcpyAsync(D.p, rk_ynew.p, (size_t)N * sizeof(double), hipMemcpyDeviceToDevice, s));
+        b.copy(rk_yold.p, b.D.p);
+        b.copy(b.D.p, rk_ynew.p);
         rk_h_last = hh;
         h_abs *= factor;
         t = t_new;
-        st.n_steps++;
+        ctl.st.n_steps++;
         return STEP_OK;
       }
       h_abs *= (ban_negatives && hc->any_negative && err < 1.0) ? 0.5 : std::max(MIN_FACTOR, 0.9 * std::pow(err, -0.2));
       rejected = true;
-      st.n_rejected++;
+      ctl.st.n_rejected++;
     }
   }
   // the stage derivatives of the accepted step are needed for dense output until the next step starts:
   // the FSAL copy K[0] <- K[6] is therefore done lazily, at the start of the next step
   bool rk_fsal_pending = false;
-
-  // one accepted step towards t_bound (internally retries rejected attempts)
-  StepStatus step(double t_bound) {
-    if (explicit_mode) {
-      if (rk_fsal_pending) {
-        KIN_HIP(hipMemcpyAsync(rk_K.p, rk_K.p + (size_t)6 * N, (size_t)N * sizeof(double), hipMemcpyDeviceToDevice, s));
-        rk_fsal_pending = false;
-      }
-      const StepStatus r = rk_step(t_bound);
-      rk_fsal_pending = true;
-      return r;
+  StepStatus rk_step_fsal(double t_bound) {
+    if (rk_fsal_pending) {
+      b.copy(rk_K.p, rk_K.p + (size_t)6 * b.N);
+      rk_fsal_pending = false;
     }
-    bool accepted = false, first_attempt = true;
-    double safety = 0.9, err_norm = 0.0, t_new = t;
-    // this step's first batch is on the device already (enqueued speculatively behind the previous step's)
-    bool take_up = spec.alive;
-    spec.alive = false; spec.enq = false;
-    while (!accepted) {
-      if (iters_left-- <= 0) return STEP_OK;  // caller checks iters_left < 0 -> MaxIters
-      const double min_step = bdf_min_step(dtmin, t);
-      if (h_abs < min_step) {
-        if (!first_attempt) return STEP_DT_MIN;
-        // a step that merely STARTS below the resolution of t is raised to it (it only fails if
-        // the corrector / error test push it below again)
-        change_D(order, min_step / h_abs);
-        h_abs = min_step;
-        n_equal = 0;
-        lu_valid = false;
-      }
-      first_attempt = false;
-      t_new = t + h_abs;
-      if (t_new - t_bound > 0.0) {
-        t_new = t_bound;
-        change_D(order, std::fabs(t_new - t) / h_abs);
-        n_equal = 0;
-        lu_valid = false;
-      }
-      const double hh = t_new - t;
-      h_abs = std::fabs(hh);
-      const double c = hh / cf.alpha[order];
-      // the speculative batch ran for another step than the one the host arrived at (cannot happen by the rules of
-      // enqueue_speculative; kept as a recovery, not a throw): the device HAS accepted the previous step, so D is current
-      // and nothing is pending - the normal path below re-runs the predictor (which clears the control block) and
-      // enqueues a batch of its own; what the speculative iterations left in y / d is rebuilt by that predictor
-      if (take_up && !(t_new == spec.t_new && hh == spec.hh && c == spec.c && order == spec.order)) { take_up = false; n_spec_dead++; }
-      if (pre_attempt) pre_attempt(t_new);
-      bool converged = false;
-      if (attempt_no++ == inject_bad_pivot_at) KIN_HIP(hipMemsetAsync(&ctrl.p->lu_bad, 1, sizeof(int), s));
-      if (force_jac_refresh) {
-        predict();
-        eval_jac(y.p);
-        jac_current = true;
-        force_jac_refresh = false;
-      }
-      // iteration matrix: the cached factorisation closest to this c, else a new one; `fresh` = made in this attempt
-      // from the Jacobian of this attempt's predictor
-      bool fresh = false;
-      const double lu_band = cache_suspended ? 0.0 : this->lu_band;   // shadows the member for this attempt
-      if (lu_band > 0.0) {
-        const int hit = nearest_slot(c);
-        if (take_up && (hit != spec.slot || force_fresh_lu)) { take_up = false; n_spec_dead++; }   // same recovery
-        if (hit >= 0 && !force_fresh_lu) { cur_slot = hit; lu.slots[hit].last_use = ++use_clock; st.n_lu_reused++; }
-        else {
-          if (force_fresh_lu && !jac_current && steps_since_jac > 20) {   // an old Jacobian is refreshed on the way
-            predict();
-            eval_jac(y.p);
-            jac_current = true;
-          }
-          factor_into(hit >= 0 ? hit : victim_slot(), c);
-          fresh = jac_current;
-        }
-        force_fresh_lu = false;
-      } else if (!lu_valid) {
-        factor_into(0, c);
-        lu_valid = true;
-        fresh = jac_current;
-      }
-      for (;;) {
-        // a matrix made in this attempt for this c counts as fresh even when the Jacobian behind it is a few steps old
-        slot_is_fresh = fresh || lu.slots[cur_slot].c_fact == c;
-        // Blind depth: two iterations are enqueued ahead of the decision, one when this factorisation converged the previous
-        // step in its first iteration (the carried rate makes that the common case; the second launch chain would be
-        // six no-ops). Whatever is not decided when the host looks gets up to two more iterations per hand-over.
-        int it = 0;
-        int blind = (last_iters == 1 && last_iter_slot == cur_slot && crate_fresh(lu.slots[cur_slot])) ? 1 : 2;
-        unsigned long long batch_seq;
-        if (take_up) {          // predictor and `blind` iterations of this attempt are running already
-          take_up = false;
-          blind = spec.blind; it = blind; batch_seq = spec.seq;
-          n_spec++;
-        } else {
-          predict();
-          batch_seq = ++seq_no;
-          for (int b = 0; b < blind; b++, it++) newton_iteration(it, c, batch_seq, b == blind - 1);
-        }
-        enqueue_speculative(t_new, t_bound, blind);
-        wait_ctrl(batch_seq);
-        while (!hc->newton_done && it < BDF_NEWTON_MAXITER) {
-          if (spec.enq) {       // undecided: the speculative batch behind has ended itself and left newton_done raised
-            KIN_HIP(hipMemsetAsync(&ctrl.p->newton_done, 0, sizeof(int), s));
-            drop_speculation();
-          }
-          const int more = std::min(2, BDF_NEWTON_MAXITER - it);
-          ++seq_no;
-          for (int b = 0; b < more; b++, it++) newton_iteration(it, c, seq_no, b == more - 1);
-          wait_ctrl(seq_no);
-        }
-        if (spec.enq && !(hc->newton_done && hc->spec_go)) drop_speculation();   // the device did not run it either
-        st.n_rhs += hc->n_iter; st.n_linsolve += hc->n_iter;   // iterations the device executed (blind launches behind the decision are no-ops)
-        if (hc->n_iter > 1) {        // a rate was measured in this attempt
-          SparseLU::Slot& q = lu.slots[cur_slot];
-          q.crate = hc->crate; q.crate_step = st.n_steps; q.crate_restart = st.n_restarts;
-        }
-        last_iters = (hc->newton_done && hc->converged) ? hc->n_iter : 0;
-        last_iter_slot = cur_slot;
-        converged = hc->newton_done && hc->converged && !hc->nonfinite;
-        if (trace)
-          fprintf(stderr, "[trace] t=%.6e h=%.3e order=%d c=%.3e slot=%d c_fact=%.3e fresh=%d jac_cur=%d -> done=%d conv=%d iters=%d dy=%.3e err=%.3e nonfinite=%d lu_bad=%d\n",
-                  t, h_abs, order, c, cur_slot, lu.slots[cur_slot].c_fact, (int)fresh, (int)jac_current, hc->newton_done, hc->converged,
-                  hc->n_iter, hc->dy_norm, hc->err_norm, hc->nonfinite, hc->lu_bad);
-        if (hc->lu_bad) {
-          // a pivot of the factorisation in hand vanished (static pivoting): whatever the corrector did with it is
-          // discarded, the slot is dropped, and the step is retried at half the size from a fresh Jacobian
-          KIN_HIP(hipMemsetAsync(&ctrl.p->lu_bad, 0, sizeof(int), s));
-          lu.slots[cur_slot].valid = false;
-          lu_valid = false;
-          force_jac_refresh = true;
-          st.n_bad_pivot++;
-          converged = false;
-          break;
-        }
-        if (converged) break;
-        st.n_newton_fail++;
-        if (lu_band > 0.0) {
-          // matrix made for this very step from a current Jacobian: the step itself is too long. Otherwise the
-          // slot is refreshed: Jacobian at the predictor (if not current), factorisation at this c, one retry
-          if (fresh) break;
-          if (!jac_current) {
-            predict();
-            eval_jac(y.p);
-            jac_current = true;
-          }
-          factor_into(cur_slot, c);
-          fresh = true;
-          continue;
-        }
-        if (jac_current) break;
-        predict();
-        eval_jac(y.p);
-        jac_current = true;
-        factor_into(0, c);
-        lu_valid = true;
-      }
-      if (!converged || (ban_negatives && hc->any_negative)) {
-        // a failed corrector cuts the step by cf_eta; isoutofdomain (methods.jl:169-171) halves it and counts like an
-        // error-test failure
-        const bool conv_failure = !converged;
-        const double eta = conv_failure ? cf_eta : 0.5;
-        h_abs *= eta;
-        change_D(order, eta);
-        n_equal = 0;
-        lu_valid = false;
-        st.n_rejected++;
-        first_selection = false;   // (CVODE: any failed attempt sets etamax = 1, the first step's 1e4 is gone)
-        if (!conv_failure) fail_score += 1.0;
-        if (fail_score >= 3.0 && order > 1) reset_history();
-        continue;
-      }
-      iter_hist[std::min(hc->n_iter, 7)]++;
-      // a reused factorisation that needed every allowed iteration is too stale to be offered again
-      if (lu_band > 0.0 && !fresh && hc->n_iter >= BDF_NEWTON_MAXITER) lu.slots[cur_slot].valid = false;
-      safety = bdf_safety(hc->n_iter);
-      err_norm = hc->err_norm;
-      if (err_norm > 1.0) {
-        const double factor = bdf_reject_factor(safety, err_norm, order);
-        h_abs *= factor;
-        change_D(order, factor);
-        n_equal = 0;
-        // without the cache the matrix is kept for the retry (the corrector converged with it; the update is scaled for
-        // the new c); with the cache the retry gets a factorisation of its own
-        force_fresh_lu = lu_band > 0.0;
-        st.n_rejected++;
-        first_selection = false;
-        fail_score += 1.0;
-        if (fail_score >= 3.0 && order > 1) reset_history();
-      } else {
-        if (hc->any_negative & 2) return STEP_UNSTABLE;   // BDF_NEG_DEEP: the negative excursion, given up early
-        accepted = true;
-      }
-    }
-    st.n_steps++;
-    steps_since_jac++;
-    fail_score = std::max(0.0, fail_score - 0.2);
-    n_equal++;
-    t = t_new;
-    if (spec.enq) {   // the device has accepted this step and is computing the next one: nothing is pending
-      spec.alive = true; spec.enq = false;
-      accept_pending = false; accept_copy = nullptr;
-    } else {
-      accept_pending = true; accept_order = order; accept_copy = nullptr;   // rides in the next predictor launch
-    }
-    jac_current = false;
-    pending_order_change = (n_equal >= order + 1);
-    if (pending_order_change) {
-      err_m = order > 1 ? hc->err_m_norm : INF;
-      err_p = order < BDF_MAX_ORDER ? hc->err_p_norm : INF;
-      err_o = err_norm;
-      safety_o = safety;
-    }
-    return STEP_OK;
+    const StepStatus r = rk_step(t_bound);
+    rk_fsal_pending = true;
+    return r;
   }
-
-  // order / step-size selection after an accepted step (done after the dense-output saves,
-  // which need the differences of the step just taken)
-  bool pending_order_change = false, first_selection = false;
-  double err_m = 0, err_p = 0, err_o = 0, safety_o = 0.9;
-  void select_order() {
-    if (explicit_mode || !pending_order_change) return;
-    pending_order_change = false;
-    const BdfOrderChoice ch = bdf_select_order(order, err_m, err_o, err_p, safety_o, first_selection);
-    order += ch.d_order;
-    first_selection = false;
-    h_abs *= ch.factor;
-    change_D(order, ch.factor);
-    n_equal = 0;
-    lu_valid = false;
-  }
-
-  // dense output of the step that ended at t (step size h_abs, differences D of `order`)
-  void interpolate(double ts, double* out) {
-    if (explicit_mode) {
-      // SciPy's RkDenseOutput for RK45: y(t) = y_old + h x sum_j K_j (sum_p P[j][p] x^p), x = (t - t_old) / h
-      static const double P[7][4] = {
-          {1, -8048581381.0 / 2820520608, 8663915743.0 / 2820520608, -12715105075.0 / 11282082432},
-          {0, 0, 0, 0},
-          {0, 131558114200.0 / 32700410799, -68118460800.0 / 10900136933, 87487479700.0 / 32700410799},
-          {0, -1754552775.0 / 470086768, 14199869525.0 / 1410260304, -10690763975.0 / 1880347072},
-          {0, 127303824393.0 / 49829197408, -318862633887.0 / 49829197408, 701980252875.0 / 199316789632},
-          {0, -282668133.0 / 205662961, 2019193451.0 / 616988883, -1453857185.0 / 822651844},
-          {0, 40617522.0 / 29380423, -110615467.0 / 29380423, 69997945.0 / 29380423}};
-      const double x = (ts - (t - rk_h_last)) / rk_h_last;
-      RkVec w;
-      for (int j = 0; j < 7; j++) {
-        double acc = 0.0, xp = x;
-        for (int q = 0; q < 4; q++) { acc += P[j][q] * xp; xp *= x; }
-        w.v[j] = rk_h_last * acc;
-      }
-      launch_rk_combine(N, 7, w, rk_yold.p, rk_K.p, out, s);
-      return;
+  // SciPy's RkDenseOutput for RK45: y(t) = y_old + h x sum_j K_j (sum_p P[j][p] x^p), x = (t - t_old) / h
+  void rk_interpolate(double ts, double* out) {
+    static const double Pd[7][4] = {
+        {1, -8048581381.0 / 2820520608, 8663915743.0 / 2820520608, -12715105075.0 / 11282082432},
+        {0, 0, 0, 0},
+        {0, 131558114200.0 / 32700410799, -68118460800.0 / 10900136933, 87487479700.0 / 32700410799},
+        {0, -1754552775.0 / 470086768, 14199869525.0 / 1410260304, -10690763975.0 / 1880347072},
+        {0, 127303824393.0 / 49829197408, -318862633887.0 / 49829197408, 701980252875.0 / 199316789632},
+        {0, -282668133.0 / 205662961, 2019193451.0 / 616988883, -1453857185.0 / 822651844},
+        {0, 40617522.0 / 29380423, -110615467.0 / 29380423, 69997945.0 / 29380423}};
+    const double x = (ts - (ctl.t - rk_h_last)) / rk_h_last;
+    RkVec w;
+    for (int j = 0; j < 7; j++) {
+      double acc = 0.0, xp = x;
+      for (int q = 0; q < 4; q++) { acc += Pd[j][q] * xp; xp *= x; }
+      w.v[j] = rk_h_last * acc;
     }
-    flush_accept();
-    BdfVec p;
-    bdf_interp_weights(order, ts, t, h_abs, p.v);
-    launch_bdf_interp(N, order, D.p, p, out, s);
+    launch_rk_combine(b.N, 7, w, rk_yold.p, rk_K.p, out, b.s);
   }
 };
 
@@ -850,14 +690,14 @@ struct Solver {
 namespace {
 
 // Whatever way a call that drives the integrator ends (a throw included): no temperature stays pending on the handle (kin_rhs /
-// kin_jac and the batched sweeps would otherwise see rate constants of different temperatures), the hook that captures the
-// call's locals is gone, and no speculative batch is left half-taken-up or held back
+// kin_jac and the batched sweeps would otherwise see rate constants of different temperatures), and no speculative batch is
+// left half-taken-up or held back; a kin_solve (`solve`) also takes its pointers out of the controller's parameters
 struct CallGuard {
-  kin_network* h; Solver& S;
+  kin_network* h; Solver& S; bool solve;
   ~CallGuard() {
-    S.pre_attempt = nullptr;
-    S.spec = Solver::Spec{};
-    S.hold_speculation = false;
+    if (solve) S.forget_call();
+    S.b.spec = HostBackend::Spec{};
+    S.b.hold_speculation = false;
     if (h->k_pending) { try { h->flush_pending_T(h->stream); } catch (...) { h->k_pending = false; } }
   }
 };
@@ -894,8 +734,8 @@ void apply_rates(kin_network* h, const double* T_stops, bool have_table, int64_t
   h->k_pending = false;
 }
 
-// The host-driven integrator as the solve driver sees it (resident_core.hpp: res_drive): Solver integrates, rows go to the
-// handle's solution buffer, which grows, and their times to h->sol_t
+// The host-driven integrator as the solve driver sees it (resident_core.hpp: res_drive): Solver integrates - the controller, or
+// the explicit mode - and rows go to the handle's solution buffer, which grows, and their times to h->sol_t
 struct HostDriven {
   static constexpr bool saves_every_step = true;   // no save grid (saveat = []): every accepted step is a row
   kin_network* h;
@@ -904,73 +744,53 @@ struct HostDriven {
   const double* T_stops;
   bool have_table;
   std::chrono::steady_clock::time_point wall0;
-  int64_t N = h->host.N;
-  hipStream_t s = h->stream;
-  SaveBuf sb{h, (int)N};
-  DevBuf<double> chunk_start;   // the chunk's first state, for its retries
-  double seg_origin = 0.0;      // global time of the current segment's tau = 0 (continuous rates: S.pre_attempt reads it)
+  SaveBuf sb{h, (int)h->host.N};
   // KIN_PROGRESS=<seconds>: a status line on stderr at most that often (the reference's `progress` option drives a progress
-  // bar from the same place, methods.jl:822-827); KIN_TRACE_CHUNK=n: Solver::trace during chunk n
+  // bar from the same place, methods.jl:822-827); KIN_TRACE_CHUNK=n: HostBackend::trace during chunk n
   const double progress_every = getenv("KIN_PROGRESS") ? std::max(1.0, atof(getenv("KIN_PROGRESS"))) : 0.0;
   std::chrono::steady_clock::time_point progress_last = wall0;
   const long long trace_chunk = getenv("KIN_TRACE_CHUNK") ? atoll(getenv("KIN_TRACE_CHUNK")) : -1;
 
   void begin() {}   // (Solver::begin_call and the upload of u0: solve_entry, before the driver)
-  double time() const { return S.t; }
-  int64_t iters() const { return S.iters_left; }
+  double time() const { return S.ctl.t; }
+  int64_t iters() const { return S.ctl.iters_left; }
   StepStatus step(double t_bound) { return S.step(t_bound); }
   void select_order() { S.select_order(); }
   void chunk_begin(int64_t nc) {
-    S.st.n_chunks++;
-    S.cache_suspended = false;
-    S.trace = (nc == trace_chunk);
+    S.b.trace = (nc == trace_chunk);
     if (progress_every > 0.0 &&
         std::chrono::duration<double>(std::chrono::steady_clock::now() - progress_last).count() >= progress_every) {
       progress_last = std::chrono::steady_clock::now();
       fprintf(stderr, "[kin_solve] chunk %lld / %lld, %.1f s, %lld steps, %lld factorisations, %lld restarts\n", (long long)nc,
-              (long long)P.n_chunks, std::chrono::duration<double>(progress_last - wall0).count(), (long long)S.st.n_steps,
-              (long long)S.st.n_factor, (long long)S.st.n_restarts);
+              (long long)P.n_chunks, std::chrono::duration<double>(progress_last - wall0).count(), (long long)S.ctl.st.n_steps,
+              (long long)S.ctl.st.n_factor, (long long)S.ctl.st.n_restarts);
       fflush(stderr);
     }
-    KIN_HIP(hipMemcpyAsync(chunk_start.p, S.y.p, N * sizeof(double), hipMemcpyDeviceToDevice, s));
+    S.ctl.chunk_begin(nc);
   }
-  void attempt_begin(int64_t maxiters) { S.iters_left = maxiters; }
+  void attempt_begin(int64_t maxiters) { S.ctl.attempt_begin(maxiters); }
   void apply_rates(int64_t si) { kin::apply_rates(h, T_stops, have_table, si); }
-  // row `row` (= h->n_saved) at global time tg joins the solution; returns where its state goes
-  double* new_row(int64_t row, double tg) { sb.reserve(row + 1); sb.push_time(tg); return sb.row(row); }
-  void save_y(int64_t row, double tg) { KIN_HIP(hipMemcpyAsync(new_row(row, tg), S.y.p, N * sizeof(double), hipMemcpyDeviceToDevice, s)); }
-  void save_interp(int64_t row, double tl, double tg) { S.interpolate(tl, new_row(row, tg)); }
-  void save_step(int64_t row, double tg) { S.save_state(new_row(row, tg)); }   // (rides in the pending accept)
-  bool segment_start(double origin, double seg_len, bool warm) {
-    seg_origin = origin;
-    if (S.pre_attempt) S.pre_attempt(0.0);   // rates at the segment start for f0 / J of the restart
-    // (carrying the history across RATE UPDATES was built and measured in round 4 - 3 180 rejected steps and 4x the time on the
-    // C4 prefix - and is gone, docs/DESIGN_HISTORY.md R4)
-    if (warm && !S.pre_attempt && !S.explicit_mode) { S.resume_chunk(); return true; }
-    return S.restart(0.0, seg_len);
-  }
+  // row `row` (= h->n_saved) at global time tg joins the solution
+  void new_row(int64_t row, double tg) { sb.reserve(row + 1); sb.push_time(tg); }
+  void save_y(int64_t row, double tg) { new_row(row, tg); S.b.copy(S.b.row(row), S.b.y.p); }
+  void save_interp(int64_t row, double tl, double tg) { new_row(row, tg); S.interpolate(tl, row); }
+  void save_step(int64_t row, double tg) { new_row(row, tg); S.b.save_state(S.b.row(row)); }   // (rides in the pending accept)
+  // (carrying the history across RATE UPDATES was built and measured in round 4 - 3 180 rejected steps and 4x the time on the
+  // C4 prefix - and is gone, docs/DESIGN_HISTORY.md R4)
+  bool segment_start(double origin, double seg_len, bool warm) { return S.segment_start(origin, seg_len, warm); }
   void segment_end(bool failed) {
     // a failed attempt leaves the accept of its last good step (and the copy of that state into the solution buffer, whose
     // time is already recorded) pending: it must not outlive the buffers it points into
-    if (failed) S.flush_accept();
-    else KIN_HIP(hipMemcpyAsync(S.y.p, S.state_ptr(), N * sizeof(double), hipMemcpyDeviceToDevice, s));
+    if (failed) S.b.flush_accept();
+    else S.b.y_from_D0();
   }
   void attempt_failed(int64_t nc, int attempts, int retcode, double t_seg, double abstol, double reltol) {
     if (progress_every > 0.0 || getenv("KIN_TIMING"))
       fprintf(stderr, "[kin_solve] chunk %lld attempt %d failed with retcode %d at local t = %.6e (h = %.3e, order %d); tolerances %.1e / %.1e\n",
-              (long long)nc, attempts, retcode, t_seg + S.t, S.h_abs, S.order, abstol, reltol);
+              (long long)nc, attempts, retcode, t_seg + S.ctl.t, S.ctl.h_abs, S.ctl.order, abstol, reltol);
   }
   void retry(double abstol, double reltol, int64_t rows) {
-    S.set_tols(abstol, reltol);
-    S.st.n_retries++;
-    S.invalidate_lu_keep_counters();
-    S.cache_suspended = true;
-    // The retried chunk starts from its start state with NEGATIVE entries set to zero. A chunk can inherit concentrations
-    // of -1e-9 (tolerance-sized, 10 x abstol is common) from its predecessor, and mass-action kinetics is unstable under
-    // them - a bimolecular term flips its sign - up to a finite-time blow-up of the exact solution from that state: every
-    // retry then dies at the same local time whatever its tolerances (3k species, 1 500 K: five attempts, all at
-    // t = 7.0e-4). The first attempt of a chunk is untouched (reference semantics); only the rescue path clips.
-    launch_clip_negative(N, chunk_start.p, S.y.p, s);
+    S.ctl.retry(abstol, reltol, rows);   // (the chunk's start state, clipped: HostBackend::y_from_chunk_start_clipped)
     h->n_saved = rows;
     h->sol_t.resize((size_t)rows);
   }
@@ -1034,10 +854,18 @@ int solve_entry(kin_network* h, const kin_params& p, const double* u0, const dou
   if (!h->solver) h->solver.reset(new Solver(h));
   Solver& S = *h->solver;
   hipStream_t s = h->stream;
-  CallGuard exit_guard{h, S};
-  S.begin_call(p, explicit_solver);
-  S.sync_wait_s = 0.0;
-  std::fill(S.iter_hist, S.iter_hist + 8, 0);
+  CallGuard exit_guard{h, S, true};
+  // the save grid (resident_setup.hpp; none: every step is saved). save_hits_end true: the chunk end is the last local save point
+  // (the usual case). false (save_interval does not divide the chunk): the final chunk's last output is the dense-output value at
+  // its last local save point. (The reference then also restarts every chunk from integ.sol.u[end] = the state at that last
+  // SAVED point while labelling it as the chunk end - a defect that is not copied: chunks always continue from the state at the
+  // chunk end.)
+  const bool has_grid = res_has_grid(p);
+  const ResGrid grid = has_grid ? make_res_grid(p) : ResGrid{};
+  S.begin_call(p, grid, explicit_solver);
+  S.P.n_stops = (int32_t)n_stops;
+  S.P.tstops = tstops;
+  if (continuous) S.set_profile(t_nodes, T_nodes, n_nodes);
   const bool have_table = variable && k_table != nullptr;
   if (have_table) {
     h->table.upload(k_table, (size_t)n_stops * R, s);
@@ -1047,58 +875,28 @@ int solve_entry(kin_network* h, const kin_params& p, const double* u0, const dou
   // ---- output storage
   h->sol_t.clear();
   h->n_saved = 0;
-  // the save grid (resident_setup.hpp; none: every step is saved). save_hits_end true: the chunk end is the last local save point
-  // (the usual case). false (save_interval does not divide the chunk): the final chunk's last output is the dense-output value at
-  // its last local save point. (The reference then also restarts every chunk from integ.sol.u[end] = the state at that last
-  // SAVED point while labelling it as the chunk end - a defect that is not copied: chunks always continue from the state at the
-  // chunk end.)
-  const bool has_grid = res_has_grid(p);
-  const ResGrid grid = has_grid ? make_res_grid(p) : ResGrid{};
-  ResParams P{};
-  res_fill_params(P, p, grid);
-  P.save_local = grid.save_local.data();
-  P.n_stops = (int32_t)n_stops;
-  P.tstops = tstops;
-  HostDriven drv{h, S, P, T_stops, have_table, wall0};
+  HostDriven drv{h, S, S.P, T_stops, have_table, wall0};
   drv.sb.reserve(has_grid ? grid.cap : 1024);
-  drv.chunk_start.alloc(N);
 
-  // continuous rates: T(t) = linear interpolation of the profile solution (resident_core.hpp), k = calculator(T(t)) re-evaluated
-  // on the device
-  if (continuous) {
-    // (no launch: the first kernel of the attempt that reads k forms it from this temperature, handle.hpp)
-    S.pre_attempt = [&](double tau) { h->set_pending_T(res_T_of(t_nodes, T_nodes, n_nodes, drv.seg_origin + tau)); };
-    h->has_rates = true;
-  } else {
-    S.pre_attempt = nullptr;
-  }
   // initial state
-  S.y.upload(u0, N, s);
+  S.b.y.upload(u0, N, s);
   const ResDriven out = res_drive(drv);
-  const int retcode = out.retcode;
-  S.flush_accept();
+  S.b.flush_accept();
   h->flush_pending_T(s);     // a temperature no kernel has consumed yet: k is what the caller may read next
   KIN_HIP(hipStreamSynchronize(s));
-  S.pre_attempt = nullptr;   // the lambda captures locals of this call
-  S.st.final_abstol = out.abstol;
-  S.st.final_reltol = out.reltol;
-  S.st.lu_dense_dim = S.lu.m; S.st.lu_sparse_rows = S.lu.ns; S.st.lu_rounds = S.lu.nrounds;
-  S.st.lu_nnz = 2 * S.lu.nnzU + S.lu.ns + (int64_t)S.lu.m * S.lu.m;
-  S.st.lu_slots = S.lu_slots;
-  S.force_jac_refresh = false;
-  S.st.wall_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - wall0).count();
-  if (getenv("KIN_TIMING"))
+  const kin_stats st = res_stats(S.result(out.retcode, out.abstol, out.reltol), S.b.lu, S.P.n_slots,
+                                 std::chrono::duration<double>(std::chrono::steady_clock::now() - wall0).count());
+  if (getenv("KIN_TIMING")) {
     fprintf(stderr, "[kin_solve] wall %.4f s, of which blocked in step syncs %.4f s (the rest is host-side enqueue); "
             "step-end hand-overs that fell back to copy + sync: %lld (fast path %s)\n",
-            S.st.wall_seconds, S.sync_wait_s, (long long)S.n_sync_fallbacks, S.fast_sync ? "on" : "off");
-  if (getenv("KIN_TIMING"))
-    fprintf(stderr, "[kin_solve] corrector iterations per converged attempt: 1:%lld 2:%lld 3:%lld 4:%lld\n", (long long)S.iter_hist[1],
-            (long long)S.iter_hist[2], (long long)S.iter_hist[3], (long long)S.iter_hist[4]);
-  if (getenv("KIN_TIMING"))
+            st.wall_seconds, S.b.sync_wait_s, (long long)S.b.n_sync_fallbacks, S.b.fast_sync ? "on" : "off");
+    fprintf(stderr, "[kin_solve] corrector iterations per converged attempt: 1:%lld 2:%lld 3:%lld 4:%lld\n", (long long)S.b.iter_hist[1],
+            (long long)S.b.iter_hist[2], (long long)S.b.iter_hist[3], (long long)S.b.iter_hist[4]);
     fprintf(stderr, "[kin_solve] speculatively enqueued steps taken up: %lld of %lld steps, enqueued for nothing: %lld\n",
-            (long long)S.n_spec, (long long)S.st.n_steps, (long long)S.n_spec_dead);
-  if (stats) *stats = S.st;
-  return retcode;
+            (long long)S.b.n_spec, (long long)st.n_steps, (long long)S.b.n_spec_dead);
+  }
+  if (stats) *stats = st;
+  return out.retcode;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1129,9 +927,8 @@ void integrator_init(kin_network* h, const kin_params& p, const double* u0, cons
   Solver& S = *h->solver;
   IntegratorState& I = *h->integ;
   hipStream_t s = h->stream;
-  S.begin_call(p, false);
-  S.pre_attempt = nullptr;
-  S.iters_left = p.maxiters;
+  S.begin_call(p, ResGrid{}, false);
+  S.ctl.attempt_begin(p.maxiters);
   I = IntegratorState{};
   I.have_table = variable && k_table != nullptr;
   if (I.have_table) { h->table.upload(k_table, (size_t)n_stops * R, s); h->table_rows = n_stops; }
@@ -1142,17 +939,17 @@ void integrator_init(kin_network* h, const kin_params& p, const double* u0, cons
   if (continuous) {
     I.t_nodes.assign(t_nodes, t_nodes + n_nodes);
     I.T_nodes.assign(T_nodes, T_nodes + n_nodes);
-    h->has_rates = true;
+    S.set_profile(I.t_nodes.data(), I.T_nodes.data(), n_nodes);   // (the integrator's span starts at global time t_loc0)
   }
   I.t_loc0 = chunks ? 0.0 : p.tspan0;
   I.t_loc1 = chunks ? p.solve_chunkstep : p.tspan1;
   I.t_seg = I.t_loc0;
-  S.y.upload(u0, N, s);
+  S.b.y.upload(u0, N, s);
   // rates in force at the start (the driver's rules, resident_core.hpp)
   I.stop_i = res_stops_passed(I.tstops.data(), n_stops, 0, chunks ? 0.0 : p.tspan0);
   if (variable) apply_rates(h, I.T_stops.data(), I.have_table, res_rates_at_stop(I.stop_i));
   I.active = true;
-  S.t = 0.0;
+  S.ctl.t = 0.0;
   KIN_HIP(hipStreamSynchronize(s));
 }
 
@@ -1162,36 +959,28 @@ int64_t integrator_step(kin_network* h, int64_t max_steps) {
   Solver& S = *h->solver;
   IntegratorState& I = *h->integ;
   hipStream_t s = h->stream;
-  const int64_t N = h->host.N;
   int64_t taken = 0;
-  // continuous rate updates: the Arrhenius rates are re-evaluated at T(global time) of every step attempt, as in
-  // solve_entry (the integrator's span starts at global time t_loc0, its segments run in local time)
-  if (!I.t_nodes.empty())
-    S.pre_attempt = [h, &I](double tau) {
-      h->set_pending_T(res_T_of(I.t_nodes.data(), I.T_nodes.data(), (int64_t)I.t_nodes.size(), I.t_seg + tau));
-    };
-  CallGuard exit_guard{h, S};
+  CallGuard exit_guard{h, S, false};
   while (I.retcode == KIN_RETCODE_SUCCESS && I.t_seg < I.t_loc1 && (max_steps <= 0 || taken < max_steps)) {
     if (!I.in_segment) {
       I.seg = res_segment_end(I.tstops.data(), (int64_t)I.tstops.size(), I.stop_i, I.t_loc1, 0.0, I.t_loc1);   // (local = global time)
-      if (S.pre_attempt) S.pre_attempt(0.0);   // rates at the segment start for f0 / J of the restart
-      if (!S.restart(0.0, I.seg.end - I.t_seg)) { I.retcode = KIN_RETCODE_UNSTABLE; break; }
+      if (!S.segment_start(I.t_seg, I.seg.end - I.t_seg, false)) { I.retcode = KIN_RETCODE_UNSTABLE; break; }
       I.in_segment = true;
     }
     const double seg_len = I.seg.end - I.t_seg;
     // the last step of this call gets no speculative batch behind it: other entry points on the handle (kin_set_rates,
     // kin_rates_at, kin_newton_solve) may run before the next call and must not find a half-run step
-    S.hold_speculation = max_steps > 0 && taken + 1 >= max_steps;
+    S.b.hold_speculation = max_steps > 0 && taken + 1 >= max_steps;
     const StepStatus ss = S.step(seg_len);
-    I.retcode = res_step_retcode(ss, S.iters_left);
-    if (I.retcode != KIN_RETCODE_SUCCESS) { S.flush_accept(); break; }
+    I.retcode = res_step_retcode(ss, S.ctl.iters_left);
+    if (I.retcode != KIN_RETCODE_SUCCESS) { S.b.flush_accept(); break; }
     S.select_order();
     taken++;
-    if (S.t >= seg_len) {   // segment finished: state = D[0]; switch the rates at a tstop
-      KIN_HIP(hipMemcpyAsync(S.y.p, S.state_ptr(), N * sizeof(double), hipMemcpyDeviceToDevice, s));
+    if (S.ctl.t >= seg_len) {   // segment finished: state = D[0]; switch the rates at a tstop
+      S.b.y_from_D0();
       I.t_seg = I.seg.end;
       I.in_segment = false;
-      S.t = 0.0;
+      S.ctl.t = 0.0;
       if (I.seg.at_stop) { apply_rates(h, I.T_stops.data(), I.have_table, I.stop_i); I.stop_i++; }
     }
   }
@@ -1204,14 +993,16 @@ void integrator_state(kin_network* h, double* t, double* u, int32_t* retcode, ki
   if (!h->integ || !h->integ->active) throw KinError(ERR_STATE, "no integrator: call kin_integrator_init first");
   Solver& S = *h->solver;
   IntegratorState& I = *h->integ;
-  if (t) *t = I.in_segment ? I.t_seg + S.t : I.t_seg;
+  if (t) *t = I.in_segment ? I.t_seg + S.ctl.t : I.t_seg;
   if (u) {
-    if (I.in_segment) S.flush_accept();
-    (I.in_segment ? S.D : S.y).download(u, h->host.N, h->stream);   // D[0] = state after the last accepted step
+    if (I.in_segment) S.b.flush_accept();
+    (I.in_segment ? S.b.D : S.b.y).download(u, h->host.N, h->stream);   // D[0] = state after the last accepted step
     KIN_HIP(hipStreamSynchronize(h->stream));
   }
   if (retcode) *retcode = I.retcode;
-  if (stats) { *stats = S.st; stats->final_abstol = S.atol; stats->final_reltol = S.rtol; }
+  // the counters and the tolerances in force; the analysis' sizes, the cache size and the wall time are kin_solve's to report
+  struct { int m = 0, ns = 0, nrounds = 0; int64_t nnzU = 0; } no_analysis;
+  if (stats) *stats = res_stats(S.result(I.retcode, S.ctl.atol, S.ctl.rtol), no_analysis, 0, 0.0);
 }
 
 void solution_max(kin_network* h, double* out_umax) {
@@ -1228,35 +1019,34 @@ void newton_solve(kin_network* h, double c, const double* u, const double* b, do
   if (!h->solver) h->solver.reset(new Solver(h));
   Solver& S = *h->solver;
   hipStream_t s = h->stream;
-  const int N = S.N;
-  S.flush_accept();
-  S.spec = Solver::Spec{};
-  S.y.upload(u, N, s);
-  S.eval_jac(S.y.p);
-  S.lu.factor(c, S.jv.p, 0, &S.ctrl.p->lu_bad, s);
-  S.cur_slot = 0;
+  const int N = S.b.N;
+  S.b.begin_segment();
+  S.b.y.upload(u, N, s);
+  S.ctl.eval_jac();
+  S.b.lu.factor(c, S.b.jv.p, 0, &S.b.ctrl.p->lu_bad, s);
+  S.ctl.cur_slot = 0;
   std::vector<int32_t> yl(N), xl(N);
-  S.lu.yloc.download(yl.data(), N, s);
-  S.lu.xloc.download(xl.data(), N, s);
-  std::vector<double> W(S.lu.w_size);
+  S.b.lu.yloc.download(yl.data(), N, s);
+  S.b.lu.xloc.download(xl.data(), N, s);
+  std::vector<double> W(S.b.lu.w_size);
   KIN_HIP(hipStreamSynchronize(s));
   std::vector<double> stage(N);
   // the solve vectors live at the tail of W: write b there element by element
-  std::vector<double> tail((size_t)(S.lu.off_x + S.lu.mpad + 8 - S.lu.off_y), 0.0);   // the solve vectors only
-  for (int i = 0; i < N; i++) tail[yl[i] - S.lu.off_y] = b[i];
-  KIN_HIP(hipMemcpyAsync(S.lu.slots[0].W.p + S.lu.off_y, tail.data(), tail.size() * sizeof(double), hipMemcpyHostToDevice, s));
-  S.lu.solve(nullptr, 0, s);
-  KIN_HIP(hipMemcpyAsync(tail.data(), S.lu.slots[0].W.p + S.lu.off_y, tail.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+  std::vector<double> tail((size_t)(S.b.lu.off_x + S.b.lu.mpad + 8 - S.b.lu.off_y), 0.0);   // the solve vectors only
+  for (int i = 0; i < N; i++) tail[yl[i] - S.b.lu.off_y] = b[i];
+  KIN_HIP(hipMemcpyAsync(S.b.lu.slots[0].W.p + S.b.lu.off_y, tail.data(), tail.size() * sizeof(double), hipMemcpyHostToDevice, s));
+  S.b.lu.solve(nullptr, 0, s);
+  KIN_HIP(hipMemcpyAsync(tail.data(), S.b.lu.slots[0].W.p + S.b.lu.off_y, tail.size() * sizeof(double), hipMemcpyDeviceToHost, s));
   int bad = 0;
-  KIN_HIP(hipMemcpyAsync(&bad, &S.ctrl.p->lu_bad, sizeof(int), hipMemcpyDeviceToHost, s));
+  KIN_HIP(hipMemcpyAsync(&bad, &S.b.ctrl.p->lu_bad, sizeof(int), hipMemcpyDeviceToHost, s));
   KIN_HIP(hipStreamSynchronize(s));
-  S.invalidate_lu();
+  S.reset_cache();
   if (bad) {
-    KIN_HIP(hipMemsetAsync(&S.ctrl.p->lu_bad, 0, sizeof(int), s));
+    KIN_HIP(hipMemsetAsync(&S.b.ctrl.p->lu_bad, 0, sizeof(int), s));
     KIN_HIP(hipStreamSynchronize(s));
     throw KinError(ERR_SOLVE_FAILED, "vanishing pivot in the factorisation of I - c J (static diagonal pivoting)");
   }
-  for (int i = 0; i < N; i++) x[i] = tail[xl[i] - S.lu.off_y];
+  for (int i = 0; i < N; i++) x[i] = tail[xl[i] - S.b.lu.off_y];
 }
 
 // Diagnostic counterpart of resident_probe for the host-driven path: K Newton-matrix solves through the solver's own analysis
@@ -1267,11 +1057,10 @@ void newton_probe(kin_network* h, int64_t K, int32_t batched, const double* u, c
                   int32_t* bad, int64_t* info) {
   if (!h->solver) h->solver.reset(new Solver(h));
   Solver& S = *h->solver;
-  SparseLU& lu = S.lu;
+  SparseLU& lu = S.b.lu;
   hipStream_t s = h->stream;
-  const int N = S.N;
-  S.flush_accept();
-  S.spec = Solver::Spec{};
+  const int N = S.b.N;
+  S.b.begin_segment();
   const int G = (int)std::min<int64_t>(K, GJ_BMAX);
   lu.ensure_slots(G, s);
   DevBuf<int> d_bad;                        // one flag word per member
@@ -1291,10 +1080,10 @@ void newton_probe(kin_network* h, int64_t K, int32_t batched, const double* u, c
     for (int i = 0; i < n; i++) {
       const int64_t t = g0 + i;
       SparseLU::Slot& q = lu.slots[i];
-      S.y.upload(u + t * N, N, s);
-      S.eval_jac(S.y.p);
-      if (batched) lu.factor_sparse_into(c[t], S.jv.p, q, d_bad.p + t, s);
-      else lu.factor_into(c[t], S.jv.p, q, lu.pinv.p, d_bad.p + t, s);
+      S.b.y.upload(u + t * N, N, s);
+      S.ctl.eval_jac();
+      if (batched) lu.factor_sparse_into(c[t], S.b.jv.p, q, d_bad.p + t, s);
+      else lu.factor_into(c[t], S.b.jv.p, q, lu.pinv.p, d_bad.p + t, s);
       Sp[i] = q.W.p + lu.off_S; S2p[i] = q.S2.p; badp[i] = d_bad.p + t;
     }
     if (batched && lu.m > 0) {
@@ -1318,8 +1107,8 @@ void newton_probe(kin_network* h, int64_t K, int32_t batched, const double* u, c
   d_bad.zero(s);
   KIN_HIP(hipStreamSynchronize(s));
   for (int64_t t = 0; t < K; t++) bad[t] = hb[t] ? 1 : 0;
-  S.cur_slot = 0;
-  S.invalidate_lu();
+  S.ctl.cur_slot = 0;
+  S.reset_cache();
   info[0] = lu.ns; info[1] = lu.m; info[2] = lu.mpad; info[3] = lu.nrounds;
   info[4] = lu.fused_tri ? 0 : lu.explicit_tri ? 1 : 2;
   // whole-workgroup rows and the longest row over every gather plan of the analysis, read back from the plans on the device
@@ -1345,16 +1134,15 @@ void newton_probe(kin_network* h, int64_t K, int32_t batched, const double* u, c
 void step_probe_fused(kin_network* h, double c, const double* u, const double* b, NewtonFuse& f, double* x, int64_t* info) {
   if (!h->solver) h->solver.reset(new Solver(h));
   Solver& S = *h->solver;
-  SparseLU& lu = S.lu;
+  SparseLU& lu = S.b.lu;
   if (!(lu.fused_tri && lu.m > 0)) throw KinError(ERR_UNSUPPORTED, "the analysis of this network has no fused solve with a dense block");
   hipStream_t s = h->stream;
-  const int N = S.N;
-  S.flush_accept();
-  S.spec = Solver::Spec{};
+  const int N = S.b.N;
+  S.b.begin_segment();
   lu.ensure_slots(1, s);
-  S.y.upload(u, N, s);
-  S.eval_jac(S.y.p);
-  lu.factor(c, S.jv.p, 0, &f.ctrl->lu_bad, s);   // (the flag of a vanished pivot goes where the integrator puts it)
+  S.b.y.upload(u, N, s);
+  S.ctl.eval_jac();
+  lu.factor(c, S.b.jv.p, 0, &f.ctrl->lu_bad, s);   // (the flag of a vanished pivot goes where the integrator puts it)
   std::vector<int32_t> yl(N), xl(N);
   lu.yloc.download(yl.data(), N, s);
   lu.xloc.download(xl.data(), N, s);
@@ -1362,7 +1150,7 @@ void step_probe_fused(kin_network* h, double c, const double* u, const double* b
   std::vector<double> tail((size_t)(lu.off_x + lu.mpad + 8 - lu.off_y), 0.0);   // the solve vectors only
   for (int i = 0; i < N; i++) tail[yl[i] - lu.off_y] = b[i];
   KIN_HIP(hipMemcpyAsync(lu.slots[0].W.p + lu.off_y, tail.data(), tail.size() * sizeof(double), hipMemcpyHostToDevice, s));
-  f.N = N; f.skip = &f.ctrl->newton_done; f.part = S.red.p;
+  f.N = N; f.skip = &f.ctrl->newton_done; f.part = S.b.red.p;
   lu.solve_newton(0, f, s);
   KIN_HIP(hipMemcpyAsync(tail.data(), lu.slots[0].W.p + lu.off_y, tail.size() * sizeof(double), hipMemcpyDeviceToHost, s));
   const SegPlanDev& p = lu.stageC;
@@ -1378,48 +1166,47 @@ void step_probe_fused(kin_network* h, double c, const double* u, const double* b
   for (int q = 0; q < p.B; q++) max_row = std::max<int64_t>(max_row, be[q] - bb[q]);
   info[0] = p.G; info[1] = p.S; info[2] = s_long; info[3] = p.B; info[4] = max_row; info[5] = lu.m;
   info[6] = lu.newton_grid(); info[7] = stagec_newton_wg(p.view());
-  S.cur_slot = 0;
-  S.invalidate_lu();
+  S.ctl.cur_slot = 0;
+  S.reset_cache();
 }
 
 // kin_eval_probe, path 0: the residual pair as newton_iteration launches it, on the caller's y, psi, d and flag value
 EvalResidPlan eval_probe_solver_plan(kin_network* h) {
   if (!h->solver) h->solver.reset(new Solver(h));
   Solver& S = *h->solver;
-  return EvalResidPlan{&S.resid_plan, S.lu.yloc.p, S.lu.off_y, S.lu.off_vec_end - S.lu.off_y};
+  return EvalResidPlan{&S.b.resid_plan, S.b.lu.yloc.p, S.b.lu.off_y, S.b.lu.off_vec_end - S.b.lu.off_y};
 }
 void eval_probe_solver_resid(kin_network* h, const double* u, double c, const double* psi, const double* d, int done, double sentinel,
                              double* vec, double* rate) {
   const EvalResidPlan pl = eval_probe_solver_plan(h);
   Solver& S = *h->solver;
-  SparseLU& lu = S.lu;
+  SparseLU& lu = S.b.lu;
   hipStream_t s = h->stream;
-  const int N = S.N;
+  const int N = S.b.N;
   const int64_t R = h->host.R;
-  S.flush_accept();
-  S.spec = Solver::Spec{};
+  S.b.begin_segment();
   lu.ensure_slots(1, s);
   double* W = lu.slots[0].W.p;
   // what the probe overwrites and a solve expects as it left it: the solve vectors of slot 0 and the control block
   std::vector<double> keep((size_t)pl.vec_len), fill((size_t)std::max<int64_t>(pl.vec_len, R), sentinel);
   BdfCtrl keep_ctrl, c_in{};
   KIN_HIP(hipMemcpyAsync(keep.data(), W + pl.off_y, keep.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-  KIN_HIP(hipMemcpyAsync(&keep_ctrl, S.ctrl.p, sizeof(BdfCtrl), hipMemcpyDeviceToHost, s));
+  KIN_HIP(hipMemcpyAsync(&keep_ctrl, S.b.ctrl.p, sizeof(BdfCtrl), hipMemcpyDeviceToHost, s));
   KIN_HIP(hipStreamSynchronize(s));
   c_in.newton_done = done;
-  KIN_HIP(hipMemcpyAsync(S.ctrl.p, &c_in, sizeof(BdfCtrl), hipMemcpyHostToDevice, s));
+  KIN_HIP(hipMemcpyAsync(S.b.ctrl.p, &c_in, sizeof(BdfCtrl), hipMemcpyHostToDevice, s));
   KIN_HIP(hipMemcpyAsync(W + pl.off_y, fill.data(), (size_t)pl.vec_len * sizeof(double), hipMemcpyHostToDevice, s));
   if (R > 0) KIN_HIP(hipMemcpyAsync(h->rate.p, fill.data(), (size_t)R * sizeof(double), hipMemcpyHostToDevice, s));
-  S.y.upload(u, N, s); S.psi.upload(psi, N, s); S.d.upload(d, N, s);
-  S.launch_residual(c, &S.ctrl.p->newton_done, W);
+  S.b.y.upload(u, N, s); S.b.psi.upload(psi, N, s); S.b.d.upload(d, N, s);
+  S.b.launch_residual(c, &S.b.ctrl.p->newton_done, W);
   KIN_HIP(hipGetLastError());
   KIN_HIP(hipMemcpyAsync(vec, W + pl.off_y, (size_t)pl.vec_len * sizeof(double), hipMemcpyDeviceToHost, s));
   if (R > 0) h->rate.download(rate, (size_t)R, s);
   KIN_HIP(hipMemcpyAsync(W + pl.off_y, keep.data(), keep.size() * sizeof(double), hipMemcpyHostToDevice, s));
-  KIN_HIP(hipMemcpyAsync(S.ctrl.p, &keep_ctrl, sizeof(BdfCtrl), hipMemcpyHostToDevice, s));
+  KIN_HIP(hipMemcpyAsync(S.b.ctrl.p, &keep_ctrl, sizeof(BdfCtrl), hipMemcpyHostToDevice, s));
   KIN_HIP(hipStreamSynchronize(s));
-  S.cur_slot = 0;
-  S.invalidate_lu();
+  S.ctl.cur_slot = 0;
+  S.reset_cache();
 }
 
 }  // namespace kin

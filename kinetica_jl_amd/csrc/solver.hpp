@@ -111,7 +111,7 @@ void newton_probe(kin_network* h, int64_t K, int32_t batched, const double* u, c
                   int32_t* bad, int64_t* info);
 // diagnostic (kin_step_probe, path 1): I - c J(u) factorised into slot 0, b placed, then SparseLU::solve_newton with `f` - the
 // caller fills the device pointers of the step state, the control block, the publication targets and the scalars; N, the skip
-// flag and the partial-sum buffer (the Solver's own) are set here. x: the solution that launch left in W; info[8]: see the header
+// flag and the partial-sum buffer (the host backend's own) are set here. x: the solution that launch left in W; info[8]: see the header
 struct NewtonFuse;
 void step_probe_fused(kin_network* h, double c, const double* u, const double* b, NewtonFuse& f, double* x, int64_t* info);
 // diagnostic (kin_eval_probe): the residual plan of the host-driven solver (path 0: solver.cpp) and of the lockstep ensemble
@@ -120,7 +120,7 @@ void step_probe_fused(kin_network* h, double c, const double* u, const double* b
 struct EvalResidPlan { const SegPlanDev* plan; const int32_t* yloc; int64_t off_y, vec_len; };
 EvalResidPlan eval_probe_solver_plan(kin_network* h);
 EvalResidPlan eval_probe_ensemble_plan(kin_network* h);
-// ... path 0's residual pair through Solver::launch_residual (what newton_iteration calls) on y = u, psi, d, c and the flag value
+// ... path 0's residual pair through HostBackend::launch_residual (what newton_iteration calls) on y = u, psi, d, c and the flag value
 // `done`: slot 0's solve vectors and the handle's rate buffer are filled with `sentinel` first and come back in vec[vec_len] and
 // rate[R]; the slot's vectors and the control block are restored afterwards
 void eval_probe_solver_resid(kin_network* h, const double* u, double c, const double* psi, const double* d, int done, double sentinel,

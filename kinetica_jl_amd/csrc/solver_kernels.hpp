@@ -24,7 +24,7 @@ struct BdfCtrl {
                 // from the same numbers), so a speculatively enqueued next step may run (solver.cpp: speculation)
 };
 
-// LU cache: per-slot copies of diag(J) and the drift test of Solver::restart (at most LU_MAX_SLOTS slots)
+// LU cache: per-slot copies of diag(J) and the drift test of a (re)start (solver.cpp: HostBackend::drift_launch) (at most LU_MAX_SLOTS slots)
 constexpr int LU_MAX_SLOTS = 128;
 struct SlotDriftArgs { const double* jd[LU_MAX_SLOTS]; double c[LU_MAX_SLOTS]; };
 void launch_jac_diag(int N, const double* jv, const int32_t* j_diag, double* jd, hipStream_t s);

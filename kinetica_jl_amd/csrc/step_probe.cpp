@@ -3,7 +3,7 @@
 // solver.cpp: step_probe_fused), the ens_* launchers of the lockstep ensemble (path 2), the resident kernel's own dispatch in its
 // default and its shared-CU build (paths 3 and 4, resident.cpp: resident_step_probe - the kernel's leader wavefront calls the
 // controller's or the backend's method, the other seven decode the command in worker_loop). Nothing here computes: the probe
-// uploads, fills the launchers' arguments the way Solver / MemberBackend / ResidentBdf fill them, launches, downloads.
+// uploads, fills the launchers' arguments the way HostBackend / MemberBackend / ResidentBdf fill them, launches, downloads.
 #include "../../include/kinetica_hip.h"
 
 #include <algorithm>
@@ -44,7 +44,7 @@ void ctrl_to(const BdfCtrl& c, double* v) {
   v[15] = c.ticket; v[16] = c.lu_bad; v[17] = c.spec_go;
 }
 
-// publication targets of the probe's own, allocated as Solver allocates its pair; all bits set until a launch publishes
+// publication targets of the probe's own, allocated as HostBackend allocates its pair; all bits set until a launch publishes
 struct Pinned {
   BdfCtrl* hc = nullptr; unsigned long long* hseq = nullptr;
   BdfCtrl* hc_dev = nullptr; unsigned long long* hseq_dev = nullptr;
@@ -101,7 +101,7 @@ void step_probe(kin_network* h, int path, int op, int64_t n64, int64_t K, int64_
   for (int64_t k = 0; k < K; k++) ctrl_from(ctrl + k * KIN_STEP_CTRL, hctrl[k]);
   d_ctrl.upload(hctrl.data(), (size_t)K, s);
   auto row = [&](int64_t k, int r) { return d_state.p + (size_t)k * per + (size_t)r * n; };
-  const size_t part_n = (size_t)bdf_reduce_slot() * bdf_reduce_blocks(n);   // as Solver sizes `red` (ens_reduce_doubles: the same)
+  const size_t part_n = (size_t)bdf_reduce_slot() * bdf_reduce_blocks(n);   // as HostBackend sizes `red` (ens_reduce_doubles: the same)
   d_part.alloc((size_t)K * part_n);
   d_part.zero(s);
   std::vector<double> hW;
@@ -173,7 +173,7 @@ void step_probe(kin_network* h, int path, int op, int64_t n64, int64_t K, int64_
     require(op == KIN_STEP_NEWTON, ERR_UNSUPPORTED, "the fused path has the corrector update only");
     const int32_t* ia = iarg; const double* da = darg;
     const int order = ia[IA_ORDER];
-    NewtonFuse f;   // as Solver::newton_iteration fills it
+    NewtonFuse f;   // as HostBackend::newton_iteration fills it
     f.skip = nullptr; f.N = n; f.m = 0; f.off_x = 0; f.x2_species = nullptr;
     f.scale = row(0, ROW_SCALE); f.y = row(0, ROW_Y); f.d = row(0, ROW_DD); f.D = row(0, ROW_D); f.order = order;
     f.upd = da[DA_UPD]; f.atol = da[DA_ATOL]; f.rtol = da[DA_RTOL];

@@ -4,64 +4,17 @@
 
 #include <algorithm>
 #include <cmath>
-#include <memory>
-#include <mutex>
-#include <numeric>
 #include <string>
-#include <cstring>
-#include <thread>
 #include <vector>
 
 #include "handle.hpp"
 #include "lu.hpp"
-#include "resident_setup.hpp"
 #include "solver.hpp"
 #include "solver_kernels.hpp"
 
 using namespace kin;
 
 static thread_local std::string g_create_err;
-
-void kin_network::flush_pending_T(hipStream_t s) {
-  if (!k_pending) return;
-  launch_arrhenius(host.R, Ea.p, A.p, has_kmax, k_max, t_mult, T_pending, k.p, s);
-  k_pending = false;
-}
-
-void kin_network::rhs_dev(const double* d_u, double* d_du) {
-  if (k_pending) { launch_rates_T(host.R, pending_at(), k.p, d_u, x0.p, x1.p, rate.p, stream); k_pending = false; }
-  else launch_rates(host.R, k.p, d_u, x0.p, x1.p, rate.p, stream);
-  launch_segsum(rhs_plan.view(), SEG_COEF_SET, rate.p, d_du, SegExtra{}, stream);
-}
-
-SweepPlan kin_network::sweep_plan_dev(int64_t B, const double* d_u, const double* d_k, const double* d_du) const {
-  const auto bits = [](const void* p) { return (unsigned)(reinterpret_cast<uintptr_t>(p) & 15); };
-  return sweep_plan(sweep_net_info(host), n_cu, B, SweepAlign{bits(d_u), bits(d_k ? d_k : k.p), bits(d_du)});
-}
-
-void kin_network::sweep_dev(int64_t B, const double* d_u, const double* d_k, double* d_du, hipStream_t s) {
-  if (!d_k) flush_pending_T(s);   // the handle's own k is about to be read: a temperature still pending is formed first
-  const SweepPlan plan = sweep_plan_dev(B, d_u, d_k, d_du);
-  if (plan.kernel == SWEEP_PER_STATE) {
-    // (sweep_plan.hpp: species ids beyond 16 bits) the single-state kernels, state after state on the same stream
-    for (int64_t b = 0; b < B; b++) {
-      launch_rates(host.R, d_k ? d_k + b * host.R : k.p, d_u + b * host.N, x0.p, x1.p, rate.p, s);
-      launch_segsum(rhs_plan.view(), SEG_COEF_SET, rate.p, d_du + b * host.N, SegExtra{}, s);
-    }
-  } else if (plan.kernel == SWEEP_BIG) {
-    big_scratch.alloc((size_t)plan.grid * (size_t)(host.N - host.big_H + host.n_pairs()));
-    launch_sweep_big(plan, host.N, host.R, host.n_pairs(), B, big_rec8.p, big_rec.p, big_expl.p, sweep_k.p, big_spec.p, big_tptr.p,
-                     big_tent.p, big_scratch.p, d_u, d_k, k.p, d_du, s);
-  } else
-    launch_sweep(plan, host.N, host.R, host.n_pairs(), B, sweep_rec.p, sweep_k.p, host.pair_rec64.empty() ? nullptr : sweep_rec64.p,
-                 sweep_copy.p, host.gen_rec8.empty() ? nullptr : gen_rec8.p, gen_k.p, gen_expl.p, d_u, d_k, k.p, d_du, s);
-}
-
-void kin_network::jac_dev(const double* d_u, double* d_vals) {
-  if (k_pending) { launch_drates_T(host.R, pending_at(), k.p, d_u, x0.p, x1.p, dr.p, stream); k_pending = false; }
-  else launch_drates(host.R, k.p, d_u, x0.p, x1.p, dr.p, stream);
-  launch_segsum(jac_plan.view(), SEG_COEF_SET, dr.p, d_vals, SegExtra{}, stream);
-}
 
 // handle.hpp's guard, but for entries that may run without a handle (kin_network_create): the message then goes to g_create_err
 #undef KIN_TRY
@@ -121,8 +74,7 @@ int kin_network_create(int64_t n_species, int64_t n_reactions, const int64_t* re
     KIN_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
     const NetworkHost& N = h->host;
     hipStream_t s = h->stream;
-    h->x0.upload(N.x0, s); h->x1.upload(N.x1, s);
-    h->sp_ptr.upload(N.sp_ptr, s); h->sp_rxn.upload(N.sp_rxn, s); h->sp_coef.upload(N.sp_coef, s);
+    upload_solve_tables(h);
     if (N.N < 65535) { h->sweep_rec.upload(N.pair_rec, s); h->sweep_k.upload(N.pair_k, s); }
     if (!N.gen_rec8.empty()) { h->gen_rec8.upload(N.gen_rec8, s); h->gen_k.upload(N.gen_k, s); h->gen_expl.upload(N.gen_expl, s); }
     if (!N.pair_rec64.empty()) { h->sweep_rec64.upload(N.pair_rec64, s); h->sweep_copy.upload(N.sweep_copy_species, s); }
@@ -131,10 +83,6 @@ int kin_network_create(int64_t n_species, int64_t n_reactions, const int64_t* re
       h->big_spec.upload(N.big_spec_of_label, s);
       h->big_tptr.upload(N.big_tail_ptr, s); h->big_tent.upload(N.big_tail_ent, s);
     }
-    h->rhs_plan.upload(build_seg_plan(N.N, N.sp_ptr.data(), nullptr, N.sp_rxn.data(), nullptr, N.sp_coef.data(), false), s);
-    h->jac_plan.upload(build_seg_plan(N.nnz(), N.jc_ptr.data(), nullptr, N.jc_src.data(), nullptr, N.jc_coef.data(), false), s);
-    h->k.alloc(N.R); h->rate.alloc(N.R); h->dr.alloc(2 * N.R + 2);
-    h->u.alloc(N.N); h->du.alloc(N.N); h->jvals.alloc(N.nnz());
     KIN_HIP(hipStreamSynchronize(s));
     *out = h;
   } catch (const KinError& e) {
@@ -155,8 +103,8 @@ int kin_lu_analyze_host(int64_t n_species, int64_t n_reactions, const int64_t* r
                         const int64_t* reac_sto, const int64_t* prod_ptr, const int64_t* prod_idx, const int64_t* prod_sto,
                         int index_base, int hub_degree, int max_rounds, int max_tail_degree, int max_degree, int min_round,
                         int64_t* info) {
-  try {
-    const NetworkHost H = compile_network(n_species, n_reactions, reac_ptr, reac_idx, reac_sto, prod_ptr, prod_idx, prod_sto, index_base);
+  return with_compiled_network(n_species, n_reactions, reac_ptr, reac_idx, reac_sto, prod_ptr, prod_idx, prod_sto, index_base, g_create_err,
+                               [&](const NetworkHost& H) {
     SparseLU lu;
     lu.host_only = true;
     LUOptions opt;
@@ -171,14 +119,7 @@ int kin_lu_analyze_host(int64_t n_species, int64_t n_reactions, const int64_t* r
       info[6] = lu.nnzLZ; info[7] = lu.nnzNVU; info[8] = lu.w_size; info[9] = lu.n_fused_products; info[10] = lu.plan_entries;
       info[11] = lu.plan_tasks;
     }
-  } catch (const KinError& e) {
-    g_create_err = e.what();
-    return e.code;
-  } catch (const std::exception& e) {
-    g_create_err = e.what();
-    return KIN_ERR_INVALID_ARG;
-  }
-  return KIN_OK;
+  });
 }
 
 int kin_network_destroy(kin_network* h) {
@@ -319,17 +260,10 @@ int kin_sweep_plan_host(int64_t n_species, int64_t n_reactions, const int64_t* r
                         int index_base, int n_cu, int64_t B, int u_bits, int k_bits, int du_bits, int64_t* info) {
   if (!info || n_cu < 1 || B < 1 || u_bits < 0 || u_bits > 15 || k_bits < 0 || k_bits > 15 || du_bits < 0 || du_bits > 15)
     return KIN_ERR_INVALID_ARG;
-  try {
-    const NetworkHost H = compile_network(n_species, n_reactions, reac_ptr, reac_idx, reac_sto, prod_ptr, prod_idx, prod_sto, index_base);
+  return with_compiled_network(n_species, n_reactions, reac_ptr, reac_idx, reac_sto, prod_ptr, prod_idx, prod_sto, index_base, g_create_err,
+                               [&](const NetworkHost& H) {
     sweep_plan_info(sweep_plan(sweep_net_info(H), n_cu, B, SweepAlign{(unsigned)u_bits, (unsigned)k_bits, (unsigned)du_bits}), info);
-  } catch (const KinError& e) {
-    g_create_err = e.what();
-    return e.code;
-  } catch (const std::exception& e) {
-    g_create_err = e.what();
-    return KIN_ERR_INVALID_ARG;
-  }
-  return KIN_OK;
+  });
 }
 
 int kin_rhs_batched(kin_network* h, int64_t B, const double* u, const double* k, double* du) {
@@ -357,8 +291,8 @@ int kin_jac_nnz(kin_network* h, int64_t* nnz) {
 int kin_drg_pattern_host(int64_t n_species, int64_t n_reactions, const int64_t* reac_ptr, const int64_t* reac_idx,
                          const int64_t* reac_sto, const int64_t* prod_ptr, const int64_t* prod_idx, const int64_t* prod_sto,
                          int index_base, int pairing, int64_t* info, int64_t* rowptr, int64_t* colidx) {
-  try {
-    const NetworkHost H = compile_network(n_species, n_reactions, reac_ptr, reac_idx, reac_sto, prod_ptr, prod_idx, prod_sto, index_base);
+  return with_compiled_network(n_species, n_reactions, reac_ptr, reac_idx, reac_sto, prod_ptr, prod_idx, prod_sto, index_base, g_create_err,
+                               [&](const NetworkHost& H) {
     const DrgTables t = build_drg_tables(H, pairing, false);
     if (info) {
       info[0] = t.E; info[1] = t.n_den; info[2] = t.n_num;
@@ -366,54 +300,33 @@ int kin_drg_pattern_host(int64_t n_species, int64_t n_reactions, const int64_t* 
     }
     if (rowptr) for (int64_t i = 0; i <= t.N; i++) rowptr[i] = t.rowptr[i] + index_base;
     if (colidx) for (int64_t e = 0; e < t.E; e++) colidx[e] = t.colidx[e] + index_base;
-  } catch (const KinError& e) {
-    g_create_err = e.what();
-    return e.code;
-  } catch (const std::exception& e) {
-    g_create_err = e.what();
-    return KIN_ERR_INVALID_ARG;
-  }
-  return KIN_OK;
+  });
 }
 
 int kin_reaction_importance_plan_host(int64_t n_species, int64_t n_reactions, const int64_t* reac_ptr, const int64_t* reac_idx,
                                       const int64_t* reac_sto, const int64_t* prod_ptr, const int64_t* prod_idx, const int64_t* prod_sto,
                                       int index_base, int pairing, int64_t* info, int64_t* partner, int64_t* species, int64_t* nu) {
-  try {
-    const NetworkHost H = compile_network(n_species, n_reactions, reac_ptr, reac_idx, reac_sto, prod_ptr, prod_idx, prod_sto, index_base);
+  return with_compiled_network(n_species, n_reactions, reac_ptr, reac_idx, reac_sto, prod_ptr, prod_idx, prod_sto, index_base, g_create_err,
+                               [&](const NetworkHost& H) {
     const RiTables t = build_ri_tables(H, pairing);
     if (info) { info[0] = t.n_records; info[1] = t.n_paired; info[2] = t.n_empty; }
     if (partner) for (int64_t r = 0; r < t.R; r++) partner[r] = t.partner[r];
     if (species) for (int64_t i = 0; i < 4 * t.R; i++) species[i] = t.species[i];
     if (nu) for (int64_t i = 0; i < 4 * t.R; i++) nu[i] = t.nu[i];
-  } catch (const KinError& e) {
-    g_create_err = e.what();
-    return e.code;
-  } catch (const std::exception& e) {
-    g_create_err = e.what();
-    return KIN_ERR_INVALID_ARG;
-  }
-  return KIN_OK;
+  });
 }
 
 int kin_pfa_pattern_host(int64_t n_species, int64_t n_reactions, const int64_t* reac_ptr, const int64_t* reac_idx,
                          const int64_t* reac_sto, const int64_t* prod_ptr, const int64_t* prod_idx, const int64_t* prod_sto,
                          int index_base, int pairing, int64_t* info, int64_t* rowptr, int64_t* colidx) {
-  try {
-    const NetworkHost H = compile_network(n_species, n_reactions, reac_ptr, reac_idx, reac_sto, prod_ptr, prod_idx, prod_sto, index_base);
+  return with_compiled_network(n_species, n_reactions, reac_ptr, reac_idx, reac_sto, prod_ptr, prod_idx, prod_sto, index_base, g_create_err,
+                               [&](const NetworkHost& H) {
     const DrgTables g = build_drg_tables(H, pairing, false);
     const PfaTables t = build_pfa_tables(g.N, g.rowptr, g.colidx);
     if (info) { info[0] = t.E; info[1] = t.E2; info[2] = t.products; info[3] = t.max_row; }
     if (rowptr) for (int64_t i = 0; i <= t.N; i++) rowptr[i] = t.rowptr2[i] + index_base;
     if (colidx) for (int64_t e = 0; e < t.E2; e++) colidx[e] = t.colidx2[e] + index_base;
-  } catch (const KinError& e) {
-    g_create_err = e.what();
-    return e.code;
-  } catch (const std::exception& e) {
-    g_create_err = e.what();
-    return KIN_ERR_INVALID_ARG;
-  }
-  return KIN_OK;
+  });
 }
 
 int kin_jac_pattern(kin_network* h, int64_t* rowptr, int64_t* colidx, int index_base) {
@@ -442,281 +355,48 @@ int kin_solve(kin_network* h, const kin_params* params, const double* u0, const 
   if (!h) return KIN_ERR_INVALID_ARG;
   KIN_TRY(h)
   require(params && u0, ERR_INVALID_ARG, "params / u0 is null");
-  int rc = solve_entry(h, *params, u0, tstops, T_stops, k_table, n_stops, stats);
-  if (n_saved) *n_saved = h->n_saved;
-  if (retcode) *retcode = rc;
-  if (rc != KIN_RETCODE_SUCCESS) throw KinError(ERR_SOLVE_FAILED, "ODE solution failed.");
+  finish_solve(h, solve_entry(h, *params, u0, tstops, T_stops, k_table, n_stops, stats), n_saved, retcode);
   KIN_CATCH(h)
 }
-
-namespace {
-
-// A solve-only copy of a handle: the compiled tables again on the device, own stream and work vectors; Solver, symbolic LU and LU
-// cache are built by its first solve and stay with it
-kin_network* clone_for_solves(kin_network* h) {
-  std::unique_ptr<kin_network> c(new kin_network());
-  c->host = h->host;
-  c->device = h->device; c->n_cu = h->n_cu;
-  KIN_HIP(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-  const NetworkHost& N = c->host;
-  hipStream_t s = c->stream;
-  c->x0.upload(N.x0, s); c->x1.upload(N.x1, s);
-  c->sp_ptr.upload(N.sp_ptr, s); c->sp_rxn.upload(N.sp_rxn, s); c->sp_coef.upload(N.sp_coef, s);
-  c->rhs_plan.upload(build_seg_plan(N.N, N.sp_ptr.data(), nullptr, N.sp_rxn.data(), nullptr, N.sp_coef.data(), false), s);
-  c->jac_plan.upload(build_seg_plan(N.nnz(), N.jc_ptr.data(), nullptr, N.jc_src.data(), nullptr, N.jc_coef.data(), false), s);
-  c->k.alloc(N.R); c->rate.alloc(N.R); c->dr.alloc(2 * N.R + 2);
-  c->u.alloc(N.N); c->du.alloc(N.N); c->jvals.alloc(N.nnz());
-  KIN_HIP(hipStreamSynchronize(s));
-  return c.release();
-}
-
-int replica_threads_max() {
-  const char* e = getenv("KIN_ENSEMBLE_THREADS");   // (read per call: tests change it)
-  return std::max(1, e ? atoi(e) : 12);
-}
-
-// A SMALL ensemble of a LARGE network: K independent kin_solve calls on K host threads, one solve-only copy of the handle each.
-// Every member is, bit for bit, what kin_solve gives for its inputs. A chain of ~14 small dependent launches per step keeps one
-// trajectory at 6.7 solves/s (first 2 chunks of the 10k-species network) and K of them at 11 / 17 / 17 / 16 for K = 2 / 4 / 8 / 12 - the
-// dispatch rate of the chip's queues; the lockstep rounds of ensemble.cpp only overtake that from K = 16 on.
-// A continuous call's member m is the kin_solve_continuous of its own profile, a per-member-stops call's the kin_solve of its
-// own (tstops, T_stops).
-void replica_ensemble(kin_network* h, const EnsembleCall& c) {
-  const int64_t N = h->host.N, R = h->host.R, K = c.K;
-  const int64_t cap = make_res_grid(c.p).cap;
-  if (c.n_rows) *c.n_rows = cap;
-  // EMPIRICAL (ROCm 7.2, MI355X; tools/replica_sequence.py): members whose streams are among the first ~4 streams of the
-  // process slow each other down when they run together - K = 4: 11.4 solves/s, with three or more streams created BEFORE theirs
-  // (and kept alive; destroyed ones do not count) 17.0; K = 8: 13.3 -> 16.7; K = 12: 13.9 -> 16.3. Which thread creates a
-  // stream makes no difference. bench.py's concurrent_replicas never saw it: torch's own streams play that role there. Four
-  // idle placeholder streams are therefore created once per process in front of the first replica's.
-  {
-    static std::once_flag once;
-    std::call_once(once, [] {
-      const int n = getenv("KIN_REPLICA_PLACEHOLDER_STREAMS") ? atoi(getenv("KIN_REPLICA_PLACEHOLDER_STREAMS")) : 4;
-      for (int i = 0; i < n; i++) { hipStream_t d = nullptr; if (hipStreamCreateWithFlags(&d, hipStreamNonBlocking) != hipSuccess) (void)hipGetLastError(); }
-    });
-  }
-  // Tn threads, member m on thread m mod Tn (a thread solves its members one after the other on its own replica): K <= the
-  // thread limit gives every member its own thread, more members share the threads evenly
-  const int64_t per = ceil_div(K, (int64_t)replica_threads_max());
-  const int64_t Tn = ceil_div(K, per);
-  while ((int64_t)h->replicas.size() < Tn) {
-    // LU-cache budget of a replica: its share of 70 % of what the device has FREE now, as if every thread of the limit were to get
-    // a replica (a later call with more members then finds the same share left for the replicas it adds; the budget is fixed when a
-    // replica's Solver is built, at its first solve)
-    size_t free_b = 0, total_b = 0;
-    KIN_HIP(hipMemGetInfo(&free_b, &total_b));
-    h->replicas.push_back(clone_for_solves(h));
-    h->replicas.back()->lu_budget_mb = std::max<size_t>(64, (size_t)((double)free_b * 0.7 / (1024.0 * 1024.0)) / (size_t)replica_threads_max());
-  }
-  // kin_ensemble_*: every member's saved rows are copied device-to-device into the handle's own [K][cap][N], zeros past n_saved
-  h->ens_sol.alloc((size_t)K * (size_t)cap * (size_t)N);
-  KIN_HIP(hipStreamSynchronize(h->stream));
-  std::vector<std::string> errs((size_t)Tn);
-  std::vector<std::thread> th;
-  std::vector<int64_t> rows((size_t)K, 0);              // every member's saved rows ...
-  std::vector<std::vector<double>> times((size_t)K);    // ... and their times (out_t: those of res_furthest)
-  th.reserve((size_t)Tn);
-  std::string spawn_err;
-  for (int64_t t = 0; t < Tn && spawn_err.empty(); t++) try {
-    th.emplace_back([&, t] {
-      try {
-        kin_network* rep = h->replicas[(size_t)t];
-        KIN_HIP(hipSetDevice(rep->device));
-        hipStream_t s = rep->stream;
-        if (h->has_arrhenius) {
-          rep->Ea.alloc(R); rep->A.alloc(R);
-          KIN_HIP(hipMemcpyAsync(rep->Ea.p, h->Ea.p, (size_t)R * sizeof(double), hipMemcpyDeviceToDevice, s));
-          KIN_HIP(hipMemcpyAsync(rep->A.p, h->A.p, (size_t)R * sizeof(double), hipMemcpyDeviceToDevice, s));
-          rep->has_arrhenius = true; rep->has_kmax = h->has_kmax; rep->k_max = h->k_max; rep->t_mult = h->t_mult;
-        }
-        for (int64_t m = t; m < K; m += Tn) {
-          if (c.member_params()) {
-            // the member's own (Ea, A) into the replica's arrays, which the next call's copy of the handle's overwrites again;
-            // the handle's own are never written
-            const EnsembleCall::Arrhenius pm = c.member_arrhenius(h, m);
-            KIN_HIP(hipMemcpyAsync(rep->Ea.p, pm.Ea, (size_t)R * sizeof(double), hipMemcpyDeviceToDevice, s));
-            KIN_HIP(hipMemcpyAsync(rep->A.p, pm.A, (size_t)R * sizeof(double), hipMemcpyDeviceToDevice, s));
-          }
-          if (c.static_rates()) {
-            stage_member_rates(h, c, m, rep->Ea.p, rep->A.p, rep->k.p, s);
-            rep->has_rates = true; rep->k_pending = false;
-          }
-          KIN_HIP(hipStreamSynchronize(s));
-          kin_stats st{};
-          const int64_t* ptr = c.node_ptr;
-          const EnsembleCall::Stops ms = c.member_stops(m);
-          const int rc = ptr ? solve_entry(rep, c.p, c.u0 + m * N, nullptr, nullptr, nullptr, 0, &st, c.t_nodes + ptr[m], c.T_nodes + ptr[m],
-                                           ptr[m + 1] - ptr[m])
-                             : solve_entry(rep, c.p, c.u0 + m * N, ms.tstops, ms.T_stops, c.k_table, ms.n, &st);
-          if (c.retcodes) c.retcodes[m] = rc;
-          if (c.stats) c.stats[m] = st;
-          const int64_t ns = std::min<int64_t>(rep->n_saved, cap);
-          rows[(size_t)m] = ns;
-          if (c.n_saved) c.n_saved[m] = ns;
-          if (c.out_u && ns > 0) rep->d_sol_u.download(c.out_u + (size_t)m * cap * N, (size_t)ns * N, s);
-          if (c.out_u && ns < cap) std::memset(c.out_u + ((size_t)m * cap + (size_t)ns) * N, 0, (size_t)(cap - ns) * N * sizeof(double));   // rows a failed member never wrote
-          // (on the replica's stream, before its next member overwrites d_sol_u; drained by the synchronisation below)
-          double* keep = h->ens_sol.p + (size_t)m * (size_t)cap * (size_t)N;
-          if (ns > 0) KIN_HIP(hipMemcpyAsync(keep, rep->d_sol_u.p, (size_t)ns * N * sizeof(double), hipMemcpyDeviceToDevice, s));
-          if (ns < cap) KIN_HIP(hipMemsetAsync(keep + (size_t)ns * N, 0, (size_t)(cap - ns) * N * sizeof(double), s));
-          KIN_HIP(hipStreamSynchronize(s));
-          if (c.out_t) times[(size_t)m].assign(rep->sol_t.begin(), rep->sol_t.begin() + std::min<int64_t>(ns, (int64_t)rep->sol_t.size()));
-        }
-      } catch (const std::exception& e) { errs[(size_t)t] = e.what(); }
-    });
-  } catch (const std::exception& e) { spawn_err = e.what(); }   // (the threads that did start are joined below before anything is thrown)
-  for (auto& x : th) x.join();
-  if (!spawn_err.empty()) throw KinError(ERR_DEVICE, "ensemble: could not start a member thread: " + spawn_err);
-  for (auto& e : errs) if (!e.empty()) throw KinError(ERR_DEVICE, "ensemble member failed: " + e);
-  if (c.out_t) { const std::vector<double>& tb = times[(size_t)res_furthest(rows)]; std::copy(tb.begin(), tb.end(), c.out_t); }
-  h->set_ensemble_record(h->ens_sol.p, K, cap, std::move(rows));
-}
-
-// Which form an ensemble call takes. Networks whose trajectory fits one compute unit: one workgroup per member, one launch
-// (resident.cpp); larger ones: kin_solve calls on host threads (replica_ensemble) or lockstep rounds of batched launches
-// (ensemble.cpp). KIN_ENSEMBLE_ROUTE = threads | lockstep forces a form (A/B runs: tools/ensemble_route_crossover.py);
-// KIN_ENSEMBLE_BATCHED=1 forces the lockstep form of a static call. The lockstep form has no continuous rate updates.
-void route_ensemble(kin_network* h, const EnsembleCall& c) {
-  const char* e = getenv("KIN_ENSEMBLE_ROUTE");
-  const std::string route = e ? e : "";
-  const bool force_batched = getenv("KIN_ENSEMBLE_BATCHED") && atoi(getenv("KIN_ENSEMBLE_BATCHED")) != 0;
-  if (route == "threads") return replica_ensemble(h, c);
-  if (c.continuous()) {
-    require(route != "lockstep", ERR_UNSUPPORTED, "the lockstep ensemble has no continuous rate updates");
-    return resident_ensemble_route(h, c.K) ? resident_ensemble(h, c) : replica_ensemble(h, c);
-  }
-  if (route == "lockstep" || force_batched) return batched_ensemble(h, c);
-  if (resident_ensemble_route(h, c.K)) return resident_ensemble(h, c);
-  // few members of a network too large for a compute unit: kin_solve calls on host threads, one member per thread up to the
-  // thread limit (beyond it the lockstep rounds are ahead at 3 000 and 10 000 species: profiles/r04_ensemble_route_crossover.jsonl)
-  // ... and ANY number of members when the lockstep form does not take the network's factorisation (it needs the fused solve
-  // with a dense Schur block; KIN_LU_FUSED=0 or a network without hubs has none): the threads then take several members each
-  if (c.K <= replica_threads_max() || !ensemble_batched_supported(h, nullptr)) return replica_ensemble(h, c);
-  batched_ensemble(h, c);
-}
-
-// A call with per-member Arrhenius parameters has its Ea[K][R], A[K][R] uploaded once, here, into the buffers that stay with the
-// ensemble record (16 K R bytes; reused by later calls); every route reads them through EnsembleCall::member_arrhenius, and
-// kin_ensemble_flux reads them from the record. A shared call takes the route as it is and leaves a shared record.
-void run_ensemble(kin_network* h, const EnsembleCall& c) {
-  h->ens.clear();   // (whatever route: its buffers are about to be reallocated or overwritten; set again by a call that succeeds)
-  if (!c.member_params()) return route_ensemble(h, c);
-  const size_t n = (size_t)c.K * (size_t)h->host.R;
-  try {
-    h->ens_Ea.alloc(n); h->ens_A.alloc(n);
-  } catch (const std::exception& e) {
-    (void)hipGetLastError();
-    throw KinError(ERR_DEVICE, "ensemble: no device memory for the per-member Arrhenius parameters (" + std::to_string(2 * n * sizeof(double)) +
-                                   " bytes): " + e.what());
-  }
-  KIN_HIP(hipMemcpyAsync(h->ens_Ea.p, c.Ea, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  KIN_HIP(hipMemcpyAsync(h->ens_A.p, c.A, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  KIN_HIP(hipStreamSynchronize(h->stream));   // (the thread route's replicas read the blocks on streams of their own)
-  EnsembleCall m = c;
-  m.d_Ea = h->ens_Ea.p; m.d_A = h->ens_A.p;
-  route_ensemble(h, m);
-  if (h->ens.valid()) { h->ens.Ea = h->ens_Ea.p; h->ens.A = h->ens_A.p; }
-}
-
-// kin_solve_ensemble_continuous / _discrete and their _params forms (Ea == A == null: the shared call, bit for bit)
-int ensemble_continuous_entry(kin_network* h, const kin_params* params, int64_t K, const double* u0, const double* Ea, const double* A,
-                              const int64_t* node_ptr, const double* t_nodes, const double* T_nodes, int64_t* n_rows, double* out_t,
-                              double* out_u, int64_t* n_saved, int32_t* retcodes, kin_stats* stats) {
-  if (!h) return KIN_ERR_INVALID_ARG;
-  KIN_TRY(h)
-  require(params && u0 && K >= 1, ERR_INVALID_ARG, "params / u0 is null, or K < 1");
-  require(node_ptr && t_nodes && T_nodes, ERR_INVALID_ARG, "node_ptr / t_nodes / T_nodes is null");
-  require((Ea == nullptr) == (A == nullptr), ERR_INVALID_ARG, "give both per-member Ea and A, or neither");
-  require(res_has_grid(*params), ERR_INVALID_ARG, "an ensemble solve needs a save grid (solve_chunks or save_interval)");
-  for (int64_t m = 0; m < K; m++) {
-    // every member needs a profile of its own: an empty one would leave the controller's T(t) nothing to read
-    require(node_ptr[m] >= 0 && node_ptr[m + 1] - node_ptr[m] >= 2, ERR_INVALID_ARG, "need >= 2 (t, T) nodes per member");
-    validate_solve(h, *params, nullptr, nullptr, nullptr, 0, t_nodes + node_ptr[m], T_nodes + node_ptr[m], node_ptr[m + 1] - node_ptr[m], false);
-  }
-  if (n_rows && !out_u && !n_saved) { *n_rows = make_res_grid(*params).cap; }   // size query
-  else {
-    EnsembleCall c{*params, K, u0, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, node_ptr, t_nodes, T_nodes, n_rows, out_t, out_u,
-                   n_saved, retcodes, stats};
-    c.Ea = Ea; c.A = A;
-    run_ensemble(h, c);
-  }
-  KIN_CATCH(h)
-}
-
-int ensemble_discrete_entry(kin_network* h, const kin_params* params, int64_t K, const double* u0, const double* Ea, const double* A,
-                            const int64_t* stop_ptr, const double* tstops, const double* T_stops, int64_t* n_rows, double* out_t,
-                            double* out_u, int64_t* n_saved, int32_t* retcodes, kin_stats* stats) {
-  if (!h) return KIN_ERR_INVALID_ARG;
-  KIN_TRY(h)
-  require(params && u0 && K >= 1, ERR_INVALID_ARG, "params / u0 is null, or K < 1");
-  require(stop_ptr && tstops && T_stops, ERR_INVALID_ARG, "stop_ptr / tstops / T_stops is null");
-  require((Ea == nullptr) == (A == nullptr), ERR_INVALID_ARG, "give both per-member Ea and A, or neither");
-  require(res_has_grid(*params), ERR_INVALID_ARG, "an ensemble solve needs a save grid (solve_chunks or save_interval)");
-  for (int64_t m = 0; m < K; m++) {
-    // every member needs a stop of its own: the controller's rates in force before the first stop are those of stop 0
-    require(stop_ptr[m] >= 0 && stop_ptr[m + 1] - stop_ptr[m] >= 1, ERR_INVALID_ARG, "need >= 1 stop per member");
-    validate_solve(h, *params, tstops + stop_ptr[m], T_stops + stop_ptr[m], nullptr, stop_ptr[m + 1] - stop_ptr[m], nullptr, nullptr, 0, false);
-  }
-  if (n_rows && !out_u && !n_saved) { *n_rows = make_res_grid(*params).cap; }   // size query
-  else {
-    EnsembleCall c{*params, K, u0, nullptr, nullptr, tstops, T_stops, nullptr, 0, stop_ptr, nullptr, nullptr, nullptr, n_rows, out_t,
-                   out_u, n_saved, retcodes, stats};
-    c.Ea = Ea; c.A = A;
-    run_ensemble(h, c);
-  }
-  KIN_CATCH(h)
-}
-
-}  // namespace
 
 int kin_solve_ensemble(kin_network* h, const kin_params* params, int64_t K, const double* u0, const double* k, const double* T,
                        const double* tstops, const double* T_stops, const double* k_table, int64_t n_stops, int64_t* n_rows,
                        double* out_t, double* out_u, int64_t* n_saved, int32_t* retcodes, kin_stats* stats) {
-  if (!h) return KIN_ERR_INVALID_ARG;
-  KIN_TRY(h)
-  require(params && u0 && K >= 1, ERR_INVALID_ARG, "params / u0 is null, or K < 1");
-  require(!(k && T), ERR_INVALID_ARG, "give per-member rate constants or per-member temperatures, not both");
-  require(!(n_stops > 0 && (k || T)), ERR_INVALID_ARG, "discrete rate updates are shared by the ensemble: no per-member k / T with tstops");
-  require(!T || h->has_arrhenius, ERR_STATE, "temperatures given but Arrhenius parameters were never set");
-  require(res_has_grid(*params), ERR_INVALID_ARG, "an ensemble solve needs a save grid (solve_chunks or save_interval)");
-  validate_solve(h, *params, tstops, T_stops, k_table, n_stops, nullptr, nullptr, 0, !(k || T));
-  if (n_rows && !out_u && !n_saved) { *n_rows = make_res_grid(*params).cap; }   // size query
-  else {
-    if (h->k_pending) h->flush_pending_T(h->stream);
-    run_ensemble(h, {*params, K, u0, k, T, tstops, T_stops, k_table, n_stops, nullptr, nullptr, nullptr, nullptr, n_rows, out_t, out_u, n_saved,
-                     retcodes, stats});
-  }
-  KIN_CATCH(h)
+  const EnsembleCall c{kin_params{}, K, u0, k, T, tstops, T_stops, k_table, n_stops, nullptr, nullptr, nullptr, nullptr, n_rows, out_t, out_u, n_saved,
+                       retcodes, stats};
+  return ensemble_entry(h, params, c, [&] {
+    require(!(k && T), ERR_INVALID_ARG, "give per-member rate constants or per-member temperatures, not both");
+    require(!(n_stops > 0 && (k || T)), ERR_INVALID_ARG, "discrete rate updates are shared by the ensemble: no per-member k / T with tstops");
+    require(!T || h->has_arrhenius, ERR_STATE, "temperatures given but Arrhenius parameters were never set");
+  }, [&] { validate_solve(h, *params, tstops, T_stops, k_table, n_stops, nullptr, nullptr, 0, !(k || T)); });
 }
 
 int kin_solve_ensemble_continuous(kin_network* h, const kin_params* params, int64_t K, const double* u0,
                                   const int64_t* node_ptr, const double* t_nodes, const double* T_nodes,
                                   int64_t* n_rows, double* out_t, double* out_u, int64_t* n_saved,
                                   int32_t* retcodes, kin_stats* stats) {
-  return ensemble_continuous_entry(h, params, K, u0, nullptr, nullptr, node_ptr, t_nodes, T_nodes, n_rows, out_t, out_u, n_saved, retcodes, stats);
+  return ensemble_member_entry(h, params, K, u0, nullptr, nullptr, true, node_ptr, t_nodes, T_nodes, n_rows, out_t, out_u, n_saved, retcodes, stats);
 }
 
 int kin_solve_ensemble_continuous_params(kin_network* h, const kin_params* params, int64_t K, const double* u0, const double* Ea,
                                          const double* A, const int64_t* node_ptr, const double* t_nodes, const double* T_nodes,
                                          int64_t* n_rows, double* out_t, double* out_u, int64_t* n_saved, int32_t* retcodes,
                                          kin_stats* stats) {
-  return ensemble_continuous_entry(h, params, K, u0, Ea, A, node_ptr, t_nodes, T_nodes, n_rows, out_t, out_u, n_saved, retcodes, stats);
+  return ensemble_member_entry(h, params, K, u0, Ea, A, true, node_ptr, t_nodes, T_nodes, n_rows, out_t, out_u, n_saved, retcodes, stats);
 }
 
 int kin_solve_ensemble_discrete(kin_network* h, const kin_params* params, int64_t K, const double* u0,
                                 const int64_t* stop_ptr, const double* tstops, const double* T_stops,
                                 int64_t* n_rows, double* out_t, double* out_u, int64_t* n_saved,
                                 int32_t* retcodes, kin_stats* stats) {
-  return ensemble_discrete_entry(h, params, K, u0, nullptr, nullptr, stop_ptr, tstops, T_stops, n_rows, out_t, out_u, n_saved, retcodes, stats);
+  return ensemble_member_entry(h, params, K, u0, nullptr, nullptr, false, stop_ptr, tstops, T_stops, n_rows, out_t, out_u, n_saved, retcodes, stats);
 }
 
 int kin_solve_ensemble_discrete_params(kin_network* h, const kin_params* params, int64_t K, const double* u0, const double* Ea,
                                        const double* A, const int64_t* stop_ptr, const double* tstops, const double* T_stops,
                                        int64_t* n_rows, double* out_t, double* out_u, int64_t* n_saved, int32_t* retcodes,
                                        kin_stats* stats) {
-  return ensemble_discrete_entry(h, params, K, u0, Ea, A, stop_ptr, tstops, T_stops, n_rows, out_t, out_u, n_saved, retcodes, stats);
+  return ensemble_member_entry(h, params, K, u0, Ea, A, false, stop_ptr, tstops, T_stops, n_rows, out_t, out_u, n_saved, retcodes, stats);
 }
 
 int kin_newton_solve(kin_network* h, double c, const double* u, const double* b, double* x) {
@@ -756,10 +436,7 @@ int kin_solve_explicit(kin_network* h, const kin_params* params, const double* u
   KIN_TRY(h)
   require(params && u0, ERR_INVALID_ARG, "params / u0 is null");
   require(n_stops >= 0, ERR_INVALID_ARG, "n_stops < 0");
-  int rc = solve_entry(h, *params, u0, tstops, T_stops, k_table, n_stops, stats, nullptr, nullptr, 0, true);
-  if (n_saved) *n_saved = h->n_saved;
-  if (retcode) *retcode = rc;
-  if (rc != KIN_RETCODE_SUCCESS) throw KinError(ERR_SOLVE_FAILED, "ODE solution failed.");
+  finish_solve(h, solve_entry(h, *params, u0, tstops, T_stops, k_table, n_stops, stats, nullptr, nullptr, 0, true), n_saved, retcode);
   KIN_CATCH(h)
 }
 
@@ -768,10 +445,7 @@ int kin_solve_continuous(kin_network* h, const kin_params* params, const double*
   if (!h) return KIN_ERR_INVALID_ARG;
   KIN_TRY(h)
   require(params && u0, ERR_INVALID_ARG, "params / u0 is null");
-  int rc = solve_entry(h, *params, u0, nullptr, nullptr, nullptr, 0, stats, t_nodes, T_nodes, n_nodes);
-  if (n_saved) *n_saved = h->n_saved;
-  if (retcode) *retcode = rc;
-  if (rc != KIN_RETCODE_SUCCESS) throw KinError(ERR_SOLVE_FAILED, "ODE solution failed.");
+  finish_solve(h, solve_entry(h, *params, u0, nullptr, nullptr, nullptr, 0, stats, t_nodes, T_nodes, n_nodes), n_saved, retcode);
   KIN_CATCH(h)
 }
 

@@ -624,16 +624,15 @@ bool ensemble_batched_supported(kin_network* h, std::string* why) {
   return E->ok;
 }
 
-// K members of one (large) network, advanced in lockstep rounds; returns the saved rows of the member whose save times are
-// those in out_t
-static int64_t batched_ensemble_block(kin_network* h, const EnsembleCall& c, int64_t* rows_out, const double** sol_out) {
+// K members of one (large) network, advanced in lockstep rounds: their results into out[K], the save times of each into
+// times[K]; the saved states stay in the solver's buffer, which is returned
+static const double* batched_ensemble_block(kin_network* h, const EnsembleCall& c, MemberResult* out, std::vector<double>* times) {
   auto wall0 = std::chrono::steady_clock::now();
   EnsembleSolver& E = *get_ensemble(h);
   if (!E.ok) throw KinError(ERR_UNSUPPORTED, E.why);
   hipStream_t s = h->stream;
   const int64_t N = h->host.N, R = h->host.R, K = c.K;
   const ResGrid g = make_res_grid(c.p);
-  if (c.n_rows) *c.n_rows = g.cap;
   const int slots = res_lu_slots(E.lu.slot_bytes(), K);
   E.prepare((int)K, slots, g.cap, c);
   ResParams P{};
@@ -648,49 +647,28 @@ static int64_t batched_ensemble_block(kin_network* h, const EnsembleCall& c, int
     for (int64_t t = 0; t < K; t++) stage_member_rates(h, c, t, h->Ea.p, h->A.p, E.reps[t].k, s);
   KIN_HIP(hipStreamSynchronize(s));
   std::vector<ResResult> res((size_t)K);
-  std::vector<std::string> errs((size_t)K);
-  std::vector<std::thread> th;
-  E.start_gj_server();
-  th.reserve((size_t)K);
-  std::string spawn_err;
-  for (int64_t t = 0; t < K; t++) {
-    try {
-      th.emplace_back([&, t] {
-        try {
-          (void)hipSetDevice(h->device);
-          // the member's own parameters: its stops (the shared ones, or its slice of a per-member call's)
-          const EnsembleCall::Stops ms = c.member_stops(t);
-          ResParams Pm = P;
-          Pm.tstops = ms.tstops; Pm.n_stops = (int32_t)ms.n;
-          MemberBackend b(E, (int)t, Pm, d_u0.p + (size_t)t * N, c.n_stops > 0 && c.k_table ? h->table.p : nullptr, ms.T_stops);
-          ResidentBdf<MemberBackend> ctl(b, Pm);
-          res[t] = ctl.run();
-        } catch (const std::exception& e) {
-          errs[t] = e.what();
-          res[t] = ResResult{};
-          res[t].retcode = RES_RET_UNSTABLE;
-        }
-        E.member_done();
-      });
-    } catch (const std::exception& e) {
-      // the host refused another thread: the members that never started leave the rounds (or the started ones would wait for them
-      // for ever), the started ones are joined (a joinable std::thread that goes out of scope terminates the process)
-      spawn_err = e.what();
-      for (int64_t q = t; q < K; q++) { res[q] = ResResult{}; res[q].retcode = RES_RET_UNSTABLE; E.member_done(); }
-      break;
-    }
+  {
+    // a member that ends, fails or never started leaves the rounds (or the others would wait for it for ever); the dense-inverse
+    // server stops once every thread is joined, whether or not the call goes on
+    struct Leave { EnsembleSolver& E; ~Leave() { E.member_done(); } };
+    struct Server { EnsembleSolver& E; ~Server() { E.stop_gj_server(); } } server{E};
+    E.start_gj_server();
+    run_member_threads(K, [&](int64_t t) {
+      Leave leave{E};
+      (void)hipSetDevice(h->device);
+      // the member's own parameters: its stops (the shared ones, or its slice of a per-member call's)
+      const EnsembleCall::Stops ms = c.member_stops(t);
+      ResParams Pm = P;
+      Pm.tstops = ms.tstops; Pm.n_stops = (int32_t)ms.n;
+      MemberBackend b(E, (int)t, Pm, d_u0.p + (size_t)t * N, c.n_stops > 0 && c.k_table ? h->table.p : nullptr, ms.T_stops);
+      ResidentBdf<MemberBackend> ctl(b, Pm);
+      res[(size_t)t] = ctl.run();
+    }, [&](int64_t) { E.member_done(); });
   }
-  for (auto& x : th) x.join();
-  E.stop_gj_server();
-  if (!spawn_err.empty()) throw KinError(ERR_DEVICE, "ensemble: could not start a member thread: " + spawn_err);
-  for (auto& e : errs) if (!e.empty()) throw KinError(ERR_DEVICE, "ensemble member failed: " + e);
   const double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - wall0).count();
   if (c.out_u) E.sol.download(c.out_u, (size_t)K * (size_t)g.cap * N, s);
   KIN_HIP(hipStreamSynchronize(s));
-  for (int64_t t = 0; t < K; t++) rows_out[t] = std::min<int64_t>(res[(size_t)t].n_saved, g.cap);
-  *sol_out = E.sol.p;
-  const int64_t best = res_member_outputs(res, g.cap, E.lu, slots, wall, c.n_saved, c.retcodes, c.stats);
-  if (c.out_t) std::copy(E.sol_t[best].begin(), E.sol_t[best].begin() + g.cap, c.out_t);
+  for (int64_t t = 0; t < K; t++) { out[t] = res_member_result(res[(size_t)t], E.lu, slots, wall); times[t] = E.sol_t[(size_t)t]; }
   if (getenv("KIN_TIMING")) {
     fprintf(stderr, "[ensemble] %lld members, %lld rounds, wall %.4f s: inside rounds %.4f s (enqueue %.4f, waiting for the device %.4f), "
             "between rounds %.4f s\n", (long long)K, (long long)E.n_rounds, wall, E.t_round, E.t_enqueue, E.t_sync, wall - E.t_round);
@@ -701,47 +679,34 @@ static int64_t batched_ensemble_block(kin_network* h, const EnsembleCall& c, int
             (long long)E.n_ops[K_VEC], (long long)E.n_ops[K_APPLY_RATES], (long long)E.n_ops[K_RHS], (long long)E.n_ops[K_JAC], (long long)E.n_ops[K_NORMS],
             (long long)E.n_ops[K_INIT_D], (long long)E.n_ops[K_DRIFT], (long long)E.n_ops[K_FACTOR], (long long)E.n_ops[K_CORRECTOR], (long long)E.n_ops[K_CORRECTOR_CONT]);
   }
-  return res[best].n_saved;
+  return E.sol.p;
 }
 
 // Every member's controller runs on a host thread of its own: an ensemble of more members than KIN_ENSEMBLE_MAX_MEMBERS
-// (default 128) is integrated block after block (the device is saturated long before that many members of a large network);
-// the save times are the members' common grid, taken from the block whose best member got furthest
+// (default 128) is integrated block after block (the device is saturated long before that many members of a large network)
 void batched_ensemble(kin_network* h, const EnsembleCall& c) {
   int64_t block = 128;
   if (const char* e = getenv("KIN_ENSEMBLE_MAX_MEMBERS")) block = std::max(1, atoi(e));
   const int64_t N = h->host.N, R = h->host.R;
   const int64_t cap = make_res_grid(c.p).cap;
-  std::vector<double> tt((size_t)cap);
-  int64_t best = -1;
+  if (c.n_rows) *c.n_rows = cap;
+  std::vector<MemberResult> res((size_t)c.K);
+  std::vector<std::vector<double>> times((size_t)c.K);
   // kin_ensemble_*: one block's states stay in the solver's buffer; several blocks reuse it, so each block's rows are copied
   // device-to-device into the handle's own [K][cap][N]
-  std::vector<int64_t> saved((size_t)c.K, 0);
   const double* sol = nullptr;
   const bool several = c.K > block;
   if (several) h->ens_sol.alloc((size_t)c.K * (size_t)cap * (size_t)N);
   for (int64_t m0 = 0; m0 < c.K; m0 += block) {
-    EnsembleCall b = c;
-    b.K = std::min(block, c.K - m0);
-    b.u0 = c.u0 + m0 * N;
-    if (c.k) b.k = c.k + m0 * R;
-    if (c.T) b.T = c.T + m0;
-    if (c.stop_ptr) b.stop_ptr = c.stop_ptr + m0;   // (member_stops reads tstops / T_stops at the absolute offsets)
-    if (c.d_Ea) { b.Ea = c.Ea + m0 * R; b.A = c.A + m0 * R; b.d_Ea = c.d_Ea + m0 * R; b.d_A = c.d_A + m0 * R; }
-    b.out_t = tt.data();
-    if (c.out_u) b.out_u = c.out_u + m0 * cap * N;
-    if (c.n_saved) b.n_saved = c.n_saved + m0;
-    if (c.retcodes) b.retcodes = c.retcodes + m0;
-    if (c.stats) b.stats = c.stats + m0;
-    const int64_t rows = batched_ensemble_block(h, b, saved.data() + m0, &sol);
-    if (c.out_t && rows > best) { std::copy(tt.begin(), tt.end(), c.out_t); best = rows; }
+    const EnsembleCall b = c.block(N, R, m0, std::min(block, c.K - m0));
+    sol = batched_ensemble_block(h, b, res.data() + m0, times.data() + m0);
     if (several) {
       KIN_HIP(hipMemcpyAsync(h->ens_sol.p + (size_t)m0 * (size_t)cap * (size_t)N, sol, (size_t)b.K * (size_t)cap * (size_t)N * sizeof(double),
                              hipMemcpyDeviceToDevice, h->stream));
       KIN_HIP(hipStreamSynchronize(h->stream));
     }
   }
-  h->set_ensemble_record(several ? h->ens_sol.p : sol, c.K, cap, std::move(saved));
+  finish_ensemble(h, c, cap, res, several ? h->ens_sol.p : sol, times.data());
 }
 
 }  // namespace kin

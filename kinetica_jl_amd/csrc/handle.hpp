@@ -147,7 +147,7 @@ struct kin_network {
   std::unique_ptr<kin::ResidentSolver, kin::ResidentDeleter> resident;   // one-workgroup-per-trajectory integrator (resident.cpp)
   std::unique_ptr<kin::EnsembleSolver, kin::EnsembleDeleter> ensemble;   // lockstep ensemble of large networks (ensemble.cpp)
   // solve-only copies of this handle (own stream, work vectors, Solver and LU cache; no sweep tables): a SMALL ensemble of a
-  // large network is K independent kin_solve calls on K host threads (capi.cpp: replica_ensemble)
+  // large network is K independent kin_solve calls on K host threads (ensemble_routes.cpp: replica_ensemble)
   std::vector<kin_network*> replicas;
   size_t lu_budget_mb = 0;   // device memory of this handle's LU cache (0: KIN_LU_CACHE_MB, default 32768); set on replicas
   std::vector<double> sol_t, sol_u;
@@ -156,8 +156,9 @@ struct kin_network {
 
   // The last ensemble call's saved states, where they live: sol[K][cap][N] (rows past n_saved[m] are zeros) in the resident
   // solver's or the lockstep ensemble's own buffer, or in ens_sol (thread route, lockstep calls of several blocks: the members'
-  // rows copied device-to-device). Cleared when an ensemble call starts, set when it succeeded; the buffers it may point to are
-  // reallocated by ensemble calls only (ResidentSolver::ensure with own_sol, EnsembleSolver::prepare, replica_ensemble).
+  // rows copied device-to-device). Cleared when an ensemble call starts (run_ensemble), set when it succeeded (finish_ensemble,
+  // both ensemble_routes.cpp); the buffers it may point to are reallocated by ensemble calls only (ResidentSolver::ensure with
+  // own_sol, EnsembleSolver::prepare, replica_ensemble).
   struct EnsembleRecord {
     const double* sol = nullptr;
     int64_t K = 0, cap = 0;

@@ -124,4 +124,22 @@ NetworkHost compile_network(int64_t n_species, int64_t n_reactions, const int64_
                             const int64_t* reac_idx, const int64_t* reac_sto, const int64_t* prod_ptr,
                             const int64_t* prod_idx, const int64_t* prod_sto, int index_base);
 
+// The guard of the entry points that take a network but no handle (kin_*_host): compiles it and runs `body` on the tables; a
+// KinError becomes its code, anything else ERR_INVALID_ARG, with the message left in `err`
+template <class Body>
+int with_compiled_network(int64_t n_species, int64_t n_reactions, const int64_t* reac_ptr, const int64_t* reac_idx,
+                          const int64_t* reac_sto, const int64_t* prod_ptr, const int64_t* prod_idx, const int64_t* prod_sto,
+                          int index_base, std::string& err, Body body) {
+  try {
+    body(compile_network(n_species, n_reactions, reac_ptr, reac_idx, reac_sto, prod_ptr, prod_idx, prod_sto, index_base));
+  } catch (const KinError& e) {
+    err = e.what();
+    return e.code;
+  } catch (const std::exception& e) {
+    err = e.what();
+    return ERR_INVALID_ARG;
+  }
+  return OK;
+}
+
 }  // namespace kin

@@ -308,12 +308,9 @@ void resident_ensemble(kin_network* h, const EnsembleCall& c) {
   run_resident(h, RS, c, g, (int)K, slots, res);
   const double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - wall0).count();
   if (c.out_u) RS.d_sol.download(c.out_u, (size_t)K * (size_t)g.cap * N, s);
-  std::vector<int64_t> rows((size_t)K);
-  for (int64_t t = 0; t < K; t++) rows[(size_t)t] = std::min<int64_t>(res[(size_t)t].n_saved, g.cap);
-  h->set_ensemble_record(RS.d_sol.p, K, g.cap, std::move(rows));   // (kin_ensemble_*: the members' states stay where they are)
-  const int64_t best = res_member_outputs(res, g.cap, RS.lu, slots, wall, c.n_saved, c.retcodes, c.stats);
-  if (c.out_t) KIN_HIP(hipMemcpyAsync(c.out_t, RS.d_solt.p + (size_t)best * (size_t)g.cap, (size_t)g.cap * sizeof(double), hipMemcpyDeviceToHost, s));
-  KIN_HIP(hipStreamSynchronize(s));
+  std::vector<MemberResult> out((size_t)K);
+  for (int64_t t = 0; t < K; t++) out[(size_t)t] = res_member_result(res[(size_t)t], RS.lu, slots, wall);
+  finish_ensemble(h, c, g.cap, out, RS.d_sol.p, nullptr, RS.d_solt.p);   // (kin_ensemble_*: the members' states stay where they are)
 }
 
 // Diagnostic: the kernel's own phases once per member on given inputs (resident_probe.hip), with the handle's current rates and

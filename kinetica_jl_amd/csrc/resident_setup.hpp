@@ -143,19 +143,16 @@ inline int64_t res_furthest(const std::vector<int64_t>& n_saved) {
   return std::max_element(n_saved.begin(), n_saved.end()) - n_saved.begin();
 }
 
-// an ensemble's per-member outputs from its members' results: n_saved (clamped to the save grid's `cap` rows), retcodes and
-// stats (each may be null); returns res_furthest of the members
+// One member's result as every ensemble route hands it to the finishing layer (solver.hpp: finish_members): its saved rows as the
+// integrator counted them, its retcode and its statistics
+struct MemberResult {
+  int64_t n_saved = 0;
+  int32_t retcode = 0;
+  kin_stats stats{};
+};
 template <class LU>
-int64_t res_member_outputs(const std::vector<ResResult>& res, int64_t cap, const LU& lu, int slots, double wall, int64_t* n_saved,
-                           int32_t* retcodes, kin_stats* stats) {
-  std::vector<int64_t> rows(res.size());
-  for (size_t t = 0; t < res.size(); t++) {
-    rows[t] = res[t].n_saved;
-    if (n_saved) n_saved[t] = std::min<int64_t>(res[t].n_saved, cap);
-    if (retcodes) retcodes[t] = res[t].retcode;
-    if (stats) stats[t] = res_stats(res[t], lu, slots, wall);
-  }
-  return res_furthest(rows);
+MemberResult res_member_result(const ResResult& r, const LU& lu, int slots, double wall) {
+  return MemberResult{r.n_saved, r.retcode, res_stats(r, lu, slots, wall)};
 }
 
 }  // namespace kin

@@ -112,7 +112,7 @@ struct HostBackend {
   // factorisations; its first second, a narrower ramp, only 446)
   int cache_slots() const {
     size_t budget_mb = lu_env_budget_mb();
-    if (h->lu_budget_mb > 0) budget_mb = std::min(budget_mb, h->lu_budget_mb);   // a replica's share (capi.cpp: replica_ensemble)
+    if (h->lu_budget_mb > 0) budget_mb = std::min(budget_mb, h->lu_budget_mb);   // a replica's share (ensemble_routes.cpp: replica_ensemble)
     const size_t fit = std::max<size_t>(1, budget_mb * 1024 * 1024 / std::max<size_t>(1, lu.slot_bytes()));
     return (int)std::min<size_t>(std::min<size_t>((size_t)lu_env_slots(128), fit), (size_t)LU_MAX_SLOTS);
   }

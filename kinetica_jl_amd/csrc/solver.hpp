@@ -1,13 +1,17 @@
 // BDF integrator + chunk/tstop driver behind kin_solve (solver.cpp, lu.cpp, solver_kernels.hip).
 #pragma once
+#include <functional>
 #include <string>
+#include <thread>
+#include <vector>
 #include "../../include/kinetica_hip.h"
 #include "handle.hpp"
+#include "resident_setup.hpp"
 
 namespace kin {
 
 // One ensemble call (kin_solve_ensemble / _continuous / _discrete), validated, as every route takes it (resident.cpp,
-// ensemble.cpp, capi.cpp: replica_ensemble): K members of the handle's network from u0[K][N]; per-member rate constants k[K][R],
+// ensemble.cpp, ensemble_routes.cpp: replica_ensemble): K members of the handle's network from u0[K][N]; per-member rate constants k[K][R],
 // or temperatures T[K] (Arrhenius), or else the handle's current rates for all; optional discrete rate updates shared by the
 // members (tstops + T_stops or k_table, n_stops of them); with stop_ptr, discrete rate updates of each member's own: member m
 // holds the Arrhenius rates at T_stops[j] from tstops[j] on, j in [stop_ptr[m], stop_ptr[m + 1]) of the concatenated arrays; or,
@@ -48,7 +52,103 @@ struct EnsembleCall {
     if (!stop_ptr) return {tstops, T_stops, n_stops};
     return {tstops + stop_ptr[m], T_stops + stop_ptr[m], stop_ptr[m + 1] - stop_ptr[m]};
   }
+  // The call restricted to members [m0, m0 + n) of a network of N species and R reactions: every per-member input and output is
+  // advanced to member m0, the shared inputs (p, the shared stops, k_table) and the call-wide outputs (n_rows, out_t) are left
+  // alone. The offsets in stop_ptr / node_ptr stay ABSOLUTE - member_stops and the continuous routes add them to tstops /
+  // T_stops / t_nodes / T_nodes - so those four do not move.
+  EnsembleCall block(int64_t N, int64_t R, int64_t m0, int64_t n) const {
+    EnsembleCall b = *this;
+    b.K = n;
+    const auto adv = [m0](auto*& q, int64_t stride) { if (q) q += m0 * stride; };
+    adv(b.u0, N); adv(b.k, R); adv(b.T, 1); adv(b.stop_ptr, 1); adv(b.node_ptr, 1);
+    adv(b.Ea, R); adv(b.A, R); adv(b.d_Ea, R); adv(b.d_A, R);
+    if (out_u) b.out_u += m0 * make_res_grid(p).cap * N;
+    adv(b.n_saved, 1); adv(b.retcodes, 1); adv(b.stats, 1);
+    return b;
+  }
 };
+
+// The finishing layer of every route, host part: the members' results into the call's per-member outputs (each may be null) -
+// n_saved clamped to the save grid's `cap` rows, retcodes, stats - and the call's out_t[cap]: the save times of res_furthest of
+// the members, zeros from its n_saved on. `times`: every member's save times on the host, or null when the furthest member's are
+// elsewhere (finish_ensemble then fetches them; the zeros are written here either way). Returns the clamped rows and that member.
+struct EnsembleRows { std::vector<int64_t> n_saved; int64_t best; };
+inline EnsembleRows finish_members(const EnsembleCall& c, int64_t cap, const MemberResult* res, const std::vector<double>* times) {
+  EnsembleRows f{std::vector<int64_t>((size_t)c.K), 0};
+  for (int64_t m = 0; m < c.K; m++) {
+    f.n_saved[(size_t)m] = std::min(res[m].n_saved, cap);
+    if (c.n_saved) c.n_saved[m] = f.n_saved[(size_t)m];
+    if (c.retcodes) c.retcodes[m] = res[m].retcode;
+    if (c.stats) c.stats[m] = res[m].stats;
+  }
+  f.best = res_furthest(f.n_saved);
+  if (c.out_t) {
+    int64_t n = f.n_saved[(size_t)f.best];
+    if (times) { n = std::min<int64_t>(n, (int64_t)times[f.best].size()); std::copy_n(times[f.best].begin(), n, c.out_t); }
+    std::fill(c.out_t + n, c.out_t + cap, 0.0);
+  }
+  return f;
+}
+// ... and the whole of it (ensemble_routes.cpp): finish_members, the furthest member's times from row `best` of dev_times[K][cap]
+// on the device where host_times is null, and the handle's ensemble record over sol[K][cap][N]. Drains the handle's stream.
+void finish_ensemble(kin_network* h, const EnsembleCall& c, int64_t cap, const std::vector<MemberResult>& res, const double* sol,
+                     const std::vector<double>* host_times, const double* dev_times = nullptr);
+
+// Member threads: body(i) for i in [0, n) on a host thread each. Every thread that started is joined before anything is thrown (a
+// joinable std::thread that goes out of scope terminates the process); when the host refuses a thread, never_started(q) is
+// called for that index and every later one - on the calling thread, while the started ones run - and no further thread is
+// tried. Then the spawn failure, else the first body's exception, is rethrown as a KinError.
+template <class Body, class NeverStarted>
+void run_member_threads(int64_t n, Body body, NeverStarted never_started) {
+  std::vector<std::string> errs((size_t)n);
+  std::vector<std::thread> th;
+  th.reserve((size_t)n);
+  std::string spawn_err;
+  for (int64_t i = 0; i < n && spawn_err.empty(); i++) {
+    try {
+      th.emplace_back([&, i] { try { body(i); } catch (const std::exception& e) { errs[(size_t)i] = e.what(); } });
+    } catch (const std::exception& e) {
+      spawn_err = e.what();
+      for (int64_t q = i; q < n; q++) never_started(q);
+    }
+  }
+  for (auto& x : th) x.join();
+  if (!spawn_err.empty()) throw KinError(ERR_DEVICE, "ensemble: could not start a member thread: " + spawn_err);
+  for (auto& e : errs) if (!e.empty()) throw KinError(ERR_DEVICE, "ensemble member failed: " + e);
+}
+
+// The thread route's assignment: K members over at most `limit` threads - `per` = ceil(K / limit) members a thread at the most,
+// `threads` = ceil(K / per) threads, member m on thread m mod threads (K <= limit: a thread per member; else the loads differ by
+// at most one)
+struct ThreadShare {
+  int64_t per, threads;
+  int64_t thread_of(int64_t m) const { return m % threads; }
+};
+inline ThreadShare replica_thread_share(int64_t K, int64_t limit) {
+  const int64_t per = ceil_div(K, limit);
+  return {per, ceil_div(K, per)};
+}
+
+// The ensemble entry points behind the extern "C" wrappers (ensemble_routes.cpp). ensemble_entry: the checks every form shares
+// - handle, params / u0 / K, the form's own `checks`, the save grid, then `validate` -, the size query (n_rows alone), or the call
+// with p filled in through run_ensemble: per-member parameters uploaded, route chosen (KIN_ENSEMBLE_ROUTE, KIN_ENSEMBLE_BATCHED)
+int ensemble_entry(kin_network* h, const kin_params* params, EnsembleCall c, const std::function<void()>& checks,
+                   const std::function<void()>& validate);
+// ... and the per-member forms through it: kin_solve_ensemble_continuous / _discrete and their _params forms (Ea == A == null:
+// the shared call, bit for bit). `nodes`: ptr / t / T are node_ptr / t_nodes / T_nodes, else stop_ptr / tstops / T_stops
+int ensemble_member_entry(kin_network* h, const kin_params* params, int64_t K, const double* u0, const double* Ea, const double* A,
+                          bool nodes, const int64_t* ptr, const double* t, const double* T, int64_t* n_rows, double* out_t,
+                          double* out_u, int64_t* n_saved, int32_t* retcodes, kin_stats* stats);
+// the compiled tables a solve reads on the device, and its work vectors, on the handle's stream (kin_network_create, which adds
+// the sweep tables; a replica of the thread route)
+void upload_solve_tables(kin_network* h);
+
+// what kin_solve / _explicit / _continuous hand back from solve_entry's retcode
+inline void finish_solve(const kin_network* h, int rc, int64_t* n_saved, int32_t* retcode) {
+  if (n_saved) *n_saved = h->n_saved;
+  if (retcode) *retcode = rc;
+  if (rc != KIN_RETCODE_SUCCESS) throw KinError(ERR_SOLVE_FAILED, "ODE solution failed.");
+}
 
 // Runs the whole solve (chunk loop, discrete rate updates, retry loop); stores the solution in
 // the handle; returns the final KIN_RETCODE_*.

@@ -50,6 +50,14 @@ def lib():
         L.res_host_step_op.argtypes = [c_void_p, c_int, P32, PD, PD, PD, PD]
         L.res_host_corrector_loop.restype = None
         L.res_host_corrector_loop.argtypes = [c_int, c_int, PD, PD, PD]
+        # the host parts of the ensemble call layer (tests/native/ensemble_call_host.cpp)
+        L.ens_host_block.restype = None
+        L.ens_host_block.argtypes = [POINTER(capi.KinParams), c_int64, c_int64, c_int64, P64, P64, c_int64, c_int64, c_int64, P64]
+        L.ens_host_thread_share.restype = None
+        L.ens_host_thread_share.argtypes = [c_int64, c_int64, P64, P64]
+        L.ens_host_finish.restype = c_int64
+        L.ens_host_finish.argtypes = [c_int64, c_int64, P64, P32, P64, PD, PD, P64, P32, POINTER(capi.KinStats), P64]
+        L.ens_host_runner.argtypes = [c_int64, c_int64, P32, P64, ctypes.c_char_p, c_int64]
         _lib = L
     return _lib
 

@@ -1006,6 +1006,68 @@ int kin_members_sobol_dev(kin_network* h, int64_t M, int64_t P, int64_t L, const
 int kin_ensemble_sobol(kin_network* h, int64_t M, int64_t P, const int32_t* w, const int64_t* species, int64_t n_sel, double* S1,
                        double* ST, double* mean, double* var /* L = n_rows */);
 
+/* ---- event times: per-species peak and level-crossing times of stored trajectories ---------------------------------------- */
+/* The questions asked of a kinetics run are timing questions - when does an intermediate peak, how long is the induction
+ * period before a product reaches 10 % of its final value, what is the half-life of the feed, how wide is a radical's pulse at
+ * half of its maximum - and over an ensemble their spread. This pass answers them where the states live.
+ *
+ * SEGMENTS. A segment s is a member of an ensemble, or the one trajectory of kin_solve: rows j = row_begin .. n_s - 1 of its
+ * block of L rows, states u[s][j][i], times t[j] (t[L] shared by all segments, or t[S][L] with t_per_segment != 0). With
+ * row_begin >= n_s the segment is empty. Rows at or past n_s are never read, neither their states nor their times.
+ *
+ * For every segment and species i:
+ *   u_peak[s][i]   the maximum over the segment's rows: seg_max's fmax chain, so with row_begin == 0 it equals kin_ensemble_max /
+ *                  kin_solution_max bit for bit. An empty segment gives 0.0.
+ *   t_peak[s][i]   t[j*], j* the first row that holds the peak. An empty segment gives `never`.
+ *   t_cross[s][i]  the time at which the species first crosses the level l:
+ *                    level_kind KIN_LEVEL_ABS       l = level[i]
+ *                               KIN_LEVEL_OF_PEAK   l = level[i] * u_peak[s][i]
+ *                               KIN_LEVEL_OF_START  l = level[i] * u[s][row_begin][i]      (one multiplication, rounded once)
+ *                  The search starts at row j0 = row_begin (start KIN_FROM_BEGIN) or j0 = j* (KIN_FROM_PEAK). jc is the first row
+ *                  j >= j0 with u[j] >= l (direction > 0, rising) or u[j] <= l (direction < 0, falling). No such row: `never`.
+ *                  jc == j0: t[j0]. Otherwise, with a = u[jc - 1] and b = u[jc], the chord
+ *                    t[jc - 1] + ((l - a) / (b - a)) * (t[jc] - t[jc - 1])
+ *                  evaluated in exactly this order in IEEE double arithmetic, every operation rounded on its own: the kernel is
+ *                  compiled with floating-point contraction off (#pragma clang fp contract(off) over event_kernels.hip, which
+ *                  is what __dsub_rn / __ddiv_rn / __dmul_rn / __dadd_rn would spell operation by operation), so no
+ *                  multiplication fuses with an addition. By construction a < l <= b (a > l >= b): b - a is never zero.
+ *                  An empty segment gives `never`.
+ * `never` is the caller's: NaN marks "no such time"; the last saved time censors instead.
+ * A NaN among the rows that take part: u_peak follows fmax (a NaN row is passed over unless every row is NaN); nothing else
+ * is specified for that species.
+ *
+ * Every output is an extremum or a first index, never a sum: the result is exactly defined whatever the decomposition, and is
+ * the same bits from call to call, between the host and the device entry, and whatever else the call holds. How it is
+ * computed (event_kernels.hip): one launch, no atomics; a workgroup owns (segment, 64 species), lanes along the species, its 4
+ * to 16 wavefronts take the parts of the segment's rows in turn and combine by "larger value, then smaller row" (peak) and
+ * "smaller row" (crossing); KIN_LEVEL_ABS and KIN_LEVEL_OF_START from KIN_FROM_BEGIN read the states once, a level or start
+ * that depends on the peak a second time in the same workgroup. KIN_EVENT_PART_ROWS caps the rows of a part and
+ * KIN_EVENT_WAVES sets the wavefronts (read per call; test knobs: results do not depend on them).
+ *
+ * Outputs [S][N]; any may be NULL, not all three; level may be NULL when t_cross is. Statuses: KIN_ERR_INVALID_ARG for S or
+ * L < 0, a null u or t with S L > 0, every output null, t_cross without level, direction == 0, an unknown level_kind or start,
+ * row_begin < 0, and from the host entries a seg_n outside [0, L] or a t that is not strictly increasing over the rows read;
+ * KIN_ERR_UNSUPPORTED for S or L >= 2^31 or N > 64 * 65535; KIN_ERR_STATE from kin_ensemble_events / kin_solution_events without
+ * a stored ensemble / solution. S L = 0 writes the empty-segment values; N = 0 writes nothing. A refused call leaves the
+ * handle as it was. The device entry only enqueues (d_seg_n: S int64 on the device, or NULL: L rows each); one stream per handle
+ * at a time. Added under KIN_ABI_VERSION 6: look the symbols up before calling them. */
+enum { KIN_LEVEL_ABS = 0, KIN_LEVEL_OF_PEAK = 1, KIN_LEVEL_OF_START = 2 };
+enum { KIN_FROM_BEGIN = 0, KIN_FROM_PEAK = 1 };
+int kin_events_segmented_dev(kin_network* h, int64_t S, int64_t L, const int64_t* d_seg_n, const double* d_u /* [S][L][N] */,
+                             const double* d_t /* [L] or [S][L] */, int t_per_segment, const double* d_level /* [N] */, int level_kind,
+                             int direction, int start, int64_t row_begin, double never, double* d_u_peak, double* d_t_peak,
+                             double* d_t_cross /* [S][N] each */, void* stream);
+int kin_events_segmented(kin_network* h, int64_t S, int64_t L, const int64_t* seg_n, const double* u, const double* t, int t_per_segment,
+                         const double* level, int level_kind, int direction, int start, int64_t row_begin, double never,
+                         double* u_peak, double* t_peak, double* t_cross);
+/* kin_events_segmented over the stored ensemble (S = K, L = n_rows, seg_n = n_saved), read where it lives. t: the save grid
+ * [n_rows], or with t_per_member != 0 every member's own [K][n_rows] (entries of rows j >= n_saved[m] are ignored). */
+int kin_ensemble_events(kin_network* h, const double* t, int t_per_member, const double* level, int level_kind, int direction, int start,
+                        int64_t row_begin, double never, double* u_peak, double* t_peak, double* t_cross /* [K][N] each */);
+/* The same over the stored states of the last kin_solve (S = 1, L = n_saved) and its saved times. */
+int kin_solution_events(kin_network* h, const double* level, int level_kind, int direction, int start, int64_t row_begin, double never,
+                        double* u_peak, double* t_peak, double* t_cross /* [N] each */);
+
 /* ---- device / build information ------------------------------------------------------- */
 int kin_device_count(int* n);
 /* Selects the device for handles created afterwards by this thread; a handle remembers the device it was created on
@@ -1024,7 +1086,8 @@ const char* kin_version(void);
  * kin_solution_pfa, kin_ensemble_pfa, and reaction elimination: kin_reaction_importance_*, kin_solution_reaction_importance,
  * kin_ensemble_reaction_importance, and the cross-member statistics: kin_members_*, kin_ensemble_moments / _quantiles /
  * _correlate, and the Sobol indices: kin_members_sobol, kin_members_sobol_dev, kin_ensemble_sobol, and the
- * per-member Arrhenius parameters: kin_solve_ensemble_continuous_params, kin_solve_ensemble_discrete_params). */
+ * per-member Arrhenius parameters: kin_solve_ensemble_continuous_params, kin_solve_ensemble_discrete_params, and the event
+ * times: kin_events_segmented, kin_events_segmented_dev, kin_ensemble_events, kin_solution_events). */
 #define KIN_ABI_VERSION 6
 int kin_abi_version(void);
 int64_t kin_struct_size(int which); /* 0: sizeof(kin_params), 1: sizeof(kin_stats), else -1 */

@@ -45,6 +45,7 @@ SYMBOLS = [
     "kin_members_inputs_host", "kin_members_moments", "kin_members_moments_dev", "kin_members_quantiles", "kin_members_quantiles_dev",
     "kin_members_correlate", "kin_members_correlate_dev", "kin_ensemble_moments", "kin_ensemble_quantiles", "kin_ensemble_correlate",
     "kin_members_sobol", "kin_members_sobol_dev", "kin_ensemble_sobol",
+    "kin_events_segmented", "kin_events_segmented_dev", "kin_ensemble_events", "kin_solution_events",
     "kin_flux_plan_host", "kin_network_compute_units",
     "kin_sweep_plan", "kin_sweep_plan_host", "kin_tiled_sweep_plan", "kin_tiled_sweep_plan_host",
 ]
@@ -52,6 +53,11 @@ SYMBOLS = [
 DRGEP_IN_SHORT_MAX, DRGEP_IN_WAVE_MAX = 32, 256
 MEMBERS_MAX_SORTED = 4096   # include/kinetica_hip.h: KIN_MEMBERS_MAX_SORTED, the participants quantiles and rank correlations take
 ABI_VERSION = 6   # include/kinetica_hip.h: KIN_ABI_VERSION this binding was written against
+# the event-time pass (include/kinetica_hip.h: KIN_LEVEL_*, the sign of `direction`, KIN_FROM_*) and the names of its results
+EVENT_KINDS = dict(abs=0, of_peak=1, of_start=2)
+EVENT_DIRECTIONS = dict(rise=1, fall=-1)
+EVENT_STARTS = dict(begin=0, peak=1)
+EVENT_OUTPUTS = ("u_peak", "t_peak", "t_cross")
 
 
 # kin_step_probe (include/kinetica_hip.h): rows of the state block, fields of the flattened control block, argument slots
@@ -100,6 +106,7 @@ _NET = [c_int64, c_int64] + [P64] * 6 + [c_int]     # a *_host entry's leading a
 _SOLVED = [P64, POINTER(c_int32), POINTER(KinStats)]      # n_saved, retcode, stats of a solve
 _MEMBERS = [P64, PD, PD, P64, POINTER(c_int32), POINTER(KinStats)]      # n_rows, out_t, out_u, n_saved, retcodes, stats of an ensemble
 _KSRC = [PD, c_int64, P64, PD]      # the rate constants of a pass on host arrays: k, n_k_rows, k_row, T
+_EVENT = [c_int, c_int, c_int, c_int64, c_double]      # what an event-time pass looks for: level_kind, direction, start, row_begin, never
 ARGTYPES = {
     "kin_struct_size": [c_int], "kin_last_error": [PV],
     "kin_network_create": _NET + [POINTER(PV)], "kin_network_destroy": [PV], "kin_network_sizes": [PV, P64, P64],
@@ -187,6 +194,10 @@ ARGTYPES = {
     "kin_members_sobol": [PV, c_int64, c_int64, c_int64, PD, P32, P64, c_int64, PD, PD, PD, PD],
     "kin_members_sobol_dev": [PV, c_int64, c_int64, c_int64, PV, P32, P64, c_int64] + [PV] * 5,
     "kin_ensemble_sobol": [PV, c_int64, c_int64, P32, P64, c_int64, PD, PD, PD, PD],
+    # event times
+    "kin_events_segmented": [PV, c_int64, c_int64, P64, PD, PD, c_int, PD] + _EVENT + [PD, PD, PD],
+    "kin_events_segmented_dev": [PV, c_int64, c_int64, PV, PV, PV, c_int, PV] + _EVENT + [PV] * 4,
+    "kin_ensemble_events": [PV, PD, c_int, PD] + _EVENT + [PD, PD, PD], "kin_solution_events": [PV, PD] + _EVENT + [PD, PD, PD],
 }
 
 _lib = None
@@ -489,6 +500,7 @@ class HipNetwork:
             raise KineticaHipError(st, lib().kin_last_error(None).decode())
         self.n = int(n_species)
         self.nr = len(arrs[0]) - 1
+        self.index_base = int(index_base)
 
     @classmethod
     def from_flat(cls, net):
@@ -1148,6 +1160,96 @@ class HipNetwork:
         """kin_ensemble_sobol: members_sobol over the stored ensemble, read where it lives (w None: the samples all of whose
         members completed the save grid)."""
         return self._sobol("kin_ensemble_sobol", None, M, P, species, w)
+
+    # --- event times: per-species peak and level-crossing times ----------------------------------------------
+    @staticmethod
+    def _event_code(value, names, what):
+        """A level kind, direction or start by name (ValueError for an unknown one) or as the integer the library takes."""
+        if isinstance(value, str):
+            if value not in names:
+                raise ValueError(f"{what} must be one of {tuple(names)}; got {value!r}")
+            return names[value]
+        return int(value)
+
+    def _event_opts(self, level, kind, direction, start, row_begin, never, want):
+        """(level[N] or None, the C arguments level_kind .. never, the wanted outputs): a scalar level broadcasts to [N]; without
+        a level t_cross is not wanted."""
+        want = tuple(want)
+        bad = [w for w in want if w not in EVENT_OUTPUTS]
+        if bad or not want:
+            raise ValueError(f"want must name some of {EVENT_OUTPUTS}; got {want}")
+        if level is None:
+            if "t_cross" in want and want != EVENT_OUTPUTS:
+                raise ValueError("t_cross needs a level")
+            want = tuple(w for w in want if w != "t_cross")
+        else:
+            level = np.asarray(level, dtype=np.float64)      # (ascontiguousarray would make a number an array of one)
+            if level.ndim == 0:
+                level = np.full(self.n, float(level))
+            level = np.ascontiguousarray(level.ravel())
+            if len(level) != self.n:
+                raise ValueError(f"level must be a number or one per species ({self.n}); got {len(level)}")
+        codes = (self._event_code(kind, EVENT_KINDS, "kind"), self._event_code(direction, EVENT_DIRECTIONS, "direction"),
+                 self._event_code(start, EVENT_STARTS, "start"), int(row_begin), float(never))
+        return level, codes, want
+
+    def _event_times(self, t, S, L):
+        """(t as float64, the t_per_segment flag): t[L] shared by the S segments, or t[S][L]."""
+        t = np.ascontiguousarray(_f64(t))
+        if t.shape == (L,):
+            return t, 0
+        if t.shape == (S, L):
+            return t, 1
+        raise ValueError(f"t must be [{L}] (one save grid) or [{S}][{L}] (one per segment); got {t.shape}")
+
+    def _events(self, entry, shape, head, level, codes, want):
+        out = {w: np.empty(shape) for w in want}
+        self._chk(getattr(lib(), entry)(self._h, *head, _pd(level), *codes, *[_pd(out.get(w)) for w in EVENT_OUTPUTS]))
+        return out
+
+    def events_segmented(self, u, t, level=None, kind="abs", direction="rise", start="begin", row_begin=0, never=float("nan"),
+                         seg_n=None, want=EVENT_OUTPUTS):
+        """kin_events_segmented on host arrays: u[S][L][N] (S segments of up to L rows, seg_n[S] of them real; None: L each), times
+        t[L] or t[S][L]. Returns a dict of u_peak, t_peak, t_cross [S][N] (those `want` names; without a level no t_cross): the
+        maximum over a segment's rows from row_begin on, the time of the first row that holds it, and the time at which the
+        species first reaches the level - `level` a number or [N]; kind "abs": the level itself, "of_peak": level x the peak,
+        "of_start": level x the value at row_begin; direction "rise" (u >= l) or "fall" (u <= l); start "begin" (search from
+        row_begin) or "peak" (from the peak's row) - by the chord between the two rows around the crossing; `never` where no row
+        meets the level or the segment is empty (include/kinetica_hip.h has the definitions)."""
+        u, S, L = self._ms_block(u, self.n)
+        if seg_n is not None:
+            seg_n = np.ascontiguousarray(seg_n, dtype=np.int64).ravel()
+            if len(seg_n) != S:
+                raise ValueError(f"seg_n must have one entry per segment ({S}); got {len(seg_n)}")
+        t, flag = self._event_times(t, S, L)
+        level, codes, want = self._event_opts(level, kind, direction, start, row_begin, never, want)
+        return self._events("kin_events_segmented", (S, self.n), (S, L, _p64(seg_n), _pd(u), _pd(t), flag), level, codes, want)
+
+    def events_segmented_dev(self, S, L, d_u, d_t, d_level=0, kind="abs", direction="rise", start="begin", row_begin=0,
+                             never=float("nan"), d_seg_n=0, t_per_segment=False, d_u_peak=0, d_t_peak=0, d_t_cross=0, stream=0):
+        """kin_events_segmented_dev: device pointers (ints; 0 = not given / not wanted) u[S][L][N], t[L] (t[S][L] with
+        t_per_segment), level[N], seg_n[S] (int64) and u_peak / t_peak / t_cross [S][N]. Only enqueues; one stream per handle
+        at a time."""
+        codes = (self._event_code(kind, EVENT_KINDS, "kind"), self._event_code(direction, EVENT_DIRECTIONS, "direction"),
+                 self._event_code(start, EVENT_STARTS, "start"), int(row_begin), float(never))
+        self._chk(lib().kin_events_segmented_dev(self._h, int(S), int(L), _dp(d_seg_n), _dp(d_u), _dp(d_t), int(bool(t_per_segment)),
+                                                 _dp(d_level), *codes, _dp(d_u_peak), _dp(d_t_peak), _dp(d_t_cross), _dp(stream)))
+
+    def ensemble_events(self, t, level=None, kind="abs", direction="rise", start="begin", row_begin=0, never=float("nan"),
+                        want=EVENT_OUTPUTS):
+        """kin_ensemble_events: events_segmented over the stored ensemble, every member's own saved rows read where they live;
+        t: the save grid [n_rows] or one per member [K][n_rows]. Returns the dict of [K][N] arrays."""
+        K, L = self.ensemble_size()[:2]
+        t, flag = self._event_times(t, K, L)
+        level, codes, want = self._event_opts(level, kind, direction, start, row_begin, never, want)
+        return self._events("kin_ensemble_events", (K, self.n), (_pd(t), flag), level, codes, want)
+
+    def solution_events(self, level=None, kind="abs", direction="rise", start="begin", row_begin=0, never=float("nan"),
+                        want=EVENT_OUTPUTS):
+        """kin_solution_events: the same over the saved states and times of the last solve, read where they live. Returns the
+        dict of [N] arrays."""
+        level, codes, want = self._event_opts(level, kind, direction, start, row_begin, never, want)
+        return self._events("kin_solution_events", (self.n,), (), level, codes, want)
 
     # --- library order (tiled sweep) --------------------------------------------------------
     def lib_layout(self):

@@ -466,6 +466,7 @@ class ODESolution:
     umax: Optional[np.ndarray] = None    # max over saved times per species, reduced on the device (kin_solution_max)
     fluxes: Optional[object] = None      # ReactionFluxes of the solve (solve_network_ensemble(fluxes=True)), else None
     ensemble_stats: Optional[object] = None   # the ensemble's one EnsembleStatistics (solve_network_ensemble(statistics=...)), else None
+    events: Optional[object] = None      # the ensemble's one EventTimes (solve_network_ensemble(events=...)), else None
 
     def __call__(self, tq):
         """Linear interpolation res.sol(t) (docs/src/getting-started.md:232-236)."""
@@ -740,7 +741,7 @@ def apply_ensemble_low_k_cutoff(rd, calc, pars, condition_sets, calculators=None
 
 
 def solve_network_ensemble(methods, sd, rd, copy_network=True, fluxes=False, trajectories=True, statistics=None,
-                           member_calculators=False):
+                           member_calculators=False, events=None):
     """EXTENSION (the reference has no ensemble call: it solves member after member through solve_network): K
     `VariableODESolve`s with Arrhenius condition sets - one temperature profile each, e.g. a set of heating rates or start
     temperatures - on one network in ONE ensemble call: kin_solve_ensemble_continuous when every set is continuous,
@@ -780,11 +781,19 @@ def solve_network_ensemble(methods, sd, rd, copy_network=True, fluxes=False, tra
     the device before the handle closes (with trajectories=False no state is downloaded). The key sobol=dict(M=, P=, ...) -
     sobol_indices' keyword arguments, species again 0-based - declares the methods a Saltelli design in sobol_design's layout
     (len(methods) == M (P + 2)) and fills ensemble_stats.sobol with its SobolIndices. A malformed `statistics` raises
-    ValueError before anything touches the GPU. None (the default): nothing is computed."""
+    ValueError before anything touches the GPU. None (the default): nothing is computed. The keys of="t_peak" | "t_cross" with
+    events=dict(...) take the statistics of that event time instead of the states (ensemble_statistics), and the sobol dict has
+    the same two keys (sobol_indices).
+
+    events=dict of event_times' keyword arguments (level, kind, direction, start, t_min, never, species; species 0-based ids
+    of the network as it is solved): every member's sol.events refers to ONE shared EventTimes - per member and species the
+    peak, its time and the time a level is first crossed - computed from the states where they live on the device before the
+    handle closes; it works with trajectories=False. A malformed dict raises ValueError before anything touches the GPU."""
     methods = list(methods)
     if not methods:
         raise ValueError("solve_network_ensemble needs at least one method")
     stat_kw = _statistics_arguments(statistics, len(methods))
+    ev_kw = None if events is None else _event_arguments(events)
     m0 = methods[0]
     for m in methods:
         if not isinstance(m, VariableODESolve) or not isinstance(m.calculator, PrecalculatedArrheniusCalculator):
@@ -834,6 +843,11 @@ def solve_network_ensemble(methods, sd, rd, copy_network=True, fluxes=False, tra
     sob_kw = None if stat_kw is None else stat_kw.get("sobol")
     if sob_kw is not None and sob_kw["species"] is not None and sob_kw["species"].max(initial=-1) >= sd_a.n:
         raise ValueError(f"statistics: sobol species ids must be below the {sd_a.n} species of the network as it is solved")
+    if ev_kw is not None:
+        if ev_kw["species"] is not None and ev_kw["species"].max(initial=-1) >= sd_a.n:
+            raise ValueError(f"events: species ids must be below the {sd_a.n} species of the network as it is solved")
+        if np.ndim(ev_kw["level"]) == 1 and len(ev_kw["level"]) != sd_a.n:
+            raise ValueError(f"events: level must be a number or one per species of the network as it is solved ({sd_a.n})")
     if discrete:
         # each member's (tstops, T(tstops)), as solve_network hands them to kin_solve
         stops = [discrete_stop_temperatures(m.conditions) for m in methods]
@@ -871,6 +885,11 @@ def solve_network_ensemble(methods, sd, rd, copy_network=True, fluxes=False, tra
             stats.species = sp0
             if sob_kw is not None:
                 stats.sobol.species = sb0
+        ev = None
+        if ev_kw is not None:
+            ev0 = ev_kw["species"]
+            ev = event_times(h, t=t, **dict(ev_kw, species=None if ev0 is None else ev0 + 1))
+            ev.species = ev0
     finally:
         h.close()
     out = []
@@ -895,6 +914,7 @@ def solve_network_ensemble(methods, sd, rd, copy_network=True, fluxes=False, tra
         sol = ODESolution(ti, ui, capi.RETCODE_NAMES[int(rcs[i])], k=sol_k, stats=st, umax=umax, fluxes=fl)
         if stat_kw is not None:
             sol.ensemble_stats = stats
+        sol.events = ev
         out.append(ODESolveOutput(sd_a, rd_a, sol, sol_k, sol_vcs, m.pars, m.conditions))
     return out
 
@@ -946,12 +966,15 @@ def _statistics_arguments(statistics, K):
         statistics = {}
     if not isinstance(statistics, dict):
         raise ValueError("statistics must be None, True or a dict of ensemble_statistics' keyword arguments")
-    known = ("quantiles", "species", "inputs", "rank", "use", "sobol")
+    known = ("quantiles", "species", "inputs", "rank", "use", "sobol", "of", "events")
     bad = [k for k in statistics if k not in known]
     if bad:
         raise ValueError(f"statistics: unknown keys {bad}; choose among {known}")
     kw = dict(quantiles=(0.05, 0.5, 0.95), species=None, inputs=None, rank=True, use=None)
     kw.update(statistics)
+    ev = _of_arguments("statistics", kw.pop("of", "states"), kw.pop("events", None), ("states", "t_peak", "t_cross"))
+    if ev is not None:      # (of="states", the default: the keywords as they always were)
+        kw.update(of=statistics["of"], events=ev)
     if kw.get("sobol") is not None:
         kw["sobol"] = _sobol_arguments(kw["sobol"], K)
     else:
@@ -984,18 +1007,34 @@ def _statistics_arguments(statistics, K):
     return kw
 
 
-def ensemble_statistics(h, t, quantiles=(0.05, 0.5, 0.95), species=None, inputs=None, rank=True, use=None, sobol=None):
+def ensemble_statistics(h, t, quantiles=(0.05, 0.5, 0.95), species=None, inputs=None, rank=True, use=None, sobol=None, of="states",
+                        events=None):
     """Statistics across the members of the ensemble stored in the handle `h` (a capi.HipNetwork after a solve_ensemble* call,
     trajectories downloaded or not), read where the states live on the device: kin_ensemble_moments, kin_ensemble_quantiles
     (quantiles: probabilities in [0, 1]; None or empty: none) and, with inputs[K][P] (one row per member: whatever was sampled -
     log-multipliers of rate constants, temperatures, heating rates, u0 entries), kin_ensemble_correlate. species: ids in the
     handle's index base, None for all. use: a mask over the members, None for those that completed the save grid `t`.
-    sobol: a dict of sobol_indices' keyword arguments (M, P, ...) when the ensemble is a Saltelli design; fills `.sobol`."""
-    m = h.ensemble_moments(use=use)
+    sobol: a dict of sobol_indices' keyword arguments (M, P, ...) when the ensemble is a Saltelli design; fills `.sobol`.
+    of="t_peak" | "t_cross" with events=dict of event_times' keyword arguments (no species: `species` selects): the statistics
+    of that event time over the members instead of the states - the [K][1][N] array of kin_ensemble_events handed to
+    kin_members_moments / _quantiles / _correlate, every result with one row; `never` entries go into them as they are, so a
+    species some participant never crosses takes whatever the statistic does with that value (NaN spreads; a censoring
+    value counts as a time)."""
+    events = _of_arguments("ensemble_statistics", of, events, ("states", "t_peak", "t_cross"))
     p = np.atleast_1d(np.asarray(() if quantiles is None else quantiles, dtype=float))
     sp = None if species is None else np.asarray(species, dtype=np.int64)
-    qv = h.ensemble_quantiles(p, species=sp, use=use) if len(p) else None
-    corr = None if inputs is None else h.ensemble_correlate(inputs, species=sp, rank=rank, use=use)
+    if of == "states":
+        m = h.ensemble_moments(use=use)
+        qv = h.ensemble_quantiles(p, species=sp, use=use) if len(p) else None
+        corr = None if inputs is None else h.ensemble_correlate(inputs, species=sp, rank=rank, use=use)
+    else:
+        arr = _event_block(h, t, of, events)
+        if use is None:      # (the stored forms' default: the members that completed the save grid)
+            _, rows, _, n_saved = h.ensemble_size()
+            use = n_saved == rows
+        m = h.members_moments(arr, use=use)
+        qv = h.members_quantiles(arr, p, species=sp, use=use) if len(p) else None
+        corr = None if inputs is None else h.members_correlate(arr, inputs, species=sp, rank=rank, use=use)
     sob = None if sobol is None else sobol_indices(h, t, **sobol)
     st = EnsembleStatistics(np.asarray(t, dtype=float), m["count"], m["mean"], m["var"], m["min"], m["max"], quantiles=qv,
                             p=p if len(p) else None, species=sp, corr=corr, rank=bool(rank))
@@ -1117,7 +1156,8 @@ class SobolIndices:
         return np.argsort(np.where(np.isnan(v), -np.inf, v) * -1.0, kind="stable")
 
 
-_SOBOL_KEYS = ("M", "P", "species", "w", "of", "n_boot", "seed", "level")
+_SOBOL_KEYS = ("M", "P", "species", "w", "of", "n_boot", "seed", "level", "events")
+_SOBOL_OF = ("states", "max", "t_peak", "t_cross")
 
 
 def _sobol_arguments(sobol, K):
@@ -1130,6 +1170,9 @@ def _sobol_arguments(sobol, K):
         raise ValueError(f"statistics: unknown sobol keys {bad}; choose among {_SOBOL_KEYS}")
     kw = dict(species=None, w=None, of="states", n_boot=0, seed=0, level=0.95)
     kw.update(sobol)
+    ev = _of_arguments("statistics: sobol", kw["of"], kw.pop("events", None), _SOBOL_OF)
+    if ev is not None:      # (an event time's indices: the one case with this key)
+        kw["events"] = ev
     for name in ("M", "P"):
         v = kw.get(name)
         if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
@@ -1148,8 +1191,6 @@ def _sobol_arguments(sobol, K):
         if w.shape != (kw["M"],) or w.dtype.kind not in "iu" or (w < 0).any():
             raise ValueError(f"statistics: sobol w must be {kw['M']} integer multiplicities >= 0")
         kw["w"] = w.astype(np.int32)
-    if kw["of"] not in ("states", "max"):
-        raise ValueError("statistics: sobol of must be 'states' or 'max'")
     nb = kw["n_boot"]
     if isinstance(nb, bool) or not isinstance(nb, (int, np.integer)) or nb < 0:
         raise ValueError("statistics: sobol n_boot must be an integer >= 0")
@@ -1159,19 +1200,21 @@ def _sobol_arguments(sobol, K):
     return kw
 
 
-def sobol_indices(h, t, M, P, species=None, w=None, of="states", n_boot=0, seed=0, level=0.95):
+def sobol_indices(h, t, M, P, species=None, w=None, of="states", n_boot=0, seed=0, level=0.95, events=None):
     """First-order and total-effect Sobol indices of the Saltelli design stored in the handle `h` (a capi.HipNetwork after a
     solve_ensemble* call over the K = M (P + 2) members of sobol_design, trajectories downloaded or not), read where the states
     live on the device (kin_ensemble_sobol). species: ids in the handle's index base, None for all. w: int multiplicities per
     base sample, None for 1 where all P + 2 members of a sample completed the save grid `t`, else 0.
     of="states": the indices of every species at every saved time; of="max": of every species' peak value over a member's own
-    rows (kin_ensemble_max's [K][N] handed to kin_members_sobol as one row; `t` is kept as given).
+    rows (kin_ensemble_max's [K][N] handed to kin_members_sobol as one row; `t` is kept as given); of="t_peak" | "t_cross" with
+    events=dict of event_times' keyword arguments (no species: `species` selects): of that event time of every species -
+    which input controls an induction time or a half-life - kin_ensemble_events' [K][N] handed over the same way (`never`
+    entries of participating members go into the sums as they are).
     n_boot > 0: bootstrap percentile intervals at `level` - n_boot replicates, each the multinomial multiplicities of
     resampling the participants with replacement (np.random.default_rng(seed)), one device pass per replicate."""
-    if of not in ("states", "max"):
-        raise ValueError("of must be 'states' or 'max'")
-    if of == "max":
-        umax = h.ensemble_max()[:, None, :]
+    events = _of_arguments("sobol_indices", of, events, _SOBOL_OF)
+    if of != "states":
+        umax = h.ensemble_max()[:, None, :] if of == "max" else _event_block(h, t, of, events)
         base = h.ensemble_sobol_weights(M, P) if w is None else np.asarray(w)
         run = lambda wt: h.members_sobol(umax, M, P, species=species, w=wt)
         r = run(base)      # (a failed member's peak is no peak: its sample is dropped here as over the states)
@@ -1197,6 +1240,163 @@ def sobol_indices(h, t, M, P, species=None, w=None, of="states", n_boot=0, seed=
     sp = None if species is None else np.asarray(species, dtype=np.int64)
     return SobolIndices(np.asarray(t, dtype=float), r["count"], r["first"], r["total"], r["mean"], r["var"], species=sp,
                         first_ci=ci[0], total_ci=ci[1])
+
+
+# ---- event times: when a species peaks and when it crosses a level (EXTENSION) ------------------------------------------------
+@dataclass
+class EventTimes:
+    """Result of event_times. Per segment - the members of an ensemble, [K][n_sel], or the one trajectory of a solve, [n_sel] -
+    and selected species (`species` as the caller gave them; None: all): u_peak the maximum over the rows that take part,
+    t_peak the time of the first row that holds it, t_cross the time at which the species first reaches the level, by the
+    chord between the two saved rows around the crossing (None when no level was given); `never` where there is no such time
+    (include/kinetica_hip.h has the definitions). t: the saved times; the other fields are the request."""
+    t: np.ndarray
+    u_peak: np.ndarray
+    t_peak: np.ndarray
+    t_cross: Optional[np.ndarray]
+    level: Optional[np.ndarray] = None
+    kind: str = "abs"
+    direction: str = "rise"
+    start: str = "begin"
+    t_min: Optional[float] = None
+    never: float = float("nan")
+    species: Optional[np.ndarray] = None
+
+
+_EVENT_KEYS = ("level", "kind", "direction", "start", "t_min", "never", "species")
+
+
+def _event_arguments(events, what="events"):
+    """A dict of event_times' keyword arguments, completed with the defaults; ValueError for anything malformed - nothing here
+    touches the device. level comes back None, a float or a float array [N]; species None or int64 ids."""
+    if not isinstance(events, dict):
+        raise ValueError(f"{what} must be a dict of event_times' keyword arguments {_EVENT_KEYS}")
+    bad = [k for k in events if k not in _EVENT_KEYS]
+    if bad:
+        raise ValueError(f"{what}: unknown keys {bad}; choose among {_EVENT_KEYS}")
+    kw = dict(level=None, kind="abs", direction="rise", start="begin", t_min=None, never=float("nan"), species=None)
+    kw.update(events)
+    if kw["level"] is not None:
+        try:
+            lv = np.asarray(kw["level"], dtype=float)
+        except (TypeError, ValueError):
+            raise ValueError(f"{what}: level must be a number or one number per species") from None
+        if lv.ndim > 1 or isinstance(kw["level"], (bool, np.bool_)):
+            raise ValueError(f"{what}: level must be a number or one number per species")
+        kw["level"] = float(lv) if lv.ndim == 0 else lv
+    for name, names in (("kind", capi.EVENT_KINDS), ("direction", capi.EVENT_DIRECTIONS), ("start", capi.EVENT_STARTS)):
+        if not isinstance(kw[name], str) or kw[name] not in names:
+            raise ValueError(f"{what}: {name} must be one of {tuple(names)}; got {kw[name]!r}")
+    for name in ("t_min", "never"):
+        v = kw[name]
+        if v is None and name == "t_min":
+            continue
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise ValueError(f"{what}: {name} must be a number")
+        kw[name] = float(v)
+    if kw["t_min"] is not None and np.isnan(kw["t_min"]):
+        raise ValueError(f"{what}: t_min must be a number")
+    if kw["species"] is not None:
+        sp = np.asarray(kw["species"])
+        if sp.ndim != 1 or sp.dtype.kind not in "iu" or (sp < 0).any():
+            raise ValueError(f"{what}: species must be a list of non-negative integer ids")
+        kw["species"] = sp.astype(np.int64)
+    return kw
+
+
+def _of_arguments(what, of, events, choices):
+    """The (of, events) pair of ensemble_statistics / sobol_indices: `of` among `choices`; of="t_peak" | "t_cross" needs
+    events=dict(...) without species (and with a level for t_cross), the others take none. Returns the completed dict or None."""
+    if of not in choices:
+        raise ValueError(f"{what}: of must be one of {choices}; got {of!r}")
+    if of not in ("t_peak", "t_cross"):
+        if events is not None:
+            raise ValueError(f"{what}: events goes with of='t_peak' or of='t_cross', not of={of!r}")
+        return None
+    kw = _event_arguments({} if events is None else events, what=f"{what}: events")
+    if kw["species"] is not None:
+        raise ValueError(f"{what}: events takes no species here; the species are selected beside `of`")
+    if of == "t_cross" and kw["level"] is None:
+        raise ValueError(f"{what}: of='t_cross' needs events=dict(level=...)")
+    return kw
+
+
+def _event_row_begin(t, t_min):
+    """The first row of the increasing times t with t >= t_min (None: row 0)."""
+    return 0 if t_min is None else int(np.searchsorted(np.asarray(t, dtype=float), float(t_min), side="left"))
+
+
+def _event_block(h, t, of, events):
+    """The event time `of` of every member and species of the handle's stored ensemble as the [K][1][N] block the
+    kin_members_* entries take."""
+    return np.ascontiguousarray(getattr(event_times(h, t=t, **events), of)[:, None, :])
+
+
+def event_times(out_or_handle, level=None, kind="abs", direction="rise", start="begin", t_min=None, never=float("nan"), species=None,
+                t=None):
+    """When does every species peak, and when does it first cross a level - the induction time before a product reaches 10 % of
+    its final value (level=0.1, kind="of_peak"), the half-life of the feed (level=0.5, kind="of_start", direction="fall"), the
+    falling edge of a pulse at half of its maximum (level=0.5, kind="of_peak", direction="fall", start="peak"). One device pass
+    (kin_events_segmented / kin_ensemble_events), no sum in it: the result is exact whatever the launch looks like.
+
+    out_or_handle: an ODESolveOutput - its saved states are handed to a handle of out.rd as the other analysis passes hand them
+    over, result arrays [n_sel] - or a capi.HipNetwork after a solve_ensemble* call (trajectories downloaded or not) with t=
+    the save grid [n_rows] (or every member's own times [K][n_rows]): the stored ensemble is read where it lives, result arrays
+    [K][n_sel], a member's rows past its n_saved taking no part.
+    level: a number or one per species, None for the peaks alone (t_cross is None then); kind "abs" | "of_peak" | "of_start";
+    direction "rise" | "fall"; start "begin" | "peak". t_min: only the rows with t >= t_min take part (turned into the pass's
+    row_begin; with per-member times it is refused). never: what a time that does not exist is reported as - NaN, or e.g.
+    t[-1] to censor. species: the columns returned - names or 0-based ids for an ODESolveOutput, ids in the handle's index base
+    for a handle; None for all. Malformed arguments raise ValueError before anything touches the device."""
+    is_out = isinstance(out_or_handle, ODESolveOutput)
+    if is_out and species is not None:
+        try:
+            if any(isinstance(x, (bool, np.bool_)) or not isinstance(x, (str, int, np.integer)) for x in species):
+                raise TypeError
+            species = _species_ids(out_or_handle.sd, species)
+        except (KeyError, TypeError, ValueError):
+            raise ValueError("events: species must be names or 0-based ids of the solve's species") from None
+    kw = _event_arguments(dict(level=level, kind=kind, direction=direction, start=start, t_min=t_min, never=never, species=species))
+    opts = dict(level=kw["level"], kind=kw["kind"], direction=kw["direction"], start=kw["start"], never=kw["never"])
+    cols = kw["species"]
+    if is_out:
+        out = out_or_handle
+        if t is not None:
+            raise ValueError("events: t goes with a handle's stored ensemble; an ODESolveOutput carries its own saved times")
+        if out.sol.u is None:
+            raise ValueError("events: the solve output holds no saved states (it was solved with trajectories=False)")
+        n = out.sd.n
+        ts = np.asarray(out.sol.t, dtype=float)
+        u = np.ascontiguousarray(np.asarray(out.sol.u, dtype=float).reshape(1, len(ts), n))
+    else:
+        if t is None:
+            raise ValueError("events: a handle needs t, the save grid of its stored ensemble")
+        n = out_or_handle.n
+        ts = np.asarray(t, dtype=float)
+        if ts.ndim not in (1, 2):
+            raise ValueError(f"events: t must be the save grid [n_rows] or every member's times [K][n_rows]; got {ts.shape}")
+        if ts.ndim == 2 and kw["t_min"] is not None:
+            raise ValueError("events: t_min needs one save grid for all members")
+        cols = None if cols is None else cols - getattr(out_or_handle, "index_base", 0)
+    if np.ndim(kw["level"]) == 1 and len(kw["level"]) != n:
+        raise ValueError(f"events: level must be a number or one per species ({n}); got {len(kw['level'])}")
+    if cols is not None and len(cols) and (cols.min() < 0 or cols.max() >= n):
+        raise ValueError(f"events: species ids must be among the {n} species")
+    row_begin = _event_row_begin(ts, kw["t_min"])
+    if is_out:
+        h = capi.HipNetwork(*out.rd.flat(n), index_base=1)
+        try:
+            r = h.events_segmented(u, ts, row_begin=row_begin, **opts)
+        finally:
+            h.close()
+        r = {q: v[0] for q, v in r.items()}
+    else:
+        r = out_or_handle.ensemble_events(ts, row_begin=row_begin, **opts)
+    if cols is not None:
+        r = {q: np.ascontiguousarray(v[..., cols]) for q, v in r.items()}
+    lv = None if kw["level"] is None else np.broadcast_to(np.asarray(kw["level"], dtype=float), (n,)).copy()
+    return EventTimes(ts, r["u_peak"], r["t_peak"], r.get("t_cross"), level=lv, kind=kw["kind"], direction=kw["direction"],
+                      start=kw["start"], t_min=kw["t_min"], never=kw["never"], species=kw["species"])
 
 
 # ---- post-hoc reaction-flux analysis (EXTENSION, in the style of the reference's analysis/: works on an ODESolveOutput) ----

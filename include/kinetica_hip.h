@@ -1068,6 +1068,72 @@ int kin_ensemble_events(kin_network* h, const double* t, int t_per_member, const
 int kin_solution_events(kin_network* h, const double* level, int level_kind, int direction, int start, int64_t row_begin, double never,
                         double* u_peak, double* t_peak, double* t_cross /* [N] each */);
 
+/* ---- resampling: stored trajectories on a common axis --------------------------------------------------------------------- */
+/* Row j of every member of an ensemble is "the state at time t[j]". Members of a heating-rate or start-temperature sweep sit at
+ * different temperatures at one saved time, so a mean, an envelope or a Sobol index "at row j" compares different stages of the
+ * programme. This pass evaluates every segment's stored trajectory at query points of an axis of its own - its temperature, a
+ * normalised time, the save grid - where the states live; its result can take the place of the stored ensemble, so that every
+ * kin_ensemble_* pass runs on rows of equal temperature.
+ *
+ * SEGMENTS. As in kin_events_segmented: segment s has rows j = row_begin .. n_s - 1 of its block of L rows, states u[s][j][i].
+ * AXIS. x[L] shared by all segments, or x[S][L] with x_per_segment != 0: non-decreasing over the rows read (plateaus are allowed:
+ *   a ramp that reaches its end value and holds), no NaN. Rows at or past n_s are never read, neither states nor axis.
+ * QUERIES. xq[Q] shared, or xq[S][Q] with xq_per_segment != 0; any order, repeats allowed.
+ * BRACKET of (s, q). jc is the first row j in [row_begin, n_s) with x[j] >= xq. The query is INSIDE iff the segment is not empty,
+ *   xq is not NaN and x[row_begin] <= xq <= x[n_s - 1]. A query that is not inside has the code jc = -1 below the range, -2 above
+ *   it, -3 for a NaN query or an empty segment.
+ * VALUE of an inside query. x[jc] == xq: u[s][jc][i], copied bit for bit (resampling at a segment's own axis returns its own
+ *   rows, -0.0 included; on a plateau the first row that holds the value). Otherwise, with a = u[s][jc - 1][i], b = u[s][jc][i]:
+ *     w = (xq - x[jc - 1]) / (x[jc] - x[jc - 1]),      result = a + w * (b - a)
+ *   evaluated in exactly this order in IEEE double arithmetic, every operation rounded on its own: the kernel is compiled with
+ *   floating-point contraction off (#pragma clang fp contract(off) over resample_kernels.hip, as event_kernels.hip is), so no
+ *   multiplication fuses with an addition. x[jc - 1] < xq <= x[jc]: the denominator is never zero. w depends on (s, q) only.
+ * OUTSIDE queries. mode KIN_RESAMPLE_FILL: every species gets `fill`, the caller's value (NaN marks "no such state").
+ *   KIN_RESAMPLE_HOLD: a query below the range gets row row_begin, one above it row n_s - 1, bit for bit; a NaN query or an
+ *   empty segment still gets `fill`. Such a held query counts as COVERED; under KIN_RESAMPLE_FILL covered means inside.
+ * OUTPUTS. u_q[S][Q][N]; optionally jc[S][Q] (int32, the codes above whatever the mode) and w[S][Q] (0.0 where the value is a
+ *   copy or the query is outside).
+ *
+ * Every output is a function of its own (s, q, i) with one order of operations: the same bits from call to call, between the
+ * host and the device entry, and under any decomposition. How it is computed (resample_kernels.hip): one launch, no atomics; a
+ * workgroup owns (segment, a tile of queries, 1024 species); its threads search one query each by bisection and leave (jc, w)
+ * in LDS, after one barrier its wavefronts take the tile's queries in turn with the lanes along the species, reading at most
+ * two rows and writing one per query. KIN_RESAMPLE_TILE_QUERIES sets the tile (1 .. 256) and KIN_RESAMPLE_WAVES the wavefronts
+ * (1 .. 16) (read per call; test knobs: results do not depend on them).
+ *
+ * Statuses: KIN_ERR_INVALID_ARG for S, L, Q or row_begin < 0, a null u or x with S L > 0, a null xq with S Q > 0, a null output,
+ * an unknown mode, and from the host entries a seg_n outside [0, L] or an axis that decreases or holds a NaN over the rows read;
+ * KIN_ERR_UNSUPPORTED for S, L or Q >= 2^31, S ceil(Q / 4) >= 2^31 or N > 64 * 65535; KIN_ERR_STATE from kin_ensemble_resample /
+ * kin_solution_resample without a stored ensemble / solution. S Q = 0 or N = 0 writes nothing. A refused call leaves the handle
+ * as it was. The device entry only enqueues (d_seg_n: S int64 on the device, or NULL: L rows each); one stream per handle at a
+ * time. Added under KIN_ABI_VERSION 6: look the symbols up before calling them. */
+enum { KIN_RESAMPLE_FILL = 0, KIN_RESAMPLE_HOLD = 1 };
+/* The bracket alone, on host arrays: no handle, no device. The normative restatement of (jc, w) above; either output may be
+ * NULL, not both. */
+int kin_resample_bracket_host(int64_t S, int64_t L, const int64_t* seg_n, const double* x, int x_per_segment, int64_t Q, const double* xq,
+                              int xq_per_segment, int64_t row_begin, int32_t* jc /* [S][Q] */, double* w /* [S][Q] */);
+int kin_resample_segmented_dev(kin_network* h, int64_t S, int64_t L, const int64_t* d_seg_n, const double* d_u /* [S][L][N] */,
+                               const double* d_x /* [L] or [S][L] */, int x_per_segment, int64_t Q, const double* d_xq /* [Q] or [S][Q] */,
+                               int xq_per_segment, int mode, double fill, int64_t row_begin, double* d_out /* [S][Q][N] */,
+                               int32_t* d_jc, double* d_w /* [S][Q] each, or NULL */, void* stream);
+int kin_resample_segmented(kin_network* h, int64_t S, int64_t L, const int64_t* seg_n, const double* u, const double* x, int x_per_segment,
+                           int64_t Q, const double* xq, int xq_per_segment, int mode, double fill, int64_t row_begin, double* out,
+                           int32_t* jc, double* w);
+/* The same over the stored states of the last kin_solve (S = 1, L = n_saved); x NULL: its saved times. out[Q][N]. */
+int kin_solution_resample(kin_network* h, const double* x /* [n_saved] or NULL */, int64_t Q, const double* xq, int mode, double fill,
+                          int64_t row_begin, double* out);
+/* The same over the stored ensemble (S = K, L = n_rows, seg_n = n_saved), read where it lives; x[n_rows], or x[K][n_rows] with
+ * x_per_member != 0 (entries of rows j >= n_saved[m] are ignored). out[K][Q][N] may be NULL when store != 0.
+ * With store != 0 THE RESULT BECOMES THE STORED ENSEMBLE (Q >= 1, else KIN_ERR_INVALID_ARG): the block goes to a handle-owned
+ * buffer and the record is (K, n_rows = Q, n_saved'), n_saved'[m] the length of the leading run of covered queries of member m -
+ * its first uncovered query ends the run, and from that query on the member's rows in the stored block are zeros, the record's
+ * invariant, whatever `fill` is (`out` holds the pass's plain result). The per-member Ea / A of a kin_solve_ensemble_*_params
+ * record stay attached. Every kin_ensemble_* entry then reads this record unchanged: kin_ensemble_size reports Q rows, and the
+ * statistics passes take by default the members that cover the whole query axis. A resampled record may be resampled again
+ * (source and destination are two handle buffers used in turn); the next kin_solve_ensemble* call replaces the record as always. */
+int kin_ensemble_resample(kin_network* h, const double* x, int x_per_member, int64_t Q, const double* xq, int xq_per_member, int mode,
+                          double fill, int64_t row_begin, int store, double* out);
+
 /* ---- device / build information ------------------------------------------------------- */
 int kin_device_count(int* n);
 /* Selects the device for handles created afterwards by this thread; a handle remembers the device it was created on
@@ -1087,7 +1153,8 @@ const char* kin_version(void);
  * kin_ensemble_reaction_importance, and the cross-member statistics: kin_members_*, kin_ensemble_moments / _quantiles /
  * _correlate, and the Sobol indices: kin_members_sobol, kin_members_sobol_dev, kin_ensemble_sobol, and the
  * per-member Arrhenius parameters: kin_solve_ensemble_continuous_params, kin_solve_ensemble_discrete_params, and the event
- * times: kin_events_segmented, kin_events_segmented_dev, kin_ensemble_events, kin_solution_events). */
+ * times: kin_events_segmented, kin_events_segmented_dev, kin_ensemble_events, kin_solution_events, and the resampling:
+ * kin_resample_bracket_host, kin_resample_segmented, kin_resample_segmented_dev, kin_solution_resample, kin_ensemble_resample). */
 #define KIN_ABI_VERSION 6
 int kin_abi_version(void);
 int64_t kin_struct_size(int which); /* 0: sizeof(kin_params), 1: sizeof(kin_stats), else -1 */

@@ -46,6 +46,7 @@ SYMBOLS = [
     "kin_members_correlate", "kin_members_correlate_dev", "kin_ensemble_moments", "kin_ensemble_quantiles", "kin_ensemble_correlate",
     "kin_members_sobol", "kin_members_sobol_dev", "kin_ensemble_sobol",
     "kin_events_segmented", "kin_events_segmented_dev", "kin_ensemble_events", "kin_solution_events",
+    "kin_resample_bracket_host", "kin_resample_segmented", "kin_resample_segmented_dev", "kin_solution_resample", "kin_ensemble_resample",
     "kin_flux_plan_host", "kin_network_compute_units",
     "kin_sweep_plan", "kin_sweep_plan_host", "kin_tiled_sweep_plan", "kin_tiled_sweep_plan_host",
 ]
@@ -58,6 +59,9 @@ EVENT_KINDS = dict(abs=0, of_peak=1, of_start=2)
 EVENT_DIRECTIONS = dict(rise=1, fall=-1)
 EVENT_STARTS = dict(begin=0, peak=1)
 EVENT_OUTPUTS = ("u_peak", "t_peak", "t_cross")
+# the resampling pass (include/kinetica_hip.h: KIN_RESAMPLE_*) and the jc codes of a query that is not inside
+RESAMPLE_MODES = dict(fill=0, hold=1)
+RESAMPLE_BELOW, RESAMPLE_ABOVE, RESAMPLE_NONE = -1, -2, -3
 
 
 # kin_step_probe (include/kinetica_hip.h): rows of the state block, fields of the flattened control block, argument slots
@@ -107,6 +111,7 @@ _SOLVED = [P64, POINTER(c_int32), POINTER(KinStats)]      # n_saved, retcode, st
 _MEMBERS = [P64, PD, PD, P64, POINTER(c_int32), POINTER(KinStats)]      # n_rows, out_t, out_u, n_saved, retcodes, stats of an ensemble
 _KSRC = [PD, c_int64, P64, PD]      # the rate constants of a pass on host arrays: k, n_k_rows, k_row, T
 _EVENT = [c_int, c_int, c_int, c_int64, c_double]      # what an event-time pass looks for: level_kind, direction, start, row_begin, never
+_RESAMPLE = [c_int, c_double, c_int64]      # what a resampling pass does besides its axes: mode, fill, row_begin
 ARGTYPES = {
     "kin_struct_size": [c_int], "kin_last_error": [PV],
     "kin_network_create": _NET + [POINTER(PV)], "kin_network_destroy": [PV], "kin_network_sizes": [PV, P64, P64],
@@ -198,6 +203,12 @@ ARGTYPES = {
     "kin_events_segmented": [PV, c_int64, c_int64, P64, PD, PD, c_int, PD] + _EVENT + [PD, PD, PD],
     "kin_events_segmented_dev": [PV, c_int64, c_int64, PV, PV, PV, c_int, PV] + _EVENT + [PV] * 4,
     "kin_ensemble_events": [PV, PD, c_int, PD] + _EVENT + [PD, PD, PD], "kin_solution_events": [PV, PD] + _EVENT + [PD, PD, PD],
+    # resampling
+    "kin_resample_bracket_host": [c_int64, c_int64, P64, PD, c_int, c_int64, PD, c_int, c_int64, P32, PD],
+    "kin_resample_segmented": [PV, c_int64, c_int64, P64, PD, PD, c_int, c_int64, PD, c_int] + _RESAMPLE + [PD, P32, PD],
+    "kin_resample_segmented_dev": [PV, c_int64, c_int64, PV, PV, PV, c_int, c_int64, PV, c_int] + _RESAMPLE + [PV] * 4,
+    "kin_solution_resample": [PV, PD, c_int64, PD] + _RESAMPLE + [PD],
+    "kin_ensemble_resample": [PV, PD, c_int, c_int64, PD, c_int] + _RESAMPLE + [c_int, PD],
 }
 
 _lib = None
@@ -289,6 +300,56 @@ def _use32(use, K):
     if len(use) != K:
         raise ValueError(f"use must have one entry per member ({K}); got {len(use)}")
     return use
+
+
+def _axis(a, S, L, what):
+    """(a as float64, the per-segment flag) of an axis or a set of queries: a[L] shared by the S segments, or a[S][L]."""
+    a = np.ascontiguousarray(_f64(a))
+    if a.shape == (L,):
+        return a, 0
+    if a.shape == (S, L):
+        return a, 1
+    raise ValueError(f"{what} must be [{L}] (shared) or [{S}][{L}] (one per segment); got {a.shape}")
+
+
+def _queries(xq, S):
+    """(xq as float64, Q, the per-segment flag): queries xq[Q] shared by the S segments, or xq[S][Q]."""
+    xq = np.ascontiguousarray(_f64(xq))
+    if xq.ndim == 1:
+        return xq, len(xq), 0
+    if xq.ndim == 2 and xq.shape[0] == S:
+        return xq, xq.shape[1], 1
+    raise ValueError(f"xq must be [Q] (shared) or [{S}][Q] (one set per segment); got {xq.shape}")
+
+
+def _seg_n(seg_n, S):
+    if seg_n is None:
+        return None
+    seg_n = np.ascontiguousarray(seg_n, dtype=np.int64).ravel()
+    if len(seg_n) != S:
+        raise ValueError(f"seg_n must have one entry per segment ({S}); got {len(seg_n)}")
+    return seg_n
+
+
+def resample_brackets(x, xq, seg_n=None, row_begin=0):
+    """kin_resample_bracket_host (no handle, no device): the brackets of the resampling pass. x[L] or x[S][L] the axis (S = 1
+    for x[L] unless seg_n or a two-dimensional xq says otherwise), xq[Q] or xq[S][Q] the queries, seg_n[S] the rows a segment
+    really has (None: L each). Returns (jc[S][Q] int32, w[S][Q]): jc the first row from row_begin on with x[j] >= xq, or
+    RESAMPLE_BELOW / _ABOVE / _NONE for a query below the segment's range, above it, or NaN / of an empty segment; w the
+    chord's weight (xq - x[jc-1]) / (x[jc] - x[jc-1]), 0.0 where x[jc] == xq or the query is not inside."""
+    x = np.ascontiguousarray(_f64(x))
+    q = np.ascontiguousarray(_f64(xq))
+    if x.ndim not in (1, 2):
+        raise ValueError(f"x must be [L] or [S][L]; got {x.shape}")
+    S = x.shape[0] if x.ndim == 2 else (q.shape[0] if q.ndim == 2 else (1 if seg_n is None else len(np.ravel(seg_n))))
+    x, x_per = _axis(x, S, x.shape[-1], "x")
+    q, Q, q_per = _queries(q, S)
+    seg_n = _seg_n(seg_n, S)
+    jc, w = np.zeros((S, Q), np.int32), np.zeros((S, Q))
+    st = lib().kin_resample_bracket_host(S, x.shape[-1], _p64(seg_n), _pd(x), x_per, Q, _pd(q), q_per, int(row_begin), _p32(jc), _pd(w))
+    if st != KIN_OK:
+        raise KineticaHipError(st, "kin_resample_bracket_host: invalid argument (sizes, seg_n, or an axis that decreases or holds a NaN)")
+    return jc, w
 
 
 def members_inputs(X, use=None, rank=True):
@@ -1250,6 +1311,69 @@ class HipNetwork:
         dict of [N] arrays."""
         level, codes, want = self._event_opts(level, kind, direction, start, row_begin, never, want)
         return self._events("kin_solution_events", (self.n,), (), level, codes, want)
+
+    # --- resampling: stored trajectories on a common axis ------------------------------------------------------
+    @staticmethod
+    def _resample_opts(mode, fill, row_begin):
+        """The C arguments mode, fill, row_begin; the mode by name (ValueError for an unknown one) or as the library's integer."""
+        if isinstance(mode, str):
+            if mode not in RESAMPLE_MODES:
+                raise ValueError(f"mode must be one of {tuple(RESAMPLE_MODES)}; got {mode!r}")
+            mode = RESAMPLE_MODES[mode]
+        return int(mode), float(fill), int(row_begin)
+
+    def resample_segmented(self, u, x, xq, seg_n=None, mode="fill", fill=float("nan"), row_begin=0, want_brackets=False):
+        """kin_resample_segmented on host arrays: u[S][L][N] (S segments of up to L rows, seg_n[S] of them real; None: L each)
+        evaluated at the queries xq[Q] or xq[S][Q] of the axis x[L] or x[S][L] (non-decreasing over the rows read). Returns
+        u_q[S][Q][N]: a row copied bit for bit where the axis holds the query, else the chord between the two rows around it;
+        a query outside the segment's range gets `fill` (mode "fill") or the segment's first / last row (mode "hold").
+        want_brackets: (u_q, jc[S][Q], w[S][Q]) - resample_brackets' pair as the device formed it."""
+        u, S, L = self._ms_block(u, self.n)
+        seg_n = _seg_n(seg_n, S)
+        x, x_per = _axis(x, S, L, "x")
+        xq, Q, q_per = _queries(xq, S)
+        out = np.empty((S, Q, self.n))
+        jc, w = (np.zeros((S, Q), np.int32), np.zeros((S, Q))) if want_brackets else (None, None)
+        self._chk(lib().kin_resample_segmented(self._h, S, L, _p64(seg_n), _pd(u), _pd(x), x_per, Q, _pd(xq), q_per,
+                                               *self._resample_opts(mode, fill, row_begin), _pd(out), _p32(jc), _pd(w)))
+        return (out, jc, w) if want_brackets else out
+
+    def resample_segmented_dev(self, S, L, d_u, d_x, Q, d_xq, d_out, mode="fill", fill=float("nan"), row_begin=0, d_seg_n=0,
+                               x_per_segment=False, xq_per_segment=False, d_jc=0, d_w=0, stream=0):
+        """kin_resample_segmented_dev: device pointers (ints; 0 = not given / not wanted) u[S][L][N], x[L] (x[S][L] with
+        x_per_segment), xq[Q] (xq[S][Q] with xq_per_segment), seg_n[S] (int64), out[S][Q][N], jc[S][Q] (int32), w[S][Q]. Only
+        enqueues; one stream per handle at a time."""
+        self._chk(lib().kin_resample_segmented_dev(self._h, int(S), int(L), _dp(d_seg_n), _dp(d_u), _dp(d_x), int(bool(x_per_segment)),
+                                                   int(Q), _dp(d_xq), int(bool(xq_per_segment)), *self._resample_opts(mode, fill, row_begin),
+                                                   _dp(d_out), _dp(d_jc), _dp(d_w), _dp(stream)))
+
+    def solution_resample(self, xq, x=None, mode="fill", fill=float("nan"), row_begin=0):
+        """kin_solution_resample: the saved states of the last solve, read where they live, at the queries xq[Q] of the axis
+        x[n_saved] (None: the saved times). Returns u_q[Q][N]."""
+        xq = np.ascontiguousarray(_f64(xq)).ravel()
+        if x is not None:
+            x = np.ascontiguousarray(_f64(x)).ravel()
+            n = self._solution()[0]
+            if len(x) != n:
+                raise ValueError(f"x must have one entry per saved row ({n}); got {len(x)}")
+        out = np.empty((len(xq), self.n))
+        self._chk(lib().kin_solution_resample(self._h, _pd(x), len(xq), _pd(xq), *self._resample_opts(mode, fill, row_begin), _pd(out)))
+        return out
+
+    def ensemble_resample(self, x, xq, mode="fill", fill=float("nan"), row_begin=0, store=False, download=True):
+        """kin_ensemble_resample: the stored ensemble, every member's own saved rows read where they live, at the queries xq[Q]
+        or xq[K][Q] of the axis x[n_rows] or x[K][n_rows]. Returns u_q[K][Q][N], or None with download=False (which needs
+        store). store: the result becomes the stored ensemble - Q rows, a member's n_saved the length of its leading run of
+        covered queries, zeros from its first uncovered query on - and every ensemble_* method reads it from then on."""
+        if not download and not store:
+            raise ValueError("download=False needs store=True: the result would go nowhere")
+        K, L = self.ensemble_size()[:2]
+        x, x_per = _axis(x, K, L, "x")
+        xq, Q, q_per = _queries(xq, K)
+        out = np.empty((K, Q, self.n)) if download else None
+        self._chk(lib().kin_ensemble_resample(self._h, _pd(x), x_per, Q, _pd(xq), q_per, *self._resample_opts(mode, fill, row_begin),
+                                              int(bool(store)), _pd(out)))
+        return out
 
     # --- library order (tiled sweep) --------------------------------------------------------
     def lib_layout(self):

@@ -173,6 +173,10 @@ struct kin_network {
   kin::DevBuf<double> ens_sol, ens_w, ens_out;   // handle-owned copy of the saved states; workspaces of kin_ensemble_max / _dot
   kin::DevBuf<double> ens_Ea, ens_A;             // the per-member parameter blocks of a kin_solve_ensemble_*_params call, reused across calls
   kin::DevBuf<int64_t> ens_segn;                 // n_saved[K] on the device
+  // resampling (resample_api.cpp): the two buffers a resampled record lives in by turns (kin_ensemble_resample with store: the
+  // result goes to the one the record is not in), and the host entries' staging of jc[S][Q] and w[S][Q]
+  kin::DevBuf<double> ens_rs[2], rs_w;
+  kin::DevBuf<int32_t> rs_jc;
   void set_ensemble_record(const double* sol, int64_t K, int64_t cap, std::vector<int64_t> n_saved) {
     ens.sol = sol; ens.K = K; ens.cap = cap; ens.n_saved = std::move(n_saved);
   }

@@ -467,6 +467,7 @@ class ODESolution:
     fluxes: Optional[object] = None      # ReactionFluxes of the solve (solve_network_ensemble(fluxes=True)), else None
     ensemble_stats: Optional[object] = None   # the ensemble's one EnsembleStatistics (solve_network_ensemble(statistics=...)), else None
     events: Optional[object] = None      # the ensemble's one EventTimes (solve_network_ensemble(events=...)), else None
+    resampled: Optional[object] = None   # the ensemble's one ResampledEnsemble (solve_network_ensemble(resample=...)), else None
 
     def __call__(self, tq):
         """Linear interpolation res.sol(t) (docs/src/getting-started.md:232-236)."""
@@ -741,7 +742,7 @@ def apply_ensemble_low_k_cutoff(rd, calc, pars, condition_sets, calculators=None
 
 
 def solve_network_ensemble(methods, sd, rd, copy_network=True, fluxes=False, trajectories=True, statistics=None,
-                           member_calculators=False, events=None):
+                           member_calculators=False, events=None, resample=None):
     """EXTENSION (the reference has no ensemble call: it solves member after member through solve_network): K
     `VariableODESolve`s with Arrhenius condition sets - one temperature profile each, e.g. a set of heating rates or start
     temperatures - on one network in ONE ensemble call: kin_solve_ensemble_continuous when every set is continuous,
@@ -788,12 +789,29 @@ def solve_network_ensemble(methods, sd, rd, copy_network=True, fluxes=False, tra
     events=dict of event_times' keyword arguments (level, kind, direction, start, t_min, never, species; species 0-based ids
     of the network as it is solved): every member's sol.events refers to ONE shared EventTimes - per member and species the
     peak, its time and the time a level is first crossed - computed from the states where they live on the device before the
-    handle closes; it works with trajectories=False. A malformed dict raises ValueError before anything touches the GPU."""
+    handle closes; it works with trajectories=False. A malformed dict raises ValueError before anything touches the GPU.
+
+    resample=dict(axis="T" | "t" | "t_rel" | array, at=[...], mode=, fill=, t_min=) puts the members on a common axis before the
+    statistics and the event times look at them: members of a heating-rate or start-temperature sweep sit at different
+    temperatures at one saved time, and a mean "at row j" compares different stages of the programme. The order inside the call:
+    the solve; whatever refers to the solve's own rows, as always (the trajectory download, sol.umax, fluxes=True); then
+    resample_ensemble(store=True) - the stored ensemble becomes the states at the queries `at` of every member's axis; then
+    statistics= and events= over that record with t = at: EnsembleStatistics.t and EventTimes.t are the query axis, and t_peak
+    under axis="T" is the peak temperature. axis="T" is the member's own temperature programme at its saved times (the values
+    sol_vcs["T"] holds; for discrete-update sets the set's profile interpolated the same way), "t" the save grid, "t_rel" the
+    time over the member's last saved time, an array [n_rows] or [K][n_rows] anything else. The axis must not decrease: a
+    cooling programme is a ValueError - negate the axis and the queries. Every member's sol.resampled refers to ONE shared
+    ResampledEnsemble (its u the resampled block when trajectories=True, else None). A malformed dict raises ValueError
+    before anything touches the GPU (an axis array's row count is compared with the save grid once that is known). None (the
+    default): the function as it was."""
     methods = list(methods)
     if not methods:
         raise ValueError("solve_network_ensemble needs at least one method")
     stat_kw = _statistics_arguments(statistics, len(methods))
     ev_kw = None if events is None else _event_arguments(events)
+    rs_kw = None if resample is None else _resample_arguments(resample, len(methods))
+    if rs_kw is not None and ev_kw is not None and not np.all(np.diff(rs_kw["at"], axis=-1) > 0):
+        raise ValueError("resample: events over the resampled record need queries `at` that increase strictly")
     m0 = methods[0]
     for m in methods:
         if not isinstance(m, VariableODESolve) or not isinstance(m.calculator, PrecalculatedArrheniusCalculator):
@@ -859,6 +877,12 @@ def solve_network_ensemble(methods, sd, rd, copy_network=True, fluxes=False, tra
                 nodes.append((np.array([pars.tspan[0], pars.tspan[1]]), np.array([prof.value, prof.value], dtype=float)))
             else:
                 nodes.append((np.asarray(prof.sol.t, dtype=float), np.asarray(prof.sol.u, dtype=float)))
+    if rs_kw is not None and isinstance(rs_kw["axis"], str) and rs_kw["axis"] == "T":
+        for m in methods:
+            prof = m.conditions.profiles[m.conditions.symbols.index("T")]
+            if not isstatic(prof) and np.any(np.diff(np.asarray(prof.sol.u, dtype=float)) < 0):
+                raise ValueError("resample: axis='T' needs temperature programmes that do not decrease; for a cooling programme "
+                                 "negate the axis and the queries (axis=-T as an array, at=-at)")
     h = capi.HipNetwork(*rd_a.flat(sd_a.n), index_base=1)
     try:
         h.set_arrhenius(calc.Ea, calc.A, calc.k_max, calc.t_mult)
@@ -875,20 +899,29 @@ def solve_network_ensemble(methods, sd, rd, copy_network=True, fluxes=False, tra
             src = ensemble_flux_sources("discrete_members", t, ns, stops=stops) if discrete else \
                 ensemble_flux_sources("continuous", t, ns, nodes=nodes)
             F = h.ensemble_flux(w=src["w"], T_rows=src["T_rows"])
+        rs, t_stat = None, t
+        if rs_kw is not None:      # from here on the stored ensemble is the resampled one and its rows are the queries
+            axis = rs_kw["axis"]
+            if isinstance(axis, str) and axis == "T":
+                axis = np.array([_member_temperatures(m.conditions, t) for m in methods])
+            rs = resample_ensemble(h, t, rs_kw["at"], axis=axis, mode=rs_kw["mode"], fill=rs_kw["fill"], t_min=rs_kw["t_min"],
+                                   store=True, download=trajectories)
+            rs.axis = rs_kw["axis"]
+            t_stat = rs_kw["at"]
         stats = None
         if stat_kw is not None:
             sp0 = stat_kw["species"]
             if sob_kw is not None:
                 sb0 = sob_kw["species"]
                 sob_kw = dict(sob_kw, species=None if sb0 is None else sb0 + 1)
-            stats = ensemble_statistics(h, t, **dict(stat_kw, species=None if sp0 is None else sp0 + 1, sobol=sob_kw))   # (the handle's base is 1)
+            stats = ensemble_statistics(h, t_stat, **dict(stat_kw, species=None if sp0 is None else sp0 + 1, sobol=sob_kw))   # (the handle's base is 1)
             stats.species = sp0
             if sob_kw is not None:
                 stats.sobol.species = sb0
         ev = None
         if ev_kw is not None:
             ev0 = ev_kw["species"]
-            ev = event_times(h, t=t, **dict(ev_kw, species=None if ev0 is None else ev0 + 1))
+            ev = event_times(h, t=t_stat, **dict(ev_kw, species=None if ev0 is None else ev0 + 1))
             ev.species = ev0
     finally:
         h.close()
@@ -915,6 +948,7 @@ def solve_network_ensemble(methods, sd, rd, copy_network=True, fluxes=False, tra
         if stat_kw is not None:
             sol.ensemble_stats = stats
         sol.events = ev
+        sol.resampled = rs
         out.append(ODESolveOutput(sd_a, rd_a, sol, sol_k, sol_vcs, m.pars, m.conditions))
     return out
 
@@ -1397,6 +1431,192 @@ def event_times(out_or_handle, level=None, kind="abs", direction="rise", start="
     lv = None if kw["level"] is None else np.broadcast_to(np.asarray(kw["level"], dtype=float), (n,)).copy()
     return EventTimes(ts, r["u_peak"], r["t_peak"], r.get("t_cross"), level=lv, kind=kw["kind"], direction=kw["direction"],
                       start=kw["start"], t_min=kw["t_min"], never=kw["never"], species=kw["species"])
+
+
+# ---- resampling: stored trajectories on a common axis (EXTENSION) -----------------------------------------------------------
+@dataclass
+class ResampledEnsemble:
+    """Result of resample_ensemble / resample_solution: the stored trajectories at the queries `at` of the axis `axis`.
+    axis: what the caller named ("t", "t_rel", "T") or gave; x: the axis as the pass read it, [n_rows] or [K][n_rows]; at: the
+    queries [Q] or [K][Q]; u: the states at them [K][Q][N] ([Q][N] for one solve), None when not downloaded; jc[K][Q]: the row
+    that closes the bracket of a query inside a member's range, -1 below it, -2 above it, -3 for a NaN query or a member
+    without rows; covered[K][Q]: the query has a state (inside, or held under mode="hold"); n_covered[K]: the length of the
+    leading run of covered queries - a member's n_saved in a stored resampled record (include/kinetica_hip.h has the
+    definitions)."""
+    axis: object
+    at: np.ndarray
+    u: Optional[np.ndarray]
+    jc: np.ndarray
+    covered: np.ndarray
+    n_covered: np.ndarray
+    x: Optional[np.ndarray] = None
+    mode: str = "fill"
+    fill: float = float("nan")
+    t_min: Optional[float] = None
+
+
+_RESAMPLE_KEYS = ("axis", "at", "mode", "fill", "t_min")
+_RESAMPLE_AXES = ("T", "t", "t_rel")
+
+
+def _resample_arguments(resample, K, what="resample", axes=_RESAMPLE_AXES):
+    """A dict of resample_ensemble's keyword arguments, completed with the defaults; ValueError for anything malformed - nothing
+    here touches the device. at comes back a float array [Q] or [K][Q], axis a name or a float array of 1 or 2 dimensions."""
+    if not isinstance(resample, dict):
+        raise ValueError(f"{what} must be a dict with the keys {_RESAMPLE_KEYS}")
+    bad = [k for k in resample if k not in _RESAMPLE_KEYS]
+    if bad:
+        raise ValueError(f"{what}: unknown keys {bad}; choose among {_RESAMPLE_KEYS}")
+    if "at" not in resample:
+        raise ValueError(f"{what}: at, the queries, is missing")
+    kw = dict(axis="t", mode="fill", fill=float("nan"), t_min=None)
+    kw.update(resample)
+
+    def numbers(v, name):
+        try:
+            a = np.asarray(v)
+            if a.dtype.kind not in "iuf":
+                raise TypeError
+            if a.ndim == 0:      # (ascontiguousarray would make a number an array of one)
+                raise TypeError
+            return np.ascontiguousarray(a, dtype=float)
+        except (TypeError, ValueError):
+            raise ValueError(f"{what}: {name} must be an array of numbers") from None
+
+    at = numbers(kw["at"], "at")
+    if not (at.ndim == 1 or (at.ndim == 2 and at.shape[0] == K)):
+        raise ValueError(f"{what}: at must be the queries [Q] or one set per member [{K}][Q]; got {at.shape}")
+    kw["at"] = at
+    if isinstance(kw["axis"], str):
+        if kw["axis"] not in axes:
+            raise ValueError(f"{what}: axis must be one of {axes} or an array; got {kw['axis']!r}")
+    else:
+        ax = numbers(kw["axis"], "axis")
+        if not (ax.ndim == 1 or (ax.ndim == 2 and ax.shape[0] == K)):
+            raise ValueError(f"{what}: an axis array must be [n_rows] or [{K}][n_rows]; got {ax.shape}")
+        kw["axis"] = ax
+    if not isinstance(kw["mode"], str) or kw["mode"] not in capi.RESAMPLE_MODES:
+        raise ValueError(f"{what}: mode must be one of {tuple(capi.RESAMPLE_MODES)}; got {kw['mode']!r}")
+    for name in ("fill", "t_min"):
+        v = kw[name]
+        if v is None and name == "t_min":
+            continue
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise ValueError(f"{what}: {name} must be a number")
+        kw[name] = float(v)
+    if kw["t_min"] is not None and np.isnan(kw["t_min"]):
+        raise ValueError(f"{what}: t_min must be a number")
+    return kw
+
+
+def _member_temperatures(conditions, t):
+    """A member's temperature programme at the save grid t: what sol_vcs["T"] holds at the member's saved times."""
+    prof = conditions.profiles[conditions.symbols.index("T")]
+    if isstatic(prof):
+        return np.full(len(t), float(prof.value))
+    return np.interp(t, prof.sol.t, prof.sol.u)
+
+
+def _resample_axis(axis, t, K, n_saved, what="resample"):
+    """The axis array [n_rows] or [K][n_rows] of a named or given axis over the save grid t; ValueError for a wrong shape or an
+    axis that decreases over a member's saved rows."""
+    L = len(t)
+    if isinstance(axis, str):
+        if axis == "t":
+            x = np.asarray(t, dtype=float)
+        elif axis == "t_rel":
+            last = np.asarray(t, dtype=float)[np.maximum(np.asarray(n_saved) - 1, 0)]
+            x = np.asarray(t, dtype=float)[None, :] / np.where(np.asarray(n_saved) > 0, last, 1.0)[:, None]
+        else:
+            raise ValueError(f"{what}: axis must be 't', 't_rel' or an array here; got {axis!r}")
+    else:
+        x = np.ascontiguousarray(axis, dtype=float)
+    if x.shape not in ((L,), (K, L)):
+        raise ValueError(f"{what}: the axis must be [{L}] or [{K}][{L}] (the save grid's rows); got {x.shape}")
+    for m in range(K):
+        rows = (x[m] if x.ndim == 2 else x)[:int(n_saved[m])]
+        if np.any(np.diff(rows) < 0):
+            raise ValueError(f"{what}: the axis decreases over member {m}'s saved rows; for a cooling programme negate the axis "
+                             "and the queries")
+    return np.ascontiguousarray(x)
+
+
+def _covered(jc, mode):
+    covered = (jc >= 0) | ((jc != capi.RESAMPLE_NONE) if mode == "hold" else False)
+    n_cov = np.array([len(c) if c.all() else int(np.argmin(c)) for c in covered.reshape(-1, covered.shape[-1])], dtype=np.int64)
+    return covered, n_cov
+
+
+def resample_ensemble(h, t, at, axis="t", mode="fill", fill=float("nan"), t_min=None, store=True, download=False):
+    """The ensemble stored in the handle `h` (a capi.HipNetwork after a solve_ensemble* call with the save grid `t`, trajectories
+    downloaded or not) at the queries `at` ([Q], or [K][Q] one set per member) of a per-member axis, computed where the states
+    live (kin_ensemble_resample): a saved row copied bit for bit where the axis holds the query, else the chord between the two
+    rows around it. axis: "t" the save grid, "t_rel" t / t[n_saved[m] - 1], or an array [n_rows] / [K][n_rows] (e.g. every
+    member's temperature at the saved times) that does not decrease over a member's saved rows. mode "fill": a query outside a
+    member's range gets `fill`; "hold": the member's first / last row. t_min: only the rows with t >= t_min take part.
+    store=True: the result becomes the stored ensemble - Q rows, a member's n_saved its n_covered - so that every ensemble_*
+    method, ensemble_statistics, sobol_indices and event_times (with t=at) run on it. download: fill `.u`. Returns a
+    ResampledEnsemble; its jc / covered / n_covered come from kin_resample_bracket_host."""
+    K, L, _, n_saved = h.ensemble_size()
+    kw = _resample_arguments(dict(at=at, axis=axis, mode=mode, fill=fill, t_min=t_min), K)
+    t = np.asarray(t, dtype=float)
+    if t.shape != (L,):
+        raise ValueError(f"resample: t must be the save grid of the stored ensemble ({L} rows); got {t.shape}")
+    x = _resample_axis(kw["axis"], t, K, n_saved)
+    rb = _event_row_begin(t, kw["t_min"])
+    jc, _ = capi.resample_brackets(x if x.ndim == 2 else np.broadcast_to(x, (K, L)), kw["at"], seg_n=n_saved, row_begin=rb)
+    u = h.ensemble_resample(x, kw["at"], mode=kw["mode"], fill=kw["fill"], row_begin=rb, store=store, download=download or not store)
+    covered, n_cov = _covered(jc, kw["mode"])
+    return ResampledEnsemble(axis, kw["at"], u if download or not store else None, jc, covered, n_cov, x=x, mode=kw["mode"],
+                             fill=kw["fill"], t_min=kw["t_min"])
+
+
+def resample_solution(out_or_handle, at, axis=None, mode="fill", fill=float("nan"), t_min=None):
+    """resample_ensemble for one solve: an ODESolveOutput - its saved states are handed to a handle of out.rd as the other
+    analysis passes hand them over; axis None or "t" its saved times, "T" its sol_vcs["T"], or an array [n_saved] - or a
+    capi.HipNetwork after a solve (kin_solution_resample, the states read where they live) with axis the array [n_saved] of its
+    saved rows: the saved times, or anything else. Returns a ResampledEnsemble with u[Q][N], jc[Q], covered[Q] and n_covered a
+    number."""
+    is_out = isinstance(out_or_handle, ODESolveOutput)
+    kw = _resample_arguments(dict(at=at, axis="t" if axis is None else axis, mode=mode, fill=fill, t_min=t_min), 1,
+                             axes=("t", "T") if is_out else ("t",))
+    if kw["at"].ndim != 1:
+        raise ValueError("resample: one solve takes one set of queries [Q]")
+    if is_out:
+        out = out_or_handle
+        if out.sol.u is None:
+            raise ValueError("resample: the solve output holds no saved states (it was solved with trajectories=False)")
+        ts = np.asarray(out.sol.t, dtype=float)
+        x = kw["axis"]
+        if isinstance(x, str) and x == "T":
+            if not out.sol_vcs or "T" not in out.sol_vcs:
+                raise ValueError("resample: axis='T' needs a solve with a temperature profile (sol_vcs['T'])")
+            x = np.asarray(out.sol_vcs["T"], dtype=float)
+        x = _resample_axis(x, ts, 1, [len(ts)])
+        if x.ndim == 2:
+            x = x[0]
+        rb = _event_row_begin(ts, kw["t_min"])
+        n = out.sd.n
+        h = capi.HipNetwork(*out.rd.flat(n), index_base=1)
+        try:
+            u = h.resample_segmented(np.asarray(out.sol.u, dtype=float).reshape(1, len(ts), n), x, kw["at"], mode=kw["mode"],
+                                     fill=kw["fill"], row_begin=rb)[0]
+        finally:
+            h.close()
+    else:
+        h = out_or_handle
+        x = None if isinstance(kw["axis"], str) else np.ascontiguousarray(kw["axis"], dtype=float)
+        if t_min is not None:
+            raise ValueError("resample: t_min goes with an ODESolveOutput (a handle's saved times are not known here)")
+        if x is None:
+            raise ValueError("resample: a handle needs the axis array of its saved rows (its saved times, or anything else)")
+        if x.ndim != 1 or np.any(np.diff(x) < 0):
+            raise ValueError("resample: the axis must be [n_saved] and must not decrease; for a cooling programme negate the axis and the queries")
+        rb = 0
+        u = h.solution_resample(kw["at"], x=x, mode=kw["mode"], fill=kw["fill"])
+    jc, _ = capi.resample_brackets(x, kw["at"], row_begin=rb)
+    covered, n_cov = _covered(jc[0], kw["mode"])
+    return ResampledEnsemble(axis, kw["at"], u, jc[0], covered, int(n_cov[0]), x=x, mode=kw["mode"], fill=kw["fill"], t_min=kw["t_min"])
 
 
 # ---- post-hoc reaction-flux analysis (EXTENSION, in the style of the reference's analysis/: works on an ODESolveOutput) ----

@@ -1034,7 +1034,8 @@ int kin_ensemble_sobol(kin_network* h, int64_t M, int64_t P, const int32_t* w, c
  *                  An empty segment gives `never`.
  * `never` is the caller's: NaN marks "no such time"; the last saved time censors instead.
  * A NaN among the rows that take part: u_peak follows fmax (a NaN row is passed over unless every row is NaN); nothing else
- * is specified for that species.
+ * is specified for that species. Zeros of both signs among the rows that hold the peak: the device's fmax orders them, u_peak
+ * is +0.0 if any such row holds +0.0 (whatever the decomposition) and t_peak the time of the first row that holds a zero.
  *
  * Every output is an extremum or a first index, never a sum: the result is exactly defined whatever the decomposition, and is
  * the same bits from call to call, between the host and the device entry, and whatever else the call holds. How it is

@@ -58,8 +58,47 @@ def lib():
         L.ens_host_finish.restype = c_int64
         L.ens_host_finish.argtypes = [c_int64, c_int64, P64, P32, P64, PD, PD, P64, P32, POINTER(capi.KinStats), P64]
         L.ens_host_runner.argtypes = [c_int64, c_int64, P32, P64, ctypes.c_char_p, c_int64]
+        # the launch plans of the event-time and resampling passes and the stored record as it lies (tests/native/pass_plan_host.cpp)
+        L.plan_host_constants.restype = None
+        L.plan_host_constants.argtypes = [P32]
+        for f in (L.plan_host_event, L.plan_host_resample):
+            f.restype = None
+            f.argtypes = [c_int64, c_int64, c_int64, c_int, P32]
+        L.plan_host_record_download.argtypes = [c_void_p, PD, c_int64]
         _lib = L
     return _lib
+
+
+def _plan(entry, a, b, c, n_cu):
+    out = np.zeros(2, np.int32)
+    getattr(lib(), entry)(int(a), int(b), int(c), int(n_cu), out.ctypes.data_as(POINTER(c_int32)))
+    return int(out[0]), int(out[1])
+
+
+def event_plan(S, L, N, n_cu):
+    """kin::event_plan: (wavefronts, rows of a part); reads KIN_EVENT_WAVES and KIN_EVENT_PART_ROWS."""
+    return _plan("plan_host_event", S, L, N, n_cu)
+
+
+def resample_plan(S, Q, N, n_cu):
+    """kin::resample_plan: (queries of a tile, wavefronts); reads KIN_RESAMPLE_TILE_QUERIES and KIN_RESAMPLE_WAVES."""
+    return _plan("plan_host_resample", S, Q, N, n_cu)
+
+
+def plan_constants():
+    out = np.zeros(6, np.int32)
+    lib().plan_host_constants(out.ctypes.data_as(POINTER(c_int32)))
+    return dict(zip(("EVENT_LANES", "EVENT_WAVES_MAX", "EVENT_ROWS_IN_FLIGHT", "RESAMPLE_SLICE", "RESAMPLE_WAVES_MAX", "RESAMPLE_TILE_MAX"),
+                    (int(v) for v in out)))
+
+
+def stored_record(h):
+    """The stored ensemble of a capi.HipNetwork as it lies on the device, [K][n_rows][N]: the rows past a member's n_saved too."""
+    K, rows, n, _ = h.ensemble_size()
+    out = np.empty((K, rows, n))
+    rc = lib().plan_host_record_download(h.handle, _pd(out), out.size)
+    assert rc == 0, f"plan_host_record_download: {rc}"
+    return out
 
 
 def _pd(a):

@@ -7,7 +7,8 @@ compared with it bit for bit.
 The cases are built at the smallest shapes at which the kernel can go wrong: species counts at the edges of a 64-species wave
 row, query counts below, at and above the tile of TILE queries the GPU tests force (so that a workgroup holds a partial tile and
 a wavefront takes several queries), segments of L, 0, 1 and about L / 2 rows with poison behind them, and a query for every
-situation the definition names."""
+situation the definition names. SLICE_CASES reach the second and third species slice of a workgroup's 1024, PLAN_CASE with
+PLANS the tiles and wavefront counts the launcher chooses for large calls."""
 import numpy as np
 
 from event_cases import same_bits  # noqa: F401  (the comparison the resampling tests use as well)
@@ -113,15 +114,22 @@ def _queries(x, n, Q, offset):
     return np.array([pool[(offset + q) % len(pool)] for q in range(Q)])
 
 
-def make_case(S, L, N, Q, seed, x_per=False, q_per=False, offset=0):
-    """Segments of L, 0, 1 and about L / 2 rows (then L again); the states past a segment's own rows are NaN and 1e300, and its
-    own axis past them NaN."""
+PAYLOADS = np.array([0x7FF8000000001234, 0xFFF80000DEADBEEF], dtype=np.uint64).view(np.float64)      # NaNs a copy has to keep
+
+
+def make_case(S, L, N, Q, seed, x_per=False, q_per=False, offset=0, seg_rows=None, row_begins=None, payloads=False):
+    """Segments of L, 0, 1 and about L / 2 rows (then L again), or of seg_rows; the states past a segment's own rows are NaN and
+    1e300, and its own axis past them NaN. payloads: the species i % 64 == 12 hold NaNs with a payload in every third row."""
     rng = np.random.default_rng(seed)
     u = np.empty((S, L, N))
     for s in range(S):
         for i in range(N):
             u[s, :, i] = _column(i % COLUMN_KINDS, L, rng)
-    seg_n = np.array([(L, 0, min(1, L), (L + 1) // 2)[s % 4] if s < 4 else L for s in range(S)], dtype=np.int64)
+    if payloads:
+        for k, j in enumerate(range(0, L, 3)):
+            u[:, j, 12::64] = PAYLOADS[k % 2]
+    seg_n = np.array([(L, 0, min(1, L), (L + 1) // 2)[s % 4] if s < 4 else L for s in range(S)] if seg_rows is None else seg_rows,
+                     dtype=np.int64)
     x = np.stack([_axis(L, rng) + 0.375 * s for s in range(S)]) if x_per else _axis(L, rng)
     xq = np.stack([_queries(x[s] if x_per else x, max(int(seg_n[s]), 1), Q, offset + s) for s in range(S)]) if q_per \
         else _queries(x[0] if x_per else x, L, Q, offset)
@@ -131,7 +139,8 @@ def make_case(S, L, N, Q, seed, x_per=False, q_per=False, offset=0):
         if x_per:
             x[s, n:] = np.nan
     half = (L + 1) // 2
-    row_begins = tuple(sorted({0, 1, max(half - 1, 0), half, max(L - 1, 0), L}))
+    if row_begins is None:
+        row_begins = tuple(sorted({0, 1, max(half - 1, 0), half, max(L - 1, 0), L}))
     name = f"S{S}-L{L}-N{N}-Q{Q}" + ("-xper" if x_per else "") + ("-qper" if q_per else "")
     return dict(id=name, u=u, x=x, xq=xq, seg_n=seg_n, row_begins=row_begins)
 
@@ -147,3 +156,24 @@ CASES = [
     make_case(4, 3, 65, 9, 8, q_per=True, offset=3),
     make_case(2, 37, 257, 5, 9, x_per=True, offset=7),
 ]
+
+# More than one species slice of SLICE species (blockIdx.y of the kernel): exactly one slice, a second slice of one species, of a
+# wave row and one species, and a third slice of one species. Segments of L and about L / 2 rows; three row_begins - every
+# row, one row of the short segment, none of it - keep the plain-Python restatement short. -0.0 (kind 1), subnormals (kind 2)
+# and NaN payloads sit on every slice: a copied row keeps them.
+SLICE = 1024
+_SLICED = dict(seg_rows=(9, 5), row_begins=(0, 4, 5), payloads=True)
+SLICE_CASES = [
+    make_case(2, 9, SLICE, 5, 21, q_per=True, offset=2, **_SLICED),
+    make_case(2, 9, SLICE + 1, 5, 22, x_per=True, q_per=True, **_SLICED),
+    make_case(2, 9, SLICE + 64 + 1, 5, 23, x_per=True, offset=8, **_SLICED),
+    make_case(2, 9, 2 * SLICE + 1, 5, 24, offset=1, **_SLICED),
+]
+
+# One case for the launcher's plans: 70 queries of 65 species over axes of 37, 19 and 1 rows. PLANS are (tile, wavefronts) pairs:
+# every tile resample_plan chooses (8, 16, 32 - 4 is FORCED's), one query per workgroup, a tile that is no power of two, and
+# the largest tile on one wavefront - 64 threads search 70 queries: the search loop's second trip - and on sixteen. A tile of
+# 32 leaves a last tile of 6 queries and gives each of 4 wavefronts 8 queries.
+PLAN_CASE = make_case(3, 37, 65, 70, 25, x_per=True, q_per=True, offset=5, seg_rows=(37, 19, 1), row_begins=(0, 18, 36), payloads=True)
+PLANS = [(1, 1), (8, 4), (16, 4), (32, 4), (33, 3), (256, 1), (256, 16)]
+GPU_CASES = CASES + SLICE_CASES + [PLAN_CASE]      # what the GPU tests run under FORCED and the launcher's own plan

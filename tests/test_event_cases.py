@@ -1,4 +1,6 @@
-"""Host-side tests (no device) of the event-time pass: the NumPy restatement against closed forms, the argument checks of the
+"""Host-side tests (no device) of the event-time pass: the NumPy restatement against closed forms and against a replay of the
+kernel's decomposition under every launcher setting the GPU tests use (which also shows that the cases reach the paths they are
+named after: the parts the second walk passes over, NaN rows, zeros of both signs), the argument checks of the
 Python layers (ValueError before anything touches a device) and how `solving` hands event times to the statistics entries,
 on a stand-in for capi.HipNetwork."""
 import ctypes
@@ -66,13 +68,112 @@ def test_cases_cover_what_they_claim():
             assert {0, min(1, L), L} <= set(c["seg_n"].tolist())
             for s, n in enumerate(c["seg_n"]):
                 assert np.all(~np.isfinite(c["u"][s, n:]) | (c["u"][s, n:] == 1e300))
-    hb = ec.CASES[-1]
+    hb = next(c for c in ec.CASES if c["id"] == "hand-built")
     r = ec.ref_events(hb["u"], hb["t"], hb["levels"]["abs"])
     t = hb["t"]
     assert r["t_cross"][0, 0] == t[C - 1] + 0.5 * (t[C] - t[C - 1]) and r["t_cross"][0, 2] == t[C]      # the halo; a sample
     assert r["t_cross"][0, 3] == t[0] and np.isnan(r["t_cross"][0, 4]) and r["t_peak"][0, 6] == t[2]
     last = ec.ref_events(hb["u"], t, hb["levels"]["of_peak"], kind="of_peak", direction="fall", start="peak")
     assert last["t_cross"][0, 9] == t[-1] and last["t_peak"][0, 9] == t[-1]
+    # the late-peak case: where its peaks and crossings land (a chord's time lies in the interval that ends at the crossing row)
+    lp, W = ec.LATE_PEAK, 2
+    u, t, lev = lp["u"], lp["t"], lp["levels"]["of_peak"]
+    L, i = u.shape[1], np.arange(64)
+    assert (u.shape, L) == ((2, L, 65), 4 * C + 1) and lp["seg_n"].tolist() == [L, 3 * C + 1]
+    peak_row = u[0, :, :64].argmax(axis=0)
+    assert peak_row.min() == 2 * C and peak_row[0] == 2 * C and peak_row.max() < 3 * C and u[0, :, 64].argmax() == 0
+    fall = ec.ref_events(u, t, lev, kind="of_peak", direction="fall", start="peak", seg_n=lp["seg_n"])["t_cross"][0]
+    rise = ec.ref_events(u, t, lev, kind="of_peak", direction="rise", start="begin", seg_n=lp["seg_n"])["t_cross"][0]
+    lands = lambda tc, rows: np.all((t[rows - 1] < tc) & (tc <= t[rows]))
+    k = i % 7
+    assert np.array_equal(fall[:64][k == 0], t[peak_row[k == 0]]) and lands(fall[:64][k == 1], peak_row[k == 1] + 1)
+    assert lands(fall[:64][k == 2], np.full((k == 2).sum(), 3 * C)) and lands(fall[:64][k == 3], np.full((k == 3).sum(), L - 1))
+    assert np.isnan(fall[:64][k == 4]).all()
+    assert lands(rise[:64][k == 5], np.full((k == 5).sum(), 2 * C - 1)) and lands(rise[:64][k == 6], np.full((k == 6).sum(), 2 * C))
+    # ... and what the second walk of the kernel's decomposition passes over: with two wavefronts and parts of C rows, parts 0
+    # and 1 of both segments in the first species group, nothing in the second (species 64 peaks at its first row)
+    for kind in ("abs", "of_peak"):
+        _, skipped, walked = ec.replay_events(u, t, lp["levels"][kind], kind=kind, direction="fall", start="peak", seg_n=lp["seg_n"],
+                                              waves=W, part_rows=C)
+        assert skipped.tolist() == [4, 0] and walked.tolist() == [5 + 4 - 4, 5 + 4], (kind, skipped, walked)
+    _, skipped, walked = ec.replay_events(u, t, lev, kind="of_peak", direction="rise", start="begin", seg_n=lp["seg_n"], waves=W, part_rows=C)
+    assert skipped.tolist() == [0, 0] and walked.tolist() == [9, 9]          # from the beginning: every part is walked
+    # the NaN and signed-zero cases hold what they are named after
+    nr = next(c for c in ec.CASES if c["id"] == "nan-rows")
+    held = np.isnan(nr["u"][0]).any(axis=0)
+    assert np.flatnonzero(held).tolist() == nr["nan_cols"] and np.isnan(nr["u"][0, :, nr["nan_cols"][7]]).all()
+    assert all(np.isnan(nr["u"][0, rb, nr["nan_cols"][rb]]) for rb in (0, 1))
+    sz = next(c for c in ec.CASES if c["id"] == "signed-zeros")
+    assert np.all(sz["u"] == 0.0) and np.signbit(sz["u"][0, :2, 0]).tolist() == [True, False] and np.signbit(sz["u"][0, :2, 1]).tolist() == [False, True]
+    assert np.signbit(sz["u"][0, :, 2]).tolist() == [True] * (2 * C) + [False]
+    # the matrix of launcher settings: every wavefront count the launcher chooses, a part of one row, parts that are no multiple of
+    # the rows in flight, and the launcher's own size
+    plans = {ec.knob_plan(kn, 37) for kn in ec.KNOBS}
+    assert {w for w, _ in plans} == {1, 2, 4, 8, 16} and {c for _, c in plans} >= {1, 3, 5, 6, 4, 8, 12, 40} and len(ec.KNOBS) == 21
+    assert [c["id"] for c in ec.MATRIX_CASES] == ["S2-L37-N130-tper", "late-peak", "signed-zeros"]
+    assert all(set(ec.MATRIX_ROW_BEGINS[c["id"]]) <= set(c["row_begins"]) for c in ec.MATRIX_CASES)
+
+
+def _peak_by_greater_than(u, row_begin, seg_n):
+    """(u_peak, row of the peak) by the chain the restatement had before it took up the header's NaN rule: from the first row,
+    a later row only if it compares greater."""
+    S, L, N = u.shape
+    peak, row = np.zeros((S, N)), np.full((S, N), -1)
+    for s in range(S):
+        n = L if seg_n is None else int(seg_n[s])
+        for i in range(N):
+            if row_begin < n:
+                col = u[s, :n, i].tolist()
+                peak[s, i], row[s, i] = col[row_begin], row_begin
+                for j in range(row_begin + 1, n):
+                    if col[j] > peak[s, i]:
+                        peak[s, i], row[s, i] = col[j], j
+    return peak, row
+
+
+def test_the_nan_rule_changes_no_case_without_a_nan_inside_a_segment():
+    for c in ec.CASES:
+        u, t, seg_n = c["u"], c["t"], c["seg_n"]
+        S, L, N = u.shape
+        inside = np.arange(L)[None, :] < (np.full(S, L) if seg_n is None else seg_n)[:, None]
+        clean = ~np.isnan(np.where(inside[:, :, None], u, 0.0)).any(axis=1)          # [S][N]: no NaN among the segment's rows
+        assert clean.all() == ("nan_cols" not in c), c["id"]
+        for rb in c["row_begins"]:
+            r = ec.ref_events(u, t, None, row_begin=rb, never=-1.0, seg_n=seg_n)
+            peak, row = _peak_by_greater_than(u, rb, seg_n)
+            T2 = np.broadcast_to(t, (S, L)) if t.ndim == 1 else t
+            t_peak = np.where(row >= 0, T2[np.arange(S)[:, None], np.maximum(row, 0)], -1.0)
+            assert r["u_peak"][clean].tobytes() == peak[clean].tobytes() and r["t_peak"][clean].tobytes() == t_peak[clean].tobytes(), (c["id"], rb)
+    # on the NaN columns: the maximum of the rows that are numbers, NaN only where every row is NaN
+    c = next(c for c in ec.CASES if c["id"] == "nan-rows")
+    for rb in c["row_begins"]:
+        got = ec.ref_events(c["u"], c["t"], None, row_begin=rb)["u_peak"][0, c["nan_cols"]]
+        rows = c["u"][0, rb:, c["nan_cols"]].T
+        every = np.isnan(rows).all(axis=0)
+        assert every.sum() == (1 if rb == 0 else 2) and np.isnan(got[every]).all()
+        assert np.array_equal(got[~every], np.nanmax(rows[:, ~every], axis=0))
+
+
+@pytest.mark.parametrize("case", ec.CASES, ids=[c["id"] for c in ec.CASES])
+def test_the_kernels_decomposition_gives_the_restatement(case):
+    """The replay under every setting of the matrix, every combination and every row_begin of the case: the bits of ref_events
+    (as the case is judged) and the same bytes under every setting."""
+    u, t, seg_n, never = case["u"], case["t"], case["seg_n"], case["never"]
+    checked = 0
+    for kind, direction, start in ec.COMBOS:
+        level = case["levels"][kind]
+        for rb in case["row_begins"]:
+            kw = dict(kind=kind, direction=direction, start=start, row_begin=rb, never=never, seg_n=seg_n)
+            ref = ec.ref_events(u, t, level, **kw)
+            first = None
+            for plan in sorted({ec.knob_plan(kn, u.shape[1]) for kn in ec.KNOBS} | {ec.knob_plan({}, u.shape[1])}):
+                got = ec.replay_events(u, t, level, waves=plan[0], part_rows=plan[1], **kw)[0]
+                first = first or got
+                for q in ec.OUTPUTS:
+                    assert ec.agree(case, q, got[q], ref[q]), (case["id"], kw, plan, q)
+                    assert ec.judged(case, q, got[q]).tobytes() == ec.judged(case, q, first[q]).tobytes(), (case["id"], kw, plan, q)
+                checked += 1
+    assert checked >= len(ec.COMBOS) * len(case["row_begins"]) * 5
 
 
 # ---- argument checks: ValueError, and no device -------------------------------------------------------------------------------------

@@ -119,6 +119,42 @@ def test_a_stored_result_is_the_record_every_ensemble_pass_reads(stored):
     assert h.ensemble_size()[1] == 9 and ec.same_bits(h.ensemble_resample(T, AT), ref)      # the next solve replaces the record
 
 
+def _stored_block(ref, run):
+    """What a stored result has to be: the restatement, zeros from each member's first uncovered query on."""
+    block = ref.copy()
+    for m in range(K):
+        block[m, run[m]:] = 0.0
+    return block
+
+
+def test_the_zero_tail_of_a_stored_result_byte_for_byte(stored):
+    """resample_zero_tail_kernel over the record as it lies on the device (res_host.stored_record: no entry of the library reads
+    the rows past a member's n_saved): every member's tail short (the fixture's queries), every member's whole block (a first
+    query below every range: n_saved' = 0) and 450 queries - Q N = 135 000 entries, more than 64 x 2048: the cap of 64
+    workgroup rows and a second grid-stride trip."""
+    from tests import res_host
+    h, T, ns, u = stored["h"], stored["T"], stored["ns"], stored["u"]
+    assert res_host.stored_record(h).tobytes() == u.tobytes()                  # the solve's own record, as downloaded
+    many = np.linspace(900.0, 1300.0, 450)
+    assert len(many) * N > 64 * 256 * 8
+    try:
+        for at, expect in ((AT, [5, 8, 9, 9]), (np.concatenate([[850.0], AT]), [0, 0, 0, 0]), (many, None)):
+            _restore(stored)
+            ref, jc, _ = rc.ref_resample(u, T, at, seg_n=ns)
+            run = rc.covered_run(jc, "fill")
+            assert expect is None or run.tolist() == expect
+            assert h.ensemble_resample(T, at, store=True, download=False) is None
+            Kk, rows, n, ns2 = h.ensemble_size()
+            assert (Kk, rows, n) == (K, len(at), N) and np.array_equal(ns2, run), (len(at), ns2, run)
+            got, block = res_host.stored_record(h), _stored_block(ref, run)
+            assert got.tobytes() == block.tobytes(), (len(at), np.argwhere(got.view(np.int64) != block.view(np.int64))[:5])
+        assert 0 < run[0] < run[1] < len(many) and run[2] == len(many)           # (of the 450: tails of two lengths, and none)
+        assert not got[0, run[0]:].any() and got[0, :run[0]].any()
+    finally:
+        _restore(stored)
+    assert h.ensemble_size()[1] == 9
+
+
 def test_resample_before_any_ensemble_solve_is_a_state_error():
     net, Ea, A = synthetic_crn(20, 60)
     h = capi.HipNetwork.from_flat(net)

@@ -2,7 +2,34 @@
 (buffers made by torch) over every case of event_cases.py, every (kind, direction, start) combination and every row_begin of
 the case, bit for bit against event_cases.ref_events (a NaN `never` by its place). The launcher's knobs are forced to parts of
 PART_ROWS rows on two wavefronts - so that a wavefront walks several parts and a crossing's interval spans two of them - and
-left at their defaults: the bytes are the same. Then the status of every refused argument."""
+left at their defaults: the bytes are the same. Then the status of every refused argument.
+
+Beyond the first cases (event_cases.py): NaN rows inside a segment, where only u_peak is specified and is compared - the
+header's fmax rule, which ref_events restates; zeros of both signs, whose peak is compared with the restatement by value, byte
+for byte between the decompositions, and with the header's rule (+0.0 if any row holds it); and LATE_PEAK, whose second walk
+passes over whole parts (tests/test_event_cases.py shows on a replay of the decomposition that it does). The longest generated
+case, LATE_PEAK and the zeros run under ec.KNOBS: 1, 4, 8 and 16 wavefronts with parts of 1, 3, 5 and 6 rows and of the
+launcher's own size. tests/test_pass_plans_host.py has event_plan itself.
+
+Measured on an MI355X: u_peak of the zero columns -0 +0 -0.., +0 -0 -0.., -0.. +0, +0.., -0.., -0.. +0 -0.. is +0.0 in all
+but the all-negative one under every setting; from row_begin 1 the second column is all -0.0 and gives -0.0.
+
+Mutation check (value-only changes on a scratch build, one at a time, nothing of it kept): which tests of this file fail, and
+what the four modules that launch these kernels did before this change (test_gpu_event_times, test_gpu_resample,
+test_gpu_ensemble_event_times, test_gpu_ensemble_resample: 38 tests; no other module reaches event_kernels.hip).
+  d the combine of the wavefronts' peaks uses bv = first ? v : (v > bv ? v : bv): 4 of the 20 tests fail -
+    every_case_bit_for_bit on nan-rows and signed-zeros, every_knob_setting on signed-zeros, and
+    signed_zeros_and_nan_rows_follow_the_stated_rules.
+    Before: MISSED - all 38 passed.
+  e the second walk passes over a part with p1 <= skip_below + 1: 13 fail - every_case_bit_for_bit on the nine generated cases
+    and on late-peak, every_knob_setting on its three.
+    Before: 9 of the 13 tests of test_gpu_event_times failed (every generated case); the other three modules passed.
+  f event_walk leaves out the guarded tail of an in-flight group (the rows of a part past its last whole group of
+    EVENT_ROWS_IN_FLIGHT; the part's first group is kept whole, so that the mutated kernel still has a peak row to read the
+    time of): 3 fail - every_knob_setting on its three cases, each first under one wavefront with parts of 5 rows.
+    Before: MISSED - all 38 passed (every part of the forced and of the default plan is a multiple of four rows or the
+    segment's last).
+  The mutations of resample_kernels.hip (a, b, c: test_gpu_resample.py) leave every test of this file passing."""
 import numpy as np
 import pytest
 
@@ -60,7 +87,9 @@ def test_every_case_bit_for_bit(case, monkeypatch):
             plain = h.events_segmented(u, t, level=level, seg_n=seg_n, **kw)
             for q in ec.OUTPUTS:
                 for name, got in (("host", host), ("device", dev), ("default plan", plain)):
-                    assert ec.same_bits(got[q], ref[q]), (case["id"], kw, q, name, got[q], ref[q])
+                    assert ec.agree(case, q, got[q], ref[q]), (case["id"], kw, q, name, got[q], ref[q])
+                    # forced and default knobs, host and device entry: the same bytes, the sign of a zero included
+                    assert ec.judged(case, q, got[q]).tobytes() == ec.judged(case, q, host[q]).tobytes(), (case["id"], kw, q, name)
             checked += 1
     assert checked == len(ec.COMBOS) * len(case["row_begins"])
     # a second call repeats the bits; outputs that are not asked for are not needed
@@ -73,6 +102,57 @@ def test_every_case_bit_for_bit(case, monkeypatch):
     peaks = events_dev(h, u, t, None, seg_n=seg_n, want=("u_peak",), row_begin=kw["row_begin"], never=never)
     assert peaks["u_peak"].tobytes() == a["u_peak"].tobytes()
     h.close()
+
+
+@pytest.mark.parametrize("case", ec.MATRIX_CASES, ids=[c["id"] for c in ec.MATRIX_CASES])
+def test_every_knob_setting_gives_the_same_bytes(case, monkeypatch):
+    """ec.KNOBS - 1, 4, 8 and 16 wavefronts with parts of 1, 3, 5 and 6 rows and of the launcher's own size, and the forced
+    setting - over every combination at a row_begin of 0 and one inside the segment, through the host and the device entry:
+    the restatement's bits, and the same bytes under every setting."""
+    u, t, seg_n, never = case["u"], case["t"], case["seg_n"], case["never"]
+    h = network(u.shape[2])
+    checked = 0
+    for kind, direction, start in ec.COMBOS:
+        level = case["levels"][kind]
+        for rb in ec.MATRIX_ROW_BEGINS[case["id"]]:
+            kw = dict(kind=kind, direction=direction, start=start, row_begin=rb, never=never)
+            ref = ec.ref_events(u, t, level, seg_n=seg_n, **kw)
+            first = None
+            for knobs in ec.KNOBS:
+                for name in ("KIN_EVENT_WAVES", "KIN_EVENT_PART_ROWS"):
+                    monkeypatch.delenv(name, raising=False)
+                for name, value in knobs.items():
+                    monkeypatch.setenv(name, value)
+                host = h.events_segmented(u, t, level=level, seg_n=seg_n, **kw)
+                dev = events_dev(h, u, t, level, seg_n=seg_n, **kw)
+                first = first or host
+                for q in ec.OUTPUTS:
+                    for name, got in (("host", host), ("device", dev)):
+                        assert ec.agree(case, q, got[q], ref[q]), (case["id"], kw, knobs, q, name, got[q], ref[q])
+                        assert ec.judged(case, q, got[q]).tobytes() == ec.judged(case, q, first[q]).tobytes(), (case["id"], kw, knobs, q, name)
+                checked += 1
+    assert checked == len(ec.COMBOS) * 2 * len(ec.KNOBS)
+    h.close()
+
+
+def test_signed_zeros_and_nan_rows_follow_the_stated_rules():
+    """What the header says of a peak among zeros of both signs and of NaN rows, on the device under the forced knobs: +0.0 if any
+    row holds +0.0, its first row's time; the maximum of the rows that are numbers, NaN only where every row is NaN."""
+    by_id = {c["id"]: c for c in ec.CASES}
+    for case in (by_id["signed-zeros"], by_id["nan-rows"]):
+        u, t = case["u"], case["t"]
+        h = network(u.shape[2])
+        for rb in case["row_begins"]:
+            got = h.events_segmented(u, t, row_begin=rb)
+            rows = u[0, rb:]
+            with np.errstate(invalid="ignore"):
+                expect = np.fmax.reduce(rows, axis=0)
+            if case.get("zeros"):
+                expect = np.where(np.signbit(rows).all(axis=0), -0.0, 0.0)
+                assert np.all(got["t_peak"] == t[rb])
+                print("signed zeros, row_begin", rb, "u_peak sign bits", np.signbit(got["u_peak"][0]).tolist())
+            assert ec.same_bits(got["u_peak"][0], expect), (case["id"], rb, got["u_peak"], expect)
+        h.close()
 
 
 def test_a_segment_does_not_depend_on_its_neighbours():

@@ -3,7 +3,27 @@
 the case, bit for bit against resample_cases.ref_resample in u_q, jc and w (a NaN by its place). The launcher's knobs are
 forced to tiles of TILE queries on two wavefronts - a partial tile, several queries per wavefront - and left at their defaults:
 the bytes are the same. A repeat gives the same bytes, nothing outside the written range is touched, and every refused
-argument has its status."""
+argument has its status.
+
+Beyond the first cases: rc.SLICE_CASES have 1024, 1025, 1089 and 2049 species - one, two and three species slices
+(blockIdx.y), whose brackets must be those of a call over one slice alone; rc.PLAN_CASE runs under every (tile, wavefronts)
+pair of rc.PLANS, the tiles resample_plan chooses for large calls and a tile larger than its workgroup among them. Every row
+that is no chord is compared byte for byte: -0.0 and NaN payloads as stored. tests/test_pass_plans_host.py has resample_plan
+itself, tests/test_resample_host.py the bisection on long axes.
+
+Mutation check (value-only changes on a scratch build, one at a time, nothing of it kept): which tests of this file fail, and
+what the four modules that launch these kernels did before this change (test_gpu_resample, test_gpu_event_times,
+test_gpu_ensemble_resample, test_gpu_ensemble_event_times: 38 tests; no other module reaches resample_kernels.hip).
+  a launch_resample launches ceil_div(N, 2 * RESAMPLE_SLICE) slices: 6 of the 22 tests fail - every_case_bit_for_bit and
+    brackets_of_a_sliced_call on the cases of 1025, 1089 and 2049 species (the sentinel is still there).
+    Before: MISSED - all 38 passed.
+  b the search loop of resample_kernel runs once (if (threadIdx.x < nq); the tile's later queries are left as `fill`, so that
+    the mutated kernel reads no row index it has not written): 1 fails - every_plan_gives_the_same_bytes, at (256, 1).
+    Before: MISSED - all 38 passed.
+  c a slice >= 1 also writes jc and w, from a search that starts at row_begin + 1: 4 fail - every_case_bit_for_bit on the
+    cases of 1025, 1089 and 2049 species, brackets_of_a_sliced_call on that of 2049 (which slice's write lands last is a race).
+    Before: MISSED - all 38 passed.
+  The mutations of event_kernels.hip (d, e, f: test_gpu_event_times.py) leave every test of this file passing."""
 import numpy as np
 import pytest
 
@@ -40,6 +60,9 @@ def resample_dev(h, u, x, xq, seg_n=None, brackets=True, **kw):
     torch.cuda.synchronize()
     out, jc, w = out.cpu().numpy(), jc.cpu().numpy(), w.cpu().numpy()
     assert np.all(out[S * Q * N:] == SENTINEL) and np.all(jc[S * Q:] == -77) and np.all(w[S * Q:] == SENTINEL)
+    assert not np.any(out[:S * Q * N] == SENTINEL)      # every species of every slice, query and segment was written
+    if brackets:
+        assert not np.any(jc[:S * Q] == -77) and not np.any(w[:S * Q] == SENTINEL)
     if not brackets:
         assert np.all(jc == -77) and np.all(w == SENTINEL)
     return out[:S * Q * N].reshape(S, Q, N), jc[:S * Q].reshape(S, Q), w[:S * Q].reshape(S, Q)
@@ -54,10 +77,14 @@ def _force(monkeypatch, on):
 
 
 def _same(got, ref):
-    return rc.same_bits(got[0], ref[0]) and np.array_equal(got[1], ref[1]) and got[2].tobytes() == ref[2].tobytes()
+    """u_q bit for bit (a NaN by its place), jc equal, w byte for byte; and every row that is no chord (w == 0: a copy, a held
+    row, the fill) byte for byte: -0.0 and NaN payloads as they were stored."""
+    plain = ref[2] == 0.0
+    return rc.same_bits(got[0], ref[0]) and np.array_equal(got[1], ref[1]) and got[2].tobytes() == ref[2].tobytes() and \
+        got[0][plain].tobytes() == ref[0][plain].tobytes()
 
 
-@pytest.mark.parametrize("case", rc.CASES, ids=[c["id"] for c in rc.CASES])
+@pytest.mark.parametrize("case", rc.GPU_CASES, ids=[c["id"] for c in rc.GPU_CASES])
 def test_every_case_bit_for_bit(case, monkeypatch):
     u, x, xq, seg_n = case["u"], case["x"], case["xq"], case["seg_n"]
     h = network(u.shape[2])
@@ -86,6 +113,54 @@ def test_every_case_bit_for_bit(case, monkeypatch):
     assert only.tobytes() == a[0].tobytes()
     bare = resample_dev(h, u, x, xq, seg_n=seg_n, brackets=False, **kw)
     assert bare[0].tobytes() == a[0].tobytes()
+    h.close()
+
+
+@pytest.mark.parametrize("case", rc.SLICE_CASES, ids=[c["id"] for c in rc.SLICE_CASES])
+def test_brackets_of_a_sliced_call_are_those_of_a_single_slice_call(case, monkeypatch):
+    """jc and w are written once, by slice 0: a call over the first 64 species alone, on the same axes, gives the same bytes;
+    and its u_q is the sliced call's first 64 columns."""
+    u, x, xq, seg_n = case["u"], case["x"], case["xq"], case["seg_n"]
+    h, h64 = network(u.shape[2]), network(64)
+    for on in (True, False):
+        _force(monkeypatch, on)
+        for rb in case["row_begins"]:
+            kw = dict(mode="hold", fill=0.125, row_begin=rb, seg_n=seg_n)
+            full = h.resample_segmented(u, x, xq, want_brackets=True, **kw)
+            dev = resample_dev(h, u, x, xq, **kw)
+            one = h64.resample_segmented(u[:, :, :64], x, xq, want_brackets=True, **kw)
+            ref = rc.ref_resample(u[:, :, :64], x, xq, **kw)
+            assert _same(one, ref), (case["id"], rb)
+            for got in (full, dev):
+                assert np.array_equal(got[1], one[1]) and got[2].tobytes() == one[2].tobytes(), (case["id"], rb, on)
+                assert got[0][:, :, :64].tobytes() == one[0].tobytes(), (case["id"], rb, on)
+    h.close(); h64.close()
+
+
+def test_every_plan_gives_the_same_bytes(monkeypatch):
+    """rc.PLAN_CASE under every (tile, wavefronts) pair of rc.PLANS: the restatement's bits in u_q, jc and w, and the same bytes
+    under every plan, through the host and the device entry."""
+    case = rc.PLAN_CASE
+    u, x, xq, seg_n = case["u"], case["x"], case["xq"], case["seg_n"]
+    assert xq.shape[-1] == 70 and u.shape[2] == 65
+    h = network(u.shape[2])
+    checked = 0
+    for rb in case["row_begins"]:
+        for req in rc.REQUESTS:
+            kw = dict(req, row_begin=rb)
+            ref = rc.ref_resample(u, x, xq, seg_n=seg_n, **kw)
+            first = None
+            for tile, waves in rc.PLANS:
+                monkeypatch.setenv("KIN_RESAMPLE_TILE_QUERIES", str(tile))
+                monkeypatch.setenv("KIN_RESAMPLE_WAVES", str(waves))
+                host = h.resample_segmented(u, x, xq, seg_n=seg_n, want_brackets=True, **kw)
+                dev = resample_dev(h, u, x, xq, seg_n=seg_n, **kw)
+                first = first or host
+                for name, got in (("host", host), ("device", dev)):
+                    assert _same(got, ref), (kw, tile, waves, name)
+                    assert all(a.tobytes() == b.tobytes() for a, b in zip(got, first)), (kw, tile, waves, name)
+                checked += 1
+    assert checked == len(case["row_begins"]) * len(rc.REQUESTS) * len(rc.PLANS)
     h.close()
 
 

@@ -1,5 +1,6 @@
 """Host tests of the resampling pass (no device): the symbols, kin_resample_bracket_host against the restatement of
-resample_cases.py bit for bit, the statuses of the host-checkable arguments, the refusal of every malformed resample= dict
+resample_cases.py bit for bit - on the cases and on axes of up to 1000 rows with plateaus of every kind, queried at, next to
+and between their values -, what the slice and plan cases hold, the statuses of the host-checkable arguments, the refusal of every malformed resample= dict
 before a handle exists, and the restatement's own self-check."""
 import os
 import re
@@ -68,6 +69,61 @@ def test_cases_cover_what_they_claim():
         if len(inner) and np.isin(s0, inner).any():
             seen.add("plateau")
     assert seen >= {"nan", "+inf", "-inf", ("jc", -1), ("jc", -2), ("jc", -3), "copy", "chord", "repeat", "unsorted", "plateau"}, seen
+
+
+def test_slice_and_plan_cases_cover_what_they_claim():
+    S1 = rc.SLICE
+    assert [c["u"].shape for c in rc.SLICE_CASES] == [(2, 9, n) for n in (S1, S1 + 1, S1 + 65, 2 * S1 + 1)]
+    assert any(c["x"].ndim == 2 and c["xq"].ndim == 2 for c in rc.SLICE_CASES) and {c["x"].ndim for c in rc.SLICE_CASES} == {1, 2}
+    for c in rc.SLICE_CASES + [rc.PLAN_CASE]:
+        u, L = c["u"], c["u"].shape[1]
+        assert len(c["row_begins"]) == 3 and c["seg_n"].tolist()[:2] == [L, (L + 1) // 2]
+        # on the last slice as on the first: -0.0, subnormals and a NaN with a payload among the rows a query copies
+        out, jc, w = rc.ref_resample(u, c["x"], c["xq"], seg_n=c["seg_n"])
+        copied = out[(jc >= 0) & (w == 0.0)]
+        assert len(copied)
+        for i0 in (0, S1) if u.shape[2] > S1 + 64 else (0,):
+            assert np.signbit(copied[:, i0 + 1]).all() and np.all(copied[:, i0 + 1] == 0.0)
+            assert np.all(np.abs(copied[:, i0 + 2]) < 2.3e-308) and np.any(copied[:, i0 + 2] != 0.0)
+            assert set(np.unique(np.ascontiguousarray(copied[:, i0 + 12]).view(np.uint64)).tolist()) & set(rc.PAYLOADS.view(np.uint64).tolist())
+    assert sum(c["u"].shape[2] > S1 + 64 for c in rc.SLICE_CASES) == 2
+    pc = rc.PLAN_CASE
+    assert pc["u"].shape == (3, 37, 65) and pc["xq"].shape == (3, 70) and pc["x"].shape == (3, 37)
+    assert rc.PLANS == [(1, 1), (8, 4), (16, 4), (32, 4), (33, 3), (256, 1), (256, 16)]
+    assert 70 % 32 == 6 and 32 // 4 == 8 and 70 > 64 * 1          # the partial tile; queries per wavefront; the search's second trip
+
+
+def _long_axes(L, rng):
+    """[4][L]: strictly increasing; one plateau over all rows but the first; over all but the last; plateaus of random length."""
+    inc = np.cumsum(rng.random(L) + 0.125) + 900.0
+    late, early = inc.copy(), inc.copy()
+    late[1:] = inc[1]
+    early[:-1] = inc[0]
+    steps = np.cumsum(np.where(rng.random(L) < 0.4, rng.random(L) + 0.125, 0.0)) + 900.0
+    return np.stack([inc, late, early, steps])
+
+
+@pytest.mark.parametrize("L", [2, 3, 64, 65, 1000])
+def test_bisection_is_the_row_walk_on_long_axes_and_plateaus(L):
+    """kin_resample_bracket_host's bisection against ref_bracket's walk over the rows: a query at every axis value, at its two
+    neighbours among the doubles, at the midpoint of every rising interval, at +-Inf and at NaN."""
+    x = _long_axes(L, np.random.default_rng(L))
+    qs = []
+    for xs in x:
+        rising = np.flatnonzero(np.diff(xs) > 0)
+        qs.append(np.concatenate([xs, np.nextafter(xs, -np.inf), np.nextafter(xs, np.inf), 0.5 * (xs[rising] + xs[rising + 1]),
+                                  [np.inf, -np.inf, np.nan]]))
+    Q = max(len(q) for q in qs)
+    xq = np.stack([np.concatenate([q, np.full(Q - len(q), np.nan)]) for q in qs])
+    assert len(np.flatnonzero(np.diff(x[3]) == 0)) > 0 or L < 4
+    for rb in sorted({0, 1, L - 1, L}):
+        jc, w = capi.resample_brackets(x, xq, row_begin=rb)
+        ref = [[rc.ref_bracket(xs, rb, L, v) for v in q] for xs, q in zip(x.tolist(), xq.tolist())]
+        jc_ref, w_ref = np.array([[r[0] for r in row] for row in ref], np.int32), np.array([[r[1] for r in row] for row in ref])
+        assert np.array_equal(jc, jc_ref), (L, rb)
+        assert w.tobytes() == w_ref.tobytes(), (L, rb)
+        if rb < L - 1:
+            assert {rc.BELOW, rc.ABOVE, rc.NONE} <= set(jc.ravel().tolist()) and (jc >= 0).any() and (w > 0.0).any()
 
 
 def test_restatement_at_a_segments_own_axis_returns_its_rows():

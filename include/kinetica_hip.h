@@ -1135,6 +1135,76 @@ int kin_solution_resample(kin_network* h, const double* x /* [n_saved] or NULL *
 int kin_ensemble_resample(kin_network* h, const double* x, int x_per_member, int64_t Q, const double* xq, int xq_per_member, int mode,
                           double fill, int64_t row_begin, int store, double* out);
 
+/* ---- observables: weighted species sums and ratios of stored states -------------------------------------------------------- */
+/* What a kinetics run is judged by is seldom one species: mole fractions u_i / sum u, lumped product classes, element totals, a
+ * selectivity, an ignition delay on a radical pool. This pass reads every stored state once, evaluates H linear forms over the
+ * species and G observables built from them, and writes them in the species' place; its result can take the place of the stored
+ * ensemble, so that every kin_ensemble_* pass that treats columns as columns runs on observables unchanged. With singleton forms
+ * and a compact output it is also the "download only these species" entry.
+ *
+ * SEGMENTS. As in kin_resample_segmented: segment s has rows j = 0 .. n_s - 1 of its block of L rows, states u[s][j][i], i < N.
+ *   Rows at or past n_s are never read. seg_n == NULL: L rows each.
+ * FORMS. H >= 0 linear forms in CSR: form_ptr[H + 1] (int64, starts at 0, non-decreasing), form_idx[nnz] (int64 species, in the
+ *   index base the handle was created with), form_w[nnz] (double). A species may repeat inside a form; its entries are separate
+ *   terms. For one state the terms of form f are t_e = form_w[e] * u[form_idx[e]], each rounded on its own; n is their number.
+ *     n == 0: the value is +0.0.
+ *     1 <= n <= 64 (short): acc = t_0, then acc = acc + t_e for e = 1 .. n - 1 in entry order. A singleton with weight 1.0 copies
+ *       the species, -0.0 included.
+ *     n > 64 (long): 64 chains; v[l] is the short rule over the entries e = l, l + 64, l + 128, ... (every chain has at least one
+ *       entry). Then for off = 32, 16, 8, 4, 2, 1: v[l] = v[l] + v[l + off] for every l < off. The value is v[0].
+ *   The class of a form depends on n only, never on how the launch is shaped.
+ * OBSERVABLES. G >= 0 outputs, each a pair (num[g], den[g]) with num[g] in [0, H). den[g] == -1: y_g = F[num[g]], copied bit for
+ *   bit. den[g] in [0, H): y_g = F[num[g]] / F[den[g]], one IEEE division; x / 0 and 0 / 0 are what IEEE says.
+ * OUTPUT. out[(s L + j) * pitch + c], pitch >= G. Column c < G of a row j < n_s is y_c; every column c >= G is 0.0; every column
+ *   of a row j >= n_s is 0.0 (the stored record's invariant). pitch == G is the compact form, pitch == N a block that every
+ *   [S][L][N] pass accepts.
+ *
+ * The kernel and the host restatement are compiled with floating-point contraction off (#pragma clang fp contract(off), as
+ * resample_kernels.hip and event_kernels.hip are). Every output is a function of its own (s, j, g) with one order of operations:
+ * the same bits from call to call, between kin_observables_host, the host entry and the device entry, and under any tiling. How
+ * it is computed (observable_kernels.hip): one launch, no atomics; a 256-thread workgroup owns a few consecutive rows of the flat
+ * (s, j) axis and stages them into LDS (a row that does not fit LDS - more than 16 384 species - is gathered from global memory
+ * instead: no species limit); a host-built plan, cached in the handle with the forms it was built from, deals short numerators one
+ * per lane and long ones one per wavefront, the forms that serve as denominators first, into a table of 64 per row and phase.
+ * KIN_OBSERVABLES_ROWS (1 .. 16) sets the rows a workgroup keeps and KIN_OBSERVABLES_LDS=0 forces the gather path (read per call;
+ * test knobs: results do not depend on them).
+ *
+ * Statuses: KIN_ERR_INVALID_ARG for a negative size, a null buffer where data is due (form_ptr with H > 0, form_idx / form_w with
+ * entries, num / den with G > 0, states with S L N > 0, the output with S L pitch > 0), a form_ptr that does not start at 0 or
+ * decreases, a species outside the network, num outside [0, H), den outside [-1, H), pitch < G, and from the host entries a seg_n
+ * outside [0, L]; KIN_ERR_UNSUPPORTED from the entries that launch the kernel for S L >= 2^31 or N, pitch, H, G or nnz >= 2^30;
+ * KIN_ERR_STATE from kin_solution_observables / kin_ensemble_observables / kin_ensemble_observable_count without a stored solution
+ * / ensemble. S L = 0 or pitch = 0 writes nothing. A refused call leaves the handle as it was. Added under KIN_ABI_VERSION 6: look
+ * the symbols up before calling them. */
+/* The definition above in plain loops on host arrays: no handle, no device. The normative restatement. */
+int kin_observables_host(int64_t N, int index_base, int64_t S, int64_t L, const int64_t* seg_n, const double* u /* [S][L][N] */, int64_t H,
+                         const int64_t* form_ptr, const int64_t* form_idx, const double* form_w, int64_t G, const int64_t* num,
+                         const int64_t* den, int64_t pitch, double* out /* [S][L][pitch] */);
+/* States and output on the device; the forms and observables are host arrays, read before the call returns. Only enqueues
+ * (d_seg_n: S int64 on the device, or NULL); one stream per handle at a time. */
+int kin_observables_segmented_dev(kin_network* h, int64_t S, int64_t L, const int64_t* d_seg_n, const double* d_u /* [S][L][N] */, int64_t H,
+                                  const int64_t* form_ptr, const int64_t* form_idx, const double* form_w, int64_t G, const int64_t* num,
+                                  const int64_t* den, int64_t pitch, double* d_out /* [S][L][pitch] */, void* stream);
+int kin_observables_segmented(kin_network* h, int64_t S, int64_t L, const int64_t* seg_n, const double* u, int64_t H,
+                              const int64_t* form_ptr, const int64_t* form_idx, const double* form_w, int64_t G, const int64_t* num,
+                              const int64_t* den, int64_t pitch, double* out);
+/* The same over the stored states of the last kin_solve (S = 1, L = n_saved). out[n_saved][pitch]. */
+int kin_solution_observables(kin_network* h, int64_t H, const int64_t* form_ptr, const int64_t* form_idx, const double* form_w, int64_t G,
+                             const int64_t* num, const int64_t* den, int64_t pitch, double* out);
+/* The same over the stored ensemble (S = K, L = n_rows, seg_n = n_saved), read where it lives. out[K][n_rows][pitch] may be NULL
+ * when store != 0. With store != 0 THE RESULT BECOMES THE STORED ENSEMBLE, as with kin_ensemble_resample: it needs pitch == N
+ * (hence G <= N) and G >= 1, else KIN_ERR_INVALID_ARG; K, n_rows and n_saved are unchanged, the block goes to the one of the two
+ * handle buffers of the resampling pass the record is not in, the per-member Ea / A stay attached, and the record is marked as a
+ * record of observables (kin_ensemble_observable_count). The passes that treat columns as columns take such a record unchanged -
+ * kin_ensemble_size / _max / _dot / _moments / _quantiles / _correlate / _sobol / _events / _resample (with store it keeps the mark)
+ * and kin_ensemble_observables itself, whose species then number the observables; the passes that need species and reactions -
+ * kin_ensemble_flux / _drg / _drgep / _pfa / _reaction_importance / _timescale - return KIN_ERR_STATE with a message that says
+ * so. There is no way back to the states: the next kin_solve_ensemble* call replaces the record as always. */
+int kin_ensemble_observables(kin_network* h, int64_t H, const int64_t* form_ptr, const int64_t* form_idx, const double* form_w, int64_t G,
+                             const int64_t* num, const int64_t* den, int64_t pitch, int store, double* out);
+/* G of a stored record of observables, 0 for a record of states. */
+int kin_ensemble_observable_count(const kin_network* h, int64_t* G);
+
 /* ---- device / build information ------------------------------------------------------- */
 int kin_device_count(int* n);
 /* Selects the device for handles created afterwards by this thread; a handle remembers the device it was created on
@@ -1155,7 +1225,9 @@ const char* kin_version(void);
  * _correlate, and the Sobol indices: kin_members_sobol, kin_members_sobol_dev, kin_ensemble_sobol, and the
  * per-member Arrhenius parameters: kin_solve_ensemble_continuous_params, kin_solve_ensemble_discrete_params, and the event
  * times: kin_events_segmented, kin_events_segmented_dev, kin_ensemble_events, kin_solution_events, and the resampling:
- * kin_resample_bracket_host, kin_resample_segmented, kin_resample_segmented_dev, kin_solution_resample, kin_ensemble_resample). */
+ * kin_resample_bracket_host, kin_resample_segmented, kin_resample_segmented_dev, kin_solution_resample, kin_ensemble_resample, and the observables:
+ * kin_observables_host, kin_observables_segmented, kin_observables_segmented_dev, kin_solution_observables,
+ * kin_ensemble_observables, kin_ensemble_observable_count). */
 #define KIN_ABI_VERSION 6
 int kin_abi_version(void);
 int64_t kin_struct_size(int which); /* 0: sizeof(kin_params), 1: sizeof(kin_stats), else -1 */

@@ -47,6 +47,8 @@ SYMBOLS = [
     "kin_members_sobol", "kin_members_sobol_dev", "kin_ensemble_sobol",
     "kin_events_segmented", "kin_events_segmented_dev", "kin_ensemble_events", "kin_solution_events",
     "kin_resample_bracket_host", "kin_resample_segmented", "kin_resample_segmented_dev", "kin_solution_resample", "kin_ensemble_resample",
+    "kin_observables_host", "kin_observables_segmented", "kin_observables_segmented_dev", "kin_solution_observables",
+    "kin_ensemble_observables", "kin_ensemble_observable_count",
     "kin_flux_plan_host", "kin_network_compute_units",
     "kin_sweep_plan", "kin_sweep_plan_host", "kin_tiled_sweep_plan", "kin_tiled_sweep_plan_host",
 ]
@@ -112,6 +114,7 @@ _MEMBERS = [P64, PD, PD, P64, POINTER(c_int32), POINTER(KinStats)]      # n_rows
 _KSRC = [PD, c_int64, P64, PD]      # the rate constants of a pass on host arrays: k, n_k_rows, k_row, T
 _EVENT = [c_int, c_int, c_int, c_int64, c_double]      # what an event-time pass looks for: level_kind, direction, start, row_begin, never
 _RESAMPLE = [c_int, c_double, c_int64]      # what a resampling pass does besides its axes: mode, fill, row_begin
+_OBSERVABLES = [c_int64, P64, P64, PD, c_int64, P64, P64, c_int64]      # H, form_ptr, form_idx, form_w, G, num, den, pitch
 ARGTYPES = {
     "kin_struct_size": [c_int], "kin_last_error": [PV],
     "kin_network_create": _NET + [POINTER(PV)], "kin_network_destroy": [PV], "kin_network_sizes": [PV, P64, P64],
@@ -209,6 +212,12 @@ ARGTYPES = {
     "kin_resample_segmented_dev": [PV, c_int64, c_int64, PV, PV, PV, c_int, c_int64, PV, c_int] + _RESAMPLE + [PV] * 4,
     "kin_solution_resample": [PV, PD, c_int64, PD] + _RESAMPLE + [PD],
     "kin_ensemble_resample": [PV, PD, c_int, c_int64, PD, c_int] + _RESAMPLE + [c_int, PD],
+    # observables
+    "kin_observables_host": [c_int64, c_int, c_int64, c_int64, P64, PD] + _OBSERVABLES + [PD],
+    "kin_observables_segmented": [PV, c_int64, c_int64, P64, PD] + _OBSERVABLES + [PD],
+    "kin_observables_segmented_dev": [PV, c_int64, c_int64, PV, PV] + _OBSERVABLES + [PV, PV],
+    "kin_solution_observables": [PV] + _OBSERVABLES + [PD], "kin_ensemble_observables": [PV] + _OBSERVABLES + [c_int, PD],
+    "kin_ensemble_observable_count": [PV, P64],
 }
 
 _lib = None
@@ -350,6 +359,45 @@ def resample_brackets(x, xq, seg_n=None, row_begin=0):
     if st != KIN_OK:
         raise KineticaHipError(st, "kin_resample_bracket_host: invalid argument (sizes, seg_n, or an axis that decreases or holds a NaN)")
     return jc, w
+
+
+def _observable_args(form_ptr, form_idx, form_w, num, den, pitch):
+    """The C arguments H, form_ptr, form_idx, form_w, G, num, den, pitch of an observables entry and (G, pitch) as integers
+    (pitch None: G, the compact form). The arrays go to the library as they are given - it checks them; only their lengths
+    are compared here. A pointer made by data_as keeps its array alive."""
+    ptr = np.ascontiguousarray(form_ptr, dtype=np.int64).ravel()
+    idx = np.ascontiguousarray(form_idx, dtype=np.int64).ravel()
+    w = _f64(form_w).ravel()
+    num = np.ascontiguousarray(num, dtype=np.int64).ravel()
+    den = np.ascontiguousarray(den, dtype=np.int64).ravel()
+    if len(idx) != len(w):
+        raise ValueError(f"form_idx and form_w must have one entry per term; got {len(idx)} and {len(w)}")
+    if len(num) != len(den):
+        raise ValueError(f"num and den must have one entry per observable; got {len(num)} and {len(den)}")
+    if len(ptr) and int(ptr[-1]) > len(idx):
+        raise ValueError(f"form_ptr ends at {int(ptr[-1])} but the forms have {len(idx)} entries")
+    H, G = max(len(ptr) - 1, 0), len(num)
+    pitch = G if pitch is None else int(pitch)
+    return [H, _p64(ptr) if len(ptr) else None, _p64(idx) if len(idx) else None, _pd(w) if len(w) else None, G,
+            _p64(num) if G else None, _p64(den) if G else None, pitch], G, pitch
+
+
+def observables_host(u, form_ptr, form_idx, form_w, num, den, pitch=None, seg_n=None, index_base=0):
+    """kin_observables_host (no handle, no device): the observables pass in plain loops, the normative restatement. u[S][L][N]
+    (S segments of up to L rows, seg_n[S] of them real; None: L each); the forms in CSR over the species (form_idx in
+    index_base); observable g is form num[g], divided by form den[g] unless that is -1. Returns out[S][L][pitch] (pitch None:
+    G): the observables in the columns below G, zeros in the others and in every row past a segment's end."""
+    u = np.ascontiguousarray(_f64(u))
+    if u.ndim != 3:
+        raise ValueError(f"u must be [S][L][N]; got {u.shape}")
+    S, L, N = u.shape
+    seg_n = _seg_n(seg_n, S)
+    args, G, pitch = _observable_args(form_ptr, form_idx, form_w, num, den, pitch)
+    out = np.full((S, L, max(pitch, 0)), np.nan)
+    st = lib().kin_observables_host(N, int(index_base), S, L, _p64(seg_n), _pd(u) if u.size else None, *args, _pd(out) if out.size else None)
+    if st != KIN_OK:
+        raise KineticaHipError(st, "kin_observables_host: invalid argument (sizes, seg_n, form_ptr, a species, num, den or pitch)")
+    return out
 
 
 def members_inputs(X, use=None, rank=True):
@@ -1374,6 +1422,50 @@ class HipNetwork:
         self._chk(lib().kin_ensemble_resample(self._h, _pd(x), x_per, Q, _pd(xq), q_per, *self._resample_opts(mode, fill, row_begin),
                                               int(bool(store)), _pd(out)))
         return out
+
+    # --- observables: weighted species sums and ratios of stored states ---------------------------------------
+    def observables_segmented(self, u, form_ptr, form_idx, form_w, num, den, pitch=None, seg_n=None):
+        """kin_observables_segmented on host arrays: u[S][L][N] (seg_n[S] rows of each segment real; None: L each), the forms in
+        CSR over the species (form_idx in the handle's index base), observable g form num[g] divided by form den[g] unless that
+        is -1. Returns out[S][L][pitch] (pitch None: G), bit for bit what observables_host gives."""
+        u, S, L = self._ms_block(u, self.n)
+        seg_n = _seg_n(seg_n, S)
+        args, G, pitch = _observable_args(form_ptr, form_idx, form_w, num, den, pitch)
+        out = np.empty((S, L, max(pitch, 0)))
+        self._chk(lib().kin_observables_segmented(self._h, S, L, _p64(seg_n), _pd(u), *args, _pd(out) if out.size else None))
+        return out
+
+    def observables_segmented_dev(self, S, L, d_u, form_ptr, form_idx, form_w, num, den, pitch, d_out, d_seg_n=0, stream=0):
+        """kin_observables_segmented_dev: device pointers (ints; 0 = not given) u[S][L][N], seg_n[S] (int64), out[S][L][pitch];
+        the forms and observables are host arrays, read before the call returns. Only enqueues; one stream per handle at a time."""
+        args, _, _ = _observable_args(form_ptr, form_idx, form_w, num, den, pitch)
+        self._chk(lib().kin_observables_segmented_dev(self._h, int(S), int(L), _dp(d_seg_n), _dp(d_u), *args, _dp(d_out), _dp(stream)))
+
+    def solution_observables(self, form_ptr, form_idx, form_w, num, den, pitch=None):
+        """kin_solution_observables: the saved states of the last solve, read where they live. Returns out[n_saved][pitch]."""
+        args, G, pitch = _observable_args(form_ptr, form_idx, form_w, num, den, pitch)
+        out = np.empty((self._solution()[0], max(pitch, 0)))
+        self._chk(lib().kin_solution_observables(self._h, *args, _pd(out) if out.size else None))
+        return out
+
+    def ensemble_observables(self, form_ptr, form_idx, form_w, num, den, pitch=None, store=False, download=True):
+        """kin_ensemble_observables: the stored ensemble, every member's own saved rows read where they live. Returns
+        out[K][n_rows][pitch], or None with download=False (which needs store). store (pitch None: N; it must be N, and
+        1 <= G <= N): the result becomes the stored ensemble - the observables in the columns below G, zeros in the others - and
+        every ensemble_* method that treats columns as columns reads it from then on; ensemble_observable_count gives G."""
+        if not download and not store:
+            raise ValueError("download=False needs store=True: the result would go nowhere")
+        K, L = self.ensemble_size()[:2]
+        args, G, pitch = _observable_args(form_ptr, form_idx, form_w, num, den, self.n if store and pitch is None else pitch)
+        out = np.empty((K, L, max(pitch, 0))) if download else None
+        self._chk(lib().kin_ensemble_observables(self._h, *args, int(bool(store)), _pd(out) if download and out.size else None))
+        return out
+
+    def ensemble_observable_count(self):
+        """kin_ensemble_observable_count: G of a stored record of observables, 0 for a record of states."""
+        G = c_int64(0)
+        self._chk(lib().kin_ensemble_observable_count(self._h, ctypes.byref(G)))
+        return G.value
 
     # --- library order (tiled sweep) --------------------------------------------------------
     def lib_layout(self):

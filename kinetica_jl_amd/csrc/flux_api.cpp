@@ -108,6 +108,7 @@ StateBatch solution_batch(kin_network* h, PassCheck check, const double* k, int6
 StateBatch ensemble_batch(kin_network* h, PassCheck check, const double* k, int64_t n_k_rows, const int64_t* k_row,
                           const double* T_rows, bool have_out, hipStream_t s) {
   require(h->ens.valid(), ERR_STATE, "no ensemble stored (kin_solve_ensemble* first)");
+  require(h->ens.observables == 0, ERR_STATE, OBSERVABLES_RECORD_MSG);
   const int64_t K = h->ens.K, cap = h->ens.cap, B = K * cap;
   require(cap < ((int64_t)1 << 31) && K < ((int64_t)1 << 31) && B < ((int64_t)1 << 31), ERR_UNSUPPORTED,
           "ensemble DRG pass: K n_rows beyond 32-bit offsets");
@@ -349,6 +350,7 @@ int kin_ensemble_flux(kin_network* h, const double* w, const double* k, int64_t 
   KIN_TRY(h)
   require(flux != nullptr, ERR_INVALID_ARG, "null output buffer");
   require_ensemble(h);
+  require(h->ens.observables == 0, ERR_STATE, OBSERVABLES_RECORD_MSG);
   const int64_t K = h->ens.K, cap = h->ens.cap, B = K * cap, R = h->host.R;
   flux_seg_check(h, K, cap, k != nullptr, k_row != nullptr, T_rows != nullptr, true);
   if (k && k_row) { require(n_k_rows >= 1, ERR_INVALID_ARG, "k has no rows"); check_seg_rows(k_row, K, cap, h->ens.n_saved.data(), n_k_rows); }

@@ -47,6 +47,11 @@ StateBatch solution_batch(kin_network* h, PassCheck check, const double* k, int6
                           const double* T_rows, bool have_out, hipStream_t s);
 StateBatch ensemble_batch(kin_network* h, PassCheck check, const double* k, int64_t n_k_rows, const int64_t* k_row,
                           const double* T_rows, bool have_out, hipStream_t s);
+// what ensemble_batch and kin_ensemble_flux answer, with KIN_ERR_STATE, on a record of observables (kin_ensemble_observables
+// with store): the passes that need species and reactions have none to work on
+constexpr const char* OBSERVABLES_RECORD_MSG =
+    "the stored ensemble is a record of observables (kin_ensemble_observables with store): its columns are no species, and this "
+    "pass needs species and reactions; solve the ensemble again";
 // the keys alone into f_k, f_krow, f_T (host_batch and solution_batch; the segmented entries of the flux pass)
 FluxSource stage_source(kin_network* h, int64_t B, const double* k, int64_t n_k_rows, const int64_t* k_row, const double* T, hipStream_t s);
 

@@ -8,6 +8,7 @@
 #include "drg.hpp"
 #include "kernels.hpp"
 #include "network.hpp"
+#include "observable_kernels.hpp"
 #include "pfa.hpp"
 #include "tiled.hpp"
 
@@ -166,9 +167,12 @@ struct kin_network {
     // solved with per-member Arrhenius parameters (kin_solve_ensemble_*_params): Ea[K][R], A[K][R] on the device (ens_Ea / ens_A,
     // which only the next per-member call overwrites); null for a record of shared parameters
     const double *Ea = nullptr, *A = nullptr;
+    // a record of observables (kin_ensemble_observables with store): its G, the columns that mean something - the others of
+    // the N are zeros and no column is a species any more; 0 for a record of states
+    int64_t observables = 0;
     bool valid() const { return sol != nullptr && K > 0; }
     bool member_params() const { return Ea != nullptr; }
-    void clear() { sol = nullptr; K = 0; cap = 0; n_saved.clear(); Ea = nullptr; A = nullptr; }
+    void clear() { sol = nullptr; K = 0; cap = 0; n_saved.clear(); Ea = nullptr; A = nullptr; observables = 0; }
   } ens;
   kin::DevBuf<double> ens_sol, ens_w, ens_out;   // handle-owned copy of the saved states; workspaces of kin_ensemble_max / _dot
   kin::DevBuf<double> ens_Ea, ens_A;             // the per-member parameter blocks of a kin_solve_ensemble_*_params call, reused across calls
@@ -177,6 +181,16 @@ struct kin_network {
   // result goes to the one the record is not in), and the host entries' staging of jc[S][Q] and w[S][Q]
   kin::DevBuf<double> ens_rs[2], rs_w;
   kin::DevBuf<int32_t> rs_jc;
+  // observables (observable_api.cpp): the forms and observables of the last call as the caller gave them - a call that brings the
+  // same ones finds its plan on the device - and the plan, on the host and uploaded
+  std::vector<int64_t> ob_h_ptr, ob_h_idx, ob_h_num, ob_h_den;
+  std::vector<double> ob_h_w;
+  kin::ObsPlanHost ob_plan;
+  bool ob_ready = false;
+  kin::DevBuf<int32_t> ob_idx;
+  kin::DevBuf<double> ob_w;
+  kin::DevBuf<kin::ObsTask> ob_tasks;
+  kin::DevBuf<kin::ObsPhase> ob_phases;
   void set_ensemble_record(const double* sol, int64_t K, int64_t cap, std::vector<int64_t> n_saved) {
     ens.sol = sol; ens.K = K; ens.cap = cap; ens.n_saved = std::move(n_saved);
   }

@@ -13,6 +13,7 @@ import copy
 import dataclasses
 import math
 from dataclasses import dataclass, field
+from collections.abc import Mapping
 from typing import Callable, Dict, List, Optional, Sequence, Union
 
 import numpy as np
@@ -468,6 +469,7 @@ class ODESolution:
     ensemble_stats: Optional[object] = None   # the ensemble's one EnsembleStatistics (solve_network_ensemble(statistics=...)), else None
     events: Optional[object] = None      # the ensemble's one EventTimes (solve_network_ensemble(events=...)), else None
     resampled: Optional[object] = None   # the ensemble's one ResampledEnsemble (solve_network_ensemble(resample=...)), else None
+    observables: Optional[object] = None   # the ensemble's one Observables (solve_network_ensemble(observables=...)), else None
 
     def __call__(self, tq):
         """Linear interpolation res.sol(t) (docs/src/getting-started.md:232-236)."""
@@ -742,7 +744,7 @@ def apply_ensemble_low_k_cutoff(rd, calc, pars, condition_sets, calculators=None
 
 
 def solve_network_ensemble(methods, sd, rd, copy_network=True, fluxes=False, trajectories=True, statistics=None,
-                           member_calculators=False, events=None, resample=None):
+                           member_calculators=False, events=None, resample=None, observables=None):
     """EXTENSION (the reference has no ensemble call: it solves member after member through solve_network): K
     `VariableODESolve`s with Arrhenius condition sets - one temperature profile each, e.g. a set of heating rates or start
     temperatures - on one network in ONE ensemble call: kin_solve_ensemble_continuous when every set is continuous,
@@ -803,7 +805,17 @@ def solve_network_ensemble(methods, sd, rd, copy_network=True, fluxes=False, tra
     cooling programme is a ValueError - negate the axis and the queries. Every member's sol.resampled refers to ONE shared
     ResampledEnsemble (its u the resampled block when trajectories=True, else None). A malformed dict raises ValueError
     before anything touches the GPU (an axis array's row count is compared with the save grid once that is known). None (the
-    default): the function as it was."""
+    default): the function as it was.
+
+    observables=an ObservableSpec or the mapping `observables()` takes (species by name or 0-based id of the network as it is
+    solved) turns the stored ensemble into observables - mole fractions, lumped classes, ratios - before the statistics and the
+    event times look at it. The order inside the call: the solve; whatever refers to the solve's own rows (the trajectory
+    download, sol.umax, fluxes=True); resample= with store, if given; then ensemble_observables(store=True) - observable g takes
+    column g of the record, the columns from G on are zeros; then statistics= and events= over that record, whose `species` now
+    number the observables (ids below G; None: all G of them, and mean / var / min / max have G columns). A vector `level` of
+    events still has one entry per column of the record, N of them, the first G for the observables. Every member's sol.observables refers to ONE shared Observables (its values
+    [K][n_rows][G] when trajectories=True, else None). A malformed argument - an unknown species, more observables than species -
+    raises ValueError before anything touches the GPU. None (the default): the function as it was."""
     methods = list(methods)
     if not methods:
         raise ValueError("solve_network_ensemble needs at least one method")
@@ -812,6 +824,8 @@ def solve_network_ensemble(methods, sd, rd, copy_network=True, fluxes=False, tra
     rs_kw = None if resample is None else _resample_arguments(resample, len(methods))
     if rs_kw is not None and ev_kw is not None and not np.all(np.diff(rs_kw["at"], axis=-1) > 0):
         raise ValueError("resample: events over the resampled record need queries `at` that increase strictly")
+    if observables is not None and not isinstance(observables, (ObservableSpec, Mapping)):
+        raise ValueError("observables must be None, an ObservableSpec or the mapping observables() takes")
     m0 = methods[0]
     for m in methods:
         if not isinstance(m, VariableODESolve) or not isinstance(m.calculator, PrecalculatedArrheniusCalculator):
@@ -856,14 +870,19 @@ def solve_network_ensemble(methods, sd, rd, copy_network=True, fluxes=False, tra
             m.calculator.splice(rids)
             spliced.append(m.calculator)
     U0 = np.array([make_u0(sd_a, m.pars) for m in methods])
-    if stat_kw is not None and stat_kw["species"] is not None and stat_kw["species"].max(initial=-1) >= sd_a.n:
-        raise ValueError(f"statistics: species ids must be below the {sd_a.n} species of the network as it is solved")
+    ob_spec = None if observables is None else _observable_spec(sd_a, observables, store=True)
+    # the columns the statistics and the event times can select: the species, or the observables that take their place
+    n_cols, cols = (sd_a.n, f"{sd_a.n} species of the network as it is solved") if ob_spec is None else (ob_spec.G, f"{ob_spec.G} observables")
+    stat_kw, ev_kw = _select_observables(stat_kw, ob_spec), _select_observables(ev_kw, ob_spec)
+    if stat_kw is not None and stat_kw["species"] is not None and stat_kw["species"].max(initial=-1) >= n_cols:
+        raise ValueError(f"statistics: species ids must be below the {cols}")
     sob_kw = None if stat_kw is None else stat_kw.get("sobol")
-    if sob_kw is not None and sob_kw["species"] is not None and sob_kw["species"].max(initial=-1) >= sd_a.n:
-        raise ValueError(f"statistics: sobol species ids must be below the {sd_a.n} species of the network as it is solved")
+    sob_kw = _select_observables(sob_kw, ob_spec)
+    if sob_kw is not None and sob_kw["species"] is not None and sob_kw["species"].max(initial=-1) >= n_cols:
+        raise ValueError(f"statistics: sobol species ids must be below the {cols}")
     if ev_kw is not None:
-        if ev_kw["species"] is not None and ev_kw["species"].max(initial=-1) >= sd_a.n:
-            raise ValueError(f"events: species ids must be below the {sd_a.n} species of the network as it is solved")
+        if ev_kw["species"] is not None and ev_kw["species"].max(initial=-1) >= n_cols:
+            raise ValueError(f"events: species ids must be below the {cols}")
         if np.ndim(ev_kw["level"]) == 1 and len(ev_kw["level"]) != sd_a.n:
             raise ValueError(f"events: level must be a number or one per species of the network as it is solved ({sd_a.n})")
     if discrete:
@@ -908,6 +927,9 @@ def solve_network_ensemble(methods, sd, rd, copy_network=True, fluxes=False, tra
                                    store=True, download=trajectories)
             rs.axis = rs_kw["axis"]
             t_stat = rs_kw["at"]
+        ob = None
+        if ob_spec is not None:      # from here on the columns of the stored ensemble are the observables
+            ob = ensemble_observables(h, ob_spec, store=True, download=trajectories)
         stats = None
         if stat_kw is not None:
             sp0 = stat_kw["species"]
@@ -916,6 +938,9 @@ def solve_network_ensemble(methods, sd, rd, copy_network=True, fluxes=False, tra
                 sob_kw = dict(sob_kw, species=None if sb0 is None else sb0 + 1)
             stats = ensemble_statistics(h, t_stat, **dict(stat_kw, species=None if sp0 is None else sp0 + 1, sobol=sob_kw))   # (the handle's base is 1)
             stats.species = sp0
+            if ob_spec is not None:      # (the moments have no selection of their own: their first G columns are the observables)
+                for name in ("mean", "var", "min", "max"):
+                    setattr(stats, name, np.ascontiguousarray(getattr(stats, name)[:, :ob_spec.G]))
             if sob_kw is not None:
                 stats.sobol.species = sb0
         ev = None
@@ -949,6 +974,7 @@ def solve_network_ensemble(methods, sd, rd, copy_network=True, fluxes=False, tra
             sol.ensemble_stats = stats
         sol.events = ev
         sol.resampled = rs
+        sol.observables = ob
         out.append(ODESolveOutput(sd_a, rd_a, sol, sol_k, sol_vcs, m.pars, m.conditions))
     return out
 
@@ -1617,6 +1643,171 @@ def resample_solution(out_or_handle, at, axis=None, mode="fill", fill=float("nan
     jc, _ = capi.resample_brackets(x, kw["at"], row_begin=rb)
     covered, n_cov = _covered(jc[0], kw["mode"])
     return ResampledEnsemble(axis, kw["at"], u, jc[0], covered, int(n_cov[0]), x=x, mode=kw["mode"], fill=kw["fill"], t_min=kw["t_min"])
+
+
+# ---- observables: weighted species sums and ratios of stored states (EXTENSION) ---------------------------------------------
+@dataclass
+class ObservableSpec:
+    """What observables() and mole_fractions() build: the names of the G observables, the H linear forms over the N species in
+    CSR (form_ptr[H + 1], form_idx 0-based, form_w) and per observable the form num[g] and the form den[g] it is divided by, -1
+    for none (include/kinetica_hip.h has the definitions)."""
+    names: tuple
+    N: int
+    form_ptr: np.ndarray
+    form_idx: np.ndarray
+    form_w: np.ndarray
+    num: np.ndarray
+    den: np.ndarray
+
+    @property
+    def G(self):
+        return len(self.num)
+
+    @property
+    def H(self):
+        return len(self.form_ptr) - 1
+
+    def arrays(self, index_base=0):
+        """(form_ptr, form_idx, form_w, num, den) as the capi entries take them, the species in `index_base`."""
+        return self.form_ptr, self.form_idx + int(index_base), self.form_w, self.num, self.den
+
+
+@dataclass
+class Observables:
+    """Result of ensemble_observables / solution_observables: names[G]; values[K][n_rows][G] ([n_saved][G] for one solve), None
+    when not downloaded; G; spec, the ObservableSpec they were computed from."""
+    names: tuple
+    values: Optional[np.ndarray]
+    G: int
+    spec: Optional[ObservableSpec] = None
+
+
+def _observable_species(sd, N, x):
+    """The 0-based id of a species given by name (with a SpeciesData) or by 0-based id; ValueError for anything else."""
+    if isinstance(x, str):
+        if sd is None or x not in sd.toInt:
+            raise ValueError(f"observables: unknown species {x!r}")
+        return sd.toInt[x] - 1
+    if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, np.integer)) or not 0 <= int(x) < N:
+        raise ValueError(f"observables: species must be names or 0-based ids below {N}; got {x!r}")
+    return int(x)
+
+
+def observables(sd_or_N, spec, store=False):
+    """An ObservableSpec from a mapping name -> what the observable is: a species (name or 0-based id), a list of species (their
+    sum, weights 1), a {species: weight} mapping (a weighted sum; a species may not repeat, a list may repeat one), or
+    ("ratio", name_a, name_b), the quotient of two other entries of the mapping that are sums themselves. sd_or_N: the
+    SpeciesData that resolves names, or the number of species (ids only). Every entry that is no ratio becomes one linear
+    form, in the mapping's order; observable g is the mapping's g-th entry. store=True also asks for G <= N, what a stored
+    record of observables needs. ValueError - nothing here touches the device - for an unknown species, an unknown or ratio
+    name inside a ratio, an empty mapping or entry type, or G > N with store."""
+    sd = sd_or_N if isinstance(sd_or_N, SpeciesData) else None
+    if sd is None and (isinstance(sd_or_N, (bool, np.bool_)) or not isinstance(sd_or_N, (int, np.integer)) or sd_or_N < 1):
+        raise ValueError("observables: the first argument must be a SpeciesData or the number of species")
+    N = sd.n if sd is not None else int(sd_or_N)
+    if not isinstance(spec, Mapping) or len(spec) == 0:
+        raise ValueError("observables: the spec must be a non-empty mapping name -> species, list, {species: weight} or ('ratio', a, b)")
+    ptr, idx, w, form_of = [0], [], [], {}
+    for name, what in spec.items():
+        if isinstance(what, tuple) and len(what) == 3 and what[0] == "ratio":
+            continue
+        if isinstance(what, Mapping):
+            terms = [(_observable_species(sd, N, k), v) for k, v in what.items()]
+        elif isinstance(what, (list, tuple, np.ndarray)):
+            terms = [(_observable_species(sd, N, k), 1.0) for k in what]
+        else:
+            terms = [(_observable_species(sd, N, what), 1.0)]
+        for i, v in terms:
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
+                raise ValueError(f"observables: the weights of {name!r} must be numbers")
+            idx.append(i); w.append(float(v))
+        form_of[name] = len(ptr) - 1
+        ptr.append(len(idx))
+    num, den = [], []
+    for name, what in spec.items():
+        if name in form_of:
+            num.append(form_of[name]); den.append(-1)
+            continue
+        for operand in what[1:]:
+            if operand not in form_of:
+                raise ValueError(f"observables: the ratio {name!r} names {operand!r}, which is no sum of the spec")
+        num.append(form_of[what[1]]); den.append(form_of[what[2]])
+    if store and len(num) > N:
+        raise ValueError(f"observables: a stored record holds at most as many observables as species ({N}); got {len(num)}")
+    return ObservableSpec(tuple(spec), N, np.array(ptr, np.int64), np.array(idx, np.int64), np.array(w, float), np.array(num, np.int64),
+                          np.array(den, np.int64))
+
+
+def mole_fractions(sd_or_N, species=None):
+    """The ObservableSpec of the mole fractions u_i / sum_k u_k of `species` (names or 0-based ids; None: all N): N singleton
+    forms and the total over all species, H = N + 1; observable g is the g-th selected species over the total."""
+    sd = sd_or_N if isinstance(sd_or_N, SpeciesData) else None
+    if sd is None and (isinstance(sd_or_N, (bool, np.bool_)) or not isinstance(sd_or_N, (int, np.integer)) or sd_or_N < 1):
+        raise ValueError("observables: the first argument must be a SpeciesData or the number of species")
+    N = sd.n if sd is not None else int(sd_or_N)
+    sel = list(range(N)) if species is None else [_observable_species(sd, N, x) for x in species]
+    if not sel:
+        raise ValueError("observables: mole fractions of no species")
+    names = tuple(f"x[{sd.toStr[i + 1]}]" if sd is not None else f"x[{i}]" for i in sel)
+    ptr = np.concatenate([np.arange(N + 1), [2 * N]]).astype(np.int64)
+    idx = np.concatenate([np.arange(N), np.arange(N)]).astype(np.int64)
+    return ObservableSpec(names, N, ptr, idx, np.ones(2 * N), np.array(sel, np.int64), np.full(len(sel), N, np.int64))
+
+
+def _select_observables(kw, spec):
+    """The keyword dict of a pass over a record of the observables `spec` (statistics, Sobol, events; None: no such pass, or no
+    observables): without a selection of its own it selects the G observables, not the N - G zero columns behind them."""
+    if kw is None or spec is None or kw["species"] is not None:
+        return kw
+    return dict(kw, species=np.arange(spec.G, dtype=np.int64))
+
+
+def _observable_spec(sd_or_N, spec, store=False):
+    """spec as an ObservableSpec for a network of sd_or_N species: one is checked against the network, a mapping built."""
+    if isinstance(spec, ObservableSpec):
+        N = sd_or_N.n if isinstance(sd_or_N, SpeciesData) else int(sd_or_N)
+        if spec.N != N:
+            raise ValueError(f"observables: the spec was built for {spec.N} species, the network has {N}")
+        if store and spec.G > N:
+            raise ValueError(f"observables: a stored record holds at most as many observables as species ({N}); got {spec.G}")
+        return spec
+    return observables(sd_or_N, spec, store=store)
+
+
+def ensemble_observables(h, spec, store=False, download=True):
+    """The observables `spec` (an ObservableSpec, or observables()' mapping with 0-based ids) of the ensemble stored in the handle
+    `h` (a capi.HipNetwork after a solve_ensemble* call), computed where the states live (kin_ensemble_observables). store=True:
+    the result becomes the stored ensemble - observable g in column g, zeros from column G on - so that ensemble_statistics,
+    sobol_indices, event_times and resample_ensemble run on the observables; the passes that need species and reactions refuse
+    such a record. Returns an Observables; values[K][n_rows][G], None with download=False (which needs store)."""
+    spec = _observable_spec(h.n, spec, store=store)
+    if not download and not store:
+        raise ValueError("observables: download=False needs store=True: the result would go nowhere")
+    v = h.ensemble_observables(*spec.arrays(h.index_base), pitch=h.n if store else spec.G, store=store, download=download)
+    return Observables(spec.names, None if v is None else np.ascontiguousarray(v[:, :, :spec.G]), spec.G, spec)
+
+
+def solution_observables(out_or_handle, spec):
+    """ensemble_observables for one solve: an ODESolveOutput - its saved states are handed to a handle of out.rd as the other
+    analysis passes hand them over, species by name or 0-based id - or a capi.HipNetwork after a solve (kin_solution_observables,
+    the states read where they live). Returns an Observables with values[n_saved][G]."""
+    if isinstance(out_or_handle, ODESolveOutput):
+        out = out_or_handle
+        spec = _observable_spec(out.sd, spec)
+        if out.sol.u is None:
+            raise ValueError("observables: the solve output holds no saved states (it was solved with trajectories=False)")
+        n = out.sd.n
+        u = np.ascontiguousarray(np.asarray(out.sol.u, dtype=float).reshape(1, -1, n))
+        h = capi.HipNetwork(*out.rd.flat(n), index_base=1)
+        try:
+            v = h.observables_segmented(u, *spec.arrays(1))[0]
+        finally:
+            h.close()
+    else:
+        h = out_or_handle
+        spec = _observable_spec(h.n, spec)
+        v = h.solution_observables(*spec.arrays(h.index_base))
+    return Observables(spec.names, v, spec.G, spec)
 
 
 # ---- post-hoc reaction-flux analysis (EXTENSION, in the style of the reference's analysis/: works on an ODESolveOutput) ----

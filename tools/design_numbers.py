@@ -243,6 +243,27 @@ def build():
     rk = b.get("ranks", {})
     add("multi-GPU", "ranks that took part in the committed bench line", f"world size {rk.get('world_size')}, backend {rk.get('backend')}; no scaling curve measured", f"{src_b} `ranks`")
 
+    # the observables pass (tools/observables_bench.py): per shape and spec the launch and the host entries next to their yardsticks
+    shape = spec = None
+    times = {}
+    for line in open(os.path.join(P, "observables_ab.txt")):
+        m = re.match(r"(\w+)\s+N=(\d+) R=\d+ K=(\d+) rows=(\d+)", line)
+        if m:
+            shape = f"{int(m.group(2))} species, K = {m.group(3)} x {m.group(4)} rows"
+        m = re.match(r" (\w+): H=(\d+) G=(\d+)", line)
+        if m:
+            spec, times = {"forms8": "eight full-length forms", "molefrac": "mole fractions"}[m.group(1)], {}
+        m = re.match(r"  (\w+)\s+([\d.]+) ms \[", line)
+        if m:
+            times[m.group(1)] = float(m.group(2))
+        if line.startswith("  dev / max"):
+            v_ = f"launch {times['dev']:.3f} ms, `kin_ensemble_max` {times['max']:.3f} ms: {times['dev'] / times['max']:.2f}"
+            if "dot8" in times:
+                v_ += (f"; compact host entry {times['compact']:.3f} ms, eight `kin_ensemble_dot` calls {times['dot8']:.3f} ms: "
+                       f"**{times['compact'] / times['dot8']:.2f}**")
+            v_ += f"; store {times['store']:.3f} ms; download + NumPy {times['numpy']:.1f} ms"
+            add("observables", f"{shape}, {spec}", v_, "observables_ab.txt")
+
     out = ["| | what | value | source (`profiles/`) |", "|---|---|---|---|"]
     last = None
     for g, w, v_, s in rows:
